@@ -274,7 +274,50 @@ def run_step(w, world_size: int = 1, handle=None, prefetch: bool = False):
     if prefetch:
         nxt = est.prefetch_traversal(w["rays_o"], w["rays_d"], render_step_size=w["step"], wait_for_inputs=False)
     w["last"] = (ri, ts, te, colors)                        # kept for the parity check that follows the timed loops
+    w["last_opac_depth"] = (opac, depth)                    # with w["last"]: what --dump-outputs writes
     return ri.numel(), loss, nxt
+
+
+DUMP_MAX_ROWS = 1 << 20      # --dump-outputs: arrays with more rows are written as a fixed, seeded sample of this many rows
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _sample_rows(n: int, seed: int) -> np.ndarray | None:
+    """Sorted row indices of a fixed, seeded sample of DUMP_MAX_ROWS of n rows; None when all n rows are kept."""
+    if n <= DUMP_MAX_ROWS:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(n, DUMP_MAX_ROWS, replace=False))
+
+
+def dump_outputs(w, loss, out_dir: str) -> dict:
+    """Write what the timed step computed in its last iteration -- the samples of OccGridEstimator.sampling, the per-ray
+    colours / opacities / depths of rendering, the loss and the parameter gradient of its backward -- as <name>.npy
+    (float32 / float64, integers as float64) under out_dir.  Per-ray and per-sample arrays longer than DUMP_MAX_ROWS are
+    written as a seeded sample of rows (the same rows for the same ray count / sample count).  Returns {name: shape}."""
+    ri, ts, te, colors = w["last"]
+    opac, depth = w["last_opac_depth"]
+    n, m = int(colors.shape[0]), int(ri.numel())
+    rays, samples = _sample_rows(n, 1), _sample_rows(m, 2)
+    pick = lambda t, rows: t if rows is None else t[torch.from_numpy(rows).to(t.device)]
+    arrays = {
+        "colors": pick(colors, rays).float(),
+        "opacities": pick(opac, rays).float(),
+        "depths": pick(depth, rays).float(),
+        "samples_per_ray": pick(torch.bincount(ri.long(), minlength=n), rays).double(),
+        "ray_indices": pick(ri, samples).double(),
+        "t_starts": pick(ts, samples).float(),
+        "t_ends": pick(te, samples).float(),
+        "n_samples": torch.tensor([m], dtype=torch.float64),
+        "loss": loss.detach().double().reshape(1),
+        "param_grad": w["params"].grad.detach().double(),
+    }
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 # ----------------------------------------------------------------------------- distributed glue
@@ -962,7 +1005,13 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the secondary configurations (cfg2 variants, cfg3, cfg5)")
     ap.add_argument("--only", default="", choices=["", "cfg2_compacting", "cfg2_random", "cfg2_testmode", "cfg4_per_rank", "cfg3", "cfg5", "cfg5_testmode"],
                     help="run ONE secondary configuration alone and print its object (for rocprofv3 passes: profiles/<round>_<cfg>_*)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0; see dump_outputs), for comparing builds")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.only:
+        ap.error("--dump-outputs writes the headline step's outputs; it does not combine with --only")
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a ROCm GPU (the product path has no CPU fallback)")
@@ -1014,11 +1063,15 @@ def main():
     t0 = time.perf_counter()
     m_last = 0
     for _ in range(args.steps):
-        m_last, _, _ = run_step(w, world)
+        m_last, loss_last, _ = run_step(w, world)
     sync()
     dt = time.perf_counter() - t0
     gc.enable()
     dt = max_over_ranks(dt, world, dev)
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before the loops below overwrite w["last"]
+        dumped = dump_outputs(w, loss_last, args.dump_outputs)
+    del loss_last
 
     # Per-kernel HIP-event times: a separate loop of the same K steps (two event records per native call would otherwise
     # sit inside `value`).
@@ -1078,6 +1131,8 @@ def main():
                        "samples_after_compaction": int(m_last), "parallelism": f"ray-sharded x{world}",
                        "field": f"synthetic analytic field, {args.field} callbacks (see bench.py NativeField/TorchField)"},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if pipe_error is not None:
             out["pipelined_error"] = pipe_error
         if dt_pipe is not None:
@@ -1195,6 +1250,7 @@ def main():
                                       grad_after_allreduce=g, grad_finite=bool(all(math.isfinite(x) for x in g)))
         if not args.no_extras and world == 1:
             w.pop("last", None)
+            w.pop("last_opac_depth", None)
             for key, fn in (("cfg2_compacting", lambda: extra_cfg2_variant(dev, args, sigma_scale=16.0)),
                             ("cfg2_random", lambda: extra_cfg2_variant(dev, args, rays="random")),
                             ("cfg2_testmode", lambda: extra_cfg2_testmode(dev, args)),
