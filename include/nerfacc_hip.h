@@ -40,7 +40,7 @@ typedef void *nfa_stream_t; /* hipStream_t */
 const char *nfa_last_error(void);
 /* The version of THIS header.  Bumped whenever an entry point changes its arguments or what it expects of them; a caller
  * built against another value must not call the library (nerfacc_amd/_backend.py refuses to load it). */
-#define NFA_VERSION 401
+#define NFA_VERSION 402
 int nfa_version(void);          /* NFA_VERSION of the header the library was built from */
 /* Knobs of the A/B tests and measurement scripts (which of two equivalent kernels a call takes, tile sizes); value NULL
  * or "" unsets.  Names: NFA_REFILL, NFA_REFILL_ALL, NFA_CONE_STAGED, NFA_SEG_TILE, NFA_WALK_NO_LATTICE.  Results never
@@ -506,6 +506,24 @@ int nfa_pdf_loss_sum_fwd(const float *q_vals, const float *q_cdfs, const float *
 int nfa_pdf_loss_mean_bwd(const float *q_cdfs, const float *k_cdfs, const uint32_t *key_ids, int64_t n_rays,
                           int32_t n_query_edges, int32_t n_key_edges, float eps, const float *g_mean, float *g_k_cdfs,
                           float *g_q_cdfs, nfa_stream_t stream);
+
+/* ------------------------------------------------------------------ cameras */
+
+/* OpenCV lens undistortion of n_points interleaved (u, v) pairs, uv / uv_out [n_points, 2] (8-byte aligned, not
+ * aliased).  params: one set of n_params floats shared by every point (param_stride 0) or one set per point
+ * (param_stride == n_params).  n_params 5 {k1,k2,p1,p2,k3} and 8 {k1,k2,p1,p2,k3,k4,k5,k6}: at most `iters` Newton
+ * steps, stopping when |det J| < eps or both |dx|, |dy| < eps; 12 {k1..k6,p1,p2,s1..s4}: exactly `iters` thin-prism
+ * fixed-point steps (eps unused), a point whose inverse radial factor turns negative is copied unchanged.
+ * ref: cuda/csrc/camera.cu:37-107,114-147 (declared at nerfacc.cpp:88-92). */
+int nfa_opencv_lens_undistortion(const float *uv, const float *params, int64_t n_points, int32_t n_params,
+                                 int64_t param_stride, float eps, int32_t iters, float *uv_out, nfa_stream_t stream);
+/* Fisheye undistortion, n_params 4 {k1,k2,k3,k4}: at most `iters` Newton steps on theta, stopping when |step| < eps.
+ * A point that does not converge or whose theta flips sign, and a point with |uv| <= eps, is copied unchanged (the
+ * reference leaves the former unwritten and writes 0 for the latter).
+ * ref: cuda/csrc/camera.cu:9-35,149-183 (declared at nerfacc.cpp:93-97). */
+int nfa_opencv_lens_undistortion_fisheye(const float *uv, const float *params, int64_t n_points, int32_t n_params,
+                                         int64_t param_stride, float eps, int32_t iters, float *uv_out,
+                                         nfa_stream_t stream);
 
 #ifdef __cplusplus
 }

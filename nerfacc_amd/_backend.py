@@ -104,6 +104,8 @@ _SIGS = {
     "nfa_importance_sampling_t": [_vp, _vp, _vp, _i64, _i64, _i64, _int, _u64, _u64, _vp, _vp, _int, _f32, _f32, _vp, _vp, _vp],
     "nfa_importance_sampling_packed": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _int, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nfa_searchsorted": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp],
+    "nfa_opencv_lens_undistortion": [_vp, _vp, _i64, _i32, _i64, _f32, _i32, _vp, _vp],
+    "nfa_opencv_lens_undistortion_fisheye": [_vp, _vp, _i64, _i32, _i64, _f32, _i32, _vp, _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],
@@ -146,7 +148,7 @@ def load() -> C.CDLL:
     return _lib
 
 
-ABI_VERSION = 401   # include/nerfacc_hip.h: NFA_VERSION
+ABI_VERSION = 402   # include/nerfacc_hip.h: NFA_VERSION
 
 
 def set_tuning(name: str, value: Optional[str]) -> None:

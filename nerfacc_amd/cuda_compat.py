@@ -20,6 +20,7 @@ import torch
 from torch import Tensor
 
 from . import _backend as B
+from . import cameras as _cameras
 from . import grid as _grid
 from . import pdf as _pdf
 from .data_specs import RayIntervals
@@ -175,9 +176,27 @@ def searchsorted(query: RaySegmentsSpec, key: RaySegmentsSpec) -> List[Tensor]:
     return list(_pdf.searchsorted(_intervals_from_spec(key), _intervals_from_spec(query)))
 
 
-def opencv_lens_undistortion(*args, **kwargs):
-    raise NotImplementedError("camera undistortion is outside the hot path this package accelerates (SURVEY.md 8)")
+def _lens(name: str, uv: Tensor, params: Tensor, counts, eps: float, iters: int) -> Tensor:
+    # camera.cu:120-125 / 155-160: CHECK_INPUT, equal ranks, [..., 2] points, and (ours) params already broadcast
+    _check(uv, "uv")
+    _check(params, "params")
+    if uv.dim() != params.dim():
+        raise RuntimeError("uv and params must have the same number of dimensions")
+    if uv.size(-1) != 2:
+        raise RuntimeError("uv must have shape [..., 2]")
+    if params.size(-1) not in counts:
+        raise RuntimeError(f"params must have shape [..., N] with N in {counts}, got {tuple(params.shape)}")
+    if params.shape[:-1] != uv.shape[:-1]:
+        raise RuntimeError(f"params {tuple(params.shape)} must be broadcast to the points {tuple(uv.shape)}")
+    return _cameras._launch(name, uv, params, eps, iters)
 
 
-def opencv_lens_undistortion_fisheye(*args, **kwargs):
-    raise NotImplementedError("camera undistortion is outside the hot path this package accelerates (SURVEY.md 8)")
+def opencv_lens_undistortion(uv: Tensor, params: Tensor, eps: float, max_iterations: int) -> Tensor:
+    """ref: camera.cu:114-147.  params [..., 5] {k1,k2,p1,p2,k3}, [..., 8] {k1,k2,p1,p2,k3,k4,k5,k6} (Newton) or
+    [..., 12] {k1..k6,p1,p2,s1..s4} (thin-prism fixed point)."""
+    return _lens("nfa_opencv_lens_undistortion", uv, params, (5, 8, 12), eps, max_iterations)
+
+
+def opencv_lens_undistortion_fisheye(uv: Tensor, params: Tensor, criteria_eps: float, criteria_iters: int) -> Tensor:
+    """ref: camera.cu:149-183.  params [..., 4] {k1,k2,k3,k4}."""
+    return _lens("nfa_opencv_lens_undistortion_fisheye", uv, params, (4,), criteria_eps, criteria_iters)
