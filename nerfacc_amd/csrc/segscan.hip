@@ -28,56 +28,24 @@
 // with the lane/element order mirrored (DIR = -1).
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.hip.h"
 
 namespace nfa {
 
-#ifndef NFA_SEG_OCC_HINTS
-#define NFA_SEG_OCC_HINTS 0  /* A/B on one box: 5-6 waves instead of 4-5 for the fused passes is within run-to-run noise */
-#endif
-#ifndef NFA_SEG_E
-#define NFA_SEG_E 4
-#endif
-// Elements per lane and step (4 or 8, consecutive).  The cross-lane part of a step (head resolution, 6 DPP steps per scan
-// channel, the window of packed_info rows) costs the same for 4 or 8 elements per lane, so 8 halves it per element; the
-// registers it costs lower the occupancy.  Measured on cfg 2 (fused fwd / bwd / visibility, us, one box): 4 -> 292 / 344 /
-// 139, 8 -> 405 / 518 / 168 (156 / 171 / 101 VGPRs: 3 / 2 / 5 waves per SIMD) -- occupancy is worth more than instructions.
-constexpr int SE = NFA_SEG_E;
-static_assert(SE == 4 || SE == 8, "NFA_SEG_E must be 4 or 8");
-constexpr int SQ = SE / 4;              // 16-byte quads per lane
+// Elements per lane and step: 4 consecutive ones, one 16-byte quad per lane and array.  (8 halves the cross-lane part of
+// a step per element -- head resolution, 6 DPP steps per scan channel, the window of packed_info rows -- but its registers
+// lower the occupancy and it was measured slower: DESIGN.md, "What the profiles showed -- round 2" (2).)
+constexpr int SE = 4;
+constexpr int SQ = SE / 4;              // 16-byte quads per lane (see Pos)
 constexpr int SEG_CHUNK = 64 * SE;      // elements per wave step
-// non-temporal loads per op (A/B switches): visibility -7 %, fused forward -2 %, but the backward pass that re-reads the
-// same arrays later loses as much (+9 us): the step does not move, so they stay off
-#ifndef NFA_NT_VIS
-#define NFA_NT_VIS false
-#endif
-#ifndef NFA_NT_FWD
-#define NFA_NT_FWD false
-#endif
-#ifndef NFA_SEG_PIPE
-#define NFA_SEG_PIPE 0
-#endif
-#ifndef NFA_SEG_ANCHOR
-#define NFA_SEG_ANCHOR 0
-#endif
 #ifndef NFA_SEG_TILE_ROWS
 #define NFA_SEG_TILE_ROWS 256
 #endif
 constexpr int64_t SEG_TILE_ROWS = NFA_SEG_TILE_ROWS;
-#ifndef NFA_SEG_WINDOW_PREFETCH
-#define NFA_SEG_WINDOW_PREFETCH 0   /* measured: neutral on cfg 2 (the row-heavy tiles are dispatched first instead), compaction 10 % slower on cfg 5 */
-#endif
-#ifndef NFA_SEG_EARLY_FETCH
-#define NFA_SEG_EARLY_FETCH 0   /* measured: neutral on cfg 2, compaction 10 % slower on cfg 5 */
-#endif
-#ifndef NFA_BWD_PIPE
-#define NFA_BWD_PIPE 1
-#endif
 #ifndef NFA_VIS_EXP_FREE
 #define NFA_VIS_EXP_FREE 1
-#endif
-#ifndef NFA_VIS_PIPE
-#define NFA_VIS_PIPE 0
 #endif
 #ifndef NFA_SEG_WAVES_PER_BLOCK
 #define NFA_SEG_WAVES_PER_BLOCK 4
@@ -140,10 +108,10 @@ __host__ __device__ inline int64_t seg_table_rows(int64_t n_tiles) { return n_ti
 // 16-byte vector helpers (addresses are 16 B aligned when VEC is true)
 // Loads are UNCONDITIONAL and RAW: a lane without valid elements reads the step's base address `ps`
 // (always inside the array), and the validity selects are applied where the values are consumed
-// (sel4).  A load inside an `if`, or a select right behind it, makes the compiler wait for that one
+// (sel).  A load inside an `if`, or a select right behind it, makes the compiler wait for that one
 // load on the spot, which serialises the 3-7 array loads of a step (one memory latency each) and
 // defeats the one-step-ahead prefetch.
-struct F4 { float v[SE]; };  // one lane's elements of a step (the name predates SE)
+struct F4 { float v[SE]; };  // one lane's elements of a step
 
 // Where a lane stands in the current step.  `c` (step base, multiple of 256) and `safe` are wave-uniform
 // and live in scalar registers; only `off` is per lane, so element addresses are scalar base + 32-bit
@@ -155,19 +123,20 @@ struct Pos {
     bool valid[SE]; // element c + off + j belongs to the tile's element range
     bool any, all;  // over the lane's SE elements
     int32_t d_lo, d_hi;  // the step's valid element offsets [d_lo, d_hi) from c (wave-uniform)
-    bool qany[SQ], qall[SQ];  // per 16-byte quad
+    // Per 16-byte quad.  With SE = 4 there is one quad per lane and qany / qall equal any / all, but folding the quad
+    // loops away changes the register allocation of most kernels (same instructions, different order), so they stay.
+    bool qany[SQ], qall[SQ];
     __device__ __forceinline__ int64_t p0() const { return c + off; }
 };
 
-template <bool VEC, bool NT = false>
+template <bool VEC>
 __device__ __forceinline__ void ld4(const float *__restrict__ p, const Pos &q, F4 &out)
 {
     const float *b = p + q.c;
     if (VEC) {
 #pragma unroll
         for (int h = 0; h < SQ; ++h) {
-            const nfa_v4f *src = reinterpret_cast<const nfa_v4f *>(b + (q.qany[h] ? q.off + 4 * h : q.safe));
-            const nfa_v4f v = NT ? __builtin_nontemporal_load(src) : *src;
+            const nfa_v4f v = *reinterpret_cast<const nfa_v4f *>(b + (q.qany[h] ? q.off + 4 * h : q.safe));
             out.v[4 * h] = v.x; out.v[4 * h + 1] = v.y; out.v[4 * h + 2] = v.z; out.v[4 * h + 3] = v.w;
         }
     } else {
@@ -183,11 +152,6 @@ __device__ __forceinline__ float sel(const F4 &r, int j, const bool valid[SE], f
 // s_waitcnt vmcnt(0) after EACH of them: sixteen serial round trips to memory in the first and last step of every tile
 // of the fused backward, 22 us of its 344.)
 #define NFA_ELEMENTWISE_PATH() asm volatile("; element-wise path" ::: "memory")
-#if defined(NFA_VOLATILE_ELEMENTWISE) && NFA_VOLATILE_ELEMENTWISE   /* the old form, for A/B runs */
-#define NFA_PV volatile
-#else
-#define NFA_PV
-#endif
 template <bool VEC>
 __device__ __forceinline__ void store4(float *__restrict__ p, const Pos &q, const float v[SE])
 {
@@ -198,10 +162,9 @@ __device__ __forceinline__ void store4(float *__restrict__ p, const Pos &q, cons
             store_f4(b + q.off + 4 * h, v[4 * h], v[4 * h + 1], v[4 * h + 2], v[4 * h + 3]);
         } else {
             NFA_ELEMENTWISE_PATH();
-            NFA_PV float *pv = b;
 #pragma unroll
             for (int j = 4 * h; j < 4 * h + 4; ++j)
-                if (q.valid[j]) pv[q.off + j] = v[j];
+                if (q.valid[j]) b[q.off + j] = v[j];
         }
     }
 }
@@ -410,13 +373,17 @@ __device__ __forceinline__ int64_t uniform64(int64_t v)
 }
 
 // ------------------------------------------------------------------------------------------
-// The engine.  Op interface (all __device__):
+// The engine.  Op interface (all __device__; OpBase below holds the defaults of the constants and of identity / comb /
+// ray_done / empty_ray):
 //   static constexpr int NCH;                       scan channels of stage A
 //   static constexpr int NCHB;                      channels of the optional stage B (additive; 0 = none):
 //                                                   per-ray totals of values derived from stage A's results
 //   static constexpr bool NEEDS_RID;                op.pre(j, pos, valid, rid) is called before stage A's
 //                                                   inputs are read (the ray id is known before any value scan)
 //   static constexpr bool TOTALS;                   op.ray_done(rid, total[NCH]) for EVERY finished ray
+//   static constexpr int MIN_WAVES_PER_EU;          occupancy floor for the register allocator (1 = none)
+//   static constexpr int RAY_LDS_FLOATS;            > 0: op.tile_begin(r_lo, r_hi, lds) stages per-ray data
+//   static constexpr bool PIPE;                     fetch the next step's inputs one step ahead (see seg_run_tile)
 //   float identity(int ch); float comb(int ch, float a, float b);   a = earlier in scan order
 //   struct Raw;                                      registers filled straight from memory
 //   void  fetch(const Pos &q, Raw &r) const;         loads only (unconditional, raw)
@@ -431,7 +398,7 @@ __device__ __forceinline__ int64_t uniform64(int64_t v)
 //   void  empty_ray(int rid);
 // Everything that is the same for the whole wave (tile bounds, step base, loop control) is kept in
 // scalar registers (the tile index is made uniform with readfirstlane).
-template <int DIR, int PIPE /* 0: none, 1: next step's loads before this step's compute, 2: before this step's stores */, class Op>
+template <int DIR, class Op>
 __device__ __forceinline__ void seg_run_tile(Op &op, const int64_t *__restrict__ packed_info,
                                              const longlong2 *__restrict__ tiles, int64_t n_rays, int64_t tile,
                                              int32_t *__restrict__ hid /* LDS, SEG_CHUNK ints, wave private */,
@@ -449,26 +416,18 @@ __device__ __forceinline__ void seg_run_tile(Op &op, const int64_t *__restrict__
     const int64_t e_lo = uniform64(t_lo.y), e_hi = uniform64(t_hi.y);  // chunks are contiguous: the last owned ray ends where the next tile begins
 
     // window of packed_info rows, in walk order v = 0..n_own-1: ray(v) = r_lo + v (fwd) / r_hi-1-v (rev)
+    // Each window of 64 rows is a load the wave waits for when its walk reaches it; a tile owns at most SEG_TILE_ROWS rows,
+    // i.e. a few windows.  (A tile of short and empty rays used to own hundreds of rows: the bench's 30 % empty rays then
+    // cost the fused passes 8 %, at 256^3 20 %.  Requesting the following window as soon as the current one was in place
+    // measured neutral on cfg 2 once the row-heavy tiles were dispatched first, and 10 % slower for compaction on cfg 5.)
     int32_t v_next = 0, win_base = 0;
-    // The window FOLLOWING the current one is requested as soon as the current one is in place (nxt_*): a tile in a region
-    // of short and empty rays owns hundreds of rows, and every window used to be a dependent load the wave waited for
-    // (the bench's 30 % empty rays cost the fused passes 8 %, at 256^3 -- the same number of rays, interleaved with short
-    // ones instead of lying in long runs -- 20 %).
-    int64_t win_s = 0, win_n = 0, nxt_s = 0, nxt_n = 0;
-    int32_t nxt_base = -1;   // window base the prefetched rows belong to (-1: none)
-    auto fetch_rows = [&](int32_t base, int64_t &rs, int64_t &rn) {
-        const int32_t v = base + lane;
+    longlong2 win = make_longlong2(0, 0);   // the lane's row of the window: {start, count}
+    auto load_window = [&]() {
+        const int32_t v = win_base + lane;
         if (v < n_own) {
             const int64_t ray = DIR > 0 ? (int64_t)r_lo + v : (int64_t)r_hi - 1 - v;
-            const longlong2 row = *reinterpret_cast<const longlong2 *>(packed_info + 2 * ray);
-            rs = row.x; rn = row.y;
+            win = *reinterpret_cast<const longlong2 *>(packed_info + 2 * ray);
         }
-    };
-    auto load_window = [&]() {
-        if (NFA_SEG_WINDOW_PREFETCH && nxt_base == win_base) { win_s = nxt_s; win_n = nxt_n; }
-        else fetch_rows(win_base, win_s, win_n);
-        nxt_base = -1;
-        if (NFA_SEG_WINDOW_PREFETCH && win_base + 64 < n_own) { nxt_base = win_base + 64; fetch_rows(nxt_base, nxt_s, nxt_n); }
     };
     load_window();
 
@@ -481,21 +440,12 @@ __device__ __forceinline__ void seg_run_tile(Op &op, const int64_t *__restrict__
     for (int ch = 0; ch < NCB; ++ch) carry_b[ch] = 0.0f;
     int32_t carry_rid = -1;
 
-    // Where the steps are anchored.  NFA_SEG_ANCHOR = 0: at multiples of the step size (a range of ~1000 elements at an
-    // arbitrary offset then touches FIVE 256-element chunks); n > 0 (a multiple of 4, which keeps every 16-byte access
-    // aligned; 32 = one 128-byte line of floats): at the tile's own range rounded to n elements -- four steps for a range of
-    // <= 1024 - n elements.  Measured (cfg 2): 32 makes the visibility pass 4 % faster (102 vs 106 us) and leaves the fused
-    // passes where they are, 4 makes the fused passes 5 % slower (every wave access then straddles one more 128-byte line);
-    // with anchored steps a ray is cut into steps relative to its TILE, so results would depend on the tiling again: off.
-#if NFA_SEG_ANCHOR == 0
+    // Steps are anchored at multiples of the step size, so a ray is cut into the same steps whatever the tiling (a range
+    // of ~1000 elements at an arbitrary offset then touches five 256-element chunks).  (Anchoring them at the tile's own
+    // range rounded to 32 elements made visibility 4 % faster on cfg 2 and the fused passes no faster, but results would
+    // depend on the tiling; rounded to 4, the fused passes were 5 % slower.)
     const int64_t c_first = DIR > 0 ? (e_lo / SEG_CHUNK) * SEG_CHUNK : ((e_hi - 1) / SEG_CHUNK) * SEG_CHUNK;
     const int64_t n_chunks = e_hi > e_lo ? ((e_hi - 1) / SEG_CHUNK - e_lo / SEG_CHUNK + 1) : 0;
-#else
-    constexpr int64_t AG = NFA_SEG_ANCHOR;
-    const int64_t a_lo = (e_lo / AG) * AG, a_hi = ((e_hi + AG - 1) / AG) * AG;
-    const int64_t c_first = DIR > 0 ? a_lo : a_hi - SEG_CHUNK;
-    const int64_t n_chunks = e_hi > e_lo ? (DIR > 0 ? (e_hi - a_lo + SEG_CHUNK - 1) / SEG_CHUNK : (a_hi - e_lo + SEG_CHUNK - 1) / SEG_CHUNK) : 0;
-#endif
 
     auto chunk_base = [&](int64_t ci) { return c_first + (DIR > 0 ? ci : -ci) * SEG_CHUNK; };
     auto make_pos = [&](int64_t c, Pos &q) {
@@ -517,7 +467,9 @@ __device__ __forceinline__ void seg_run_tile(Op &op, const int64_t *__restrict__
             q.qall[h] = (q.off + 4 * h >= d_lo) && (q.off + 4 * h + 3 < d_hi);
         }
     };
-    // Software pipeline (PIPE): the loads of step i+1 are issued before step i is computed and stored
+    // When a step's inputs are requested (Op::PIPE).  false: in the step itself, after its segment heads have gone through
+    // LDS, just before op.load (the first step's before the loop; requesting them before the heads was neutral on cfg 2
+    // and made compaction 10 % slower on cfg 5).  true: one step ahead, before the previous step is computed and stored
     // (vmcnt retires in order: loads issued BEFORE the stores can be waited for without them).
     typename Op::Raw raw_cur, raw_next;
     if (n_chunks > 0) {
@@ -527,17 +479,10 @@ __device__ __forceinline__ void seg_run_tile(Op &op, const int64_t *__restrict__
     }
     for (int64_t ci = 0; ci < n_chunks; ++ci) {
         const int64_t c = chunk_base(ci);
-        if (PIPE == 1 && ci + 1 < n_chunks) {
+        if (Op::PIPE && ci + 1 < n_chunks) {
             Pos qn;
             make_pos(chunk_base(ci + 1), qn);
             op.fetch(qn, raw_next);
-        }
-        if (PIPE == 0 && ci > 0 && NFA_SEG_EARLY_FETCH) {
-            // this step's inputs are requested BEFORE its segment heads are resolved (the window of packed_info rows, the
-            // LDS scatter and its read-back: ~150 instructions and two LDS round trips that need none of the data)
-            Pos qf;
-            make_pos(c, qf);
-            op.fetch(qf, raw_cur);
         }
         // ---- segment heads of this chunk -> LDS
 #pragma unroll
@@ -546,11 +491,11 @@ __device__ __forceinline__ void seg_run_tile(Op &op, const int64_t *__restrict__
         for (;;) {
             const int32_t v = win_base + lane;
             const bool live = v >= v_next && v < n_own;
-            const int64_t key = DIR > 0 ? win_s : win_s + win_n - 1;
+            const int64_t key = DIR > 0 ? win.x : win.x + win.y - 1;
             const bool take = live && (DIR > 0 ? key < c + SEG_CHUNK : key >= c);
             const int32_t ray = DIR > 0 ? r_lo + v : r_hi - 1 - v;
             if (take) {
-                if (win_n > 0) hid[(int)(key - c)] = ray;
+                if (win.y > 0) hid[(int)(key - c)] = ray;
                 else op.empty_ray(ray);
             }
             const int cnt = __builtin_popcountll(__ballot(take));
@@ -577,7 +522,7 @@ __device__ __forceinline__ void seg_run_tile(Op &op, const int64_t *__restrict__
         // ---- this step's data
         Pos q;
         make_pos(c, q);
-        if (PIPE == 0 && ci > 0 && !NFA_SEG_EARLY_FETCH) op.fetch(q, raw_cur);   // (the old place, for A/B runs)
+        if (!Op::PIPE && ci > 0) op.fetch(q, raw_cur);
         op.load(raw_cur, q);
 
         // ---- segment structure of this step: ray id of every element (scan order k, address j = DIR>0 ? k : 3-k)
@@ -614,13 +559,6 @@ __device__ __forceinline__ void seg_run_tile(Op &op, const int64_t *__restrict__
         // ---- stage B (optional): per-ray totals of values derived from stage A's results.  The per-element
         //      outputs are complete after stage A: they are stored first (their registers are free for stage B
         //      and the stores are in flight while it runs).
-        if (PIPE == 2 && ci + 1 < n_chunks) {
-            // the results are in registers, most temporaries are dead: request the next step's inputs BEFORE the stores
-            // (vmcnt retires in order, so the next step can wait for its loads without waiting for these stores)
-            Pos qn;
-            make_pos(chunk_base(ci + 1), qn);
-            op.fetch(qn, raw_next);
-        }
         op.store(q);
         if constexpr (Op::NCHB > 0) {
             scan_totals<NCB>(hd,
@@ -628,13 +566,13 @@ __device__ __forceinline__ void seg_run_tile(Op &op, const int64_t *__restrict__
                              carry_b, [&](int32_t rid, int ch, float t) { op.ray_done_b(rid, ch, t); });
         }
         carry_rid = lane_value(hd.rid[SE - 1], hd.carry_lane);
-        if (PIPE) raw_cur = raw_next;
+        if (Op::PIPE) raw_cur = raw_next;
     }
     // remaining owned rays are all empty (their start equals e_hi / e_lo)
     for (;;) {
         const int32_t v = win_base + lane;
         const bool live = v >= v_next && v < n_own;
-        if (live && win_n <= 0) op.empty_ray(DIR > 0 ? r_lo + v : r_hi - 1 - v);
+        if (live && win.y <= 0) op.empty_ray(DIR > 0 ? r_lo + v : r_hi - 1 - v);
         v_next = min(win_base + 64, n_own);
         if (v_next < n_own) { win_base = v_next; load_window(); continue; }
         break;
@@ -648,7 +586,7 @@ __device__ __forceinline__ void seg_run_tile(Op &op, const int64_t *__restrict__
     }
 }
 
-template <int DIR, int PIPE, class Op>
+template <int DIR, class Op>
 __global__ __launch_bounds__(64 * SEG_WAVES_PER_BLOCK, Op::MIN_WAVES_PER_EU) void seg_kernel(Op op, const int64_t *__restrict__ packed_info,
                                                                        const longlong2 *__restrict__ tiles,
                                                                        int64_t n_rays, int64_t n_tiles)
@@ -659,7 +597,7 @@ __global__ __launch_bounds__(64 * SEG_WAVES_PER_BLOCK, Op::MIN_WAVES_PER_EU) voi
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t tile = (int64_t)blockIdx.x * SEG_WAVES_PER_BLOCK + wave;
     if (tile >= n_tiles) return;
-    seg_run_tile<DIR, PIPE>(op, packed_info, tiles, n_rays, tile, hid_all + wave * SEG_CHUNK, ray_all + wave * RL);
+    seg_run_tile<DIR>(op, packed_info, tiles, n_rays, tile, hid_all + wave * SEG_CHUNK, ray_all + wave * RL);
 }
 
 template <int DIR, class Op>
@@ -668,25 +606,23 @@ static void launch_seg(const Op &op, const int64_t *packed_info, const int64_t *
 {
     const longlong2 *tiles = reinterpret_cast<const longlong2 *>(tiles_raw);
     const unsigned grid = (unsigned)ceil_div64(n_tiles, SEG_WAVES_PER_BLOCK);
-    // NFA_SEG_PIPE (compile time): 0 = a step's loads are requested when the step starts; 1 = one step ahead, before the
-    // previous step's compute (its registers cost occupancy: slower on every op); 2 = one step ahead, between the previous
-    // step's compute and its stores.
-    hipLaunchKernelGGL((seg_kernel<DIR, Op::PIPE, Op>), dim3(grid), dim3(64 * SEG_WAVES_PER_BLOCK), 0, s, op, packed_info, tiles,
+    hipLaunchKernelGGL((seg_kernel<DIR, Op>), dim3(grid), dim3(64 * SEG_WAVES_PER_BLOCK), 0, s, op, packed_info, tiles,
                        n_rays, n_tiles);
 }
 
 // ------------------------------------------------------------------------------------------
-// Ops.  `Raw` holds what one step loads (fetched one step ahead by the engine); the per-step
-// working registers are members (fully unrolled, register resident).
+// Ops.  `Raw` holds what one step loads (op.fetch, issued by the engine in the step itself or, with PIPE, one step
+// ahead); the per-step working registers are members (fully unrolled, register resident).  Every op takes its defaults
+// from OpBase and restates only what differs.
 
-struct OpBase1 {  // one additive channel
+struct OpBase {  // one additive channel
     static constexpr int NCH = 1;
     static constexpr int NCHB = 0;
     static constexpr bool NEEDS_RID = false;
     static constexpr bool TOTALS = false;
     static constexpr int MIN_WAVES_PER_EU = 1;  // occupancy floor asked of the register allocator (1 = none)
     static constexpr int RAY_LDS_FLOATS = 0;    // per-wave LDS floats for per-ray data staged at tile start (tile_begin)
-    static constexpr int PIPE = NFA_SEG_PIPE;   // when the next step's loads are requested (seg_run_tile)
+    static constexpr bool PIPE = false;         // the next step's loads are requested one step ahead (seg_run_tile)
     __device__ __forceinline__ float identity(int) const { return 0.0f; }
     __device__ __forceinline__ float comb(int, float a, float b) const { return a + b; }
     __device__ __forceinline__ void ray_done(int, const float *) const {}
@@ -695,14 +631,7 @@ struct OpBase1 {  // one additive channel
 
 // ---- plain scans: scan.cu:9-165 (sum), :127-165 / :217-257 (prod)
 template <bool EXCL, bool PROD, bool VEC>
-struct ScanOp {
-    static constexpr int NCH = 1;
-    static constexpr int NCHB = 0;
-    static constexpr bool NEEDS_RID = false;
-    static constexpr bool TOTALS = false;
-    static constexpr int MIN_WAVES_PER_EU = 1;  // occupancy floor asked of the register allocator (1 = none)
-    static constexpr int RAY_LDS_FLOATS = 0;    // per-wave LDS floats for per-ray data staged at tile start (tile_begin)
-    static constexpr int PIPE = NFA_SEG_PIPE;   // when the next step's loads are requested (seg_run_tile)
+struct ScanOp : OpBase {
     struct Raw { F4 x; };
     const float *in;
     float *out;
@@ -722,14 +651,12 @@ struct ScanOp {
         res[j] = EXCL ? (is_head ? identity(0) : prev[0]) : incl[0];
     }
     __device__ __forceinline__ void store(const Pos &q) { store4<VEC>(out, q, res); }
-    __device__ __forceinline__ void ray_done(int, const float *) const {}
-    __device__ __forceinline__ void empty_ray(int) const {}
 };
 
 // ---- prod backward: reverse {incl,excl} sum of g*out, divided by clamp_min(in, 1e-10)
 //      scan.cu:169-214, :259-304
 template <bool EXCL, bool VEC>
-struct ProdBwdOp : OpBase1 {
+struct ProdBwdOp : OpBase {
     struct Raw { F4 o, g, in; };
     const float *in, *outv, *g;
     float *gin;
@@ -757,7 +684,7 @@ struct ProdBwdOp : OpBase1 {
 
 // ---- transmittance / alpha / weights from density, volrend.py:256-264, :358-362
 template <bool VEC>
-struct DensityFwdOp : OpBase1 {
+struct DensityFwdOp : OpBase {
     struct Raw { F4 a, b, s, pf; };
     const float *ts, *te, *sig, *prefix;
     float *w, *tr, *al;
@@ -798,9 +725,7 @@ struct DensityFwdOp : OpBase1 {
     }
     __device__ __forceinline__ void store(const Pos &q)
     {
-        const bool *valid = q.valid;
-        const int64_t p0 = q.p0();
-        (void)valid; (void)p0;
+        (void)q.p0();   // (no effect, but without it the compiler allocates this op's registers differently)
         if (w) store4<VEC>(w, q, rw);
         if (tr) store4<VEC>(tr, q, rt);
         if (al) store4<VEC>(al, q, ra);
@@ -815,10 +740,9 @@ struct DensityFwdOp : OpBase1 {
                     *reinterpret_cast<Q4 *>(b + q.off + 4 * h + crid[4 * h]) = v;
                 } else {
                     NFA_ELEMENTWISE_PATH();
-            NFA_PV float *pv = b;
 #pragma unroll
                     for (int j = 4 * h; j < 4 * h + 4; ++j)
-                        if (q.valid[j]) pv[q.off + j + crid[j]] = 1.0f - rt[j];
+                        if (q.valid[j]) b[q.off + j + crid[j]] = 1.0f - rt[j];
                 }
             }
         }
@@ -827,14 +751,7 @@ struct DensityFwdOp : OpBase1 {
 
 // ---- transmittance / weights from alpha, volrend.py:200-206, :305-309
 template <bool VEC>
-struct AlphaFwdOp {
-    static constexpr int NCH = 1;
-    static constexpr int NCHB = 0;
-    static constexpr bool NEEDS_RID = false;
-    static constexpr bool TOTALS = false;
-    static constexpr int MIN_WAVES_PER_EU = 1;  // occupancy floor asked of the register allocator (1 = none)
-    static constexpr int RAY_LDS_FLOATS = 0;    // per-wave LDS floats for per-ray data staged at tile start (tile_begin)
-    static constexpr int PIPE = NFA_SEG_PIPE;   // when the next step's loads are requested (seg_run_tile)
+struct AlphaFwdOp : OpBase {
     struct Raw { F4 a, pf; };
     const float *al, *prefix;
     float *w, *tr;
@@ -861,19 +778,14 @@ struct AlphaFwdOp {
     }
     __device__ __forceinline__ void store(const Pos &q)
     {
-        const bool *valid = q.valid;
-        const int64_t p0 = q.p0();
-        (void)valid; (void)p0;
         if (w) store4<VEC>(w, q, rw);
         if (tr) store4<VEC>(tr, q, rt);
     }
-    __device__ __forceinline__ void ray_done(int, const float *) const {}
-    __device__ __forceinline__ void empty_ray(int) const {}
 };
 
 // ---- backward of the fused density op (reverse scan), SURVEY App. A.7
 template <bool VEC, bool CDF = false /* the gradient arrives at the CDF rows of DensityFwdOp::cdf: g_T[p] = -g_cdf[p + ray] */>
-struct DensityBwdOp : OpBase1 {
+struct DensityBwdOp : OpBase {
     static constexpr bool NEEDS_RID = CDF;
     struct Raw { F4 a, b, T, A, gw, gt, ga; };
     const float *ts, *te, *tr, *al, *gw, *gt, *ga;
@@ -938,9 +850,7 @@ struct DensityBwdOp : OpBase1 {
     }
     __device__ __forceinline__ void store(const Pos &q)
     {
-        const bool *valid = q.valid;
-        const int64_t p0 = q.p0();
-        (void)valid; (void)p0;
+        (void)q.p0();   // (no effect, but without it the compiler allocates this op's registers differently)
         if (gsig) store4<VEC>(gsig, q, rs);
         if (gx) store4<VEC>(gx, q, rx);
     }
@@ -948,7 +858,7 @@ struct DensityBwdOp : OpBase1 {
 
 // ---- backward of the fused alpha op: g_a = g_w T - sum_{i>k}(g_w_i w_i + g_T_i T_i) / max(1-a, 1e-10)
 template <bool VEC>
-struct AlphaBwdOp : OpBase1 {
+struct AlphaBwdOp : OpBase {
     struct Raw { F4 T, A, gw, gt; };
     const float *al, *tr, *gw, *gt;
     float *galpha;
@@ -983,14 +893,8 @@ struct AlphaBwdOp : OpBase1 {
 // ---- visibility mask, volrend.py:412-418 / :474-480.  COUNT adds the per-ray number of visible
 //      samples (what the sampler's compaction needs) as a stage-B scan of the mask just computed.
 template <bool DENSITY, bool VEC, bool COUNT>
-struct VisibilityOp {
-    static constexpr int NCH = 1;
+struct VisibilityOp : OpBase {
     static constexpr int NCHB = COUNT ? 1 : 0;
-    static constexpr bool NEEDS_RID = false;
-    static constexpr bool TOTALS = false;
-    static constexpr int MIN_WAVES_PER_EU = 1;  // occupancy floor asked of the register allocator (1 = none)
-    static constexpr int RAY_LDS_FLOATS = 0;    // per-wave LDS floats for per-ray data staged at tile start (tile_begin)
-    static constexpr int PIPE = NFA_VIS_PIPE;   // (measured per op: 0, 1 and 2 are within noise here)
     struct Raw { F4 s, pf, a, b; };
     const float *ts, *te, *val, *prefix;
     float eps, thre;
@@ -1006,11 +910,11 @@ struct VisibilityOp {
     __device__ __forceinline__ float comb(int, float a, float b) const { return DENSITY ? a + b : a * b; }
     __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
     {
-        ld4<VEC, NFA_NT_VIS>(val, q, r.s);
-        if (prefix) ld4<VEC, NFA_NT_VIS>(prefix, q, r.pf);
+        ld4<VEC>(val, q, r.s);
+        if (prefix) ld4<VEC>(prefix, q, r.pf);
         if (DENSITY) {
-            ld4<VEC, NFA_NT_VIS>(ts, q, r.a);
-            ld4<VEC, NFA_NT_VIS>(te, q, r.b);
+            ld4<VEC>(ts, q, r.a);
+            ld4<VEC>(te, q, r.b);
         }
     }
     __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
@@ -1048,9 +952,6 @@ struct VisibilityOp {
     __device__ __forceinline__ void ray_done_b(int rid, int, float tot) const { cnts[rid] = (int64_t)tot; }
     __device__ __forceinline__ void store(const Pos &q)
     {
-        const bool *valid = q.valid;
-        const int64_t p0 = q.p0();
-        (void)valid; (void)p0;
         uint8_t *b = vis + q.c;
 #pragma unroll
         for (int h = 0; h < SQ; ++h) {
@@ -1058,14 +959,12 @@ struct VisibilityOp {
                 *reinterpret_cast<uchar4 *>(b + q.off + 4 * h) = make_uchar4(m[4 * h], m[4 * h + 1], m[4 * h + 2], m[4 * h + 3]);
             } else {
                 NFA_ELEMENTWISE_PATH();
-                NFA_PV uint8_t *pv = b;
 #pragma unroll
                 for (int j = 4 * h; j < 4 * h + 4; ++j)
-                    if (q.valid[j]) pv[q.off + j] = m[j];
+                    if (q.valid[j]) b[q.off + j] = m[j];
             }
         }
     }
-    __device__ __forceinline__ void ray_done(int, const float *) const {}
     __device__ __forceinline__ void empty_ray(int rid) const
     {
         if (COUNT) cnts[rid] = 0;
@@ -1097,7 +996,7 @@ __device__ __forceinline__ float mask_sel(const U4 &m, int j, const bool valid[S
 
 // ---- compaction of the visible samples (per-ray output offsets = cumsum of VisibilityOp's counts)
 template <bool VEC>
-struct CompactOp : OpBase1 {
+struct CompactOp : OpBase {
     // The kept samples of a step go to CONSECUTIVE output positions (out_starts is the running sum of the per-ray counts and
     // a ray's kept samples are numbered by the scan), so the wave packs them in LDS and writes them out as 16-byte vectors,
     // 4 outputs per lane, instead of three predicated 4/8-byte scatters per element.  A caller whose out_starts are not that
@@ -1229,22 +1128,15 @@ struct CompactOp : OpBase1 {
 
 // ---- per-ray accumulation of w * values[:, d0:d0+C], volrend.py:532-547
 template <int C, bool VEC>
-struct AccumOp {
+struct AccumOp : OpBase {
     static constexpr int NCH = C;
-    static constexpr int NCHB = 0;
-    static constexpr bool NEEDS_RID = false;
     static constexpr bool TOTALS = true;
-    static constexpr int MIN_WAVES_PER_EU = 1;
-    static constexpr int RAY_LDS_FLOATS = 0;    // per-wave LDS floats for per-ray data staged at tile start (tile_begin)
-    static constexpr int PIPE = NFA_SEG_PIPE;   // when the next step's loads are requested (seg_run_tile)
     struct Raw { F4 w; float v[SE][C]; };
     const float *w, *vals;  // vals may be null (C == 1): accumulate w
     int32_t D, d0;
     float *out;
     int accumulate;
     float xv[SE][C];
-    __device__ __forceinline__ float identity(int) const { return 0.0f; }
-    __device__ __forceinline__ float comb(int, float a, float b) const { return a + b; }
     __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
     {
         ld4<VEC>(w, q, r.w);
@@ -1284,7 +1176,7 @@ struct AccumOp {
 };
 
 template <int C, bool VEC>
-struct AccumBwdOp : OpBase1 {
+struct AccumBwdOp : OpBase {
     struct Raw { F4 w, g; float v[SE][C]; };
     const float *w, *vals, *gout;
     int32_t D, d0;
@@ -1329,9 +1221,6 @@ struct AccumBwdOp : OpBase1 {
     }
     __device__ __forceinline__ void store(const Pos &q)
     {
-        const bool *valid = q.valid;
-        const int64_t p0 = q.p0();
-        (void)valid; (void)p0;
         if (gw) store4<VEC>(gw, q, res);
     }
 };
@@ -1390,11 +1279,10 @@ __device__ __forceinline__ void store_rgb12(float *rgb, bool vec, const Pos &q, 
             store_f4(o + 8, s[8], s[9], s[10], s[11]);
         } else {
             NFA_ELEMENTWISE_PATH();
-            NFA_PV float *pv = b;
 #pragma unroll
             for (int j = 4 * h; j < 4 * h + 4; ++j)
                 if (q.valid[j]) {
-                    pv[3 * (q.off + j)] = g[3 * j]; pv[3 * (q.off + j) + 1] = g[3 * j + 1]; pv[3 * (q.off + j) + 2] = g[3 * j + 2];
+                    b[3 * (q.off + j)] = g[3 * j]; b[3 * (q.off + j) + 1] = g[3 * j + 1]; b[3 * (q.off + j) + 2] = g[3 * j + 2];
                 }
         }
     }
@@ -1402,20 +1290,13 @@ __device__ __forceinline__ void store_rgb12(float *rgb, bool vec, const Pos &q, 
 
 // ---- the three accumulations of `rendering` fused: colours(3), opacity, depth  (volrend.py:140-151)
 template <bool VEC>
-struct RenderAccumOp {
+struct RenderAccumOp : OpBase {
     static constexpr int NCH = 5;
-    static constexpr int NCHB = 0;
-    static constexpr bool NEEDS_RID = false;
     static constexpr bool TOTALS = true;
-    static constexpr int MIN_WAVES_PER_EU = 1;
-    static constexpr int RAY_LDS_FLOATS = 0;    // per-wave LDS floats for per-ray data staged at tile start (tile_begin)
-    static constexpr int PIPE = NFA_SEG_PIPE;   // when the next step's loads are requested (seg_run_tile)
     struct Raw { F4 w, a, b; float c[3 * SE]; };
     const float *w, *rgb, *ts, *te;
     float *colors, *opac, *depth;
     float xv[SE][5];
-    __device__ __forceinline__ float identity(int) const { return 0.0f; }
-    __device__ __forceinline__ float comb(int, float a, float b) const { return a + b; }
     __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
     {
         ld4<VEC>(w, q, r.w);
@@ -1453,7 +1334,7 @@ struct RenderAccumOp {
 };
 
 template <bool VEC>
-struct RenderAccumBwdOp : OpBase1 {
+struct RenderAccumBwdOp : OpBase {
     struct Raw { F4 w, a, b; float c[3 * SE]; };
     const float *w, *rgb, *ts, *te, *gc, *go, *gd;
     float *gw, *grgb;
@@ -1491,9 +1372,6 @@ struct RenderAccumBwdOp : OpBase1 {
     }
     __device__ __forceinline__ void store(const Pos &q)
     {
-        const bool *valid = q.valid;
-        const int64_t p0 = q.p0();
-        (void)valid; (void)p0;
         if (gw) store4<VEC>(gw, q, res);
         if (grgb) store_rgb12(grgb, VEC, q, gr);
     }
@@ -1504,18 +1382,17 @@ struct RenderAccumBwdOp : OpBase1 {
 //      colour / opacity / un-normalised depth.  Bit-identical to DensityFwdOp followed by
 //      RenderAccumOp (same expressions, same scan tree), 12 B/sample less traffic.
 template <bool VEC>
-struct RenderFusedFwdOp : OpBase1 {
-    static constexpr int NCHB = 5;
-    static constexpr int MIN_WAVES_PER_EU = NFA_SEG_OCC_HINTS ? 6 : 1;  // 81 VGPRs without the hint: one over the 6-wave budget
+struct RenderFusedFwdOp : OpBase {
+    static constexpr int NCHB = 5;   // (81 VGPRs: one over the 6-wave budget; asking for 6 waves was within noise)
     struct Raw { F4 a, b, s; float c[3 * SE]; };
     const float *ts, *te, *sig, *rgb;
     float *w, *tr, *al, *colors, *opac, *depth;
     float xs[SE], mid[SE], rw[SE], rt[SE], ra[SE], c[3 * SE];
     __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
     {
-        ld4<VEC, NFA_NT_FWD>(ts, q, r.a);
-        ld4<VEC, NFA_NT_FWD>(te, q, r.b);
-        ld4<VEC, NFA_NT_FWD>(sig, q, r.s);
+        ld4<VEC>(ts, q, r.a);
+        ld4<VEC>(te, q, r.b);
+        ld4<VEC>(sig, q, r.s);
         load_rgb12(rgb, VEC, q, r.c);
     }
     __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
@@ -1558,9 +1435,6 @@ struct RenderFusedFwdOp : OpBase1 {
     }
     __device__ __forceinline__ void store(const Pos &q)
     {
-        const bool *valid = q.valid;
-        const int64_t p0 = q.p0();
-        (void)valid; (void)p0;
         if (w) store4<VEC>(w, q, rw);
         if (tr) store4<VEC>(tr, q, rt);
         if (al) store4<VEC>(al, q, ra);
@@ -1572,7 +1446,7 @@ struct RenderFusedFwdOp : OpBase1 {
 //      and rgb / opacity / depth accumulated IN PLACE into the per-ray image buffers.  Nothing per sample is written.
 //      A ray is owned by one wave, which reads its old opacity for all the ray's samples before it adds the total.
 template <bool VEC>
-struct RenderStepOp : OpBase1 {
+struct RenderStepOp : OpBase {
     static constexpr int NCHB = 5;
     static constexpr bool NEEDS_RID = true;
     struct Raw { F4 a, b, s; float c[3 * SE]; };
@@ -1639,21 +1513,18 @@ struct RenderStepOp : OpBase1 {
 //      from the per-ray output gradients (needs the ray id before the scan: NEEDS_RID), added to the
 //      gradients arriving at extras' weights / trans / alphas, and pushed through the transmittance
 //      chain.  Same expressions as RenderAccumBwdOp followed by DensityBwdOp.
-#ifndef NFA_BWD_RAY_CAP
-#define NFA_BWD_RAY_CAP 192   // 0: no staging (A/B switch)
-#endif
 template <bool VEC, bool EXTRA /* gradients arrive at weights / trans / alphas too */>
-struct RenderFusedBwdOp : OpBase1 {
+struct RenderFusedBwdOp : OpBase {
     static constexpr bool NEEDS_RID = true;
-    static constexpr int MIN_WAVES_PER_EU = (NFA_SEG_OCC_HINTS && !EXTRA) ? 5 : 1;  // 98 VGPRs without the hint: two over the 5-wave budget
+    // (98 VGPRs without EXTRA: two over the 5-wave budget; asking for 5 waves was within noise)
     // The per-ray output gradients (colour, opacity, depth: 5 floats per ray) are needed per ELEMENT, after the ray id is
     // known: as global gathers they were a second, dependent memory latency in every step (12 gather instructions per lane
     // and step; SQ counters: the pass waits 80 % of its wave-cycles, VALU 36 % busy).  The rays of a tile are consecutive,
     // so the wave stages their gradients in LDS with coalesced loads at tile start (up to RAY_CAP rays, the rest falls
     // back to the gathers) and the per-element reads are LDS reads.
-    static constexpr int RAY_CAP = NFA_BWD_RAY_CAP;
+    static constexpr int RAY_CAP = 192;
     static constexpr int RAY_LDS_FLOATS = 8 * RAY_CAP;   // {g_r, g_g, g_b, g_opacity, g_depth, -, -, -} per ray
-    static constexpr int PIPE = NFA_BWD_PIPE;   // measured per op: a full step ahead is 2-4 % faster here (313 -> 300 us), 2 % slower on the forward pass
+    static constexpr bool PIPE = true;   // measured per op: a full step ahead is 2-4 % faster here (313 -> 300 us), 2 % slower on the forward pass
     struct Raw { F4 a, b, T, A, gw, gt, ga; float c[3 * SE]; };
     const float *ts, *te, *rgb, *tr, *al, *gc, *go, *gd, *gw, *gt, *ga;
     float *gsig, *grgb;
@@ -1813,6 +1684,23 @@ static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t
 template <typename... P>
 static inline bool all_aligned16(P... p) { return (aligned16(p) && ...); }
 
+// Host-side dispatch of a run-time value to a compile-time one: f(std::true_type / std::false_type), and f(the channel
+// count 1..4 as std::integral_constant<int, C>).
+template <class F>
+static void dispatch_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+static void dispatch_channels(int c, F &&f)
+{
+    if (c == 4) f(std::integral_constant<int, 4>{});
+    else if (c == 3) f(std::integral_constant<int, 3>{});
+    else if (c == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 1>{});
+}
+
 }  // namespace nfa
 
 using namespace nfa;
@@ -1863,22 +1751,15 @@ int nfa_packed_scan(int kind, int reverse, const int64_t *packed_info, const int
     NFA_REQUIRE(inputs && outputs, "packed_scan: null data pointer");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(inputs, outputs);
-#define NFA_SCAN_CASE(EX, PR)                                                                             \
-    do {                                                                                                  \
-        if (vec) { ScanOp<EX, PR, true> op; op.in = inputs; op.out = outputs;                            \
-            if (reverse) launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s);                      \
-            else launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s); }                             \
-        else { ScanOp<EX, PR, false> op; op.in = inputs; op.out = outputs;                               \
-            if (reverse) launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s);                      \
-            else launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s); }                             \
-    } while (0)
-    switch (kind) {
-        case 0: NFA_SCAN_CASE(false, false); break;
-        case 1: NFA_SCAN_CASE(true, false); break;
-        case 2: NFA_SCAN_CASE(false, true); break;
-        default: NFA_SCAN_CASE(true, true); break;
-    }
-#undef NFA_SCAN_CASE
+    dispatch_bool(kind & 1, [&](auto EX) {
+        dispatch_bool(kind >= 2, [&](auto PR) {
+            dispatch_bool(vec, [&](auto V) {
+                ScanOp<EX, PR, V> op;
+                op.in = inputs; op.out = outputs;
+                dispatch_bool(reverse != 0, [&](auto REV) { launch_seg<REV ? -1 : 1>(op, packed_info, tiles, n_rays, n_tiles, s); });
+            });
+        });
+    });
     NFA_CHECK_LAUNCH("packed_scan");
     return NFA_OK;
 }
@@ -1911,12 +1792,13 @@ int nfa_packed_prod_backward(int kind, const int64_t *packed_info, const int64_t
     NFA_REQUIRE(inputs && outputs && grad_outputs && grad_inputs, "packed_prod_backward: null data pointer");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(inputs, outputs, grad_outputs, grad_inputs);
-#define NFA_PB(EX, V)                                                                                      \
-    do { ProdBwdOp<EX, V> op; op.in = inputs; op.outv = outputs; op.g = grad_outputs; op.gin = grad_inputs; \
-         launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-    if (kind == 2) { if (vec) NFA_PB(false, true); else NFA_PB(false, false); }
-    else           { if (vec) NFA_PB(true, true); else NFA_PB(true, false); }
-#undef NFA_PB
+    dispatch_bool(kind == 3, [&](auto EX) {
+        dispatch_bool(vec, [&](auto V) {
+            ProdBwdOp<EX, V> op;
+            op.in = inputs; op.outv = outputs; op.g = grad_outputs; op.gin = grad_inputs;
+            launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s);
+        });
+    });
     NFA_CHECK_LAUNCH("packed_prod_backward");
     return NFA_OK;
 }
@@ -1931,11 +1813,12 @@ int nfa_render_from_density_fwd(const float *t_starts, const float *t_ends, cons
     NFA_REQUIRE(t_starts && t_ends && sigmas, "render_from_density_fwd: null input");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(t_starts, t_ends, sigmas, prefix_trans, weights, trans, alphas);
-#define NFA_DF(V)                                                                                          \
-    do { DensityFwdOp<V> op; op.ts = t_starts; op.te = t_ends; op.sig = sigmas; op.prefix = prefix_trans;   \
-         op.w = weights; op.tr = trans; op.al = alphas; launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-    if (vec) NFA_DF(true); else NFA_DF(false);
-#undef NFA_DF
+    dispatch_bool(vec, [&](auto V) {
+        DensityFwdOp<V> op;
+        op.ts = t_starts; op.te = t_ends; op.sig = sigmas; op.prefix = prefix_trans;
+        op.w = weights; op.tr = trans; op.al = alphas;
+        launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+    });
     NFA_CHECK_LAUNCH("render_from_density_fwd");
     return NFA_OK;
 }
@@ -1949,11 +1832,11 @@ int nfa_render_from_alpha_fwd(const float *alphas, const float *prefix_trans, co
     NFA_REQUIRE(alphas, "render_from_alpha_fwd: null input");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(alphas, prefix_trans, weights, trans);
-#define NFA_AF(V)                                                                                          \
-    do { AlphaFwdOp<V> op; op.al = alphas; op.prefix = prefix_trans; op.w = weights; op.tr = trans;          \
-         launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-    if (vec) NFA_AF(true); else NFA_AF(false);
-#undef NFA_AF
+    dispatch_bool(vec, [&](auto V) {
+        AlphaFwdOp<V> op;
+        op.al = alphas; op.prefix = prefix_trans; op.w = weights; op.tr = trans;
+        launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+    });
     NFA_CHECK_LAUNCH("render_from_alpha_fwd");
     return NFA_OK;
 }
@@ -1968,12 +1851,12 @@ int nfa_render_from_density_bwd(const float *t_starts, const float *t_ends, cons
     NFA_REQUIRE(t_starts && t_ends && trans && alphas && (grad_sigmas || grad_x), "render_from_density_bwd: null pointer");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(t_starts, t_ends, trans, alphas, g_weights, g_trans, g_alphas, grad_sigmas, grad_x);
-#define NFA_DB(V)                                                                                          \
-    do { DensityBwdOp<V> op; op.ts = t_starts; op.te = t_ends; op.tr = trans; op.al = alphas; op.gw = g_weights; \
-         op.gt = g_trans; op.ga = g_alphas; op.gsig = grad_sigmas; op.gx = grad_x;                            \
-         launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-    if (vec) NFA_DB(true); else NFA_DB(false);
-#undef NFA_DB
+    dispatch_bool(vec, [&](auto V) {
+        DensityBwdOp<V> op;
+        op.ts = t_starts; op.te = t_ends; op.tr = trans; op.al = alphas;
+        op.gw = g_weights; op.gt = g_trans; op.ga = g_alphas; op.gsig = grad_sigmas; op.gx = grad_x;
+        launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s);
+    });
     NFA_CHECK_LAUNCH("render_from_density_bwd");
     return NFA_OK;
 }
@@ -1988,12 +1871,12 @@ int nfa_density_cdf_rows_fwd(const float *t_starts, const float *t_ends, const f
     NFA_REQUIRE(row_len >= 1 && n_rays * (int64_t)row_len == n_elems, "density_cdf_rows_fwd: n_elems must be n_rays * row_len");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(t_starts, t_ends, sigmas, trans, alphas);
-#define NFA_DC(V)                                                                                          \
-    do { DensityFwdOp<V> op; op.ts = t_starts; op.te = t_ends; op.sig = sigmas; op.prefix = nullptr;         \
-         op.w = nullptr; op.tr = trans; op.al = alphas; op.cdf = cdfs; op.row_len = row_len;                \
-         launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-    if (vec) NFA_DC(true); else NFA_DC(false);
-#undef NFA_DC
+    dispatch_bool(vec, [&](auto V) {
+        DensityFwdOp<V> op;
+        op.ts = t_starts; op.te = t_ends; op.sig = sigmas; op.prefix = nullptr;
+        op.w = nullptr; op.tr = trans; op.al = alphas; op.cdf = cdfs; op.row_len = row_len;
+        launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+    });
     NFA_CHECK_LAUNCH("density_cdf_rows_fwd");
     return NFA_OK;
 }
@@ -2009,12 +1892,12 @@ int nfa_density_cdf_rows_bwd(const float *t_starts, const float *t_ends, const f
     NFA_REQUIRE(row_len >= 1 && n_rays * (int64_t)row_len == n_elems, "density_cdf_rows_bwd: n_elems must be n_rays * row_len");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(t_starts, t_ends, trans, alphas, grad_sigmas);
-#define NFA_DCB(V)                                                                                         \
-    do { DensityBwdOp<V, true> op; op.ts = t_starts; op.te = t_ends; op.tr = trans; op.al = alphas; op.gw = nullptr; \
-         op.gt = nullptr; op.ga = nullptr; op.gcdf = g_cdfs; op.gsig = grad_sigmas; op.gx = nullptr;          \
-         launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-    if (vec) NFA_DCB(true); else NFA_DCB(false);
-#undef NFA_DCB
+    dispatch_bool(vec, [&](auto V) {
+        DensityBwdOp<V, true> op;
+        op.ts = t_starts; op.te = t_ends; op.tr = trans; op.al = alphas;
+        op.gw = nullptr; op.gt = nullptr; op.ga = nullptr; op.gcdf = g_cdfs; op.gsig = grad_sigmas; op.gx = nullptr;
+        launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s);
+    });
     NFA_CHECK_LAUNCH("density_cdf_rows_bwd");
     return NFA_OK;
 }
@@ -2028,11 +1911,11 @@ int nfa_render_from_alpha_bwd(const float *alphas, const float *trans, const flo
     NFA_REQUIRE(alphas && trans && grad_alphas, "render_from_alpha_bwd: null pointer");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(alphas, trans, g_weights, g_trans, grad_alphas);
-#define NFA_AB(V)                                                                                          \
-    do { AlphaBwdOp<V> op; op.al = alphas; op.tr = trans; op.gw = g_weights; op.gt = g_trans; op.galpha = grad_alphas; \
-         launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-    if (vec) NFA_AB(true); else NFA_AB(false);
-#undef NFA_AB
+    dispatch_bool(vec, [&](auto V) {
+        AlphaBwdOp<V> op;
+        op.al = alphas; op.tr = trans; op.gw = g_weights; op.gt = g_trans; op.galpha = grad_alphas;
+        launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s);
+    });
     NFA_CHECK_LAUNCH("render_from_alpha_bwd");
     return NFA_OK;
 }
@@ -2060,15 +1943,16 @@ int nfa_render_visibility(const float *t_starts, const float *t_ends, const floa
         // the uchar4 mask store needs 4-byte alignment of vis, the float loads 16
         const bool vec = all_aligned16(t_starts, t_ends, sigmas_or_alphas, prefix_trans) &&
                          (reinterpret_cast<uintptr_t>(vis) & 3) == 0;
-#define NFA_VIS(DN, V, CN)                                                                                 \
-    do { VisibilityOp<DN, V, CN> op; op.ts = t_starts; op.te = t_ends; op.val = sigmas_or_alphas; op.prefix = prefix_trans; \
-         op.eps = early_stop_eps; op.thre = alpha_thre; op.vis = vis; op.cnts = vis_cnts; op.s_lo = s_lo; op.s_hi = s_hi; \
-         launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-#define NFA_VIS2(DN, V) do { if (vis_cnts) NFA_VIS(DN, V, true); else NFA_VIS(DN, V, false); } while (0)
-        if (density) { if (vec) NFA_VIS2(true, true); else NFA_VIS2(true, false); }
-        else         { if (vec) NFA_VIS2(false, true); else NFA_VIS2(false, false); }
-#undef NFA_VIS2
-#undef NFA_VIS
+        dispatch_bool(density, [&](auto DN) {
+            dispatch_bool(vec, [&](auto V) {
+                dispatch_bool(vis_cnts != nullptr, [&](auto CN) {
+                    VisibilityOp<DN, V, CN> op;
+                    op.ts = t_starts; op.te = t_ends; op.val = sigmas_or_alphas; op.prefix = prefix_trans;
+                    op.eps = early_stop_eps; op.thre = alpha_thre; op.vis = vis; op.cnts = vis_cnts; op.s_lo = s_lo; op.s_hi = s_hi;
+                    launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+                });
+            });
+        });
     } else if (vis_cnts && n_rays > 0) {
         if (hipMemsetAsync(vis_cnts, 0, sizeof(int64_t) * n_rays, s) != hipSuccess) { set_error("render_visibility: memset failed"); return NFA_EHIP; }
     }
@@ -2086,12 +1970,12 @@ int nfa_compact_samples(const uint8_t *vis, const float *t_starts, const float *
     NFA_REQUIRE(capacity >= 0, "compact_samples: negative capacity");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(t_starts, t_ends);
-#define NFA_CP(V)                                                                                          \
-    do { CompactOp<V> op; op.vis = vis; op.vis_vec = (reinterpret_cast<uintptr_t>(vis) & 3) == 0; op.ts = t_starts; op.te = t_ends; op.out_starts = out_starts;       \
-         op.o_ri = out_ray_indices; op.o_ts = out_t_starts; op.o_te = out_t_ends; op.cap = capacity;        \
-         launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-    if (vec) NFA_CP(true); else NFA_CP(false);
-#undef NFA_CP
+    dispatch_bool(vec, [&](auto V) {
+        CompactOp<V> op;
+        op.vis = vis; op.vis_vec = (reinterpret_cast<uintptr_t>(vis) & 3) == 0; op.ts = t_starts; op.te = t_ends;
+        op.out_starts = out_starts; op.o_ri = out_ray_indices; op.o_ts = out_t_starts; op.o_te = out_t_ends; op.cap = capacity;
+        launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+    });
     NFA_CHECK_LAUNCH("compact_samples");
     return NFA_OK;
 }
@@ -2108,12 +1992,13 @@ int nfa_accumulate_along_rays(const float *weights, const float *values, int32_t
     const bool vec = all_aligned16(weights);
     for (int32_t d0 = 0; d0 < D;) {
         const int32_t c = (D - d0 >= 4) ? 4 : (D - d0);
-#define NFA_ACC(C, V)                                                                                      \
-    do { AccumOp<C, V> op; op.w = weights; op.vals = values; op.D = D; op.d0 = d0; op.out = out;             \
-         op.accumulate = accumulate; launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-        if (vec) { if (c == 4) NFA_ACC(4, true); else if (c == 3) NFA_ACC(3, true); else if (c == 2) NFA_ACC(2, true); else NFA_ACC(1, true); }
-        else     { if (c == 4) NFA_ACC(4, false); else if (c == 3) NFA_ACC(3, false); else if (c == 2) NFA_ACC(2, false); else NFA_ACC(1, false); }
-#undef NFA_ACC
+        dispatch_channels(c, [&](auto C) {
+            dispatch_bool(vec, [&](auto V) {
+                AccumOp<C, V> op;
+                op.w = weights; op.vals = values; op.D = D; op.d0 = d0; op.out = out; op.accumulate = accumulate;
+                launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+            });
+        });
         d0 += c;
     }
     NFA_CHECK_LAUNCH("accumulate_along_rays");
@@ -2144,13 +2029,14 @@ int nfa_accumulate_along_rays_bwd(const float *weights, const float *values, int
     const bool vec = all_aligned16(weights, g_weights);
     for (int32_t d0 = 0; d0 < D;) {
         const int32_t c = (D - d0 >= 4) ? 4 : (D - d0);
-#define NFA_ACB(C, V)                                                                                      \
-    do { AccumBwdOp<C, V> op; op.w = weights; op.vals = values; op.gout = g_out; op.D = D; op.d0 = d0;       \
-         op.first = (d0 == 0); op.gw = g_weights; op.gv = g_values;                                          \
-         launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-        if (vec) { if (c == 4) NFA_ACB(4, true); else if (c == 3) NFA_ACB(3, true); else if (c == 2) NFA_ACB(2, true); else NFA_ACB(1, true); }
-        else     { if (c == 4) NFA_ACB(4, false); else if (c == 3) NFA_ACB(3, false); else if (c == 2) NFA_ACB(2, false); else NFA_ACB(1, false); }
-#undef NFA_ACB
+        dispatch_channels(c, [&](auto C) {
+            dispatch_bool(vec, [&](auto V) {
+                AccumBwdOp<C, V> op;
+                op.w = weights; op.vals = values; op.gout = g_out; op.D = D; op.d0 = d0;
+                op.first = (d0 == 0); op.gw = g_weights; op.gv = g_values;
+                launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+            });
+        });
         d0 += c;
     }
     NFA_CHECK_LAUNCH("accumulate_along_rays_bwd");
@@ -2167,12 +2053,12 @@ int nfa_render_accumulate_fwd(const float *weights, const float *rgbs, const flo
                 "render_accumulate_fwd: null pointer");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(weights, rgbs, t_starts, t_ends);
-#define NFA_RA(V)                                                                                          \
-    do { RenderAccumOp<V> op; op.w = weights; op.rgb = rgbs; op.ts = t_starts; op.te = t_ends;               \
-         op.colors = colors; op.opac = opacities; op.depth = depths;                                         \
-         launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-    if (vec) NFA_RA(true); else NFA_RA(false);
-#undef NFA_RA
+    dispatch_bool(vec, [&](auto V) {
+        RenderAccumOp<V> op;
+        op.w = weights; op.rgb = rgbs; op.ts = t_starts; op.te = t_ends;
+        op.colors = colors; op.opac = opacities; op.depth = depths;
+        launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+    });
     NFA_CHECK_LAUNCH("render_accumulate_fwd");
     return NFA_OK;
 }
@@ -2187,12 +2073,12 @@ int nfa_render_accumulate_bwd(const float *weights, const float *rgbs, const flo
     NFA_REQUIRE(weights && rgbs && t_starts && t_ends && (g_weights || g_rgbs), "render_accumulate_bwd: null pointer");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(weights, rgbs, t_starts, t_ends, g_weights, g_rgbs);
-#define NFA_RB(V)                                                                                          \
-    do { RenderAccumBwdOp<V> op; op.w = weights; op.rgb = rgbs; op.ts = t_starts; op.te = t_ends;            \
-         op.gc = g_colors; op.go = g_opacities; op.gd = g_depths; op.gw = g_weights; op.grgb = g_rgbs;       \
-         launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-    if (vec) NFA_RB(true); else NFA_RB(false);
-#undef NFA_RB
+    dispatch_bool(vec, [&](auto V) {
+        RenderAccumBwdOp<V> op;
+        op.w = weights; op.rgb = rgbs; op.ts = t_starts; op.te = t_ends;
+        op.gc = g_colors; op.go = g_opacities; op.gd = g_depths; op.gw = g_weights; op.grgb = g_rgbs;
+        launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+    });
     NFA_CHECK_LAUNCH("render_accumulate_bwd");
     return NFA_OK;
 }
@@ -2208,12 +2094,12 @@ int nfa_render_fused_fwd(const float *t_starts, const float *t_ends, const float
                 "render_fused_fwd: null pointer");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(t_starts, t_ends, sigmas, rgbs, weights, trans, alphas);
-#define NFA_FF(V)                                                                                          \
-    do { RenderFusedFwdOp<V> op; op.ts = t_starts; op.te = t_ends; op.sig = sigmas; op.rgb = rgbs; op.w = weights; \
-         op.tr = trans; op.al = alphas; op.colors = colors; op.opac = opacities; op.depth = depths;          \
-         launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-    if (vec) NFA_FF(true); else NFA_FF(false);
-#undef NFA_FF
+    dispatch_bool(vec, [&](auto V) {
+        RenderFusedFwdOp<V> op;
+        op.ts = t_starts; op.te = t_ends; op.sig = sigmas; op.rgb = rgbs; op.w = weights; op.tr = trans; op.al = alphas;
+        op.colors = colors; op.opac = opacities; op.depth = depths;
+        launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+    });
     NFA_CHECK_LAUNCH("render_fused_fwd");
     return NFA_OK;
 }
@@ -2229,15 +2115,16 @@ int nfa_render_fused_bwd(const float *t_starts, const float *t_ends, const float
     NFA_REQUIRE(t_starts && t_ends && rgbs && trans && alphas && (grad_sigmas || grad_rgbs), "render_fused_bwd: null pointer");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(t_starts, t_ends, rgbs, trans, alphas, g_weights, g_trans, g_alphas, grad_sigmas, grad_rgbs);
-#define NFA_FB(V, X)                                                                                       \
-    do { RenderFusedBwdOp<V, X> op; op.ts = t_starts; op.te = t_ends; op.rgb = rgbs; op.tr = trans; op.al = alphas; \
-         op.gc = g_colors; op.go = g_opacities; op.gd = g_depths; op.gw = g_weights; op.gt = g_trans; op.ga = g_alphas; \
-         op.gsig = grad_sigmas; op.grgb = grad_rgbs;                                                         \
-         launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
     const bool extra = g_weights || g_trans || g_alphas;
-    if (vec) { if (extra) NFA_FB(true, true); else NFA_FB(true, false); }
-    else     { if (extra) NFA_FB(false, true); else NFA_FB(false, false); }
-#undef NFA_FB
+    dispatch_bool(vec, [&](auto V) {
+        dispatch_bool(extra, [&](auto X) {
+            RenderFusedBwdOp<V, X> op;
+            op.ts = t_starts; op.te = t_ends; op.rgb = rgbs; op.tr = trans; op.al = alphas;
+            op.gc = g_colors; op.go = g_opacities; op.gd = g_depths; op.gw = g_weights; op.gt = g_trans; op.ga = g_alphas;
+            op.gsig = grad_sigmas; op.grgb = grad_rgbs;
+            launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s);
+        });
+    });
     NFA_CHECK_LAUNCH("render_fused_bwd");
     return NFA_OK;
 }
@@ -2252,13 +2139,13 @@ int nfa_render_step_accumulate(const float *t_starts, const float *t_ends, const
     NFA_REQUIRE(t_starts && t_ends && sigmas && rgbs && colors && opacities && depths, "render_step_accumulate: null pointer");
     hipStream_t s = as_stream(stream);
     const bool vec = all_aligned16(t_starts, t_ends, sigmas, rgbs);
-#define NFA_RS(V)                                                                                          \
-    do { RenderStepOp<V> op; op.ts = t_starts; op.te = t_ends; op.sig = sigmas; op.rgb = rgbs; op.thre = alpha_thre; \
-         op.colors = colors; op.opac = opacities; op.depth = depths;                                         \
-         op.n_visible = reinterpret_cast<unsigned long long *>(n_visible);                                   \
-         launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s); } while (0)
-    if (vec) NFA_RS(true); else NFA_RS(false);
-#undef NFA_RS
+    dispatch_bool(vec, [&](auto V) {
+        RenderStepOp<V> op;
+        op.ts = t_starts; op.te = t_ends; op.sig = sigmas; op.rgb = rgbs; op.thre = alpha_thre;
+        op.colors = colors; op.opac = opacities; op.depth = depths;
+        op.n_visible = reinterpret_cast<unsigned long long *>(n_visible);
+        launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+    });
     NFA_CHECK_LAUNCH("render_step_accumulate");
     return NFA_OK;
 }
