@@ -40,7 +40,7 @@ typedef void *nfa_stream_t; /* hipStream_t */
 const char *nfa_last_error(void);
 /* The version of THIS header.  Bumped whenever an entry point changes its arguments or what it expects of them; a caller
  * built against another value must not call the library (nerfacc_amd/_backend.py refuses to load it). */
-#define NFA_VERSION 402
+#define NFA_VERSION 403
 int nfa_version(void);          /* NFA_VERSION of the header the library was built from */
 /* Knobs of the A/B tests and measurement scripts (which of two equivalent kernels a call takes, tile sizes); value NULL
  * or "" unsets.  Names: NFA_REFILL, NFA_REFILL_ALL, NFA_CONE_STAGED, NFA_SEG_TILE, NFA_WALK_NO_LATTICE.  Results never
@@ -433,6 +433,20 @@ int nfa_render_fused_bwd(const float *t_starts, const float *t_ends, const float
                          const float *g_alphas, const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles,
                          int64_t n_rays, int64_t n_elems, float *grad_sigmas, float *grad_rgbs,
                          nfa_stream_t stream);
+
+/* Mip-NeRF 360 distortion loss per ray (Barron et al. 2022, eq. 15) over samples in non-decreasing midpoint order
+ * within each ray: loss[r] = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 (t_end_i - t_start_i), m = (t_start + t_end) / 2
+ * (input out of that order gets what the O(n) prefix-sum form gives; it is not detected).  Also writes the per-ray totals
+ * w_tot[r] = sum w_i and s_tot[r] = sum w_i (m_i - m_first(r)) the backward needs.  Empty rays get 0. */
+int nfa_distortion_fwd(const float *weights, const float *t_starts, const float *t_ends, const int64_t *packed_info,
+                       const int64_t *tiles, int64_t n_tiles, int64_t n_rays, int64_t n_elems, float *loss, float *w_tot,
+                       float *s_tot, nfa_stream_t stream);
+/* Its backward in one reverse pass: g_loss[r] is the gradient of loss[r]; w_tot / s_tot are the forward's.  Writes
+ * grad_weights[n], grad_t_starts[n], grad_t_ends[n]; each may be NULL (not needed), not all three. */
+int nfa_distortion_bwd(const float *weights, const float *t_starts, const float *t_ends, const float *w_tot,
+                       const float *s_tot, const float *g_loss, const int64_t *packed_info, const int64_t *tiles,
+                       int64_t n_tiles, int64_t n_rays, int64_t n_elems, float *grad_weights, float *grad_t_starts,
+                       float *grad_t_ends, nfa_stream_t stream);
 
 /* One iteration of the test-mode marching loop (ref: examples/utils.py:370-405) in one pass: weights from
  * densities with prefix_trans = 1 - opacities[ray], samples with alpha < alpha_thre dropped (alpha_thre <= 0:

@@ -100,6 +100,8 @@ _SIGS = {
     "nfa_render_fused_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nfa_render_fused_bwd": [_vp] * 13 + [_i64, _i64, _i64, _vp, _vp, _vp],
     "nfa_render_step_accumulate": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp],
+    "nfa_distortion_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
+    "nfa_distortion_bwd": [_vp] * 8 + [_i64, _i64, _i64, _vp, _vp, _vp, _vp],
     "nfa_importance_sampling": [_vp, _vp, _vp, _i64, _i64, _i64, _int, _u64, _u64, _vp, _vp, _vp],
     "nfa_importance_sampling_t": [_vp, _vp, _vp, _i64, _i64, _i64, _int, _u64, _u64, _vp, _vp, _int, _f32, _f32, _vp, _vp, _vp],
     "nfa_importance_sampling_packed": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _int, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -148,7 +150,7 @@ def load() -> C.CDLL:
     return _lib
 
 
-ABI_VERSION = 402   # include/nerfacc_hip.h: NFA_VERSION
+ABI_VERSION = 403   # include/nerfacc_hip.h: NFA_VERSION
 
 
 def set_tuning(name: str, value: Optional[str]) -> None:

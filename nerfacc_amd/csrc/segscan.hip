@@ -1618,6 +1618,157 @@ struct RenderFusedBwdOp : OpBase {
     }
 };
 
+// ---- Mip-NeRF 360 distortion loss (Barron et al. 2022, eq. 15) over samples in non-decreasing midpoint order per ray:
+//      L = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 s_i = sum_k [2 w_k (d_k W<k - S<k) + w_k^2 s_k / 3], with
+//      W<k / S<k the exclusive prefix sums of w and w*d, d = m - m(first sample of the ray).  The loss is shift-invariant;
+//      the shift keeps d W - S free of cancellation when t is large.  Input out of midpoint order gets
+//      what this formula gives (not detected).
+// The first midpoint of every ray a tile touches is read at tile start into LDS (a tile owns at most SEG_TILE_ROWS rays;
+// more would fall back to gathers), so pre() knows d before stage A.
+constexpr int DIST_RAY_CAP = SEG_TILE_ROWS < 256 ? (int)SEG_TILE_ROWS : 256;
+__device__ __forceinline__ float dist_mid(float a, float b) { return (a + b) / 2.0f; }
+__device__ __forceinline__ float dist_first_mid(const int64_t *packed_info, const float *ts, const float *te, int64_t r)
+{
+    const longlong2 pr = *reinterpret_cast<const longlong2 *>(packed_info + 2 * r);
+    return pr.y > 0 ? dist_mid(ts[pr.x], te[pr.x]) : 0.0f;   // (an empty ray has no element to read)
+}
+
+// forward: stage A scans {w, w*d}; stage B totals the per-element term into loss[ray]; TOTALS write W_tot / S_tot
+template <bool VEC>
+struct DistortionFwdOp : OpBase {
+    static constexpr int NCH = 2;
+    static constexpr int NCHB = 1;
+    static constexpr bool NEEDS_RID = true;
+    static constexpr bool TOTALS = true;
+    static constexpr int RAY_LDS_FLOATS = DIST_RAY_CAP;   // m_first per ray
+    struct Raw { F4 a, b, w; };
+    const int64_t *pinfo;
+    const float *ts, *te, *w;
+    float *loss, *wtot, *stot;
+    const float *m_lds = nullptr;
+    int32_t g_lo = 0, g_n = 0;
+    float ww[SE], mid[SE], sw[SE], d[SE], term[SE];
+    __device__ __forceinline__ void tile_begin(int32_t r_lo, int32_t r_hi, float *lds)
+    {
+        m_lds = lds; g_lo = r_lo; g_n = min(r_hi - r_lo, DIST_RAY_CAP);
+        __builtin_amdgcn_wave_barrier();
+        for (int32_t i = lane_id(); i < g_n; i += 64) lds[i] = dist_first_mid(pinfo, ts, te, (int64_t)g_lo + i);
+        __builtin_amdgcn_wave_barrier();
+    }
+    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
+    {
+        ld4<VEC>(ts, q, r.a);
+        ld4<VEC>(te, q, r.b);
+        ld4<VEC>(w, q, r.w);
+    }
+    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
+    {
+        const bool *valid = pos.valid;
+#pragma unroll
+        for (int j = 0; j < SE; ++j) {
+            ww[j] = sel(r.w, j, valid, 0.0f);
+            mid[j] = dist_mid(r.a.v[j], r.b.v[j]);
+            sw[j] = valid[j] ? r.b.v[j] - r.a.v[j] : 0.0f;
+        }
+    }
+    __device__ __forceinline__ void pre(int j, int64_t, bool valid, int rid)
+    {
+        float m0 = 0.0f;
+        if (valid) {
+            const uint32_t slot = (uint32_t)(rid - g_lo);
+            m0 = slot < (uint32_t)g_n ? m_lds[slot] : dist_first_mid(pinfo, ts, te, rid);
+        }
+        d[j] = valid ? mid[j] - m0 : 0.0f;
+    }
+    __device__ __forceinline__ void store_pre(const Pos &) const {}
+    __device__ __forceinline__ float x(int j, int ch) const { return ch == 0 ? ww[j] : ww[j] * d[j]; }
+    __device__ __forceinline__ void emit(int j, int64_t, bool, bool is_head, int, int, const float *, const float prev[2])
+    {
+        const float Wl = is_head ? 0.0f : prev[0], Sl = is_head ? 0.0f : prev[1];
+        term[j] = 2.0f * ww[j] * (d[j] * Wl - Sl) + ww[j] * ww[j] * sw[j] * (1.0f / 3.0f);
+    }
+    __device__ __forceinline__ float xb(int j, int) const { return term[j]; }
+    __device__ __forceinline__ void ray_done(int rid, const float t[2]) const { wtot[rid] = t[0]; stot[rid] = t[1]; }
+    __device__ __forceinline__ void ray_done_b(int rid, int, float t) const { loss[rid] = t; }
+    __device__ __forceinline__ void empty_ray(int rid) const { loss[rid] = 0.0f; wtot[rid] = 0.0f; stot[rid] = 0.0f; }
+    __device__ __forceinline__ void store(const Pos &) const {}
+};
+
+// backward: one reverse pass scans {w, w*d} into the exclusive suffix sums W>k / S>k; the prefix sums follow from the
+// forward's totals (W<k = W_tot - W>k - w_k).  {g[ray], m_first, W_tot, S_tot} are staged in LDS at tile start.
+//   dL/dw_k = 2 (d_k (W_tot - 2 W>k) + 2 S>k - S_tot) + 2/3 w_k s_k      (= 2 (A_k + B_k) + 2/3 w_k s_k)
+//   dL/dm_k = 2 w_k (W<k - W>k),  dL/ds_k = w_k^2 / 3;  t_start = m - s/2, t_end = m + s/2
+template <bool VEC>
+struct DistortionBwdOp : OpBase {
+    static constexpr int NCH = 2;
+    static constexpr bool NEEDS_RID = true;
+    static constexpr int RAY_LDS_FLOATS = 4 * DIST_RAY_CAP;   // {g, m_first, W_tot, S_tot} per ray
+    struct Raw { F4 a, b, w; };
+    const int64_t *pinfo;
+    const float *ts, *te, *w, *wtot, *stot, *gl;
+    float *gw, *gts, *gte;
+    const float *r_lds = nullptr;
+    int32_t g_lo = 0, g_n = 0;
+    float ww[SE], mid[SE], sw[SE], d[SE], G[SE], WT[SE], ST[SE], rw[SE], rts[SE], rte[SE];
+    __device__ __forceinline__ float4 ray_row(int64_t r) const
+    {
+        return make_float4(gl[r], dist_first_mid(pinfo, ts, te, r), wtot[r], stot[r]);
+    }
+    __device__ __forceinline__ void tile_begin(int32_t r_lo, int32_t r_hi, float *lds)
+    {
+        // (the pass runs from the tile's last ray to its first: a tile owning more than DIST_RAY_CAP rays stages the last ones)
+        r_lds = lds; g_n = min(r_hi - r_lo, DIST_RAY_CAP); g_lo = r_hi - g_n;
+        __builtin_amdgcn_wave_barrier();
+        for (int32_t i = lane_id(); i < g_n; i += 64) *reinterpret_cast<float4 *>(lds + 4 * i) = ray_row((int64_t)g_lo + i);
+        __builtin_amdgcn_wave_barrier();
+    }
+    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
+    {
+        ld4<VEC>(ts, q, r.a);
+        ld4<VEC>(te, q, r.b);
+        ld4<VEC>(w, q, r.w);
+    }
+    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
+    {
+        const bool *valid = pos.valid;
+#pragma unroll
+        for (int j = 0; j < SE; ++j) {
+            ww[j] = sel(r.w, j, valid, 0.0f);
+            mid[j] = dist_mid(r.a.v[j], r.b.v[j]);
+            sw[j] = valid[j] ? r.b.v[j] - r.a.v[j] : 0.0f;
+        }
+    }
+    __device__ __forceinline__ void pre(int j, int64_t, bool valid, int rid)
+    {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (valid) {
+            const uint32_t slot = (uint32_t)(rid - g_lo);
+            v = slot < (uint32_t)g_n ? *reinterpret_cast<const float4 *>(r_lds + 4 * slot) : ray_row(rid);
+        }
+        G[j] = v.x; WT[j] = v.z; ST[j] = v.w;
+        d[j] = valid ? mid[j] - v.y : 0.0f;
+    }
+    __device__ __forceinline__ void store_pre(const Pos &) const {}
+    __device__ __forceinline__ float x(int j, int ch) const { return ch == 0 ? ww[j] : ww[j] * d[j]; }
+    __device__ __forceinline__ void emit(int j, int64_t, bool, bool is_head, int, int, const float *, const float prev[2])
+    {
+        const float Wg = is_head ? 0.0f : prev[0], Sg = is_head ? 0.0f : prev[1];
+        const float g = G[j], wj = ww[j];
+        const float ab = d[j] * (WT[j] - 2.0f * Wg) + 2.0f * Sg - ST[j];
+        const float gm = g * 2.0f * wj * (WT[j] - 2.0f * Wg - wj);
+        const float gs = g * wj * wj * (1.0f / 3.0f);
+        rw[j] = g * (2.0f * ab + (2.0f / 3.0f) * wj * sw[j]);
+        rts[j] = 0.5f * gm - gs;
+        rte[j] = 0.5f * gm + gs;
+    }
+    __device__ __forceinline__ void store(const Pos &q)
+    {
+        if (gw) store4<VEC>(gw, q, rw);
+        if (gts) store4<VEC>(gts, q, rts);
+        if (gte) store4<VEC>(gte, q, rte);
+    }
+};
+
 // ------------------------------------------------------------------------------------------
 // Generic fallback: arbitrary (start, count) chunks, one wave per ray (semantics of
 // include/utils_scan.cuh incl. `normalize`).
@@ -2126,6 +2277,46 @@ int nfa_render_fused_bwd(const float *t_starts, const float *t_ends, const float
         });
     });
     NFA_CHECK_LAUNCH("render_fused_bwd");
+    return NFA_OK;
+}
+
+int nfa_distortion_fwd(const float *weights, const float *t_starts, const float *t_ends, const int64_t *packed_info,
+                       const int64_t *tiles, int64_t n_tiles, int64_t n_rays, int64_t n_elems, float *loss, float *w_tot,
+                       float *s_tot, nfa_stream_t stream)
+{
+    SEG_COMMON_CHECKS("distortion_fwd");
+    if (n_rays == 0) return NFA_OK;
+    NFA_REQUIRE(loss && w_tot && s_tot && (n_elems == 0 || (weights && t_starts && t_ends)), "distortion_fwd: null pointer");
+    hipStream_t s = as_stream(stream);
+    const bool vec = all_aligned16(weights, t_starts, t_ends);
+    dispatch_bool(vec, [&](auto V) {
+        DistortionFwdOp<V> op;
+        op.pinfo = packed_info; op.ts = t_starts; op.te = t_ends; op.w = weights;
+        op.loss = loss; op.wtot = w_tot; op.stot = s_tot;
+        launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+    });
+    NFA_CHECK_LAUNCH("distortion_fwd");
+    return NFA_OK;
+}
+
+int nfa_distortion_bwd(const float *weights, const float *t_starts, const float *t_ends, const float *w_tot, const float *s_tot,
+                       const float *g_loss, const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays,
+                       int64_t n_elems, float *grad_weights, float *grad_t_starts, float *grad_t_ends, nfa_stream_t stream)
+{
+    SEG_COMMON_CHECKS("distortion_bwd");
+    if (n_elems == 0) return NFA_OK;
+    NFA_REQUIRE(weights && t_starts && t_ends && w_tot && s_tot && g_loss && (grad_weights || grad_t_starts || grad_t_ends),
+                "distortion_bwd: null pointer");
+    hipStream_t s = as_stream(stream);
+    const bool vec = all_aligned16(weights, t_starts, t_ends, grad_weights, grad_t_starts, grad_t_ends);
+    dispatch_bool(vec, [&](auto V) {
+        DistortionBwdOp<V> op;
+        op.pinfo = packed_info; op.ts = t_starts; op.te = t_ends; op.w = weights;
+        op.wtot = w_tot; op.stot = s_tot; op.gl = g_loss;
+        op.gw = grad_weights; op.gts = grad_t_starts; op.gte = grad_t_ends;
+        launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s);
+    });
+    NFA_CHECK_LAUNCH("distortion_bwd");
     return NFA_OK;
 }
 
