@@ -72,6 +72,28 @@ int nfa_exclusive_cumsum_pairs_stats_i64(const int64_t *cnts, int64_t n, int64_t
 int nfa_pack_info(const int64_t *ray_indices, int64_t n, int64_t n_rays, int64_t *packed_info /*[n_rays,2]*/,
                   int32_t *flags /*[1], set to 1 if unsorted/out of range*/, void *scratch, nfa_stream_t stream);
 
+/* Sample data between the packed layout (packed[n_packed, row], rows of ray r at packed_info[r] = {start, count}) and the
+ * padded one (padded[n_rays, n_per_ray, row]); a row is row_bytes opaque bytes (any dtype, any feature width).  Which
+ * padded slot a packed row belongs to:
+ *   mask NULL   the first min(count, n_per_ray) rows of ray r's chunk are slots 0 .. min(count, n_per_ray) - 1 of row r;
+ *               the rest of the chunk is dropped (nerfacc 0.3's unpack_data).  Chunks must not overlap;
+ *   mask given  (uint8 [n_rays, n_per_ray]) the chunk's rows go to the set slots of row r in row-major order, count ==
+ *               the row's popcount (data[mask]: nerfacc 0.3's pack_data, packed_info from nfa_mask_row_counts and
+ *               nfa_exclusive_cumsum_pairs_i64).
+ * Rows move in the widest chunks of 16, 8, 4, 2 or 1 bytes that row_bytes and both base pointers allow.  Deterministic (no
+ * accumulation); packed rows outside [0, n_packed) are never touched.  The packed pointer may be NULL when n_packed == 0.
+ * nfa_unpack_rows writes every padded slot: slots with no packed row get the pad value (pad_bytes bytes at pad_host,
+ * repeated; pad_bytes 0 = zeros).
+ * nfa_pack_rows writes the packed rows of the chunks: with mask NULL, rows dropped by nfa_unpack_rows get zeros (its
+ * gradient); packed rows that no chunk covers are not written. */
+int nfa_unpack_rows(const void *packed, const int64_t *packed_info /*[n_rays,2]*/, const uint8_t *mask, int64_t n_rays,
+                    int64_t n_per_ray, int64_t n_packed, int64_t row_bytes, const void *pad_host, int32_t pad_bytes,
+                    void *padded, nfa_stream_t stream);
+int nfa_pack_rows(const void *padded, const int64_t *packed_info /*[n_rays,2]*/, const uint8_t *mask, int64_t n_rays,
+                  int64_t n_per_ray, int64_t n_packed, int64_t row_bytes, void *packed, nfa_stream_t stream);
+/* counts[r] = number of nonzero bytes in mask row r (uint8 [n_rows, n_cols]). */
+int nfa_mask_row_counts(const uint8_t *mask, int64_t n_rows, int64_t n_cols, int64_t *counts, nfa_stream_t stream);
+
 /* 1 bit per cell copy of a torch.bool grid [n_cells] (derived cache, never serialised). */
 int nfa_pack_bits(const uint8_t *binaries, int64_t n_cells, uint32_t *bits /*[(n_cells+31)/32]*/, nfa_stream_t stream);
 

@@ -10,7 +10,7 @@ from .estimators.occ_grid import OccGridEstimator
 from .estimators.prop_net import PropNetEstimator
 from .graphs import CapturedStep  # extension (hipGraph replay of fixed-shape steps); not part of the reference's 20 names
 from .grid import ray_aabb_intersect, traverse_grids
-from .pack import pack_info
+from .pack import pack_data, pack_info, unpack_data, unpack_info  # pack_data / unpack_*: nerfacc 0.3 names, not in __all__
 from .pdf import importance_sampling, searchsorted
 from .scan import exclusive_prod, exclusive_sum, inclusive_prod, inclusive_sum
 from .version import __version__

@@ -54,6 +54,9 @@ _SIGS = {
     "nfa_pdf_loss_sum_fwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp],
     "nfa_pdf_loss_mean_bwd": [_vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp],
     "nfa_pack_bits": [_vp, _i64, _vp, _vp],
+    "nfa_unpack_rows": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i32, _vp, _vp],
+    "nfa_pack_rows": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp],
+    "nfa_mask_row_counts": [_vp, _i64, _i64, _vp, _vp],
     "nfa_ray_aabb_intersect": [_vp, _vp, _i64, _vp, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp],
     "nfa_ray_events": [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
     "nfa_traverse_grids": [C.POINTER(TraverseArgs), _vp],

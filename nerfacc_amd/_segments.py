@@ -27,6 +27,7 @@ class SegInfo:
     contiguous: bool             # starts[r+1] == starts[r] + cnts[r]  (flat kernels usable)
     sorted_indices: bool = True  # for infos derived from ray_indices
     n_tiles: int = 0
+    trusted: bool = False        # produced by this package: the chunks tile [0, n_elems) in ray order
 
 
 _ATTR = "_nfa_seg"
@@ -43,7 +44,7 @@ def _build_tiles(packed_info: Tensor, n_elems: int, trusted: bool) -> SegInfo:
         B.call("nfa_seg_build_tiles", B.ptr(packed_info), n_rays, n_elems, tile_elems, n_tiles, B.ptr(tiles), B.ptr(flag),
                B.stream())
         ok = True if trusted else (int(flag.item()) == 0)  # one read-back for foreign packed_info
-    return SegInfo(packed_info, n_rays, n_elems, tiles if ok else None, ok, n_tiles=n_tiles)
+    return SegInfo(packed_info, n_rays, n_elems, tiles if ok else None, ok, n_tiles=n_tiles, trusted=trusted)
 
 
 def seginfo_from_packed(packed_info: Tensor, n_elems: int, trusted: bool = False) -> SegInfo:
