@@ -13,6 +13,10 @@ One "step" = one pass of the hot path over one synthetic batch (cf
 Rank 0 prints ONE JSON line.  Inputs are resident in HBM before the timed region.  Rays shard
 across ranks (independent batches, weak scaling); the only collective is the all-reduce of the
 2-float parameter gradient.
+
+A plain run does only what that line's headline figure needs.  `--full` adds, after the timed
+steps, the per-kernel HIP-event times and roofline, the CPU baseline with the parity check against
+the oracle, and the secondary configurations (cfg 2 variants, test-mode loop, cfg 3, cfg 4 per rank, cfg 5).
 """
 from __future__ import annotations
 
@@ -995,14 +999,18 @@ def main():
                     help="synthetic radiance field: three streaming HIP kernels (bench_csrc/field.hip) or torch elementwise ops")
     ap.add_argument("--bin-rays", default="auto", choices=["auto", "on", "off"],
                     help="estimator.bin_rays: auto = decided from the previous batch's coherence (the default of the library)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the per-kernel times and roofline, the CPU baseline and parity check, and "
+                         "the secondary configurations (each can be left out with its --no-* option); without it the run prints "
+                         "the headline line alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and parity check")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: no per-kernel times, roofline and op table")
     ap.add_argument("--pipelined", action="store_true",
-                    help="also time the K steps with the next batch's traversal prefetched on a second stream (OccGridEstimator."
-                         "prefetch_traversal); off by default since round 4: with that round's walk it measures like the sequential "
-                         "step (1.39-1.45 ms against 1.40-1.44) -- DESIGN.md 6")
+                    help="with --full: also time the K steps with the next batch's traversal prefetched on a second stream "
+                         "(OccGridEstimator.prefetch_traversal); off by default since round 4: with that round's walk it measures "
+                         "like the sequential step (1.39-1.45 ms against 1.40-1.44) -- DESIGN.md 6")
     ap.add_argument("--no-pipelined", action="store_true", help="(accepted for older scripts: the pipelined loop is off unless --pipelined)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary configurations (cfg2 variants, cfg3, cfg5)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary configurations (cfg2 variants, cfg3, cfg5)")
     ap.add_argument("--only", default="", choices=["", "cfg2_compacting", "cfg2_random", "cfg2_testmode", "cfg4_per_rank", "cfg3", "cfg5", "cfg5_testmode"],
                     help="run ONE secondary configuration alone and print its object (for rocprofv3 passes: profiles/<round>_<cfg>_*)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
@@ -1012,6 +1020,10 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.only:
         ap.error("--dump-outputs writes the headline step's outputs; it does not combine with --only")
+    if args.pipelined and not args.full:
+        ap.error("--pipelined adds a loop to the full run: give it with --full")
+    if not args.full:   # a plain run: only what the headline line needs
+        args.no_kernel_timing = args.no_cpu_baseline = args.no_extras = True
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a ROCm GPU (the product path has no CPU fallback)")

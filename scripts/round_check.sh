@@ -10,7 +10,7 @@ timeout -k 10 500 python -m pytest tests -m gpu -x -q > $OUT/${TAG}_tests.log 2>
 tail -3 $OUT/${TAG}_tests.log
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.log 2>&1 || { tail -30 $OUT/${TAG}_smoke.log; exit 1; }
 tail -2 $OUT/${TAG}_smoke.log
-timeout -k 10 500 python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || { tail -30 $OUT/${TAG}_bench.err; exit 1; }
+timeout -k 10 500 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || { tail -30 $OUT/${TAG}_bench.err; exit 1; }
 python -c "
 import json,sys
 d=json.loads(open('$OUT/${TAG}_bench.json').read().strip().splitlines()[-1])

@@ -1597,7 +1597,7 @@ def test_cfg5_regime_test_mode_loop(dev, oracle):
 def test_full_size_bit_exact_vs_oracle(dev, oracle):
     """BASELINE cfg 2 at FULL size (1024x1024 image rays, 128^3 shell10 grid, step 2 sqrt(3)/1024): the sampler's
     (ray_indices, t_starts, t_ends) and packed_info bit for bit against the oracle, colours of rendering() within 1e-5.
-    The same comparison runs inside bench.py after the timed loops (`parity_checked`)."""
+    The same comparison runs inside `bench.py --full` after the timed loops (`parity_checked`)."""
     import bench
     from oracle import check as OC
     w = bench.make_workload(dev, n_rays=1024 * 1024, res=128)
