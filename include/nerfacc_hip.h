@@ -561,6 +561,34 @@ int nfa_opencv_lens_undistortion_fisheye(const float *uv, const float *params, i
                                          int64_t param_stride, float eps, int32_t iters, float *uv_out,
                                          nfa_stream_t stream);
 
+/* ------------------------------------------------------------------ input encodings */
+
+/* tiny-cuda-nn's `HashGrid` encoding (Instant-NGP's multiresolution hash grid, Mueller et al. 2022) with 3-D input and
+ * linear interpolation; the formulas are those of csrc/encoding.hip's header.  x [n_points, 3], y [n_points, n_levels *
+ * n_features], params the flat [sum(sizes) * n_features] table laid out [level][entry][feature].  The level table
+ * (n_levels entries each, host memory) is computed by the caller in float32: scale_l = exp2f(l log2f(per_level_scale)) *
+ * base_resolution - 1, resolution_l = ceil(scale_l) + 1, size_l = min(roundup8(resolution_l^3), 2^log2_hashmap_size);
+ * a size that does not follow from the resolution is rejected.  n_features 1, 2, 4 or 8, n_levels 1..32,
+ * log2_hashmap_size 10..24, n_params = sum(sizes) * n_features < 2^31.  Every index is reduced modulo the level's size,
+ * so any input (non-finite included) stays inside the table. */
+int nfa_hashgrid_fwd(const float *x, const float *params, int64_t n_points, int32_t n_levels, int32_t n_features,
+                     int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                     const int32_t *sizes_host, int64_t n_params, float *y, nfa_stream_t stream);
+/* Backward of nfa_hashgrid_fwd given grad_y [n_points, n_levels * n_features]: grad_params (optional, ZEROED by the
+ * caller) receives the scatter of w_c * grad_y through float atomics (the order of the adds is not fixed); grad_x
+ * (optional, needs params) [n_points, 3] is written, summed over levels in level order (bitwise reproducible).  At
+ * least one of the two is given. */
+int nfa_hashgrid_bwd(const float *x, const float *params, const float *grad_y, int64_t n_points, int32_t n_levels,
+                     int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                     const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
+                     float *grad_x, nfa_stream_t stream);
+/* tiny-cuda-nn's `SphericalHarmonics` encoding: directions dirs [n_points, 3] in [0, 1]^3, u = 2 dirs - 1 (not
+ * renormalised), degree 1..4, out [n_points, degree^2] (16-byte aligned) with Instant-NGP's real SH basis and constants.
+ * The backward writes grad_dirs [n_points, 3] from grad_out [n_points, degree^2] (16-byte aligned). */
+int nfa_sh_fwd(const float *dirs, int64_t n_points, int32_t degree, float *out, nfa_stream_t stream);
+int nfa_sh_bwd(const float *dirs, const float *grad_out, int64_t n_points, int32_t degree, float *grad_dirs,
+               nfa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,10 @@ _SIGS = {
     "nfa_searchsorted": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp],
     "nfa_opencv_lens_undistortion": [_vp, _vp, _i64, _i32, _i64, _f32, _i32, _vp, _vp],
     "nfa_opencv_lens_undistortion_fisheye": [_vp, _vp, _i64, _i32, _i64, _f32, _i32, _vp, _vp],
+    "nfa_hashgrid_fwd": [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
+    "nfa_hashgrid_bwd": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "nfa_sh_fwd": [_vp, _i64, _i32, _vp, _vp],
+    "nfa_sh_bwd": [_vp, _vp, _i64, _i32, _vp, _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],

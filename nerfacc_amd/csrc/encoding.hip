@@ -1,0 +1,457 @@
+// encoding.hip -- input encodings of Instant-NGP radiance fields: the multiresolution hash grid (D = 3, linear
+// interpolation) and the spherical-harmonics direction encoding, as tiny-cuda-nn's `HashGrid` and `SphericalHarmonics`
+// define them (Mueller et al. 2022, "Instant Neural Graphics Primitives", sec. 3).
+//
+// Hash grid, per point x and level l (all integer arithmetic uint32, wrapping):
+//   p_d = x_d * scale_l + 0.5 (a multiply, then an add: the library builds with -ffp-contract=off)
+//   g_d = (uint32)(int32)floor(p_d) (floor clamped to [-2^31, 2^31 - 128] first, so every finite input converts),
+//   f_d = p_d - floor(p_d)
+//   corner c = c0 + 2 c1 + 4 c2 in the order 0..7, q_d = g_d + c_d:
+//     dense level:  idx = (q0 + q1 res + q2 res^2) mod size_l
+//     hashed level: idx = (q0 ^ q1 * 2654435761 ^ q2 * 805459861) & (size_l - 1)
+//     w_c = ((c0 ? f0 : 1 - f0) * (c1 ? f1 : 1 - f1)) * (c2 ? f2 : 1 - f2)
+//   y[n, l F + j] = sum_c w_c params[(offset_l + idx_c) F + j], summed from 0 in corner order.
+// Every index is reduced modulo the level's size, so any input (NaN and inf included) reads and writes inside the table.
+// nerfacc_amd/encodings.py restates the same operations in torch, bit for bit.
+//
+// Layout: the forward runs one level per workgroup row and one lane per point; the backward one lane per (point, level),
+// the level varying fastest inside a wave, so a wave covers 64 / L points x all L levels (64 mod L lanes idle).  A
+// corner's F features are one vector load (F = 2: float2).  The per-level constants are a kernarg table.
+// The backward scatters w_c * dL/dy with no-return global_atomic_add_f32 into a zeroed float32 table gradient; dL/dx
+// (optional) is formed per (point, level) and summed over the point's levels in level order across lanes, so it is
+// bitwise reproducible.
+#include "common.hip.h"
+
+namespace nfa {
+
+#define NFA_HG_MAX_LEVELS 32
+
+struct HashGridLevels {
+    float scale[NFA_HG_MAX_LEVELS];
+    uint32_t res[NFA_HG_MAX_LEVELS];
+    uint32_t offset[NFA_HG_MAX_LEVELS];   // in entries
+    uint32_t size[NFA_HG_MAX_LEVELS];     // in entries; a power of two on hashed levels
+    uint32_t hashed;                      // bit l: level l is hashed
+    int32_t n_levels;
+    int32_t pts_per_wave;                 // 64 / n_levels
+};
+
+template <int F> struct FVec;
+template <> struct FVec<1> { float v[1]; };
+template <> struct FVec<2> { float v[2]; } __attribute__((aligned(8)));
+template <> struct FVec<4> { float v[4]; } __attribute__((aligned(16)));
+template <> struct FVec<8> { float v[8]; } __attribute__((aligned(16)));
+
+struct Cell {
+    uint32_t g[3];
+    float f[3];
+};
+
+__device__ __forceinline__ Cell locate(const float *__restrict__ xp, float scale)
+{
+    Cell c;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float p = xp[d] * scale + 0.5f;
+        const float fl = floorf(p);
+        c.f[d] = p - fl;
+        const float cl = fminf(fmaxf(fl, -2147483648.0f), 2147483520.0f);   // NaN -> -2^31
+        c.g[d] = (uint32_t)(int32_t)cl;
+    }
+    return c;
+}
+
+__device__ __forceinline__ uint32_t corner_index(const Cell &c, int corner, bool hashed, uint32_t res, uint32_t size)
+{
+    const uint32_t q0 = c.g[0] + (corner & 1), q1 = c.g[1] + ((corner >> 1) & 1), q2 = c.g[2] + ((corner >> 2) & 1);
+    if (hashed) return (q0 ^ (q1 * 2654435761u) ^ (q2 * 805459861u)) & (size - 1u);
+    return (q0 + q1 * res + q2 * (res * res)) % size;
+}
+
+__device__ __forceinline__ float corner_factor(const Cell &c, int corner, int d)
+{
+    return ((corner >> d) & 1) ? c.f[d] : 1.0f - c.f[d];
+}
+
+// (point, level) of this lane; false for the idle lanes of a wave
+__device__ __forceinline__ bool lane_item(const HashGridLevels &T, int64_t wave, int64_t n_points, int64_t &n, int &l)
+{
+    const int lane = (int)(threadIdx.x & 63);
+    const int p = lane / T.n_levels;
+    l = lane - p * T.n_levels;
+    n = wave * T.pts_per_wave + p;
+    return p < T.pts_per_wave && n < n_points;
+}
+
+// Forward: one level per workgroup row (blockIdx.y), one lane per point.  A wave's 64 points read one level's table, which
+// stays in one XCD's L2 (4 MiB: a hashed level of the NGP grid), and write their F-float pieces at a stride of L F floats.
+// Measured against one lane per (point, level) with the level fastest in the wave (coalesced output rows): 0.83-0.90 of
+// its time at 2^20 points (DESIGN.md "Input encodings").
+template <int F>
+__global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const float *__restrict__ x, const float *__restrict__ params,
+                                                           int64_t n_points, const HashGridLevels T, float *__restrict__ y)
+{
+    const int l = (int)blockIdx.y;
+    const bool hashed = (T.hashed >> l) & 1u;
+    const uint32_t res = T.res[l], size = T.size[l];
+    const float scale = T.scale[l];
+    const FVec<F> *tab = reinterpret_cast<const FVec<F> *>(params) + T.offset[l];
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < n_points; n += stride) {
+        const Cell c = locate(x + n * 3, scale);
+        float acc[F];
+#pragma unroll
+        for (int j = 0; j < F; ++j) acc[j] = 0.0f;
+#pragma unroll
+        for (int corner = 0; corner < 8; ++corner) {
+            const FVec<F> v = tab[corner_index(c, corner, hashed, res, size)];
+            const float wc = (corner_factor(c, corner, 0) * corner_factor(c, corner, 1)) * corner_factor(c, corner, 2);
+#pragma unroll
+            for (int j = 0; j < F; ++j) acc[j] = acc[j] + wc * v.v[j];
+        }
+        FVec<F> out;
+#pragma unroll
+        for (int j = 0; j < F; ++j) out.v[j] = acc[j];
+        reinterpret_cast<FVec<F> *>(y)[n * T.n_levels + l] = out;
+    }
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restrict__ x, const float *__restrict__ params,
+                                                           const float *__restrict__ g_y, int64_t n_points,
+                                                           const HashGridLevels T, float *__restrict__ g_params,
+                                                           float *__restrict__ g_x)
+{
+    const int64_t n_waves = ceil_div64(n_points, T.pts_per_wave);
+    const int64_t wave_stride = (int64_t)gridDim.x * (blockDim.x / 64);
+    for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / 64; w < n_waves; w += wave_stride) {
+        int64_t n;
+        int l;
+        const bool active = lane_item(T, w, n_points, n, l);
+        float dx[3] = {0.0f, 0.0f, 0.0f};
+        if (active) {
+            const Cell c = locate(x + n * 3, T.scale[l]);
+            const bool hashed = (T.hashed >> l) & 1u;
+            const uint32_t res = T.res[l], size = T.size[l];
+            const FVec<F> g = reinterpret_cast<const FVec<F> *>(g_y)[n * T.n_levels + l];
+            const uint32_t base = T.offset[l];
+#pragma unroll
+            for (int corner = 0; corner < 8; ++corner) {
+                const uint32_t e = base + corner_index(c, corner, hashed, res, size);
+                if (g_params) {
+                    const float wc = (corner_factor(c, corner, 0) * corner_factor(c, corner, 1)) * corner_factor(c, corner, 2);
+                    float *dst = g_params + (size_t)e * F;
+#pragma unroll
+                    for (int j = 0; j < F; ++j) unsafeAtomicAdd(dst + j, wc * g.v[j]);
+                }
+                if (g_x) {
+                    const FVec<F> v = reinterpret_cast<const FVec<F> *>(params)[e];
+                    float dot = 0.0f;
+#pragma unroll
+                    for (int j = 0; j < F; ++j) dot = dot + g.v[j] * v.v[j];
+                    const float f0 = corner_factor(c, corner, 0), f1 = corner_factor(c, corner, 1),
+                                f2 = corner_factor(c, corner, 2);
+                    const float t0 = (f1 * f2) * dot, t1 = (f0 * f2) * dot, t2 = (f0 * f1) * dot;
+                    dx[0] = (corner & 1) ? dx[0] + t0 : dx[0] - t0;
+                    dx[1] = (corner & 2) ? dx[1] + t1 : dx[1] - t1;
+                    dx[2] = (corner & 4) ? dx[2] + t2 : dx[2] - t2;
+                }
+            }
+            if (g_x) {
+                const float s = T.scale[l];
+                dx[0] *= s; dx[1] *= s; dx[2] *= s;
+            }
+        }
+        if (g_x) {
+            // sum over the point's L lanes in level order; the level-0 lane writes (wave-uniform branch)
+            const int lane = (int)(threadIdx.x & 63);
+            const int first = lane - l;
+            float s[3] = {0.0f, 0.0f, 0.0f};
+            for (int k = 0; k < T.n_levels; ++k) {
+                const int src = min(first + k, 63);
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    const float v = __shfl(dx[d], src, 64);
+                    s[d] = k == 0 ? v : s[d] + v;
+                }
+            }
+            if (active && l == 0) {
+                g_x[n * 3 + 0] = s[0];
+                g_x[n * 3 + 1] = s[1];
+                g_x[n * 3 + 2] = s[2];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- spherical harmonics
+// tiny-cuda-nn's convention: directions d in [0, 1]^3, u = 2 d - 1 (not renormalised); degree^2 outputs per point.
+#define SH_C0 0.28209479177387814f
+#define SH_C1 0.48860251190291987f
+#define SH_C2A 1.0925484305920792f
+#define SH_C2B 0.94617469575755997f
+#define SH_C2C 0.31539156525251999f
+#define SH_C2D 0.54627421529603959f
+#define SH_C3A 0.59004358992664352f
+#define SH_C3B 2.8906114426405538f
+#define SH_C3C 0.45704579946446572f
+#define SH_C3D 0.3731763325901154f
+#define SH_C3E 1.4453057213202769f
+
+template <int DEG>
+__device__ __forceinline__ void sh_eval(float x, float y, float z, float *o)
+{
+    o[0] = SH_C0;
+    if constexpr (DEG > 1) {
+        o[1] = -SH_C1 * y;
+        o[2] = SH_C1 * z;
+        o[3] = -SH_C1 * x;
+    }
+    if constexpr (DEG > 2) {
+        const float xy = x * y, yz = y * z, xz = x * z, x2 = x * x, y2 = y * y, z2 = z * z;
+        o[4] = SH_C2A * xy;
+        o[5] = -SH_C2A * yz;
+        o[6] = SH_C2B * z2 - SH_C2C;
+        o[7] = -SH_C2A * xz;
+        o[8] = SH_C2D * (x2 - y2);
+        if constexpr (DEG > 3) {
+            o[9] = SH_C3A * y * (-3.0f * x2 + y2);
+            o[10] = SH_C3B * xy * z;
+            o[11] = SH_C3C * y * (1.0f - 5.0f * z2);
+            o[12] = SH_C3D * z * (5.0f * z2 - 3.0f);
+            o[13] = SH_C3C * x * (1.0f - 5.0f * z2);
+            o[14] = SH_C3E * z * (x2 - y2);
+            o[15] = SH_C3A * x * (-x2 + 3.0f * y2);
+        }
+    }
+}
+
+// dL/du of sum_k g_k Y_k(u)
+template <int DEG>
+__device__ __forceinline__ void sh_grad(float x, float y, float z, const float *g, float *du)
+{
+    float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    if constexpr (DEG > 1) {
+        gy += -SH_C1 * g[1];
+        gz += SH_C1 * g[2];
+        gx += -SH_C1 * g[3];
+    }
+    if constexpr (DEG > 2) {
+        gx += SH_C2A * y * g[4];
+        gy += SH_C2A * x * g[4];
+        gy += -SH_C2A * z * g[5];
+        gz += -SH_C2A * y * g[5];
+        gz += 2.0f * SH_C2B * z * g[6];
+        gx += -SH_C2A * z * g[7];
+        gz += -SH_C2A * x * g[7];
+        gx += 2.0f * SH_C2D * x * g[8];
+        gy += -2.0f * SH_C2D * y * g[8];
+        if constexpr (DEG > 3) {
+            const float x2 = x * x, y2 = y * y, z2 = z * z;
+            gx += -6.0f * SH_C3A * x * y * g[9];
+            gy += SH_C3A * (-3.0f * x2 + 3.0f * y2) * g[9];
+            gx += SH_C3B * y * z * g[10];
+            gy += SH_C3B * x * z * g[10];
+            gz += SH_C3B * x * y * g[10];
+            gy += SH_C3C * (1.0f - 5.0f * z2) * g[11];
+            gz += -10.0f * SH_C3C * y * z * g[11];
+            gz += SH_C3D * (15.0f * z2 - 3.0f) * g[12];
+            gx += SH_C3C * (1.0f - 5.0f * z2) * g[13];
+            gz += -10.0f * SH_C3C * x * z * g[13];
+            gx += 2.0f * SH_C3E * x * z * g[14];
+            gy += -2.0f * SH_C3E * y * z * g[14];
+            gz += SH_C3E * (x2 - y2) * g[14];
+            gx += SH_C3A * (-3.0f * x2 + 3.0f * y2) * g[15];
+            gy += 6.0f * SH_C3A * x * y * g[15];
+        }
+    }
+    du[0] = gx;
+    du[1] = gy;
+    du[2] = gz;
+}
+
+// Row of K floats: float4 pieces when K is a multiple of 4 (rows stay 16-byte aligned), single floats otherwise.
+template <int K>
+__device__ __forceinline__ void store_row(float *dst, const float *v)
+{
+    if constexpr (K % 4 == 0) {
+#pragma unroll
+        for (int k = 0; k < K; k += 4) reinterpret_cast<float4 *>(dst)[k / 4] = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < K; ++k) dst[k] = v[k];
+    }
+}
+template <int K>
+__device__ __forceinline__ void load_row(const float *src, float *v)
+{
+    if constexpr (K % 4 == 0) {
+#pragma unroll
+        for (int k = 0; k < K; k += 4) {
+            const float4 q = reinterpret_cast<const float4 *>(src)[k / 4];
+            v[k] = q.x; v[k + 1] = q.y; v[k + 2] = q.z; v[k + 3] = q.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < K; ++k) v[k] = src[k];
+    }
+}
+
+template <int DEG>
+__global__ __launch_bounds__(256) void sh_fwd_kernel(const float *__restrict__ dirs, int64_t n, float *__restrict__ out)
+{
+    constexpr int K = DEG * DEG;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float x = 2.0f * dirs[i * 3 + 0] - 1.0f, y = 2.0f * dirs[i * 3 + 1] - 1.0f, z = 2.0f * dirs[i * 3 + 2] - 1.0f;
+        float o[K];
+        sh_eval<DEG>(x, y, z, o);
+        store_row<K>(out + i * K, o);
+    }
+}
+
+template <int DEG>
+__global__ __launch_bounds__(256) void sh_bwd_kernel(const float *__restrict__ dirs, const float *__restrict__ g_out,
+                                                     int64_t n, float *__restrict__ g_dirs)
+{
+    constexpr int K = DEG * DEG;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float x = 2.0f * dirs[i * 3 + 0] - 1.0f, y = 2.0f * dirs[i * 3 + 1] - 1.0f, z = 2.0f * dirs[i * 3 + 2] - 1.0f;
+        float g[K], du[3];
+        load_row<K>(g_out + i * K, g);
+        sh_grad<DEG>(x, y, z, g, du);
+        g_dirs[i * 3 + 0] = 2.0f * du[0];   // du / dd = 2
+        g_dirs[i * 3 + 1] = 2.0f * du[1];
+        g_dirs[i * 3 + 2] = 2.0f * du[2];
+    }
+}
+
+// ---------------------------------------------------------------- argument checks
+static int hashgrid_table(const char *name, int64_t n_points, int32_t n_levels, int32_t n_features,
+                          int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                          const int32_t *sizes_host, int64_t n_params, HashGridLevels &T)
+{
+    NFA_REQUIRE(n_points >= 0 && n_params >= 0, "%s: negative size", name);
+    NFA_REQUIRE(n_features == 1 || n_features == 2 || n_features == 4 || n_features == 8,
+                "%s: n_features must be 1, 2, 4 or 8 (got %d)", name, n_features);
+    NFA_REQUIRE(n_levels >= 1 && n_levels <= NFA_HG_MAX_LEVELS, "%s: n_levels must be in 1..32 (got %d)", name, n_levels);
+    NFA_REQUIRE(log2_hashmap_size >= 10 && log2_hashmap_size <= 24, "%s: log2_hashmap_size must be in 10..24 (got %d)",
+                name, log2_hashmap_size);
+    NFA_REQUIRE(n_params < ((int64_t)1 << 31), "%s: too many parameters (%lld)", name, (long long)n_params);
+    NFA_REQUIRE(scales_host && resolutions_host && sizes_host, "%s: null level table", name);
+    const int64_t table = (int64_t)1 << log2_hashmap_size;
+    int64_t offset = 0;
+    T = {};
+    for (int l = 0; l < n_levels; ++l) {
+        const int64_t r = resolutions_host[l], s = sizes_host[l];
+        NFA_REQUIRE(r >= 1, "%s: level %d resolution %lld out of range", name, l, (long long)r);
+        const int64_t dense = r > (1 << 20) ? INT64_MAX : (r * r * r + 7) / 8 * 8;   // (no overflow; hashed anyway)
+        NFA_REQUIRE(s == (dense < table ? dense : table), "%s: level %d size %lld is not min(roundup8(res^3), 2^%d)",
+                    name, l, (long long)s, log2_hashmap_size);
+        T.scale[l] = scales_host[l];
+        T.res[l] = (uint32_t)r;
+        T.offset[l] = (uint32_t)offset;
+        T.size[l] = (uint32_t)s;
+        if (dense > table) T.hashed |= 1u << l;
+        offset += s;
+    }
+    NFA_REQUIRE(offset * n_features == n_params, "%s: n_params %lld != %lld entries x %d features", name,
+                (long long)n_params, (long long)offset, n_features);
+    T.n_levels = n_levels;
+    T.pts_per_wave = 64 / n_levels;
+    return NFA_OK;
+}
+
+static unsigned hashgrid_grid(int64_t n_points, const HashGridLevels &T)
+{
+    return grid_1d(ceil_div64(n_points, T.pts_per_wave) * 64, 256);
+}
+
+}  // namespace nfa
+
+using namespace nfa;
+
+int nfa_hashgrid_fwd(const float *x, const float *params, int64_t n_points, int32_t n_levels, int32_t n_features,
+                     int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                     const int32_t *sizes_host, int64_t n_params, float *y, nfa_stream_t stream)
+{
+    HashGridLevels T;
+    const int rc = hashgrid_table("hashgrid_fwd", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                                  resolutions_host, sizes_host, n_params, T);
+    if (rc != NFA_OK) return rc;
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(x && params && y, "hashgrid_fwd: null pointer");
+    hipStream_t s = as_stream(stream);
+    const dim3 grid(grid_1d(n_points, 256, 256 * 16 / n_levels + 1), n_levels), block(256);
+    switch (n_features) {
+    case 1: hipLaunchKernelGGL(hashgrid_fwd_kernel<1>, grid, block, 0, s, x, params, n_points, T, y); break;
+    case 2: hipLaunchKernelGGL(hashgrid_fwd_kernel<2>, grid, block, 0, s, x, params, n_points, T, y); break;
+    case 4: hipLaunchKernelGGL(hashgrid_fwd_kernel<4>, grid, block, 0, s, x, params, n_points, T, y); break;
+    default: hipLaunchKernelGGL(hashgrid_fwd_kernel<8>, grid, block, 0, s, x, params, n_points, T, y); break;
+    }
+    NFA_CHECK_LAUNCH("hashgrid_fwd");
+    return NFA_OK;
+}
+
+int nfa_hashgrid_bwd(const float *x, const float *params, const float *grad_y, int64_t n_points, int32_t n_levels,
+                     int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                     const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
+                     float *grad_x, nfa_stream_t stream)
+{
+    HashGridLevels T;
+    const int rc = hashgrid_table("hashgrid_bwd", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                                  resolutions_host, sizes_host, n_params, T);
+    if (rc != NFA_OK) return rc;
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(x && grad_y && (grad_params || grad_x) && (params || !grad_x), "hashgrid_bwd: null pointer");
+    const dim3 grid(hashgrid_grid(n_points, T)), block(256);
+    hipStream_t s = as_stream(stream);
+    switch (n_features) {
+    case 1: hipLaunchKernelGGL(hashgrid_bwd_kernel<1>, grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
+    case 2: hipLaunchKernelGGL(hashgrid_bwd_kernel<2>, grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
+    case 4: hipLaunchKernelGGL(hashgrid_bwd_kernel<4>, grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
+    default: hipLaunchKernelGGL(hashgrid_bwd_kernel<8>, grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
+    }
+    NFA_CHECK_LAUNCH("hashgrid_bwd");
+    return NFA_OK;
+}
+
+int nfa_sh_fwd(const float *dirs, int64_t n_points, int32_t degree, float *out, nfa_stream_t stream)
+{
+    NFA_REQUIRE(n_points >= 0, "sh_fwd: negative size");
+    NFA_REQUIRE(degree >= 1 && degree <= 4, "sh_fwd: degree must be in 1..4 (got %d)", degree);
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(dirs && out, "sh_fwd: null pointer");
+    NFA_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0, "sh_fwd: out must be 16-byte aligned");
+    const dim3 grid(grid_1d(n_points, 256)), block(256);
+    hipStream_t s = as_stream(stream);
+    switch (degree) {
+    case 1: hipLaunchKernelGGL(sh_fwd_kernel<1>, grid, block, 0, s, dirs, n_points, out); break;
+    case 2: hipLaunchKernelGGL(sh_fwd_kernel<2>, grid, block, 0, s, dirs, n_points, out); break;
+    case 3: hipLaunchKernelGGL(sh_fwd_kernel<3>, grid, block, 0, s, dirs, n_points, out); break;
+    default: hipLaunchKernelGGL(sh_fwd_kernel<4>, grid, block, 0, s, dirs, n_points, out); break;
+    }
+    NFA_CHECK_LAUNCH("sh_fwd");
+    return NFA_OK;
+}
+
+int nfa_sh_bwd(const float *dirs, const float *grad_out, int64_t n_points, int32_t degree, float *grad_dirs,
+               nfa_stream_t stream)
+{
+    NFA_REQUIRE(n_points >= 0, "sh_bwd: negative size");
+    NFA_REQUIRE(degree >= 1 && degree <= 4, "sh_bwd: degree must be in 1..4 (got %d)", degree);
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(dirs && grad_out && grad_dirs, "sh_bwd: null pointer");
+    NFA_REQUIRE(reinterpret_cast<uintptr_t>(grad_out) % 16 == 0, "sh_bwd: grad_out must be 16-byte aligned");
+    const dim3 grid(grid_1d(n_points, 256)), block(256);
+    hipStream_t s = as_stream(stream);
+    switch (degree) {
+    case 1: hipLaunchKernelGGL(sh_bwd_kernel<1>, grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
+    case 2: hipLaunchKernelGGL(sh_bwd_kernel<2>, grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
+    case 3: hipLaunchKernelGGL(sh_bwd_kernel<3>, grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
+    default: hipLaunchKernelGGL(sh_bwd_kernel<4>, grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
+    }
+    NFA_CHECK_LAUNCH("sh_bwd");
+    return NFA_OK;
+}

@@ -1,0 +1,312 @@
+"""Input encodings of Instant-NGP radiance fields (native kernels: csrc/encoding.hip).
+
+``HashGridEncoding`` and ``SphericalHarmonicsEncoding`` stand for tiny-cuda-nn's ``HashGrid`` (3-D input, linear
+interpolation) and ``SphericalHarmonics`` encodings, the two encodings nerfacc's example radiance fields
+(``examples/radiance_fields/ngp.py``: ``NGPRadianceField``, ``NGPDensityField``) are built on; the MLPs around them are
+plain ``torch.nn`` layers.  ``encoding_from_tcnn_config`` builds them from the config dicts those examples pass to tcnn.
+Parameter layout compatibility with tcnn checkpoints is not a goal.
+
+CUDA float32 tensors run on libnerfacc_hip.so; CPU tensors and other dtypes run the same formulas in torch (the hash grid's
+torch path reproduces the native forward bit for bit).  Under ``torch.autocast`` both encodings run in float32, as tcnn's
+do.  Neither direction reads from the device, so a step that uses them can be captured (``CapturedStep``).
+
+Not part of ``nerfacc_amd.__all__`` (that list mirrors the reference's exactly); import the module.
+"""
+from __future__ import annotations
+
+import ctypes
+import ctypes.util
+import math
+
+import numpy as np
+import torch
+from torch import Tensor, nn
+from torch.autograd.function import once_differentiable
+
+from . import _backend as B
+
+__all__ = ["HashGridEncoding", "SphericalHarmonicsEncoding", "encoding_from_tcnn_config"]
+
+_M32 = 0xFFFFFFFF
+_PRIMES = (2654435761, 805459861)   # tcnn's hash primes of dimensions 1 and 2 (dimension 0: 1)
+
+_libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+_libm.exp2f.restype = ctypes.c_float
+_libm.exp2f.argtypes = [ctypes.c_float]
+_libm.log2f.restype = ctypes.c_float
+_libm.log2f.argtypes = [ctypes.c_float]
+
+
+class LevelTable:
+    """Per-level constants of a hash grid, computed once on the host in float32 (the C library's exp2f / log2f):
+
+        scale_l = exp2f(l * log2f(per_level_scale)) * base_resolution - 1,   res_l = ceil(scale_l) + 1,
+        size_l = min(roundup8(res_l^3), 2^log2_hashmap_size) (hashed when the dense size is larger),
+        offset_l = sum of the sizes of the levels before l.
+    """
+
+    def __init__(self, n_levels: int, log2_hashmap_size: int, base_resolution: float, per_level_scale: float):
+        f32 = np.float32
+        lg = f32(_libm.log2f(float(f32(per_level_scale))))
+        self.scales, self.resolutions, self.sizes, self.offsets, self.hashed = [], [], [], [], []
+        table, offset = 1 << int(log2_hashmap_size), 0
+        for l in range(int(n_levels)):
+            e = f32(f32(l) * lg)
+            s = f32(f32(_libm.exp2f(float(e))) * f32(base_resolution)) - f32(1.0)
+            r = int(math.ceil(float(s))) + 1
+            dense = (r ** 3 + 7) // 8 * 8
+            self.scales.append(float(s))
+            self.resolutions.append(r)
+            self.sizes.append(min(dense, table))
+            self.hashed.append(dense > table)
+            self.offsets.append(offset)
+            offset += self.sizes[-1]
+        self.n_entries = offset
+        self.log2_hashmap_size = int(log2_hashmap_size)
+        # host arrays handed to nfa_hashgrid_{fwd,bwd} (read synchronously by each call)
+        self.c_scales = (ctypes.c_float * len(self.scales))(*self.scales)
+        self.c_res = (ctypes.c_int32 * len(self.scales))(*[min(r, 1 << 30) for r in self.resolutions])
+        self.c_sizes = (ctypes.c_int32 * len(self.scales))(*self.sizes)
+
+
+def _hashgrid_torch(x: Tensor, params: Tensor, t: LevelTable, n_features: int) -> Tensor:
+    """The hash grid in torch, op for op as csrc/encoding.hip computes it (x [N, 3] and params in one float dtype)."""
+    F = n_features
+    table = params.view(-1, F)
+    outs = []
+    for l in range(len(t.scales)):
+        p = x * t.scales[l] + 0.5   # (a float32 value: exact in x's dtype)
+        fl = torch.floor(p)
+        f = p - fl
+        g = fl.detach().clamp(-2147483648.0, 2147483520.0).to(torch.int64) & _M32
+        lvl = table[t.offsets[l]: t.offsets[l] + t.sizes[l]]
+        size, res = t.sizes[l], t.resolutions[l]
+        acc = torch.zeros(x.shape[0], F, dtype=x.dtype, device=x.device)
+        for c in range(8):
+            b = [(c >> d) & 1 for d in range(3)]
+            q = [(g[:, d] + b[d]) & _M32 for d in range(3)]
+            if t.hashed[l]:
+                idx = (q[0] ^ ((q[1] * _PRIMES[0]) & _M32) ^ ((q[2] * _PRIMES[1]) & _M32)) & (size - 1)
+            else:
+                idx = ((q[0] + q[1] * res + q[2] * (res * res & _M32)) & _M32) % size
+            w = [f[:, d] if b[d] else 1.0 - f[:, d] for d in range(3)]
+            wc = (w[0] * w[1]) * w[2]
+            acc = acc + wc[:, None] * lvl[idx]
+        outs.append(acc)
+    return torch.cat(outs, -1)
+
+
+def _aligned16(t: Tensor) -> Tensor:
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _HashGridFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, params, enc: "HashGridEncoding"):
+        B.require_device(x, params)
+        t, L, F = enc.table, enc.n_levels, enc.n_features_per_level
+        N = x.shape[0]
+        y = torch.empty(N, L * F, dtype=torch.float32, device=x.device)
+        if N:
+            with torch.cuda.device(x.device):
+                B.call("nfa_hashgrid_fwd", B.ptr(x), B.ptr(params), N, L, F, t.log2_hashmap_size, t.c_scales, t.c_res,
+                       t.c_sizes, params.numel(), B.ptr(y), B.stream())
+        ctx.enc = enc
+        ctx.save_for_backward(x, params)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_y):
+        need_x, need_p = ctx.needs_input_grad[:2]
+        if g_y is None or not (need_x or need_p):
+            return None, None, None
+        x, params = ctx.saved_tensors
+        enc = ctx.enc
+        t, L, F = enc.table, enc.n_levels, enc.n_features_per_level
+        g = _aligned16(g_y.to(torch.float32))
+        g_p = torch.zeros_like(params) if need_p else None
+        g_x = torch.empty_like(x) if need_x else None
+        if x.shape[0]:
+            with torch.cuda.device(x.device):
+                B.call("nfa_hashgrid_bwd", B.ptr(x), B.ptr(params), B.ptr(g), x.shape[0], L, F, t.log2_hashmap_size,
+                       t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(g_p), B.ptr(g_x), B.stream())
+        return g_x, g_p, None
+
+
+class _SHFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dirs, degree: int):
+        B.require_device(dirs)
+        N = dirs.shape[0]
+        out = torch.empty(N, degree * degree, dtype=torch.float32, device=dirs.device)
+        if N:
+            with torch.cuda.device(dirs.device):
+                B.call("nfa_sh_fwd", B.ptr(dirs), N, degree, B.ptr(out), B.stream())
+        ctx.degree = degree
+        ctx.save_for_backward(dirs)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        if g_out is None or not ctx.needs_input_grad[0]:
+            return None, None
+        (dirs,) = ctx.saved_tensors
+        g = _aligned16(g_out.to(torch.float32))
+        g_d = torch.empty_like(dirs)
+        if dirs.shape[0]:
+            with torch.cuda.device(dirs.device):
+                B.call("nfa_sh_bwd", B.ptr(dirs), B.ptr(g), dirs.shape[0], ctx.degree, B.ptr(g_d), B.stream())
+        return g_d, None
+
+
+def _autocast_off(x: Tensor):
+    """(x as the encodings see it, a context that disables autocast): float32 inputs under autocast, like tcnn's
+    ``custom_fwd(cast_inputs=torch.float32)``."""
+    dt = x.device.type
+    if torch.is_autocast_enabled(dt) and x.is_floating_point():
+        x = x.float()
+    return x, torch.autocast(dt, enabled=False)
+
+
+class HashGridEncoding(nn.Module):
+    """tiny-cuda-nn's ``HashGrid`` encoding with 3-D input and linear interpolation: ``forward(x[..., 3]) -> [...,
+    n_levels * n_features_per_level]``, level-major (output ``l * F + j`` is feature ``j`` of level ``l``).
+
+    ``params`` is one flat float32 table of ``sum(sizes) * F`` values laid out ``[level][entry][feature]``, initialised
+    uniform in +-1e-4.  ``scales``, ``resolutions``, ``offsets`` and ``sizes`` are the per-level constants
+    (:class:`LevelTable`).  Inputs outside [0, 1] are legal (every index wraps into its level); results for non-finite
+    inputs are unspecified.  Differentiable w.r.t. ``params`` and ``x``.
+    """
+
+    def __init__(self, n_input_dims: int = 3, n_levels: int = 16, n_features_per_level: int = 2,
+                 log2_hashmap_size: int = 19, base_resolution: float = 16, per_level_scale: float = 2.0):
+        super().__init__()
+        if n_input_dims != 3:
+            raise ValueError(f"HashGridEncoding: only 3 input dimensions are supported (got {n_input_dims})")
+        if n_features_per_level not in (1, 2, 4, 8):
+            raise ValueError(f"HashGridEncoding: n_features_per_level must be 1, 2, 4 or 8 (got {n_features_per_level})")
+        if not 1 <= n_levels <= 32:
+            raise ValueError(f"HashGridEncoding: n_levels must be in 1..32 (got {n_levels})")
+        if not 10 <= log2_hashmap_size <= 24:
+            raise ValueError(f"HashGridEncoding: log2_hashmap_size must be in 10..24 (got {log2_hashmap_size})")
+        if not (base_resolution >= 1 and per_level_scale >= 1):
+            raise ValueError("HashGridEncoding: base_resolution and per_level_scale must be >= 1")
+        self.n_input_dims = 3
+        self.n_levels, self.n_features_per_level = int(n_levels), int(n_features_per_level)
+        self.log2_hashmap_size = int(log2_hashmap_size)
+        self.base_resolution, self.per_level_scale = base_resolution, float(per_level_scale)
+        self.n_output_dims = self.n_levels * self.n_features_per_level
+        self.table = LevelTable(n_levels, log2_hashmap_size, base_resolution, per_level_scale)
+        n_params = self.table.n_entries * self.n_features_per_level
+        if n_params >= 1 << 31:
+            raise ValueError(f"HashGridEncoding: {n_params} parameters (at most 2^31 - 1)")
+        self.params = nn.Parameter(torch.empty(n_params, dtype=torch.float32).uniform_(-1e-4, 1e-4))
+
+    scales = property(lambda self: list(self.table.scales))
+    resolutions = property(lambda self: list(self.table.resolutions))
+    offsets = property(lambda self: list(self.table.offsets))
+    sizes = property(lambda self: list(self.table.sizes))
+
+    def forward(self, x: Tensor) -> Tensor:
+        assert x.shape[-1] == 3, "HashGridEncoding: x must have shape (..., 3)"
+        x, ctx = _autocast_off(x)
+        with ctx:
+            lead = x.shape[:-1]
+            x2 = x.reshape(-1, 3)
+            p = self.params
+            if x2.is_cuda and x2.dtype == torch.float32 and p.dtype == torch.float32 and p.device == x2.device:
+                y = _HashGridFn.apply(x2.contiguous(), p, self)
+            else:
+                dt = torch.promote_types(x2.dtype, p.dtype)
+                y = _hashgrid_torch(x2.to(dt), p.to(dt), self.table, self.n_features_per_level)
+            return y.view(*lead, self.n_output_dims)
+
+    def extra_repr(self) -> str:
+        return (f"n_levels={self.n_levels}, n_features_per_level={self.n_features_per_level}, "
+                f"log2_hashmap_size={self.log2_hashmap_size}, base_resolution={self.base_resolution}, "
+                f"per_level_scale={self.per_level_scale}")
+
+
+# Instant-NGP's real spherical-harmonics basis (tcnn's constants)
+_SH = dict(c0=0.28209479177387814, c1=0.48860251190291987, c2a=1.0925484305920792, c2b=0.94617469575755997,
+           c2c=0.31539156525251999, c2d=0.54627421529603959, c3a=0.59004358992664352, c3b=2.8906114426405538,
+           c3c=0.45704579946446572, c3d=0.3731763325901154, c3e=1.4453057213202769)
+
+
+def _sh_torch(d: Tensor, degree: int) -> Tensor:
+    u = 2.0 * d - 1.0
+    x, y, z = u[:, 0], u[:, 1], u[:, 2]
+    k = _SH
+    out = [torch.full_like(x, k["c0"])]
+    if degree > 1:
+        out += [-k["c1"] * y, k["c1"] * z, -k["c1"] * x]
+    if degree > 2:
+        x2, y2, z2 = x * x, y * y, z * z
+        out += [k["c2a"] * x * y, -k["c2a"] * y * z, k["c2b"] * z2 - k["c2c"], -k["c2a"] * x * z, k["c2d"] * (x2 - y2)]
+        if degree > 3:
+            out += [k["c3a"] * y * (-3.0 * x2 + y2), k["c3b"] * x * y * z, k["c3c"] * y * (1.0 - 5.0 * z2),
+                    k["c3d"] * z * (5.0 * z2 - 3.0), k["c3c"] * x * (1.0 - 5.0 * z2), k["c3e"] * z * (x2 - y2),
+                    k["c3a"] * x * (-x2 + 3.0 * y2)]
+    return torch.stack(out, -1)
+
+
+class SphericalHarmonicsEncoding(nn.Module):
+    """tiny-cuda-nn's ``SphericalHarmonics`` encoding: directions in [0, 1]^3 (``u = 2 d - 1``, not renormalised), ``degree``
+    1..4, ``forward(d[..., 3]) -> [..., degree^2]``.  Differentiable w.r.t. the directions."""
+
+    def __init__(self, n_input_dims: int = 3, degree: int = 4):
+        super().__init__()
+        if n_input_dims != 3:
+            raise ValueError(f"SphericalHarmonicsEncoding: only 3 input dimensions are supported (got {n_input_dims})")
+        if not 1 <= degree <= 4:
+            raise ValueError(f"SphericalHarmonicsEncoding: degree must be in 1..4 (got {degree})")
+        self.n_input_dims, self.degree = 3, int(degree)
+        self.n_output_dims = self.degree * self.degree
+
+    def forward(self, d: Tensor) -> Tensor:
+        assert d.shape[-1] == 3, "SphericalHarmonicsEncoding: directions must have shape (..., 3)"
+        d, ctx = _autocast_off(d)
+        with ctx:
+            lead = d.shape[:-1]
+            d2 = d.reshape(-1, 3)
+            if d2.is_cuda and d2.dtype == torch.float32:
+                y = _SHFn.apply(d2.contiguous(), self.degree)
+            else:
+                y = _sh_torch(d2, self.degree)
+            return y.view(*lead, self.n_output_dims)
+
+    def extra_repr(self) -> str:
+        return f"degree={self.degree}"
+
+
+def encoding_from_tcnn_config(n_input_dims: int, config: dict) -> nn.Module:
+    """The encoding a tiny-cuda-nn encoding config describes: ``HashGrid`` (linear interpolation), ``SphericalHarmonics``,
+    or ``Composite`` with ONE nested encoding over all input dimensions (as ``ngp.py`` builds its direction encoding).
+    Anything else raises ``ValueError``."""
+    if not isinstance(config, dict) or "otype" not in config:
+        raise ValueError(f"not a tcnn encoding config: {config!r}")
+    otype = config["otype"]
+    if otype == "HashGrid":
+        interp = config.get("interpolation", "Linear")
+        if interp != "Linear":
+            raise ValueError(f"HashGrid: only linear interpolation is supported (got {interp!r})")
+        return HashGridEncoding(n_input_dims, n_levels=int(config.get("n_levels", 16)),
+                                n_features_per_level=int(config.get("n_features_per_level", 2)),
+                                log2_hashmap_size=int(config.get("log2_hashmap_size", 19)),
+                                base_resolution=config.get("base_resolution", 16),
+                                per_level_scale=float(config.get("per_level_scale", 2.0)))
+    if otype == "SphericalHarmonics":
+        return SphericalHarmonicsEncoding(n_input_dims, degree=int(config.get("degree", 4)))
+    if otype == "Composite":
+        nested = config.get("nested", [])
+        if len(nested) != 1:
+            raise ValueError(f"Composite: exactly one nested encoding is supported (got {len(nested)})")
+        inner = dict(nested[0])
+        dims = inner.pop("n_dims_to_encode", n_input_dims)
+        if dims != n_input_dims:
+            raise ValueError(f"Composite: the nested encoding must cover all {n_input_dims} dimensions (got {dims})")
+        return encoding_from_tcnn_config(n_input_dims, inner)
+    raise ValueError(f"unsupported tcnn encoding {otype!r} (supported: HashGrid, SphericalHarmonics, Composite)")

@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""Times the hash-grid and spherical-harmonics encodings (csrc/encoding.hip) with HIP events against the torch path of
+nerfacc_amd.encodings on the same GPU, and prints one JSON line per case.
+    python scripts/bench_encodings.py [--reps 20] [--sizes 18,20] [--no-torch]
+Cases: ngp.py's NGPRadianceField grid (L 16, F 2, 2^19) and NGPDensityField grid (L 5, F 2, 2^17) at N = 2^18 and 2^20, on
+two point sets: uniform in [0, 1]^3, and the midpoints of OccGridEstimator.sampling on bench.py's cfg 2 scene (1024^2 image
+rays, 128^3 shell grid), in the order a training step presents them (ray by ray, along each ray).
+Algorithmic bytes: forward reads x (12 B) and 8 corners x F x 4 B per (point, level), writes L F 4 B per point; backward
+reads x and dL/dy (12 + L F 4 B per point) and adds 8 x F x 4 B per (point, level) to the table gradient (the atomic
+bytes); dL/dx adds the 8 corner reads again and writes 12 B per point.  Zeroing the gradient is timed on its own."""
+import argparse
+import json
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from nerfacc_amd import _backend as B  # noqa: E402
+from nerfacc_amd.encodings import HashGridEncoding, SphericalHarmonicsEncoding, _hashgrid_torch  # noqa: E402
+
+
+def timed(fn, reps):
+    for _ in range(3):
+        fn()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(reps):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) * 1e3 / reps   # us
+
+
+def occgrid_midpoints(dev, n):
+    import bench
+    w = bench.make_workload(dev)
+    ri, ts, te = w["estimator"].sampling(w["rays_o"], w["rays_d"], sigma_fn=w["sigma_fn"], render_step_size=w["step"],
+                                         early_stop_eps=1e-4, alpha_thre=0.0)
+    ri, m = ri[:n], ((ts + te) / 2)[:n]
+    x = w["rays_o"][ri] + w["rays_d"][ri] * m[:, None]
+    return ((x + 1.0) / 2.0).contiguous(), int(ts.numel())
+
+
+CONFIGS = {
+    "radiance": dict(n_levels=16, n_features_per_level=2, log2_hashmap_size=19, base_resolution=16,
+                     per_level_scale=np.exp((np.log(4096) - np.log(16)) / 15).tolist()),
+    "density": dict(n_levels=5, n_features_per_level=2, log2_hashmap_size=17, base_resolution=16,
+                    per_level_scale=np.exp((np.log(128) - np.log(16)) / 4).tolist()),
+}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--sizes", default="18,20")
+    ap.add_argument("--no-torch", action="store_true")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    B.load()
+    sizes = [1 << int(s) for s in args.sizes.split(",")]
+    real, n_samples = occgrid_midpoints(dev, max(sizes))
+    assert real.shape[0] >= max(sizes), (real.shape, n_samples)
+    torch.manual_seed(0)
+    uni = torch.rand(max(sizes), 3, device=dev)
+    for cname, cfg in CONFIGS.items():
+        torch.manual_seed(0)
+        enc = HashGridEncoding(3, **cfg).to(dev)
+        L, F = enc.n_levels, enc.n_features_per_level
+        P = enc.params
+        for N in sizes:
+            for pname, pts in (("uniform", uni[:N]), ("occgrid", real[:N])):
+                x = pts.clone()
+                xg = pts.clone().requires_grad_(True)
+                g = torch.randn(N, L * F, device=dev)
+                row = dict(config=cname, points=pname, N=N, L=L, F=F, params=P.numel())
+                with torch.no_grad():
+                    row["fwd_us"] = timed(lambda: enc(x), args.reps)
+                y = enc(x)
+                row["zero_grad_us"] = timed(lambda: torch.zeros_like(P), args.reps)
+
+                def bwd_params():
+                    enc.params.grad = None
+                    torch.autograd.backward(y, g, retain_graph=True)
+
+                row["bwd_params_us_incl_zero"] = timed(bwd_params, args.reps)
+                yx = enc(xg)
+
+                def bwd_both():
+                    enc.params.grad = None
+                    xg.grad = None
+                    torch.autograd.backward(yx, g, retain_graph=True)
+
+                row["bwd_params_x_us_incl_zero"] = timed(bwd_both, args.reps)
+                row["bwd_params_us"] = row["bwd_params_us_incl_zero"] - row["zero_grad_us"]
+                row["bwd_params_x_us"] = row["bwd_params_x_us_incl_zero"] - row["zero_grad_us"]
+                corner_b = 8 * F * 4 * N * L
+                row["fwd_bytes"] = 12 * N + corner_b + L * F * 4 * N
+                row["fwd_TBps"] = row["fwd_bytes"] / row["fwd_us"] / 1e6
+                row["atomic_bytes"] = corner_b
+                row["bwd_atomic_TBps"] = corner_b / row["bwd_params_us"] / 1e6
+                row["Mpts_per_s_fwd"] = N / row["fwd_us"]
+                if not args.no_torch:
+                    with torch.no_grad():
+                        row["torch_fwd_us"] = timed(lambda: _hashgrid_torch(x, P, enc.table, F), max(2, args.reps // 4))
+                        yt = _hashgrid_torch(x, P, enc.table, F)
+                    row["torch_fwd_bit_identical"] = bool(torch.equal(yt, enc(x)))
+                    pt = P.detach().clone().requires_grad_(True)
+                    yt = _hashgrid_torch(x, pt, enc.table, F)
+
+                    def torch_bwd():
+                        pt.grad = None
+                        torch.autograd.backward(yt, g, retain_graph=True)
+
+                    row["torch_bwd_params_us"] = timed(torch_bwd, max(2, args.reps // 4))
+                    enc.params.grad = None
+                    torch.autograd.backward(y, g, retain_graph=True)
+                    d = (pt.grad - enc.params.grad).abs()
+                    row["torch_vs_native_grad_max_abs"] = float(d.max())
+                    row["grad_max_abs"] = float(pt.grad.abs().max())
+                    row["speedup_fwd"] = row["torch_fwd_us"] / row["fwd_us"]
+                    row["speedup_bwd_params"] = row["torch_bwd_params_us"] / row["bwd_params_us_incl_zero"]
+                print(json.dumps(row), flush=True)
+                del y, yx
+    for N in sizes:
+        sh = SphericalHarmonicsEncoding(3, 4)
+        d = (torch.rand(N, 3, device=dev)).requires_grad_(True)
+        out = sh(d)
+        go = torch.randn_like(out)
+        row = dict(config="sh4", N=N)
+        with torch.no_grad():
+            row["fwd_us"] = timed(lambda: sh(d), args.reps)
+
+        def shb():
+            d.grad = None
+            torch.autograd.backward(out, go, retain_graph=True)
+
+        row["bwd_us"] = timed(shb, args.reps)
+        row["fwd_TBps"] = (12 + 64) * N / row["fwd_us"] / 1e6
+        row["bwd_TBps"] = (12 + 64 + 12) * N / row["bwd_us"] / 1e6
+        print(json.dumps(row), flush=True)
+    print(json.dumps(dict(occgrid_samples_cfg2=n_samples)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
