@@ -34,12 +34,14 @@ def build(force: bool = False) -> str:
     """gcc-compile the C restatement (no FMA contraction, OpenMP)."""
     os.makedirs(_BUILD, exist_ok=True)
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(_SRC):
+        # per-process temp name: concurrent builders (the spawned ranks of test_distributed_cpu) each rename their own file
+        tmp = f"{_SO}.{os.getpid()}.tmp"
         cmd = ["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-shared", "-fPIC",
-               "-fvisibility=hidden", "-o", _SO + ".tmp", _SRC, "-lm"]
+               "-fvisibility=hidden", "-o", tmp, _SRC, "-lm"]
         if _SANITIZE:
             cmd[1:2] = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
         subprocess.run(cmd, check=True)
-        os.replace(_SO + ".tmp", _SO)
+        os.replace(tmp, _SO)
     return _SO
 
 

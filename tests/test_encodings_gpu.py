@@ -10,13 +10,28 @@ pytestmark = pytest.mark.gpu
 M32 = 0xFFFFFFFF
 
 
+NGP_SCALE = np.exp((np.log(4096) - np.log(16)) / 15).tolist()
+# (n_levels, n_features_per_level, log2_hashmap_size, base_resolution, per_level_scale)
+CONFIGS = {
+    "radiance": (16, 2, 19, 16, NGP_SCALE),                                    # NGPRadianceField
+    "density": (5, 2, 17, 16, np.exp((np.log(128) - np.log(16)) / 4).tolist()),  # NGPDensityField
+    "F1_L1": (1, 1, 14, 16, 2.0),          # one level: no cross-lane sum of dL/dx
+    "F1_L32": (32, 1, 12, 16, 1.3),        # 2 points per wave
+    "F1_L3_2p24": (3, 1, 24, 128, 4.0),    # 2 hashed levels of 2^24 entries (~142 MB of parameters)
+    "F2_L24": (24, 2, 16, 16, 1.2),        # 16 idle lanes per wave
+    "F4_L3": (3, 4, 14, 16, 2.0),          # one idle lane
+    "F4_ngp": (16, 4, 19, 16, NGP_SCALE),  # the NGP radiance field's shape at F = 4
+    "F8_L7_edge": (7, 8, 12, 16, 1.0),     # every level 16^3 = 2^12 entries: exactly on the dense / hashed boundary
+    "F8_L32": (32, 8, 15, 16, 1.3),        # widest
+    "F2_odd_res": (4, 2, 16, 10.5, 1.5),   # level 0: 11^3 entries, padded to 1336
+}
+
+
 def ngp_grid(kind, seed=0):
     from nerfacc_amd.encodings import HashGridEncoding
     torch.manual_seed(seed)
-    if kind == "radiance":   # NGPRadianceField
-        enc = HashGridEncoding(3, 16, 2, 19, 16, np.exp((np.log(4096) - np.log(16)) / 15).tolist())
-    else:                    # NGPDensityField
-        enc = HashGridEncoding(3, 5, 2, 17, 16, np.exp((np.log(128) - np.log(16)) / 4).tolist())
+    L, F, log2, base, scale = CONFIGS[kind]
+    enc = HashGridEncoding(3, L, F, log2, base, scale)
     with torch.no_grad():
         enc.params.uniform_(-1, 1)
     return enc
@@ -27,14 +42,41 @@ def points(n, seed, lo=0.0, hi=1.0):
     return torch.rand(n, 3, generator=g) * (hi - lo) + lo
 
 
-@pytest.mark.parametrize("kind", ["radiance", "density"])
-@pytest.mark.parametrize("n", [1, 63, 65, 4097, 1 << 20])
+def with_cell_boundaries(x, enc, seed):
+    """x with rows replaced by points on cell boundaries of every level (x * scale_l + 0.5 an integer in float32) and by
+    x = 1.0 and 0.0 coordinates."""
+    g = torch.Generator().manual_seed(seed)
+    x = x.clone()
+    n = x.shape[0]
+    rows = []
+    for s in enc.scales:
+        k = torch.arange(0, int(s) + 2, dtype=torch.float32)
+        c = (k - 0.5) / s
+        c = c[(c * s + 0.5) == torch.floor(c * s + 0.5)]   # (float32 arithmetic, as the kernels do it)
+        if c.numel():
+            rows.append(c[torch.randint(0, c.numel(), (max(n // (4 * len(enc.scales)), 1), 3), generator=g)])
+    rows.append(torch.tensor([[1.0, 1.0, 1.0], [1.0, 0.0, 0.5], [0.0, 0.0, 0.0]]))
+    b = torch.cat(rows)[: max(n - 1, 1)]
+    x[1: 1 + b.shape[0]] = b[: n - 1] if n > 1 else x[1:]
+    if n == 1:
+        x[0] = torch.tensor([1.0, 1.0, 1.0])
+    return x
+
+
+ORIG = ("radiance", "density")
+FWD_CASES = [pytest.param(kind, n, id=f"{n}-{kind}")
+             for kind in CONFIGS for n in (1, 63, 65, 4097, 1 << 20) if n < (1 << 20) or kind in ORIG]
+
+
+@pytest.mark.parametrize("kind,n", FWD_CASES)
 def test_forward_bit_identical_to_torch_path(dev, kind, n):
     enc = ngp_grid(kind)
     x = points(n, n)
     if n > 8:   # out-of-range finite points as well
         x[: n // 8] = points(n // 8, n + 1, -2.0, 3.0)
         x[0] = torch.tensor([1e6, -1e7, 3e9])
+    if kind not in ORIG:
+        x = with_cell_boundaries(x, enc, n)
     ref = enc(x)                                   # CPU: the torch path
     got = enc.to(dev)(x.to(dev))
     assert got.shape == ref.shape == (n, enc.n_output_dims)
@@ -113,11 +155,13 @@ def restate_grads(x, params, enc, g):
     return gp.view(-1), cnt, absum.view(-1), gx
 
 
-@pytest.mark.parametrize("kind", ["radiance", "density"])
+@pytest.mark.parametrize("kind", list(CONFIGS))
 def test_backward_against_float64(dev, kind):
     enc = ngp_grid(kind)
     n = 1 << 16
     x = points(n, 11, -0.25, 1.25)
+    if kind not in ORIG:
+        x = with_cell_boundaries(x, enc, 11)
     g = torch.randn(n, enc.n_output_dims, generator=torch.Generator().manual_seed(12))
     encd = enc.to(dev)
     xd = x.to(dev).requires_grad_(True)
