@@ -36,6 +36,27 @@ void set_error(const char *fmt, ...);
 // environment.  NULL: not set.
 const char *tuning_env(const char *name);
 
+// The launch plan of the cone walk's two forms (grid.hip: nfa_traverse_cone_runs, walk.hip: nfa_traverse_cone_walk) for n_walk rays:
+// the refilling kernel for limited walks (NFA_REFILL_ALL = "1": for unlimited ones too, for measurements), where a wave owns
+// `chunk` entries of the ray list and leaves its cell loop when fewer than `min_busy` lanes are walking; one ray per lane
+// otherwise, and always with NFA_REFILL = "0".  NFA_REFILL = "chunk,min_busy" sets the two numbers.
+struct RefillPlan {
+    bool refill;
+    int64_t chunk;
+    int32_t min_busy;
+};
+static inline RefillPlan refill_plan(int64_t n_walk, int32_t steps_limit)
+{
+    const char *refill_env = tuning_env("NFA_REFILL"), *refill_all = tuning_env("NFA_REFILL_ALL");
+    if (!(steps_limit > 0 || (refill_all && refill_all[0] == '1')) || (refill_env && refill_env[0] == '0')) return RefillPlan{false, 64, 64};
+    // entries per wave: enough of them that a lane is refilled several times, as long as the launch still fills the chip
+    int64_t chunk = ((n_walk + 4095) / 4096 + 63) / 64 * 64;
+    chunk = chunk < 64 ? 64 : (chunk > 1024 ? 1024 : chunk);
+    int min_busy = 48;
+    if (refill_env) { long c = 0; int m = 0; if (sscanf(refill_env, "%ld,%d", &c, &m) == 2 && c >= 64 && m >= 1 && m <= 64) { chunk = c / 64 * 64; min_busy = m; } }
+    return RefillPlan{true, chunk, min_busy};
+}
+
 static inline hipStream_t as_stream(nfa_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 __host__ __device__ static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -119,7 +140,7 @@ __device__ __forceinline__ uint32_t mad_u24(uint32_t a, uint32_t b, uint32_t c)
 // takes the blocks dealt to it.  A cost that is periodic in the block index with a period that divides 8 therefore lands
 // on a few XCDs: the rays of a 1024-pixel image row are four 256-ray blocks, the two middle ones cross the most cells, and
 // XCDs 1, 2, 5, 6 were still walking them while the other four had been idle for the last third of the launch (wave
-// time stamps, scripts/walk_timeline.py: 4096 busy waves, then 2000).  Within each group of 8 consecutive blocks the work
+// time stamps, DESIGN.md: 4096 busy waves, then 2000).  Within each group of 8 consecutive blocks the work
 // items are rotated by the group's number, so every XCD sees every residue; a bijection on [0, n_blocks).
 __device__ __forceinline__ int64_t xcd_fair_block(uint32_t b, uint32_t n_blocks)
 {
@@ -166,20 +187,17 @@ __device__ __forceinline__ int32_t lane_value(int32_t v, int32_t l) { return __b
 __device__ __forceinline__ float lane_value(float v, int32_t l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 
 
-// 16-byte stores of streamed outputs.  NFA_NT_STORES=1 marks them non-temporal (A/B switch).
-#ifndef NFA_NT_STORES
-#define NFA_NT_STORES 0
-#endif
+// 16-byte stores of streamed outputs.  NT marks them non-temporal: traverse2.hip's expansions do, the engine ops lose with it.
 typedef float nfa_v4f __attribute__((ext_vector_type(4)));
 typedef long long nfa_v2l __attribute__((ext_vector_type(2)));
-template <bool NT = (NFA_NT_STORES != 0)>
+template <bool NT = false>
 __device__ __forceinline__ void store_f4(float *p, float a, float b, float c, float d)
 {
     nfa_v4f v = {a, b, c, d};
     if (NT) __builtin_nontemporal_store(v, reinterpret_cast<nfa_v4f *>(p));
     else *reinterpret_cast<nfa_v4f *>(p) = v;
 }
-template <bool NT = (NFA_NT_STORES != 0)>
+template <bool NT = false>
 __device__ __forceinline__ void store_l2(int64_t *p, int64_t a, int64_t b)
 {
     nfa_v2l v = {a, b};

@@ -143,12 +143,6 @@ enum { EMIT_NONE = 0, EMIT_API = 1, EMIT_DIRECT = 2, EMIT_RUNS = 3 };
 // t * cone) from its first distance, so {t_first, k_start} determines every sample of it; chains are cut every
 // CONE_RUN_CAP samples so that the expansion (expand_runs_kernel<EXP_CONE>) iterates the recurrence at most that often
 // per output.  The second walk of the fill pass becomes a coalesced expansion.
-#ifndef NFA_REFILL_SPLIT
-#define NFA_REFILL_SPLIT 1
-#endif
-#ifndef NFA_TRAVERSE_SPLIT
-#define NFA_TRAVERSE_SPLIT 0
-#endif
 constexpr int CONE_RUN_CAP = 64;
 struct RunOut {
     int32_t *run_cnts;          // [n_rays]
@@ -393,7 +387,7 @@ __device__ __forceinline__ void traverse_span(const nfa_traverse_args &a, int64_
     SpanState sp;
     span_begin(a, o, d, inv, level, this_tmin, this_tmax, st, sp);
     if (a.traverse_steps_limit > 0 && st.n_samples >= a.traverse_steps_limit) return;
-    while (!span_cell<EMIT, HAS_IV, HAS_SM, EMIT == EMIT_RUNS && NFA_TRAVERSE_SPLIT != 0>(a, tid, iv_base, sm_base, sp, st, ro)) {}
+    while (!span_cell<EMIT, HAS_IV, HAS_SM, false>(a, tid, iv_base, sm_base, sp, st, ro)) {}
 }
 
 // EMIT_NONE  : count pass (mode 0)
@@ -401,9 +395,6 @@ __device__ __forceinline__ void traverse_span(const nfa_traverse_args &a, int64_
 // EMIT_DIRECT: (t_starts, t_ends, ray_indices) per sample (modes 1, 2)
 // FUSED      : single grid, intersection computed here (t_sorted/t_indices/hits are NULL)
 template <int EMIT, bool HAS_IV, bool HAS_SM, bool FUSED>
-#ifdef NFA_TRAVERSE_WAVES
-__attribute__((amdgpu_waves_per_eu(NFA_TRAVERSE_WAVES, 8)))
-#endif
 __global__ __launch_bounds__(256) void traverse_kernel(const nfa_traverse_args a_in, const RunOut ro)
 {
     if (a_in.run_if_nonzero && *a_in.run_if_nonzero == 0) return;   // (a fill pass launched without the host knowing whether it is needed)
@@ -631,7 +622,7 @@ __global__ __launch_bounds__(256) void traverse_refill_kernel(const nfa_traverse
         const int32_t need = next < end ? min_busy : (n_walking * 3 >> 2) > 1 ? (n_walking * 3 >> 2) : 1;
         do {
             if (phase == WALK) {
-                if (span_cell<EMIT_RUNS, false, true, NFA_REFILL_SPLIT != 0>(a, tid, 0, 0, sp, st, ro))
+                if (span_cell<EMIT_RUNS, false, true, true>(a, tid, 0, 0, sp, st, ro))
                     phase = (limit > 0 && st.n_samples >= limit) ? FINISH : SPAN;  // budget spent: nothing after it changes the ray (see traverse_kernel)
             }
         } while (__popcll(__ballot(phase == WALK)) >= need);
@@ -921,9 +912,10 @@ int nfa_ray_events(const float *rays_o, const float *rays_d, int64_t n_rays, con
     NFA_REQUIRE(rays_o && rays_d && aabbs && t_sorted && t_indices && hits, "ray_events: null pointer");
     const dim3 grid(grid_1d(n_rays, 256)), block(256);
     hipStream_t s = as_stream(stream);
-#define NFA_EV(G) case G: hipLaunchKernelGGL(ray_events_kernel<G>, grid, block, 0, s, rays_o, rays_d, n_rays, aabbs, t_sorted, t_indices, hits); break
-    switch (n_aabbs) { NFA_EV(1); NFA_EV(2); NFA_EV(3); NFA_EV(4); NFA_EV(5); NFA_EV(6); NFA_EV(7); NFA_EV(8); }
-#undef NFA_EV
+    static constexpr decltype(&ray_events_kernel<1>) kernels[NFA_MAX_EVENT_LEVELS] = {
+        ray_events_kernel<1>, ray_events_kernel<2>, ray_events_kernel<3>, ray_events_kernel<4>,
+        ray_events_kernel<5>, ray_events_kernel<6>, ray_events_kernel<7>, ray_events_kernel<8>};
+    hipLaunchKernelGGL(kernels[n_aabbs - 1], grid, block, 0, s, rays_o, rays_d, n_rays, aabbs, t_sorted, t_indices, hits);
     NFA_CHECK_LAUNCH("ray_events");
     return NFA_OK;
 }
@@ -1002,19 +994,11 @@ int nfa_traverse_cone_runs(const nfa_traverse_args *pa, int32_t *run_cnts, uint6
     ro.n_order = ray_order ? n_order : a.n_rays;
     NFA_REQUIRE(!ray_order || (n_order >= 0 && n_order <= a.n_rays), "traverse_cone_runs: n_order out of range");
     if (ray_order && n_order == 0) return NFA_OK;
-    const char *refill_env = tuning_env("NFA_REFILL");  // "0": one ray per lane; "chunk,min_busy": tuning
-    const char *refill_all = tuning_env("NFA_REFILL_ALL");
-    if ((a.traverse_steps_limit > 0 || (refill_all && refill_all[0] == '1')) && !(refill_env && refill_env[0] == '0')) {
-        // slots per wave: enough of them that a lane is refilled several times, as long as the launch still fills the chip
-        const int64_t n_walk = ro.n_order;
-        int64_t chunk = ((n_walk + 4095) / 4096 + 63) / 64 * 64;
-        chunk = chunk < 64 ? 64 : (chunk > 1024 ? 1024 : chunk);
-        int min_busy = 48;
-        if (refill_env) { long c = 0; int m = 0; if (sscanf(refill_env, "%ld,%d", &c, &m) == 2 && c >= 64 && m >= 1 && m <= 64) { chunk = c / 64 * 64; min_busy = m; } }
-        const int64_t n_waves = (n_walk + chunk - 1) / chunk;
-        const unsigned grid = (unsigned)((n_waves + 3) / 4);
-        if (fused) hipLaunchKernelGGL((traverse_refill_kernel<true>), dim3(grid), dim3(256), 0, s, a, ro, (int32_t)chunk, (int32_t)min_busy);
-        else       hipLaunchKernelGGL((traverse_refill_kernel<false>), dim3(grid), dim3(256), 0, s, a, ro, (int32_t)chunk, (int32_t)min_busy);
+    const RefillPlan plan = refill_plan(ro.n_order, a.traverse_steps_limit);
+    if (plan.refill) {
+        const unsigned grid = (unsigned)ceil_div64(ceil_div64(ro.n_order, plan.chunk), 4);   // four waves per workgroup
+        if (fused) hipLaunchKernelGGL((traverse_refill_kernel<true>), dim3(grid), dim3(256), 0, s, a, ro, (int32_t)plan.chunk, plan.min_busy);
+        else       hipLaunchKernelGGL((traverse_refill_kernel<false>), dim3(grid), dim3(256), 0, s, a, ro, (int32_t)plan.chunk, plan.min_busy);
     } else {
         launch_traverse<EMIT_RUNS, false, true>(a, fused, s, ro);
     }

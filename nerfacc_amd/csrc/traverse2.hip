@@ -11,32 +11,23 @@
 //                 sample centres; expand_intervals: the API's edge stream with is_left / is_right.
 // Results are bit-identical to the reference's serial accumulation (oracle/nerfacc_oracle.c).
 #include "common.hip.h"
-#ifndef NFA_NT_EXPAND
-#define NFA_NT_EXPAND 1   /* sample arrays are written once and read by later kernels long after they left L2: non-temporal stores, expand 160 -> 152 us and the whole cfg-2 step -40 us (A/B on one box); the engine ops lose with them */
-#endif
 #include "march.h"
 
 namespace nfa {
 
+// The expansions' stores are non-temporal (store_f4<true> / store_l2<true>): sample arrays are written once and read by later
+// kernels long after they left L2: expand 160 -> 152 us and the whole cfg-2 step -40 us (A/B on one box); the engine ops lose
+// with them.
 constexpr int EXP_RPW = 32;        // rays per wave batch in the expansion
-#ifndef NFA_EXP_QMAX
-#define NFA_EXP_QMAX 1024
-#endif
-constexpr int EXP_QMAX = NFA_EXP_QMAX;  // runs staged per batch (EXP_RPW * max_runs)
-#ifndef NFA_EXP_IV_QMAX
-#define NFA_EXP_IV_QMAX 256
-#endif
-#ifndef NFA_EXP_RUNS_QMAX
-#define NFA_EXP_RUNS_QMAX 1024  /* one group; 256 (2 more waves per SIMD) measured 2 % slower here (156 vs 152.5 us), where it made expand_intervals 26 % faster */
-#endif
-constexpr int EXP_RUNS_QMAX = NFA_EXP_RUNS_QMAX;  // expand_runs stages a batch's records this many at a time (>= 32: one ray's)
+constexpr int EXP_QMAX = 1024;     // runs staged per batch (EXP_RPW * max_runs)
+// expand_runs stages a batch's records this many at a time (>= 32: one ray's): one group; 256 (2 more waves per SIMD) measured
+// 2 % slower here (156 vs 152.5 us), where it made expand_intervals 26 % faster
+constexpr int EXP_RUNS_QMAX = 1024;
 static_assert(EXP_RUNS_QMAX >= 32 && EXP_RUNS_QMAX <= EXP_QMAX, "expand_runs: a ray's records must fit the staging area");
-constexpr int EXP_IV_QMAX = NFA_EXP_IV_QMAX;  // expand_intervals stages a batch's records this many at a time (>= 32: one ray's)
+constexpr int EXP_IV_QMAX = 256;   // expand_intervals stages a batch's records this many at a time (>= 32: one ray's)
 static_assert(EXP_IV_QMAX >= 32 && EXP_IV_QMAX <= EXP_QMAX, "expand_intervals: a ray's records must fit the staging area");
-#ifndef NFA_EXP_WPB
-#define NFA_EXP_WPB 2  /* measured on cfg 2: 1 wave 176 us, 2 waves 160 us, 4 waves 175 us */
-#endif
-constexpr int EXP_WPB = NFA_EXP_WPB;  // waves per workgroup of the expansion kernels (they never cooperate)
+// waves per workgroup of the expansion kernels (they never cooperate); measured on cfg 2: 1 wave 176 us, 2 waves 160 us, 4 waves 175 us
+constexpr int EXP_WPB = 2;
 
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pack_bricks_kernel(const uint8_t *__restrict__ binaries, int32_t n_grids,
@@ -388,13 +379,13 @@ __global__ __launch_bounds__(64 * EXP_WPB) void expand_runs_kernel(int64_t n_ray
                 }
                 if (vec && valid[0] && valid[1] && valid[2] && valid[3]) {
                     if (MODE == EXP_MIDS) {
-                        store_f4<NFA_NT_EXPAND>(t_mids + p0, ts4[0], ts4[1], ts4[2], ts4[3]);
+                        store_f4<true>(t_mids + p0, ts4[0], ts4[1], ts4[2], ts4[3]);
                     } else if (MODE == EXP_STARTS_ENDS || MODE == EXP_CONE) {
-                        store_f4<NFA_NT_EXPAND>(t_starts + p0, ts4[0], ts4[1], ts4[2], ts4[3]);
-                        store_f4<NFA_NT_EXPAND>(t_ends + p0, te4[0], te4[1], te4[2], te4[3]);
+                        store_f4<true>(t_starts + p0, ts4[0], ts4[1], ts4[2], ts4[3]);
+                        store_f4<true>(t_ends + p0, te4[0], te4[1], te4[2], te4[3]);
                     }
-                    store_l2<NFA_NT_EXPAND>(ray_indices + p0, ri4[0], ri4[1]);
-                    store_l2<NFA_NT_EXPAND>(ray_indices + p0 + 2, ri4[2], ri4[3]);
+                    store_l2<true>(ray_indices + p0, ri4[0], ri4[1]);
+                    store_l2<true>(ray_indices + p0 + 2, ri4[2], ri4[3]);
                 } else {
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
@@ -418,9 +409,6 @@ __global__ __launch_bounds__(64 * EXP_WPB) void expand_runs_kernel(int64_t n_ray
 // then the end t_first + m * inc of each of its samples.  is_right is false exactly at chain starts, is_left
 // is false exactly before a chain start (or the end of the ray's edges).  Same batch / chunk structure as
 // expand_runs_kernel; one lane per ray stages that ray's records (it needs the running count of chain starts).
-#ifdef NFA_EXP_IV_WAVES
-__attribute__((amdgpu_waves_per_eu(NFA_EXP_IV_WAVES, NFA_EXP_IV_WAVES)))
-#endif
 __global__ __launch_bounds__(64 * EXP_WPB) void expand_intervals_kernel(int64_t n_rays, float dt, const int32_t *__restrict__ run_cnts,
                                                                const unsigned long long *__restrict__ runs, int32_t max_runs,
                                                                const longlong2 *__restrict__ iv_packed_info,
@@ -595,9 +583,9 @@ __global__ __launch_bounds__(64 * EXP_WPB) void expand_intervals_kernel(int64_t 
                 }
                 __builtin_amdgcn_wave_barrier();
                 if (vec && all4) {
-                    store_f4<NFA_NT_EXPAND>(vals + p0, v4[0], v4[1], v4[2], v4[3]);
-                    store_l2<NFA_NT_EXPAND>(ray_indices + p0, ri4[0], ri4[1]);
-                    store_l2<NFA_NT_EXPAND>(ray_indices + p0 + 2, ri4[2], ri4[3]);
+                    store_f4<true>(vals + p0, v4[0], v4[1], v4[2], v4[3]);
+                    store_l2<true>(ray_indices + p0, ri4[0], ri4[1]);
+                    store_l2<true>(ray_indices + p0 + 2, ri4[2], ri4[3]);
                 } else {
 #pragma unroll
                     for (int k = 0; k < 4; ++k)

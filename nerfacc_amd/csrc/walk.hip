@@ -28,27 +28,15 @@
 
 namespace nfa {
 
-#ifndef NFA_WK_EV
-#define NFA_WK_EV 16
-#endif
-constexpr int WK_EV = NFA_WK_EV;           // list slots per ray: 17 x 4 bytes of LDS per lane
-#ifndef NFA_WALK_WAVES
-#define NFA_WALK_WAVES 5   /* 100 -> 95 registers (one 8-byte spill outside the loops): 5 waves per SIMD instead of 4 fill a part of the
-                              time a slot waits for its next workgroup (scripts/walk_timeline.py): 168 -> 160 us on cfg 2, 384 -> 351 at 256^3 */
-#endif
-#if NFA_WALK_WAVES > 0
-#define NFA_WALK_OCC __attribute__((amdgpu_waves_per_eu(NFA_WALK_WAVES, NFA_WALK_WAVES)))
-#else
-#define NFA_WALK_OCC
-#endif
-static_assert(NFA_WK_EV == 16 || NFA_WK_EV == 8, "the list-full test is one bit of the slot address: a power of two");
-#ifndef NFA_WALK_LG
-#define NFA_WALK_LG 8    /* log2 of the bytes of one list slot = 4 bytes x threads per workgroup: 8 = 64 threads, one wave.  A workgroup's
-                            wave slots and LDS are handed on when its LAST wave is done; the waves of a 256-thread workgroup differ by
-                            tens of microseconds (wave time stamps, scripts/walk_timeline.py).  256 / 128 / 64 threads: 146.9 / 144.7 /
-                            142.0 us on cfg 2, 286.5 / 285.0 / 273.4 at 256^3 (one box) */
-#endif
-constexpr int WK_LG = NFA_WALK_LG;
+constexpr int WK_EV = 16;                  // list slots per ray: 17 x 4 bytes of LDS per lane
+static_assert(WK_EV == 16 || WK_EV == 8, "the list-full test is one bit of the slot address: a power of two");
+// waves per SIMD of the lattice walk: 100 -> 95 registers (one 8-byte spill outside the loops): 5 waves per SIMD instead of 4 fill a
+// part of the time a slot waits for its next workgroup (wave time stamps): 168 -> 160 us on cfg 2, 384 -> 351 at 256^3
+constexpr int WK_WAVES = 5;
+// log2 of the bytes of one list slot = 4 bytes x threads per workgroup: 8 = 64 threads, one wave.  A workgroup's wave slots and LDS
+// are handed on when its LAST wave is done; the waves of a 256-thread workgroup differ by tens of microseconds (wave time stamps,
+// DESIGN.md).  256 / 128 / 64 threads: 146.9 / 144.7 / 142.0 us on cfg 2, 286.5 / 285.0 / 273.4 at 256^3 (one box)
+constexpr int WK_LG = 8;
 constexpr int WK_THREADS = 1 << (WK_LG - 2);
 constexpr uint32_t WK_FULL = (uint32_t)WK_EV << WK_LG;  // slot address bit that says "the open entry sits in slot WK_EV"
 constexpr uint32_t WK_GUARD = (1u << 9) | (1u << 19) | (1u << 29);
@@ -87,10 +75,6 @@ struct WalkParams {
     int64_t n_order;             // entries of `order` (< n_rays: only the listed rays are walked; the others keep their outputs)
     ApproachTable approach;      // march.h; n == 0: none
     LatticeTable lat;            // march.h: the lattice of the launch's near plane and step (walk_kernel<.., LATTICE = true>)
-#ifdef NFA_WALK_STAMPS
-    unsigned long long *stamps;  // debugging aid (scripts/walk_timeline.py): [waves][4] = {start, end (s_memrealtime, 100 MHz), HW_ID, XCC_ID}
-    const int32_t *tile_order;   // experiment: workgroup b walks tile tile_order[b]
-#endif
 };
 
 enum { WK_EMPTY = 0, WK_OCC = 1, WK_SPAN = 2 };
@@ -466,9 +450,6 @@ __device__ __forceinline__ void lattice_run(LatState &s, char *col /* LDS column
             *reinterpret_cast<uint32_t *>(slot) = w;
         } while (failed != 0u);
     }
-#ifdef NFA_WALK_NO_PASSB   /* timing experiment: thresholds converted, nothing emitted (wrong results) */
-    return;
-#endif
     // ---- pass B: the list, in integers (grid.cu:153-163 span start, :193-206 empty cells, :207-262 occupied cells)
     int32_t k = 0;
     while (k < cnt) {
@@ -592,12 +573,10 @@ __device__ __forceinline__ void walk_span_setup(const nfa_traverse_args &a, cons
 // 5 half-rate + 22 full-rate instructions and one 16-byte LDS read per cell (registers: 5 + 27, and six registers more).
 // Rows of 16 bytes, lanes 16 bytes apart, axes 4096 bytes apart: a quad of lanes reads four different bank groups
 // whichever rows its lanes pick.
-#ifndef NFA_CONE_THREADS
-#define NFA_CONE_THREADS 256   /* lanes per workgroup of the cone-angle kernels (their LDS tables are laid out for that many).  Unlike the
-                                  constant-step walk they gain nothing from smaller workgroups (their rays are binned by length, their waves own
-                                  chunks): 256 / 128 / 64 lanes: cfg 5's count pass 7.20 / 7.23 / 7.26 ms, its test-mode image 98.8 / 101.4 / 100.8 ms */
-#endif
-constexpr int CONE_THREADS = NFA_CONE_THREADS;
+// lanes per workgroup of the cone-angle kernels (their LDS tables are laid out for that many).  Unlike the constant-step walk they
+// gain nothing from smaller workgroups (their rays are binned by length, their waves own chunks): 256 / 128 / 64 lanes: cfg 5's
+// count pass 7.20 / 7.23 / 7.26 ms, its test-mode image 98.8 / 101.4 / 100.8 ms
+constexpr int CONE_THREADS = 256;
 constexpr uint32_t WK_TAB_AXIS = CONE_THREADS * 16;   // (the cone kernels' workgroups, whatever the constant-step walk's are)
 static_assert((WK_TAB_AXIS & (WK_TAB_AXIS - 1)) == 0, "the row address is formed by OR-ing the axis offset into the lane's");
 __device__ __forceinline__ float dda_step_lds(const char *lds, uint32_t ax /* the lane's x row */, uint32_t az /* its z row */, float &tx,
@@ -694,11 +673,7 @@ __device__ __forceinline__ void dda_table_write(char *tab_lds, const WalkSpan &s
 __device__ __forceinline__ void walk_request(uint32_t widx, uint32_t flip, const uint32_t *__restrict__ bits, uint32_t &i, uint32_t &w)
 {
     i = widx ^ flip;
-#if defined(NFA_WALK_EXP) && NFA_WALK_EXP == 2  /* timing experiment: every load hits one 128-byte line */
-    const uint32_t off = ((i >> 5) & 31u) << 2;
-#else
     const uint32_t off = (i >> 5) << 2;
-#endif
     asm volatile("global_load_dword %0, %1, %2" : "=v"(w) : "v"(off), "s"(bits) : "memory");
 }
 // the older of the two words in flight has arrived / both have
@@ -722,15 +697,15 @@ __device__ __forceinline__ bool walk_stop(uint32_t over, uint32_t ev_addr)
 // registers it would occupy 80 scalar registers and be selected entry by entry).  The offset of the second by-value
 // argument is the ABI's: arguments are laid out in order, each at its natural alignment.
 static_assert(alignof(WalkParams) == 8 && sizeof(nfa_traverse_args) % 8 == 0, "walk kernels: WalkParams follows nfa_traverse_args in the kernarg segment");
-__device__ __forceinline__ void approach_to_lds(ApproachLds &tb, const WalkParams &p)
+// (thread t copies entry t of each table: a workgroup has to have a thread for every entry)
+static_assert(WK_THREADS >= APPROACH_MAX, "approach_to_lds: one thread per entry of the approach table");
+static_assert(WK_THREADS >= LATTICE_MAX_ROWS && WK_THREADS >= LATTICE_MAX_BINADES, "lattice_to_lds: one thread per row and per binade of the lattice table");
+__device__ __forceinline__ void approach_to_lds(ApproachLds &tb)
 {
     const char *ka = (const char *)__builtin_amdgcn_kernarg_segment_ptr();
     constexpr size_t p_off = (sizeof(nfa_traverse_args) + alignof(WalkParams) - 1) / alignof(WalkParams) * alignof(WalkParams);
     const WalkParams *pk = reinterpret_cast<const WalkParams *>(ka + p_off);
     if (threadIdx.x < APPROACH_MAX) { tb.T[threadIdx.x] = pk->approach.T[threadIdx.x]; tb.q[threadIdx.x] = pk->approach.q[threadIdx.x]; }
-#ifdef NFA_WALK_DEBUG
-    if (threadIdx.x == 0 && (pk->n_rays != p.n_rays || pk->approach.n != p.approach.n)) __builtin_trap();
-#endif
 }
 
 // The lattice table of the launch, staged the same way; the rows of the binade table with what lattice_J_fast needs
@@ -759,7 +734,6 @@ struct WalkOut {
     float t_last;
     int32_t n_samples, n_chains, n_runs;
 };
-#define WALK_DDA(tx_, ty_, tz_, widx_, over_) dda_step_reg_end(sp.dx, sp.dy, sp.dz, sp.mx, sp.my, sp.mz, tx_, ty_, tz_, sp.end, widx_, over_)
 template <bool FUSED, bool HAS_LIMIT, bool LATTICE>
 __device__ __forceinline__ void walk_ray(const nfa_traverse_args &a, const WalkParams &p, int64_t tid, char *ev_lds,
                                          uint32_t lane_off, const ApproachLds &tb, const LatticeLds &lt, int32_t steps_limit, WalkOut &out)
@@ -874,7 +848,7 @@ __device__ __forceinline__ void walk_ray(const nfa_traverse_args &a, const WalkP
                 in_span = 1;
                 // the first cell's step: its exit distance, the request for the second cell's word
                 __builtin_amdgcn_s_waitcnt(0xC07F);
-                m_p = WALK_DDA(sp.tx, sp.ty, sp.tz, sp.widx, sp.over);
+                m_p = dda_step_reg_end(sp.dx, sp.dy, sp.dz, sp.mx, sp.my, sp.mz, sp.tx, sp.ty, sp.tz, sp.end, sp.widx, sp.over);
                 walk_request(sp.widx, sp.flip, bits, i_q, w_q);
                 par = 0;
             }
@@ -893,16 +867,13 @@ __device__ __forceinline__ void walk_ray(const nfa_traverse_args &a, const WalkP
             // would be waited for.  With nothing in flight at the loop's head it finds vmcnt(1) in both halves.
             // vmcnt(0) lgkmcnt(0), expcnt untouched:
             __builtin_amdgcn_s_waitcnt(0x0070);
-#if defined(NFA_WALK_EXP) && NFA_WALK_EXP == 5   /* timing experiment: everything but the cell loop */
-            over = 0u;
-#else
             if (over != 0u) {
                 // (`par`: whose registers hold the unrecorded cell when the loop is left -- the lanes leave it one by one and
                 //  nothing is moved on the way out: a move of a register with a request in flight waits for the request.  A lane
                 //  that left after the first half resumes with the second.)
                 bool go = true;
                 if (par) {
-                    m_p = WALK_DDA(tx, ty, tz, widx, over);
+                    m_p = dda_step_reg_end(sp.dx, sp.dy, sp.dz, sp.mx, sp.my, sp.mz, tx, ty, tz, sp.end, widx, over);
                     walk_arrived(w_q, over);
                     walk_record(m_q, w_q, i_q, open_type, ev_addr, ev_lds);
                     walk_request(widx, flip, bits, i_q, w_q);
@@ -910,12 +881,12 @@ __device__ __forceinline__ void walk_ray(const nfa_traverse_args &a, const WalkP
                     go = !walk_stop(over, ev_addr);
                 }
                 if (go) for (;;) {
-                    m_q = WALK_DDA(tx, ty, tz, widx, over);   // out of Q
+                    m_q = dda_step_reg_end(sp.dx, sp.dy, sp.dz, sp.mx, sp.my, sp.mz, tx, ty, tz, sp.end, widx, over);   // out of Q
                     walk_arrived(w_p, over);
                     walk_record(m_p, w_p, i_p, open_type, ev_addr, ev_lds);
                     walk_request(widx, flip, bits, i_p, w_p);                               // P's registers: the cell behind Q
                     if (walk_stop(over, ev_addr)) { par = 1; break; }
-                    m_p = WALK_DDA(tx, ty, tz, widx, over);   // out of the cell in P's registers
+                    m_p = dda_step_reg_end(sp.dx, sp.dy, sp.dz, sp.mx, sp.my, sp.mz, tx, ty, tz, sp.end, widx, over);   // out of the cell in P's registers
                     walk_arrived(w_q, over);
                     walk_record(m_q, w_q, i_q, open_type, ev_addr, ev_lds);
                     walk_request(widx, flip, bits, i_q, w_q);
@@ -924,7 +895,6 @@ __device__ __forceinline__ void walk_ray(const nfa_traverse_args &a, const WalkP
                 asm volatile("" : "+v"(par));   // (otherwise "the cell recorded last" is tracked with a move in every cell)
                 m_last = par ? m_p : m_q;   // the cell recorded last
             }
-#endif
             walk_arrived_all(w_p, w_q);
             sp.tx = tx; sp.ty = ty; sp.tz = tz; sp.widx = widx; sp.over = over;
             if (ev_addr >= WK_FULL) break;   // list full: phase 2 first (the unrecorded cell stays so)
@@ -936,10 +906,8 @@ __device__ __forceinline__ void walk_ray(const nfa_traverse_args &a, const WalkP
         // ---------------- phase 2
         int32_t cnt = (int32_t)(ev_addr >> WK_LG);
         if (finished && has_open) { cnt += 1; has_open = 0; }
-#ifndef NFA_WALK_NO_PHASE2
         if (LATTICE) lattice_run<HAS_LIMIT>(ls, col, cnt, ev_span, dt * 0.5f, limit, p, lt, tid);
         else marcher_run<HAS_LIMIT>(s, col, cnt, ev_span, dt, limit, p, tb, tid);
-#endif
         if (finished || (limit > 0 && (LATTICE ? ls.n_samples : s.n_samples) >= limit)) break;
         // the open entry moves to slot 0
         ev_span = 0u;
@@ -958,11 +926,8 @@ __device__ __forceinline__ void walk_body(const nfa_traverse_args &a, const Walk
     __shared__ __attribute__((aligned(16))) char ev_lds[(WK_EV + 1) << WK_LG];   // [WK_EV + 1][256] floats
     __shared__ ApproachLds tb;
     __shared__ LatticeLds lt;
-#ifdef NFA_WALK_STAMPS
-    const unsigned long long st_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
     if (LATTICE) lattice_to_lds(lt);
-    else approach_to_lds(tb, p);
+    else approach_to_lds(tb);
     __syncthreads();
     const uint32_t lane_off = 4u * threadIdx.x;
     // device-side controls (include/nerfacc_hip.h: steps_limit_dev, n_listed_dev): a loop that does not wait for the host
@@ -970,11 +935,7 @@ __device__ __forceinline__ void walk_body(const nfa_traverse_args &a, const Walk
     if (HAS_LIMIT && steps_limit <= 0) return;
     int64_t n_walk = p.order ? p.n_order : a.n_rays;
     if (p.order && a.n_listed_dev) n_walk = min(n_walk, *a.n_listed_dev);
-#ifdef NFA_WALK_STAMPS
-    const int64_t bid = p.tile_order ? (int64_t)p.tile_order[blockIdx.x] : xcd_fair_block(blockIdx.x, gridDim.x);
-#else
     const int64_t bid = xcd_fair_block(blockIdx.x, gridDim.x);
-#endif
     for (int64_t slot_i = bid * blockDim.x + threadIdx.x; slot_i < n_walk;
          slot_i += (int64_t)blockDim.x * gridDim.x) {
         const int64_t tid = p.order ? (int64_t)p.order[slot_i] : slot_i;
@@ -996,17 +957,10 @@ __device__ __forceinline__ void walk_body(const nfa_traverse_args &a, const Walk
         p.run_cnts[tid] = n_runs;
         if (n_runs > p.max_runs) atomicAdd(p.overflow, 1);
     }
-#ifdef NFA_WALK_STAMPS
-    if (p.stamps && (threadIdx.x & 63) == 0) {
-        unsigned long long *o = p.stamps + (bid * (WK_THREADS / 64) + (threadIdx.x >> 6)) * 4;
-        o[0] = st_t0; o[1] = __builtin_amdgcn_s_memrealtime(); o[2] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_REG_HW_ID
-        o[3] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));  // HW_REG_XCC_ID
-    }
-#endif
 }
 // (two kernels: the register budget of the lattice form is held to 5 waves per SIMD, the per-ray marcher keeps what it needs)
 template <bool FUSED, bool HAS_LIMIT>
-NFA_WALK_OCC __global__ __launch_bounds__(WK_THREADS) void walk_lattice_kernel(const nfa_traverse_args a, const WalkParams p)
+__attribute__((amdgpu_waves_per_eu(WK_WAVES, WK_WAVES))) __global__ __launch_bounds__(WK_THREADS) void walk_lattice_kernel(const nfa_traverse_args a, const WalkParams p)
 {
     walk_body<FUSED, HAS_LIMIT, true>(a, p);
 }
@@ -1042,16 +996,7 @@ struct ConeParams {
     uint4 *arena;                // [arena_cap], zeroed by the caller (samples == 0: unused entry)
     int32_t arena_cap;
     int32_t *arena_count;        // [1] entries handed out (whole blocks), zeroed by the call
-#ifdef NFA_CONE_PROFILE
-    unsigned long long *profile; // [8] debugging aid: cycles outside / inside the cell loop, trips, lane-trips, rounds
-#endif
 };
-#ifndef NFA_CONE_WALK_SPLIT
-#define NFA_CONE_WALK_SPLIT 0
-#endif
-#ifndef NFA_CONE_REFILL_SPLIT
-#define NFA_CONE_REFILL_SPLIT 1
-#endif
 constexpr uint32_t CONE_ARENA_BLOCK = 16u;          // arena entries a ray takes per atomic (a power of two)
 constexpr uint32_t CONE_ARENA_NONE = 0xFFFFFFFFu;    // the lane's arena state: the arena was full when this ray asked
 constexpr uint32_t CONE_ARENA_FRESH = 0xFFFFFFFEu;   //                         no entry yet
@@ -1331,11 +1276,9 @@ __device__ __forceinline__ bool cone_ray_masked(const nfa_traverse_args &a, cons
 }
 
 // one ray per lane, from its first span to its last
-#ifndef NFA_CONE_WALK_WAVES
-#define NFA_CONE_WALK_WAVES 6   /* 89 -> 80 registers: 6 waves per SIMD instead of 5; cfg 5's traversal 10.6 -> 10.1 ms (4 waves 11.4, 8 spill: 10.8) */
-#endif
+constexpr int CONE_WALK_WAVES = 6;   // 89 -> 80 registers: 6 waves per SIMD instead of 5; cfg 5's traversal 10.6 -> 10.1 ms (4 waves 11.4, 8 spill: 10.8)
 template <bool FUSED>
-__attribute__((amdgpu_waves_per_eu(NFA_CONE_WALK_WAVES, NFA_CONE_WALK_WAVES)))
+__attribute__((amdgpu_waves_per_eu(CONE_WALK_WAVES, CONE_WALK_WAVES)))
 __global__ __launch_bounds__(CONE_THREADS) void cone_walk_kernel(const nfa_traverse_args a, const ConeParams p_in)
 {
     __shared__ __attribute__((aligned(16))) char s_tab[3 * WK_TAB_AXIS];
@@ -1362,7 +1305,7 @@ __global__ __launch_bounds__(CONE_THREADS) void cone_walk_kernel(const nfa_trave
         unsigned long long w_cur = 0ull;
         uint32_t i_cur = 0u;
         while (cone_next_span<FUSED>(a, p, tid, o, d, near_plane, far_plane, ev, st, sp, span_tmax, w_cur, i_cur)) {
-            while (!cone_cell<NFA_CONE_WALK_SPLIT != 0>(a, p, tid, span_tmax, sp, w_cur, i_cur, st, arena_slot)) {}
+            while (!cone_cell<false>(a, p, tid, span_tmax, sp, w_cur, i_cur, st, arena_slot)) {}
             // The budget is spent: the last thing that happened was a sample (continuous), so the spans still to come would
             // change nothing (grid.cu:151,185: no fast-forward, no cell visited).
             if (limit > 0 && st.n_samples >= limit) break;
@@ -1379,9 +1322,6 @@ __global__ __launch_bounds__(CONE_THREADS) void cone_walk_kernel(const nfa_trave
 // lanes are still walking, sets up new rays (and the next spans of rays that crossed into another level) on the free
 // lanes, and re-enters.  Per ray the same functions as cone_walk_kernel: identical results.
 template <bool FUSED, bool STAGED /* the event list travels with the lane (n_grids <= 4) */>
-#ifdef NFA_CONE_REFILL_WAVES
-__attribute__((amdgpu_waves_per_eu(NFA_CONE_REFILL_WAVES, NFA_CONE_REFILL_WAVES)))
-#endif
 __global__ __launch_bounds__(CONE_THREADS) void cone_refill_kernel(const nfa_traverse_args a, const ConeParams p_in)
 {
     static_assert(!(FUSED && STAGED), "a fused walk has no event list");
@@ -1413,9 +1353,6 @@ __global__ __launch_bounds__(CONE_THREADS) void cone_refill_kernel(const nfa_tra
     unsigned long long w_cur = 0ull;
     uint32_t i_cur = 0u;
 
-#ifdef NFA_CONE_PROFILE
-    unsigned long long pf_setup = 0, pf_cells = 0, pf_trips = 0, pf_lanes = 0, pf_rounds = 0, pf_t = __builtin_amdgcn_s_memtime();
-#endif
     for (;;) {
         // Two passes: rays that left a span in the cell loop (their next span, or their end), then the rays handed to the
         // lanes that are free after that.
@@ -1454,9 +1391,6 @@ __global__ __launch_bounds__(CONE_THREADS) void cone_refill_kernel(const nfa_tra
             }
         }
         const unsigned long long walking = __ballot(phase == WALK);
-#ifdef NFA_CONE_PROFILE
-        { const unsigned long long t1 = __builtin_amdgcn_s_memtime(); pf_setup += t1 - pf_t; pf_t = t1; pf_rounds++; }
-#endif
         if (walking == 0ull) {
             if (next >= end) break;  // (every lane is IDLE here: SPAN and FINISH were resolved above)
             continue;
@@ -1465,25 +1399,12 @@ __global__ __launch_bounds__(CONE_THREADS) void cone_refill_kernel(const nfa_tra
         const int32_t n_walking = __popcll(walking);
         const int32_t need = next < end ? p.min_busy : (n_walking * 3 >> 2) > 1 ? (n_walking * 3 >> 2) : 1;
         do {
-#ifdef NFA_CONE_PROFILE
-            pf_trips++; pf_lanes += __popcll(__ballot(phase == WALK));
-#endif
             if (phase == WALK) {
-                if (cone_cell<NFA_CONE_REFILL_SPLIT != 0>(a, p, tid, span_tmax, sp, w_cur, i_cur, st, arena_slot))
+                if (cone_cell<true>(a, p, tid, span_tmax, sp, w_cur, i_cur, st, arena_slot))
                     phase = (limit > 0 && st.n_samples >= limit) ? FINISH : SPAN;  // budget spent: nothing after it changes the ray
             }
         } while (__popcll(__ballot(phase == WALK)) >= need);
-#ifdef NFA_CONE_PROFILE
-        { const unsigned long long t1 = __builtin_amdgcn_s_memtime(); pf_cells += t1 - pf_t; pf_t = t1; }
-#endif
     }
-#ifdef NFA_CONE_PROFILE
-    if (p.profile && lane == 0) {
-        unsigned long long *pr = p.profile + 8 * (wave & 127);
-        atomicAdd(pr + 0, pf_setup); atomicAdd(pr + 1, pf_cells); atomicAdd(pr + 2, pf_trips); atomicAdd(pr + 3, pf_lanes);
-        atomicAdd(pr + 4, pf_rounds); atomicAdd(pr + 5, 1ull);
-    }
-#endif
 }
 
 }  // namespace nfa
@@ -1558,26 +1479,14 @@ int nfa_traverse_runs(const nfa_traverse_args *pa, const uint32_t *bits, int32_t
     if (near_hint == near_hint && !tuning_env("NFA_WALK_NO_LATTICE")) lattice_table_build(p.lat, near_hint, a.step_size);
     const bool lattice = p.lat.n_rows >= 1 && p.lat.n_binades >= 1;
     if (!lattice && near_hint == near_hint) approach_table_build(p.approach, near_hint, a.step_size);
-#ifdef NFA_WALK_STAMPS
-    { const char *e = getenv("NFA_WALK_STAMPS_PTR"); p.stamps = e ? reinterpret_cast<unsigned long long *>(strtoull(e, nullptr, 0)) : nullptr; }
-    { const char *e = getenv("NFA_WALK_ORDER_PTR"); p.tile_order = e ? reinterpret_cast<const int32_t *>(strtoull(e, nullptr, 0)) : nullptr; }
-#endif
     const size_t shmem = 0;  // the lists are static LDS
     const unsigned grid = grid_1d(p.n_order, WK_THREADS, 1 << 20);
     const bool lim = a.traverse_steps_limit > 0;
-#define NFA_WALK_LAUNCH(K, F, L) hipLaunchKernelGGL((K<F, L>), dim3(grid), dim3(WK_THREADS), shmem, s, a, p)
-    if (lattice) {
-        if (fused && !lim)      NFA_WALK_LAUNCH(walk_lattice_kernel, true, false);
-        else if (fused)         NFA_WALK_LAUNCH(walk_lattice_kernel, true, true);
-        else if (!lim)          NFA_WALK_LAUNCH(walk_lattice_kernel, false, false);
-        else                    NFA_WALK_LAUNCH(walk_lattice_kernel, false, true);
-    } else {
-        if (fused && !lim)      NFA_WALK_LAUNCH(walk_kernel, true, false);
-        else if (fused)         NFA_WALK_LAUNCH(walk_kernel, true, true);
-        else if (!lim)          NFA_WALK_LAUNCH(walk_kernel, false, false);
-        else                    NFA_WALK_LAUNCH(walk_kernel, false, true);
-    }
-#undef NFA_WALK_LAUNCH
+    // (in the order the code object has always had them: the lattice form first, the fused kernels first)
+    static constexpr decltype(&walk_kernel<false, false>) kernels[2][2][2] = {   // [!lattice][!fused][lim]
+        {{walk_lattice_kernel<true, false>, walk_lattice_kernel<true, true>}, {walk_lattice_kernel<false, false>, walk_lattice_kernel<false, true>}},
+        {{walk_kernel<true, false>, walk_kernel<true, true>}, {walk_kernel<false, false>, walk_kernel<false, true>}}};
+    hipLaunchKernelGGL(kernels[!lattice][!fused][lim], dim3(grid), dim3(WK_THREADS), shmem, s, a, p);
     NFA_CHECK_LAUNCH("traverse_runs");
     return NFA_OK;
 }
@@ -1656,31 +1565,16 @@ int nfa_traverse_cone_walk(const nfa_traverse_args *pa, const uint32_t *bits, in
     p.n_order = ray_order ? n_order : a.n_rays;
     NFA_REQUIRE(!ray_order || (n_order >= 0 && n_order <= a.n_rays), "traverse_cone_walk: n_order out of range");
     if (ray_order && n_order == 0) return NFA_OK;
-#ifdef NFA_CONE_PROFILE
-    {   // debugging aid: env NFA_CONE_PROFILE_PTR = address of a zeroed device buffer of 128 x 8 uint64
-        const char *e = getenv("NFA_CONE_PROFILE_PTR");
-        p.profile = e ? reinterpret_cast<unsigned long long *>(strtoull(e, nullptr, 0)) : nullptr;
-    }
-#endif
-    const char *refill_env = tuning_env("NFA_REFILL");  // "0": one ray per lane also for limited walks; "chunk,min_busy": tuning
-    const char *refill_all = tuning_env("NFA_REFILL_ALL");   // "1": the refilling kernel for unlimited walks too (measurements)
-    if ((a.traverse_steps_limit > 0 || (refill_all && refill_all[0] == '1')) && !(refill_env && refill_env[0] == '0')) {
-        // entries per wave: enough of them that a lane is refilled several times, as long as the launch still fills the chip
-        int64_t chunk = ((p.n_order + 4095) / 4096 + 63) / 64 * 64;
-        chunk = chunk < 64 ? 64 : (chunk > 1024 ? 1024 : chunk);
-        int min_busy = 48;
-        if (refill_env) { long c = 0; int m = 0; if (sscanf(refill_env, "%ld,%d", &c, &m) == 2 && c >= 64 && m >= 1 && m <= 64) { chunk = c / 64 * 64; min_busy = m; } }
-        p.chunk = (int32_t)chunk; p.min_busy = min_busy;
-        const int64_t n_waves = (p.n_order + chunk - 1) / chunk;
-        constexpr int wpb = CONE_THREADS / 64;
-        const unsigned grid = (unsigned)((n_waves + wpb - 1) / wpb);
+    const RefillPlan plan = refill_plan(p.n_order, a.traverse_steps_limit);
+    p.chunk = (int32_t)plan.chunk; p.min_busy = plan.min_busy;
+    if (plan.refill) {
+        const unsigned grid = (unsigned)ceil_div64(ceil_div64(p.n_order, plan.chunk), CONE_THREADS / 64);   // waves, then workgroups
         const char *staged_env = tuning_env("NFA_CONE_STAGED");   // "0": event lists read from memory (A/B)
         const bool staged = !fused && 2 * a.n_grids <= CONE_EV_MAX && !(staged_env && staged_env[0] == '0');
         if (fused)       hipLaunchKernelGGL((cone_refill_kernel<true, false>), dim3(grid), dim3(CONE_THREADS), 0, s, a, p);
         else if (staged) hipLaunchKernelGGL((cone_refill_kernel<false, true>), dim3(grid), dim3(CONE_THREADS), 0, s, a, p);
         else             hipLaunchKernelGGL((cone_refill_kernel<false, false>), dim3(grid), dim3(CONE_THREADS), 0, s, a, p);
     } else {
-        p.chunk = 64; p.min_busy = 64;
         const unsigned grid = grid_1d(p.n_order, CONE_THREADS, 1 << 20);
         if (fused) hipLaunchKernelGGL((cone_walk_kernel<true>), dim3(grid), dim3(CONE_THREADS), 0, s, a, p);
         else       hipLaunchKernelGGL((cone_walk_kernel<false>), dim3(grid), dim3(CONE_THREADS), 0, s, a, p);

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Times the kernels of the sampler's traversal alone (walk + cumsum + expansion) with HIP events.
     python scripts/walk_bench.py [--res 128] [--rays image|random] [--reps 20] [--bin-rays]
-Build-time knobs for experiments go through NERFACC_AMD_EXTRA_FLAGS (e.g. -DNFA_WALK_WAVES=8)."""
+Extra compiler flags for experiments go through NERFACC_AMD_EXTRA_FLAGS (e.g. -Rpass-analysis=kernel-resource-usage); the
+traversal sources have no build-time switches, an experiment edits the constant it is about."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -2,6 +2,8 @@
 import os
 import re
 
+import pytest
+
 from conftest import ROOT
 
 
@@ -179,3 +181,246 @@ def test_segscan_argument_errors():
             assert rc == 0, (fn, kw, rc, lib.nfa_last_error())
         else:
             assert rc == -1 and lib.nfa_last_error() == msg.encode(), (fn, kw, rc, lib.nfa_last_error())
+
+
+# The traversal entry points (csrc/grid.hip, csrc/walk.hip): arguments in C order, and for each one its checks in the
+# order in which they fire: (what is wrong, the error text), None = the call returns NFA_OK without a launch.  Names of
+# nfa_traverse_args fields go into the struct when the entry point takes one.
+_TRAV = {
+    "nfa_traverse_grids": "args stream",
+    "nfa_traverse_runs": "args bits run_cnts runs max_runs overflow_count near_hint ray_order n_order stream",
+    "nfa_traverse_cone_walk": "args bits run_cnts runs max_runs overflow_count arena arena_capacity ray_order n_order stream",
+    "nfa_traverse_cone_runs": "args run_cnts runs max_runs overflow_count ray_order n_order stream",
+    "nfa_pack_walk_bits": "binaries n_grids res bits stream",
+    "nfa_ray_events": "rays_o rays_d n_rays aabbs n_aabbs t_sorted t_indices hits stream",
+    "nfa_expand_cone_arena": "arena n_entries step_size cone_angle packed_info t_starts t_ends ray_indices stream",
+}
+# arguments that are not (required) pointers, at values every check accepts
+_TRAV_SCALARS = {"max_runs": 8, "near_hint": float("nan"), "ray_order": None, "n_order": 0, "arena_capacity": 0,
+                 "n_grids": 1, "res": (8, 8, 8), "n_rays": 4, "n_aabbs": 1, "n_entries": 4, "step_size": 0.01, "cone_angle": 0.001}
+# a struct every check of nfa_traverse_runs accepts (one grid, intersection in the kernel, count pass); steps_limit_dev is
+# set so that nfa_traverse_runs makes no HIP call before its checks
+_ARGS_BASE = dict(n_rays=4, rays_o=P, rays_d=P, n_grids=1, res=(8, 8, 8), binaries=P, aabbs=P, near_planes=P, far_planes=P,
+                  step_size=0.01, cone_angle=0.0, traverse_steps_limit=0, mode=0, sm_cnts=P, steps_limit_dev=P)
+_EVENTS = dict(hits=P, t_sorted=P, t_indices=P)
+_HUGE = dict(res=(512, 512, 512), n_grids=16, **_EVENTS)   # 16 levels of 2^27 cells: 2^31 bits
+
+
+def _nulls(names, msg, **kw):
+    return [({n: None, **kw}, msg) for n in names.split()]
+
+
+def _run_record_checks(nm, cone, mode_words, beyond, inputs, null_msg):
+    """The checks nfa_traverse_runs, nfa_traverse_cone_walk and nfa_traverse_cone_runs have in common, in their order."""
+    angle = "cone_angle > 0" if cone else "cone_angle == 0"
+    return [
+        ({"step_size": 0.0}, f"{nm}: needs step_size > 0 and {angle}"),
+        ({"cone_angle": 0.0 if cone else 0.1}, f"{nm}: needs step_size > 0 and {angle}"),
+        ({"mode": 1}, f"{nm}: mode must be 0 (all rays) or 2 ({mode_words})"),
+        ({"mode": 2}, "traverse_steps_limit must be > 0 when over_allocate is true"),
+        *_nulls(inputs + " run_cnts runs", null_msg),
+        ({"max_runs": 0}, f"{nm}: max_runs must be in [1, 32]"),
+        ({"max_runs": 33}, f"{nm}: max_runs must be in [1, 32]"),
+        ({"n_grids": 0}, f"{nm}: bad grid shape"),
+        ({"res": (8, 0, 8)}, f"{nm}: bad grid shape"),
+        beyond,
+        ({"hits": P}, f"{nm}: t_sorted, t_indices and hits must be given together"),
+        ({"t_sorted": P, "t_indices": P}, f"{nm}: t_sorted, t_indices and hits must be given together"),
+        ({"n_grids": 2, "hits": None, "t_sorted": None, "t_indices": None}, f"{nm}: in-kernel intersection supports one grid"),
+    ]
+
+
+def _order_checks(nm):
+    return [
+        ({"ray_order": P, "n_order": -1}, f"{nm}: n_order out of range"),
+        ({"ray_order": P, "n_order": 5}, f"{nm}: n_order out of range"),
+        ({"ray_order": P, "n_order": 0}, None),
+    ]
+
+
+_WALK_INPUTS = "rays_o rays_d aabbs near_planes far_planes sm_cnts bits"
+_TRAV_CHECKS = {
+    "nfa_traverse_grids": [
+        ({"args": None}, "traverse_grids: null args"),
+        ({"n_rays": -1}, "traverse_grids: n_rays out of range"),
+        ({"n_rays": 1 << 31}, "traverse_grids: n_rays out of range"),
+        ({"n_rays": 0}, None),
+        ({"mode": 3}, "traverse_grids: mode must be 0, 1 or 2"),
+        ({"mode": -1}, "traverse_grids: mode must be 0, 1 or 2"),
+        *_nulls("rays_o rays_d binaries aabbs near_planes far_planes", "traverse_grids: null input pointer"),
+        ({"n_grids": 0}, "traverse_grids: bad grid shape"),
+        ({"res": (8, 8, 0)}, "traverse_grids: bad grid shape"),
+        ({"res": (2048, 1024, 1024)}, "traverse_grids: grid level too large"),
+        ({"hits": P}, "traverse_grids: t_sorted, t_indices and hits must be given together"),
+        ({"n_grids": 2}, "traverse_grids: in-kernel intersection supports one grid; pass t_sorted/t_indices/hits"),
+        ({"mode": 2}, "traverse_steps_limit must be > 0 when over_allocate is true"),
+        ({"sm_cnts": None}, "traverse_grids: nothing to compute", "alone"),   # (the next case asks for intervals: that would heal it)
+        ({"mode": 1, "iv_cnts": P}, "traverse_grids: interval outputs missing"),
+        ({"mode": 1, "sm_starts": None}, "traverse_grids: sample starts missing"),
+        ({"mode": 1, "sm_starts": P, "sm_t_starts": P}, "traverse_grids: direct emission needs sm_t_starts, sm_t_ends and no intervals"),
+        ({"mode": 1, "sm_starts": P}, "traverse_grids: sample outputs missing"),
+    ],
+    "nfa_traverse_runs": [
+        ({"args": None}, "traverse_runs: null args"),
+        ({"n_rays": -1}, "traverse_runs: n_rays out of range"),
+        ({"n_rays": 1 << 31}, "traverse_runs: n_rays out of range"),
+        ({"overflow_count": None}, "traverse_runs: overflow_count is null"),
+        ({"n_rays": 0}, None),
+        *_run_record_checks("traverse_runs", False, "rays_mask + limit",
+                            ({"res": (513, 8, 8)}, "traverse_runs: at most 512 cells per axis (use nfa_traverse_grids beyond)"),
+                            _WALK_INPUTS, "traverse_runs: null pointer"),
+        (_HUGE, "traverse_runs: grid too large"),
+        *_order_checks("traverse_runs"),
+    ],
+    "nfa_traverse_cone_walk": [
+        ({"args": None}, "traverse_cone_walk: null args"),
+        ({"n_rays": -1}, "traverse_cone_walk: n_rays out of range"),
+        ({"n_rays": 1 << 31}, "traverse_cone_walk: n_rays out of range"),
+        ({"overflow_count": None}, "traverse_cone_walk: overflow_count is null"),
+        # ---- from here on overflow_count has been cleared on the device
+        ({"arena_capacity": -16}, "traverse_cone_walk: arena_capacity must be a multiple of 16"),
+        ({"arena": P, "arena_capacity": 24}, "traverse_cone_walk: arena_capacity must be a multiple of 16"),
+        ({"n_rays": 0}, None),
+        *_run_record_checks("traverse_cone_walk", True, "rays_mask + traverse_steps_limit",
+                            ({"res": (8, 8, 513)}, "traverse_cone_walk: at most 512 cells per axis (use nfa_traverse_cone_runs beyond)"),
+                            _WALK_INPUTS, "traverse_cone_walk: null pointer (or interval outputs requested)"),
+        ({"res": (2, 2, 2)}, "traverse_cone_walk: a level of the grid copy must be a whole number of 64-bit words (at least 4 cells per axis) "
+                             "and the copy below 2^31 bits"),
+        (_HUGE, "traverse_cone_walk: a level of the grid copy must be a whole number of 64-bit words (at least 4 cells per axis) "
+                "and the copy below 2^31 bits"),
+        *_order_checks("traverse_cone_walk"),
+    ],
+    "nfa_traverse_cone_runs": [
+        ({"args": None}, "traverse_cone_runs: null args"),
+        ({"n_rays": -1}, "traverse_cone_runs: n_rays out of range"),
+        ({"n_rays": 1 << 31}, "traverse_cone_runs: n_rays out of range"),
+        ({"overflow_count": None}, "traverse_cone_runs: overflow_count is null"),
+        # ---- from here on overflow_count has been cleared on the device
+        ({"n_rays": 0}, None),
+        *_run_record_checks("traverse_cone_runs", True, "rays_mask + traverse_steps_limit",
+                            ({"res": (2048, 1024, 1024)}, "traverse_cone_runs: grid level too large"),
+                            "rays_o rays_d binaries aabbs near_planes far_planes sm_cnts",
+                            "traverse_cone_runs: null pointer (or interval outputs requested)"),
+        *_order_checks("traverse_cone_runs"),
+    ],
+    "nfa_pack_walk_bits": [
+        *_nulls("binaries res bits", "pack_walk_bits: bad arguments"),
+        ({"n_grids": 0}, "pack_walk_bits: bad arguments"),
+        ({"res": (0, 8, 8)}, "pack_walk_bits: 1..512 cells per axis"),
+        ({"res": (8, 513, 8)}, "pack_walk_bits: 1..512 cells per axis"),
+        ({"res": (512, 512, 512), "n_grids": 16}, "pack_walk_bits: grid too large"),
+    ],
+    "nfa_ray_events": [
+        ({"n_rays": -1}, "ray_events: 1..NFA_MAX_EVENT_LEVELS boxes"),
+        ({"n_aabbs": 0}, "ray_events: 1..NFA_MAX_EVENT_LEVELS boxes"),
+        ({"n_aabbs": 9}, "ray_events: 1..NFA_MAX_EVENT_LEVELS boxes"),
+        ({"n_rays": 0}, None),
+        *_nulls("rays_o rays_d aabbs t_sorted t_indices hits", "ray_events: null pointer"),
+    ],
+    "nfa_expand_cone_arena": [
+        ({"n_entries": -1}, "expand_cone_arena: negative n_entries"),
+        ({"n_entries": 0}, None),
+        *_nulls("arena packed_info t_starts t_ends ray_indices", "expand_cone_arena: null pointer"),
+        ({"step_size": 0.0}, "expand_cone_arena: step_size and cone_angle must be > 0"),
+        ({"cone_angle": 0.0}, "expand_cone_arena: step_size and cone_angle must be > 0"),
+    ],
+}
+# leading checks that are decided before the entry point makes its first HIP call (the others: all of them)
+_TRAV_HOST_ONLY = {"nfa_traverse_cone_walk": 4, "nfa_traverse_cone_runs": 4}
+
+
+# No case may get as far as a launch (the pointers are stand-ins).  Each case has something wrong with it, but two of them
+# merged can heal each other, so whatever passes every check still ends without a launch: an empty ray list for the
+# run-record entry points (their last early return), a fill pass without outputs for nfa_traverse_grids (its last checks).
+_TRAV_LAST_RESORT = {fn: {"ray_order": P, "n_order": 0} for fn in ("nfa_traverse_runs", "nfa_traverse_cone_walk", "nfa_traverse_cone_runs")}
+
+
+def _trav_args(fn):
+    if fn == "nfa_traverse_grids":
+        return {**_ARGS_BASE, "mode": 1}
+    return {**_ARGS_BASE, "cone_angle": 0.0 if fn == "nfa_traverse_runs" else 0.001}
+
+
+def _trav_call(lib, fn, kw, args_base, call_base):
+    import ctypes as C
+    from nerfacc_amd import _backend as B
+    names = _TRAV[fn].split()
+    takes_struct = names[0] == "args"
+    fields = {f[0] for f in B.TraverseArgs._fields_}
+    st = dict(args_base)
+    call = dict(call_base)
+    for k, v in kw.items():
+        (st if takes_struct and k in fields else call)[k] = v
+    a = B.TraverseArgs()
+    for k, v in st.items():
+        setattr(a, k, (C.c_int32 * 3)(*v) if k == "res" else v)
+    args = []
+    for n in names:
+        if n == "args":
+            args.append(C.byref(a) if call.get("args", 1) is not None else None)
+        elif n in call:
+            args.append(call[n])
+        elif n in _TRAV_SCALARS:
+            args.append(_TRAV_SCALARS[n])
+        else:
+            args.append(None if n == "stream" else P)
+    if not takes_struct and "res" in names:
+        i = names.index("res")
+        args[i] = (C.c_int32 * 3)(*args[i]) if args[i] is not None else None
+    lib.nfa_set_tuning(b"", None)  # leaves a known error text behind
+    return getattr(lib, fn)(*args), lib.nfa_last_error()
+
+
+def _trav_check(lib, fn, checks, first, last, args_over=None, call_base=None):
+    """checks[first:last], each alone, and each together with the first later check of another outcome: the earlier one fires."""
+    args_base = {**_trav_args(fn), **(args_over or {})}
+    call_base = {**_TRAV_LAST_RESORT.get(fn, {}), **(call_base or {})}
+    for i in range(first, last):
+        kw, msg, *alone = checks[i]
+        later = {} if alone else next((c[0] for c in checks[i + 1:] if c[1] != msg), {})
+        for case in (kw, {**later, **kw}):
+            rc, err = _trav_call(lib, fn, case, args_base, call_base)
+            if msg is None:
+                assert rc == 0, (fn, case, rc, err)
+            else:
+                assert rc == -1 and err == msg.encode(), (fn, case, rc, err, msg)
+
+
+def test_traversal_argument_errors():
+    """Every traversal entry point checks its arguments in a fixed order and reports the first failure with a fixed text.
+    Here: the checks that are decided on the host before the entry point's first HIP call (nfa_traverse_cone_walk and
+    nfa_traverse_cone_runs clear overflow_count on the device after their fourth; the rest of theirs is in the GPU test)."""
+    from nerfacc_amd import _backend as B
+    lib = B.load()
+    for fn, checks in _TRAV_CHECKS.items():
+        _trav_check(lib, fn, checks, 0, _TRAV_HOST_ONLY.get(fn, len(checks)))
+
+
+@pytest.mark.gpu
+def test_traversal_argument_errors_after_the_memset(dev):
+    """The checks of the run-record entry points that follow the clearing of overflow_count (a real device buffer here:
+    the stand-in address must not reach hipMemsetAsync), and which words of it each entry point clears."""
+    import torch
+    from nerfacc_amd import _backend as B
+    lib = B.load()
+    ovf = torch.empty(2, dtype=torch.int32, device=dev)
+    for fn, cleared, args_over in (("nfa_traverse_cone_walk", [0, 0], None), ("nfa_traverse_cone_runs", [0, 7], None),
+                                   ("nfa_traverse_runs", [0, 0], {"steps_limit_dev": None})):
+        checks = _TRAV_CHECKS[fn]
+        call_base = {"overflow_count": ovf.data_ptr()}
+        _trav_check(lib, fn, checks, 0, len(checks), args_over, call_base)
+        # the clearing comes before every check behind "overflow_count is null", the n_rays == 0 return included
+        for kw in ({"n_rays": 0}, {"step_size": 0.0}, {"ray_order": P, "n_order": 0}):
+            ovf.fill_(7)
+            torch.cuda.synchronize()
+            _trav_call(lib, fn, kw, {**_trav_args(fn), **(args_over or {})}, {**_TRAV_LAST_RESORT[fn], **call_base})
+            torch.cuda.synchronize()
+            assert ovf.tolist() == cleared, (fn, kw, ovf.tolist())
+    # a device-driven call (steps_limit_dev set) leaves overflow_count to nfa_testmode_begin
+    lim = torch.ones(1, dtype=torch.int32, device=dev)
+    ovf.fill_(7)
+    torch.cuda.synchronize()
+    rc, err = _trav_call(lib, "nfa_traverse_runs", {"step_size": 0.0}, {**_ARGS_BASE, "steps_limit_dev": lim.data_ptr()},
+                         {**_TRAV_LAST_RESORT["nfa_traverse_runs"], "overflow_count": ovf.data_ptr()})
+    torch.cuda.synchronize()
+    assert rc == -1 and err == b"traverse_runs: needs step_size > 0 and cone_angle == 0" and ovf.tolist() == [7, 7]
