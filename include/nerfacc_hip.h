@@ -589,6 +589,39 @@ int nfa_sh_fwd(const float *dirs, int64_t n_points, int32_t degree, float *out, 
 int nfa_sh_bwd(const float *dirs, const float *grad_out, int64_t n_points, int32_t degree, float *grad_dirs,
                nfa_stream_t stream);
 
+/* ------------------------------------------------------------------ sample positions */
+
+/* What every field does between sampling() and its encodings, in one pass over the samples.  Replaces the torch
+ * composition of ref: examples/utils.py:83-85 (positions = rays_o[ray_indices] + rays_d[ray_indices] * (t_starts + t_ends)
+ * [:, None] / 2.0) and of ref: examples/radiance_fields/ngp.py:42-66,158-164,185 (aabb normalisation, contract_to_unisphere,
+ * the inside-the-box selector, (dir + 1) / 2).
+ *   p = o[r] + (d[r] * (t_start + t_end)) / 2, each operation rounded on its own: bit-identical to the torch expression;
+ *   with a box {min xyz, max xyz} (aabb_host: 6 host floats read during the call, or aabb: 6 device floats; not both)
+ *   x = (p - min) / (max - min); contraction 1 (sphere, |.|_2) or 2 (cube, |.|_inf) then maps u = 2 x - 1, where the norm m
+ *   exceeds 1, to (2 - 1/m) (u / m), and x = u / 4 + 0.5 (the box lands on [0.25, 0.75]^3).
+ * rays_o / rays_d [n_rays, 3]; t_starts / t_ends [n_elems]; ray_indices [n_elems] in any order, or NULL for batched input
+ * of n_rays rows of samples_per_ray samples (ray = element / samples_per_ray).  An index outside [0, n_rays) gives NaN rows.
+ * Outputs, each optional, at least one: positions [n_elems, 3] (p, or x with a box); dirs [n_elems, 3] with dirs_mode 1
+ * (d[r]) or 2 ((d[r] + 1) / 2), NULL with dirs_mode 0; selector [n_elems] (needs a box): all of 0 < x < 1. */
+int nfa_sample_positions_fwd(const float *rays_o, const float *rays_d, const float *t_starts, const float *t_ends,
+                             const int64_t *ray_indices, int64_t n_rays, int64_t n_elems, int64_t samples_per_ray,
+                             const float *aabb_host, const float *aabb, int32_t contraction, int32_t dirs_mode,
+                             float *positions, float *dirs, uint8_t *selector, nfa_stream_t stream);
+/* Its backward.  g_positions [n_elems, 3] / g_dirs [n_elems, 3] are the gradients that arrived (either may be NULL); per
+ * sample g_p = J^T g_positions at the recomputed point and grad_t_starts = grad_t_ends = 1/2 d[r] . g_p.
+ * With grad_rays_o and / or grad_rays_d [n_rays, 3]: one pass of the segmented engine over samples grouped by ray
+ * (packed_info / tiles as for the other packed-segment entry points; ray_indices is not read): grad_rays_o[r] = sum g_p,
+ * grad_rays_d[r] = sum ((t_start + t_end) / 2 g_p + s g_dirs), s = 1 (dirs_mode 1) or 1/2 (2), each ray summed by one
+ * wave: no atomics, bitwise reproducible, zeros for empty rays; grad_t_starts / grad_t_ends optional; grad_p NULL.
+ * Without them: a flat pass for ray indices in any order (packed_info / tiles unused, g_positions required) that writes
+ * grad_p [n_elems, 3] = g_p and / or grad_t_starts / grad_t_ends; the caller reduces grad_p over rays. */
+int nfa_sample_positions_bwd(const float *rays_o, const float *rays_d, const float *t_starts, const float *t_ends,
+                             const int64_t *ray_indices, const float *g_positions, const float *g_dirs,
+                             const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays,
+                             int64_t n_elems, int64_t samples_per_ray, const float *aabb_host, const float *aabb,
+                             int32_t contraction, int32_t dirs_mode, float *grad_rays_o, float *grad_rays_d,
+                             float *grad_t_starts, float *grad_t_ends, float *grad_p, nfa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

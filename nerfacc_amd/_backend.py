@@ -115,6 +115,8 @@ _SIGS = {
     "nfa_hashgrid_bwd": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
     "nfa_sh_fwd": [_vp, _i64, _i32, _vp, _vp],
     "nfa_sh_bwd": [_vp, _vp, _i64, _i32, _vp, _vp],
+    "nfa_sample_positions_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
+    "nfa_sample_positions_bwd": [_vp] * 9 + [_i64, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "common.hip.h"
+#include "samples.h"
 
 namespace nfa {
 
@@ -1769,6 +1770,81 @@ struct DistortionBwdOp : OpBase {
     }
 };
 
+// ---- backward of nfa_sample_positions_fwd (samples.h) in one pass: per sample g_p = J^T g_x at the recomputed point
+//      (o[r], d[r] are known before the values: NEEDS_RID) and g_t_start = g_t_end = 1/2 d[r] . g_p; per ray the six sums
+//      g_o[r] = sum g_p and g_d[r] = sum (m g_p + dscale g_dirs), m = (t_start + t_end) / 2, written by the wave that owns
+//      the ray: no atomics (torch's index_add_ has them), the same bits every run, zeros for empty rays.
+template <bool VEC, int MODE>
+struct SamplePosBwdOp : OpBase {
+    static constexpr int NCH = 6;
+    static constexpr bool NEEDS_RID = true;
+    static constexpr bool TOTALS = true;
+    struct Raw { F4 a, b; float gx[3 * SE], gd[3 * SE]; };
+    const float *o, *d, *ts, *te, *gx, *gdirs;   // gx / gdirs may be null (no gradient arrived there)
+    SampleBox box;
+    float dscale;                                // d dirs / d d[r]: 1 ("raw") or 1/2 ("unit")
+    float *go, *gd, *gts, *gte;                  // each may be null
+    float tsv[SE], tev[SE], gxv[3 * SE], gdv[3 * SE], xv[SE][6], rt[SE];
+    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
+    {
+        ld4<VEC>(ts, q, r.a);
+        ld4<VEC>(te, q, r.b);
+        if (gx) load_rgb12(gx, VEC, q, r.gx);
+        if (gdirs) load_rgb12(gdirs, VEC, q, r.gd);
+    }
+    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
+    {
+#pragma unroll
+        for (int j = 0; j < SE; ++j) { tsv[j] = r.a.v[j]; tev[j] = r.b.v[j]; }
+#pragma unroll
+        for (int k = 0; k < 3 * SE; ++k) gxv[k] = gdv[k] = 0.0f;
+        if (gx) fix_rgb12(gx, VEC, pos, r.gx, gxv);
+        if (gdirs) fix_rgb12(gdirs, VEC, pos, r.gd, gdv);
+    }
+    __device__ __forceinline__ void pre(int j, int64_t, bool valid, int rid)
+    {
+        rt[j] = 0.0f;
+#pragma unroll
+        for (int ch = 0; ch < 6; ++ch) xv[j][ch] = 0.0f;
+        if (!valid) return;
+        float ro[3], rd[3], p[3] = {0.f, 0.f, 0.f}, g[3] = {gxv[3 * j], gxv[3 * j + 1], gxv[3 * j + 2]};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { ro[k] = o[3 * (int64_t)rid + k]; rd[k] = d[3 * (int64_t)rid + k]; }
+        if (MODE != SP_NONE) {
+            float lo[3], ext[3];
+            box_resolve(box, lo, ext);
+            if (MODE == SP_SPHERE || MODE == SP_CUBE) sample_point(ro, rd, tsv[j], tev[j], p);
+            sample_grad_point<MODE>(p, lo, ext, g);
+        }
+        const float m = (tsv[j] + tev[j]) / 2.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            xv[j][k] = g[k];
+            xv[j][3 + k] = m * g[k] + dscale * gdv[3 * j + k];
+        }
+        rt[j] = 0.5f * (rd[0] * g[0] + rd[1] * g[1] + rd[2] * g[2]);
+    }
+    __device__ __forceinline__ void store_pre(const Pos &) const {}
+    __device__ __forceinline__ float x(int j, int ch) const { return xv[j][ch]; }
+    __device__ __forceinline__ void emit(int, int64_t, bool, bool, int, int, const float *, const float *) const {}
+    __device__ __forceinline__ void store(const Pos &q)
+    {
+        if (gts) store4<VEC>(gts, q, rt);
+        if (gte) store4<VEC>(gte, q, rt);
+    }
+    __device__ __forceinline__ void put(int rid, const float *t) const
+    {
+        if (go) { go[3 * (int64_t)rid] = t[0]; go[3 * (int64_t)rid + 1] = t[1]; go[3 * (int64_t)rid + 2] = t[2]; }
+        if (gd) { gd[3 * (int64_t)rid] = t[3]; gd[3 * (int64_t)rid + 1] = t[4]; gd[3 * (int64_t)rid + 2] = t[5]; }
+    }
+    __device__ __forceinline__ void ray_done(int rid, const float t[6]) const { put(rid, t); }
+    __device__ __forceinline__ void empty_ray(int rid) const
+    {
+        const float z[6] = {0, 0, 0, 0, 0, 0};
+        put(rid, z);
+    }
+};
+
 // ------------------------------------------------------------------------------------------
 // Generic fallback: arbitrary (start, count) chunks, one wave per ray (semantics of
 // include/utils_scan.cuh incl. `normalize`).
@@ -2338,6 +2414,54 @@ int nfa_render_step_accumulate(const float *t_starts, const float *t_ends, const
         launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
     });
     NFA_CHECK_LAUNCH("render_step_accumulate");
+    return NFA_OK;
+}
+
+int nfa_sample_positions_bwd(const float *rays_o, const float *rays_d, const float *t_starts, const float *t_ends,
+                             const int64_t *ray_indices, const float *g_positions, const float *g_dirs,
+                             const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays, int64_t n_elems,
+                             int64_t samples_per_ray, const float *aabb_host, const float *aabb, int32_t contraction,
+                             int32_t dirs_mode, float *grad_rays_o, float *grad_rays_d, float *grad_t_starts,
+                             float *grad_t_ends, float *grad_p, nfa_stream_t stream)
+{
+    NFA_REQUIRE(n_rays >= 0 && n_elems >= 0 && samples_per_ray >= 0, "sample_positions_bwd: negative size");
+    NFA_REQUIRE(n_rays < ((int64_t)1 << 31) - 64, "sample_positions_bwd: too many rays");
+    NFA_REQUIRE(contraction >= 0 && contraction <= 2 && dirs_mode >= 0 && dirs_mode <= 2,
+                "sample_positions_bwd: contraction and dirs_mode must be 0, 1 or 2");
+    const bool has_box = aabb_host || aabb;
+    NFA_REQUIRE(has_box || contraction == 0, "sample_positions_bwd: contraction needs an aabb");
+    NFA_REQUIRE(!(aabb_host && aabb), "sample_positions_bwd: aabb given twice");
+    const bool per_ray = grad_rays_o || grad_rays_d;
+    if (n_elems == 0 && (n_rays == 0 || !per_ray)) return NFA_OK;
+    NFA_REQUIRE(rays_o && rays_d && t_starts && t_ends, "sample_positions_bwd: null pointer");
+    NFA_REQUIRE(!g_dirs || dirs_mode != 0, "sample_positions_bwd: g_dirs needs dirs_mode");
+    SampleBox box;
+    for (int k = 0; k < 3; ++k) { box.lo[k] = aabb_host ? aabb_host[k] : 0.0f; box.hi[k] = aabb_host ? aabb_host[3 + k] : 1.0f; }
+    box.dev = aabb;
+    const int mode = has_box ? SP_AABB + contraction : SP_NONE;
+    hipStream_t s = as_stream(stream);
+    if (!per_ray) {
+        NFA_REQUIRE(g_positions && (grad_p || grad_t_starts || grad_t_ends), "sample_positions_bwd: null pointer");
+        NFA_REQUIRE(ray_indices ? n_rays >= 1 : (samples_per_ray >= 1 && n_elems == n_rays * samples_per_ray),
+                    "sample_positions_bwd: without ray_indices n_elems must be n_rays * samples_per_ray");
+        launch_sample_positions_bwd_flat(mode, box, rays_o, rays_d, t_starts, t_ends, ray_indices, n_rays, n_elems, samples_per_ray,
+                                         g_positions, grad_p, grad_t_starts, grad_t_ends, s);
+        NFA_CHECK_LAUNCH("sample_positions_bwd");
+        return NFA_OK;
+    }
+    NFA_REQUIRE(packed_info && tiles && n_tiles >= 1, "sample_positions_bwd: packed_info/tiles is null");
+    NFA_REQUIRE((g_positions || g_dirs) && !grad_p, "sample_positions_bwd: per-ray sums need g_positions or g_dirs, and write no grad_p");
+    const bool vec = all_aligned16(t_starts, t_ends, g_positions, g_dirs, grad_t_starts, grad_t_ends);
+    dispatch_bool(vec, [&](auto V) {
+        dispatch_sample_mode(mode, [&](auto M) {
+            SamplePosBwdOp<decltype(V)::value, decltype(M)::value> op;
+            op.o = rays_o; op.d = rays_d; op.ts = t_starts; op.te = t_ends; op.gx = g_positions; op.gdirs = g_dirs;
+            op.box = box; op.dscale = dirs_mode == 2 ? 0.5f : 1.0f;
+            op.go = grad_rays_o; op.gd = grad_rays_d; op.gts = grad_t_starts; op.gte = grad_t_ends;
+            launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+        });
+    });
+    NFA_CHECK_LAUNCH("sample_positions_bwd");
     return NFA_OK;
 }
 
