@@ -6,6 +6,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/nerfacc_hip.h"
 
 #define NFA_WAVE 64
@@ -70,6 +72,38 @@ static inline unsigned grid_1d(int64_t n, int block, int64_t cap = 256 * 16)
     return (unsigned)g;
 }
 
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+template <typename... P>
+static inline bool all_aligned16(P... p) { return (aligned16(p) && ...); }
+
+// Host-side dispatch of a run-time value to a compile-time one: f(std::true_type / std::false_type), f(the channel
+// count 1..4 as std::integral_constant<int, C>), and f(the lanes per ray, a power of two 2..64, as
+// std::integral_constant<int, L>; anything else goes to 64).
+template <class F>
+static void dispatch_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+static void dispatch_channels(int c, F &&f)
+{
+    if (c == 4) f(std::integral_constant<int, 4>{});
+    else if (c == 3) f(std::integral_constant<int, 3>{});
+    else if (c == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 1>{});
+}
+template <class F>
+static void dispatch_lanes(int l, F &&f)
+{
+    if (l == 2) f(std::integral_constant<int, 2>{});
+    else if (l == 4) f(std::integral_constant<int, 4>{});
+    else if (l == 8) f(std::integral_constant<int, 8>{});
+    else if (l == 16) f(std::integral_constant<int, 16>{});
+    else if (l == 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
+
 // ---------------------------------------------------------------- wave64 primitives
 __device__ __forceinline__ int lane_id() { return __lane_id(); }
 
@@ -87,6 +121,21 @@ __device__ __forceinline__ int64_t wave_incl_sum_i64(int64_t v)
         if (lane >= off) v += u;
     }
     return v;
+}
+
+__device__ __forceinline__ float wave_sum_f32(float v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, NFA_WAVE);
+    return v;
+}
+
+// a wave-uniform 64-bit value into a scalar register pair
+__device__ __forceinline__ int64_t uniform64(int64_t v)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
 // Cross-lane moves as DPP modifiers (one VALU instruction each, no LDS crossbar round trip):

@@ -1,6 +1,6 @@
 // pdf.hip -- inverse-CDF importance sampling and per-ray searchsorted.
 //
-// Semantics: /root/reference/nerfacc/cuda/csrc/pdf.cu:98-167 (importance_sampling_kernel),
+// Semantics: ref: nerfacc/cuda/csrc/pdf.cu:98-167 (importance_sampling_kernel),
 // :169-241 (compute_intervels_kernel), :245-286 (searchsorted_kernel), :43-63 (upper_bound).
 // Structure (ours): the two reference kernels are fused; a power-of-two lane group owns one ray,
 // each lane inverts the CDF for one sample, neighbouring samples are exchanged with wave
@@ -11,20 +11,49 @@
 
 namespace nfa {
 
-__device__ __forceinline__ int64_t upper_bound_f(const float *__restrict__ data, int64_t start, int64_t end, float val)
+// upper_bound (pdf.cu:43-63) over [start, end): I = int64_t on rows in global memory, int on rows staged in LDS
+template <typename I>
+__device__ __forceinline__ I upper_bound(const float *data, I start, I end, float val)
 {
     while (start < end) {
-        const int64_t mid = start + ((end - start) >> 1);
+        const I mid = start + ((end - start) >> 1);
         if (!(data[mid] > val)) start = mid + 1;
         else end = mid;
     }
     return start;
 }
-__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi)
+// the two entries around the position p that upper_bound returned, clamped to the row [first, last]
+template <typename I>
+struct Bracket { I lower, upper; };
+template <typename I>
+__device__ __forceinline__ Bracket<I> bracket(I p, I first, I last)
 {
-    const int64_t m = v < hi ? v : hi;
-    return m > lo ? m : lo;
+    auto clamp = [&](I v) { const I m = v < last ? v : last; return m > first ? m : first; };
+    return {clamp(p - 1), clamp(p)};
 }
+// One round of the same bisection written with selects, for a wave-uniform number of rounds: a lane whose range is empty
+// idles and reads lds[fallback].
+__device__ __forceinline__ void bisect_step(int &start, int &end, float key, const float *lds, int fallback)
+{
+    const bool act = start < end;
+    const int mid = start + ((end - start) >> 1);
+    const bool right = !(lds[act ? mid : fallback] > key);
+    start = (act && right) ? mid + 1 : start;
+    end = (act && !right) ? mid : end;
+}
+
+// t at CDF value u between the bracketing entries (pdf.cu:146-166); a flat CDF step gives the midpoint
+__device__ __forceinline__ float invert_cdf(float u, float u_lower, float u_upper, float t_lower, float t_upper)
+{
+    const float du = u_upper - u_lower;
+    return du < 1e-10f ? (t_lower + t_upper) * 0.5f : (u - u_lower) * ((t_upper - t_lower) / du) + t_lower;
+}
+
+// The S + 1 interval edges from the S samples (pdf.cu:205-239): midpoints between neighbours, the outer two mirrored
+// and clipped to the ray's range.
+__device__ __forceinline__ float first_edge(float t, float t_next, float t_min) { return fmaxf(t - (t_next - t) * 0.5f, t_min); }
+__device__ __forceinline__ float mid_edge(float t, float t_prev) { return (t + t_prev) * 0.5f; }
+__device__ __forceinline__ float last_edge(float t, float t_prev, float t_max) { return fminf(t + (t - t_prev) * 0.5f, t_max); }
 
 // Philox4x32-10 (Salmon et al. 2011), counter layout of curand_init(seed, subsequence, offset).
 __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t subsequence, uint64_t offset)
@@ -45,27 +74,40 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t subseque
     }
     const uint32_t out[4] = {c0, c1, c2, c3};
     // curand_uniform: x * 2^-32 + 2^-33  (in (0, 1])
-    return (float)out[offset & 3] * 2.3283064365386963e-10f + 1.1641532182693481e-10f;
+    return (float)out[offset & 3] * 0x1p-32f + 0x1p-33f;
 }
 
-__device__ __forceinline__ int upper_bound_lds(const float *data, int start, int end, float val)
-{
-    while (start < end) {
-        const int mid = start + ((end - start) >> 1);
-        if (!(data[mid] > val)) start = mid + 1;
-        else end = mid;
-    }
-    return start;
-}
-
-__device__ __forceinline__ int64_t uniform64_pdf(int64_t v)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
+// The wave's index in the launch, and the number of waves.
+__device__ __forceinline__ int64_t wave_index() { return ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; }
+__device__ __forceinline__ int64_t wave_count() { return ((int64_t)gridDim.x * blockDim.x) >> 6; }
 
 constexpr int IS_STAGE_MAX = 512;  // CDF entries a wave may stage in LDS (x 2 arrays x 4 waves = 16 KiB per workgroup)
+
+// A wave owns blocks of RB consecutive rays (RB a multiple of the rays per group, at most 64) and walks a block in groups.
+// The jitter is one Philox draw per RAY (ten rounds of four 32-bit multiplies, quarter rate): lane i draws it for ray i of
+// the block once, the groups fetch it by shuffle -- with one ray per wave (S = 64) every lane would repeat the same 100+
+// instructions for every ray.
+struct WaveBlockWalk {
+    int64_t rb, next_rb;   // first ray of the block of this group / of the next one
+    int sub, next_sub;     // the group's first ray within its block
+    float lane_bias;
+    __device__ __forceinline__ explicit WaveBlockWalk(int64_t first) : rb(first), next_rb(first), sub(0), next_sub(0), lane_bias(0.5f) {}
+    // the first ray of this group; works out where the next group starts
+    __device__ __forceinline__ int64_t begin_group(int lane, int rays_per_group, int RB, int64_t n_rays, int64_t n_waves,
+                                                   int stratified, uint64_t seed, uint64_t offset)
+    {
+        if (sub == 0) {
+            lane_bias = 0.5f;
+            if (stratified && lane < RB && rb + lane < n_rays) lane_bias = philox_uniform(seed, (uint64_t)(rb + lane), offset);
+        }
+        next_rb = rb;
+        next_sub = sub + rays_per_group;
+        if (next_sub >= RB || rb + next_sub >= n_rays) { next_sub = 0; next_rb = rb + n_waves * RB; }
+        return rb + sub;
+    }
+    __device__ __forceinline__ float bias(int grp) const { return __shfl(lane_bias, sub + grp, 64); }   // of ray grp of the group
+    __device__ __forceinline__ void next_group() { rb = next_rb; sub = next_sub; }
+};
 
 // L lanes per ray (power of two <= 64); 64 / L rays per wave.
 // STAGED (batched input whose rays fit): the wave's rays are consecutive rows of one contiguous block, which is
@@ -95,15 +137,13 @@ __global__ __launch_bounds__(256) void importance_sampling_kernel(
     const int lane = lane_id();
     const int gl = lane & (L - 1);            // lane within the ray's group
     const int rays_per_wave = 64 / L;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t wave = wave_index(), n_waves = wave_count();
     float *lc = s_cdf[threadIdx.x >> 6], *lv = s_val[threadIdx.x >> 6];
-    // A wave owns blocks of RB consecutive rays (RB a multiple of 64 / L, at most 64).  The jitter is one Philox draw per RAY
-    // (ten rounds of four 32-bit multiplies, quarter rate): lane i draws it for ray i of the block once, the groups fetch
-    // it by shuffle -- with one ray per wave (S = 64) every lane would repeat the same 100+ instructions for every ray.
     // STAGED: the rows of the NEXT group of rays are requested (into registers) before the current group is searched, and
     // written to LDS when their turn comes: without that every group is one exposed memory latency (load -> LDS -> search
     // -> store, ~3 us) and the kernel runs at the rate occupancy x group / latency.
+    // (The request / write loops are written out in each of the four kernels that stage rows this way: behind a shared
+    // function the compiler addresses the requests differently and the kernels' register budgets move, up for <16, 4>.)
     constexpr int SLOTS = STAGED ? IS_STAGE_MAX / 64 : 1;
     float pc[SLOTS], pv[SLOTS];
     auto rows_here = [&](int64_t r0) { return (int)(min((int64_t)rays_per_wave, n_rays - r0) * n_edges_per_ray); };
@@ -118,21 +158,10 @@ __global__ __launch_bounds__(256) void importance_sampling_kernel(
                 pv[k] = in_vals[blk + (f < n_h ? f : 0)];
             }
     };
-    int64_t rb = wave * RB;
-    int sub = 0;
-    float lane_bias = 0.5f;
-    if (STAGED && rb < n_rays) prefetch(rb);
-    while (rb < n_rays) {
-        if (sub == 0) {
-            lane_bias = 0.5f;
-            if (stratified && lane < RB && rb + lane < n_rays) lane_bias = philox_uniform(seed, (uint64_t)(rb + lane), offset);
-        }
-        const int64_t r0 = rb + sub;
-        int64_t next_rb = rb;
-        int next_sub = sub + rays_per_wave;
-        if (next_sub >= RB || rb + next_sub >= n_rays) { next_sub = 0; next_rb = rb + n_waves * RB; }
-        const int cur_sub = sub;
-        rb = next_rb; sub = next_sub;
+    WaveBlockWalk walk(wave * RB);
+    if (STAGED && walk.rb < n_rays) prefetch(walk.rb);
+    while (walk.rb < n_rays) {
+        const int64_t r0 = walk.begin_group(lane, rays_per_wave, RB, n_rays, n_waves, stratified, seed, offset);
         const int64_t ray = r0 + lane / L;
         const bool ray_ok = ray < n_rays;
         int64_t base = 0, last = 0;
@@ -151,12 +180,12 @@ __global__ __launch_bounds__(256) void importance_sampling_kernel(
                     if (f < n_h) { lc[f] = pc[k]; lv[f] = pv[k]; }
                 }
             __builtin_amdgcn_wave_barrier();
-            if (next_rb < n_rays) prefetch(next_rb + next_sub);
+            if (walk.next_rb < n_rays) prefetch(walk.next_rb + walk.next_sub);
             lbase = (lane / L) * (int)n_edges_per_ray;
         }
         const int llast = lbase + (int)n_edges_per_ray - 1;
         float u_floor = 0.f, u_step = 0.f, t_min = 0.f, t_max = 0.f;
-        const float bias = __shfl(lane_bias, cur_sub + lane / L, 64);
+        const float bias = walk.bias(lane / L);
         if (ray_ok) {
             u_floor = STAGED ? lc[lbase] : cdfs[base];
             const float u_ceil = STAGED ? lc[llast] : cdfs[last];
@@ -173,19 +202,13 @@ __global__ __launch_bounds__(256) void importance_sampling_kernel(
                 const float u = u_floor + (sid + bias) * u_step;
                 float u_lower, u_upper, t_lower, t_upper;
                 if (STAGED) {
-                    const int p = upper_bound_lds(lc, lbase, llast, u);
-                    const int p0 = min(max(p - 1, lbase), llast), p1 = min(max(p, lbase), llast);
-                    u_lower = lc[p0]; u_upper = lc[p1]; t_lower = lv[p0]; t_upper = lv[p1];
+                    const Bracket<int> b = bracket(upper_bound(lc, lbase, llast, u), lbase, llast);
+                    u_lower = lc[b.lower]; u_upper = lc[b.upper]; t_lower = lv[b.lower]; t_upper = lv[b.upper];
                 } else {
-                    const int64_t p = upper_bound_f(cdfs, base, last, u);
-                    const int64_t p0 = clamp64(p - 1, base, last), p1 = clamp64(p, base, last);
-                    u_lower = cdfs[p0]; u_upper = cdfs[p1]; t_lower = in_vals[p0]; t_upper = in_vals[p1];
+                    const Bracket<int64_t> b = bracket(upper_bound(cdfs, base, last, u), base, last);
+                    u_lower = cdfs[b.lower]; u_upper = cdfs[b.upper]; t_lower = in_vals[b.lower]; t_upper = in_vals[b.upper];
                 }
-                if (u_upper - u_lower < 1e-10f) t = (t_lower + t_upper) * 0.5f;
-                else {
-                    const float scaling = (t_upper - t_lower) / (u_upper - u_lower);
-                    t = (u - u_lower) * scaling + t_lower;
-                }
+                t = invert_cdf(u, u_lower, u_upper, t_lower, t_upper);
                 if (out_sm) out_sm[ray * S + sid] = t;
             }
             // neighbours (pdf.cu:209-239)
@@ -197,18 +220,15 @@ __global__ __launch_bounds__(256) void importance_sampling_kernel(
                     emit_edge(ray, 0, t_min);
                     emit_edge(ray, 1, t_max);
                 } else if (sid == 0) {
-                    const float half_width = (t_next - t) * 0.5f;  // S >= 2 and L >= 2 guarantee lane 1 holds t_1
-                    emit_edge(ray, 0, fmaxf(t - half_width, t_min));
+                    emit_edge(ray, 0, first_edge(t, t_next, t_min));  // S >= 2 and L >= 2 guarantee lane 1 holds t_1
                 } else {
-                    emit_edge(ray, sid, (t + t_prev) * 0.5f);
-                    if (sid == S - 1) {
-                        const float half_width = (t - t_prev) * 0.5f;
-                        emit_edge(ray, sid + 1, fminf(t + half_width, t_max));
-                    }
+                    emit_edge(ray, sid, mid_edge(t, t_prev));
+                    if (sid == S - 1) emit_edge(ray, sid + 1, last_edge(t, t_prev, t_max));
                 }
             }
             t_carry = __shfl(t, L - 1, L);
         }
+        walk.next_group();
     }
 }
 
@@ -233,8 +253,7 @@ __global__ __launch_bounds__(256) void importance_sampling_rows_kernel(
     __shared__ float s_val[4][IS_STAGE_MAX];
     const int lane = lane_id();
     const int gl = lane & (LL - 1), grp = lane / LL;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t wave = wave_index(), n_waves = wave_count();
     float *lc = s_cdf[threadIdx.x >> 6], *lv = s_val[threadIdx.x >> 6];
     float pc[SLOTS], pv[SLOTS];
     auto rows_here = [&](int64_t r0) { return (int)min((int64_t)RPW, n_rays - r0) * n_edges; };
@@ -249,33 +268,21 @@ __global__ __launch_bounds__(256) void importance_sampling_rows_kernel(
                 pv[k] = v[f < n_h ? f : 0];
             }
     };
-    int64_t rb = uniform64_pdf(wave * RB);
-    int sub = 0;
-    float lane_bias = 0.5f;
-    if (rb < n_rays) prefetch(rb);
-    while (rb < n_rays) {
-        if (sub == 0) {
-            lane_bias = 0.5f;
-            if (stratified && lane < RB && rb + lane < n_rays) lane_bias = philox_uniform(seed, (uint64_t)(rb + lane), offset);
-        }
-        const int64_t r0 = rb + sub;
-        int64_t next_rb = rb;
-        int next_sub = sub + RPW;
-        if (next_sub >= RB || rb + next_sub >= n_rays) { next_sub = 0; next_rb = rb + n_waves * RB; }
-        const float bias = __shfl(lane_bias, sub + grp, 64);
-        rb = next_rb; sub = next_sub;
-        {
-            const int n_h = rows_here(r0);
-            __builtin_amdgcn_wave_barrier();
+    WaveBlockWalk walk(uniform64(wave * RB));
+    if (walk.rb < n_rays) prefetch(walk.rb);
+    while (walk.rb < n_rays) {
+        const int64_t r0 = walk.begin_group(lane, RPW, RB, n_rays, n_waves, stratified, seed, offset);
+        const float bias = walk.bias(grp);
+        const int n_h = rows_here(r0);
+        __builtin_amdgcn_wave_barrier();
 #pragma unroll
-            for (int k = 0; k < SLOTS; ++k)
-                if (64 * k < n_h) {
-                    const int f = lane + 64 * k;
-                    if (f < n_h) { lc[f] = pc[k]; lv[f] = pv[k]; }
-                }
-            __builtin_amdgcn_wave_barrier();
-            if (next_rb < n_rays) prefetch(next_rb + next_sub);
-        }
+        for (int k = 0; k < SLOTS; ++k)
+            if (64 * k < n_h) {
+                const int f = lane + 64 * k;
+                if (f < n_h) { lc[f] = pc[k]; lv[f] = pv[k]; }
+            }
+        __builtin_amdgcn_wave_barrier();
+        if (walk.next_rb < n_rays) prefetch(walk.next_rb + walk.next_sub);
         const bool ray_ok = r0 + grp < n_rays;
         const int lbase = ray_ok ? grp * n_edges : 0, llast = lbase + n_edges - 1;
         const float u_floor = lc[lbase], u_ceil = lc[llast], t_min = lv[lbase], t_max = lv[llast];
@@ -290,21 +297,13 @@ __global__ __launch_bounds__(256) void importance_sampling_rows_kernel(
         }
         for (int it = 0; it < n_rounds; ++it) {
 #pragma unroll
-            for (int i = 0; i < NB; ++i) {
-                const bool act = start[i] < end[i];
-                const int mid = start[i] + ((end[i] - start[i]) >> 1);
-                const bool right = !(lc[act ? mid : lbase] > u[i]);
-                start[i] = (act && right) ? mid + 1 : start[i];
-                end[i] = (act && !right) ? mid : end[i];
-            }
+            for (int i = 0; i < NB; ++i) bisect_step(start[i], end[i], u[i], lc, lbase);
         }
         float t[NB];
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
-            const int p0 = min(max(start[i] - 1, lbase), llast), p1 = min(max(start[i], lbase), llast);
-            const float u_lower = lc[p0], u_upper = lc[p1], t_lower = lv[p0], t_upper = lv[p1];
-            const float du = u_upper - u_lower;
-            t[i] = du < 1e-10f ? (t_lower + t_upper) * 0.5f : (u[i] - u_lower) * ((t_upper - t_lower) / du) + t_lower;
+            const Bracket<int> b = bracket(start[i], lbase, llast);
+            t[i] = invert_cdf(u[i], lc[b.lower], lc[b.upper], lv[b.lower], lv[b.upper]);
         }
         // edges (pdf.cu:205-239): the lane forms edge k = sample id of each of its samples, the ray's last sample also edge S
         float *iv = out_iv + r0 * (S + 1) + grp * (S + 1);
@@ -318,10 +317,10 @@ __global__ __launch_bounds__(256) void importance_sampling_rows_kernel(
             const float t_carry = __shfl(t[i > 0 ? i - 1 : 0], LL - 1, LL);   // (every lane takes part in a shuffle)
             if (i > 0 && gl == 0) t_prev = t_carry;
             const float t_next = __shfl_down(t[i], 1, LL);   // only the first sample of a ray looks at it (S >= 2: lane 1 holds t_1)
-            e[i] = sid == 0 ? fmaxf(t[i] - (t_next - t[i]) * 0.5f, t_min) : (t[i] + t_prev) * 0.5f;
+            e[i] = sid == 0 ? first_edge(t[i], t_next, t_min) : mid_edge(t[i], t_prev);
             if (S == 1) e[i] = t_min;  // one sample: its interval is the ray's whole range
             const bool ok = ray_ok && sid < S;
-            if (sid == S - 1) e_last = S == 1 ? t_max : fminf(t[i] + (t[i] - t_prev) * 0.5f, t_max);
+            if (sid == S - 1) e_last = S == 1 ? t_max : last_edge(t[i], t_prev, t_max);
             if (out_sm && ok) (out_sm + r0 * S)[grp * S + sid] = t[i];
             if (ok) iv[sid] = e[i];
             if (ok && sid == S - 1) iv[S] = e_last;
@@ -339,6 +338,7 @@ __global__ __launch_bounds__(256) void importance_sampling_rows_kernel(
                 if (ray_ok && sid < S) { (out_ts + r0 * S)[grp * S + sid] = te0[i]; (out_te + r0 * S)[grp * S + sid] = te1; }
             }
         }
+        walk.next_group();
     }
 }
 
@@ -358,8 +358,9 @@ __global__ __launch_bounds__(256) void importance_sampling_packed_kernel(
     int64_t *__restrict__ iv_ray_indices, uint8_t *__restrict__ iv_left, uint8_t *__restrict__ iv_right)
 {
     const int lane = lane_id(), gl = lane & (ISP_L - 1);
-    const int64_t group = (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * (64 / ISP_L) + lane / ISP_L;
-    const int64_t n_groups = (((int64_t)gridDim.x * blockDim.x) >> 6) * (64 / ISP_L);
+    const int64_t wave = wave_index(), n_waves = wave_count();
+    const int64_t group = wave * (64 / ISP_L) + lane / ISP_L;
+    const int64_t n_groups = n_waves * (64 / ISP_L);
     const int64_t n_iter = ceil_div64(n_rays, n_groups);
     for (int64_t it = 0; it < n_iter; ++it) {   // (uniform trip count: the shuffles below need every lane of the wave)
         const int64_t ray = group + it * n_groups;
@@ -390,14 +391,8 @@ __global__ __launch_bounds__(256) void importance_sampling_packed_kernel(
             float t = 0.f;
             if (ok) {  // pdf.cu:133-166
                 const float u = u_floor + (sid + bias) * u_step;
-                const int64_t p = upper_bound_f(cdfs, base, last, u);
-                const int64_t p0 = clamp64(p - 1, base, last), p1 = clamp64(p, base, last);
-                const float u_lower = cdfs[p0], u_upper = cdfs[p1], t_lower = in_vals[p0], t_upper = in_vals[p1];
-                if (u_upper - u_lower < 1e-10f) t = (t_lower + t_upper) * 0.5f;
-                else {
-                    const float scaling = (t_upper - t_lower) / (u_upper - u_lower);
-                    t = (u - u_lower) * scaling + t_lower;
-                }
+                const Bracket<int64_t> b = bracket(upper_bound(cdfs, base, last, u), base, last);
+                t = invert_cdf(u, cdfs[b.lower], cdfs[b.upper], in_vals[b.lower], in_vals[b.upper]);
                 sm_vals[o_sm + sid] = t;
                 sm_ray_indices[o_sm + sid] = ray;
             }
@@ -412,10 +407,10 @@ __global__ __launch_bounds__(256) void importance_sampling_packed_kernel(
                     iv_right[o_iv + j] = j > 0 ? 1 : 0;
                 };
                 if (S == 1) { edge(0, t_min); edge(1, t_max); }
-                else if (sid == 0) edge(0, fmaxf(t - (t_next - t) * 0.5f, t_min));
+                else if (sid == 0) edge(0, first_edge(t, t_next, t_min));
                 else {
-                    edge(sid, (t + t_prev) * 0.5f);
-                    if (sid == S - 1) edge(sid + 1, fminf(t + (t - t_prev) * 0.5f, t_max));
+                    edge(sid, mid_edge(t, t_prev));
+                    if (sid == S - 1) edge(sid + 1, last_edge(t, t_prev, t_max));
                 }
             }
             t_carry = __shfl(t, ISP_L - 1, ISP_L);
@@ -449,9 +444,9 @@ __global__ __launch_bounds__(256) void searchsorted_kernel(
             if (tid < q_total) {
                 const int64_t ray_id = tid / q_per_ray;
                 const int lbase = (int)((ray_id - r_first) * k_per_ray), llast = lbase + (int)k_per_ray - 1;
-                const int p = upper_bound_lds(lk, lbase, llast, q_vals[tid]);
-                ids_left[tid] = min(max(p - 1, lbase), llast) - lbase;
-                ids_right[tid] = min(max(p, lbase), llast) - lbase;
+                const Bracket<int> b = bracket(upper_bound(lk, lbase, llast, q_vals[tid]), lbase, llast);
+                ids_left[tid] = b.lower - lbase;
+                ids_right[tid] = b.upper - lbase;
             }
             continue;
         }
@@ -470,10 +465,9 @@ __global__ __launch_bounds__(256) void searchsorted_kernel(
         int64_t base, last;
         if (k_packed) { base = k_packed[2 * ray_id]; last = base + k_packed[2 * ray_id + 1] - 1; }
         else { base = ray_id * k_per_ray; last = base + k_per_ray - 1; }
-        const int64_t p = upper_bound_f(k_vals, base, last, q_vals[tid]);
-        const int64_t l = clamp64(p - 1, base, last), r = clamp64(p, base, last);
-        ids_left[tid] = q_batched ? l - base : l;
-        ids_right[tid] = q_batched ? r - base : r;
+        const Bracket<int64_t> b = bracket(upper_bound(k_vals, base, last, q_vals[tid]), base, last);
+        ids_left[tid] = q_batched ? b.lower - base : b.lower;
+        ids_right[tid] = q_batched ? b.upper - base : b.upper;
     }
 }
 
@@ -487,16 +481,24 @@ __global__ __launch_bounds__(256) void searchsorted_kernel(
 // in LDS (only the ray's own lane group touches it) and writes it once.
 constexpr int PL_STAGE_MAX = 1024;  // key entries (vals + cdfs [+ grad row]) a wave may stage
 
+// One interval's excess d = max(w - wo, 0) and its loss term l = d^2 / (w + eps); the gradients of l for an incoming
+// gradient g (taken where d > 0):  d l / d wo = -2 d / (w + eps);  d l / d w = 2 d / (w + eps) - d^2 / (w + eps)^2
+__device__ __forceinline__ float pdf_loss_excess(float w, float wo) { return fmaxf(w - wo, 0.0f); }
+__device__ __forceinline__ float pdf_loss_term(float w, float wo, float eps)
+{
+    const float d = pdf_loss_excess(w, wo);
+    return (d * d) / (w + eps);
+}
+struct PdfLossGrad { float gwo, gw; };
+__device__ __forceinline__ PdfLossGrad pdf_loss_grad(float w, float d, float eps, float g)
+{
+    const float inv = 1.0f / (w + eps);
+    return {-2.0f * d * inv * g, (2.0f * d * inv - d * d * inv * inv) * g};
+}
+
 // The mean form (PropNetEstimator.compute_loss takes `.mean()` of the loss, ref prop_net.py:151): the forward leaves one partial
 // sum per wave instead of the loss array (the caller adds them up: deterministic, the wave -> rows assignment is fixed), the
 // backward takes the scalar gradient of the mean.  Saves writing and re-reading the loss array and its expanded gradient.
-__device__ __forceinline__ float pl_wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void pdf_loss_fwd_kernel(const float *__restrict__ q_vals, const float *__restrict__ q_cdfs,
                                                            const float *__restrict__ k_vals, const float *__restrict__ k_cdfs,
                                                            int64_t n_rays, int Q1, int K1, int L, float eps,
@@ -508,8 +510,7 @@ __global__ __launch_bounds__(256) void pdf_loss_fwd_kernel(const float *__restri
     __shared__ float s_kc[4][PL_STAGE_MAX];
     const int lane = lane_id(), gl = lane & (L - 1), rpw = 64 / L, Q = Q1 - 1;
     float *kv = s_kv[threadIdx.x >> 6], *kc = s_kc[threadIdx.x >> 6];
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t wave = wave_index(), n_waves = wave_count();
     for (int64_t r0 = wave * rpw; r0 < n_rays; r0 += n_waves * rpw) {
         const int n_here = (int)min((int64_t)rpw, n_rays - r0);
         __builtin_amdgcn_wave_barrier();
@@ -521,13 +522,9 @@ __global__ __launch_bounds__(256) void pdf_loss_fwd_kernel(const float *__restri
             const int kb = slot * K1, kl = kb + K1 - 1;
             const float *qv = q_vals + ray * Q1, *qc = q_cdfs + ray * Q1;
             for (int j = gl; j < Q; j += L) {
-                const int pl = upper_bound_lds(kv, kb, kl, qv[j]);
-                const int pr = upper_bound_lds(kv, kb, kl, qv[j + 1]);
-                const int left = min(max(pl - 1, kb), kl), right = min(max(pr, kb), kl);
-                const float w = qc[j + 1] - qc[j];
-                const float wo = kc[right] - kc[left];
-                const float d = fmaxf(w - wo, 0.0f);
-                const float l = (d * d) / (w + eps);
+                const int left = bracket(upper_bound(kv, kb, kl, qv[j]), kb, kl).lower;
+                const int right = bracket(upper_bound(kv, kb, kl, qv[j + 1]), kb, kl).upper;
+                const float l = pdf_loss_term(qc[j + 1] - qc[j], kc[right] - kc[left], eps);
                 if (loss) loss[ray * Q + j] = l;
                 acc += l;
                 if (ids) ids[ray * Q + j] = (uint32_t)(left - kb) | ((uint32_t)(right - kb) << 16);
@@ -535,7 +532,7 @@ __global__ __launch_bounds__(256) void pdf_loss_fwd_kernel(const float *__restri
         }
     }
     if (partials) {
-        const float tot = pl_wave_sum(acc);
+        const float tot = wave_sum_f32(acc);
         if (lane == 0) partials[wave] = tot;
     }
 }
@@ -557,8 +554,7 @@ __global__ __launch_bounds__(256) void pdf_loss_fwd_rows_kernel(const float *__r
     __shared__ float s_kc[4][STAGE];
     const int lane = lane_id(), gl = lane & (LL - 1), grp = lane / LL, Q = Q1 - 1;
     float *kv = s_kv[threadIdx.x >> 6], *kc = s_kc[threadIdx.x >> 6];
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t wave = wave_index(), n_waves = wave_count();
     float pkv[SLOTS], pkc[SLOTS], pq[4];
     auto rows_here = [&](int64_t r0) { return (int)min((int64_t)RPW, n_rays - r0) * K1; };
     auto prefetch = [&](int64_t r0) {
@@ -575,12 +571,12 @@ __global__ __launch_bounds__(256) void pdf_loss_fwd_rows_kernel(const float *__r
         const float *qv = q_vals + r0 * Q1, *qc = q_cdfs + r0 * Q1;
         pq[0] = qv[qo]; pq[1] = qv[qo + 1]; pq[2] = qc[qo]; pq[3] = qc[qo + 1];
     };
-    int64_t r0 = uniform64_pdf(wave * RPW);
+    int64_t r0 = uniform64(wave * RPW);
     if (r0 < n_rays) prefetch(r0);
     while (r0 < n_rays) {
         const int64_t r_next = r0 + n_waves * RPW;
-        const int n_h = rows_here(r0);
         __builtin_amdgcn_wave_barrier();
+        const int n_h = rows_here(r0);
 #pragma unroll
         for (int k = 0; k < SLOTS; ++k)
             if (64 * k < n_h) {
@@ -594,18 +590,13 @@ __global__ __launch_bounds__(256) void pdf_loss_fwd_rows_kernel(const float *__r
         const int kb = (r0 + grp < n_rays) ? grp * K1 : 0, kl = kb + K1 - 1;
         int s0 = kb, e0 = kl, s1 = kb, e1 = kl;   // upper_bound(kv, qa), upper_bound(kv, qb) over [kb, kl)
         for (int it = 0; it < n_rounds; ++it) {
-            const bool a0 = s0 < e0, a1 = s1 < e1;
-            const int m0 = s0 + ((e0 - s0) >> 1), m1 = s1 + ((e1 - s1) >> 1);
-            const bool g0 = !(kv[a0 ? m0 : kb] > qa), g1 = !(kv[a1 ? m1 : kb] > qb);
-            s0 = (a0 && g0) ? m0 + 1 : s0; e0 = (a0 && !g0) ? m0 : e0;
-            s1 = (a1 && g1) ? m1 + 1 : s1; e1 = (a1 && !g1) ? m1 : e1;
+            bisect_step(s0, e0, qa, kv, kb);
+            bisect_step(s1, e1, qb, kv, kb);
         }
-        const int left = min(max(s0 - 1, kb), kl), right = min(max(s1, kb), kl);
-        const float wo = kc[right] - kc[left];
-        const float d = fmaxf(w - wo, 0.0f);
+        const int left = bracket(s0, kb, kl).lower, right = bracket(s1, kb, kl).upper;
         const int o = grp * Q + gl;
         if (ok) {
-            const float l = (d * d) / (w + eps);
+            const float l = pdf_loss_term(w, kc[right] - kc[left], eps);
             if (loss) (loss + r0 * Q)[o] = l;
             acc += l;
             if (ids) (ids + r0 * Q)[o] = (uint32_t)(left - kb) | ((uint32_t)(right - kb) << 16);
@@ -613,7 +604,7 @@ __global__ __launch_bounds__(256) void pdf_loss_fwd_rows_kernel(const float *__r
         r0 = r_next;
     }
     if (partials) {
-        const float tot = pl_wave_sum(acc);
+        const float tot = wave_sum_f32(acc);
         if (lane == 0) partials[wave] = tot;
     }
 }
@@ -631,8 +622,7 @@ __global__ __launch_bounds__(256) void pdf_loss_bwd_kernel(const float *__restri
     __shared__ float s_gq[4][PL_STAGE_MAX];
     const int lane = lane_id(), gl = lane & (L - 1), rpw = 64 / L, Q = Q1 - 1;
     float *gk = s_g[threadIdx.x >> 6], *gq = s_gq[threadIdx.x >> 6];
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t wave = wave_index(), n_waves = wave_count();
     for (int64_t r0 = wave * rpw; r0 < n_rays; r0 += n_waves * rpw) {
         const int n_here = (int)min((int64_t)rpw, n_rays - r0);
         __builtin_amdgcn_wave_barrier();
@@ -648,17 +638,14 @@ __global__ __launch_bounds__(256) void pdf_loss_bwd_kernel(const float *__restri
                 const uint32_t id = ids[ray * Q + j];
                 const int left = (int)(id & 0xFFFFu), right = (int)(id >> 16);
                 const float w = qc[j + 1] - qc[j];
-                const float d = fmaxf(w - (kc[right] - kc[left]), 0.0f);
+                const float d = pdf_loss_excess(w, kc[right] - kc[left]);
                 if (d > 0.0f) {
-                    // d l / d wo = -2 d / (w + eps);  d l / d w = 2 d / (w + eps) - d^2 / (w + eps)^2
-                    const float g = g_loss ? g_loss[ray * Q + j] : g_all, inv = 1.0f / (w + eps);
-                    const float gwo = -2.0f * d * inv * g;
-                    atomicAdd(&gk[kb + right], gwo);
-                    atomicAdd(&gk[kb + left], -gwo);
+                    const PdfLossGrad gr = pdf_loss_grad(w, d, eps, g_loss ? g_loss[ray * Q + j] : g_all);
+                    atomicAdd(&gk[kb + right], gr.gwo);
+                    atomicAdd(&gk[kb + left], -gr.gwo);
                     if (g_q_cdfs) {
-                        const float gw = (2.0f * d * inv - d * d * inv * inv) * g;
-                        atomicAdd(&gq[slot * Q1 + j + 1], gw);
-                        atomicAdd(&gq[slot * Q1 + j], -gw);
+                        atomicAdd(&gq[slot * Q1 + j + 1], gr.gw);
+                        atomicAdd(&gq[slot * Q1 + j], -gr.gw);
                     }
                 }
             }
@@ -687,8 +674,7 @@ __global__ __launch_bounds__(256) void pdf_loss_bwd_rows_kernel(const float *__r
     __shared__ float s_gq[4][64 + RPW];      // RPW rows of Q1 <= LL + 1 entries
     const int lane = lane_id(), gl = lane & (LL - 1), grp = lane / LL, Q = Q1 - 1;
     float *kc = s_kc[threadIdx.x >> 6], *gk = s_gk[threadIdx.x >> 6], *gq = s_gq[threadIdx.x >> 6];
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t wave = wave_index(), n_waves = wave_count();
     float pkc[SLOTS], pq0, pq1, pg;
     uint32_t pid;
     auto rows_here = [&](int64_t r0) { return (int)min((int64_t)RPW, n_rays - r0); };
@@ -708,7 +694,7 @@ __global__ __launch_bounds__(256) void pdf_loss_bwd_rows_kernel(const float *__r
         pid = (ids + r0 * Q)[lo];
         pg = g_loss ? (g_loss + r0 * Q)[lo] : g_all;
     };
-    int64_t r0 = uniform64_pdf(wave * RPW);
+    int64_t r0 = uniform64(wave * RPW);
     if (r0 < n_rays) prefetch(r0);
     while (r0 < n_rays) {
         const int64_t r_next = r0 + n_waves * RPW;
@@ -728,17 +714,14 @@ __global__ __launch_bounds__(256) void pdf_loss_bwd_rows_kernel(const float *__r
         const bool ok = (r0 + grp < n_rays) && gl < Q;
         const int kb = (r0 + grp < n_rays) ? grp * K1 : 0;
         const int left = min((int)(id & 0xFFFFu), K1 - 1), right = min((int)(id >> 16), K1 - 1);
-        const float d = fmaxf(w - (kc[kb + right] - kc[kb + left]), 0.0f);
+        const float d = pdf_loss_excess(w, kc[kb + right] - kc[kb + left]);
         if (ok && d > 0.0f) {
-            // d l / d wo = -2 d / (w + eps);  d l / d w = 2 d / (w + eps) - d^2 / (w + eps)^2
-            const float inv = 1.0f / (w + eps);
-            const float gwo = -2.0f * d * inv * g;
-            atomicAdd(&gk[kb + right], gwo);
-            atomicAdd(&gk[kb + left], -gwo);
+            const PdfLossGrad gr = pdf_loss_grad(w, d, eps, g);
+            atomicAdd(&gk[kb + right], gr.gwo);
+            atomicAdd(&gk[kb + left], -gr.gwo);
             if (g_q_cdfs) {
-                const float gw = (2.0f * d * inv - d * d * inv * inv) * g;
-                atomicAdd(&gq[grp * Q1 + gl + 1], gw);
-                atomicAdd(&gq[grp * Q1 + gl], -gw);
+                atomicAdd(&gq[grp * Q1 + gl + 1], gr.gw);
+                atomicAdd(&gq[grp * Q1 + gl], -gr.gw);
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -756,7 +739,30 @@ __global__ __launch_bounds__(256) void pdf_loss_bwd_rows_kernel(const float *__r
 
 }  // namespace nfa
 
+
 using namespace nfa;
+
+// lanes per ray: the power of two in [2, 64] that covers n entries (longer rows are walked in blocks of 64)
+static int lanes_per_ray(int64_t n)
+{
+    int L = 2;
+    while (L < 64 && L < n) L <<= 1;
+    return L;
+}
+// rays per wave block (the Philox draws of a block are shared out over the lanes): 64 when that still leaves >= 4096 waves
+static int rays_per_block(int64_t n_rays, int rays_per_wave)
+{
+    int RB = rays_per_wave;
+    while (RB < 64 && n_rays / (2 * RB) >= 4096) RB <<= 1;
+    return RB;
+}
+// rounds until a bisection range of n_edges - 1 entries is empty
+static int bisection_rounds(int n_edges)
+{
+    int n_rounds = 0;
+    while ((1 << n_rounds) <= n_edges - 1) ++n_rounds;
+    return n_rounds;
+}
 
 extern "C" {
 
@@ -771,49 +777,34 @@ static int launch_importance_sampling(const float *in_vals, const float *cdfs, c
     NFA_REQUIRE(in_vals && cdfs && out_intervals, "importance_sampling: null pointer");
     NFA_REQUIRE(in_packed_info || n_edges_per_ray >= 1, "importance_sampling: need packed_info or n_edges_per_ray >= 1");
     NFA_REQUIRE(transform == 0 || (out_ts && out_te), "importance_sampling: t_starts / t_ends missing");
-    int L = 2;
-    while (L < 64 && L < n_samples) L <<= 1;
+    const int L = lanes_per_ray(n_samples);
     const int64_t rays_per_wave = 64 / L;
-    // rays per wave block (the Philox draws of a block are shared out over the lanes): 64 when that still leaves >= 4096 waves
-    int RB = (int)rays_per_wave;
-    while (RB < 64 && n_rays / (2 * RB) >= 4096) RB <<= 1;
-    const int64_t n_waves = ceil_div64(n_rays, (int64_t)RB);
-    const unsigned grid = grid_1d(n_waves * 64, 256, 1 << 16);
+    const auto grid_for = [&](int RB) { return dim3(grid_1d(ceil_div64(n_rays, (int64_t)RB) * 64, 256, 1 << 16)); };
     const bool staged = !in_packed_info && rays_per_wave * n_edges_per_ray <= IS_STAGE_MAX;
     if (staged && n_samples <= 64 && n_edges_per_ray < (1 << 20)) {
-        int n_rounds = 0;
-        while ((1 << n_rounds) <= (int)n_edges_per_ray - 1) ++n_rounds;   // rounds until a range of n_edges - 1 entries is empty
+        const int n_rounds = bisection_rounds((int)n_edges_per_ray);
         // more than 16 samples per ray: 16 lanes per ray and 2 or 4 samples per lane (4 rays per group instead of 1-2:
         // the per-group work is shared and a lane's bisections overlap), if four CDF rows fit the stage
         const bool blocks = n_samples > 16 && 4 * n_edges_per_ray <= IS_STAGE_MAX;
         const int LL = blocks ? 16 : L, NB = blocks ? (n_samples > 32 ? 4 : 2) : 1;
-        const int64_t rpw = 64 / LL;
-        int RBk = (int)rpw;
-        while (RBk < 64 && n_rays / (2 * RBk) >= 4096) RBk <<= 1;
-        const unsigned gridk = grid_1d(ceil_div64(n_rays, (int64_t)RBk) * 64, 256, 1 << 16);
-#define NFA_IS_ROWS(L_, NB_)                                                                                              \
-    hipLaunchKernelGGL((importance_sampling_rows_kernel<L_, NB_>), dim3(gridk), dim3(256), 0, as_stream(stream), in_vals, cdfs, n_rays, \
-                       (int)n_edges_per_ray, (int)n_samples, n_rounds, RBk, stratified, seed, offset, out_intervals, out_samples, \
-                       transform, t_a, t_b, out_ts, out_te)
-        if (NB == 4) NFA_IS_ROWS(16, 4);
-        else if (NB == 2) NFA_IS_ROWS(16, 2);
-        else switch (LL) {
-            case 2: NFA_IS_ROWS(2, 1); break;
-            case 4: NFA_IS_ROWS(4, 1); break;
-            case 8: NFA_IS_ROWS(8, 1); break;
-            case 16: NFA_IS_ROWS(16, 1); break;
-            case 32: NFA_IS_ROWS(32, 1); break;
-            default: NFA_IS_ROWS(64, 1); break;
-        }
-#undef NFA_IS_ROWS
-    } else if (staged)
-        hipLaunchKernelGGL(importance_sampling_kernel<true>, dim3(grid), dim3(256), 0, as_stream(stream), in_vals, cdfs,
-                           in_packed_info, n_rays, n_edges_per_ray, n_samples, L, RB, stratified, seed, offset, out_intervals,
-                           out_samples, transform, t_a, t_b, out_ts, out_te);
-    else
-        hipLaunchKernelGGL(importance_sampling_kernel<false>, dim3(grid), dim3(256), 0, as_stream(stream), in_vals, cdfs,
-                           in_packed_info, n_rays, n_edges_per_ray, n_samples, L, RB, stratified, seed, offset, out_intervals,
-                           out_samples, transform, t_a, t_b, out_ts, out_te);
+        const int RB = rays_per_block(n_rays, 64 / LL);
+        auto launch = [&](auto ll, auto nb) {
+            hipLaunchKernelGGL((importance_sampling_rows_kernel<decltype(ll)::value, decltype(nb)::value>), grid_for(RB), dim3(256), 0,
+                               as_stream(stream), in_vals, cdfs, n_rays, (int)n_edges_per_ray, (int)n_samples, n_rounds, RB, stratified,
+                               seed, offset, out_intervals, out_samples, transform, t_a, t_b, out_ts, out_te);
+        };
+        using L16 = std::integral_constant<int, 16>;
+        if (NB == 4) launch(L16{}, std::integral_constant<int, 4>{});
+        else if (NB == 2) launch(L16{}, std::integral_constant<int, 2>{});
+        else dispatch_lanes(LL, [&](auto ll) { launch(ll, std::integral_constant<int, 1>{}); });
+    } else {
+        const int RB = rays_per_block(n_rays, (int)rays_per_wave);
+        dispatch_bool(staged, [&](auto ST) {
+            hipLaunchKernelGGL(importance_sampling_kernel<ST>, grid_for(RB), dim3(256), 0, as_stream(stream), in_vals, cdfs,
+                               in_packed_info, n_rays, n_edges_per_ray, n_samples, L, RB, stratified, seed, offset, out_intervals,
+                               out_samples, transform, t_a, t_b, out_ts, out_te);
+        });
+    }
     NFA_CHECK_LAUNCH("importance_sampling");
     return NFA_OK;
 }
@@ -867,62 +858,53 @@ int nfa_searchsorted(const float *q_vals, const int64_t *q_packed_info, const in
     NFA_REQUIRE(k_packed_info || k_per_ray >= 1, "searchsorted: batched key needs k_per_ray");
     // rays touched by 64 consecutive queries: at most 63 / q_per_ray + 2
     const bool staged = !q_packed_info && !k_packed_info && (63 / q_per_ray + 2) * k_per_ray <= IS_STAGE_MAX;
-    if (staged)
-        hipLaunchKernelGGL(searchsorted_kernel<true>, dim3(grid_1d(q_total, 256)), dim3(256), 0, as_stream(stream), q_vals,
+    dispatch_bool(staged, [&](auto ST) {
+        hipLaunchKernelGGL(searchsorted_kernel<ST>, dim3(grid_1d(q_total, 256)), dim3(256), 0, as_stream(stream), q_vals,
                            q_packed_info, q_ray_indices, q_n_rays, q_per_ray, q_total, k_vals, k_packed_info, k_per_ray,
                            ids_left, ids_right);
-    else
-        hipLaunchKernelGGL(searchsorted_kernel<false>, dim3(grid_1d(q_total, 256)), dim3(256), 0, as_stream(stream), q_vals,
-                           q_packed_info, q_ray_indices, q_n_rays, q_per_ray, q_total, k_vals, k_packed_info, k_per_ray,
-                           ids_left, ids_right);
+    });
     NFA_CHECK_LAUNCH("searchsorted");
     return NFA_OK;
 }
 
-static int pdf_loss_lanes(int Q, int K1, int Q1)
+// The launch of both directions of the loss: L lanes per ray, the grid, and whether the rows kernels apply (one query
+// interval per lane, the key rows of a group in half the stage).
+struct PdfLossPlan {
+    int L;
+    unsigned grid;
+    bool rows;
+};
+static PdfLossPlan pdf_loss_plan(int64_t n_rays, int32_t n_query_edges, int32_t n_key_edges)
 {
-    int L = 2;
-    while (L < 64 && L < Q) L <<= 1;
-    while (L < 64 && (64 / L) * (K1 > Q1 ? K1 : Q1) > PL_STAGE_MAX) L <<= 1;  // fewer rays per wave until the rows fit
-    return L;
+    int L = lanes_per_ray(n_query_edges - 1);
+    while (L < 64 && (64 / L) * (n_key_edges > n_query_edges ? n_key_edges : n_query_edges) > PL_STAGE_MAX) L <<= 1;  // fewer rays per wave until the rows fit
+    return {L, grid_1d(ceil_div64(n_rays, 64 / L) * 64, 256, 1 << 16),
+            n_query_edges - 1 <= L && (64 / L) * n_key_edges <= PL_STAGE_MAX / 2};
 }
-
-static unsigned pdf_loss_grid(int64_t n_rays, int32_t n_query_edges, int32_t n_key_edges)
+static int pdf_loss_check_sizes(const char *name, int64_t n_rays, int32_t n_query_edges, int32_t n_key_edges)
 {
-    const int L = pdf_loss_lanes(n_query_edges - 1, n_key_edges, n_query_edges);
-    return grid_1d(ceil_div64(n_rays, 64 / L) * 64, 256, 1 << 16);
+    NFA_REQUIRE(n_rays >= 0 && n_query_edges >= 2 && n_key_edges >= 1, "%s: bad sizes", name);
+    NFA_REQUIRE(n_key_edges <= PL_STAGE_MAX && n_query_edges <= PL_STAGE_MAX, "%s: rows longer than 1024 edges are not supported", name);
+    return NFA_OK;
 }
 
 static int pdf_loss_fwd_impl(const float *q_vals, const float *q_cdfs, const float *k_vals, const float *k_cdfs, int64_t n_rays,
                              int32_t n_query_edges, int32_t n_key_edges, float eps, float *loss, uint32_t *key_ids,
                              float *partials, nfa_stream_t stream)
 {
-    NFA_REQUIRE(n_rays >= 0 && n_query_edges >= 2 && n_key_edges >= 1, "pdf_loss_fwd: bad sizes");
-    NFA_REQUIRE(n_key_edges <= PL_STAGE_MAX && n_query_edges <= PL_STAGE_MAX, "pdf_loss_fwd: rows longer than 1024 edges are not supported");
+    if (const int rc = pdf_loss_check_sizes("pdf_loss_fwd", n_rays, n_query_edges, n_key_edges)) return rc;
     if (n_rays == 0) return NFA_OK;
     NFA_REQUIRE(q_vals && q_cdfs && k_vals && k_cdfs && (loss || partials), "pdf_loss_fwd: null pointer");
-    const int L = pdf_loss_lanes(n_query_edges - 1, n_key_edges, n_query_edges);
-    const unsigned grid = pdf_loss_grid(n_rays, n_query_edges, n_key_edges);
-    if (n_query_edges - 1 <= L && (64 / L) * n_key_edges <= PL_STAGE_MAX / 2) {
-        int n_rounds = 0;
-        while ((1 << n_rounds) <= (int)n_key_edges - 1) ++n_rounds;
-#define NFA_PL_ROWS(LL)                                                                                                   \
-    hipLaunchKernelGGL(pdf_loss_fwd_rows_kernel<LL>, dim3(grid), dim3(256), 0, as_stream(stream), q_vals, q_cdfs, k_vals, k_cdfs, \
-                       n_rays, (int)n_query_edges, (int)n_key_edges, n_rounds, eps, loss, key_ids, partials)
-        switch (L) {
-            case 2: NFA_PL_ROWS(2); break;
-            case 4: NFA_PL_ROWS(4); break;
-            case 8: NFA_PL_ROWS(8); break;
-            case 16: NFA_PL_ROWS(16); break;
-            case 32: NFA_PL_ROWS(32); break;
-            default: NFA_PL_ROWS(64); break;
-        }
-#undef NFA_PL_ROWS
-        NFA_CHECK_LAUNCH("pdf_loss_fwd");
-        return NFA_OK;
-    }
-    hipLaunchKernelGGL(pdf_loss_fwd_kernel, dim3(grid), dim3(256), 0, as_stream(stream), q_vals, q_cdfs, k_vals, k_cdfs,
-                       n_rays, (int)n_query_edges, (int)n_key_edges, L, eps, loss, key_ids, partials);
+    const PdfLossPlan plan = pdf_loss_plan(n_rays, n_query_edges, n_key_edges);
+    if (plan.rows) {
+        const int n_rounds = bisection_rounds((int)n_key_edges);
+        dispatch_lanes(plan.L, [&](auto ll) {
+            hipLaunchKernelGGL(pdf_loss_fwd_rows_kernel<decltype(ll)::value>, dim3(plan.grid), dim3(256), 0, as_stream(stream), q_vals,
+                               q_cdfs, k_vals, k_cdfs, n_rays, (int)n_query_edges, (int)n_key_edges, n_rounds, eps, loss, key_ids, partials);
+        });
+    } else
+        hipLaunchKernelGGL(pdf_loss_fwd_kernel, dim3(plan.grid), dim3(256), 0, as_stream(stream), q_vals, q_cdfs, k_vals, k_cdfs,
+                           n_rays, (int)n_query_edges, (int)n_key_edges, plan.L, eps, loss, key_ids, partials);
     NFA_CHECK_LAUNCH("pdf_loss_fwd");
     return NFA_OK;
 }
@@ -937,7 +919,7 @@ int nfa_pdf_loss_fwd(const float *q_vals, const float *q_cdfs, const float *k_va
 int64_t nfa_pdf_loss_partials(int64_t n_rays, int32_t n_query_edges, int32_t n_key_edges)
 {
     if (n_rays <= 0 || n_query_edges < 2 || n_key_edges < 1) return 0;
-    return (int64_t)pdf_loss_grid(n_rays, n_query_edges, n_key_edges) * 4;   // waves of the launch
+    return (int64_t)pdf_loss_plan(n_rays, n_query_edges, n_key_edges).grid * 4;   // waves of the launch
 }
 
 int nfa_pdf_loss_sum_fwd(const float *q_vals, const float *q_cdfs, const float *k_vals, const float *k_cdfs, int64_t n_rays,
@@ -951,31 +933,19 @@ static int pdf_loss_bwd_impl(const float *q_cdfs, const float *k_cdfs, const uin
                              int32_t n_query_edges, int32_t n_key_edges, float eps, const float *g_loss, const float *g_mean,
                              float *g_k_cdfs, float *g_q_cdfs, nfa_stream_t stream)
 {
-    NFA_REQUIRE(n_rays >= 0 && n_query_edges >= 2 && n_key_edges >= 1, "pdf_loss_bwd: bad sizes");
-    NFA_REQUIRE(n_key_edges <= PL_STAGE_MAX && n_query_edges <= PL_STAGE_MAX, "pdf_loss_bwd: rows longer than 1024 edges are not supported");
+    if (const int rc = pdf_loss_check_sizes("pdf_loss_bwd", n_rays, n_query_edges, n_key_edges)) return rc;
     if (n_rays == 0) return NFA_OK;
     NFA_REQUIRE(q_cdfs && k_cdfs && key_ids && (g_loss || g_mean) && g_k_cdfs, "pdf_loss_bwd: null pointer");
-    const int L = pdf_loss_lanes(n_query_edges - 1, n_key_edges, n_query_edges);
-    const unsigned grid = pdf_loss_grid(n_rays, n_query_edges, n_key_edges);
+    const PdfLossPlan plan = pdf_loss_plan(n_rays, n_query_edges, n_key_edges);
     const float count = (float)((double)n_rays * (double)(n_query_edges - 1));
-    if (n_query_edges - 1 <= L && (64 / L) * n_key_edges <= PL_STAGE_MAX / 2) {
-#define NFA_PLB_ROWS(LL)                                                                                                  \
-    hipLaunchKernelGGL(pdf_loss_bwd_rows_kernel<LL>, dim3(grid), dim3(256), 0, as_stream(stream), q_cdfs, k_cdfs, key_ids, n_rays, \
-                       (int)n_query_edges, (int)n_key_edges, eps, g_loss, g_k_cdfs, g_q_cdfs, g_mean, count)
-        switch (L) {
-            case 2: NFA_PLB_ROWS(2); break;
-            case 4: NFA_PLB_ROWS(4); break;
-            case 8: NFA_PLB_ROWS(8); break;
-            case 16: NFA_PLB_ROWS(16); break;
-            case 32: NFA_PLB_ROWS(32); break;
-            default: NFA_PLB_ROWS(64); break;
-        }
-#undef NFA_PLB_ROWS
-        NFA_CHECK_LAUNCH("pdf_loss_bwd");
-        return NFA_OK;
-    }
-    hipLaunchKernelGGL(pdf_loss_bwd_kernel, dim3(grid), dim3(256), 0, as_stream(stream), q_cdfs, k_cdfs, key_ids, n_rays,
-                       (int)n_query_edges, (int)n_key_edges, L, eps, g_loss, g_k_cdfs, g_q_cdfs, g_mean, count);
+    if (plan.rows)
+        dispatch_lanes(plan.L, [&](auto ll) {
+            hipLaunchKernelGGL(pdf_loss_bwd_rows_kernel<decltype(ll)::value>, dim3(plan.grid), dim3(256), 0, as_stream(stream), q_cdfs,
+                               k_cdfs, key_ids, n_rays, (int)n_query_edges, (int)n_key_edges, eps, g_loss, g_k_cdfs, g_q_cdfs, g_mean, count);
+        });
+    else
+        hipLaunchKernelGGL(pdf_loss_bwd_kernel, dim3(plan.grid), dim3(256), 0, as_stream(stream), q_cdfs, k_cdfs, key_ids, n_rays,
+                           (int)n_query_edges, (int)n_key_edges, plan.L, eps, g_loss, g_k_cdfs, g_q_cdfs, g_mean, count);
     NFA_CHECK_LAUNCH("pdf_loss_bwd");
     return NFA_OK;
 }

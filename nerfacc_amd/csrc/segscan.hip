@@ -28,8 +28,6 @@
 // with the lane/element order mirrored (DIR = -1).
 #include <stdlib.h>
 
-#include <type_traits>
-
 #include "common.hip.h"
 #include "samples.h"
 
@@ -364,13 +362,6 @@ __device__ __forceinline__ void scan_totals(const StepHeads &hd, FX &&xb, float 
         const float nxt = (hd.open_prefix && hd.lh[SE - 1] < 0) ? carry[ch] + av[0] : av[0];   // (see scan_values)
         carry[ch] = lane_value(hd.carry_on_lane_end ? nxt : incl, hd.carry_lane);
     }
-}
-
-__device__ __forceinline__ int64_t uniform64(int64_t v)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1905,27 +1896,6 @@ __global__ __launch_bounds__(256) void accumulate_atomic_kernel(const float *__r
         const float v = vals ? w[e] * vals[i] : w[e];
         atomicAdd(out + r * D + ch, v);
     }
-}
-
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-template <typename... P>
-static inline bool all_aligned16(P... p) { return (aligned16(p) && ...); }
-
-// Host-side dispatch of a run-time value to a compile-time one: f(std::true_type / std::false_type), and f(the channel
-// count 1..4 as std::integral_constant<int, C>).
-template <class F>
-static void dispatch_bool(bool b, F &&f)
-{
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
-}
-template <class F>
-static void dispatch_channels(int c, F &&f)
-{
-    if (c == 4) f(std::integral_constant<int, 4>{});
-    else if (c == 3) f(std::integral_constant<int, 3>{});
-    else if (c == 2) f(std::integral_constant<int, 2>{});
-    else f(std::integral_constant<int, 1>{});
 }
 
 }  // namespace nfa

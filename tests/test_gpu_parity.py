@@ -1012,9 +1012,27 @@ def test_importance_sampling_and_searchsorted(dev, oracle):
         assert_close(r_iv.vals, e_iv, atol=1e-6, rtol=1e-6); assert_close(r_sm.vals, e_sm, atol=1e-6, rtol=1e-6)
     r_iv, _ = na.importance_sampling(na.RayIntervals(vals=T(v2, dev)), T(c2, dev), 1)     # S == 1: the ray's whole range
     assert np.array_equal(r_iv.vals.cpu().numpy(), v2[:, [0, -1]])
+    from nerfacc_amd.estimators.prop_net import _transform_stot
+    # the short-row kernel's other lane counts, one sample per lane: 4 and 16 lanes per ray, and 32 and 64 with CDF rows too
+    # long for four of them to share the stage (4 * 200 > 512); 131 rays leave every one of them a ragged last group.  Once
+    # more with the fused s -> t mapping: same intervals, t rows bit-equal to the tensor expression on them.
+    for S3, E3 in ((3, 9), (12, 9), (20, 200), (40, 200)):
+        v3 = np.sort(rng.random((131, E3)), -1).astype(np.float32); c3 = np.sort(rng.random((131, E3)), -1).astype(np.float32)
+        for strat in (False, True):
+            torch.manual_seed(77)
+            seed, off = gen.initial_seed(), gen.get_offset()
+            r_iv, r_sm = na.importance_sampling(na.RayIntervals(vals=T(v3, dev)), T(c3, dev), S3, stratified=strat)
+            e_iv, e_sm = oracle.importance_sampling(v3, c3, S3, strat, seed=seed, offset=off)
+            assert_close(r_iv.vals, e_iv, atol=1e-6, rtol=1e-6); assert_close(r_sm.vals, e_sm, atol=1e-6, rtol=1e-6)
+            torch.manual_seed(77)
+            f_iv, f_sm, f_ts, f_te = na.importance_sampling(na.RayIntervals(vals=T(v3, dev)), T(c3, dev), S3, stratified=strat,
+                                                            transform=("lindisp", 0.2, 7.3))
+            assert torch.equal(r_iv.vals, f_iv.vals) and torch.equal(r_sm.vals, f_sm.vals)
+            t_ref = _transform_stot("lindisp", r_iv.vals, 0.2, 7.3)
+            assert f_ts.is_contiguous() and f_te.is_contiguous() and f_ts.shape == (131, S3)
+            assert torch.equal(f_ts, t_ref[:, :-1]) and torch.equal(f_te, t_ref[:, 1:])
     # s -> t mapping fused into the resampling: same intervals, and t rows bit-equal to the reference's tensor
     # expression (estimators/prop_net.py:215-229) on them, for both mappings, short and long rows, packed input too
-    from nerfacc_amd.estimators.prop_net import _transform_stot
     for kind, lo, hi in (("uniform", 2.0, 6.0), ("lindisp", 0.05, 1e3), ("lindisp", 0.2, 7.3)):
         for S in (2, 16, 150):
             p_iv, p_sm = na.importance_sampling(na.RayIntervals(vals=T(v, dev)), T(c, dev), S)
@@ -1335,7 +1353,7 @@ def test_pdf_loss_fused_matches_composition(dev):
     from nerfacc_amd.estimators.prop_net import _pdf_loss
     from nerfacc_amd.pdf import searchsorted
     rng = np.random.default_rng(5)
-    for R, Q1, K1 in ((513, 17, 65), (40, 65, 65), (7, 3, 2), (300, 129, 33)):
+    for R, Q1, K1 in ((513, 17, 65), (40, 65, 65), (7, 3, 2), (300, 129, 33), (131, 5, 9), (131, 8, 12), (131, 30, 40), (67, 4, 100)):
         def mk(n):
             v = np.sort(rng.uniform(0, 1, (R, n)).astype(np.float32), -1)
             c = np.sort(rng.uniform(0, 1, (R, n)).astype(np.float32), -1)
@@ -1368,7 +1386,8 @@ def test_pdf_loss_mean_form_matches_the_loss_array(dev):
     from nerfacc_amd.data_specs import RayIntervals
     from nerfacc_amd.estimators.prop_net import _pdf_loss, _pdf_loss_mean
     rng = np.random.default_rng(15)
-    for R, Q1, K1 in ((100_003, 17, 65), (513, 17, 65), (40, 65, 65), (7, 3, 2), (300, 129, 33), (1, 2, 1)):
+    for R, Q1, K1 in ((100_003, 17, 65), (513, 17, 65), (40, 65, 65), (7, 3, 2), (300, 129, 33), (1, 2, 1), (131, 5, 9), (131, 8, 12),
+                      (131, 30, 40), (67, 4, 100)):
         def mk(n):
             v = np.sort(rng.uniform(0, 1, (R, n)).astype(np.float32), -1)
             c = np.sort(rng.uniform(0, 1, (R, n)).astype(np.float32), -1)
