@@ -254,4 +254,167 @@ __device__ __forceinline__ void store_l2(int64_t *p, int64_t a, int64_t b)
     else *reinterpret_cast<nfa_v2l *>(p) = v;
 }
 
+// ---------------------------------------------------------------- what the traversal kernels of grid.hip and walk.hip share
+// Slab test, grid.cu:284-313 / include/utils_grid.cuh:10-55; tmin / tmax mean something only for a hit.
+__device__ __forceinline__ bool slab_test(const float o[3], const float inv[3], const float *bmin, const float *bmax, float near,
+                                          float far, float &tmin, float &tmax)
+{
+    float lo, hi;
+    if (inv[0] >= 0) { tmin = (bmin[0] - o[0]) * inv[0]; tmax = (bmax[0] - o[0]) * inv[0]; }
+    else             { tmin = (bmax[0] - o[0]) * inv[0]; tmax = (bmin[0] - o[0]) * inv[0]; }
+#pragma unroll
+    for (int a = 1; a < 3; ++a) {
+        if (inv[a] >= 0) { lo = (bmin[a] - o[a]) * inv[a]; hi = (bmax[a] - o[a]) * inv[a]; }
+        else             { lo = (bmax[a] - o[a]) * inv[a]; hi = (bmin[a] - o[a]) * inv[a]; }
+        if (tmin > hi || lo > tmax) return false;
+        if (lo > tmin) tmin = lo;
+        if (hi < tmax) tmax = hi;
+    }
+    if (tmax <= 0) return false;
+    tmin = fmaxf(tmin, near);
+    tmax = fminf(tmax, far);
+    return true;
+}
+
+// The event walk, grid.cu:125-150: the ray's next span (level, [this_tmin, this_tmax)) from its sorted intersection list,
+// `ev` the next event to look at (2 * G: none left).  EVENTS says where the list lives: index(i), t(i), hit(level).
+struct EventsInMemory {   // the caller's t_indices / t_sorted / hits rows
+    const int64_t *ti;
+    const float *ts;
+    const uint8_t *hits;
+    __device__ __forceinline__ EventsInMemory(const nfa_traverse_args &a, int64_t tid)
+        : ti(a.t_indices + tid * 2 * a.n_grids), ts(a.t_sorted + tid * 2 * a.n_grids), hits(a.hits + tid * a.n_grids) {}
+    __device__ __forceinline__ int64_t index(int32_t i) const { return ti[i]; }
+    __device__ __forceinline__ float t(int32_t i) const { return ts[i]; }
+    __device__ __forceinline__ bool hit(int32_t level) const { return hits[level] != 0; }
+};
+template <class EVENTS>
+__device__ __forceinline__ bool next_event_span(const EVENTS &e, int32_t G, float near_plane, float far_plane, int32_t &ev,
+                                                int32_t &level, float &this_tmin, float &this_tmax)
+{
+    while (ev < 2 * G - 1) {
+        const int32_t i = ev++;
+        const auto idx = e.index(i);
+        level = event_level(idx, G);
+        bool ok = (uint32_t)level < (uint32_t)G && e.hit(level);
+        if (ok && idx >= G) {  // leaving: inside the next grid?
+            const auto nidx = e.index(i + 1);
+            level = event_level(nidx, G);
+            ok = nidx >= G && (uint32_t)level < (uint32_t)G && e.hit(level);
+        }
+        this_tmin = fmaxf(e.t(i), near_plane);
+        this_tmax = fminf(e.t(i + 1), far_plane);
+        if (ok && this_tmin < this_tmax) return true;
+    }
+    return false;
+}
+// Run records of the cone-angle count passes (nfa_traverse_cone_runs, nfa_traverse_cone_walk; same format as traverse2.hip's):
+// {t_first : f32 | k_start : 31, continues_previous : 1}, slot-major.  With a cone angle a chain of samples is the recurrence
+// t <- t + max(step, t * cone) from its first distance, so {t_first, k_start} determines every sample of it; chains are cut
+// every CONE_RUN_CAP samples so that the expansion (expand_runs_kernel<EXP_CONE>) iterates the recurrence at most that often
+// per output.  The second walk of the fill pass becomes a coalesced expansion.
+constexpr int CONE_RUN_CAP = 64;
+struct RunOut {
+    int32_t *run_cnts;          // [n_rays]
+    unsigned long long *runs;   // [max_runs, n_rays]
+    int32_t max_runs;
+    int32_t *overflow;          // [1]
+    const int32_t *order;       // lane -> ray assignment (nfa_bin_rays / nfa_bin_rays_levels) or NULL
+    int64_t n_order;            // its entries (< n_rays: only the listed rays are walked; the others keep their outputs)
+};
+__device__ __forceinline__ unsigned long long run_record(float t_first, int32_t k_start, int32_t continues)
+{
+    return (unsigned long long)__float_as_uint(t_first) | ((unsigned long long)((uint32_t)k_start | (continues ? 0x80000000u : 0u)) << 32);
+}
+// the end of a ray of a count pass that leaves run records
+__device__ __forceinline__ void run_ray_close(const nfa_traverse_args &a, const RunOut &ro, int64_t tid, float t_last, int32_t n_samples,
+                                              int32_t n_runs)
+{
+    if (a.terminate_planes) a.terminate_planes[tid] = t_last;
+    a.sm_cnts[tid] = n_samples;
+    // rays with > 2^21 samples go to the serial fill (the expansion packs a 27-bit batch offset)
+    if (n_samples > (1 << 21) && n_runs <= ro.max_runs) n_runs = ro.max_runs + 1;
+    ro.run_cnts[tid] = n_runs;
+    if (n_runs > ro.max_runs) atomicAdd(ro.overflow, 1);
+}
+// a ray masked out by rays_mask (grid.cu:100; the reference leaves its outputs uninitialised, we define them)
+__device__ __forceinline__ bool ray_masked(const nfa_traverse_args &a, const RunOut &ro, int64_t tid)
+{
+    if (!(a.mode == 2 && a.rays_mask != nullptr && !a.rays_mask[tid])) return false;
+    if (a.terminate_planes) a.terminate_planes[tid] = a.near_planes[tid];
+    if (a.iv_cnts) a.iv_cnts[tid] = 0;
+    if (a.sm_cnts) a.sm_cnts[tid] = 0;
+    if (ro.run_cnts) ro.run_cnts[tid] = 0;
+    return true;
+}
+// The ray's planes, origin and direction; false for a ray without geometry.  A non-finite origin or direction: upstream its NaN
+// planes survive fmaxf / fminf as [near, far] and the ray is sampled all the way to the far plane (1e10 by default).  Here it
+// gets no samples.
+__device__ __forceinline__ bool ray_load(const nfa_traverse_args &a, int64_t tid, float &near_plane, float &far_plane, float o[3], float d[3])
+{
+    near_plane = a.near_planes[tid]; far_plane = a.far_planes[tid];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) { o[ax] = a.rays_o[3 * tid + ax]; d[ax] = a.rays_d[3 * tid + ax]; }
+    return isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]) && isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]);
+}
+
+// The refilling scheduler of the limited cone walks (traverse_steps_limit > 0: one iteration of the test-mode loop,
+// examples/utils.py:252-425).  Such walks stop after a handful of samples, i.e. after a number of cells that is geometric in the
+// local occupancy.  With one ray per lane from start to end a wave lasts as long as its unluckiest ray: on cfg 5 (2 % scattered
+// occupancy) the mean is 50 cells to the first sample, the maximum over 64 lanes about 240, and the lanes are busy a fifth of
+// the time (2.5 ms per call for 2 M rays where the cells themselves are worth 0.3 ms).  Here a wave (number `wave` of the
+// launch) owns `chunk` consecutive slots of the ray list and a lane that has finished its ray is given the next one: the wave
+// leaves its cell loop when fewer than `min_busy` lanes are still walking, sets up new rays (and the next spans of rays that
+// crossed into another level) on the free lanes, and re-enters; when the chunk is handed out, it stays until a quarter of the
+// walking lanes have left.  The WALKER holds a lane's ray and does the arithmetic -- the same functions as its one-ray-per-lane
+// kernel, so results are identical --:
+//     bool take(tid)      load ray tid; false: nothing to walk (masked: its outputs are written; or filtered out)
+//     bool next_span()    set up the ray's next span; false: it has none left
+//     int  cell()         visit one cell: RF_WALK (the span goes on), RF_SPAN (it is over), RF_FINISH (the sample budget is
+//                         spent: nothing after it changes the ray)
+//     void finish()       write the ray's outputs
+enum { RF_IDLE = 0, RF_SPAN = 1, RF_WALK = 2, RF_FINISH = 3 };
+template <class WALKER>
+__device__ __forceinline__ void refill_schedule(WALKER &w, const int32_t *order, int64_t n_walk, int64_t wave, int32_t chunk, int32_t min_busy)
+{
+    const int lane = lane_id();
+    const unsigned long long lanes_below = (1ull << lane) - 1ull;
+    int64_t next = wave * chunk;  // (wave-uniform) first slot not handed out yet
+    const int64_t end = next + chunk < n_walk ? next + chunk : n_walk;
+    int32_t phase = RF_IDLE;
+    for (;;) {
+        // Two passes: rays that left a span in the cell loop (their next span, or their end), then the rays handed to
+        // the lanes that are free after that.
+#pragma nounroll
+        for (int pass = 0; pass < 2; ++pass) {
+            if (phase == RF_SPAN) phase = w.next_span() ? RF_WALK : RF_FINISH;
+            if (phase == RF_FINISH) {
+                w.finish();
+                phase = RF_IDLE;
+            }
+            if (pass == 1) break;
+            // ---- free lanes take the next rays of the wave's chunk
+            const unsigned long long idle = __ballot(phase == RF_IDLE);
+            if (idle != 0ull && next < end) {
+                if (phase == RF_IDLE) {
+                    const int64_t slot = next + __popcll(idle & lanes_below);
+                    if (slot < end && w.take(order ? (int64_t)order[slot] : slot)) phase = RF_SPAN;
+                }
+                next += __popcll(idle);
+            }
+        }
+        const unsigned long long walking = __ballot(phase == RF_WALK);
+        if (walking == 0ull) {
+            if (next >= end) break;  // (every lane is idle here: RF_SPAN and RF_FINISH were resolved above)
+            continue;
+        }
+        // ---- cells, for as long as enough lanes have one to visit
+        const int32_t n_walking = __popcll(walking);
+        const int32_t need = next < end ? min_busy : (n_walking * 3 >> 2) > 1 ? (n_walking * 3 >> 2) : 1;
+        do {
+            if (phase == RF_WALK) phase = w.cell();
+        } while (__popcll(__ballot(phase == RF_WALK)) >= need);
+    }
+}
+
 }  // namespace nfa

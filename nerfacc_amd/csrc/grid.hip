@@ -37,27 +37,7 @@ const char *tuning_env(const char *name)
 }
 
 // ------------------------------------------------------------------------------------------
-// Slab test, grid.cu:284-313 / include/utils_grid.cuh:10-55.
-__device__ __forceinline__ bool slab_test(const float o[3], const float inv[3], const float *bmin,
-                                          const float *bmax, float near, float far, float &tmin,
-                                          float &tmax)
-{
-    float lo, hi;
-    if (inv[0] >= 0) { tmin = (bmin[0] - o[0]) * inv[0]; tmax = (bmax[0] - o[0]) * inv[0]; }
-    else             { tmin = (bmax[0] - o[0]) * inv[0]; tmax = (bmin[0] - o[0]) * inv[0]; }
-#pragma unroll
-    for (int a = 1; a < 3; ++a) {
-        if (inv[a] >= 0) { lo = (bmin[a] - o[a]) * inv[a]; hi = (bmax[a] - o[a]) * inv[a]; }
-        else             { lo = (bmax[a] - o[a]) * inv[a]; hi = (bmin[a] - o[a]) * inv[a]; }
-        if (tmin > hi || lo > tmax) return false;
-        if (lo > tmin) tmin = lo;
-        if (hi < tmax) tmax = hi;
-    }
-    if (tmax <= 0) return false;
-    tmin = fmaxf(tmin, near);
-    tmax = fminf(tmax, far);
-    return true;
-}
+// ray_aabb_intersect, grid.cu:284-313 (slab_test: common.hip.h)
 
 __global__ __launch_bounds__(256) void ray_aabb_kernel(const float *__restrict__ rays_o,
                                                        const float *__restrict__ rays_d, int64_t n_rays,
@@ -138,20 +118,8 @@ __global__ __launch_bounds__(256) void ray_events_kernel(const float *__restrict
 
 enum { EMIT_NONE = 0, EMIT_API = 1, EMIT_DIRECT = 2, EMIT_RUNS = 3 };
 
-// EMIT_RUNS: a count pass that also leaves run records (same format as traverse2.hip's: {t_first : f32 | k_start : 31,
-// continues_previous : 1}, slot-major).  With a cone angle a chain of samples is the recurrence t <- t + max(step,
-// t * cone) from its first distance, so {t_first, k_start} determines every sample of it; chains are cut every
-// CONE_RUN_CAP samples so that the expansion (expand_runs_kernel<EXP_CONE>) iterates the recurrence at most that often
-// per output.  The second walk of the fill pass becomes a coalesced expansion.
-constexpr int CONE_RUN_CAP = 64;
-struct RunOut {
-    int32_t *run_cnts;          // [n_rays]
-    unsigned long long *runs;   // [max_runs, n_rays]
-    int32_t max_runs;
-    int32_t *overflow;          // [1]
-    const int32_t *order;       // lane -> ray assignment (nfa_bin_rays / nfa_bin_rays_levels) or NULL
-    int64_t n_order;            // its entries (< n_rays: only the listed rays are walked; the others keep their outputs)
-};
+// EMIT_RUNS: a count pass that also leaves run records (common.hip.h: RunOut, run_record); the second walk of the fill pass
+// becomes a coalesced expansion (expand_runs_kernel<EXP_CONE>).
 
 struct RayState {
     float t_last;
@@ -241,15 +209,12 @@ __device__ __forceinline__ bool span_cell(const nfa_traverse_args &a, int64_t ti
     int32_t (&cur)[3] = sp.cur;
     const float this_tmax = sp.this_tmax;
 
-    // one sample [t_last, t_next) (grid.cu:219-258)
+    // what one sample [t_last, t_next) writes (grid.cu:219-258); the state moves on after it
     auto emit = [&](float t_next) {
         if (EMIT == EMIT_RUNS) {
             const bool cut = !st.continuous || st.run_len == CONE_RUN_CAP;
             if (cut) {
-                if (st.n_runs < ro.max_runs)
-                    ro.runs[(int64_t)st.n_runs * a.n_rays + tid] =
-                        (unsigned long long)f32_bits(st.t_last) |
-                        ((unsigned long long)((uint32_t)st.n_samples | (st.continuous ? 0x80000000u : 0u)) << 32);
+                if (st.n_runs < ro.max_runs) ro.runs[(int64_t)st.n_runs * a.n_rays + tid] = run_record(st.t_last, st.n_samples, st.continuous);
                 st.n_runs++;
             }
             st.run_len = cut ? 1 : st.run_len + 1;
@@ -283,9 +248,6 @@ __device__ __forceinline__ bool span_cell(const nfa_traverse_args &a, int64_t ti
                 if (a.sm_ray_indices) a.sm_ray_indices[idx] = tid;
             }
         }
-        st.n_samples++;
-        st.continuous = 1;
-        st.t_last = t_next;
     };
 
     const bool use_bricks = a.bricks != nullptr;
@@ -314,62 +276,10 @@ __device__ __forceinline__ bool span_cell(const nfa_traverse_args &a, int64_t ti
     if (fetch) w_next = a.bricks[bid_next];
 
     if (step_size <= 0.0f) {  // one interval per occupied cell (grid.cu:155,198,212)
-        if (occupied) emit(t_traverse);
+        if (occupied) { emit(t_traverse); st.n_samples++; st.continuous = 1; st.t_last = t_traverse; }
         else { st.t_last = t_traverse; st.continuous = 0; }
-    } else if (SPLIT) {
-        // The same two marches for walks that spend their time in empty cells (limited walks): the empty cell's is
-        // straight-line code -- eight select steps cover a cell of the finest level at the smallest step, the loop behind
-        // them runs only for what is left (a step that makes no progress leaves t_last unchanged, the loop then sees it and
-        // the jump below applies, as in the merged loop) -- and the sampling loop runs only when some lane has an occupied cell.
-        float dt = calc_dt(st.t_last, cone, step_size);
-        if (!occupied) {
-            if (t_traverse - st.t_last > 8.0f * dt) st.t_last = fast_forward_exact(st.t_last, t_traverse, dt);
-            const float half = dt * 0.5f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float t_next = st.t_last + dt;
-                st.t_last = (st.t_last + half < t_traverse) ? t_next : st.t_last;
-            }
-            for (;;) {
-                const float t_next = st.t_last + dt;
-                if (!((st.t_last + half < t_traverse) && (t_next != st.t_last))) break;
-                st.t_last = t_next;
-            }
-            if (st.t_last + half < t_traverse) st.t_last = t_traverse;
-            st.continuous = 0;
-        } else {
-            for (;;) {
-                const float t_next = st.t_last + dt;
-                const bool budget = !(limit > 0 && st.n_samples >= limit);
-                if (!((st.t_last + dt * 0.5f < t_traverse) && (t_next != st.t_last) && budget)) break;
-                emit(t_next);
-                dt = calc_dt(t_next, cone, step_size);
-            }
-        }
     } else {
-        // March to t_traverse.  An empty cell skips with the dt of its first step (grid.cu:193-206), an occupied
-        // one emits with dt recomputed per sample (grid.cu:207-262): one loop, so that a wave whose lanes sit in
-        // cells of both kinds runs it once.  (Measured: two loops, and empty cells walked ahead with the occupied
-        // ones sampled in batches, are both slower -- 14.0 and 22-24 ms against 12.8 ms on cfg 5.)
-        float dt = calc_dt(st.t_last, cone, step_size);
-        // a skip of many steps (cell much larger than the step): closed form (march.h), same result as the loop
-        if (!occupied && t_traverse - st.t_last > 8.0f * dt) st.t_last = fast_forward_exact(st.t_last, t_traverse, dt);
-        for (;;) {
-            const float t_next = st.t_last + dt;
-            const bool budget = !(occupied && limit > 0 && st.n_samples >= limit);
-            if (!((st.t_last + dt * 0.5f < t_traverse) && (t_next != st.t_last) && budget)) break;
-            if (occupied) {
-                emit(t_next);
-                dt = calc_dt(t_next, cone, step_size);
-            } else {
-                st.t_last = t_next;
-            }
-        }
-        if (!occupied) {
-            // left the loop before the target without progress (ours: the reference would spin): jump there
-            if (st.t_last + dt * 0.5f < t_traverse) st.t_last = t_traverse;
-            st.continuous = 0;
-        }
+        march_cell<SPLIT>(st.t_last, st.continuous, st.n_samples, occupied, t_traverse, step_size, cone, limit, emit);
     }
     st.brick_id = fetch ? bid_next : st.brick_id;
     st.brick_lo = fetch ? (uint32_t)w_next : st.brick_lo;
@@ -388,6 +298,21 @@ __device__ __forceinline__ void traverse_span(const nfa_traverse_args &a, int64_
     span_begin(a, o, d, inv, level, this_tmin, this_tmax, st, sp);
     if (a.traverse_steps_limit > 0 && st.n_samples >= a.traverse_steps_limit) return;
     while (!span_cell<EMIT, HAS_IV, HAS_SM, false>(a, tid, iv_base, sm_base, sp, st, ro)) {}
+}
+
+// The ray's next span: from its event list (common.hip.h), or (FUSED: a single grid, no list; grid.py:158-162 with the events
+// (t_min: enter 0), (t_max: leave 0)) from the slab test here: ev = 0 is the one span not taken yet.
+template <bool FUSED>
+__device__ __forceinline__ bool next_span(const nfa_traverse_args &a, int64_t tid, const float o[3], const float inv[3], float near_plane,
+                                          float far_plane, int32_t &ev, int32_t &level, float &this_tmin, float &this_tmax)
+{
+    if (FUSED) {
+        if (ev != 0) return false;
+        ev = 1;
+        level = 0;
+        return slab_test(o, inv, a.aabbs, a.aabbs + 3, near_plane, far_plane, this_tmin, this_tmax) && this_tmin < this_tmax;
+    }
+    return next_event_span(EventsInMemory(a, tid), a.n_grids, near_plane, far_plane, ev, level, this_tmin, this_tmax);
 }
 
 // EMIT_NONE  : count pass (mode 0)
@@ -409,14 +334,7 @@ __global__ __launch_bounds__(256) void traverse_kernel(const nfa_traverse_args a
         // (a wave runs as long as its longest ray: with unrelated rays the lanes of a wave get rays of similar length)
         const int64_t tid = (EMIT == EMIT_RUNS && ro.order) ? (int64_t)ro.order[slot_i] : slot_i;
         const bool overalloc = a.mode == 2;
-        if (overalloc && a.rays_mask != nullptr && !a.rays_mask[tid]) {  // grid.cu:100
-            // (the reference leaves these entries uninitialised; we define them)
-            if (a.terminate_planes) a.terminate_planes[tid] = a.near_planes[tid];
-            if (HAS_IV) a.iv_cnts[tid] = 0;
-            if (HAS_SM) a.sm_cnts[tid] = 0;
-            if (EMIT == EMIT_RUNS) ro.run_cnts[tid] = 0;
-            continue;
-        }
+        if (ray_masked(a, ro, tid)) continue;
         if (a.ray_filter != nullptr && a.ray_filter[tid] <= a.ray_filter_min) continue;
         int64_t iv_base = 0, sm_base = 0;
         if (EMIT != EMIT_NONE && EMIT != EMIT_RUNS) {
@@ -427,9 +345,8 @@ __global__ __launch_bounds__(256) void traverse_kernel(const nfa_traverse_args a
             if (HAS_IV) iv_base = a.iv_starts[tid];
             if (HAS_SM) sm_base = a.sm_starts[tid];
         }
-        const float near_plane = a.near_planes[tid], far_plane = a.far_planes[tid];
-        const float o[3] = {a.rays_o[3 * tid], a.rays_o[3 * tid + 1], a.rays_o[3 * tid + 2]};
-        const float d[3] = {a.rays_d[3 * tid], a.rays_d[3 * tid + 1], a.rays_d[3 * tid + 2]};
+        float near_plane, far_plane, o[3], d[3];
+        const bool ray_ok = ray_load(a, tid, near_plane, far_plane, o, d);
         const float inv[3] = {1.0f / d[0], 1.0f / d[1], 1.0f / d[2]};
 
         RayState st;
@@ -440,56 +357,22 @@ __global__ __launch_bounds__(256) void traverse_kernel(const nfa_traverse_args a
         st.brick_id = -1; st.brick_lo = st.brick_hi = 0u;
         st.n_runs = 0; st.run_len = 0;
 
-        // A ray with a non-finite origin or direction has no geometry: upstream its NaN planes survive fmaxf / fminf as
-        // [near, far] and the ray is sampled all the way to the far plane (1e10 by default).  Here it gets no samples.
-        const bool ray_ok = isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]) && isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]);
-        if (FUSED) {
-            // grid.py:158-162 with one grid: events are (t_min: enter 0), (t_max: leave 0).
-            float tmin, tmax;
-            const bool hit = ray_ok && slab_test(o, inv, a.aabbs, a.aabbs + 3, -INFINITY, INFINITY, tmin, tmax);
-            if (hit) {
-                const float this_tmin = fmaxf(tmin, near_plane);
-                const float this_tmax = fminf(tmax, far_plane);
-                if (this_tmin < this_tmax)
-                    traverse_span<EMIT, HAS_IV, HAS_SM>(a, tid, o, d, inv, 0, this_tmin, this_tmax, iv_base,
-                                                        sm_base, st, ro);
-            }
-        } else {
-            const int32_t G = a.n_grids;
-            const uint8_t *hits = a.hits + tid * G;
-            const float *ts = a.t_sorted + tid * 2 * G;
-            const int64_t *ti = a.t_indices + tid * 2 * G;
-            for (int32_t i = 0; i < (ray_ok ? 2 * G - 1 : 0); ++i) {  // grid.cu:125-150
-                const int64_t idx = ti[i];
-                const bool is_entering = idx < G;
-                int32_t level = event_level(idx, G);
-                if ((uint32_t)level >= (uint32_t)G || !hits[level]) continue;
-                if (!is_entering) {
-                    const int64_t nidx = ti[i + 1];
-                    if (nidx < G) continue;
-                    level = event_level(nidx, G);
-                    if ((uint32_t)level >= (uint32_t)G || !hits[level]) continue;
-                }
-                const float this_tmin = fmaxf(ts[i], near_plane);
-                const float this_tmax = fminf(ts[i + 1], far_plane);
-                if (this_tmin >= this_tmax) continue;
-                traverse_span<EMIT, HAS_IV, HAS_SM>(a, tid, o, d, inv, level, this_tmin, this_tmax, iv_base,
-                                                    sm_base, st, ro);
-                // The budget is spent: the last thing that happened was a sample (continuous), so the spans still to
-                // come would change nothing (grid.cu:151,185: no fast-forward, no cell visited) -- skip their set-up.
-                if (a.traverse_steps_limit > 0 && st.n_samples >= a.traverse_steps_limit) break;
-            }
-        }
-        if (a.terminate_planes) a.terminate_planes[tid] = st.t_last;
-        if (EMIT == EMIT_NONE || EMIT == EMIT_RUNS || overalloc) {
-            if (HAS_IV) a.iv_cnts[tid] = st.n_intervals;
-            if (HAS_SM) a.sm_cnts[tid] = st.n_samples;
+        int32_t ev = ray_ok ? 0 : 2 * a.n_grids, level;
+        float this_tmin, this_tmax;
+        while (next_span<FUSED>(a, tid, o, inv, near_plane, far_plane, ev, level, this_tmin, this_tmax)) {
+            traverse_span<EMIT, HAS_IV, HAS_SM>(a, tid, o, d, inv, level, this_tmin, this_tmax, iv_base, sm_base, st, ro);
+            // The budget is spent: the last thing that happened was a sample (continuous), so the spans still to
+            // come would change nothing (grid.cu:151,185: no fast-forward, no cell visited) -- skip their set-up.
+            if (FUSED || (a.traverse_steps_limit > 0 && st.n_samples >= a.traverse_steps_limit)) break;   // (FUSED: it was the only span)
         }
         if (EMIT == EMIT_RUNS) {
-            // rays with > 2^21 samples go to the serial fill (the expansion packs a 27-bit batch offset)
-            if (st.n_samples > (1 << 21) && st.n_runs <= ro.max_runs) st.n_runs = ro.max_runs + 1;
-            ro.run_cnts[tid] = st.n_runs;
-            if (st.n_runs > ro.max_runs) atomicAdd(ro.overflow, 1);
+            run_ray_close(a, ro, tid, st.t_last, st.n_samples, st.n_runs);
+            continue;
+        }
+        if (a.terminate_planes) a.terminate_planes[tid] = st.t_last;
+        if (EMIT == EMIT_NONE || overalloc) {
+            if (HAS_IV) a.iv_cnts[tid] = st.n_intervals;
+            if (HAS_SM) a.sm_cnts[tid] = st.n_samples;
         }
     }
 }
@@ -503,130 +386,52 @@ static void launch_traverse(const nfa_traverse_args &a, bool fused, hipStream_t 
 }
 
 // ------------------------------------------------------------------------------------------
-// Limited walks (traverse_steps_limit > 0: one iteration of the test-mode loop, examples/utils.py:252-425) stop after a
-// handful of samples, i.e. after a number of cells that is geometric in the local occupancy.  With one ray per lane from
-// start to end a wave lasts as long as its unluckiest ray: on cfg 5 (2 % scattered occupancy) the mean is 50 cells to the
-// first sample, the maximum over 64 lanes about 240, and the lanes are busy a fifth of the time (2.5 ms per call for
-// 2 M rays where the cells themselves are worth 0.3 ms).  Here a wave owns `chunk` consecutive slots of the ray list and
-// a lane that has finished its ray is given the next one: the wave leaves its cell loop when fewer than `min_busy` lanes
-// are still walking, sets up new rays (and the next spans of rays that crossed into another level) on the free lanes, and
-// re-enters.  Per ray the arithmetic is span_begin / span_cell, the same code as traverse_kernel: results are identical.
+// Limited walks (traverse_steps_limit > 0): the refilling scheduler (common.hip.h: refill_schedule) with this file's walker.
+// Per ray the arithmetic is span_begin / span_cell, the same code as traverse_kernel: results are identical.
+template <bool FUSED>
+struct BrickWalker {
+    const nfa_traverse_args &a;
+    const RunOut &ro;
+    int64_t tid;
+    int32_t ev;
+    float near_plane, far_plane, o[3], d[3], inv[3];
+    RayState st;
+    SpanState &sp;   // (the kernel's: a local of its own, as in traverse_span)
+    __device__ __forceinline__ bool take(int64_t ray)
+    {
+        tid = ray;
+        if (ray_masked(a, ro, tid)) return false;
+        if (a.ray_filter != nullptr && a.ray_filter[tid] <= a.ray_filter_min) return false;
+        const bool ray_ok = ray_load(a, tid, near_plane, far_plane, o, d);
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) inv[ax] = 1.0f / d[ax];
+        st.t_last = near_plane; st.continuous = 0; st.n_samples = 0;
+        st.brick_id = -1; st.n_runs = 0; st.run_len = 0;
+        ev = ray_ok ? 0 : 2 * a.n_grids;
+        return true;
+    }
+    __device__ __forceinline__ bool next_span()
+    {
+        int32_t level;
+        float this_tmin, this_tmax;
+        if (!nfa::next_span<FUSED>(a, tid, o, inv, near_plane, far_plane, ev, level, this_tmin, this_tmax)) return false;
+        span_begin(a, o, d, inv, level, this_tmin, this_tmax, st, sp);
+        return true;
+    }
+    __device__ __forceinline__ int cell()
+    {
+        if (!span_cell<EMIT_RUNS, false, true, true>(a, tid, 0, 0, sp, st, ro)) return RF_WALK;
+        return (a.traverse_steps_limit > 0 && st.n_samples >= a.traverse_steps_limit) ? RF_FINISH : RF_SPAN;
+    }
+    __device__ __forceinline__ void finish() { run_ray_close(a, ro, tid, st.t_last, st.n_samples, st.n_runs); }
+};
 template <bool FUSED>
 __global__ __launch_bounds__(256) void traverse_refill_kernel(const nfa_traverse_args a, const RunOut ro, const int32_t chunk,
                                                               const int32_t min_busy)
 {
-    enum { IDLE = 0, SPAN = 1, WALK = 2, FINISH = 3 };
-    const int lane = lane_id();
-    const unsigned long long lanes_below = (1ull << lane) - 1ull;
-    const int64_t n_walk = ro.order ? ro.n_order : a.n_rays;
-    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    int64_t next = wave * chunk;  // (wave-uniform) first slot not handed out yet
-    const int64_t end = next + chunk < n_walk ? next + chunk : n_walk;
-    const int32_t limit = a.traverse_steps_limit;
-    const int32_t G = a.n_grids;
-
-    int32_t phase = IDLE, ev = 0;
-    int64_t tid = 0;
-    float near_plane = 0.0f, far_plane = 0.0f;
-    float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, 0.0f}, inv[3] = {0.0f, 0.0f, 0.0f};
-    RayState st;
     SpanState sp;
-    st.t_last = 0.0f; st.continuous = 0; st.n_intervals = 0; st.n_samples = 0;
-    st.brick_id = -1; st.brick_lo = st.brick_hi = 0u; st.n_runs = 0; st.run_len = 0;
-
-    for (;;) {
-        // Two passes: rays that left a span in the cell loop (their next span, or their end), then the rays handed to
-        // the lanes that are free after that.
-#pragma nounroll
-        for (int pass = 0; pass < 2; ++pass) {
-            // ---- lanes between spans: the ray's next span, or its end
-            if (phase == SPAN) {
-                bool found = false;
-                if (FUSED) {
-                    if (ev == 0) {
-                        float tmin, tmax;
-                        if (slab_test(o, inv, a.aabbs, a.aabbs + 3, -INFINITY, INFINITY, tmin, tmax)) {
-                            const float this_tmin = fmaxf(tmin, near_plane);
-                            const float this_tmax = fminf(tmax, far_plane);
-                            if (this_tmin < this_tmax) { span_begin(a, o, d, inv, 0, this_tmin, this_tmax, st, sp); found = true; }
-                        }
-                    }
-                    ev = 1;
-                } else {
-                    const uint8_t *hits = a.hits + tid * G;
-                    const float *ts = a.t_sorted + tid * 2 * G;
-                    const int64_t *ti = a.t_indices + tid * 2 * G;
-                    while (ev < 2 * G - 1 && !found) {  // grid.cu:125-150
-                        const int32_t i = ev++;
-                        const int64_t idx = ti[i];
-                        int32_t level = event_level(idx, G);
-                        bool ok = (uint32_t)level < (uint32_t)G && hits[level] != 0;
-                        if (ok && idx >= G) {  // leaving: inside the next grid?
-                            const int64_t nidx = ti[i + 1];
-                            level = event_level(nidx, G);
-                            ok = nidx >= G && (uint32_t)level < (uint32_t)G && hits[level] != 0;
-                        }
-                        const float this_tmin = fmaxf(ts[i], near_plane);
-                        const float this_tmax = fminf(ts[i + 1], far_plane);
-                        if (ok && this_tmin < this_tmax) { span_begin(a, o, d, inv, level, this_tmin, this_tmax, st, sp); found = true; }
-                    }
-                }
-                phase = found ? WALK : FINISH;
-            }
-            if (phase == FINISH) {
-                if (a.terminate_planes) a.terminate_planes[tid] = st.t_last;
-                a.sm_cnts[tid] = st.n_samples;
-                if (st.n_samples > (1 << 21) && st.n_runs <= ro.max_runs) st.n_runs = ro.max_runs + 1;
-                ro.run_cnts[tid] = st.n_runs;
-                if (st.n_runs > ro.max_runs) atomicAdd(ro.overflow, 1);
-                phase = IDLE;
-            }
-            if (pass == 1) break;
-            // ---- free lanes take the next rays of the wave's chunk
-            const unsigned long long idle = __ballot(phase == IDLE);
-            if (idle != 0ull && next < end) {
-                if (phase == IDLE) {
-                    const int64_t slot = next + __popcll(idle & lanes_below);
-                    if (slot < end) {
-                        tid = ro.order ? (int64_t)ro.order[slot] : slot;
-                        if (a.mode == 2 && a.rays_mask != nullptr && !a.rays_mask[tid]) {  // grid.cu:100 (outputs defined, as in traverse_kernel)
-                            if (a.terminate_planes) a.terminate_planes[tid] = a.near_planes[tid];
-                            a.sm_cnts[tid] = 0;
-                            ro.run_cnts[tid] = 0;
-                        } else if (!(a.ray_filter != nullptr && a.ray_filter[tid] <= a.ray_filter_min)) {
-                            near_plane = a.near_planes[tid]; far_plane = a.far_planes[tid];
-    #pragma unroll
-                            for (int ax = 0; ax < 3; ++ax) {
-                                o[ax] = a.rays_o[3 * tid + ax];
-                                d[ax] = a.rays_d[3 * tid + ax];
-                                inv[ax] = 1.0f / d[ax];
-                            }
-                            st.t_last = near_plane; st.continuous = 0; st.n_samples = 0;
-                            st.brick_id = -1; st.n_runs = 0; st.run_len = 0;
-                            const bool ray_ok = isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]) && isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]);
-                            ev = ray_ok ? 0 : 2 * G;  // (no geometry: no spans, see traverse_kernel)
-                            phase = SPAN;
-                        }
-                    }
-                }
-                next += __popcll(idle);
-            }
-        }
-        const unsigned long long walking = __ballot(phase == WALK);
-        if (walking == 0ull) {
-            if (next >= end) break;  // (every lane is IDLE here: SPAN and FINISH were resolved above)
-            continue;
-        }
-        // ---- cells, for as long as enough lanes have one to visit
-        const int32_t n_walking = __popcll(walking);
-        const int32_t need = next < end ? min_busy : (n_walking * 3 >> 2) > 1 ? (n_walking * 3 >> 2) : 1;
-        do {
-            if (phase == WALK) {
-                if (span_cell<EMIT_RUNS, false, true, true>(a, tid, 0, 0, sp, st, ro))
-                    phase = (limit > 0 && st.n_samples >= limit) ? FINISH : SPAN;  // budget spent: nothing after it changes the ray (see traverse_kernel)
-            }
-        } while (__popcll(__ballot(phase == WALK)) >= need);
-    }
+    BrickWalker<FUSED> w{a, ro, 0, 0, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, RayState{0.0f, 0, 0, 0, -1, 0u, 0u, 0, 0}, sp};
+    refill_schedule(w, ro.order, ro.order ? ro.n_order : a.n_rays, (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), chunk, min_busy);
 }
 
 // ------------------------------------------------------------------------------------------

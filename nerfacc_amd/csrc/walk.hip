@@ -980,12 +980,7 @@ __global__ __launch_bounds__(WK_THREADS) void walk_kernel(const nfa_traverse_arg
 struct ConeParams {
     const uint32_t *bits;
     WalkLayout lay;
-    int32_t *run_cnts;           // [n_rays]
-    unsigned long long *runs;    // [max_runs, n_rays] slot-major
-    int32_t max_runs;
-    int32_t *overflow;           // [1]
-    const int32_t *order;        // lane -> ray assignment or NULL
-    int64_t n_order;
+    RunOut ro;                   // the counts and run records (common.hip.h), the lane -> ray assignment
     int32_t chunk, min_busy;     // cone_refill_kernel: entries of the ray list per wave; lanes that keep the cell loop going
     // Records that do not fit the ray's max_runs slots go to an ARENA instead of sending the ray to the serial fill pass (a
     // second full walk: 1.2 ms per step on cfg 5 for 0.1 % of the rays): the ray keeps max_runs - 1 records, its last slot
@@ -1000,7 +995,6 @@ struct ConeParams {
 constexpr uint32_t CONE_ARENA_BLOCK = 16u;          // arena entries a ray takes per atomic (a power of two)
 constexpr uint32_t CONE_ARENA_NONE = 0xFFFFFFFFu;    // the lane's arena state: the arena was full when this ray asked
 constexpr uint32_t CONE_ARENA_FRESH = 0xFFFFFFFEu;   //                         no entry yet
-constexpr int CONE_WALK_RUN_CAP = 64;   // = grid.hip's CONE_RUN_CAP: the expansion iterates the recurrence at most this often
 struct ConeRay {
     float t_last;
     int32_t continuous, n_samples, n_runs, run_len;
@@ -1023,7 +1017,6 @@ template <bool SPLIT>
 __device__ __forceinline__ bool cone_cell(const nfa_traverse_args &a, const ConeParams &p, int64_t tid, float this_tmax, WalkSpan &sp,
                                           unsigned long long &w_cur, uint32_t &i_cur, ConeRay &st, uint32_t *arena_slot /* LDS, this lane's */)
 {
-    const float step_size = a.step_size, cone = a.cone_angle;
     const int32_t limit = a.traverse_steps_limit;
     const uint32_t w_half = (i_cur & 32u) ? (uint32_t)(w_cur >> 32) : (uint32_t)w_cur;
     const bool occupied = __builtin_amdgcn_ubfe(w_half, i_cur, 1u) != 0u;   // bit (i_cur & 31) of the half
@@ -1049,18 +1042,18 @@ __device__ __forceinline__ bool cone_cell(const nfa_traverse_args &a, const Cone
     unsigned long long w_next = 0ull;
     if (fetch) w_next = reinterpret_cast<const unsigned long long *>(p.bits)[i_next >> 6];
 
-    // one sample [t_last, t_next) (grid.cu:219-258): counted, and a run record at the head of a chain and every 64 samples
-    auto emit = [&](float t_next) {
-        const bool cut = !st.continuous || st.run_len == CONE_WALK_RUN_CAP;
+    // what one sample [t_last, t_next) writes (grid.cu:219-258): a run record at the head of a chain and every 64 samples
+    auto emit = [&](float) {
+        const bool cut = !st.continuous || st.run_len == CONE_RUN_CAP;
         if (cut) {
-            const uint32_t kc = (uint32_t)st.n_samples | (st.continuous ? 0x80000000u : 0u);
-            const int32_t inl = p.arena ? p.max_runs - 1 : p.max_runs;   // records the ray keeps in its own slots
+            const unsigned long long rec = run_record(st.t_last, st.n_samples, st.continuous);
+            const int32_t inl = p.arena ? p.ro.max_runs - 1 : p.ro.max_runs;   // records the ray keeps in its own slots
             if (st.n_runs < inl) {
-                p.runs[(int64_t)st.n_runs * a.n_rays + tid] = (unsigned long long)f32_bits(st.t_last) | ((unsigned long long)kc << 32);
+                p.ro.runs[(int64_t)st.n_runs * a.n_rays + tid] = rec;
             } else if (p.arena) {
                 uint32_t e = *arena_slot;                                // the ray's previous arena entry (CONE_ARENA_NONE: gave up)
                 if (st.n_runs == inl) {
-                    p.runs[(int64_t)inl * a.n_rays + tid] = 0x7FC00000ull | ((unsigned long long)(uint32_t)st.n_samples << 32);
+                    p.ro.runs[(int64_t)inl * a.n_rays + tid] = 0x7FC00000ull | ((unsigned long long)(uint32_t)st.n_samples << 32);
                     e = CONE_ARENA_FRESH;
                 } else if (e < CONE_ARENA_NONE) {
                     reinterpret_cast<uint32_t *>(p.arena + e)[3] = (uint32_t)st.run_len;   // the previous entry is complete: its samples
@@ -1069,7 +1062,7 @@ __device__ __forceinline__ bool cone_cell(const nfa_traverse_args &a, const Cone
                     e = (e == CONE_ARENA_FRESH || ((e + 1u) & (CONE_ARENA_BLOCK - 1u)) == 0u) ? (uint32_t)atomicAdd(p.arena_count, (int32_t)CONE_ARENA_BLOCK)
                                                                                              : e + 1u;
                     if (e + CONE_ARENA_BLOCK <= (uint32_t)p.arena_cap || (e & (CONE_ARENA_BLOCK - 1u)) != 0u)
-                        p.arena[e] = make_uint4(f32_bits(st.t_last), kc, (uint32_t)tid, 0u);
+                        p.arena[e] = make_uint4((uint32_t)rec, (uint32_t)(rec >> 32), (uint32_t)tid, 0u);
                     else
                         e = CONE_ARENA_NONE;                             // the arena is full: this ray goes to the serial fill pass
                 }
@@ -1078,201 +1071,97 @@ __device__ __forceinline__ bool cone_cell(const nfa_traverse_args &a, const Cone
             st.n_runs++;
         }
         st.run_len = cut ? 1 : st.run_len + 1;
-        st.n_samples++;
-        st.continuous = 1;
-        st.t_last = t_next;
     };
-    // March to t_traverse.  An empty cell skips with the dt of its first step (grid.cu:193-206), an occupied one emits with
-    // dt recomputed per sample (grid.cu:207-262): one loop, so that a wave whose lanes sit in cells of both kinds runs it once.
-    float dt = calc_dt(st.t_last, cone, step_size);
-    if (SPLIT) {
-        // The same two marches for walks that spend their time in empty cells (limited walks).  The empty cell's is
-        // straight-line code: eight select steps cover a cell of the finest level at the smallest step, the loop behind them
-        // runs only for what is left (a step without progress leaves t_last unchanged; the loop then sees it and the jump
-        // applies, as in the merged loop); the sampling loop runs only when some lane of the wave has an occupied cell.
-        if (!occupied) {
-            if (t_traverse - st.t_last > 8.0f * dt) st.t_last = fast_forward_exact(st.t_last, t_traverse, dt);
-            const float half = dt * 0.5f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float t_next = st.t_last + dt;
-                st.t_last = (st.t_last + half < t_traverse) ? t_next : st.t_last;
-            }
-            for (;;) {
-                const float t_next = st.t_last + dt;
-                if (!((st.t_last + half < t_traverse) && (t_next != st.t_last))) break;
-                st.t_last = t_next;
-            }
-            if (st.t_last + half < t_traverse) st.t_last = t_traverse;
-            st.continuous = 0;
-        } else {
-            for (;;) {
-                const float t_next = st.t_last + dt;
-                const bool budget = !(limit > 0 && st.n_samples >= limit);
-                if (!((st.t_last + dt * 0.5f < t_traverse) && (t_next != st.t_last) && budget)) break;
-                emit(t_next);
-                dt = calc_dt(t_next, cone, step_size);
-            }
-        }
-    } else {
-        // a skip of many steps (cell much larger than the step): closed form (march.h), same result as the loop
-        if (!occupied && t_traverse - st.t_last > 8.0f * dt) st.t_last = fast_forward_exact(st.t_last, t_traverse, dt);
-        for (;;) {
-            const float t_next = st.t_last + dt;
-            const bool budget = !(occupied && limit > 0 && st.n_samples >= limit);
-            if (!((st.t_last + dt * 0.5f < t_traverse) && (t_next != st.t_last) && budget)) break;
-            if (occupied) {
-                emit(t_next);
-                dt = calc_dt(t_next, cone, step_size);
-            } else {
-                st.t_last = t_next;
-            }
-        }
-        if (!occupied) {
-            // left the loop before the target without progress (ours: the reference would spin): jump there
-            if (st.t_last + dt * 0.5f < t_traverse) st.t_last = t_traverse;
-            st.continuous = 0;
-        }
-    }
+    march_cell<SPLIT>(st.t_last, st.continuous, st.n_samples, occupied, t_traverse, a.step_size, a.cone_angle, limit, emit);
     i_cur = i_next;
     w_cur = fetch ? w_next : w_cur;
     return done || (limit > 0 && st.n_samples >= limit);
 }
 
-// The ray's next span from its event list (grid.cu:125-150), or from the in-kernel slab test (FUSED: one grid).  `ev`: the
-// next event to look at (FUSED: 0 = the span not taken yet).
+// A ray's event list held by the lane: the (at most eight) argsort indices packed four bits each, the hit flags as a bit mask,
+// the sorted distances in the lane's LDS column -- loaded in one go when the lane takes the ray.  Read from memory event by
+// event (an index, then the flag it points at, then two distances: a chain of dependent loads per event, three to six events
+// before a fresh ray's first span) the list was most of a refill round's 19 k cycles.
+constexpr int CONE_EV_MAX = 8;   // 2 * n_grids entries: up to four levels
+struct EventsStaged {
+    uint32_t ti_pack, hit_mask;
+    float *ts_col;
+    __device__ __forceinline__ void stage(const nfa_traverse_args &a, int64_t tid)
+    {
+        const int32_t G = a.n_grids;
+        const EventsInMemory e(a, tid);
+        uint32_t pk = 0u, hm = 0u;
+#pragma unroll
+        for (int i = 0; i < CONE_EV_MAX; ++i)
+            if (i < 2 * G) {
+                const int64_t v = e.ti[i];
+                pk |= ((uint64_t)v < (uint64_t)(2 * G) ? (uint32_t)v : 15u) << (4 * i);   // (out of range: 15, a level nobody hits)
+                ts_col[i * CONE_THREADS] = e.ts[i];
+            }
+#pragma unroll
+        for (int g = 0; g < CONE_EV_MAX / 2; ++g)
+            if (g < G) hm |= (e.hits[g] != 0 ? 1u : 0u) << g;
+        ti_pack = pk; hit_mask = hm;
+    }
+    __device__ __forceinline__ int32_t index(int32_t i) const { return (int32_t)((ti_pack >> (4 * i)) & 15u); }
+    __device__ __forceinline__ float t(int32_t i) const { return ts_col[i * CONE_THREADS]; }
+    __device__ __forceinline__ bool hit(int32_t level) const { return ((hit_mask >> level) & 1u) != 0u; }
+};
+
+// The ray's next span -- from its event list (common.hip.h: next_event_span; `staged`: the lane's copy of the list, NULL: the
+// caller's arrays), or from the slab test here (FUSED: one grid; ev = 0: the span not taken yet) -- and its first cell.
 template <bool FUSED>
-__device__ __forceinline__ bool cone_next_span(const nfa_traverse_args &a, const ConeParams &p, int64_t tid, const float o[3],
-                                               const float d[3], float near_plane, float far_plane, int32_t &ev, ConeRay &st,
-                                               WalkSpan &sp, float &span_tmax, unsigned long long &w_cur, uint32_t &i_cur)
+__device__ __forceinline__ bool cone_next_span(const nfa_traverse_args &a, const ConeParams &p, int64_t tid, const EventsStaged *staged,
+                                               const float o[3], const float d[3], float near_plane, float far_plane, int32_t &ev,
+                                               ConeRay &st, WalkSpan &sp, float &span_tmax, unsigned long long &w_cur, uint32_t &i_cur)
 {
-    const int32_t G = a.n_grids;
+    int32_t level = 0;
+    float this_tmin, this_tmax;
+    bool found;
     if (FUSED) {
         if (ev != 0) return false;
         ev = 1;
+        // common.hip.h's slab_test written out with a flag in place of its early returns: with the shared function
+        // cone_walk_kernel<true>, pinned to 6 waves per SIMD, goes from 36 to 80 bytes of scratch per lane (and the flag form as
+        // the shared one takes ray_events_kernel<8> from 7 waves per SIMD to 3)
         const float inv[3] = {1.0f / d[0], 1.0f / d[1], 1.0f / d[2]};
-        float tmin, tmax, lo, hi;
-        bool hit = true;
+        float lo, hi;
+        found = true;
         const float *bmin = a.aabbs, *bmax = a.aabbs + 3;
-        if (inv[0] >= 0) { tmin = (bmin[0] - o[0]) * inv[0]; tmax = (bmax[0] - o[0]) * inv[0]; }
-        else             { tmin = (bmax[0] - o[0]) * inv[0]; tmax = (bmin[0] - o[0]) * inv[0]; }
+        if (inv[0] >= 0) { this_tmin = (bmin[0] - o[0]) * inv[0]; this_tmax = (bmax[0] - o[0]) * inv[0]; }
+        else             { this_tmin = (bmax[0] - o[0]) * inv[0]; this_tmax = (bmin[0] - o[0]) * inv[0]; }
 #pragma unroll
         for (int ax = 1; ax < 3; ++ax) {
             if (inv[ax] >= 0) { lo = (bmin[ax] - o[ax]) * inv[ax]; hi = (bmax[ax] - o[ax]) * inv[ax]; }
             else              { lo = (bmax[ax] - o[ax]) * inv[ax]; hi = (bmin[ax] - o[ax]) * inv[ax]; }
-            if (tmin > hi || lo > tmax) hit = false;
-            if (lo > tmin) tmin = lo;
-            if (hi < tmax) tmax = hi;
+            if (this_tmin > hi || lo > this_tmax) found = false;
+            if (lo > this_tmin) this_tmin = lo;
+            if (hi < this_tmax) this_tmax = hi;
         }
-        if (tmax <= 0) hit = false;
-        const float this_tmin = fmaxf(tmin, near_plane), this_tmax = fminf(tmax, far_plane);
-        if (!(hit && this_tmin < this_tmax)) return false;
-        span_tmax = this_tmax;
-        cone_span_begin(a, p, o, d, 0, this_tmin, this_tmax, st, sp, w_cur, i_cur);
-        return true;
+        if (this_tmax <= 0) found = false;
+        this_tmin = fmaxf(this_tmin, near_plane); this_tmax = fminf(this_tmax, far_plane);
+        found = found && this_tmin < this_tmax;
+    } else if (staged) {
+        found = next_event_span(*staged, a.n_grids, near_plane, far_plane, ev, level, this_tmin, this_tmax);
     } else {
-        const uint8_t *hits = a.hits + tid * G;
-        const float *ts = a.t_sorted + tid * 2 * G;
-        const int64_t *ti = a.t_indices + tid * 2 * G;
-        while (ev < 2 * G - 1) {
-            const int32_t i = ev++;
-            const int64_t idx = ti[i];
-            int32_t level = event_level(idx, G);
-            bool ok = (uint32_t)level < (uint32_t)G && hits[level] != 0;
-            if (ok && idx >= G) {  // leaving: inside the next grid?
-                const int64_t nidx = ti[i + 1];
-                level = event_level(nidx, G);
-                ok = nidx >= G && (uint32_t)level < (uint32_t)G && hits[level] != 0;
-            }
-            const float this_tmin = fmaxf(ts[i], near_plane);
-            const float this_tmax = fminf(ts[i + 1], far_plane);
-            if (ok && this_tmin < this_tmax) {
-                span_tmax = this_tmax;
-                cone_span_begin(a, p, o, d, level, this_tmin, this_tmax, st, sp, w_cur, i_cur);
-                return true;
-            }
-        }
-        return false;
+        found = next_event_span(EventsInMemory(a, tid), a.n_grids, near_plane, far_plane, ev, level, this_tmin, this_tmax);
     }
-}
-
-// The same walk over a ray's event list held by the lane: the (at most eight) argsort indices packed four bits each, the hit
-// flags as a bit mask, the sorted distances in the lane's LDS column -- loaded in one go when the lane takes the ray.  Read from
-// memory event by event (an index, then the flag it points at, then two distances: a chain of dependent loads per event,
-// three to six events before a fresh ray's first span) the list was most of a refill round's 19 k cycles.
-constexpr int CONE_EV_MAX = 8;   // 2 * n_grids entries: up to four levels
-__device__ __forceinline__ void cone_stage_events(const nfa_traverse_args &a, int64_t tid, uint32_t &ti_pack, uint32_t &hit_mask, float *ts_col)
-{
-    const int32_t G = a.n_grids;
-    const int64_t *ti = a.t_indices + tid * 2 * G;
-    const float *ts = a.t_sorted + tid * 2 * G;
-    const uint8_t *hits = a.hits + tid * G;
-    uint32_t pk = 0u, hm = 0u;
-#pragma unroll
-    for (int i = 0; i < CONE_EV_MAX; ++i)
-        if (i < 2 * G) {
-            const int64_t v = ti[i];
-            pk |= ((uint64_t)v < (uint64_t)(2 * G) ? (uint32_t)v : 15u) << (4 * i);   // (out of range: 15, a level nobody hits)
-            ts_col[i * CONE_THREADS] = ts[i];
-        }
-#pragma unroll
-    for (int g = 0; g < CONE_EV_MAX / 2; ++g)
-        if (g < G) hm |= (hits[g] != 0 ? 1u : 0u) << g;
-    ti_pack = pk; hit_mask = hm;
-}
-
-__device__ __forceinline__ bool cone_next_span_staged(const nfa_traverse_args &a, const ConeParams &p, const float o[3], const float d[3],
-                                                      float near_plane, float far_plane, int32_t &ev, uint32_t ti_pack, uint32_t hit_mask,
-                                                      const float *ts_col, ConeRay &st, WalkSpan &sp, float &span_tmax,
-                                                      unsigned long long &w_cur, uint32_t &i_cur)
-{
-    const int32_t G = a.n_grids;
-    while (ev < 2 * G - 1) {  // grid.cu:125-150
-        const int32_t i = ev++;
-        const int32_t idx = (int32_t)((ti_pack >> (4 * i)) & 15u);
-        int32_t level = idx >= G ? idx - G : idx;
-        bool ok = level < G && ((hit_mask >> level) & 1u) != 0u;
-        if (ok && idx >= G) {  // leaving: inside the next grid?
-            const int32_t nidx = (int32_t)((ti_pack >> (4 * (i + 1))) & 15u);
-            level = nidx >= G ? nidx - G : nidx;
-            ok = nidx >= G && level < G && ((hit_mask >> level) & 1u) != 0u;
-        }
-        const float this_tmin = fmaxf(ts_col[i * CONE_THREADS], near_plane);
-        const float this_tmax = fminf(ts_col[(i + 1) * CONE_THREADS], far_plane);
-        if (ok && this_tmin < this_tmax) {
-            span_tmax = this_tmax;
-            cone_span_begin(a, p, o, d, level, this_tmin, this_tmax, st, sp, w_cur, i_cur);
-            return true;
-        }
-    }
-    return false;
+    if (!found) return false;
+    span_tmax = this_tmax;
+    cone_span_begin(a, p, o, d, level, this_tmin, this_tmax, st, sp, w_cur, i_cur);
+    return true;
 }
 
 __device__ __forceinline__ void cone_ray_out(const nfa_traverse_args &a, const ConeParams &p, int64_t tid, const ConeRay &st,
                                              const uint32_t *arena_slot)
 {
-    if (a.terminate_planes) a.terminate_planes[tid] = st.t_last;
-    a.sm_cnts[tid] = st.n_samples;
-    // rays with > 2^21 samples go to the serial fill (the expansion packs a 27-bit batch offset)
     int32_t n_runs = st.n_runs;
-    if (p.arena && n_runs >= p.max_runs) {   // the ray's last records are in the arena: its slots hold max_runs - 1 of them + the sentinel
+    if (p.arena && n_runs >= p.ro.max_runs) {   // the ray's last records are in the arena: its slots hold max_runs - 1 of them + the sentinel
         const uint32_t e = *arena_slot;
-        if (e < CONE_ARENA_FRESH) { reinterpret_cast<uint32_t *>(p.arena + e)[3] = (uint32_t)st.run_len; n_runs = p.max_runs; }
-        else n_runs = p.max_runs + 1;
+        if (e < CONE_ARENA_FRESH) { reinterpret_cast<uint32_t *>(p.arena + e)[3] = (uint32_t)st.run_len; n_runs = p.ro.max_runs; }
+        else n_runs = p.ro.max_runs + 1;
     }
-    if (st.n_samples > (1 << 21) && n_runs <= p.max_runs) n_runs = p.max_runs + 1;
-    p.run_cnts[tid] = n_runs;
-    if (n_runs > p.max_runs) atomicAdd(p.overflow, 1);
-}
-
-// a ray masked out by rays_mask (grid.cu:100; the reference leaves its outputs uninitialised, we define them)
-__device__ __forceinline__ bool cone_ray_masked(const nfa_traverse_args &a, const ConeParams &p, int64_t tid)
-{
-    if (!(a.mode == 2 && a.rays_mask != nullptr && !a.rays_mask[tid])) return false;
-    if (a.terminate_planes) a.terminate_planes[tid] = a.near_planes[tid];
-    a.sm_cnts[tid] = 0;
-    p.run_cnts[tid] = 0;
-    return true;
+    run_ray_close(a, p.ro, tid, st.t_last, st.n_samples, n_runs);
 }
 
 // one ray per lane, from its first span to its last
@@ -1286,25 +1175,22 @@ __global__ __launch_bounds__(CONE_THREADS) void cone_walk_kernel(const nfa_trave
     p.tab_lds = s_tab;
     __shared__ uint32_t s_arena[CONE_THREADS];        // per lane: the ray's current arena entry (cone_cell: emit)
     uint32_t *const arena_slot = s_arena + threadIdx.x;
-    const int64_t n_walk = p.order ? p.n_order : a.n_rays;
+    const int64_t n_walk = p.ro.order ? p.ro.n_order : a.n_rays;
     const int32_t limit = a.traverse_steps_limit;
     for (int64_t slot_i = xcd_fair_block(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x; slot_i < n_walk;
          slot_i += (int64_t)blockDim.x * gridDim.x) {
-        const int64_t tid = p.order ? (int64_t)p.order[slot_i] : slot_i;
-        if (cone_ray_masked(a, p, tid)) continue;
-        const float near_plane = a.near_planes[tid], far_plane = a.far_planes[tid];
-        const float o[3] = {a.rays_o[3 * tid], a.rays_o[3 * tid + 1], a.rays_o[3 * tid + 2]};
-        const float d[3] = {a.rays_d[3 * tid], a.rays_d[3 * tid + 1], a.rays_d[3 * tid + 2]};
+        const int64_t tid = p.ro.order ? (int64_t)p.ro.order[slot_i] : slot_i;
+        if (ray_masked(a, p.ro, tid)) continue;
+        float near_plane, far_plane, o[3], d[3];
+        const bool ray_ok = ray_load(a, tid, near_plane, far_plane, o, d);
         ConeRay st;
         st.t_last = near_plane; st.continuous = 0; st.n_samples = 0; st.n_runs = 0; st.run_len = 0;
-        // (a ray with a non-finite origin or direction has no geometry: no samples, see grid.hip's traverse_kernel)
-        const bool ray_ok = isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]) && isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]);
         int32_t ev = ray_ok ? 0 : 2 * a.n_grids;
         WalkSpan sp;
         float span_tmax = 0.f;
         unsigned long long w_cur = 0ull;
         uint32_t i_cur = 0u;
-        while (cone_next_span<FUSED>(a, p, tid, o, d, near_plane, far_plane, ev, st, sp, span_tmax, w_cur, i_cur)) {
+        while (cone_next_span<FUSED>(a, p, tid, nullptr, o, d, near_plane, far_plane, ev, st, sp, span_tmax, w_cur, i_cur)) {
             while (!cone_cell<false>(a, p, tid, span_tmax, sp, w_cur, i_cur, st, arena_slot)) {}
             // The budget is spent: the last thing that happened was a sample (continuous), so the spans still to come would
             // change nothing (grid.cu:151,185: no fast-forward, no cell visited).
@@ -1314,14 +1200,43 @@ __global__ __launch_bounds__(CONE_THREADS) void cone_walk_kernel(const nfa_trave
     }
 }
 
-// Limited walks (traverse_steps_limit > 0: one iteration of the test-mode loop, examples/utils.py:252-425) stop after a
-// handful of samples, i.e. after a number of cells that is geometric in the local occupancy; with one ray per lane a wave
-// lasts as long as its unluckiest ray (cfg 5, 2 % scattered occupancy: 50 cells to the first sample on average, ~240 for
-// the worst of 64 lanes, lanes busy a fifth of the time).  Here a wave owns `chunk` consecutive entries of the ray list
-// and a lane that has finished its ray is given the next one: the wave leaves its cell loop when fewer than `min_busy`
-// lanes are still walking, sets up new rays (and the next spans of rays that crossed into another level) on the free
-// lanes, and re-enters.  Per ray the same functions as cone_walk_kernel: identical results.
+// Limited walks: the refilling scheduler (common.hip.h: refill_schedule) with this file's walker.  Per ray the same functions as
+// cone_walk_kernel: identical results.
 template <bool FUSED, bool STAGED /* the event list travels with the lane (n_grids <= 4) */>
+struct ConeWalker {
+    const nfa_traverse_args &a;
+    const ConeParams &p;
+    uint32_t *arena_slot;
+    EventsStaged staged;
+    int64_t tid;
+    int32_t ev;
+    float near_plane, far_plane, span_tmax, o[3], d[3];
+    ConeRay st;
+    WalkSpan sp;
+    unsigned long long w_cur;
+    uint32_t i_cur;
+    __device__ __forceinline__ bool take(int64_t ray)
+    {
+        tid = ray;
+        if (ray_masked(a, p.ro, tid)) return false;
+        const bool ray_ok = ray_load(a, tid, near_plane, far_plane, o, d);
+        if (STAGED) staged.stage(a, tid);
+        st.t_last = near_plane; st.continuous = 0; st.n_samples = 0; st.n_runs = 0; st.run_len = 0;
+        ev = ray_ok ? 0 : 2 * a.n_grids;
+        return true;
+    }
+    __device__ __forceinline__ bool next_span()
+    {
+        return cone_next_span<FUSED>(a, p, tid, STAGED ? &staged : nullptr, o, d, near_plane, far_plane, ev, st, sp, span_tmax, w_cur, i_cur);
+    }
+    __device__ __forceinline__ int cell()
+    {
+        if (!cone_cell<true>(a, p, tid, span_tmax, sp, w_cur, i_cur, st, arena_slot)) return RF_WALK;
+        return (a.traverse_steps_limit > 0 && st.n_samples >= a.traverse_steps_limit) ? RF_FINISH : RF_SPAN;
+    }
+    __device__ __forceinline__ void finish() { cone_ray_out(a, p, tid, st, arena_slot); }
+};
+template <bool FUSED, bool STAGED>
 __global__ __launch_bounds__(CONE_THREADS) void cone_refill_kernel(const nfa_traverse_args a, const ConeParams p_in)
 {
     static_assert(!(FUSED && STAGED), "a fused walk has no event list");
@@ -1330,82 +1245,11 @@ __global__ __launch_bounds__(CONE_THREADS) void cone_refill_kernel(const nfa_tra
     p.tab_lds = s_tab;
     __shared__ float ts_lds[STAGED ? CONE_EV_MAX * CONE_THREADS : 1];
     __shared__ uint32_t s_arena[CONE_THREADS];        // per lane: the ray's current arena entry (cone_cell: emit)
-    uint32_t *const arena_slot = s_arena + threadIdx.x;
-    float *const ts_col = ts_lds + (STAGED ? threadIdx.x : 0);
-    uint32_t ti_pack = 0u, hit_mask = 0u;
-    enum { IDLE = 0, SPAN = 1, WALK = 2, FINISH = 3 };
-    const int lane = lane_id();
-    const unsigned long long lanes_below = (1ull << lane) - 1ull;
-    const int64_t n_walk = p.order ? p.n_order : a.n_rays;
-    const int64_t wave = xcd_fair_block(blockIdx.x, gridDim.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    int64_t next = wave * p.chunk;  // (wave-uniform) first entry not handed out yet
-    const int64_t end = next + p.chunk < n_walk ? next + p.chunk : n_walk;
-    const int32_t limit = a.traverse_steps_limit;
-
-    int32_t phase = IDLE, ev = 0;
-    int64_t tid = 0;
-    float near_plane = 0.0f, far_plane = 0.0f, span_tmax = 0.0f;
-    float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, 0.0f};
-    ConeRay st;
-    st.t_last = 0.0f; st.continuous = 0; st.n_samples = 0; st.n_runs = 0; st.run_len = 0;
-    WalkSpan sp;
-    sp.tx = sp.ty = sp.tz = sp.dx = sp.dy = sp.dz = 0.f; sp.mx = sp.my = sp.mz = 0u; sp.rem = 0u; sp.widx = 0u; sp.flip = 0u; sp.end = 0u; sp.over = 0u;
-    unsigned long long w_cur = 0ull;
-    uint32_t i_cur = 0u;
-
-    for (;;) {
-        // Two passes: rays that left a span in the cell loop (their next span, or their end), then the rays handed to the
-        // lanes that are free after that.
-#pragma nounroll
-        for (int pass = 0; pass < 2; ++pass) {
-            if (phase == SPAN) {
-                bool found;
-                if (STAGED) found = cone_next_span_staged(a, p, o, d, near_plane, far_plane, ev, ti_pack, hit_mask, ts_col, st, sp, span_tmax, w_cur, i_cur);
-                else found = cone_next_span<FUSED>(a, p, tid, o, d, near_plane, far_plane, ev, st, sp, span_tmax, w_cur, i_cur);
-                phase = found ? WALK : FINISH;
-            }
-            if (phase == FINISH) {
-                cone_ray_out(a, p, tid, st, arena_slot);
-                phase = IDLE;
-            }
-            if (pass == 1) break;
-            const unsigned long long idle = __ballot(phase == IDLE);
-            if (idle != 0ull && next < end) {
-                if (phase == IDLE) {
-                    const int64_t slot = next + __popcll(idle & lanes_below);
-                    if (slot < end) {
-                        tid = p.order ? (int64_t)p.order[slot] : slot;
-                        if (!cone_ray_masked(a, p, tid)) {
-                            near_plane = a.near_planes[tid]; far_plane = a.far_planes[tid];
-#pragma unroll
-                            for (int ax = 0; ax < 3; ++ax) { o[ax] = a.rays_o[3 * tid + ax]; d[ax] = a.rays_d[3 * tid + ax]; }
-                            if (STAGED) cone_stage_events(a, tid, ti_pack, hit_mask, ts_col);
-                            st.t_last = near_plane; st.continuous = 0; st.n_samples = 0; st.n_runs = 0; st.run_len = 0;
-                            const bool ray_ok = isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]) && isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]);
-                            ev = ray_ok ? 0 : 2 * a.n_grids;
-                            phase = SPAN;
-                        }
-                    }
-                }
-                next += __popcll(idle);
-            }
-        }
-        const unsigned long long walking = __ballot(phase == WALK);
-        if (walking == 0ull) {
-            if (next >= end) break;  // (every lane is IDLE here: SPAN and FINISH were resolved above)
-            continue;
-        }
-        // ---- cells, for as long as enough lanes have one to visit
-        const int32_t n_walking = __popcll(walking);
-        const int32_t need = next < end ? p.min_busy : (n_walking * 3 >> 2) > 1 ? (n_walking * 3 >> 2) : 1;
-        do {
-            if (phase == WALK) {
-                if (cone_cell<true>(a, p, tid, span_tmax, sp, w_cur, i_cur, st, arena_slot))
-                    phase = (limit > 0 && st.n_samples >= limit) ? FINISH : SPAN;  // budget spent: nothing after it changes the ray
-            }
-        } while (__popcll(__ballot(phase == WALK)) >= need);
-    }
+    ConeWalker<FUSED, STAGED> w{a, p, s_arena + threadIdx.x, {0u, 0u, ts_lds + (STAGED ? threadIdx.x : 0)}};
+    refill_schedule(w, p.ro.order, p.ro.order ? p.ro.n_order : a.n_rays,
+                    xcd_fair_block(blockIdx.x, gridDim.x) * (blockDim.x >> 6) + (threadIdx.x >> 6), p.chunk, p.min_busy);
 }
+
 
 }  // namespace nfa
 
@@ -1554,28 +1398,28 @@ int nfa_traverse_cone_walk(const nfa_traverse_args *pa, const uint32_t *bits, in
     p.lay = walk_layout(a.res);
     NFA_REQUIRE(p.lay.bits >= 6 && ((int64_t)a.n_grids << p.lay.bits) < ((int64_t)1 << 31),
                 "traverse_cone_walk: a level of the grid copy must be a whole number of 64-bit words (at least 4 cells per axis) and the copy below 2^31 bits");
-    p.run_cnts = run_cnts;
-    p.runs = reinterpret_cast<unsigned long long *>(runs);
-    p.max_runs = max_runs;
-    p.overflow = overflow_count;
+    p.ro.run_cnts = run_cnts;
+    p.ro.runs = reinterpret_cast<unsigned long long *>(runs);
+    p.ro.max_runs = max_runs;
+    p.ro.overflow = overflow_count;
     p.arena = (arena && arena_capacity > 0 && max_runs >= 2) ? reinterpret_cast<uint4 *>(arena) : nullptr;
     p.arena_cap = arena_capacity;
     p.arena_count = overflow_count + 1;
-    p.order = ray_order;
-    p.n_order = ray_order ? n_order : a.n_rays;
+    p.ro.order = ray_order;
+    p.ro.n_order = ray_order ? n_order : a.n_rays;
     NFA_REQUIRE(!ray_order || (n_order >= 0 && n_order <= a.n_rays), "traverse_cone_walk: n_order out of range");
     if (ray_order && n_order == 0) return NFA_OK;
-    const RefillPlan plan = refill_plan(p.n_order, a.traverse_steps_limit);
+    const RefillPlan plan = refill_plan(p.ro.n_order, a.traverse_steps_limit);
     p.chunk = (int32_t)plan.chunk; p.min_busy = plan.min_busy;
     if (plan.refill) {
-        const unsigned grid = (unsigned)ceil_div64(ceil_div64(p.n_order, plan.chunk), CONE_THREADS / 64);   // waves, then workgroups
+        const unsigned grid = (unsigned)ceil_div64(ceil_div64(p.ro.n_order, plan.chunk), CONE_THREADS / 64);   // waves, then workgroups
         const char *staged_env = tuning_env("NFA_CONE_STAGED");   // "0": event lists read from memory (A/B)
         const bool staged = !fused && 2 * a.n_grids <= CONE_EV_MAX && !(staged_env && staged_env[0] == '0');
         if (fused)       hipLaunchKernelGGL((cone_refill_kernel<true, false>), dim3(grid), dim3(CONE_THREADS), 0, s, a, p);
         else if (staged) hipLaunchKernelGGL((cone_refill_kernel<false, true>), dim3(grid), dim3(CONE_THREADS), 0, s, a, p);
         else             hipLaunchKernelGGL((cone_refill_kernel<false, false>), dim3(grid), dim3(CONE_THREADS), 0, s, a, p);
     } else {
-        const unsigned grid = grid_1d(p.n_order, CONE_THREADS, 1 << 20);
+        const unsigned grid = grid_1d(p.ro.n_order, CONE_THREADS, 1 << 20);
         if (fused) hipLaunchKernelGGL((cone_walk_kernel<true>), dim3(grid), dim3(CONE_THREADS), 0, s, a, p);
         else       hipLaunchKernelGGL((cone_walk_kernel<false>), dim3(grid), dim3(CONE_THREADS), 0, s, a, p);
     }

@@ -37,7 +37,8 @@ def test_native_library_is_loaded(dev):
 def test_cone_walk_forms_agree_and_match_oracle(dev, oracle):
     """Distance-dependent steps: the count pass exists over the brick-packed grid (grid.hip: traverse_kernel<EMIT_RUNS>, one ray
     per lane; traverse_refill_kernel for limited walks) and over the 1-bit grid copy (walk.hip: cone_walk_kernel,
-    cone_refill_kernel).  Every form must produce the same samples, counts and termination planes, bit for bit -- and the
+    cone_refill_kernel); the two refilling kernels are one scheduler with a walker each, run here with chunks that end in the
+    middle of a wave too.  Every form must produce the same samples, counts and termination planes, bit for bit -- and the
     oracle's: nested levels, one level with the in-kernel slab test, masks, step limits from 1 to 40, a wide and a narrow cone,
     resolutions that are not multiples of 4, rays with zero direction components and rays that miss."""
     rng = np.random.default_rng(int(os.environ.get("NFA_CONE_SEED", "77")))   # NFA_CONE_SEED: soak runs with other seeds
@@ -49,6 +50,9 @@ def test_cone_walk_forms_agree_and_match_oracle(dev, oracle):
         (4, (16, 16, 16), 0.02, 30_000, 1e-2, 0.004, 7, True, True),
         (2, (50, 24, 30), 0.3, 3_000, 5e-3, 0.05, 40, False, True),
         (5, (16, 16, 16), 0.05, 6_000, 1e-2, 0.004, 5, True, True),    # ten events per ray: the refill kernel reads them from memory
+        # grids the 1-bit walk refuses (an axis shorter than 4): every form is routed to grid.hip's kernels by the public dispatch
+        (1, (3, 20, 12), 0.3, 4_000, 5e-3, 0.01, 3, True, True),       # ... its refilling walker, in-kernel slab test
+        (2, (20, 3, 12), 0.3, 4_000, 5e-3, 0.01, None, False, True),   # ... its unlimited one-ray-per-lane EMIT_RUNS kernel, event list
     ]
     from nerfacc_amd import _backend as NB
     saved = (na.grid.CONE_WALK,)
@@ -67,7 +71,8 @@ def test_cone_walk_forms_agree_and_match_oracle(dev, oracle):
             args = (T(o, dev), T(d, dev), T(b, dev), est.aabbs, T(near, dev), T(far, dev), step, cone)
             outs = {}
             for form, (walk, refill) in {"walk": (True, None), "walk, one ray per lane": (True, "0"), "bricks": (False, None),
-                                         "bricks, one ray per lane": (False, "0"), "walk, small chunks": (True, "64,40")}.items():
+                                         "bricks, one ray per lane": (False, "0"), "walk, small chunks": (True, "64,40"),
+                                         "bricks, small chunks": (False, "64,40")}.items():
                 na.grid.CONE_WALK = walk
                 NB.set_tuning("NFA_REFILL", refill)
                 outs[form] = na.grid._traverse_samples(*args, **kw)

@@ -202,6 +202,84 @@ extern "C" long lattice_check(float near, float dt, long max_steps, unsigned see
     }
     return checked;
 }
+
+// One cell of a march with a cone angle: march.h's march_cell<false> (the merged loop) and march_cell<true> (the split form)
+// against the reference's cell restated serially (grid.cu:193-262): an empty cell is fast_forward, then continuous = 0; an
+// occupied one is the emit loop with the budget test and the no-progress guard.  Returns the number of cells in which either
+// form differs from it in t_last, continuous, n_samples or any emitted (t_last, t_next), bit for bit; branches[]: how often the
+// inputs reached each case (counted here, from the inputs and the serial run).
+enum { BR_NOTHING, BR_SHORTCUT, BR_SELECT, BR_TAIL, BR_STUCK_EMPTY, BR_STUCK_OCCUPIED, BR_CELL_END, BR_BUDGET_STOP, BR_AT_LIMIT,
+       BR_ONE_UNDER, BR_BELOW_LIMIT, BR_UNLIMITED, BR_STEP_DT, BR_CONE_DT, BR_DT_CHANGES, BR_COUNT };
+struct CellResult {
+    float t_last; int32_t continuous, n_samples;
+    std::vector<uint32_t> pairs;
+    bool operator==(const CellResult& o) const {
+        return nfa::f32_bits(t_last) == nfa::f32_bits(o.t_last) && continuous == o.continuous && n_samples == o.n_samples && pairs == o.pairs;
+    }
+};
+template <bool SPLIT>
+static CellResult cell_shared(float t_last, int32_t continuous, int32_t n_samples, bool occupied, float t_traverse, float step, float cone, int32_t limit) {
+    CellResult r;
+    nfa::march_cell<SPLIT>(t_last, continuous, n_samples, occupied, t_traverse, step, cone, limit,
+                           [&](float t_next) { r.pairs.push_back(nfa::f32_bits(t_last)); r.pairs.push_back(nfa::f32_bits(t_next)); });
+    r.t_last = t_last; r.continuous = continuous; r.n_samples = n_samples;
+    return r;
+}
+static CellResult cell_serial(float t_last, int32_t continuous, int32_t n_samples, bool occupied, float t_traverse, float step, float cone, int32_t limit,
+                              long* br) {
+    CellResult r;
+    const float dt0 = nfa::calc_dt(t_last, cone, step);
+    if (!(t_last + dt0 * 0.5f < t_traverse)) br[BR_NOTHING]++;
+    br[dt0 == step ? BR_STEP_DT : BR_CONE_DT]++;
+    if (!occupied) {
+        // what the shared forms do with this cell: the closed form beyond 8 dt, else up to eight select steps, then the loop
+        const bool shortcut = t_traverse - t_last > 8.0f * dt0;
+        long steps = 0;
+        for (;;) {   // fast_forward
+            if (t_last + dt0 * 0.5f >= t_traverse) break;
+            const float t_new = t_last + dt0;
+            if (t_new == t_last) { t_last = t_traverse; br[BR_STUCK_EMPTY]++; break; }
+            t_last = t_new; steps++;
+        }
+        continuous = 0;
+        if (shortcut) br[BR_SHORTCUT]++;
+        else if (steps > 8) br[BR_TAIL]++;
+        else if (steps >= 1) br[BR_SELECT]++;
+    } else {
+        if (limit <= 0) br[BR_UNLIMITED]++;
+        else if (n_samples >= limit) br[BR_AT_LIMIT]++;
+        else if (n_samples == limit - 1) br[BR_ONE_UNDER]++;
+        else br[BR_BELOW_LIMIT]++;
+        bool dt_changed = false;
+        for (;;) {
+            const float dt = nfa::calc_dt(t_last, cone, step);
+            const bool more = t_last + dt * 0.5f < t_traverse && t_last + dt != t_last;
+            if (!(limit <= 0 || n_samples < limit)) { if (more) br[BR_BUDGET_STOP]++; break; }
+            if (t_last + dt * 0.5f >= t_traverse) { br[BR_CELL_END]++; break; }
+            const float t_next = t_last + dt;
+            if (t_next == t_last) { br[BR_STUCK_OCCUPIED]++; break; }   // no-progress guard
+            dt_changed = dt_changed || dt != dt0;
+            r.pairs.push_back(nfa::f32_bits(t_last)); r.pairs.push_back(nfa::f32_bits(t_next));
+            n_samples++; continuous = 1; t_last = t_next;
+        }
+        if (dt_changed) br[BR_DT_CHANGES]++;
+    }
+    r.t_last = t_last; r.continuous = continuous; r.n_samples = n_samples;
+    return r;
+}
+extern "C" long march_cells(const float* t_last, const int32_t* continuous, const int32_t* n_samples, const int32_t* occupied, const float* t_traverse,
+                            const float* step, const float* cone, const int32_t* limit, long n, long* branches) {
+    long bad = 0;
+    for (int i = 0; i < BR_COUNT; ++i) branches[i] = 0;
+    for (long i = 0; i < n; ++i) {
+        const bool occ = occupied[i] != 0;
+        const CellResult want = cell_serial(t_last[i], continuous[i], n_samples[i], occ, t_traverse[i], step[i], cone[i], limit[i], branches);
+        const CellResult merged = cell_shared<false>(t_last[i], continuous[i], n_samples[i], occ, t_traverse[i], step[i], cone[i], limit[i]);
+        const CellResult split = cell_shared<true>(t_last[i], continuous[i], n_samples[i], occ, t_traverse[i], step[i], cone[i], limit[i]);
+        if (!(merged == want) || !(split == want)) bad++;
+    }
+    return bad;
+}
 '''
 
 
@@ -356,6 +434,56 @@ def test_lattice_table_and_J_match_the_serial_loop(tmp_path):
         assert n > 3000
         total += n; fast += bad[2]
     assert fast > 0.5 * total      # the fast form serves most thresholds
+
+
+MARCH_BRANCHES = ["nothing to do (t_traverse <= t_last)", "empty: the > 8 dt shortcut", "empty: select steps only", "empty: the tail loop",
+                  "empty: no progress, jump", "occupied: no progress", "occupied: cell end", "occupied: stopped by the budget",
+                  "occupied: starts at the limit", "occupied: starts one under the limit", "occupied: starts below the limit",
+                  "occupied: no limit", "dt = step at the start", "dt = t * cone at the start", "dt changes inside a cell"]
+
+
+def test_march_cell_matches_the_serial_cell(tmp_path):
+    """march.h's march_cell -- the one copy of the per-cell march of the cone-angle kernels (grid.hip: span_cell, walk.hip:
+    cone_cell), in its merged and its split form -- against the reference's cell written out serially in the harness
+    (grid.cu:193-262): t_last, continuous, n_samples and every emitted (t_last, t_next) are bit-identical, on random cells
+    that reach every branch of both forms (counted in the harness)."""
+    lib = _build(tmp_path)
+    lib.march_cells.restype = C.c_long
+    rng = np.random.default_rng(11)
+    n = 6000
+    cone = rng.choice(np.float32([0.003, 0.004, 0.02, 0.05]), n)
+    step = (10 ** rng.uniform(-3, -2, n)).astype(np.float32)
+    t_last = (10 ** rng.uniform(np.log10(0.05), np.log10(50), n)).astype(np.float32)       # t * cone on both sides of step
+    dt = np.maximum(step, t_last * cone)
+    t_traverse = (t_last + dt * 10 ** rng.uniform(-1, np.log10(200), n)).astype(np.float32)   # a fraction of dt .. 200 dt
+    back = rng.random(n) < 0.05
+    t_traverse[back] = (t_last[back] - rng.random(back.sum()) * (rng.random(back.sum()) < 0.5)).astype(np.float32)   # at or behind t_last
+    # t_last at 2^20 .. 2^25 dt (dt at calc_dt's 1e10 cap): around 2^24 dt a step is less than half an ulp -- no progress --
+    # or it depends on the rounding; at 2^21 .. 2^23.5 dt a step is a few ulps, eight rounded steps fall short of 8 dt and
+    # cells of 5 .. 8 dt need the tail loop behind the select steps
+    m = 900
+    huge = (1e10 * 2.0 ** np.concatenate([rng.uniform(20, 25.5, 500), np.full(100, 24.0), rng.uniform(21, 23.5, 300)])).astype(np.float32)
+    t_last = np.concatenate([t_last, huge])
+    t_traverse = np.concatenate([t_traverse, (huge.astype(np.float64) + 1e10 * np.concatenate([rng.uniform(0.3, 30, 600), rng.uniform(5, 8, 300)])).astype(np.float32)])
+    cone = np.concatenate([cone, rng.choice(np.float32([0.003, 0.004, 0.02, 0.05]), m)])
+    step = np.concatenate([step, (10 ** rng.uniform(-3, -2, m)).astype(np.float32)])
+    n += m
+    occupied = (rng.random(n) < 0.5).astype(np.int32)
+    occupied[-300:] = rng.random(300) < 0.2
+    continuous = (rng.random(n) < 0.5).astype(np.int32)
+    limit = rng.choice(np.int32([0, 1, 4, 40]), n)
+    kind = rng.integers(0, 3, n)                                                             # below, one under, at the limit
+    n_samples = np.where(limit == 0, rng.integers(0, 100, n),
+                         np.where(kind == 0, (rng.random(n) * np.maximum(limit - 1, 0)).astype(np.int64), np.where(kind == 1, limit - 1, limit))).astype(np.int32)
+    branches = (C.c_long * len(MARCH_BRANCHES))()
+    p = lambda x: np.ascontiguousarray(x).ctypes.data_as(C.c_void_p)
+    arrays = [np.ascontiguousarray(a) for a in (t_last, continuous, n_samples, occupied, t_traverse, step, cone, limit)]
+    assert [a.dtype for a in arrays] == [np.float32, np.int32, np.int32, np.int32, np.float32, np.float32, np.float32, np.int32]
+    bad = lib.march_cells(*[p(a) for a in arrays], C.c_long(n), branches)
+    reached = dict(zip(MARCH_BRANCHES, list(branches)))
+    print(reached)
+    assert bad == 0, bad
+    assert all(v > 0 for v in reached.values()), reached
 
 
 LAYOUT_HARNESS = r'''
