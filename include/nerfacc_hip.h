@@ -622,6 +622,45 @@ int nfa_sample_positions_bwd(const float *rays_o, const float *rays_d, const flo
                              int32_t contraction, int32_t dirs_mode, float *grad_rays_o, float *grad_rays_d,
                              float *grad_t_starts, float *grad_t_ends, float *grad_p, nfa_stream_t stream);
 
+/* ------------------------------------------------------------------ rays from cameras */
+
+/* Rays of n_rays pixels in one pass.  Replaces the "generate rays" block of the loaders, ref: examples/datasets/
+ * nerf_synthetic.py:194-227 and examples/datasets/nerf_360_v2.py:326-359 (camera_dirs, directions, origins, viewdirs), and
+ * the undistortion call a distorted camera makes inside it (ref: cuda/csrc/camera.cu:9-107):
+ *   u = (x - cx + pixel_center) / fx, v = (y - cy + pixel_center) / fy; with a lens (u, v) <- the undistorted point, by the
+ *   solvers of nfa_opencv_lens_undistortion (n_dist 8) / _fisheye (fisheye != 0, n_dist 4) with their eps and iters, bit for
+ *   bit; c = (u, s v, s) with s = -1 (opengl != 0) or 1; d_i = (R_i0 c_0 + R_i1 c_1) + R_i2 c_2; viewdirs = d / |d|
+ *   (normalize != 0) or d; origins = the translation column.  Each operation is rounded on its own.
+ * x / y [n_rays]: float32, int32 or int64 (pixel_dtype 0 / 1 / 2; integers are converted here), aligned to their element.
+ * camera_ids [n_rays] in any order, or NULL with n_cameras == 1; an id outside [0, n_cameras) gives NaN rows.
+ * K [n_cameras, 9] row-major (k_stride 9) or one shared row (k_stride 0); camtoworlds rows of 12 or 16 floats (3x4 or 4x4
+ * row-major; pose_stride 12 / 16) or one shared row (0); distortion [n_cameras, n_dist] (dist_stride n_dist) or one shared
+ * row (0), NULL with n_dist 0.  origins / viewdirs [n_rays, 3].  n_rays == 0 returns at once. */
+int nfa_generate_rays_fwd(const void *x, const void *y, int32_t pixel_dtype, const int64_t *camera_ids, int64_t n_rays,
+                          int64_t n_cameras, const float *K, int64_t k_stride, const float *camtoworlds, int64_t pose_stride,
+                          const float *distortion, int32_t n_dist, int64_t dist_stride, int32_t fisheye, int32_t opengl,
+                          float pixel_center, int32_t normalize, float eps, int32_t iters, float *origins, float *viewdirs,
+                          nfa_stream_t stream);
+/* Its backward towards the cameras: what differentiating those loader lines with respect to the poses (ref: docs/source/
+ * examples/camera/barf.rst) and intrinsics gives, as per-camera sums without float atomics: bitwise reproducible.
+ * g_origins / g_viewdirs [n_rays, 3] are the gradients that arrived (either may be NULL).  Rays are taken in camera
+ * order: camera_ids [n_rays] holds the ids SORTED ascending and order [n_rays] the ray of each sorted position (NULL: the
+ * rays are in that order already); x, y, g_origins and g_viewdirs are indexed by ray.  The sorted rays are cut into chunks of
+ * nfa_generate_rays_chunk(); a workgroup sums each (chunk, camera) run in a fixed order and writes it to row chunk + camera of
+ * partials [n_partial_rows >= ceil(n_rays / chunk) + n_cameras - 1, 16] (scratch, need not be initialised); a second
+ * launch adds each camera's rows in a fixed order and writes grad_camtoworlds [n_cameras, pose_floats] (pose_floats 12 or
+ * 16: the bottom row of a 4x4 gets 0) and grad_K [n_cameras, 9] (fx, fy, cx, cy; 0 elsewhere), either optional; a camera
+ * without rays gets zeros.  The caller sums the rows of a table it passed with stride 0.  With n_dist 8 the gradient of K
+ * passes through the inverse of the distortion Jacobian at the solution (0 where |det J| < eps); with the fisheye lens
+ * grad_K must be NULL.  The distortion parameters get no gradient.  n_rays == 0 returns at once and writes nothing. */
+int nfa_generate_rays_bwd(const void *x, const void *y, int32_t pixel_dtype, const int64_t *camera_ids, const int64_t *order,
+                          int64_t n_rays, int64_t n_cameras, const float *K, int64_t k_stride, const float *camtoworlds,
+                          int64_t pose_stride, const float *distortion, int32_t n_dist, int64_t dist_stride, int32_t fisheye,
+                          int32_t opengl, float pixel_center, int32_t normalize, float eps, int32_t iters,
+                          const float *g_origins, const float *g_viewdirs, float *partials, int64_t n_partial_rows,
+                          int32_t pose_floats, float *grad_camtoworlds, float *grad_K, nfa_stream_t stream);
+int nfa_generate_rays_chunk(void);   /* rays per chunk of the backward's reduction (a constant of the build) */
+
 #ifdef __cplusplus
 }
 #endif

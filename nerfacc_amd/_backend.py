@@ -117,6 +117,11 @@ _SIGS = {
     "nfa_sh_bwd": [_vp, _vp, _i64, _i32, _vp, _vp],
     "nfa_sample_positions_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
     "nfa_sample_positions_bwd": [_vp] * 9 + [_i64, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "nfa_generate_rays_fwd": [_vp, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _f32, _i32,
+                              _vp, _vp, _vp],
+    "nfa_generate_rays_bwd": [_vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _f32,
+                              _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp],
+    "nfa_generate_rays_chunk": [],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],

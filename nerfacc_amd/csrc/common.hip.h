@@ -254,6 +254,22 @@ __device__ __forceinline__ void store_l2(int64_t *p, int64_t a, int64_t b)
     else *reinterpret_cast<nfa_v2l *>(p) = v;
 }
 
+// Four consecutive xyz rows (48 B) of a streamed [n, 3] output from element e on: three 16-byte stores when `vec` (the base
+// is 16-byte aligned and the quad is full), else the first `cnt` rows element by element (samples.hip, rays.hip).
+__device__ __forceinline__ void store_rows12(float *__restrict__ out, int64_t e, bool vec, int cnt, const float v[12])
+{
+    float *b = out + 3 * e;
+    if (vec) {
+        store_f4(b, v[0], v[1], v[2], v[3]);
+        store_f4(b + 4, v[4], v[5], v[6], v[7]);
+        store_f4(b + 8, v[8], v[9], v[10], v[11]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < cnt) { b[3 * j] = v[3 * j]; b[3 * j + 1] = v[3 * j + 1]; b[3 * j + 2] = v[3 * j + 2]; }
+    }
+}
+
 // ---------------------------------------------------------------- what the traversal kernels of grid.hip and walk.hip share
 // Slab test, grid.cu:284-313 / include/utils_grid.cuh:10-55; tmin / tmax mean something only for a hit.
 __device__ __forceinline__ bool slab_test(const float o[3], const float inv[3], const float *bmin, const float *bmax, float near,

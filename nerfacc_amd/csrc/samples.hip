@@ -44,20 +44,6 @@ __device__ __forceinline__ void ray_rows(const float *__restrict__ o, const floa
     }
 }
 
-__device__ __forceinline__ void store_rows12(float *__restrict__ out, int64_t e, bool vec, int cnt, const float v[12])
-{
-    float *b = out + 3 * e;
-    if (vec) {
-        store_f4(b, v[0], v[1], v[2], v[3]);
-        store_f4(b + 4, v[4], v[5], v[6], v[7]);
-        store_f4(b + 8, v[8], v[9], v[10], v[11]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < cnt) { b[3 * j] = v[3 * j]; b[3 * j + 1] = v[3 * j + 1]; b[3 * j + 2] = v[3 * j + 2]; }
-    }
-}
-
 template <bool VEC, int MODE>
 __global__ __launch_bounds__(256) void sample_positions_kernel(SampleFwdArgs a)
 {
