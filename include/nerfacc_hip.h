@@ -456,6 +456,36 @@ int nfa_render_fused_bwd(const float *t_starts, const float *t_ends, const float
                          int64_t n_rays, int64_t n_elems, float *grad_sigmas, float *grad_rgbs,
                          nfa_stream_t stream);
 
+/* `rendering` from the field's RAW outputs (ref: volrend.py:109-151 with the activations of
+ * examples/radiance_fields/ngp.py:23-36,174-175,196 applied on load): nfa_render_fused_fwd with
+ *   sigma = selector ? density_act(raw_sigma + density_bias) : 0     and     rgb = rgb_act(raw_rgb).
+ * density_act: NFA_ACT_NONE, NFA_ACT_TRUNC_EXP (exp(z); its derivative is exp(min(z, 15))), NFA_ACT_EXP, NFA_ACT_RELU,
+ * NFA_ACT_SOFTPLUS (beta 1, threshold 20); rgb_act: NFA_RGB_ACT_NONE, NFA_RGB_ACT_SIGMOID.  selector[n] (bytes, 0 = false;
+ * may be NULL = all true) is a select: a non-finite raw density behind a false entry has no effect.  act_sigmas[n] and
+ * act_rgbs[n,3] (each may be NULL) receive the activated values.  With NFA_ACT_NONE, NFA_RGB_ACT_NONE, bias 0 and no
+ * selector the results are bit-identical to nfa_render_fused_fwd. */
+#define NFA_ACT_NONE 0
+#define NFA_ACT_TRUNC_EXP 1
+#define NFA_ACT_EXP 2
+#define NFA_ACT_RELU 3
+#define NFA_ACT_SOFTPLUS 4
+#define NFA_RGB_ACT_NONE 0
+#define NFA_RGB_ACT_SIGMOID 1
+int nfa_render_raw_fwd(const float *t_starts, const float *t_ends, const float *raw_sigmas, const float *raw_rgbs,
+                       const uint8_t *selector, int32_t density_act, float density_bias, int32_t rgb_act,
+                       const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays,
+                       int64_t n_elems, float *weights, float *trans, float *alphas, float *act_sigmas,
+                       float *act_rgbs, float *colors, float *opacities, float *depths, nfa_stream_t stream);
+/* Its backward in one reverse pass, from the raw inputs and the forward's trans alone: sigma, alpha and rgb are formed
+ * again with the forward's expressions and the activations' derivatives are multiplied in.  Gradient arguments as for
+ * nfa_render_fused_bwd.  Writes grad_raw_sigmas[n] (exactly 0 where selector is false) and/or grad_raw_rgbs[n,3]. */
+int nfa_render_raw_bwd(const float *t_starts, const float *t_ends, const float *raw_sigmas, const float *raw_rgbs,
+                       const uint8_t *selector, int32_t density_act, float density_bias, int32_t rgb_act,
+                       const float *trans, const float *g_colors, const float *g_opacities, const float *g_depths,
+                       const float *g_weights, const float *g_trans, const float *g_alphas,
+                       const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays,
+                       int64_t n_elems, float *grad_raw_sigmas, float *grad_raw_rgbs, nfa_stream_t stream);
+
 /* Mip-NeRF 360 distortion loss per ray (Barron et al. 2022, eq. 15) over samples in non-decreasing midpoint order
  * within each ray: loss[r] = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 (t_end_i - t_start_i), m = (t_start + t_end) / 2
  * (input out of that order gets what the O(n) prefix-sum form gives; it is not detected).  Also writes the per-ray totals

@@ -102,6 +102,8 @@ _SIGS = {
     "nfa_render_accumulate_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp],
     "nfa_render_fused_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nfa_render_fused_bwd": [_vp] * 13 + [_i64, _i64, _i64, _vp, _vp, _vp],
+    "nfa_render_raw_fwd": [_vp] * 5 + [_i32, _f32, _i32, _vp, _vp, _i64, _i64, _i64] + [_vp] * 9,
+    "nfa_render_raw_bwd": [_vp] * 5 + [_i32, _f32, _i32] + [_vp] * 9 + [_i64, _i64, _i64, _vp, _vp, _vp],
     "nfa_render_step_accumulate": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp],
     "nfa_distortion_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     "nfa_distortion_bwd": [_vp] * 8 + [_i64, _i64, _i64, _vp, _vp, _vp, _vp],
