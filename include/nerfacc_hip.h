@@ -10,7 +10,8 @@
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless its name ends in _host;
- *   - fp32 data, int64 indices/counts, uint8 for bool tensors (torch.bool);
+ *   - fp32 data, int64 indices/counts, uint8 for bool tensors (torch.bool); the `_t` entries take an element type
+ *     (NFA_ELEM_*) for the per-sample activation streams named in their comments, which then arrive as void *;
  *   - all work is enqueued on `stream` (hipStream_t passed as void*); nothing
  *     synchronises unless stated;
  *   - return value: 0 on success, otherwise a negative NFA_E* code; the text
@@ -36,6 +37,13 @@ extern "C" {
 #define NFA_MAX_GRID_LEVELS 8 /* fused in-kernel intersection+sort supports up to this many levels */
 
 typedef void *nfa_stream_t; /* hipStream_t */
+
+/* Element type of a per-sample activation stream of the `_t` entries.  Arithmetic is float32 whatever the code: a half
+ * value widens exactly on load, and a store rounds the float32 value the NFA_ELEM_F32 entry would have stored once, to
+ * nearest even (results in fp16's subnormal range included).  Any other code is NFA_EINVAL. */
+#define NFA_ELEM_F32 0
+#define NFA_ELEM_F16 1   /* IEEE binary16 */
+#define NFA_ELEM_BF16 2  /* bfloat16 */
 
 const char *nfa_last_error(void);
 /* The version of THIS header.  Bumped whenever an entry point changes its arguments or what it expects of them; a caller
@@ -485,6 +493,22 @@ int nfa_render_raw_bwd(const float *t_starts, const float *t_ends, const float *
                        const float *g_weights, const float *g_trans, const float *g_alphas,
                        const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays,
                        int64_t n_elems, float *grad_raw_sigmas, float *grad_raw_rgbs, nfa_stream_t stream);
+/* The two passes with raw_sigmas / raw_rgbs, and what is written in their shape (act_sigmas / act_rgbs forward,
+ * grad_raw_sigmas / grad_raw_rgbs backward), as elements of type `elem` (NFA_ELEM_*); everything else stays float32.
+ * nfa_render_raw_fwd / nfa_render_raw_bwd are the NFA_ELEM_F32 case.  A half stream takes the vector form when it is
+ * 8-byte aligned (and every float32 per-sample array 16-byte aligned, as above); any other address, aligned to the element
+ * (2 bytes), takes the scalar form, with identical results. */
+int nfa_render_raw_fwd_t(int32_t elem, const float *t_starts, const float *t_ends, const void *raw_sigmas,
+                         const void *raw_rgbs, const uint8_t *selector, int32_t density_act, float density_bias,
+                         int32_t rgb_act, const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles,
+                         int64_t n_rays, int64_t n_elems, float *weights, float *trans, float *alphas, void *act_sigmas,
+                         void *act_rgbs, float *colors, float *opacities, float *depths, nfa_stream_t stream);
+int nfa_render_raw_bwd_t(int32_t elem, const float *t_starts, const float *t_ends, const void *raw_sigmas,
+                         const void *raw_rgbs, const uint8_t *selector, int32_t density_act, float density_bias,
+                         int32_t rgb_act, const float *trans, const float *g_colors, const float *g_opacities,
+                         const float *g_depths, const float *g_weights, const float *g_trans, const float *g_alphas,
+                         const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays,
+                         int64_t n_elems, void *grad_raw_sigmas, void *grad_raw_rgbs, nfa_stream_t stream);
 
 /* Mip-NeRF 360 distortion loss per ray (Barron et al. 2022, eq. 15) over samples in non-decreasing midpoint order
  * within each ray: loss[r] = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 (t_end_i - t_start_i), m = (t_start + t_end) / 2
@@ -618,6 +642,21 @@ int nfa_hashgrid_bwd(const float *x, const float *params, const float *grad_y, i
 int nfa_sh_fwd(const float *dirs, int64_t n_points, int32_t degree, float *out, nfa_stream_t stream);
 int nfa_sh_bwd(const float *dirs, const float *grad_out, int64_t n_points, int32_t degree, float *grad_dirs,
                nfa_stream_t stream);
+/* The four encoding passes with y / grad_y and out / grad_out as elements of type `elem` (NFA_ELEM_*): a point's
+ * n_features values of a level, and a direction's row, are converted once and moved as one vector.  x, dirs, params and
+ * every gradient written stay float32.  The entries above are the NFA_ELEM_F32 case, with what they ask of their
+ * pointers; half y, grad_y, out and grad_out must be 16-byte aligned. */
+int nfa_hashgrid_fwd_t(int32_t elem, const float *x, const float *params, int64_t n_points, int32_t n_levels,
+                       int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                       const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, void *y,
+                       nfa_stream_t stream);
+int nfa_hashgrid_bwd_t(int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points,
+                       int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                       const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
+                       float *grad_x, nfa_stream_t stream);
+int nfa_sh_fwd_t(int32_t elem, const float *dirs, int64_t n_points, int32_t degree, void *out, nfa_stream_t stream);
+int nfa_sh_bwd_t(int32_t elem, const float *dirs, const void *grad_out, int64_t n_points, int32_t degree,
+                 float *grad_dirs, nfa_stream_t stream);
 
 /* ------------------------------------------------------------------ sample positions */
 

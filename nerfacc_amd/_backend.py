@@ -104,6 +104,8 @@ _SIGS = {
     "nfa_render_fused_bwd": [_vp] * 13 + [_i64, _i64, _i64, _vp, _vp, _vp],
     "nfa_render_raw_fwd": [_vp] * 5 + [_i32, _f32, _i32, _vp, _vp, _i64, _i64, _i64] + [_vp] * 9,
     "nfa_render_raw_bwd": [_vp] * 5 + [_i32, _f32, _i32] + [_vp] * 9 + [_i64, _i64, _i64, _vp, _vp, _vp],
+    "nfa_render_raw_fwd_t": [_i32] + [_vp] * 5 + [_i32, _f32, _i32, _vp, _vp, _i64, _i64, _i64] + [_vp] * 9,
+    "nfa_render_raw_bwd_t": [_i32] + [_vp] * 5 + [_i32, _f32, _i32] + [_vp] * 9 + [_i64, _i64, _i64, _vp, _vp, _vp],
     "nfa_render_step_accumulate": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp],
     "nfa_distortion_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     "nfa_distortion_bwd": [_vp] * 8 + [_i64, _i64, _i64, _vp, _vp, _vp, _vp],
@@ -117,6 +119,10 @@ _SIGS = {
     "nfa_hashgrid_bwd": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
     "nfa_sh_fwd": [_vp, _i64, _i32, _vp, _vp],
     "nfa_sh_bwd": [_vp, _vp, _i64, _i32, _vp, _vp],
+    "nfa_hashgrid_fwd_t": [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
+    "nfa_hashgrid_bwd_t": [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "nfa_sh_fwd_t": [_i32, _vp, _i64, _i32, _vp, _vp],
+    "nfa_sh_bwd_t": [_i32, _vp, _vp, _i64, _i32, _vp, _vp],
     "nfa_sample_positions_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
     "nfa_sample_positions_bwd": [_vp] * 9 + [_i64, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "nfa_generate_rays_fwd": [_vp, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _f32, _i32,
@@ -167,6 +173,10 @@ def load() -> C.CDLL:
 
 
 ABI_VERSION = 403   # include/nerfacc_hip.h: NFA_VERSION
+
+
+# include/nerfacc_hip.h: NFA_ELEM_*, the element type of the `_t` entries' activation streams
+ELEM_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
 def set_tuning(name: str, value: Optional[str]) -> None:

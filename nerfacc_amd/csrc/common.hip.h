@@ -239,6 +239,60 @@ __device__ __forceinline__ float lane_value(float v, int32_t l) { return __int_a
 // 16-byte stores of streamed outputs.  NT marks them non-temporal: traverse2.hip's expansions do, the engine ops lose with it.
 typedef float nfa_v4f __attribute__((ext_vector_type(4)));
 typedef long long nfa_v2l __attribute__((ext_vector_type(2)));
+typedef uint32_t nfa_v2u __attribute__((ext_vector_type(2)));
+typedef uint32_t nfa_v4u __attribute__((ext_vector_type(4)));
+
+// ---------------------------------------------------------------- half-precision activation streams (NFA_ELEM_*)
+// fp16 and bf16 are storage types only: every value is widened on load (exact) and arithmetic stays float32.  A store is
+// the compiler's conversion of the float32 value the float32 kernels store: one rounding to nearest even, results in fp16's
+// subnormal range kept (the f16 denormal mode is on by default), on gfx950 the packed bf16 convert.  Halves travel as the 16-bit halves of
+// dwords, two to a dword, lower address in the low half.
+typedef _Float16 nfa_f16;
+typedef __bf16 nfa_bf16;
+template <class E> struct ElemTag { using type = E; };
+
+template <class E>
+__device__ __forceinline__ uint32_t half_bits(float v)   // E(v) in the low 16 bits
+{
+    static_assert(sizeof(E) == 2, "half element types only");
+    // The float32 value exists, rounded, before it is converted: left to itself the compiler folds the float32 multiply or
+    // add that produced it into v_fma_mixlo_f16, which rounds the exact result to fp16 once -- in about one value of 2^13
+    // not the fp16 nearest to the float32 value the float32 kernel stores.  (No instruction: a constraint on a register.)
+    asm("" : "+v"(v));
+    const E h = (E)v;
+    uint16_t b;
+    __builtin_memcpy(&b, &h, 2);
+    return b;
+}
+template <class E>
+__device__ __forceinline__ float half_value(uint32_t bits16)
+{
+    if constexpr (std::is_same<E, nfa_bf16>::value) {
+        return __uint_as_float(bits16 << 16);
+    } else {
+        const uint16_t b = (uint16_t)bits16;
+        E h;
+        __builtin_memcpy(&h, &b, 2);
+        return (float)h;
+    }
+}
+template <class E>
+__device__ __forceinline__ uint32_t pack_halves(float lo, float hi) { return half_bits<E>(lo) | (half_bits<E>(hi) << 16); }
+// half k (0 or 1) of a dword
+template <class E>
+__device__ __forceinline__ float unpack_half(uint32_t w, int k) { return half_value<E>(k ? w >> 16 : w & 0xFFFFu); }
+
+// f(ElemTag<float / nfa_f16 / nfa_bf16>) for an NFA_ELEM_* code; false for any other code
+template <class F>
+static bool dispatch_elem(int32_t elem, F &&f)
+{
+    if (elem == NFA_ELEM_F32) f(ElemTag<float>{});
+    else if (elem == NFA_ELEM_F16) f(ElemTag<nfa_f16>{});
+    else if (elem == NFA_ELEM_BF16) f(ElemTag<nfa_bf16>{});
+    else return false;
+    return true;
+}
+
 template <bool NT = false>
 __device__ __forceinline__ void store_f4(float *p, float a, float b, float c, float d)
 {

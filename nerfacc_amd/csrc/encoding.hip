@@ -20,6 +20,11 @@
 // The backward scatters w_c * dL/dy with no-return global_atomic_add_f32 into a zeroed float32 table gradient; dL/dx
 // (optional) is formed per (point, level) and summed over the point's levels in level order across lanes, so it is
 // bitwise reproducible.
+//
+// Element types: y / dL/dy (and the spherical harmonics' out / dL/dout) are float, fp16 or bf16 (NFA_ELEM_*, common.hip.h).
+// The arithmetic is the float32 one whatever the type; a point's F values of a level are converted once and moved as one
+// vector of 2 F bytes.  The forward keeps its layout for half outputs: with F = 2 a wave writes 4-byte pieces at a 64-byte
+// stride, and still takes 0.80-0.85 of the time of one lane per (point, level) (DESIGN.md "Half-precision field path").
 #include "common.hip.h"
 
 namespace nfa {
@@ -41,6 +46,51 @@ template <> struct FVec<1> { float v[1]; };
 template <> struct FVec<2> { float v[2]; } __attribute__((aligned(8)));
 template <> struct FVec<4> { float v[4]; } __attribute__((aligned(16)));
 template <> struct FVec<8> { float v[8]; } __attribute__((aligned(16)));
+
+// K consecutive halves (E = fp16 or bf16) at p from / as floats, K = 1, 2, 4 or a multiple of 8: pieces of 2, 4, 8 or 16
+// bytes; p is aligned to the piece.
+template <int K, class E>
+__device__ __forceinline__ void store_elems(E *p, const float *v)
+{
+    if constexpr (K == 1) {
+        *reinterpret_cast<uint16_t *>(p) = (uint16_t)half_bits<E>(v[0]);
+    } else if constexpr (K == 2) {
+        *reinterpret_cast<uint32_t *>(p) = pack_halves<E>(v[0], v[1]);
+    } else if constexpr (K == 4) {
+        const nfa_v2u w = {pack_halves<E>(v[0], v[1]), pack_halves<E>(v[2], v[3])};
+        *reinterpret_cast<nfa_v2u *>(p) = w;
+    } else {
+        static_assert(K % 8 == 0, "K must be 1, 2, 4 or a multiple of 8");
+#pragma unroll
+        for (int k = 0; k < K; k += 8) {
+            const nfa_v4u w = {pack_halves<E>(v[k], v[k + 1]), pack_halves<E>(v[k + 2], v[k + 3]),
+                               pack_halves<E>(v[k + 4], v[k + 5]), pack_halves<E>(v[k + 6], v[k + 7])};
+            *reinterpret_cast<nfa_v4u *>(p + k) = w;
+        }
+    }
+}
+template <int K, class E>
+__device__ __forceinline__ void load_elems(const E *p, float *v)
+{
+    if constexpr (K == 1) {
+        v[0] = half_value<E>(*reinterpret_cast<const uint16_t *>(p));
+    } else if constexpr (K == 2) {
+        const uint32_t w = *reinterpret_cast<const uint32_t *>(p);
+        v[0] = unpack_half<E>(w, 0); v[1] = unpack_half<E>(w, 1);
+    } else if constexpr (K == 4) {
+        const nfa_v2u w = *reinterpret_cast<const nfa_v2u *>(p);
+        v[0] = unpack_half<E>(w.x, 0); v[1] = unpack_half<E>(w.x, 1); v[2] = unpack_half<E>(w.y, 0); v[3] = unpack_half<E>(w.y, 1);
+    } else {
+        static_assert(K % 8 == 0, "K must be 1, 2, 4 or a multiple of 8");
+#pragma unroll
+        for (int k = 0; k < K; k += 8) {
+            const nfa_v4u w = *reinterpret_cast<const nfa_v4u *>(p + k);
+            v[k] = unpack_half<E>(w.x, 0); v[k + 1] = unpack_half<E>(w.x, 1); v[k + 2] = unpack_half<E>(w.y, 0);
+            v[k + 3] = unpack_half<E>(w.y, 1); v[k + 4] = unpack_half<E>(w.z, 0); v[k + 5] = unpack_half<E>(w.z, 1);
+            v[k + 6] = unpack_half<E>(w.w, 0); v[k + 7] = unpack_half<E>(w.w, 1);
+        }
+    }
+}
 
 struct Cell {
     uint32_t g[3];
@@ -87,9 +137,9 @@ __device__ __forceinline__ bool lane_item(const HashGridLevels &T, int64_t wave,
 // stays in one XCD's L2 (4 MiB: a hashed level of the NGP grid), and write their F-float pieces at a stride of L F floats.
 // Measured against one lane per (point, level) with the level fastest in the wave (coalesced output rows): 0.83-0.90 of
 // its time at 2^20 points (DESIGN.md "Input encodings").
-template <int F>
+template <int F, class E>
 __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const float *__restrict__ x, const float *__restrict__ params,
-                                                           int64_t n_points, const HashGridLevels T, float *__restrict__ y)
+                                                           int64_t n_points, const HashGridLevels T, E *__restrict__ y)
 {
     const int l = (int)blockIdx.y;
     const bool hashed = (T.hashed >> l) & 1u;
@@ -109,16 +159,20 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const float *__restri
 #pragma unroll
             for (int j = 0; j < F; ++j) acc[j] = acc[j] + wc * v.v[j];
         }
-        FVec<F> out;
+        if constexpr (std::is_same<E, float>::value) {
+            FVec<F> out;
 #pragma unroll
-        for (int j = 0; j < F; ++j) out.v[j] = acc[j];
-        reinterpret_cast<FVec<F> *>(y)[n * T.n_levels + l] = out;
+            for (int j = 0; j < F; ++j) out.v[j] = acc[j];
+            reinterpret_cast<FVec<F> *>(y)[n * T.n_levels + l] = out;
+        } else {
+            store_elems<F>(y + (n * T.n_levels + l) * F, acc);
+        }
     }
 }
 
-template <int F>
+template <int F, class E>
 __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restrict__ x, const float *__restrict__ params,
-                                                           const float *__restrict__ g_y, int64_t n_points,
+                                                           const E *__restrict__ g_y, int64_t n_points,
                                                            const HashGridLevels T, float *__restrict__ g_params,
                                                            float *__restrict__ g_x)
 {
@@ -133,7 +187,9 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restri
             const Cell c = locate(x + n * 3, T.scale[l]);
             const bool hashed = (T.hashed >> l) & 1u;
             const uint32_t res = T.res[l], size = T.size[l];
-            const FVec<F> g = reinterpret_cast<const FVec<F> *>(g_y)[n * T.n_levels + l];
+            FVec<F> g;
+            if constexpr (std::is_same<E, float>::value) g = reinterpret_cast<const FVec<F> *>(g_y)[n * T.n_levels + l];
+            else load_elems<F>(g_y + (n * T.n_levels + l) * F, g.v);
             const uint32_t base = T.offset[l];
 #pragma unroll
             for (int corner = 0; corner < 8; ++corner) {
@@ -271,6 +327,28 @@ __device__ __forceinline__ void sh_grad(float x, float y, float z, const float *
 }
 
 // Row of K floats: float4 pieces when K is a multiple of 4 (rows stay 16-byte aligned), single floats otherwise.
+// Row of K halves (2 K bytes from a 16-byte aligned base: 2, 8, 18 or 32): K = 16 two 16-byte pieces, K = 4 one 8-byte
+// piece, single halves otherwise.
+template <int K, class E>
+__device__ __forceinline__ void store_row(E *dst, const float *v)
+{
+    if constexpr (K % 8 == 0 || K == 4) {
+        store_elems<K>(dst, v);
+    } else {
+#pragma unroll
+        for (int k = 0; k < K; ++k) store_elems<1>(dst + k, v + k);
+    }
+}
+template <int K, class E>
+__device__ __forceinline__ void load_row(const E *src, float *v)
+{
+    if constexpr (K % 8 == 0 || K == 4) {
+        load_elems<K>(src, v);
+    } else {
+#pragma unroll
+        for (int k = 0; k < K; ++k) load_elems<1>(src + k, v + k);
+    }
+}
 template <int K>
 __device__ __forceinline__ void store_row(float *dst, const float *v)
 {
@@ -297,8 +375,8 @@ __device__ __forceinline__ void load_row(const float *src, float *v)
     }
 }
 
-template <int DEG>
-__global__ __launch_bounds__(256) void sh_fwd_kernel(const float *__restrict__ dirs, int64_t n, float *__restrict__ out)
+template <int DEG, class E>
+__global__ __launch_bounds__(256) void sh_fwd_kernel(const float *__restrict__ dirs, int64_t n, E *__restrict__ out)
 {
     constexpr int K = DEG * DEG;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -310,8 +388,8 @@ __global__ __launch_bounds__(256) void sh_fwd_kernel(const float *__restrict__ d
     }
 }
 
-template <int DEG>
-__global__ __launch_bounds__(256) void sh_bwd_kernel(const float *__restrict__ dirs, const float *__restrict__ g_out,
+template <int DEG, class E>
+__global__ __launch_bounds__(256) void sh_bwd_kernel(const float *__restrict__ dirs, const E *__restrict__ g_out,
                                                      int64_t n, float *__restrict__ g_dirs)
 {
     constexpr int K = DEG * DEG;
@@ -368,13 +446,11 @@ static unsigned hashgrid_grid(int64_t n_points, const HashGridLevels &T)
     return grid_1d(ceil_div64(n_points, T.pts_per_wave) * 64, 256);
 }
 
-}  // namespace nfa
-
-using namespace nfa;
-
-int nfa_hashgrid_fwd(const float *x, const float *params, int64_t n_points, int32_t n_levels, int32_t n_features,
-                     int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
-                     const int32_t *sizes_host, int64_t n_params, float *y, nfa_stream_t stream)
+// ---------------------------------------------------------------- the entries, one implementation per element type
+template <class E>
+static int hashgrid_fwd(const float *x, const float *params, int64_t n_points, int32_t n_levels, int32_t n_features,
+                        int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                        const int32_t *sizes_host, int64_t n_params, E *y, nfa_stream_t stream)
 {
     HashGridLevels T;
     const int rc = hashgrid_table("hashgrid_fwd", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
@@ -382,22 +458,24 @@ int nfa_hashgrid_fwd(const float *x, const float *params, int64_t n_points, int3
     if (rc != NFA_OK) return rc;
     if (n_points == 0) return NFA_OK;
     NFA_REQUIRE(x && params && y, "hashgrid_fwd: null pointer");
+    NFA_REQUIRE((std::is_same<E, float>::value) || aligned16(y), "hashgrid_fwd: a half y must be 16-byte aligned");
     hipStream_t s = as_stream(stream);
     const dim3 grid(grid_1d(n_points, 256, 256 * 16 / n_levels + 1), n_levels), block(256);
     switch (n_features) {
-    case 1: hipLaunchKernelGGL(hashgrid_fwd_kernel<1>, grid, block, 0, s, x, params, n_points, T, y); break;
-    case 2: hipLaunchKernelGGL(hashgrid_fwd_kernel<2>, grid, block, 0, s, x, params, n_points, T, y); break;
-    case 4: hipLaunchKernelGGL(hashgrid_fwd_kernel<4>, grid, block, 0, s, x, params, n_points, T, y); break;
-    default: hipLaunchKernelGGL(hashgrid_fwd_kernel<8>, grid, block, 0, s, x, params, n_points, T, y); break;
+    case 1: hipLaunchKernelGGL((hashgrid_fwd_kernel<1, E>), grid, block, 0, s, x, params, n_points, T, y); break;
+    case 2: hipLaunchKernelGGL((hashgrid_fwd_kernel<2, E>), grid, block, 0, s, x, params, n_points, T, y); break;
+    case 4: hipLaunchKernelGGL((hashgrid_fwd_kernel<4, E>), grid, block, 0, s, x, params, n_points, T, y); break;
+    default: hipLaunchKernelGGL((hashgrid_fwd_kernel<8, E>), grid, block, 0, s, x, params, n_points, T, y); break;
     }
     NFA_CHECK_LAUNCH("hashgrid_fwd");
     return NFA_OK;
 }
 
-int nfa_hashgrid_bwd(const float *x, const float *params, const float *grad_y, int64_t n_points, int32_t n_levels,
-                     int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
-                     const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
-                     float *grad_x, nfa_stream_t stream)
+template <class E>
+static int hashgrid_bwd(const float *x, const float *params, const E *grad_y, int64_t n_points, int32_t n_levels,
+                        int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                        const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
+                        float *grad_x, nfa_stream_t stream)
 {
     HashGridLevels T;
     const int rc = hashgrid_table("hashgrid_bwd", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
@@ -405,53 +483,123 @@ int nfa_hashgrid_bwd(const float *x, const float *params, const float *grad_y, i
     if (rc != NFA_OK) return rc;
     if (n_points == 0) return NFA_OK;
     NFA_REQUIRE(x && grad_y && (grad_params || grad_x) && (params || !grad_x), "hashgrid_bwd: null pointer");
+    NFA_REQUIRE((std::is_same<E, float>::value) || aligned16(grad_y), "hashgrid_bwd: a half grad_y must be 16-byte aligned");
     const dim3 grid(hashgrid_grid(n_points, T)), block(256);
     hipStream_t s = as_stream(stream);
     switch (n_features) {
-    case 1: hipLaunchKernelGGL(hashgrid_bwd_kernel<1>, grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
-    case 2: hipLaunchKernelGGL(hashgrid_bwd_kernel<2>, grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
-    case 4: hipLaunchKernelGGL(hashgrid_bwd_kernel<4>, grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
-    default: hipLaunchKernelGGL(hashgrid_bwd_kernel<8>, grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
+    case 1: hipLaunchKernelGGL((hashgrid_bwd_kernel<1, E>), grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
+    case 2: hipLaunchKernelGGL((hashgrid_bwd_kernel<2, E>), grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
+    case 4: hipLaunchKernelGGL((hashgrid_bwd_kernel<4, E>), grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
+    default: hipLaunchKernelGGL((hashgrid_bwd_kernel<8, E>), grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
     }
     NFA_CHECK_LAUNCH("hashgrid_bwd");
     return NFA_OK;
 }
 
-int nfa_sh_fwd(const float *dirs, int64_t n_points, int32_t degree, float *out, nfa_stream_t stream)
+template <class E>
+static int sh_fwd(const float *dirs, int64_t n_points, int32_t degree, E *out, nfa_stream_t stream)
 {
     NFA_REQUIRE(n_points >= 0, "sh_fwd: negative size");
     NFA_REQUIRE(degree >= 1 && degree <= 4, "sh_fwd: degree must be in 1..4 (got %d)", degree);
     if (n_points == 0) return NFA_OK;
     NFA_REQUIRE(dirs && out, "sh_fwd: null pointer");
-    NFA_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0, "sh_fwd: out must be 16-byte aligned");
+    NFA_REQUIRE(aligned16(out), "sh_fwd: out must be 16-byte aligned");
     const dim3 grid(grid_1d(n_points, 256)), block(256);
     hipStream_t s = as_stream(stream);
     switch (degree) {
-    case 1: hipLaunchKernelGGL(sh_fwd_kernel<1>, grid, block, 0, s, dirs, n_points, out); break;
-    case 2: hipLaunchKernelGGL(sh_fwd_kernel<2>, grid, block, 0, s, dirs, n_points, out); break;
-    case 3: hipLaunchKernelGGL(sh_fwd_kernel<3>, grid, block, 0, s, dirs, n_points, out); break;
-    default: hipLaunchKernelGGL(sh_fwd_kernel<4>, grid, block, 0, s, dirs, n_points, out); break;
+    case 1: hipLaunchKernelGGL((sh_fwd_kernel<1, E>), grid, block, 0, s, dirs, n_points, out); break;
+    case 2: hipLaunchKernelGGL((sh_fwd_kernel<2, E>), grid, block, 0, s, dirs, n_points, out); break;
+    case 3: hipLaunchKernelGGL((sh_fwd_kernel<3, E>), grid, block, 0, s, dirs, n_points, out); break;
+    default: hipLaunchKernelGGL((sh_fwd_kernel<4, E>), grid, block, 0, s, dirs, n_points, out); break;
     }
     NFA_CHECK_LAUNCH("sh_fwd");
     return NFA_OK;
 }
 
-int nfa_sh_bwd(const float *dirs, const float *grad_out, int64_t n_points, int32_t degree, float *grad_dirs,
-               nfa_stream_t stream)
+template <class E>
+static int sh_bwd(const float *dirs, const E *grad_out, int64_t n_points, int32_t degree, float *grad_dirs, nfa_stream_t stream)
 {
     NFA_REQUIRE(n_points >= 0, "sh_bwd: negative size");
     NFA_REQUIRE(degree >= 1 && degree <= 4, "sh_bwd: degree must be in 1..4 (got %d)", degree);
     if (n_points == 0) return NFA_OK;
     NFA_REQUIRE(dirs && grad_out && grad_dirs, "sh_bwd: null pointer");
-    NFA_REQUIRE(reinterpret_cast<uintptr_t>(grad_out) % 16 == 0, "sh_bwd: grad_out must be 16-byte aligned");
+    NFA_REQUIRE(aligned16(grad_out), "sh_bwd: grad_out must be 16-byte aligned");
     const dim3 grid(grid_1d(n_points, 256)), block(256);
     hipStream_t s = as_stream(stream);
     switch (degree) {
-    case 1: hipLaunchKernelGGL(sh_bwd_kernel<1>, grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
-    case 2: hipLaunchKernelGGL(sh_bwd_kernel<2>, grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
-    case 3: hipLaunchKernelGGL(sh_bwd_kernel<3>, grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
-    default: hipLaunchKernelGGL(sh_bwd_kernel<4>, grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
+    case 1: hipLaunchKernelGGL((sh_bwd_kernel<1, E>), grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
+    case 2: hipLaunchKernelGGL((sh_bwd_kernel<2, E>), grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
+    case 3: hipLaunchKernelGGL((sh_bwd_kernel<3, E>), grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
+    default: hipLaunchKernelGGL((sh_bwd_kernel<4, E>), grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
     }
     NFA_CHECK_LAUNCH("sh_bwd");
     return NFA_OK;
+}
+
+}  // namespace nfa
+
+using namespace nfa;
+
+#define ELEM_DISPATCH(name, elem, call)                                                        \
+    int rc = NFA_OK;                                                                           \
+    if (!dispatch_elem(elem, [&](auto tag) { using E = typename decltype(tag)::type; rc = call; })) \
+        NFA_REQUIRE(false, name ": elem must be NFA_ELEM_F32, NFA_ELEM_F16 or NFA_ELEM_BF16 (got %d)", (int)(elem)); \
+    return rc
+
+int nfa_hashgrid_fwd_t(int32_t elem, const float *x, const float *params, int64_t n_points, int32_t n_levels,
+                       int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                       const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, void *y,
+                       nfa_stream_t stream)
+{
+    ELEM_DISPATCH("hashgrid_fwd", elem, hashgrid_fwd(x, params, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                                                     resolutions_host, sizes_host, n_params, static_cast<E *>(y), stream));
+}
+
+int nfa_hashgrid_fwd(const float *x, const float *params, int64_t n_points, int32_t n_levels, int32_t n_features,
+                     int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                     const int32_t *sizes_host, int64_t n_params, float *y, nfa_stream_t stream)
+{
+    return nfa_hashgrid_fwd_t(NFA_ELEM_F32, x, params, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                              resolutions_host, sizes_host, n_params, y, stream);
+}
+
+int nfa_hashgrid_bwd_t(int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points,
+                       int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                       const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
+                       float *grad_x, nfa_stream_t stream)
+{
+    ELEM_DISPATCH("hashgrid_bwd", elem, hashgrid_bwd(x, params, static_cast<const E *>(grad_y), n_points, n_levels, n_features,
+                                                     log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params,
+                                                     grad_params, grad_x, stream));
+}
+
+int nfa_hashgrid_bwd(const float *x, const float *params, const float *grad_y, int64_t n_points, int32_t n_levels,
+                     int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                     const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
+                     float *grad_x, nfa_stream_t stream)
+{
+    return nfa_hashgrid_bwd_t(NFA_ELEM_F32, x, params, grad_y, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                              resolutions_host, sizes_host, n_params, grad_params, grad_x, stream);
+}
+
+int nfa_sh_fwd_t(int32_t elem, const float *dirs, int64_t n_points, int32_t degree, void *out, nfa_stream_t stream)
+{
+    ELEM_DISPATCH("sh_fwd", elem, sh_fwd(dirs, n_points, degree, static_cast<E *>(out), stream));
+}
+
+int nfa_sh_fwd(const float *dirs, int64_t n_points, int32_t degree, float *out, nfa_stream_t stream)
+{
+    return nfa_sh_fwd_t(NFA_ELEM_F32, dirs, n_points, degree, out, stream);
+}
+
+int nfa_sh_bwd_t(int32_t elem, const float *dirs, const void *grad_out, int64_t n_points, int32_t degree, float *grad_dirs,
+                 nfa_stream_t stream)
+{
+    ELEM_DISPATCH("sh_bwd", elem, sh_bwd(dirs, static_cast<const E *>(grad_out), n_points, degree, grad_dirs, stream));
+}
+
+int nfa_sh_bwd(const float *dirs, const float *grad_out, int64_t n_points, int32_t degree, float *grad_dirs,
+               nfa_stream_t stream)
+{
+    return nfa_sh_bwd_t(NFA_ELEM_F32, dirs, grad_out, n_points, degree, grad_dirs, stream);
 }

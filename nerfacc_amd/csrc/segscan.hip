@@ -1617,6 +1617,104 @@ struct RenderFusedBwdOp : OpBase {
 //      it forms sigma, alpha and c again from the raw ones with the forward's expressions.
 //      Compiler's report (VEC forms, no scratch in any): forward 91 VGPRs against RenderFusedFwdOp's 81, both 5 waves per
 //      SIMD; backward 124 against RenderFusedBwdOp's 117 (4 waves), with EXTRA 147 against 137 (3 waves).
+// Half twins of ld4 / store4 / load_rgb12 / fix_rgb12 / store_rgb12 for raw streams of E = fp16 or bf16 (common.hip.h).  A
+// lane's 4 elements are 8 bytes, its 4 colours 24: with VEC (the stream 8-byte aligned) one and three 8-byte vectors, raw
+// like the float loads -- the halves are widened where they are consumed (elem / fix_rgb12), not behind the load.
+// Without VEC every element is a 2-byte access, packed into the same dwords.
+static_assert(SE == 4, "the half twins move one 8-byte quad per lane");
+template <class E> struct H4 { uint32_t w[2]; };    // one lane's elements of a step, raw
+template <class E> struct H12 { uint32_t w[6]; };   // one lane's colours of a step, raw
+__device__ __forceinline__ float elem(const F4 &r, int j) { return r.v[j]; }
+template <class E>
+__device__ __forceinline__ float elem(const H4<E> &r, int j) { return unpack_half<E>(r.w[j / 2], j % 2); }
+__device__ __forceinline__ uint32_t raw_half(const void *b, int32_t i) { return reinterpret_cast<const uint16_t *>(b)[i]; }
+
+template <bool VEC, class E>
+__device__ __forceinline__ void ld4(const E *__restrict__ p, const Pos &q, H4<E> &out)
+{
+    const E *b = p + q.c;
+    if (VEC) {
+        const nfa_v2u v = *reinterpret_cast<const nfa_v2u *>(b + (q.qany[0] ? q.off : q.safe));
+        out.w[0] = v.x; out.w[1] = v.y;
+    } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            out.w[h] = raw_half(b, q.valid[2 * h] ? q.off + 2 * h : q.safe) | (raw_half(b, q.valid[2 * h + 1] ? q.off + 2 * h + 1 : q.safe) << 16);
+    }
+}
+template <bool VEC, class E>
+__device__ __forceinline__ void store4(E *__restrict__ p, const Pos &q, const float v[SE])
+{
+    E *b = p + q.c;
+    if (VEC && q.qall[0]) {
+        const nfa_v2u w = {pack_halves<E>(v[0], v[1]), pack_halves<E>(v[2], v[3])};
+        *reinterpret_cast<nfa_v2u *>(b + q.off) = w;
+    } else {
+        NFA_ELEMENTWISE_PATH();
+#pragma unroll
+        for (int j = 0; j < SE; ++j)
+            if (q.valid[j]) reinterpret_cast<uint16_t *>(b)[q.off + j] = (uint16_t)half_bits<E>(v[j]);
+    }
+}
+template <class E>
+__device__ __forceinline__ void load_rgb12(const E *rgb, bool vec, const Pos &q, H12<E> &c)
+{
+    const E *b = rgb + 3 * q.c;
+    if (vec) {
+        const nfa_v2u *v = reinterpret_cast<const nfa_v2u *>(b + 3 * (q.qall[0] ? q.off : q.safe));
+        const nfa_v2u q0 = v[0], q1 = v[1], q2 = v[2];
+        c.w[0] = q0.x; c.w[1] = q0.y; c.w[2] = q1.x; c.w[3] = q1.y; c.w[4] = q2.x; c.w[5] = q2.y;
+    } else {
+#pragma unroll
+        for (int j = 0; j < SE; j += 2) {   // two samples: six halves, three dwords
+            const int32_t e0 = 3 * (q.valid[j] ? q.off + j : q.safe), e1 = 3 * (q.valid[j + 1] ? q.off + j + 1 : q.safe);
+            c.w[3 * j / 2] = raw_half(b, e0) | (raw_half(b, e0 + 1) << 16);
+            c.w[3 * j / 2 + 1] = raw_half(b, e0 + 2) | (raw_half(b, e1) << 16);
+            c.w[3 * j / 2 + 2] = raw_half(b, e1 + 1) | (raw_half(b, e1 + 2) << 16);
+        }
+    }
+}
+template <class E>
+__device__ __forceinline__ void fix_rgb12(const E *rgb, bool vec, const Pos &q, const H12<E> &raw, float c[3 * SE])
+{
+#pragma unroll
+    for (int k = 0; k < 3 * SE; ++k) c[k] = unpack_half<E>(raw.w[k / 2], k % 2);
+    if (vec && q.any && !q.all) {  // rare: first / last lane of a range
+        const E *b = rgb + 3 * q.c;
+#pragma unroll
+        for (int j = 0; j < SE; ++j)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) c[3 * j + k] = q.valid[j] ? half_value<E>(raw_half(b, 3 * (q.off + j) + k)) : 0.0f;
+    }
+#pragma unroll
+    for (int j = 0; j < SE; ++j)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[3 * j + k] = q.valid[j] ? c[3 * j + k] : 0.0f;
+}
+template <class E>
+__device__ __forceinline__ void store_rgb12(E *rgb, bool vec, const Pos &q, const float g[3 * SE])
+{
+    E *b = rgb + 3 * q.c;
+    if (vec && q.qall[0]) {
+        nfa_v2u *o = reinterpret_cast<nfa_v2u *>(b + 3 * q.off);
+        const nfa_v2u w0 = {pack_halves<E>(g[0], g[1]), pack_halves<E>(g[2], g[3])};
+        const nfa_v2u w1 = {pack_halves<E>(g[4], g[5]), pack_halves<E>(g[6], g[7])};
+        const nfa_v2u w2 = {pack_halves<E>(g[8], g[9]), pack_halves<E>(g[10], g[11])};
+        o[0] = w0; o[1] = w1; o[2] = w2;
+    } else {
+        NFA_ELEMENTWISE_PATH();
+#pragma unroll
+        for (int j = 0; j < SE; ++j)
+            if (q.valid[j]) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) reinterpret_cast<uint16_t *>(b)[3 * (q.off + j) + k] = (uint16_t)half_bits<E>(g[3 * j + k]);
+            }
+    }
+}
+// what an op keeps of a step's raw loads from a stream of E
+template <class E> struct RawStream { typedef H4<E> S4; typedef H12<E> C12; };
+template <> struct RawStream<float> { typedef F4 S4; typedef float C12[3 * SE]; };
+
 struct RawAct {
     const uint8_t *mask;   // [n] bool, or null: where false the density is exactly 0 and so is its gradient
     int32_t mask_vec;      // mask is 4-byte aligned
@@ -1653,13 +1751,16 @@ struct RawAct {
     __device__ __forceinline__ bool live(const U4 &m, int j) const { return !mask || ((m.w[j / 4] >> (8 * (j % 4))) & 0xFFu); }
 };
 
-template <bool VEC>
+template <bool VEC, class ET /* element type of sig / rgb / asig / argb */>
 struct RenderRawFwdOp : OpBase {
     static constexpr int NCHB = 5;
-    struct Raw { F4 a, b, s; U4 m; float c[3 * SE]; };
-    const float *ts, *te, *sig, *rgb;
+    struct Raw { F4 a, b; typename RawStream<ET>::S4 s; U4 m; typename RawStream<ET>::C12 c; };
+    const float *ts, *te;
+    const ET *sig, *rgb;
     RawAct act;
-    float *w, *tr, *al, *asig, *argb, *colors, *opac, *depth;
+    float *w, *tr, *al;
+    ET *asig, *argb;
+    float *colors, *opac, *depth;
     float xs[SE], mid[SE], sg[SE], rw[SE], rt[SE], ra[SE], c[3 * SE];
     __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
     {
@@ -1676,7 +1777,7 @@ struct RenderRawFwdOp : OpBase {
         act.colours(c);
 #pragma unroll
         for (int j = 0; j < SE; ++j) {
-            sg[j] = act.live(r.m, j) ? act.density(r.s.v[j] + act.bias) : 0.0f;
+            sg[j] = act.live(r.m, j) ? act.density(elem(r.s, j) + act.bias) : 0.0f;
             xs[j] = valid[j] ? sg[j] * (r.b.v[j] - r.a.v[j]) : 0.0f;
             mid[j] = (r.a.v[j] + r.b.v[j]) / 2.0f;
         }
@@ -1714,16 +1815,18 @@ struct RenderRawFwdOp : OpBase {
     }
 };
 
-template <bool VEC, bool EXTRA /* gradients arrive at weights / trans / alphas too */>
+template <bool VEC, bool EXTRA /* gradients arrive at weights / trans / alphas too */, class ET /* of sig / rgb / gsig / grgb */>
 struct RenderRawBwdOp : OpBase {
     static constexpr bool NEEDS_RID = true;
     static constexpr int RAY_CAP = 192;                  // per-ray gradients staged in LDS: see RenderFusedBwdOp
     static constexpr int RAY_LDS_FLOATS = 8 * RAY_CAP;   // {g_r, g_g, g_b, g_opacity, g_depth, -, -, -} per ray
     static constexpr bool PIPE = true;
-    struct Raw { F4 a, b, T, s, gw, gt, ga; U4 m; float c[3 * SE]; };
-    const float *ts, *te, *sig, *rgb, *tr, *gc, *go, *gd, *gw, *gt, *ga;
+    struct Raw { F4 a, b, T; typename RawStream<ET>::S4 s; F4 gw, gt, ga; U4 m; typename RawStream<ET>::C12 c; };
+    const float *ts, *te;
+    const ET *sig, *rgb;
+    const float *tr, *gc, *go, *gd, *gw, *gt, *ga;
     RawAct act;
-    float *gsig, *grgb;
+    ET *gsig, *grgb;
     const float *g_lds = nullptr;
     int32_t g_lo = 0, g_n = 0;
     __device__ __forceinline__ void tile_begin(int32_t r_lo, int32_t r_hi, float *lds)
@@ -1764,7 +1867,7 @@ struct RenderRawBwdOp : OpBase {
         for (int j = 0; j < SE; ++j) {
             // sigma and alpha as the forward pass formed them
             const bool on = act.live(r.m, j);
-            const float z = r.s.v[j] + act.bias;
+            const float z = elem(r.s, j) + act.bias;
             const float s = on ? act.density(z) : 0.0f;
             ds[j] = (on && valid[j]) ? act.density_grad(z, s) : 0.0f;
             dlt[j] = r.b.v[j] - r.a.v[j];
@@ -2552,11 +2655,17 @@ static RawAct raw_act(const uint8_t *selector, int32_t density_act, float densit
                 name ": density_act must be in 0..4 (got %d)", (int)density_act);                                \
     NFA_REQUIRE(rgb_act == NFA_RGB_ACT_NONE || rgb_act == NFA_RGB_ACT_SIGMOID, name ": rgb_act must be 0 or 1 (got %d)", (int)rgb_act)
 
-int nfa_render_raw_fwd(const float *t_starts, const float *t_ends, const float *raw_sigmas, const float *raw_rgbs,
-                       const uint8_t *selector, int32_t density_act, float density_bias, int32_t rgb_act,
-                       const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays, int64_t n_elems,
-                       float *weights, float *trans, float *alphas, float *act_sigmas, float *act_rgbs, float *colors,
-                       float *opacities, float *depths, nfa_stream_t stream)
+extern "C++" {   // one implementation per element type
+// A half stream takes the vector form when its quads are 8-byte aligned
+static inline bool aligned_quads(const float *p) { return aligned16(p); }
+static inline bool aligned_quads(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+template <class E>
+static int render_raw_fwd(const float *t_starts, const float *t_ends, const E *raw_sigmas, const E *raw_rgbs,
+                          const uint8_t *selector, int32_t density_act, float density_bias, int32_t rgb_act,
+                          const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays, int64_t n_elems,
+                          float *weights, float *trans, float *alphas, E *act_sigmas, E *act_rgbs, float *colors,
+                          float *opacities, float *depths, nfa_stream_t stream)
 {
     SEG_COMMON_CHECKS("render_raw_fwd");
     RAW_ACT_CHECKS("render_raw_fwd");
@@ -2564,9 +2673,10 @@ int nfa_render_raw_fwd(const float *t_starts, const float *t_ends, const float *
     NFA_REQUIRE(colors && opacities && depths && (n_elems == 0 || (t_starts && t_ends && raw_sigmas && raw_rgbs)),
                 "render_raw_fwd: null pointer");
     hipStream_t s = as_stream(stream);
-    const bool vec = all_aligned16(t_starts, t_ends, raw_sigmas, raw_rgbs, weights, trans, alphas, act_sigmas, act_rgbs);
+    const bool vec = all_aligned16(t_starts, t_ends, weights, trans, alphas) && aligned_quads(raw_sigmas) &&
+                     aligned_quads(raw_rgbs) && aligned_quads(act_sigmas) && aligned_quads(act_rgbs);
     dispatch_bool(vec, [&](auto V) {
-        RenderRawFwdOp<V> op;
+        RenderRawFwdOp<V, E> op;
         op.ts = t_starts; op.te = t_ends; op.sig = raw_sigmas; op.rgb = raw_rgbs;
         op.act = raw_act(selector, density_act, density_bias, rgb_act);
         op.w = weights; op.tr = trans; op.al = alphas; op.asig = act_sigmas; op.argb = act_rgbs;
@@ -2577,12 +2687,13 @@ int nfa_render_raw_fwd(const float *t_starts, const float *t_ends, const float *
     return NFA_OK;
 }
 
-int nfa_render_raw_bwd(const float *t_starts, const float *t_ends, const float *raw_sigmas, const float *raw_rgbs,
-                       const uint8_t *selector, int32_t density_act, float density_bias, int32_t rgb_act, const float *trans,
-                       const float *g_colors, const float *g_opacities, const float *g_depths, const float *g_weights,
-                       const float *g_trans, const float *g_alphas, const int64_t *packed_info, const int64_t *tiles,
-                       int64_t n_tiles, int64_t n_rays, int64_t n_elems, float *grad_raw_sigmas, float *grad_raw_rgbs,
-                       nfa_stream_t stream)
+template <class E>
+static int render_raw_bwd(const float *t_starts, const float *t_ends, const E *raw_sigmas, const E *raw_rgbs,
+                          const uint8_t *selector, int32_t density_act, float density_bias, int32_t rgb_act, const float *trans,
+                          const float *g_colors, const float *g_opacities, const float *g_depths, const float *g_weights,
+                          const float *g_trans, const float *g_alphas, const int64_t *packed_info, const int64_t *tiles,
+                          int64_t n_tiles, int64_t n_rays, int64_t n_elems, E *grad_raw_sigmas, E *grad_raw_rgbs,
+                          nfa_stream_t stream)
 {
     SEG_COMMON_CHECKS("render_raw_bwd");
     RAW_ACT_CHECKS("render_raw_bwd");
@@ -2590,12 +2701,12 @@ int nfa_render_raw_bwd(const float *t_starts, const float *t_ends, const float *
     NFA_REQUIRE(t_starts && t_ends && raw_sigmas && raw_rgbs && trans && (grad_raw_sigmas || grad_raw_rgbs),
                 "render_raw_bwd: null pointer");
     hipStream_t s = as_stream(stream);
-    const bool vec = all_aligned16(t_starts, t_ends, raw_sigmas, raw_rgbs, trans, g_weights, g_trans, g_alphas, grad_raw_sigmas,
-                                   grad_raw_rgbs);
+    const bool vec = all_aligned16(t_starts, t_ends, trans, g_weights, g_trans, g_alphas) && aligned_quads(raw_sigmas) &&
+                     aligned_quads(raw_rgbs) && aligned_quads(grad_raw_sigmas) && aligned_quads(grad_raw_rgbs);
     const bool extra = g_weights || g_trans || g_alphas;
     dispatch_bool(vec, [&](auto V) {
         dispatch_bool(extra, [&](auto X) {
-            RenderRawBwdOp<V, X> op;
+            RenderRawBwdOp<V, X, E> op;
             op.ts = t_starts; op.te = t_ends; op.sig = raw_sigmas; op.rgb = raw_rgbs; op.tr = trans;
             op.act = raw_act(selector, density_act, density_bias, rgb_act);
             op.gc = g_colors; op.go = g_opacities; op.gd = g_depths; op.gw = g_weights; op.gt = g_trans; op.ga = g_alphas;
@@ -2605,6 +2716,62 @@ int nfa_render_raw_bwd(const float *t_starts, const float *t_ends, const float *
     });
     NFA_CHECK_LAUNCH("render_raw_bwd");
     return NFA_OK;
+}
+
+}  // extern "C++"
+
+#define RAW_ELEM_DISPATCH(name, call)                                                                                  \
+    int rc = NFA_OK;                                                                                                   \
+    if (!dispatch_elem(elem, [&](auto tag) { using E = typename decltype(tag)::type; rc = call; }))                     \
+        NFA_REQUIRE(false, name ": elem must be NFA_ELEM_F32, NFA_ELEM_F16 or NFA_ELEM_BF16 (got %d)", (int)elem);      \
+    return rc
+
+int nfa_render_raw_fwd_t(int32_t elem, const float *t_starts, const float *t_ends, const void *raw_sigmas,
+                         const void *raw_rgbs, const uint8_t *selector, int32_t density_act, float density_bias,
+                         int32_t rgb_act, const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles,
+                         int64_t n_rays, int64_t n_elems, float *weights, float *trans, float *alphas, void *act_sigmas,
+                         void *act_rgbs, float *colors, float *opacities, float *depths, nfa_stream_t stream)
+{
+    RAW_ELEM_DISPATCH("render_raw_fwd", render_raw_fwd(
+        t_starts, t_ends, static_cast<const E *>(raw_sigmas), static_cast<const E *>(raw_rgbs), selector, density_act,
+        density_bias, rgb_act, packed_info, tiles, n_tiles, n_rays, n_elems, weights, trans, alphas,
+        static_cast<E *>(act_sigmas), static_cast<E *>(act_rgbs), colors, opacities, depths, stream));
+}
+
+int nfa_render_raw_fwd(const float *t_starts, const float *t_ends, const float *raw_sigmas, const float *raw_rgbs,
+                       const uint8_t *selector, int32_t density_act, float density_bias, int32_t rgb_act,
+                       const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays, int64_t n_elems,
+                       float *weights, float *trans, float *alphas, float *act_sigmas, float *act_rgbs, float *colors,
+                       float *opacities, float *depths, nfa_stream_t stream)
+{
+    return nfa_render_raw_fwd_t(NFA_ELEM_F32, t_starts, t_ends, raw_sigmas, raw_rgbs, selector, density_act, density_bias,
+                                rgb_act, packed_info, tiles, n_tiles, n_rays, n_elems, weights, trans, alphas, act_sigmas,
+                                act_rgbs, colors, opacities, depths, stream);
+}
+
+int nfa_render_raw_bwd_t(int32_t elem, const float *t_starts, const float *t_ends, const void *raw_sigmas,
+                         const void *raw_rgbs, const uint8_t *selector, int32_t density_act, float density_bias,
+                         int32_t rgb_act, const float *trans, const float *g_colors, const float *g_opacities,
+                         const float *g_depths, const float *g_weights, const float *g_trans, const float *g_alphas,
+                         const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays,
+                         int64_t n_elems, void *grad_raw_sigmas, void *grad_raw_rgbs, nfa_stream_t stream)
+{
+    RAW_ELEM_DISPATCH("render_raw_bwd", render_raw_bwd(
+        t_starts, t_ends, static_cast<const E *>(raw_sigmas), static_cast<const E *>(raw_rgbs), selector, density_act,
+        density_bias, rgb_act, trans, g_colors, g_opacities, g_depths, g_weights, g_trans, g_alphas, packed_info, tiles,
+        n_tiles, n_rays, n_elems, static_cast<E *>(grad_raw_sigmas), static_cast<E *>(grad_raw_rgbs), stream));
+}
+
+int nfa_render_raw_bwd(const float *t_starts, const float *t_ends, const float *raw_sigmas, const float *raw_rgbs,
+                       const uint8_t *selector, int32_t density_act, float density_bias, int32_t rgb_act, const float *trans,
+                       const float *g_colors, const float *g_opacities, const float *g_depths, const float *g_weights,
+                       const float *g_trans, const float *g_alphas, const int64_t *packed_info, const int64_t *tiles,
+                       int64_t n_tiles, int64_t n_rays, int64_t n_elems, float *grad_raw_sigmas, float *grad_raw_rgbs,
+                       nfa_stream_t stream)
+{
+    return nfa_render_raw_bwd_t(NFA_ELEM_F32, t_starts, t_ends, raw_sigmas, raw_rgbs, selector, density_act, density_bias,
+                                rgb_act, trans, g_colors, g_opacities, g_depths, g_weights, g_trans, g_alphas, packed_info,
+                                tiles, n_tiles, n_rays, n_elems, grad_raw_sigmas, grad_raw_rgbs, stream);
 }
 
 int nfa_distortion_fwd(const float *weights, const float *t_starts, const float *t_ends, const int64_t *packed_info,

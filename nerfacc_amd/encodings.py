@@ -10,6 +10,11 @@ CUDA float32 tensors run on libnerfacc_hip.so; CPU tensors and other dtypes run 
 torch path reproduces the native forward bit for bit).  Under ``torch.autocast`` both encodings run in float32, as tcnn's
 do.  Neither direction reads from the device, so a step that uses them can be captured (``CapturedStep``).
 
+``out_dtype`` (``None``: float32) makes an encoding write fp16 or bf16 activations, as tcnn's do by default, and take
+the gradient in that dtype: the arithmetic stays float32, the kernels convert each value once as they store or load it, so
+the output equals ``float32_output.to(out_dtype)`` bit for bit and no cast pass runs next to a mixed-precision MLP.
+``"autocast"`` follows the active autocast dtype.  Parameters, inputs and their gradients are float32 either way.
+
 Not part of ``nerfacc_amd.__all__`` (that list mirrors the reference's exactly); import the module.
 """
 from __future__ import annotations
@@ -101,18 +106,53 @@ def _aligned16(t: Tensor) -> Tensor:
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
+_HALF = (torch.float16, torch.bfloat16)
+
+
+def _check_out_dtype(out_dtype):
+    if out_dtype is None or out_dtype == "autocast" or out_dtype in _HALF:   # (a str never equals a torch.dtype)
+        return out_dtype
+    if out_dtype == torch.float32:
+        return None
+    raise ValueError(f"out_dtype must be None, torch.float32, torch.float16, torch.bfloat16 or 'autocast' (got {out_dtype!r})")
+
+
+def _resolve_out_dtype(out_dtype, x: Tensor) -> torch.dtype:
+    """The dtype an encoding returns for input ``x``; call before autocast is switched off."""
+    if out_dtype is None:
+        return torch.float32
+    if out_dtype == "autocast":
+        dt = x.device.type
+        if torch.is_autocast_enabled(dt) and torch.get_autocast_dtype(dt) in _HALF:
+            return torch.get_autocast_dtype(dt)
+        return torch.float32
+    return out_dtype
+
+
+def _entry(name: str, dtype: torch.dtype):
+    """(entry point, leading arguments): float32 calls the unsuffixed entry as ever, fp16 / bf16 the ``_t`` one."""
+    return (name, ()) if dtype == torch.float32 else (name + "_t", (B.ELEM_CODES[dtype],))
+
+
+def _grad_as(g: Tensor, dtype: torch.dtype) -> Tensor:
+    """The incoming gradient as the backward kernels read it: contiguous, 16-byte aligned, in the output's dtype (autograd
+    delivers it in that dtype, so a half gradient is handed over as it is, never widened)."""
+    return _aligned16(g if g.dtype == dtype else g.to(dtype))
+
+
 class _HashGridFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, params, enc: "HashGridEncoding"):
+    def forward(ctx, x, params, enc: "HashGridEncoding", dtype: torch.dtype):
         B.require_device(x, params)
         t, L, F = enc.table, enc.n_levels, enc.n_features_per_level
         N = x.shape[0]
-        y = torch.empty(N, L * F, dtype=torch.float32, device=x.device)
+        y = torch.empty(N, L * F, dtype=dtype, device=x.device)
         if N:
             with torch.cuda.device(x.device):
-                B.call("nfa_hashgrid_fwd", B.ptr(x), B.ptr(params), N, L, F, t.log2_hashmap_size, t.c_scales, t.c_res,
+                entry, elem = _entry("nfa_hashgrid_fwd", dtype)
+                B.call(entry, *elem, B.ptr(x), B.ptr(params), N, L, F, t.log2_hashmap_size, t.c_scales, t.c_res,
                        t.c_sizes, params.numel(), B.ptr(y), B.stream())
-        ctx.enc = enc
+        ctx.enc, ctx.dtype = enc, dtype
         ctx.save_for_backward(x, params)
         return y
 
@@ -121,30 +161,32 @@ class _HashGridFn(torch.autograd.Function):
     def backward(ctx, g_y):
         need_x, need_p = ctx.needs_input_grad[:2]
         if g_y is None or not (need_x or need_p):
-            return None, None, None
+            return None, None, None, None
         x, params = ctx.saved_tensors
         enc = ctx.enc
         t, L, F = enc.table, enc.n_levels, enc.n_features_per_level
-        g = _aligned16(g_y.to(torch.float32))
+        g = _grad_as(g_y, ctx.dtype)
         g_p = torch.zeros_like(params) if need_p else None
         g_x = torch.empty_like(x) if need_x else None
         if x.shape[0]:
             with torch.cuda.device(x.device):
-                B.call("nfa_hashgrid_bwd", B.ptr(x), B.ptr(params), B.ptr(g), x.shape[0], L, F, t.log2_hashmap_size,
+                entry, elem = _entry("nfa_hashgrid_bwd", ctx.dtype)
+                B.call(entry, *elem, B.ptr(x), B.ptr(params), B.ptr(g), x.shape[0], L, F, t.log2_hashmap_size,
                        t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(g_p), B.ptr(g_x), B.stream())
-        return g_x, g_p, None
+        return g_x, g_p, None, None
 
 
 class _SHFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, dirs, degree: int):
+    def forward(ctx, dirs, degree: int, dtype: torch.dtype):
         B.require_device(dirs)
         N = dirs.shape[0]
-        out = torch.empty(N, degree * degree, dtype=torch.float32, device=dirs.device)
+        out = torch.empty(N, degree * degree, dtype=dtype, device=dirs.device)
         if N:
             with torch.cuda.device(dirs.device):
-                B.call("nfa_sh_fwd", B.ptr(dirs), N, degree, B.ptr(out), B.stream())
-        ctx.degree = degree
+                entry, elem = _entry("nfa_sh_fwd", dtype)
+                B.call(entry, *elem, B.ptr(dirs), N, degree, B.ptr(out), B.stream())
+        ctx.degree, ctx.dtype = degree, dtype
         ctx.save_for_backward(dirs)
         return out
 
@@ -152,14 +194,15 @@ class _SHFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g_out):
         if g_out is None or not ctx.needs_input_grad[0]:
-            return None, None
+            return None, None, None
         (dirs,) = ctx.saved_tensors
-        g = _aligned16(g_out.to(torch.float32))
+        g = _grad_as(g_out, ctx.dtype)
         g_d = torch.empty_like(dirs)
         if dirs.shape[0]:
             with torch.cuda.device(dirs.device):
-                B.call("nfa_sh_bwd", B.ptr(dirs), B.ptr(g), dirs.shape[0], ctx.degree, B.ptr(g_d), B.stream())
-        return g_d, None
+                entry, elem = _entry("nfa_sh_bwd", ctx.dtype)
+                B.call(entry, *elem, B.ptr(dirs), B.ptr(g), dirs.shape[0], ctx.degree, B.ptr(g_d), B.stream())
+        return g_d, None, None
 
 
 def _autocast_off(x: Tensor):
@@ -179,11 +222,16 @@ class HashGridEncoding(nn.Module):
     uniform in +-1e-4.  ``scales``, ``resolutions``, ``offsets`` and ``sizes`` are the per-level constants
     (:class:`LevelTable`).  Inputs outside [0, 1] are legal (every index wraps into its level); results for non-finite
     inputs are unspecified.  Differentiable w.r.t. ``params`` and ``x``.
+
+    ``out_dtype``: ``None`` (float32 output, also under autocast), ``torch.float16`` / ``torch.bfloat16`` (the float32
+    result rounded once to nearest even, written by the kernel itself; the gradient arrives and is read in that dtype),
+    or ``"autocast"`` (the active autocast dtype of the input's device when that is fp16 or bf16, else float32).
     """
 
     def __init__(self, n_input_dims: int = 3, n_levels: int = 16, n_features_per_level: int = 2,
-                 log2_hashmap_size: int = 19, base_resolution: float = 16, per_level_scale: float = 2.0):
+                 log2_hashmap_size: int = 19, base_resolution: float = 16, per_level_scale: float = 2.0, out_dtype=None):
         super().__init__()
+        self.out_dtype = _check_out_dtype(out_dtype)
         if n_input_dims != 3:
             raise ValueError(f"HashGridEncoding: only 3 input dimensions are supported (got {n_input_dims})")
         if n_features_per_level not in (1, 2, 4, 8):
@@ -212,22 +260,25 @@ class HashGridEncoding(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:
         assert x.shape[-1] == 3, "HashGridEncoding: x must have shape (..., 3)"
+        out = _resolve_out_dtype(self.out_dtype, x)
         x, ctx = _autocast_off(x)
         with ctx:
             lead = x.shape[:-1]
             x2 = x.reshape(-1, 3)
             p = self.params
             if x2.is_cuda and x2.dtype == torch.float32 and p.dtype == torch.float32 and p.device == x2.device:
-                y = _HashGridFn.apply(x2.contiguous(), p, self)
+                y = _HashGridFn.apply(x2.contiguous(), p, self, out)
             else:
                 dt = torch.promote_types(x2.dtype, p.dtype)
                 y = _hashgrid_torch(x2.to(dt), p.to(dt), self.table, self.n_features_per_level)
+                if self.out_dtype is not None:
+                    y = y.to(out)
             return y.view(*lead, self.n_output_dims)
 
     def extra_repr(self) -> str:
         return (f"n_levels={self.n_levels}, n_features_per_level={self.n_features_per_level}, "
                 f"log2_hashmap_size={self.log2_hashmap_size}, base_resolution={self.base_resolution}, "
-                f"per_level_scale={self.per_level_scale}")
+                f"per_level_scale={self.per_level_scale}" + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else ""))
 
 
 # Instant-NGP's real spherical-harmonics basis (tcnn's constants)
@@ -255,10 +306,12 @@ def _sh_torch(d: Tensor, degree: int) -> Tensor:
 
 class SphericalHarmonicsEncoding(nn.Module):
     """tiny-cuda-nn's ``SphericalHarmonics`` encoding: directions in [0, 1]^3 (``u = 2 d - 1``, not renormalised), ``degree``
-    1..4, ``forward(d[..., 3]) -> [..., degree^2]``.  Differentiable w.r.t. the directions."""
+    1..4, ``forward(d[..., 3]) -> [..., degree^2]``.  Differentiable w.r.t. the directions.  ``out_dtype`` as for
+    :class:`HashGridEncoding`."""
 
-    def __init__(self, n_input_dims: int = 3, degree: int = 4):
+    def __init__(self, n_input_dims: int = 3, degree: int = 4, out_dtype=None):
         super().__init__()
+        self.out_dtype = _check_out_dtype(out_dtype)
         if n_input_dims != 3:
             raise ValueError(f"SphericalHarmonicsEncoding: only 3 input dimensions are supported (got {n_input_dims})")
         if not 1 <= degree <= 4:
@@ -268,24 +321,27 @@ class SphericalHarmonicsEncoding(nn.Module):
 
     def forward(self, d: Tensor) -> Tensor:
         assert d.shape[-1] == 3, "SphericalHarmonicsEncoding: directions must have shape (..., 3)"
+        out = _resolve_out_dtype(self.out_dtype, d)
         d, ctx = _autocast_off(d)
         with ctx:
             lead = d.shape[:-1]
             d2 = d.reshape(-1, 3)
             if d2.is_cuda and d2.dtype == torch.float32:
-                y = _SHFn.apply(d2.contiguous(), self.degree)
+                y = _SHFn.apply(d2.contiguous(), self.degree, out)
             else:
                 y = _sh_torch(d2, self.degree)
+                if self.out_dtype is not None:
+                    y = y.to(out)
             return y.view(*lead, self.n_output_dims)
 
     def extra_repr(self) -> str:
-        return f"degree={self.degree}"
+        return f"degree={self.degree}" + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else "")
 
 
-def encoding_from_tcnn_config(n_input_dims: int, config: dict) -> nn.Module:
+def encoding_from_tcnn_config(n_input_dims: int, config: dict, out_dtype=None) -> nn.Module:
     """The encoding a tiny-cuda-nn encoding config describes: ``HashGrid`` (linear interpolation), ``SphericalHarmonics``,
     or ``Composite`` with ONE nested encoding over all input dimensions (as ``ngp.py`` builds its direction encoding).
-    Anything else raises ``ValueError``."""
+    Anything else raises ``ValueError``.  ``out_dtype`` is handed to the encoding built."""
     if not isinstance(config, dict) or "otype" not in config:
         raise ValueError(f"not a tcnn encoding config: {config!r}")
     otype = config["otype"]
@@ -297,9 +353,9 @@ def encoding_from_tcnn_config(n_input_dims: int, config: dict) -> nn.Module:
                                 n_features_per_level=int(config.get("n_features_per_level", 2)),
                                 log2_hashmap_size=int(config.get("log2_hashmap_size", 19)),
                                 base_resolution=config.get("base_resolution", 16),
-                                per_level_scale=float(config.get("per_level_scale", 2.0)))
+                                per_level_scale=float(config.get("per_level_scale", 2.0)), out_dtype=out_dtype)
     if otype == "SphericalHarmonics":
-        return SphericalHarmonicsEncoding(n_input_dims, degree=int(config.get("degree", 4)))
+        return SphericalHarmonicsEncoding(n_input_dims, degree=int(config.get("degree", 4)), out_dtype=out_dtype)
     if otype == "Composite":
         nested = config.get("nested", [])
         if len(nested) != 1:
@@ -308,5 +364,5 @@ def encoding_from_tcnn_config(n_input_dims: int, config: dict) -> nn.Module:
         dims = inner.pop("n_dims_to_encode", n_input_dims)
         if dims != n_input_dims:
             raise ValueError(f"Composite: the nested encoding must cover all {n_input_dims} dimensions (got {dims})")
-        return encoding_from_tcnn_config(n_input_dims, inner)
+        return encoding_from_tcnn_config(n_input_dims, inner, out_dtype)
     raise ValueError(f"unsupported tcnn encoding {otype!r} (supported: HashGrid, SphericalHarmonics, Composite)")

@@ -65,18 +65,33 @@ def activate_rgb(raw_rgbs: Tensor, activation: str) -> Tensor:
     return torch.sigmoid(raw_rgbs) if activation == "sigmoid" else raw_rgbs
 
 
+_HALF = (torch.float16, torch.bfloat16)
+
+
+def _raw_entry(name: str, dtype: torch.dtype):
+    """(entry point, leading arguments) for raw streams of ``dtype``: float32 calls the unsuffixed entry as ever, fp16 and
+    bf16 the ``_t`` one with its element-type code."""
+    return (name, ()) if dtype == torch.float32 else (name + "_t", (B.ELEM_CODES[dtype],))
+
+
 class _RenderRaw(torch.autograd.Function):
-    """One forward and one backward pass over the samples; saves the inputs and ``trans`` only."""
+    """One forward and one backward pass over the samples; saves the inputs and ``trans`` only.  ``raw_sigmas`` and
+    ``raw_rgbs`` share one dtype, float32, fp16 or bf16: the activated values and both gradients are written in it,
+    everything else is float32."""
 
     @staticmethod
     def forward(ctx, t_starts, t_ends, raw_sigmas, raw_rgbs, selector, seg: SegInfo, dens: int, bias: float, col: int,
                 return_activated: bool):
         ctx.set_materialize_grads(False)  # unused outputs arrive as None, not as zero tensors
-        ts, te, sg, c = _f32c(t_starts), _f32c(t_ends), _f32c(raw_sigmas), _f32c(raw_rgbs)
+        ts, te = _f32c(t_starts), _f32c(t_ends)
+        if raw_sigmas.dtype in _HALF and raw_rgbs.dtype == raw_sigmas.dtype:
+            sg, c = raw_sigmas.contiguous(), raw_rgbs.contiguous()
+        else:
+            sg, c = _f32c(raw_sigmas), _f32c(raw_rgbs)
         sel = None if selector is None else selector.contiguous()
         dev = B.require_device(ts, te, sg, c, sel)
         R, n = seg.n_rays, sg.numel()
-        weights, trans, alphas = torch.empty_like(sg), torch.empty_like(sg), torch.empty_like(sg)
+        weights, trans, alphas = torch.empty_like(ts), torch.empty_like(ts), torch.empty_like(ts)
         a_sig = torch.empty_like(sg) if return_activated else None
         a_rgb = torch.empty_like(c) if return_activated else None
         colors = torch.empty((R, 3), dtype=torch.float32, device=dev)
@@ -84,7 +99,8 @@ class _RenderRaw(torch.autograd.Function):
         depth = torch.empty((R, 1), dtype=torch.float32, device=dev)
         if R:
             with torch.cuda.device(dev):
-                B.call("nfa_render_raw_fwd", B.ptr(ts), B.ptr(te), B.ptr(sg), B.ptr(c), B.ptr(sel), dens, bias, col,
+                entry, elem = _raw_entry("nfa_render_raw_fwd", sg.dtype)
+                B.call(entry, *elem, B.ptr(ts), B.ptr(te), B.ptr(sg), B.ptr(c), B.ptr(sel), dens, bias, col,
                        B.ptr(seg.packed_info), B.ptr(seg.tiles), seg.n_tiles, R, n, B.ptr(weights), B.ptr(trans),
                        B.ptr(alphas), B.ptr(a_sig), B.ptr(a_rgb), B.ptr(colors), B.ptr(opac), B.ptr(depth), B.stream())
         ctx.seg, ctx.act, ctx.has_sel = seg, (dens, bias, col), sel is not None
@@ -109,7 +125,8 @@ class _RenderRaw(torch.autograd.Function):
         g_rgb = torch.empty_like(c) if need_c else None
         if trans.numel() and (need_sg or need_c):
             with torch.cuda.device(trans.device):
-                B.call("nfa_render_raw_bwd", B.ptr(ts), B.ptr(te), B.ptr(sg), B.ptr(c), B.ptr(sel), dens, bias, col,
+                entry, elem = _raw_entry("nfa_render_raw_bwd", sg.dtype)
+                B.call(entry, *elem, B.ptr(ts), B.ptr(te), B.ptr(sg), B.ptr(c), B.ptr(sel), dens, bias, col,
                        B.ptr(trans), B.ptr(_f32c(g_c)), B.ptr(_f32c(g_o)), B.ptr(_f32c(g_d)), B.ptr(_f32c(g_w)),
                        B.ptr(_f32c(g_t)), B.ptr(_f32c(g_a)), B.ptr(seg.packed_info), B.ptr(seg.tiles), seg.n_tiles,
                        seg.n_rays, trans.numel(), B.ptr(g_sig), B.ptr(g_rgb), B.stream())
@@ -147,9 +164,13 @@ def rendering_from_raw(
     or ``density_bias`` (the contract of ``rendering``).
 
     CUDA float32 inputs with ray-sorted ``ray_indices`` take one native pass each way (there the activated values, when
-    asked for, carry no gradient).  Everything else takes the same activations in torch, followed by ``rendering``
-    (CUDA float32: unsorted indices, ``t_starts`` / ``t_ends`` that require a gradient) or, where ``rendering`` has no
-    packed ops (CPU tensors, other dtypes), by its formulas in plain torch.
+    asked for, carry no gradient).  So do ``raw_rgbs`` and ``raw_sigmas`` that are both fp16 or both bf16 (a field run
+    under ``torch.autocast``) next to float32 ``t_starts`` / ``t_ends``: the passes load the halves directly and compute
+    in float32; ``colors``, ``opacities``, ``depths``, ``weights``, ``trans`` and ``alphas`` are float32, the activated
+    values and the gradients are in the raw dtype (each the float32 result rounded once).  Everything else takes the
+    same activations in torch, followed by ``rendering`` (CUDA float32: unsorted indices, ``t_starts`` / ``t_ends`` that
+    require a gradient) or, where ``rendering`` has no packed ops (CPU tensors, other dtypes, one half and one float32
+    raw input, half ``t_starts`` / ``t_ends``), by its formulas in plain torch.
     """
     if density_activation not in DENSITY_ACTIVATIONS:
         raise ValueError(f"density_activation must be one of {sorted(DENSITY_ACTIVATIONS)}, got {density_activation!r}")
@@ -167,7 +188,10 @@ def rendering_from_raw(
     density_bias = float(density_bias)
 
     all_f32_cuda = all(t.is_cuda and t.dtype == torch.float32 for t in (t_starts, t_ends, raw_sigmas, raw_rgbs))
-    native = all_f32_cuda and not ((t_starts.requires_grad or t_ends.requires_grad) and torch.is_grad_enabled())
+    half_raw = (all(t.is_cuda and t.dtype == torch.float32 for t in (t_starts, t_ends)) and raw_sigmas.is_cuda
+                and raw_rgbs.is_cuda and raw_sigmas.dtype in _HALF and raw_rgbs.dtype == raw_sigmas.dtype
+                and t_starts.device == t_ends.device == raw_sigmas.device == raw_rgbs.device)
+    native = (all_f32_cuda or half_raw) and not ((t_starts.requires_grad or t_ends.requires_grad) and torch.is_grad_enabled())
     if native:
         seg = seginfo_from_ray_indices(ray_indices, n_rays)
         native = seg.contiguous and seg.sorted_indices
@@ -178,7 +202,7 @@ def rendering_from_raw(
         extras = {"weights": weights, "alphas": alphas, "trans": trans}
         if return_activated:
             extras.update(sigmas=a_sig, rgbs=a_rgb)
-        return _finish_rendering(colors, opacities, depths, extras, raw_rgbs, render_bkgd)
+        return _finish_rendering(colors, opacities, depths, extras, colors, render_bkgd)   # (float32's eps)
 
     sigmas = activate_density(raw_sigmas, density_activation, density_bias, selector)
     rgbs = activate_rgb(raw_rgbs, rgb_activation)

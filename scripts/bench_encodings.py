@@ -7,7 +7,12 @@ two point sets: uniform in [0, 1]^3, and the midpoints of OccGridEstimator.sampl
 rays, 128^3 shell grid), in the order a training step presents them (ray by ray, along each ray).
 Algorithmic bytes: forward reads x (12 B) and 8 corners x F x 4 B per (point, level), writes L F 4 B per point; backward
 reads x and dL/dy (12 + L F 4 B per point) and adds 8 x F x 4 B per (point, level) to the table gradient (the atomic
-bytes); dL/dx adds the 8 corner reads again and writes 12 B per point.  Zeroing the gradient is timed on its own."""
+bytes); dL/dx adds the 8 corner reads again and writes 12 B per point.  Zeroing the gradient is timed on its own.
+    python scripts/bench_encodings.py --dtype bfloat16 [--sizes 20,22] [--reps 20] [--windows 7]
+times the half-precision output instead (out_dtype, the `_t` entries): forward and forward + backward of the grid with a
+half output and a half incoming gradient, against what the same user code runs without out_dtype -- the float32 op
+followed by `.to(dtype)`, whose backward widens the gradient again.  The two alternate, window by window, in one process;
+each figure is the median over the windows."""
 import argparse
 import json
 import math
@@ -35,6 +40,48 @@ def timed(fn, reps):
     return t0.elapsed_time(t1) * 1e3 / reps   # us
 
 
+def alternating_medians(fns, reps, windows):
+    """{name: median us} of `windows` timed windows per function, the functions taking turns."""
+    times = {k: [] for k in fns}
+    for _ in range(windows):
+        for k, fn in fns.items():
+            times[k].append(timed(fn, reps))
+    return {k: float(np.median(v)) for k, v in times.items()}
+
+
+def half_rows(args, dev, dtype):
+    sizes = [1 << int(s) for s in args.sizes.split(",")]
+    torch.manual_seed(0)
+    uni = torch.rand(max(sizes), 3, device=dev)
+    for cname, cfg in CONFIGS.items():
+        torch.manual_seed(0)
+        enc = HashGridEncoding(3, **cfg).to(dev)
+        half = HashGridEncoding(3, out_dtype=dtype, **cfg)
+        half.params = enc.params
+        L, F = enc.n_levels, enc.n_features_per_level
+        for N in sizes:
+            x = uni[:N].clone()
+            g = torch.randn(N, L * F, device=dev).to(dtype)
+            assert torch.equal(half(x), enc(x).to(dtype))
+
+            def step(fn):
+                enc.params.grad = None
+                fn(x).backward(g)
+
+            def fwd(fn):
+                with torch.no_grad():
+                    fn(x)
+
+            native, cast = half, (lambda t: enc(t).to(dtype))
+            m = alternating_medians({"half_fwd_us": lambda: fwd(native), "f32_cast_fwd_us": lambda: fwd(cast),
+                                     "half_fwd_bwd_us": lambda: step(native), "f32_cast_fwd_bwd_us": lambda: step(cast)},
+                                    args.reps, args.windows)
+            row = dict(config=cname, dtype=str(dtype), N=N, L=L, F=F, **m)
+            row["speedup_fwd"] = m["f32_cast_fwd_us"] / m["half_fwd_us"]
+            row["speedup_fwd_bwd"] = m["f32_cast_fwd_bwd_us"] / m["half_fwd_bwd_us"]
+            print(json.dumps(row), flush=True)
+
+
 def occgrid_midpoints(dev, n):
     import bench
     w = bench.make_workload(dev)
@@ -58,9 +105,13 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--sizes", default="18,20")
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--dtype", default="float32", choices=["float32", "float16", "bfloat16"])
+    ap.add_argument("--windows", type=int, default=7)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     B.load()
+    if args.dtype != "float32":
+        return half_rows(args, dev, getattr(torch, args.dtype))
     sizes = [1 << int(s) for s in args.sizes.split(",")]
     real, n_samples = occgrid_midpoints(dev, max(sizes))
     assert real.shape[0] >= max(sizes), (real.shape, n_samples)

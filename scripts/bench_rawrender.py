@@ -10,7 +10,11 @@ grad) and forward + backward towards the raw outputs with fixed upstream gradien
 of the two native passes.
 Algorithmic bytes per sample: raw forward 12 (t_starts, t_ends, raw_sigma) + 12 (raw_rgb) + 1 (selector) + 12 (weights,
 trans, alphas) = 37; raw backward 16 (t_starts, t_ends, raw_sigma, trans) + 12 (raw_rgb) + 1 + 16 (gradients) = 45;
-render_fused forward 36, backward 44.  Per-ray arrays and packed_info are not counted."""
+render_fused forward 36, backward 44.  Per-ray arrays and packed_info are not counted.
+    python scripts/bench_rawrender.py --dtype bfloat16 [--sizes 1048576,4194304] [--reps 20] [--windows 7]
+times fp16 / bf16 raw inputs instead (nfa_render_raw_{fwd,bwd}_t: 29 B per sample each way) against what the same user
+code runs without them -- `.float()` on both raw tensors, the float32 passes, and the cast's backward -- the two
+alternating window by window in one process; each figure is the median over the windows."""
 import argparse
 import json
 import os
@@ -40,6 +44,42 @@ def timed(fn, reps):
     return t0.elapsed_time(t1) / reps   # ms
 
 
+def half_rows(args, dev, dtype):
+    import statistics
+    for n in [int(s) for s in args.sizes.split(",")]:
+        ts, te, raw_sig, raw_rgb, sel, ri, R = make_inputs(n, dev)
+        seginfo_from_ray_indices(ri, R)
+        rs, rc = raw_sig.to(dtype).requires_grad_(True), raw_rgb.to(dtype).requires_grad_(True)
+        gout = [torch.randn(R, 3, device=dev), torch.randn(R, 1, device=dev), torch.randn(R, 1, device=dev)]
+
+        def half(a, b):
+            return rendering_from_raw(ts, te, b, a, ri, R, density_activation="trunc_exp", density_bias=-1.0,
+                                      rgb_activation="sigmoid", selector=sel)[:3]
+
+        def widened(a, b):
+            return half(a.float(), b.float())
+
+        def fwd(fn):
+            with torch.no_grad():
+                return fn(rs, rc)
+
+        def both(fn):
+            return torch.autograd.grad(fn(rs, rc), [rs, rc], gout)
+
+        assert all(torch.equal(u, v) for u, v in zip(fwd(half), fwd(widened)))
+        assert all(torch.equal(u, v) for u, v in zip(both(half), both(widened)))
+        fns = {"half_fwd_ms": lambda: fwd(half), "f32_cast_fwd_ms": lambda: fwd(widened),
+               "half_fwd_bwd_ms": lambda: both(half), "f32_cast_fwd_bwd_ms": lambda: both(widened)}
+        times = {k: [] for k in fns}
+        for _ in range(args.windows):
+            for k, fn in fns.items():
+                times[k].append(timed(fn, args.reps))
+        row = dict(n=n, n_rays=R, dtype=str(dtype), **{k: statistics.median(v) for k, v in times.items()})
+        row["speedup_fwd"] = row["f32_cast_fwd_ms"] / row["half_fwd_ms"]
+        row["speedup_fwd_bwd"] = row["f32_cast_fwd_bwd_ms"] / row["half_fwd_bwd_ms"]
+        print(json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in row.items()}), flush=True)
+
+
 def make_inputs(n, dev):
     g = torch.Generator(device=dev).manual_seed(0)
     n_rays = max(1, round(n / 30.8))
@@ -63,11 +103,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--sizes", default="32200000,1000000")
+    ap.add_argument("--dtype", default="float32", choices=["float32", "float16", "bfloat16"])
+    ap.add_argument("--windows", type=int, default=7)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_rawrender.py needs a ROCm device: nothing is measured without one")
     dev = torch.device("cuda:0")
     B.load()
+    if args.dtype != "float32":
+        return half_rows(args, dev, getattr(torch, args.dtype))
     for n in [int(s) for s in args.sizes.split(",")]:
         ts, te, raw_sig, raw_rgb, sel, ri, R = make_inputs(n, dev)
         seginfo_from_ray_indices(ri, R)   # what sampling() attaches to the indices it returns
