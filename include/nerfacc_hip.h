@@ -636,6 +636,16 @@ int nfa_hashgrid_bwd(const float *x, const float *params, const float *grad_y, i
                      int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
                      const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
                      float *grad_x, nfa_stream_t stream);
+/* Second order: the backward of nfa_hashgrid_bwd's grad_x output (the formulas are in csrc/encoding.hip's header, "Second
+ * order").  grad_grad_x [n_points, 3] (required) is the gradient that arrives for grad_x.  Outputs, each optional, at least
+ * one: grad_grad_y [n_points, n_levels * n_features] (towards grad_y; needs params) is written; grad_params (towards params;
+ * ZEROED by the caller, needs grad_y) receives float atomic adds like nfa_hashgrid_bwd's; grad_x [n_points, 3] (towards x:
+ * the mixed second partials; needs params and grad_y) is written, summed over levels in level order.  grad_grad_y and
+ * grad_x are bitwise reproducible.  The derivative of nfa_hashgrid_bwd's grad_params output is not provided. */
+int nfa_hashgrid_bwd_bwd(const float *x, const float *params, const float *grad_y, const float *grad_grad_x, int64_t n_points,
+                         int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                         const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_grad_y,
+                         float *grad_params, float *grad_x, nfa_stream_t stream);
 /* tiny-cuda-nn's `SphericalHarmonics` encoding: directions dirs [n_points, 3] in [0, 1]^3, u = 2 dirs - 1 (not
  * renormalised), degree 1..4, out [n_points, degree^2] (16-byte aligned) with Instant-NGP's real SH basis and constants.
  * The backward writes grad_dirs [n_points, 3] from grad_out [n_points, degree^2] (16-byte aligned). */
@@ -654,6 +664,11 @@ int nfa_hashgrid_bwd_t(int32_t elem, const float *x, const float *params, const 
                        int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
                        const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
                        float *grad_x, nfa_stream_t stream);
+/* nfa_hashgrid_bwd_bwd with grad_y and grad_grad_y as elements of type `elem` (half: both 16-byte aligned). */
+int nfa_hashgrid_bwd_bwd_t(int32_t elem, const float *x, const float *params, const void *grad_y, const float *grad_grad_x,
+                           int64_t n_points, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
+                           const float *scales_host, const int32_t *resolutions_host, const int32_t *sizes_host,
+                           int64_t n_params, void *grad_grad_y, float *grad_params, float *grad_x, nfa_stream_t stream);
 int nfa_sh_fwd_t(int32_t elem, const float *dirs, int64_t n_points, int32_t degree, void *out, nfa_stream_t stream);
 int nfa_sh_bwd_t(int32_t elem, const float *dirs, const void *grad_out, int64_t n_points, int32_t degree,
                  float *grad_dirs, nfa_stream_t stream);

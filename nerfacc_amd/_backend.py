@@ -121,6 +121,8 @@ _SIGS = {
     "nfa_sh_bwd": [_vp, _vp, _i64, _i32, _vp, _vp],
     "nfa_hashgrid_fwd_t": [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
     "nfa_hashgrid_bwd_t": [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "nfa_hashgrid_bwd_bwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "nfa_hashgrid_bwd_bwd_t": [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "nfa_sh_fwd_t": [_i32, _vp, _i64, _i32, _vp, _vp],
     "nfa_sh_bwd_t": [_i32, _vp, _vp, _i64, _i32, _vp, _vp],
     "nfa_sample_positions_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],

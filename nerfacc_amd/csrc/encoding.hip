@@ -21,6 +21,19 @@
 // (optional) is formed per (point, level) and summed over the point's levels in level order across lanes, so it is
 // bitwise reproducible.
 //
+// Second order (hashgrid_bwd_bwd_kernel): the derivative of the backward's dL/dx output.  With g the point's dL/dy piece of the
+// level, v = gg_x[n] the gradient that arrives for dL/dx[n], s = scale_l, w_d = (c_d ? f_d : 1 - f_d), u_d = (c_d ? v_d : -v_d)
+// and T_c the corner's F parameters, per corner in the order 0..7:
+//   a_c = ((u_0 * (w_1 * w_2) + u_1 * (w_0 * w_2)) + u_2 * (w_0 * w_1)) * s
+//   gg_y[n, l F + j] = sum_c a_c * T_c[j], summed from 0 in corner order           (towards dL/dy; element type of dL/dy)
+//   G2_T[idx_c][j]  += a_c * g[j]                                                   (towards params; float atomics as above)
+//   dot_c = sum_j g[j] * T_c[j] from 0 in feature order;
+//   h_0 = (u_1 * w_2 + u_2 * w_1) * dot_c, h_1 = (u_0 * w_2 + u_2 * w_0) * dot_c, h_2 = (u_0 * w_1 + u_1 * w_0) * dot_c
+//   x2_l[e] = ((sum_c (c_e ? + : -) h_e) * s) * s;  x2[n, e] = sum_l x2_l[e] in level order across lanes (towards x)
+// x2 has mixed partials only (linear interpolation has no pure second derivative); floor() contributes no gradient and the
+// cell is the one locate() gives.  Same lane layout as the backward; each output is optional, and the corner parameters are
+// read only for gg_y and x2.
+//
 // Element types: y / dL/dy (and the spherical harmonics' out / dL/dout) are float, fp16 or bf16 (NFA_ELEM_*, common.hip.h).
 // The arithmetic is the float32 one whatever the type; a point's F values of a level are converted once and moved as one
 // vector of 2 F bytes.  The forward keeps its layout for half outputs: with F = 2 a wave writes 4-byte pieces at a 64-byte
@@ -235,6 +248,99 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restri
                 g_x[n * 3 + 0] = s[0];
                 g_x[n * 3 + 1] = s[1];
                 g_x[n * 3 + 2] = s[2];
+            }
+        }
+    }
+}
+
+// Second order: the derivative of the backward's dL/dx output, given its incoming gradient v = gg_x[n] (header: "Second
+// order").  Shape of hashgrid_bwd_kernel; every output is optional, and the corners are read only for gg_y and x2.
+template <int F, class E>
+__global__ __launch_bounds__(256) void hashgrid_bwd_bwd_kernel(const float *__restrict__ x, const float *__restrict__ params,
+                                                               const E *__restrict__ g_y, const float *__restrict__ gg_x,
+                                                               int64_t n_points, const HashGridLevels T,
+                                                               E *__restrict__ gg_y, float *__restrict__ g_params,
+                                                               float *__restrict__ g_x)
+{
+    const int64_t n_waves = ceil_div64(n_points, T.pts_per_wave);
+    const int64_t wave_stride = (int64_t)gridDim.x * (blockDim.x / 64);
+    for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / 64; w < n_waves; w += wave_stride) {
+        int64_t n;
+        int l;
+        const bool active = lane_item(T, w, n_points, n, l);
+        float dx[3] = {0.0f, 0.0f, 0.0f};
+        if (active) {
+            const float s = T.scale[l];
+            const Cell c = locate(x + n * 3, s);
+            const bool hashed = (T.hashed >> l) & 1u;
+            const uint32_t res = T.res[l], size = T.size[l];
+            const float v0 = gg_x[n * 3 + 0], v1 = gg_x[n * 3 + 1], v2 = gg_x[n * 3 + 2];
+            FVec<F> g = {};
+            if (g_params || g_x) {
+                if constexpr (std::is_same<E, float>::value) g = reinterpret_cast<const FVec<F> *>(g_y)[n * T.n_levels + l];
+                else load_elems<F>(g_y + (n * T.n_levels + l) * F, g.v);
+            }
+            float acc[F];
+#pragma unroll
+            for (int j = 0; j < F; ++j) acc[j] = 0.0f;
+            const uint32_t base = T.offset[l];
+#pragma unroll
+            for (int corner = 0; corner < 8; ++corner) {
+                const uint32_t e = base + corner_index(c, corner, hashed, res, size);
+                const float w0 = corner_factor(c, corner, 0), w1 = corner_factor(c, corner, 1), w2 = corner_factor(c, corner, 2);
+                const float u0 = (corner & 1) ? v0 : -v0, u1 = (corner & 2) ? v1 : -v1, u2 = (corner & 4) ? v2 : -v2;
+                const float a = ((u0 * (w1 * w2) + u1 * (w0 * w2)) + u2 * (w0 * w1)) * s;
+                if (g_params) {
+                    float *dst = g_params + (size_t)e * F;
+#pragma unroll
+                    for (int j = 0; j < F; ++j) unsafeAtomicAdd(dst + j, a * g.v[j]);
+                }
+                if (gg_y || g_x) {
+                    const FVec<F> t = reinterpret_cast<const FVec<F> *>(params)[e];
+#pragma unroll
+                    for (int j = 0; j < F; ++j) acc[j] = acc[j] + a * t.v[j];
+                    if (g_x) {
+                        float dot = 0.0f;
+#pragma unroll
+                        for (int j = 0; j < F; ++j) dot = dot + g.v[j] * t.v[j];
+                        const float t0 = (u1 * w2 + u2 * w1) * dot, t1 = (u0 * w2 + u2 * w0) * dot, t2 = (u0 * w1 + u1 * w0) * dot;
+                        dx[0] = (corner & 1) ? dx[0] + t0 : dx[0] - t0;
+                        dx[1] = (corner & 2) ? dx[1] + t1 : dx[1] - t1;
+                        dx[2] = (corner & 4) ? dx[2] + t2 : dx[2] - t2;
+                    }
+                }
+            }
+            if (gg_y) {
+                if constexpr (std::is_same<E, float>::value) {
+                    FVec<F> out;
+#pragma unroll
+                    for (int j = 0; j < F; ++j) out.v[j] = acc[j];
+                    reinterpret_cast<FVec<F> *>(gg_y)[n * T.n_levels + l] = out;
+                } else {
+                    store_elems<F>(gg_y + (n * T.n_levels + l) * F, acc);
+                }
+            }
+            if (g_x) {
+                dx[0] = (dx[0] * s) * s; dx[1] = (dx[1] * s) * s; dx[2] = (dx[2] * s) * s;
+            }
+        }
+        if (g_x) {
+            // sum over the point's L lanes in level order; the level-0 lane writes (wave-uniform branch)
+            const int lane = (int)(threadIdx.x & 63);
+            const int first = lane - l;
+            float sum[3] = {0.0f, 0.0f, 0.0f};
+            for (int k = 0; k < T.n_levels; ++k) {
+                const int src = min(first + k, 63);
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    const float v = __shfl(dx[d], src, 64);
+                    sum[d] = k == 0 ? v : sum[d] + v;
+                }
+            }
+            if (active && l == 0) {
+                g_x[n * 3 + 0] = sum[0];
+                g_x[n * 3 + 1] = sum[1];
+                g_x[n * 3 + 2] = sum[2];
             }
         }
     }
@@ -497,6 +603,38 @@ static int hashgrid_bwd(const float *x, const float *params, const E *grad_y, in
 }
 
 template <class E>
+static int hashgrid_bwd_bwd(const float *x, const float *params, const E *grad_y, const float *grad_grad_x, int64_t n_points,
+                            int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                            const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, E *grad_grad_y,
+                            float *grad_params, float *grad_x, nfa_stream_t stream)
+{
+    HashGridLevels T;
+    const int rc = hashgrid_table("hashgrid_bwd_bwd", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                                  resolutions_host, sizes_host, n_params, T);
+    if (rc != NFA_OK) return rc;
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(grad_grad_x, "hashgrid_bwd_bwd: grad_grad_x is null");
+    NFA_REQUIRE(grad_grad_y || grad_params || grad_x, "hashgrid_bwd_bwd: no output requested");
+    NFA_REQUIRE(x && (grad_y || !(grad_params || grad_x)) && (params || !(grad_grad_y || grad_x)), "hashgrid_bwd_bwd: null pointer");
+    NFA_REQUIRE((std::is_same<E, float>::value) || (aligned16(grad_y) && aligned16(grad_grad_y)),
+                "hashgrid_bwd_bwd: half grad_y and grad_grad_y must be 16-byte aligned");
+    const dim3 grid(hashgrid_grid(n_points, T)), block(256);
+    hipStream_t s = as_stream(stream);
+    switch (n_features) {
+    case 1: hipLaunchKernelGGL((hashgrid_bwd_bwd_kernel<1, E>), grid, block, 0, s, x, params, grad_y, grad_grad_x, n_points, T,
+                               grad_grad_y, grad_params, grad_x); break;
+    case 2: hipLaunchKernelGGL((hashgrid_bwd_bwd_kernel<2, E>), grid, block, 0, s, x, params, grad_y, grad_grad_x, n_points, T,
+                               grad_grad_y, grad_params, grad_x); break;
+    case 4: hipLaunchKernelGGL((hashgrid_bwd_bwd_kernel<4, E>), grid, block, 0, s, x, params, grad_y, grad_grad_x, n_points, T,
+                               grad_grad_y, grad_params, grad_x); break;
+    default: hipLaunchKernelGGL((hashgrid_bwd_bwd_kernel<8, E>), grid, block, 0, s, x, params, grad_y, grad_grad_x, n_points, T,
+                               grad_grad_y, grad_params, grad_x); break;
+    }
+    NFA_CHECK_LAUNCH("hashgrid_bwd_bwd");
+    return NFA_OK;
+}
+
+template <class E>
 static int sh_fwd(const float *dirs, int64_t n_points, int32_t degree, E *out, nfa_stream_t stream)
 {
     NFA_REQUIRE(n_points >= 0, "sh_fwd: negative size");
@@ -580,6 +718,27 @@ int nfa_hashgrid_bwd(const float *x, const float *params, const float *grad_y, i
 {
     return nfa_hashgrid_bwd_t(NFA_ELEM_F32, x, params, grad_y, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
                               resolutions_host, sizes_host, n_params, grad_params, grad_x, stream);
+}
+
+int nfa_hashgrid_bwd_bwd_t(int32_t elem, const float *x, const float *params, const void *grad_y, const float *grad_grad_x,
+                           int64_t n_points, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
+                           const float *scales_host, const int32_t *resolutions_host, const int32_t *sizes_host,
+                           int64_t n_params, void *grad_grad_y, float *grad_params, float *grad_x, nfa_stream_t stream)
+{
+    ELEM_DISPATCH("hashgrid_bwd_bwd", elem, hashgrid_bwd_bwd(x, params, static_cast<const E *>(grad_y), grad_grad_x, n_points,
+                                                             n_levels, n_features, log2_hashmap_size, scales_host,
+                                                             resolutions_host, sizes_host, n_params,
+                                                             static_cast<E *>(grad_grad_y), grad_params, grad_x, stream));
+}
+
+int nfa_hashgrid_bwd_bwd(const float *x, const float *params, const float *grad_y, const float *grad_grad_x, int64_t n_points,
+                         int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                         const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_grad_y,
+                         float *grad_params, float *grad_x, nfa_stream_t stream)
+{
+    return nfa_hashgrid_bwd_bwd_t(NFA_ELEM_F32, x, params, grad_y, grad_grad_x, n_points, n_levels, n_features,
+                                  log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params, grad_grad_y,
+                                  grad_params, grad_x, stream);
 }
 
 int nfa_sh_fwd_t(int32_t elem, const float *dirs, int64_t n_points, int32_t degree, void *out, nfa_stream_t stream)

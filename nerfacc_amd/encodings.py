@@ -157,23 +157,56 @@ class _HashGridFn(torch.autograd.Function):
         return y
 
     @staticmethod
-    @once_differentiable
     def backward(ctx, g_y):
         need_x, need_p = ctx.needs_input_grad[:2]
         if g_y is None or not (need_x or need_p):
             return None, None, None, None
         x, params = ctx.saved_tensors
-        enc = ctx.enc
+        g_x, g_p = _HashGridBwdFn.apply(x, params, _grad_as(g_y, ctx.dtype), ctx.enc, ctx.dtype, need_x, need_p)
+        return g_x, g_p, None, None
+
+
+class _HashGridBwdFn(torch.autograd.Function):
+    """The hash grid's backward as a function ``(x, params, g_y) -> (g_x, g_params)``, so that ``g_x`` can be differentiated
+    again (``create_graph=True``: Eikonal terms, normals).  Its own backward is one ``nfa_hashgrid_bwd_bwd[_t]`` call."""
+
+    @staticmethod
+    def forward(ctx, x, params, g, enc: "HashGridEncoding", dtype: torch.dtype, need_x: bool, need_p: bool):
         t, L, F = enc.table, enc.n_levels, enc.n_features_per_level
-        g = _grad_as(g_y, ctx.dtype)
         g_p = torch.zeros_like(params) if need_p else None
         g_x = torch.empty_like(x) if need_x else None
         if x.shape[0]:
             with torch.cuda.device(x.device):
-                entry, elem = _entry("nfa_hashgrid_bwd", ctx.dtype)
+                entry, elem = _entry("nfa_hashgrid_bwd", dtype)
                 B.call(entry, *elem, B.ptr(x), B.ptr(params), B.ptr(g), x.shape[0], L, F, t.log2_hashmap_size,
                        t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(g_p), B.ptr(g_x), B.stream())
-        return g_x, g_p, None, None
+        ctx.enc, ctx.dtype = enc, dtype
+        ctx.save_for_backward(x, params, g)
+        ctx.set_materialize_grads(False)
+        return g_x, g_p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gg_x, gg_p):
+        if gg_p is not None:
+            raise NotImplementedError("HashGridEncoding: the derivative of the table gradient (dL/dparams) is not "
+                                      "implemented; only dL/dx can be differentiated again")
+        need_x, need_p, need_g = ctx.needs_input_grad[:3]
+        if gg_x is None or not (need_x or need_p or need_g):
+            return (None,) * 7
+        x, params, g = ctx.saved_tensors
+        enc = ctx.enc
+        t, L, F = enc.table, enc.n_levels, enc.n_features_per_level
+        v = gg_x.to(torch.float32).contiguous()
+        x2 = torch.empty_like(x) if need_x else None
+        g2_p = torch.zeros_like(params) if need_p else None
+        gg_y = torch.empty_like(g) if need_g else None
+        if x.shape[0]:
+            with torch.cuda.device(x.device):
+                entry, elem = _entry("nfa_hashgrid_bwd_bwd", ctx.dtype)
+                B.call(entry, *elem, B.ptr(x), B.ptr(params), B.ptr(g), B.ptr(v), x.shape[0], L, F, t.log2_hashmap_size,
+                       t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(gg_y), B.ptr(g2_p), B.ptr(x2), B.stream())
+        return x2, g2_p, gg_y, None, None, None, None
 
 
 class _SHFn(torch.autograd.Function):
@@ -221,7 +254,12 @@ class HashGridEncoding(nn.Module):
     ``params`` is one flat float32 table of ``sum(sizes) * F`` values laid out ``[level][entry][feature]``, initialised
     uniform in +-1e-4.  ``scales``, ``resolutions``, ``offsets`` and ``sizes`` are the per-level constants
     (:class:`LevelTable`).  Inputs outside [0, 1] are legal (every index wraps into its level); results for non-finite
-    inputs are unspecified.  Differentiable w.r.t. ``params`` and ``x``.
+    inputs are unspecified.  Differentiable w.r.t. ``params`` and ``x``, and twice where the first derivative taken is the
+    one w.r.t. ``x``: ``torch.autograd.grad(y, x, g, create_graph=True)`` gives a ``dL/dx`` that can be differentiated
+    w.r.t. ``params``, ``x`` and ``g`` (one native pass; what an Eikonal term, analytic normals or any regulariser of the
+    field's spatial gradient needs).  With linear interpolation the second derivative w.r.t. ``x`` has mixed partials only,
+    and ``floor`` contributes nothing.  Differentiating ``dL/dparams`` again raises ``NotImplementedError``; there is no
+    third order.
 
     ``out_dtype``: ``None`` (float32 output, also under autocast), ``torch.float16`` / ``torch.bfloat16`` (the float32
     result rounded once to nearest even, written by the kernel itself; the gradient arrives and is read in that dtype),

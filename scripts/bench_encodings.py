@@ -12,7 +12,13 @@ bytes); dL/dx adds the 8 corner reads again and writes 12 B per point.  Zeroing 
 times the half-precision output instead (out_dtype, the `_t` entries): forward and forward + backward of the grid with a
 half output and a half incoming gradient, against what the same user code runs without out_dtype -- the float32 op
 followed by `.to(dtype)`, whose backward widens the gradient again.  The two alternate, window by window, in one process;
-each figure is the median over the windows."""
+each figure is the median over the windows.
+    python scripts/bench_encodings.py --eikonal [--sizes 18] [--reps 10] [--windows 7]
+times an Eikonal-shaped step on uniform points: forward, `autograd.grad(y, x, g, create_graph=True)`, then the backward of a
+function of that dL/dx (sum of squares) towards the table -- natively (nfa_hashgrid_fwd, _bwd, _bwd_bwd) and through
+`_hashgrid_torch` on the same GPU, the only way to run such a step without the second-order pass.  The two alternate window by
+window; medians.  The native step is also split: the first-order part (forward + backward with create_graph) and the
+second-order pass alone (the step minus the first-order part)."""
 import argparse
 import json
 import math
@@ -82,6 +88,44 @@ def half_rows(args, dev, dtype):
             print(json.dumps(row), flush=True)
 
 
+def eikonal_rows(args, dev):
+    sizes = [1 << int(s) for s in args.sizes.split(",")]
+    torch.manual_seed(0)
+    uni = torch.rand(max(sizes), 3, device=dev)
+    for cname, cfg in CONFIGS.items():
+        torch.manual_seed(0)
+        enc = HashGridEncoding(3, **cfg).to(dev)
+        with torch.no_grad():
+            enc.params.uniform_(-1, 1)
+        L, F = enc.n_levels, enc.n_features_per_level
+        for N in sizes:
+            x = uni[:N].clone().requires_grad_(True)
+            g = torch.randn(N, L * F, device=dev)
+
+            def first(fn):
+                (g_x,) = torch.autograd.grad(fn(x), x, g, create_graph=True)
+                return g_x
+
+            def step(fn):
+                enc.params.grad = None
+                x.grad = None
+                (first(fn) ** 2).sum().backward()
+
+            native, torch_path = enc, (lambda t: _hashgrid_torch(t, enc.params, enc.table, F))
+            step(native)
+            gp, gx = enc.params.grad.clone(), x.grad.clone()
+            step(torch_path)
+            row = dict(config=cname, mode="eikonal", N=N, L=L, F=F,
+                       grad_params_max_abs_diff=float((enc.params.grad - gp).abs().max()), grad_params_max_abs=float(gp.abs().max()),
+                       grad_x_max_abs_diff=float((x.grad - gx).abs().max()), grad_x_max_abs=float(gx.abs().max()))
+            m = alternating_medians({"native_step_us": lambda: step(native), "torch_step_us": lambda: step(torch_path),
+                                     "native_first_order_us": lambda: first(native)}, args.reps, args.windows)
+            row.update(m)
+            row["native_second_order_us"] = m["native_step_us"] - m["native_first_order_us"]
+            row["speedup"] = m["torch_step_us"] / m["native_step_us"]
+            print(json.dumps(row), flush=True)
+
+
 def occgrid_midpoints(dev, n):
     import bench
     w = bench.make_workload(dev)
@@ -107,9 +151,12 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--dtype", default="float32", choices=["float32", "float16", "bfloat16"])
     ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--eikonal", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     B.load()
+    if args.eikonal:
+        return eikonal_rows(args, dev)
     if args.dtype != "float32":
         return half_rows(args, dev, getattr(torch, args.dtype))
     sizes = [1 << int(s) for s in args.sizes.split(",")]
