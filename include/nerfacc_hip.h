@@ -669,6 +669,32 @@ int nfa_hashgrid_bwd_bwd_t(int32_t elem, const float *x, const float *params, co
                            int64_t n_points, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
                            const float *scales_host, const int32_t *resolutions_host, const int32_t *sizes_host,
                            int64_t n_params, void *grad_grad_y, float *grad_params, float *grad_x, nfa_stream_t stream);
+/* The two hash-grid backward passes with a bitwise reproducible table gradient: arguments and results of
+ * nfa_hashgrid_bwd_t / nfa_hashgrid_bwd_bwd_t (elem: any NFA_ELEM_* code, NFA_ELEM_F32 included), except that grad_params
+ * (ZEROED by the caller) is formed without float atomics, in an order that depends on the arguments alone.  Per level:
+ *   items i = 8 n + c (point n, corner c) carry the corner's entry index as key and are sorted by key with a stable radix
+ *   sort, so equal keys stay in ascending point and then corner; the sorted array is cut into tiles of 256 items; the part
+ *   of a run of equal keys inside one tile (a segment) is summed from its first term, left to right; a run inside one tile
+ *   is its segment; a run across tile borders is the sum of its segments' sums in tile order, from the first one's.
+ *   Each term is the float32 value the atomic pass adds: ((w0 w1) w2) grad_y[j], at second order a_c grad_y[j].
+ * Entries that receive nothing are not written.  grad_x, grad_grad_y come from the passes above, unchanged.
+ * scratch (device memory, 16-byte aligned, contents irrelevant before and after) holds scratch_bytes >=
+ * nfa_hashgrid_sorted_scratch_bytes(n_points, n_levels, log2_hashmap_size) bytes:
+ *   M = 8 n_points, level_bytes = 16 M + 1024 (ceil(M / 4096) + 1) + 64 ceil(M / 256),
+ *   bytes = n_levels level_bytes where that is at most 2^29, else max(2^29, level_bytes); 0 for no points.  (The levels are
+ *   sorted min(n_levels, max(1, floor(2^29 / level_bytes))) at a time, one slab each.)
+ * 8 n_points must be below 2^32.  Without grad_params the calls are nfa_hashgrid_bwd_t / nfa_hashgrid_bwd_bwd_t and scratch
+ * is not looked at.  Nothing is read back from the device; the launches follow from the arguments alone. */
+int64_t nfa_hashgrid_sorted_scratch_bytes(int64_t n_points, int32_t n_levels, int32_t log2_hashmap_size);
+int nfa_hashgrid_bwd_sorted(int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points,
+                            int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                            const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
+                            float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream);
+int nfa_hashgrid_bwd_bwd_sorted(int32_t elem, const float *x, const float *params, const void *grad_y,
+                                const float *grad_grad_x, int64_t n_points, int32_t n_levels, int32_t n_features,
+                                int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                                const int32_t *sizes_host, int64_t n_params, void *grad_grad_y, float *grad_params,
+                                float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream);
 int nfa_sh_fwd_t(int32_t elem, const float *dirs, int64_t n_points, int32_t degree, void *out, nfa_stream_t stream);
 int nfa_sh_bwd_t(int32_t elem, const float *dirs, const void *grad_out, int64_t n_points, int32_t degree,
                  float *grad_dirs, nfa_stream_t stream);

@@ -20,6 +20,8 @@
 // The backward scatters w_c * dL/dy with no-return global_atomic_add_f32 into a zeroed float32 table gradient; dL/dx
 // (optional) is formed per (point, level) and summed over the point's levels in level order across lanes, so it is
 // bitwise reproducible.
+// The `_sorted` entries form the same table gradient (of both orders) without float atomics, by a stable sort of the (point,
+// corner) items by entry and a segmented sum in a fixed order: "reproducible table gradient" below.
 //
 // Second order (hashgrid_bwd_bwd_kernel): the derivative of the backward's dL/dx output.  With g the point's dL/dy piece of the
 // level, v = gg_x[n] the gradient that arrives for dL/dx[n], s = scale_l, w_d = (c_d ? f_d : 1 - f_d), u_d = (c_d ? v_d : -v_d)
@@ -674,6 +676,463 @@ static int sh_bwd(const float *dirs, const E *grad_out, int64_t n_points, int32_
     return NFA_OK;
 }
 
+// ---------------------------------------------------------------- reproducible table gradient: sort and segmented sum
+// nfa_hashgrid_bwd_sorted / nfa_hashgrid_bwd_bwd_sorted form the table gradient without float atomics.  THE ORDER OF THE SUM,
+// per level (tests/hashgrid_sorted_reference.py restates it):
+//   items   i = 8 n + c for point n and corner c, in that order; key_i = the corner's entry index inside the level (locate /
+//           corner_index as above); term_i[j] = coef_i * g[n][j] in float32, coef_i = (w_0 * w_1) * w_2 at first order and
+//           a_c (header, "Second order") at second order, g the point's dL/dy piece of the level converted once.
+//   sort    the items are sorted by key with a stable LSD radix sort (8-bit digits over the ceil(log2 size_l) significant bits):
+//           equal keys stay in ascending i, that is ascending point and then corner.
+//   tiles   the sorted array is cut into tiles of NFA_HS_TILE = 256 consecutive items.  A run of equal keys is cut into
+//           segments at the tile borders; a segment's sum starts from its first term and adds the following ones left to
+//           right, s = (..((t_0 + t_1) + t_2) + ..).
+//   carry   a run that lies inside one tile is its segment.  A run that crosses tile borders is the sum of its segments'
+//           sums in tile order, starting from the first segment's, P = (..((s_0 + s_1) + s_2) + ..).
+//   Every entry that received an item is written once with a plain store; the others are not touched (the caller zeroes).
+// Nothing here depends on arrival order: launch shapes follow from (n_points, n_levels, the level sizes) alone and nothing
+// is read back, so a step can be captured.
+//
+// Scratch: levels are processed in groups of G, one level per workgroup row, each with its own slab of
+//   level_bytes = 16 M + 1024 (B + 1) + 64 Tn,  M = 8 n_points, B = ceil(M / 4096), Tn = ceil(M / 256):
+//   two key and two id buffers of M uint32 (ping-pong), 256 B block counts + 256 digit totals, Tn x {head, tail} x 8 floats;
+//   G = min(n_levels, max(1, floor(2^29 / level_bytes))); scratch = n_levels level_bytes where that is at most 2^29, else
+//   max(2^29, level_bytes): at least G level_bytes, and monotone in n_points.
+// Radix pass p of a level (skipped by levels with fewer significant bits): hs_count (digit counts per block of 4096 items,
+// digit-major), hs_scan (exclusive prefix of each digit's row over the blocks, and the digit's total), hs_scatter (a wave
+// owns 1024 consecutive items, 64 at a time in lane order; equal digits are ranked by lane inside the wave, waves and blocks
+// in order: stable).  Pass 0 takes the id from the position.  The work of hs_sum is bounded by the tile: the 256 terms are
+// formed in parallel into LDS and the thread at each segment's first item adds at most 256 of them; hs_carry walks a crossing
+// run's segment sums, one thread per (run, feature).
+#define NFA_HS_TILE 256
+#define NFA_HS_BLOCK_ITEMS 4096
+#define NFA_HS_BUDGET ((int64_t)1 << 29)
+
+struct HashSortPlan {
+    int64_t items, n_blocks, n_tiles, level_bytes, scratch_bytes;
+    int32_t group;
+};
+
+static HashSortPlan hashsort_plan(int64_t n_points, int32_t n_levels)
+{
+    HashSortPlan p;
+    p.items = 8 * n_points;
+    p.n_blocks = ceil_div64(p.items, NFA_HS_BLOCK_ITEMS);
+    p.n_tiles = ceil_div64(p.items, NFA_HS_TILE);
+    p.level_bytes = 16 * p.items + 1024 * (p.n_blocks + 1) + 64 * p.n_tiles;
+    int64_t g = p.level_bytes > 0 ? NFA_HS_BUDGET / p.level_bytes : n_levels;
+    g = g < 1 ? 1 : (g > n_levels ? n_levels : g);
+    p.group = (int32_t)g;
+    p.scratch_bytes = n_levels * p.level_bytes <= NFA_HS_BUDGET ? n_levels * p.level_bytes
+                                                                : (p.level_bytes > NFA_HS_BUDGET ? p.level_bytes : NFA_HS_BUDGET);
+    return p;
+}
+
+struct HashSortArgs {
+    unsigned char *scratch;
+    int64_t level_bytes;
+    int64_t items;       // < 2^32
+    int64_t n_blocks;
+    int64_t n_tiles;
+    int64_t n_points;
+    int32_t first_level;   // the group's first level; blockIdx.y counts from it
+};
+
+struct HashSortView {
+    uint32_t *keys0, *keys1, *ids0, *ids1, *hist, *totals;
+    float *part;   // [n_tiles][2 (head, tail)][8]
+    // (selects, not arrays: a dynamically indexed member would be moved to LDS)
+    __device__ __forceinline__ uint32_t *keys(int which) const { return which ? keys1 : keys0; }
+    __device__ __forceinline__ uint32_t *ids(int which) const { return which ? ids1 : ids0; }
+};
+
+__device__ __forceinline__ HashSortView hs_view(const HashSortArgs &A, int slot)
+{
+    unsigned char *b = A.scratch + (int64_t)slot * A.level_bytes;
+    HashSortView v;
+    v.keys0 = reinterpret_cast<uint32_t *>(b);
+    v.keys1 = v.keys0 + A.items;
+    v.ids0 = v.keys1 + A.items;
+    v.ids1 = v.ids0 + A.items;
+    v.hist = v.ids1 + A.items;
+    v.totals = v.hist + 256 * A.n_blocks;
+    v.part = reinterpret_cast<float *>(v.totals + 256);
+    return v;
+}
+
+// radix passes of a level: 8-bit digits over the significant bits of its keys (size >= 8: at least one)
+__host__ __device__ static inline int hs_passes(uint32_t size)
+{
+    int bits = 1;
+    while (bits < 32 && (1u << bits) < size) ++bits;
+    return (bits + 7) / 8;
+}
+
+__device__ __forceinline__ uint32_t wave_incl_sum_u32(uint32_t v)
+{
+    const int lane = lane_id();
+#pragma unroll
+    for (int off = 1; off < NFA_WAVE; off <<= 1) {
+        const uint32_t u = __shfl_up(v, off, NFA_WAVE);
+        if (lane >= off) v += u;
+    }
+    return v;
+}
+
+// exclusive prefix of v over the 256 threads of a workgroup (ws: 4 words of LDS, used once)
+__device__ __forceinline__ uint32_t block_excl_sum_256(uint32_t v, uint32_t *ws, uint32_t &total)
+{
+    const int w = (int)(threadIdx.x >> 6);
+    const uint32_t incl = wave_incl_sum_u32(v);
+    if ((threadIdx.x & 63) == 63) ws[w] = incl;
+    __syncthreads();
+    uint32_t pre = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) pre += k < w ? ws[k] : 0u;
+    total = ws[0] + ws[1] + ws[2] + ws[3];
+    return pre + incl - v;
+}
+
+__global__ __launch_bounds__(256) void hs_keys_kernel(const float *__restrict__ x, const HashGridLevels T, const HashSortArgs A)
+{
+    const int l = A.first_level + (int)blockIdx.y;
+    const bool hashed = (T.hashed >> l) & 1u;
+    const uint32_t res = T.res[l], size = T.size[l];
+    const float scale = T.scale[l];
+    uint32_t *keys = hs_view(A, (int)blockIdx.y).keys0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.items; i += stride) {
+        const Cell c = locate(x + (i >> 3) * 3, scale);
+        keys[i] = corner_index(c, (int)(i & 7), hashed, res, size);
+    }
+}
+
+__global__ __launch_bounds__(256) void hs_count_kernel(const HashGridLevels T, const HashSortArgs A, int pass)
+{
+    __shared__ uint32_t h[256];
+    const int l = A.first_level + (int)blockIdx.y;
+    if (pass >= hs_passes(T.size[l])) return;
+    const HashSortView V = hs_view(A, (int)blockIdx.y);
+    const uint32_t *keys = V.keys(pass & 1);
+    const int shift = 8 * pass;
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * NFA_HS_BLOCK_ITEMS + threadIdx.x;
+    uint32_t key[NFA_HS_BLOCK_ITEMS / 256];   // the loads first, all in flight together
+#pragma unroll
+    for (int k = 0; k < NFA_HS_BLOCK_ITEMS / 256; ++k) key[k] = base + k * 256 < A.items ? keys[base + k * 256] : 0u;
+#pragma unroll
+    for (int k = 0; k < NFA_HS_BLOCK_ITEMS / 256; ++k)
+        if (base + k * 256 < A.items) atomicAdd(&h[(key[k] >> shift) & 255u], 1u);   // (integer counts: any order)
+    __syncthreads();
+    V.hist[(int64_t)threadIdx.x * A.n_blocks + blockIdx.x] = h[threadIdx.x];
+}
+
+// one workgroup per (digit, level): the digit's block counts -> their exclusive prefix over the blocks, and the total
+__global__ __launch_bounds__(256) void hs_scan_kernel(const HashGridLevels T, const HashSortArgs A, int pass)
+{
+    __shared__ uint32_t ws[4];
+    const int l = A.first_level + (int)blockIdx.y;
+    if (pass >= hs_passes(T.size[l])) return;
+    const HashSortView V = hs_view(A, (int)blockIdx.y);
+    uint32_t *row = V.hist + (int64_t)blockIdx.x * A.n_blocks;
+    const int64_t per = ceil_div64(A.n_blocks, 256);
+    const int64_t lo = (int64_t)threadIdx.x * per < A.n_blocks ? (int64_t)threadIdx.x * per : A.n_blocks;
+    const int64_t hi = lo + per < A.n_blocks ? lo + per : A.n_blocks;
+    uint32_t sum = 0;
+    for (int64_t j = lo; j < hi; ++j) sum += row[j];
+    uint32_t total;
+    uint32_t run = block_excl_sum_256(sum, ws, total);
+    for (int64_t j = lo; j < hi; ++j) {
+        const uint32_t v = row[j];
+        row[j] = run;
+        run += v;
+    }
+    if (threadIdx.x == 0) V.totals[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void hs_scatter_kernel(const HashGridLevels T, const HashSortArgs A, int pass)
+{
+    __shared__ uint32_t woff[4][256];   // per wave and digit: the count, then the next output position
+    __shared__ uint32_t ws[4];
+    const int l = A.first_level + (int)blockIdx.y;
+    if (pass >= hs_passes(T.size[l])) return;
+    const HashSortView V = hs_view(A, (int)blockIdx.y);
+    const uint32_t *kin = V.keys(pass & 1), *iin = pass ? V.ids(pass & 1) : nullptr;
+    uint32_t *kout = V.keys((pass + 1) & 1), *iout = V.ids((pass + 1) & 1);
+    const int shift = 8 * pass;
+    const int tid = (int)threadIdx.x, w = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) woff[k][tid] = 0;
+    __syncthreads();
+    constexpr int ROUNDS = NFA_HS_BLOCK_ITEMS / 256;   // a wave's 1024 items, 64 at a time
+    const int64_t base = (int64_t)blockIdx.x * NFA_HS_BLOCK_ITEMS + w * (ROUNDS * 64) + lane;
+    uint32_t key[ROUNDS], id[ROUNDS];   // all loads are issued before the ranking loop, whose rounds depend on each other
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+        const int64_t i = base + r * 64;
+        key[r] = i < A.items ? kin[i] : 0u;
+        id[r] = iin && i < A.items ? iin[i] : (uint32_t)i;
+    }
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r)
+        if (base + r * 64 < A.items) atomicAdd(&woff[w][(key[r] >> shift) & 255u], 1u);
+    __syncthreads();
+    {   // thread = digit: where the block's items of this digit start, then each wave's share in wave order
+        uint32_t total;
+        const uint32_t digit_base = block_excl_sum_256(V.totals[tid], ws, total);
+        uint32_t o = digit_base + V.hist[(int64_t)tid * A.n_blocks + blockIdx.x];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t c = woff[k][tid];
+            woff[k][tid] = o;
+            o += c;
+        }
+    }
+    __syncthreads();
+    volatile uint32_t *my = woff[w];
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+        const int64_t i = base + r * 64;
+        const bool valid = i < A.items;
+        const uint32_t d = (key[r] >> shift) & 255u;
+        unsigned long long same = __ballot(valid);   // the valid lanes with this lane's digit
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (d >> b) & 1u;
+            const unsigned long long bal = __ballot(bit);
+            same &= bit ? bal : ~bal;
+        }
+        const int rank = __popcll(same & below);
+        uint32_t off = 0;
+        if (valid) {
+            off = my[d];
+            const uint32_t pos = off + (uint32_t)rank;
+            if ((int64_t)pos < A.items) {
+                kout[pos] = key[r];
+                iout[pos] = id[r];
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (valid && rank == 0) my[d] = off + (uint32_t)__popcll(same);
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// term of item (n, corner) of level l: coef * g[j] (header of this section)
+template <int F, class E, bool SECOND>
+__device__ __forceinline__ void hs_term(const float *__restrict__ x, const E *__restrict__ g_y, const float *__restrict__ gg_x,
+                                        const HashGridLevels &T, int l, int64_t n, int corner, float *out)
+{
+    const float s = T.scale[l];
+    const Cell c = locate(x + n * 3, s);
+    FVec<F> g;
+    if constexpr (std::is_same<E, float>::value) g = reinterpret_cast<const FVec<F> *>(g_y)[n * T.n_levels + l];
+    else load_elems<F>(g_y + (n * T.n_levels + l) * F, g.v);
+    const float w0 = corner_factor(c, corner, 0), w1 = corner_factor(c, corner, 1), w2 = corner_factor(c, corner, 2);
+    float coef;
+    if constexpr (SECOND) {
+        const float v0 = gg_x[n * 3 + 0], v1 = gg_x[n * 3 + 1], v2 = gg_x[n * 3 + 2];
+        const float u0 = (corner & 1) ? v0 : -v0, u1 = (corner & 2) ? v1 : -v1, u2 = (corner & 4) ? v2 : -v2;
+        coef = ((u0 * (w1 * w2) + u1 * (w0 * w2)) + u2 * (w0 * w1)) * s;
+    } else {
+        coef = (w0 * w1) * w2;
+    }
+#pragma unroll
+    for (int j = 0; j < F; ++j) out[j] = coef * g.v[j];
+}
+
+template <int F, class E, bool SECOND>
+__global__ __launch_bounds__(256) void hs_sum_kernel(const float *__restrict__ x, const E *__restrict__ g_y,
+                                                     const float *__restrict__ gg_x, const HashGridLevels T,
+                                                     const HashSortArgs A, float *__restrict__ g_params)
+{
+    __shared__ uint32_t sk[NFA_HS_TILE];
+    __shared__ float sv[F * NFA_HS_TILE];
+    const int l = A.first_level + (int)blockIdx.y;
+    const HashSortView V = hs_view(A, (int)blockIdx.y);
+    const int sorted = hs_passes(T.size[l]) & 1;
+    const uint32_t *keys = V.keys(sorted), *ids = V.ids(sorted);
+    const int64_t t0 = (int64_t)blockIdx.x * NFA_HS_TILE;
+    const int cnt = (int)(A.items - t0 < NFA_HS_TILE ? A.items - t0 : NFA_HS_TILE);
+    const int tid = (int)threadIdx.x;
+    uint32_t key = 0;
+    if (tid < cnt) {
+        key = keys[t0 + tid];
+        const uint32_t id = ids[t0 + tid];
+        const int64_t n = (int64_t)(id >> 3);
+        float term[F];
+#pragma unroll
+        for (int j = 0; j < F; ++j) term[j] = 0.0f;
+        if (n < A.n_points) hs_term<F, E, SECOND>(x, g_y, gg_x, T, l, n, (int)(id & 7u), term);
+#pragma unroll
+        for (int j = 0; j < F; ++j) sv[j * NFA_HS_TILE + tid] = term[j];
+    }
+    sk[tid] = key;
+    __syncthreads();
+    if (tid < cnt && (tid == 0 || sk[tid - 1] != key)) {   // the first item of a segment
+        float acc[F];
+#pragma unroll
+        for (int j = 0; j < F; ++j) acc[j] = sv[j * NFA_HS_TILE + tid];
+        int p = tid;
+        while (p + 1 < cnt && sk[p + 1] == key) {
+            ++p;
+#pragma unroll
+            for (int j = 0; j < F; ++j) acc[j] = acc[j] + sv[j * NFA_HS_TILE + p];
+        }
+        const bool open_left = tid == 0 && t0 > 0 && keys[t0 - 1] == key;
+        const bool open_right = p == cnt - 1 && t0 + cnt < A.items && keys[t0 + cnt] == key;
+        float *dst = nullptr;
+        if (open_right) dst = V.part + ((int64_t)blockIdx.x * 2 + 1) * 8;
+        else if (open_left) dst = V.part + ((int64_t)blockIdx.x * 2) * 8;
+        else if (key < T.size[l]) dst = g_params + ((size_t)T.offset[l] + key) * F;
+        if (dst) {
+#pragma unroll
+            for (int j = 0; j < F; ++j) dst[j] = acc[j];
+        }
+    }
+}
+
+// Runs that cross tile borders: one thread per (tile, feature); the thread of the tile in which a run starts adds the run's
+// segment sums in tile order (the tail of its tile, then whole tiles' tails, then the head of the tile where the run ends).
+__global__ __launch_bounds__(256) void hs_carry_kernel(const HashGridLevels T, const HashSortArgs A, int F,
+                                                       float *__restrict__ g_params)
+{
+    const int l = A.first_level + (int)blockIdx.y;
+    const HashSortView V = hs_view(A, (int)blockIdx.y);
+    const uint32_t *keys = V.keys(hs_passes(T.size[l]) & 1);
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t t = idx / F;
+    const int j = (int)(idx - t * F);
+    if (t >= A.n_tiles) return;
+    const int64_t t0 = t * NFA_HS_TILE, end = t0 + NFA_HS_TILE;
+    if (end >= A.items) return;                                        // the last tile: nothing follows
+    const uint32_t k = keys[end - 1];
+    if (keys[end] != k) return;                                        // its last run ends with the tile
+    if (t0 > 0 && keys[t0] == k && keys[t0 - 1] == k) return;          // the run started in an earlier tile
+    float acc = V.part[(t * 2 + 1) * 8 + j];
+    for (int64_t t2 = t + 1; t2 < A.n_tiles; ++t2) {
+        const int64_t e2 = t2 * NFA_HS_TILE + NFA_HS_TILE;
+        const bool more = e2 < A.items && keys[e2 - 1] == k && keys[e2] == k;   // the whole tile, and the run goes on
+        acc = acc + V.part[(t2 * 2 + (more ? 1 : 0)) * 8 + j];
+        if (!more) break;
+    }
+    if (k < T.size[l]) g_params[((size_t)T.offset[l] + k) * F + j] = acc;
+}
+
+static int hashsort_check(const char *name, int64_t n_points, int32_t n_levels, const void *scratch, int64_t scratch_bytes)
+{
+    NFA_REQUIRE(8 * n_points < ((int64_t)1 << 32), "%s: 8 * n_points must be below 2^32 (got n_points %lld)", name,
+                (long long)n_points);
+    const HashSortPlan p = hashsort_plan(n_points, n_levels);
+    NFA_REQUIRE(scratch, "%s: scratch is null (a table gradient needs nfa_hashgrid_sorted_scratch_bytes bytes)", name);
+    NFA_REQUIRE(aligned16(scratch), "%s: scratch must be 16-byte aligned", name);
+    NFA_REQUIRE(scratch_bytes >= p.scratch_bytes, "%s: scratch too small (%lld bytes, %lld needed)", name,
+                (long long)scratch_bytes, (long long)p.scratch_bytes);
+    return NFA_OK;
+}
+
+// the table gradient of either order (gg_x: second) into the zeroed grad_params
+template <class E>
+static int hashsort_table_grad(const char *name, const float *x, const E *grad_y, const float *gg_x, int64_t n_points,
+                               int32_t n_features, const HashGridLevels &T, float *grad_params, void *scratch, hipStream_t s)
+{
+    const HashSortPlan p = hashsort_plan(n_points, T.n_levels);
+    HashSortArgs A;
+    A.scratch = static_cast<unsigned char *>(scratch);
+    A.level_bytes = p.level_bytes;
+    A.items = p.items;
+    A.n_blocks = p.n_blocks;
+    A.n_tiles = p.n_tiles;
+    A.n_points = n_points;
+    const dim3 block(256);
+    for (int first = 0; first < T.n_levels; first += p.group) {
+        const unsigned g = (unsigned)(T.n_levels - first < p.group ? T.n_levels - first : p.group);
+        A.first_level = first;
+        int passes = 0;
+        for (unsigned k = 0; k < g; ++k) passes = passes > hs_passes(T.size[first + k]) ? passes : hs_passes(T.size[first + k]);
+        hipLaunchKernelGGL(hs_keys_kernel, dim3(grid_1d(p.items, 256), g), block, 0, s, x, T, A);
+        for (int pass = 0; pass < passes; ++pass) {
+            hipLaunchKernelGGL(hs_count_kernel, dim3((unsigned)p.n_blocks, g), block, 0, s, T, A, pass);
+            hipLaunchKernelGGL(hs_scan_kernel, dim3(256, g), block, 0, s, T, A, pass);
+            hipLaunchKernelGGL(hs_scatter_kernel, dim3((unsigned)p.n_blocks, g), block, 0, s, T, A, pass);
+        }
+        const dim3 tiles((unsigned)p.n_tiles, g);
+#define HS_SUM(F)                                                                                                          \
+        if (gg_x) hipLaunchKernelGGL((hs_sum_kernel<F, E, true>), tiles, block, 0, s, x, grad_y, gg_x, T, A, grad_params);  \
+        else hipLaunchKernelGGL((hs_sum_kernel<F, E, false>), tiles, block, 0, s, x, grad_y, gg_x, T, A, grad_params)
+        switch (n_features) {
+        case 1: HS_SUM(1); break;
+        case 2: HS_SUM(2); break;
+        case 4: HS_SUM(4); break;
+        default: HS_SUM(8); break;
+        }
+#undef HS_SUM
+        hipLaunchKernelGGL(hs_carry_kernel, dim3((unsigned)ceil_div64(p.n_tiles * n_features, 256), g), block, 0, s, T, A,
+                           (int)n_features, grad_params);
+    }
+    NFA_CHECK_LAUNCH(name);
+    return NFA_OK;
+}
+
+template <class E>
+static int hashgrid_bwd_sorted(const float *x, const float *params, const E *grad_y, int64_t n_points, int32_t n_levels,
+                               int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                               const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
+                               float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream)
+{
+    if (!grad_params)
+        return hashgrid_bwd(x, params, grad_y, n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host,
+                            sizes_host, n_params, grad_params, grad_x, stream);
+    HashGridLevels T;
+    int rc = hashgrid_table("hashgrid_bwd_sorted", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                            resolutions_host, sizes_host, n_params, T);
+    if (rc != NFA_OK) return rc;
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(x && grad_y && (params || !grad_x), "hashgrid_bwd_sorted: null pointer");
+    NFA_REQUIRE((std::is_same<E, float>::value) || aligned16(grad_y), "hashgrid_bwd_sorted: a half grad_y must be 16-byte aligned");
+    rc = hashsort_check("hashgrid_bwd_sorted", n_points, n_levels, scratch, scratch_bytes);
+    if (rc != NFA_OK) return rc;
+    if (grad_x) {
+        rc = hashgrid_bwd(x, params, grad_y, n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host,
+                          sizes_host, n_params, (float *)nullptr, grad_x, stream);
+        if (rc != NFA_OK) return rc;
+    }
+    return hashsort_table_grad<E>("hashgrid_bwd_sorted", x, grad_y, nullptr, n_points, n_features, T, grad_params, scratch,
+                                  as_stream(stream));
+}
+
+template <class E>
+static int hashgrid_bwd_bwd_sorted(const float *x, const float *params, const E *grad_y, const float *grad_grad_x,
+                                   int64_t n_points, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
+                                   const float *scales_host, const int32_t *resolutions_host, const int32_t *sizes_host,
+                                   int64_t n_params, E *grad_grad_y, float *grad_params, float *grad_x, void *scratch,
+                                   int64_t scratch_bytes, nfa_stream_t stream)
+{
+    if (!grad_params)
+        return hashgrid_bwd_bwd(x, params, grad_y, grad_grad_x, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                                resolutions_host, sizes_host, n_params, grad_grad_y, grad_params, grad_x, stream);
+    HashGridLevels T;
+    int rc = hashgrid_table("hashgrid_bwd_bwd_sorted", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                            resolutions_host, sizes_host, n_params, T);
+    if (rc != NFA_OK) return rc;
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(grad_grad_x, "hashgrid_bwd_bwd_sorted: grad_grad_x is null");
+    NFA_REQUIRE(x && grad_y && (params || !(grad_grad_y || grad_x)), "hashgrid_bwd_bwd_sorted: null pointer");
+    NFA_REQUIRE((std::is_same<E, float>::value) || (aligned16(grad_y) && aligned16(grad_grad_y)),
+                "hashgrid_bwd_bwd_sorted: half grad_y and grad_grad_y must be 16-byte aligned");
+    rc = hashsort_check("hashgrid_bwd_bwd_sorted", n_points, n_levels, scratch, scratch_bytes);
+    if (rc != NFA_OK) return rc;
+    if (grad_grad_y || grad_x) {
+        rc = hashgrid_bwd_bwd(x, params, grad_y, grad_grad_x, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                              resolutions_host, sizes_host, n_params, grad_grad_y, (float *)nullptr, grad_x, stream);
+        if (rc != NFA_OK) return rc;
+    }
+    return hashsort_table_grad<E>("hashgrid_bwd_bwd_sorted", x, grad_y, grad_grad_x, n_points, n_features, T, grad_params,
+                                  scratch, as_stream(stream));
+}
+
 }  // namespace nfa
 
 using namespace nfa;
@@ -761,4 +1220,35 @@ int nfa_sh_bwd(const float *dirs, const float *grad_out, int64_t n_points, int32
                nfa_stream_t stream)
 {
     return nfa_sh_bwd_t(NFA_ELEM_F32, dirs, grad_out, n_points, degree, grad_dirs, stream);
+}
+
+int64_t nfa_hashgrid_sorted_scratch_bytes(int64_t n_points, int32_t n_levels, int32_t log2_hashmap_size)
+{
+    (void)log2_hashmap_size;   // every level sorts all 8 n_points items, whatever its size
+    if (n_points <= 0 || n_levels < 1) return 0;
+    const HashSortPlan p = hashsort_plan(n_points, n_levels > NFA_HG_MAX_LEVELS ? NFA_HG_MAX_LEVELS : n_levels);
+    return p.scratch_bytes;
+}
+
+int nfa_hashgrid_bwd_sorted(int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points,
+                            int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                            const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
+                            float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream)
+{
+    ELEM_DISPATCH("hashgrid_bwd_sorted", elem,
+                  hashgrid_bwd_sorted(x, params, static_cast<const E *>(grad_y), n_points, n_levels, n_features,
+                                      log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params, grad_params,
+                                      grad_x, scratch, scratch_bytes, stream));
+}
+
+int nfa_hashgrid_bwd_bwd_sorted(int32_t elem, const float *x, const float *params, const void *grad_y,
+                                const float *grad_grad_x, int64_t n_points, int32_t n_levels, int32_t n_features,
+                                int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                                const int32_t *sizes_host, int64_t n_params, void *grad_grad_y, float *grad_params,
+                                float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream)
+{
+    ELEM_DISPATCH("hashgrid_bwd_bwd_sorted", elem,
+                  hashgrid_bwd_bwd_sorted(x, params, static_cast<const E *>(grad_y), grad_grad_x, n_points, n_levels,
+                                          n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params,
+                                          static_cast<E *>(grad_grad_y), grad_params, grad_x, scratch, scratch_bytes, stream));
 }

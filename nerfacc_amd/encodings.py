@@ -134,6 +134,19 @@ def _entry(name: str, dtype: torch.dtype):
     return (name, ()) if dtype == torch.float32 else (name + "_t", (B.ELEM_CODES[dtype],))
 
 
+SORTED_MAX_POINTS = (1 << 29) - 1   # nfa_hashgrid_*_sorted: the item id 8 n + c is 32 bits wide
+
+
+def _sorted_scratch(enc: "HashGridEncoding", n_points: int, device) -> Tensor:
+    """The scratch of one ``nfa_hashgrid_*_sorted`` call: a byte tensor from torch's allocator (under graph capture: the
+    graph's pool), sized by the library."""
+    if n_points > SORTED_MAX_POINTS:
+        raise ValueError(f"HashGridEncoding(deterministic=True): {n_points} points in one call (at most 2^29 - 1 = "
+                         f"{SORTED_MAX_POINTS}: the sorted table gradient numbers its 8 * n_points items in 32 bits)")
+    nbytes = B.load().nfa_hashgrid_sorted_scratch_bytes(n_points, enc.n_levels, enc.table.log2_hashmap_size)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 def _grad_as(g: Tensor, dtype: torch.dtype) -> Tensor:
     """The incoming gradient as the backward kernels read it: contiguous, 16-byte aligned, in the output's dtype (autograd
     delivers it in that dtype, so a half gradient is handed over as it is, never widened)."""
@@ -177,9 +190,15 @@ class _HashGridBwdFn(torch.autograd.Function):
         g_x = torch.empty_like(x) if need_x else None
         if x.shape[0]:
             with torch.cuda.device(x.device):
-                entry, elem = _entry("nfa_hashgrid_bwd", dtype)
-                B.call(entry, *elem, B.ptr(x), B.ptr(params), B.ptr(g), x.shape[0], L, F, t.log2_hashmap_size,
-                       t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(g_p), B.ptr(g_x), B.stream())
+                if enc.deterministic and need_p:
+                    scratch = _sorted_scratch(enc, x.shape[0], x.device)
+                    B.call("nfa_hashgrid_bwd_sorted", B.ELEM_CODES[dtype], B.ptr(x), B.ptr(params), B.ptr(g), x.shape[0], L, F,
+                           t.log2_hashmap_size, t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(g_p), B.ptr(g_x),
+                           B.ptr(scratch), scratch.numel(), B.stream())
+                else:
+                    entry, elem = _entry("nfa_hashgrid_bwd", dtype)
+                    B.call(entry, *elem, B.ptr(x), B.ptr(params), B.ptr(g), x.shape[0], L, F, t.log2_hashmap_size,
+                           t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(g_p), B.ptr(g_x), B.stream())
         ctx.enc, ctx.dtype = enc, dtype
         ctx.save_for_backward(x, params, g)
         ctx.set_materialize_grads(False)
@@ -203,9 +222,15 @@ class _HashGridBwdFn(torch.autograd.Function):
         gg_y = torch.empty_like(g) if need_g else None
         if x.shape[0]:
             with torch.cuda.device(x.device):
-                entry, elem = _entry("nfa_hashgrid_bwd_bwd", ctx.dtype)
-                B.call(entry, *elem, B.ptr(x), B.ptr(params), B.ptr(g), B.ptr(v), x.shape[0], L, F, t.log2_hashmap_size,
-                       t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(gg_y), B.ptr(g2_p), B.ptr(x2), B.stream())
+                if enc.deterministic and need_p:
+                    scratch = _sorted_scratch(enc, x.shape[0], x.device)
+                    B.call("nfa_hashgrid_bwd_bwd_sorted", B.ELEM_CODES[ctx.dtype], B.ptr(x), B.ptr(params), B.ptr(g), B.ptr(v),
+                           x.shape[0], L, F, t.log2_hashmap_size, t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(gg_y),
+                           B.ptr(g2_p), B.ptr(x2), B.ptr(scratch), scratch.numel(), B.stream())
+                else:
+                    entry, elem = _entry("nfa_hashgrid_bwd_bwd", ctx.dtype)
+                    B.call(entry, *elem, B.ptr(x), B.ptr(params), B.ptr(g), B.ptr(v), x.shape[0], L, F, t.log2_hashmap_size,
+                           t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(gg_y), B.ptr(g2_p), B.ptr(x2), B.stream())
         return x2, g2_p, gg_y, None, None, None, None
 
 
@@ -264,12 +289,23 @@ class HashGridEncoding(nn.Module):
     ``out_dtype``: ``None`` (float32 output, also under autocast), ``torch.float16`` / ``torch.bfloat16`` (the float32
     result rounded once to nearest even, written by the kernel itself; the gradient arrives and is read in that dtype),
     or ``"autocast"`` (the active autocast dtype of the input's device when that is fp16 or bf16, else float32).
+
+    ``deterministic``: by default the native table gradient (``dL/dparams``, at first and at second order) is scattered
+    with float atomics, so its last bits change from run to run.  ``True`` forms it by a stable sort of the (point,
+    corner) contributions by table entry and a segmented sum in a fixed order (``nfa_hashgrid_bwd_sorted``,
+    ``nfa_hashgrid_bwd_bwd_sorted``; the order is stated in csrc/encoding.hip): the same inputs give the same bits on
+    every run, at the price of a scratch tensor per call (at most 512 MiB unless one level alone needs more) and at most
+    2^29 - 1 points per call (``ValueError`` above).  Every other result is the same on both settings.  The torch path
+    (CPU tensors, other dtypes) ignores the flag: its reproducibility is torch's own (``index`` backward, see
+    ``torch.use_deterministic_algorithms``).
     """
 
     def __init__(self, n_input_dims: int = 3, n_levels: int = 16, n_features_per_level: int = 2,
-                 log2_hashmap_size: int = 19, base_resolution: float = 16, per_level_scale: float = 2.0, out_dtype=None):
+                 log2_hashmap_size: int = 19, base_resolution: float = 16, per_level_scale: float = 2.0, out_dtype=None,
+                 deterministic: bool = False):
         super().__init__()
         self.out_dtype = _check_out_dtype(out_dtype)
+        self.deterministic = bool(deterministic)
         if n_input_dims != 3:
             raise ValueError(f"HashGridEncoding: only 3 input dimensions are supported (got {n_input_dims})")
         if n_features_per_level not in (1, 2, 4, 8):
@@ -316,7 +352,8 @@ class HashGridEncoding(nn.Module):
     def extra_repr(self) -> str:
         return (f"n_levels={self.n_levels}, n_features_per_level={self.n_features_per_level}, "
                 f"log2_hashmap_size={self.log2_hashmap_size}, base_resolution={self.base_resolution}, "
-                f"per_level_scale={self.per_level_scale}" + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else ""))
+                f"per_level_scale={self.per_level_scale}" + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else "")
+                + (", deterministic=True" if self.deterministic else ""))
 
 
 # Instant-NGP's real spherical-harmonics basis (tcnn's constants)
@@ -376,10 +413,10 @@ class SphericalHarmonicsEncoding(nn.Module):
         return f"degree={self.degree}" + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else "")
 
 
-def encoding_from_tcnn_config(n_input_dims: int, config: dict, out_dtype=None) -> nn.Module:
+def encoding_from_tcnn_config(n_input_dims: int, config: dict, out_dtype=None, deterministic: bool = False) -> nn.Module:
     """The encoding a tiny-cuda-nn encoding config describes: ``HashGrid`` (linear interpolation), ``SphericalHarmonics``,
     or ``Composite`` with ONE nested encoding over all input dimensions (as ``ngp.py`` builds its direction encoding).
-    Anything else raises ``ValueError``.  ``out_dtype`` is handed to the encoding built."""
+    Anything else raises ``ValueError``.  ``out_dtype`` is handed to the encoding built, ``deterministic`` to a hash grid."""
     if not isinstance(config, dict) or "otype" not in config:
         raise ValueError(f"not a tcnn encoding config: {config!r}")
     otype = config["otype"]
@@ -391,7 +428,8 @@ def encoding_from_tcnn_config(n_input_dims: int, config: dict, out_dtype=None) -
                                 n_features_per_level=int(config.get("n_features_per_level", 2)),
                                 log2_hashmap_size=int(config.get("log2_hashmap_size", 19)),
                                 base_resolution=config.get("base_resolution", 16),
-                                per_level_scale=float(config.get("per_level_scale", 2.0)), out_dtype=out_dtype)
+                                per_level_scale=float(config.get("per_level_scale", 2.0)), out_dtype=out_dtype,
+                                deterministic=deterministic)
     if otype == "SphericalHarmonics":
         return SphericalHarmonicsEncoding(n_input_dims, degree=int(config.get("degree", 4)), out_dtype=out_dtype)
     if otype == "Composite":
@@ -402,5 +440,5 @@ def encoding_from_tcnn_config(n_input_dims: int, config: dict, out_dtype=None) -
         dims = inner.pop("n_dims_to_encode", n_input_dims)
         if dims != n_input_dims:
             raise ValueError(f"Composite: the nested encoding must cover all {n_input_dims} dimensions (got {dims})")
-        return encoding_from_tcnn_config(n_input_dims, inner, out_dtype)
+        return encoding_from_tcnn_config(n_input_dims, inner, out_dtype, deterministic)
     raise ValueError(f"unsupported tcnn encoding {otype!r} (supported: HashGrid, SphericalHarmonics, Composite)")

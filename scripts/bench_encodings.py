@@ -18,7 +18,13 @@ times an Eikonal-shaped step on uniform points: forward, `autograd.grad(y, x, g,
 function of that dL/dx (sum of squares) towards the table -- natively (nfa_hashgrid_fwd, _bwd, _bwd_bwd) and through
 `_hashgrid_torch` on the same GPU, the only way to run such a step without the second-order pass.  The two alternate window by
 window; medians.  The native step is also split: the first-order part (forward + backward with create_graph) and the
-second-order pass alone (the step minus the first-order part)."""
+second-order pass alone (the step minus the first-order part).
+    python scripts/bench_encodings.py --deterministic [--dtype bfloat16] [--sizes 18,20] [--reps 10] [--windows 7]
+    python scripts/bench_encodings.py --deterministic --eikonal [--sizes 18]
+times the reproducible table gradient (HashGridEncoding(deterministic=True): nfa_hashgrid_bwd_sorted, _bwd_bwd_sorted) next
+to the atomic one of the same build: the backward towards the table (zeroing included) on uniform and occgrid points, or the
+Eikonal-shaped step.  The two alternate window by window; each figure is the median over the windows, `*_spread` the
+(min, max) over them.  `scratch_bytes` is what one sorted call allocates."""
 import argparse
 import json
 import math
@@ -53,6 +59,92 @@ def alternating_medians(fns, reps, windows):
         for k, fn in fns.items():
             times[k].append(timed(fn, reps))
     return {k: float(np.median(v)) for k, v in times.items()}
+
+
+def alternating_stats(fns, reps, windows):
+    """{name_us: median, name_spread: (min, max)} of `windows` timed windows per function, the functions taking turns."""
+    times = {k: [] for k in fns}
+    for _ in range(windows):
+        for k, fn in fns.items():
+            times[k].append(timed(fn, reps))
+    out = {}
+    for k, v in times.items():
+        out[k + "_us"] = float(np.median(v))
+        out[k + "_spread"] = (float(min(v)), float(max(v)))
+    return out
+
+
+def sorted_pair(cfg, dev, out_dtype=None):
+    """(atomic grid, sorted grid) on one parameter tensor, uniform in +-1."""
+    torch.manual_seed(0)
+    enc = HashGridEncoding(3, out_dtype=out_dtype, **cfg).to(dev)
+    with torch.no_grad():
+        enc.params.uniform_(-1, 1)
+    det = HashGridEncoding(3, out_dtype=out_dtype, deterministic=True, **cfg)
+    det.params = enc.params
+    return enc, det
+
+
+def deterministic_rows(args, dev, dtype):
+    sizes = [1 << int(s) for s in args.sizes.split(",")]
+    scratch = B.load().nfa_hashgrid_sorted_scratch_bytes
+    torch.manual_seed(0)
+    uni = torch.rand(max(sizes), 3, device=dev)
+    if args.eikonal:
+        for cname, cfg in CONFIGS.items():
+            enc, det = sorted_pair(cfg, dev)
+            L, F = enc.n_levels, enc.n_features_per_level
+            for N in sizes:
+                x = uni[:N].clone().requires_grad_(True)
+                g = torch.randn(N, L * F, device=dev)
+
+                def step(fn):
+                    enc.params.grad = None
+                    x.grad = None
+                    (g_x,) = torch.autograd.grad(fn(x), x, g, create_graph=True)
+                    (g_x ** 2).sum().backward()
+
+                step(det)
+                gp = enc.params.grad.clone()
+                step(det)
+                row = dict(config=cname, mode="eikonal", N=N, L=L, F=F, sorted_repeats_bitwise=bool(torch.equal(gp, enc.params.grad)),
+                           scratch_bytes=int(scratch(N, L, cfg["log2_hashmap_size"])))
+                step(enc)
+                row["sorted_vs_atomic_max_abs"] = float((enc.params.grad - gp).abs().max())
+                row["grad_max_abs"] = float(gp.abs().max())
+                row.update(alternating_stats({"atomic_step": lambda: step(enc), "sorted_step": lambda: step(det)}, args.reps, args.windows))
+                row["sorted_over_atomic"] = row["sorted_step_us"] / row["atomic_step_us"]
+                print(json.dumps(row), flush=True)
+        return
+    real, _ = occgrid_midpoints(dev, max(sizes))
+    out_dtype = None if dtype == torch.float32 else dtype
+    for cname, cfg in CONFIGS.items():
+        enc, det = sorted_pair(cfg, dev, out_dtype)
+        L, F = enc.n_levels, enc.n_features_per_level
+        for N in sizes:
+            for pname, pts in (("uniform", uni[:N]), ("occgrid", real[:N])):
+                x = pts.clone()
+                g = torch.randn(N, L * F, device=dev).to(dtype)
+                ys = {"atomic": enc(x), "sorted": det(x)}
+
+                def bwd(k):
+                    enc.params.grad = None
+                    torch.autograd.backward(ys[k], g, retain_graph=True)
+
+                bwd("sorted")
+                gp = enc.params.grad.clone()
+                bwd("sorted")
+                row = dict(config=cname, points=pname, dtype=str(dtype), N=N, L=L, F=F,
+                           sorted_repeats_bitwise=bool(torch.equal(gp, enc.params.grad)),
+                           scratch_bytes=int(scratch(N, L, cfg["log2_hashmap_size"])))
+                bwd("atomic")
+                row["sorted_vs_atomic_max_abs"] = float((enc.params.grad - gp).abs().max())
+                row["grad_max_abs"] = float(gp.abs().max())
+                row.update(alternating_stats({"atomic_bwd_params": lambda: bwd("atomic"), "sorted_bwd_params": lambda: bwd("sorted")},
+                                             args.reps, args.windows))
+                row["sorted_over_atomic"] = row["sorted_bwd_params_us"] / row["atomic_bwd_params_us"]
+                print(json.dumps(row), flush=True)
+                del ys
 
 
 def half_rows(args, dev, dtype):
@@ -152,9 +244,12 @@ def main():
     ap.add_argument("--dtype", default="float32", choices=["float32", "float16", "bfloat16"])
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--eikonal", action="store_true")
+    ap.add_argument("--deterministic", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     B.load()
+    if args.deterministic:
+        return deterministic_rows(args, dev, getattr(torch, args.dtype))
     if args.eikonal:
         return eikonal_rows(args, dev)
     if args.dtype != "float32":
