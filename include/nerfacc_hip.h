@@ -618,8 +618,9 @@ int nfa_opencv_lens_undistortion_fisheye(const float *uv, const float *params, i
 /* ------------------------------------------------------------------ input encodings */
 
 /* tiny-cuda-nn's `HashGrid` encoding (Instant-NGP's multiresolution hash grid, Mueller et al. 2022) with 3-D input and
- * linear interpolation; the formulas are those of csrc/encoding.hip's header.  x [n_points, 3], y [n_points, n_levels *
- * n_features], params the flat [sum(sizes) * n_features] table laid out [level][entry][feature].  The level table
+ * linear interpolation (smoothstep: the `_i` entries below); the formulas are those of csrc/encoding.hip's header.
+ * x [n_points, 3], y [n_points, n_levels * n_features], params the flat [sum(sizes) * n_features] table laid out
+ * [level][entry][feature].  The level table
  * (n_levels entries each, host memory) is computed by the caller in float32: scale_l = exp2f(l log2f(per_level_scale)) *
  * base_resolution - 1, resolution_l = ceil(scale_l) + 1, size_l = min(roundup8(resolution_l^3), 2^log2_hashmap_size);
  * a size that does not follow from the resolution is rejected.  n_features 1, 2, 4 or 8, n_levels 1..32,
@@ -695,6 +696,40 @@ int nfa_hashgrid_bwd_bwd_sorted(int32_t elem, const float *x, const float *param
                                 int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
                                 const int32_t *sizes_host, int64_t n_params, void *grad_grad_y, float *grad_params,
                                 float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream);
+/* The five hash-grid passes with the interpolation as a leading argument; everything else as in nfa_hashgrid_fwd_t,
+ * nfa_hashgrid_bwd_t, nfa_hashgrid_bwd_bwd_t, nfa_hashgrid_bwd_sorted and nfa_hashgrid_bwd_bwd_sorted, which are the
+ * NFA_INTERP_LINEAR case.  NFA_INTERP_SMOOTHSTEP is tiny-cuda-nn's "interpolation": "Smoothstep": the corner weights are
+ * formed from S(f) = f^2 (3 - 2 f) instead of the fraction f, so the encoding is C^1 across cell faces and grad_x of the
+ * second order gains the pure second partials (S'' = 6 - 12 f) next to the mixed ones; the operations, in float32 and in a
+ * fixed order, are in csrc/encoding.hip's header, "Smoothstep interpolation".  What is bitwise reproducible, the order of
+ * the sorted table gradient (with the smoothstep coefficient in place of the linear one) and the scratch are unchanged.
+ * Any other interp is NFA_EINVAL, checked before every other argument. */
+#define NFA_INTERP_LINEAR 0
+#define NFA_INTERP_SMOOTHSTEP 1
+int nfa_hashgrid_fwd_i(int32_t interp, int32_t elem, const float *x, const float *params, int64_t n_points,
+                       int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                       const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, void *y,
+                       nfa_stream_t stream);
+int nfa_hashgrid_bwd_i(int32_t interp, int32_t elem, const float *x, const float *params, const void *grad_y,
+                       int64_t n_points, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
+                       const float *scales_host, const int32_t *resolutions_host, const int32_t *sizes_host,
+                       int64_t n_params, float *grad_params, float *grad_x, nfa_stream_t stream);
+int nfa_hashgrid_bwd_bwd_i(int32_t interp, int32_t elem, const float *x, const float *params, const void *grad_y,
+                           const float *grad_grad_x, int64_t n_points, int32_t n_levels, int32_t n_features,
+                           int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                           const int32_t *sizes_host, int64_t n_params, void *grad_grad_y, float *grad_params,
+                           float *grad_x, nfa_stream_t stream);
+int nfa_hashgrid_bwd_sorted_i(int32_t interp, int32_t elem, const float *x, const float *params, const void *grad_y,
+                              int64_t n_points, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
+                              const float *scales_host, const int32_t *resolutions_host, const int32_t *sizes_host,
+                              int64_t n_params, float *grad_params, float *grad_x, void *scratch,
+                              int64_t scratch_bytes, nfa_stream_t stream);
+int nfa_hashgrid_bwd_bwd_sorted_i(int32_t interp, int32_t elem, const float *x, const float *params,
+                                  const void *grad_y, const float *grad_grad_x, int64_t n_points, int32_t n_levels,
+                                  int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                                  const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params,
+                                  void *grad_grad_y, float *grad_params, float *grad_x, void *scratch,
+                                  int64_t scratch_bytes, nfa_stream_t stream);
 int nfa_sh_fwd_t(int32_t elem, const float *dirs, int64_t n_points, int32_t degree, void *out, nfa_stream_t stream);
 int nfa_sh_bwd_t(int32_t elem, const float *dirs, const void *grad_out, int64_t n_points, int32_t degree,
                  float *grad_dirs, nfa_stream_t stream);

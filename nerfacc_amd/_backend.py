@@ -126,6 +126,12 @@ _SIGS = {
     "nfa_hashgrid_sorted_scratch_bytes": [_i64, _i32, _i32],
     "nfa_hashgrid_bwd_sorted": [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp],
     "nfa_hashgrid_bwd_bwd_sorted": [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp],
+    "nfa_hashgrid_fwd_i": [_i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
+    "nfa_hashgrid_bwd_i": [_i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "nfa_hashgrid_bwd_bwd_i": [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "nfa_hashgrid_bwd_sorted_i": [_i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp],
+    "nfa_hashgrid_bwd_bwd_sorted_i": [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                      _i64, _vp],
     "nfa_sh_fwd_t": [_i32, _vp, _i64, _i32, _vp, _vp],
     "nfa_sh_bwd_t": [_i32, _vp, _vp, _i64, _i32, _vp, _vp],
     "nfa_sample_positions_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
@@ -182,6 +188,8 @@ ABI_VERSION = 403   # include/nerfacc_hip.h: NFA_VERSION
 
 # include/nerfacc_hip.h: NFA_ELEM_*, the element type of the `_t` entries' activation streams
 ELEM_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+# include/nerfacc_hip.h: NFA_INTERP_*, the hash grid's interpolation (the leading argument of the `_i` entries)
+INTERP_CODES = {"Linear": 0, "Smoothstep": 1}
 
 
 def set_tuning(name: str, value: Optional[str]) -> None:

@@ -1,6 +1,6 @@
-// encoding.hip -- input encodings of Instant-NGP radiance fields: the multiresolution hash grid (D = 3, linear
-// interpolation) and the spherical-harmonics direction encoding, as tiny-cuda-nn's `HashGrid` and `SphericalHarmonics`
-// define them (Mueller et al. 2022, "Instant Neural Graphics Primitives", sec. 3).
+// encoding.hip -- input encodings of Instant-NGP radiance fields: the multiresolution hash grid (D = 3, linear or
+// smoothstep interpolation) and the spherical-harmonics direction encoding, as tiny-cuda-nn's `HashGrid` and
+// `SphericalHarmonics` define them (Mueller et al. 2022, "Instant Neural Graphics Primitives", sec. 3).
 //
 // Hash grid, per point x and level l (all integer arithmetic uint32, wrapping):
 //   p_d = x_d * scale_l + 0.5 (a multiply, then an add: the library builds with -ffp-contract=off)
@@ -35,6 +35,22 @@
 // x2 has mixed partials only (linear interpolation has no pure second derivative); floor() contributes no gradient and the
 // cell is the one locate() gives.  Same lane layout as the backward; each output is optional, and the corner parameters are
 // read only for gg_y and x2.
+//
+// Smoothstep interpolation (NFA_INTERP_SMOOTHSTEP; tiny-cuda-nn's "interpolation": "Smoothstep"): everything up to f_d, g_d and
+// the corner index is as above.  Per dimension d of a (point, level), float32, formed once in exactly these operations:
+//   S_d = (f_d * f_d) * (3 - 2 * f_d),   S'_d = (6 * f_d) * (1 - f_d),   S''_d = 6 - 12 * f_d
+//   w_d = (c_d ? S_d : 1 - S_d)                                    (replaces c_d ? f_d : 1 - f_d everywhere above)
+//   forward:   w_c = (w_0 * w_1) * w_2 and the sum over the corners as above; the table gradient term is w_c * g[j].
+//   backward:  the corner sum of dL/dx_d as above (sign of c_d, the two other factors, dot_c), then dL/dx_d = (sum * S'_d) * s,
+//              summed over the levels as above.  S'(0) = 0: dL/dx_d vanishes on the cell faces of a level, the grid is C^1.
+//   second order: u_d = (c_d ? v_d : -v_d) * S'_d (one multiply; the kernels form v_d * S'_d once and negate, the same bits);
+//              a_c, gg_y and G2_T as above with this u_d;
+//              h_e = (S'_e * (u_a * w_b + u_b * w_a) + (v_e * S''_e) * (w_a * w_b)) * dot_c, (a, b) = (1, 2), (0, 2), (0, 1)
+//              for e = 0, 1, 2, with v_e * S''_e formed once per (point, level);
+//              x2_l[e] = ((sum_c (c_e ? + : -) h_e) * s) * s, summed over the levels as above.
+//              The second summand of h_e is the pure second partial d2/dx_e2 that the linear grid lacks.
+// The interpolation is a template parameter of the kernels that form a weight (forward, backward, second order, hs_term of the
+// sorted path); the Linear instantiations are the code they were before it existed.
 //
 // Element types: y / dL/dy (and the spherical harmonics' out / dL/dout) are float, fp16 or bf16 (NFA_ELEM_*, common.hip.h).
 // The arithmetic is the float32 one whatever the type; a point's F values of a level are converted once and moved as one
@@ -138,6 +154,18 @@ __device__ __forceinline__ float corner_factor(const Cell &c, int corner, int d)
     return ((corner >> d) & 1) ? c.f[d] : 1.0f - c.f[d];
 }
 
+// Smoothstep (header): the cell's fractions become S_d, so that corner_factor() gives w_d; d1 = S', d2 = S''
+__device__ __forceinline__ void smoothstep(Cell &c, float *d1, float *d2)
+{
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float f = c.f[d];
+        d1[d] = (6.0f * f) * (1.0f - f);
+        d2[d] = 6.0f - 12.0f * f;
+        c.f[d] = (f * f) * (3.0f - 2.0f * f);
+    }
+}
+
 // (point, level) of this lane; false for the idle lanes of a wave
 __device__ __forceinline__ bool lane_item(const HashGridLevels &T, int64_t wave, int64_t n_points, int64_t &n, int &l)
 {
@@ -152,7 +180,7 @@ __device__ __forceinline__ bool lane_item(const HashGridLevels &T, int64_t wave,
 // stays in one XCD's L2 (4 MiB: a hashed level of the NGP grid), and write their F-float pieces at a stride of L F floats.
 // Measured against one lane per (point, level) with the level fastest in the wave (coalesced output rows): 0.83-0.90 of
 // its time at 2^20 points (DESIGN.md "Input encodings").
-template <int F, class E>
+template <int F, class E, int I>
 __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const float *__restrict__ x, const float *__restrict__ params,
                                                            int64_t n_points, const HashGridLevels T, E *__restrict__ y)
 {
@@ -163,7 +191,11 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const float *__restri
     const FVec<F> *tab = reinterpret_cast<const FVec<F> *>(params) + T.offset[l];
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < n_points; n += stride) {
-        const Cell c = locate(x + n * 3, scale);
+        Cell c = locate(x + n * 3, scale);
+        if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
+            float d1[3], d2[3];
+            smoothstep(c, d1, d2);
+        }
         float acc[F];
 #pragma unroll
         for (int j = 0; j < F; ++j) acc[j] = 0.0f;
@@ -185,7 +217,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const float *__restri
     }
 }
 
-template <int F, class E>
+template <int F, class E, int I>
 __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restrict__ x, const float *__restrict__ params,
                                                            const E *__restrict__ g_y, int64_t n_points,
                                                            const HashGridLevels T, float *__restrict__ g_params,
@@ -199,7 +231,9 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restri
         const bool active = lane_item(T, w, n_points, n, l);
         float dx[3] = {0.0f, 0.0f, 0.0f};
         if (active) {
-            const Cell c = locate(x + n * 3, T.scale[l]);
+            Cell c = locate(x + n * 3, T.scale[l]);
+            float d1[3], d2[3];
+            if constexpr (I == NFA_INTERP_SMOOTHSTEP) smoothstep(c, d1, d2);
             const bool hashed = (T.hashed >> l) & 1u;
             const uint32_t res = T.res[l], size = T.size[l];
             FVec<F> g;
@@ -230,7 +264,11 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restri
             }
             if (g_x) {
                 const float s = T.scale[l];
-                dx[0] *= s; dx[1] *= s; dx[2] *= s;
+                if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
+                    dx[0] = (dx[0] * d1[0]) * s; dx[1] = (dx[1] * d1[1]) * s; dx[2] = (dx[2] * d1[2]) * s;
+                } else {
+                    dx[0] *= s; dx[1] *= s; dx[2] *= s;
+                }
             }
         }
         if (g_x) {
@@ -257,7 +295,7 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restri
 
 // Second order: the derivative of the backward's dL/dx output, given its incoming gradient v = gg_x[n] (header: "Second
 // order").  Shape of hashgrid_bwd_kernel; every output is optional, and the corners are read only for gg_y and x2.
-template <int F, class E>
+template <int F, class E, int I>
 __global__ __launch_bounds__(256) void hashgrid_bwd_bwd_kernel(const float *__restrict__ x, const float *__restrict__ params,
                                                                const E *__restrict__ g_y, const float *__restrict__ gg_x,
                                                                int64_t n_points, const HashGridLevels T,
@@ -273,10 +311,17 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_bwd_kernel(const float *__re
         float dx[3] = {0.0f, 0.0f, 0.0f};
         if (active) {
             const float s = T.scale[l];
-            const Cell c = locate(x + n * 3, s);
+            Cell c = locate(x + n * 3, s);
             const bool hashed = (T.hashed >> l) & 1u;
             const uint32_t res = T.res[l], size = T.size[l];
-            const float v0 = gg_x[n * 3 + 0], v1 = gg_x[n * 3 + 1], v2 = gg_x[n * 3 + 2];
+            float v0 = gg_x[n * 3 + 0], v1 = gg_x[n * 3 + 1], v2 = gg_x[n * 3 + 2];
+            float d1[3], p0, p1, p2;   // Smoothstep: S'_d, v_d * S''_d; v_d becomes v_d * S'_d
+            if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
+                float d2[3];
+                smoothstep(c, d1, d2);
+                p0 = v0 * d2[0]; p1 = v1 * d2[1]; p2 = v2 * d2[2];
+                v0 = v0 * d1[0]; v1 = v1 * d1[1]; v2 = v2 * d1[2];
+            }
             FVec<F> g = {};
             if (g_params || g_x) {
                 if constexpr (std::is_same<E, float>::value) g = reinterpret_cast<const FVec<F> *>(g_y)[n * T.n_levels + l];
@@ -305,7 +350,14 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_bwd_kernel(const float *__re
                         float dot = 0.0f;
 #pragma unroll
                         for (int j = 0; j < F; ++j) dot = dot + g.v[j] * t.v[j];
-                        const float t0 = (u1 * w2 + u2 * w1) * dot, t1 = (u0 * w2 + u2 * w0) * dot, t2 = (u0 * w1 + u1 * w0) * dot;
+                        float t0, t1, t2;
+                        if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
+                            t0 = (d1[0] * (u1 * w2 + u2 * w1) + p0 * (w1 * w2)) * dot;
+                            t1 = (d1[1] * (u0 * w2 + u2 * w0) + p1 * (w0 * w2)) * dot;
+                            t2 = (d1[2] * (u0 * w1 + u1 * w0) + p2 * (w0 * w1)) * dot;
+                        } else {
+                            t0 = (u1 * w2 + u2 * w1) * dot; t1 = (u0 * w2 + u2 * w0) * dot; t2 = (u0 * w1 + u1 * w0) * dot;
+                        }
                         dx[0] = (corner & 1) ? dx[0] + t0 : dx[0] - t0;
                         dx[1] = (corner & 2) ? dx[1] + t1 : dx[1] - t1;
                         dx[2] = (corner & 4) ? dx[2] + t2 : dx[2] - t2;
@@ -555,10 +607,34 @@ static unsigned hashgrid_grid(int64_t n_points, const HashGridLevels &T)
 }
 
 // ---------------------------------------------------------------- the entries, one implementation per element type
+static int check_interp(const char *name, int32_t interp)
+{
+    NFA_REQUIRE(interp == NFA_INTERP_LINEAR || interp == NFA_INTERP_SMOOTHSTEP,
+                "%s: interp must be NFA_INTERP_LINEAR (0) or NFA_INTERP_SMOOTHSTEP (1) (got %d)", name, interp);
+    return NFA_OK;
+}
+
+// Host-side dispatch of (n_features, interp), both checked before, to compile-time values:
+// f(std::integral_constant<int, F>, std::integral_constant<int, I>)
+template <class Fn>
+static void dispatch_grid(int32_t n_features, int32_t interp, Fn &&f)
+{
+    dispatch_bool(interp == NFA_INTERP_SMOOTHSTEP, [&](auto smooth) {
+        using I = std::integral_constant<int, decltype(smooth)::value ? NFA_INTERP_SMOOTHSTEP : NFA_INTERP_LINEAR>;
+        switch (n_features) {
+        case 1: f(std::integral_constant<int, 1>{}, I{}); break;
+        case 2: f(std::integral_constant<int, 2>{}, I{}); break;
+        case 4: f(std::integral_constant<int, 4>{}, I{}); break;
+        default: f(std::integral_constant<int, 8>{}, I{}); break;
+        }
+    });
+}
+
 template <class E>
-static int hashgrid_fwd(const float *x, const float *params, int64_t n_points, int32_t n_levels, int32_t n_features,
-                        int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
-                        const int32_t *sizes_host, int64_t n_params, E *y, nfa_stream_t stream)
+static int hashgrid_fwd(int32_t interp, const float *x, const float *params, int64_t n_points, int32_t n_levels,
+                        int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                        const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, E *y,
+                        nfa_stream_t stream)
 {
     HashGridLevels T;
     const int rc = hashgrid_table("hashgrid_fwd", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
@@ -569,19 +645,16 @@ static int hashgrid_fwd(const float *x, const float *params, int64_t n_points, i
     NFA_REQUIRE((std::is_same<E, float>::value) || aligned16(y), "hashgrid_fwd: a half y must be 16-byte aligned");
     hipStream_t s = as_stream(stream);
     const dim3 grid(grid_1d(n_points, 256, 256 * 16 / n_levels + 1), n_levels), block(256);
-    switch (n_features) {
-    case 1: hipLaunchKernelGGL((hashgrid_fwd_kernel<1, E>), grid, block, 0, s, x, params, n_points, T, y); break;
-    case 2: hipLaunchKernelGGL((hashgrid_fwd_kernel<2, E>), grid, block, 0, s, x, params, n_points, T, y); break;
-    case 4: hipLaunchKernelGGL((hashgrid_fwd_kernel<4, E>), grid, block, 0, s, x, params, n_points, T, y); break;
-    default: hipLaunchKernelGGL((hashgrid_fwd_kernel<8, E>), grid, block, 0, s, x, params, n_points, T, y); break;
-    }
+    dispatch_grid(n_features, interp, [&](auto f, auto i) {
+        hipLaunchKernelGGL((hashgrid_fwd_kernel<f(), E, i()>), grid, block, 0, s, x, params, n_points, T, y);
+    });
     NFA_CHECK_LAUNCH("hashgrid_fwd");
     return NFA_OK;
 }
 
 template <class E>
-static int hashgrid_bwd(const float *x, const float *params, const E *grad_y, int64_t n_points, int32_t n_levels,
-                        int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+static int hashgrid_bwd(int32_t interp, const float *x, const float *params, const E *grad_y, int64_t n_points,
+                        int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
                         const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
                         float *grad_x, nfa_stream_t stream)
 {
@@ -594,21 +667,19 @@ static int hashgrid_bwd(const float *x, const float *params, const E *grad_y, in
     NFA_REQUIRE((std::is_same<E, float>::value) || aligned16(grad_y), "hashgrid_bwd: a half grad_y must be 16-byte aligned");
     const dim3 grid(hashgrid_grid(n_points, T)), block(256);
     hipStream_t s = as_stream(stream);
-    switch (n_features) {
-    case 1: hipLaunchKernelGGL((hashgrid_bwd_kernel<1, E>), grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
-    case 2: hipLaunchKernelGGL((hashgrid_bwd_kernel<2, E>), grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
-    case 4: hipLaunchKernelGGL((hashgrid_bwd_kernel<4, E>), grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
-    default: hipLaunchKernelGGL((hashgrid_bwd_kernel<8, E>), grid, block, 0, s, x, params, grad_y, n_points, T, grad_params, grad_x); break;
-    }
+    dispatch_grid(n_features, interp, [&](auto f, auto i) {
+        hipLaunchKernelGGL((hashgrid_bwd_kernel<f(), E, i()>), grid, block, 0, s, x, params, grad_y, n_points, T, grad_params,
+                           grad_x);
+    });
     NFA_CHECK_LAUNCH("hashgrid_bwd");
     return NFA_OK;
 }
 
 template <class E>
-static int hashgrid_bwd_bwd(const float *x, const float *params, const E *grad_y, const float *grad_grad_x, int64_t n_points,
-                            int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
-                            const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, E *grad_grad_y,
-                            float *grad_params, float *grad_x, nfa_stream_t stream)
+static int hashgrid_bwd_bwd(int32_t interp, const float *x, const float *params, const E *grad_y, const float *grad_grad_x,
+                            int64_t n_points, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
+                            const float *scales_host, const int32_t *resolutions_host, const int32_t *sizes_host,
+                            int64_t n_params, E *grad_grad_y, float *grad_params, float *grad_x, nfa_stream_t stream)
 {
     HashGridLevels T;
     const int rc = hashgrid_table("hashgrid_bwd_bwd", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
@@ -622,16 +693,10 @@ static int hashgrid_bwd_bwd(const float *x, const float *params, const E *grad_y
                 "hashgrid_bwd_bwd: half grad_y and grad_grad_y must be 16-byte aligned");
     const dim3 grid(hashgrid_grid(n_points, T)), block(256);
     hipStream_t s = as_stream(stream);
-    switch (n_features) {
-    case 1: hipLaunchKernelGGL((hashgrid_bwd_bwd_kernel<1, E>), grid, block, 0, s, x, params, grad_y, grad_grad_x, n_points, T,
-                               grad_grad_y, grad_params, grad_x); break;
-    case 2: hipLaunchKernelGGL((hashgrid_bwd_bwd_kernel<2, E>), grid, block, 0, s, x, params, grad_y, grad_grad_x, n_points, T,
-                               grad_grad_y, grad_params, grad_x); break;
-    case 4: hipLaunchKernelGGL((hashgrid_bwd_bwd_kernel<4, E>), grid, block, 0, s, x, params, grad_y, grad_grad_x, n_points, T,
-                               grad_grad_y, grad_params, grad_x); break;
-    default: hipLaunchKernelGGL((hashgrid_bwd_bwd_kernel<8, E>), grid, block, 0, s, x, params, grad_y, grad_grad_x, n_points, T,
-                               grad_grad_y, grad_params, grad_x); break;
-    }
+    dispatch_grid(n_features, interp, [&](auto f, auto i) {
+        hipLaunchKernelGGL((hashgrid_bwd_bwd_kernel<f(), E, i()>), grid, block, 0, s, x, params, grad_y, grad_grad_x,
+                           n_points, T, grad_grad_y, grad_params, grad_x);
+    });
     NFA_CHECK_LAUNCH("hashgrid_bwd_bwd");
     return NFA_OK;
 }
@@ -921,12 +986,14 @@ __global__ __launch_bounds__(256) void hs_scatter_kernel(const HashGridLevels T,
 }
 
 // term of item (n, corner) of level l: coef * g[j] (header of this section)
-template <int F, class E, bool SECOND>
+template <int F, class E, bool SECOND, int I>
 __device__ __forceinline__ void hs_term(const float *__restrict__ x, const E *__restrict__ g_y, const float *__restrict__ gg_x,
                                         const HashGridLevels &T, int l, int64_t n, int corner, float *out)
 {
     const float s = T.scale[l];
-    const Cell c = locate(x + n * 3, s);
+    Cell c = locate(x + n * 3, s);
+    float d1[3], d2[3];
+    if constexpr (I == NFA_INTERP_SMOOTHSTEP) smoothstep(c, d1, d2);
     FVec<F> g;
     if constexpr (std::is_same<E, float>::value) g = reinterpret_cast<const FVec<F> *>(g_y)[n * T.n_levels + l];
     else load_elems<F>(g_y + (n * T.n_levels + l) * F, g.v);
@@ -934,7 +1001,10 @@ __device__ __forceinline__ void hs_term(const float *__restrict__ x, const E *__
     float coef;
     if constexpr (SECOND) {
         const float v0 = gg_x[n * 3 + 0], v1 = gg_x[n * 3 + 1], v2 = gg_x[n * 3 + 2];
-        const float u0 = (corner & 1) ? v0 : -v0, u1 = (corner & 2) ? v1 : -v1, u2 = (corner & 4) ? v2 : -v2;
+        float u0 = (corner & 1) ? v0 : -v0, u1 = (corner & 2) ? v1 : -v1, u2 = (corner & 4) ? v2 : -v2;
+        if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
+            u0 = u0 * d1[0]; u1 = u1 * d1[1]; u2 = u2 * d1[2];
+        }
         coef = ((u0 * (w1 * w2) + u1 * (w0 * w2)) + u2 * (w0 * w1)) * s;
     } else {
         coef = (w0 * w1) * w2;
@@ -943,7 +1013,7 @@ __device__ __forceinline__ void hs_term(const float *__restrict__ x, const E *__
     for (int j = 0; j < F; ++j) out[j] = coef * g.v[j];
 }
 
-template <int F, class E, bool SECOND>
+template <int F, class E, bool SECOND, int I>
 __global__ __launch_bounds__(256) void hs_sum_kernel(const float *__restrict__ x, const E *__restrict__ g_y,
                                                      const float *__restrict__ gg_x, const HashGridLevels T,
                                                      const HashSortArgs A, float *__restrict__ g_params)
@@ -965,7 +1035,7 @@ __global__ __launch_bounds__(256) void hs_sum_kernel(const float *__restrict__ x
         float term[F];
 #pragma unroll
         for (int j = 0; j < F; ++j) term[j] = 0.0f;
-        if (n < A.n_points) hs_term<F, E, SECOND>(x, g_y, gg_x, T, l, n, (int)(id & 7u), term);
+        if (n < A.n_points) hs_term<F, E, SECOND, I>(x, g_y, gg_x, T, l, n, (int)(id & 7u), term);
 #pragma unroll
         for (int j = 0; j < F; ++j) sv[j * NFA_HS_TILE + tid] = term[j];
     }
@@ -1035,8 +1105,9 @@ static int hashsort_check(const char *name, int64_t n_points, int32_t n_levels, 
 
 // the table gradient of either order (gg_x: second) into the zeroed grad_params
 template <class E>
-static int hashsort_table_grad(const char *name, const float *x, const E *grad_y, const float *gg_x, int64_t n_points,
-                               int32_t n_features, const HashGridLevels &T, float *grad_params, void *scratch, hipStream_t s)
+static int hashsort_table_grad(const char *name, int32_t interp, const float *x, const E *grad_y, const float *gg_x,
+                               int64_t n_points, int32_t n_features, const HashGridLevels &T, float *grad_params, void *scratch,
+                               hipStream_t s)
 {
     const HashSortPlan p = hashsort_plan(n_points, T.n_levels);
     HashSortArgs A;
@@ -1059,16 +1130,12 @@ static int hashsort_table_grad(const char *name, const float *x, const E *grad_y
             hipLaunchKernelGGL(hs_scatter_kernel, dim3((unsigned)p.n_blocks, g), block, 0, s, T, A, pass);
         }
         const dim3 tiles((unsigned)p.n_tiles, g);
-#define HS_SUM(F)                                                                                                          \
-        if (gg_x) hipLaunchKernelGGL((hs_sum_kernel<F, E, true>), tiles, block, 0, s, x, grad_y, gg_x, T, A, grad_params);  \
-        else hipLaunchKernelGGL((hs_sum_kernel<F, E, false>), tiles, block, 0, s, x, grad_y, gg_x, T, A, grad_params)
-        switch (n_features) {
-        case 1: HS_SUM(1); break;
-        case 2: HS_SUM(2); break;
-        case 4: HS_SUM(4); break;
-        default: HS_SUM(8); break;
-        }
-#undef HS_SUM
+        dispatch_grid(n_features, interp, [&](auto f, auto i) {
+            if (gg_x)
+                hipLaunchKernelGGL((hs_sum_kernel<f(), E, true, i()>), tiles, block, 0, s, x, grad_y, gg_x, T, A, grad_params);
+            else
+                hipLaunchKernelGGL((hs_sum_kernel<f(), E, false, i()>), tiles, block, 0, s, x, grad_y, gg_x, T, A, grad_params);
+        });
         hipLaunchKernelGGL(hs_carry_kernel, dim3((unsigned)ceil_div64(p.n_tiles * n_features, 256), g), block, 0, s, T, A,
                            (int)n_features, grad_params);
     }
@@ -1077,14 +1144,14 @@ static int hashsort_table_grad(const char *name, const float *x, const E *grad_y
 }
 
 template <class E>
-static int hashgrid_bwd_sorted(const float *x, const float *params, const E *grad_y, int64_t n_points, int32_t n_levels,
-                               int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+static int hashgrid_bwd_sorted(int32_t interp, const float *x, const float *params, const E *grad_y, int64_t n_points,
+                               int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
                                const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
                                float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream)
 {
     if (!grad_params)
-        return hashgrid_bwd(x, params, grad_y, n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host,
-                            sizes_host, n_params, grad_params, grad_x, stream);
+        return hashgrid_bwd(interp, x, params, grad_y, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                            resolutions_host, sizes_host, n_params, grad_params, grad_x, stream);
     HashGridLevels T;
     int rc = hashgrid_table("hashgrid_bwd_sorted", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
                             resolutions_host, sizes_host, n_params, T);
@@ -1095,24 +1162,24 @@ static int hashgrid_bwd_sorted(const float *x, const float *params, const E *gra
     rc = hashsort_check("hashgrid_bwd_sorted", n_points, n_levels, scratch, scratch_bytes);
     if (rc != NFA_OK) return rc;
     if (grad_x) {
-        rc = hashgrid_bwd(x, params, grad_y, n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host,
-                          sizes_host, n_params, (float *)nullptr, grad_x, stream);
+        rc = hashgrid_bwd(interp, x, params, grad_y, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                          resolutions_host, sizes_host, n_params, (float *)nullptr, grad_x, stream);
         if (rc != NFA_OK) return rc;
     }
-    return hashsort_table_grad<E>("hashgrid_bwd_sorted", x, grad_y, nullptr, n_points, n_features, T, grad_params, scratch,
-                                  as_stream(stream));
+    return hashsort_table_grad<E>("hashgrid_bwd_sorted", interp, x, grad_y, nullptr, n_points, n_features, T, grad_params,
+                                  scratch, as_stream(stream));
 }
 
 template <class E>
-static int hashgrid_bwd_bwd_sorted(const float *x, const float *params, const E *grad_y, const float *grad_grad_x,
-                                   int64_t n_points, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
-                                   const float *scales_host, const int32_t *resolutions_host, const int32_t *sizes_host,
-                                   int64_t n_params, E *grad_grad_y, float *grad_params, float *grad_x, void *scratch,
-                                   int64_t scratch_bytes, nfa_stream_t stream)
+static int hashgrid_bwd_bwd_sorted(int32_t interp, const float *x, const float *params, const E *grad_y,
+                                   const float *grad_grad_x, int64_t n_points, int32_t n_levels, int32_t n_features,
+                                   int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                                   const int32_t *sizes_host, int64_t n_params, E *grad_grad_y, float *grad_params,
+                                   float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream)
 {
     if (!grad_params)
-        return hashgrid_bwd_bwd(x, params, grad_y, grad_grad_x, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
-                                resolutions_host, sizes_host, n_params, grad_grad_y, grad_params, grad_x, stream);
+        return hashgrid_bwd_bwd(interp, x, params, grad_y, grad_grad_x, n_points, n_levels, n_features, log2_hashmap_size,
+                                scales_host, resolutions_host, sizes_host, n_params, grad_grad_y, grad_params, grad_x, stream);
     HashGridLevels T;
     int rc = hashgrid_table("hashgrid_bwd_bwd_sorted", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
                             resolutions_host, sizes_host, n_params, T);
@@ -1125,12 +1192,13 @@ static int hashgrid_bwd_bwd_sorted(const float *x, const float *params, const E 
     rc = hashsort_check("hashgrid_bwd_bwd_sorted", n_points, n_levels, scratch, scratch_bytes);
     if (rc != NFA_OK) return rc;
     if (grad_grad_y || grad_x) {
-        rc = hashgrid_bwd_bwd(x, params, grad_y, grad_grad_x, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
-                              resolutions_host, sizes_host, n_params, grad_grad_y, (float *)nullptr, grad_x, stream);
+        rc = hashgrid_bwd_bwd(interp, x, params, grad_y, grad_grad_x, n_points, n_levels, n_features, log2_hashmap_size,
+                              scales_host, resolutions_host, sizes_host, n_params, grad_grad_y, (float *)nullptr, grad_x,
+                              stream);
         if (rc != NFA_OK) return rc;
     }
-    return hashsort_table_grad<E>("hashgrid_bwd_bwd_sorted", x, grad_y, grad_grad_x, n_points, n_features, T, grad_params,
-                                  scratch, as_stream(stream));
+    return hashsort_table_grad<E>("hashgrid_bwd_bwd_sorted", interp, x, grad_y, grad_grad_x, n_points, n_features, T,
+                                  grad_params, scratch, as_stream(stream));
 }
 
 }  // namespace nfa
@@ -1143,13 +1211,24 @@ using namespace nfa;
         NFA_REQUIRE(false, name ": elem must be NFA_ELEM_F32, NFA_ELEM_F16 or NFA_ELEM_BF16 (got %d)", (int)(elem)); \
     return rc
 
+int nfa_hashgrid_fwd_i(int32_t interp, int32_t elem, const float *x, const float *params, int64_t n_points, int32_t n_levels,
+                       int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                       const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, void *y,
+                       nfa_stream_t stream)
+{
+    if (check_interp("hashgrid_fwd", interp) != NFA_OK) return NFA_EINVAL;
+    ELEM_DISPATCH("hashgrid_fwd", elem, hashgrid_fwd(interp, x, params, n_points, n_levels, n_features, log2_hashmap_size,
+                                                     scales_host, resolutions_host, sizes_host, n_params, static_cast<E *>(y),
+                                                     stream));
+}
+
 int nfa_hashgrid_fwd_t(int32_t elem, const float *x, const float *params, int64_t n_points, int32_t n_levels,
                        int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
                        const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, void *y,
                        nfa_stream_t stream)
 {
-    ELEM_DISPATCH("hashgrid_fwd", elem, hashgrid_fwd(x, params, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
-                                                     resolutions_host, sizes_host, n_params, static_cast<E *>(y), stream));
+    return nfa_hashgrid_fwd_i(NFA_INTERP_LINEAR, elem, x, params, n_points, n_levels, n_features, log2_hashmap_size,
+                              scales_host, resolutions_host, sizes_host, n_params, y, stream);
 }
 
 int nfa_hashgrid_fwd(const float *x, const float *params, int64_t n_points, int32_t n_levels, int32_t n_features,
@@ -1160,14 +1239,24 @@ int nfa_hashgrid_fwd(const float *x, const float *params, int64_t n_points, int3
                               resolutions_host, sizes_host, n_params, y, stream);
 }
 
+int nfa_hashgrid_bwd_i(int32_t interp, int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points,
+                       int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                       const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
+                       float *grad_x, nfa_stream_t stream)
+{
+    if (check_interp("hashgrid_bwd", interp) != NFA_OK) return NFA_EINVAL;
+    ELEM_DISPATCH("hashgrid_bwd", elem, hashgrid_bwd(interp, x, params, static_cast<const E *>(grad_y), n_points, n_levels,
+                                                     n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host,
+                                                     n_params, grad_params, grad_x, stream));
+}
+
 int nfa_hashgrid_bwd_t(int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points,
                        int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
                        const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
                        float *grad_x, nfa_stream_t stream)
 {
-    ELEM_DISPATCH("hashgrid_bwd", elem, hashgrid_bwd(x, params, static_cast<const E *>(grad_y), n_points, n_levels, n_features,
-                                                     log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params,
-                                                     grad_params, grad_x, stream));
+    return nfa_hashgrid_bwd_i(NFA_INTERP_LINEAR, elem, x, params, grad_y, n_points, n_levels, n_features, log2_hashmap_size,
+                              scales_host, resolutions_host, sizes_host, n_params, grad_params, grad_x, stream);
 }
 
 int nfa_hashgrid_bwd(const float *x, const float *params, const float *grad_y, int64_t n_points, int32_t n_levels,
@@ -1179,15 +1268,27 @@ int nfa_hashgrid_bwd(const float *x, const float *params, const float *grad_y, i
                               resolutions_host, sizes_host, n_params, grad_params, grad_x, stream);
 }
 
+int nfa_hashgrid_bwd_bwd_i(int32_t interp, int32_t elem, const float *x, const float *params, const void *grad_y,
+                           const float *grad_grad_x, int64_t n_points, int32_t n_levels, int32_t n_features,
+                           int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                           const int32_t *sizes_host, int64_t n_params, void *grad_grad_y, float *grad_params, float *grad_x,
+                           nfa_stream_t stream)
+{
+    if (check_interp("hashgrid_bwd_bwd", interp) != NFA_OK) return NFA_EINVAL;
+    ELEM_DISPATCH("hashgrid_bwd_bwd", elem, hashgrid_bwd_bwd(interp, x, params, static_cast<const E *>(grad_y), grad_grad_x,
+                                                             n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                                                             resolutions_host, sizes_host, n_params,
+                                                             static_cast<E *>(grad_grad_y), grad_params, grad_x, stream));
+}
+
 int nfa_hashgrid_bwd_bwd_t(int32_t elem, const float *x, const float *params, const void *grad_y, const float *grad_grad_x,
                            int64_t n_points, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
                            const float *scales_host, const int32_t *resolutions_host, const int32_t *sizes_host,
                            int64_t n_params, void *grad_grad_y, float *grad_params, float *grad_x, nfa_stream_t stream)
 {
-    ELEM_DISPATCH("hashgrid_bwd_bwd", elem, hashgrid_bwd_bwd(x, params, static_cast<const E *>(grad_y), grad_grad_x, n_points,
-                                                             n_levels, n_features, log2_hashmap_size, scales_host,
-                                                             resolutions_host, sizes_host, n_params,
-                                                             static_cast<E *>(grad_grad_y), grad_params, grad_x, stream));
+    return nfa_hashgrid_bwd_bwd_i(NFA_INTERP_LINEAR, elem, x, params, grad_y, grad_grad_x, n_points, n_levels, n_features,
+                                  log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params, grad_grad_y,
+                                  grad_params, grad_x, stream);
 }
 
 int nfa_hashgrid_bwd_bwd(const float *x, const float *params, const float *grad_y, const float *grad_grad_x, int64_t n_points,
@@ -1230,15 +1331,40 @@ int64_t nfa_hashgrid_sorted_scratch_bytes(int64_t n_points, int32_t n_levels, in
     return p.scratch_bytes;
 }
 
+int nfa_hashgrid_bwd_sorted_i(int32_t interp, int32_t elem, const float *x, const float *params, const void *grad_y,
+                              int64_t n_points, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
+                              const float *scales_host, const int32_t *resolutions_host, const int32_t *sizes_host,
+                              int64_t n_params, float *grad_params, float *grad_x, void *scratch, int64_t scratch_bytes,
+                              nfa_stream_t stream)
+{
+    if (check_interp("hashgrid_bwd_sorted", interp) != NFA_OK) return NFA_EINVAL;
+    ELEM_DISPATCH("hashgrid_bwd_sorted", elem,
+                  hashgrid_bwd_sorted(interp, x, params, static_cast<const E *>(grad_y), n_points, n_levels, n_features,
+                                      log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params, grad_params,
+                                      grad_x, scratch, scratch_bytes, stream));
+}
+
 int nfa_hashgrid_bwd_sorted(int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points,
                             int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
                             const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
                             float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream)
 {
-    ELEM_DISPATCH("hashgrid_bwd_sorted", elem,
-                  hashgrid_bwd_sorted(x, params, static_cast<const E *>(grad_y), n_points, n_levels, n_features,
-                                      log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params, grad_params,
-                                      grad_x, scratch, scratch_bytes, stream));
+    return nfa_hashgrid_bwd_sorted_i(NFA_INTERP_LINEAR, elem, x, params, grad_y, n_points, n_levels, n_features,
+                                     log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params, grad_params,
+                                     grad_x, scratch, scratch_bytes, stream);
+}
+
+int nfa_hashgrid_bwd_bwd_sorted_i(int32_t interp, int32_t elem, const float *x, const float *params, const void *grad_y,
+                                  const float *grad_grad_x, int64_t n_points, int32_t n_levels, int32_t n_features,
+                                  int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                                  const int32_t *sizes_host, int64_t n_params, void *grad_grad_y, float *grad_params,
+                                  float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream)
+{
+    if (check_interp("hashgrid_bwd_bwd_sorted", interp) != NFA_OK) return NFA_EINVAL;
+    ELEM_DISPATCH("hashgrid_bwd_bwd_sorted", elem,
+                  hashgrid_bwd_bwd_sorted(interp, x, params, static_cast<const E *>(grad_y), grad_grad_x, n_points, n_levels,
+                                          n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params,
+                                          static_cast<E *>(grad_grad_y), grad_params, grad_x, scratch, scratch_bytes, stream));
 }
 
 int nfa_hashgrid_bwd_bwd_sorted(int32_t elem, const float *x, const float *params, const void *grad_y,
@@ -1247,8 +1373,7 @@ int nfa_hashgrid_bwd_bwd_sorted(int32_t elem, const float *x, const float *param
                                 const int32_t *sizes_host, int64_t n_params, void *grad_grad_y, float *grad_params,
                                 float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream)
 {
-    ELEM_DISPATCH("hashgrid_bwd_bwd_sorted", elem,
-                  hashgrid_bwd_bwd_sorted(x, params, static_cast<const E *>(grad_y), grad_grad_x, n_points, n_levels,
-                                          n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params,
-                                          static_cast<E *>(grad_grad_y), grad_params, grad_x, scratch, scratch_bytes, stream));
+    return nfa_hashgrid_bwd_bwd_sorted_i(NFA_INTERP_LINEAR, elem, x, params, grad_y, grad_grad_x, n_points, n_levels,
+                                         n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params,
+                                         grad_grad_y, grad_params, grad_x, scratch, scratch_bytes, stream);
 }

@@ -1,7 +1,7 @@
 """Input encodings of Instant-NGP radiance fields (native kernels: csrc/encoding.hip).
 
-``HashGridEncoding`` and ``SphericalHarmonicsEncoding`` stand for tiny-cuda-nn's ``HashGrid`` (3-D input, linear
-interpolation) and ``SphericalHarmonics`` encodings, the two encodings nerfacc's example radiance fields
+``HashGridEncoding`` and ``SphericalHarmonicsEncoding`` stand for tiny-cuda-nn's ``HashGrid`` (3-D input, linear or
+smoothstep interpolation) and ``SphericalHarmonics`` encodings, the two encodings nerfacc's example radiance fields
 (``examples/radiance_fields/ngp.py``: ``NGPRadianceField``, ``NGPDensityField``) are built on; the MLPs around them are
 plain ``torch.nn`` layers.  ``encoding_from_tcnn_config`` builds them from the config dicts those examples pass to tcnn.
 Parameter layout compatibility with tcnn checkpoints is not a goal.
@@ -74,8 +74,9 @@ class LevelTable:
         self.c_sizes = (ctypes.c_int32 * len(self.scales))(*self.sizes)
 
 
-def _hashgrid_torch(x: Tensor, params: Tensor, t: LevelTable, n_features: int) -> Tensor:
-    """The hash grid in torch, op for op as csrc/encoding.hip computes it (x [N, 3] and params in one float dtype)."""
+def _hashgrid_torch(x: Tensor, params: Tensor, t: LevelTable, n_features: int, interp: int = 0) -> Tensor:
+    """The hash grid in torch, op for op as csrc/encoding.hip computes it (x [N, 3] and params in one float dtype);
+    ``interp``: a ``B.INTERP_CODES`` value."""
     F = n_features
     table = params.view(-1, F)
     outs = []
@@ -83,6 +84,8 @@ def _hashgrid_torch(x: Tensor, params: Tensor, t: LevelTable, n_features: int) -
         p = x * t.scales[l] + 0.5   # (a float32 value: exact in x's dtype)
         fl = torch.floor(p)
         f = p - fl
+        if interp == B.INTERP_CODES["Smoothstep"]:
+            f = (f * f) * (3.0 - 2.0 * f)   # S(f) takes the fraction's place in the corner weights
         g = fl.detach().clamp(-2147483648.0, 2147483520.0).to(torch.int64) & _M32
         lvl = table[t.offsets[l]: t.offsets[l] + t.sizes[l]]
         size, res = t.sizes[l], t.resolutions[l]
@@ -129,9 +132,17 @@ def _resolve_out_dtype(out_dtype, x: Tensor) -> torch.dtype:
     return out_dtype
 
 
-def _entry(name: str, dtype: torch.dtype):
-    """(entry point, leading arguments): float32 calls the unsuffixed entry as ever, fp16 / bf16 the ``_t`` one."""
+def _entry(name: str, dtype: torch.dtype, interp: int = 0):
+    """(entry point, leading arguments): float32 calls the unsuffixed entry as ever, fp16 / bf16 the ``_t`` one, and an
+    interpolation other than Linear the ``_i`` one."""
+    if interp:
+        return name + "_i", (interp, B.ELEM_CODES[dtype])
     return (name, ()) if dtype == torch.float32 else (name + "_t", (B.ELEM_CODES[dtype],))
+
+
+def _sorted_entry(name: str, dtype: torch.dtype, interp: int = 0):
+    """The same for the ``_sorted`` entries, which always take the element code."""
+    return (name + "_i", (interp, B.ELEM_CODES[dtype])) if interp else (name, (B.ELEM_CODES[dtype],))
 
 
 SORTED_MAX_POINTS = (1 << 29) - 1   # nfa_hashgrid_*_sorted: the item id 8 n + c is 32 bits wide
@@ -162,7 +173,7 @@ class _HashGridFn(torch.autograd.Function):
         y = torch.empty(N, L * F, dtype=dtype, device=x.device)
         if N:
             with torch.cuda.device(x.device):
-                entry, elem = _entry("nfa_hashgrid_fwd", dtype)
+                entry, elem = _entry("nfa_hashgrid_fwd", dtype, enc.interp)
                 B.call(entry, *elem, B.ptr(x), B.ptr(params), N, L, F, t.log2_hashmap_size, t.c_scales, t.c_res,
                        t.c_sizes, params.numel(), B.ptr(y), B.stream())
         ctx.enc, ctx.dtype = enc, dtype
@@ -181,7 +192,7 @@ class _HashGridFn(torch.autograd.Function):
 
 class _HashGridBwdFn(torch.autograd.Function):
     """The hash grid's backward as a function ``(x, params, g_y) -> (g_x, g_params)``, so that ``g_x`` can be differentiated
-    again (``create_graph=True``: Eikonal terms, normals).  Its own backward is one ``nfa_hashgrid_bwd_bwd[_t]`` call."""
+    again (``create_graph=True``: Eikonal terms, normals).  Its own backward is one ``nfa_hashgrid_bwd_bwd[_t|_i]`` call."""
 
     @staticmethod
     def forward(ctx, x, params, g, enc: "HashGridEncoding", dtype: torch.dtype, need_x: bool, need_p: bool):
@@ -192,11 +203,12 @@ class _HashGridBwdFn(torch.autograd.Function):
             with torch.cuda.device(x.device):
                 if enc.deterministic and need_p:
                     scratch = _sorted_scratch(enc, x.shape[0], x.device)
-                    B.call("nfa_hashgrid_bwd_sorted", B.ELEM_CODES[dtype], B.ptr(x), B.ptr(params), B.ptr(g), x.shape[0], L, F,
+                    entry, lead = _sorted_entry("nfa_hashgrid_bwd_sorted", dtype, enc.interp)
+                    B.call(entry, *lead, B.ptr(x), B.ptr(params), B.ptr(g), x.shape[0], L, F,
                            t.log2_hashmap_size, t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(g_p), B.ptr(g_x),
                            B.ptr(scratch), scratch.numel(), B.stream())
                 else:
-                    entry, elem = _entry("nfa_hashgrid_bwd", dtype)
+                    entry, elem = _entry("nfa_hashgrid_bwd", dtype, enc.interp)
                     B.call(entry, *elem, B.ptr(x), B.ptr(params), B.ptr(g), x.shape[0], L, F, t.log2_hashmap_size,
                            t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(g_p), B.ptr(g_x), B.stream())
         ctx.enc, ctx.dtype = enc, dtype
@@ -224,11 +236,12 @@ class _HashGridBwdFn(torch.autograd.Function):
             with torch.cuda.device(x.device):
                 if enc.deterministic and need_p:
                     scratch = _sorted_scratch(enc, x.shape[0], x.device)
-                    B.call("nfa_hashgrid_bwd_bwd_sorted", B.ELEM_CODES[ctx.dtype], B.ptr(x), B.ptr(params), B.ptr(g), B.ptr(v),
+                    entry, lead = _sorted_entry("nfa_hashgrid_bwd_bwd_sorted", ctx.dtype, enc.interp)
+                    B.call(entry, *lead, B.ptr(x), B.ptr(params), B.ptr(g), B.ptr(v),
                            x.shape[0], L, F, t.log2_hashmap_size, t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(gg_y),
                            B.ptr(g2_p), B.ptr(x2), B.ptr(scratch), scratch.numel(), B.stream())
                 else:
-                    entry, elem = _entry("nfa_hashgrid_bwd_bwd", ctx.dtype)
+                    entry, elem = _entry("nfa_hashgrid_bwd_bwd", ctx.dtype, enc.interp)
                     B.call(entry, *elem, B.ptr(x), B.ptr(params), B.ptr(g), B.ptr(v), x.shape[0], L, F, t.log2_hashmap_size,
                            t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(gg_y), B.ptr(g2_p), B.ptr(x2), B.stream())
         return x2, g2_p, gg_y, None, None, None, None
@@ -273,8 +286,8 @@ def _autocast_off(x: Tensor):
 
 
 class HashGridEncoding(nn.Module):
-    """tiny-cuda-nn's ``HashGrid`` encoding with 3-D input and linear interpolation: ``forward(x[..., 3]) -> [...,
-    n_levels * n_features_per_level]``, level-major (output ``l * F + j`` is feature ``j`` of level ``l``).
+    """tiny-cuda-nn's ``HashGrid`` encoding with 3-D input and linear or smoothstep interpolation: ``forward(x[..., 3]) ->
+    [..., n_levels * n_features_per_level]``, level-major (output ``l * F + j`` is feature ``j`` of level ``l``).
 
     ``params`` is one flat float32 table of ``sum(sizes) * F`` values laid out ``[level][entry][feature]``, initialised
     uniform in +-1e-4.  ``scales``, ``resolutions``, ``offsets`` and ``sizes`` are the per-level constants
@@ -282,8 +295,9 @@ class HashGridEncoding(nn.Module):
     inputs are unspecified.  Differentiable w.r.t. ``params`` and ``x``, and twice where the first derivative taken is the
     one w.r.t. ``x``: ``torch.autograd.grad(y, x, g, create_graph=True)`` gives a ``dL/dx`` that can be differentiated
     w.r.t. ``params``, ``x`` and ``g`` (one native pass; what an Eikonal term, analytic normals or any regulariser of the
-    field's spatial gradient needs).  With linear interpolation the second derivative w.r.t. ``x`` has mixed partials only,
-    and ``floor`` contributes nothing.  Differentiating ``dL/dparams`` again raises ``NotImplementedError``; there is no
+    field's spatial gradient needs).  With linear interpolation the second derivative w.r.t. ``x`` has mixed partials only;
+    with ``interpolation="Smoothstep"`` it has the pure second partials along each axis as well.  ``floor`` contributes
+    nothing on either.  Differentiating ``dL/dparams`` again raises ``NotImplementedError``; there is no
     third order.
 
     ``out_dtype``: ``None`` (float32 output, also under autocast), ``torch.float16`` / ``torch.bfloat16`` (the float32
@@ -298,14 +312,26 @@ class HashGridEncoding(nn.Module):
     2^29 - 1 points per call (``ValueError`` above).  Every other result is the same on both settings.  The torch path
     (CPU tensors, other dtypes) ignores the flag: its reproducibility is torch's own (``index`` backward, see
     ``torch.use_deterministic_algorithms``).
+
+    ``interpolation``: ``"Linear"`` or ``"Smoothstep"`` (case-insensitive; tcnn's ``"interpolation"``).  Smoothstep forms the
+    corner weights from ``S(f) = f^2 (3 - 2 f)`` instead of the cell fraction ``f``: the encoding becomes C^1 (``dL/dx`` is
+    continuous, and zero along an axis on that axis' cell faces, so analytic normals are not faceted) and its second
+    derivative gains the curvature along each axis.  All three native passes, both table-gradient modes and every
+    ``out_dtype`` take it; parameters, ``state_dict``, the level table and the initialisation do not depend on it.
+    tcnn's ``"Nearest"`` is not provided.
     """
 
     def __init__(self, n_input_dims: int = 3, n_levels: int = 16, n_features_per_level: int = 2,
                  log2_hashmap_size: int = 19, base_resolution: float = 16, per_level_scale: float = 2.0, out_dtype=None,
-                 deterministic: bool = False):
+                 deterministic: bool = False, interpolation: str = "Linear"):
         super().__init__()
         self.out_dtype = _check_out_dtype(out_dtype)
         self.deterministic = bool(deterministic)
+        names = {k.lower(): k for k in B.INTERP_CODES}
+        if not isinstance(interpolation, str) or interpolation.lower() not in names:
+            raise ValueError(f"HashGridEncoding: interpolation must be 'Linear' or 'Smoothstep' (got {interpolation!r})")
+        self.interpolation = names[interpolation.lower()]
+        self.interp = B.INTERP_CODES[self.interpolation]   # NFA_INTERP_*
         if n_input_dims != 3:
             raise ValueError(f"HashGridEncoding: only 3 input dimensions are supported (got {n_input_dims})")
         if n_features_per_level not in (1, 2, 4, 8):
@@ -344,7 +370,7 @@ class HashGridEncoding(nn.Module):
                 y = _HashGridFn.apply(x2.contiguous(), p, self, out)
             else:
                 dt = torch.promote_types(x2.dtype, p.dtype)
-                y = _hashgrid_torch(x2.to(dt), p.to(dt), self.table, self.n_features_per_level)
+                y = _hashgrid_torch(x2.to(dt), p.to(dt), self.table, self.n_features_per_level, self.interp)
                 if self.out_dtype is not None:
                     y = y.to(out)
             return y.view(*lead, self.n_output_dims)
@@ -353,7 +379,8 @@ class HashGridEncoding(nn.Module):
         return (f"n_levels={self.n_levels}, n_features_per_level={self.n_features_per_level}, "
                 f"log2_hashmap_size={self.log2_hashmap_size}, base_resolution={self.base_resolution}, "
                 f"per_level_scale={self.per_level_scale}" + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else "")
-                + (", deterministic=True" if self.deterministic else ""))
+                + (", deterministic=True" if self.deterministic else "")
+                + (f", interpolation={self.interpolation}" if self.interp else ""))
 
 
 # Instant-NGP's real spherical-harmonics basis (tcnn's constants)
@@ -416,7 +443,8 @@ class SphericalHarmonicsEncoding(nn.Module):
 def encoding_from_tcnn_config(n_input_dims: int, config: dict, out_dtype=None, deterministic: bool = False) -> nn.Module:
     """The encoding a tiny-cuda-nn encoding config describes: ``HashGrid`` (linear interpolation), ``SphericalHarmonics``,
     or ``Composite`` with ONE nested encoding over all input dimensions (as ``ngp.py`` builds its direction encoding).
-    Anything else raises ``ValueError``.  ``out_dtype`` is handed to the encoding built, ``deterministic`` to a hash grid."""
+    Anything else raises ``ValueError``.  ``out_dtype`` is handed to the encoding built, ``deterministic`` to a hash grid.
+    ``"interpolation": "Smoothstep"`` is still refused here; build it with ``HashGridEncoding(..., interpolation="Smoothstep")``."""
     if not isinstance(config, dict) or "otype" not in config:
         raise ValueError(f"not a tcnn encoding config: {config!r}")
     otype = config["otype"]

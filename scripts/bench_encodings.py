@@ -24,7 +24,13 @@ second-order pass alone (the step minus the first-order part).
 times the reproducible table gradient (HashGridEncoding(deterministic=True): nfa_hashgrid_bwd_sorted, _bwd_bwd_sorted) next
 to the atomic one of the same build: the backward towards the table (zeroing included) on uniform and occgrid points, or the
 Eikonal-shaped step.  The two alternate window by window; each figure is the median over the windows, `*_spread` the
-(min, max) over them.  `scratch_bytes` is what one sorted call allocates."""
+(min, max) over them.  `scratch_bytes` is what one sorted call allocates.
+    python scripts/bench_encodings.py --interpolation Smoothstep [--sizes 20] [--reps 10] [--windows 7]
+times the three native passes of a HashGridEncoding(interpolation=...) next to the Linear grid on the same table, uniform
+points: the forward, the backward (table gradient and dL/dx; atomic and deterministic=True) and the second-order pass alone (the
+backward of a dL/dx built with create_graph; atomic and sorted).  All take turns window by window in one process; `*_us` is
+the median over the windows, `*_spread` the (min, max), `*_ratio` the named grid's median over Linear's.  With
+`--interpolation Linear` the second grid is Linear again: the ratios are then the spread of a pass against itself."""
 import argparse
 import json
 import math
@@ -147,6 +153,53 @@ def deterministic_rows(args, dev, dtype):
                 del ys
 
 
+def interpolation_rows(args, dev):
+    sizes = [1 << int(s) for s in args.sizes.split(",")]
+    torch.manual_seed(0)
+    uni = torch.rand(max(sizes), 3, device=dev)
+    other = "linear_again" if args.interpolation.lower() == "linear" else args.interpolation.lower()
+    for cname, cfg in CONFIGS.items():
+        torch.manual_seed(0)
+        base = HashGridEncoding(3, **cfg).to(dev)
+        with torch.no_grad():
+            base.params.uniform_(-1, 1)
+        L, F = base.n_levels, base.n_features_per_level
+
+        def grid(interpolation, deterministic):
+            enc = HashGridEncoding(3, deterministic=deterministic, interpolation=interpolation, **cfg)
+            enc.params = base.params
+            return enc
+
+        for N in sizes:
+            x = uni[:N].clone().requires_grad_(True)
+            g = torch.randn(N, L * F, device=dev, requires_grad=True)
+            v = torch.randn(N, 3, device=dev)
+
+            def fwd(enc):
+                with torch.no_grad():
+                    enc(x)
+
+            def bwd(out, grad):   # out = y: the backward; out = dL/dx built with create_graph: the second-order pass alone
+                base.params.grad = x.grad = g.grad = None
+                torch.autograd.backward(out, grad, retain_graph=True)
+
+            fns = {}
+            for tag, name in (("linear", "Linear"), (other, args.interpolation)):
+                for mode, enc in (("atomic", grid(name, False)), ("sorted", grid(name, True))):
+                    if mode == "atomic":
+                        fns[f"{tag}_fwd"] = lambda enc=enc: fwd(enc)
+                    y = enc(x)
+                    (g_x,) = torch.autograd.grad(enc(x), x, g, create_graph=True)
+                    fns[f"{tag}_bwd_{mode}"] = lambda y=y: bwd(y, g.detach())
+                    fns[f"{tag}_bwd2_{mode}"] = lambda g_x=g_x: bwd(g_x, v)
+            row = dict(config=cname, interpolation=args.interpolation, N=N, L=L, F=F)
+            row.update(alternating_stats(fns, args.reps, args.windows))
+            for k in ("fwd", "bwd_atomic", "bwd_sorted", "bwd2_atomic", "bwd2_sorted"):
+                row[k + "_ratio"] = row[f"{other}_{k}_us"] / row[f"linear_{k}_us"]
+            print(json.dumps(row), flush=True)
+            del fns
+
+
 def half_rows(args, dev, dtype):
     sizes = [1 << int(s) for s in args.sizes.split(",")]
     torch.manual_seed(0)
@@ -245,9 +298,12 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--eikonal", action="store_true")
     ap.add_argument("--deterministic", action="store_true")
+    ap.add_argument("--interpolation", default=None, help="time this interpolation's passes against Linear's")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     B.load()
+    if args.interpolation is not None:
+        return interpolation_rows(args, dev)
     if args.deterministic:
         return deterministic_rows(args, dev, getattr(torch, args.dtype))
     if args.eikonal:
