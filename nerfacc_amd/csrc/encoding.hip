@@ -142,19 +142,23 @@ __device__ __forceinline__ Cell locate(const float *__restrict__ xp, float scale
     return c;
 }
 
-__device__ __forceinline__ uint32_t corner_index(const Cell &c, int corner, bool hashed, uint32_t res, uint32_t size)
+// A level's constants, read once out of the kernarg table
+struct LevelRef {
+    float scale;
+    uint32_t res, size, offset;
+    bool hashed;
+    __device__ __forceinline__ LevelRef(const HashGridLevels &T, int l)
+        : scale(T.scale[l]), res(T.res[l]), size(T.size[l]), offset(T.offset[l]), hashed((T.hashed >> l) & 1u) {}
+};
+
+__device__ __forceinline__ uint32_t corner_index(const Cell &c, int corner, const LevelRef &L)
 {
     const uint32_t q0 = c.g[0] + (corner & 1), q1 = c.g[1] + ((corner >> 1) & 1), q2 = c.g[2] + ((corner >> 2) & 1);
-    if (hashed) return (q0 ^ (q1 * 2654435761u) ^ (q2 * 805459861u)) & (size - 1u);
-    return (q0 + q1 * res + q2 * (res * res)) % size;
+    if (L.hashed) return (q0 ^ (q1 * 2654435761u) ^ (q2 * 805459861u)) & (L.size - 1u);
+    return (q0 + q1 * L.res + q2 * (L.res * L.res)) % L.size;
 }
 
-__device__ __forceinline__ float corner_factor(const Cell &c, int corner, int d)
-{
-    return ((corner >> d) & 1) ? c.f[d] : 1.0f - c.f[d];
-}
-
-// Smoothstep (header): the cell's fractions become S_d, so that corner_factor() gives w_d; d1 = S', d2 = S''
+// Smoothstep (header): the cell's fractions become S_d, so that Corner gives w_d; d1 = S', d2 = S''
 __device__ __forceinline__ void smoothstep(Cell &c, float *d1, float *d2)
 {
 #pragma unroll
@@ -166,14 +170,56 @@ __device__ __forceinline__ void smoothstep(Cell &c, float *d1, float *d2)
     }
 }
 
-// (point, level) of this lane; false for the idle lanes of a wave
-__device__ __forceinline__ bool lane_item(const HashGridLevels &T, int64_t wave, int64_t n_points, int64_t &n, int &l)
+// The terms of one corner (header).  This is the one place where a table-gradient coefficient is written down: the atomic
+// kernels and hs_term of the sorted path both take it from here, so each sorted term is the float32 value the atomic pass adds.
+struct Corner {
+    int bits;
+    float w[3];   // w_d = (c_d ? f_d : 1 - f_d), f_d being S_d under Smoothstep
+    __device__ __forceinline__ Corner(const Cell &c, int corner) : bits(corner)
+    {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) w[d] = ((corner >> d) & 1) ? c.f[d] : 1.0f - c.f[d];
+    }
+    // u_d = (c_d ? v_d : -v_d); Smoothstep: v holds v_d * S'_d, formed once per (point, level)
+    __device__ __forceinline__ void signed_v(const float *v, float *u) const
+    {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) u[d] = ((bits >> d) & 1) ? v[d] : -v[d];
+    }
+    __device__ __forceinline__ float first_order() const { return (w[0] * w[1]) * w[2]; }                  // w_c
+    __device__ __forceinline__ float second_order(const float *u, float s) const                             // a_c
+    {
+        return ((u[0] * (w[1] * w[2]) + u[1] * (w[0] * w[2])) + u[2] * (w[0] * w[1])) * s;
+    }
+    // dx_d = (c_d ? dx_d + t_d : dx_d - t_d)
+    __device__ __forceinline__ void accumulate(float *dx, float t0, float t1, float t2) const
+    {
+        dx[0] = (bits & 1) ? dx[0] + t0 : dx[0] - t0;
+        dx[1] = (bits & 2) ? dx[1] + t1 : dx[1] - t1;
+        dx[2] = (bits & 4) ? dx[2] + t2 : dx[2] - t2;
+    }
+};
+
+// A point's F values of a level (piece = n * n_levels + l) from / as floats: float as one FVec<F>, halves as 2 F bytes
+template <int F, class E>
+__device__ __forceinline__ FVec<F> load_piece(const E *__restrict__ p, int64_t piece)
 {
-    const int lane = (int)(threadIdx.x & 63);
-    const int p = lane / T.n_levels;
-    l = lane - p * T.n_levels;
-    n = wave * T.pts_per_wave + p;
-    return p < T.pts_per_wave && n < n_points;
+    FVec<F> v;
+    if constexpr (std::is_same<E, float>::value) v = reinterpret_cast<const FVec<F> *>(p)[piece];
+    else load_elems<F>(p + piece * F, v.v);
+    return v;
+}
+template <int F, class E>
+__device__ __forceinline__ void store_piece(E *__restrict__ p, int64_t piece, const float *v)
+{
+    if constexpr (std::is_same<E, float>::value) {
+        FVec<F> out;
+#pragma unroll
+        for (int j = 0; j < F; ++j) out.v[j] = v[j];
+        reinterpret_cast<FVec<F> *>(p)[piece] = out;
+    } else {
+        store_elems<F>(p + piece * F, v);
+    }
 }
 
 // Forward: one level per workgroup row (blockIdx.y), one lane per point.  A wave's 64 points read one level's table, which
@@ -185,13 +231,11 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const float *__restri
                                                            int64_t n_points, const HashGridLevels T, E *__restrict__ y)
 {
     const int l = (int)blockIdx.y;
-    const bool hashed = (T.hashed >> l) & 1u;
-    const uint32_t res = T.res[l], size = T.size[l];
-    const float scale = T.scale[l];
-    const FVec<F> *tab = reinterpret_cast<const FVec<F> *>(params) + T.offset[l];
+    const LevelRef L(T, l);
+    const FVec<F> *tab = reinterpret_cast<const FVec<F> *>(params) + L.offset;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < n_points; n += stride) {
-        Cell c = locate(x + n * 3, scale);
+        Cell c = locate(x + n * 3, L.scale);
         if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
             float d1[3], d2[3];
             smoothstep(c, d1, d2);
@@ -201,21 +245,51 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const float *__restri
         for (int j = 0; j < F; ++j) acc[j] = 0.0f;
 #pragma unroll
         for (int corner = 0; corner < 8; ++corner) {
-            const FVec<F> v = tab[corner_index(c, corner, hashed, res, size)];
-            const float wc = (corner_factor(c, corner, 0) * corner_factor(c, corner, 1)) * corner_factor(c, corner, 2);
+            const FVec<F> v = tab[corner_index(c, corner, L)];
+            const float wc = Corner(c, corner).first_order();
 #pragma unroll
             for (int j = 0; j < F; ++j) acc[j] = acc[j] + wc * v.v[j];
         }
-        if constexpr (std::is_same<E, float>::value) {
-            FVec<F> out;
-#pragma unroll
-            for (int j = 0; j < F; ++j) out.v[j] = acc[j];
-            reinterpret_cast<FVec<F> *>(y)[n * T.n_levels + l] = out;
-        } else {
-            store_elems<F>(y + (n * T.n_levels + l) * F, acc);
-        }
+        store_piece<F>(y, n * T.n_levels + l, acc);
     }
 }
+
+// The wave loop of the two (point, level) kernels and the (point, level) of this lane in it: a wave covers 64 / L points x
+// all L levels (64 mod L lanes idle).  The dL/dx shares go to sum_levels() by value: handed over as a pointer to the
+// kernel's array they cost the second-order kernels 4-6 VGPRs and a wave per SIMD.
+struct LaneItems {
+    int64_t w, n_waves, wave_stride, n_points, n;
+    int n_levels, pts_per_wave, l;
+    bool active;   // false for the idle lanes of a wave
+    __device__ __forceinline__ LaneItems(const HashGridLevels &T, int64_t n_points_)
+        : w(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / 64), n_waves(ceil_div64(n_points_, T.pts_per_wave)),
+          wave_stride((int64_t)gridDim.x * (blockDim.x / 64)), n_points(n_points_), n_levels(T.n_levels),
+          pts_per_wave(T.pts_per_wave) { item(); }
+    __device__ __forceinline__ void item()
+    {
+        const int lane = (int)(threadIdx.x & 63);
+        const int p = lane / n_levels;
+        l = lane - p * n_levels;
+        n = w * pts_per_wave + p;
+        active = p < pts_per_wave && n < n_points;
+    }
+    __device__ __forceinline__ bool more() const { return w < n_waves; }
+    __device__ __forceinline__ void next() { w += wave_stride; item(); }
+    // dx summed over the point's L lanes in level order; the level-0 lane writes (call under a wave-uniform branch)
+    __device__ __forceinline__ void sum_levels(float d0, float d1, float d2, float *__restrict__ g_x) const
+    {
+        const int first = (int)(threadIdx.x & 63) - l;
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+        for (int k = 0; k < n_levels; ++k) {
+            const int src = min(first + k, 63);
+            const float v0 = __shfl(d0, src, 64), v1 = __shfl(d1, src, 64), v2 = __shfl(d2, src, 64);
+            s0 = k == 0 ? v0 : s0 + v0; s1 = k == 0 ? v1 : s1 + v1; s2 = k == 0 ? v2 : s2 + v2;
+        }
+        if (active && l == 0) {
+            g_x[n * 3 + 0] = s0; g_x[n * 3 + 1] = s1; g_x[n * 3 + 2] = s2;
+        }
+    }
+};
 
 template <int F, class E, int I>
 __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restrict__ x, const float *__restrict__ params,
@@ -223,28 +297,22 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restri
                                                            const HashGridLevels T, float *__restrict__ g_params,
                                                            float *__restrict__ g_x)
 {
-    const int64_t n_waves = ceil_div64(n_points, T.pts_per_wave);
-    const int64_t wave_stride = (int64_t)gridDim.x * (blockDim.x / 64);
-    for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / 64; w < n_waves; w += wave_stride) {
-        int64_t n;
-        int l;
-        const bool active = lane_item(T, w, n_points, n, l);
+    for (LaneItems it(T, n_points); it.more(); it.next()) {
         float dx[3] = {0.0f, 0.0f, 0.0f};
-        if (active) {
-            Cell c = locate(x + n * 3, T.scale[l]);
+        if (it.active) {
+            const int64_t n = it.n;
+            const int l = it.l;
+            const LevelRef L(T, l);
+            Cell c = locate(x + n * 3, L.scale);
             float d1[3], d2[3];
             if constexpr (I == NFA_INTERP_SMOOTHSTEP) smoothstep(c, d1, d2);
-            const bool hashed = (T.hashed >> l) & 1u;
-            const uint32_t res = T.res[l], size = T.size[l];
-            FVec<F> g;
-            if constexpr (std::is_same<E, float>::value) g = reinterpret_cast<const FVec<F> *>(g_y)[n * T.n_levels + l];
-            else load_elems<F>(g_y + (n * T.n_levels + l) * F, g.v);
-            const uint32_t base = T.offset[l];
+            const FVec<F> g = load_piece<F>(g_y, n * T.n_levels + l);
 #pragma unroll
             for (int corner = 0; corner < 8; ++corner) {
-                const uint32_t e = base + corner_index(c, corner, hashed, res, size);
+                const uint32_t e = L.offset + corner_index(c, corner, L);
+                const Corner k(c, corner);
                 if (g_params) {
-                    const float wc = (corner_factor(c, corner, 0) * corner_factor(c, corner, 1)) * corner_factor(c, corner, 2);
+                    const float wc = k.first_order();
                     float *dst = g_params + (size_t)e * F;
 #pragma unroll
                     for (int j = 0; j < F; ++j) unsafeAtomicAdd(dst + j, wc * g.v[j]);
@@ -254,16 +322,11 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restri
                     float dot = 0.0f;
 #pragma unroll
                     for (int j = 0; j < F; ++j) dot = dot + g.v[j] * v.v[j];
-                    const float f0 = corner_factor(c, corner, 0), f1 = corner_factor(c, corner, 1),
-                                f2 = corner_factor(c, corner, 2);
-                    const float t0 = (f1 * f2) * dot, t1 = (f0 * f2) * dot, t2 = (f0 * f1) * dot;
-                    dx[0] = (corner & 1) ? dx[0] + t0 : dx[0] - t0;
-                    dx[1] = (corner & 2) ? dx[1] + t1 : dx[1] - t1;
-                    dx[2] = (corner & 4) ? dx[2] + t2 : dx[2] - t2;
+                    k.accumulate(dx, (k.w[1] * k.w[2]) * dot, (k.w[0] * k.w[2]) * dot, (k.w[0] * k.w[1]) * dot);
                 }
             }
             if (g_x) {
-                const float s = T.scale[l];
+                const float s = L.scale;
                 if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
                     dx[0] = (dx[0] * d1[0]) * s; dx[1] = (dx[1] * d1[1]) * s; dx[2] = (dx[2] * d1[2]) * s;
                 } else {
@@ -271,25 +334,7 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restri
                 }
             }
         }
-        if (g_x) {
-            // sum over the point's L lanes in level order; the level-0 lane writes (wave-uniform branch)
-            const int lane = (int)(threadIdx.x & 63);
-            const int first = lane - l;
-            float s[3] = {0.0f, 0.0f, 0.0f};
-            for (int k = 0; k < T.n_levels; ++k) {
-                const int src = min(first + k, 63);
-#pragma unroll
-                for (int d = 0; d < 3; ++d) {
-                    const float v = __shfl(dx[d], src, 64);
-                    s[d] = k == 0 ? v : s[d] + v;
-                }
-            }
-            if (active && l == 0) {
-                g_x[n * 3 + 0] = s[0];
-                g_x[n * 3 + 1] = s[1];
-                g_x[n * 3 + 2] = s[2];
-            }
-        }
+        if (g_x) it.sum_levels(dx[0], dx[1], dx[2], g_x);
     }
 }
 
@@ -302,41 +347,36 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_bwd_kernel(const float *__re
                                                                E *__restrict__ gg_y, float *__restrict__ g_params,
                                                                float *__restrict__ g_x)
 {
-    const int64_t n_waves = ceil_div64(n_points, T.pts_per_wave);
-    const int64_t wave_stride = (int64_t)gridDim.x * (blockDim.x / 64);
-    for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / 64; w < n_waves; w += wave_stride) {
-        int64_t n;
-        int l;
-        const bool active = lane_item(T, w, n_points, n, l);
+    for (LaneItems it(T, n_points); it.more(); it.next()) {
         float dx[3] = {0.0f, 0.0f, 0.0f};
-        if (active) {
-            const float s = T.scale[l];
+        if (it.active) {
+            const int64_t n = it.n;
+            const int l = it.l;
+            const LevelRef L(T, l);
+            const float s = L.scale;
             Cell c = locate(x + n * 3, s);
-            const bool hashed = (T.hashed >> l) & 1u;
-            const uint32_t res = T.res[l], size = T.size[l];
-            float v0 = gg_x[n * 3 + 0], v1 = gg_x[n * 3 + 1], v2 = gg_x[n * 3 + 2];
-            float d1[3], p0, p1, p2;   // Smoothstep: S'_d, v_d * S''_d; v_d becomes v_d * S'_d
+            float v[3] = {gg_x[n * 3 + 0], gg_x[n * 3 + 1], gg_x[n * 3 + 2]};
+            float d1[3], p[3];   // Smoothstep: S'_d, v_d * S''_d; v_d becomes v_d * S'_d
             if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
                 float d2[3];
                 smoothstep(c, d1, d2);
-                p0 = v0 * d2[0]; p1 = v1 * d2[1]; p2 = v2 * d2[2];
-                v0 = v0 * d1[0]; v1 = v1 * d1[1]; v2 = v2 * d1[2];
+                p[0] = v[0] * d2[0]; p[1] = v[1] * d2[1]; p[2] = v[2] * d2[2];
+                v[0] = v[0] * d1[0]; v[1] = v[1] * d1[1]; v[2] = v[2] * d1[2];
             }
+            const int64_t piece = n * T.n_levels + l;
             FVec<F> g = {};
-            if (g_params || g_x) {
-                if constexpr (std::is_same<E, float>::value) g = reinterpret_cast<const FVec<F> *>(g_y)[n * T.n_levels + l];
-                else load_elems<F>(g_y + (n * T.n_levels + l) * F, g.v);
-            }
+            if (g_params || g_x) g = load_piece<F>(g_y, piece);
             float acc[F];
 #pragma unroll
             for (int j = 0; j < F; ++j) acc[j] = 0.0f;
-            const uint32_t base = T.offset[l];
 #pragma unroll
             for (int corner = 0; corner < 8; ++corner) {
-                const uint32_t e = base + corner_index(c, corner, hashed, res, size);
-                const float w0 = corner_factor(c, corner, 0), w1 = corner_factor(c, corner, 1), w2 = corner_factor(c, corner, 2);
-                const float u0 = (corner & 1) ? v0 : -v0, u1 = (corner & 2) ? v1 : -v1, u2 = (corner & 4) ? v2 : -v2;
-                const float a = ((u0 * (w1 * w2) + u1 * (w0 * w2)) + u2 * (w0 * w1)) * s;
+                const uint32_t e = L.offset + corner_index(c, corner, L);
+                const Corner k(c, corner);
+                const float *w = k.w;
+                float u[3];
+                k.signed_v(v, u);
+                const float a = k.second_order(u, s);
                 if (g_params) {
                     float *dst = g_params + (size_t)e * F;
 #pragma unroll
@@ -350,53 +390,23 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_bwd_kernel(const float *__re
                         float dot = 0.0f;
 #pragma unroll
                         for (int j = 0; j < F; ++j) dot = dot + g.v[j] * t.v[j];
-                        float t0, t1, t2;
                         if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
-                            t0 = (d1[0] * (u1 * w2 + u2 * w1) + p0 * (w1 * w2)) * dot;
-                            t1 = (d1[1] * (u0 * w2 + u2 * w0) + p1 * (w0 * w2)) * dot;
-                            t2 = (d1[2] * (u0 * w1 + u1 * w0) + p2 * (w0 * w1)) * dot;
+                            k.accumulate(dx, (d1[0] * (u[1] * w[2] + u[2] * w[1]) + p[0] * (w[1] * w[2])) * dot,
+                                         (d1[1] * (u[0] * w[2] + u[2] * w[0]) + p[1] * (w[0] * w[2])) * dot,
+                                         (d1[2] * (u[0] * w[1] + u[1] * w[0]) + p[2] * (w[0] * w[1])) * dot);
                         } else {
-                            t0 = (u1 * w2 + u2 * w1) * dot; t1 = (u0 * w2 + u2 * w0) * dot; t2 = (u0 * w1 + u1 * w0) * dot;
+                            k.accumulate(dx, (u[1] * w[2] + u[2] * w[1]) * dot, (u[0] * w[2] + u[2] * w[0]) * dot,
+                                         (u[0] * w[1] + u[1] * w[0]) * dot);
                         }
-                        dx[0] = (corner & 1) ? dx[0] + t0 : dx[0] - t0;
-                        dx[1] = (corner & 2) ? dx[1] + t1 : dx[1] - t1;
-                        dx[2] = (corner & 4) ? dx[2] + t2 : dx[2] - t2;
                     }
                 }
             }
-            if (gg_y) {
-                if constexpr (std::is_same<E, float>::value) {
-                    FVec<F> out;
-#pragma unroll
-                    for (int j = 0; j < F; ++j) out.v[j] = acc[j];
-                    reinterpret_cast<FVec<F> *>(gg_y)[n * T.n_levels + l] = out;
-                } else {
-                    store_elems<F>(gg_y + (n * T.n_levels + l) * F, acc);
-                }
-            }
+            if (gg_y) store_piece<F>(gg_y, piece, acc);
             if (g_x) {
                 dx[0] = (dx[0] * s) * s; dx[1] = (dx[1] * s) * s; dx[2] = (dx[2] * s) * s;
             }
         }
-        if (g_x) {
-            // sum over the point's L lanes in level order; the level-0 lane writes (wave-uniform branch)
-            const int lane = (int)(threadIdx.x & 63);
-            const int first = lane - l;
-            float sum[3] = {0.0f, 0.0f, 0.0f};
-            for (int k = 0; k < T.n_levels; ++k) {
-                const int src = min(first + k, 63);
-#pragma unroll
-                for (int d = 0; d < 3; ++d) {
-                    const float v = __shfl(dx[d], src, 64);
-                    sum[d] = k == 0 ? v : sum[d] + v;
-                }
-            }
-            if (active && l == 0) {
-                g_x[n * 3 + 0] = sum[0];
-                g_x[n * 3 + 1] = sum[1];
-                g_x[n * 3 + 2] = sum[2];
-            }
-        }
+        if (g_x) it.sum_levels(dx[0], dx[1], dx[2], g_x);
     }
 }
 
@@ -566,38 +576,45 @@ __global__ __launch_bounds__(256) void sh_bwd_kernel(const float *__restrict__ d
 }
 
 // ---------------------------------------------------------------- argument checks
-static int hashgrid_table(const char *name, int64_t n_points, int32_t n_levels, int32_t n_features,
-                          int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
-                          const int32_t *sizes_host, int64_t n_params, HashGridLevels &T)
+// The grid description of a call, filled at the extern "C" boundary
+struct GridArgs {
+    int64_t n_points;
+    int32_t n_levels, n_features, log2_hashmap_size;
+    const float *scales_host;
+    const int32_t *resolutions_host, *sizes_host;
+    int64_t n_params;
+};
+
+static int hashgrid_table(const char *name, const GridArgs &G, HashGridLevels &T)
 {
-    NFA_REQUIRE(n_points >= 0 && n_params >= 0, "%s: negative size", name);
-    NFA_REQUIRE(n_features == 1 || n_features == 2 || n_features == 4 || n_features == 8,
-                "%s: n_features must be 1, 2, 4 or 8 (got %d)", name, n_features);
-    NFA_REQUIRE(n_levels >= 1 && n_levels <= NFA_HG_MAX_LEVELS, "%s: n_levels must be in 1..32 (got %d)", name, n_levels);
-    NFA_REQUIRE(log2_hashmap_size >= 10 && log2_hashmap_size <= 24, "%s: log2_hashmap_size must be in 10..24 (got %d)",
-                name, log2_hashmap_size);
-    NFA_REQUIRE(n_params < ((int64_t)1 << 31), "%s: too many parameters (%lld)", name, (long long)n_params);
-    NFA_REQUIRE(scales_host && resolutions_host && sizes_host, "%s: null level table", name);
-    const int64_t table = (int64_t)1 << log2_hashmap_size;
+    NFA_REQUIRE(G.n_points >= 0 && G.n_params >= 0, "%s: negative size", name);
+    NFA_REQUIRE(G.n_features == 1 || G.n_features == 2 || G.n_features == 4 || G.n_features == 8,
+                "%s: n_features must be 1, 2, 4 or 8 (got %d)", name, G.n_features);
+    NFA_REQUIRE(G.n_levels >= 1 && G.n_levels <= NFA_HG_MAX_LEVELS, "%s: n_levels must be in 1..32 (got %d)", name, G.n_levels);
+    NFA_REQUIRE(G.log2_hashmap_size >= 10 && G.log2_hashmap_size <= 24, "%s: log2_hashmap_size must be in 10..24 (got %d)",
+                name, G.log2_hashmap_size);
+    NFA_REQUIRE(G.n_params < ((int64_t)1 << 31), "%s: too many parameters (%lld)", name, (long long)G.n_params);
+    NFA_REQUIRE(G.scales_host && G.resolutions_host && G.sizes_host, "%s: null level table", name);
+    const int64_t table = (int64_t)1 << G.log2_hashmap_size;
     int64_t offset = 0;
     T = {};
-    for (int l = 0; l < n_levels; ++l) {
-        const int64_t r = resolutions_host[l], s = sizes_host[l];
+    for (int l = 0; l < G.n_levels; ++l) {
+        const int64_t r = G.resolutions_host[l], s = G.sizes_host[l];
         NFA_REQUIRE(r >= 1, "%s: level %d resolution %lld out of range", name, l, (long long)r);
         const int64_t dense = r > (1 << 20) ? INT64_MAX : (r * r * r + 7) / 8 * 8;   // (no overflow; hashed anyway)
         NFA_REQUIRE(s == (dense < table ? dense : table), "%s: level %d size %lld is not min(roundup8(res^3), 2^%d)",
-                    name, l, (long long)s, log2_hashmap_size);
-        T.scale[l] = scales_host[l];
+                    name, l, (long long)s, G.log2_hashmap_size);
+        T.scale[l] = G.scales_host[l];
         T.res[l] = (uint32_t)r;
         T.offset[l] = (uint32_t)offset;
         T.size[l] = (uint32_t)s;
         if (dense > table) T.hashed |= 1u << l;
         offset += s;
     }
-    NFA_REQUIRE(offset * n_features == n_params, "%s: n_params %lld != %lld entries x %d features", name,
-                (long long)n_params, (long long)offset, n_features);
-    T.n_levels = n_levels;
-    T.pts_per_wave = 64 / n_levels;
+    NFA_REQUIRE(offset * G.n_features == G.n_params, "%s: n_params %lld != %lld entries x %d features", name,
+                (long long)G.n_params, (long long)offset, G.n_features);
+    T.n_levels = G.n_levels;
+    T.pts_per_wave = 64 / G.n_levels;
     return NFA_OK;
 }
 
@@ -607,6 +624,8 @@ static unsigned hashgrid_grid(int64_t n_points, const HashGridLevels &T)
 }
 
 // ---------------------------------------------------------------- the entries, one implementation per element type
+// Each pass is a check of its arguments (which builds the level table) and a launch with the checked table; the `_sorted`
+// passes check once under their own name and call the launch half of the plain pass.
 static int check_interp(const char *name, int32_t interp)
 {
     NFA_REQUIRE(interp == NFA_INTERP_LINEAR || interp == NFA_INTERP_SMOOTHSTEP,
@@ -614,61 +633,51 @@ static int check_interp(const char *name, int32_t interp)
     return NFA_OK;
 }
 
-// Host-side dispatch of (n_features, interp), both checked before, to compile-time values:
-// f(std::integral_constant<int, F>, std::integral_constant<int, I>)
+// Host-side dispatch of a run-time value to a compile-time one, f(std::integral_constant<int, V>), for the V... it was
+// checked to be one of; of (n_features, interp) to f(.. <int, F>, .. <int, I>); and of the spherical-harmonics degree.
+template <int... V, class Fn>
+static void dispatch_int(int32_t v, Fn &&f)
+{
+    (void)((v == V && (f(std::integral_constant<int, V>{}), true)) || ...);
+}
 template <class Fn>
 static void dispatch_grid(int32_t n_features, int32_t interp, Fn &&f)
 {
-    dispatch_bool(interp == NFA_INTERP_SMOOTHSTEP, [&](auto smooth) {
-        using I = std::integral_constant<int, decltype(smooth)::value ? NFA_INTERP_SMOOTHSTEP : NFA_INTERP_LINEAR>;
-        switch (n_features) {
-        case 1: f(std::integral_constant<int, 1>{}, I{}); break;
-        case 2: f(std::integral_constant<int, 2>{}, I{}); break;
-        case 4: f(std::integral_constant<int, 4>{}, I{}); break;
-        default: f(std::integral_constant<int, 8>{}, I{}); break;
-        }
+    dispatch_int<NFA_INTERP_LINEAR, NFA_INTERP_SMOOTHSTEP>(interp, [&](auto i) {
+        dispatch_int<1, 2, 4, 8>(n_features, [&](auto n) { f(n, i); });
     });
+}
+template <class Fn>
+static void dispatch_degree(int32_t degree, Fn &&f)
+{
+    dispatch_int<1, 2, 3, 4>(degree, f);
 }
 
 template <class E>
-static int hashgrid_fwd(int32_t interp, const float *x, const float *params, int64_t n_points, int32_t n_levels,
-                        int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
-                        const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, E *y,
-                        nfa_stream_t stream)
+static int hashgrid_fwd(int32_t interp, const float *x, const float *params, const GridArgs &G, E *y, nfa_stream_t stream)
 {
     HashGridLevels T;
-    const int rc = hashgrid_table("hashgrid_fwd", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
-                                  resolutions_host, sizes_host, n_params, T);
+    const int rc = hashgrid_table("hashgrid_fwd", G, T);
     if (rc != NFA_OK) return rc;
-    if (n_points == 0) return NFA_OK;
+    if (G.n_points == 0) return NFA_OK;
     NFA_REQUIRE(x && params && y, "hashgrid_fwd: null pointer");
     NFA_REQUIRE((std::is_same<E, float>::value) || aligned16(y), "hashgrid_fwd: a half y must be 16-byte aligned");
     hipStream_t s = as_stream(stream);
-    const dim3 grid(grid_1d(n_points, 256, 256 * 16 / n_levels + 1), n_levels), block(256);
-    dispatch_grid(n_features, interp, [&](auto f, auto i) {
-        hipLaunchKernelGGL((hashgrid_fwd_kernel<f(), E, i()>), grid, block, 0, s, x, params, n_points, T, y);
+    const dim3 grid(grid_1d(G.n_points, 256, 256 * 16 / G.n_levels + 1), G.n_levels), block(256);
+    dispatch_grid(G.n_features, interp, [&](auto f, auto i) {
+        hipLaunchKernelGGL((hashgrid_fwd_kernel<f(), E, i()>), grid, block, 0, s, x, params, G.n_points, T, y);
     });
     NFA_CHECK_LAUNCH("hashgrid_fwd");
     return NFA_OK;
 }
 
 template <class E>
-static int hashgrid_bwd(int32_t interp, const float *x, const float *params, const E *grad_y, int64_t n_points,
-                        int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
-                        const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
-                        float *grad_x, nfa_stream_t stream)
+static int hashgrid_bwd_launch(int32_t interp, const float *x, const float *params, const E *grad_y, const GridArgs &G,
+                               const HashGridLevels &T, float *grad_params, float *grad_x, hipStream_t s)
 {
-    HashGridLevels T;
-    const int rc = hashgrid_table("hashgrid_bwd", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
-                                  resolutions_host, sizes_host, n_params, T);
-    if (rc != NFA_OK) return rc;
-    if (n_points == 0) return NFA_OK;
-    NFA_REQUIRE(x && grad_y && (grad_params || grad_x) && (params || !grad_x), "hashgrid_bwd: null pointer");
-    NFA_REQUIRE((std::is_same<E, float>::value) || aligned16(grad_y), "hashgrid_bwd: a half grad_y must be 16-byte aligned");
-    const dim3 grid(hashgrid_grid(n_points, T)), block(256);
-    hipStream_t s = as_stream(stream);
-    dispatch_grid(n_features, interp, [&](auto f, auto i) {
-        hipLaunchKernelGGL((hashgrid_bwd_kernel<f(), E, i()>), grid, block, 0, s, x, params, grad_y, n_points, T, grad_params,
+    const dim3 grid(hashgrid_grid(G.n_points, T)), block(256);
+    dispatch_grid(G.n_features, interp, [&](auto f, auto i) {
+        hipLaunchKernelGGL((hashgrid_bwd_kernel<f(), E, i()>), grid, block, 0, s, x, params, grad_y, G.n_points, T, grad_params,
                            grad_x);
     });
     NFA_CHECK_LAUNCH("hashgrid_bwd");
@@ -676,29 +685,47 @@ static int hashgrid_bwd(int32_t interp, const float *x, const float *params, con
 }
 
 template <class E>
-static int hashgrid_bwd_bwd(int32_t interp, const float *x, const float *params, const E *grad_y, const float *grad_grad_x,
-                            int64_t n_points, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
-                            const float *scales_host, const int32_t *resolutions_host, const int32_t *sizes_host,
-                            int64_t n_params, E *grad_grad_y, float *grad_params, float *grad_x, nfa_stream_t stream)
+static int hashgrid_bwd(int32_t interp, const float *x, const float *params, const E *grad_y, const GridArgs &G,
+                        float *grad_params, float *grad_x, nfa_stream_t stream)
 {
     HashGridLevels T;
-    const int rc = hashgrid_table("hashgrid_bwd_bwd", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
-                                  resolutions_host, sizes_host, n_params, T);
+    const int rc = hashgrid_table("hashgrid_bwd", G, T);
     if (rc != NFA_OK) return rc;
-    if (n_points == 0) return NFA_OK;
+    if (G.n_points == 0) return NFA_OK;
+    NFA_REQUIRE(x && grad_y && (grad_params || grad_x) && (params || !grad_x), "hashgrid_bwd: null pointer");
+    NFA_REQUIRE((std::is_same<E, float>::value) || aligned16(grad_y), "hashgrid_bwd: a half grad_y must be 16-byte aligned");
+    return hashgrid_bwd_launch(interp, x, params, grad_y, G, T, grad_params, grad_x, as_stream(stream));
+}
+
+template <class E>
+static int hashgrid_bwd_bwd_launch(int32_t interp, const float *x, const float *params, const E *grad_y,
+                                   const float *grad_grad_x, const GridArgs &G, const HashGridLevels &T, E *grad_grad_y,
+                                   float *grad_params, float *grad_x, hipStream_t s)
+{
+    const dim3 grid(hashgrid_grid(G.n_points, T)), block(256);
+    dispatch_grid(G.n_features, interp, [&](auto f, auto i) {
+        hipLaunchKernelGGL((hashgrid_bwd_bwd_kernel<f(), E, i()>), grid, block, 0, s, x, params, grad_y, grad_grad_x,
+                           G.n_points, T, grad_grad_y, grad_params, grad_x);
+    });
+    NFA_CHECK_LAUNCH("hashgrid_bwd_bwd");
+    return NFA_OK;
+}
+
+template <class E>
+static int hashgrid_bwd_bwd(int32_t interp, const float *x, const float *params, const E *grad_y, const float *grad_grad_x,
+                            const GridArgs &G, E *grad_grad_y, float *grad_params, float *grad_x, nfa_stream_t stream)
+{
+    HashGridLevels T;
+    const int rc = hashgrid_table("hashgrid_bwd_bwd", G, T);
+    if (rc != NFA_OK) return rc;
+    if (G.n_points == 0) return NFA_OK;
     NFA_REQUIRE(grad_grad_x, "hashgrid_bwd_bwd: grad_grad_x is null");
     NFA_REQUIRE(grad_grad_y || grad_params || grad_x, "hashgrid_bwd_bwd: no output requested");
     NFA_REQUIRE(x && (grad_y || !(grad_params || grad_x)) && (params || !(grad_grad_y || grad_x)), "hashgrid_bwd_bwd: null pointer");
     NFA_REQUIRE((std::is_same<E, float>::value) || (aligned16(grad_y) && aligned16(grad_grad_y)),
                 "hashgrid_bwd_bwd: half grad_y and grad_grad_y must be 16-byte aligned");
-    const dim3 grid(hashgrid_grid(n_points, T)), block(256);
-    hipStream_t s = as_stream(stream);
-    dispatch_grid(n_features, interp, [&](auto f, auto i) {
-        hipLaunchKernelGGL((hashgrid_bwd_bwd_kernel<f(), E, i()>), grid, block, 0, s, x, params, grad_y, grad_grad_x,
-                           n_points, T, grad_grad_y, grad_params, grad_x);
-    });
-    NFA_CHECK_LAUNCH("hashgrid_bwd_bwd");
-    return NFA_OK;
+    return hashgrid_bwd_bwd_launch(interp, x, params, grad_y, grad_grad_x, G, T, grad_grad_y, grad_params, grad_x,
+                                   as_stream(stream));
 }
 
 template <class E>
@@ -711,12 +738,9 @@ static int sh_fwd(const float *dirs, int64_t n_points, int32_t degree, E *out, n
     NFA_REQUIRE(aligned16(out), "sh_fwd: out must be 16-byte aligned");
     const dim3 grid(grid_1d(n_points, 256)), block(256);
     hipStream_t s = as_stream(stream);
-    switch (degree) {
-    case 1: hipLaunchKernelGGL((sh_fwd_kernel<1, E>), grid, block, 0, s, dirs, n_points, out); break;
-    case 2: hipLaunchKernelGGL((sh_fwd_kernel<2, E>), grid, block, 0, s, dirs, n_points, out); break;
-    case 3: hipLaunchKernelGGL((sh_fwd_kernel<3, E>), grid, block, 0, s, dirs, n_points, out); break;
-    default: hipLaunchKernelGGL((sh_fwd_kernel<4, E>), grid, block, 0, s, dirs, n_points, out); break;
-    }
+    dispatch_degree(degree, [&](auto deg) {
+        hipLaunchKernelGGL((sh_fwd_kernel<deg(), E>), grid, block, 0, s, dirs, n_points, out);
+    });
     NFA_CHECK_LAUNCH("sh_fwd");
     return NFA_OK;
 }
@@ -731,12 +755,9 @@ static int sh_bwd(const float *dirs, const E *grad_out, int64_t n_points, int32_
     NFA_REQUIRE(aligned16(grad_out), "sh_bwd: grad_out must be 16-byte aligned");
     const dim3 grid(grid_1d(n_points, 256)), block(256);
     hipStream_t s = as_stream(stream);
-    switch (degree) {
-    case 1: hipLaunchKernelGGL((sh_bwd_kernel<1, E>), grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
-    case 2: hipLaunchKernelGGL((sh_bwd_kernel<2, E>), grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
-    case 3: hipLaunchKernelGGL((sh_bwd_kernel<3, E>), grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
-    default: hipLaunchKernelGGL((sh_bwd_kernel<4, E>), grid, block, 0, s, dirs, grad_out, n_points, grad_dirs); break;
-    }
+    dispatch_degree(degree, [&](auto deg) {
+        hipLaunchKernelGGL((sh_bwd_kernel<deg(), E>), grid, block, 0, s, dirs, grad_out, n_points, grad_dirs);
+    });
     NFA_CHECK_LAUNCH("sh_bwd");
     return NFA_OK;
 }
@@ -860,15 +881,12 @@ __device__ __forceinline__ uint32_t block_excl_sum_256(uint32_t v, uint32_t *ws,
 
 __global__ __launch_bounds__(256) void hs_keys_kernel(const float *__restrict__ x, const HashGridLevels T, const HashSortArgs A)
 {
-    const int l = A.first_level + (int)blockIdx.y;
-    const bool hashed = (T.hashed >> l) & 1u;
-    const uint32_t res = T.res[l], size = T.size[l];
-    const float scale = T.scale[l];
+    const LevelRef L(T, A.first_level + (int)blockIdx.y);
     uint32_t *keys = hs_view(A, (int)blockIdx.y).keys0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.items; i += stride) {
-        const Cell c = locate(x + (i >> 3) * 3, scale);
-        keys[i] = corner_index(c, (int)(i & 7), hashed, res, size);
+        const Cell c = locate(x + (i >> 3) * 3, L.scale);
+        keys[i] = corner_index(c, (int)(i & 7), L);
     }
 }
 
@@ -985,29 +1003,25 @@ __global__ __launch_bounds__(256) void hs_scatter_kernel(const HashGridLevels T,
     }
 }
 
-// term of item (n, corner) of level l: coef * g[j] (header of this section)
+// term of item (n, corner) of level l: coef * g[j] (header of this section), coef being Corner's
 template <int F, class E, bool SECOND, int I>
 __device__ __forceinline__ void hs_term(const float *__restrict__ x, const E *__restrict__ g_y, const float *__restrict__ gg_x,
                                         const HashGridLevels &T, int l, int64_t n, int corner, float *out)
 {
-    const float s = T.scale[l];
+    const float s = LevelRef(T, l).scale;
     Cell c = locate(x + n * 3, s);
     float d1[3], d2[3];
     if constexpr (I == NFA_INTERP_SMOOTHSTEP) smoothstep(c, d1, d2);
-    FVec<F> g;
-    if constexpr (std::is_same<E, float>::value) g = reinterpret_cast<const FVec<F> *>(g_y)[n * T.n_levels + l];
-    else load_elems<F>(g_y + (n * T.n_levels + l) * F, g.v);
-    const float w0 = corner_factor(c, corner, 0), w1 = corner_factor(c, corner, 1), w2 = corner_factor(c, corner, 2);
+    const FVec<F> g = load_piece<F>(g_y, n * T.n_levels + l);
+    const Corner k(c, corner);
     float coef;
     if constexpr (SECOND) {
-        const float v0 = gg_x[n * 3 + 0], v1 = gg_x[n * 3 + 1], v2 = gg_x[n * 3 + 2];
-        float u0 = (corner & 1) ? v0 : -v0, u1 = (corner & 2) ? v1 : -v1, u2 = (corner & 4) ? v2 : -v2;
-        if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
-            u0 = u0 * d1[0]; u1 = u1 * d1[1]; u2 = u2 * d1[2];
-        }
-        coef = ((u0 * (w1 * w2) + u1 * (w0 * w2)) + u2 * (w0 * w1)) * s;
+        float v[3] = {gg_x[n * 3 + 0], gg_x[n * 3 + 1], gg_x[n * 3 + 2]}, u[3];
+        if constexpr (I == NFA_INTERP_SMOOTHSTEP) { v[0] = v[0] * d1[0]; v[1] = v[1] * d1[1]; v[2] = v[2] * d1[2]; }
+        k.signed_v(v, u);
+        coef = k.second_order(u, s);
     } else {
-        coef = (w0 * w1) * w2;
+        coef = k.first_order();
     }
 #pragma unroll
     for (int j = 0; j < F; ++j) out[j] = coef * g.v[j];
@@ -1091,11 +1105,11 @@ __global__ __launch_bounds__(256) void hs_carry_kernel(const HashGridLevels T, c
     if (k < T.size[l]) g_params[((size_t)T.offset[l] + k) * F + j] = acc;
 }
 
-static int hashsort_check(const char *name, int64_t n_points, int32_t n_levels, const void *scratch, int64_t scratch_bytes)
+static int hashsort_check(const char *name, const GridArgs &G, const void *scratch, int64_t scratch_bytes)
 {
-    NFA_REQUIRE(8 * n_points < ((int64_t)1 << 32), "%s: 8 * n_points must be below 2^32 (got n_points %lld)", name,
-                (long long)n_points);
-    const HashSortPlan p = hashsort_plan(n_points, n_levels);
+    NFA_REQUIRE(8 * G.n_points < ((int64_t)1 << 32), "%s: 8 * n_points must be below 2^32 (got n_points %lld)", name,
+                (long long)G.n_points);
+    const HashSortPlan p = hashsort_plan(G.n_points, G.n_levels);
     NFA_REQUIRE(scratch, "%s: scratch is null (a table gradient needs nfa_hashgrid_sorted_scratch_bytes bytes)", name);
     NFA_REQUIRE(aligned16(scratch), "%s: scratch must be 16-byte aligned", name);
     NFA_REQUIRE(scratch_bytes >= p.scratch_bytes, "%s: scratch too small (%lld bytes, %lld needed)", name,
@@ -1106,17 +1120,10 @@ static int hashsort_check(const char *name, int64_t n_points, int32_t n_levels, 
 // the table gradient of either order (gg_x: second) into the zeroed grad_params
 template <class E>
 static int hashsort_table_grad(const char *name, int32_t interp, const float *x, const E *grad_y, const float *gg_x,
-                               int64_t n_points, int32_t n_features, const HashGridLevels &T, float *grad_params, void *scratch,
-                               hipStream_t s)
+                               const GridArgs &G, const HashGridLevels &T, float *grad_params, void *scratch, hipStream_t s)
 {
-    const HashSortPlan p = hashsort_plan(n_points, T.n_levels);
-    HashSortArgs A;
-    A.scratch = static_cast<unsigned char *>(scratch);
-    A.level_bytes = p.level_bytes;
-    A.items = p.items;
-    A.n_blocks = p.n_blocks;
-    A.n_tiles = p.n_tiles;
-    A.n_points = n_points;
+    const HashSortPlan p = hashsort_plan(G.n_points, T.n_levels);
+    HashSortArgs A = {static_cast<unsigned char *>(scratch), p.level_bytes, p.items, p.n_blocks, p.n_tiles, G.n_points, 0};
     const dim3 block(256);
     for (int first = 0; first < T.n_levels; first += p.group) {
         const unsigned g = (unsigned)(T.n_levels - first < p.group ? T.n_levels - first : p.group);
@@ -1130,75 +1137,63 @@ static int hashsort_table_grad(const char *name, int32_t interp, const float *x,
             hipLaunchKernelGGL(hs_scatter_kernel, dim3((unsigned)p.n_blocks, g), block, 0, s, T, A, pass);
         }
         const dim3 tiles((unsigned)p.n_tiles, g);
-        dispatch_grid(n_features, interp, [&](auto f, auto i) {
+        dispatch_grid(G.n_features, interp, [&](auto f, auto i) {
             if (gg_x)
                 hipLaunchKernelGGL((hs_sum_kernel<f(), E, true, i()>), tiles, block, 0, s, x, grad_y, gg_x, T, A, grad_params);
             else
                 hipLaunchKernelGGL((hs_sum_kernel<f(), E, false, i()>), tiles, block, 0, s, x, grad_y, gg_x, T, A, grad_params);
         });
-        hipLaunchKernelGGL(hs_carry_kernel, dim3((unsigned)ceil_div64(p.n_tiles * n_features, 256), g), block, 0, s, T, A,
-                           (int)n_features, grad_params);
+        hipLaunchKernelGGL(hs_carry_kernel, dim3((unsigned)ceil_div64(p.n_tiles * G.n_features, 256), g), block, 0, s, T, A,
+                           (int)G.n_features, grad_params);
     }
     NFA_CHECK_LAUNCH(name);
     return NFA_OK;
 }
 
 template <class E>
-static int hashgrid_bwd_sorted(int32_t interp, const float *x, const float *params, const E *grad_y, int64_t n_points,
-                               int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
-                               const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
-                               float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream)
+static int hashgrid_bwd_sorted(int32_t interp, const float *x, const float *params, const E *grad_y, const GridArgs &G,
+                               float *grad_params, float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream)
 {
-    if (!grad_params)
-        return hashgrid_bwd(interp, x, params, grad_y, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
-                            resolutions_host, sizes_host, n_params, grad_params, grad_x, stream);
+    if (!grad_params) return hashgrid_bwd(interp, x, params, grad_y, G, grad_params, grad_x, stream);
     HashGridLevels T;
-    int rc = hashgrid_table("hashgrid_bwd_sorted", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
-                            resolutions_host, sizes_host, n_params, T);
+    int rc = hashgrid_table("hashgrid_bwd_sorted", G, T);
     if (rc != NFA_OK) return rc;
-    if (n_points == 0) return NFA_OK;
+    if (G.n_points == 0) return NFA_OK;
     NFA_REQUIRE(x && grad_y && (params || !grad_x), "hashgrid_bwd_sorted: null pointer");
     NFA_REQUIRE((std::is_same<E, float>::value) || aligned16(grad_y), "hashgrid_bwd_sorted: a half grad_y must be 16-byte aligned");
-    rc = hashsort_check("hashgrid_bwd_sorted", n_points, n_levels, scratch, scratch_bytes);
+    rc = hashsort_check("hashgrid_bwd_sorted", G, scratch, scratch_bytes);
     if (rc != NFA_OK) return rc;
+    hipStream_t s = as_stream(stream);
     if (grad_x) {
-        rc = hashgrid_bwd(interp, x, params, grad_y, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
-                          resolutions_host, sizes_host, n_params, (float *)nullptr, grad_x, stream);
+        rc = hashgrid_bwd_launch(interp, x, params, grad_y, G, T, (float *)nullptr, grad_x, s);
         if (rc != NFA_OK) return rc;
     }
-    return hashsort_table_grad<E>("hashgrid_bwd_sorted", interp, x, grad_y, nullptr, n_points, n_features, T, grad_params,
-                                  scratch, as_stream(stream));
+    return hashsort_table_grad<E>("hashgrid_bwd_sorted", interp, x, grad_y, nullptr, G, T, grad_params, scratch, s);
 }
 
 template <class E>
 static int hashgrid_bwd_bwd_sorted(int32_t interp, const float *x, const float *params, const E *grad_y,
-                                   const float *grad_grad_x, int64_t n_points, int32_t n_levels, int32_t n_features,
-                                   int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
-                                   const int32_t *sizes_host, int64_t n_params, E *grad_grad_y, float *grad_params,
+                                   const float *grad_grad_x, const GridArgs &G, E *grad_grad_y, float *grad_params,
                                    float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream)
 {
     if (!grad_params)
-        return hashgrid_bwd_bwd(interp, x, params, grad_y, grad_grad_x, n_points, n_levels, n_features, log2_hashmap_size,
-                                scales_host, resolutions_host, sizes_host, n_params, grad_grad_y, grad_params, grad_x, stream);
+        return hashgrid_bwd_bwd(interp, x, params, grad_y, grad_grad_x, G, grad_grad_y, grad_params, grad_x, stream);
     HashGridLevels T;
-    int rc = hashgrid_table("hashgrid_bwd_bwd_sorted", n_points, n_levels, n_features, log2_hashmap_size, scales_host,
-                            resolutions_host, sizes_host, n_params, T);
+    int rc = hashgrid_table("hashgrid_bwd_bwd_sorted", G, T);
     if (rc != NFA_OK) return rc;
-    if (n_points == 0) return NFA_OK;
+    if (G.n_points == 0) return NFA_OK;
     NFA_REQUIRE(grad_grad_x, "hashgrid_bwd_bwd_sorted: grad_grad_x is null");
     NFA_REQUIRE(x && grad_y && (params || !(grad_grad_y || grad_x)), "hashgrid_bwd_bwd_sorted: null pointer");
     NFA_REQUIRE((std::is_same<E, float>::value) || (aligned16(grad_y) && aligned16(grad_grad_y)),
                 "hashgrid_bwd_bwd_sorted: half grad_y and grad_grad_y must be 16-byte aligned");
-    rc = hashsort_check("hashgrid_bwd_bwd_sorted", n_points, n_levels, scratch, scratch_bytes);
+    rc = hashsort_check("hashgrid_bwd_bwd_sorted", G, scratch, scratch_bytes);
     if (rc != NFA_OK) return rc;
+    hipStream_t s = as_stream(stream);
     if (grad_grad_y || grad_x) {
-        rc = hashgrid_bwd_bwd(interp, x, params, grad_y, grad_grad_x, n_points, n_levels, n_features, log2_hashmap_size,
-                              scales_host, resolutions_host, sizes_host, n_params, grad_grad_y, (float *)nullptr, grad_x,
-                              stream);
+        rc = hashgrid_bwd_bwd_launch(interp, x, params, grad_y, grad_grad_x, G, T, grad_grad_y, (float *)nullptr, grad_x, s);
         if (rc != NFA_OK) return rc;
     }
-    return hashsort_table_grad<E>("hashgrid_bwd_bwd_sorted", interp, x, grad_y, grad_grad_x, n_points, n_features, T,
-                                  grad_params, scratch, as_stream(stream));
+    return hashsort_table_grad<E>("hashgrid_bwd_bwd_sorted", interp, x, grad_y, grad_grad_x, G, T, grad_params, scratch, s);
 }
 
 }  // namespace nfa
@@ -1217,9 +1212,8 @@ int nfa_hashgrid_fwd_i(int32_t interp, int32_t elem, const float *x, const float
                        nfa_stream_t stream)
 {
     if (check_interp("hashgrid_fwd", interp) != NFA_OK) return NFA_EINVAL;
-    ELEM_DISPATCH("hashgrid_fwd", elem, hashgrid_fwd(interp, x, params, n_points, n_levels, n_features, log2_hashmap_size,
-                                                     scales_host, resolutions_host, sizes_host, n_params, static_cast<E *>(y),
-                                                     stream));
+    const GridArgs G = {n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params};
+    ELEM_DISPATCH("hashgrid_fwd", elem, hashgrid_fwd(interp, x, params, G, static_cast<E *>(y), stream));
 }
 
 int nfa_hashgrid_fwd_t(int32_t elem, const float *x, const float *params, int64_t n_points, int32_t n_levels,
@@ -1245,9 +1239,9 @@ int nfa_hashgrid_bwd_i(int32_t interp, int32_t elem, const float *x, const float
                        float *grad_x, nfa_stream_t stream)
 {
     if (check_interp("hashgrid_bwd", interp) != NFA_OK) return NFA_EINVAL;
-    ELEM_DISPATCH("hashgrid_bwd", elem, hashgrid_bwd(interp, x, params, static_cast<const E *>(grad_y), n_points, n_levels,
-                                                     n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host,
-                                                     n_params, grad_params, grad_x, stream));
+    const GridArgs G = {n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params};
+    ELEM_DISPATCH("hashgrid_bwd", elem,
+                  hashgrid_bwd(interp, x, params, static_cast<const E *>(grad_y), G, grad_params, grad_x, stream));
 }
 
 int nfa_hashgrid_bwd_t(int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points,
@@ -1275,9 +1269,8 @@ int nfa_hashgrid_bwd_bwd_i(int32_t interp, int32_t elem, const float *x, const f
                            nfa_stream_t stream)
 {
     if (check_interp("hashgrid_bwd_bwd", interp) != NFA_OK) return NFA_EINVAL;
-    ELEM_DISPATCH("hashgrid_bwd_bwd", elem, hashgrid_bwd_bwd(interp, x, params, static_cast<const E *>(grad_y), grad_grad_x,
-                                                             n_points, n_levels, n_features, log2_hashmap_size, scales_host,
-                                                             resolutions_host, sizes_host, n_params,
+    const GridArgs G = {n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params};
+    ELEM_DISPATCH("hashgrid_bwd_bwd", elem, hashgrid_bwd_bwd(interp, x, params, static_cast<const E *>(grad_y), grad_grad_x, G,
                                                              static_cast<E *>(grad_grad_y), grad_params, grad_x, stream));
 }
 
@@ -1338,10 +1331,10 @@ int nfa_hashgrid_bwd_sorted_i(int32_t interp, int32_t elem, const float *x, cons
                               nfa_stream_t stream)
 {
     if (check_interp("hashgrid_bwd_sorted", interp) != NFA_OK) return NFA_EINVAL;
+    const GridArgs G = {n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params};
     ELEM_DISPATCH("hashgrid_bwd_sorted", elem,
-                  hashgrid_bwd_sorted(interp, x, params, static_cast<const E *>(grad_y), n_points, n_levels, n_features,
-                                      log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params, grad_params,
-                                      grad_x, scratch, scratch_bytes, stream));
+                  hashgrid_bwd_sorted(interp, x, params, static_cast<const E *>(grad_y), G, grad_params, grad_x, scratch,
+                                      scratch_bytes, stream));
 }
 
 int nfa_hashgrid_bwd_sorted(int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points,
@@ -1361,9 +1354,9 @@ int nfa_hashgrid_bwd_bwd_sorted_i(int32_t interp, int32_t elem, const float *x, 
                                   float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream)
 {
     if (check_interp("hashgrid_bwd_bwd_sorted", interp) != NFA_OK) return NFA_EINVAL;
+    const GridArgs G = {n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params};
     ELEM_DISPATCH("hashgrid_bwd_bwd_sorted", elem,
-                  hashgrid_bwd_bwd_sorted(interp, x, params, static_cast<const E *>(grad_y), grad_grad_x, n_points, n_levels,
-                                          n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params,
+                  hashgrid_bwd_bwd_sorted(interp, x, params, static_cast<const E *>(grad_y), grad_grad_x, G,
                                           static_cast<E *>(grad_grad_y), grad_params, grad_x, scratch, scratch_bytes, stream));
 }
 

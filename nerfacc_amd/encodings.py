@@ -134,15 +134,19 @@ def _resolve_out_dtype(out_dtype, x: Tensor) -> torch.dtype:
 
 def _entry(name: str, dtype: torch.dtype, interp: int = 0):
     """(entry point, leading arguments): float32 calls the unsuffixed entry as ever, fp16 / bf16 the ``_t`` one, and an
-    interpolation other than Linear the ``_i`` one."""
+    interpolation other than Linear the ``_i`` one.  The ``_sorted`` entries always take the element code."""
     if interp:
         return name + "_i", (interp, B.ELEM_CODES[dtype])
+    if name.endswith("_sorted"):
+        return name, (B.ELEM_CODES[dtype],)
     return (name, ()) if dtype == torch.float32 else (name + "_t", (B.ELEM_CODES[dtype],))
 
 
-def _sorted_entry(name: str, dtype: torch.dtype, interp: int = 0):
-    """The same for the ``_sorted`` entries, which always take the element code."""
-    return (name + "_i", (interp, B.ELEM_CODES[dtype])) if interp else (name, (B.ELEM_CODES[dtype],))
+def _table_args(enc: "HashGridEncoding", n_points: int, params: Tensor):
+    """The grid description every ``nfa_hashgrid_*`` entry takes after its tensors."""
+    t = enc.table
+    return (n_points, enc.n_levels, enc.n_features_per_level, t.log2_hashmap_size, t.c_scales, t.c_res, t.c_sizes,
+            params.numel())
 
 
 SORTED_MAX_POINTS = (1 << 29) - 1   # nfa_hashgrid_*_sorted: the item id 8 n + c is 32 bits wide
@@ -168,14 +172,12 @@ class _HashGridFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, params, enc: "HashGridEncoding", dtype: torch.dtype):
         B.require_device(x, params)
-        t, L, F = enc.table, enc.n_levels, enc.n_features_per_level
         N = x.shape[0]
-        y = torch.empty(N, L * F, dtype=dtype, device=x.device)
+        y = torch.empty(N, enc.n_levels * enc.n_features_per_level, dtype=dtype, device=x.device)
         if N:
             with torch.cuda.device(x.device):
-                entry, elem = _entry("nfa_hashgrid_fwd", dtype, enc.interp)
-                B.call(entry, *elem, B.ptr(x), B.ptr(params), N, L, F, t.log2_hashmap_size, t.c_scales, t.c_res,
-                       t.c_sizes, params.numel(), B.ptr(y), B.stream())
+                entry, lead = _entry("nfa_hashgrid_fwd", dtype, enc.interp)
+                B.call(entry, *lead, B.ptr(x), B.ptr(params), *_table_args(enc, N, params), B.ptr(y), B.stream())
         ctx.enc, ctx.dtype = enc, dtype
         ctx.save_for_backward(x, params)
         return y
@@ -196,21 +198,18 @@ class _HashGridBwdFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, params, g, enc: "HashGridEncoding", dtype: torch.dtype, need_x: bool, need_p: bool):
-        t, L, F = enc.table, enc.n_levels, enc.n_features_per_level
         g_p = torch.zeros_like(params) if need_p else None
         g_x = torch.empty_like(x) if need_x else None
         if x.shape[0]:
             with torch.cuda.device(x.device):
+                args = (B.ptr(x), B.ptr(params), B.ptr(g), *_table_args(enc, x.shape[0], params), B.ptr(g_p), B.ptr(g_x))
                 if enc.deterministic and need_p:
                     scratch = _sorted_scratch(enc, x.shape[0], x.device)
-                    entry, lead = _sorted_entry("nfa_hashgrid_bwd_sorted", dtype, enc.interp)
-                    B.call(entry, *lead, B.ptr(x), B.ptr(params), B.ptr(g), x.shape[0], L, F,
-                           t.log2_hashmap_size, t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(g_p), B.ptr(g_x),
-                           B.ptr(scratch), scratch.numel(), B.stream())
+                    entry, lead = _entry("nfa_hashgrid_bwd_sorted", dtype, enc.interp)
+                    B.call(entry, *lead, *args, B.ptr(scratch), scratch.numel(), B.stream())
                 else:
-                    entry, elem = _entry("nfa_hashgrid_bwd", dtype, enc.interp)
-                    B.call(entry, *elem, B.ptr(x), B.ptr(params), B.ptr(g), x.shape[0], L, F, t.log2_hashmap_size,
-                           t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(g_p), B.ptr(g_x), B.stream())
+                    entry, lead = _entry("nfa_hashgrid_bwd", dtype, enc.interp)
+                    B.call(entry, *lead, *args, B.stream())
         ctx.enc, ctx.dtype = enc, dtype
         ctx.save_for_backward(x, params, g)
         ctx.set_materialize_grads(False)
@@ -227,23 +226,21 @@ class _HashGridBwdFn(torch.autograd.Function):
             return (None,) * 7
         x, params, g = ctx.saved_tensors
         enc = ctx.enc
-        t, L, F = enc.table, enc.n_levels, enc.n_features_per_level
         v = gg_x.to(torch.float32).contiguous()
         x2 = torch.empty_like(x) if need_x else None
         g2_p = torch.zeros_like(params) if need_p else None
         gg_y = torch.empty_like(g) if need_g else None
         if x.shape[0]:
             with torch.cuda.device(x.device):
+                args = (B.ptr(x), B.ptr(params), B.ptr(g), B.ptr(v), *_table_args(enc, x.shape[0], params), B.ptr(gg_y),
+                        B.ptr(g2_p), B.ptr(x2))
                 if enc.deterministic and need_p:
                     scratch = _sorted_scratch(enc, x.shape[0], x.device)
-                    entry, lead = _sorted_entry("nfa_hashgrid_bwd_bwd_sorted", ctx.dtype, enc.interp)
-                    B.call(entry, *lead, B.ptr(x), B.ptr(params), B.ptr(g), B.ptr(v),
-                           x.shape[0], L, F, t.log2_hashmap_size, t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(gg_y),
-                           B.ptr(g2_p), B.ptr(x2), B.ptr(scratch), scratch.numel(), B.stream())
+                    entry, lead = _entry("nfa_hashgrid_bwd_bwd_sorted", ctx.dtype, enc.interp)
+                    B.call(entry, *lead, *args, B.ptr(scratch), scratch.numel(), B.stream())
                 else:
-                    entry, elem = _entry("nfa_hashgrid_bwd_bwd", ctx.dtype, enc.interp)
-                    B.call(entry, *elem, B.ptr(x), B.ptr(params), B.ptr(g), B.ptr(v), x.shape[0], L, F, t.log2_hashmap_size,
-                           t.c_scales, t.c_res, t.c_sizes, params.numel(), B.ptr(gg_y), B.ptr(g2_p), B.ptr(x2), B.stream())
+                    entry, lead = _entry("nfa_hashgrid_bwd_bwd", ctx.dtype, enc.interp)
+                    B.call(entry, *lead, *args, B.stream())
         return x2, g2_p, gg_y, None, None, None, None
 
 
