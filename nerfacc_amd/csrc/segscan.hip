@@ -674,12 +674,182 @@ struct ProdBwdOp : OpBase {
     __device__ __forceinline__ void store(const Pos &q) { store4<VEC>(gin, q, res); }
 };
 
+// ------------------------------------------------------------------------------------------
+// The rendering family -- DensityFwd/BwdOp, RenderAccum/AccumBwdOp, RenderFusedFwd/BwdOp, RenderRawFwd/BwdOp, RenderStepOp
+// (volrend.py:109-151, :256-264, :358-362) -- is assembled from the steps below, each written once.  They are plain
+// functions of values and base structs with __forceinline__ members: an op is a kernel argument and its working arrays
+// are members, so after inlining a step reads and writes the op's own registers.
+
+// ---- the density stage: sigma * delta (0 outside the range) is what stage A sums along the ray; with S the sum in front
+//      of a sample, T = exp(-S), alpha = 1 - exp(-sigma * delta), w = T * alpha
+__device__ __forceinline__ float sigma_delta(bool valid, float sigma, float delta) { return valid ? sigma * delta : 0.0f; }
+__device__ __forceinline__ float midpoint(float ts, float te) { return (ts + te) / 2.0f; }
+__device__ __forceinline__ float alpha_of(float xs) { return 1.0f - expf(-xs); }
+__device__ __forceinline__ void trans_alpha(bool is_head, const float prev[1], float xs, float &T, float &a)
+{
+    const float S = is_head ? 0.0f : prev[0];
+    T = expf(-S);
+    a = alpha_of(xs);
+}
+// the per-sample outputs of that stage (each may be null)
+struct SampleOut {
+    float *w, *tr, *al;
+    template <bool VEC>
+    __device__ __forceinline__ void store_wta(const Pos &q, const float rw[SE], const float rt[SE], const float ra[SE]) const
+    {
+        if (w) store4<VEC>(w, q, rw);
+        if (tr) store4<VEC>(tr, q, rt);
+        if (al) store4<VEC>(al, q, ra);
+    }
+};
+
+// ---- the five channels stage B totals per ray: w * rgb, w, w * mid -> colours(3), opacity, un-normalised depth
+__device__ __forceinline__ float render_channel(int ch, float w, const float *c3, float mid)
+{
+    return ch < 3 ? w * c3[ch] : (ch == 3 ? w : w * mid);
+}
+// the per-ray outputs those totals go to: stored, added in place (the test-mode step), zero for an empty ray
+struct RayOut {
+    float *colors, *opac, *depth;   // [R,3], [R], [R]
+    template <bool ADD>
+    static __device__ __forceinline__ void set(float *o, float t) { *o = ADD ? *o + t : t; }
+    template <bool ADD>
+    __device__ __forceinline__ void ray_put(int rid, int ch, float t) const
+    {
+        if (ch < 3) set<ADD>(colors + 3 * (int64_t)rid + ch, t);
+        else if (ch == 3) set<ADD>(opac + rid, t);
+        else set<ADD>(depth + rid, t);
+    }
+    __device__ __forceinline__ void ray_store(int rid, int ch, float t) const { ray_put<false>(rid, ch, t); }
+    __device__ __forceinline__ void ray_add(int rid, int ch, float t) const { ray_put<true>(rid, ch, t); }
+    __device__ __forceinline__ void ray_store(int rid, const float t[5]) const
+    {
+#pragma unroll
+        for (int ch = 0; ch < 5; ++ch) ray_store(rid, ch, t[ch]);
+    }
+    __device__ __forceinline__ void ray_zero(int rid) const
+    {
+        const float z[5] = {0, 0, 0, 0, 0};
+        ray_store(rid, z);
+    }
+};
+// what the one-pass forward ops share: stage A scans sigma * delta, stage B totals the five channels of w
+struct RenderFwdStage : OpBase, RayOut {
+    static constexpr int NCHB = 5;
+    float xs[SE], mid[SE], rw[SE], c[3 * SE];
+    __device__ __forceinline__ void sample(int j, bool valid, float sigma, float ts, float te)
+    {
+        xs[j] = sigma_delta(valid, sigma, te - ts);
+        mid[j] = midpoint(ts, te);
+    }
+    __device__ __forceinline__ float x(int j, int) const { return xs[j]; }
+    __device__ __forceinline__ float xb(int j, int ch) const { return render_channel(ch, rw[j], c + 3 * j, mid[j]); }
+};
+
+// ---- backward: the per-ray output gradients {g_colour(3), g_opacity, g_depth} (each array may be null) ...
+struct RayGrads {
+    const float *gc, *go, *gd;
+    __device__ __forceinline__ void get(int rid, float g[5]) const   // gathered from memory
+    {
+        g[0] = gc ? gc[3 * (int64_t)rid] : 0.0f; g[1] = gc ? gc[3 * (int64_t)rid + 1] : 0.0f; g[2] = gc ? gc[3 * (int64_t)rid + 2] : 0.0f;
+        g[3] = go ? go[rid] : 0.0f; g[4] = gd ? gd[rid] : 0.0f;
+    }
+};
+// ... staged in LDS.  They are needed per ELEMENT, after the ray id is known: as global gathers they were a second,
+// dependent memory latency in every step (12 gather instructions per lane and step; SQ counters: the pass waits 80 % of
+// its wave-cycles, VALU 36 % busy).  The rays of a tile are consecutive, so the wave stages their gradients in LDS with
+// coalesced loads at tile start (up to RAY_CAP rays, the rest falls back to the gathers) and the per-element reads are LDS
+// reads.
+struct RayGradStage : RayGrads {
+    static constexpr int RAY_CAP = 192;
+    static constexpr int LDS_FLOATS = 8 * RAY_CAP;   // {g_r, g_g, g_b, g_opacity, g_depth, -, -, -} per ray
+    const float *g_lds = nullptr;
+    int32_t g_lo = 0, g_n = 0;
+    __device__ __forceinline__ void tile_begin(int32_t r_lo, int32_t r_hi, float *lds)
+    {
+        // (the pass runs from the tile's last ray to its first: when the tile owns more than RAY_CAP rays the stage holds
+        //  the LAST ones, which most of its elements belong to)
+        g_lds = lds; g_n = min(r_hi - r_lo, RAY_CAP); g_lo = r_hi - g_n;
+        __builtin_amdgcn_wave_barrier();
+        for (int32_t i = lane_id(); i < g_n; i += 64) {
+            const int64_t r = (int64_t)g_lo + i;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (gc) { v.x = gc[3 * r]; v.y = gc[3 * r + 1]; v.z = gc[3 * r + 2]; }
+            if (go) v.w = go[r];
+            *reinterpret_cast<float4 *>(lds + 8 * i) = v;
+            lds[8 * i + 4] = gd ? gd[r] : 0.0f;
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    __device__ __forceinline__ void get(int rid, float g[5]) const
+    {
+        const uint32_t slot = (uint32_t)(rid - g_lo);
+        if (slot < (uint32_t)g_n) {   // staged (the usual case)
+            const float4 v = *reinterpret_cast<const float4 *>(g_lds + 8 * slot);
+            g[0] = v.x; g[1] = v.y; g[2] = v.z; g[3] = v.w; g[4] = g_lds[8 * slot + 4];
+        } else {
+            RayGrads::get(rid, g);
+        }
+    }
+};
+// ... and what they make of one sample: the gradient of the three accumulations w.r.t. its weight (returned) and its
+// colour (g_rgb3), from the sample's colour c3, weight w and midpoint.  G is RayGrads or RayGradStage.
+template <class G>
+__device__ __forceinline__ float sample_grads(const G &rays, bool valid, int rid, const float *c3, float w, float mid, float *g_rgb3)
+{
+    float g_w = 0.0f;
+    g_rgb3[0] = g_rgb3[1] = g_rgb3[2] = 0.0f;
+    if (valid) {
+        float g[5];
+        rays.get(rid, g);
+        if (rays.gc) {
+            g_w += g[0] * c3[0] + g[1] * c3[1] + g[2] * c3[2];
+            g_rgb3[0] = g[0] * w; g_rgb3[1] = g[1] * w; g_rgb3[2] = g[2] * w;
+        }
+        if (rays.go) g_w += g[3];
+        if (rays.gd) g_w += g[4] * mid;
+    }
+    return g_w;
+}
+
+// ---- backward: the gradients arriving at the per-sample weights / trans / alphas (each may be null; EXTRA false: none is
+//      looked at), fetched raw and selected under `valid`
+template <bool EXTRA>
+struct ExtraGrads {
+    struct GRaw { F4 gw, gt, ga; };
+    const float *gw, *gt, *ga;
+    template <bool VEC>
+    __device__ __forceinline__ void fetch_extra(const Pos &q, GRaw &r) const
+    {
+        if (EXTRA) {
+            if (gw) ld4<VEC>(gw, q, r.gw);
+            if (gt) ld4<VEC>(gt, q, r.gt);
+            if (ga) ld4<VEC>(ga, q, r.ga);
+        }
+    }
+    __device__ __forceinline__ void select_extra(const GRaw &r, int j, bool valid, float &GW, float &GT, float &GA) const
+    {
+        GW = (EXTRA && gw && valid) ? r.gw.v[j] : 0.0f;
+        GT = (EXTRA && gt && valid) ? r.gt.v[j] : 0.0f;
+        GA = (EXTRA && ga && valid) ? r.ga.v[j] : 0.0f;
+    }
+};
+
+// ---- backward through the transmittance chain: the reverse scan sums q = GW w + GT T over the samples
+//      behind a sample; with E that sum, the gradient w.r.t. sigma * delta is B
+__device__ __forceinline__ float chain_input(float GW, float GT, float T, float w) { return GW * w + GT * T; }
+__device__ __forceinline__ float chain_grad(bool is_head, const float prev[1], float GW, float GA, float T, float A)
+{
+    const float E = is_head ? 0.0f : prev[0];
+    const float om = 1.0f - A;
+    return GW * T * om + GA * om - E;
+}
+
 // ---- transmittance / alpha / weights from density, volrend.py:256-264, :358-362
 template <bool VEC>
-struct DensityFwdOp : OpBase {
+struct DensityFwdOp : OpBase, SampleOut {
     struct Raw { F4 a, b, s, pf; };
     const float *ts, *te, *sig, *prefix;
-    float *w, *tr, *al;
     // batched rows of row_len samples (PropNetEstimator): the resampler's CDF rows `1 - cat([T, 0])` (row_len + 1 entries,
     // ref estimators/prop_net.py:104-107) written by the same pass; element p of ray r lands at p + r
     float *cdf = nullptr;
@@ -698,17 +868,16 @@ struct DensityFwdOp : OpBase {
         const bool *valid = pos.valid;
 #pragma unroll
         for (int j = 0; j < SE; ++j) {
-            xs[j] = valid[j] ? r.s.v[j] * (r.b.v[j] - r.a.v[j]) : 0.0f;
+            xs[j] = sigma_delta(valid[j], r.s.v[j], r.b.v[j] - r.a.v[j]);
             pf[j] = prefix ? r.pf.v[j] : 1.0f;
         }
     }
     __device__ __forceinline__ float x(int j, int) const { return xs[j]; }
     __device__ __forceinline__ void emit(int j, int64_t pos, bool valid, bool is_head, int rid, int, const float *, const float prev[1])
     {
-        const float S = is_head ? 0.0f : prev[0];
-        float T = expf(-S);
+        float T, a;
+        trans_alpha(is_head, prev, xs[j], T, a);
         if (prefix) T *= pf[j];
-        const float a = 1.0f - expf(-xs[j]);
         rt[j] = T; ra[j] = a; rw[j] = T * a;
         if (cdf) {
             crid[j] = rid;
@@ -718,9 +887,7 @@ struct DensityFwdOp : OpBase {
     __device__ __forceinline__ void store(const Pos &q)
     {
         (void)q.p0();   // (no effect, but without it the compiler allocates this op's registers differently)
-        if (w) store4<VEC>(w, q, rw);
-        if (tr) store4<VEC>(tr, q, rt);
-        if (al) store4<VEC>(al, q, ra);
+        store_wta<VEC>(q, rw, rt, ra);
         if (cdf) {
             // a quad inside one row is one 16-byte store at a 4-byte aligned address (rows are shifted by their index)
             struct __attribute__((packed, aligned(4))) Q4 { float x, y, z, w; };
@@ -777,10 +944,10 @@ struct AlphaFwdOp : OpBase {
 
 // ---- backward of the fused density op (reverse scan), SURVEY App. A.7
 template <bool VEC, bool CDF = false /* the gradient arrives at the CDF rows of DensityFwdOp::cdf: g_T[p] = -g_cdf[p + ray] */>
-struct DensityBwdOp : OpBase {
+struct DensityBwdOp : OpBase, ExtraGrads<true> {
     static constexpr bool NEEDS_RID = CDF;
-    struct Raw { F4 a, b, T, A, gw, gt, ga; };
-    const float *ts, *te, *tr, *al, *gw, *gt, *ga;
+    struct Raw { F4 a, b, T, A; GRaw g; };
+    const float *ts, *te, *tr, *al;
     const float *gcdf = nullptr;
     float *gsig, *gx;
     float T[SE], A[SE], GW[SE], GA[SE], dlt[SE], q[SE], rs[SE], rx[SE];
@@ -804,8 +971,7 @@ struct DensityBwdOp : OpBase {
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float GT = -g4[j];
-                q[4 * h + j] = GW[4 * h + j] * (T[4 * h + j] * A[4 * h + j]) + GT * T[4 * h + j];
+                q[4 * h + j] = chain_input(GW[4 * h + j], -g4[j], T[4 * h + j], T[4 * h + j] * A[4 * h + j]);
             }
         }
     }
@@ -815,9 +981,7 @@ struct DensityBwdOp : OpBase {
         ld4<VEC>(te, q, r.b);
         ld4<VEC>(tr, q, r.T);
         if (!CDF) ld4<VEC>(al, q, r.A);   // (with only g_T arriving alpha drops out: B = -E, q = g_T T)
-        if (gw) ld4<VEC>(gw, q, r.gw);
-        if (gt) ld4<VEC>(gt, q, r.gt);
-        if (ga) ld4<VEC>(ga, q, r.ga);
+        fetch_extra<VEC>(q, r.g);
     }
     __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
     {
@@ -825,19 +989,16 @@ struct DensityBwdOp : OpBase {
 #pragma unroll
         for (int j = 0; j < SE; ++j) {
             T[j] = sel(r.T, j, valid, 0.0f); A[j] = CDF ? 0.0f : sel(r.A, j, valid, 0.0f);
-            GW[j] = (gw && valid[j]) ? r.gw.v[j] : 0.0f;
-            const float GT = (gt && valid[j]) ? r.gt.v[j] : 0.0f;
-            GA[j] = (ga && valid[j]) ? r.ga.v[j] : 0.0f;
+            float GT;
+            select_extra(r.g, j, valid[j], GW[j], GT, GA[j]);
             dlt[j] = r.b.v[j] - r.a.v[j];
-            q[j] = GW[j] * (T[j] * A[j]) + GT * T[j];
+            q[j] = chain_input(GW[j], GT, T[j], T[j] * A[j]);
         }
     }
     __device__ __forceinline__ float x(int j, int) const { return q[j]; }
     __device__ __forceinline__ void emit(int j, int64_t, bool, bool is_head, int, int, const float *, const float prev[1])
     {
-        const float E = is_head ? 0.0f : prev[0];
-        const float om = 1.0f - A[j];
-        const float B = GW[j] * T[j] * om + GA[j] * om - E;
+        const float B = chain_grad(is_head, prev, GW[j], GA[j], T[j], A[j]);
         rx[j] = B; rs[j] = dlt[j] * B;
     }
     __device__ __forceinline__ void store(const Pos &q)
@@ -1280,343 +1441,6 @@ __device__ __forceinline__ void store_rgb12(float *rgb, bool vec, const Pos &q, 
     }
 }
 
-// ---- the three accumulations of `rendering` fused: colours(3), opacity, depth  (volrend.py:140-151)
-template <bool VEC>
-struct RenderAccumOp : OpBase {
-    static constexpr int NCH = 5;
-    static constexpr bool TOTALS = true;
-    struct Raw { F4 w, a, b; float c[3 * SE]; };
-    const float *w, *rgb, *ts, *te;
-    float *colors, *opac, *depth;
-    float xv[SE][5];
-    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
-    {
-        ld4<VEC>(w, q, r.w);
-        ld4<VEC>(ts, q, r.a);
-        ld4<VEC>(te, q, r.b);
-        load_rgb12(rgb, VEC, q, r.c);
-    }
-    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
-    {
-        const bool *valid = pos.valid;
-        float c[3 * SE];
-        fix_rgb12(rgb, VEC, pos, r.c, c);
-#pragma unroll
-        for (int j = 0; j < SE; ++j) {
-            const float ww = sel(r.w, j, valid, 0.0f);
-            xv[j][0] = ww * c[3 * j]; xv[j][1] = ww * c[3 * j + 1]; xv[j][2] = ww * c[3 * j + 2];
-            xv[j][3] = ww;
-            xv[j][4] = ww * ((r.a.v[j] + r.b.v[j]) / 2.0f);
-        }
-    }
-    __device__ __forceinline__ float x(int j, int ch) const { return xv[j][ch]; }
-    __device__ __forceinline__ void put(int rid, const float *t) const
-    {
-        colors[3 * (int64_t)rid] = t[0]; colors[3 * (int64_t)rid + 1] = t[1]; colors[3 * (int64_t)rid + 2] = t[2];
-        opac[rid] = t[3]; depth[rid] = t[4];
-    }
-    __device__ __forceinline__ void emit(int, int64_t, bool, bool, int, int, const float *, const float *) const {}
-    __device__ __forceinline__ void store(const Pos &) const {}
-    __device__ __forceinline__ void ray_done(int rid, const float t[5]) const { put(rid, t); }
-    __device__ __forceinline__ void empty_ray(int rid) const
-    {
-        const float z[5] = {0, 0, 0, 0, 0};
-        put(rid, z);
-    }
-};
-
-template <bool VEC>
-struct RenderAccumBwdOp : OpBase {
-    struct Raw { F4 w, a, b; float c[3 * SE]; };
-    const float *w, *rgb, *ts, *te, *gc, *go, *gd;
-    float *gw, *grgb;
-    float ww[SE], mid[SE], res[SE], c[3 * SE], gr[3 * SE];
-    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
-    {
-        ld4<VEC>(w, q, r.w);
-        ld4<VEC>(ts, q, r.a);
-        ld4<VEC>(te, q, r.b);
-        load_rgb12(rgb, VEC, q, r.c);
-    }
-    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
-    {
-        const bool *valid = pos.valid;
-        (void)valid;
-#pragma unroll
-        for (int j = 0; j < SE; ++j) { ww[j] = r.w.v[j]; mid[j] = (r.a.v[j] + r.b.v[j]) / 2.0f; }
-        fix_rgb12(rgb, VEC, pos, r.c, c);
-    }
-    __device__ __forceinline__ float x(int, int) const { return 0.0f; }
-    __device__ __forceinline__ void emit(int j, int64_t, bool valid, bool, int rid, int, const float *, const float *)
-    {
-        float g = 0.0f;
-        gr[3 * j] = gr[3 * j + 1] = gr[3 * j + 2] = 0.0f;
-        if (valid) {
-            if (gc) {
-                const float g0 = gc[3 * (int64_t)rid], g1 = gc[3 * (int64_t)rid + 1], g2 = gc[3 * (int64_t)rid + 2];
-                g += g0 * c[3 * j] + g1 * c[3 * j + 1] + g2 * c[3 * j + 2];
-                gr[3 * j] = g0 * ww[j]; gr[3 * j + 1] = g1 * ww[j]; gr[3 * j + 2] = g2 * ww[j];
-            }
-            if (go) g += go[rid];
-            if (gd) g += gd[rid] * mid[j];
-        }
-        res[j] = g;
-    }
-    __device__ __forceinline__ void store(const Pos &q)
-    {
-        if (gw) store4<VEC>(gw, q, res);
-        if (grgb) store_rgb12(grgb, VEC, q, gr);
-    }
-};
-
-// ---- `rendering` with a density callback in ONE pass (volrend.py:109-151): stage A scans
-//      sigma*delta into transmittance -> (w, T, alpha); stage B scans w*rgb, w, w*mid into the per-ray
-//      colour / opacity / un-normalised depth.  Bit-identical to DensityFwdOp followed by
-//      RenderAccumOp (same expressions, same scan tree), 12 B/sample less traffic.
-template <bool VEC>
-struct RenderFusedFwdOp : OpBase {
-    static constexpr int NCHB = 5;   // (81 VGPRs: one over the 6-wave budget; asking for 6 waves was within noise)
-    struct Raw { F4 a, b, s; float c[3 * SE]; };
-    const float *ts, *te, *sig, *rgb;
-    float *w, *tr, *al, *colors, *opac, *depth;
-    float xs[SE], mid[SE], rw[SE], rt[SE], ra[SE], c[3 * SE];
-    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
-    {
-        ld4<VEC>(ts, q, r.a);
-        ld4<VEC>(te, q, r.b);
-        ld4<VEC>(sig, q, r.s);
-        load_rgb12(rgb, VEC, q, r.c);
-    }
-    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
-    {
-        const bool *valid = pos.valid;
-        fix_rgb12(rgb, VEC, pos, r.c, c);
-#pragma unroll
-        for (int j = 0; j < SE; ++j) {
-            xs[j] = valid[j] ? r.s.v[j] * (r.b.v[j] - r.a.v[j]) : 0.0f;
-            mid[j] = (r.a.v[j] + r.b.v[j]) / 2.0f;
-        }
-    }
-    __device__ __forceinline__ float x(int j, int) const { return xs[j]; }
-    __device__ __forceinline__ void emit(int j, int64_t, bool, bool is_head, int, int, const float *, const float prev[1])
-    {
-        const float S = is_head ? 0.0f : prev[0];
-        const float T = expf(-S);
-        const float a = 1.0f - expf(-xs[j]);
-        rt[j] = T; ra[j] = a; rw[j] = T * a;
-    }
-    __device__ __forceinline__ float xb(int j, int ch) const
-    {
-        return ch < 3 ? rw[j] * c[3 * j + ch] : (ch == 3 ? rw[j] : rw[j] * mid[j]);
-    }
-    __device__ __forceinline__ void put(int rid, const float *t) const
-    {
-        colors[3 * (int64_t)rid] = t[0]; colors[3 * (int64_t)rid + 1] = t[1]; colors[3 * (int64_t)rid + 2] = t[2];
-        opac[rid] = t[3]; depth[rid] = t[4];
-    }
-    __device__ __forceinline__ void ray_done_b(int rid, int ch, float t) const
-    {
-        if (ch < 3) colors[3 * (int64_t)rid + ch] = t;
-        else if (ch == 3) opac[rid] = t;
-        else depth[rid] = t;
-    }
-    __device__ __forceinline__ void empty_ray(int rid) const
-    {
-        const float z[5] = {0, 0, 0, 0, 0};
-        put(rid, z);
-    }
-    __device__ __forceinline__ void store(const Pos &q)
-    {
-        if (w) store4<VEC>(w, q, rw);
-        if (tr) store4<VEC>(tr, q, rt);
-        if (al) store4<VEC>(al, q, ra);
-    }
-};
-
-// ---- one iteration of the test-mode marching loop (ref: examples/utils.py:370-405) in one pass: weights with
-//      prefix_trans = 1 - opacity[ray] (the ray id is known before the scan), samples with alpha < alpha_thre dropped,
-//      and rgb / opacity / depth accumulated IN PLACE into the per-ray image buffers.  Nothing per sample is written.
-//      A ray is owned by one wave, which reads its old opacity for all the ray's samples before it adds the total.
-template <bool VEC>
-struct RenderStepOp : OpBase {
-    static constexpr int NCHB = 5;
-    static constexpr bool NEEDS_RID = true;
-    struct Raw { F4 a, b, s; float c[3 * SE]; };
-    const float *ts, *te, *sig, *rgb;
-    float thre;
-    float *colors, *opac, *depth;  // [R,3], [R], [R] in/out
-    unsigned long long *n_visible;  // [NFA_VISIBLE_SLOTS] += samples that pass the alpha threshold (the loop's sample count), or null
-    float xs[SE], mid[SE], pf[SE], rw[SE], c[3 * SE];
-    bool keep[SE];
-    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
-    {
-        ld4<VEC>(ts, q, r.a);
-        ld4<VEC>(te, q, r.b);
-        ld4<VEC>(sig, q, r.s);
-        load_rgb12(rgb, VEC, q, r.c);
-    }
-    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
-    {
-        const bool *valid = pos.valid;
-        fix_rgb12(rgb, VEC, pos, r.c, c);
-#pragma unroll
-        for (int j = 0; j < SE; ++j) {
-            xs[j] = valid[j] ? r.s.v[j] * (r.b.v[j] - r.a.v[j]) : 0.0f;
-            mid[j] = (r.a.v[j] + r.b.v[j]) / 2.0f;
-        }
-    }
-    __device__ __forceinline__ void pre(int j, int64_t, bool valid, int rid) { pf[j] = valid ? 1.0f - opac[rid] : 1.0f; }
-    __device__ __forceinline__ void store_pre(const Pos &) const {}
-    __device__ __forceinline__ float x(int j, int) const { return xs[j]; }
-    __device__ __forceinline__ void emit(int j, int64_t, bool valid, bool is_head, int, int, const float *, const float prev[1])
-    {
-        const float S = is_head ? 0.0f : prev[0];
-        const float T = expf(-S) * pf[j];
-        const float a = 1.0f - expf(-xs[j]);
-        keep[j] = valid && !(thre > 0.0f && !(a >= thre));
-        rw[j] = keep[j] ? T * a : 0.0f;
-    }
-    __device__ __forceinline__ float xb(int j, int ch) const
-    {
-        return ch < 3 ? rw[j] * c[3 * j + ch] : (ch == 3 ? rw[j] : rw[j] * mid[j]);
-    }
-    __device__ __forceinline__ void ray_done_b(int rid, int ch, float t) const
-    {
-        if (ch < 3) colors[3 * (int64_t)rid + ch] += t;
-        else if (ch == 3) opac[rid] += t;
-        else depth[rid] += t;
-    }
-    __device__ __forceinline__ void store(const Pos &) const
-    {
-        if (n_visible) {
-            int c = 0;
-#pragma unroll
-            for (int j = 0; j < SE; ++j) c += __builtin_popcountll(__ballot(keep[j]));
-            // One counter per step was one ADDRESS for the whole launch: atomics on one address are served one after the
-            // other by its L2 channel (~15 ns each), and 33 k steps (8 M samples) made that 0.5 ms -- the whole pass.  The count
-            // is spread over NFA_VISIBLE_SLOTS counters by wave; the caller adds them up.
-            if (c > 0 && lane_id() == 0)
-                atomicAdd(n_visible + ((blockIdx.x * SEG_WAVES_PER_BLOCK + (threadIdx.x >> 6)) & (NFA_VISIBLE_SLOTS - 1)), (unsigned long long)c);
-        }
-    }
-};
-
-// ---- its backward in one reverse pass: the gradient of the three accumulations w.r.t. w is formed
-//      from the per-ray output gradients (needs the ray id before the scan: NEEDS_RID), added to the
-//      gradients arriving at extras' weights / trans / alphas, and pushed through the transmittance
-//      chain.  Same expressions as RenderAccumBwdOp followed by DensityBwdOp.
-template <bool VEC, bool EXTRA /* gradients arrive at weights / trans / alphas too */>
-struct RenderFusedBwdOp : OpBase {
-    static constexpr bool NEEDS_RID = true;
-    // (98 VGPRs without EXTRA: two over the 5-wave budget; asking for 5 waves was within noise)
-    // The per-ray output gradients (colour, opacity, depth: 5 floats per ray) are needed per ELEMENT, after the ray id is
-    // known: as global gathers they were a second, dependent memory latency in every step (12 gather instructions per lane
-    // and step; SQ counters: the pass waits 80 % of its wave-cycles, VALU 36 % busy).  The rays of a tile are consecutive,
-    // so the wave stages their gradients in LDS with coalesced loads at tile start (up to RAY_CAP rays, the rest falls
-    // back to the gathers) and the per-element reads are LDS reads.
-    static constexpr int RAY_CAP = 192;
-    static constexpr int RAY_LDS_FLOATS = 8 * RAY_CAP;   // {g_r, g_g, g_b, g_opacity, g_depth, -, -, -} per ray
-    static constexpr bool PIPE = true;   // measured per op: a full step ahead is 2-4 % faster here (313 -> 300 us), 2 % slower on the forward pass
-    struct Raw { F4 a, b, T, A, gw, gt, ga; float c[3 * SE]; };
-    const float *ts, *te, *rgb, *tr, *al, *gc, *go, *gd, *gw, *gt, *ga;
-    float *gsig, *grgb;
-    const float *g_lds = nullptr;
-    int32_t g_lo = 0, g_n = 0;
-    __device__ __forceinline__ void tile_begin(int32_t r_lo, int32_t r_hi, float *lds)
-    {
-        // (the pass runs from the tile's last ray to its first: when the tile owns more than RAY_CAP rays the stage holds
-        //  the LAST ones, which most of its elements belong to)
-        g_lds = lds; g_n = min(r_hi - r_lo, RAY_CAP); g_lo = r_hi - g_n;
-        __builtin_amdgcn_wave_barrier();
-        for (int32_t i = lane_id(); i < g_n; i += 64) {
-            const int64_t r = (int64_t)g_lo + i;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (gc) { v.x = gc[3 * r]; v.y = gc[3 * r + 1]; v.z = gc[3 * r + 2]; }
-            if (go) v.w = go[r];
-            *reinterpret_cast<float4 *>(lds + 8 * i) = v;
-            lds[8 * i + 4] = gd ? gd[r] : 0.0f;
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    float T[SE], A[SE], GW[SE], GT[SE], GA[SE], dlt[SE], mid[SE], q[SE], rs[SE], c[3 * SE], gr[3 * SE];
-    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
-    {
-        ld4<VEC>(ts, q, r.a);
-        ld4<VEC>(te, q, r.b);
-        ld4<VEC>(tr, q, r.T);
-        ld4<VEC>(al, q, r.A);
-        if (EXTRA) {
-            if (gw) ld4<VEC>(gw, q, r.gw);
-            if (gt) ld4<VEC>(gt, q, r.gt);
-            if (ga) ld4<VEC>(ga, q, r.ga);
-        }
-        load_rgb12(rgb, VEC, q, r.c);
-    }
-    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
-    {
-        const bool *valid = pos.valid;
-        fix_rgb12(rgb, VEC, pos, r.c, c);
-#pragma unroll
-        for (int j = 0; j < SE; ++j) {
-            T[j] = sel(r.T, j, valid, 0.0f); A[j] = sel(r.A, j, valid, 0.0f);
-            GW[j] = (EXTRA && gw && valid[j]) ? r.gw.v[j] : 0.0f;
-            GT[j] = (EXTRA && gt && valid[j]) ? r.gt.v[j] : 0.0f;
-            GA[j] = (EXTRA && ga && valid[j]) ? r.ga.v[j] : 0.0f;
-            dlt[j] = r.b.v[j] - r.a.v[j];
-            mid[j] = (r.a.v[j] + r.b.v[j]) / 2.0f;
-        }
-    }
-    __device__ __forceinline__ void pre(int j, int64_t, bool valid, int rid)
-    {
-        float g = 0.0f;
-        gr[3 * j] = gr[3 * j + 1] = gr[3 * j + 2] = 0.0f;
-        const float wj = T[j] * A[j];
-        if (valid) {
-            const uint32_t slot = (uint32_t)(rid - g_lo);
-            float g0, g1, g2, g3, g4;
-            if (slot < (uint32_t)g_n) {   // staged (the usual case)
-                const float4 v = *reinterpret_cast<const float4 *>(g_lds + 8 * slot);
-                g0 = v.x; g1 = v.y; g2 = v.z; g3 = v.w; g4 = g_lds[8 * slot + 4];
-            } else {
-                g0 = gc ? gc[3 * (int64_t)rid] : 0.0f; g1 = gc ? gc[3 * (int64_t)rid + 1] : 0.0f; g2 = gc ? gc[3 * (int64_t)rid + 2] : 0.0f;
-                g3 = go ? go[rid] : 0.0f; g4 = gd ? gd[rid] : 0.0f;
-            }
-            if (gc) {
-                g += g0 * c[3 * j] + g1 * c[3 * j + 1] + g2 * c[3 * j + 2];
-                gr[3 * j] = g0 * wj; gr[3 * j + 1] = g1 * wj; gr[3 * j + 2] = g2 * wj;
-            }
-            if (go) g += g3;
-            if (gd) g += g4 * mid[j];
-        }
-        GW[j] = g + GW[j];
-        q[j] = GW[j] * wj + GT[j] * T[j];
-    }
-    // g_rgb is complete before the scan: stored first (frees its registers, stores in flight during the scan)
-    __device__ __forceinline__ void store_pre(const Pos &pq)
-    {
-        if (grgb) store_rgb12(grgb, VEC, pq, gr);
-    }
-    __device__ __forceinline__ float x(int j, int) const { return q[j]; }
-    __device__ __forceinline__ void emit(int j, int64_t, bool, bool is_head, int, int, const float *, const float prev[1])
-    {
-        const float E = is_head ? 0.0f : prev[0];
-        const float om = 1.0f - A[j];
-        const float Bv = GW[j] * T[j] * om + GA[j] * om - E;
-        rs[j] = dlt[j] * Bv;
-    }
-    __device__ __forceinline__ void store(const Pos &pq)
-    {
-        if (gsig) store4<VEC>(gsig, pq, rs);
-    }
-};
-
-// ---- `rendering` from the field's RAW outputs: the two passes above with the field's last activations applied on load
-//      (examples/radiance_fields/ngp.py:23-36,174-175,196: density = trunc_exp(x - 1) * selector, rgb = sigmoid(x)).
-//      The activation kind is a member, so its branch is wave-uniform; with NFA_ACT_NONE, bias 0 and no mask both passes
-//      compute what RenderFusedFwdOp / RenderFusedBwdOp compute, bit for bit.  The backward keeps no activated value:
-//      it forms sigma, alpha and c again from the raw ones with the forward's expressions.
-//      Compiler's report (VEC forms, no scratch in any): forward 91 VGPRs against RenderFusedFwdOp's 81, both 5 waves per
-//      SIMD; backward 124 against RenderFusedBwdOp's 117 (4 waves), with EXTRA 147 against 137 (3 waves).
 // Half twins of ld4 / store4 / load_rgb12 / fix_rgb12 / store_rgb12 for raw streams of E = fp16 or bf16 (common.hip.h).  A
 // lane's 4 elements are 8 bytes, its 4 colours 24: with VEC (the stream 8-byte aligned) one and three 8-byte vectors, raw
 // like the float loads -- the halves are widened where they are consumed (elem / fix_rgb12), not behind the load.
@@ -1714,7 +1538,232 @@ __device__ __forceinline__ void store_rgb12(E *rgb, bool vec, const Pos &q, cons
 // what an op keeps of a step's raw loads from a stream of E
 template <class E> struct RawStream { typedef H4<E> S4; typedef H12<E> C12; };
 template <> struct RawStream<float> { typedef F4 S4; typedef float C12[3 * SE]; };
+template <class E> using Quad = typename RawStream<E>::S4;    // a lane's 4 elements of a step
+template <class E> using Rgb12 = typename RawStream<E>::C12;  // its 4 colours
 
+// ---- the three accumulations of `rendering` fused: colours(3), opacity, depth  (volrend.py:140-151)
+template <bool VEC>
+struct RenderAccumOp : OpBase, RayOut {
+    static constexpr int NCH = 5;
+    static constexpr bool TOTALS = true;
+    struct Raw { Quad<float> w, a, b; Rgb12<float> c; };
+    const float *w, *rgb, *ts, *te;
+    float xv[SE][5];
+    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
+    {
+        ld4<VEC>(w, q, r.w);
+        ld4<VEC>(ts, q, r.a);
+        ld4<VEC>(te, q, r.b);
+        load_rgb12(rgb, VEC, q, r.c);
+    }
+    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
+    {
+        const bool *valid = pos.valid;
+        float c[3 * SE];
+        fix_rgb12(rgb, VEC, pos, r.c, c);
+#pragma unroll
+        for (int j = 0; j < SE; ++j) {
+            const float ww = sel(r.w, j, valid, 0.0f);
+#pragma unroll
+            for (int ch = 0; ch < 5; ++ch) xv[j][ch] = render_channel(ch, ww, c + 3 * j, midpoint(r.a.v[j], r.b.v[j]));
+        }
+    }
+    __device__ __forceinline__ float x(int j, int ch) const { return xv[j][ch]; }
+    __device__ __forceinline__ void emit(int, int64_t, bool, bool, int, int, const float *, const float *) const {}
+    __device__ __forceinline__ void store(const Pos &) const {}
+    __device__ __forceinline__ void ray_done(int rid, const float t[5]) const { ray_store(rid, t); }
+    __device__ __forceinline__ void empty_ray(int rid) const { ray_zero(rid); }
+};
+
+template <bool VEC>
+struct RenderAccumBwdOp : OpBase, RayGrads {
+    struct Raw { Quad<float> w, a, b; Rgb12<float> c; };
+    const float *w, *rgb, *ts, *te;
+    float *gw, *grgb;
+    float ww[SE], mid[SE], res[SE], c[3 * SE], gr[3 * SE];
+    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
+    {
+        ld4<VEC>(w, q, r.w);
+        ld4<VEC>(ts, q, r.a);
+        ld4<VEC>(te, q, r.b);
+        load_rgb12(rgb, VEC, q, r.c);
+    }
+    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
+    {
+#pragma unroll
+        for (int j = 0; j < SE; ++j) { ww[j] = r.w.v[j]; mid[j] = midpoint(r.a.v[j], r.b.v[j]); }
+        fix_rgb12(rgb, VEC, pos, r.c, c);
+    }
+    __device__ __forceinline__ float x(int, int) const { return 0.0f; }
+    __device__ __forceinline__ void emit(int j, int64_t, bool valid, bool, int rid, int, const float *, const float *)
+    {
+        res[j] = sample_grads(*this, valid, rid, c + 3 * j, ww[j], mid[j], gr + 3 * j);
+    }
+    __device__ __forceinline__ void store(const Pos &q)
+    {
+        if (gw) store4<VEC>(gw, q, res);
+        if (grgb) store_rgb12(grgb, VEC, q, gr);
+    }
+};
+
+// ---- `rendering` with a density callback in ONE pass (volrend.py:109-151): stage A scans
+//      sigma*delta into transmittance -> (w, T, alpha); stage B scans w*rgb, w, w*mid into the per-ray
+//      colour / opacity / un-normalised depth.  Bit-identical to DensityFwdOp followed by
+//      RenderAccumOp (same expressions, same scan tree), 12 B/sample less traffic.
+template <bool VEC>
+struct RenderFusedFwdOp : RenderFwdStage, SampleOut {   // (81 VGPRs: one over the 6-wave budget; asking for 6 waves was within noise)
+    struct Raw { Quad<float> a, b, s; Rgb12<float> c; };
+    const float *ts, *te, *sig, *rgb;
+    float rt[SE], ra[SE];
+    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
+    {
+        ld4<VEC>(ts, q, r.a);
+        ld4<VEC>(te, q, r.b);
+        ld4<VEC>(sig, q, r.s);
+        load_rgb12(rgb, VEC, q, r.c);
+    }
+    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
+    {
+        fix_rgb12(rgb, VEC, pos, r.c, c);
+#pragma unroll
+        for (int j = 0; j < SE; ++j) sample(j, pos.valid[j], r.s.v[j], r.a.v[j], r.b.v[j]);
+    }
+    __device__ __forceinline__ void emit(int j, int64_t, bool, bool is_head, int, int, const float *, const float prev[1])
+    {
+        trans_alpha(is_head, prev, xs[j], rt[j], ra[j]);
+        rw[j] = rt[j] * ra[j];
+    }
+    __device__ __forceinline__ void ray_done_b(int rid, int ch, float t) const { ray_store(rid, ch, t); }
+    __device__ __forceinline__ void empty_ray(int rid) const { ray_zero(rid); }
+    __device__ __forceinline__ void store(const Pos &q) { store_wta<VEC>(q, rw, rt, ra); }
+};
+
+// ---- one iteration of the test-mode marching loop (ref: examples/utils.py:370-405) in one pass: weights with
+//      prefix_trans = 1 - opacity[ray] (the ray id is known before the scan), samples with alpha < alpha_thre dropped,
+//      and rgb / opacity / depth accumulated IN PLACE into the per-ray image buffers.  Nothing per sample is written.
+//      A ray is owned by one wave, which reads its old opacity for all the ray's samples before it adds the total.
+template <bool VEC>
+struct RenderStepOp : RenderFwdStage {
+    static constexpr bool NEEDS_RID = true;
+    struct Raw { Quad<float> a, b, s; Rgb12<float> c; };
+    const float *ts, *te, *sig, *rgb;
+    float thre;
+    unsigned long long *n_visible;  // [NFA_VISIBLE_SLOTS] += samples that pass the alpha threshold (the loop's sample count), or null
+    float pf[SE];
+    bool keep[SE];
+    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
+    {
+        ld4<VEC>(ts, q, r.a);
+        ld4<VEC>(te, q, r.b);
+        ld4<VEC>(sig, q, r.s);
+        load_rgb12(rgb, VEC, q, r.c);
+    }
+    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
+    {
+        fix_rgb12(rgb, VEC, pos, r.c, c);
+#pragma unroll
+        for (int j = 0; j < SE; ++j) sample(j, pos.valid[j], r.s.v[j], r.a.v[j], r.b.v[j]);
+    }
+    __device__ __forceinline__ void pre(int j, int64_t, bool valid, int rid) { pf[j] = valid ? 1.0f - opac[rid] : 1.0f; }
+    __device__ __forceinline__ void store_pre(const Pos &) const {}
+    __device__ __forceinline__ void emit(int j, int64_t, bool valid, bool is_head, int, int, const float *, const float prev[1])
+    {
+        float T, a;
+        trans_alpha(is_head, prev, xs[j], T, a);
+        T = T * pf[j];
+        keep[j] = valid && !(thre > 0.0f && !(a >= thre));
+        rw[j] = keep[j] ? T * a : 0.0f;
+    }
+    __device__ __forceinline__ void ray_done_b(int rid, int ch, float t) const { ray_add(rid, ch, t); }
+    __device__ __forceinline__ void store(const Pos &) const
+    {
+        if (n_visible) {
+            int c = 0;
+#pragma unroll
+            for (int j = 0; j < SE; ++j) c += __builtin_popcountll(__ballot(keep[j]));
+            // One counter per step was one ADDRESS for the whole launch: atomics on one address are served one after the
+            // other by its L2 channel (~15 ns each), and 33 k steps (8 M samples) made that 0.5 ms -- the whole pass.  The count
+            // is spread over NFA_VISIBLE_SLOTS counters by wave; the caller adds them up.
+            if (c > 0 && lane_id() == 0)
+                atomicAdd(n_visible + ((blockIdx.x * SEG_WAVES_PER_BLOCK + (threadIdx.x >> 6)) & (NFA_VISIBLE_SLOTS - 1)), (unsigned long long)c);
+        }
+    }
+};
+
+// ---- what the one-pass backward ops share (one reverse pass): the gradient of the three accumulations w.r.t. w is formed
+//      from the per-ray output gradients (needs the ray id before the scan: NEEDS_RID), added to the gradients arriving at
+//      extras' weights / trans / alphas, and pushed through the transmittance chain.  Same expressions as
+//      RenderAccumBwdOp followed by DensityBwdOp.
+template <bool EXTRA /* gradients arrive at weights / trans / alphas too */>
+struct RenderBwdStage : OpBase, RayGradStage, ExtraGrads<EXTRA> {
+    static constexpr bool NEEDS_RID = true;
+    static constexpr int RAY_LDS_FLOATS = RayGradStage::LDS_FLOATS;
+    static constexpr bool PIPE = true;   // measured per op: a full step ahead is 2-4 % faster here (313 -> 300 us), 2 % slower on the forward pass
+    float T[SE], A[SE], GW[SE], GT[SE], GA[SE], dlt[SE], mid[SE], q[SE], rs[SE], c[3 * SE], gr[3 * SE];
+    // T, A, c and the extra gradients of the step are in place
+    __device__ __forceinline__ void sample(int j, float ts, float te) { dlt[j] = te - ts; mid[j] = midpoint(ts, te); }
+    __device__ __forceinline__ void pre(int j, int64_t, bool valid, int rid)
+    {
+        const float wj = T[j] * A[j];
+        GW[j] = sample_grads(*this, valid, rid, c + 3 * j, wj, mid[j], gr + 3 * j) + GW[j];
+        q[j] = chain_input(GW[j], GT[j], T[j], wj);
+    }
+    __device__ __forceinline__ float x(int j, int) const { return q[j]; }
+    __device__ __forceinline__ float chain(int j, bool is_head, const float prev[1]) const
+    {
+        return chain_grad(is_head, prev, GW[j], GA[j], T[j], A[j]);
+    }
+};
+
+template <bool VEC, bool EXTRA>
+struct RenderFusedBwdOp : RenderBwdStage<EXTRA> {   // (98 VGPRs without EXTRA: two over the 5-wave budget; asking for 5 waves was within noise)
+    typedef RenderBwdStage<EXTRA> S;
+    struct Raw { Quad<float> a, b, T, A; typename S::GRaw g; Rgb12<float> c; };
+    const float *ts, *te, *rgb, *tr, *al;
+    float *gsig, *grgb;
+    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
+    {
+        ld4<VEC>(ts, q, r.a);
+        ld4<VEC>(te, q, r.b);
+        ld4<VEC>(tr, q, r.T);
+        ld4<VEC>(al, q, r.A);
+        this->template fetch_extra<VEC>(q, r.g);
+        load_rgb12(rgb, VEC, q, r.c);
+    }
+    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
+    {
+        const bool *valid = pos.valid;
+        fix_rgb12(rgb, VEC, pos, r.c, S::c);
+#pragma unroll
+        for (int j = 0; j < SE; ++j) {
+            S::T[j] = sel(r.T, j, valid, 0.0f); S::A[j] = sel(r.A, j, valid, 0.0f);
+            this->select_extra(r.g, j, valid[j], S::GW[j], S::GT[j], S::GA[j]);
+            S::sample(j, r.a.v[j], r.b.v[j]);
+        }
+    }
+    // g_rgb is complete before the scan: stored first (frees its registers, stores in flight during the scan)
+    __device__ __forceinline__ void store_pre(const Pos &pq)
+    {
+        if (grgb) store_rgb12(grgb, VEC, pq, S::gr);
+    }
+    __device__ __forceinline__ void emit(int j, int64_t, bool, bool is_head, int, int, const float *, const float prev[1])
+    {
+        S::rs[j] = S::dlt[j] * S::chain(j, is_head, prev);
+    }
+    __device__ __forceinline__ void store(const Pos &pq)
+    {
+        if (gsig) store4<VEC>(gsig, pq, S::rs);
+    }
+};
+
+// ---- `rendering` from the field's RAW outputs: the two passes above with the field's last activations applied on load
+//      (examples/radiance_fields/ngp.py:23-36,174-175,196: density = trunc_exp(x - 1) * selector, rgb = sigmoid(x)).
+//      The activation kind is a member, so its branch is wave-uniform; with NFA_ACT_NONE, bias 0 and no mask both passes
+//      compute what RenderFusedFwdOp / RenderFusedBwdOp compute, bit for bit: they are the same shared steps around another
+//      load.  The backward keeps no activated value: it forms sigma, alpha and c again from the raw ones with the
+//      forward's expressions.
+//      Compiler's report (VEC forms, no scratch in any): forward 91 VGPRs against RenderFusedFwdOp's 81, both 5 waves per
+//      SIMD; backward 117 against RenderFusedBwdOp's 117 (4 waves), with EXTRA 141 against 136 (3 waves).
 struct RawAct {
     const uint8_t *mask;   // [n] bool, or null: where false the density is exactly 0 and so is its gradient
     int32_t mask_vec;      // mask is 4-byte aligned
@@ -1752,16 +1801,13 @@ struct RawAct {
 };
 
 template <bool VEC, class ET /* element type of sig / rgb / asig / argb */>
-struct RenderRawFwdOp : OpBase {
-    static constexpr int NCHB = 5;
-    struct Raw { F4 a, b; typename RawStream<ET>::S4 s; U4 m; typename RawStream<ET>::C12 c; };
+struct RenderRawFwdOp : RenderFwdStage, SampleOut {
+    struct Raw { Quad<float> a, b; Quad<ET> s; U4 m; Rgb12<ET> c; };
     const float *ts, *te;
     const ET *sig, *rgb;
     RawAct act;
-    float *w, *tr, *al;
     ET *asig, *argb;
-    float *colors, *opac, *depth;
-    float xs[SE], mid[SE], sg[SE], rw[SE], rt[SE], ra[SE], c[3 * SE];
+    float sg[SE], rt[SE], ra[SE];
     __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
     {
         ld4<VEC>(ts, q, r.a);
@@ -1772,97 +1818,54 @@ struct RenderRawFwdOp : OpBase {
     }
     __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
     {
-        const bool *valid = pos.valid;
         fix_rgb12(rgb, VEC, pos, r.c, c);
         act.colours(c);
 #pragma unroll
         for (int j = 0; j < SE; ++j) {
             sg[j] = act.live(r.m, j) ? act.density(elem(r.s, j) + act.bias) : 0.0f;
-            xs[j] = valid[j] ? sg[j] * (r.b.v[j] - r.a.v[j]) : 0.0f;
-            mid[j] = (r.a.v[j] + r.b.v[j]) / 2.0f;
+            sample(j, pos.valid[j], sg[j], r.a.v[j], r.b.v[j]);
         }
     }
-    __device__ __forceinline__ float x(int j, int) const { return xs[j]; }
     __device__ __forceinline__ void emit(int j, int64_t, bool, bool is_head, int, int, const float *, const float prev[1])
     {
-        const float S = is_head ? 0.0f : prev[0];
-        const float T = expf(-S);
-        const float a = 1.0f - expf(-xs[j]);
-        rt[j] = T; ra[j] = a; rw[j] = T * a;
+        trans_alpha(is_head, prev, xs[j], rt[j], ra[j]);
+        rw[j] = rt[j] * ra[j];
     }
-    __device__ __forceinline__ float xb(int j, int ch) const
-    {
-        return ch < 3 ? rw[j] * c[3 * j + ch] : (ch == 3 ? rw[j] : rw[j] * mid[j]);
-    }
-    __device__ __forceinline__ void ray_done_b(int rid, int ch, float t) const
-    {
-        if (ch < 3) colors[3 * (int64_t)rid + ch] = t;
-        else if (ch == 3) opac[rid] = t;
-        else depth[rid] = t;
-    }
-    __device__ __forceinline__ void empty_ray(int rid) const
-    {
-        colors[3 * (int64_t)rid] = 0.0f; colors[3 * (int64_t)rid + 1] = 0.0f; colors[3 * (int64_t)rid + 2] = 0.0f;
-        opac[rid] = 0.0f; depth[rid] = 0.0f;
-    }
+    __device__ __forceinline__ void ray_done_b(int rid, int ch, float t) const { ray_store(rid, ch, t); }
+    __device__ __forceinline__ void empty_ray(int rid) const { ray_zero(rid); }
     __device__ __forceinline__ void store(const Pos &q)
     {
-        if (w) store4<VEC>(w, q, rw);
-        if (tr) store4<VEC>(tr, q, rt);
-        if (al) store4<VEC>(al, q, ra);
+        store_wta<VEC>(q, rw, rt, ra);
         if (asig) store4<VEC>(asig, q, sg);
         if (argb) store_rgb12(argb, VEC, q, c);
     }
 };
 
-template <bool VEC, bool EXTRA /* gradients arrive at weights / trans / alphas too */, class ET /* of sig / rgb / gsig / grgb */>
-struct RenderRawBwdOp : OpBase {
-    static constexpr bool NEEDS_RID = true;
-    static constexpr int RAY_CAP = 192;                  // per-ray gradients staged in LDS: see RenderFusedBwdOp
-    static constexpr int RAY_LDS_FLOATS = 8 * RAY_CAP;   // {g_r, g_g, g_b, g_opacity, g_depth, -, -, -} per ray
-    static constexpr bool PIPE = true;
-    struct Raw { F4 a, b, T; typename RawStream<ET>::S4 s; F4 gw, gt, ga; U4 m; typename RawStream<ET>::C12 c; };
+template <bool VEC, bool EXTRA, class ET /* of sig / rgb / gsig / grgb */>
+struct RenderRawBwdOp : RenderBwdStage<EXTRA> {
+    typedef RenderBwdStage<EXTRA> S;
+    struct Raw { Quad<float> a, b, T; Quad<ET> s; typename S::GRaw g; U4 m; Rgb12<ET> c; };
     const float *ts, *te;
     const ET *sig, *rgb;
-    const float *tr, *gc, *go, *gd, *gw, *gt, *ga;
+    const float *tr;
     RawAct act;
     ET *gsig, *grgb;
-    const float *g_lds = nullptr;
-    int32_t g_lo = 0, g_n = 0;
-    __device__ __forceinline__ void tile_begin(int32_t r_lo, int32_t r_hi, float *lds)
-    {
-        g_lds = lds; g_n = min(r_hi - r_lo, RAY_CAP); g_lo = r_hi - g_n;   // (the LAST rays of the tile: the pass runs backwards)
-        __builtin_amdgcn_wave_barrier();
-        for (int32_t i = lane_id(); i < g_n; i += 64) {
-            const int64_t r = (int64_t)g_lo + i;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (gc) { v.x = gc[3 * r]; v.y = gc[3 * r + 1]; v.z = gc[3 * r + 2]; }
-            if (go) v.w = go[r];
-            *reinterpret_cast<float4 *>(lds + 8 * i) = v;
-            lds[8 * i + 4] = gd ? gd[r] : 0.0f;
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    float T[SE], A[SE], GW[SE], GT[SE], GA[SE], dlt[SE], mid[SE], ds[SE], q[SE], rs[SE], c[3 * SE], gr[3 * SE];
+    float ds[SE];
     __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
     {
         ld4<VEC>(ts, q, r.a);
         ld4<VEC>(te, q, r.b);
         ld4<VEC>(tr, q, r.T);
         ld4<VEC>(sig, q, r.s);
-        if (EXTRA) {
-            if (gw) ld4<VEC>(gw, q, r.gw);
-            if (gt) ld4<VEC>(gt, q, r.gt);
-            if (ga) ld4<VEC>(ga, q, r.ga);
-        }
+        this->template fetch_extra<VEC>(q, r.g);
         if (act.mask) load_mask4(act.mask, act.mask_vec != 0, q, r.m);
         load_rgb12(rgb, VEC, q, r.c);
     }
     __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
     {
         const bool *valid = pos.valid;
-        fix_rgb12(rgb, VEC, pos, r.c, c);
-        act.colours(c);
+        fix_rgb12(rgb, VEC, pos, r.c, S::c);
+        act.colours(S::c);
 #pragma unroll
         for (int j = 0; j < SE; ++j) {
             // sigma and alpha as the forward pass formed them
@@ -1870,60 +1873,31 @@ struct RenderRawBwdOp : OpBase {
             const float z = elem(r.s, j) + act.bias;
             const float s = on ? act.density(z) : 0.0f;
             ds[j] = (on && valid[j]) ? act.density_grad(z, s) : 0.0f;
-            dlt[j] = r.b.v[j] - r.a.v[j];
-            const float xs = valid[j] ? s * dlt[j] : 0.0f;
-            T[j] = sel(r.T, j, valid, 0.0f); A[j] = valid[j] ? 1.0f - expf(-xs) : 0.0f;
-            GW[j] = (EXTRA && gw && valid[j]) ? r.gw.v[j] : 0.0f;
-            GT[j] = (EXTRA && gt && valid[j]) ? r.gt.v[j] : 0.0f;
-            GA[j] = (EXTRA && ga && valid[j]) ? r.ga.v[j] : 0.0f;
-            mid[j] = (r.a.v[j] + r.b.v[j]) / 2.0f;
+            S::sample(j, r.a.v[j], r.b.v[j]);
+            S::T[j] = sel(r.T, j, valid, 0.0f); S::A[j] = valid[j] ? alpha_of(sigma_delta(valid[j], s, S::dlt[j])) : 0.0f;
+            this->select_extra(r.g, j, valid[j], S::GW[j], S::GT[j], S::GA[j]);
         }
     }
-    __device__ __forceinline__ void pre(int j, int64_t, bool valid, int rid)
+    __device__ __forceinline__ void pre(int j, int64_t pos, bool valid, int rid)
     {
-        float g = 0.0f;
-        gr[3 * j] = gr[3 * j + 1] = gr[3 * j + 2] = 0.0f;
-        const float wj = T[j] * A[j];
-        if (valid) {
-            const uint32_t slot = (uint32_t)(rid - g_lo);
-            float g0, g1, g2, g3, g4;
-            if (slot < (uint32_t)g_n) {   // staged (the usual case)
-                const float4 v = *reinterpret_cast<const float4 *>(g_lds + 8 * slot);
-                g0 = v.x; g1 = v.y; g2 = v.z; g3 = v.w; g4 = g_lds[8 * slot + 4];
-            } else {
-                g0 = gc ? gc[3 * (int64_t)rid] : 0.0f; g1 = gc ? gc[3 * (int64_t)rid + 1] : 0.0f; g2 = gc ? gc[3 * (int64_t)rid + 2] : 0.0f;
-                g3 = go ? go[rid] : 0.0f; g4 = gd ? gd[rid] : 0.0f;
-            }
-            if (gc) {
-                g += g0 * c[3 * j] + g1 * c[3 * j + 1] + g2 * c[3 * j + 2];
-                gr[3 * j] = g0 * wj; gr[3 * j + 1] = g1 * wj; gr[3 * j + 2] = g2 * wj;
-                if (act.col == NFA_RGB_ACT_SIGMOID) {   // d sigmoid = c (1 - c)
+        S::pre(j, pos, valid, rid);
+        if (valid && S::gc && act.col == NFA_RGB_ACT_SIGMOID) {   // d sigmoid = c (1 - c)
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) gr[3 * j + k] *= c[3 * j + k] * (1.0f - c[3 * j + k]);
-                }
-            }
-            if (go) g += g3;
-            if (gd) g += g4 * mid[j];
+            for (int k = 0; k < 3; ++k) S::gr[3 * j + k] *= S::c[3 * j + k] * (1.0f - S::c[3 * j + k]);
         }
-        GW[j] = g + GW[j];
-        q[j] = GW[j] * wj + GT[j] * T[j];
     }
     __device__ __forceinline__ void store_pre(const Pos &pq)
     {
-        if (grgb) store_rgb12(grgb, VEC, pq, gr);
+        if (grgb) store_rgb12(grgb, VEC, pq, S::gr);
     }
-    __device__ __forceinline__ float x(int j, int) const { return q[j]; }
     __device__ __forceinline__ void emit(int j, int64_t, bool, bool is_head, int, int, const float *, const float prev[1])
     {
-        const float E = is_head ? 0.0f : prev[0];
-        const float om = 1.0f - A[j];
-        const float Bv = GW[j] * T[j] * om + GA[j] * om - E;
         // (a select, not a product: where the derivative is 0 -- a masked sample -- the gradient is exactly 0)
-        rs[j] = ds[j] != 0.0f ? dlt[j] * Bv * ds[j] : 0.0f;
+        S::rs[j] = ds[j] != 0.0f ? S::dlt[j] * S::chain(j, is_head, prev) * ds[j] : 0.0f;
     }
     __device__ __forceinline__ void store(const Pos &pq)
     {
-        if (gsig) store4<VEC>(gsig, pq, rs);
+        if (gsig) store4<VEC>(gsig, pq, S::rs);
     }
 };
 
@@ -2225,6 +2199,52 @@ using namespace nfa;
     if (n_elems == 0 && n_rays == 0) return NFA_OK;                                                      \
     NFA_REQUIRE(packed_info && tiles && n_tiles >= 1, name ": packed_info/tiles is null")
 
+// A half stream takes the vector form when its quads are 8-byte aligned
+static inline bool aligned_quads(const float *p) { return aligned16(p); }
+static inline bool aligned_quads(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+// The one-pass rendering ops, RenderFused*Op and RenderRaw*Op<E>, share most of their streams.  One launch helper per
+// direction tests the alignment (own_aligned: that of the streams only the caller's op has), picks the op's compile-time
+// form -- make(V) / make(V, X) returns the op with its own members filled -- fills the shared members and launches.
+template <class E, class Make>
+static int launch_render_fwd(const char *name, Make &&make, bool own_aligned, const float *t_starts, const float *t_ends, const E *sigmas,
+                             const E *rgbs, float *weights, float *trans, float *alphas, float *colors, float *opacities,
+                             float *depths, const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays,
+                             nfa_stream_t stream)
+{
+    const bool vec = own_aligned && all_aligned16(t_starts, t_ends, weights, trans, alphas) && aligned_quads(sigmas) && aligned_quads(rgbs);
+    dispatch_bool(vec, [&](auto V) {
+        auto op = make(V);
+        op.ts = t_starts; op.te = t_ends; op.sig = sigmas; op.rgb = rgbs; op.w = weights; op.tr = trans; op.al = alphas;
+        op.colors = colors; op.opac = opacities; op.depth = depths;
+        launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, as_stream(stream));
+    });
+    NFA_CHECK_LAUNCH(name);
+    return NFA_OK;
+}
+
+template <class E, class Make>
+static int launch_render_bwd(const char *name, Make &&make, bool own_aligned, const float *t_starts, const float *t_ends, const E *rgbs,
+                             const float *trans, const float *g_colors, const float *g_opacities, const float *g_depths,
+                             const float *g_weights, const float *g_trans, const float *g_alphas, E *grad_sigmas, E *grad_rgbs,
+                             const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays, nfa_stream_t stream)
+{
+    const bool vec = own_aligned && all_aligned16(t_starts, t_ends, trans, g_weights, g_trans, g_alphas) && aligned_quads(rgbs) &&
+                     aligned_quads(grad_sigmas) && aligned_quads(grad_rgbs);
+    const bool extra = g_weights || g_trans || g_alphas;
+    dispatch_bool(vec, [&](auto V) {
+        dispatch_bool(extra, [&](auto X) {
+            auto op = make(V, X);
+            op.ts = t_starts; op.te = t_ends; op.rgb = rgbs; op.tr = trans;
+            op.gc = g_colors; op.go = g_opacities; op.gd = g_depths; op.gw = g_weights; op.gt = g_trans; op.ga = g_alphas;
+            op.gsig = grad_sigmas; op.grgb = grad_rgbs;
+            launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, as_stream(stream));
+        });
+    });
+    NFA_CHECK_LAUNCH(name);
+    return NFA_OK;
+}
+
 extern "C" {
 
 void nfa_seg_plan(int64_t n_elems, int64_t n_rays, int64_t *tile_elems, int64_t *n_tiles)
@@ -2286,12 +2306,11 @@ int nfa_packed_scan_generic(int kind, int reverse, int normalize, const int64_t 
     NFA_REQUIRE(packed_info && inputs && outputs, "packed_scan_generic: null pointer");
     hipStream_t s = as_stream(stream);
     const unsigned grid = grid_1d(n_rays * 64, 256, 1 << 16);
-    switch (kind) {
-        case 0: hipLaunchKernelGGL((generic_scan_kernel<false, false>), dim3(grid), dim3(256), 0, s, packed_info, n_rays, inputs, outputs, reverse, normalize); break;
-        case 1: hipLaunchKernelGGL((generic_scan_kernel<true, false>), dim3(grid), dim3(256), 0, s, packed_info, n_rays, inputs, outputs, reverse, normalize); break;
-        case 2: hipLaunchKernelGGL((generic_scan_kernel<false, true>), dim3(grid), dim3(256), 0, s, packed_info, n_rays, inputs, outputs, reverse, normalize); break;
-        default: hipLaunchKernelGGL((generic_scan_kernel<true, true>), dim3(grid), dim3(256), 0, s, packed_info, n_rays, inputs, outputs, reverse, normalize); break;
-    }
+    dispatch_bool(kind & 1, [&](auto EX) {
+        dispatch_bool(kind >= 2, [&](auto PR) {
+            hipLaunchKernelGGL((generic_scan_kernel<EX, PR>), dim3(grid), dim3(256), 0, s, packed_info, n_rays, inputs, outputs, reverse, normalize);
+        });
+    });
     NFA_CHECK_LAUNCH("packed_scan_generic");
     return NFA_OK;
 }
@@ -2606,16 +2625,8 @@ int nfa_render_fused_fwd(const float *t_starts, const float *t_ends, const float
     if (n_rays == 0) return NFA_OK;
     NFA_REQUIRE(colors && opacities && depths && (n_elems == 0 || (t_starts && t_ends && sigmas && rgbs)),
                 "render_fused_fwd: null pointer");
-    hipStream_t s = as_stream(stream);
-    const bool vec = all_aligned16(t_starts, t_ends, sigmas, rgbs, weights, trans, alphas);
-    dispatch_bool(vec, [&](auto V) {
-        RenderFusedFwdOp<V> op;
-        op.ts = t_starts; op.te = t_ends; op.sig = sigmas; op.rgb = rgbs; op.w = weights; op.tr = trans; op.al = alphas;
-        op.colors = colors; op.opac = opacities; op.depth = depths;
-        launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
-    });
-    NFA_CHECK_LAUNCH("render_fused_fwd");
-    return NFA_OK;
+    return launch_render_fwd("render_fused_fwd", [](auto V) { return RenderFusedFwdOp<V>(); }, true, t_starts, t_ends, sigmas, rgbs,
+                             weights, trans, alphas, colors, opacities, depths, packed_info, tiles, n_tiles, n_rays, stream);
 }
 
 int nfa_render_fused_bwd(const float *t_starts, const float *t_ends, const float *rgbs, const float *trans, const float *alphas,
@@ -2627,20 +2638,9 @@ int nfa_render_fused_bwd(const float *t_starts, const float *t_ends, const float
     SEG_COMMON_CHECKS("render_fused_bwd");
     if (n_elems == 0) return NFA_OK;
     NFA_REQUIRE(t_starts && t_ends && rgbs && trans && alphas && (grad_sigmas || grad_rgbs), "render_fused_bwd: null pointer");
-    hipStream_t s = as_stream(stream);
-    const bool vec = all_aligned16(t_starts, t_ends, rgbs, trans, alphas, g_weights, g_trans, g_alphas, grad_sigmas, grad_rgbs);
-    const bool extra = g_weights || g_trans || g_alphas;
-    dispatch_bool(vec, [&](auto V) {
-        dispatch_bool(extra, [&](auto X) {
-            RenderFusedBwdOp<V, X> op;
-            op.ts = t_starts; op.te = t_ends; op.rgb = rgbs; op.tr = trans; op.al = alphas;
-            op.gc = g_colors; op.go = g_opacities; op.gd = g_depths; op.gw = g_weights; op.gt = g_trans; op.ga = g_alphas;
-            op.gsig = grad_sigmas; op.grgb = grad_rgbs;
-            launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s);
-        });
-    });
-    NFA_CHECK_LAUNCH("render_fused_bwd");
-    return NFA_OK;
+    return launch_render_bwd("render_fused_bwd", [&](auto V, auto X) { RenderFusedBwdOp<V, X> op; op.al = alphas; return op; },
+                             aligned16(alphas), t_starts, t_ends, rgbs, trans, g_colors, g_opacities, g_depths, g_weights, g_trans,
+                             g_alphas, grad_sigmas, grad_rgbs, packed_info, tiles, n_tiles, n_rays, stream);
 }
 
 static RawAct raw_act(const uint8_t *selector, int32_t density_act, float density_bias, int32_t rgb_act)
@@ -2656,9 +2656,6 @@ static RawAct raw_act(const uint8_t *selector, int32_t density_act, float densit
     NFA_REQUIRE(rgb_act == NFA_RGB_ACT_NONE || rgb_act == NFA_RGB_ACT_SIGMOID, name ": rgb_act must be 0 or 1 (got %d)", (int)rgb_act)
 
 extern "C++" {   // one implementation per element type
-// A half stream takes the vector form when its quads are 8-byte aligned
-static inline bool aligned_quads(const float *p) { return aligned16(p); }
-static inline bool aligned_quads(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 template <class E>
 static int render_raw_fwd(const float *t_starts, const float *t_ends, const E *raw_sigmas, const E *raw_rgbs,
@@ -2672,19 +2669,10 @@ static int render_raw_fwd(const float *t_starts, const float *t_ends, const E *r
     if (n_rays == 0) return NFA_OK;
     NFA_REQUIRE(colors && opacities && depths && (n_elems == 0 || (t_starts && t_ends && raw_sigmas && raw_rgbs)),
                 "render_raw_fwd: null pointer");
-    hipStream_t s = as_stream(stream);
-    const bool vec = all_aligned16(t_starts, t_ends, weights, trans, alphas) && aligned_quads(raw_sigmas) &&
-                     aligned_quads(raw_rgbs) && aligned_quads(act_sigmas) && aligned_quads(act_rgbs);
-    dispatch_bool(vec, [&](auto V) {
-        RenderRawFwdOp<V, E> op;
-        op.ts = t_starts; op.te = t_ends; op.sig = raw_sigmas; op.rgb = raw_rgbs;
-        op.act = raw_act(selector, density_act, density_bias, rgb_act);
-        op.w = weights; op.tr = trans; op.al = alphas; op.asig = act_sigmas; op.argb = act_rgbs;
-        op.colors = colors; op.opac = opacities; op.depth = depths;
-        launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
-    });
-    NFA_CHECK_LAUNCH("render_raw_fwd");
-    return NFA_OK;
+    const RawAct act = raw_act(selector, density_act, density_bias, rgb_act);
+    auto make = [&](auto V) { RenderRawFwdOp<V, E> op; op.act = act; op.asig = act_sigmas; op.argb = act_rgbs; return op; };
+    return launch_render_fwd("render_raw_fwd", make, aligned_quads(act_sigmas) && aligned_quads(act_rgbs), t_starts, t_ends, raw_sigmas,
+                             raw_rgbs, weights, trans, alphas, colors, opacities, depths, packed_info, tiles, n_tiles, n_rays, stream);
 }
 
 template <class E>
@@ -2700,22 +2688,11 @@ static int render_raw_bwd(const float *t_starts, const float *t_ends, const E *r
     if (n_elems == 0) return NFA_OK;
     NFA_REQUIRE(t_starts && t_ends && raw_sigmas && raw_rgbs && trans && (grad_raw_sigmas || grad_raw_rgbs),
                 "render_raw_bwd: null pointer");
-    hipStream_t s = as_stream(stream);
-    const bool vec = all_aligned16(t_starts, t_ends, trans, g_weights, g_trans, g_alphas) && aligned_quads(raw_sigmas) &&
-                     aligned_quads(raw_rgbs) && aligned_quads(grad_raw_sigmas) && aligned_quads(grad_raw_rgbs);
-    const bool extra = g_weights || g_trans || g_alphas;
-    dispatch_bool(vec, [&](auto V) {
-        dispatch_bool(extra, [&](auto X) {
-            RenderRawBwdOp<V, X, E> op;
-            op.ts = t_starts; op.te = t_ends; op.sig = raw_sigmas; op.rgb = raw_rgbs; op.tr = trans;
-            op.act = raw_act(selector, density_act, density_bias, rgb_act);
-            op.gc = g_colors; op.go = g_opacities; op.gd = g_depths; op.gw = g_weights; op.gt = g_trans; op.ga = g_alphas;
-            op.gsig = grad_raw_sigmas; op.grgb = grad_raw_rgbs;
-            launch_seg<-1>(op, packed_info, tiles, n_rays, n_tiles, s);
-        });
-    });
-    NFA_CHECK_LAUNCH("render_raw_bwd");
-    return NFA_OK;
+    const RawAct act = raw_act(selector, density_act, density_bias, rgb_act);
+    auto make = [&](auto V, auto X) { RenderRawBwdOp<V, X, E> op; op.sig = raw_sigmas; op.act = act; return op; };
+    return launch_render_bwd("render_raw_bwd", make, aligned_quads(raw_sigmas), t_starts, t_ends, raw_rgbs, trans, g_colors, g_opacities,
+                             g_depths, g_weights, g_trans, g_alphas, grad_raw_sigmas, grad_raw_rgbs, packed_info, tiles, n_tiles, n_rays,
+                             stream);
 }
 
 }  // extern "C++"

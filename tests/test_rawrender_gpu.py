@@ -274,3 +274,59 @@ def test_other_inputs_take_the_torch_composition(dev, monkeypatch):
     assert torch.allclose(colors, want["colors"], rtol=1e-4, atol=1e-5) and torch.allclose(opac, want["opacities"], rtol=1e-4, atol=1e-5)
     (g,) = torch.autograd.grad(opac.sum(), ts)
     assert bool(torch.isfinite(g).all())
+
+
+PARTIAL_LOSSES = {"opacity": lambda colors, opac, depth: opac.sum(),
+                  "depth": lambda colors, opac, depth: depth.sum(),
+                  "colour_and_opacity": lambda colors, opac, depth: (colors ** 2).sum() + opac.sum()}
+
+
+@pytest.mark.parametrize("loss", list(PARTIAL_LOSSES))
+def test_partial_losses_give_the_same_gradients_on_all_three_paths(dev, monkeypatch, loss):
+    """A gradient that arrives only at opacity, only at depth (through its normalisation: at opacity and the raw depth),
+    or at colours and opacity: the passes then run without some of the per-ray gradient arrays (null pointers).  The
+    fused pass, the two-pass composition and rendering_from_raw without activations must agree bit for bit."""
+    c = case(dev)
+    sig = (c["raw_sig"].abs() * 0.3).contiguous()
+    rgb = torch.sigmoid(c["raw_rgb"])
+    R = c["rays"].R
+    log = CallLog(monkeypatch)
+
+    def grads(render):
+        s, r = sig.clone().requires_grad_(True), rgb.clone().requires_grad_(True)
+        colors, opac, depth = render(s, r)
+        return torch.autograd.grad(PARTIAL_LOSSES[loss](colors, opac, depth), [s, r], allow_unused=True)
+
+    def rendering(fuse):
+        def render(s, r):
+            na.volrend.FUSE_RENDERING = fuse
+            try:
+                return na.rendering(c["ts"], c["te"], c["ri"], n_rays=R, rgb_sigma_fn=lambda *_: (r, s))[:3]
+            finally:
+                na.volrend.FUSE_RENDERING = True
+        return render
+
+    def from_raw(s, r):
+        return rendering_from_raw(c["ts"], c["te"], r, s, c["ri"], R, density_activation="none", density_bias=0.0,
+                                  rgb_activation="none", selector=None)[:3]
+
+    fused, two_pass, raw = grads(rendering(True)), grads(rendering(False)), grads(from_raw)
+    names = log.names()
+    assert [n for n in names if n.endswith("_bwd")] == ["nfa_render_fused_bwd", "nfa_render_accumulate_bwd",
+                                                        "nfa_render_from_density_bwd", "nfa_render_raw_bwd"]
+    # which per-ray gradients reached the passes: (g_colors, g_opacities, g_depths)
+    present = {"opacity": (False, True, False), "depth": (False, True, True), "colour_and_opacity": (True, True, False)}[loss]
+    by_name = dict(log.calls)
+    for entry, first in (("nfa_render_fused_bwd", 5), ("nfa_render_accumulate_bwd", 4), ("nfa_render_raw_bwd", 9)):
+        assert tuple(p is not None for p in by_name[entry][first:first + 3]) == present, entry
+
+    def is_zero(g):
+        return g is None or not bool(g.any())
+
+    for which, a, b, d in zip(("g_sigmas", "g_rgbs"), fused, two_pass, raw):
+        if any(is_zero(g) for g in (a, b, d)):
+            assert is_zero(a) and is_zero(b) and is_zero(d), (loss, which)
+        else:
+            assert torch.equal(a, b) and torch.equal(a, d), (loss, which)
+    assert not is_zero(fused[0])                             # every one of these losses depends on the densities
+    assert is_zero(fused[1]) == (not present[0])             # and on the colours only through `colors`
