@@ -410,6 +410,14 @@ int nfa_render_visibility(const float *t_starts, const float *t_ends, const floa
                           const float *prefix_trans, float early_stop_eps, float alpha_thre,
                           const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays,
                           int64_t n_elems, uint8_t *vis, int64_t *vis_cnts, nfa_stream_t stream);
+/* Constant-step samples: the `_cs` entries are their siblings with `t_ends` replaced by `step`, for samples that satisfy
+ * t_ends[i] == t_starts[i] + step (one fp32 add) for every i -- what the constant-step sampler (step_size > 0, no cone
+ * angle) emits.  The t_ends stream is not read (4 bytes per sample less traffic); given such samples every result is
+ * bit-identical to the sibling's.  step must be finite and > 0; densities only (t_starts is required). */
+int nfa_render_visibility_cs(const float *t_starts, float step, const float *sigmas, const float *prefix_trans,
+                             float early_stop_eps, float alpha_thre, const int64_t *packed_info, const int64_t *tiles,
+                             int64_t n_tiles, int64_t n_rays, int64_t n_elems, uint8_t *vis, int64_t *vis_cnts,
+                             nfa_stream_t stream);
 /* Boolean-mask compaction of (ray_indices, t_starts, t_ends) with known per-ray output offsets (ref: estimators/
  * occ_grid.py:216-220, three boolean-index gathers).  capacity: elements the output arrays hold; nothing is written at or
  * beyond it (a caller that sized them from the previous batch, before this batch's total reached the host, repeats the call
@@ -463,6 +471,17 @@ int nfa_render_fused_bwd(const float *t_starts, const float *t_ends, const float
                          const float *g_alphas, const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles,
                          int64_t n_rays, int64_t n_elems, float *grad_sigmas, float *grad_rgbs,
                          nfa_stream_t stream);
+/* The two passes for constant-step samples (see nfa_render_visibility_cs). */
+int nfa_render_fused_fwd_cs(const float *t_starts, float step, const float *sigmas, const float *rgbs,
+                            const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays,
+                            int64_t n_elems, float *weights, float *trans, float *alphas, float *colors,
+                            float *opacities, float *depths, nfa_stream_t stream);
+int nfa_render_fused_bwd_cs(const float *t_starts, float step, const float *rgbs, const float *trans,
+                            const float *alphas, const float *g_colors, const float *g_opacities,
+                            const float *g_depths, const float *g_weights, const float *g_trans,
+                            const float *g_alphas, const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles,
+                            int64_t n_rays, int64_t n_elems, float *grad_sigmas, float *grad_rgbs,
+                            nfa_stream_t stream);
 
 /* `rendering` from the field's RAW outputs (ref: volrend.py:109-151 with the activations of
  * examples/radiance_fields/ngp.py:23-36,174-175,196 applied on load): nfa_render_fused_fwd with

@@ -94,6 +94,7 @@ _SIGS = {
     "nfa_density_cdf_rows_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp],
     "nfa_render_from_alpha_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp],
     "nfa_render_visibility": [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp],
+    "nfa_render_visibility_cs": [_vp, _f32, _vp, _vp, _f32, _f32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp],
     "nfa_compact_samples": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp],
     "nfa_accumulate_along_rays": [_vp, _vp, _i32, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp],
     "nfa_accumulate_along_rays_atomic": [_vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp],
@@ -102,6 +103,8 @@ _SIGS = {
     "nfa_render_accumulate_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp],
     "nfa_render_fused_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nfa_render_fused_bwd": [_vp] * 13 + [_i64, _i64, _i64, _vp, _vp, _vp],
+    "nfa_render_fused_fwd_cs": [_vp, _f32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "nfa_render_fused_bwd_cs": [_vp, _f32] + [_vp] * 11 + [_i64, _i64, _i64, _vp, _vp, _vp],
     "nfa_render_raw_fwd": [_vp] * 5 + [_i32, _f32, _i32, _vp, _vp, _i64, _i64, _i64] + [_vp] * 9,
     "nfa_render_raw_bwd": [_vp] * 5 + [_i32, _f32, _i32] + [_vp] * 9 + [_i64, _i64, _i64, _vp, _vp, _vp],
     "nfa_render_raw_fwd_t": [_i32] + [_vp] * 5 + [_i32, _f32, _i32, _vp, _vp, _i64, _i64, _i64] + [_vp] * 9,

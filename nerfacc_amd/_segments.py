@@ -9,6 +9,8 @@ pre-tagged so that no validation read-back is needed for them.
 """
 from __future__ import annotations
 
+import ctypes
+import weakref
 from dataclasses import dataclass
 from typing import Optional
 
@@ -114,6 +116,44 @@ def resolve(n_elems: int, packed_info: Optional[Tensor], ray_indices: Optional[T
             n_rays = int(ray_indices.max().item()) + 1 if ray_indices.numel() else 0
         return seginfo_from_ray_indices(ray_indices, n_rays)
     return None
+
+
+# ----------------------------------------------------------------------------- constant-step samples
+# The constant-step sampler (step_size > 0, no cone angle) emits t_ends[i] == t_starts[i] + step for every sample (one fp32
+# add), so the passes that read both can form t_ends from t_starts (csrc/segscan.hip: ConstStep, the `_cs` entries).  That
+# holds for the sampler's own untouched output only, so the t_ends tensor it returns carries a tag that names the state of
+# both tensors; anything else -- a clone, an in-place edit, a foreign t_starts -- does not match it and takes the entries
+# that load t_ends.
+_ATTR_CS = "_nfa_const_step"
+
+
+def tag_const_step(t_starts: Tensor, t_ends: Tensor, step: float) -> None:
+    """Mark ``t_ends`` as ``t_starts + step`` (``step``: what the kernels were given; kept as the fp32 value they saw).
+    A subset of such samples (the compaction's output) may be tagged the same way."""
+    # (the object by weak reference: an id alone may be a later tensor's)
+    tag = (t_ends._version, weakref.ref(t_starts), t_starts.data_ptr(), t_starts._version, ctypes.c_float(float(step)).value)
+    try:
+        setattr(t_ends, _ATTR_CS, tag)
+    except Exception:  # pragma: no cover
+        pass
+
+
+def const_step_of(t_starts: Optional[Tensor], t_ends: Optional[Tensor]) -> Optional[float]:
+    """The step when ``t_ends`` still is the tagged companion of exactly this ``t_starts``, else None."""
+    tag = getattr(t_ends, _ATTR_CS, None) if t_ends is not None else None
+    if tag is None or t_starts is None:
+        return None
+    te_version, ts_ref, ts_ptr, ts_version, step = tag
+    if t_ends._version != te_version or ts_ref() is not t_starts:
+        return None
+    if t_starts.data_ptr() != ts_ptr or t_starts._version != ts_version:
+        return None
+    for t in (t_starts, t_ends):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()):
+            return None
+    if t_starts.shape != t_ends.shape or not (0.0 < step < float("inf")):
+        return None
+    return step
 
 
 # ----------------------------------------------------------------------------- batched tensors

@@ -691,6 +691,22 @@ __device__ __forceinline__ void trans_alpha(bool is_head, const float prev[1], f
     T = expf(-S);
     a = alpha_of(xs);
 }
+// ---- constant-step samples (CS): the sampler's own output with step_size > 0 and no cone angle has
+//      t_ends[i] == t_starts[i] + step for every sample (one fp32 add: the marching recurrence t_next = t_last + dt,
+//      ref grid.cu:213-215), so the t_ends stream carries nothing the pass does not have already: it is not loaded and
+//      formed from t_starts.  The sum is used exactly where the loaded value was (sigma * (te - ts), (ts + te) / 2), so
+//      every result is bit for bit the one of the form that loads it.  Without CS the base is empty and the op is laid out
+//      as before.
+template <bool CS> struct ConstStep {};
+template <> struct ConstStep<true> { float step; };
+struct NoQuad {};   // stands in Raw for the quad that is not loaded
+template <bool CS, class Op, class QA, class QB>
+__device__ __forceinline__ float t_end_of(const Op &op, const QA &a, const QB &b, int j)
+{
+    if constexpr (CS) return a.v[j] + op.step;
+    else return b.v[j];
+}
+
 // the per-sample outputs of that stage (each may be null)
 struct SampleOut {
     float *w, *tr, *al;
@@ -1045,10 +1061,10 @@ struct AlphaBwdOp : OpBase {
 
 // ---- visibility mask, volrend.py:412-418 / :474-480.  COUNT adds the per-ray number of visible
 //      samples (what the sampler's compaction needs) as a stage-B scan of the mask just computed.
-template <bool DENSITY, bool VEC, bool COUNT>
-struct VisibilityOp : OpBase {
+template <bool DENSITY, bool VEC, bool COUNT, bool CS = false>
+struct VisibilityOp : OpBase, ConstStep<CS> {
     static constexpr int NCHB = COUNT ? 1 : 0;
-    struct Raw { F4 s, pf, a, b; };
+    struct Raw { F4 s, pf, a; std::conditional_t<CS, NoQuad, F4> b; };
     const float *ts, *te, *val, *prefix;
     float eps, thre;
     // Density without a prefix: T = exp(-S) >= eps is decided on S (the scanned sum) wherever S is clearly on one side of
@@ -1067,7 +1083,7 @@ struct VisibilityOp : OpBase {
         if (prefix) ld4<VEC>(prefix, q, r.pf);
         if (DENSITY) {
             ld4<VEC>(ts, q, r.a);
-            ld4<VEC>(te, q, r.b);
+            if constexpr (!CS) ld4<VEC>(te, q, r.b);
         }
     }
     __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
@@ -1077,7 +1093,7 @@ struct VisibilityOp : OpBase {
         for (int j = 0; j < SE; ++j) {
             pf[j] = prefix ? r.pf.v[j] : 1.0f;
             const float sv = sel(r.s, j, valid, 0.0f);
-            if (DENSITY) { x0[j] = valid[j] ? sv * (r.b.v[j] - r.a.v[j]) : 0.0f; a4[j] = (thre > 0.0f) ? 1.0f - expf(-x0[j]) : 1.0f; }  // alpha only when it is tested
+            if (DENSITY) { x0[j] = valid[j] ? sv * (t_end_of<CS>(*this, r.a, r.b, j) - r.a.v[j]) : 0.0f; a4[j] = (thre > 0.0f) ? 1.0f - expf(-x0[j]) : 1.0f; }  // alpha only when it is tested
             else { a4[j] = sv; x0[j] = 1.0f - sv; }
         }
     }
@@ -1610,15 +1626,15 @@ struct RenderAccumBwdOp : OpBase, RayGrads {
 //      sigma*delta into transmittance -> (w, T, alpha); stage B scans w*rgb, w, w*mid into the per-ray
 //      colour / opacity / un-normalised depth.  Bit-identical to DensityFwdOp followed by
 //      RenderAccumOp (same expressions, same scan tree), 12 B/sample less traffic.
-template <bool VEC>
-struct RenderFusedFwdOp : RenderFwdStage, SampleOut {   // (81 VGPRs: one over the 6-wave budget; asking for 6 waves was within noise)
-    struct Raw { Quad<float> a, b, s; Rgb12<float> c; };
+template <bool VEC, bool CS = false>
+struct RenderFusedFwdOp : RenderFwdStage, SampleOut, ConstStep<CS> {   // (81 VGPRs: one over the 6-wave budget; asking for 6 waves was within noise)
+    struct Raw { Quad<float> a; std::conditional_t<CS, NoQuad, Quad<float>> b; Quad<float> s; Rgb12<float> c; };
     const float *ts, *te, *sig, *rgb;
     float rt[SE], ra[SE];
     __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
     {
         ld4<VEC>(ts, q, r.a);
-        ld4<VEC>(te, q, r.b);
+        if constexpr (!CS) ld4<VEC>(te, q, r.b);
         ld4<VEC>(sig, q, r.s);
         load_rgb12(rgb, VEC, q, r.c);
     }
@@ -1626,7 +1642,7 @@ struct RenderFusedFwdOp : RenderFwdStage, SampleOut {   // (81 VGPRs: one over t
     {
         fix_rgb12(rgb, VEC, pos, r.c, c);
 #pragma unroll
-        for (int j = 0; j < SE; ++j) sample(j, pos.valid[j], r.s.v[j], r.a.v[j], r.b.v[j]);
+        for (int j = 0; j < SE; ++j) sample(j, pos.valid[j], r.s.v[j], r.a.v[j], t_end_of<CS>(*this, r.a, r.b, j));
     }
     __device__ __forceinline__ void emit(int j, int64_t, bool, bool is_head, int, int, const float *, const float prev[1])
     {
@@ -1715,16 +1731,16 @@ struct RenderBwdStage : OpBase, RayGradStage, ExtraGrads<EXTRA> {
     }
 };
 
-template <bool VEC, bool EXTRA>
-struct RenderFusedBwdOp : RenderBwdStage<EXTRA> {   // (98 VGPRs without EXTRA: two over the 5-wave budget; asking for 5 waves was within noise)
+template <bool VEC, bool EXTRA, bool CS = false>
+struct RenderFusedBwdOp : RenderBwdStage<EXTRA>, ConstStep<CS> {   // (98 VGPRs without EXTRA: two over the 5-wave budget; asking for 5 waves was within noise)
     typedef RenderBwdStage<EXTRA> S;
-    struct Raw { Quad<float> a, b, T, A; typename S::GRaw g; Rgb12<float> c; };
+    struct Raw { Quad<float> a; std::conditional_t<CS, NoQuad, Quad<float>> b; Quad<float> T, A; typename S::GRaw g; Rgb12<float> c; };
     const float *ts, *te, *rgb, *tr, *al;
     float *gsig, *grgb;
     __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
     {
         ld4<VEC>(ts, q, r.a);
-        ld4<VEC>(te, q, r.b);
+        if constexpr (!CS) ld4<VEC>(te, q, r.b);
         ld4<VEC>(tr, q, r.T);
         ld4<VEC>(al, q, r.A);
         this->template fetch_extra<VEC>(q, r.g);
@@ -1738,7 +1754,7 @@ struct RenderFusedBwdOp : RenderBwdStage<EXTRA> {   // (98 VGPRs without EXTRA: 
         for (int j = 0; j < SE; ++j) {
             S::T[j] = sel(r.T, j, valid, 0.0f); S::A[j] = sel(r.A, j, valid, 0.0f);
             this->select_extra(r.g, j, valid[j], S::GW[j], S::GT[j], S::GA[j]);
-            S::sample(j, r.a.v[j], r.b.v[j]);
+            S::sample(j, r.a.v[j], t_end_of<CS>(*this, r.a, r.b, j));
         }
     }
     // g_rgb is complete before the scan: stored first (frees its registers, stores in flight during the scan)
@@ -2453,6 +2469,19 @@ int nfa_render_from_alpha_bwd(const float *alphas, const float *trans, const flo
     return NFA_OK;
 }
 
+// VisibilityOp's band [s_lo, s_hi] around S = -ln(eps), where exp(-S) crosses eps; expf is good to a couple of ulps, the band
+// is +-2e-5 relative (~20 ulps)
+static void visibility_band(float early_stop_eps, float &s_lo, float &s_hi)
+{
+    if (early_stop_eps > 0.0f) {
+        const double L = -log((double)early_stop_eps);
+        const double w = 2e-5 * (L > 1.0 ? L : 1.0);
+        s_lo = (float)(L - w); s_hi = (float)(L + w);
+    } else {   // every transmittance >= eps (exp(-S) is never negative; a NaN sum stays invisible as before)
+        s_lo = INFINITY; s_hi = INFINITY;
+    }
+}
+
 int nfa_render_visibility(const float *t_starts, const float *t_ends, const float *sigmas_or_alphas,
                           const float *prefix_trans, float early_stop_eps, float alpha_thre,
                           const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays, int64_t n_elems,
@@ -2464,15 +2493,8 @@ int nfa_render_visibility(const float *t_starts, const float *t_ends, const floa
         NFA_REQUIRE(sigmas_or_alphas && vis, "render_visibility: null pointer");
         const bool density = t_starts != nullptr;
         NFA_REQUIRE(!density || t_ends, "render_visibility: t_ends is null");
-        // S = -ln(eps) is where exp(-S) crosses eps; expf is good to a couple of ulps, the band is +-2e-5 relative (~20 ulps)
         float s_lo, s_hi;
-        if (early_stop_eps > 0.0f) {
-            const double L = -log((double)early_stop_eps);
-            const double w = 2e-5 * (L > 1.0 ? L : 1.0);
-            s_lo = (float)(L - w); s_hi = (float)(L + w);
-        } else {   // every transmittance >= eps (exp(-S) is never negative; a NaN sum stays invisible as before)
-            s_lo = INFINITY; s_hi = INFINITY;
-        }
+        visibility_band(early_stop_eps, s_lo, s_hi);
         // the uchar4 mask store needs 4-byte alignment of vis, the float loads 16
         const bool vec = all_aligned16(t_starts, t_ends, sigmas_or_alphas, prefix_trans) &&
                          (reinterpret_cast<uintptr_t>(vis) & 3) == 0;
@@ -2490,6 +2512,37 @@ int nfa_render_visibility(const float *t_starts, const float *t_ends, const floa
         if (hipMemsetAsync(vis_cnts, 0, sizeof(int64_t) * n_rays, s) != hipSuccess) { set_error("render_visibility: memset failed"); return NFA_EHIP; }
     }
     NFA_CHECK_LAUNCH("render_visibility");
+    return NFA_OK;
+}
+
+// The constant-step (_cs) entries: their siblings with `t_ends` replaced by the step the samples were marched with
+// (ConstStep above); densities only.
+#define SEG_STEP_CHECK(name) NFA_REQUIRE(step > 0.0f && step < INFINITY, name ": step must be > 0")
+
+int nfa_render_visibility_cs(const float *t_starts, float step, const float *sigmas, const float *prefix_trans,
+                             float early_stop_eps, float alpha_thre, const int64_t *packed_info, const int64_t *tiles,
+                             int64_t n_tiles, int64_t n_rays, int64_t n_elems, uint8_t *vis, int64_t *vis_cnts, nfa_stream_t stream)
+{
+    SEG_COMMON_CHECKS("render_visibility_cs");
+    SEG_STEP_CHECK("render_visibility_cs");
+    hipStream_t s = as_stream(stream);
+    if (n_elems > 0) {
+        NFA_REQUIRE(t_starts && sigmas && vis, "render_visibility_cs: null pointer");
+        float s_lo, s_hi;
+        visibility_band(early_stop_eps, s_lo, s_hi);
+        const bool vec = all_aligned16(t_starts, sigmas, prefix_trans) && (reinterpret_cast<uintptr_t>(vis) & 3) == 0;
+        dispatch_bool(vec, [&](auto V) {
+            dispatch_bool(vis_cnts != nullptr, [&](auto CN) {
+                VisibilityOp<true, V, CN, true> op;
+                op.ts = t_starts; op.te = nullptr; op.step = step; op.val = sigmas; op.prefix = prefix_trans;
+                op.eps = early_stop_eps; op.thre = alpha_thre; op.vis = vis; op.cnts = vis_cnts; op.s_lo = s_lo; op.s_hi = s_hi;
+                launch_seg<1>(op, packed_info, tiles, n_rays, n_tiles, s);
+            });
+        });
+    } else if (vis_cnts && n_rays > 0) {
+        if (hipMemsetAsync(vis_cnts, 0, sizeof(int64_t) * n_rays, s) != hipSuccess) { set_error("render_visibility_cs: memset failed"); return NFA_EHIP; }
+    }
+    NFA_CHECK_LAUNCH("render_visibility_cs");
     return NFA_OK;
 }
 
@@ -2640,6 +2693,36 @@ int nfa_render_fused_bwd(const float *t_starts, const float *t_ends, const float
     NFA_REQUIRE(t_starts && t_ends && rgbs && trans && alphas && (grad_sigmas || grad_rgbs), "render_fused_bwd: null pointer");
     return launch_render_bwd("render_fused_bwd", [&](auto V, auto X) { RenderFusedBwdOp<V, X> op; op.al = alphas; return op; },
                              aligned16(alphas), t_starts, t_ends, rgbs, trans, g_colors, g_opacities, g_depths, g_weights, g_trans,
+                             g_alphas, grad_sigmas, grad_rgbs, packed_info, tiles, n_tiles, n_rays, stream);
+}
+
+int nfa_render_fused_fwd_cs(const float *t_starts, float step, const float *sigmas, const float *rgbs,
+                            const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays, int64_t n_elems,
+                            float *weights, float *trans, float *alphas, float *colors, float *opacities, float *depths,
+                            nfa_stream_t stream)
+{
+    SEG_COMMON_CHECKS("render_fused_fwd_cs");
+    SEG_STEP_CHECK("render_fused_fwd_cs");
+    if (n_rays == 0) return NFA_OK;
+    NFA_REQUIRE(colors && opacities && depths && (n_elems == 0 || (t_starts && sigmas && rgbs)), "render_fused_fwd_cs: null pointer");
+    return launch_render_fwd("render_fused_fwd_cs", [&](auto V) { RenderFusedFwdOp<V, true> op; op.step = step; return op; }, true,
+                             t_starts, nullptr, sigmas, rgbs, weights, trans, alphas, colors, opacities, depths, packed_info, tiles,
+                             n_tiles, n_rays, stream);
+}
+
+int nfa_render_fused_bwd_cs(const float *t_starts, float step, const float *rgbs, const float *trans, const float *alphas,
+                            const float *g_colors, const float *g_opacities, const float *g_depths, const float *g_weights,
+                            const float *g_trans, const float *g_alphas, const int64_t *packed_info, const int64_t *tiles,
+                            int64_t n_tiles, int64_t n_rays, int64_t n_elems, float *grad_sigmas, float *grad_rgbs,
+                            nfa_stream_t stream)
+{
+    SEG_COMMON_CHECKS("render_fused_bwd_cs");
+    SEG_STEP_CHECK("render_fused_bwd_cs");
+    if (n_elems == 0) return NFA_OK;
+    NFA_REQUIRE(t_starts && rgbs && trans && alphas && (grad_sigmas || grad_rgbs), "render_fused_bwd_cs: null pointer");
+    return launch_render_bwd("render_fused_bwd_cs",
+                             [&](auto V, auto X) { RenderFusedBwdOp<V, X, true> op; op.al = alphas; op.step = step; return op; },
+                             aligned16(alphas), t_starts, nullptr, rgbs, trans, g_colors, g_opacities, g_depths, g_weights, g_trans,
                              g_alphas, grad_sigmas, grad_rgbs, packed_info, tiles, n_tiles, n_rays, stream);
 }
 

@@ -19,8 +19,9 @@ import torch
 from torch import Tensor
 
 from .. import _backend as B
-from .._segments import SegInfo, tag_ray_indices, tag_trusted
+from .._segments import SegInfo, const_step_of, tag_const_step, tag_ray_indices, tag_trusted
 from ..grid import _enlarge_aabb, _exclusive_cumsum, _traverse_samples
+from .. import volrend as _volrend
 from ..volrend import _visibility_native
 from .base import AbstractEstimator
 
@@ -229,7 +230,9 @@ class OccGridEstimator(AbstractEstimator):
                 else:
                     sigmas = torch.empty((0,), device=t_starts.device)
                 assert sigmas.shape == t_starts.shape, "sigmas must have shape of (N,)! Got {}".format(sigmas.shape)
-                vis, cnts = _visibility_native(seg, t_starts, t_ends, sigmas, None, early_stop_eps, alpha_thre, True)
+                # (asked after the callback: it may have written into the arrays)
+                step = const_step_of(t_starts, t_ends) if _volrend.DERIVE_T_ENDS else None
+                vis, cnts = _visibility_native(seg, t_starts, t_ends, sigmas, None, early_stop_eps, alpha_thre, True, step=step)
             else:
                 if t_starts.shape[0] != 0:
                     alphas = alpha_fn(t_starts, t_ends, ray_indices)
@@ -525,6 +528,9 @@ def _compact(seg: SegInfo, vis: Tensor, cnts: Tensor, t_starts: Tensor, t_ends: 
             te = torch.empty(m, dtype=torch.float32, device=dev)
             if m > 0:
                 run(ri, ts, te, m)
+        step = const_step_of(t_starts, t_ends)
+        if step is not None:   # a subset of constant-step samples is one
+            tag_const_step(ts, te, step)
         packed = torch.stack([out_starts, cnts], dim=-1)
     info = tag_trusted(packed, m)
     tag_ray_indices(ri, seg.n_rays, info)

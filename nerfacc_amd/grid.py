@@ -16,7 +16,7 @@ import torch
 from torch import Tensor
 
 from . import _backend as B
-from ._segments import tag_ray_indices, tag_trusted
+from ._segments import tag_const_step, tag_ray_indices, tag_trusted
 from .data_specs import RayIntervals, RaySamples
 
 
@@ -576,6 +576,9 @@ def _traverse_samples(rays_o, rays_d, binaries, aabbs, near_planes, far_planes, 
                 B.call("nfa_fill_ray_indices", n_rays, B.ptr(packed_info), B.ptr(ray_indices), B.stream())
     info = tag_trusted(packed_info, n_sm)
     tag_ray_indices(ray_indices, n_rays, info)
+    if use_runs and not masked:
+        # every sample, the serially filled rays' included, is t_last + step (grid.cu:213-215)
+        tag_const_step(t_starts, t_ends, step_size)
     out = (ray_indices, t_starts, t_ends, packed_info)
     return (*out, terminate) if return_terminate else out
 

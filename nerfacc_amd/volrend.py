@@ -16,12 +16,15 @@ from torch import Tensor
 from torch.autograd.function import once_differentiable
 
 from . import _backend as B
-from ._segments import SegInfo, batched_native, resolve, seginfo_from_ray_indices
+from ._segments import SegInfo, batched_native, const_step_of, resolve, seginfo_from_ray_indices
 from .scan import exclusive_prod, exclusive_sum
 
 
 # rendering(): one fused pass each way (True) or weights + accumulation as two passes (False, for A/B tests)
 FUSE_RENDERING = True
+# the sampler's own constant-step output: the passes form t_ends from t_starts instead of loading it (True), or load it as
+# for any other input (False, for A/B tests); same results either way (_segments.const_step_of)
+DERIVE_T_ENDS = True
 
 
 def _f32c(t: Optional[Tensor]) -> Optional[Tensor]:
@@ -204,7 +207,8 @@ class _RenderFused(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, t_starts, t_ends, sigmas, rgbs, seg: SegInfo):
+    def forward(ctx, t_starts, t_ends, sigmas, rgbs, seg: SegInfo, step: Optional[float] = None):
+        # step: t_ends is t_starts + step (const_step_of, decided by the caller): it is neither read nor kept for the backward
         ctx.set_materialize_grads(False)  # unused outputs arrive as None, not as zero tensors
         ts, te, sg, c = _f32c(t_starts), _f32c(t_ends), _f32c(sigmas), _f32c(rgbs)
         dev = B.require_device(ts, te, sg, c)
@@ -215,17 +219,30 @@ class _RenderFused(torch.autograd.Function):
         depth = torch.empty((R, 1), dtype=torch.float32, device=dev)
         if R:
             with torch.cuda.device(dev):
-                B.call("nfa_render_fused_fwd", B.ptr(ts), B.ptr(te), B.ptr(sg), B.ptr(c), B.ptr(seg.packed_info),
-                       B.ptr(seg.tiles), seg.n_tiles, R, n, B.ptr(weights), B.ptr(trans), B.ptr(alphas), B.ptr(colors),
-                       B.ptr(opac), B.ptr(depth), B.stream())
-        ctx.seg = seg
-        ctx.save_for_backward(ts, te, c, trans, alphas)
+                if step is None:
+                    B.call("nfa_render_fused_fwd", B.ptr(ts), B.ptr(te), B.ptr(sg), B.ptr(c), B.ptr(seg.packed_info),
+                           B.ptr(seg.tiles), seg.n_tiles, R, n, B.ptr(weights), B.ptr(trans), B.ptr(alphas), B.ptr(colors),
+                           B.ptr(opac), B.ptr(depth), B.stream())
+                else:   # (under the sibling's name: the instrumentation keys on it)
+                    B.call_group("nfa_render_fused_fwd", lambda: B.call(
+                        "nfa_render_fused_fwd_cs", B.ptr(ts), step, B.ptr(sg), B.ptr(c), B.ptr(seg.packed_info),
+                        B.ptr(seg.tiles), seg.n_tiles, R, n, B.ptr(weights), B.ptr(trans), B.ptr(alphas), B.ptr(colors),
+                        B.ptr(opac), B.ptr(depth), B.stream()))
+        ctx.seg, ctx.step = seg, step
+        if step is None:
+            ctx.save_for_backward(ts, te, c, trans, alphas)
+        else:
+            ctx.save_for_backward(ts, c, trans, alphas)
         return colors, opac, depth, weights, trans, alphas
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_c, g_o, g_d, g_w, g_t, g_a):
-        ts, te, c, trans, alphas = ctx.saved_tensors
+        step = ctx.step
+        if step is None:
+            ts, te, c, trans, alphas = ctx.saved_tensors
+        else:
+            ts, c, trans, alphas = ctx.saved_tensors
         seg = ctx.seg
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             raise NotImplementedError("nerfacc_amd: rendering is not differentiable w.r.t. t_starts / t_ends "
@@ -235,11 +252,17 @@ class _RenderFused(torch.autograd.Function):
         g_rgb = torch.empty_like(c) if need_c else None
         if trans.numel() and (need_sg or need_c):
             with torch.cuda.device(trans.device):
-                B.call("nfa_render_fused_bwd", B.ptr(ts), B.ptr(te), B.ptr(c), B.ptr(trans), B.ptr(alphas),
-                       B.ptr(_f32c(g_c)), B.ptr(_f32c(g_o)), B.ptr(_f32c(g_d)), B.ptr(_f32c(g_w)), B.ptr(_f32c(g_t)),
-                       B.ptr(_f32c(g_a)), B.ptr(seg.packed_info), B.ptr(seg.tiles), seg.n_tiles, seg.n_rays,
-                       trans.numel(), B.ptr(g_sig), B.ptr(g_rgb), B.stream())
-        return None, None, g_sig, g_rgb, None
+                grads = [_f32c(g) for g in (g_c, g_o, g_d, g_w, g_t, g_a)]
+                if step is None:
+                    B.call("nfa_render_fused_bwd", B.ptr(ts), B.ptr(te), B.ptr(c), B.ptr(trans), B.ptr(alphas),
+                           *(B.ptr(g) for g in grads), B.ptr(seg.packed_info), B.ptr(seg.tiles), seg.n_tiles, seg.n_rays,
+                           trans.numel(), B.ptr(g_sig), B.ptr(g_rgb), B.stream())
+                else:
+                    B.call_group("nfa_render_fused_bwd", lambda: B.call(
+                        "nfa_render_fused_bwd_cs", B.ptr(ts), step, B.ptr(c), B.ptr(trans), B.ptr(alphas),
+                        *(B.ptr(g) for g in grads), B.ptr(seg.packed_info), B.ptr(seg.tiles), seg.n_tiles, seg.n_rays,
+                        trans.numel(), B.ptr(g_sig), B.ptr(g_rgb), B.stream()))
+        return None, None, g_sig, g_rgb, None, None
 
 
 def _use_fused(seg: Optional[SegInfo], *tensors: Optional[Tensor]) -> bool:
@@ -292,7 +315,9 @@ def rendering(
                 and rgbs.dtype == torch.float32 and rgbs.dim() == 2 \
                 and not (t_starts.requires_grad or t_ends.requires_grad):
             # the whole of volrend.py:109-151 as one pass each way
-            colors, opacities, depths, weights, trans, alphas = _RenderFused.apply(t_starts, t_ends, sigmas, rgbs, seg)
+            # (asked after the callback: it may have written into the arrays)
+            step = const_step_of(t_starts, t_ends) if DERIVE_T_ENDS else None
+            colors, opacities, depths, weights, trans, alphas = _RenderFused.apply(t_starts, t_ends, sigmas, rgbs, seg, step)
             extras = {"weights": weights, "alphas": alphas, "trans": trans, "sigmas": sigmas, "rgbs": rgbs}
             return _finish_rendering(colors, opacities, depths, extras, rgbs, render_bkgd)
         weights, trans, alphas = render_weight_from_density(
@@ -434,16 +459,23 @@ def render_weight_from_density(
 
 
 def _visibility_native(seg: SegInfo, t_starts, t_ends, vals, prefix_trans, early_stop_eps, alpha_thre,
-                       want_counts: bool = False):
+                       want_counts: bool = False, step: Optional[float] = None):
+    """``step``: ``t_ends`` is ``t_starts + step`` (const_step_of, decided by the caller) and is not read."""
     ts, te, v, pf = _f32c(t_starts), _f32c(t_ends), _f32c(vals), _f32c(prefix_trans)
     dev = B.require_device(v, ts, te, pf)
     n = v.numel()
     vis = torch.empty(n, dtype=torch.bool, device=dev)
     cnts = torch.empty(seg.n_rays, dtype=torch.int64, device=dev) if want_counts else None
     with torch.cuda.device(dev):
-        B.call("nfa_render_visibility", B.ptr(ts), B.ptr(te), B.ptr(v), B.ptr(pf), float(early_stop_eps),
-               float(alpha_thre), B.ptr(seg.packed_info), B.ptr(seg.tiles), seg.n_tiles, seg.n_rays, n, B.ptr(vis), B.ptr(cnts),
-               B.stream())
+        if step is None or ts is None:
+            B.call("nfa_render_visibility", B.ptr(ts), B.ptr(te), B.ptr(v), B.ptr(pf), float(early_stop_eps),
+                   float(alpha_thre), B.ptr(seg.packed_info), B.ptr(seg.tiles), seg.n_tiles, seg.n_rays, n, B.ptr(vis),
+                   B.ptr(cnts), B.stream())
+        else:   # (under the sibling's name: the instrumentation keys on it)
+            B.call_group("nfa_render_visibility", lambda: B.call(
+                "nfa_render_visibility_cs", B.ptr(ts), step, B.ptr(v), B.ptr(pf), float(early_stop_eps),
+                float(alpha_thre), B.ptr(seg.packed_info), B.ptr(seg.tiles), seg.n_tiles, seg.n_rays, n, B.ptr(vis),
+                B.ptr(cnts), B.stream()))
     return (vis, cnts) if want_counts else vis
 
 
