@@ -529,6 +529,43 @@ int nfa_render_raw_bwd_t(int32_t elem, const float *t_starts, const float *t_end
                          const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays,
                          int64_t n_elems, void *grad_raw_sigmas, void *grad_raw_rgbs, nfa_stream_t stream);
 
+/* `rendering` of a signed-distance field: nfa_render_fused_fwd with the SDF-to-opacity conversion applied on load.  It
+ * replaces the torch composition a surface model runs in front of render_weight_from_alpha / rendering (about fifteen
+ * elementwise passes each way): NeuS' alpha from the logistic CDF of the SDF at the two ends of a sample (Wang et al.
+ * 2021, models/renderer.py: the `((prev_cdf - next_cdf + 1e-5) / (prev_cdf + 1e-5)).clip(0, 1)` block, here without its
+ * 1e-5), or VolSDF's density, the Laplace CDF of the SDF times 1 / beta (Yariv et al. 2021, model/density.py).
+ * With d = t_end - t_start, r = cos_anneal_ratio, s = *param (ONE float on the device, read by the kernel: inv_s for
+ * NFA_SDF_NEUS, beta for NFA_SDF_VOLSDF; both must be > 0, which is not checked), float32 throughout:
+ *   NFA_SDF_NEUS    ct = -(max(0.5 - 0.5 cos, 0) (1 - r) + max(-cos, 0) r);  h = ct d / 2;  n = sdf + h;  p = sdf - h;
+ *                   x = max(sp(-s n) - sp(-s p), 0),  sp(y) = max(y, 0) + log1p(exp(-|y|))
+ *   NFA_SDF_VOLSDF  e = exp(-|sdf| / s) / 2;  x = (sdf >= 0 ? e : 1 - e) / s * d
+ *   alpha = 1 - exp(-x),  trans = exp(-(sum of x in front of the sample)),  weight = trans alpha,
+ * and colours, opacities, depths as nfa_render_fused_fwd forms them from the weights and rgb = rgb_act(raw_rgb)
+ * (NFA_RGB_ACT_*).  cos[n] is read by NFA_SDF_NEUS only (NULL otherwise).  selector[n] (bytes, 0 = false; may be NULL = all
+ * true) is a select: where it is false x is exactly 0 and a non-finite sdf has no effect.  weights, trans, alphas: each
+ * may be NULL.  Empty rays get zeros. */
+#define NFA_SDF_NEUS 0
+#define NFA_SDF_VOLSDF 1
+int nfa_render_sdf_fwd(const float *t_starts, const float *t_ends, const float *sdfs, const float *cos,
+                       const float *raw_rgbs, const uint8_t *selector, int32_t model, const float *param,
+                       float cos_anneal_ratio, int32_t rgb_act, const int64_t *packed_info, const int64_t *tiles,
+                       int64_t n_tiles, int64_t n_rays, int64_t n_elems, float *weights, float *trans, float *alphas,
+                       float *colors, float *opacities, float *depths, nfa_stream_t stream);
+/* Its backward in one reverse pass, from the inputs and the forward's trans alone: x, alpha and rgb are formed again
+ * with the forward's expressions and dL/dx is multiplied into the derivatives of x.  Gradient arguments as for
+ * nfa_render_fused_bwd.  Writes grad_sdfs[n], grad_cos[n] (NFA_SDF_NEUS only; must be NULL otherwise), grad_param[n] --
+ * PER SAMPLE, dL/dx dx/d(*param): the gradient of the parameter is the sum of that stream, left to the caller, so the
+ * pass has no float atomics -- and grad_raw_rgbs[n,3]; each may be NULL (not needed, then neither formed nor written),
+ * not all four.  Where selector is false, and for NFA_SDF_NEUS where x is 0, all of a sample's gradients but
+ * grad_raw_rgbs are exactly 0. */
+int nfa_render_sdf_bwd(const float *t_starts, const float *t_ends, const float *sdfs, const float *cos,
+                       const float *raw_rgbs, const uint8_t *selector, int32_t model, const float *param,
+                       float cos_anneal_ratio, int32_t rgb_act, const float *trans, const float *g_colors,
+                       const float *g_opacities, const float *g_depths, const float *g_weights, const float *g_trans,
+                       const float *g_alphas, const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles,
+                       int64_t n_rays, int64_t n_elems, float *grad_sdfs, float *grad_cos, float *grad_param,
+                       float *grad_raw_rgbs, nfa_stream_t stream);
+
 /* Mip-NeRF 360 distortion loss per ray (Barron et al. 2022, eq. 15) over samples in non-decreasing midpoint order
  * within each ray: loss[r] = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 (t_end_i - t_start_i), m = (t_start + t_end) / 2
  * (input out of that order gets what the O(n) prefix-sum form gives; it is not detected).  Also writes the per-ray totals

@@ -109,6 +109,8 @@ _SIGS = {
     "nfa_render_raw_bwd": [_vp] * 5 + [_i32, _f32, _i32] + [_vp] * 9 + [_i64, _i64, _i64, _vp, _vp, _vp],
     "nfa_render_raw_fwd_t": [_i32] + [_vp] * 5 + [_i32, _f32, _i32, _vp, _vp, _i64, _i64, _i64] + [_vp] * 9,
     "nfa_render_raw_bwd_t": [_i32] + [_vp] * 5 + [_i32, _f32, _i32] + [_vp] * 9 + [_i64, _i64, _i64, _vp, _vp, _vp],
+    "nfa_render_sdf_fwd": [_vp] * 6 + [_i32, _vp, _f32, _i32, _vp, _vp, _i64, _i64, _i64] + [_vp] * 7,
+    "nfa_render_sdf_bwd": [_vp] * 6 + [_i32, _vp, _f32, _i32] + [_vp] * 9 + [_i64, _i64, _i64] + [_vp] * 5,
     "nfa_render_step_accumulate": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp],
     "nfa_distortion_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     "nfa_distortion_bwd": [_vp] * 8 + [_i64, _i64, _i64, _vp, _vp, _vp, _vp],

@@ -675,8 +675,8 @@ struct ProdBwdOp : OpBase {
 };
 
 // ------------------------------------------------------------------------------------------
-// The rendering family -- DensityFwd/BwdOp, RenderAccum/AccumBwdOp, RenderFusedFwd/BwdOp, RenderRawFwd/BwdOp, RenderStepOp
-// (volrend.py:109-151, :256-264, :358-362) -- is assembled from the steps below, each written once.  They are plain
+// The rendering family -- DensityFwd/BwdOp, RenderAccum/AccumBwdOp, RenderFusedFwd/BwdOp, RenderRawFwd/BwdOp, RenderSdfFwd/BwdOp,
+// RenderStepOp (volrend.py:109-151, :256-264, :358-362) -- is assembled from the steps below, each written once.  They are plain
 // functions of values and base structs with __forceinline__ members: an op is a kernel argument and its working arrays
 // are members, so after inlining a step reads and writes the op's own registers.
 
@@ -1917,6 +1917,199 @@ struct RenderRawBwdOp : RenderBwdStage<EXTRA> {
     }
 };
 
+// ---- `rendering` of a signed-distance field: the two passes above with the SDF-to-opacity conversion of NeuS (Wang et
+//      al. 2021, the logistic CDF of the SDF at the two ends of a sample) or VolSDF (Yariv et al. 2021, the Laplace CDF of
+//      the SDF times 1 / beta) applied on load.  What the conversion yields is x, the summand of stage A
+//      (RenderFwdStage::xs): alpha = 1 - exp(-x), T = exp(-sum of x in front), so trans_alpha / chain_grad serve unchanged.
+//      The model is a template parameter; the mask and the sigmoid colour step are RawAct's.  The backward keeps trans
+//      only: it forms x, alpha and c again with the forward's expressions (the same function, so bit for bit) and
+//      multiplies dL/dx into the derivatives of x.
+//      Arithmetic: float32 throughout, no contraction (-ffp-contract=off), expf / log1pf of the device library.  With
+//      d = t_end - t_start, r = cos_anneal_ratio, s = *param (inv_s / beta: ONE float read through its device pointer, the
+//      same for every sample):
+//        NeuS    ct = -(max(0.5 - 0.5 cos, 0) (1 - r) + max(-cos, 0) r)                          (<= 0)
+//                h = ct (d 0.5);  n = sdf + h;  p = sdf - h                                      (next, previous: n <= p)
+//                sp(y) = max(y, 0) + log1pf(expf(-|y|))
+//                x = max(sp(-s n) - sp(-s p), 0)        = log Phi(s p) - log Phi(s n), Phi the logistic function: the
+//                                                         published (Phi(p) - Phi(n) + 1e-5) / (Phi(p) + 1e-5) without its 1e-5
+//                with sn = 1 / (1 + expf(s n)), sq = 1 / (1 + expf(s p)), and all three exactly 0 where x is 0:
+//                dx/dsdf = s (sq - sn);  dx/dcos = -(s (d 0.5)) (sn + sq) (0.5 (1 - r) [cos < 1] + r [cos < 0]);
+//                dx/ds = p sq - n sn
+//        VolSDF  e = 0.5 expf(-|sdf| / s);  psi = sdf >= 0 ? e : 1 - e;  sigma = psi / s;  x = sigma d
+//                dx/dsdf = d (-e / (s s));  dx/ds = d (-psi / (s s) + e sdf / (s s s))
+//      Where the mask is false x and every derivative are exactly 0 (selects, not products).  The gradient towards s is
+//      written per sample (dL/dx dx/ds); the caller sums the stream, so no float atomics and two runs give the same bits.
+//      Compiler's report: DESIGN.md, "Rendering from SDF fields".
+struct SdfParam {
+    const float *value;   // [1] on the device: inv_s (NeuS) or beta (VolSDF)
+    float ratio;          // cos_anneal_ratio (NeuS)
+};
+__device__ __forceinline__ float sdf_softplus(float y) { return fmaxf(y, 0.0f) + log1pf(expf(-fabsf(y))); }
+__device__ __forceinline__ float sdf_logistic_neg(float y) { return 1.0f / (1.0f + expf(y)); }   // Phi(-y)
+
+template <int MODEL> struct SdfModel;
+template <>
+struct SdfModel<NFA_SDF_NEUS> {
+    static constexpr bool HAS_COS = true;
+    // x of one sample; with D also its derivatives w.r.t. sdf, cos and s
+    template <bool D>
+    static __device__ __forceinline__ float x(float sdf, float cs, float d, float s, float r, float &dx_sdf, float &dx_cos, float &dx_s)
+    {
+        const float ct = -(fmaxf(0.5f - 0.5f * cs, 0.0f) * (1.0f - r) + fmaxf(-cs, 0.0f) * r);
+        const float hd = d * 0.5f;
+        const float h = ct * hd;
+        const float n = sdf + h, p = sdf - h;
+        const float diff = sdf_softplus(-s * n) - sdf_softplus(-s * p);
+        const float xv = diff < 0.0f ? 0.0f : diff;
+        if (D) {
+            const bool on = xv > 0.0f;
+            const float sn = sdf_logistic_neg(s * n), sq = sdf_logistic_neg(s * p);
+            const float dct = 0.5f * (1.0f - r) * (cs < 1.0f ? 1.0f : 0.0f) + r * (cs < 0.0f ? 1.0f : 0.0f);
+            dx_sdf = on ? s * (sq - sn) : 0.0f;
+            dx_cos = on ? -(s * hd) * (sn + sq) * dct : 0.0f;
+            dx_s = on ? p * sq - n * sn : 0.0f;
+        }
+        return xv;
+    }
+};
+template <>
+struct SdfModel<NFA_SDF_VOLSDF> {
+    static constexpr bool HAS_COS = false;
+    template <bool D>
+    static __device__ __forceinline__ float x(float sdf, float, float d, float s, float, float &dx_sdf, float &dx_cos, float &dx_s)
+    {
+        const float e = 0.5f * expf(-fabsf(sdf) / s);
+        const float psi = sdf >= 0.0f ? e : 1.0f - e;
+        if (D) {
+            const float s2 = s * s;
+            dx_sdf = d * (-e / s2);
+            dx_cos = 0.0f;
+            dx_s = d * (-psi / s2 + e * sdf / (s2 * s));
+        }
+        return psi / s * d;
+    }
+};
+// the cos quad of a step where the model has one
+template <bool HAS> struct CosQuad { typedef Quad<float> type; };
+template <> struct CosQuad<false> { typedef NoQuad type; };
+template <class Q>
+__device__ __forceinline__ float cos_elem(const Q &q, int j)
+{
+    if constexpr (std::is_same<Q, NoQuad>::value) return 0.0f;
+    else return q.v[j];
+}
+
+template <bool VEC, int MODEL>
+struct RenderSdfFwdOp : RenderFwdStage, SampleOut {
+    typedef SdfModel<MODEL> M;
+    struct Raw { Quad<float> a, b, s; typename CosQuad<M::HAS_COS>::type cs; U4 m; float prm; Rgb12<float> c; };
+    const float *ts, *te, *sig /* sdfs */, *cosv, *rgb;
+    RawAct act;   // the mask and the colour step
+    SdfParam par;
+    float rt[SE], ra[SE];
+    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
+    {
+        ld4<VEC>(ts, q, r.a);
+        ld4<VEC>(te, q, r.b);
+        ld4<VEC>(sig, q, r.s);
+        if constexpr (M::HAS_COS) ld4<VEC>(cosv, q, r.cs);
+        if (act.mask) load_mask4(act.mask, act.mask_vec != 0, q, r.m);
+        r.prm = *par.value;
+        load_rgb12(rgb, VEC, q, r.c);
+    }
+    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
+    {
+        fix_rgb12(rgb, VEC, pos, r.c, c);
+        act.colours(c);
+#pragma unroll
+        for (int j = 0; j < SE; ++j) {
+            float u0, u1, u2;
+            const float xv = M::template x<false>(r.s.v[j], cos_elem(r.cs, j), r.b.v[j] - r.a.v[j], r.prm, par.ratio, u0, u1, u2);
+            xs[j] = (pos.valid[j] && act.live(r.m, j)) ? xv : 0.0f;
+            mid[j] = midpoint(r.a.v[j], r.b.v[j]);
+        }
+    }
+    __device__ __forceinline__ void emit(int j, int64_t, bool, bool is_head, int, int, const float *, const float prev[1])
+    {
+        trans_alpha(is_head, prev, xs[j], rt[j], ra[j]);
+        rw[j] = rt[j] * ra[j];
+    }
+    __device__ __forceinline__ void ray_done_b(int rid, int ch, float t) const { ray_store(rid, ch, t); }
+    __device__ __forceinline__ void empty_ray(int rid) const { ray_zero(rid); }
+    __device__ __forceinline__ void store(const Pos &q) { store_wta<VEC>(q, rw, rt, ra); }
+};
+
+template <bool VEC, bool EXTRA, int MODEL>
+struct RenderSdfBwdOp : RenderBwdStage<EXTRA> {
+    typedef RenderBwdStage<EXTRA> S;
+    typedef SdfModel<MODEL> M;
+    // NeuS with EXTRA holds one quad and three derivative factors more than RenderRawBwdOp<EXTRA> (141 VGPRs): with the next
+    // step's loads in registers as well it is 181 VGPRs, 2 waves per SIMD, and held to the 3-wave budget it spills.  That
+    // form fetches in the step itself instead.
+    static constexpr bool PIPE = !(M::HAS_COS && EXTRA);
+    struct Raw { Quad<float> a, b, T, s; typename CosQuad<M::HAS_COS>::type cs; typename S::GRaw g; U4 m; float prm; Rgb12<float> c; };
+    const float *ts, *te, *sig /* sdfs */, *cosv, *rgb, *tr;
+    RawAct act;
+    SdfParam par;
+    float *gsig /* g_sdfs */, *gcos, *gpar, *grgb;
+    float d_sdf[SE], d_cos[SE], d_par[SE], rc[SE], rp[SE];
+    __device__ __forceinline__ void fetch(const Pos &q, Raw &r) const
+    {
+        ld4<VEC>(ts, q, r.a);
+        ld4<VEC>(te, q, r.b);
+        ld4<VEC>(tr, q, r.T);
+        ld4<VEC>(sig, q, r.s);
+        if constexpr (M::HAS_COS) ld4<VEC>(cosv, q, r.cs);
+        this->template fetch_extra<VEC>(q, r.g);
+        if (act.mask) load_mask4(act.mask, act.mask_vec != 0, q, r.m);
+        r.prm = *par.value;
+        load_rgb12(rgb, VEC, q, r.c);
+    }
+    __device__ __forceinline__ void load(const Raw &r, const Pos &pos)
+    {
+        const bool *valid = pos.valid;
+        fix_rgb12(rgb, VEC, pos, r.c, S::c);
+        act.colours(S::c);
+#pragma unroll
+        for (int j = 0; j < SE; ++j) {
+            // x and alpha as the forward pass formed them
+            const bool on = valid[j] && act.live(r.m, j);
+            S::sample(j, r.a.v[j], r.b.v[j]);
+            float d0, d1, d2;
+            const float xv = M::template x<true>(r.s.v[j], cos_elem(r.cs, j), S::dlt[j], r.prm, par.ratio, d0, d1, d2);
+            d_sdf[j] = on ? d0 : 0.0f; d_cos[j] = on ? d1 : 0.0f; d_par[j] = on ? d2 : 0.0f;
+            S::T[j] = sel(r.T, j, valid, 0.0f); S::A[j] = on ? alpha_of(xv) : 0.0f;
+            this->select_extra(r.g, j, valid[j], S::GW[j], S::GT[j], S::GA[j]);
+        }
+    }
+    __device__ __forceinline__ void pre(int j, int64_t pos, bool valid, int rid)
+    {
+        S::pre(j, pos, valid, rid);
+        if (valid && S::gc && act.col == NFA_RGB_ACT_SIGMOID) {   // d sigmoid = c (1 - c)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) S::gr[3 * j + k] *= S::c[3 * j + k] * (1.0f - S::c[3 * j + k]);
+        }
+    }
+    __device__ __forceinline__ void store_pre(const Pos &pq)
+    {
+        if (grgb) store_rgb12(grgb, VEC, pq, S::gr);
+    }
+    __device__ __forceinline__ void emit(int j, int64_t, bool, bool is_head, int, int, const float *, const float prev[1])
+    {
+        // (selects, not products: where a derivative is 0 -- a masked sample, x = 0 -- the gradient is exactly 0)
+        const float gx = S::chain(j, is_head, prev);
+        S::rs[j] = d_sdf[j] != 0.0f ? gx * d_sdf[j] : 0.0f;
+        if constexpr (M::HAS_COS) rc[j] = d_cos[j] != 0.0f ? gx * d_cos[j] : 0.0f;
+        rp[j] = d_par[j] != 0.0f ? gx * d_par[j] : 0.0f;
+    }
+    __device__ __forceinline__ void store(const Pos &pq)
+    {
+        if (gsig) store4<VEC>(gsig, pq, S::rs);
+        if constexpr (M::HAS_COS) { if (gcos) store4<VEC>(gcos, pq, rc); }
+        if (gpar) store4<VEC>(gpar, pq, rp);
+    }
+};
+
 // ---- Mip-NeRF 360 distortion loss (Barron et al. 2022, eq. 15) over samples in non-decreasing midpoint order per ray:
 //      L = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 s_i = sum_k [2 w_k (d_k W<k - S<k) + w_k^2 s_k / 3], with
 //      W<k / S<k the exclusive prefix sums of w and w*d, d = m - m(first sample of the ray).  The loss is shift-invariant;
@@ -2832,6 +3025,76 @@ int nfa_render_raw_bwd(const float *t_starts, const float *t_ends, const float *
     return nfa_render_raw_bwd_t(NFA_ELEM_F32, t_starts, t_ends, raw_sigmas, raw_rgbs, selector, density_act, density_bias,
                                 rgb_act, trans, g_colors, g_opacities, g_depths, g_weights, g_trans, g_alphas, packed_info,
                                 tiles, n_tiles, n_rays, n_elems, grad_raw_sigmas, grad_raw_rgbs, stream);
+}
+
+#define SDF_MODEL_CHECKS(name)                                                                                     \
+    NFA_REQUIRE(model == NFA_SDF_NEUS || model == NFA_SDF_VOLSDF, name ": model must be 0 or 1 (got %d)", (int)model); \
+    NFA_REQUIRE(rgb_act == NFA_RGB_ACT_NONE || rgb_act == NFA_RGB_ACT_SIGMOID, name ": rgb_act must be 0 or 1 (got %d)", (int)rgb_act)
+
+extern "C++" {
+template <class F>
+static void dispatch_sdf_model(int32_t model, F &&f)
+{
+    if (model == NFA_SDF_NEUS) f(std::integral_constant<int, NFA_SDF_NEUS>{});
+    else f(std::integral_constant<int, NFA_SDF_VOLSDF>{});
+}
+}  // extern "C++"
+
+int nfa_render_sdf_fwd(const float *t_starts, const float *t_ends, const float *sdfs, const float *cos, const float *raw_rgbs,
+                       const uint8_t *selector, int32_t model, const float *param, float cos_anneal_ratio, int32_t rgb_act,
+                       const int64_t *packed_info, const int64_t *tiles, int64_t n_tiles, int64_t n_rays, int64_t n_elems,
+                       float *weights, float *trans, float *alphas, float *colors, float *opacities, float *depths,
+                       nfa_stream_t stream)
+{
+    SEG_COMMON_CHECKS("render_sdf_fwd");
+    SDF_MODEL_CHECKS("render_sdf_fwd");
+    if (n_rays == 0) return NFA_OK;
+    NFA_REQUIRE(colors && opacities && depths && (n_elems == 0 || (t_starts && t_ends && sdfs && raw_rgbs)),
+                "render_sdf_fwd: null pointer");
+    NFA_REQUIRE(n_elems == 0 || model != NFA_SDF_NEUS || cos, "render_sdf_fwd: cos is null (NFA_SDF_NEUS)");
+    NFA_REQUIRE(param, "render_sdf_fwd: param is null");
+    const RawAct act = raw_act(selector, NFA_ACT_NONE, 0.0f, rgb_act);
+    const SdfParam par = {param, cos_anneal_ratio};
+    int rc = NFA_OK;
+    dispatch_sdf_model(model, [&](auto tag) {
+        constexpr int MD = decltype(tag)::value;
+        auto make = [&](auto V) { RenderSdfFwdOp<V, MD> op; op.cosv = cos; op.act = act; op.par = par; return op; };
+        rc = launch_render_fwd("render_sdf_fwd", make, MD != NFA_SDF_NEUS || aligned16(cos), t_starts, t_ends, sdfs, raw_rgbs, weights,
+                               trans, alphas, colors, opacities, depths, packed_info, tiles, n_tiles, n_rays, stream);
+    });
+    return rc;
+}
+
+int nfa_render_sdf_bwd(const float *t_starts, const float *t_ends, const float *sdfs, const float *cos, const float *raw_rgbs,
+                       const uint8_t *selector, int32_t model, const float *param, float cos_anneal_ratio, int32_t rgb_act,
+                       const float *trans, const float *g_colors, const float *g_opacities, const float *g_depths,
+                       const float *g_weights, const float *g_trans, const float *g_alphas, const int64_t *packed_info,
+                       const int64_t *tiles, int64_t n_tiles, int64_t n_rays, int64_t n_elems, float *grad_sdfs, float *grad_cos,
+                       float *grad_param, float *grad_raw_rgbs, nfa_stream_t stream)
+{
+    SEG_COMMON_CHECKS("render_sdf_bwd");
+    SDF_MODEL_CHECKS("render_sdf_bwd");
+    if (n_elems == 0) return NFA_OK;
+    NFA_REQUIRE(t_starts && t_ends && sdfs && raw_rgbs && trans && (grad_sdfs || grad_cos || grad_param || grad_raw_rgbs),
+                "render_sdf_bwd: null pointer");
+    NFA_REQUIRE(model != NFA_SDF_NEUS || cos, "render_sdf_bwd: cos is null (NFA_SDF_NEUS)");
+    NFA_REQUIRE(model == NFA_SDF_NEUS || !grad_cos, "render_sdf_bwd: grad_cos given with NFA_SDF_VOLSDF");
+    NFA_REQUIRE(param, "render_sdf_bwd: param is null");
+    const RawAct act = raw_act(selector, NFA_ACT_NONE, 0.0f, rgb_act);
+    const SdfParam par = {param, cos_anneal_ratio};
+    int rc = NFA_OK;
+    dispatch_sdf_model(model, [&](auto tag) {
+        constexpr int MD = decltype(tag)::value;
+        auto make = [&](auto V, auto X) {
+            RenderSdfBwdOp<V, X, MD> op;
+            op.sig = sdfs; op.cosv = cos; op.act = act; op.par = par; op.gcos = grad_cos; op.gpar = grad_param;
+            return op;
+        };
+        rc = launch_render_bwd("render_sdf_bwd", make, all_aligned16(sdfs, grad_cos, grad_param) && (MD != NFA_SDF_NEUS || aligned16(cos)),
+                               t_starts, t_ends, raw_rgbs, trans, g_colors, g_opacities, g_depths, g_weights, g_trans, g_alphas,
+                               grad_sdfs, grad_raw_rgbs, packed_info, tiles, n_tiles, n_rays, stream);
+    });
+    return rc;
 }
 
 int nfa_distortion_fwd(const float *weights, const float *t_starts, const float *t_ends, const int64_t *packed_info,
