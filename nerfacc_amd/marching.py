@@ -114,6 +114,9 @@ def render_rays_test_mode(
         n_counted = 0
         if ray_indices.numel() > 0:
             rgbs, sigmas = rgb_sigma_fn(t_starts, t_ends, ray_indices)
+            # (an autocast field returns fp16 / bf16, a field may return views: every form of the loop feeds the same
+            #  contiguous float32 values to the same pass)
+            rgbs, sigmas = rgbs.float().contiguous(), sigmas.float().contiguous()
             seg = getattr(packed_info, "_nfa_seg", None)
             if (seg is not None and seg[2].contiguous and rgbs.dtype == sigmas.dtype == torch.float32
                     and rgbs.dim() == 2 and rgbs.shape[-1] == 3):
@@ -126,7 +129,7 @@ def render_rays_test_mode(
                 #  scattered back after.  Since a tile owns at most 256 rows the engine walks runs of finished rays for nothing,
                 #  and the gathers, scatters and the `nonzero` read-back cost more than they saved: 114 -> 105 ms per cfg-5 image,
                 #  17.2 -> 12.5 ms per cfg-2 image without them.)
-                _render_step_native(seg[2], t_starts, t_ends, sigmas.contiguous(), rgbs.contiguous(), alpha_thre,
+                _render_step_native(seg[2], t_starts, t_ends, sigmas, rgbs, alpha_thre,
                                     rgb, opacity, depth, counter)
                 n_counted = 0 if alpha_thre > 0 else ray_indices.shape[0]
             else:
@@ -186,7 +189,8 @@ class PaddedTestModeLoop:
       replays through a pinned copy, WITHOUT waiting for it: by the time it has queued the next replays the earlier copy has
       landed.  Iterations queued after the last ray died find ``state[0] == 0`` and do nothing.
 
-    Same results as :func:`render_rays_test_mode` (same kernels on the same values; checked in tests/test_gpu_parity.py)."""
+    Same results as :func:`render_rays_test_mode` (same kernels on the same values; checked in tests/test_gpu_parity.py and, at
+    the boundary shapes -- full arrays, a handful of rays, the fill pass, a spent budget -- in tests/test_testmode_gpu.py)."""
 
     def __init__(self, max_samples, rgb_sigma_fn, estimator, rays_o, rays_d, near_plane=0.0, far_plane=1e10, render_step_size=1e-3,
                  alpha_thre=0.0, early_stop_eps=1e-4, check_every: int = 4, use_graph: bool = True):
@@ -272,8 +276,10 @@ class PaddedTestModeLoop:
         B.call("nfa_traverse_grids", C.byref(self.fill_args), s())          # rays with more than MAX_RUNS runs, if any
         B.call("nfa_seg_build_tiles", B.ptr(self.packed_info), R, cap, self.tile_elems, self.n_tiles, B.ptr(self.tiles), None, s())
         rgbs, sigmas = self.fn(self.t_starts, self.t_ends, self.ray_indices)
-        B.call("nfa_render_step_accumulate", B.ptr(self.t_starts), B.ptr(self.t_ends), B.ptr(sigmas.contiguous()),
-               B.ptr(rgbs.contiguous()), B.ptr(self.packed_info), B.ptr(self.tiles), self.n_tiles, R, cap, self.alpha_thre,
+        # the pass reads float32: a half-precision callback (an autocast field) is converted, as in render_exact
+        rgbs, sigmas = rgbs.float().contiguous(), sigmas.float().contiguous()
+        B.call("nfa_render_step_accumulate", B.ptr(self.t_starts), B.ptr(self.t_ends), B.ptr(sigmas),
+               B.ptr(rgbs), B.ptr(self.packed_info), B.ptr(self.tiles), self.n_tiles, R, cap, self.alpha_thre,
                B.ptr(self.rgb), B.ptr(self.opacity), B.ptr(self.depth), B.ptr(self.n_visible), s())
         B.call("nfa_testmode_alive", B.ptr(self.opacity), B.ptr(self.packed_info), B.ptr(self.state), self.opc_thre, R,
                B.ptr(self.ray_mask), B.ptr(self.alive), B.ptr(self.alive_count), 0 if self.alpha_thre > 0 else 1, s())
@@ -359,13 +365,17 @@ class PaddedTestModeLoop:
             budget = -(-self.max_samples // self.min_samples)
             pending = []                                     # (event, pinned slot) of the alive counts on their way to the host
             done = False
+            batches = 0                                      # batches queued so far: the pinned slots alternate with it
             self.iterations_queued = 0
             while not done and budget > 0:
                 for _ in range(min(self.check_every, budget)):
                     self.graph.replay() if self.graph is not None else self._iteration()
                     budget -= 1
                     self.iterations_queued += 1
-                slot = len(pending) & 1
+                # (len(pending) is popped back to 1 below and would name slot 1 for every batch after the first: a copy would
+                #  land in the slot whose earlier value has not been read yet)
+                slot = batches & 1
+                batches += 1
                 self.host[slot:slot + 1].copy_(self.alive_count[0:1], non_blocking=True)
                 ev = torch.cuda.Event(); ev.record()
                 pending.append((ev, slot))
