@@ -786,6 +786,37 @@ int nfa_hashgrid_bwd_bwd_sorted_i(int32_t interp, int32_t elem, const float *x, 
                                   const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params,
                                   void *grad_grad_y, float *grad_params, float *grad_x, void *scratch,
                                   int64_t scratch_bytes, nfa_stream_t stream);
+/* The forward, the first-order backward and its sorted form with the number of input dimensions as a leading argument:
+ * tiny-cuda-nn's `GridEncoding<T, N_POS_DIMS, N_FEATURES_PER_LEVEL, HASH_TYPE>` (grid type Hash, CoherentPrime hash,
+ * include/tiny-cuda-nn/encodings/grid.h) for N_POS_DIMS = n_dims = 2, 3 or 4: `kernel_grid` (forward), `kernel_grid_backward`
+ * (table gradient) and `kernel_grid_backward_input` (grad_x).  n_dims = 3 is nfa_hashgrid_fwd_i, nfa_hashgrid_bwd_i and
+ * nfa_hashgrid_bwd_sorted_i, bit for bit; those and every entry above are its n_dims = 3 case.  For n_dims = 2 and 4, per
+ * csrc/encoding.hip's header, "Other dimensions":
+ *   x and grad_x are [n_points, n_dims], contiguous, and must be 16-byte aligned (a point is one 8- or 16-byte access);
+ *   a corner is c = sum_d c_d 2^d, visited in the order 0 .. 2^n_dims - 1, its weight the left-associated product of the
+ *   first n_dims factors; a hashed level's index is q0 ^ q1 2654435761 ^ q2 805459861 ^ q3 3674653429 (the first n_dims
+ *   terms) masked to the level, a dense level's (sum_d q_d res^d mod 2^32) mod size;
+ *   size_l = min(roundup8(resolution_l^n_dims), 2^log2_hashmap_size), which the level table handed in must satisfy (scales
+ *   and resolutions do not depend on n_dims);
+ *   the sorted table gradient numbers its items i = 2^n_dims n + c: M = 2^n_dims n_points in the scratch formula above, and
+ *   2^n_dims n_points must be below 2^32.
+ * Everything else (interp, elem, which outputs are optional, what is bitwise reproducible) is as in the `_i` entries.  Any
+ * other n_dims is NFA_EINVAL (nfa_hashgrid_sorted_scratch_bytes_d: -1) with a message that names the value.  The second
+ * order exists for n_dims = 3 only. */
+int nfa_hashgrid_fwd_d(int32_t n_dims, int32_t interp, int32_t elem, const float *x, const float *params, int64_t n_points,
+                       int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                       const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, void *y,
+                       nfa_stream_t stream);
+int nfa_hashgrid_bwd_d(int32_t n_dims, int32_t interp, int32_t elem, const float *x, const float *params,
+                       const void *grad_y, int64_t n_points, int32_t n_levels, int32_t n_features,
+                       int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                       const int32_t *sizes_host, int64_t n_params, float *grad_params, float *grad_x, nfa_stream_t stream);
+int nfa_hashgrid_bwd_sorted_d(int32_t n_dims, int32_t interp, int32_t elem, const float *x, const float *params,
+                              const void *grad_y, int64_t n_points, int32_t n_levels, int32_t n_features,
+                              int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                              const int32_t *sizes_host, int64_t n_params, float *grad_params, float *grad_x,
+                              void *scratch, int64_t scratch_bytes, nfa_stream_t stream);
+int64_t nfa_hashgrid_sorted_scratch_bytes_d(int32_t n_dims, int64_t n_points, int32_t n_levels, int32_t log2_hashmap_size);
 int nfa_sh_fwd_t(int32_t elem, const float *dirs, int64_t n_points, int32_t degree, void *out, nfa_stream_t stream);
 int nfa_sh_bwd_t(int32_t elem, const float *dirs, const void *grad_out, int64_t n_points, int32_t degree,
                  float *grad_dirs, nfa_stream_t stream);

@@ -137,6 +137,11 @@ _SIGS = {
     "nfa_hashgrid_bwd_sorted_i": [_i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp],
     "nfa_hashgrid_bwd_bwd_sorted_i": [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                       _i64, _vp],
+    "nfa_hashgrid_fwd_d": [_i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
+    "nfa_hashgrid_bwd_d": [_i32, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "nfa_hashgrid_bwd_sorted_d": [_i32, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64,
+                                  _vp],
+    "nfa_hashgrid_sorted_scratch_bytes_d": [_i32, _i64, _i32, _i32],
     "nfa_sh_fwd_t": [_i32, _vp, _i64, _i32, _vp, _vp],
     "nfa_sh_bwd_t": [_i32, _vp, _vp, _i64, _i32, _vp, _vp],
     "nfa_sample_positions_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
@@ -152,7 +157,7 @@ _SIGS = {
     "nfa_set_tuning": [C.c_char_p, C.c_char_p],
     "nfa_device_arch": [C.c_char_p, _int],
 }
-_RESTYPES = {"nfa_grid_rebinarize_scratch_bytes": _i64, "nfa_hashgrid_sorted_scratch_bytes": _i64, "nfa_bricks_words": _i64, "nfa_walk_bits_words": _i64, "nfa_pdf_loss_partials": _i64, "nfa_cumsum_scratch_bytes": _i64, "nfa_seg_table_rows": _i64, "nfa_seg_plan": None, "nfa_last_error": C.c_char_p}
+_RESTYPES = {"nfa_grid_rebinarize_scratch_bytes": _i64, "nfa_hashgrid_sorted_scratch_bytes": _i64, "nfa_hashgrid_sorted_scratch_bytes_d": _i64, "nfa_bricks_words": _i64, "nfa_walk_bits_words": _i64, "nfa_pdf_loss_partials": _i64, "nfa_cumsum_scratch_bytes": _i64, "nfa_seg_table_rows": _i64, "nfa_seg_plan": None, "nfa_last_error": C.c_char_p}
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

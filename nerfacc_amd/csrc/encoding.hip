@@ -1,6 +1,9 @@
-// encoding.hip -- input encodings of Instant-NGP radiance fields: the multiresolution hash grid (D = 3, linear or
-// smoothstep interpolation) and the spherical-harmonics direction encoding, as tiny-cuda-nn's `HashGrid` and
-// `SphericalHarmonics` define them (Mueller et al. 2022, "Instant Neural Graphics Primitives", sec. 3).
+// encoding.hip -- input encodings of Instant-NGP radiance fields: the multiresolution hash grid (D = 2, 3 or 4 input
+// dimensions, linear or smoothstep interpolation) and the spherical-harmonics direction encoding, as tiny-cuda-nn's
+// `HashGrid` and `SphericalHarmonics` define them (Mueller et al. 2022, "Instant Neural Graphics Primitives", sec. 3).
+//
+// The formulas below are written out for D = 3; "Other dimensions" after them states what D = 2 and D = 4 change.  D is a
+// template parameter of every step that depends on it; the second order is D = 3 only.
 //
 // Hash grid, per point x and level l (all integer arithmetic uint32, wrapping):
 //   p_d = x_d * scale_l + 0.5 (a multiply, then an add: the library builds with -ffp-contract=off)
@@ -51,6 +54,23 @@
 //              The second summand of h_e is the pure second partial d2/dx_e2 that the linear grid lacks.
 // The interpolation is a template parameter of the kernels that form a weight (forward, backward, second order, hs_term of the
 // sorted path); the Linear instantiations are the code they were before it existed.
+//
+// Other dimensions (D = 2, 4; forward, first-order backward and the sorted table gradient).  x is [N, D], contiguous and
+// 16-byte aligned, a point being one 8-byte (D = 2) or 16-byte (D = 4) load; p_d, g_d, f_d (and S_d, S'_d) per dimension as above.
+//   corner c = sum_d c_d 2^d in the order 0 .. 2^D - 1, q_d = g_d + c_d
+//     dense level:  idx = (sum_d q_d res^d mod 2^32) mod size_l, the powers formed as wrapping products and the sum taken in
+//                   ascending d
+//     hashed level: idx = (q0 ^ q1 * 2654435761 ^ q2 * 805459861 ^ q3 * 3674653429) & (size_l - 1), the first D terms
+//                   (tiny-cuda-nn's primes of dimensions 0..3)
+//     size_l = min(roundup8(res_l^D), 2^log2_hashmap_size), hashed when roundup8(res_l^D) is the larger; scale_l and res_l
+//                   do not depend on D
+//     w_c = ((w_0 * w_1) * w_2) * w_3, the left-associated product of the first D factors
+//   forward and table-gradient term as above over the 2^D corners.
+//   dL/dx_e: per corner (sign of c_e) (prod_{d != e} w_d) * dot_c, the product over the other dimensions in ascending d,
+//     left-associated; then the corner sum * s (Linear) or (* S'_e) * s (Smoothstep), summed over the levels as above.
+//   The sorted path numbers its items i = 2^D n + c (2^D n_points < 2^32) and is otherwise unchanged.
+// At D = 4 the 16 corners of a (point, level) are visited in groups, in corner order, a group's gathers being consumed before
+// the next group's start (corner_group below; DESIGN.md "Hash grid: 2-D and 4-D inputs").
 //
 // Element types: y / dL/dy (and the spherical harmonics' out / dL/dout) are float, fp16 or bf16 (NFA_ELEM_*, common.hip.h).
 // The arithmetic is the float32 one whatever the type; a point's F values of a level are converted once and moved as one
@@ -123,16 +143,31 @@ __device__ __forceinline__ void load_elems(const E *p, float *v)
     }
 }
 
-struct Cell {
-    uint32_t g[3];
-    float f[3];
+#define NFA_HG_MAX_DIMS 4
+
+template <int D> struct Cell {
+    uint32_t g[D];
+    float f[D];
 };
 
-__device__ __forceinline__ Cell locate(const float *__restrict__ xp, float scale)
+// The cell of the point at p on a level.  D = 2 and 4 read the point as one 8- or 16-byte load (x is 16-byte aligned).
+template <int D>
+__device__ __forceinline__ Cell<D> locate(const float *__restrict__ p, float scale)
 {
-    Cell c;
+    float xp[D];
+    if constexpr (D == 2) {
+        const float2 v = *reinterpret_cast<const float2 *>(p);
+        xp[0] = v.x; xp[1] = v.y;
+    } else if constexpr (D == 4) {
+        const float4 v = *reinterpret_cast<const float4 *>(p);
+        xp[0] = v.x; xp[1] = v.y; xp[2] = v.z; xp[3] = v.w;
+    } else {
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
+        for (int d = 0; d < D; ++d) xp[d] = p[d];
+    }
+    Cell<D> c;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
         const float p = xp[d] * scale + 0.5f;
         const float fl = floorf(p);
         c.f[d] = p - fl;
@@ -151,18 +186,36 @@ struct LevelRef {
         : scale(T.scale[l]), res(T.res[l]), size(T.size[l]), offset(T.offset[l]), hashed((T.hashed >> l) & 1u) {}
 };
 
-__device__ __forceinline__ uint32_t corner_index(const Cell &c, int corner, const LevelRef &L)
+// tiny-cuda-nn's hash primes of dimensions 1..3 (dimension 0: 1)
+__host__ __device__ constexpr uint32_t hash_prime(int d) { return d == 1 ? 2654435761u : d == 2 ? 805459861u : 3674653429u; }
+
+template <int D>
+__device__ __forceinline__ uint32_t corner_index(const Cell<D> &c, int corner, const LevelRef &L)
 {
-    const uint32_t q0 = c.g[0] + (corner & 1), q1 = c.g[1] + ((corner >> 1) & 1), q2 = c.g[2] + ((corner >> 2) & 1);
-    if (L.hashed) return (q0 ^ (q1 * 2654435761u) ^ (q2 * 805459861u)) & (L.size - 1u);
-    return (q0 + q1 * L.res + q2 * (L.res * L.res)) % L.size;
+    uint32_t q[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) q[d] = c.g[d] + ((corner >> d) & 1);
+    if (L.hashed) {
+        uint32_t h = q[0];
+#pragma unroll
+        for (int d = 1; d < D; ++d) h ^= q[d] * hash_prime(d);
+        return h & (L.size - 1u);
+    }
+    uint32_t idx = q[0], power = L.res;
+#pragma unroll
+    for (int d = 1; d < D; ++d) {
+        idx += q[d] * power;
+        power *= L.res;
+    }
+    return idx % L.size;
 }
 
 // Smoothstep (header): the cell's fractions become S_d, so that Corner gives w_d; d1 = S', d2 = S''
-__device__ __forceinline__ void smoothstep(Cell &c, float *d1, float *d2)
+template <int D>
+__device__ __forceinline__ void smoothstep(Cell<D> &c, float *d1, float *d2)
 {
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
+    for (int d = 0; d < D; ++d) {
         const float f = c.f[d];
         d1[d] = (6.0f * f) * (1.0f - f);
         d2[d] = 6.0f - 12.0f * f;
@@ -172,31 +225,55 @@ __device__ __forceinline__ void smoothstep(Cell &c, float *d1, float *d2)
 
 // The terms of one corner (header).  This is the one place where a table-gradient coefficient is written down: the atomic
 // kernels and hs_term of the sorted path both take it from here, so each sorted term is the float32 value the atomic pass adds.
-struct Corner {
+template <int D> struct Corner {
     int bits;
-    float w[3];   // w_d = (c_d ? f_d : 1 - f_d), f_d being S_d under Smoothstep
-    __device__ __forceinline__ Corner(const Cell &c, int corner) : bits(corner)
+    float w[D];   // w_d = (c_d ? f_d : 1 - f_d), f_d being S_d under Smoothstep
+    __device__ __forceinline__ Corner(const Cell<D> &c, int corner) : bits(corner)
     {
 #pragma unroll
-        for (int d = 0; d < 3; ++d) w[d] = ((corner >> d) & 1) ? c.f[d] : 1.0f - c.f[d];
+        for (int d = 0; d < D; ++d) w[d] = ((corner >> d) & 1) ? c.f[d] : 1.0f - c.f[d];
     }
     // u_d = (c_d ? v_d : -v_d); Smoothstep: v holds v_d * S'_d, formed once per (point, level)
     __device__ __forceinline__ void signed_v(const float *v, float *u) const
     {
 #pragma unroll
-        for (int d = 0; d < 3; ++d) u[d] = ((bits >> d) & 1) ? v[d] : -v[d];
+        for (int d = 0; d < D; ++d) u[d] = ((bits >> d) & 1) ? v[d] : -v[d];
     }
-    __device__ __forceinline__ float first_order() const { return (w[0] * w[1]) * w[2]; }                  // w_c
+    __device__ __forceinline__ float first_order() const                                                     // w_c
+    {
+        float p = w[0];
+#pragma unroll
+        for (int d = 1; d < D; ++d) p = p * w[d];
+        return p;
+    }
+    // prod_{d != e} w_d in ascending d, left-associated: the factor of dot_c in dL/dx_e
+    template <int E> __device__ __forceinline__ float others() const
+    {
+        constexpr int a = E == 0 ? 1 : 0;
+        float p = w[a];
+        if constexpr (D > 2) {
+            constexpr int b = a + 1 == E ? a + 2 : a + 1;
+            p = p * w[b];
+            if constexpr (D > 3) p = p * w[b + 1 == E ? b + 2 : b + 1];
+        }
+        return p;
+    }
     __device__ __forceinline__ float second_order(const float *u, float s) const                             // a_c
     {
+        static_assert(D == 3, "the second order is 3-D only");
         return ((u[0] * (w[1] * w[2]) + u[1] * (w[0] * w[2])) + u[2] * (w[0] * w[1])) * s;
     }
     // dx_d = (c_d ? dx_d + t_d : dx_d - t_d)
-    __device__ __forceinline__ void accumulate(float *dx, float t0, float t1, float t2) const
+    __device__ __forceinline__ void accumulate(float *dx, const float *t) const
     {
-        dx[0] = (bits & 1) ? dx[0] + t0 : dx[0] - t0;
-        dx[1] = (bits & 2) ? dx[1] + t1 : dx[1] - t1;
-        dx[2] = (bits & 4) ? dx[2] + t2 : dx[2] - t2;
+#pragma unroll
+        for (int d = 0; d < D; ++d) dx[d] = ((bits >> d) & 1) ? dx[d] + t[d] : dx[d] - t[d];
+    }
+    // the first-order terms t_e = (prod_{d != e} w_d) * dot_c, e = 0 .. D - 1
+    template <size_t... E> __device__ __forceinline__ void accumulate_dot(float *dx, float dot, std::index_sequence<E...>) const
+    {
+        const float t[D] = {(others<(int)E>() * dot)...};
+        accumulate(dx, t);
     }
 };
 
@@ -226,7 +303,19 @@ __device__ __forceinline__ void store_piece(E *__restrict__ p, int64_t piece, co
 // stays in one XCD's L2 (4 MiB: a hashed level of the NGP grid), and write their F-float pieces at a stride of L F floats.
 // Measured against one lane per (point, level) with the level fastest in the wave (coalesced output rows): 0.83-0.90 of
 // its time at 2^20 points (DESIGN.md "Input encodings").
-template <int F, class E, int I>
+// The corners of a (point, level) are visited in groups of corner_group<D, F>(): the loop over the groups is a real loop,
+// the group itself unrolled, so a group's gathers are in flight together and are consumed before the next group's start.
+// Up to D = 3 the group is all 2^D corners.  At D = 4 it is 8 corners, 4 from F = 4: with all 16 gathers in flight the
+// forward holds 16 F values (146 VGPRs at F = 8, 3 waves per SIMD; DESIGN.md "Hash grid: 2-D and 4-D inputs").  The corner
+// order of the sums does not depend on the grouping.
+template <int D, int F>
+__host__ __device__ constexpr int corner_group() { return D <= 3 ? 1 << D : F >= 4 ? 4 : 8; }
+// (the backward holds a point's F values of dL/dy and its D shares of dL/dx next to a corner's values: at D = 4 all 16
+// corners are unrolled up to F = 2, F = 4 takes them in pairs and F = 8 one by one)
+template <int D, int F>
+__host__ __device__ constexpr int corner_group_bwd() { return D <= 3 || F < 4 ? 1 << D : F < 8 ? 2 : 1; }
+
+template <int D, int F, class E, int I>
 __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const float *__restrict__ x, const float *__restrict__ params,
                                                            int64_t n_points, const HashGridLevels T, E *__restrict__ y)
 {
@@ -235,20 +324,23 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const float *__restri
     const FVec<F> *tab = reinterpret_cast<const FVec<F> *>(params) + L.offset;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < n_points; n += stride) {
-        Cell c = locate(x + n * 3, L.scale);
+        Cell<D> c = locate<D>(x + n * D, L.scale);
         if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
-            float d1[3], d2[3];
+            float d1[D], d2[D];
             smoothstep(c, d1, d2);
         }
         float acc[F];
 #pragma unroll
         for (int j = 0; j < F; ++j) acc[j] = 0.0f;
+#pragma nounroll
+        for (int first = 0; first < (1 << D); first += corner_group<D, F>()) {
 #pragma unroll
-        for (int corner = 0; corner < 8; ++corner) {
-            const FVec<F> v = tab[corner_index(c, corner, L)];
-            const float wc = Corner(c, corner).first_order();
+            for (int corner = first; corner < first + corner_group<D, F>(); ++corner) {
+                const FVec<F> v = tab[corner_index(c, corner, L)];
+                const float wc = Corner<D>(c, corner).first_order();
 #pragma unroll
-            for (int j = 0; j < F; ++j) acc[j] = acc[j] + wc * v.v[j];
+                for (int j = 0; j < F; ++j) acc[j] = acc[j] + wc * v.v[j];
+            }
         }
         store_piece<F>(y, n * T.n_levels + l, acc);
     }
@@ -276,41 +368,72 @@ struct LaneItems {
     __device__ __forceinline__ bool more() const { return w < n_waves; }
     __device__ __forceinline__ void next() { w += wave_stride; item(); }
     // dx summed over the point's L lanes in level order; the level-0 lane writes (call under a wave-uniform branch)
-    __device__ __forceinline__ void sum_levels(float d0, float d1, float d2, float *__restrict__ g_x) const
+    // (g_x [N, D]: one 8- or 16-byte store per point at D = 2, 4, which need it 16-byte aligned like x)
+    // (share: this lane's D shares, s: the D running sums, all by value and as scalars; see above.  S... is deduced from the
+    // Shares tag alone, so both packs have D floats.  For D = 3, sum_levels(dx, g_x, ..) calls
+    //   sum_shares(g_x, Shares<float, float, float>{}, dx[0], dx[1], dx[2], 0.0f, 0.0f, 0.0f), whose loop body reads
+    //   v0 = __shfl(share0, src, 64), v1 = .., v2 = ..;  s0 = k == 0 ? v0 : s0 + v0;  s1 = ..;  s2 = ..;
+    // the three scalar sums of the 3-D code this came from.)
+    template <class... S> struct Shares {};
+    template <class... S>
+    __device__ __forceinline__ void sum_shares(float *__restrict__ g_x, Shares<S...>, S... share, S... s) const
     {
+        constexpr int D = sizeof...(S);
         const int first = (int)(threadIdx.x & 63) - l;
-        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
         for (int k = 0; k < n_levels; ++k) {
             const int src = min(first + k, 63);
-            const float v0 = __shfl(d0, src, 64), v1 = __shfl(d1, src, 64), v2 = __shfl(d2, src, 64);
-            s0 = k == 0 ? v0 : s0 + v0; s1 = k == 0 ? v1 : s1 + v1; s2 = k == 0 ? v2 : s2 + v2;
+            [&](auto... v) { ((s = k == 0 ? v : s + v), ...); }(__shfl(share, src, 64)...);
         }
         if (active && l == 0) {
-            g_x[n * 3 + 0] = s0; g_x[n * 3 + 1] = s1; g_x[n * 3 + 2] = s2;
+            const float out[D] = {s...};
+            if constexpr (D == 2) {
+                reinterpret_cast<float2 *>(g_x)[n] = make_float2(out[0], out[1]);
+            } else if constexpr (D == 4) {
+                reinterpret_cast<float4 *>(g_x)[n] = make_float4(out[0], out[1], out[2], out[3]);
+            } else {
+#pragma unroll
+                for (int d = 0; d < D; ++d) g_x[n * D + d] = out[d];
+            }
         }
+    }
+    template <int D, size_t... K>
+    __device__ __forceinline__ void sum_levels(const float (&dx)[D], float *__restrict__ g_x, std::index_sequence<K...>) const
+    {
+        sum_shares(g_x, Shares<decltype(+dx[K])...>{}, dx[K]..., ((void)K, 0.0f)...);
     }
 };
 
-template <int F, class E, int I>
+// A (point, level)'s corner sums of dL/dx_d, d = 0 .. D - 1, times s (Linear) or (* S'_d) * s (Smoothstep).  Written as a
+// pack expansion, like the level sum above: as loops over d the D = 3 kernels come out with other registers.
+template <int I, int D, size_t... K>
+__device__ __forceinline__ void scale_dx(float (&dx)[D], const float *d1, float s, std::index_sequence<K...>)
+{
+    if constexpr (I == NFA_INTERP_SMOOTHSTEP) ((dx[K] = (dx[K] * d1[K]) * s), ...);
+    else ((dx[K] *= s), ...);
+}
+
+template <int D, int F, class E, int I>
 __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restrict__ x, const float *__restrict__ params,
                                                            const E *__restrict__ g_y, int64_t n_points,
                                                            const HashGridLevels T, float *__restrict__ g_params,
                                                            float *__restrict__ g_x)
 {
     for (LaneItems it(T, n_points); it.more(); it.next()) {
-        float dx[3] = {0.0f, 0.0f, 0.0f};
+        float dx[D] = {};
         if (it.active) {
             const int64_t n = it.n;
             const int l = it.l;
             const LevelRef L(T, l);
-            Cell c = locate(x + n * 3, L.scale);
-            float d1[3], d2[3];
+            Cell<D> c = locate<D>(x + n * D, L.scale);
+            float d1[D], d2[D];
             if constexpr (I == NFA_INTERP_SMOOTHSTEP) smoothstep(c, d1, d2);
             const FVec<F> g = load_piece<F>(g_y, n * T.n_levels + l);
+#pragma nounroll
+            for (int first = 0; first < (1 << D); first += corner_group_bwd<D, F>())
 #pragma unroll
-            for (int corner = 0; corner < 8; ++corner) {
+            for (int corner = first; corner < first + corner_group_bwd<D, F>(); ++corner) {
                 const uint32_t e = L.offset + corner_index(c, corner, L);
-                const Corner k(c, corner);
+                const Corner<D> k(c, corner);
                 if (g_params) {
                     const float wc = k.first_order();
                     float *dst = g_params + (size_t)e * F;
@@ -322,19 +445,15 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const float *__restri
                     float dot = 0.0f;
 #pragma unroll
                     for (int j = 0; j < F; ++j) dot = dot + g.v[j] * v.v[j];
-                    k.accumulate(dx, (k.w[1] * k.w[2]) * dot, (k.w[0] * k.w[2]) * dot, (k.w[0] * k.w[1]) * dot);
+                    k.accumulate_dot(dx, dot, std::make_index_sequence<D>{});
                 }
             }
             if (g_x) {
                 const float s = L.scale;
-                if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
-                    dx[0] = (dx[0] * d1[0]) * s; dx[1] = (dx[1] * d1[1]) * s; dx[2] = (dx[2] * d1[2]) * s;
-                } else {
-                    dx[0] *= s; dx[1] *= s; dx[2] *= s;
-                }
+                scale_dx<I>(dx, d1, s, std::make_index_sequence<D>{});
             }
         }
-        if (g_x) it.sum_levels(dx[0], dx[1], dx[2], g_x);
+        if (g_x) it.sum_levels(dx, g_x, std::make_index_sequence<D>{});
     }
 }
 
@@ -354,7 +473,7 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_bwd_kernel(const float *__re
             const int l = it.l;
             const LevelRef L(T, l);
             const float s = L.scale;
-            Cell c = locate(x + n * 3, s);
+            Cell<3> c = locate<3>(x + n * 3, s);
             float v[3] = {gg_x[n * 3 + 0], gg_x[n * 3 + 1], gg_x[n * 3 + 2]};
             float d1[3], p[3];   // Smoothstep: S'_d, v_d * S''_d; v_d becomes v_d * S'_d
             if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
@@ -372,7 +491,7 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_bwd_kernel(const float *__re
 #pragma unroll
             for (int corner = 0; corner < 8; ++corner) {
                 const uint32_t e = L.offset + corner_index(c, corner, L);
-                const Corner k(c, corner);
+                const Corner<3> k(c, corner);
                 const float *w = k.w;
                 float u[3];
                 k.signed_v(v, u);
@@ -391,12 +510,14 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_bwd_kernel(const float *__re
 #pragma unroll
                         for (int j = 0; j < F; ++j) dot = dot + g.v[j] * t.v[j];
                         if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
-                            k.accumulate(dx, (d1[0] * (u[1] * w[2] + u[2] * w[1]) + p[0] * (w[1] * w[2])) * dot,
-                                         (d1[1] * (u[0] * w[2] + u[2] * w[0]) + p[1] * (w[0] * w[2])) * dot,
-                                         (d1[2] * (u[0] * w[1] + u[1] * w[0]) + p[2] * (w[0] * w[1])) * dot);
+                            const float t[3] = {(d1[0] * (u[1] * w[2] + u[2] * w[1]) + p[0] * (w[1] * w[2])) * dot,
+                                                (d1[1] * (u[0] * w[2] + u[2] * w[0]) + p[1] * (w[0] * w[2])) * dot,
+                                                (d1[2] * (u[0] * w[1] + u[1] * w[0]) + p[2] * (w[0] * w[1])) * dot};
+                            k.accumulate(dx, t);
                         } else {
-                            k.accumulate(dx, (u[1] * w[2] + u[2] * w[1]) * dot, (u[0] * w[2] + u[2] * w[0]) * dot,
-                                         (u[0] * w[1] + u[1] * w[0]) * dot);
+                            const float t[3] = {(u[1] * w[2] + u[2] * w[1]) * dot, (u[0] * w[2] + u[2] * w[0]) * dot,
+                                                (u[0] * w[1] + u[1] * w[0]) * dot};
+                            k.accumulate(dx, t);
                         }
                     }
                 }
@@ -406,7 +527,7 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_bwd_kernel(const float *__re
                 dx[0] = (dx[0] * s) * s; dx[1] = (dx[1] * s) * s; dx[2] = (dx[2] * s) * s;
             }
         }
-        if (g_x) it.sum_levels(dx[0], dx[1], dx[2], g_x);
+        if (g_x) it.sum_levels(dx, g_x, std::make_index_sequence<3>{});
     }
 }
 
@@ -578,6 +699,7 @@ __global__ __launch_bounds__(256) void sh_bwd_kernel(const float *__restrict__ d
 // ---------------------------------------------------------------- argument checks
 // The grid description of a call, filled at the extern "C" boundary
 struct GridArgs {
+    int32_t n_dims;   // 2, 3 or 4
     int64_t n_points;
     int32_t n_levels, n_features, log2_hashmap_size;
     const float *scales_host;
@@ -587,6 +709,7 @@ struct GridArgs {
 
 static int hashgrid_table(const char *name, const GridArgs &G, HashGridLevels &T)
 {
+    NFA_REQUIRE(G.n_dims >= 2 && G.n_dims <= NFA_HG_MAX_DIMS, "%s: n_dims must be 2, 3 or 4 (got %d)", name, G.n_dims);
     NFA_REQUIRE(G.n_points >= 0 && G.n_params >= 0, "%s: negative size", name);
     NFA_REQUIRE(G.n_features == 1 || G.n_features == 2 || G.n_features == 4 || G.n_features == 8,
                 "%s: n_features must be 1, 2, 4 or 8 (got %d)", name, G.n_features);
@@ -601,9 +724,12 @@ static int hashgrid_table(const char *name, const GridArgs &G, HashGridLevels &T
     for (int l = 0; l < G.n_levels; ++l) {
         const int64_t r = G.resolutions_host[l], s = G.sizes_host[l];
         NFA_REQUIRE(r >= 1, "%s: level %d resolution %lld out of range", name, l, (long long)r);
-        const int64_t dense = r > (1 << 20) ? INT64_MAX : (r * r * r + 7) / 8 * 8;   // (no overflow; hashed anyway)
-        NFA_REQUIRE(s == (dense < table ? dense : table), "%s: level %d size %lld is not min(roundup8(res^3), 2^%d)",
-                    name, l, (long long)s, G.log2_hashmap_size);
+        const int64_t big = (int64_t)1 << 40;   // past every table: res^D stops here (no overflow; hashed anyway)
+        int64_t cells = r > (1 << 20) ? big : 1;
+        for (int d = 0; d < G.n_dims && cells < big; ++d) cells *= r;
+        const int64_t dense = cells >= big ? INT64_MAX : (cells + 7) / 8 * 8;
+        NFA_REQUIRE(s == (dense < table ? dense : table), "%s: level %d size %lld is not min(roundup8(res^%d), 2^%d)",
+                    name, l, (long long)s, G.n_dims, G.log2_hashmap_size);
         T.scale[l] = G.scales_host[l];
         T.res[l] = (uint32_t)r;
         T.offset[l] = (uint32_t)offset;
@@ -634,17 +760,20 @@ static int check_interp(const char *name, int32_t interp)
 }
 
 // Host-side dispatch of a run-time value to a compile-time one, f(std::integral_constant<int, V>), for the V... it was
-// checked to be one of; of (n_features, interp) to f(.. <int, F>, .. <int, I>); and of the spherical-harmonics degree.
+// checked to be one of; of a grid's (n_dims, n_features, interp) to f(.. <int, D>, .. <int, F>, .. <int, I>) for the Dims... a
+// pass is instantiated for (all three, or 3 alone: the second order); and of the spherical-harmonics degree.
 template <int... V, class Fn>
 static void dispatch_int(int32_t v, Fn &&f)
 {
     (void)((v == V && (f(std::integral_constant<int, V>{}), true)) || ...);
 }
-template <class Fn>
-static void dispatch_grid(int32_t n_features, int32_t interp, Fn &&f)
+template <int... Dims, class Fn>
+static void dispatch_grid(const GridArgs &G, int32_t interp, Fn &&f)
 {
-    dispatch_int<NFA_INTERP_LINEAR, NFA_INTERP_SMOOTHSTEP>(interp, [&](auto i) {
-        dispatch_int<1, 2, 4, 8>(n_features, [&](auto n) { f(n, i); });
+    dispatch_int<Dims...>(G.n_dims, [&](auto d) {
+        dispatch_int<NFA_INTERP_LINEAR, NFA_INTERP_SMOOTHSTEP>(interp, [&](auto i) {
+            dispatch_int<1, 2, 4, 8>(G.n_features, [&](auto n) { f(d, n, i); });
+        });
     });
 }
 template <class Fn>
@@ -661,11 +790,12 @@ static int hashgrid_fwd(int32_t interp, const float *x, const float *params, con
     if (rc != NFA_OK) return rc;
     if (G.n_points == 0) return NFA_OK;
     NFA_REQUIRE(x && params && y, "hashgrid_fwd: null pointer");
+    NFA_REQUIRE(G.n_dims == 3 || aligned16(x), "hashgrid_fwd: x must be 16-byte aligned at n_dims %d", G.n_dims);
     NFA_REQUIRE((std::is_same<E, float>::value) || aligned16(y), "hashgrid_fwd: a half y must be 16-byte aligned");
     hipStream_t s = as_stream(stream);
     const dim3 grid(grid_1d(G.n_points, 256, 256 * 16 / G.n_levels + 1), G.n_levels), block(256);
-    dispatch_grid(G.n_features, interp, [&](auto f, auto i) {
-        hipLaunchKernelGGL((hashgrid_fwd_kernel<f(), E, i()>), grid, block, 0, s, x, params, G.n_points, T, y);
+    dispatch_grid<2, 3, 4>(G, interp, [&](auto d, auto f, auto i) {
+        hipLaunchKernelGGL((hashgrid_fwd_kernel<d(), f(), E, i()>), grid, block, 0, s, x, params, G.n_points, T, y);
     });
     NFA_CHECK_LAUNCH("hashgrid_fwd");
     return NFA_OK;
@@ -676,9 +806,9 @@ static int hashgrid_bwd_launch(int32_t interp, const float *x, const float *para
                                const HashGridLevels &T, float *grad_params, float *grad_x, hipStream_t s)
 {
     const dim3 grid(hashgrid_grid(G.n_points, T)), block(256);
-    dispatch_grid(G.n_features, interp, [&](auto f, auto i) {
-        hipLaunchKernelGGL((hashgrid_bwd_kernel<f(), E, i()>), grid, block, 0, s, x, params, grad_y, G.n_points, T, grad_params,
-                           grad_x);
+    dispatch_grid<2, 3, 4>(G, interp, [&](auto d, auto f, auto i) {
+        hipLaunchKernelGGL((hashgrid_bwd_kernel<d(), f(), E, i()>), grid, block, 0, s, x, params, grad_y, G.n_points, T,
+                           grad_params, grad_x);
     });
     NFA_CHECK_LAUNCH("hashgrid_bwd");
     return NFA_OK;
@@ -693,6 +823,8 @@ static int hashgrid_bwd(int32_t interp, const float *x, const float *params, con
     if (rc != NFA_OK) return rc;
     if (G.n_points == 0) return NFA_OK;
     NFA_REQUIRE(x && grad_y && (grad_params || grad_x) && (params || !grad_x), "hashgrid_bwd: null pointer");
+    NFA_REQUIRE(G.n_dims == 3 || all_aligned16(x, grad_x), "hashgrid_bwd: x and grad_x must be 16-byte aligned at n_dims %d",
+                G.n_dims);
     NFA_REQUIRE((std::is_same<E, float>::value) || aligned16(grad_y), "hashgrid_bwd: a half grad_y must be 16-byte aligned");
     return hashgrid_bwd_launch(interp, x, params, grad_y, G, T, grad_params, grad_x, as_stream(stream));
 }
@@ -703,7 +835,7 @@ static int hashgrid_bwd_bwd_launch(int32_t interp, const float *x, const float *
                                    float *grad_params, float *grad_x, hipStream_t s)
 {
     const dim3 grid(hashgrid_grid(G.n_points, T)), block(256);
-    dispatch_grid(G.n_features, interp, [&](auto f, auto i) {
+    dispatch_grid<3>(G, interp, [&](auto, auto f, auto i) {
         hipLaunchKernelGGL((hashgrid_bwd_bwd_kernel<f(), E, i()>), grid, block, 0, s, x, params, grad_y, grad_grad_x,
                            G.n_points, T, grad_grad_y, grad_params, grad_x);
     });
@@ -764,10 +896,11 @@ static int sh_bwd(const float *dirs, const E *grad_out, int64_t n_points, int32_
 
 // ---------------------------------------------------------------- reproducible table gradient: sort and segmented sum
 // nfa_hashgrid_bwd_sorted / nfa_hashgrid_bwd_bwd_sorted form the table gradient without float atomics.  THE ORDER OF THE SUM,
-// per level (tests/hashgrid_sorted_reference.py restates it):
-//   items   i = 8 n + c for point n and corner c, in that order; key_i = the corner's entry index inside the level (locate /
-//           corner_index as above); term_i[j] = coef_i * g[n][j] in float32, coef_i = (w_0 * w_1) * w_2 at first order and
-//           a_c (header, "Second order") at second order, g the point's dL/dy piece of the level converted once.
+// per level (tests/hashgrid_sorted_reference.py restates it; for any D tests/hashgrid_nd_reference.py):
+//   items   i = 2^D n + c (D = 3: 8 n + c) for point n and corner c, in that order; key_i = the corner's entry index inside
+//           the level (locate / corner_index as above); term_i[j] = coef_i * g[n][j] in float32, coef_i = w_c, the left-
+//           associated product of the first D factors (D = 3: (w_0 * w_1) * w_2), at first order and a_c (header, "Second
+//           order"; D = 3 only) at second order, g the point's dL/dy piece of the level converted once.
 //   sort    the items are sorted by key with a stable LSD radix sort (8-bit digits over the ceil(log2 size_l) significant bits):
 //           equal keys stay in ascending i, that is ascending point and then corner.
 //   tiles   the sorted array is cut into tiles of NFA_HS_TILE = 256 consecutive items.  A run of equal keys is cut into
@@ -780,7 +913,7 @@ static int sh_bwd(const float *dirs, const E *grad_out, int64_t n_points, int32_
 // is read back, so a step can be captured.
 //
 // Scratch: levels are processed in groups of G, one level per workgroup row, each with its own slab of
-//   level_bytes = 16 M + 1024 (B + 1) + 64 Tn,  M = 8 n_points, B = ceil(M / 4096), Tn = ceil(M / 256):
+//   level_bytes = 16 M + 1024 (B + 1) + 64 Tn,  M = 2^D n_points, B = ceil(M / 4096), Tn = ceil(M / 256):
 //   two key and two id buffers of M uint32 (ping-pong), 256 B block counts + 256 digit totals, Tn x {head, tail} x 8 floats;
 //   G = min(n_levels, max(1, floor(2^29 / level_bytes))); scratch = n_levels level_bytes where that is at most 2^29, else
 //   max(2^29, level_bytes): at least G level_bytes, and monotone in n_points.
@@ -799,10 +932,10 @@ struct HashSortPlan {
     int32_t group;
 };
 
-static HashSortPlan hashsort_plan(int64_t n_points, int32_t n_levels)
+static HashSortPlan hashsort_plan(int64_t n_points, int32_t n_levels, int32_t n_dims)
 {
     HashSortPlan p;
-    p.items = 8 * n_points;
+    p.items = n_points << n_dims;   // 2^D items per point
     p.n_blocks = ceil_div64(p.items, NFA_HS_BLOCK_ITEMS);
     p.n_tiles = ceil_div64(p.items, NFA_HS_TILE);
     p.level_bytes = 16 * p.items + 1024 * (p.n_blocks + 1) + 64 * p.n_tiles;
@@ -879,14 +1012,15 @@ __device__ __forceinline__ uint32_t block_excl_sum_256(uint32_t v, uint32_t *ws,
     return pre + incl - v;
 }
 
+template <int D>
 __global__ __launch_bounds__(256) void hs_keys_kernel(const float *__restrict__ x, const HashGridLevels T, const HashSortArgs A)
 {
     const LevelRef L(T, A.first_level + (int)blockIdx.y);
     uint32_t *keys = hs_view(A, (int)blockIdx.y).keys0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.items; i += stride) {
-        const Cell c = locate(x + (i >> 3) * 3, L.scale);
-        keys[i] = corner_index(c, (int)(i & 7), L);
+        const Cell<D> c = locate<D>(x + (i >> D) * D, L.scale);
+        keys[i] = corner_index(c, (int)(i & ((1 << D) - 1)), L);
     }
 }
 
@@ -1004,18 +1138,19 @@ __global__ __launch_bounds__(256) void hs_scatter_kernel(const HashGridLevels T,
 }
 
 // term of item (n, corner) of level l: coef * g[j] (header of this section), coef being Corner's
-template <int F, class E, bool SECOND, int I>
+template <int D, int F, class E, bool SECOND, int I>
 __device__ __forceinline__ void hs_term(const float *__restrict__ x, const E *__restrict__ g_y, const float *__restrict__ gg_x,
                                         const HashGridLevels &T, int l, int64_t n, int corner, float *out)
 {
     const float s = LevelRef(T, l).scale;
-    Cell c = locate(x + n * 3, s);
-    float d1[3], d2[3];
+    Cell<D> c = locate<D>(x + n * D, s);
+    float d1[D], d2[D];
     if constexpr (I == NFA_INTERP_SMOOTHSTEP) smoothstep(c, d1, d2);
     const FVec<F> g = load_piece<F>(g_y, n * T.n_levels + l);
-    const Corner k(c, corner);
+    const Corner<D> k(c, corner);
     float coef;
     if constexpr (SECOND) {
+        static_assert(D == 3, "the second order is 3-D only");
         float v[3] = {gg_x[n * 3 + 0], gg_x[n * 3 + 1], gg_x[n * 3 + 2]}, u[3];
         if constexpr (I == NFA_INTERP_SMOOTHSTEP) { v[0] = v[0] * d1[0]; v[1] = v[1] * d1[1]; v[2] = v[2] * d1[2]; }
         k.signed_v(v, u);
@@ -1027,7 +1162,7 @@ __device__ __forceinline__ void hs_term(const float *__restrict__ x, const E *__
     for (int j = 0; j < F; ++j) out[j] = coef * g.v[j];
 }
 
-template <int F, class E, bool SECOND, int I>
+template <int D, int F, class E, bool SECOND, int I>
 __global__ __launch_bounds__(256) void hs_sum_kernel(const float *__restrict__ x, const E *__restrict__ g_y,
                                                      const float *__restrict__ gg_x, const HashGridLevels T,
                                                      const HashSortArgs A, float *__restrict__ g_params)
@@ -1045,11 +1180,11 @@ __global__ __launch_bounds__(256) void hs_sum_kernel(const float *__restrict__ x
     if (tid < cnt) {
         key = keys[t0 + tid];
         const uint32_t id = ids[t0 + tid];
-        const int64_t n = (int64_t)(id >> 3);
+        const int64_t n = (int64_t)(id >> D);
         float term[F];
 #pragma unroll
         for (int j = 0; j < F; ++j) term[j] = 0.0f;
-        if (n < A.n_points) hs_term<F, E, SECOND, I>(x, g_y, gg_x, T, l, n, (int)(id & 7u), term);
+        if (n < A.n_points) hs_term<D, F, E, SECOND, I>(x, g_y, gg_x, T, l, n, (int)(id & ((1u << D) - 1u)), term);
 #pragma unroll
         for (int j = 0; j < F; ++j) sv[j * NFA_HS_TILE + tid] = term[j];
     }
@@ -1107,9 +1242,9 @@ __global__ __launch_bounds__(256) void hs_carry_kernel(const HashGridLevels T, c
 
 static int hashsort_check(const char *name, const GridArgs &G, const void *scratch, int64_t scratch_bytes)
 {
-    NFA_REQUIRE(8 * G.n_points < ((int64_t)1 << 32), "%s: 8 * n_points must be below 2^32 (got n_points %lld)", name,
-                (long long)G.n_points);
-    const HashSortPlan p = hashsort_plan(G.n_points, G.n_levels);
+    NFA_REQUIRE(G.n_points < ((int64_t)1 << (32 - G.n_dims)), "%s: %d * n_points must be below 2^32 (got n_points %lld)", name,
+                1 << G.n_dims, (long long)G.n_points);
+    const HashSortPlan p = hashsort_plan(G.n_points, G.n_levels, G.n_dims);
     NFA_REQUIRE(scratch, "%s: scratch is null (a table gradient needs nfa_hashgrid_sorted_scratch_bytes bytes)", name);
     NFA_REQUIRE(aligned16(scratch), "%s: scratch must be 16-byte aligned", name);
     NFA_REQUIRE(scratch_bytes >= p.scratch_bytes, "%s: scratch too small (%lld bytes, %lld needed)", name,
@@ -1122,7 +1257,7 @@ template <class E>
 static int hashsort_table_grad(const char *name, int32_t interp, const float *x, const E *grad_y, const float *gg_x,
                                const GridArgs &G, const HashGridLevels &T, float *grad_params, void *scratch, hipStream_t s)
 {
-    const HashSortPlan p = hashsort_plan(G.n_points, T.n_levels);
+    const HashSortPlan p = hashsort_plan(G.n_points, T.n_levels, G.n_dims);
     HashSortArgs A = {static_cast<unsigned char *>(scratch), p.level_bytes, p.items, p.n_blocks, p.n_tiles, G.n_points, 0};
     const dim3 block(256);
     for (int first = 0; first < T.n_levels; first += p.group) {
@@ -1130,19 +1265,23 @@ static int hashsort_table_grad(const char *name, int32_t interp, const float *x,
         A.first_level = first;
         int passes = 0;
         for (unsigned k = 0; k < g; ++k) passes = passes > hs_passes(T.size[first + k]) ? passes : hs_passes(T.size[first + k]);
-        hipLaunchKernelGGL(hs_keys_kernel, dim3(grid_1d(p.items, 256), g), block, 0, s, x, T, A);
+        dispatch_int<2, 3, 4>(G.n_dims, [&](auto d) {
+            hipLaunchKernelGGL(hs_keys_kernel<d()>, dim3(grid_1d(p.items, 256), g), block, 0, s, x, T, A);
+        });
         for (int pass = 0; pass < passes; ++pass) {
             hipLaunchKernelGGL(hs_count_kernel, dim3((unsigned)p.n_blocks, g), block, 0, s, T, A, pass);
             hipLaunchKernelGGL(hs_scan_kernel, dim3(256, g), block, 0, s, T, A, pass);
             hipLaunchKernelGGL(hs_scatter_kernel, dim3((unsigned)p.n_blocks, g), block, 0, s, T, A, pass);
         }
         const dim3 tiles((unsigned)p.n_tiles, g);
-        dispatch_grid(G.n_features, interp, [&](auto f, auto i) {
-            if (gg_x)
-                hipLaunchKernelGGL((hs_sum_kernel<f(), E, true, i()>), tiles, block, 0, s, x, grad_y, gg_x, T, A, grad_params);
-            else
-                hipLaunchKernelGGL((hs_sum_kernel<f(), E, false, i()>), tiles, block, 0, s, x, grad_y, gg_x, T, A, grad_params);
-        });
+        if (gg_x)
+            dispatch_grid<3>(G, interp, [&](auto d, auto f, auto i) {
+                hipLaunchKernelGGL((hs_sum_kernel<d(), f(), E, true, i()>), tiles, block, 0, s, x, grad_y, gg_x, T, A, grad_params);
+            });
+        else
+            dispatch_grid<2, 3, 4>(G, interp, [&](auto d, auto f, auto i) {
+                hipLaunchKernelGGL((hs_sum_kernel<d(), f(), E, false, i()>), tiles, block, 0, s, x, grad_y, gg_x, T, A, grad_params);
+            });
         hipLaunchKernelGGL(hs_carry_kernel, dim3((unsigned)ceil_div64(p.n_tiles * G.n_features, 256), g), block, 0, s, T, A,
                            (int)G.n_features, grad_params);
     }
@@ -1160,6 +1299,8 @@ static int hashgrid_bwd_sorted(int32_t interp, const float *x, const float *para
     if (rc != NFA_OK) return rc;
     if (G.n_points == 0) return NFA_OK;
     NFA_REQUIRE(x && grad_y && (params || !grad_x), "hashgrid_bwd_sorted: null pointer");
+    NFA_REQUIRE(G.n_dims == 3 || all_aligned16(x, grad_x),
+                "hashgrid_bwd_sorted: x and grad_x must be 16-byte aligned at n_dims %d", G.n_dims);
     NFA_REQUIRE((std::is_same<E, float>::value) || aligned16(grad_y), "hashgrid_bwd_sorted: a half grad_y must be 16-byte aligned");
     rc = hashsort_check("hashgrid_bwd_sorted", G, scratch, scratch_bytes);
     if (rc != NFA_OK) return rc;
@@ -1206,14 +1347,24 @@ using namespace nfa;
         NFA_REQUIRE(false, name ": elem must be NFA_ELEM_F32, NFA_ELEM_F16 or NFA_ELEM_BF16 (got %d)", (int)(elem)); \
     return rc
 
+int nfa_hashgrid_fwd_d(int32_t n_dims, int32_t interp, int32_t elem, const float *x, const float *params, int64_t n_points,
+                       int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                       const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, void *y,
+                       nfa_stream_t stream)
+{
+    if (check_interp("hashgrid_fwd", interp) != NFA_OK) return NFA_EINVAL;
+    const GridArgs G = {n_dims, n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host,
+                        n_params};
+    ELEM_DISPATCH("hashgrid_fwd", elem, hashgrid_fwd(interp, x, params, G, static_cast<E *>(y), stream));
+}
+
 int nfa_hashgrid_fwd_i(int32_t interp, int32_t elem, const float *x, const float *params, int64_t n_points, int32_t n_levels,
                        int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
                        const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, void *y,
                        nfa_stream_t stream)
 {
-    if (check_interp("hashgrid_fwd", interp) != NFA_OK) return NFA_EINVAL;
-    const GridArgs G = {n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params};
-    ELEM_DISPATCH("hashgrid_fwd", elem, hashgrid_fwd(interp, x, params, G, static_cast<E *>(y), stream));
+    return nfa_hashgrid_fwd_d(3, interp, elem, x, params, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                              resolutions_host, sizes_host, n_params, y, stream);
 }
 
 int nfa_hashgrid_fwd_t(int32_t elem, const float *x, const float *params, int64_t n_points, int32_t n_levels,
@@ -1233,15 +1384,25 @@ int nfa_hashgrid_fwd(const float *x, const float *params, int64_t n_points, int3
                               resolutions_host, sizes_host, n_params, y, stream);
 }
 
+int nfa_hashgrid_bwd_d(int32_t n_dims, int32_t interp, int32_t elem, const float *x, const float *params, const void *grad_y,
+                       int64_t n_points, int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size,
+                       const float *scales_host, const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params,
+                       float *grad_params, float *grad_x, nfa_stream_t stream)
+{
+    if (check_interp("hashgrid_bwd", interp) != NFA_OK) return NFA_EINVAL;
+    const GridArgs G = {n_dims, n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host,
+                        n_params};
+    ELEM_DISPATCH("hashgrid_bwd", elem,
+                  hashgrid_bwd(interp, x, params, static_cast<const E *>(grad_y), G, grad_params, grad_x, stream));
+}
+
 int nfa_hashgrid_bwd_i(int32_t interp, int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points,
                        int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
                        const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
                        float *grad_x, nfa_stream_t stream)
 {
-    if (check_interp("hashgrid_bwd", interp) != NFA_OK) return NFA_EINVAL;
-    const GridArgs G = {n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params};
-    ELEM_DISPATCH("hashgrid_bwd", elem,
-                  hashgrid_bwd(interp, x, params, static_cast<const E *>(grad_y), G, grad_params, grad_x, stream));
+    return nfa_hashgrid_bwd_d(3, interp, elem, x, params, grad_y, n_points, n_levels, n_features, log2_hashmap_size, scales_host,
+                              resolutions_host, sizes_host, n_params, grad_params, grad_x, stream);
 }
 
 int nfa_hashgrid_bwd_t(int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points,
@@ -1269,7 +1430,7 @@ int nfa_hashgrid_bwd_bwd_i(int32_t interp, int32_t elem, const float *x, const f
                            nfa_stream_t stream)
 {
     if (check_interp("hashgrid_bwd_bwd", interp) != NFA_OK) return NFA_EINVAL;
-    const GridArgs G = {n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params};
+    const GridArgs G = {3, n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params};
     ELEM_DISPATCH("hashgrid_bwd_bwd", elem, hashgrid_bwd_bwd(interp, x, params, static_cast<const E *>(grad_y), grad_grad_x, G,
                                                              static_cast<E *>(grad_grad_y), grad_params, grad_x, stream));
 }
@@ -1316,12 +1477,35 @@ int nfa_sh_bwd(const float *dirs, const float *grad_out, int64_t n_points, int32
     return nfa_sh_bwd_t(NFA_ELEM_F32, dirs, grad_out, n_points, degree, grad_dirs, stream);
 }
 
+int64_t nfa_hashgrid_sorted_scratch_bytes_d(int32_t n_dims, int64_t n_points, int32_t n_levels, int32_t log2_hashmap_size)
+{
+    (void)log2_hashmap_size;   // every level sorts all 2^D n_points items, whatever its size
+    if (n_dims < 2 || n_dims > NFA_HG_MAX_DIMS) {
+        set_error("hashgrid_sorted_scratch_bytes: n_dims must be 2, 3 or 4 (got %d)", n_dims);
+        return -1;
+    }
+    if (n_points <= 0 || n_levels < 1) return 0;
+    const HashSortPlan p = hashsort_plan(n_points, n_levels > NFA_HG_MAX_LEVELS ? NFA_HG_MAX_LEVELS : n_levels, n_dims);
+    return p.scratch_bytes;
+}
+
 int64_t nfa_hashgrid_sorted_scratch_bytes(int64_t n_points, int32_t n_levels, int32_t log2_hashmap_size)
 {
-    (void)log2_hashmap_size;   // every level sorts all 8 n_points items, whatever its size
-    if (n_points <= 0 || n_levels < 1) return 0;
-    const HashSortPlan p = hashsort_plan(n_points, n_levels > NFA_HG_MAX_LEVELS ? NFA_HG_MAX_LEVELS : n_levels);
-    return p.scratch_bytes;
+    return nfa_hashgrid_sorted_scratch_bytes_d(3, n_points, n_levels, log2_hashmap_size);
+}
+
+int nfa_hashgrid_bwd_sorted_d(int32_t n_dims, int32_t interp, int32_t elem, const float *x, const float *params,
+                              const void *grad_y, int64_t n_points, int32_t n_levels, int32_t n_features,
+                              int32_t log2_hashmap_size, const float *scales_host, const int32_t *resolutions_host,
+                              const int32_t *sizes_host, int64_t n_params, float *grad_params, float *grad_x, void *scratch,
+                              int64_t scratch_bytes, nfa_stream_t stream)
+{
+    if (check_interp("hashgrid_bwd_sorted", interp) != NFA_OK) return NFA_EINVAL;
+    const GridArgs G = {n_dims, n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host,
+                        n_params};
+    ELEM_DISPATCH("hashgrid_bwd_sorted", elem,
+                  hashgrid_bwd_sorted(interp, x, params, static_cast<const E *>(grad_y), G, grad_params, grad_x, scratch,
+                                      scratch_bytes, stream));
 }
 
 int nfa_hashgrid_bwd_sorted_i(int32_t interp, int32_t elem, const float *x, const float *params, const void *grad_y,
@@ -1330,11 +1514,9 @@ int nfa_hashgrid_bwd_sorted_i(int32_t interp, int32_t elem, const float *x, cons
                               int64_t n_params, float *grad_params, float *grad_x, void *scratch, int64_t scratch_bytes,
                               nfa_stream_t stream)
 {
-    if (check_interp("hashgrid_bwd_sorted", interp) != NFA_OK) return NFA_EINVAL;
-    const GridArgs G = {n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params};
-    ELEM_DISPATCH("hashgrid_bwd_sorted", elem,
-                  hashgrid_bwd_sorted(interp, x, params, static_cast<const E *>(grad_y), G, grad_params, grad_x, scratch,
-                                      scratch_bytes, stream));
+    return nfa_hashgrid_bwd_sorted_d(3, interp, elem, x, params, grad_y, n_points, n_levels, n_features, log2_hashmap_size,
+                                     scales_host, resolutions_host, sizes_host, n_params, grad_params, grad_x, scratch,
+                                     scratch_bytes, stream);
 }
 
 int nfa_hashgrid_bwd_sorted(int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points,
@@ -1354,7 +1536,7 @@ int nfa_hashgrid_bwd_bwd_sorted_i(int32_t interp, int32_t elem, const float *x, 
                                   float *grad_x, void *scratch, int64_t scratch_bytes, nfa_stream_t stream)
 {
     if (check_interp("hashgrid_bwd_bwd_sorted", interp) != NFA_OK) return NFA_EINVAL;
-    const GridArgs G = {n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params};
+    const GridArgs G = {3, n_points, n_levels, n_features, log2_hashmap_size, scales_host, resolutions_host, sizes_host, n_params};
     ELEM_DISPATCH("hashgrid_bwd_bwd_sorted", elem,
                   hashgrid_bwd_bwd_sorted(interp, x, params, static_cast<const E *>(grad_y), grad_grad_x, G,
                                           static_cast<E *>(grad_grad_y), grad_params, grad_x, scratch, scratch_bytes, stream));

@@ -1,7 +1,7 @@
 """Input encodings of Instant-NGP radiance fields (native kernels: csrc/encoding.hip).
 
-``HashGridEncoding`` and ``SphericalHarmonicsEncoding`` stand for tiny-cuda-nn's ``HashGrid`` (3-D input, linear or
-smoothstep interpolation) and ``SphericalHarmonics`` encodings, the two encodings nerfacc's example radiance fields
+``HashGridEncoding`` and ``SphericalHarmonicsEncoding`` stand for tiny-cuda-nn's ``HashGrid`` (2-D, 3-D or 4-D input, linear
+or smoothstep interpolation) and ``SphericalHarmonics`` encodings, the two encodings nerfacc's example radiance fields
 (``examples/radiance_fields/ngp.py``: ``NGPRadianceField``, ``NGPDensityField``) are built on; the MLPs around them are
 plain ``torch.nn`` layers.  ``encoding_from_tcnn_config`` builds them from the config dicts those examples pass to tcnn.
 Parameter layout compatibility with tcnn checkpoints is not a goal.
@@ -33,7 +33,8 @@ from . import _backend as B
 __all__ = ["HashGridEncoding", "SphericalHarmonicsEncoding", "encoding_from_tcnn_config"]
 
 _M32 = 0xFFFFFFFF
-_PRIMES = (2654435761, 805459861)   # tcnn's hash primes of dimensions 1 and 2 (dimension 0: 1)
+_PRIMES = (1, 2654435761, 805459861, 3674653429)   # tcnn's hash primes of dimensions 0..3
+GRID_DIMS = (2, 3, 4)   # input dimensions of the native hash grid
 
 _libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
 _libm.exp2f.restype = ctypes.c_float
@@ -46,12 +47,16 @@ class LevelTable:
     """Per-level constants of a hash grid, computed once on the host in float32 (the C library's exp2f / log2f):
 
         scale_l = exp2f(l * log2f(per_level_scale)) * base_resolution - 1,   res_l = ceil(scale_l) + 1,
-        size_l = min(roundup8(res_l^3), 2^log2_hashmap_size) (hashed when the dense size is larger),
+        size_l = min(roundup8(res_l^D), 2^log2_hashmap_size) (hashed when the dense size is larger), D = n_dims,
         offset_l = sum of the sizes of the levels before l.
+
+    ``scale_l`` and ``res_l`` do not depend on ``n_dims``; ``res_l^D`` is a Python int (no overflow).
     """
 
-    def __init__(self, n_levels: int, log2_hashmap_size: int, base_resolution: float, per_level_scale: float):
+    def __init__(self, n_levels: int, log2_hashmap_size: int, base_resolution: float, per_level_scale: float,
+                 n_dims: int = 3):
         f32 = np.float32
+        self.n_dims = int(n_dims)
         lg = f32(_libm.log2f(float(f32(per_level_scale))))
         self.scales, self.resolutions, self.sizes, self.offsets, self.hashed = [], [], [], [], []
         table, offset = 1 << int(log2_hashmap_size), 0
@@ -59,7 +64,7 @@ class LevelTable:
             e = f32(f32(l) * lg)
             s = f32(f32(_libm.exp2f(float(e))) * f32(base_resolution)) - f32(1.0)
             r = int(math.ceil(float(s))) + 1
-            dense = (r ** 3 + 7) // 8 * 8
+            dense = (r ** self.n_dims + 7) // 8 * 8
             self.scales.append(float(s))
             self.resolutions.append(r)
             self.sizes.append(min(dense, table))
@@ -75,9 +80,9 @@ class LevelTable:
 
 
 def _hashgrid_torch(x: Tensor, params: Tensor, t: LevelTable, n_features: int, interp: int = 0) -> Tensor:
-    """The hash grid in torch, op for op as csrc/encoding.hip computes it (x [N, 3] and params in one float dtype);
-    ``interp``: a ``B.INTERP_CODES`` value."""
-    F = n_features
+    """The hash grid in torch, op for op as csrc/encoding.hip computes it (x [N, D], D = ``t.n_dims``, and params in one
+    float dtype); ``interp``: a ``B.INTERP_CODES`` value."""
+    F, D = n_features, t.n_dims
     table = params.view(-1, F)
     outs = []
     for l in range(len(t.scales)):
@@ -90,15 +95,24 @@ def _hashgrid_torch(x: Tensor, params: Tensor, t: LevelTable, n_features: int, i
         lvl = table[t.offsets[l]: t.offsets[l] + t.sizes[l]]
         size, res = t.sizes[l], t.resolutions[l]
         acc = torch.zeros(x.shape[0], F, dtype=x.dtype, device=x.device)
-        for c in range(8):
-            b = [(c >> d) & 1 for d in range(3)]
-            q = [(g[:, d] + b[d]) & _M32 for d in range(3)]
+        for c in range(1 << D):
+            b = [(c >> d) & 1 for d in range(D)]
+            q = [(g[:, d] + b[d]) & _M32 for d in range(D)]
             if t.hashed[l]:
-                idx = (q[0] ^ ((q[1] * _PRIMES[0]) & _M32) ^ ((q[2] * _PRIMES[1]) & _M32)) & (size - 1)
+                idx = q[0]
+                for d in range(1, D):
+                    idx = idx ^ ((q[d] * _PRIMES[d]) & _M32)
+                idx = idx & (size - 1)
             else:
-                idx = ((q[0] + q[1] * res + q[2] * (res * res & _M32)) & _M32) % size
-            w = [f[:, d] if b[d] else 1.0 - f[:, d] for d in range(3)]
-            wc = (w[0] * w[1]) * w[2]
+                idx, power = q[0], res   # (sum_d q_d res^d mod 2^32: the powers wrap, every partial sum is reduced)
+                for d in range(1, D):
+                    idx = (idx + q[d] * power) & _M32
+                    power = (power * res) & _M32
+                idx = idx % size
+            w = [f[:, d] if b[d] else 1.0 - f[:, d] for d in range(D)]
+            wc = w[0]
+            for d in range(1, D):
+                wc = wc * w[d]
             acc = acc + wc[:, None] * lvl[idx]
         outs.append(acc)
     return torch.cat(outs, -1)
@@ -132,9 +146,12 @@ def _resolve_out_dtype(out_dtype, x: Tensor) -> torch.dtype:
     return out_dtype
 
 
-def _entry(name: str, dtype: torch.dtype, interp: int = 0):
+def _entry(name: str, dtype: torch.dtype, interp: int = 0, n_dims: int = 3):
     """(entry point, leading arguments): float32 calls the unsuffixed entry as ever, fp16 / bf16 the ``_t`` one, and an
-    interpolation other than Linear the ``_i`` one.  The ``_sorted`` entries always take the element code."""
+    interpolation other than Linear the ``_i`` one.  The ``_sorted`` entries always take the element code.  A hash grid of
+    2 or 4 input dimensions calls the ``_d`` entry, which takes all three codes."""
+    if n_dims != 3:
+        return name + "_d", (n_dims, interp, B.ELEM_CODES[dtype])
     if interp:
         return name + "_i", (interp, B.ELEM_CODES[dtype])
     if name.endswith("_sorted"):
@@ -149,16 +166,25 @@ def _table_args(enc: "HashGridEncoding", n_points: int, params: Tensor):
             params.numel())
 
 
-SORTED_MAX_POINTS = (1 << 29) - 1   # nfa_hashgrid_*_sorted: the item id 8 n + c is 32 bits wide
+SORTED_MAX_POINTS = (1 << 29) - 1   # nfa_hashgrid_*_sorted: the item id 8 n + c is 32 bits wide (3-D)
+
+
+def sorted_max_points(n_dims: int) -> int:
+    """The most points one ``deterministic=True`` call takes: the item id ``2^D n + c`` is 32 bits wide."""
+    return (1 << (32 - n_dims)) - 1
 
 
 def _sorted_scratch(enc: "HashGridEncoding", n_points: int, device) -> Tensor:
     """The scratch of one ``nfa_hashgrid_*_sorted`` call: a byte tensor from torch's allocator (under graph capture: the
     graph's pool), sized by the library."""
-    if n_points > SORTED_MAX_POINTS:
-        raise ValueError(f"HashGridEncoding(deterministic=True): {n_points} points in one call (at most 2^29 - 1 = "
-                         f"{SORTED_MAX_POINTS}: the sorted table gradient numbers its 8 * n_points items in 32 bits)")
-    nbytes = B.load().nfa_hashgrid_sorted_scratch_bytes(n_points, enc.n_levels, enc.table.log2_hashmap_size)
+    D = enc.n_input_dims
+    if n_points > sorted_max_points(D):
+        raise ValueError(f"HashGridEncoding(deterministic=True): {n_points} points in one call (at most 2^{32 - D} - 1 = "
+                         f"{sorted_max_points(D)}: the sorted table gradient numbers its {1 << D} * n_points items in 32 bits)")
+    if D == 3:
+        nbytes = B.load().nfa_hashgrid_sorted_scratch_bytes(n_points, enc.n_levels, enc.table.log2_hashmap_size)
+    else:
+        nbytes = B.load().nfa_hashgrid_sorted_scratch_bytes_d(D, n_points, enc.n_levels, enc.table.log2_hashmap_size)
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
@@ -176,7 +202,7 @@ class _HashGridFn(torch.autograd.Function):
         y = torch.empty(N, enc.n_levels * enc.n_features_per_level, dtype=dtype, device=x.device)
         if N:
             with torch.cuda.device(x.device):
-                entry, lead = _entry("nfa_hashgrid_fwd", dtype, enc.interp)
+                entry, lead = _entry("nfa_hashgrid_fwd", dtype, enc.interp, enc.n_input_dims)
                 B.call(entry, *lead, B.ptr(x), B.ptr(params), *_table_args(enc, N, params), B.ptr(y), B.stream())
         ctx.enc, ctx.dtype = enc, dtype
         ctx.save_for_backward(x, params)
@@ -205,10 +231,10 @@ class _HashGridBwdFn(torch.autograd.Function):
                 args = (B.ptr(x), B.ptr(params), B.ptr(g), *_table_args(enc, x.shape[0], params), B.ptr(g_p), B.ptr(g_x))
                 if enc.deterministic and need_p:
                     scratch = _sorted_scratch(enc, x.shape[0], x.device)
-                    entry, lead = _entry("nfa_hashgrid_bwd_sorted", dtype, enc.interp)
+                    entry, lead = _entry("nfa_hashgrid_bwd_sorted", dtype, enc.interp, enc.n_input_dims)
                     B.call(entry, *lead, *args, B.ptr(scratch), scratch.numel(), B.stream())
                 else:
-                    entry, lead = _entry("nfa_hashgrid_bwd", dtype, enc.interp)
+                    entry, lead = _entry("nfa_hashgrid_bwd", dtype, enc.interp, enc.n_input_dims)
                     B.call(entry, *lead, *args, B.stream())
         ctx.enc, ctx.dtype = enc, dtype
         ctx.save_for_backward(x, params, g)
@@ -218,6 +244,9 @@ class _HashGridBwdFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gg_x, gg_p):
+        if ctx.enc.n_input_dims != 3 and gg_x is not None:
+            raise NotImplementedError(f"HashGridEncoding: the second order (differentiating dL/dx again) is implemented for 3 "
+                                      f"input dimensions only (this grid has {ctx.enc.n_input_dims})")
         if gg_p is not None:
             raise NotImplementedError("HashGridEncoding: the derivative of the table gradient (dL/dparams) is not "
                                       "implemented; only dL/dx can be differentiated again")
@@ -283,8 +312,17 @@ def _autocast_off(x: Tensor):
 
 
 class HashGridEncoding(nn.Module):
-    """tiny-cuda-nn's ``HashGrid`` encoding with 3-D input and linear or smoothstep interpolation: ``forward(x[..., 3]) ->
-    [..., n_levels * n_features_per_level]``, level-major (output ``l * F + j`` is feature ``j`` of level ``l``).
+    """tiny-cuda-nn's ``HashGrid`` encoding with 2-D, 3-D or 4-D input (``n_input_dims`` = D) and linear or smoothstep
+    interpolation: ``forward(x[..., D]) -> [..., n_levels * n_features_per_level]``, level-major (output ``l * F + j`` is
+    feature ``j`` of level ``l``).
+
+    ``n_input_dims``: 2 (image-space and tri-plane / K-Planes style fields), 3, or 4 ((x, y, z, t) of a dynamic scene).  A
+    level has ``min(roundup8(res^D), 2^log2_hashmap_size)`` entries, the cell has ``2^D`` corners, and the hash uses
+    tcnn's primes of the first D dimensions (csrc/encoding.hip, "Other dimensions").  For D = 2 and 4 the forward, the
+    first-order backward (``dL/dparams`` in both modes, ``dL/dx``), both interpolations and every ``out_dtype`` are native
+    kernels; differentiating ``dL/dx`` again (``create_graph=True``) raises ``NotImplementedError`` there: the second
+    order is 3-D only (the torch path on CPU tensors is differentiated by autograd to any order).  ``deterministic=True``
+    takes at most ``2^(32 - D) - 1`` points per call.  What follows is true of every D unless it says 3-D.
 
     ``params`` is one flat float32 table of ``sum(sizes) * F`` values laid out ``[level][entry][feature]``, initialised
     uniform in +-1e-4.  ``scales``, ``resolutions``, ``offsets`` and ``sizes`` are the per-level constants
@@ -306,7 +344,7 @@ class HashGridEncoding(nn.Module):
     corner) contributions by table entry and a segmented sum in a fixed order (``nfa_hashgrid_bwd_sorted``,
     ``nfa_hashgrid_bwd_bwd_sorted``; the order is stated in csrc/encoding.hip): the same inputs give the same bits on
     every run, at the price of a scratch tensor per call (at most 512 MiB unless one level alone needs more) and at most
-    2^29 - 1 points per call (``ValueError`` above).  Every other result is the same on both settings.  The torch path
+    2^29 - 1 points per call at D = 3, ``2^(32 - D) - 1`` in general (``ValueError`` above).  Every other result is the same on both settings.  The torch path
     (CPU tensors, other dtypes) ignores the flag: its reproducibility is torch's own (``index`` backward, see
     ``torch.use_deterministic_algorithms``).
 
@@ -329,8 +367,8 @@ class HashGridEncoding(nn.Module):
             raise ValueError(f"HashGridEncoding: interpolation must be 'Linear' or 'Smoothstep' (got {interpolation!r})")
         self.interpolation = names[interpolation.lower()]
         self.interp = B.INTERP_CODES[self.interpolation]   # NFA_INTERP_*
-        if n_input_dims != 3:
-            raise ValueError(f"HashGridEncoding: only 3 input dimensions are supported (got {n_input_dims})")
+        if n_input_dims not in GRID_DIMS:
+            raise ValueError(f"HashGridEncoding: n_input_dims must be 2, 3 or 4 (got {n_input_dims})")
         if n_features_per_level not in (1, 2, 4, 8):
             raise ValueError(f"HashGridEncoding: n_features_per_level must be 1, 2, 4 or 8 (got {n_features_per_level})")
         if not 1 <= n_levels <= 32:
@@ -339,12 +377,12 @@ class HashGridEncoding(nn.Module):
             raise ValueError(f"HashGridEncoding: log2_hashmap_size must be in 10..24 (got {log2_hashmap_size})")
         if not (base_resolution >= 1 and per_level_scale >= 1):
             raise ValueError("HashGridEncoding: base_resolution and per_level_scale must be >= 1")
-        self.n_input_dims = 3
+        self.n_input_dims = int(n_input_dims)
         self.n_levels, self.n_features_per_level = int(n_levels), int(n_features_per_level)
         self.log2_hashmap_size = int(log2_hashmap_size)
         self.base_resolution, self.per_level_scale = base_resolution, float(per_level_scale)
         self.n_output_dims = self.n_levels * self.n_features_per_level
-        self.table = LevelTable(n_levels, log2_hashmap_size, base_resolution, per_level_scale)
+        self.table = LevelTable(n_levels, log2_hashmap_size, base_resolution, per_level_scale, self.n_input_dims)
         n_params = self.table.n_entries * self.n_features_per_level
         if n_params >= 1 << 31:
             raise ValueError(f"HashGridEncoding: {n_params} parameters (at most 2^31 - 1)")
@@ -356,15 +394,17 @@ class HashGridEncoding(nn.Module):
     sizes = property(lambda self: list(self.table.sizes))
 
     def forward(self, x: Tensor) -> Tensor:
-        assert x.shape[-1] == 3, "HashGridEncoding: x must have shape (..., 3)"
+        D = self.n_input_dims
+        assert x.shape[-1] == D, f"HashGridEncoding: x must have shape (..., {D})"
         out = _resolve_out_dtype(self.out_dtype, x)
         x, ctx = _autocast_off(x)
         with ctx:
             lead = x.shape[:-1]
-            x2 = x.reshape(-1, 3)
+            x2 = x.reshape(-1, D)
             p = self.params
             if x2.is_cuda and x2.dtype == torch.float32 and p.dtype == torch.float32 and p.device == x2.device:
-                y = _HashGridFn.apply(x2.contiguous(), p, self, out)
+                # (2-D and 4-D points are moved as one 8- or 16-byte vector: 16-byte aligned)
+                y = _HashGridFn.apply(x2.contiguous() if D == 3 else _aligned16(x2), p, self, out)
             else:
                 dt = torch.promote_types(x2.dtype, p.dtype)
                 y = _hashgrid_torch(x2.to(dt), p.to(dt), self.table, self.n_features_per_level, self.interp)
@@ -373,9 +413,10 @@ class HashGridEncoding(nn.Module):
             return y.view(*lead, self.n_output_dims)
 
     def extra_repr(self) -> str:
-        return (f"n_levels={self.n_levels}, n_features_per_level={self.n_features_per_level}, "
+        return ((f"n_input_dims={self.n_input_dims}, " if self.n_input_dims != 3 else "")
+                + f"n_levels={self.n_levels}, n_features_per_level={self.n_features_per_level}, "
                 f"log2_hashmap_size={self.log2_hashmap_size}, base_resolution={self.base_resolution}, "
-                f"per_level_scale={self.per_level_scale}" + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else "")
+                f"per_level_scale={self.per_level_scale}") + ((f", out_dtype={self.out_dtype}" if self.out_dtype is not None else "")
                 + (", deterministic=True" if self.deterministic else "")
                 + (f", interpolation={self.interpolation}" if self.interp else ""))
 
@@ -441,7 +482,9 @@ def encoding_from_tcnn_config(n_input_dims: int, config: dict, out_dtype=None, d
     """The encoding a tiny-cuda-nn encoding config describes: ``HashGrid`` (linear interpolation), ``SphericalHarmonics``,
     or ``Composite`` with ONE nested encoding over all input dimensions (as ``ngp.py`` builds its direction encoding).
     Anything else raises ``ValueError``.  ``out_dtype`` is handed to the encoding built, ``deterministic`` to a hash grid.
-    ``"interpolation": "Smoothstep"`` is still refused here; build it with ``HashGridEncoding(..., interpolation="Smoothstep")``."""
+    ``"interpolation": "Smoothstep"`` is still refused here; build it with ``HashGridEncoding(..., interpolation="Smoothstep")``.
+    A ``HashGrid`` of other than 3 input dimensions is refused here too (``only 3 input dimensions``); build a 2-D or 4-D grid
+    with ``HashGridEncoding(n_input_dims=2 or 4, ...)``."""
     if not isinstance(config, dict) or "otype" not in config:
         raise ValueError(f"not a tcnn encoding config: {config!r}")
     otype = config["otype"]
@@ -449,6 +492,9 @@ def encoding_from_tcnn_config(n_input_dims: int, config: dict, out_dtype=None, d
         interp = config.get("interpolation", "Linear")
         if interp != "Linear":
             raise ValueError(f"HashGrid: only linear interpolation is supported (got {interp!r})")
+        if n_input_dims != 3:
+            raise ValueError(f"HashGrid: only 3 input dimensions are supported here (got {n_input_dims}); "
+                             f"HashGridEncoding(n_input_dims=...) takes 2, 3 or 4")
         return HashGridEncoding(n_input_dims, n_levels=int(config.get("n_levels", 16)),
                                 n_features_per_level=int(config.get("n_features_per_level", 2)),
                                 log2_hashmap_size=int(config.get("log2_hashmap_size", 19)),
