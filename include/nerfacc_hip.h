@@ -821,6 +821,32 @@ int nfa_sh_fwd_t(int32_t elem, const float *dirs, int64_t n_points, int32_t degr
 int nfa_sh_bwd_t(int32_t elem, const float *dirs, const void *grad_out, int64_t n_points, int32_t degree,
                  float *grad_dirs, nfa_stream_t stream);
 
+/* The plane-factorised multiscale encoding of K-Planes (Fridovich-Keil et al. 2023; `interpolate_ms_features` with
+ * concat_features = True) for n_dims = 3 (3 planes) or 4 (6 planes, axis 3 is time), x [n_points, n_dims] in [0, 1]
+ * (K-Planes' u in [-1, 1] is x = (u + 1) / 2).  The planes of a scale are the axis pairs (a, b), a < b, in lexicographic
+ * order.  res_host: n_scales * n_dims host ints read during the call, res_host[s * n_dims + d] = R_{s,d} >= 2, the nodes
+ * of scale s along axis d.  params: one float32 table; plane (s, k) is a row-major [R_{s,b}, R_{s,a}, n_features] block,
+ * the blocks in scale-major, then plane order without gaps (fewer than 2^31 floats in all).  A plane is sampled
+ * bilinearly with the border rule of grid_sample(padding_mode="border", align_corners=True): node coordinate x_d (R - 1)
+ * clamped to [0, R - 1] (NaN to 0), so every input reads and writes inside its planes.  The planes' samples of a scale are
+ * multiplied (reduce = NFA_PLANE_PRODUCT) or added (NFA_PLANE_SUM) in plane order; y [n_points, n_scales * n_features],
+ * scale-major, as elements of type `elem` (NFA_ELEM_*; float32 arithmetic, rounded once).  n_features: 4, 8, 16 or 32;
+ * n_scales: 1..8.  Every operation is written out in csrc/planes.hip's header.
+ * nfa_planegrid_bwd: grad_y [n_points, n_scales * n_features] in `elem`; grad_params (the table's size, float32, zeroed
+ * by the caller; float atomics, so its last bits depend on the arrival order) and grad_x [n_points, n_dims] (no atomics:
+ * bitwise reproducible; 0 on an axis whose coordinate is outside [0, 1] or not finite) are each optional, at least one.
+ * The samples are recomputed from x and params.  No pointer needs more than its element's alignment.
+ * n_points == 0 returns NFA_OK before anything else is looked at.  Otherwise the arguments are checked in this order, each
+ * with its own message, before any launch: n_points, n_dims, reduce, elem, n_features, n_scales, res_host (null; a
+ * resolution below 2; the size limit), null pointers. */
+#define NFA_PLANE_PRODUCT 0
+#define NFA_PLANE_SUM 1
+int nfa_planegrid_fwd(int32_t n_dims, int32_t reduce, int32_t elem, const float *x, const float *params, int64_t n_points,
+                      int32_t n_scales, int32_t n_features, const int32_t *res_host, void *y, nfa_stream_t stream);
+int nfa_planegrid_bwd(int32_t n_dims, int32_t reduce, int32_t elem, const float *x, const float *params, const void *grad_y,
+                      int64_t n_points, int32_t n_scales, int32_t n_features, const int32_t *res_host, float *grad_params,
+                      float *grad_x, nfa_stream_t stream);
+
 /* ------------------------------------------------------------------ sample positions */
 
 /* What every field does between sampling() and its encodings, in one pass over the samples.  Replaces the torch

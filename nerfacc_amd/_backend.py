@@ -144,6 +144,8 @@ _SIGS = {
     "nfa_hashgrid_sorted_scratch_bytes_d": [_i32, _i64, _i32, _i32],
     "nfa_sh_fwd_t": [_i32, _vp, _i64, _i32, _vp, _vp],
     "nfa_sh_bwd_t": [_i32, _vp, _vp, _i64, _i32, _vp, _vp],
+    "nfa_planegrid_fwd": [_i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, C.POINTER(_i32), _vp, _vp],
+    "nfa_planegrid_bwd": [_i32, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(_i32), _vp, _vp, _vp],
     "nfa_sample_positions_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
     "nfa_sample_positions_bwd": [_vp] * 9 + [_i64, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "nfa_generate_rays_fwd": [_vp, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _f32, _i32,
@@ -200,6 +202,8 @@ ABI_VERSION = 403   # include/nerfacc_hip.h: NFA_VERSION
 ELEM_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 # include/nerfacc_hip.h: NFA_INTERP_*, the hash grid's interpolation (the leading argument of the `_i` entries)
 INTERP_CODES = {"Linear": 0, "Smoothstep": 1}
+# include/nerfacc_hip.h: NFA_PLANE_*, how the plane grid combines the planes of a scale
+PLANE_REDUCE_CODES = {"product": 0, "sum": 1}
 
 
 def set_tuning(name: str, value: Optional[str]) -> None:

@@ -6,6 +6,9 @@ or smoothstep interpolation) and ``SphericalHarmonics`` encodings, the two encod
 plain ``torch.nn`` layers.  ``encoding_from_tcnn_config`` builds them from the config dicts those examples pass to tcnn.
 Parameter layout compatibility with tcnn checkpoints is not a goal.
 
+``PlaneGridEncoding`` is the plane-factorised multiscale encoding of K-Planes (3-D: tri-planes, 4-D: the six planes of a
+dynamic scene) as one native pass each way (csrc/planes.hip); it shares ``out_dtype`` and the device rules below.
+
 CUDA float32 tensors run on libnerfacc_hip.so; CPU tensors and other dtypes run the same formulas in torch (the hash grid's
 torch path reproduces the native forward bit for bit).  Under ``torch.autocast`` both encodings run in float32, as tcnn's
 do.  Neither direction reads from the device, so a step that uses them can be captured (``CapturedStep``).
@@ -21,6 +24,7 @@ from __future__ import annotations
 
 import ctypes
 import ctypes.util
+import itertools
 import math
 
 import numpy as np
@@ -30,7 +34,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _backend as B
 
-__all__ = ["HashGridEncoding", "SphericalHarmonicsEncoding", "encoding_from_tcnn_config"]
+__all__ = ["HashGridEncoding", "SphericalHarmonicsEncoding", "PlaneGridEncoding", "encoding_from_tcnn_config"]
 
 _M32 = 0xFFFFFFFF
 _PRIMES = (1, 2654435761, 805459861, 3674653429)   # tcnn's hash primes of dimensions 0..3
@@ -476,6 +480,204 @@ class SphericalHarmonicsEncoding(nn.Module):
 
     def extra_repr(self) -> str:
         return f"degree={self.degree}" + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else "")
+
+
+PLANE_DIMS = (3, 4)   # input dimensions of the native plane grid
+
+
+class PlaneTable:
+    """The planes of a plane grid, computed once on the host: ``planes`` (the axis pairs ``(a, b)``, ``a < b``, in
+    ``itertools.combinations`` order), ``res[s][d] = R_d * m_s`` for the spatial axes ``d < 3`` and ``R_3`` for the time
+    axis, and, per scale ``s`` and plane ``k``, ``offsets[s][k]`` / ``sizes[s][k]`` in floats: plane ``(s, k)`` is the
+    row-major ``[R_b, R_a, F]`` block at ``offsets[s][k]``, the blocks in scale-major, then plane order without gaps."""
+
+    def __init__(self, n_dims: int, resolution, multiscale_res, n_features: int):
+        D = self.n_dims = int(n_dims)
+        self.n_features = int(n_features)
+        self.planes = list(itertools.combinations(range(D), 2))
+        self.res = [[int(resolution[d]) * int(m) if d < 3 else int(resolution[d]) for d in range(D)] for m in multiscale_res]
+        self.offsets, self.sizes, offset = [], [], 0
+        for r in self.res:
+            self.sizes.append([r[a] * r[b] * self.n_features for a, b in self.planes])
+            self.offsets.append([offset + sum(self.sizes[-1][:k]) for k in range(len(self.planes))])
+            offset += sum(self.sizes[-1])
+        self.n_params = offset
+        # host array handed to nfa_planegrid_{fwd,bwd} (read synchronously by each call)
+        flat = [min(v, (1 << 31) - 1) for r in self.res for v in r]
+        self.c_res = (ctypes.c_int32 * len(flat))(*flat)
+
+
+def _planegrid_torch(x: Tensor, params: Tensor, t: PlaneTable, reduce: int = 0) -> Tensor:
+    """The plane grid in torch, op for op as csrc/planes.hip computes it (x [N, D], D = ``t.n_dims``, and params in one
+    float dtype); ``reduce``: a ``B.PLANE_REDUCE_CODES`` value."""
+    F, D = t.n_features, t.n_dims
+    outs = []
+    for s, res in enumerate(t.res):
+        cell = []
+        for d in range(D):
+            rm1 = float(res[d] - 1)
+            p = x[:, d] * rm1
+            q = torch.where(p >= 0, p, torch.zeros_like(p))        # (NaN gives 0: `where`, not `maximum`)
+            q = torch.where(q <= rm1, q, torch.full_like(q, rm1))
+            i = torch.floor(q.detach()).to(torch.int64).clamp(max=res[d] - 2)
+            cell.append((i, q - i.to(q.dtype)))
+        out = None
+        for k, (a, b) in enumerate(t.planes):
+            plane = params[t.offsets[s][k]: t.offsets[s][k] + t.sizes[s][k]].view(-1, F)
+            (ia, fa), (ib, fb) = cell[a], cell[b]
+            row = ib * res[a] + ia
+            v = torch.zeros(x.shape[0], F, dtype=x.dtype, device=x.device)
+            for c in range(4):
+                ca, cb = c & 1, c >> 1
+                w = (fa if ca else 1.0 - fa) * (fb if cb else 1.0 - fb)
+                v = v + w[:, None] * plane[row + (cb * res[a] + ca)]
+            out = v if out is None else (out + v if reduce else out * v)
+        outs.append(out)
+    return torch.cat(outs, -1)
+
+
+class _PlaneGridFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, params, enc: "PlaneGridEncoding", dtype: torch.dtype):
+        B.require_device(x, params)
+        N = x.shape[0]
+        y = torch.empty(N, enc.n_output_dims, dtype=dtype, device=x.device)
+        if N:
+            with torch.cuda.device(x.device):
+                B.call("nfa_planegrid_fwd", *enc._lead(dtype), B.ptr(x), B.ptr(params), *enc._table_args(N), B.ptr(y), B.stream())
+        ctx.enc, ctx.dtype = enc, dtype
+        ctx.save_for_backward(x, params)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        need_x, need_p = ctx.needs_input_grad[:2]
+        if g_y is None or not (need_x or need_p):
+            return None, None, None, None
+        x, params = ctx.saved_tensors
+        g_x, g_p = _PlaneGridBwdFn.apply(x, params, _grad_as(g_y, ctx.dtype), ctx.enc, ctx.dtype, need_x, need_p)
+        return g_x, g_p, None, None
+
+
+class _PlaneGridBwdFn(torch.autograd.Function):
+    """The plane grid's backward as a function ``(x, params, g_y) -> (g_x, g_params)`` of its own, so that differentiating
+    it again (``create_graph=True``) fails with a message that names the encoding instead of a missing ``grad_fn``."""
+
+    @staticmethod
+    def forward(ctx, x, params, g, enc: "PlaneGridEncoding", dtype: torch.dtype, need_x: bool, need_p: bool):
+        g_p = torch.zeros_like(params) if need_p else None
+        g_x = torch.empty_like(x) if need_x else None
+        if x.shape[0]:
+            with torch.cuda.device(x.device):
+                B.call("nfa_planegrid_bwd", *enc._lead(dtype), B.ptr(x), B.ptr(params), B.ptr(g),
+                       *enc._table_args(x.shape[0]), B.ptr(g_p), B.ptr(g_x), B.stream())
+        ctx.set_materialize_grads(False)
+        return g_x, g_p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gg_x, gg_p):
+        raise NotImplementedError("PlaneGridEncoding: the second order (differentiating dL/dx or dL/dparams again) is not "
+                                  "implemented on the native path; the torch path on CPU tensors is differentiated by autograd")
+
+
+class PlaneGridEncoding(nn.Module):
+    """The plane-factorised multiscale encoding of K-Planes (Fridovich-Keil et al. 2023): its ``interpolate_ms_features``
+    with ``concat_features=True`` as one native pass each way (csrc/planes.hip).  ``forward(x[..., D]) -> [..., S * F]`` for
+    ``x`` in [0, 1]^D (K-Planes' ``u`` in [-1, 1] is ``x = (u + 1) / 2``), scale ``s`` at columns ``s F .. s F + F - 1``.
+
+    ``n_input_dims`` D: 3 (a static scene: 3 planes per scale) or 4 ((x, y, z, t): 6 planes).  The planes are the axis
+    pairs ``(a, b)``, ``a < b``, in ``itertools.combinations(range(D), 2)`` order.  ``resolution`` ``(R_0, .., R_{D-1})``
+    and ``multiscale_res`` ``(m_0, .., m_{S-1})`` (S in 1..8): scale ``s`` has ``R_d m_s`` nodes along a spatial axis and
+    ``R_3`` along the time axis, every one at least 2.  ``n_features`` F: 4, 8, 16 or 32 per plane.
+
+    ``params`` is one flat float32 table (fewer than 2^31 values): plane ``(s, k)`` is the row-major ``[R_b, R_a, F]`` block
+    at ``offsets[s][k]``, scale-major, then plane order; ``plane(s, k)`` is that view and ``plane(s, k).permute(2, 0, 1)[None]``
+    the ``[1, F, H, W]`` tensor K-Planes hands to ``grid_sample``.  A plane is sampled as ``F.grid_sample(mode="bilinear",
+    padding_mode="border", align_corners=True)`` samples it; ``reduce`` is ``"product"`` (K-Planes) or ``"sum"``
+    (EG3D-style tri-planes) over the planes of a scale.  Initialised as K-Planes: uniform in ``init = (0.1, 0.5)``, planes
+    that contain the time axis ones when ``reduce="product"``.
+
+    Every input is legal: a coordinate outside [0, 1] samples the border, NaN samples node 0, and ``dL/dx`` is zero on such
+    an axis.  Differentiable once w.r.t. ``params`` (float atomics: the last bits change from run to run) and ``x`` (bitwise
+    reproducible); the torch path (CPU tensors, other dtypes) is differentiated by autograd.  On a grid node the native
+    ``dL/dx`` is the derivative towards the upper cell (the lower one at x = 1).  ``out_dtype`` as for
+    :class:`HashGridEncoding`."""
+
+    def __init__(self, n_input_dims: int, resolution, multiscale_res=(1,), n_features: int = 32, reduce: str = "product",
+                 init=(0.1, 0.5), out_dtype=None):
+        super().__init__()
+        self.out_dtype = _check_out_dtype(out_dtype)
+        if n_input_dims not in PLANE_DIMS:
+            raise ValueError(f"PlaneGridEncoding: n_input_dims must be 3 or 4 (got {n_input_dims})")
+        if n_features not in (4, 8, 16, 32):
+            raise ValueError(f"PlaneGridEncoding: n_features must be 4, 8, 16 or 32 (got {n_features})")
+        if reduce not in B.PLANE_REDUCE_CODES:
+            raise ValueError(f"PlaneGridEncoding: reduce must be 'product' or 'sum' (got {reduce!r})")
+        resolution, multiscale_res = tuple(int(r) for r in resolution), tuple(int(m) for m in multiscale_res)
+        if len(resolution) != n_input_dims:
+            raise ValueError(f"PlaneGridEncoding: resolution must have {n_input_dims} entries (got {len(resolution)})")
+        if not 1 <= len(multiscale_res) <= 8:
+            raise ValueError(f"PlaneGridEncoding: multiscale_res must have 1..8 entries (got {len(multiscale_res)})")
+        self.n_input_dims, self.n_features, self.reduce = int(n_input_dims), int(n_features), reduce
+        self.resolution, self.multiscale_res = resolution, multiscale_res
+        self.table = PlaneTable(n_input_dims, resolution, multiscale_res, n_features)
+        for s, r in enumerate(self.table.res):
+            if min(r) < 2:
+                raise ValueError(f"PlaneGridEncoding: every resolution must be at least 2 (scale {s} has {tuple(r)})")
+        if self.table.n_params >= 1 << 31:
+            raise ValueError(f"PlaneGridEncoding: {self.table.n_params} parameters (at most 2^31 - 1)")
+        self.n_scales = len(multiscale_res)
+        self.n_output_dims = self.n_scales * self.n_features
+        self.init = (float(init[0]), float(init[1]))
+        self.params = nn.Parameter(torch.empty(self.table.n_params, dtype=torch.float32).uniform_(*self.init))
+        if reduce == "product":
+            with torch.no_grad():
+                for s in range(self.n_scales):
+                    for k, (a, b) in enumerate(self.table.planes):
+                        if b == 3:
+                            self.plane(s, k).fill_(1.0)
+
+    planes = property(lambda self: list(self.table.planes))
+    resolutions = property(lambda self: [list(r) for r in self.table.res])
+    offsets = property(lambda self: [list(o) for o in self.table.offsets])
+    sizes = property(lambda self: [list(z) for z in self.table.sizes])
+
+    def plane(self, s: int, k: int) -> Tensor:
+        """Plane ``k`` of scale ``s`` as a ``[R_b, R_a, F]`` view of ``params``."""
+        t = self.table
+        a, b = t.planes[k]
+        return self.params[t.offsets[s][k]: t.offsets[s][k] + t.sizes[s][k]].view(t.res[s][b], t.res[s][a], self.n_features)
+
+    def _lead(self, dtype: torch.dtype):
+        return self.n_input_dims, B.PLANE_REDUCE_CODES[self.reduce], B.ELEM_CODES[dtype]
+
+    def _table_args(self, n_points: int):
+        return n_points, self.n_scales, self.n_features, self.table.c_res
+
+    def forward(self, x: Tensor) -> Tensor:
+        D = self.n_input_dims
+        assert x.shape[-1] == D, f"PlaneGridEncoding: x must have shape (..., {D})"
+        out = _resolve_out_dtype(self.out_dtype, x)
+        x, ctx = _autocast_off(x)
+        with ctx:
+            lead = x.shape[:-1]
+            x2 = x.reshape(-1, D)
+            p = self.params
+            if x2.is_cuda and x2.dtype == torch.float32 and p.dtype == torch.float32 and p.device == x2.device:
+                y = _PlaneGridFn.apply(x2.contiguous(), p, self, out)   # (element-wise access: no alignment beyond 4 bytes)
+            else:
+                dt = torch.promote_types(x2.dtype, p.dtype)
+                y = _planegrid_torch(x2.to(dt), p.to(dt), self.table, B.PLANE_REDUCE_CODES[self.reduce])
+                if self.out_dtype is not None:
+                    y = y.to(out)
+            return y.view(*lead, self.n_output_dims)
+
+    def extra_repr(self) -> str:
+        return (f"n_input_dims={self.n_input_dims}, resolution={self.resolution}, multiscale_res={self.multiscale_res}, "
+                f"n_features={self.n_features}, reduce={self.reduce!r}"
+                + (f", init={self.init}" if self.init != (0.1, 0.5) else "")
+                + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else ""))
 
 
 def encoding_from_tcnn_config(n_input_dims: int, config: dict, out_dtype=None, deterministic: bool = False) -> nn.Module:
