@@ -847,6 +847,31 @@ int nfa_planegrid_bwd(int32_t n_dims, int32_t reduce, int32_t elem, const float 
                       int64_t n_points, int32_t n_scales, int32_t n_features, const int32_t *res_host, float *grad_params,
                       float *grad_x, nfa_stream_t stream);
 
+/* The regularisers K-Planes puts on the plane tables themselves, over the plane grid above (same n_dims, n_scales,
+ * n_features, res_host and params layout).  Plane (s, k) seen as p[j, i, f], j < H = R_{s,b} rows, i < W = R_{s,a}, f < F:
+ *   tv_h   = sum (p[j+1,i,f] - p[j,i,f])^2 / (F (H-1) W)          tv_w = sum (p[j,i+1,f] - p[j,i,f])^2 / (F H (W-1))
+ *   smooth = sum ((p[j+2,i,f] - p[j+1,i,f]) - (p[j+1,i,f] - p[j,i,f]))^2 / (F (H-2) W)      (0 when H = 2)
+ *   l1     = sum |1 - p[j,i,f]| / (F H W)
+ * smooth and l1 exist on the time planes only (b == 3: planes 2, 4, 5 at n_dims = 4, the rows are the time axis); on a
+ * spatial plane they are 0 and their incoming gradients are not looked at.
+ * nfa_planereg_fwd: terms [n_scales, n_planes, 4] = (tv_h, tv_w, smooth, l1) per plane, two launches (per-tile sums into
+ * partials, then one workgroup per plane), no atomics: the same bits on every run; the order of the sums is in
+ * csrc/planereg.hip's header.  partials: device scratch of n_partials >= nfa_planereg_partials(n_dims, n_scales,
+ * n_features, res_host) rows of 4 floats, contents irrelevant before and after.  nfa_planereg_partials is host-only
+ * arithmetic on the shape (-1 with a message for a shape the passes refuse).
+ * nfa_planereg_bwd: grad_terms [n_scales, n_planes, 4], a DEVICE pointer; grad_params (the table's size) receives
+ * sum_t grad_terms[s, k, t] d terms[s, k, t] / d params in one launch with plain stores: every element is written (the
+ * caller need not zero it) and the result is bitwise reproducible.  d |1 - p| / dp is 0 at p == 1.  NaN and Inf
+ * parameters propagate; no index depends on data and nothing is read back from the device.
+ * params, partials, terms and grad_params must be 16-byte aligned (every plane starts on a 16-byte piece of params).
+ * The arguments are checked in this order, each with its own message, before any launch: n_dims, n_features, n_scales,
+ * res_host (null; a resolution below 2; the size limit), null pointers, alignment, n_partials. */
+int64_t nfa_planereg_partials(int32_t n_dims, int32_t n_scales, int32_t n_features, const int32_t *res_host);
+int nfa_planereg_fwd(int32_t n_dims, const float *params, int32_t n_scales, int32_t n_features, const int32_t *res_host,
+                     float *partials, int64_t n_partials, float *terms, nfa_stream_t stream);
+int nfa_planereg_bwd(int32_t n_dims, const float *params, int32_t n_scales, int32_t n_features, const int32_t *res_host,
+                     const float *grad_terms, float *grad_params, nfa_stream_t stream);
+
 /* ------------------------------------------------------------------ sample positions */
 
 /* What every field does between sampling() and its encodings, in one pass over the samples.  Replaces the torch

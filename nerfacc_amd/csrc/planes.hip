@@ -44,22 +44,9 @@
 // Element types: y / dL/dy are float, fp16 or bf16 (NFA_ELEM_*): float32 arithmetic, one rounding as the value is stored,
 // one lane per element.  x needs no alignment beyond its 4 bytes.
 #include "common.hip.h"
+#include "plane_layout.h"   // PlaneGridDesc, plane_a / plane_b, plane_layout (shared with planereg.hip)
 
 namespace nfa {
-
-#define NFA_PG_MAX_SCALES 8
-#define NFA_PG_MAX_PLANES 6
-
-struct PlaneGridDesc {
-    int32_t res[NFA_PG_MAX_SCALES][4];                      // R_{s,d}
-    uint32_t offset[NFA_PG_MAX_SCALES][NFA_PG_MAX_PLANES];  // first float of plane (s, k)
-    int32_t n_scales;
-};
-
-template <int D> __host__ __device__ constexpr int n_planes() { return D * (D - 1) / 2; }
-// the axes (a, b) of plane k
-template <int D> __host__ __device__ constexpr int plane_a(int k) { return D == 3 ? (k < 2 ? 0 : 1) : (k < 3 ? 0 : k < 5 ? 1 : 2); }
-template <int D> __host__ __device__ constexpr int plane_b(int k) { return D == 3 ? (k == 0 ? 1 : 2) : (k < 3 ? k + 1 : k < 5 ? k - 1 : 3); }
 
 struct Axis {
     uint32_t i;   // the lower node, in [0, R - 2]
@@ -246,29 +233,7 @@ static int planegrid_desc(const char *name, const PlaneGridArgs &A, PlaneGridDes
     NFA_REQUIRE(A.n_features == 4 || A.n_features == 8 || A.n_features == 16 || A.n_features == 32,
                 "%s: n_features must be 4, 8, 16 or 32 (got %d)", name, A.n_features);
     NFA_REQUIRE(A.n_scales >= 1 && A.n_scales <= NFA_PG_MAX_SCALES, "%s: n_scales must be in 1..8 (got %d)", name, A.n_scales);
-    NFA_REQUIRE(A.res_host != nullptr, "%s: null resolution table", name);
-    P = {};
-    const int D = A.n_dims;
-    const int64_t limit = (int64_t)1 << 31;
-    int64_t total = 0;
-    for (int s = 0; s < A.n_scales; ++s) {
-        for (int d = 0; d < D; ++d) {
-            const int32_t r = A.res_host[s * D + d];
-            NFA_REQUIRE(r >= 2, "%s: scale %d axis %d resolution %d is below 2", name, s, d, r);
-            P.res[s][d] = r;
-        }
-        int k = 0;
-        for (int a = 0; a < D; ++a)
-            for (int b = a + 1; b < D; ++b, ++k) {
-                const int64_t cells = (int64_t)P.res[s][a] * P.res[s][b];   // (< 2^62)
-                NFA_REQUIRE(cells < limit && total + cells * A.n_features < limit,
-                            "%s: too many parameters (at most 2^31 - 1 floats)", name);
-                P.offset[s][k] = (uint32_t)total;
-                total += cells * A.n_features;
-            }
-    }
-    P.n_scales = A.n_scales;
-    return NFA_OK;
+    return plane_layout(name, A.n_dims, A.n_features, A.n_scales, A.res_host, P);
 }
 
 template <int... V, class Fn>

@@ -1,7 +1,12 @@
-"""Regularisers over packed samples (native kernels: csrc/segscan.hip, ``DistortionFwdOp`` / ``DistortionBwdOp``).
+"""Regularisers over packed samples (native kernels: csrc/segscan.hip, ``DistortionFwdOp`` / ``DistortionBwdOp``) and over
+the tables of a plane grid (csrc/planereg.hip).
 
 ``distortion`` is the Mip-NeRF 360 distortion loss (Barron et al. 2022, eq. 15), the other half of the proposal-sampling
 recipe ``PropNetEstimator`` implements.  Earlier nerfacc releases shipped a packed version; 0.5 dropped it.
+
+``plane_terms`` / ``plane_regularization`` are the regularisers K-Planes (Fridovich-Keil et al. 2023) adds to every step, over
+the planes of a :class:`~nerfacc_amd.encodings.PlaneGridEncoding`: total variation in space, the second difference along
+time and the L1 pull of the space-time planes towards 1, as one native pass each way.
 
 Not part of ``nerfacc_amd.__all__`` (that list mirrors the reference's exactly); import the module.
 """
@@ -16,8 +21,9 @@ from torch.autograd.function import once_differentiable
 
 from . import _backend as B
 from ._segments import SegInfo, batched_native, resolve
+from .encodings import _aligned16
 
-__all__ = ["distortion"]
+__all__ = ["distortion", "plane_terms", "plane_regularization"]
 
 
 class _Distortion(torch.autograd.Function):
@@ -153,3 +159,165 @@ def distortion(
         ids, idx = torch.sort(ray_indices.to(torch.int64), stable=True)
         R = n_rays
     return _distortion_torch(weights[idx], t_starts[idx], t_ends[idx], ids, R)
+
+
+# ----------------------------------------------------------------------------- plane regularisers (csrc/planereg.hip)
+def _plane_shapes(table):
+    """(offset, size, H, W, is_time) of every plane of a ``PlaneTable``, in table order."""
+    return [(table.offsets[s][k], table.sizes[s][k], res[b], res[a], b == 3)
+            for s, res in enumerate(table.res) for k, (a, b) in enumerate(table.planes)]
+
+
+def _plane_counts(H: int, W: int, F: int, time: bool):
+    """The number of summands of (tv_h, tv_w, smooth, l1) on an ``[H, W, F]`` plane; 0: the term does not exist."""
+    return (F * (H - 1) * W, F * H * (W - 1), F * (H - 2) * W if time else 0, F * H * W if time else 0)
+
+
+def _plane_terms_torch(params: Tensor, table) -> Tensor:
+    """The four terms per plane by slicing, in ``params``' dtype; differentiated by autograd."""
+    F, rows = table.n_features, []
+    for off, size, H, W, time in _plane_shapes(table):
+        p = params[off: off + size].view(H, W, F)
+        n_h, n_w, n_s, n_l = _plane_counts(H, W, F, time)
+        dh = p[1:] - p[:-1]
+        dw = p[:, 1:] - p[:, :-1]
+        zero = params.new_zeros(())
+        smooth = ((dh[1:] - dh[:-1]) ** 2).sum() / n_s if n_s else zero
+        l1 = (1.0 - p).abs().sum() / n_l if n_l else zero
+        rows.append(torch.stack([(dh ** 2).sum() / n_h, (dw ** 2).sum() / n_w, smooth, l1]))
+    return torch.stack(rows).view(len(table.res), len(table.planes), 4)
+
+
+def _plane_terms_grad_torch(params: Tensor, grad_terms: Tensor, table) -> Tensor:
+    """``d (grad_terms . terms) / d params`` in float32, operation for operation as ``nfa_planereg_bwd`` forms it (the
+    stencils and their order: csrc/planereg.hip's header), so the two agree bit for bit."""
+    F = table.n_features
+    p32, g32 = params.detach().to(torch.float32), grad_terms.detach().to(torch.float32).reshape(-1, 4)
+    out = torch.empty_like(p32)
+    for n, (off, size, H, W, time) in enumerate(_plane_shapes(table)):
+        p = p32[off: off + size].view(H, W, F)
+        inv = torch.tensor([1.0 / c if c else 0.0 for c in _plane_counts(H, W, F, time)], dtype=torch.float32, device=p.device)
+        c = g32[n] * inv
+        zr, zc = p.new_zeros(1, W, F), p.new_zeros(H, 1, F)
+        dh = p[1:] - p[:-1]
+        gh = torch.cat([zr, dh]) - torch.cat([dh, zr])
+        dw = p[:, 1:] - p[:, :-1]
+        gw = torch.cat([zc, dw], 1) - torch.cat([dw, zc], 1)
+        g = (2.0 * c[0]) * gh + (2.0 * c[1]) * gw
+        if time:
+            d2 = dh[1:] - dh[:-1]
+            gs = (torch.cat([zr, zr, d2]) - 2.0 * torch.cat([zr, d2, zr])) + torch.cat([d2, zr, zr])
+            d = p - 1.0
+            sg = torch.where(d > 0, torch.ones_like(d), torch.where(d < 0, -torch.ones_like(d), d))
+            g = (g + (2.0 * c[2]) * gs) + c[3] * sg
+        out[off: off + size] = g.reshape(-1)
+    return out
+
+
+def _planereg_args(enc):
+    return enc.n_scales, enc.n_features, enc.table.c_res
+
+
+class _PlaneTermsFn(torch.autograd.Function):
+    """``terms`` in two launches (``nfa_planereg_fwd``); the table gradient through :class:`_PlaneTermsBwdFn`."""
+
+    @staticmethod
+    def forward(ctx, params, enc):
+        dev = B.require_device(params)
+        p = _aligned16(params)
+        n_partials = B.load().nfa_planereg_partials(enc.n_input_dims, *_planereg_args(enc))   # (host arithmetic on the shape)
+        partials = torch.empty(n_partials, 4, dtype=torch.float32, device=dev)
+        terms = torch.empty(enc.n_scales, len(enc.table.planes), 4, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            B.call("nfa_planereg_fwd", enc.n_input_dims, B.ptr(p), *_planereg_args(enc), B.ptr(partials), n_partials,
+                   B.ptr(terms), B.stream())
+        ctx.enc = enc
+        ctx.save_for_backward(p)
+        return terms
+
+    @staticmethod
+    def backward(ctx, g_terms):
+        if g_terms is None or not ctx.needs_input_grad[0]:
+            return None, None
+        (p,) = ctx.saved_tensors
+        return _PlaneTermsBwdFn.apply(p, g_terms.to(torch.float32).contiguous(), ctx.enc), None
+
+
+class _PlaneTermsBwdFn(torch.autograd.Function):
+    """The backward as a function ``(params, g_terms) -> g_params`` of its own, so that differentiating it again fails with
+    a message that names ``plane_terms`` instead of a missing ``grad_fn`` (as ``_PlaneGridBwdFn`` does)."""
+
+    @staticmethod
+    def forward(ctx, p, g, enc):
+        g_p = torch.empty_like(p)   # (every element is written)
+        with torch.cuda.device(p.device):
+            B.call("nfa_planereg_bwd", enc.n_input_dims, B.ptr(p), *_planereg_args(enc), B.ptr(g), B.ptr(g_p), B.stream())
+        return g_p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gg_p):
+        raise NotImplementedError("plane_terms: the second order (differentiating dL/dparams again) is not implemented on the "
+                                  "native path; the torch path on CPU tensors is differentiated by autograd")
+
+
+def plane_terms(enc) -> Tensor:
+    """The four regularisation terms of every plane of a :class:`~nerfacc_amd.encodings.PlaneGridEncoding`:
+    ``[n_scales, n_planes, 4]`` float32 on ``enc.params``' device, ``(tv_h, tv_w, smooth, l1)`` per plane.  With plane
+    ``(s, k)`` seen as ``p[j, i, f]`` (``enc.plane(s, k)``: ``j < H`` rows, ``i < W``, ``f < F``), each a mean:
+
+        tv_h   = sum (p[j+1,i,f] - p[j,i,f])^2 / (F (H-1) W)
+        tv_w   = sum (p[j,i+1,f] - p[j,i,f])^2 / (F H (W-1))
+        smooth = sum ((p[j+2,i,f] - p[j+1,i,f]) - (p[j+1,i,f] - p[j,i,f]))^2 / (F (H-2) W)
+        l1     = sum |1 - p[j,i,f]| / (F H W)
+
+    ``smooth`` and ``l1`` exist on the time planes only (those whose rows are the time axis: ``k`` = 2, 4, 5 at D = 4); on
+    a spatial plane they are exactly 0, and ``smooth`` is 0 (with zero gradient) when the time axis has 2 nodes.  The
+    derivative of ``|1 - p|`` is ``sign(p - 1)``, 0 at ``p == 1``.
+
+    In terms of K-Planes' regularisers, up to weights: its ``compute_plane_tv`` of a plane is ``2 (tv_h + tv_w)``, its
+    ``compute_plane_smoothness`` is ``smooth`` and its ``L1TimePlanes`` sums ``l1``; its ``PlaneTV`` counts the spatial planes
+    twice.
+
+    Differentiable once towards ``enc.params``.  CUDA float32 parameters run on libnerfacc_hip.so (csrc/planereg.hip: two
+    launches forward, one backward, no atomics, nothing read back from the device: the same bits on every run); anything
+    else (CPU tensors, other dtypes) runs the same formulas in torch and is differentiated by autograd."""
+    params = enc.params
+    if params.is_cuda and params.dtype == torch.float32:
+        return _PlaneTermsFn.apply(params, enc)
+    dt = torch.promote_types(params.dtype, torch.float32)
+    return _plane_terms_torch(params.to(dt), enc.table).to(torch.float32)
+
+
+_REG_WEIGHTS: dict = {}   # (n_dims, n_scales, the four weights, device) -> [n_scales, n_planes, 4]
+
+
+def _reg_weights(enc, tv: float, tv_time: float, time_smoothness: float, l1_time: float) -> Tensor:
+    key = (enc.n_input_dims, enc.n_scales, tv, tv_time, time_smoothness, l1_time, enc.params.device)
+    w = _REG_WEIGHTS.get(key)
+    if w is None:
+        row = [[tv_time, tv_time, time_smoothness, l1_time] if b == 3 else [tv, tv, 0.0, 0.0] for _, b in enc.table.planes]
+        w = _REG_WEIGHTS[key] = torch.tensor([row] * enc.n_scales, dtype=torch.float32, device=enc.params.device)
+    return w
+
+
+def plane_regularization(enc, tv: float = 0.0, tv_time: Optional[float] = None, time_smoothness: float = 0.0,
+                         l1_time: float = 0.0) -> Tensor:
+    """The weighted sum of :func:`plane_terms` over the scales and planes of ``enc``, a scalar:
+
+        sum_s [ tv sum_{spatial k} (tv_h + tv_w) + tv_time sum_{time k} (tv_h + tv_w)
+                + time_smoothness sum_{time k} smooth + l1_time sum_{time k} l1 ]
+
+    ``tv_time=None`` means ``tv``.  A non-zero ``time_smoothness`` on an encoding whose time axis has fewer than 3 nodes
+    raises ``ValueError`` (there is no second difference to penalise).  Example: K-Planes' ``PlaneTV(w)`` is
+    ``plane_regularization(enc, tv=4 * w, tv_time=2 * w)``: K-Planes counts the spatial planes twice and its per-plane value
+    is ``2 (tv_h + tv_w)``.
+
+    It is ``plane_terms(enc)`` dotted with a constant weight tensor that is built once per (shape, weights, device) and
+    kept, so a call makes no host-to-device copy after the first."""
+    tv, time_smoothness, l1_time = float(tv), float(time_smoothness), float(l1_time)
+    tv_time = tv if tv_time is None else float(tv_time)
+    if time_smoothness != 0.0 and enc.n_input_dims == 4 and min(r[3] for r in enc.table.res) < 3:
+        raise ValueError("plane_regularization: time_smoothness needs at least 3 nodes along the time axis "
+                         f"(got {min(r[3] for r in enc.table.res)})")
+    return (plane_terms(enc) * _reg_weights(enc, tv, tv_time, time_smoothness, l1_time)).sum()

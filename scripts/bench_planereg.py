@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""Times `plane_regularization` (total variation, time smoothness and L1 of the plane tables: csrc/planereg.hip) against the
+same formulas in torch (slice differences, squares and means per plane, autograd) on the same GPU, on the K-Planes D-NeRF
+hybrid shape -- D = 4, resolution (64, 64, 64, 150), multiscale_res (1, 2, 4, 8), F = 32 -- and on its static D = 3 tri-plane
+part, and prints one JSON line per shape.
+    python scripts/bench_planereg.py [--window-ms 200] [--windows 5] [--features 32] [--no-torch]
+Per line: the native forward (`fwd`, under no_grad), the native forward + backward into `params.grad`-sized storage
+(`fwd_bwd`), and the same two through torch (`torch_fwd`, `torch_fwd_bwd`) on the same parameters.  The four take turns
+window by window in one process.  A window is as many calls as fill `--window-ms` of device time (at least 3; counted once
+per pass from a timed probe after 3 warm-up calls) between two HIP events; `*_us` is the median of the windows' means,
+`*_spread` their (min, max), `*_reps` the calls per window.  `bwd_us` = `fwd_bwd_us` - `fwd_us`.  `*_peak_mib`: the
+allocator's peak during one forward + backward of that form, above what was allocated before it.
+`bound`: the bytes a pass cannot avoid -- the table read once forward, read once and its gradient written once backward --
+and the time they take at the measured HBM copy rate (6.29 TB/s); `fwd_tbps` / `bwd_tbps` are those bytes over the measured
+times (achieved rates of the minimum traffic, not of the traffic the kernels cause: halo rows and neighbour nodes are read
+again, mostly from a cache), `*_bound_frac` = bound time / measured time.  `max_rel_diff_vs_torch`: the two forms' losses
+at the size that is timed."""
+import argparse
+import json
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from nerfacc_amd import losses  # noqa: E402
+from nerfacc_amd.encodings import PlaneGridEncoding  # noqa: E402
+
+HBM_BPS = 6.29e12      # measured float4 copy rate
+WEIGHTS = dict(tv=2e-4, tv_time=1e-4, time_smoothness=1e-3, l1_time=1e-4)
+
+
+def timed(fn, reps):
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(reps):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) * 1e3 / reps   # us
+
+
+def peak_mib(fn):
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    out = fn()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - base
+    del out
+    return round(peak / 2 ** 20, 1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--window-ms", type=float, default=200.0)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--features", type=int, default=32)
+    ap.add_argument("--no-torch", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_planereg.py measures on a GPU; none is available")
+    dev = torch.device("cuda:0")
+    shapes = {4: (64, 64, 64, 150), 3: (64, 64, 64)}
+    ms = (1, 2, 4, 8)
+    for D, res in shapes.items():
+        torch.manual_seed(D)
+        enc = PlaneGridEncoding(D, res, ms, n_features=a.features).to(dev)
+        with torch.no_grad():   # a table in training: around its initial values, nothing exactly 1
+            enc.params.add_(0.05 * torch.randn_like(enc.params))
+        w = losses._reg_weights(enc, WEIGHTS["tv"], WEIGHTS["tv_time"], WEIGHTS["time_smoothness"], WEIGHTS["l1_time"])
+
+        def native():
+            return losses.plane_regularization(enc, **WEIGHTS)
+
+        def composed():
+            return (losses._plane_terms_torch(enc.params, enc.table) * w).sum()
+
+        def no_grad(f):
+            def g():
+                with torch.no_grad():
+                    return f()
+            return g
+
+        def with_grad(f):
+            return lambda: torch.autograd.grad(f(), enc.params)
+        passes = {"fwd": no_grad(native), "fwd_bwd": with_grad(native)}
+        if not a.no_torch:
+            passes.update(torch_fwd=no_grad(composed), torch_fwd_bwd=with_grad(composed))
+            with torch.no_grad():
+                x, y = float(native()), float(composed())
+            err = abs(x - y) / abs(y)
+        times, reps = {k: [] for k in passes}, {}
+        for k, fn in passes.items():
+            for _ in range(3):
+                fn()
+            reps[k] = max(3, int(math.ceil(a.window_ms * 1e3 / timed(fn, 3))))
+        for _ in range(a.windows):
+            for k, fn in passes.items():
+                times[k].append(timed(fn, reps[k]))
+        table = enc.params.numel() * 4
+        row = {"n_dims": D, "resolution": list(res), "multiscale_res": list(ms), "n_features": a.features,
+               "n_params": enc.params.numel(), "weights": WEIGHTS, "window_ms": a.window_ms, "windows": a.windows}
+        for k, v in times.items():
+            row[k + "_us"] = round(float(np.median(v)), 1)
+            row[k + "_spread"] = [round(min(v), 1), round(max(v), 1)]
+            row[k + "_reps"] = reps[k]
+        row["bwd_us"] = round(row["fwd_bwd_us"] - row["fwd_us"], 1)
+        row["fwd_bwd_peak_mib"] = peak_mib(passes["fwd_bwd"])
+        if not a.no_torch:
+            row["torch_bwd_us"] = round(row["torch_fwd_bwd_us"] - row["torch_fwd_us"], 1)
+            row["torch_fwd_bwd_peak_mib"] = peak_mib(passes["torch_fwd_bwd"])
+            row["fwd_ratio"] = round(row["torch_fwd_us"] / row["fwd_us"], 2)
+            row["fwd_bwd_ratio"] = round(row["torch_fwd_bwd_us"] / row["fwd_bwd_us"], 2)
+            row["max_rel_diff_vs_torch"] = err
+        fwd_bound, bwd_bound = table / HBM_BPS * 1e6, 2 * table / HBM_BPS * 1e6
+        row["bound"] = {"fwd_bytes": table, "fwd_us": round(fwd_bound, 1), "bwd_bytes": 2 * table, "bwd_us": round(bwd_bound, 1)}
+        row["fwd_tbps"] = round(table / row["fwd_us"] / 1e6, 2)
+        row["bwd_tbps"] = round(2 * table / row["bwd_us"] / 1e6, 2)
+        row["fwd_bound_frac"] = round(fwd_bound / row["fwd_us"], 3)
+        row["bwd_bound_frac"] = round(bwd_bound / row["bwd_us"], 3)
+        print(json.dumps(row), flush=True)
+        del enc, w
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
