@@ -872,6 +872,39 @@ int nfa_planereg_fwd(int32_t n_dims, const float *params, int32_t n_scales, int3
 int nfa_planereg_bwd(int32_t n_dims, const float *params, int32_t n_scales, int32_t n_features, const int32_t *res_host,
                      const float *grad_terms, float *grad_params, nfa_stream_t stream);
 
+/* The vector-matrix (VM) decomposition of TensoRF (Chen et al. 2022; `TensorVMSplit`), x [n_points, 3] in [0, 1] (TensoRF's
+ * u in [-1, 1] is x = (u + 1) / 2).  Modes m = 0, 1, 2: plane axes (a, b) = (0,1) (0,2) (1,2) (matMode), line axis c = 2, 1, 0
+ * (vecMode).  res_host: 3 host ints read during the call, R_d >= 2 nodes along axis d.  n_components C: a multiple of 4 in
+ * 4..96, the same for every mode.  params: one float32 table without gaps (fewer than 2^31 floats); for m in order the plane,
+ * a row-major [R_b, R_a, C] block, then the line, a [R_c, C] block.  Plane and line are sampled bilinearly / linearly with
+ * the border rule of grid_sample(padding_mode="border", align_corners=True) (node coordinate x_d (R - 1) clamped to
+ * [0, R - 1], NaN to 0: every input reads and writes inside its blocks) and multiplied: t_m[j] = plane_m[j] * line_m[j].
+ * reduce = NFA_VM_CONCAT: y [n_points, 3 C], y[n, m C + j] = t_m[j] (compute_appfeature before basis_mat);
+ * NFA_VM_SUM: y [n_points, 1], the sum of all 3 C terms in the fixed order of csrc/vmgrid.hip's header
+ * (compute_densityfeature).  y holds elements of type `elem` (NFA_ELEM_*; float32 arithmetic, rounded once).
+ * nfa_vmgrid_bwd: grad_y in y's shape and `elem`; grad_params (the table's size, float32, zeroed by the caller; float
+ * atomics -- the line blocks through a per-workgroup copy in LDS while a line fits 64 KiB -- so its last bits depend on the
+ * arrival order) and grad_x [n_points, 3] (no atomics: bitwise reproducible; 0 on an axis whose coordinate is outside [0, 1]
+ * or not finite) are each optional, at least one.  The samples are recomputed from x and params.  No pointer needs more
+ * than its element's alignment.
+ * n_points == 0 returns NFA_OK before anything else is looked at.  Otherwise the arguments are checked in this order, each
+ * with its own message, before any launch: n_points, reduce, elem, n_components, res_host (null; a resolution below 2; the
+ * size limit), null pointers.
+ * nfa_vmgrid_resample (`up_sampling_VM`): dst_params, a table of the same layout at the resolution dst_res_host, receives
+ * at every node of every plane and line the bilinear / linear sample of src_params' block at, per axis,
+ * (float)i' * ((float)(R - 1) / (float)(R' - 1)): F.interpolate(mode="bilinear", align_corners=True).  Up, down or
+ * unchanged, each axis on its own; equal resolutions copy (finite values).  The tables must not overlap.  Checked in this
+ * order: n_components, the resolution tables (null; a source, then a destination resolution below 2 or beyond the size
+ * limit), null pointers. */
+#define NFA_VM_CONCAT 0
+#define NFA_VM_SUM 1
+int nfa_vmgrid_fwd(int32_t reduce, int32_t elem, const float *x, const float *params, int64_t n_points, int32_t n_components,
+                   const int32_t *res_host, void *y, nfa_stream_t stream);
+int nfa_vmgrid_bwd(int32_t reduce, int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points,
+                   int32_t n_components, const int32_t *res_host, float *grad_params, float *grad_x, nfa_stream_t stream);
+int nfa_vmgrid_resample(const float *src_params, const int32_t *src_res_host, float *dst_params, const int32_t *dst_res_host,
+                        int32_t n_components, nfa_stream_t stream);
+
 /* ------------------------------------------------------------------ sample positions */
 
 /* What every field does between sampling() and its encodings, in one pass over the samples.  Replaces the torch

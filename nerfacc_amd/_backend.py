@@ -149,6 +149,9 @@ _SIGS = {
     "nfa_planereg_partials": [_i32, _i32, _i32, C.POINTER(_i32)],
     "nfa_planereg_fwd": [_i32, _vp, _i32, _i32, C.POINTER(_i32), _vp, _i64, _vp, _vp],
     "nfa_planereg_bwd": [_i32, _vp, _i32, _i32, C.POINTER(_i32), _vp, _vp, _vp],
+    "nfa_vmgrid_fwd": [_i32, _i32, _vp, _vp, _i64, _i32, C.POINTER(_i32), _vp, _vp],
+    "nfa_vmgrid_bwd": [_i32, _i32, _vp, _vp, _vp, _i64, _i32, C.POINTER(_i32), _vp, _vp, _vp],
+    "nfa_vmgrid_resample": [_vp, C.POINTER(_i32), _vp, C.POINTER(_i32), _i32, _vp],
     "nfa_sample_positions_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
     "nfa_sample_positions_bwd": [_vp] * 9 + [_i64, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "nfa_generate_rays_fwd": [_vp, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _f32, _i32,
@@ -207,6 +210,8 @@ ELEM_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 INTERP_CODES = {"Linear": 0, "Smoothstep": 1}
 # include/nerfacc_hip.h: NFA_PLANE_*, how the plane grid combines the planes of a scale
 PLANE_REDUCE_CODES = {"product": 0, "sum": 1}
+# include/nerfacc_hip.h: NFA_VM_*, what the VM grid does with the three modes' terms
+VM_REDUCE_CODES = {"concat": 0, "sum": 1}
 
 
 def set_tuning(name: str, value: Optional[str]) -> None:

@@ -103,6 +103,12 @@ static void dispatch_lanes(int l, F &&f)
     else if (l == 32) f(std::integral_constant<int, 32>{});
     else f(std::integral_constant<int, 64>{});
 }
+// f(std::integral_constant<int, v>) when v is one of V...; nothing otherwise
+template <int... V, class Fn>
+static void dispatch_value(int32_t v, Fn &&f)
+{
+    (void)((v == V && (f(std::integral_constant<int, V>{}), true)) || ...);
+}
 
 // ---------------------------------------------------------------- wave64 primitives
 __device__ __forceinline__ int lane_id() { return __lane_id(); }

@@ -44,29 +44,10 @@
 // Element types: y / dL/dy are float, fp16 or bf16 (NFA_ELEM_*): float32 arithmetic, one rounding as the value is stored,
 // one lane per element.  x needs no alignment beyond its 4 bytes.
 #include "common.hip.h"
+#include "axis.h"           // Axis, locate_axis, store_elem / load_elem (shared with vmgrid.hip)
 #include "plane_layout.h"   // PlaneGridDesc, plane_a / plane_b, plane_layout (shared with planereg.hip)
 
 namespace nfa {
-
-struct Axis {
-    uint32_t i;   // the lower node, in [0, R - 2]
-    float f;      // the fraction, in [0, 1]
-    float rm1;    // (float)(R - 1)
-    bool in;      // the coordinate is inside [0, 1]
-};
-__device__ __forceinline__ Axis locate_axis(float x, int32_t R)
-{
-    Axis a;
-    a.rm1 = (float)(R - 1);
-    const float p = x * a.rm1;
-    a.in = p >= 0.0f && p <= a.rm1;
-    float q = p >= 0.0f ? p : 0.0f;
-    q = q <= a.rm1 ? q : a.rm1;
-    const int i = min((int)floorf(q), R - 2);
-    a.i = (uint32_t)i;
-    a.f = q - (float)i;
-    return a;
-}
 
 // The 4 corners of plane (a, b) around a point, for feature j: their first float, weights and values.
 struct Taps {
@@ -89,19 +70,6 @@ __device__ __forceinline__ float tap_value(Taps &c, const float *__restrict__ pa
 #pragma unroll
     for (int k = 0; k < 4; ++k) v = v + c.w[k] * c.t[k];
     return v;
-}
-
-template <class E>
-__device__ __forceinline__ void store_elem(E *p, float v)
-{
-    if constexpr (std::is_same<E, float>::value) *p = v;
-    else *reinterpret_cast<uint16_t *>(p) = (uint16_t)half_bits<E>(v);
-}
-template <class E>
-__device__ __forceinline__ float load_elem(const E *p)
-{
-    if constexpr (std::is_same<E, float>::value) return *p;
-    else return half_value<E>(*reinterpret_cast<const uint16_t *>(p));
 }
 
 // Forward: one scale per workgroup row, F lanes per point.
@@ -236,11 +204,6 @@ static int planegrid_desc(const char *name, const PlaneGridArgs &A, PlaneGridDes
     return plane_layout(name, A.n_dims, A.n_features, A.n_scales, A.res_host, P);
 }
 
-template <int... V, class Fn>
-static void dispatch_value(int32_t v, Fn &&f)
-{
-    (void)((v == V && (f(std::integral_constant<int, V>{}), true)) || ...);
-}
 template <class Fn>
 static void dispatch_planegrid(const PlaneGridArgs &A, Fn &&f)
 {

@@ -8,6 +8,8 @@ Parameter layout compatibility with tcnn checkpoints is not a goal.
 
 ``PlaneGridEncoding`` is the plane-factorised multiscale encoding of K-Planes (3-D: tri-planes, 4-D: the six planes of a
 dynamic scene) as one native pass each way (csrc/planes.hip); it shares ``out_dtype`` and the device rules below.
+``VMGridEncoding`` is TensoRF's vector-matrix decomposition (three plane x line modes, concatenated for the appearance or
+summed for the density) with its grid resampling (csrc/vmgrid.hip), under the same rules.
 
 CUDA float32 tensors run on libnerfacc_hip.so; CPU tensors and other dtypes run the same formulas in torch (the hash grid's
 torch path reproduces the native forward bit for bit).  Under ``torch.autocast`` both encodings run in float32, as tcnn's
@@ -34,7 +36,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _backend as B
 
-__all__ = ["HashGridEncoding", "SphericalHarmonicsEncoding", "PlaneGridEncoding", "encoding_from_tcnn_config"]
+__all__ = ["HashGridEncoding", "SphericalHarmonicsEncoding", "PlaneGridEncoding", "VMGridEncoding", "encoding_from_tcnn_config"]
 
 _M32 = 0xFFFFFFFF
 _PRIMES = (1, 2654435761, 805459861, 3674653429)   # tcnn's hash primes of dimensions 0..3
@@ -677,6 +679,265 @@ class PlaneGridEncoding(nn.Module):
         return (f"n_input_dims={self.n_input_dims}, resolution={self.resolution}, multiscale_res={self.multiscale_res}, "
                 f"n_features={self.n_features}, reduce={self.reduce!r}"
                 + (f", init={self.init}" if self.init != (0.1, 0.5) else "")
+                + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else ""))
+
+
+VM_MODES = ((0, 1, 2), (0, 2, 1), (1, 2, 0))   # (a, b, c) per mode: TensoRF's matMode (plane axes) and vecMode (line axis)
+
+
+def _vm_lanes(n_components: int) -> int:
+    """The lane-group width of csrc/vmgrid.hip: the largest power of two <= 32 that divides C."""
+    return next(w for w in (32, 16, 8, 4) if n_components % w == 0)
+
+
+class VMTable:
+    """The blocks of a VM grid, computed once on the host: per mode ``m`` with axes ``(a, b, c) = VM_MODES[m]`` the plane,
+    a row-major ``[R_b, R_a, C]`` block at ``plane_offsets[m]``, then the line, a ``[R_c, C]`` block at ``line_offsets[m]``,
+    the modes in order without gaps (sizes in floats)."""
+
+    def __init__(self, resolution, n_components: int):
+        self.res = [int(r) for r in resolution]
+        C = self.n_components = int(n_components)
+        self.plane_offsets, self.plane_sizes, self.line_offsets, self.line_sizes, offset = [], [], [], [], 0
+        for a, b, c in VM_MODES:
+            self.plane_offsets.append(offset)
+            self.plane_sizes.append(self.res[a] * self.res[b] * C)
+            offset += self.plane_sizes[-1]
+            self.line_offsets.append(offset)
+            self.line_sizes.append(self.res[c] * C)
+            offset += self.line_sizes[-1]
+        self.n_params = offset
+        # host array handed to nfa_vmgrid_{fwd,bwd,resample} (read synchronously by each call)
+        self.c_res = (ctypes.c_int32 * 3)(*[min(r, (1 << 31) - 1) for r in self.res])
+
+    def plane(self, params: Tensor, m: int) -> Tensor:
+        a, b, _ = VM_MODES[m]
+        o = self.plane_offsets[m]
+        return params[o: o + self.plane_sizes[m]].view(self.res[b], self.res[a], self.n_components)
+
+    def line(self, params: Tensor, m: int) -> Tensor:
+        o = self.line_offsets[m]
+        return params[o: o + self.line_sizes[m]].view(self.res[VM_MODES[m][2]], self.n_components)
+
+
+def _locate_nodes(p: Tensor, R: int):
+    """axis.h's locate_pos for node coordinates ``p`` among ``R`` nodes: (i, f), i int64 in [0, R - 2], f in [0, 1]."""
+    rm1 = float(R - 1)
+    q = torch.where(p >= 0, p, torch.zeros_like(p))        # (NaN gives 0: `where`, not `maximum`)
+    q = torch.where(q <= rm1, q, torch.full_like(q, rm1))
+    i = torch.floor(q.detach()).to(torch.int64).clamp(max=R - 2)
+    return i, q - i.to(q.dtype)
+
+
+def _vm_plane_value(plane: Tensor, Ra: int, ia, fa, ib, fb) -> Tensor:
+    """The 4-tap sum of csrc/planes.hip / csrc/vmgrid.hip on a ``[R_b * R_a, C]`` plane, corner order, from 0."""
+    row = ib * Ra + ia
+    v = torch.zeros(ia.shape[0], plane.shape[1], dtype=plane.dtype, device=plane.device)
+    for k in range(4):
+        ka, kb = k & 1, k >> 1
+        w = (fa if ka else 1.0 - fa) * (fb if kb else 1.0 - fb)
+        v = v + w[:, None] * plane[row + (kb * Ra + ka)]
+    return v
+
+
+def _vm_line_value(line: Tensor, ic, fc) -> Tensor:
+    """``(0 + (1 - f) L[i]) + f L[i + 1]`` on a ``[R_c, C]`` line."""
+    v = torch.zeros(ic.shape[0], line.shape[1], dtype=line.dtype, device=line.device)
+    v = v + (1.0 - fc)[:, None] * line[ic]
+    return v + fc[:, None] * line[ic + 1]
+
+
+def _vmgrid_torch(x: Tensor, params: Tensor, t: VMTable, reduce: int = 0) -> Tensor:
+    """The VM grid in torch, op for op as csrc/vmgrid.hip computes it, the lane sums and the xor butterfly of ``"sum"``
+    included (x [N, 3] and params in one float dtype); ``reduce``: a ``B.VM_REDUCE_CODES`` value."""
+    C = t.n_components
+    cell = [_locate_nodes(x[:, d] * float(t.res[d] - 1), t.res[d]) for d in range(3)]
+    terms = []
+    for m, (a, b, c) in enumerate(VM_MODES):
+        pv = _vm_plane_value(t.plane(params, m).view(-1, C), t.res[a], *cell[a], *cell[b])
+        terms.append(pv * _vm_line_value(t.line(params, m), *cell[c]))
+    if not reduce:
+        return torch.cat(terms, -1)
+    L = _vm_lanes(C)
+    lanes = torch.zeros(x.shape[0], L, dtype=x.dtype, device=x.device)
+    for term in terms:
+        for r in range(C // L):
+            lanes = lanes + term[:, r * L: (r + 1) * L]
+    lane = torch.arange(L, device=x.device)
+    off = L // 2
+    while off:
+        lanes = lanes + lanes[:, lane ^ off]
+        off //= 2
+    return lanes[:, :1]
+
+
+def _vm_resample_torch(params: Tensor, src: VMTable, dst: VMTable) -> Tensor:
+    """``nfa_vmgrid_resample`` in torch, op for op (TensoRF's ``up_sampling_VM``): the table of ``dst`` whose every node is
+    the sample of ``src``'s block at ``i' * ((R - 1) / (R' - 1))`` per axis, the quotient and the product in params' dtype."""
+    C, dt, dev = src.n_components, params.dtype, params.device
+
+    def nodes(d):
+        scale = torch.tensor(src.res[d] - 1, dtype=dt) / torch.tensor(dst.res[d] - 1, dtype=dt)
+        return _locate_nodes(torch.arange(dst.res[d], dtype=dt, device=dev) * scale.to(dev), src.res[d])
+
+    cell = [nodes(d) for d in range(3)]
+    out = []
+    for m, (a, b, c) in enumerate(VM_MODES):
+        ia, fa = (v.repeat(dst.res[b]) for v in cell[a])               # node (i'_b, i'_a), row-major: a runs fastest
+        ib, fb = (v.repeat_interleave(dst.res[a]) for v in cell[b])
+        out.append(_vm_plane_value(src.plane(params, m).view(-1, C), src.res[a], ia, fa, ib, fb).reshape(-1))
+        out.append(_vm_line_value(src.line(params, m), *cell[c]).reshape(-1))
+    return torch.cat(out)
+
+
+class _VMGridFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, params, enc: "VMGridEncoding", dtype: torch.dtype):
+        B.require_device(x, params)
+        N = x.shape[0]
+        y = torch.empty(N, enc.n_output_dims, dtype=dtype, device=x.device)
+        if N:
+            with torch.cuda.device(x.device):
+                B.call("nfa_vmgrid_fwd", *enc._lead(dtype), B.ptr(x), B.ptr(params), *enc._table_args(N), B.ptr(y), B.stream())
+        ctx.enc, ctx.dtype = enc, dtype
+        ctx.save_for_backward(x, params)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        need_x, need_p = ctx.needs_input_grad[:2]
+        if g_y is None or not (need_x or need_p):
+            return None, None, None, None
+        x, params = ctx.saved_tensors
+        g_x, g_p = _VMGridBwdFn.apply(x, params, _grad_as(g_y, ctx.dtype), ctx.enc, ctx.dtype, need_x, need_p)
+        return g_x, g_p, None, None
+
+
+class _VMGridBwdFn(torch.autograd.Function):
+    """The VM grid's backward as a function ``(x, params, g_y) -> (g_x, g_params)`` of its own, so that differentiating it
+    again (``create_graph=True``) fails with a message that names the encoding instead of a missing ``grad_fn``."""
+
+    @staticmethod
+    def forward(ctx, x, params, g, enc: "VMGridEncoding", dtype: torch.dtype, need_x: bool, need_p: bool):
+        g_p = torch.zeros_like(params) if need_p else None
+        g_x = torch.empty_like(x) if need_x else None
+        if x.shape[0]:
+            with torch.cuda.device(x.device):
+                B.call("nfa_vmgrid_bwd", *enc._lead(dtype), B.ptr(x), B.ptr(params), B.ptr(g), *enc._table_args(x.shape[0]),
+                       B.ptr(g_p), B.ptr(g_x), B.stream())
+        ctx.set_materialize_grads(False)
+        return g_x, g_p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gg_x, gg_p):
+        raise NotImplementedError("VMGridEncoding: the second order (differentiating dL/dx or dL/dparams again) is not "
+                                  "implemented on the native path; the torch path on CPU tensors is differentiated by autograd")
+
+
+class VMGridEncoding(nn.Module):
+    """The vector-matrix (VM) decomposition of TensoRF (Chen et al. 2022), ``TensorVMSplit``'s feature grids, as one native
+    pass each way (csrc/vmgrid.hip).  ``forward(x[..., 3])`` for ``x`` in [0, 1]^3 (TensoRF's ``u`` in [-1, 1] is
+    ``x = (u + 1) / 2``) gives ``[..., 3 C]`` with ``reduce="concat"`` (mode ``m`` at columns ``m C .. m C + C - 1``:
+    ``compute_appfeature`` before ``basis_mat``) or ``[..., 1]`` with ``reduce="sum"`` (``compute_densityfeature``).
+
+    Mode ``m`` has the axes ``(a, b, c) = VM_MODES[m]``: the plane over ``matMode = (0,1) (0,2) (1,2)``, the line along
+    ``vecMode = 2, 1, 0``.  ``resolution`` ``(R_0, R_1, R_2)``, every one at least 2; ``n_components`` C per mode, a multiple
+    of 4 in 4..96 (TensoRF: 16 for the density, 48 for the appearance).
+
+    ``params`` is one flat float32 table (fewer than 2^31 values): per mode the plane, then the line, without gaps
+    (``offsets`` / ``sizes``: ``[[plane, line]]`` per mode, in floats).  ``plane(m)`` is the ``[R_b, R_a, C]`` view and
+    ``plane(m).permute(2, 0, 1)[None]`` the ``[1, C, H, W]`` tensor TensoRF keeps in ``density_plane[m]`` / ``app_plane[m]``;
+    ``line(m)`` is the ``[R_c, C]`` view and ``line(m).t()[None, :, :, None]`` TensoRF's ``[1, C, R, 1]`` line.  Both are
+    sampled as ``F.grid_sample(mode="bilinear", padding_mode="border", align_corners=True)`` samples them (TensoRF pads
+    with zeros, which differs outside the box only) and multiplied.  Initialised as TensoRF: ``init_scale * randn``.
+
+    Every input is legal: a coordinate outside [0, 1] samples the border, NaN samples node 0, and ``dL/dx`` is zero on such
+    an axis.  Differentiable once w.r.t. ``params`` (float atomics: the last bits change from run to run) and ``x`` (bitwise
+    reproducible); the torch path (CPU tensors, other dtypes) is differentiated by autograd.  ``out_dtype`` as for
+    :class:`HashGridEncoding`.  ``resampled(resolution)`` is TensoRF's ``up_sampling_VM``."""
+
+    def __init__(self, resolution, n_components: int = 16, reduce: str = "concat", init_scale: float = 0.1, out_dtype=None):
+        super().__init__()
+        self._configure(resolution, n_components, reduce, init_scale, out_dtype)
+        self.params = nn.Parameter(torch.randn(self.table.n_params, dtype=torch.float32) * self.init_scale)
+
+    def _configure(self, resolution, n_components, reduce, init_scale, out_dtype):
+        """The checks and everything of the module but ``params`` (``resampled`` fills those itself)."""
+        self.out_dtype = _check_out_dtype(out_dtype)
+        if not (isinstance(n_components, int) and 4 <= n_components <= 96 and n_components % 4 == 0):
+            raise ValueError(f"VMGridEncoding: n_components must be a multiple of 4 in 4..96 (got {n_components})")
+        if reduce not in B.VM_REDUCE_CODES:
+            raise ValueError(f"VMGridEncoding: reduce must be 'concat' or 'sum' (got {reduce!r})")
+        resolution = tuple(int(r) for r in resolution)
+        if len(resolution) != 3:
+            raise ValueError(f"VMGridEncoding: resolution must have 3 entries (got {len(resolution)})")
+        if min(resolution) < 2:
+            raise ValueError(f"VMGridEncoding: every resolution must be at least 2 (got {resolution})")
+        self.n_input_dims, self.n_components, self.reduce, self.resolution = 3, n_components, reduce, resolution
+        self.table = VMTable(resolution, n_components)
+        if self.table.n_params >= 1 << 31:
+            raise ValueError(f"VMGridEncoding: {self.table.n_params} parameters (at most 2^31 - 1)")
+        self.n_output_dims = 3 * n_components if reduce == "concat" else 1
+        self.init_scale = float(init_scale)
+
+    modes = property(lambda self: list(VM_MODES))
+    offsets = property(lambda self: [[p, l] for p, l in zip(self.table.plane_offsets, self.table.line_offsets)])
+    sizes = property(lambda self: [[p, l] for p, l in zip(self.table.plane_sizes, self.table.line_sizes)])
+
+    def plane(self, m: int) -> Tensor:
+        """The plane of mode ``m`` as a ``[R_b, R_a, C]`` view of ``params``."""
+        return self.table.plane(self.params, m)
+
+    def line(self, m: int) -> Tensor:
+        """The line of mode ``m`` as a ``[R_c, C]`` view of ``params``."""
+        return self.table.line(self.params, m)
+
+    def _lead(self, dtype: torch.dtype):
+        return B.VM_REDUCE_CODES[self.reduce], B.ELEM_CODES[dtype]
+
+    def _table_args(self, n_points: int):
+        return n_points, self.n_components, self.table.c_res
+
+    def forward(self, x: Tensor) -> Tensor:
+        assert x.shape[-1] == 3, "VMGridEncoding: x must have shape (..., 3)"
+        out = _resolve_out_dtype(self.out_dtype, x)
+        x, ctx = _autocast_off(x)
+        with ctx:
+            lead = x.shape[:-1]
+            x2 = x.reshape(-1, 3)
+            p = self.params
+            if x2.is_cuda and x2.dtype == torch.float32 and p.dtype == torch.float32 and p.device == x2.device:
+                y = _VMGridFn.apply(x2.contiguous(), p, self, out)   # (element-wise access: no alignment beyond 4 bytes)
+            else:
+                dt = torch.promote_types(x2.dtype, p.dtype)
+                y = _vmgrid_torch(x2.to(dt), p.to(dt), self.table, B.VM_REDUCE_CODES[self.reduce])
+                if self.out_dtype is not None:
+                    y = y.to(out)
+            return y.view(*lead, self.n_output_dims)
+
+    @torch.no_grad()
+    def resampled(self, resolution) -> "VMGridEncoding":
+        """A new module on the same device whose planes and lines are these resampled to ``resolution`` (each axis up, down
+        or unchanged): ``F.interpolate(mode="bilinear", align_corners=True)`` of every block, TensoRF's ``up_sampling_VM``.
+        The same resolution copies the table bit for bit (finite values).  Optimiser state does not follow: build a new
+        optimiser, as TensoRF does."""
+        new = VMGridEncoding.__new__(VMGridEncoding)   # (no random table is drawn for a module that gets this one's samples)
+        nn.Module.__init__(new)
+        new._configure(resolution, self.n_components, self.reduce, self.init_scale, self.out_dtype)
+        p = self.params.detach()
+        if p.is_cuda and p.dtype == torch.float32:
+            q = torch.empty(new.table.n_params, dtype=torch.float32, device=p.device)
+            with torch.cuda.device(p.device):
+                B.call("nfa_vmgrid_resample", B.ptr(p), self.table.c_res, B.ptr(q), new.table.c_res, self.n_components, B.stream())
+        else:
+            q = _vm_resample_torch(p, self.table, new.table)
+        new.params = nn.Parameter(q, requires_grad=self.params.requires_grad)
+        return new
+
+    def extra_repr(self) -> str:
+        return (f"resolution={self.resolution}, n_components={self.n_components}, reduce={self.reduce!r}"
+                + (f", init_scale={self.init_scale}" if self.init_scale != 0.1 else "")
                 + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else ""))
 
 
