@@ -102,7 +102,8 @@ int nfa_pack_rows(const void *padded, const int64_t *packed_info /*[n_rays,2]*/,
 /* counts[r] = number of nonzero bytes in mask row r (uint8 [n_rows, n_cols]). */
 int nfa_mask_row_counts(const uint8_t *mask, int64_t n_rows, int64_t n_cols, int64_t *counts, nfa_stream_t stream);
 
-/* 1 bit per cell copy of a torch.bool grid [n_cells] (derived cache, never serialised). */
+/* 1 bit per cell copy of a torch.bool grid [n_cells] (derived cache, never serialised).
+ * Layout: cell i (any non-zero byte = occupied) is bit i & 31 of word i >> 5; the last word's unused bits are 0. */
 int nfa_pack_bits(const uint8_t *binaries, int64_t n_cells, uint32_t *bits /*[(n_cells+31)/32]*/, nfa_stream_t stream);
 
 /* ------------------------------------------------------------------ grid */
@@ -322,11 +323,14 @@ int nfa_expand_intervals(int64_t n_rays, float step_size, const int32_t *run_cnt
  *                         indices are cell ids inside one level, x slowest; aabb = the level's 6 floats on the device)
  *   nfa_grid_ema_update   occs[cell_base + indices[i]] = max(occs[...] * ema_decay, occ[i])   (ref :393-398); a cell
  *                         listed several times gets max(occs * decay, max_i occ_i) -- deterministic, one of the values
- *                         the reference's index_put may leave.  scratch: n floats.
+ *                         the reference's index_put may leave.  max is torch.maximum for every float32: a NaN (stored
+ *                         value times decay, or candidate) wins and is written as 0x7FC00000, -0 counts as zero.
+ *                         scratch: n floats.
  *   nfa_grid_rebinarize   thre = min(mean(occs[occs >= 0]), occ_thre) reduced on the device, binaries = occs > thre
  *                         (ref :403-404) written as the torch.bool buffer AND as the walk's 1-bit grid copy
- *                         (nfa_pack_walk_bits layout); scratch: nfa_grid_rebinarize_scratch_bytes(), on return its last
- *                         two floats hold {thre, mean}. */
+ *                         (nfa_pack_walk_bits layout); scratch: nfa_grid_rebinarize_scratch_bytes(), on return the two
+ *                         floats at byte offset nfa_grid_rebinarize_scratch_bytes() - 16 hold {thre, mean} (the first two
+ *                         of its last four floats; the last two are unused). */
 int nfa_grid_cell_points(const int64_t *indices, const float *jitter /*[n,3]*/, int64_t n, const int32_t *res,
                          const float *aabb /*[6]*/, float *x /*[n,3]*/, nfa_stream_t stream);
 int nfa_grid_ema_update(float *occs, int64_t cell_base, const int64_t *indices, int64_t n, const float *occ,

@@ -18,6 +18,8 @@
 
 namespace nfa {
 
+constexpr unsigned int CANONICAL_NAN = 0x7FC00000u;   // the one NaN pattern the EMA update stores (positive sign, quiet)
+
 __global__ __launch_bounds__(256) void cell_points_kernel(const int64_t *__restrict__ indices, const float *__restrict__ jitter,
                                                           int64_t n, int32_t rx, int32_t ry, int32_t rz,
                                                           const float *__restrict__ aabb, float *__restrict__ x)
@@ -43,8 +45,10 @@ __global__ __launch_bounds__(256) void ema_gather_kernel(const float *__restrict
                                                          const int64_t *__restrict__ indices, int64_t n, float decay,
                                                          float *__restrict__ dec)
 {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)blockDim.x * gridDim.x)
-        dec[i] = occs[cell_base + indices[i]] * decay;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)blockDim.x * gridDim.x) {
+        const float d = occs[cell_base + indices[i]] * decay;
+        dec[i] = d != d ? __uint_as_float(CANONICAL_NAN) : d;   // atomic_max_f32 needs a stored NaN to be the canonical one
+    }
 }
 __global__ __launch_bounds__(256) void ema_decay_kernel(float *__restrict__ occs, int64_t cell_base,
                                                         const int64_t *__restrict__ indices, int64_t n,
@@ -54,12 +58,19 @@ __global__ __launch_bounds__(256) void ema_decay_kernel(float *__restrict__ occs
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)blockDim.x * gridDim.x)
         occs[cell_base + indices[i]] = dec[i];
 }
+// torch.maximum(*addr, v) for every float32 v, whatever the order of the atomics on one cell, given that *addr holds no NaN
+// other than CANONICAL_NAN (ema_gather_kernel sees to it).  Order-preserving integer views: floats with a clear sign bit
+// (+0 included) compare like signed ints and beat every float with the sign bit set, which reads as a negative int; floats
+// with the sign bit set (-0 included) compare like reversed unsigned ints and lose to every float with a clear sign bit,
+// which reads as a smaller unsigned.  CANONICAL_NAN is above +inf as a signed int and below every sign-bit pattern as an
+// unsigned one, so once stored it stays: NaN propagates.  The branch goes by the sign BIT (v >= 0 would send -0 to the
+// signed side as INT_MIN, where it never replaces a stored negative value).
 __device__ __forceinline__ void atomic_max_f32(float *addr, float v)
 {
-    if (v != v) { atomicExch(reinterpret_cast<unsigned int *>(addr), __float_as_uint(v)); return; }  // torch.maximum propagates NaN
-    // order-preserving integer views: non-negative floats compare like signed ints, negative ones like reversed unsigned
-    if (v >= 0.0f) atomicMax(reinterpret_cast<int *>(addr), __float_as_int(v));
-    else atomicMin(reinterpret_cast<unsigned int *>(addr), __float_as_uint(v));
+    if (v != v) { atomicExch(reinterpret_cast<unsigned int *>(addr), CANONICAL_NAN); return; }
+    const unsigned int u = __float_as_uint(v);
+    if ((u >> 31) == 0u) atomicMax(reinterpret_cast<int *>(addr), (int)u);
+    else atomicMin(reinterpret_cast<unsigned int *>(addr), u);
 }
 __global__ __launch_bounds__(256) void ema_max_kernel(float *__restrict__ occs, int64_t cell_base,
                                                       const int64_t *__restrict__ indices, int64_t n,
