@@ -909,6 +909,33 @@ int nfa_vmgrid_bwd(int32_t reduce, int32_t elem, const float *x, const float *pa
 int nfa_vmgrid_resample(const float *src_params, const int32_t *src_res_host, float *dst_params, const int32_t *dst_res_host,
                         int32_t n_components, nfa_stream_t stream);
 
+/* The regularisers TensoRF puts on the VM tables themselves, over the VM grid above (same n_components, res_host and params
+ * layout).  Mode m with its plane seen as p[j, i, k], j < H = R_b rows, i < W = R_a, k < C, and its line as l[r, k], r < R = R_c:
+ *   tv_h     = sum (p[j+1,i,k] - p[j,i,k])^2 / (C (H-1) W)         tv_line = sum (l[r+1,k] - l[r,k])^2 / (C (R-1))
+ *   tv_w     = sum (p[j,i+1,k] - p[j,i,k])^2 / (C H (W-1))         l1_line = sum |l[r,k]| / (C R)
+ *   l1_plane = sum |p[j,i,k]| / (C H W)                            ortho   = sum_{i<j} |G_ij| / (C (C-1) / 2)
+ *   G_ij = sum_r l[r,i] l[r,j], r ascending from 0
+ * (TensorVMSplit: TVLoss of a plane is 2 (tv_h + tv_w), density_L1 is sum_m (l1_plane + l1_line), vector_comp_diffs is
+ * sum_m ortho.)
+ * nfa_vmreg_fwd: terms [3, 6] = (tv_h, tv_w, l1_plane, tv_line, l1_line, ortho) per mode, two launches (per-tile sums of the
+ * planes into partials, then one workgroup per mode), no atomics: the same bits on every run; the order of the sums is in
+ * csrc/vmreg.hip's header.  partials: device scratch of n_partials >= nfa_vmreg_partials(n_components, res_host) rows of 4
+ * floats, contents irrelevant before and after.  signs [3, C, C] receives sign(G_ij) (0 at 0, NaN stays NaN; the diagonal
+ * is 0), which nfa_vmreg_bwd reads back: hand it the buffer of the forward over the same params.  nfa_vmreg_partials is
+ * host-only arithmetic on the shape (-1 with a message for a shape the passes refuse).
+ * nfa_vmreg_bwd: grad_terms [3, 6], a DEVICE pointer; grad_params (the table's size) receives sum_t grad_terms[m, t]
+ * d terms[m, t] / d params in one launch with plain stores: every element is written (the caller need not zero it) and the
+ * result is bitwise reproducible.  d |v| / dv is 0 at v == 0; d ortho / d l[r,i] = sum_{j != i} signs[m,i,j] l[r,j] / (C (C-1)
+ * / 2).  NaN and Inf parameters propagate within their mode; no index depends on data and nothing is read back from the
+ * device.  params, partials, signs and grad_params must be 16-byte aligned (every block starts on a 16-byte piece of params).
+ * The arguments are checked in this order, each with its own message, before any launch: n_components, res_host (null; a
+ * resolution below 2; the size limit), null pointers, alignment, n_partials. */
+int64_t nfa_vmreg_partials(int32_t n_components, const int32_t *res_host);
+int nfa_vmreg_fwd(const float *params, int32_t n_components, const int32_t *res_host, float *partials, int64_t n_partials,
+                  float *signs, float *terms, nfa_stream_t stream);
+int nfa_vmreg_bwd(const float *params, int32_t n_components, const int32_t *res_host, const float *grad_terms, const float *signs,
+                  float *grad_params, nfa_stream_t stream);
+
 /* ------------------------------------------------------------------ sample positions */
 
 /* What every field does between sampling() and its encodings, in one pass over the samples.  Replaces the torch

@@ -152,6 +152,9 @@ _SIGS = {
     "nfa_vmgrid_fwd": [_i32, _i32, _vp, _vp, _i64, _i32, C.POINTER(_i32), _vp, _vp],
     "nfa_vmgrid_bwd": [_i32, _i32, _vp, _vp, _vp, _i64, _i32, C.POINTER(_i32), _vp, _vp, _vp],
     "nfa_vmgrid_resample": [_vp, C.POINTER(_i32), _vp, C.POINTER(_i32), _i32, _vp],
+    "nfa_vmreg_partials": [_i32, C.POINTER(_i32)],
+    "nfa_vmreg_fwd": [_vp, _i32, C.POINTER(_i32), _vp, _i64, _vp, _vp, _vp],
+    "nfa_vmreg_bwd": [_vp, _i32, C.POINTER(_i32), _vp, _vp, _vp, _vp],
     "nfa_sample_positions_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
     "nfa_sample_positions_bwd": [_vp] * 9 + [_i64, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "nfa_generate_rays_fwd": [_vp, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _f32, _i32,
@@ -165,7 +168,7 @@ _SIGS = {
     "nfa_set_tuning": [C.c_char_p, C.c_char_p],
     "nfa_device_arch": [C.c_char_p, _int],
 }
-_RESTYPES = {"nfa_grid_rebinarize_scratch_bytes": _i64, "nfa_hashgrid_sorted_scratch_bytes": _i64, "nfa_hashgrid_sorted_scratch_bytes_d": _i64, "nfa_planereg_partials": _i64, "nfa_bricks_words": _i64, "nfa_walk_bits_words": _i64, "nfa_pdf_loss_partials": _i64, "nfa_cumsum_scratch_bytes": _i64, "nfa_seg_table_rows": _i64, "nfa_seg_plan": None, "nfa_last_error": C.c_char_p}
+_RESTYPES = {"nfa_grid_rebinarize_scratch_bytes": _i64, "nfa_hashgrid_sorted_scratch_bytes": _i64, "nfa_hashgrid_sorted_scratch_bytes_d": _i64, "nfa_planereg_partials": _i64, "nfa_vmreg_partials": _i64, "nfa_bricks_words": _i64, "nfa_walk_bits_words": _i64, "nfa_pdf_loss_partials": _i64, "nfa_cumsum_scratch_bytes": _i64, "nfa_seg_table_rows": _i64, "nfa_seg_plan": None, "nfa_last_error": C.c_char_p}
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

@@ -1,5 +1,5 @@
-"""Regularisers over packed samples (native kernels: csrc/segscan.hip, ``DistortionFwdOp`` / ``DistortionBwdOp``) and over
-the tables of a plane grid (csrc/planereg.hip).
+"""Regularisers over packed samples (native kernels: csrc/segscan.hip, ``DistortionFwdOp`` / ``DistortionBwdOp``), over
+the tables of a plane grid (csrc/planereg.hip) and over the tables of a VM grid (csrc/vmreg.hip).
 
 ``distortion`` is the Mip-NeRF 360 distortion loss (Barron et al. 2022, eq. 15), the other half of the proposal-sampling
 recipe ``PropNetEstimator`` implements.  Earlier nerfacc releases shipped a packed version; 0.5 dropped it.
@@ -7,6 +7,10 @@ recipe ``PropNetEstimator`` implements.  Earlier nerfacc releases shipped a pack
 ``plane_terms`` / ``plane_regularization`` are the regularisers K-Planes (Fridovich-Keil et al. 2023) adds to every step, over
 the planes of a :class:`~nerfacc_amd.encodings.PlaneGridEncoding`: total variation in space, the second difference along
 time and the L1 pull of the space-time planes towards 1, as one native pass each way.
+
+``vm_terms`` / ``vm_regularization`` are the regularisers TensoRF (Chen et al. 2022) adds to a step, over the planes and lines
+of a :class:`~nerfacc_amd.encodings.VMGridEncoding`: total variation, the L1 pull towards 0 and the orthogonality penalty on
+the line components, as two launches forward and one backward.
 
 Not part of ``nerfacc_amd.__all__`` (that list mirrors the reference's exactly); import the module.
 """
@@ -23,7 +27,7 @@ from . import _backend as B
 from ._segments import SegInfo, batched_native, resolve
 from .encodings import _aligned16
 
-__all__ = ["distortion", "plane_terms", "plane_regularization"]
+__all__ = ["distortion", "plane_terms", "plane_regularization", "vm_terms", "vm_regularization"]
 
 
 class _Distortion(torch.autograd.Function):
@@ -321,3 +325,171 @@ def plane_regularization(enc, tv: float = 0.0, tv_time: Optional[float] = None, 
         raise ValueError("plane_regularization: time_smoothness needs at least 3 nodes along the time axis "
                          f"(got {min(r[3] for r in enc.table.res)})")
     return (plane_terms(enc) * _reg_weights(enc, tv, tv_time, time_smoothness, l1_time)).sum()
+
+
+# ----------------------------------------------------------------------------- VM-grid regularisers (csrc/vmreg.hip)
+def _vm_counts(H: int, W: int, R: int, C: int):
+    """The number of summands of (tv_h, tv_w, l1_plane, tv_line, l1_line, ortho) of a mode; every one positive."""
+    return (C * (H - 1) * W, C * H * (W - 1), C * H * W, C * (R - 1), C * R, C * (C - 1) // 2)
+
+
+def _vm_terms_torch(params: Tensor, table) -> Tensor:
+    """The six terms per mode by slicing (and the Gram matrix by a matmul), in ``params``' dtype; differentiated by
+    autograd."""
+    C, rows = table.n_components, []
+    for m in range(3):
+        p, l = table.plane(params, m), table.line(params, m)
+        n = _vm_counts(p.shape[0], p.shape[1], l.shape[0], C)
+        gram = torch.triu(l.t() @ l, diagonal=1)
+        rows.append(torch.stack([((p[1:] - p[:-1]) ** 2).sum() / n[0], ((p[:, 1:] - p[:, :-1]) ** 2).sum() / n[1],
+                                 p.abs().sum() / n[2], ((l[1:] - l[:-1]) ** 2).sum() / n[3], l.abs().sum() / n[4],
+                                 gram.abs().sum() / n[5]]))
+    return torch.stack(rows)
+
+
+def _sign0(v: Tensor) -> Tensor:
+    """1, -1, and ``v`` itself where it is neither above nor below 0 (0 at 0; NaN stays NaN): csrc/vmreg.hip's ``vr_sign``."""
+    return torch.where(v > 0, torch.ones_like(v), torch.where(v < 0, -torch.ones_like(v), v))
+
+
+def _vm_terms_grad_torch(params: Tensor, grad_terms: Tensor, table) -> Tensor:
+    """``d (grad_terms . terms) / d params`` in float32, operation for operation as ``nfa_vmreg_bwd`` forms it from the
+    signs ``nfa_vmreg_fwd`` leaves (the stencils and their order: csrc/vmreg.hip's header), so the two agree bit for bit.
+    The Gram matrix is summed over ``r`` ascending from 0, ``go`` over ``j`` ascending from 0; the term ``j == i`` is skipped
+    (not multiplied by a zero sign), as in the kernel."""
+    C = table.n_components
+    p32, g32 = params.detach().to(torch.float32), grad_terms.detach().to(torch.float32).reshape(3, 6)
+    out = torch.empty_like(p32)
+    comp = torch.arange(C, device=p32.device)
+    for m in range(3):
+        p, l = table.plane(p32, m), table.line(p32, m)
+        H, W, R = p.shape[0], p.shape[1], l.shape[0]
+        inv = torch.tensor([1.0 / n for n in _vm_counts(H, W, R, C)], dtype=torch.float32, device=p.device)
+        c = g32[m] * inv
+        zr, zc, zl = p.new_zeros(1, W, C), p.new_zeros(H, 1, C), p.new_zeros(1, C)
+        dh = p[1:] - p[:-1]
+        gh = torch.cat([zr, dh]) - torch.cat([dh, zr])
+        dw = p[:, 1:] - p[:, :-1]
+        gw = torch.cat([zc, dw], 1) - torch.cat([dw, zc], 1)
+        g_plane = ((2.0 * c[0]) * gh + (2.0 * c[1]) * gw) + c[2] * _sign0(p)
+        dt = l[1:] - l[:-1]
+        gt = torch.cat([zl, dt]) - torch.cat([dt, zl])
+        gram = p.new_zeros(C, C)
+        for r in range(R):
+            gram = gram + l[r][:, None] * l[r][None, :]
+        s = _sign0(gram)
+        go = p.new_zeros(R, C)
+        for j in range(C):
+            go = torch.where(comp != j, go + s[:, j][None, :] * l[:, j][:, None], go)
+        g_line = ((2.0 * c[3]) * gt + c[4] * _sign0(l)) + c[5] * go
+        table.plane(out, m).copy_(g_plane)
+        table.line(out, m).copy_(g_line)
+    return out
+
+
+def _vmreg_args(enc):
+    return enc.n_components, enc.table.c_res
+
+
+class _VMTermsFn(torch.autograd.Function):
+    """``terms`` in two launches (``nfa_vmreg_fwd``); the table gradient through :class:`_VMTermsBwdFn`, which reads the
+    Gram matrix's signs this pass leaves."""
+
+    @staticmethod
+    def forward(ctx, params, enc):
+        dev = B.require_device(params)
+        p = _aligned16(params)
+        C = enc.n_components
+        n_partials = B.load().nfa_vmreg_partials(*_vmreg_args(enc))   # (host arithmetic on the shape)
+        partials = torch.empty(n_partials, 4, dtype=torch.float32, device=dev)
+        signs = torch.empty(3, C, C, dtype=torch.float32, device=dev)
+        terms = torch.empty(3, 6, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            B.call("nfa_vmreg_fwd", B.ptr(p), *_vmreg_args(enc), B.ptr(partials), n_partials, B.ptr(signs), B.ptr(terms),
+                   B.stream())
+        ctx.enc = enc
+        ctx.save_for_backward(p, signs)
+        return terms
+
+    @staticmethod
+    def backward(ctx, g_terms):
+        if g_terms is None or not ctx.needs_input_grad[0]:
+            return None, None
+        p, signs = ctx.saved_tensors
+        return _VMTermsBwdFn.apply(p, g_terms.to(torch.float32).contiguous(), signs, ctx.enc), None
+
+
+class _VMTermsBwdFn(torch.autograd.Function):
+    """The backward as a function ``(params, g_terms, signs) -> g_params`` of its own, so that differentiating it again
+    fails with a message that names ``vm_terms`` instead of a missing ``grad_fn`` (as ``_PlaneTermsBwdFn`` does)."""
+
+    @staticmethod
+    def forward(ctx, p, g, signs, enc):
+        g_p = torch.empty_like(p)   # (every element is written)
+        with torch.cuda.device(p.device):
+            B.call("nfa_vmreg_bwd", B.ptr(p), *_vmreg_args(enc), B.ptr(g), B.ptr(signs), B.ptr(g_p), B.stream())
+        return g_p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gg_p):
+        raise NotImplementedError("vm_terms: the second order (differentiating dL/dparams again) is not implemented on the "
+                                  "native path; the torch path on CPU tensors is differentiated by autograd")
+
+
+def vm_terms(enc) -> Tensor:
+    """The six regularisation terms of every mode of a :class:`~nerfacc_amd.encodings.VMGridEncoding`: ``[3, 6]`` float32 on
+    ``enc.params``' device, ``(tv_h, tv_w, l1_plane, tv_line, l1_line, ortho)`` per mode.  With mode ``m``'s plane seen as
+    ``p[j, i, k]`` (``enc.plane(m)``: ``j < H`` rows, ``i < W``, ``k < C``) and its line as ``l[r, k]`` (``enc.line(m)``:
+    ``r < R``), each a mean:
+
+        tv_h     = sum (p[j+1,i,k] - p[j,i,k])^2 / (C (H-1) W)
+        tv_w     = sum (p[j,i+1,k] - p[j,i,k])^2 / (C H (W-1))
+        l1_plane = sum |p[j,i,k]| / (C H W)
+        tv_line  = sum (l[r+1,k] - l[r,k])^2 / (C (R-1))
+        l1_line  = sum |l[r,k]| / (C R)
+        ortho    = sum_{i<j} |G_ij| / (C (C-1) / 2),   G_ij = sum_r l[r,i] l[r,j]
+
+    The derivative of ``|v|`` is ``sign(v)``, 0 at ``v == 0``; that of ``ortho`` towards ``l[r,i]`` is
+    ``sum_{j != i} sign(G_ij) l[r,j] / (C (C-1) / 2)``.
+
+    In terms of TensoRF's ``TensorVMSplit``, on the ``[1, C, H, W]`` / ``[1, C, R, 1]`` views
+    (``plane(m).permute(2, 0, 1)[None]``, ``line(m).t()[None, :, :, None]``): ``TVLoss()`` of a plane is
+    ``2 (tv_h + tv_w)``, ``density_L1`` is ``sum_m (l1_plane + l1_line)`` and ``vector_comp_diffs`` is ``sum_m ortho`` (the
+    mean over the ordered off-diagonal pairs equals the mean over ``i < j``).  ``tv_line`` is this library's own term.
+    Nothing beyond these formulas is claimed.
+
+    Differentiable once towards ``enc.params``.  CUDA float32 parameters run on libnerfacc_hip.so (csrc/vmreg.hip: two
+    launches forward, one backward, no atomics, nothing read back from the device: the same bits on every run); anything
+    else (CPU tensors, other dtypes) runs the same formulas in torch and is differentiated by autograd."""
+    params = enc.params
+    if params.is_cuda and params.dtype == torch.float32:
+        return _VMTermsFn.apply(params, enc)
+    dt = torch.promote_types(params.dtype, torch.float32)
+    return _vm_terms_torch(params.to(dt), enc.table).to(torch.float32)
+
+
+_VM_WEIGHTS: dict = {}   # (the four weights, device) -> [3, 6]
+
+
+def _vm_weights(enc, tv: float, l1: float, tv_line: float, ortho: float) -> Tensor:
+    key = (tv, l1, tv_line, ortho, enc.params.device)
+    w = _VM_WEIGHTS.get(key)
+    if w is None:
+        w = _VM_WEIGHTS[key] = torch.tensor([[tv, tv, l1, tv_line, l1, ortho]] * 3, dtype=torch.float32, device=enc.params.device)
+    return w
+
+
+def vm_regularization(enc, tv: float = 0.0, l1: float = 0.0, tv_line: float = 0.0, ortho: float = 0.0) -> Tensor:
+    """The weighted sum of :func:`vm_terms` over the modes of ``enc``, a scalar:
+
+        sum_m [ tv (tv_h + tv_w) + l1 (l1_plane + l1_line) + tv_line tv_line + ortho ortho ]
+
+    In TensoRF's training loop, for a weight ``w`` each: ``TV_loss_density(TVLoss()) * w`` (and ``TV_loss_app``) is
+    ``tv = 0.02 * w``, because TensoRF multiplies the per-plane value by 1e-2 and that value is ``2 (tv_h + tv_w)``;
+    ``density_L1() * w`` is ``l1 = w``; ``vector_comp_diffs() * w`` is ``ortho = w`` -- each on the grid (density or
+    appearance) TensoRF applies it to.
+
+    It is ``vm_terms(enc)`` dotted with a constant weight tensor that is built once per (weights, device) and kept, so a call
+    makes no host-to-device copy after the first."""
+    return (vm_terms(enc) * _vm_weights(enc, float(tv), float(l1), float(tv_line), float(ortho))).sum()
