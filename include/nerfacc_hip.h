@@ -936,6 +936,31 @@ int nfa_vmreg_fwd(const float *params, int32_t n_components, const int32_t *res_
 int nfa_vmreg_bwd(const float *params, int32_t n_components, const int32_t *res_host, const float *grad_terms, const float *signs,
                   float *grad_params, nfa_stream_t stream);
 
+/* NeRF's sinusoidal (positional) encoding (ref: examples/radiance_fields/mlp.py, SinusoidalEncoder) of x [n_points, n_dims],
+ * n_dims D in 1..4, with the n_freqs L in 0..16 frequencies s_k = 2^(min_deg + k) (-16 <= min_deg, min_deg + L <= 32).  A row
+ * has K = (identity ? D : 0) + 2 L D columns in the reference's order: x (identity != 0; bitwise copies), then
+ * a_kd sin(s_k x_d) at column k D + d of the sine block, then a_kd cos(s_k x_d) in the same order;
+ * a_kd = w_k exp(-1/2 s_k^2 var[n, d]) with w = freq_weights [L] (device float32; NULL: 1) and var [n_points, D] (NULL:
+ * no factor; mip-NeRF's integrated encoding with a diagonal covariance).  The cosine is evaluated itself, not as the
+ * reference's sin(fl32(s_k x + pi/2)); sine, cosine and exp are the device library's accurate functions, float32 throughout.
+ * out / grad_out / grad_grad_out [n_points, K] hold elements of type `elem` (NFA_ELEM_*; rounded once as stored) and must be
+ * 16-byte aligned: they move as contiguous 16-byte (float32) or 8-byte (halves) pieces.  Everything else is float32.
+ * nfa_sinenc_bwd: grad_x [n_points, D] = g_id + sum_k s_k a_kd (g_sin cos - g_cos sin) and grad_var [n_points, D] =
+ * -1/2 sum_k s_k^2 (g_sin out_sin + g_cos out_cos), each optional, at least one (grad_var needs var).
+ * nfa_sinenc_bwd_bwd (no var): for gg_x [n_points, D], grad_grad_out (identity gg_x, sine gg_x s_k w_k cos, cosine
+ * -gg_x s_k w_k sin) and grad_x [n_points, D] = -gg_x sum_k s_k^2 w_k (g_sin sin + g_cos cos), each optional, at least one.
+ * Every sum runs in a fixed order in one lane: no atomics, bitwise reproducible; nothing is read back or allocated.
+ * The arguments are checked in this order, each with its own message, before any HIP call: elem, n_dims, n_freqs, min_deg,
+ * n_points (negative; above 2^31 - 1); then n_points == 0 (or K == 0) returns NFA_OK; then null pointers, alignment. */
+int nfa_sinenc_fwd(int32_t elem, const float *x, const float *var, const float *freq_weights, int64_t n_points, int32_t n_dims,
+                   int32_t min_deg, int32_t n_freqs, int32_t identity, void *out, nfa_stream_t stream);
+int nfa_sinenc_bwd(int32_t elem, const float *x, const float *var, const float *freq_weights, const void *grad_out, int64_t n_points,
+                   int32_t n_dims, int32_t min_deg, int32_t n_freqs, int32_t identity, float *grad_x, float *grad_var,
+                   nfa_stream_t stream);
+int nfa_sinenc_bwd_bwd(int32_t elem, const float *x, const float *freq_weights, const void *grad_out, const float *gg_x,
+                       int64_t n_points, int32_t n_dims, int32_t min_deg, int32_t n_freqs, int32_t identity, void *grad_grad_out,
+                       float *grad_x, nfa_stream_t stream);
+
 /* ------------------------------------------------------------------ sample positions */
 
 /* What every field does between sampling() and its encodings, in one pass over the samples.  Replaces the torch

@@ -155,6 +155,9 @@ _SIGS = {
     "nfa_vmreg_partials": [_i32, C.POINTER(_i32)],
     "nfa_vmreg_fwd": [_vp, _i32, C.POINTER(_i32), _vp, _i64, _vp, _vp, _vp],
     "nfa_vmreg_bwd": [_vp, _i32, C.POINTER(_i32), _vp, _vp, _vp, _vp],
+    "nfa_sinenc_fwd": [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp],
+    "nfa_sinenc_bwd": [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "nfa_sinenc_bwd_bwd": [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "nfa_sample_positions_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
     "nfa_sample_positions_bwd": [_vp] * 9 + [_i64, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "nfa_generate_rays_fwd": [_vp, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _f32, _i32,

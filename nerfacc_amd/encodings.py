@@ -10,6 +10,9 @@ Parameter layout compatibility with tcnn checkpoints is not a goal.
 dynamic scene) as one native pass each way (csrc/planes.hip); it shares ``out_dtype`` and the device rules below.
 ``VMGridEncoding`` is TensoRF's vector-matrix decomposition (three plane x line modes, concatenated for the appearance or
 summed for the density) with its grid resampling (csrc/vmgrid.hip), under the same rules.
+``SinusoidalEncoding`` is NeRF's positional encoding, the front end of the reference's MLP fields
+(``examples/radiance_fields/mlp.py``: ``SinusoidalEncoder``), with one native pass each for the forward, the backward and the
+second order (csrc/sinenc.hip); it has no parameters and is not reachable through ``encoding_from_tcnn_config``.
 
 CUDA float32 tensors run on libnerfacc_hip.so; CPU tensors and other dtypes run the same formulas in torch (the hash grid's
 torch path reproduces the native forward bit for bit).  Under ``torch.autocast`` both encodings run in float32, as tcnn's
@@ -36,7 +39,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _backend as B
 
-__all__ = ["HashGridEncoding", "SphericalHarmonicsEncoding", "PlaneGridEncoding", "VMGridEncoding", "encoding_from_tcnn_config"]
+__all__ = ["HashGridEncoding", "SphericalHarmonicsEncoding", "PlaneGridEncoding", "VMGridEncoding", "SinusoidalEncoding",
+           "barf_window", "encoding_from_tcnn_config"]
 
 _M32 = 0xFFFFFFFF
 _PRIMES = (1, 2654435761, 805459861, 3674653429)   # tcnn's hash primes of dimensions 0..3
@@ -938,6 +942,190 @@ class VMGridEncoding(nn.Module):
     def extra_repr(self) -> str:
         return (f"resolution={self.resolution}, n_components={self.n_components}, reduce={self.reduce!r}"
                 + (f", init_scale={self.init_scale}" if self.init_scale != 0.1 else "")
+                + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else ""))
+
+
+SIN_DIMS = (1, 2, 3, 4)   # input dimensions of the native sinusoidal encoding
+SIN_MAX_FREQS = 16
+
+
+def barf_window(alpha, n_freqs: int) -> Tensor:
+    """BARF's coarse-to-fine weights of ``n_freqs`` frequencies at progress ``alpha`` in [0, n_freqs] (Lin et al. 2021, eq. 14;
+    the Nerfies window is the same curve): ``w_k = (1 - cos(pi * clamp(alpha - k, 0, 1))) / 2`` as a float32 tensor, on
+    ``alpha``'s device when that is a tensor.  Hand it to ``SinusoidalEncoding.forward(..., freq_weights=w)``."""
+    alpha = torch.as_tensor(alpha, dtype=torch.float32)
+    k = torch.arange(int(n_freqs), dtype=torch.float32, device=alpha.device)
+    return (1.0 - torch.cos(math.pi * torch.clamp(alpha - k, 0.0, 1.0))) / 2.0
+
+
+def _sinusoidal_torch(x: Tensor, min_deg: int, max_deg: int, use_identity: bool = True, var: Tensor | None = None,
+                      freq_weights: Tensor | None = None) -> Tensor:
+    """The sinusoidal encoding in torch: the reference's formula literally (``sin`` of ``cat([xb, xb + 0.5 * pi])``; bit for
+    bit its ``SinusoidalEncoder`` without ``var`` and ``freq_weights``), both blocks times ``a = w_k exp(-0.5 s_k^2 var_d)``
+    where those are given."""
+    if max_deg == min_deg:
+        return x
+    L, D = max_deg - min_deg, x.shape[-1]
+    scales = torch.tensor([2.0 ** i for i in range(min_deg, max_deg)], dtype=x.dtype, device=x.device)
+    xb = torch.reshape(x[..., None, :] * scales[:, None], list(x.shape[:-1]) + [L * D])
+    latent = torch.sin(torch.cat([xb, xb + 0.5 * math.pi], dim=-1))
+    if var is not None or freq_weights is not None:
+        a = torch.ones(L, 1, dtype=x.dtype, device=x.device) if freq_weights is None else freq_weights.to(x.dtype)[:, None]
+        if var is not None:
+            a = a * torch.exp((-0.5 * (scales * scales))[:, None] * var[..., None, :])
+        a = torch.reshape(a.expand(*x.shape[:-1], L, D), list(x.shape[:-1]) + [L * D])
+        latent = latent * torch.cat([a, a], dim=-1)
+    if use_identity:
+        latent = torch.cat([x, latent], dim=-1)
+    return latent
+
+
+class _SinEncFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, var, fw, enc: "SinusoidalEncoding", dtype: torch.dtype):
+        B.require_device(x, var, fw)
+        N = x.shape[0]
+        y = torch.empty(N, enc.n_output_dims, dtype=dtype, device=x.device)
+        if N:
+            with torch.cuda.device(x.device):
+                B.call("nfa_sinenc_fwd", B.ELEM_CODES[dtype], B.ptr(x), B.ptr(var), B.ptr(fw), *enc._args(N), B.ptr(y), B.stream())
+        ctx.enc, ctx.dtype, ctx.has_var, ctx.has_fw = enc, dtype, var is not None, fw is not None
+        ctx.save_for_backward(x, *(t for t in (var, fw) if t is not None))
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        need_x, need_v = ctx.needs_input_grad[:2]
+        if g_y is None or not (need_x or need_v):
+            return None, None, None, None, None
+        x, *rest = ctx.saved_tensors
+        var = rest.pop(0) if ctx.has_var else None
+        fw = rest.pop(0) if ctx.has_fw else None
+        g_x, g_v = _SinEncBwdFn.apply(x, var, fw, _grad_as(g_y, ctx.dtype), ctx.enc, ctx.dtype, need_x, need_v)
+        return g_x, g_v, None, None, None
+
+
+class _SinEncBwdFn(torch.autograd.Function):
+    """The sinusoidal encoding's backward as a function ``(x, var, g_y) -> (g_x, g_var)``, so that ``g_x`` can be
+    differentiated again (``create_graph=True``: the Eikonal term of an SDF MLP).  Its own backward is one
+    ``nfa_sinenc_bwd_bwd`` call; with ``var`` there is no second order."""
+
+    @staticmethod
+    def forward(ctx, x, var, fw, g, enc: "SinusoidalEncoding", dtype: torch.dtype, need_x: bool, need_v: bool):
+        g_x = torch.empty_like(x) if need_x else None
+        g_v = torch.empty_like(var) if need_v else None
+        if x.shape[0]:
+            with torch.cuda.device(x.device):
+                B.call("nfa_sinenc_bwd", B.ELEM_CODES[dtype], B.ptr(x), B.ptr(var), B.ptr(fw), B.ptr(g), *enc._args(x.shape[0]),
+                       B.ptr(g_x), B.ptr(g_v), B.stream())
+        ctx.enc, ctx.dtype, ctx.has_var, ctx.has_fw = enc, dtype, var is not None, fw is not None
+        ctx.save_for_backward(x, g, *((fw,) if fw is not None else ()))
+        ctx.set_materialize_grads(False)
+        return g_x, g_v
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gg_x, gg_v):
+        if gg_x is None and gg_v is None:
+            return (None,) * 8
+        if ctx.has_var or gg_v is not None:
+            raise NotImplementedError("SinusoidalEncoding: the second order (differentiating dL/dx or dL/dvar again) is not "
+                                      "implemented with var; the torch path on CPU tensors is differentiated by autograd")
+        need_x, need_g = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+        if not (need_x or need_g):
+            return (None,) * 8
+        x, g, *rest = ctx.saved_tensors
+        fw = rest[0] if ctx.has_fw else None
+        v = gg_x.to(torch.float32).contiguous()
+        x2 = torch.empty_like(x) if need_x else None
+        gg_y = torch.empty_like(g) if need_g else None
+        if x.shape[0]:
+            with torch.cuda.device(x.device):
+                B.call("nfa_sinenc_bwd_bwd", B.ELEM_CODES[ctx.dtype], B.ptr(x), B.ptr(fw), B.ptr(g), B.ptr(v),
+                       *ctx.enc._args(x.shape[0]), B.ptr(gg_y), B.ptr(x2), B.stream())
+        return x2, None, None, gg_y, None, None, None, None
+
+
+class SinusoidalEncoding(nn.Module):
+    """NeRF's sinusoidal (positional) encoding, the reference's ``SinusoidalEncoder(x_dim, min_deg, max_deg, use_identity)``
+    (``examples/radiance_fields/mlp.py``) as one native pass each way (csrc/sinenc.hip):
+    ``forward(x[..., D]) -> [..., latent_dim]``, ``latent_dim = n_output_dims = (int(use_identity) + 2 L) D``,
+    ``L = max_deg - min_deg``.  Columns in the reference's order: ``x`` (when ``use_identity``; bitwise copies), then
+    ``sin(2^k x_d)`` at column ``(k - min_deg) D + d`` of the sine block, then the cosine block in the same order.
+    ``L == 0`` returns ``x`` itself whatever ``use_identity`` is, as the reference does.
+
+    ``n_input_dims`` D in 1..4, L in 0..16, ``-16 <= min_deg <= max_deg <= 32``.  No parameters.
+
+    ``forward(x, var=None, freq_weights=None)``.  ``freq_weights``: a float32 tensor of L per-frequency weights on ``x``'s
+    device; both blocks of frequency ``k`` are multiplied by ``w_k`` (BARF's coarse-to-fine schedule, see
+    :func:`barf_window`; the Nerfies window; FreeNeRF's frequency mask).  It is read through its pointer when the pass runs,
+    so a training loop can update it in place, also inside a captured step; it gets no gradient.  ``var``: a ``[..., D]``
+    diagonal variance in ``x``'s shape; both blocks are multiplied by ``exp(-0.5 4^k var_d)``, mip-NeRF's integrated
+    positional encoding (the identity columns are untouched).
+
+    CUDA float32 inputs run the native passes: float32 arithmetic with the device library's accurate ``sincosf`` / ``expf``,
+    the cosine evaluated itself (the reference's ``sin(x_b + pi/2)`` rounds the phase; the two differ by at most that
+    rounding, ``2^-22 max(1, |2^k x|)``).  Differentiable w.r.t. ``x`` and ``var``, bitwise reproducible, and w.r.t. ``x`` a
+    second time: ``torch.autograd.grad(y, x, g, create_graph=True)`` gives a ``dL/dx`` that can be differentiated towards
+    ``x`` and ``g`` (one native pass).  With ``var`` the second order raises ``NotImplementedError``.  CPU tensors and other
+    dtypes take the torch path, the reference's formula literally (bit for bit the reference), differentiated by autograd.
+    ``out_dtype`` as for :class:`HashGridEncoding`."""
+
+    def __init__(self, n_input_dims: int, min_deg: int, max_deg: int, use_identity: bool = True, out_dtype=None):
+        super().__init__()
+        self.out_dtype = _check_out_dtype(out_dtype)
+        if n_input_dims not in SIN_DIMS:
+            raise ValueError(f"SinusoidalEncoding: n_input_dims must be in 1..4 (got {n_input_dims})")
+        if not (isinstance(min_deg, int) and isinstance(max_deg, int) and -16 <= min_deg <= max_deg <= 32):
+            raise ValueError(f"SinusoidalEncoding: need integers -16 <= min_deg <= max_deg <= 32 (got min_deg={min_deg}, "
+                             f"max_deg={max_deg})")
+        if max_deg - min_deg > SIN_MAX_FREQS:
+            raise ValueError(f"SinusoidalEncoding: at most {SIN_MAX_FREQS} frequencies (got max_deg - min_deg = {max_deg - min_deg})")
+        self.n_input_dims, self.min_deg, self.max_deg = int(n_input_dims), min_deg, max_deg
+        self.use_identity = bool(use_identity)
+        self.n_freqs = max_deg - min_deg
+        self.n_output_dims = (int(self.use_identity) + 2 * self.n_freqs) * self.n_input_dims
+
+    latent_dim = property(lambda self: self.n_output_dims)
+
+    def _args(self, n_points: int):
+        return n_points, self.n_input_dims, self.min_deg, self.n_freqs, int(self.use_identity)
+
+    def forward(self, x: Tensor, var: Tensor | None = None, freq_weights: Tensor | None = None) -> Tensor:
+        D, L = self.n_input_dims, self.n_freqs
+        if x.shape[-1] != D:
+            raise ValueError(f"SinusoidalEncoding: x must have shape (..., {D}) (got {tuple(x.shape)})")
+        if var is not None and var.shape != x.shape:
+            raise ValueError(f"SinusoidalEncoding: var must have x's shape {tuple(x.shape)} (got {tuple(var.shape)})")
+        if freq_weights is not None:
+            if freq_weights.shape != (L,) or freq_weights.dtype != torch.float32:
+                raise ValueError(f"SinusoidalEncoding: freq_weights must be a float32 tensor of shape ({L},) (got "
+                                 f"{tuple(freq_weights.shape)}, {freq_weights.dtype})")
+            if freq_weights.device != x.device:
+                raise ValueError(f"SinusoidalEncoding: freq_weights must be on x's device {x.device} (got {freq_weights.device})")
+        if L == 0:
+            return x
+        out = _resolve_out_dtype(self.out_dtype, x)
+        x, ctx = _autocast_off(x)
+        with ctx:
+            lead = x.shape[:-1]
+            x2 = x.reshape(-1, D)
+            v2 = None if var is None else var.reshape(-1, D)
+            if x2.is_cuda and x2.dtype == torch.float32 and (v2 is None or (v2.dtype == torch.float32 and v2.device == x2.device)):
+                fw = None if freq_weights is None else freq_weights.detach().contiguous()
+                y = _SinEncFn.apply(x2.contiguous(), None if v2 is None else v2.contiguous(), fw, self, out)
+            else:
+                if v2 is not None:
+                    v2 = v2.to(x2.dtype)
+                y = _sinusoidal_torch(x2, self.min_deg, self.max_deg, self.use_identity, v2,
+                                      None if freq_weights is None else freq_weights.detach())
+                if self.out_dtype is not None:
+                    y = y.to(out)
+            return y.view(*lead, self.n_output_dims)
+
+    def extra_repr(self) -> str:
+        return (f"n_input_dims={self.n_input_dims}, min_deg={self.min_deg}, max_deg={self.max_deg}"
+                + ("" if self.use_identity else ", use_identity=False")
                 + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else ""))
 
 
