@@ -32,7 +32,8 @@ def hipcc() -> str | None:
 
 
 def _deps() -> list[str]:
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, h) for h in ("common.hip.h", "march.h", "walk_layout.h", "samples.h", "camera.h", "plane_layout.h", "axis.h")]
+    # every header under csrc/, so that a new one cannot be left out of the content hash
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")]
     hdr = os.path.join(INCLUDE, "nerfacc_hip.h")
     if os.path.exists(hdr):
         deps.append(hdr)

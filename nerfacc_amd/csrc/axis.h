@@ -1,6 +1,7 @@
 // axis.h -- the per-axis locate step of the dense grids sampled as grid_sample(padding_mode="border", align_corners=True)
-// samples them, and the element load / store of their activation streams; shared by planes.hip (the K-Planes plane grid)
-// and vmgrid.hip (the TensoRF vector-matrix grid), so both use one copy.
+// samples them, the bilinear taps of a plane and the linear ones of a line, and the element load / store of their activation
+// streams; shared by planes.hip (the K-Planes plane grid) and vmgrid.hip (the TensoRF vector-matrix grid), so both use one
+// copy.
 //
 // An axis of R >= 2 nodes, all arithmetic float32, every operation rounded on its own:
 //   p = x * (float)(R - 1)                                                  (locate_axis; locate_pos is given p itself)
@@ -8,6 +9,15 @@
 //   q = p >= 0 ? p : 0 (NaN gives 0), then q = q <= R - 1 ? q : R - 1      (fminf(fmaxf(p, 0), R - 1), -0 kept as it is)
 //   i = min((int)floorf(q), R - 2),   f = q - (float)i                     (f in [0, 1]; 1 only at the upper border)
 // i and i + 1 lie in [0, R - 1] for every input, NaN and +-inf included.
+//
+// A plane over the axes (a, b), a row-major [R_b, R_a] block of nodes of `stride` floats, and a line of such nodes; per
+// component j, corners k = k_a + 2 k_b in the order 0..3:
+//   w_k = (k_a ? f_a : 1 - f_a) * (k_b ? f_b : 1 - f_b),   T_k = table[((i_b + k_b) R_a + i_a + k_a) stride + j]
+//   plane_value  = sum_k w_k * T_k, summed from 0 in corner order
+//   line_value   = (0 + (1 - f) * l_0) + f * l_1
+//   plane_slopes: dv_a = (((0 - (1 - f_b) * T_0) + (1 - f_b) * T_1) - f_b * T_2) + f_b * T_3        (d plane_value / d f_a)
+//                 dv_b = (((0 - (1 - f_a) * T_0) - f_a * T_1) + (1 - f_a) * T_2) + f_a * T_3        (d plane_value / d f_b)
+// Index arithmetic is uint32 (a table holds fewer than 2^31 floats).
 #pragma once
 #include "common.hip.h"
 
@@ -33,6 +43,42 @@ __device__ __forceinline__ Axis locate_pos(float p, int32_t R)
     return a;
 }
 __device__ __forceinline__ Axis locate_axis(float x, int32_t R) { return locate_pos(x * (float)(R - 1), R); }
+
+// The 4 corners of a plane at float `base` around a point: the first float of each corner's node (component 0; planes.hip
+// folds its lane's component into `base` and loads component 0) and the corner weights.
+struct Taps {
+    uint32_t e[4];
+    float w[4];
+};
+__device__ __forceinline__ Taps plane_taps(uint32_t base, const Axis &a, const Axis &b, uint32_t Ra, uint32_t stride)
+{
+    Taps t;
+    const uint32_t e0 = base + (b.i * Ra + a.i) * stride;
+    t.e[0] = e0; t.e[1] = e0 + stride; t.e[2] = e0 + Ra * stride; t.e[3] = e0 + Ra * stride + stride;
+    const float wa0 = 1.0f - a.f, wb0 = 1.0f - b.f;
+    t.w[0] = wa0 * wb0; t.w[1] = a.f * wb0; t.w[2] = wa0 * b.f; t.w[3] = a.f * b.f;
+    return t;
+}
+// the corners' values of component j
+__device__ __forceinline__ void load_taps(const float *__restrict__ table, const Taps &t, uint32_t j, float (&T)[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) T[k] = table[t.e[k] + j];
+}
+__device__ __forceinline__ float plane_value(const float (&w)[4], const float (&T)[4])
+{
+    float v = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v = v + w[k] * T[k];
+    return v;
+}
+__device__ __forceinline__ float line_value(float f, float l0, float l1) { return (0.0f + (1.0f - f) * l0) + f * l1; }
+__device__ __forceinline__ void plane_slopes(float fa, float fb, const float (&T)[4], float &dva, float &dvb)
+{
+    const float wa0 = 1.0f - fa, wb0 = 1.0f - fb;
+    dva = (((0.0f - wb0 * T[0]) + wb0 * T[1]) - fb * T[2]) + fb * T[3];
+    dvb = (((0.0f - wa0 * T[0]) - fa * T[1]) + wa0 * T[2]) + fa * T[3];
+}
 
 template <class E>
 __device__ __forceinline__ void store_elem(E *p, float v)

@@ -11,7 +11,7 @@
 // the locate step is axis.h's (border clamp, NaN -> node 0, the `in` flag, i <= R - 2, f in [0, 1]).  Per mode and
 // component j, with P the mode's plane and Ln its line:
 //   w_k = (k_a ? f_a : 1 - f_a) * (k_b ? f_b : 1 - f_b),  corners k = k_a + 2 k_b in the order 0..3
-//   pv[j] = sum_k w_k * P[((i_b + k_b) R_a + i_a + k_a) C + j], summed from 0 in corner order        (as planes.hip)
+//   pv[j] = sum_k w_k * P[((i_b + k_b) R_a + i_a + k_a) C + j], summed from 0 in corner order  (axis.h's plane_value)
 //   lv[j] = (0 + (1 - f_c) * Ln[i_c C + j]) + f_c * Ln[(i_c + 1) C + j]
 //   t_m[j] = pv[j] * lv[j]
 // which is F.grid_sample(mode="bilinear", padding_mode="border", align_corners=True) of the [1, C, R_b, R_a] plane and of
@@ -28,7 +28,7 @@
 //   gk = g[j] * lv[j],  gl = g[j] * pv[j]
 //   plane gradient:  G[corner k][j] += w_k * gk        (no-return global_atomic_add_f32 into a zeroed float32 gradient)
 //   line gradient:   G[i_c][j] += (1 - f_c) * gl,  G[i_c + 1][j] += f_c * gl                              (see below)
-//   dv_a, dv_b as in planes.hip (d pv / d f_a, d pv / d f_b, corner order);  dl = L_1 - L_0
+//   dv_a, dv_b = axis.h's plane_slopes (d pv / d f_a, d pv / d f_b, corner order);  dl = L_1 - L_0
 //   t_a += gk * dv_a,  t_b += gk * dv_b,  t_c += gl * dl, over the lane's components in ascending order, from 0
 //   share_d = in_d ? t_d * (float)(R_d - 1) : 0, summed over the L lanes by the xor butterfly
 //   dL/dx[n, d] = ((share_d of mode 0) + share_d of mode 1) + share_d of mode 2
@@ -59,47 +59,13 @@
 // contiguous.  Each axis has its own R and R': up, down or unchanged.  At R' = R, p = i' exactly and a node copies its
 // source (finite values; the sum from 0 turns a -0 into +0).
 #include "common.hip.h"
-#include "axis.h"   // Axis, locate_axis / locate_pos, store_elem / load_elem (shared with planes.hip)
+#include "axis.h"        // Axis, locate_axis / locate_pos, the taps, store_elem / load_elem (shared with planes.hip)
+#include "vm_layout.h"   // vm_a / vm_b / vm_c, VMDesc, vm_check_c, vm_layout (shared with vmreg.hip)
 
 namespace nfa {
 
 #define NFA_VM_LDS_BYTES 65536   // the line copy a workgroup of the backward may keep in LDS
 #define NFA_VM_BWD_BLOCK 512
-
-__host__ __device__ constexpr int vm_a(int m) { return m < 2 ? 0 : 1; }
-__host__ __device__ constexpr int vm_b(int m) { return m == 0 ? 1 : 2; }
-__host__ __device__ constexpr int vm_c(int m) { return 2 - m; }
-
-struct VMDesc {
-    int32_t res[3];
-    uint32_t plane[3], line[3];   // first float of mode m's plane and line
-    int32_t C;
-};
-
-// One mode around a point: the first floats of the 4 plane corners and of the lower line node (component 0), and the
-// corner weights.
-struct VMTaps {
-    uint32_t e[4], el;
-    float w[4];
-};
-__device__ __forceinline__ VMTaps vm_taps(const VMDesc &V, int m, const Axis &a, const Axis &b, const Axis &c, uint32_t Ra)
-{
-    VMTaps t;
-    const uint32_t C = (uint32_t)V.C, e0 = V.plane[m] + (b.i * Ra + a.i) * C;
-    t.e[0] = e0; t.e[1] = e0 + C; t.e[2] = e0 + Ra * C; t.e[3] = e0 + Ra * C + C;
-    t.el = V.line[m] + c.i * C;
-    const float wa0 = 1.0f - a.f, wb0 = 1.0f - b.f;
-    t.w[0] = wa0 * wb0; t.w[1] = a.f * wb0; t.w[2] = wa0 * b.f; t.w[3] = a.f * b.f;
-    return t;
-}
-__device__ __forceinline__ float plane_value(const float (&w)[4], const float (&T)[4])
-{
-    float v = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v = v + w[k] * T[k];
-    return v;
-}
-__device__ __forceinline__ float line_value(float f, float l0, float l1) { return (0.0f + (1.0f - f) * l0) + f * l1; }
 
 // Forward: L lanes per point, the modes and the lane's components in loops.
 template <int L, int RED, class E>
@@ -119,12 +85,12 @@ __global__ __launch_bounds__(256) void vmgrid_fwd_kernel(const float *__restrict
 #pragma unroll
         for (int m = 0; m < 3; ++m) {
             const Axis &c = ax[vm_c(m)];
-            const VMTaps t = vm_taps(V, m, ax[vm_a(m)], ax[vm_b(m)], c, (uint32_t)V.res[vm_a(m)]);
+            const Taps t = plane_taps(V.plane[m], ax[vm_a(m)], ax[vm_b(m)], (uint32_t)V.res[vm_a(m)], (uint32_t)C);
+            const uint32_t el = V.line[m] + c.i * (uint32_t)C;   // the lower line node, component 0
             for (int j = l; j < C; j += L) {
                 float T[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) T[k] = params[t.e[k] + (uint32_t)j];
-                const float l0 = params[t.el + (uint32_t)j], l1 = params[t.el + (uint32_t)(C + j)];
+                load_taps(params, t, (uint32_t)j, T);
+                const float l0 = params[el + (uint32_t)j], l1 = params[el + (uint32_t)(C + j)];
                 const float term = plane_value(t.w, T) * line_value(c.f, l0, l1);
                 if constexpr (RED == NFA_VM_CONCAT) {
                     if (valid) store_elem(y + n * (3 * C) + (m * C + j), term);
@@ -165,16 +131,16 @@ __global__ __launch_bounds__(NFA_VM_BWD_BLOCK) void vmgrid_bwd_kernel(const floa
             const int64_t n = valid ? base + lp : n_points - 1;
             const Axis a = locate_axis(x[n * 3 + da], V.res[da]), b = locate_axis(x[n * 3 + db], V.res[db]),
                        c = locate_axis(x[n * 3 + dc], V.res[dc]);
-            const VMTaps t = vm_taps(V, m, a, b, c, (uint32_t)V.res[da]);
-            const float wa0 = 1.0f - a.f, wb0 = 1.0f - b.f, wc0 = 1.0f - c.f;
+            const Taps t = plane_taps(V.plane[m], a, b, (uint32_t)V.res[da], (uint32_t)C);
+            const uint32_t el = V.line[m] + c.i * (uint32_t)C;   // the lower line node, component 0
+            const float wc0 = 1.0f - c.f;
             const E *g_row = RED == NFA_VM_CONCAT ? g_y + n * (3 * C) + m * C : g_y + n;
             float ta = 0.0f, tb = 0.0f, tc = 0.0f;
             for (int j = l; j < C; j += L) {
                 const float g = load_elem(RED == NFA_VM_CONCAT ? g_row + j : g_row);
                 float T[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) T[k] = params[t.e[k] + (uint32_t)j];
-                const float l0 = params[t.el + (uint32_t)j], l1 = params[t.el + (uint32_t)(C + j)];
+                load_taps(params, t, (uint32_t)j, T);
+                const float l0 = params[el + (uint32_t)j], l1 = params[el + (uint32_t)(C + j)];
                 const float pv = plane_value(t.w, T), lv = line_value(c.f, l0, l1);
                 const float gk = g * lv, gl = g * pv;
                 if (g_params != nullptr && valid) {
@@ -185,13 +151,13 @@ __global__ __launch_bounds__(NFA_VM_BWD_BLOCK) void vmgrid_bwd_kernel(const floa
                         __hip_atomic_fetch_add(acc, wc0 * gl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         __hip_atomic_fetch_add(acc + C, c.f * gl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     } else {
-                        unsafeAtomicAdd(g_params + (t.el + (uint32_t)j), wc0 * gl);
-                        unsafeAtomicAdd(g_params + (t.el + (uint32_t)(C + j)), c.f * gl);
+                        unsafeAtomicAdd(g_params + (el + (uint32_t)j), wc0 * gl);
+                        unsafeAtomicAdd(g_params + (el + (uint32_t)(C + j)), c.f * gl);
                     }
                 }
                 if (g_x != nullptr) {
-                    const float dva = (((0.0f - wb0 * T[0]) + wb0 * T[1]) - b.f * T[2]) + b.f * T[3];
-                    const float dvb = (((0.0f - wa0 * T[0]) - a.f * T[1]) + wa0 * T[2]) + a.f * T[3];
+                    float dva, dvb;
+                    plane_slopes(a.f, b.f, T, dva, dvb);
                     ta = ta + gk * dva;
                     tb = tb + gk * dvb;
                     tc = tc + gl * (l1 - l0);
@@ -245,10 +211,9 @@ __global__ __launch_bounds__(256) void vmgrid_resample_kernel(const float *__res
             const uint32_t rel = e - R.dst.plane[m], node = rel / C, j = rel % C, Wd = (uint32_t)R.dst.res[da];
             const Axis a = locate_pos((float)(node % Wd) * R.scale[da], R.src.res[da]);
             const Axis b = locate_pos((float)(node / Wd) * R.scale[db], R.src.res[db]);
-            const VMTaps t = vm_taps(R.src, m, a, b, a, (uint32_t)R.src.res[da]);   // (the line tap is not used)
+            const Taps t = plane_taps(R.src.plane[m], a, b, (uint32_t)R.src.res[da], C);
             float T[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) T[k] = src[t.e[k] + j];
+            load_taps(src, t, j, T);
             v = plane_value(t.w, T);
         }
         dst[e] = v;
@@ -256,33 +221,6 @@ __global__ __launch_bounds__(256) void vmgrid_resample_kernel(const float *__res
 }
 
 // ---------------------------------------------------------------- host side
-// The checks of a component count and a resolution table, in this order (C; null; a resolution below 2; the size limit),
-// and the blocks' offsets.  `what` names the table in the messages ("" for the one table of the forward and backward).
-static int vm_check_c(const char *name, int32_t C)
-{
-    NFA_REQUIRE(C >= 4 && C <= 96 && C % 4 == 0, "%s: n_components must be a multiple of 4 in 4..96 (got %d)", name, C);
-    return NFA_OK;
-}
-static int vm_layout(const char *name, const char *what, int32_t C, const int32_t *res_host, VMDesc &V, int64_t &total)
-{
-    V = {};
-    V.C = C;
-    for (int d = 0; d < 3; ++d) {
-        NFA_REQUIRE(res_host[d] >= 2, "%s: %saxis %d resolution %d is below 2", name, what, d, res_host[d]);
-        V.res[d] = res_host[d];
-    }
-    const int64_t limit = (int64_t)1 << 31;
-    total = 0;
-    for (int m = 0; m < 3; ++m) {
-        const int64_t cells = (int64_t)V.res[vm_a(m)] * V.res[vm_b(m)] + V.res[vm_c(m)];   // (< 2^62 + 2^31)
-        NFA_REQUIRE(cells < limit && total + cells * C < limit, "%s: too many %sparameters (at most 2^31 - 1 floats)", name, what);
-        V.plane[m] = (uint32_t)total;
-        V.line[m] = (uint32_t)(total + (int64_t)V.res[vm_a(m)] * V.res[vm_b(m)] * C);
-        total += cells * C;
-    }
-    return NFA_OK;
-}
-
 struct VMArgs {
     int32_t reduce, elem;
     int64_t n_points;

@@ -513,44 +513,55 @@ class PlaneTable:
         self.c_res = (ctypes.c_int32 * len(flat))(*flat)
 
 
+def _locate_nodes(p: Tensor, R: int):
+    """axis.h's locate_pos for node coordinates ``p`` among ``R`` nodes: (i, f), i int64 in [0, R - 2], f in [0, 1]."""
+    rm1 = float(R - 1)
+    q = torch.where(p >= 0, p, torch.zeros_like(p))        # (NaN gives 0: `where`, not `maximum`)
+    q = torch.where(q <= rm1, q, torch.full_like(q, rm1))
+    i = torch.floor(q.detach()).to(torch.int64).clamp(max=R - 2)
+    return i, q - i.to(q.dtype)
+
+
+def _plane_value(plane: Tensor, Ra: int, ia, fa, ib, fb) -> Tensor:
+    """axis.h's plane_value, the 4-tap sum of csrc/planes.hip and csrc/vmgrid.hip, on a ``[R_b * R_a, C]`` plane: corner
+    order, from 0."""
+    row = ib * Ra + ia
+    v = torch.zeros(ia.shape[0], plane.shape[1], dtype=plane.dtype, device=plane.device)
+    for k in range(4):
+        ka, kb = k & 1, k >> 1
+        w = (fa if ka else 1.0 - fa) * (fb if kb else 1.0 - fb)
+        v = v + w[:, None] * plane[row + (kb * Ra + ka)]
+    return v
+
+
 def _planegrid_torch(x: Tensor, params: Tensor, t: PlaneTable, reduce: int = 0) -> Tensor:
     """The plane grid in torch, op for op as csrc/planes.hip computes it (x [N, D], D = ``t.n_dims``, and params in one
     float dtype); ``reduce``: a ``B.PLANE_REDUCE_CODES`` value."""
-    F, D = t.n_features, t.n_dims
+    F = t.n_features
     outs = []
     for s, res in enumerate(t.res):
-        cell = []
-        for d in range(D):
-            rm1 = float(res[d] - 1)
-            p = x[:, d] * rm1
-            q = torch.where(p >= 0, p, torch.zeros_like(p))        # (NaN gives 0: `where`, not `maximum`)
-            q = torch.where(q <= rm1, q, torch.full_like(q, rm1))
-            i = torch.floor(q.detach()).to(torch.int64).clamp(max=res[d] - 2)
-            cell.append((i, q - i.to(q.dtype)))
+        cell = [_locate_nodes(x[:, d] * float(res[d] - 1), res[d]) for d in range(t.n_dims)]
         out = None
         for k, (a, b) in enumerate(t.planes):
             plane = params[t.offsets[s][k]: t.offsets[s][k] + t.sizes[s][k]].view(-1, F)
-            (ia, fa), (ib, fb) = cell[a], cell[b]
-            row = ib * res[a] + ia
-            v = torch.zeros(x.shape[0], F, dtype=x.dtype, device=x.device)
-            for c in range(4):
-                ca, cb = c & 1, c >> 1
-                w = (fa if ca else 1.0 - fa) * (fb if cb else 1.0 - fb)
-                v = v + w[:, None] * plane[row + (cb * res[a] + ca)]
+            v = _plane_value(plane, res[a], *cell[a], *cell[b])
             out = v if out is None else (out + v if reduce else out * v)
         outs.append(out)
     return torch.cat(outs, -1)
 
 
-class _PlaneGridFn(torch.autograd.Function):
+class _GridFn(torch.autograd.Function):
+    """The native pass of a :class:`PlaneGridEncoding` or a :class:`VMGridEncoding`: ``enc._entries`` names its forward
+    and backward entry, ``enc._lead`` / ``enc._table_args`` give their arguments around the pointers."""
+
     @staticmethod
-    def forward(ctx, x, params, enc: "PlaneGridEncoding", dtype: torch.dtype):
+    def forward(ctx, x, params, enc, dtype: torch.dtype):
         B.require_device(x, params)
         N = x.shape[0]
         y = torch.empty(N, enc.n_output_dims, dtype=dtype, device=x.device)
         if N:
             with torch.cuda.device(x.device):
-                B.call("nfa_planegrid_fwd", *enc._lead(dtype), B.ptr(x), B.ptr(params), *enc._table_args(N), B.ptr(y), B.stream())
+                B.call(enc._entries[0], *enc._lead(dtype), B.ptr(x), B.ptr(params), *enc._table_args(N), B.ptr(y), B.stream())
         ctx.enc, ctx.dtype = enc, dtype
         ctx.save_for_backward(x, params)
         return y
@@ -561,30 +572,32 @@ class _PlaneGridFn(torch.autograd.Function):
         if g_y is None or not (need_x or need_p):
             return None, None, None, None
         x, params = ctx.saved_tensors
-        g_x, g_p = _PlaneGridBwdFn.apply(x, params, _grad_as(g_y, ctx.dtype), ctx.enc, ctx.dtype, need_x, need_p)
+        g_x, g_p = _GridBwdFn.apply(x, params, _grad_as(g_y, ctx.dtype), ctx.enc, ctx.dtype, need_x, need_p)
         return g_x, g_p, None, None
 
 
-class _PlaneGridBwdFn(torch.autograd.Function):
-    """The plane grid's backward as a function ``(x, params, g_y) -> (g_x, g_params)`` of its own, so that differentiating
-    it again (``create_graph=True``) fails with a message that names the encoding instead of a missing ``grad_fn``."""
+class _GridBwdFn(torch.autograd.Function):
+    """The grid's backward as a function ``(x, params, g_y) -> (g_x, g_params)`` of its own, so that differentiating it
+    again (``create_graph=True``) fails with a message that names the encoding instead of a missing ``grad_fn``."""
 
     @staticmethod
-    def forward(ctx, x, params, g, enc: "PlaneGridEncoding", dtype: torch.dtype, need_x: bool, need_p: bool):
+    def forward(ctx, x, params, g, enc, dtype: torch.dtype, need_x: bool, need_p: bool):
         g_p = torch.zeros_like(params) if need_p else None
         g_x = torch.empty_like(x) if need_x else None
         if x.shape[0]:
             with torch.cuda.device(x.device):
-                B.call("nfa_planegrid_bwd", *enc._lead(dtype), B.ptr(x), B.ptr(params), B.ptr(g),
-                       *enc._table_args(x.shape[0]), B.ptr(g_p), B.ptr(g_x), B.stream())
+                B.call(enc._entries[1], *enc._lead(dtype), B.ptr(x), B.ptr(params), B.ptr(g), *enc._table_args(x.shape[0]),
+                       B.ptr(g_p), B.ptr(g_x), B.stream())
+        ctx.enc = enc
         ctx.set_materialize_grads(False)
         return g_x, g_p
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gg_x, gg_p):
-        raise NotImplementedError("PlaneGridEncoding: the second order (differentiating dL/dx or dL/dparams again) is not "
-                                  "implemented on the native path; the torch path on CPU tensors is differentiated by autograd")
+        raise NotImplementedError(f"{type(ctx.enc).__name__}: the second order (differentiating dL/dx or dL/dparams again) is "
+                                  "not implemented on the native path; the torch path on CPU tensors is differentiated by "
+                                  "autograd")
 
 
 class PlaneGridEncoding(nn.Module):
@@ -649,6 +662,8 @@ class PlaneGridEncoding(nn.Module):
     offsets = property(lambda self: [list(o) for o in self.table.offsets])
     sizes = property(lambda self: [list(z) for z in self.table.sizes])
 
+    _entries = ("nfa_planegrid_fwd", "nfa_planegrid_bwd")
+
     def plane(self, s: int, k: int) -> Tensor:
         """Plane ``k`` of scale ``s`` as a ``[R_b, R_a, F]`` view of ``params``."""
         t = self.table
@@ -671,7 +686,7 @@ class PlaneGridEncoding(nn.Module):
             x2 = x.reshape(-1, D)
             p = self.params
             if x2.is_cuda and x2.dtype == torch.float32 and p.dtype == torch.float32 and p.device == x2.device:
-                y = _PlaneGridFn.apply(x2.contiguous(), p, self, out)   # (element-wise access: no alignment beyond 4 bytes)
+                y = _GridFn.apply(x2.contiguous(), p, self, out)   # (element-wise access: no alignment beyond 4 bytes)
             else:
                 dt = torch.promote_types(x2.dtype, p.dtype)
                 y = _planegrid_torch(x2.to(dt), p.to(dt), self.table, B.PLANE_REDUCE_CODES[self.reduce])
@@ -724,26 +739,6 @@ class VMTable:
         return params[o: o + self.line_sizes[m]].view(self.res[VM_MODES[m][2]], self.n_components)
 
 
-def _locate_nodes(p: Tensor, R: int):
-    """axis.h's locate_pos for node coordinates ``p`` among ``R`` nodes: (i, f), i int64 in [0, R - 2], f in [0, 1]."""
-    rm1 = float(R - 1)
-    q = torch.where(p >= 0, p, torch.zeros_like(p))        # (NaN gives 0: `where`, not `maximum`)
-    q = torch.where(q <= rm1, q, torch.full_like(q, rm1))
-    i = torch.floor(q.detach()).to(torch.int64).clamp(max=R - 2)
-    return i, q - i.to(q.dtype)
-
-
-def _vm_plane_value(plane: Tensor, Ra: int, ia, fa, ib, fb) -> Tensor:
-    """The 4-tap sum of csrc/planes.hip / csrc/vmgrid.hip on a ``[R_b * R_a, C]`` plane, corner order, from 0."""
-    row = ib * Ra + ia
-    v = torch.zeros(ia.shape[0], plane.shape[1], dtype=plane.dtype, device=plane.device)
-    for k in range(4):
-        ka, kb = k & 1, k >> 1
-        w = (fa if ka else 1.0 - fa) * (fb if kb else 1.0 - fb)
-        v = v + w[:, None] * plane[row + (kb * Ra + ka)]
-    return v
-
-
 def _vm_line_value(line: Tensor, ic, fc) -> Tensor:
     """``(0 + (1 - f) L[i]) + f L[i + 1]`` on a ``[R_c, C]`` line."""
     v = torch.zeros(ic.shape[0], line.shape[1], dtype=line.dtype, device=line.device)
@@ -758,7 +753,7 @@ def _vmgrid_torch(x: Tensor, params: Tensor, t: VMTable, reduce: int = 0) -> Ten
     cell = [_locate_nodes(x[:, d] * float(t.res[d] - 1), t.res[d]) for d in range(3)]
     terms = []
     for m, (a, b, c) in enumerate(VM_MODES):
-        pv = _vm_plane_value(t.plane(params, m).view(-1, C), t.res[a], *cell[a], *cell[b])
+        pv = _plane_value(t.plane(params, m).view(-1, C), t.res[a], *cell[a], *cell[b])
         terms.append(pv * _vm_line_value(t.line(params, m), *cell[c]))
     if not reduce:
         return torch.cat(terms, -1)
@@ -789,54 +784,9 @@ def _vm_resample_torch(params: Tensor, src: VMTable, dst: VMTable) -> Tensor:
     for m, (a, b, c) in enumerate(VM_MODES):
         ia, fa = (v.repeat(dst.res[b]) for v in cell[a])               # node (i'_b, i'_a), row-major: a runs fastest
         ib, fb = (v.repeat_interleave(dst.res[a]) for v in cell[b])
-        out.append(_vm_plane_value(src.plane(params, m).view(-1, C), src.res[a], ia, fa, ib, fb).reshape(-1))
+        out.append(_plane_value(src.plane(params, m).view(-1, C), src.res[a], ia, fa, ib, fb).reshape(-1))
         out.append(_vm_line_value(src.line(params, m), *cell[c]).reshape(-1))
     return torch.cat(out)
-
-
-class _VMGridFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, params, enc: "VMGridEncoding", dtype: torch.dtype):
-        B.require_device(x, params)
-        N = x.shape[0]
-        y = torch.empty(N, enc.n_output_dims, dtype=dtype, device=x.device)
-        if N:
-            with torch.cuda.device(x.device):
-                B.call("nfa_vmgrid_fwd", *enc._lead(dtype), B.ptr(x), B.ptr(params), *enc._table_args(N), B.ptr(y), B.stream())
-        ctx.enc, ctx.dtype = enc, dtype
-        ctx.save_for_backward(x, params)
-        return y
-
-    @staticmethod
-    def backward(ctx, g_y):
-        need_x, need_p = ctx.needs_input_grad[:2]
-        if g_y is None or not (need_x or need_p):
-            return None, None, None, None
-        x, params = ctx.saved_tensors
-        g_x, g_p = _VMGridBwdFn.apply(x, params, _grad_as(g_y, ctx.dtype), ctx.enc, ctx.dtype, need_x, need_p)
-        return g_x, g_p, None, None
-
-
-class _VMGridBwdFn(torch.autograd.Function):
-    """The VM grid's backward as a function ``(x, params, g_y) -> (g_x, g_params)`` of its own, so that differentiating it
-    again (``create_graph=True``) fails with a message that names the encoding instead of a missing ``grad_fn``."""
-
-    @staticmethod
-    def forward(ctx, x, params, g, enc: "VMGridEncoding", dtype: torch.dtype, need_x: bool, need_p: bool):
-        g_p = torch.zeros_like(params) if need_p else None
-        g_x = torch.empty_like(x) if need_x else None
-        if x.shape[0]:
-            with torch.cuda.device(x.device):
-                B.call("nfa_vmgrid_bwd", *enc._lead(dtype), B.ptr(x), B.ptr(params), B.ptr(g), *enc._table_args(x.shape[0]),
-                       B.ptr(g_p), B.ptr(g_x), B.stream())
-        ctx.set_materialize_grads(False)
-        return g_x, g_p
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gg_x, gg_p):
-        raise NotImplementedError("VMGridEncoding: the second order (differentiating dL/dx or dL/dparams again) is not "
-                                  "implemented on the native path; the torch path on CPU tensors is differentiated by autograd")
 
 
 class VMGridEncoding(nn.Module):
@@ -889,6 +839,8 @@ class VMGridEncoding(nn.Module):
     offsets = property(lambda self: [[p, l] for p, l in zip(self.table.plane_offsets, self.table.line_offsets)])
     sizes = property(lambda self: [[p, l] for p, l in zip(self.table.plane_sizes, self.table.line_sizes)])
 
+    _entries = ("nfa_vmgrid_fwd", "nfa_vmgrid_bwd")
+
     def plane(self, m: int) -> Tensor:
         """The plane of mode ``m`` as a ``[R_b, R_a, C]`` view of ``params``."""
         return self.table.plane(self.params, m)
@@ -912,7 +864,7 @@ class VMGridEncoding(nn.Module):
             x2 = x.reshape(-1, 3)
             p = self.params
             if x2.is_cuda and x2.dtype == torch.float32 and p.dtype == torch.float32 and p.device == x2.device:
-                y = _VMGridFn.apply(x2.contiguous(), p, self, out)   # (element-wise access: no alignment beyond 4 bytes)
+                y = _GridFn.apply(x2.contiguous(), p, self, out)   # (element-wise access: no alignment beyond 4 bytes)
             else:
                 dt = torch.promote_types(x2.dtype, p.dtype)
                 y = _vmgrid_torch(x2.to(dt), p.to(dt), self.table, B.VM_REDUCE_CODES[self.reduce])

@@ -192,6 +192,21 @@ def _plane_terms_torch(params: Tensor, table) -> Tensor:
     return torch.stack(rows).view(len(table.res), len(table.planes), 4)
 
 
+def _sign0(v: Tensor) -> Tensor:
+    """1, -1, and ``v`` itself where it is neither above nor below 0 (0 at 0; NaN stays NaN): csrc/plane_tiles.h's ``sign0``."""
+    return torch.where(v > 0, torch.ones_like(v), torch.where(v < 0, -torch.ones_like(v), v))
+
+
+def _tv_stencils(p: Tensor):
+    """``(gh, gw)`` of an ``[H, W, F]`` plane as csrc/plane_tiles.h's backward row walk forms them: ``A - B`` of the
+    differences towards the previous and the next row (node), a literal 0 where that row (node) does not exist."""
+    H, W, F = p.shape
+    zr, zc = p.new_zeros(1, W, F), p.new_zeros(H, 1, F)
+    dh = p[1:] - p[:-1]
+    dw = p[:, 1:] - p[:, :-1]
+    return torch.cat([zr, dh]) - torch.cat([dh, zr]), torch.cat([zc, dw], 1) - torch.cat([dw, zc], 1)
+
+
 def _plane_terms_grad_torch(params: Tensor, grad_terms: Tensor, table) -> Tensor:
     """``d (grad_terms . terms) / d params`` in float32, operation for operation as ``nfa_planereg_bwd`` forms it (the
     stencils and their order: csrc/planereg.hip's header), so the two agree bit for bit."""
@@ -202,18 +217,13 @@ def _plane_terms_grad_torch(params: Tensor, grad_terms: Tensor, table) -> Tensor
         p = p32[off: off + size].view(H, W, F)
         inv = torch.tensor([1.0 / c if c else 0.0 for c in _plane_counts(H, W, F, time)], dtype=torch.float32, device=p.device)
         c = g32[n] * inv
-        zr, zc = p.new_zeros(1, W, F), p.new_zeros(H, 1, F)
-        dh = p[1:] - p[:-1]
-        gh = torch.cat([zr, dh]) - torch.cat([dh, zr])
-        dw = p[:, 1:] - p[:, :-1]
-        gw = torch.cat([zc, dw], 1) - torch.cat([dw, zc], 1)
+        gh, gw = _tv_stencils(p)
         g = (2.0 * c[0]) * gh + (2.0 * c[1]) * gw
         if time:
+            zr, dh = p.new_zeros(1, W, F), p[1:] - p[:-1]
             d2 = dh[1:] - dh[:-1]
             gs = (torch.cat([zr, zr, d2]) - 2.0 * torch.cat([zr, d2, zr])) + torch.cat([d2, zr, zr])
-            d = p - 1.0
-            sg = torch.where(d > 0, torch.ones_like(d), torch.where(d < 0, -torch.ones_like(d), d))
-            g = (g + (2.0 * c[2]) * gs) + c[3] * sg
+            g = (g + (2.0 * c[2]) * gs) + c[3] * _sign0(p - 1.0)
         out[off: off + size] = g.reshape(-1)
     return out
 
@@ -249,7 +259,7 @@ class _PlaneTermsFn(torch.autograd.Function):
 
 class _PlaneTermsBwdFn(torch.autograd.Function):
     """The backward as a function ``(params, g_terms) -> g_params`` of its own, so that differentiating it again fails with
-    a message that names ``plane_terms`` instead of a missing ``grad_fn`` (as ``_PlaneGridBwdFn`` does)."""
+    a message that names ``plane_terms`` instead of a missing ``grad_fn`` (as ``encodings._GridBwdFn`` does)."""
 
     @staticmethod
     def forward(ctx, p, g, enc):
@@ -347,11 +357,6 @@ def _vm_terms_torch(params: Tensor, table) -> Tensor:
     return torch.stack(rows)
 
 
-def _sign0(v: Tensor) -> Tensor:
-    """1, -1, and ``v`` itself where it is neither above nor below 0 (0 at 0; NaN stays NaN): csrc/vmreg.hip's ``vr_sign``."""
-    return torch.where(v > 0, torch.ones_like(v), torch.where(v < 0, -torch.ones_like(v), v))
-
-
 def _vm_terms_grad_torch(params: Tensor, grad_terms: Tensor, table) -> Tensor:
     """``d (grad_terms . terms) / d params`` in float32, operation for operation as ``nfa_vmreg_bwd`` forms it from the
     signs ``nfa_vmreg_fwd`` leaves (the stencils and their order: csrc/vmreg.hip's header), so the two agree bit for bit.
@@ -366,13 +371,10 @@ def _vm_terms_grad_torch(params: Tensor, grad_terms: Tensor, table) -> Tensor:
         H, W, R = p.shape[0], p.shape[1], l.shape[0]
         inv = torch.tensor([1.0 / n for n in _vm_counts(H, W, R, C)], dtype=torch.float32, device=p.device)
         c = g32[m] * inv
-        zr, zc, zl = p.new_zeros(1, W, C), p.new_zeros(H, 1, C), p.new_zeros(1, C)
-        dh = p[1:] - p[:-1]
-        gh = torch.cat([zr, dh]) - torch.cat([dh, zr])
-        dw = p[:, 1:] - p[:, :-1]
-        gw = torch.cat([zc, dw], 1) - torch.cat([dw, zc], 1)
+        gh, gw = _tv_stencils(p)
         g_plane = ((2.0 * c[0]) * gh + (2.0 * c[1]) * gw) + c[2] * _sign0(p)
         dt = l[1:] - l[:-1]
+        zl = p.new_zeros(1, C)
         gt = torch.cat([zl, dt]) - torch.cat([dt, zl])
         gram = p.new_zeros(C, C)
         for r in range(R):

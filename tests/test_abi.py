@@ -23,6 +23,16 @@ def test_header_and_library_agree():
     assert seg_plan(2048, 1000) == (1024, 2 + 1000 // 256 + 1)   # a tile also ends after 256 rays
 
 
+def test_every_header_is_in_the_content_hash():
+    """A header under csrc/ that `_deps()` leaves out would let a stale library survive an edit to it."""
+    from nerfacc_amd import _build
+    headers = {os.path.join(_build.CSRC, f) for f in os.listdir(_build.CSRC) if f.endswith(".h")}
+    assert headers, "no headers found"
+    deps = set(_build._deps())
+    assert headers <= deps, sorted(headers - deps)
+    assert {os.path.join(_build.CSRC, s) for s in _build.SOURCES} <= deps
+
+
 def test_argument_errors_are_reported():
     from nerfacc_amd import _backend as B
     import ctypes as C

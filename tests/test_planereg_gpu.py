@@ -11,15 +11,16 @@ import planereg_reference as R
 
 pytestmark = pytest.mark.gpu
 
-# The kernels' constants (csrc/planereg.hip): a tile is NFA_PR_ROWS rows by NFA_PR_QUADS 16-byte pieces, one workgroup each;
-# a wave-instruction spans 64 lanes * 4 floats of a row; a lane of the finish kernel starts a new run of partial rows every
-# NFA_PR_RUN rows, i.e. a plane of more than NFA_PR_QUADS * NFA_PR_RUN tiles takes the several-runs path.
-NFA_PR_ROWS, NFA_PR_QUADS, NFA_PR_RUN, WAVE_FLOATS = 16, 256, 256, 256
+# The kernels' constants (csrc/plane_tiles.h, csrc/planereg.hip): a tile is NFA_PT_ROWS rows by NFA_PT_QUADS 16-byte pieces,
+# one workgroup each; a wave-instruction spans 64 lanes * 4 floats of a row; the finish kernel has NFA_PR_FIN lanes per plane,
+# and a lane starts a new run of partial rows every NFA_PR_RUN rows, i.e. a plane of more than NFA_PR_FIN * NFA_PR_RUN tiles
+# takes the several-runs path.
+NFA_PT_ROWS, NFA_PT_QUADS, NFA_PR_FIN, NFA_PR_RUN, WAVE_FLOATS = 16, 256, 256, 256, 256
 # Scale 1 of LARGE has [66, 140, 8] planes: 66 rows are 5 row blocks (not a multiple of 16), W F = 1120 floats are 2 segments
 # (not a multiple of the 1024 floats of a tile's row, nor of the 256 floats of a wave): 10 workgroups for that plane.
 LARGE = ((70, 33, 9, 11), (1, 2), 8)
 SHAPES = [(res, ms, F) for _, res, ms in R.CASES for F in R.FEATURES] + [LARGE]
-assert (2 * 33) % NFA_PR_ROWS and (2 * 70 * 8) % (4 * NFA_PR_QUADS) and (2 * 70 * 8) % WAVE_FLOATS and 2 * 70 * 8 > 4 * NFA_PR_QUADS
+assert (2 * 33) % NFA_PT_ROWS and (2 * 70 * 8) % (4 * NFA_PT_QUADS) and (2 * 70 * 8) % WAVE_FLOATS and 2 * 70 * 8 > 4 * NFA_PT_QUADS
 
 
 def _enc(res, ms, F, dev, params=None):
@@ -67,9 +68,9 @@ def test_values(dev, res, ms, F):
 
 
 def test_values_with_several_runs_of_partial_rows(dev):
-    """A plane of more than NFA_PR_QUADS * NFA_PR_RUN = 65536 tiles: the finish kernel's lanes add more than one run."""
+    """A plane of more than NFA_PR_FIN * NFA_PR_RUN = 65536 tiles: the finish kernel's lanes add more than one run."""
     from nerfacc_amd.losses import plane_terms
-    res, ms, F = (2, 2, NFA_PR_ROWS * (NFA_PR_QUADS * NFA_PR_RUN + 2) + 8), (1,), 4
+    res, ms, F = (2, 2, NFA_PT_ROWS * (NFA_PR_FIN * NFA_PR_RUN + 2) + 8), (1,), 4
     enc = _enc(res, ms, F, dev, torch.zeros(1))
     with torch.no_grad():
         enc.params.copy_(1.0 + 0.5 * torch.randn(enc.params.numel(), generator=torch.Generator().manual_seed(3)).to(dev))
@@ -77,7 +78,7 @@ def test_values_with_several_runs_of_partial_rows(dev):
         ref = R.terms_reference(enc.params.detach(), res, ms, F)      # float64, on the device
     from nerfacc_amd import _backend as B
     need = B.load().nfa_planereg_partials(3, 1, F, enc.table.c_res)
-    assert need == 1 + 2 * (NFA_PR_QUADS * NFA_PR_RUN + 3)
+    assert need == 1 + 2 * (NFA_PR_FIN * NFA_PR_RUN + 3)
     torch.testing.assert_close(got.double(), ref, rtol=1e-4, atol=0.0)
 
 

@@ -11,29 +11,29 @@ import vmreg_reference as R
 
 pytestmark = pytest.mark.gpu
 
-# The kernels' constants (csrc/vmreg.hip): a plane tile is NFA_VR_ROWS rows by NFA_VR_QUADS 16-byte pieces, one workgroup
-# each; a wave-instruction spans 64 lanes * 4 floats of a row; the finish kernel has NFA_VR_FIN lanes per mode, and a lane
-# starts a new run every NFA_VR_RUN partial rows (line quads), i.e. a plane of more than NFA_VR_FIN * NFA_VR_RUN tiles takes
-# the several-runs path; a line is copied to LDS while 4 max(R) C + NFA_VR_SCRATCH <= NFA_VR_LDS_BYTES.
-NFA_VR_ROWS, NFA_VR_QUADS, NFA_VR_FIN, NFA_VR_RUN, WAVE_FLOATS = 16, 256, 512, 128, 256
+# The kernels' constants (csrc/plane_tiles.h, csrc/vmreg.hip): a plane tile is NFA_PT_ROWS rows by NFA_PT_QUADS 16-byte
+# pieces, one workgroup each; a wave-instruction spans 64 lanes * 4 floats of a row; the finish kernel has NFA_VR_FIN lanes
+# per mode, and a lane starts a new run every NFA_VR_RUN partial rows (line quads), i.e. a plane of more than NFA_VR_FIN *
+# NFA_VR_RUN tiles takes the several-runs path; a line is copied to LDS while 4 max(R) C + NFA_VR_SCRATCH <= NFA_VR_LDS_BYTES.
+NFA_PT_ROWS, NFA_PT_QUADS, NFA_VR_FIN, NFA_VR_RUN, WAVE_FLOATS = 16, 256, 512, 128, 256
 NFA_VR_LDS_BYTES, NFA_VR_SCRATCH = 65536, 256
 # Mode 0 of LARGE has a [33, 70, 24] plane: 33 rows are 3 row blocks (not a multiple of 16), W C = 1680 floats are 2 segments
 # (more than the 1024 floats of a tile's row, a multiple neither of them nor of the 256 floats of a wave): 6 workgroups.
 LARGE = ((70, 33, 9), 24)
-assert 33 % NFA_VR_ROWS and (70 * 24) % (4 * NFA_VR_QUADS) and (70 * 24) % WAVE_FLOATS and 70 * 24 > 4 * NFA_VR_QUADS
+assert 33 % NFA_PT_ROWS and (70 * 24) % (4 * NFA_PT_QUADS) and (70 * 24) % WAVE_FLOATS and 70 * 24 > 4 * NFA_PT_QUADS
 # A line too long for the LDS copy (153,600 bytes), and the longest that C = 96 components fit (170 rows: 65,280 + 256 bytes).
 LONG_LINE = ((4, 4, 400), 96)
 LDS_FULL = ((4, 4, 170), 96)
 assert 4 * 400 * 96 + NFA_VR_SCRATCH > NFA_VR_LDS_BYTES >= 4 * 170 * 96 + NFA_VR_SCRATCH > NFA_VR_LDS_BYTES - 4 * 96
 SHAPES = [(res, C) for res in R.RESOLUTIONS for C in R.COMPONENTS] + [LARGE, LONG_LINE, LDS_FULL, ((5, 4, 33), 48)]
 # Two planes of more than NFA_VR_FIN * NFA_VR_RUN = 65536 tiles, and a line of 2049 quads per lane of the finish kernel (17 runs)
-SEVERAL_RUNS = ((2, 2, NFA_VR_ROWS * (NFA_VR_FIN * NFA_VR_RUN + 2) + 8), 4)
+SEVERAL_RUNS = ((2, 2, NFA_PT_ROWS * (NFA_VR_FIN * NFA_VR_RUN + 2) + 8), 4)
 
 
 def plane_chain():
     """The longest chain of float32 additions a plane term passes through (csrc/vmreg.hip's header): 64 in a lane of a
     tile, 6 + 3 for the tile, 127 + 256 for a lane of the finish kernel, 6 + 7 for its workgroup."""
-    return 4 * NFA_VR_ROWS + 9 + (NFA_VR_RUN - 1) + 256 + 13
+    return 4 * NFA_PT_ROWS + 9 + (NFA_VR_RUN - 1) + 256 + 13
 
 
 def line_chain(rows, C):
