@@ -1033,6 +1033,55 @@ int nfa_generate_rays_bwd(const void *x, const void *y, int32_t pixel_dtype, con
                           int32_t pose_floats, float *grad_camtoworlds, float *grad_K, nfa_stream_t stream);
 int nfa_generate_rays_chunk(void);   /* rays per chunk of the backward's reduction (a constant of the build) */
 
+/* ------------------------------------------------------------------ fused MLP */
+
+/* The field's network as fused half-precision MFMA passes: tiny-cuda-nn's FullyFusedMLP with ReLU hidden layers, no biases
+ * and no output activation (ref: examples/radiance_fields/ngp.py:131-135, 150-154, 255-259).  n_hidden + 1 matrices W_l
+ * [out_l, in_l] (torch's Linear layout), in_0 = n_in, out_last = n_out, every other side `width`:
+ *   H_0 = relu(x W_0^T), H_l = relu(H_{l-1} W_l^T), y = H_last W_L^T.
+ * Shapes: elem NFA_ELEM_F16 or NFA_ELEM_BF16 (the network's type: weights, hidden activations, dZ), width 64 or 128,
+ * n_hidden 1..4, n_in 1..256, n_out 1..32; and the packed images below must fit the 160 KiB of LDS of a compute unit
+ * beside 16,896 B of store staging (the message gives the sizes).  All four entries check, in this order: elem, width,
+ * n_hidden, n_in, n_out, n_points >= 0, the LDS budget, the other element codes; then n_points == 0 returns NFA_OK
+ * whatever the pointers are; then null pointers and alignment.  Nothing reaches the GPU before every check passed.
+ * Rounding (always to nearest even): x and the masters to `elem`, every hidden activation after its ReLU, every dZ_l after
+ * its mask, y / grad_x once as stored; float32 outputs are the float32 accumulators unrounded.
+ *
+ * nfa_mlp_pack_weights: params = the float32 masters, W_0 .. W_L flat in that order, to the two images the passes read
+ * (one launch).  A packed matrix A [rows, k] is a run of 1 KiB blocks (m, q), m < ceil(rows / 32) major, q < ceil(k / 16):
+ * element ((m KQ + q) 64 + lane) 8 + j = A[32 m + (lane & 31)][16 q + kpos], zero outside A, with kpos = 8 (lane >> 5) + j for
+ * the layer whose other operand comes from memory (layer 0 forward, the last layer backward) and 8 (j >> 2) + 4 (lane >> 5) +
+ * (j & 3) elsewhere (the order in which an accumulator tile presents its rows as the next operand).  fwd_image: A = W_l;
+ * bwd_image: A = W_l^T; layers in order.  fwd_elems / bwd_elems: the images' sizes in elements, which must be exactly
+ * sum_l ceil(out_l / 32) ceil(in_l / 16) 512 and sum_l ceil(in_l / 32) ceil(out_l / 16) 512.  Images are 16-byte aligned. */
+int nfa_mlp_pack_weights(int32_t elem, const float *params, int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden,
+                         void *fwd_image, int64_t fwd_elems, void *bwd_image, int64_t bwd_elems, nfa_stream_t stream);
+/* One launch for the whole network.  x [n_points, n_in] of x_elem (NFA_ELEM_F32: rounded on load; or elem), rows of a
+ * multiple of 8 elements from a 16-byte aligned base load as 16-byte pieces, any other shape element by element.
+ * y [n_points, n_out] of y_elem (elem, or NFA_ELEM_F32).  save_hidden != 0: hidden [n_hidden, n_points, width] (elem,
+ * 8-byte aligned) receives the rounded post-ReLU activations; otherwise nothing but y is written. */
+int nfa_mlp_fwd(int32_t elem, const void *x, int32_t x_elem, const void *fwd_image, int64_t n_points, int32_t n_in, int32_t n_out,
+                int32_t width, int32_t n_hidden, void *y, int32_t y_elem, void *hidden, int32_t save_hidden, nfa_stream_t stream);
+/* One launch for the gradient chain: dZ_L = grad_y rounded to elem (g_elem: NFA_ELEM_F32 or elem), dH_{l-1} = dZ_l W_l,
+ * dZ_{l-1} = dH_{l-1} * (H_{l-1} > 0) with H from `hidden` as nfa_mlp_fwd saved it.  Writes dz [n_hidden, n_points, width]
+ * (elem; dZ_0 .. dZ_{L-1}), dz_out [n_points, n_out] (elem; dZ_L, optional: a caller whose grad_y is of type elem
+ * already passes grad_y to nfa_mlp_bwd_weights instead) and grad_x [n_points, n_in] of x_elem (optional). */
+int nfa_mlp_bwd_data(int32_t elem, const void *grad_y, int32_t g_elem, const void *hidden, const void *bwd_image, int64_t n_points,
+                     int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden, void *dz, void *dz_out, void *grad_x,
+                     int32_t x_elem, nfa_stream_t stream);
+/* grad_params (the masters' layout, float32, overwritten) = dW_l = dZ_l^T H_{l-1}, H_{-1} = x rounded as the forward rounds
+ * it: split-K MFMA over the points and an ordered sum, two launches, no atomics, bitwise reproducible.  The points are
+ * cut into n_slices = ceil(n_points / slice) slices, slice = ceil(n_points / s) rounded up to a multiple of 64 with
+ * s = clamp(ceil(n_points / NFA_MLP_WGRAD_MIN_SLICE), 1, NFA_MLP_WGRAD_MAX_SLICES): a function of n_points alone.  A
+ * workgroup per (slice, layer) writes its float32 partial to partials [n_slices, n_params] (scratch of partial_floats floats,
+ * need not be initialised; too small is NFA_EINVAL), the second launch adds the slices in ascending order.  hidden, dz:
+ * as above, 16-byte aligned; dz_out [n_points, n_out] of elem. */
+#define NFA_MLP_WGRAD_MIN_SLICE 256
+#define NFA_MLP_WGRAD_MAX_SLICES 256
+int nfa_mlp_bwd_weights(int32_t elem, const void *x, int32_t x_elem, const void *hidden, const void *dz, const void *dz_out,
+                        int64_t n_points, int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden, float *partials,
+                        int64_t partial_floats, float *grad_params, nfa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

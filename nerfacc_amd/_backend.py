@@ -165,6 +165,10 @@ _SIGS = {
     "nfa_generate_rays_bwd": [_vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _f32,
                               _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp],
     "nfa_generate_rays_chunk": [],
+    "nfa_mlp_pack_weights": [_i32, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp],
+    "nfa_mlp_fwd": [_i32, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp],
+    "nfa_mlp_bwd_data": [_i32, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp],
+    "nfa_mlp_bwd_weights": [_i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],

@@ -1,0 +1,604 @@
+// mlp.hip -- the field's network as fused half-precision MFMA passes: tiny-cuda-nn's FullyFusedMLP (no biases, ReLU on the
+// hidden layers, no output activation), n_hidden + 1 weight matrices W_l [out_l, in_l] (torch's Linear layout), width 64 or 128.
+//
+//   forward     H_0 = relu(x W_0^T), H_l = relu(H_{l-1} W_l^T), y = H_last W_L^T          one launch (nfa_mlp_fwd)
+//   data grad   dZ_L = g, dH_{l-1} = dZ_l W_l, dZ_{l-1} = dH_{l-1} * (H_{l-1} > 0), dx = dZ_0 W_0   one launch (nfa_mlp_bwd_data)
+//   weight grad dW_l = dZ_l^T H_{l-1}, H_{-1} = x                                         split-K + ordered sum (nfa_mlp_bwd_weights)
+//
+// Everything works TRANSPOSED, with the weights as the A operand of v_mfma_f32_32x32x16_{f16,bf16}: a wave owns 32 points, a point
+// is a COLUMN of every tile and so stays on lane (point & 31) of both lane halves through all layers.  The 32x32 float32 result
+// of one layer has its rows (neurons) in the 16 accumulator registers of a lane; converted pairwise to half, registers
+// 8s .. 8s+7 are the B fragment of k-step s of the next layer, with no lane movement and no LDS.  The k order inside such a step
+// is permuted (element j of lane half h is row 16s + 8(j>>2) + 4h + (j&3)); the packed weight images absorb the permutation, so
+// a lane's A fragment is one 16-byte LDS read whatever the layer.
+//
+// Packed image of a matrix A [rows, k] (rows padded to 32, k to 16, padding zero): blocks of 1 KiB, block (m, q) = rows
+// 32m .. 32m+31, k-step q, at element ((m KQ + q) 64 + lane) 8 + j, lane = 32h + r: A[32m + r][16q + kpos(h, j)], with
+// kpos = 8h + j where the B operand is loaded from memory (first product of a chain) and the permuted order above elsewhere.
+// The forward image holds W_l, the backward image W_l^T (rows = inputs of the layer, k = its outputs).
+//
+// Rounding points (all to nearest even, the compiler's conversion; never the pkrtz form): x and the masters to the half type
+// on load / when packed, every hidden activation after its ReLU, every dZ_l after its mask, y and dx once as stored (float32
+// outputs are the accumulators themselves).  Products are exact in float32 and summed by the MFMA in float32.
+//
+// EXEC is all ones around every MFMA: a partial tile clamps the point index of its loads and masks only its stores.
+#include "common.hip.h"
+
+namespace nfa {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int MLP_WAVES = 4;                              // waves per workgroup of the two fused passes
+constexpr int STAGE_LD = 33;                              // floats per row of a wave's 32 x 32 store staging tile (odd: no conflicts)
+constexpr int64_t STAGE_BYTES = (int64_t)MLP_WAVES * 32 * STAGE_LD * 4;
+constexpr int64_t LDS_BUDGET = 160 * 1024;
+
+struct Shape {
+    int32_t n_in, n_out, W, n_hidden;
+    __host__ __device__ int layers() const { return n_hidden + 1; }
+    __host__ __device__ int in_dim(int l) const { return l == 0 ? n_in : W; }
+    __host__ __device__ int out_dim(int l) const { return l == n_hidden ? n_out : W; }
+    __host__ __device__ int64_t master_off(int l) const
+    {
+        int64_t o = 0;
+        for (int i = 0; i < l; ++i) o += (int64_t)out_dim(i) * in_dim(i);
+        return o;
+    }
+    // forward image: A = W_l; backward image: A = W_l^T
+    __host__ __device__ int fwd_mt(int l) const { return (out_dim(l) + 31) / 32; }
+    __host__ __device__ int fwd_kq(int l) const { return (in_dim(l) + 15) / 16; }
+    __host__ __device__ int bwd_mt(int l) const { return (in_dim(l) + 31) / 32; }
+    __host__ __device__ int bwd_kq(int l) const { return (out_dim(l) + 15) / 16; }
+    __host__ __device__ int64_t fwd_off(int l) const   // in elements; fwd_off(layers()) is the image's size
+    {
+        int64_t o = 0;
+        for (int i = 0; i < l; ++i) o += (int64_t)fwd_mt(i) * fwd_kq(i) * 512;
+        return o;
+    }
+    __host__ __device__ int64_t bwd_off(int l) const
+    {
+        int64_t o = 0;
+        for (int i = 0; i < l; ++i) o += (int64_t)bwd_mt(i) * bwd_kq(i) * 512;
+        return o;
+    }
+};
+
+__host__ __device__ inline int kpos(bool permuted, int h, int j) { return permuted ? 8 * (j >> 2) + 4 * h + (j & 3) : 8 * h + j; }
+// row of a 32 x 32 accumulator tile that register `reg` of lane half h holds (the column is lane & 31)
+__device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+
+template <class E>
+__device__ __forceinline__ f32x16 mfma(nfa_v4u a, nfa_v4u b, f32x16 c)
+{
+    if constexpr (std::is_same<E, nfa_f16>::value)
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// ---------------------------------------------------------------- packing
+
+template <class E>
+__global__ __launch_bounds__(256) void mlp_pack_kernel(Shape S, const float *__restrict__ params, uint16_t *__restrict__ fwd,
+                                                       uint16_t *__restrict__ bwd, int64_t fwd_elems, int64_t bwd_elems)
+{
+    const int L = S.layers();
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < fwd_elems + bwd_elems; idx += (int64_t)gridDim.x * 256) {
+        const bool is_bwd = idx >= fwd_elems;
+        const int64_t e = is_bwd ? idx - fwd_elems : idx;
+        int l = 0;
+        int64_t off = 0;
+        for (;; ++l) {
+            const int64_t sz = (is_bwd ? (int64_t)S.bwd_mt(l) * S.bwd_kq(l) : (int64_t)S.fwd_mt(l) * S.fwd_kq(l)) * 512;
+            if (e < off + sz || l == L - 1) break;
+            off += sz;
+        }
+        const int64_t local = e - off;
+        const int j = (int)(local & 7), lane = (int)((local >> 3) & 63);
+        const int64_t blk = local >> 9;
+        const int KQ = is_bwd ? S.bwd_kq(l) : S.fwd_kq(l);
+        const int q = (int)(blk % KQ), m = (int)(blk / KQ);
+        const int row = 32 * m + (lane & 31);
+        // the B operand of a chain's first product comes from memory in natural k order: layer 0 forward, the last layer backward
+        const bool permuted = is_bwd ? (l != L - 1) : (l != 0);
+        const int k = 16 * q + kpos(permuted, lane >> 5, j);
+        const int in = S.in_dim(l), out = S.out_dim(l);
+        float v = 0.f;
+        if (!is_bwd) { if (row < out && k < in) v = params[S.master_off(l) + (int64_t)row * in + k]; }
+        else         { if (row < in && k < out) v = params[S.master_off(l) + (int64_t)k * in + row]; }
+        (is_bwd ? bwd : fwd)[e] = (uint16_t)half_bits<E>(v);
+    }
+}
+
+// ---------------------------------------------------------------- pieces shared by the passes
+
+// Elements k0 .. k0+7 of row `row` of a [*, ld] matrix as a B fragment of element type E; columns >= ld read as zero.  The
+// matrix holds float32 (rounded here) or E.  `vec`: ld is a multiple of 8 and the base is 16-byte aligned.
+template <class E>
+__device__ __forceinline__ nfa_v4u load_row8(const void *base, bool is_f32, int64_t row, int ld, int k0, bool vec)
+{
+    nfa_v4u f = {0u, 0u, 0u, 0u};
+    if (vec) {
+        if (k0 < ld) {
+            if (is_f32) {
+                const nfa_v4f *p = reinterpret_cast<const nfa_v4f *>(static_cast<const float *>(base) + row * ld + k0);
+                const nfa_v4f a = p[0], b = p[1];
+                f[0] = pack_halves<E>(a[0], a[1]); f[1] = pack_halves<E>(a[2], a[3]);
+                f[2] = pack_halves<E>(b[0], b[1]); f[3] = pack_halves<E>(b[2], b[3]);
+            } else {
+                f = *reinterpret_cast<const nfa_v4u *>(static_cast<const uint16_t *>(base) + row * ld + k0);
+            }
+        }
+    } else {
+        uint32_t b[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            b[j] = 0u;
+            if (k0 + j < ld)
+                b[j] = is_f32 ? half_bits<E>(static_cast<const float *>(base)[row * ld + k0 + j])
+                              : (uint32_t)static_cast<const uint16_t *>(base)[row * ld + k0 + j];
+        }
+#pragma unroll
+        for (int d = 0; d < 4; ++d) f[d] = b[2 * d] | (b[2 * d + 1] << 16);
+    }
+    return f;
+}
+
+// registers 8s .. 8s+7 of an accumulator tile, rounded pairwise to E: the B fragment of k-step s of the next product
+template <class E>
+__device__ __forceinline__ nfa_v4u acc_frag(const f32x16 &a, int s)
+{
+    nfa_v4u f;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) f[d] = pack_halves<E>(a[8 * s + 2 * d], a[8 * s + 2 * d + 1]);
+    return f;
+}
+
+// The two fragments of tile t of a [*, W] half matrix's row p: 8-byte pieces at columns 32t + 8g + 4h, g = 0..3, which are
+// registers 4g .. 4g+3 of the accumulator tile the fragments came from.
+template <int W>
+__device__ __forceinline__ void store_tile_row(uint16_t *m, int64_t p, int t, int h, const nfa_v4u &f0, const nfa_v4u &f1)
+{
+    nfa_v2u *d = reinterpret_cast<nfa_v2u *>(m + p * W + 32 * t + 4 * h);
+    d[0] = nfa_v2u{f0[0], f0[1]};
+    d[2] = nfa_v2u{f0[2], f0[3]};
+    d[4] = nfa_v2u{f1[0], f1[1]};
+    d[6] = nfa_v2u{f1[2], f1[3]};
+}
+
+// A wave's 32 x 32 accumulator tile (row = column of the output matrix, column = point) to memory through its LDS staging
+// tile, so that stores run along the output rows: columns col0 .. col0+ncols-1 of rows row0 .. row0+nrows-1 of out [*, ld].
+template <class E>
+__device__ __forceinline__ void stage_store(const f32x16 &acc, float *st, void *out, bool out_f32, int64_t row0, int nrows, int ld,
+                                            int col0, int ncols, int lane)
+{
+    const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) st[r * STAGE_LD + acc_row(reg, h)] = acc[reg];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int total = nrows * ncols;
+    for (int i = lane; i < total; i += NFA_WAVE) {
+        const int pr = i / ncols, c = i - pr * ncols;
+        const float v = st[pr * STAGE_LD + c];
+        const int64_t gi = (row0 + pr) * ld + col0 + c;
+        if (out_f32) static_cast<float *>(out)[gi] = v;
+        else static_cast<uint16_t *>(out)[gi] = (uint16_t)half_bits<E>(v);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ void stage_image(nfa_v4u *dst, const nfa_v4u *src, int64_t n16)
+{
+    for (int64_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+    __syncthreads();
+}
+
+// ---------------------------------------------------------------- forward
+
+template <class E, int W>
+__global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_fwd_kernel(Shape S, const void *__restrict__ x, int x_f32, int x_vec,
+                                                                      const uint16_t *__restrict__ image, int64_t image_elems,
+                                                                      int64_t N, void *__restrict__ y, int y_f32,
+                                                                      uint16_t *__restrict__ hidden)
+{
+    constexpr int MT = W / 32, KQ = W / 16;
+    extern __shared__ __attribute__((aligned(16))) unsigned char mlp_lds[];
+    nfa_v4u *wimg = reinterpret_cast<nfa_v4u *>(mlp_lds);
+    stage_image(wimg, reinterpret_cast<const nfa_v4u *>(image), image_elems / 8);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    float *st = reinterpret_cast<float *>(mlp_lds + image_elems * 2) + wave * 32 * STAGE_LD;
+    const int kq0 = S.fwd_kq(0);
+    const int64_t n_tiles = (N + 31) / 32;
+    for (int64_t tile = (int64_t)blockIdx.x * MLP_WAVES + wave; tile < n_tiles; tile += (int64_t)gridDim.x * MLP_WAVES) {
+        const int64_t p = tile * 32 + r, pc = p < N ? p : N - 1;
+        f32x16 acc[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
+        for (int q = 0; q < kq0; ++q) {
+            const nfa_v4u b = load_row8<E>(x, x_f32 != 0, pc, S.n_in, 16 * q + 8 * h, x_vec != 0);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) acc[m] = mfma<E>(wimg[(m * kq0 + q) * 64 + lane], b, acc[m]);
+        }
+        int64_t off16 = (int64_t)MT * kq0 * 64;   // in 16-byte fragments
+        nfa_v4u hf[KQ];
+        for (int l = 1;; ++l) {
+            // H_{l-1} = relu(acc), rounded: the next product's B fragments, and what the backward reads
+#pragma unroll
+            for (int t = 0; t < MT; ++t) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[t][i] = acc[t][i] < 0.f ? 0.f : acc[t][i];
+                hf[2 * t] = acc_frag<E>(acc[t], 0);
+                hf[2 * t + 1] = acc_frag<E>(acc[t], 1);
+                if (hidden && p < N) store_tile_row<W>(hidden + (int64_t)(l - 1) * N * W, p, t, h, hf[2 * t], hf[2 * t + 1]);
+            }
+            if (l == S.n_hidden) break;
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
+#pragma unroll
+                for (int q = 0; q < KQ; ++q) acc[m] = mfma<E>(wimg[off16 + (m * KQ + q) * 64 + lane], hf[q], acc[m]);
+            }
+            off16 += (int64_t)MT * KQ * 64;
+        }
+        f32x16 o;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[i] = 0.f;
+#pragma unroll
+        for (int q = 0; q < KQ; ++q) o = mfma<E>(wimg[off16 + q * 64 + lane], hf[q], o);
+        const int64_t row0 = tile * 32;
+        stage_store<E>(o, st, y, y_f32 != 0, row0, (int)(N - row0 < 32 ? N - row0 : 32), S.n_out, 0, S.n_out, lane);
+    }
+}
+
+// ---------------------------------------------------------------- data gradient
+
+template <class E, int W>
+__global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_bwd_data_kernel(Shape S, const void *__restrict__ g, int g_f32, int g_vec,
+                                                                           const uint16_t *__restrict__ hidden,
+                                                                           const uint16_t *__restrict__ image, int64_t image_elems,
+                                                                           int64_t N, uint16_t *__restrict__ dz,
+                                                                           uint16_t *__restrict__ dz_out, void *__restrict__ dx,
+                                                                           int dx_f32)
+{
+    constexpr int MT = W / 32, KQ = W / 16;
+    extern __shared__ __attribute__((aligned(16))) unsigned char mlp_lds[];
+    nfa_v4u *wimg = reinterpret_cast<nfa_v4u *>(mlp_lds);
+    stage_image(wimg, reinterpret_cast<const nfa_v4u *>(image), image_elems / 8);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    float *st = reinterpret_cast<float *>(mlp_lds + image_elems * 2) + wave * 32 * STAGE_LD;
+    const int L = S.layers(), kqo = S.bwd_kq(L - 1), mt0 = S.bwd_mt(0);
+    const int64_t n_tiles = (N + 31) / 32;
+    for (int64_t tile = (int64_t)blockIdx.x * MLP_WAVES + wave; tile < n_tiles; tile += (int64_t)gridDim.x * MLP_WAVES) {
+        const int64_t p = tile * 32 + r, pc = p < N ? p : N - 1;
+        f32x16 acc[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
+        // dH_last = W_L^T dZ_L, dZ_L = g rounded
+        int64_t off16 = S.bwd_off(L - 1) / 8;
+        for (int q = 0; q < kqo; ++q) {
+            const nfa_v4u b = load_row8<E>(g, g_f32 != 0, pc, S.n_out, 16 * q + 8 * h, g_vec != 0);
+            if (dz_out && p < N) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int k = 16 * q + 8 * h + j;
+                    if (k < S.n_out) dz_out[p * S.n_out + k] = (uint16_t)(b[j >> 1] >> (16 * (j & 1)));
+                }
+            }
+#pragma unroll
+            for (int m = 0; m < MT; ++m) acc[m] = mfma<E>(wimg[off16 + (m * kqo + q) * 64 + lane], b, acc[m]);
+        }
+        nfa_v4u df[KQ];
+        for (int l = S.n_hidden - 1;; --l) {
+            // dZ_l = dH_l * (H_l > 0), rounded
+            const uint16_t *hl = hidden + (int64_t)l * N * W;
+#pragma unroll
+            for (int t = 0; t < MT; ++t) {
+                const nfa_v2u *hp = reinterpret_cast<const nfa_v2u *>(hl + pc * W + 32 * t + 4 * h);
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) {
+                    const nfa_v2u hv = hp[2 * gq];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float a = unpack_half<E>(hv[i >> 1], i & 1);
+                        acc[t][4 * gq + i] = a > 0.f ? acc[t][4 * gq + i] : 0.f;
+                    }
+                }
+                df[2 * t] = acc_frag<E>(acc[t], 0);
+                df[2 * t + 1] = acc_frag<E>(acc[t], 1);
+                if (p < N) store_tile_row<W>(dz + (int64_t)l * N * W, p, t, h, df[2 * t], df[2 * t + 1]);
+            }
+            if (l == 0) break;
+            off16 = S.bwd_off(l) / 8;
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
+#pragma unroll
+                for (int q = 0; q < KQ; ++q) acc[m] = mfma<E>(wimg[off16 + (m * KQ + q) * 64 + lane], df[q], acc[m]);
+            }
+        }
+        if (dx) {   // dx = W_0^T dZ_0, 32 input features at a time
+            const int64_t row0 = tile * 32;
+            const int nrows = (int)(N - row0 < 32 ? N - row0 : 32);
+            for (int m = 0; m < mt0; ++m) {
+                f32x16 o;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[i] = 0.f;
+#pragma unroll
+                for (int q = 0; q < KQ; ++q) o = mfma<E>(wimg[(m * KQ + q) * 64 + lane], df[q], o);
+                const int ncols = S.n_in - 32 * m < 32 ? S.n_in - 32 * m : 32;
+                stage_store<E>(o, st, dx, dx_f32 != 0, row0, nrows, S.n_in, 32 * m, ncols, lane);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- weight gradient
+
+constexpr int WG_CHUNK = 64;          // points staged per step
+constexpr int WG_LD = WG_CHUNK + 8;   // halves per row of the transposed LDS images (16-byte aligned rows)
+
+// Rows c0 .. c0+63 of src [*, ld] (float32 or E; rows >= n1 and columns >= ld read as zero), transposed into T [colsP][WG_LD].
+template <class E>
+__device__ __forceinline__ void stage_transposed(uint16_t *T, const void *src, bool is_f32, int ld, int colsP, int64_t c0, int64_t n1,
+                                                 bool vec)
+{
+    const int units = (colsP / 8) * WG_CHUNK;
+    for (int u = threadIdx.x; u < units; u += blockDim.x) {
+        const int n = u & (WG_CHUNK - 1), cg = u >> 6;
+        nfa_v4u f = {0u, 0u, 0u, 0u};
+        if (c0 + n < n1) f = load_row8<E>(src, is_f32, c0 + n, ld, 8 * cg, vec);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) T[(8 * cg + j) * WG_LD + n] = (uint16_t)(f[j >> 1] >> (16 * (j & 1)));
+    }
+}
+
+// Workgroup (slice, layer): partial dW_l over the slice's points, the 32 x 32 tiles of [out_l, in_l] dealt round-robin to the waves.
+template <class E, int W>
+__global__ __launch_bounds__(256) void mlp_wgrad_kernel(Shape S, const void *__restrict__ x, int x_f32, int x_vec,
+                                                        const uint16_t *__restrict__ hidden, const uint16_t *__restrict__ dz,
+                                                        const uint16_t *__restrict__ dz_out, int dzo_vec, int64_t N, int64_t slice_len,
+                                                        float *__restrict__ partials, int64_t P)
+{
+    constexpr int MAXT = (W / 32) * 8 / 4;   // tiles per wave at most: (W / 32) x (256 / 32) tiles over 4 waves
+    __shared__ __attribute__((aligned(16))) uint16_t Ta[128 * WG_LD];
+    __shared__ __attribute__((aligned(16))) uint16_t Tb[256 * WG_LD];
+    const int l = blockIdx.y, L = S.layers();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int M = S.out_dim(l), K = S.in_dim(l);
+    const int mt = (M + 31) / 32, nt = (K + 31) / 32, n_tile = mt * nt;
+    const void *a_src = l == L - 1 ? (const void *)dz_out : (const void *)(dz + (int64_t)l * N * W);
+    const bool a_vec = l == L - 1 ? dzo_vec != 0 : true;
+    const void *b_src = l == 0 ? x : (const void *)(hidden + (int64_t)(l - 1) * N * W);
+    const bool b_f32 = l == 0 && x_f32 != 0, b_vec = l == 0 ? x_vec != 0 : true;
+    f32x16 acc[MAXT];
+#pragma unroll
+    for (int i = 0; i < MAXT; ++i)
+#pragma unroll
+        for (int k = 0; k < 16; ++k) acc[i][k] = 0.f;
+    const int64_t n0 = (int64_t)blockIdx.x * slice_len, n1 = n0 + slice_len < N ? n0 + slice_len : N;
+    for (int64_t c0 = n0; c0 < n1; c0 += WG_CHUNK) {
+        __syncthreads();
+        stage_transposed<E>(Ta, a_src, false, M, mt * 32, c0, n1, a_vec);
+        stage_transposed<E>(Tb, b_src, b_f32, K, nt * 32, c0, n1, b_vec);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < MAXT; ++i) {
+            const int tile = wave + 4 * i;
+            if (tile < n_tile) {   // wave-uniform
+                const int tm = tile / nt, tn = tile - tm * nt;
+#pragma unroll
+                for (int ks = 0; ks < WG_CHUNK / 16; ++ks) {
+                    const nfa_v4u a = *reinterpret_cast<const nfa_v4u *>(Ta + (32 * tm + r) * WG_LD + 16 * ks + 8 * h);
+                    const nfa_v4u b = *reinterpret_cast<const nfa_v4u *>(Tb + (32 * tn + r) * WG_LD + 16 * ks + 8 * h);
+                    acc[i] = mfma<E>(a, b, acc[i]);
+                }
+            }
+        }
+    }
+    float *out = partials + (int64_t)blockIdx.x * P + S.master_off(l);
+#pragma unroll
+    for (int i = 0; i < MAXT; ++i) {
+        const int tile = wave + 4 * i;
+        if (tile < n_tile) {
+            const int tm = tile / nt, tn = tile - tm * nt, col = 32 * tn + r;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int row = 32 * tm + acc_row(reg, h);
+                if (row < M && col < K) out[(int64_t)row * K + col] = acc[i][reg];
+            }
+        }
+    }
+}
+
+// grad[e] = ((partials[0][e] + partials[1][e]) + ...): one order, whatever the launch
+__global__ __launch_bounds__(256) void mlp_wgrad_sum_kernel(const float *__restrict__ partials, int64_t n_slices, int64_t P,
+                                                            float *__restrict__ grad)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= P) return;
+    float s = partials[e];
+    for (int64_t k = 1; k < n_slices; ++k) s += partials[k * P + e];
+    grad[e] = s;
+}
+
+// ---------------------------------------------------------------- host side
+
+int check_shape(const char *who, int32_t elem, int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden, int64_t n_points, Shape *S)
+{
+    NFA_REQUIRE(elem == NFA_ELEM_F16 || elem == NFA_ELEM_BF16, "%s: elem %d: the network's type is NFA_ELEM_F16 or NFA_ELEM_BF16", who, elem);
+    NFA_REQUIRE(width == 64 || width == 128, "%s: width %d: 64 or 128 neurons are supported", who, width);
+    NFA_REQUIRE(n_hidden >= 1 && n_hidden <= 4, "%s: n_hidden %d: 1 to 4 hidden layers are supported", who, n_hidden);
+    NFA_REQUIRE(n_in >= 1 && n_in <= 256, "%s: n_in %d: 1 to 256 input features are supported", who, n_in);
+    NFA_REQUIRE(n_out >= 1 && n_out <= 32, "%s: n_out %d: 1 to 32 outputs are supported", who, n_out);
+    NFA_REQUIRE(n_points >= 0, "%s: n_points %lld is negative", who, (long long)n_points);
+    *S = Shape{n_in, n_out, width, n_hidden};
+    const int64_t f = S->fwd_off(S->layers()) * 2, b = S->bwd_off(S->layers()) * 2;
+    NFA_REQUIRE(f + STAGE_BYTES <= LDS_BUDGET && b + STAGE_BYTES <= LDS_BUDGET,
+                "%s: the packed weights do not fit the LDS: forward image %lld B, backward image %lld B, each with %lld B of store "
+                "staging, against %lld B per compute unit (n_in %d, n_out %d, width %d, n_hidden %d)",
+                who, (long long)f, (long long)b, (long long)STAGE_BYTES, (long long)LDS_BUDGET, n_in, n_out, width, n_hidden);
+    return NFA_OK;
+}
+
+bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+bool row8_vec(const void *p, int ld) { return ld % 8 == 0 && aligned_to(p, 16); }
+
+template <class F>
+bool dispatch_mlp(int32_t elem, int32_t width, F &&f)
+{
+    if (elem == NFA_ELEM_F16 && width == 64) f(ElemTag<nfa_f16>{}, std::integral_constant<int, 64>{});
+    else if (elem == NFA_ELEM_F16 && width == 128) f(ElemTag<nfa_f16>{}, std::integral_constant<int, 128>{});
+    else if (elem == NFA_ELEM_BF16 && width == 64) f(ElemTag<nfa_bf16>{}, std::integral_constant<int, 64>{});
+    else if (elem == NFA_ELEM_BF16 && width == 128) f(ElemTag<nfa_bf16>{}, std::integral_constant<int, 128>{});
+    else return false;
+    return true;
+}
+
+// workgroups of a fused pass: as many as stay resident (LDS and the 8 that 32 waves allow), never more than there are tiles
+unsigned fused_grid(int64_t n_points, int64_t lds_bytes)
+{
+    int64_t per_cu = LDS_BUDGET / lds_bytes;
+    per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
+    const int64_t want = ceil_div64(ceil_div64(n_points, 32), MLP_WAVES);
+    return (unsigned)(want < 256 * per_cu ? want : 256 * per_cu);
+}
+
+template <class Kern>
+int allow_lds(const char *who, Kern kern, int64_t lds_bytes)
+{
+    if (lds_bytes <= 64 * 1024) return NFA_OK;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) {
+        set_error("%s: %lld bytes of LDS refused: %s", who, (long long)lds_bytes, hipGetErrorString(e));
+        return NFA_EHIP;
+    }
+    return NFA_OK;
+}
+
+int64_t wgrad_slice_len(int64_t n_points)
+{
+    int64_t s = ceil_div64(n_points, NFA_MLP_WGRAD_MIN_SLICE);
+    s = s > NFA_MLP_WGRAD_MAX_SLICES ? NFA_MLP_WGRAD_MAX_SLICES : (s < 1 ? 1 : s);
+    return ceil_div64(ceil_div64(n_points, s), WG_CHUNK) * WG_CHUNK;
+}
+
+}  // namespace
+}  // namespace nfa
+
+using namespace nfa;
+
+int nfa_mlp_pack_weights(int32_t elem, const float *params, int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden,
+                         void *fwd_image, int64_t fwd_elems, void *bwd_image, int64_t bwd_elems, nfa_stream_t stream)
+{
+    Shape S;
+    if (int rc = check_shape("nfa_mlp_pack_weights", elem, n_in, n_out, width, n_hidden, 0, &S)) return rc;
+    const int64_t fe = S.fwd_off(S.layers()), be = S.bwd_off(S.layers());
+    NFA_REQUIRE(fwd_elems == fe && bwd_elems == be, "nfa_mlp_pack_weights: the images hold %lld and %lld elements for this shape, "
+                "got %lld and %lld", (long long)fe, (long long)be, (long long)fwd_elems, (long long)bwd_elems);
+    NFA_REQUIRE(params && fwd_image && bwd_image, "nfa_mlp_pack_weights: null pointer");
+    NFA_REQUIRE(aligned_to(fwd_image, 16) && aligned_to(bwd_image, 16), "nfa_mlp_pack_weights: the images must be 16-byte aligned");
+    dispatch_elem(elem, [&](auto tag) {
+        using E = typename decltype(tag)::type;
+        if constexpr (sizeof(E) == 2)
+            mlp_pack_kernel<E><<<grid_1d(fe + be, 256), 256, 0, as_stream(stream)>>>(S, params, static_cast<uint16_t *>(fwd_image),
+                                                                                   static_cast<uint16_t *>(bwd_image), fe, be);
+    });
+    NFA_CHECK_LAUNCH("nfa_mlp_pack_weights");
+    return NFA_OK;
+}
+
+int nfa_mlp_fwd(int32_t elem, const void *x, int32_t x_elem, const void *fwd_image, int64_t n_points, int32_t n_in, int32_t n_out,
+                int32_t width, int32_t n_hidden, void *y, int32_t y_elem, void *hidden, int32_t save_hidden, nfa_stream_t stream)
+{
+    Shape S;
+    if (int rc = check_shape("nfa_mlp_fwd", elem, n_in, n_out, width, n_hidden, n_points, &S)) return rc;
+    NFA_REQUIRE(x_elem == NFA_ELEM_F32 || x_elem == elem, "nfa_mlp_fwd: x_elem %d: float32 or the network's type (%d)", x_elem, elem);
+    NFA_REQUIRE(y_elem == NFA_ELEM_F32 || y_elem == elem, "nfa_mlp_fwd: y_elem %d: float32 or the network's type (%d)", y_elem, elem);
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(x && fwd_image && y && (!save_hidden || hidden), "nfa_mlp_fwd: null pointer");
+    NFA_REQUIRE(aligned_to(fwd_image, 16) && aligned_to(hidden, 8) && aligned_to(x, x_elem == NFA_ELEM_F32 ? 4 : 2) &&
+                aligned_to(y, y_elem == NFA_ELEM_F32 ? 4 : 2), "nfa_mlp_fwd: misaligned pointer (image 16, hidden 8, x and y their element)");
+    const int64_t img = S.fwd_off(S.layers()), lds = img * 2 + STAGE_BYTES;
+    int rc = NFA_OK;
+    dispatch_mlp(elem, width, [&](auto tag, auto w) {
+        using E = typename decltype(tag)::type;
+        auto kern = mlp_fwd_kernel<E, decltype(w)::value>;
+        if ((rc = allow_lds("nfa_mlp_fwd", kern, lds)) != NFA_OK) return;
+        kern<<<fused_grid(n_points, lds), MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(
+            S, x, x_elem == NFA_ELEM_F32, row8_vec(x, n_in), static_cast<const uint16_t *>(fwd_image), img, n_points, y,
+            y_elem == NFA_ELEM_F32, save_hidden ? static_cast<uint16_t *>(hidden) : nullptr);
+    });
+    if (rc != NFA_OK) return rc;
+    NFA_CHECK_LAUNCH("nfa_mlp_fwd");
+    return NFA_OK;
+}
+
+int nfa_mlp_bwd_data(int32_t elem, const void *grad_y, int32_t g_elem, const void *hidden, const void *bwd_image, int64_t n_points,
+                     int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden, void *dz, void *dz_out, void *grad_x,
+                     int32_t x_elem, nfa_stream_t stream)
+{
+    Shape S;
+    if (int rc = check_shape("nfa_mlp_bwd_data", elem, n_in, n_out, width, n_hidden, n_points, &S)) return rc;
+    NFA_REQUIRE(g_elem == NFA_ELEM_F32 || g_elem == elem, "nfa_mlp_bwd_data: g_elem %d: float32 or the network's type (%d)", g_elem, elem);
+    NFA_REQUIRE(x_elem == NFA_ELEM_F32 || x_elem == elem, "nfa_mlp_bwd_data: x_elem %d: float32 or the network's type (%d)", x_elem, elem);
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(grad_y && hidden && bwd_image && dz, "nfa_mlp_bwd_data: null pointer");
+    NFA_REQUIRE(aligned_to(bwd_image, 16) && aligned_to(hidden, 8) && aligned_to(dz, 8) && aligned_to(dz_out, 2) &&
+                aligned_to(grad_y, g_elem == NFA_ELEM_F32 ? 4 : 2) && aligned_to(grad_x, x_elem == NFA_ELEM_F32 ? 4 : 2),
+                "nfa_mlp_bwd_data: misaligned pointer (image 16, hidden and dz 8, the others their element)");
+    const int64_t img = S.bwd_off(S.layers()), lds = img * 2 + STAGE_BYTES;
+    int rc = NFA_OK;
+    dispatch_mlp(elem, width, [&](auto tag, auto w) {
+        using E = typename decltype(tag)::type;
+        auto kern = mlp_bwd_data_kernel<E, decltype(w)::value>;
+        if ((rc = allow_lds("nfa_mlp_bwd_data", kern, lds)) != NFA_OK) return;
+        kern<<<fused_grid(n_points, lds), MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(
+            S, grad_y, g_elem == NFA_ELEM_F32, row8_vec(grad_y, n_out), static_cast<const uint16_t *>(hidden),
+            static_cast<const uint16_t *>(bwd_image), img, n_points, static_cast<uint16_t *>(dz), static_cast<uint16_t *>(dz_out),
+            grad_x, x_elem == NFA_ELEM_F32);
+    });
+    if (rc != NFA_OK) return rc;
+    NFA_CHECK_LAUNCH("nfa_mlp_bwd_data");
+    return NFA_OK;
+}
+
+int nfa_mlp_bwd_weights(int32_t elem, const void *x, int32_t x_elem, const void *hidden, const void *dz, const void *dz_out,
+                        int64_t n_points, int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden, float *partials,
+                        int64_t partial_floats, float *grad_params, nfa_stream_t stream)
+{
+    Shape S;
+    if (int rc = check_shape("nfa_mlp_bwd_weights", elem, n_in, n_out, width, n_hidden, n_points, &S)) return rc;
+    NFA_REQUIRE(x_elem == NFA_ELEM_F32 || x_elem == elem, "nfa_mlp_bwd_weights: x_elem %d: float32 or the network's type (%d)", x_elem, elem);
+    NFA_REQUIRE(partial_floats >= 0, "nfa_mlp_bwd_weights: partial_floats %lld is negative", (long long)partial_floats);
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(x && hidden && dz && dz_out && partials && grad_params, "nfa_mlp_bwd_weights: null pointer");
+    NFA_REQUIRE(aligned_to(hidden, 16) && aligned_to(dz, 16) && aligned_to(dz_out, 2) && aligned_to(x, x_elem == NFA_ELEM_F32 ? 4 : 2) &&
+                aligned_to(partials, 4) && aligned_to(grad_params, 4),
+                "nfa_mlp_bwd_weights: misaligned pointer (hidden and dz 16, the others their element)");
+    const int64_t P = S.master_off(S.layers()), slice_len = wgrad_slice_len(n_points), n_slices = ceil_div64(n_points, slice_len);
+    NFA_REQUIRE(partial_floats >= n_slices * P, "nfa_mlp_bwd_weights: partials holds %lld floats, %lld slices of %lld parameters need %lld",
+                (long long)partial_floats, (long long)n_slices, (long long)P, (long long)(n_slices * P));
+    dispatch_mlp(elem, width, [&](auto tag, auto w) {
+        using E = typename decltype(tag)::type;
+        mlp_wgrad_kernel<E, decltype(w)::value><<<dim3((unsigned)n_slices, (unsigned)S.layers()), 256, 0, as_stream(stream)>>>(
+            S, x, x_elem == NFA_ELEM_F32, row8_vec(x, n_in), static_cast<const uint16_t *>(hidden), static_cast<const uint16_t *>(dz),
+            static_cast<const uint16_t *>(dz_out), row8_vec(dz_out, n_out), n_points, slice_len, partials, P);
+    });
+    NFA_CHECK_LAUNCH("nfa_mlp_bwd_weights");
+    mlp_wgrad_sum_kernel<<<(unsigned)ceil_div64(P, 256), 256, 0, as_stream(stream)>>>(partials, n_slices, P, grad_params);
+    NFA_CHECK_LAUNCH("nfa_mlp_bwd_weights (sum)");
+    return NFA_OK;
+}

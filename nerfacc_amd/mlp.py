@@ -1,0 +1,301 @@
+"""The field's network as fused half-precision MFMA passes (csrc/mlp.hip): tiny-cuda-nn's ``FullyFusedMLP``.
+
+The reference's NGP fields put ``tcnn.Network(otype="FullyFusedMLP")`` between the encodings and the renderer (ref:
+examples/radiance_fields/ngp.py:131-135, 150-154, 255-259): 64 neurons, 1 or 2 hidden layers, ReLU, no biases, no output
+activation (the output activations live in :func:`nerfacc_amd.rendering_from_raw`).  :class:`FusedMLP` is that component:
+the encodings hand it fp16 / bf16 activations (``out_dtype=``), it hands the renderer fp16 / bf16 raw outputs, and the
+gradients travel back the same way, with no cast pass and no ``torch.autocast`` in between.
+
+Not part of ``nerfacc_amd.__all__`` (nerfacc has no such module): ``from nerfacc_amd.mlp import FusedMLP``.
+"""
+from __future__ import annotations
+
+import math
+from typing import List, Optional, Sequence
+
+import torch
+from torch import Tensor, nn
+from torch.autograd.function import once_differentiable
+
+from . import _backend as B
+
+WIDTHS = (64, 128)
+MAX_HIDDEN_LAYERS = 4
+MAX_INPUT_DIMS = 256
+MAX_OUTPUT_DIMS = 32
+LDS_BUDGET = 160 * 1024          # bytes of LDS per compute unit
+STAGE_BYTES = 4 * 32 * 33 * 4    # the four waves' store staging tiles (csrc/mlp.hip: STAGE_BYTES)
+# include/nerfacc_hip.h: NFA_MLP_WGRAD_MIN_SLICE, NFA_MLP_WGRAD_MAX_SLICES
+WGRAD_MIN_SLICE = 256
+WGRAD_MAX_SLICES = 256
+
+
+def _cdiv(a: int, b: int) -> int:
+    return -(-a // b)
+
+
+def layer_dims(n_in: int, n_out: int, width: int, n_hidden: int) -> List[tuple]:
+    """``[(out_l, in_l)]`` of the ``n_hidden + 1`` matrices."""
+    ins = [n_in] + [width] * n_hidden
+    outs = [width] * n_hidden + [n_out]
+    return list(zip(outs, ins))
+
+
+def image_elems(n_in: int, n_out: int, width: int, n_hidden: int) -> tuple:
+    """Elements of the packed forward and backward weight images (include/nerfacc_hip.h: nfa_mlp_pack_weights)."""
+    dims = layer_dims(n_in, n_out, width, n_hidden)
+    fwd = sum(_cdiv(o, 32) * _cdiv(i, 16) * 512 for o, i in dims)
+    bwd = sum(_cdiv(i, 32) * _cdiv(o, 16) * 512 for o, i in dims)
+    return fwd, bwd
+
+
+def wgrad_slices(n_points: int) -> int:
+    """Slices the weight gradient cuts ``n_points`` into (include/nerfacc_hip.h: nfa_mlp_bwd_weights)."""
+    s = min(max(_cdiv(n_points, WGRAD_MIN_SLICE), 1), WGRAD_MAX_SLICES)
+    slice_len = _cdiv(_cdiv(n_points, s), 64) * 64
+    return _cdiv(n_points, slice_len)
+
+
+# ---------------------------------------------------------------- the arithmetic restated in torch (CPU tensors)
+
+def _forward_torch(x: Tensor, weights: Sequence[Tensor], dtype: torch.dtype, out_f32: bool):
+    """(y, hidden): float32 sums of exact products, rounded where the kernels round (x, W, every hidden activation, y)."""
+    h = x.to(dtype).float()
+    hidden = []
+    for l, w in enumerate(weights):
+        z = h @ w.to(dtype).float().t()
+        if l < len(weights) - 1:
+            h = torch.relu(z).to(dtype).float()
+            hidden.append(h)
+    return (z if out_f32 else z.to(dtype)), hidden
+
+
+def _backward_torch(x: Tensor, weights: Sequence[Tensor], hidden: Sequence[Tensor], g: Tensor, dtype: torch.dtype,
+                    need_x: bool, need_p: bool):
+    """(dL/dx in x's dtype, dL/dparams flat float32, [dZ_l]) with dZ_l rounded as the kernels round it."""
+    dz = g.to(dtype).float()
+    dzs, g_w = [dz], []
+    g_x = None
+    for l in range(len(weights) - 1, -1, -1):
+        h_prev = hidden[l - 1] if l > 0 else x.to(dtype).float()
+        if need_p:
+            g_w.append(dz.t() @ h_prev)
+        if l == 0 and not need_x:
+            break
+        dh = dz @ weights[l].to(dtype).float()
+        if l > 0:
+            dz = (dh * (h_prev > 0)).to(dtype).float()
+            dzs.append(dz)
+        else:
+            g_x = dh.to(x.dtype)
+    g_p = torch.cat([w.reshape(-1) for w in reversed(g_w)]) if need_p else None
+    return g_x, g_p, dzs[::-1]
+
+
+# ---------------------------------------------------------------- autograd
+
+class _MLPFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, params: Tensor, mlp: "FusedMLP"):
+        N = x.shape[0]
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        out_f32 = mlp.out_dtype == torch.float32
+        ctx.mlp = mlp
+        if N == 0:
+            ctx.save_for_backward(x, params)
+            return torch.empty(0, mlp.n_output_dims, dtype=mlp.out_dtype, device=x.device)
+        if not x.is_cuda:
+            y, hidden = _forward_torch(x, mlp._views(params), mlp.dtype, out_f32)
+            ctx.save_for_backward(x, params, *hidden)
+            return y
+        B.require_device(x, params)
+        elem = B.ELEM_CODES[mlp.dtype]
+        fwd_img, bwd_img = mlp._images(params)
+        y = torch.empty(N, mlp.n_output_dims, dtype=mlp.out_dtype, device=x.device)
+        hidden = torch.empty(mlp.n_hidden_layers, N, mlp.n_neurons, dtype=mlp.dtype, device=x.device) if need_grad else None
+        with torch.cuda.device(x.device):
+            B.call("nfa_mlp_fwd", elem, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(fwd_img), N, *mlp._shape, B.ptr(y),
+                   B.ELEM_CODES[y.dtype], B.ptr(hidden), int(need_grad), B.stream())
+        if need_grad:
+            ctx.save_for_backward(x, params, hidden, bwd_img)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        need_x, need_p = ctx.needs_input_grad[:2]
+        if g_y is None or not (need_x or need_p):
+            return None, None, None
+        x, params, *saved = ctx.saved_tensors
+        g_x, g_p = _MLPBwdFn.apply(x, params, g_y, ctx.mlp, need_x, need_p, *saved)
+        return g_x, g_p, None
+
+
+class _MLPBwdFn(torch.autograd.Function):
+    """The backward as a function ``(x, params, g_y) -> (g_x, g_params)`` of its own, so that differentiating it again
+    (``create_graph=True``) fails with a message that names the module instead of a missing ``grad_fn``."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, params: Tensor, g: Tensor, mlp: "FusedMLP", need_x: bool, need_p: bool, *saved):
+        ctx.set_materialize_grads(False)
+        N = x.shape[0]
+        if N == 0:
+            return (torch.empty_like(x) if need_x else None), (torch.zeros_like(params) if need_p else None)
+        if g.dtype not in (torch.float32, mlp.dtype):
+            g = g.float()
+        g = g.contiguous()
+        if not x.is_cuda:
+            g_x, g_p, _ = _backward_torch(x, mlp._views(params), saved, g, mlp.dtype, need_x, need_p)
+            return g_x, g_p
+        hidden, bwd_img = saved
+        elem, dev = B.ELEM_CODES[mlp.dtype], x.device
+        dz = torch.empty(mlp.n_hidden_layers, N, mlp.n_neurons, dtype=mlp.dtype, device=dev)
+        dz_out = g if g.dtype == mlp.dtype else torch.empty(N, mlp.n_output_dims, dtype=mlp.dtype, device=dev)
+        g_x = torch.empty_like(x) if need_x else None
+        g_p = None
+        with torch.cuda.device(dev):
+            B.call("nfa_mlp_bwd_data", elem, B.ptr(g), B.ELEM_CODES[g.dtype], B.ptr(hidden), B.ptr(bwd_img), N, *mlp._shape,
+                   B.ptr(dz), None if dz_out is g else B.ptr(dz_out), B.ptr(g_x), B.ELEM_CODES[x.dtype], B.stream())
+            if need_p:
+                P = params.numel()
+                partials = torch.empty(wgrad_slices(N) * P, dtype=torch.float32, device=dev)
+                g_p = torch.empty(P, dtype=torch.float32, device=dev)
+                B.call("nfa_mlp_bwd_weights", elem, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(hidden), B.ptr(dz), B.ptr(dz_out), N,
+                       *mlp._shape, B.ptr(partials), partials.numel(), B.ptr(g_p), B.stream())
+        return g_x, g_p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gg_x, gg_p):
+        raise NotImplementedError("FusedMLP: the second order (differentiating dL/dx or dL/dparams again, create_graph=True) is not "
+                                  "implemented; a field with an Eikonal term keeps a torch MLP")
+
+
+class FusedMLP(nn.Module):
+    """tiny-cuda-nn's ``FullyFusedMLP``: ``n_hidden_layers + 1`` weight matrices, no biases, ReLU on the hidden layers and
+    no output activation, as one native launch forward and three backward.
+
+    ``n_neurons`` 64 or 128, ``n_hidden_layers`` 1..4, ``n_input_dims`` 1..256, ``n_output_dims`` 1..32; a configuration
+    whose packed weights do not fit the 160 KiB of LDS of a compute unit is refused here, with the sizes in the message.
+    ``dtype`` (fp16 or bf16) is the type of the weights as the kernels see them, of the hidden activations and of the
+    gradients between the layers; sums are float32.  The parameters are float32 masters in ONE flat ``nn.Parameter``
+    (``params``), each matrix in torch's ``Linear`` layout ``[out, in]``: :meth:`weight` is a view of one,
+    :meth:`linear_weights` / :meth:`load_linear_weights` exchange them with ``nn.Linear(bias=False)`` layers.  They are
+    initialised as tcnn does: Xavier uniform per matrix, drawn from ``generator`` (default: a generator seeded 1337).
+
+    ``forward(x)``: ``x [N, n_input_dims]`` float32 or ``dtype``, contiguous; a float32 ``x`` is rounded to ``dtype`` as
+    the kernel loads it.  Returns ``[N, n_output_dims]`` in ``dtype``, or with ``out_dtype=torch.float32`` the float32
+    accumulators unrounded.  ``dL/dx`` comes back in ``x``'s dtype, ``dL/dparams`` float32 without atomics: the same bits
+    on every run.  ``torch.autocast`` changes nothing: the module handles its own precision.  CPU tensors take a torch
+    restatement with the same rounding points.  Differentiating the gradients again raises ``NotImplementedError``.
+    """
+
+    def __init__(self, n_input_dims: int, n_output_dims: int, n_neurons: int = 64, n_hidden_layers: int = 2,
+                 dtype: torch.dtype = torch.float16, out_dtype: Optional[torch.dtype] = None,
+                 generator: Optional[torch.Generator] = None):
+        super().__init__()
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"FusedMLP: dtype {dtype}: torch.float16 or torch.bfloat16")
+        if out_dtype not in (None, dtype, torch.float32):
+            raise ValueError(f"FusedMLP: out_dtype {out_dtype}: None, dtype ({dtype}) or torch.float32")
+        if n_neurons not in WIDTHS:
+            raise ValueError(f"FusedMLP: n_neurons {n_neurons}: one of {WIDTHS} (wider networks stay torch)")
+        if not 1 <= n_hidden_layers <= MAX_HIDDEN_LAYERS:
+            raise ValueError(f"FusedMLP: n_hidden_layers {n_hidden_layers}: 1 to {MAX_HIDDEN_LAYERS}")
+        if not 1 <= n_input_dims <= MAX_INPUT_DIMS:
+            raise ValueError(f"FusedMLP: n_input_dims {n_input_dims}: 1 to {MAX_INPUT_DIMS}")
+        if not 1 <= n_output_dims <= MAX_OUTPUT_DIMS:
+            raise ValueError(f"FusedMLP: n_output_dims {n_output_dims}: 1 to {MAX_OUTPUT_DIMS}")
+        fwd, bwd = image_elems(n_input_dims, n_output_dims, n_neurons, n_hidden_layers)
+        if max(fwd, bwd) * 2 + STAGE_BYTES > LDS_BUDGET:
+            raise ValueError(f"FusedMLP: the packed weights do not fit the LDS: forward image {fwd * 2} B, backward image {bwd * 2} B, "
+                             f"each with {STAGE_BYTES} B of store staging, against {LDS_BUDGET} B per compute unit "
+                             f"(n_input_dims {n_input_dims}, n_output_dims {n_output_dims}, n_neurons {n_neurons}, "
+                             f"n_hidden_layers {n_hidden_layers})")
+        self.n_input_dims, self.n_output_dims = n_input_dims, n_output_dims
+        self.n_neurons, self.n_hidden_layers = n_neurons, n_hidden_layers
+        self.dtype, self.out_dtype = dtype, out_dtype or dtype
+        self._shape = (n_input_dims, n_output_dims, n_neurons, n_hidden_layers)
+        self._dims = layer_dims(*self._shape)
+        self._offsets = [0]
+        for o, i in self._dims:
+            self._offsets.append(self._offsets[-1] + o * i)
+        self._image_elems = (fwd, bwd)
+        self._packed = None   # (key, forward image, backward image)
+        if generator is None:
+            generator = torch.Generator().manual_seed(1337)
+        init = []
+        for o, i in self._dims:
+            bound = math.sqrt(6.0 / (i + o))
+            init.append((torch.rand(o * i, generator=generator, dtype=torch.float32) * 2.0 - 1.0) * bound)
+        self.params = nn.Parameter(torch.cat(init))
+
+    @property
+    def n_layers(self) -> int:
+        return self.n_hidden_layers + 1
+
+    def _views(self, params: Tensor) -> List[Tensor]:
+        return [params[self._offsets[l]:self._offsets[l + 1]].view(*self._dims[l]) for l in range(self.n_layers)]
+
+    def weight(self, l: int) -> Tensor:
+        """The view ``[out_l, in_l]`` of matrix ``l`` in ``params``."""
+        return self._views(self.params)[l]
+
+    def linear_weights(self) -> List[Tensor]:
+        """Copies of the matrices, for ``nn.Linear(bias=False).weight``."""
+        return [w.detach().clone() for w in self._views(self.params)]
+
+    @torch.no_grad()
+    def load_linear_weights(self, weights: Sequence[Tensor]) -> None:
+        if len(weights) != self.n_layers:
+            raise ValueError(f"FusedMLP: {len(weights)} matrices for {self.n_layers} layers")
+        for l, (w, v) in enumerate(zip(weights, self._views(self.params))):
+            if tuple(w.shape) != tuple(v.shape):
+                raise ValueError(f"FusedMLP: matrix {l} is {tuple(w.shape)}, expected {tuple(v.shape)}")
+            v.copy_(w)
+
+    def _images(self, params: Tensor):
+        """The packed images of the current masters: one small launch per change of ``params``."""
+        key = (params.data_ptr(), params._version, params.device)
+        if self._packed is None or self._packed[0] != key:
+            fwd = torch.empty(self._image_elems[0], dtype=self.dtype, device=params.device)
+            bwd = torch.empty(self._image_elems[1], dtype=self.dtype, device=params.device)
+            with torch.cuda.device(params.device):
+                B.call("nfa_mlp_pack_weights", B.ELEM_CODES[self.dtype], B.ptr(params), *self._shape, B.ptr(fwd), fwd.numel(),
+                       B.ptr(bwd), bwd.numel(), B.stream())
+            self._packed = (key, fwd, bwd)
+        return self._packed[1], self._packed[2]
+
+    def forward(self, x: Tensor) -> Tensor:
+        if x.dim() != 2 or x.shape[1] != self.n_input_dims:
+            raise ValueError(f"FusedMLP: x must be [N, {self.n_input_dims}], got {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, self.dtype):
+            raise TypeError(f"FusedMLP: x is {x.dtype}: torch.float32 or the network's {self.dtype}")
+        with torch.autocast(x.device.type, enabled=False):
+            return _MLPFn.apply(x.contiguous(), self.params.float().contiguous(), self)
+
+    def extra_repr(self) -> str:
+        return (f"{self.n_input_dims} -> {' -> '.join([str(self.n_neurons)] * self.n_hidden_layers)} -> {self.n_output_dims}, "
+                f"dtype={self.dtype}, out_dtype={self.out_dtype}")
+
+
+_TCNN_KEYS = ("otype", "activation", "output_activation", "n_neurons", "n_hidden_layers")
+
+
+def mlp_from_tcnn_config(n_input_dims: int, n_output_dims: int, config: dict, dtype: torch.dtype = torch.float16,
+                         out_dtype: Optional[torch.dtype] = None, generator: Optional[torch.Generator] = None) -> FusedMLP:
+    """A :class:`FusedMLP` from a tiny-cuda-nn network config: ``{"otype": "FullyFusedMLP", "activation": "ReLU",
+    "output_activation": "None", "n_neurons": 64 | 128, "n_hidden_layers": 1..4}``.  Anything else raises ``ValueError``
+    with the offending key in the message (defaults are tcnn's: 128 neurons, 5 hidden layers, so give both)."""
+    for k in config:
+        if k not in _TCNN_KEYS:
+            raise ValueError(f"mlp_from_tcnn_config: key '{k}' is not supported (supported: {', '.join(_TCNN_KEYS)})")
+    for k, want, default in (("otype", "FullyFusedMLP", "FullyFusedMLP"), ("activation", "ReLU", "ReLU"),
+                             ("output_activation", "None", "None")):
+        if config.get(k, default) != want:
+            raise ValueError(f"mlp_from_tcnn_config: '{k}': {config.get(k)!r} is not supported, only {want!r}")
+    n_neurons, n_hidden = config.get("n_neurons", 128), config.get("n_hidden_layers", 5)
+    if n_neurons not in WIDTHS:
+        raise ValueError(f"mlp_from_tcnn_config: 'n_neurons': {n_neurons!r} is not supported, one of {WIDTHS}")
+    if not (isinstance(n_hidden, int) and 1 <= n_hidden <= MAX_HIDDEN_LAYERS):
+        raise ValueError(f"mlp_from_tcnn_config: 'n_hidden_layers': {n_hidden!r} is not supported, 1 to {MAX_HIDDEN_LAYERS}")
+    return FusedMLP(n_input_dims, n_output_dims, n_neurons, n_hidden, dtype=dtype, out_dtype=out_dtype, generator=generator)
