@@ -1041,11 +1041,11 @@ int nfa_generate_rays_chunk(void);   /* rays per chunk of the backward's reducti
  *   H_0 = relu(x W_0^T), H_l = relu(H_{l-1} W_l^T), y = H_last W_L^T.
  * Shapes: elem NFA_ELEM_F16 or NFA_ELEM_BF16 (the network's type: weights, hidden activations, dZ), width 64 or 128,
  * n_hidden 1..4, n_in 1..256, n_out 1..32; and the packed images below must fit the 160 KiB of LDS of a compute unit
- * beside 16,896 B of store staging (the message gives the sizes).  All four entries check, in this order: elem, width,
+ * beside 16,896 B of store staging (the message gives the sizes).  All five entries check, in this order: elem, width,
  * n_hidden, n_in, n_out, n_points >= 0, the LDS budget, the other element codes; then n_points == 0 returns NFA_OK
  * whatever the pointers are; then null pointers and alignment.  Nothing reaches the GPU before every check passed.
- * Rounding (always to nearest even): x and the masters to `elem`, every hidden activation after its ReLU, every dZ_l after
- * its mask, y / grad_x once as stored; float32 outputs are the float32 accumulators unrounded.
+ * Rounding (always to nearest even): x, v and the masters to `elem`, every hidden activation after its ReLU, every dZ_l and
+ * T_l after its mask, y / grad_x / u once as stored; float32 outputs are the float32 accumulators unrounded.
  *
  * nfa_mlp_pack_weights: params = the float32 masters, W_0 .. W_L flat in that order, to the two images the passes read
  * (one launch).  A packed matrix A [rows, k] is a run of 1 KiB blocks (m, q), m < ceil(rows / 32) major, q < ceil(k / 16):
@@ -1075,12 +1075,24 @@ int nfa_mlp_bwd_data(int32_t elem, const void *grad_y, int32_t g_elem, const voi
  * s = clamp(ceil(n_points / NFA_MLP_WGRAD_MIN_SLICE), 1, NFA_MLP_WGRAD_MAX_SLICES): a function of n_points alone.  A
  * workgroup per (slice, layer) writes its float32 partial to partials [n_slices, n_params] (scratch of partial_floats floats,
  * need not be initialised; too small is NFA_EINVAL), the second launch adds the slices in ascending order.  hidden, dz:
- * as above, 16-byte aligned; dz_out [n_points, n_out] of elem. */
+ * as above, 16-byte aligned; dz_out [n_points, n_out] of elem.
+ * The second order reuses this entry as it stands: called with x := v and hidden := tangent of nfa_mlp_tangent (and dz, dz_out
+ * of the first backward) it returns ds/dW_l = dZ_l^T T_{l-1}. */
 #define NFA_MLP_WGRAD_MIN_SLICE 256
 #define NFA_MLP_WGRAD_MAX_SLICES 256
 int nfa_mlp_bwd_weights(int32_t elem, const void *x, int32_t x_elem, const void *hidden, const void *dz, const void *dz_out,
                         int64_t n_points, int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden, float *partials,
                         int64_t partial_floats, float *grad_params, nfa_stream_t stream);
+/* The second order (double backward), one launch for the whole network.  With v [n_points, n_in] the cotangent of grad_x and
+ * s = <v, grad_x>: T_{-1} = v rounded to elem (v_elem: NFA_ELEM_F32 or elem; loaded as nfa_mlp_fwd loads x),
+ * T_l = (T_{l-1} W_l^T) * (H_l > 0) rounded to elem, l < n_hidden, with H from `hidden` as nfa_mlp_fwd saved it (the saved
+ * mask, not a ReLU of the tangent), and u = T_last W_L^T = ds/dgrad_y.  The backward is linear in grad_y and the masks are
+ * piecewise constant, so this is exact; ds/dx is zero.  Writes u [n_points, n_out] of u_elem (elem: rounded once; NFA_ELEM_F32:
+ * the accumulators) and tangent [n_hidden, n_points, width] (elem, 8-byte aligned; T_0 .. T_{L-1}; optional: NULL when no
+ * weight gradient is wanted), laid out as `hidden`: ds/dW_l = dZ_l^T T_{l-1} is nfa_mlp_bwd_weights on (v, tangent). */
+int nfa_mlp_tangent(int32_t elem, const void *v, int32_t v_elem, const void *hidden, const void *fwd_image, int64_t n_points,
+                    int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden, void *tangent, void *u, int32_t u_elem,
+                    nfa_stream_t stream);
 
 #ifdef __cplusplus
 }

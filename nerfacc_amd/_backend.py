@@ -169,6 +169,7 @@ _SIGS = {
     "nfa_mlp_fwd": [_i32, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp],
     "nfa_mlp_bwd_data": [_i32, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp],
     "nfa_mlp_bwd_weights": [_i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
+    "nfa_mlp_tangent": [_i32, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],

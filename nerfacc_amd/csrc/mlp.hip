@@ -4,6 +4,10 @@
 //   forward     H_0 = relu(x W_0^T), H_l = relu(H_{l-1} W_l^T), y = H_last W_L^T          one launch (nfa_mlp_fwd)
 //   data grad   dZ_L = g, dH_{l-1} = dZ_l W_l, dZ_{l-1} = dH_{l-1} * (H_{l-1} > 0), dx = dZ_0 W_0   one launch (nfa_mlp_bwd_data)
 //   weight grad dW_l = dZ_l^T H_{l-1}, H_{-1} = x                                         split-K + ordered sum (nfa_mlp_bwd_weights)
+//   tangent     T_{-1} = v, T_l = (T_{l-1} W_l^T) * (H_l > 0), u = T_last W_L^T           one launch (nfa_mlp_tangent)
+//
+// The tangent pass is the second order: with v the cotangent of dx and s = <v, dx>, u = ds/dg and ds/dW_l = dZ_l^T T_{l-1}, which is
+// the weight gradient pass run on (v, T) in the place of (x, H).  The masks are the saved ones, never a ReLU of the tangent.
 //
 // Everything works TRANSPOSED, with the weights as the A operand of v_mfma_f32_32x32x16_{f16,bf16}: a wave owns 32 points, a point
 // is a COLUMN of every tile and so stays on lane (point & 31) of both lane halves through all layers.  The 32x32 float32 result
@@ -18,7 +22,7 @@
 // The forward image holds W_l, the backward image W_l^T (rows = inputs of the layer, k = its outputs).
 //
 // Rounding points (all to nearest even, the compiler's conversion; never the pkrtz form): x and the masters to the half type
-// on load / when packed, every hidden activation after its ReLU, every dZ_l after its mask, y and dx once as stored (float32
+// on load / when packed, every hidden activation after its ReLU, every dZ_l and T_l after its mask, y, dx and u once as stored (float32
 // outputs are the accumulators themselves).  Products are exact in float32 and summed by the MFMA in float32.
 //
 // EXEC is all ones around every MFMA: a partial tile clamps the point index of its loads and masks only its stores.
@@ -31,7 +35,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int MLP_WAVES = 4;                              // waves per workgroup of the two fused passes
+constexpr int MLP_WAVES = 4;                              // waves per workgroup of the fused passes
 constexpr int STAGE_LD = 33;                              // floats per row of a wave's 32 x 32 store staging tile (odd: no conflicts)
 constexpr int64_t STAGE_BYTES = (int64_t)MLP_WAVES * 32 * STAGE_LD * 4;
 constexpr int64_t LDS_BUDGET = 160 * 1024;
@@ -169,6 +173,22 @@ __device__ __forceinline__ void store_tile_row(uint16_t *m, int64_t p, int t, in
     d[6] = nfa_v2u{f1[2], f1[3]};
 }
 
+// acc *= (H > 0) for tile t of row p of a saved [*, W] activation matrix H: the pieces store_tile_row wrote, register for register.
+template <class E, int W>
+__device__ __forceinline__ void mask_tile_row(f32x16 &acc, const uint16_t *m, int64_t p, int t, int h)
+{
+    const nfa_v2u *hp = reinterpret_cast<const nfa_v2u *>(m + p * W + 32 * t + 4 * h);
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+        const nfa_v2u hv = hp[2 * gq];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float a = unpack_half<E>(hv[i >> 1], i & 1);
+            acc[4 * gq + i] = a > 0.f ? acc[4 * gq + i] : 0.f;
+        }
+    }
+}
+
 // A wave's 32 x 32 accumulator tile (row = column of the output matrix, column = point) to memory through its LDS staging
 // tile, so that stores run along the output rows: columns col0 .. col0+ncols-1 of rows row0 .. row0+nrows-1 of out [*, ld].
 template <class E>
@@ -200,13 +220,15 @@ __device__ __forceinline__ void stage_image(nfa_v4u *dst, const nfa_v4u *src, in
     __syncthreads();
 }
 
-// ---------------------------------------------------------------- forward
+// ---------------------------------------------------------------- forward and tangent forward
 
-template <class E, int W>
-__global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_fwd_kernel(Shape S, const void *__restrict__ x, int x_f32, int x_vec,
-                                                                      const uint16_t *__restrict__ image, int64_t image_elems,
-                                                                      int64_t N, void *__restrict__ y, int y_f32,
-                                                                      uint16_t *__restrict__ hidden)
+// The layer chain W_L act(... act(W_0 in)) over the workgroup's tiles, for both passes that run it.  Forward: act = ReLU, the
+// rounded activations go to `save` (the backward's `hidden`, optional).  TANGENT: act = the mask (mask_l > 0) of the activations
+// the forward saved, the rounded T_l go to `save` (optional): the derivative of the chain along `in`, which is linear in it.
+template <class E, int W, bool TANGENT>
+__device__ __forceinline__ void mlp_chain(const Shape &S, const void *__restrict__ in, int in_f32, int in_vec,
+                                          const uint16_t *__restrict__ image, int64_t image_elems, int64_t N, void *__restrict__ out,
+                                          int out_f32, const uint16_t *__restrict__ mask, uint16_t *__restrict__ save)
 {
     constexpr int MT = W / 32, KQ = W / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char mlp_lds[];
@@ -224,21 +246,26 @@ __global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_fwd_kernel(Shape S, 
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
         for (int q = 0; q < kq0; ++q) {
-            const nfa_v4u b = load_row8<E>(x, x_f32 != 0, pc, S.n_in, 16 * q + 8 * h, x_vec != 0);
+            const nfa_v4u b = load_row8<E>(in, in_f32 != 0, pc, S.n_in, 16 * q + 8 * h, in_vec != 0);
 #pragma unroll
             for (int m = 0; m < MT; ++m) acc[m] = mfma<E>(wimg[(m * kq0 + q) * 64 + lane], b, acc[m]);
         }
         int64_t off16 = (int64_t)MT * kq0 * 64;   // in 16-byte fragments
         nfa_v4u hf[KQ];
         for (int l = 1;; ++l) {
-            // H_{l-1} = relu(acc), rounded: the next product's B fragments, and what the backward reads
+            // H_{l-1} = relu(acc) (T_{l-1} = acc * (H_{l-1} > 0)), rounded: the next product's B fragments, and what the
+            // backward (the second weight gradient) reads
 #pragma unroll
             for (int t = 0; t < MT; ++t) {
+                if constexpr (TANGENT) {
+                    mask_tile_row<E, W>(acc[t], mask + (int64_t)(l - 1) * N * W, pc, t, h);
+                } else {
 #pragma unroll
-                for (int i = 0; i < 16; ++i) acc[t][i] = acc[t][i] < 0.f ? 0.f : acc[t][i];
+                    for (int i = 0; i < 16; ++i) acc[t][i] = acc[t][i] < 0.f ? 0.f : acc[t][i];
+                }
                 hf[2 * t] = acc_frag<E>(acc[t], 0);
                 hf[2 * t + 1] = acc_frag<E>(acc[t], 1);
-                if (hidden && p < N) store_tile_row<W>(hidden + (int64_t)(l - 1) * N * W, p, t, h, hf[2 * t], hf[2 * t + 1]);
+                if (save && p < N) store_tile_row<W>(save + (int64_t)(l - 1) * N * W, p, t, h, hf[2 * t], hf[2 * t + 1]);
             }
             if (l == S.n_hidden) break;
 #pragma unroll
@@ -256,8 +283,28 @@ __global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_fwd_kernel(Shape S, 
 #pragma unroll
         for (int q = 0; q < KQ; ++q) o = mfma<E>(wimg[off16 + q * 64 + lane], hf[q], o);
         const int64_t row0 = tile * 32;
-        stage_store<E>(o, st, y, y_f32 != 0, row0, (int)(N - row0 < 32 ? N - row0 : 32), S.n_out, 0, S.n_out, lane);
+        stage_store<E>(o, st, out, out_f32 != 0, row0, (int)(N - row0 < 32 ? N - row0 : 32), S.n_out, 0, S.n_out, lane);
     }
+}
+
+template <class E, int W>
+__global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_fwd_kernel(Shape S, const void *__restrict__ x, int x_f32, int x_vec,
+                                                                      const uint16_t *__restrict__ image, int64_t image_elems,
+                                                                      int64_t N, void *__restrict__ y, int y_f32,
+                                                                      uint16_t *__restrict__ hidden)
+{
+    mlp_chain<E, W, false>(S, x, x_f32, x_vec, image, image_elems, N, y, y_f32, nullptr, hidden);
+}
+
+// T_{-1} = v, T_l = (W_l T_{l-1}) * (H_l > 0), u = W_L T_{L-1}: the forward's chain on the forward image, masks from `hidden`
+template <class E, int W>
+__global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_tangent_kernel(Shape S, const void *__restrict__ v, int v_f32, int v_vec,
+                                                                          const uint16_t *__restrict__ hidden,
+                                                                          const uint16_t *__restrict__ image, int64_t image_elems,
+                                                                          int64_t N, uint16_t *__restrict__ tangent,
+                                                                          void *__restrict__ u, int u_f32)
+{
+    mlp_chain<E, W, true>(S, v, v_f32, v_vec, image, image_elems, N, u, u_f32, hidden, tangent);
 }
 
 // ---------------------------------------------------------------- data gradient
@@ -305,16 +352,7 @@ __global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_bwd_data_kernel(Shap
             const uint16_t *hl = hidden + (int64_t)l * N * W;
 #pragma unroll
             for (int t = 0; t < MT; ++t) {
-                const nfa_v2u *hp = reinterpret_cast<const nfa_v2u *>(hl + pc * W + 32 * t + 4 * h);
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const nfa_v2u hv = hp[2 * gq];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float a = unpack_half<E>(hv[i >> 1], i & 1);
-                        acc[t][4 * gq + i] = a > 0.f ? acc[t][4 * gq + i] : 0.f;
-                    }
-                }
+                mask_tile_row<E, W>(acc[t], hl, pc, t, h);
                 df[2 * t] = acc_frag<E>(acc[t], 0);
                 df[2 * t + 1] = acc_frag<E>(acc[t], 1);
                 if (p < N) store_tile_row<W>(dz + (int64_t)l * N * W, p, t, h, df[2 * t], df[2 * t + 1]);
@@ -600,5 +638,33 @@ int nfa_mlp_bwd_weights(int32_t elem, const void *x, int32_t x_elem, const void 
     NFA_CHECK_LAUNCH("nfa_mlp_bwd_weights");
     mlp_wgrad_sum_kernel<<<(unsigned)ceil_div64(P, 256), 256, 0, as_stream(stream)>>>(partials, n_slices, P, grad_params);
     NFA_CHECK_LAUNCH("nfa_mlp_bwd_weights (sum)");
+    return NFA_OK;
+}
+
+int nfa_mlp_tangent(int32_t elem, const void *v, int32_t v_elem, const void *hidden, const void *fwd_image, int64_t n_points,
+                    int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden, void *tangent, void *u, int32_t u_elem,
+                    nfa_stream_t stream)
+{
+    Shape S;
+    if (int rc = check_shape("nfa_mlp_tangent", elem, n_in, n_out, width, n_hidden, n_points, &S)) return rc;
+    NFA_REQUIRE(v_elem == NFA_ELEM_F32 || v_elem == elem, "nfa_mlp_tangent: v_elem %d: float32 or the network's type (%d)", v_elem, elem);
+    NFA_REQUIRE(u_elem == NFA_ELEM_F32 || u_elem == elem, "nfa_mlp_tangent: u_elem %d: float32 or the network's type (%d)", u_elem, elem);
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(v && hidden && fwd_image && u, "nfa_mlp_tangent: null pointer");
+    NFA_REQUIRE(aligned_to(fwd_image, 16) && aligned_to(hidden, 8) && aligned_to(tangent, 8) && aligned_to(v, v_elem == NFA_ELEM_F32 ? 4 : 2) &&
+                aligned_to(u, u_elem == NFA_ELEM_F32 ? 4 : 2),
+                "nfa_mlp_tangent: misaligned pointer (image 16, hidden and tangent 8, v and u their element)");
+    const int64_t img = S.fwd_off(S.layers()), lds = img * 2 + STAGE_BYTES;
+    int rc = NFA_OK;
+    dispatch_mlp(elem, width, [&](auto tag, auto w) {
+        using E = typename decltype(tag)::type;
+        auto kern = mlp_tangent_kernel<E, decltype(w)::value>;
+        if ((rc = allow_lds("nfa_mlp_tangent", kern, lds)) != NFA_OK) return;
+        kern<<<fused_grid(n_points, lds), MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(
+            S, v, v_elem == NFA_ELEM_F32, row8_vec(v, n_in), static_cast<const uint16_t *>(hidden),
+            static_cast<const uint16_t *>(fwd_image), img, n_points, static_cast<uint16_t *>(tangent), u, u_elem == NFA_ELEM_F32);
+    });
+    if (rc != NFA_OK) return rc;
+    NFA_CHECK_LAUNCH("nfa_mlp_tangent");
     return NFA_OK;
 }

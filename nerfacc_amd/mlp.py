@@ -92,6 +92,23 @@ def _backward_torch(x: Tensor, weights: Sequence[Tensor], hidden: Sequence[Tenso
     return g_x, g_p, dzs[::-1]
 
 
+def _tangent_torch(v: Tensor, weights: Sequence[Tensor], hidden: Sequence[Tensor], dzs: Sequence[Tensor], dtype: torch.dtype,
+                   need_p: bool):
+    """The second order: (u float32 unrounded, ds/dparams flat float32, [T_{-1}, T_0 .. T_{L-1}]) for the cotangent ``v`` of
+    dL/dx.  The derivative of the network along ``v`` with the SAVED masks (``hidden`` > 0, never a ReLU of the tangent),
+    every ``T_l`` rounded after its mask as the tangent kernel rounds it; ``ds/dW_l = dZ_l^T T_{l-1}`` with the first
+    backward's ``dZ_l``."""
+    t = v.to(dtype).float()
+    ts = [t]
+    for l, w in enumerate(weights):
+        z = t @ w.to(dtype).float().t()
+        if l < len(weights) - 1:
+            t = (z * (hidden[l] > 0)).to(dtype).float()
+            ts.append(t)
+    g_p = torch.cat([(dz.t() @ t).reshape(-1) for dz, t in zip(dzs, ts)]) if need_p else None
+    return z, g_p, ts
+
+
 # ---------------------------------------------------------------- autograd
 
 class _MLPFn(torch.autograd.Function):
@@ -116,8 +133,8 @@ class _MLPFn(torch.autograd.Function):
         with torch.cuda.device(x.device):
             B.call("nfa_mlp_fwd", elem, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(fwd_img), N, *mlp._shape, B.ptr(y),
                    B.ELEM_CODES[y.dtype], B.ptr(hidden), int(need_grad), B.stream())
-        if need_grad:
-            ctx.save_for_backward(x, params, hidden, bwd_img)
+        if need_grad:   # the second order runs the chain again on the forward image
+            ctx.save_for_backward(x, params, hidden, bwd_img, *([fwd_img] if mlp.second_order else []))
         return y
 
     @staticmethod
@@ -132,11 +149,14 @@ class _MLPFn(torch.autograd.Function):
 
 class _MLPBwdFn(torch.autograd.Function):
     """The backward as a function ``(x, params, g_y) -> (g_x, g_params)`` of its own, so that differentiating it again
-    (``create_graph=True``) fails with a message that names the module instead of a missing ``grad_fn``."""
+    (``create_graph=True``) fails with a message that names the module instead of a missing ``grad_fn``, or, for a module
+    with ``second_order=True``, runs the tangent pass: with ``v`` the cotangent of ``g_x`` and ``s = <v, g_x>``,
+    ``T_{-1} = v``, ``T_l = M_l * (W_l T_{l-1})``, ``ds/dg_y = W_L T_{L-1}``, ``ds/dW_l = dZ_l^T T_{l-1}``, ``ds/dx = 0``."""
 
     @staticmethod
     def forward(ctx, x: Tensor, params: Tensor, g: Tensor, mlp: "FusedMLP", need_x: bool, need_p: bool, *saved):
         ctx.set_materialize_grads(False)
+        ctx.mlp, ctx.g_dtype, ctx.g_shape, ctx.n_saved = mlp, g.dtype, g.shape, len(saved)
         N = x.shape[0]
         if N == 0:
             return (torch.empty_like(x) if need_x else None), (torch.zeros_like(params) if need_p else None)
@@ -144,9 +164,12 @@ class _MLPBwdFn(torch.autograd.Function):
             g = g.float()
         g = g.contiguous()
         if not x.is_cuda:
-            g_x, g_p, _ = _backward_torch(x, mlp._views(params), saved, g, mlp.dtype, need_x, need_p)
+            with torch.autocast("cpu", enabled=False):   # a backward called under autocast must not round the float32 sums
+                g_x, g_p, dzs = _backward_torch(x, mlp._views(params), saved, g, mlp.dtype, need_x, need_p)
+            if mlp.second_order:   # retained only under create_graph=True: a plain backward runs this in no-grad mode
+                ctx.save_for_backward(params, *saved, *dzs)
             return g_x, g_p
-        hidden, bwd_img = saved
+        hidden, bwd_img, *fwd_img = saved
         elem, dev = B.ELEM_CODES[mlp.dtype], x.device
         dz = torch.empty(mlp.n_hidden_layers, N, mlp.n_neurons, dtype=mlp.dtype, device=dev)
         dz_out = g if g.dtype == mlp.dtype else torch.empty(N, mlp.n_output_dims, dtype=mlp.dtype, device=dev)
@@ -161,18 +184,57 @@ class _MLPBwdFn(torch.autograd.Function):
                 g_p = torch.empty(P, dtype=torch.float32, device=dev)
                 B.call("nfa_mlp_bwd_weights", elem, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(hidden), B.ptr(dz), B.ptr(dz_out), N,
                        *mlp._shape, B.ptr(partials), partials.numel(), B.ptr(g_p), B.stream())
+        if mlp.second_order:   # retained only under create_graph=True: a plain backward runs this in no-grad mode
+            ctx.save_for_backward(hidden, dz, dz_out, *fwd_img)
         return g_x, g_p
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gg_x, gg_p):
-        raise NotImplementedError("FusedMLP: the second order (differentiating dL/dx or dL/dparams again, create_graph=True) is not "
-                                  "implemented; a field with an Eikonal term keeps a torch MLP")
+        mlp = ctx.mlp
+        if not mlp.second_order:
+            raise NotImplementedError("FusedMLP: the second order (differentiating dL/dx or dL/dparams again, create_graph=True) is not "
+                                      "enabled for this module: construct it with second_order=True (that of dL/dx, which an "
+                                      "Eikonal term needs)")
+        if gg_p is not None:
+            raise NotImplementedError("FusedMLP: the second order of dL/dparams (a cotangent for dL/dparams) is not implemented, "
+                                      "only that of dL/dx")
+        need_p, need_g = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        none = (None,) * (6 + ctx.n_saved)
+        if gg_x is None or not (need_p or need_g):
+            return none
+        N, P = gg_x.shape[0], mlp._offsets[-1]
+        v = gg_x.contiguous()
+        u_dtype = ctx.g_dtype if ctx.g_dtype in (torch.float32, mlp.dtype) else torch.float32
+        if N == 0:
+            u = torch.empty(ctx.g_shape, dtype=ctx.g_dtype, device=v.device) if need_g else None
+            return (None, torch.zeros(P, dtype=torch.float32, device=v.device) if need_p else None, u) + none[3:]
+        L = mlp.n_hidden_layers
+        if not v.is_cuda:
+            params, *saved = ctx.saved_tensors
+            hidden, dzs = saved[:L], saved[L:]
+            with torch.autocast("cpu", enabled=False):
+                u, g_p, _ = _tangent_torch(v, mlp._views(params), hidden, dzs, mlp.dtype, need_p)
+            return (None, g_p, u.to(ctx.g_dtype) if need_g else None) + none[3:]
+        hidden, dz, dz_out, fwd_img = ctx.saved_tensors
+        elem, dev = B.ELEM_CODES[mlp.dtype], v.device
+        tangent = torch.empty(L, N, mlp.n_neurons, dtype=mlp.dtype, device=dev) if need_p else None
+        u = torch.empty(N, mlp.n_output_dims, dtype=u_dtype, device=dev)
+        g_p = None
+        with torch.cuda.device(dev):
+            B.call("nfa_mlp_tangent", elem, B.ptr(v), B.ELEM_CODES[v.dtype], B.ptr(hidden), B.ptr(fwd_img), N, *mlp._shape,
+                   B.ptr(tangent), B.ptr(u), B.ELEM_CODES[u_dtype], B.stream())
+            if need_p:   # ds/dW_l = dZ_l^T T_{l-1}: the weight gradient pass on (v, T) in the place of (x, H)
+                partials = torch.empty(wgrad_slices(N) * P, dtype=torch.float32, device=dev)
+                g_p = torch.empty(P, dtype=torch.float32, device=dev)
+                B.call("nfa_mlp_bwd_weights", elem, B.ptr(v), B.ELEM_CODES[v.dtype], B.ptr(tangent), B.ptr(dz), B.ptr(dz_out), N,
+                       *mlp._shape, B.ptr(partials), partials.numel(), B.ptr(g_p), B.stream())
+        return (None, g_p, (u if u.dtype == ctx.g_dtype else u.to(ctx.g_dtype)) if need_g else None) + none[3:]
 
 
 class FusedMLP(nn.Module):
     """tiny-cuda-nn's ``FullyFusedMLP``: ``n_hidden_layers + 1`` weight matrices, no biases, ReLU on the hidden layers and
-    no output activation, as one native launch forward and three backward.
+    no output activation, as one native launch forward and three backward (and, on request, three for the second order).
 
     ``n_neurons`` 64 or 128, ``n_hidden_layers`` 1..4, ``n_input_dims`` 1..256, ``n_output_dims`` 1..32; a configuration
     whose packed weights do not fit the 160 KiB of LDS of a compute unit is refused here, with the sizes in the message.
@@ -186,12 +248,21 @@ class FusedMLP(nn.Module):
     the kernel loads it.  Returns ``[N, n_output_dims]`` in ``dtype``, or with ``out_dtype=torch.float32`` the float32
     accumulators unrounded.  ``dL/dx`` comes back in ``x``'s dtype, ``dL/dparams`` float32 without atomics: the same bits
     on every run.  ``torch.autocast`` changes nothing: the module handles its own precision.  CPU tensors take a torch
-    restatement with the same rounding points.  Differentiating the gradients again raises ``NotImplementedError``.
+    restatement with the same rounding points.
+
+    ``second_order=True`` makes ``dL/dx`` differentiable once more (``create_graph=True``: an Eikonal term on an SDF field's
+    normals): one more fused launch, the tangent pass, and the weight gradient passes again.  For a ReLU network this is
+    exact: ``dL/dx`` is linear in ``dL/dy`` and in each matrix and its masks are piecewise constant, so the gradient of
+    ``<v, dL/dx>`` towards ``x`` is zero (``None``), towards ``dL/dy`` it is the network's derivative along ``v`` and towards
+    the masters a weight gradient with the tangent activations in the place of the activations; float32, without atomics,
+    the same bits on every run.  It costs memory only under ``create_graph=True``, where the graph keeps the ``dZ_l`` alive.
+    The derivative of ``dL/dparams`` and a third order raise.  Without it (the default) differentiating the gradients again
+    raises ``NotImplementedError``.
     """
 
     def __init__(self, n_input_dims: int, n_output_dims: int, n_neurons: int = 64, n_hidden_layers: int = 2,
                  dtype: torch.dtype = torch.float16, out_dtype: Optional[torch.dtype] = None,
-                 generator: Optional[torch.Generator] = None):
+                 generator: Optional[torch.Generator] = None, second_order: bool = False):
         super().__init__()
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError(f"FusedMLP: dtype {dtype}: torch.float16 or torch.bfloat16")
@@ -214,6 +285,7 @@ class FusedMLP(nn.Module):
         self.n_input_dims, self.n_output_dims = n_input_dims, n_output_dims
         self.n_neurons, self.n_hidden_layers = n_neurons, n_hidden_layers
         self.dtype, self.out_dtype = dtype, out_dtype or dtype
+        self.second_order = bool(second_order)
         self._shape = (n_input_dims, n_output_dims, n_neurons, n_hidden_layers)
         self._dims = layer_dims(*self._shape)
         self._offsets = [0]
@@ -275,14 +347,15 @@ class FusedMLP(nn.Module):
 
     def extra_repr(self) -> str:
         return (f"{self.n_input_dims} -> {' -> '.join([str(self.n_neurons)] * self.n_hidden_layers)} -> {self.n_output_dims}, "
-                f"dtype={self.dtype}, out_dtype={self.out_dtype}")
+                f"dtype={self.dtype}, out_dtype={self.out_dtype}" + (", second_order=True" if self.second_order else ""))
 
 
 _TCNN_KEYS = ("otype", "activation", "output_activation", "n_neurons", "n_hidden_layers")
 
 
 def mlp_from_tcnn_config(n_input_dims: int, n_output_dims: int, config: dict, dtype: torch.dtype = torch.float16,
-                         out_dtype: Optional[torch.dtype] = None, generator: Optional[torch.Generator] = None) -> FusedMLP:
+                         out_dtype: Optional[torch.dtype] = None, generator: Optional[torch.Generator] = None,
+                         second_order: bool = False) -> FusedMLP:
     """A :class:`FusedMLP` from a tiny-cuda-nn network config: ``{"otype": "FullyFusedMLP", "activation": "ReLU",
     "output_activation": "None", "n_neurons": 64 | 128, "n_hidden_layers": 1..4}``.  Anything else raises ``ValueError``
     with the offending key in the message (defaults are tcnn's: 128 neurons, 5 hidden layers, so give both)."""
@@ -298,4 +371,5 @@ def mlp_from_tcnn_config(n_input_dims: int, n_output_dims: int, config: dict, dt
         raise ValueError(f"mlp_from_tcnn_config: 'n_neurons': {n_neurons!r} is not supported, one of {WIDTHS}")
     if not (isinstance(n_hidden, int) and 1 <= n_hidden <= MAX_HIDDEN_LAYERS):
         raise ValueError(f"mlp_from_tcnn_config: 'n_hidden_layers': {n_hidden!r} is not supported, 1 to {MAX_HIDDEN_LAYERS}")
-    return FusedMLP(n_input_dims, n_output_dims, n_neurons, n_hidden, dtype=dtype, out_dtype=out_dtype, generator=generator)
+    return FusedMLP(n_input_dims, n_output_dims, n_neurons, n_hidden, dtype=dtype, out_dtype=out_dtype, generator=generator,
+                    second_order=second_order)
