@@ -1094,6 +1094,54 @@ int nfa_mlp_tangent(int32_t elem, const void *v, int32_t v_elem, const void *hid
                     int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden, void *tangent, void *u, int32_t u_elem,
                     nfa_stream_t stream);
 
+/* The same five passes for the reference's MLP class (ref: examples/radiance_fields/mlp.py, MLP), restricted to what the
+ * kernels hold: biases and skip connections on top of the network above.  The five entries above are these with bias = 0 and
+ * skip_mask = 0, bit for bit.
+ *   bias != 0: every layer has a float32 bias b_l [out_l], z_l = b_l + W_l in_l.  A bias is never rounded: it is the float32
+ *     value the layer's accumulator starts from.
+ *   skip_mask: bit l set (2 <= l <= n_hidden) makes layer l a "cat layer" whose input is [H_{l-1}, x], in this column order, x
+ *     rounded as layer 0 sees it; its matrix is [out_l, width + n_in].  The reference's skip_layer = s sets bit i + 1 for every
+ *     hidden layer 0 < i < n_hidden with i % s == 0; bit n_hidden is the output layer.
+ * Parameters (params, grad_params, each slice of partials): all matrices W_0 .. W_L in layer order, row-major [out_l, in_l] with
+ * in_l = width + n_in at a cat layer, then (bias != 0) all biases b_0 .. b_L in layer order: n_params = sum out_l in_l + sum out_l.
+ * Limits, checked by every entry after n_points >= 0 and before the LDS budget (a null descriptor first of all): bias is 0
+ * or 1; skip_mask has no bit outside 2 .. n_hidden; with a skip, n_in + width <= 256 (what the weight gradient stages for one
+ * layer).  The LDS budget counts the longer images and, for the forward pass, (n_hidden width + 32) 4 bytes of biases.  The
+ * other checks and their order are those of the entries above.
+ * Images: the forward image of a cat layer has width / 16 + ceil(n_in / 16) k-steps, the H part in the permuted k order and
+ * behind it the x part in the natural order 8 (lane >> 5) + j (its operand comes from memory, as layer 0's does); the backward
+ * image of a cat layer has width + n_in rows, rows >= width feed grad_x only; a cat OUTPUT layer's backward image is in natural
+ * k order throughout.  fwd_elems / bwd_elems follow the formulas of nfa_mlp_pack_weights with these in_l and k-step counts.
+ * The biases are not part of the images: nfa_mlp_net_fwd reads them as float32. */
+typedef struct nfa_mlp_desc {
+    int32_t n_in, n_out, width, n_hidden;
+    int32_t bias;        /* 0 or 1 */
+    int32_t skip_mask;   /* bit l: layer l takes [H_{l-1}, x] */
+} nfa_mlp_desc;
+/* params: the matrices of the layout above (the biases behind them are not read). */
+int nfa_mlp_net_pack_weights(int32_t elem, const nfa_mlp_desc *net, const float *params, void *fwd_image, int64_t fwd_elems,
+                             void *bwd_image, int64_t bwd_elems, nfa_stream_t stream);
+/* As nfa_mlp_fwd.  bias: b_0 .. b_L, float32, sum out_l of them in layer order (params + sum out_l in_l); read only when
+ * net->bias != 0, staged once per workgroup beside the image. */
+int nfa_mlp_net_fwd(int32_t elem, const nfa_mlp_desc *net, const void *x, int32_t x_elem, const void *fwd_image, const float *bias,
+                    int64_t n_points, void *y, int32_t y_elem, void *hidden, int32_t save_hidden, nfa_stream_t stream);
+/* As nfa_mlp_bwd_data; grad_x = dZ_0 W_0 + sum over the cat layers of dZ_l W_l[:, width:], summed in float32 in one accumulator
+ * and rounded once as stored.  The biases do not enter. */
+int nfa_mlp_net_bwd_data(int32_t elem, const nfa_mlp_desc *net, const void *grad_y, int32_t g_elem, const void *hidden,
+                         const void *bwd_image, int64_t n_points, void *dz, void *dz_out, void *grad_x, int32_t x_elem,
+                         nfa_stream_t stream);
+/* As nfa_mlp_bwd_weights, n_params as above: dW_l = dZ_l^T [H_{l-1}, x] at a cat layer, and db_l = sum_p dZ_l[p, :] in float32
+ * over the same slices, the points of a slice in a fixed order and the slices in ascending order: no atomics, bitwise
+ * reproducible.  zero_bias != 0 writes zeros into the bias segment instead: the second-order call (x := v, hidden := tangent)
+ * sets it, since the masks are piecewise constant and d<v, grad_x>/db is zero. */
+int nfa_mlp_net_bwd_weights(int32_t elem, const nfa_mlp_desc *net, const void *x, int32_t x_elem, const void *hidden, const void *dz,
+                            const void *dz_out, int64_t n_points, float *partials, int64_t partial_floats, float *grad_params,
+                            int32_t zero_bias, nfa_stream_t stream);
+/* As nfa_mlp_tangent: every accumulator starts at zero (a bias has no tangent) and a cat layer sees [T_{l-1}, v], the output
+ * layer included: u = W_L [T_{L-1}(, v)].  ds/dW_l = dZ_l^T [T_{l-1}(, v)] is nfa_mlp_net_bwd_weights on (v, tangent). */
+int nfa_mlp_net_tangent(int32_t elem, const nfa_mlp_desc *net, const void *v, int32_t v_elem, const void *hidden, const void *fwd_image,
+                        int64_t n_points, void *tangent, void *u, int32_t u_elem, nfa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,11 @@ class TraverseArgs(C.Structure):
     ]
 
 
+class MLPDesc(C.Structure):
+    """struct nfa_mlp_desc (include/nerfacc_hip.h)."""
+    _fields_ = [("n_in", _i32), ("n_out", _i32), ("width", _i32), ("n_hidden", _i32), ("bias", _i32), ("skip_mask", _i32)]
+
+
 # name -> argtypes (all return int unless listed in _RESTYPES)
 _SIGS = {
     "nfa_exclusive_cumsum_i64": [_vp, _i64, _vp, _vp, _vp, _vp],
@@ -170,6 +175,11 @@ _SIGS = {
     "nfa_mlp_bwd_data": [_i32, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp],
     "nfa_mlp_bwd_weights": [_i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
     "nfa_mlp_tangent": [_i32, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp],
+    "nfa_mlp_net_pack_weights": [_i32, C.POINTER(MLPDesc), _vp, _vp, _i64, _vp, _i64, _vp],
+    "nfa_mlp_net_fwd": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp],
+    "nfa_mlp_net_bwd_data": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp],
+    "nfa_mlp_net_bwd_weights": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp],
+    "nfa_mlp_net_tangent": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],

@@ -1,5 +1,10 @@
 // mlp.hip -- the field's network as fused half-precision MFMA passes: tiny-cuda-nn's FullyFusedMLP (no biases, ReLU on the
-// hidden layers, no output activation), n_hidden + 1 weight matrices W_l [out_l, in_l] (torch's Linear layout), width 64 or 128.
+// hidden layers, no output activation), n_hidden + 1 weight matrices W_l [out_l, in_l] (torch's Linear layout), width 64 or 128;
+// and, described by nfa_mlp_desc, the reference's MLP class: float32 biases b_l and skip connections (a "cat layer" l takes
+// [H_{l-1}, x], its matrix is [out_l, W + n_in]).  The lines below are the plain chain; with both features
+//   z_l = b_l + W_l in_l, in_l = [H_{l-1}, x] at a cat layer;  dx += W_l[:, W:]^T dZ_l and dW_l = dZ_l^T [H_{l-1}, x] there;
+//   db_l = sum_p dZ_l[p, :];  the tangent starts every accumulator at zero and sees [T_{l-1}, v] at a cat layer.
+// A bias is never rounded: it is the float32 value an MFMA accumulator starts from.
 //
 //   forward     H_0 = relu(x W_0^T), H_l = relu(H_{l-1} W_l^T), y = H_last W_L^T          one launch (nfa_mlp_fwd)
 //   data grad   dZ_L = g, dH_{l-1} = dZ_l W_l, dZ_{l-1} = dH_{l-1} * (H_{l-1} > 0), dx = dZ_0 W_0   one launch (nfa_mlp_bwd_data)
@@ -14,7 +19,9 @@
 // of one layer has its rows (neurons) in the 16 accumulator registers of a lane; converted pairwise to half, registers
 // 8s .. 8s+7 are the B fragment of k-step s of the next layer, with no lane movement and no LDS.  The k order inside such a step
 // is permuted (element j of lane half h is row 16s + 8(j>>2) + 4h + (j&3)); the packed weight images absorb the permutation, so
-// a lane's A fragment is one 16-byte LDS read whatever the layer.
+// a lane's A fragment is one 16-byte LDS read whatever the layer.  A cat layer appends ceil(n_in / 16) k-steps in natural order
+// behind its W / 16 permuted ones (forward image: their B fragments are rows of x from memory, as layer 0's are) and n_in rows
+// behind its W rows (backward image: they feed dL/dx only).
 //
 // Packed image of a matrix A [rows, k] (rows padded to 32, k to 16, padding zero): blocks of 1 KiB, block (m, q) = rows
 // 32m .. 32m+31, k-step q, at element ((m KQ + q) 64 + lane) 8 + j, lane = 32h + r: A[32m + r][16q + kpos(h, j)], with
@@ -42,9 +49,21 @@ constexpr int64_t LDS_BUDGET = 160 * 1024;
 
 struct Shape {
     int32_t n_in, n_out, W, n_hidden;
+    int32_t bias;        // every layer has a float32 bias, behind the matrices in the flat parameters
+    int32_t skip_mask;   // bit l (2 <= l <= n_hidden): layer l is a cat layer, its input is [H_{l-1}, x]
     __host__ __device__ int layers() const { return n_hidden + 1; }
-    __host__ __device__ int in_dim(int l) const { return l == 0 ? n_in : W; }
+    __host__ __device__ bool cat(int l) const { return (skip_mask >> l) & 1; }
+    __host__ __device__ int in_dim(int l) const { return l == 0 ? n_in : W + (cat(l) ? n_in : 0); }
     __host__ __device__ int out_dim(int l) const { return l == n_hidden ? n_out : W; }
+    __host__ __device__ int64_t bias_off(int l) const   // of b_l in the flat parameters; bias_off(layers()) is their number with biases
+    {
+        int64_t o = master_off(layers());
+        for (int i = 0; i < l; ++i) o += out_dim(i);
+        return o;
+    }
+    __host__ __device__ int64_t n_params() const { return bias ? bias_off(layers()) : master_off(layers()); }
+    // floats of the biases as a forward pass holds them in LDS: layer l at l W, the output layer padded to 32 rows with zeros
+    __host__ __device__ int lds_bias_floats() const { return bias ? n_hidden * W + 32 : 0; }
     __host__ __device__ int64_t master_off(int l) const
     {
         int64_t o = 0;
@@ -53,7 +72,7 @@ struct Shape {
     }
     // forward image: A = W_l; backward image: A = W_l^T
     __host__ __device__ int fwd_mt(int l) const { return (out_dim(l) + 31) / 32; }
-    __host__ __device__ int fwd_kq(int l) const { return (in_dim(l) + 15) / 16; }
+    __host__ __device__ int fwd_kq(int l) const { return cat(l) ? W / 16 + (n_in + 15) / 16 : (in_dim(l) + 15) / 16; }
     __host__ __device__ int bwd_mt(int l) const { return (in_dim(l) + 31) / 32; }
     __host__ __device__ int bwd_kq(int l) const { return (out_dim(l) + 15) / 16; }
     __host__ __device__ int64_t fwd_off(int l) const   // in elements; fwd_off(layers()) is the image's size
@@ -107,8 +126,10 @@ __global__ __launch_bounds__(256) void mlp_pack_kernel(Shape S, const float *__r
         const int q = (int)(blk % KQ), m = (int)(blk / KQ);
         const int row = 32 * m + (lane & 31);
         // the B operand of a chain's first product comes from memory in natural k order: layer 0 forward, the last layer backward
+        // and the x part of a cat layer forward, which starts on a k-step boundary (W is a multiple of 16)
         const bool permuted = is_bwd ? (l != L - 1) : (l != 0);
-        const int k = 16 * q + kpos(permuted, lane >> 5, j);
+        const bool x_part = !is_bwd && S.cat(l) && q >= S.W / 16;
+        const int k = x_part ? S.W + 16 * (q - S.W / 16) + kpos(false, lane >> 5, j) : 16 * q + kpos(permuted, lane >> 5, j);
         const int in = S.in_dim(l), out = S.out_dim(l);
         float v = 0.f;
         if (!is_bwd) { if (row < out && k < in) v = params[S.master_off(l) + (int64_t)row * in + k]; }
@@ -189,6 +210,31 @@ __device__ __forceinline__ void mask_tile_row(f32x16 &acc, const uint16_t *m, in
     }
 }
 
+// The B fragment of k-step s read back from row p of a [*, W] half matrix that store_tile_row wrote: the lane's own two pieces.
+template <int W>
+__device__ __forceinline__ nfa_v4u load_tile_frag(const uint16_t *m, int64_t p, int s, int h)
+{
+    const nfa_v2u *d = reinterpret_cast<const nfa_v2u *>(m + p * W + 16 * s + 4 * h);
+    const nfa_v2u a = d[0], b = d[2];
+    return nfa_v4u{a[0], a[1], b[0], b[1]};
+}
+
+// An accumulator tile's start: rows 32m .. 32m+31 of a layer's float32 bias (lb: that tile's 32 floats in LDS), or zero.
+__device__ __forceinline__ void init_acc(f32x16 &a, bool has_bias, const float *lb, int h)
+{
+    if (has_bias) {
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+            const nfa_v4f v = *reinterpret_cast<const nfa_v4f *>(lb + 8 * gq + 4 * h);   // acc_row(4 gq + i, h) = 8 gq + 4 h + i
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a[4 * gq + i] = v[i];
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a[i] = 0.f;
+    }
+}
+
 // A wave's 32 x 32 accumulator tile (row = column of the output matrix, column = point) to memory through its LDS staging
 // tile, so that stores run along the output rows: columns col0 .. col0+ncols-1 of rows row0 .. row0+nrows-1 of out [*, ld].
 template <class E>
@@ -220,31 +266,48 @@ __device__ __forceinline__ void stage_image(nfa_v4u *dst, const nfa_v4u *src, in
     __syncthreads();
 }
 
+// The shape as an instantiation sees it: without EXT both features are compile-time zeros, so every in_dim / k-step count folds
+// to the plain chain's and the plain kernels are the code they were before the features existed.
+template <bool EXT>
+__device__ __forceinline__ Shape shape_of(Shape S)
+{
+    if constexpr (!EXT) { S.bias = 0; S.skip_mask = 0; }
+    return S;
+}
+
 // ---------------------------------------------------------------- forward and tangent forward
 
 // The layer chain W_L act(... act(W_0 in)) over the workgroup's tiles, for both passes that run it.  Forward: act = ReLU, the
 // rounded activations go to `save` (the backward's `hidden`, optional).  TANGENT: act = the mask (mask_l > 0) of the activations
 // the forward saved, the rounded T_l go to `save` (optional): the derivative of the chain along `in`, which is linear in it.
-template <class E, int W, bool TANGENT>
+// `bias` (forward only; the tangent of a bias is zero): b_0 .. b_L float32, staged once behind the image; every accumulator
+// starts from its rows.  A cat layer runs kq0 more k-steps whose B fragments are rows of `in`, loaded again as layer 0 loads them.
+template <class E, int W, bool TANGENT, bool EXT>
 __device__ __forceinline__ void mlp_chain(const Shape &S, const void *__restrict__ in, int in_f32, int in_vec,
-                                          const uint16_t *__restrict__ image, int64_t image_elems, int64_t N, void *__restrict__ out,
-                                          int out_f32, const uint16_t *__restrict__ mask, uint16_t *__restrict__ save)
+                                          const uint16_t *__restrict__ image, int64_t image_elems, const float *__restrict__ bias,
+                                          int64_t N, void *__restrict__ out, int out_f32, const uint16_t *__restrict__ mask,
+                                          uint16_t *__restrict__ save)
 {
     constexpr int MT = W / 32, KQ = W / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char mlp_lds[];
     nfa_v4u *wimg = reinterpret_cast<nfa_v4u *>(mlp_lds);
+    const bool has_bias = EXT && !TANGENT && S.bias != 0;
+    float *lb = reinterpret_cast<float *>(mlp_lds + image_elems * 2);
+    const int n_lb = has_bias ? S.lds_bias_floats() : 0;
+    for (int i = threadIdx.x; i < n_lb; i += blockDim.x) {
+        const int i_out = i - S.n_hidden * W;   // >= 0: row of the output layer, zero beyond n_out
+        lb[i] = i_out < 0 || i_out < S.n_out ? bias[i] : 0.f;
+    }
     stage_image(wimg, reinterpret_cast<const nfa_v4u *>(image), image_elems / 8);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    float *st = reinterpret_cast<float *>(mlp_lds + image_elems * 2) + wave * 32 * STAGE_LD;
+    float *st = lb + n_lb + wave * 32 * STAGE_LD;
     const int kq0 = S.fwd_kq(0);
     const int64_t n_tiles = (N + 31) / 32;
     for (int64_t tile = (int64_t)blockIdx.x * MLP_WAVES + wave; tile < n_tiles; tile += (int64_t)gridDim.x * MLP_WAVES) {
         const int64_t p = tile * 32 + r, pc = p < N ? p : N - 1;
         f32x16 acc[MT];
 #pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
+        for (int m = 0; m < MT; ++m) init_acc(acc[m], has_bias, lb + 32 * m, h);
         for (int q = 0; q < kq0; ++q) {
             const nfa_v4u b = load_row8<E>(in, in_f32 != 0, pc, S.n_in, 16 * q + 8 * h, in_vec != 0);
 #pragma unroll
@@ -268,49 +331,63 @@ __device__ __forceinline__ void mlp_chain(const Shape &S, const void *__restrict
                 if (save && p < N) store_tile_row<W>(save + (int64_t)(l - 1) * N * W, p, t, h, hf[2 * t], hf[2 * t + 1]);
             }
             if (l == S.n_hidden) break;
+            const bool cat = EXT && S.cat(l);
+            const int kql = KQ + (cat ? kq0 : 0);   // k-steps of this layer's image
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
+                init_acc(acc[m], has_bias, lb + l * W + 32 * m, h);
 #pragma unroll
-                for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
-#pragma unroll
-                for (int q = 0; q < KQ; ++q) acc[m] = mfma<E>(wimg[off16 + (m * KQ + q) * 64 + lane], hf[q], acc[m]);
+                for (int q = 0; q < KQ; ++q) acc[m] = mfma<E>(wimg[off16 + (m * kql + q) * 64 + lane], hf[q], acc[m]);
             }
-            off16 += (int64_t)MT * KQ * 64;
+            if (cat) {
+                for (int q = 0; q < kq0; ++q) {
+                    const nfa_v4u b = load_row8<E>(in, in_f32 != 0, pc, S.n_in, 16 * q + 8 * h, in_vec != 0);
+#pragma unroll
+                    for (int m = 0; m < MT; ++m) acc[m] = mfma<E>(wimg[off16 + (m * kql + KQ + q) * 64 + lane], b, acc[m]);
+                }
+            }
+            off16 += (int64_t)MT * kql * 64;
         }
         f32x16 o;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[i] = 0.f;
+        init_acc(o, has_bias, lb + S.n_hidden * W, h);
 #pragma unroll
         for (int q = 0; q < KQ; ++q) o = mfma<E>(wimg[off16 + q * 64 + lane], hf[q], o);
+        if (EXT && S.cat(S.n_hidden)) {
+            for (int q = 0; q < kq0; ++q) {
+                const nfa_v4u b = load_row8<E>(in, in_f32 != 0, pc, S.n_in, 16 * q + 8 * h, in_vec != 0);
+                o = mfma<E>(wimg[off16 + (KQ + q) * 64 + lane], b, o);
+            }
+        }
         const int64_t row0 = tile * 32;
         stage_store<E>(o, st, out, out_f32 != 0, row0, (int)(N - row0 < 32 ? N - row0 : 32), S.n_out, 0, S.n_out, lane);
     }
 }
 
-template <class E, int W>
+template <class E, int W, bool EXT>
 __global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_fwd_kernel(Shape S, const void *__restrict__ x, int x_f32, int x_vec,
                                                                       const uint16_t *__restrict__ image, int64_t image_elems,
-                                                                      int64_t N, void *__restrict__ y, int y_f32,
-                                                                      uint16_t *__restrict__ hidden)
+                                                                      const float *__restrict__ bias, int64_t N,
+                                                                      void *__restrict__ y, int y_f32, uint16_t *__restrict__ hidden)
 {
-    mlp_chain<E, W, false>(S, x, x_f32, x_vec, image, image_elems, N, y, y_f32, nullptr, hidden);
+    mlp_chain<E, W, false, EXT>(shape_of<EXT>(S), x, x_f32, x_vec, image, image_elems, bias, N, y, y_f32, nullptr, hidden);
 }
 
-// T_{-1} = v, T_l = (W_l T_{l-1}) * (H_l > 0), u = W_L T_{L-1}: the forward's chain on the forward image, masks from `hidden`
-template <class E, int W>
+// T_{-1} = v, T_l = (W_l [T_{l-1}(, v)]) * (H_l > 0), u = W_L [T_{L-1}(, v)]: the forward's chain on the forward image, masks from
+// `hidden`, no biases
+template <class E, int W, bool EXT>
 __global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_tangent_kernel(Shape S, const void *__restrict__ v, int v_f32, int v_vec,
                                                                           const uint16_t *__restrict__ hidden,
                                                                           const uint16_t *__restrict__ image, int64_t image_elems,
                                                                           int64_t N, uint16_t *__restrict__ tangent,
                                                                           void *__restrict__ u, int u_f32)
 {
-    mlp_chain<E, W, true>(S, v, v_f32, v_vec, image, image_elems, N, u, u_f32, hidden, tangent);
+    mlp_chain<E, W, true, EXT>(shape_of<EXT>(S), v, v_f32, v_vec, image, image_elems, nullptr, N, u, u_f32, hidden, tangent);
 }
 
 // ---------------------------------------------------------------- data gradient
 
-template <class E, int W>
-__global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_bwd_data_kernel(Shape S, const void *__restrict__ g, int g_f32, int g_vec,
+template <class E, int W, bool EXT>
+__global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_bwd_data_kernel(Shape S_, const void *__restrict__ g, int g_f32, int g_vec,
                                                                            const uint16_t *__restrict__ hidden,
                                                                            const uint16_t *__restrict__ image, int64_t image_elems,
                                                                            int64_t N, uint16_t *__restrict__ dz,
@@ -318,6 +395,7 @@ __global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_bwd_data_kernel(Shap
                                                                            int dx_f32)
 {
     constexpr int MT = W / 32, KQ = W / 16;
+    const Shape S = shape_of<EXT>(S_);
     extern __shared__ __attribute__((aligned(16))) unsigned char mlp_lds[];
     nfa_v4u *wimg = reinterpret_cast<nfa_v4u *>(mlp_lds);
     stage_image(wimg, reinterpret_cast<const nfa_v4u *>(image), image_elems / 8);
@@ -367,15 +445,40 @@ __global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_bwd_data_kernel(Shap
                 for (int q = 0; q < KQ; ++q) acc[m] = mfma<E>(wimg[off16 + (m * KQ + q) * 64 + lane], df[q], acc[m]);
             }
         }
-        if (dx) {   // dx = W_0^T dZ_0, 32 input features at a time
+        if (dx) {   // dx = W_0^T dZ_0 + sum over the cat layers W_l[:, W:]^T dZ_l, 32 input features at a time
             const int64_t row0 = tile * 32;
             const int nrows = (int)(N - row0 < 32 ? N - row0 : 32);
+            if (EXT && S.skip_mask) {
+                // df[] holds dZ_0 by now, so a cat layer's dZ_l comes back from dz.  Each lane reads exactly the two 8-byte pieces
+                // it stored itself (store_tile_row and load_tile_frag address the same columns for a lane), and the lanes of a
+                // partial tile beyond N read row N - 1, which a lane of this same wave stored: nothing crosses waves, so making
+                // the wave's own stores visible to the wave is enough.
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
             for (int m = 0; m < mt0; ++m) {
                 f32x16 o;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) o[i] = 0.f;
 #pragma unroll
                 for (int q = 0; q < KQ; ++q) o = mfma<E>(wimg[(m * KQ + q) * 64 + lane], df[q], o);
+                for (int l = 2; EXT && l < L; ++l) {
+                    if (!S.cat(l)) continue;
+                    // rows W + 32m .. of the layer's image: row tile MT + m
+                    const int64_t base = S.bwd_off(l) / 8;
+                    if (l == L - 1) {   // dZ_L = g, natural k order as in the first product
+                        for (int q = 0; q < kqo; ++q) {
+                            const nfa_v4u b = load_row8<E>(g, g_f32 != 0, pc, S.n_out, 16 * q + 8 * h, g_vec != 0);
+                            o = mfma<E>(wimg[base + ((MT + m) * kqo + q) * 64 + lane], b, o);
+                        }
+                    } else {
+                        const uint16_t *dzl = dz + (int64_t)l * N * W;
+#pragma unroll
+                        for (int q = 0; q < KQ; ++q)
+                            o = mfma<E>(wimg[base + ((MT + m) * KQ + q) * 64 + lane], load_tile_frag<W>(dzl, pc, q, h), o);
+                    }
+                }
                 const int ncols = S.n_in - 32 * m < 32 ? S.n_in - 32 * m : 32;
                 stage_store<E>(o, st, dx, dx_f32 != 0, row0, nrows, S.n_in, 32 * m, ncols, lane);
             }
@@ -404,13 +507,18 @@ __device__ __forceinline__ void stage_transposed(uint16_t *T, const void *src, b
 }
 
 // Workgroup (slice, layer): partial dW_l over the slice's points, the 32 x 32 tiles of [out_l, in_l] dealt round-robin to the waves.
-template <class E, int W>
-__global__ __launch_bounds__(256) void mlp_wgrad_kernel(Shape S, const void *__restrict__ x, int x_f32, int x_vec,
+// A cat layer's B operand [H_{l-1}, x] is staged from its two sources into the one Tb (W + n_in <= 256 rows).  With biases the
+// workgroup also writes the slice's partial db_l = sum_p dZ_l[p, :]: thread c adds column c of the staged dZ in float32, the
+// points in ascending order (eight at a time as a fixed tree), so the sum over the slices has one order whatever the launch;
+// `zero_bias` writes zeros there instead (the second order: d/db of <v, dL/dx> is zero, the masks being piecewise constant).
+template <class E, int W, bool EXT>
+__global__ __launch_bounds__(256) void mlp_wgrad_kernel(Shape S_, const void *__restrict__ x, int x_f32, int x_vec,
                                                         const uint16_t *__restrict__ hidden, const uint16_t *__restrict__ dz,
                                                         const uint16_t *__restrict__ dz_out, int dzo_vec, int64_t N, int64_t slice_len,
-                                                        float *__restrict__ partials, int64_t P)
+                                                        float *__restrict__ partials, int64_t P, int zero_bias)
 {
     constexpr int MAXT = (W / 32) * 8 / 4;   // tiles per wave at most: (W / 32) x (256 / 32) tiles over 4 waves
+    const Shape S = shape_of<EXT>(S_);
     __shared__ __attribute__((aligned(16))) uint16_t Ta[128 * WG_LD];
     __shared__ __attribute__((aligned(16))) uint16_t Tb[256 * WG_LD];
     const int l = blockIdx.y, L = S.layers();
@@ -421,6 +529,8 @@ __global__ __launch_bounds__(256) void mlp_wgrad_kernel(Shape S, const void *__r
     const bool a_vec = l == L - 1 ? dzo_vec != 0 : true;
     const void *b_src = l == 0 ? x : (const void *)(hidden + (int64_t)(l - 1) * N * W);
     const bool b_f32 = l == 0 && x_f32 != 0, b_vec = l == 0 ? x_vec != 0 : true;
+    const bool cat = EXT && S.cat(l), has_bias = EXT && S.bias != 0, col_sum = has_bias && !zero_bias && (int)threadIdx.x < M;
+    float db = 0.f;
     f32x16 acc[MAXT];
 #pragma unroll
     for (int i = 0; i < MAXT; ++i)
@@ -430,8 +540,22 @@ __global__ __launch_bounds__(256) void mlp_wgrad_kernel(Shape S, const void *__r
     for (int64_t c0 = n0; c0 < n1; c0 += WG_CHUNK) {
         __syncthreads();
         stage_transposed<E>(Ta, a_src, false, M, mt * 32, c0, n1, a_vec);
-        stage_transposed<E>(Tb, b_src, b_f32, K, nt * 32, c0, n1, b_vec);
+        if (cat) {
+            stage_transposed<E>(Tb, b_src, false, W, W, c0, n1, true);
+            stage_transposed<E>(Tb + W * WG_LD, x, x_f32 != 0, S.n_in, nt * 32 - W, c0, n1, x_vec != 0);
+        } else {
+            stage_transposed<E>(Tb, b_src, b_f32, K, nt * 32, c0, n1, b_vec);
+        }
         __syncthreads();
+        if (col_sum) {   // points beyond the slice were staged as zeros
+#pragma unroll
+            for (int n8 = 0; n8 < WG_CHUNK / 8; ++n8) {
+                const nfa_v4u f = *reinterpret_cast<const nfa_v4u *>(Ta + threadIdx.x * WG_LD + 8 * n8);
+                const float s0 = unpack_half<E>(f[0], 0) + unpack_half<E>(f[0], 1), s1 = unpack_half<E>(f[1], 0) + unpack_half<E>(f[1], 1);
+                const float s2 = unpack_half<E>(f[2], 0) + unpack_half<E>(f[2], 1), s3 = unpack_half<E>(f[3], 0) + unpack_half<E>(f[3], 1);
+                db += (s0 + s1) + (s2 + s3);
+            }
+        }
 #pragma unroll
         for (int i = 0; i < MAXT; ++i) {
             const int tile = wave + 4 * i;
@@ -446,6 +570,7 @@ __global__ __launch_bounds__(256) void mlp_wgrad_kernel(Shape S, const void *__r
             }
         }
     }
+    if (has_bias && (int)threadIdx.x < M) partials[(int64_t)blockIdx.x * P + S.bias_off(l) + threadIdx.x] = db;
     float *out = partials + (int64_t)blockIdx.x * P + S.master_off(l);
 #pragma unroll
     for (int i = 0; i < MAXT; ++i) {
@@ -474,33 +599,54 @@ __global__ __launch_bounds__(256) void mlp_wgrad_sum_kernel(const float *__restr
 
 // ---------------------------------------------------------------- host side
 
-int check_shape(const char *who, int32_t elem, int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden, int64_t n_points, Shape *S)
+int check_shape(const char *who, int32_t elem, const nfa_mlp_desc *net, int64_t n_points, Shape *S)
 {
+    NFA_REQUIRE(net, "%s: the network descriptor is null", who);
+    const int32_t n_in = net->n_in, n_out = net->n_out, width = net->width, n_hidden = net->n_hidden;
     NFA_REQUIRE(elem == NFA_ELEM_F16 || elem == NFA_ELEM_BF16, "%s: elem %d: the network's type is NFA_ELEM_F16 or NFA_ELEM_BF16", who, elem);
     NFA_REQUIRE(width == 64 || width == 128, "%s: width %d: 64 or 128 neurons are supported", who, width);
     NFA_REQUIRE(n_hidden >= 1 && n_hidden <= 4, "%s: n_hidden %d: 1 to 4 hidden layers are supported", who, n_hidden);
     NFA_REQUIRE(n_in >= 1 && n_in <= 256, "%s: n_in %d: 1 to 256 input features are supported", who, n_in);
     NFA_REQUIRE(n_out >= 1 && n_out <= 32, "%s: n_out %d: 1 to 32 outputs are supported", who, n_out);
     NFA_REQUIRE(n_points >= 0, "%s: n_points %lld is negative", who, (long long)n_points);
-    *S = Shape{n_in, n_out, width, n_hidden};
-    const int64_t f = S->fwd_off(S->layers()) * 2, b = S->bwd_off(S->layers()) * 2;
-    NFA_REQUIRE(f + STAGE_BYTES <= LDS_BUDGET && b + STAGE_BYTES <= LDS_BUDGET,
-                "%s: the packed weights do not fit the LDS: forward image %lld B, backward image %lld B, each with %lld B of store "
-                "staging, against %lld B per compute unit (n_in %d, n_out %d, width %d, n_hidden %d)",
-                who, (long long)f, (long long)b, (long long)STAGE_BYTES, (long long)LDS_BUDGET, n_in, n_out, width, n_hidden);
+    NFA_REQUIRE(net->bias == 0 || net->bias == 1, "%s: bias %d: 0 or 1", who, net->bias);
+    NFA_REQUIRE((net->skip_mask & ~((2 << n_hidden) - 4)) == 0, "%s: skip_mask 0x%x: only bits 2 to n_hidden (%d) may be set: layer 0 "
+                "takes x itself and layer 1 follows it", who, (unsigned)net->skip_mask, n_hidden);
+    NFA_REQUIRE(net->skip_mask == 0 || n_in + width <= 256, "%s: n_in %d + width %d = %d: a layer that takes [H, x] holds at most 256 "
+                "inputs", who, n_in, width, n_in + width);
+    *S = Shape{n_in, n_out, width, n_hidden, net->bias, net->skip_mask};
+    const int64_t f = S->fwd_off(S->layers()) * 2, b = S->bwd_off(S->layers()) * 2, fb = (int64_t)S->lds_bias_floats() * 4;
+    NFA_REQUIRE(f + fb + STAGE_BYTES <= LDS_BUDGET && b + STAGE_BYTES <= LDS_BUDGET,
+                "%s: the packed weights do not fit the LDS: forward image %lld B with %lld B of biases, backward image %lld B, each with "
+                "%lld B of store staging, against %lld B per compute unit (n_in %d, n_out %d, width %d, n_hidden %d, bias %d, "
+                "skip_mask 0x%x)", who, (long long)f, (long long)fb, (long long)b, (long long)STAGE_BYTES, (long long)LDS_BUDGET, n_in,
+                n_out, width, n_hidden, net->bias, (unsigned)net->skip_mask);
     return NFA_OK;
+}
+
+nfa_mlp_desc plain_net(int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden)
+{
+    return nfa_mlp_desc{n_in, n_out, width, n_hidden, 0, 0};
 }
 
 bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 bool row8_vec(const void *p, int ld) { return ld % 8 == 0 && aligned_to(p, 16); }
 
+// EXT: the network has biases or a skip.  The plain chain is an instantiation of its own, in which both are compiled out: with
+// them as run-time conditions the forward kernel's register count cut its occupancy from 5 to 3 waves per SIMD (64 wide).
 template <class F>
-bool dispatch_mlp(int32_t elem, int32_t width, F &&f)
+bool dispatch_mlp(int32_t elem, const Shape &S, F &&f)
 {
-    if (elem == NFA_ELEM_F16 && width == 64) f(ElemTag<nfa_f16>{}, std::integral_constant<int, 64>{});
-    else if (elem == NFA_ELEM_F16 && width == 128) f(ElemTag<nfa_f16>{}, std::integral_constant<int, 128>{});
-    else if (elem == NFA_ELEM_BF16 && width == 64) f(ElemTag<nfa_bf16>{}, std::integral_constant<int, 64>{});
-    else if (elem == NFA_ELEM_BF16 && width == 128) f(ElemTag<nfa_bf16>{}, std::integral_constant<int, 128>{});
+    auto widths = [&](auto tag, auto ext) {
+        if (S.W == 64) f(tag, std::integral_constant<int, 64>{}, ext);
+        else f(tag, std::integral_constant<int, 128>{}, ext);
+    };
+    auto exts = [&](auto tag) {
+        if (S.bias || S.skip_mask) widths(tag, std::true_type{});
+        else widths(tag, std::false_type{});
+    };
+    if (elem == NFA_ELEM_F16) exts(ElemTag<nfa_f16>{});
+    else if (elem == NFA_ELEM_BF16) exts(ElemTag<nfa_bf16>{});
     else return false;
     return true;
 }
@@ -533,138 +679,213 @@ int64_t wgrad_slice_len(int64_t n_points)
     return ceil_div64(ceil_div64(n_points, s), WG_CHUNK) * WG_CHUNK;
 }
 
-}  // namespace
-}  // namespace nfa
+// The five passes behind both families of entries; `who` is the name of the entry that was called.
 
-using namespace nfa;
-
-int nfa_mlp_pack_weights(int32_t elem, const float *params, int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden,
-                         void *fwd_image, int64_t fwd_elems, void *bwd_image, int64_t bwd_elems, nfa_stream_t stream)
+int pack_weights(const char *who, int32_t elem, const nfa_mlp_desc *net, const float *params, void *fwd_image, int64_t fwd_elems,
+                 void *bwd_image, int64_t bwd_elems, nfa_stream_t stream)
 {
     Shape S;
-    if (int rc = check_shape("nfa_mlp_pack_weights", elem, n_in, n_out, width, n_hidden, 0, &S)) return rc;
+    if (int rc = check_shape(who, elem, net, 0, &S)) return rc;
     const int64_t fe = S.fwd_off(S.layers()), be = S.bwd_off(S.layers());
-    NFA_REQUIRE(fwd_elems == fe && bwd_elems == be, "nfa_mlp_pack_weights: the images hold %lld and %lld elements for this shape, "
-                "got %lld and %lld", (long long)fe, (long long)be, (long long)fwd_elems, (long long)bwd_elems);
-    NFA_REQUIRE(params && fwd_image && bwd_image, "nfa_mlp_pack_weights: null pointer");
-    NFA_REQUIRE(aligned_to(fwd_image, 16) && aligned_to(bwd_image, 16), "nfa_mlp_pack_weights: the images must be 16-byte aligned");
+    NFA_REQUIRE(fwd_elems == fe && bwd_elems == be, "%s: the images hold %lld and %lld elements for this shape, got %lld and %lld", who,
+                (long long)fe, (long long)be, (long long)fwd_elems, (long long)bwd_elems);
+    NFA_REQUIRE(params && fwd_image && bwd_image, "%s: null pointer", who);
+    NFA_REQUIRE(aligned_to(fwd_image, 16) && aligned_to(bwd_image, 16), "%s: the images must be 16-byte aligned", who);
     dispatch_elem(elem, [&](auto tag) {
         using E = typename decltype(tag)::type;
         if constexpr (sizeof(E) == 2)
             mlp_pack_kernel<E><<<grid_1d(fe + be, 256), 256, 0, as_stream(stream)>>>(S, params, static_cast<uint16_t *>(fwd_image),
                                                                                    static_cast<uint16_t *>(bwd_image), fe, be);
     });
-    NFA_CHECK_LAUNCH("nfa_mlp_pack_weights");
+    NFA_CHECK_LAUNCH(who);
     return NFA_OK;
+}
+
+int fwd(const char *who, int32_t elem, const nfa_mlp_desc *net, const void *x, int32_t x_elem, const void *fwd_image, const float *bias,
+        int64_t n_points, void *y, int32_t y_elem, void *hidden, int32_t save_hidden, nfa_stream_t stream)
+{
+    Shape S;
+    if (int rc = check_shape(who, elem, net, n_points, &S)) return rc;
+    NFA_REQUIRE(x_elem == NFA_ELEM_F32 || x_elem == elem, "%s: x_elem %d: float32 or the network's type (%d)", who, x_elem, elem);
+    NFA_REQUIRE(y_elem == NFA_ELEM_F32 || y_elem == elem, "%s: y_elem %d: float32 or the network's type (%d)", who, y_elem, elem);
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(x && fwd_image && y && (!save_hidden || hidden) && (!S.bias || bias), "%s: null pointer", who);
+    NFA_REQUIRE(aligned_to(fwd_image, 16) && aligned_to(hidden, 8) && aligned_to(x, x_elem == NFA_ELEM_F32 ? 4 : 2) &&
+                aligned_to(y, y_elem == NFA_ELEM_F32 ? 4 : 2) && aligned_to(bias, 4),
+                "%s: misaligned pointer (image 16, hidden 8, x, y and bias their element)", who);
+    const int64_t img = S.fwd_off(S.layers()), lds = img * 2 + (int64_t)S.lds_bias_floats() * 4 + STAGE_BYTES;
+    int rc = NFA_OK;
+    dispatch_mlp(elem, S, [&](auto tag, auto w, auto ext) {
+        using E = typename decltype(tag)::type;
+        auto kern = mlp_fwd_kernel<E, decltype(w)::value, decltype(ext)::value>;
+        if ((rc = allow_lds(who, kern, lds)) != NFA_OK) return;
+        kern<<<fused_grid(n_points, lds), MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(
+            S, x, x_elem == NFA_ELEM_F32, row8_vec(x, S.n_in), static_cast<const uint16_t *>(fwd_image), img, S.bias ? bias : nullptr,
+            n_points, y, y_elem == NFA_ELEM_F32, save_hidden ? static_cast<uint16_t *>(hidden) : nullptr);
+    });
+    if (rc != NFA_OK) return rc;
+    NFA_CHECK_LAUNCH(who);
+    return NFA_OK;
+}
+
+int bwd_data(const char *who, int32_t elem, const nfa_mlp_desc *net, const void *grad_y, int32_t g_elem, const void *hidden,
+             const void *bwd_image, int64_t n_points, void *dz, void *dz_out, void *grad_x, int32_t x_elem, nfa_stream_t stream)
+{
+    Shape S;
+    if (int rc = check_shape(who, elem, net, n_points, &S)) return rc;
+    NFA_REQUIRE(g_elem == NFA_ELEM_F32 || g_elem == elem, "%s: g_elem %d: float32 or the network's type (%d)", who, g_elem, elem);
+    NFA_REQUIRE(x_elem == NFA_ELEM_F32 || x_elem == elem, "%s: x_elem %d: float32 or the network's type (%d)", who, x_elem, elem);
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(grad_y && hidden && bwd_image && dz, "%s: null pointer", who);
+    NFA_REQUIRE(aligned_to(bwd_image, 16) && aligned_to(hidden, 8) && aligned_to(dz, 8) && aligned_to(dz_out, 2) &&
+                aligned_to(grad_y, g_elem == NFA_ELEM_F32 ? 4 : 2) && aligned_to(grad_x, x_elem == NFA_ELEM_F32 ? 4 : 2),
+                "%s: misaligned pointer (image 16, hidden and dz 8, the others their element)", who);
+    const int64_t img = S.bwd_off(S.layers()), lds = img * 2 + STAGE_BYTES;
+    int rc = NFA_OK;
+    dispatch_mlp(elem, S, [&](auto tag, auto w, auto ext) {
+        using E = typename decltype(tag)::type;
+        auto kern = mlp_bwd_data_kernel<E, decltype(w)::value, decltype(ext)::value>;
+        if ((rc = allow_lds(who, kern, lds)) != NFA_OK) return;
+        kern<<<fused_grid(n_points, lds), MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(
+            S, grad_y, g_elem == NFA_ELEM_F32, row8_vec(grad_y, S.n_out), static_cast<const uint16_t *>(hidden),
+            static_cast<const uint16_t *>(bwd_image), img, n_points, static_cast<uint16_t *>(dz), static_cast<uint16_t *>(dz_out),
+            grad_x, x_elem == NFA_ELEM_F32);
+    });
+    if (rc != NFA_OK) return rc;
+    NFA_CHECK_LAUNCH(who);
+    return NFA_OK;
+}
+
+int bwd_weights(const char *who, int32_t elem, const nfa_mlp_desc *net, const void *x, int32_t x_elem, const void *hidden, const void *dz,
+                const void *dz_out, int64_t n_points, float *partials, int64_t partial_floats, float *grad_params, int32_t zero_bias,
+                nfa_stream_t stream)
+{
+    Shape S;
+    if (int rc = check_shape(who, elem, net, n_points, &S)) return rc;
+    NFA_REQUIRE(x_elem == NFA_ELEM_F32 || x_elem == elem, "%s: x_elem %d: float32 or the network's type (%d)", who, x_elem, elem);
+    NFA_REQUIRE(partial_floats >= 0, "%s: partial_floats %lld is negative", who, (long long)partial_floats);
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(x && hidden && dz && dz_out && partials && grad_params, "%s: null pointer", who);
+    NFA_REQUIRE(aligned_to(hidden, 16) && aligned_to(dz, 16) && aligned_to(dz_out, 2) && aligned_to(x, x_elem == NFA_ELEM_F32 ? 4 : 2) &&
+                aligned_to(partials, 4) && aligned_to(grad_params, 4),
+                "%s: misaligned pointer (hidden and dz 16, the others their element)", who);
+    const int64_t P = S.n_params(), slice_len = wgrad_slice_len(n_points), n_slices = ceil_div64(n_points, slice_len);
+    NFA_REQUIRE(partial_floats >= n_slices * P, "%s: partials holds %lld floats, %lld slices of %lld parameters need %lld", who,
+                (long long)partial_floats, (long long)n_slices, (long long)P, (long long)(n_slices * P));
+    dispatch_mlp(elem, S, [&](auto tag, auto w, auto ext) {
+        using E = typename decltype(tag)::type;
+        mlp_wgrad_kernel<E, decltype(w)::value, decltype(ext)::value><<<dim3((unsigned)n_slices, (unsigned)S.layers()), 256, 0, as_stream(stream)>>>(
+            S, x, x_elem == NFA_ELEM_F32, row8_vec(x, S.n_in), static_cast<const uint16_t *>(hidden), static_cast<const uint16_t *>(dz),
+            static_cast<const uint16_t *>(dz_out), row8_vec(dz_out, S.n_out), n_points, slice_len, partials, P, zero_bias != 0);
+    });
+    NFA_CHECK_LAUNCH(who);
+    mlp_wgrad_sum_kernel<<<(unsigned)ceil_div64(P, 256), 256, 0, as_stream(stream)>>>(partials, n_slices, P, grad_params);
+    NFA_CHECK_LAUNCH(who);
+    return NFA_OK;
+}
+
+int tangent_pass(const char *who, int32_t elem, const nfa_mlp_desc *net, const void *v, int32_t v_elem, const void *hidden,
+                 const void *fwd_image, int64_t n_points, void *tangent, void *u, int32_t u_elem, nfa_stream_t stream)
+{
+    Shape S;
+    if (int rc = check_shape(who, elem, net, n_points, &S)) return rc;
+    NFA_REQUIRE(v_elem == NFA_ELEM_F32 || v_elem == elem, "%s: v_elem %d: float32 or the network's type (%d)", who, v_elem, elem);
+    NFA_REQUIRE(u_elem == NFA_ELEM_F32 || u_elem == elem, "%s: u_elem %d: float32 or the network's type (%d)", who, u_elem, elem);
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(v && hidden && fwd_image && u, "%s: null pointer", who);
+    NFA_REQUIRE(aligned_to(fwd_image, 16) && aligned_to(hidden, 8) && aligned_to(tangent, 8) && aligned_to(v, v_elem == NFA_ELEM_F32 ? 4 : 2) &&
+                aligned_to(u, u_elem == NFA_ELEM_F32 ? 4 : 2),
+                "%s: misaligned pointer (image 16, hidden and tangent 8, v and u their element)", who);
+    const int64_t img = S.fwd_off(S.layers()), lds = img * 2 + STAGE_BYTES;   // no biases: a bias has no tangent
+    int rc = NFA_OK;
+    dispatch_mlp(elem, S, [&](auto tag, auto w, auto ext) {
+        using E = typename decltype(tag)::type;
+        auto kern = mlp_tangent_kernel<E, decltype(w)::value, decltype(ext)::value>;
+        if ((rc = allow_lds(who, kern, lds)) != NFA_OK) return;
+        kern<<<fused_grid(n_points, lds), MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(
+            S, v, v_elem == NFA_ELEM_F32, row8_vec(v, S.n_in), static_cast<const uint16_t *>(hidden),
+            static_cast<const uint16_t *>(fwd_image), img, n_points, static_cast<uint16_t *>(tangent), u, u_elem == NFA_ELEM_F32);
+    });
+    if (rc != NFA_OK) return rc;
+    NFA_CHECK_LAUNCH(who);
+    return NFA_OK;
+}
+
+}  // namespace
+}  // namespace nfa
+
+using namespace nfa;
+
+int nfa_mlp_net_pack_weights(int32_t elem, const nfa_mlp_desc *net, const float *params, void *fwd_image, int64_t fwd_elems,
+                             void *bwd_image, int64_t bwd_elems, nfa_stream_t stream)
+{
+    return pack_weights("nfa_mlp_net_pack_weights", elem, net, params, fwd_image, fwd_elems, bwd_image, bwd_elems, stream);
+}
+
+int nfa_mlp_net_fwd(int32_t elem, const nfa_mlp_desc *net, const void *x, int32_t x_elem, const void *fwd_image, const float *bias,
+                    int64_t n_points, void *y, int32_t y_elem, void *hidden, int32_t save_hidden, nfa_stream_t stream)
+{
+    return fwd("nfa_mlp_net_fwd", elem, net, x, x_elem, fwd_image, bias, n_points, y, y_elem, hidden, save_hidden, stream);
+}
+
+int nfa_mlp_net_bwd_data(int32_t elem, const nfa_mlp_desc *net, const void *grad_y, int32_t g_elem, const void *hidden,
+                         const void *bwd_image, int64_t n_points, void *dz, void *dz_out, void *grad_x, int32_t x_elem,
+                         nfa_stream_t stream)
+{
+    return bwd_data("nfa_mlp_net_bwd_data", elem, net, grad_y, g_elem, hidden, bwd_image, n_points, dz, dz_out, grad_x, x_elem, stream);
+}
+
+int nfa_mlp_net_bwd_weights(int32_t elem, const nfa_mlp_desc *net, const void *x, int32_t x_elem, const void *hidden, const void *dz,
+                            const void *dz_out, int64_t n_points, float *partials, int64_t partial_floats, float *grad_params,
+                            int32_t zero_bias, nfa_stream_t stream)
+{
+    return bwd_weights("nfa_mlp_net_bwd_weights", elem, net, x, x_elem, hidden, dz, dz_out, n_points, partials, partial_floats,
+                       grad_params, zero_bias, stream);
+}
+
+int nfa_mlp_net_tangent(int32_t elem, const nfa_mlp_desc *net, const void *v, int32_t v_elem, const void *hidden, const void *fwd_image,
+                        int64_t n_points, void *tangent, void *u, int32_t u_elem, nfa_stream_t stream)
+{
+    return tangent_pass("nfa_mlp_net_tangent", elem, net, v, v_elem, hidden, fwd_image, n_points, tangent, u, u_elem, stream);
+}
+
+// The tiny-cuda-nn entries: the same passes for a descriptor without biases and without skips.
+
+int nfa_mlp_pack_weights(int32_t elem, const float *params, int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden,
+                         void *fwd_image, int64_t fwd_elems, void *bwd_image, int64_t bwd_elems, nfa_stream_t stream)
+{
+    const nfa_mlp_desc net = plain_net(n_in, n_out, width, n_hidden);
+    return pack_weights("nfa_mlp_pack_weights", elem, &net, params, fwd_image, fwd_elems, bwd_image, bwd_elems, stream);
 }
 
 int nfa_mlp_fwd(int32_t elem, const void *x, int32_t x_elem, const void *fwd_image, int64_t n_points, int32_t n_in, int32_t n_out,
                 int32_t width, int32_t n_hidden, void *y, int32_t y_elem, void *hidden, int32_t save_hidden, nfa_stream_t stream)
 {
-    Shape S;
-    if (int rc = check_shape("nfa_mlp_fwd", elem, n_in, n_out, width, n_hidden, n_points, &S)) return rc;
-    NFA_REQUIRE(x_elem == NFA_ELEM_F32 || x_elem == elem, "nfa_mlp_fwd: x_elem %d: float32 or the network's type (%d)", x_elem, elem);
-    NFA_REQUIRE(y_elem == NFA_ELEM_F32 || y_elem == elem, "nfa_mlp_fwd: y_elem %d: float32 or the network's type (%d)", y_elem, elem);
-    if (n_points == 0) return NFA_OK;
-    NFA_REQUIRE(x && fwd_image && y && (!save_hidden || hidden), "nfa_mlp_fwd: null pointer");
-    NFA_REQUIRE(aligned_to(fwd_image, 16) && aligned_to(hidden, 8) && aligned_to(x, x_elem == NFA_ELEM_F32 ? 4 : 2) &&
-                aligned_to(y, y_elem == NFA_ELEM_F32 ? 4 : 2), "nfa_mlp_fwd: misaligned pointer (image 16, hidden 8, x and y their element)");
-    const int64_t img = S.fwd_off(S.layers()), lds = img * 2 + STAGE_BYTES;
-    int rc = NFA_OK;
-    dispatch_mlp(elem, width, [&](auto tag, auto w) {
-        using E = typename decltype(tag)::type;
-        auto kern = mlp_fwd_kernel<E, decltype(w)::value>;
-        if ((rc = allow_lds("nfa_mlp_fwd", kern, lds)) != NFA_OK) return;
-        kern<<<fused_grid(n_points, lds), MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(
-            S, x, x_elem == NFA_ELEM_F32, row8_vec(x, n_in), static_cast<const uint16_t *>(fwd_image), img, n_points, y,
-            y_elem == NFA_ELEM_F32, save_hidden ? static_cast<uint16_t *>(hidden) : nullptr);
-    });
-    if (rc != NFA_OK) return rc;
-    NFA_CHECK_LAUNCH("nfa_mlp_fwd");
-    return NFA_OK;
+    const nfa_mlp_desc net = plain_net(n_in, n_out, width, n_hidden);
+    return fwd("nfa_mlp_fwd", elem, &net, x, x_elem, fwd_image, nullptr, n_points, y, y_elem, hidden, save_hidden, stream);
 }
 
 int nfa_mlp_bwd_data(int32_t elem, const void *grad_y, int32_t g_elem, const void *hidden, const void *bwd_image, int64_t n_points,
                      int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden, void *dz, void *dz_out, void *grad_x,
                      int32_t x_elem, nfa_stream_t stream)
 {
-    Shape S;
-    if (int rc = check_shape("nfa_mlp_bwd_data", elem, n_in, n_out, width, n_hidden, n_points, &S)) return rc;
-    NFA_REQUIRE(g_elem == NFA_ELEM_F32 || g_elem == elem, "nfa_mlp_bwd_data: g_elem %d: float32 or the network's type (%d)", g_elem, elem);
-    NFA_REQUIRE(x_elem == NFA_ELEM_F32 || x_elem == elem, "nfa_mlp_bwd_data: x_elem %d: float32 or the network's type (%d)", x_elem, elem);
-    if (n_points == 0) return NFA_OK;
-    NFA_REQUIRE(grad_y && hidden && bwd_image && dz, "nfa_mlp_bwd_data: null pointer");
-    NFA_REQUIRE(aligned_to(bwd_image, 16) && aligned_to(hidden, 8) && aligned_to(dz, 8) && aligned_to(dz_out, 2) &&
-                aligned_to(grad_y, g_elem == NFA_ELEM_F32 ? 4 : 2) && aligned_to(grad_x, x_elem == NFA_ELEM_F32 ? 4 : 2),
-                "nfa_mlp_bwd_data: misaligned pointer (image 16, hidden and dz 8, the others their element)");
-    const int64_t img = S.bwd_off(S.layers()), lds = img * 2 + STAGE_BYTES;
-    int rc = NFA_OK;
-    dispatch_mlp(elem, width, [&](auto tag, auto w) {
-        using E = typename decltype(tag)::type;
-        auto kern = mlp_bwd_data_kernel<E, decltype(w)::value>;
-        if ((rc = allow_lds("nfa_mlp_bwd_data", kern, lds)) != NFA_OK) return;
-        kern<<<fused_grid(n_points, lds), MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(
-            S, grad_y, g_elem == NFA_ELEM_F32, row8_vec(grad_y, n_out), static_cast<const uint16_t *>(hidden),
-            static_cast<const uint16_t *>(bwd_image), img, n_points, static_cast<uint16_t *>(dz), static_cast<uint16_t *>(dz_out),
-            grad_x, x_elem == NFA_ELEM_F32);
-    });
-    if (rc != NFA_OK) return rc;
-    NFA_CHECK_LAUNCH("nfa_mlp_bwd_data");
-    return NFA_OK;
+    const nfa_mlp_desc net = plain_net(n_in, n_out, width, n_hidden);
+    return bwd_data("nfa_mlp_bwd_data", elem, &net, grad_y, g_elem, hidden, bwd_image, n_points, dz, dz_out, grad_x, x_elem, stream);
 }
 
 int nfa_mlp_bwd_weights(int32_t elem, const void *x, int32_t x_elem, const void *hidden, const void *dz, const void *dz_out,
                         int64_t n_points, int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden, float *partials,
                         int64_t partial_floats, float *grad_params, nfa_stream_t stream)
 {
-    Shape S;
-    if (int rc = check_shape("nfa_mlp_bwd_weights", elem, n_in, n_out, width, n_hidden, n_points, &S)) return rc;
-    NFA_REQUIRE(x_elem == NFA_ELEM_F32 || x_elem == elem, "nfa_mlp_bwd_weights: x_elem %d: float32 or the network's type (%d)", x_elem, elem);
-    NFA_REQUIRE(partial_floats >= 0, "nfa_mlp_bwd_weights: partial_floats %lld is negative", (long long)partial_floats);
-    if (n_points == 0) return NFA_OK;
-    NFA_REQUIRE(x && hidden && dz && dz_out && partials && grad_params, "nfa_mlp_bwd_weights: null pointer");
-    NFA_REQUIRE(aligned_to(hidden, 16) && aligned_to(dz, 16) && aligned_to(dz_out, 2) && aligned_to(x, x_elem == NFA_ELEM_F32 ? 4 : 2) &&
-                aligned_to(partials, 4) && aligned_to(grad_params, 4),
-                "nfa_mlp_bwd_weights: misaligned pointer (hidden and dz 16, the others their element)");
-    const int64_t P = S.master_off(S.layers()), slice_len = wgrad_slice_len(n_points), n_slices = ceil_div64(n_points, slice_len);
-    NFA_REQUIRE(partial_floats >= n_slices * P, "nfa_mlp_bwd_weights: partials holds %lld floats, %lld slices of %lld parameters need %lld",
-                (long long)partial_floats, (long long)n_slices, (long long)P, (long long)(n_slices * P));
-    dispatch_mlp(elem, width, [&](auto tag, auto w) {
-        using E = typename decltype(tag)::type;
-        mlp_wgrad_kernel<E, decltype(w)::value><<<dim3((unsigned)n_slices, (unsigned)S.layers()), 256, 0, as_stream(stream)>>>(
-            S, x, x_elem == NFA_ELEM_F32, row8_vec(x, n_in), static_cast<const uint16_t *>(hidden), static_cast<const uint16_t *>(dz),
-            static_cast<const uint16_t *>(dz_out), row8_vec(dz_out, n_out), n_points, slice_len, partials, P);
-    });
-    NFA_CHECK_LAUNCH("nfa_mlp_bwd_weights");
-    mlp_wgrad_sum_kernel<<<(unsigned)ceil_div64(P, 256), 256, 0, as_stream(stream)>>>(partials, n_slices, P, grad_params);
-    NFA_CHECK_LAUNCH("nfa_mlp_bwd_weights (sum)");
-    return NFA_OK;
+    const nfa_mlp_desc net = plain_net(n_in, n_out, width, n_hidden);
+    return bwd_weights("nfa_mlp_bwd_weights", elem, &net, x, x_elem, hidden, dz, dz_out, n_points, partials, partial_floats, grad_params,
+                       0, stream);
 }
 
 int nfa_mlp_tangent(int32_t elem, const void *v, int32_t v_elem, const void *hidden, const void *fwd_image, int64_t n_points,
                     int32_t n_in, int32_t n_out, int32_t width, int32_t n_hidden, void *tangent, void *u, int32_t u_elem,
                     nfa_stream_t stream)
 {
-    Shape S;
-    if (int rc = check_shape("nfa_mlp_tangent", elem, n_in, n_out, width, n_hidden, n_points, &S)) return rc;
-    NFA_REQUIRE(v_elem == NFA_ELEM_F32 || v_elem == elem, "nfa_mlp_tangent: v_elem %d: float32 or the network's type (%d)", v_elem, elem);
-    NFA_REQUIRE(u_elem == NFA_ELEM_F32 || u_elem == elem, "nfa_mlp_tangent: u_elem %d: float32 or the network's type (%d)", u_elem, elem);
-    if (n_points == 0) return NFA_OK;
-    NFA_REQUIRE(v && hidden && fwd_image && u, "nfa_mlp_tangent: null pointer");
-    NFA_REQUIRE(aligned_to(fwd_image, 16) && aligned_to(hidden, 8) && aligned_to(tangent, 8) && aligned_to(v, v_elem == NFA_ELEM_F32 ? 4 : 2) &&
-                aligned_to(u, u_elem == NFA_ELEM_F32 ? 4 : 2),
-                "nfa_mlp_tangent: misaligned pointer (image 16, hidden and tangent 8, v and u their element)");
-    const int64_t img = S.fwd_off(S.layers()), lds = img * 2 + STAGE_BYTES;
-    int rc = NFA_OK;
-    dispatch_mlp(elem, width, [&](auto tag, auto w) {
-        using E = typename decltype(tag)::type;
-        auto kern = mlp_tangent_kernel<E, decltype(w)::value>;
-        if ((rc = allow_lds("nfa_mlp_tangent", kern, lds)) != NFA_OK) return;
-        kern<<<fused_grid(n_points, lds), MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(
-            S, v, v_elem == NFA_ELEM_F32, row8_vec(v, n_in), static_cast<const uint16_t *>(hidden),
-            static_cast<const uint16_t *>(fwd_image), img, n_points, static_cast<uint16_t *>(tangent), u, u_elem == NFA_ELEM_F32);
-    });
-    if (rc != NFA_OK) return rc;
-    NFA_CHECK_LAUNCH("nfa_mlp_tangent");
-    return NFA_OK;
+    const nfa_mlp_desc net = plain_net(n_in, n_out, width, n_hidden);
+    return tangent_pass("nfa_mlp_tangent", elem, &net, v, v_elem, hidden, fwd_image, n_points, tangent, u, u_elem, stream);
 }

@@ -1,4 +1,5 @@
-"""The field's network as fused half-precision MFMA passes (csrc/mlp.hip): tiny-cuda-nn's ``FullyFusedMLP``.
+"""The field's network as fused half-precision MFMA passes (csrc/mlp.hip): tiny-cuda-nn's ``FullyFusedMLP``, and with
+``bias=`` / ``skip_layer=`` the reference's own ``MLP`` class (ref: examples/radiance_fields/mlp.py) up to 128 neurons.
 
 The reference's NGP fields put ``tcnn.Network(otype="FullyFusedMLP")`` between the encodings and the renderer (ref:
 examples/radiance_fields/ngp.py:131-135, 150-154, 255-259): 64 neurons, 1 or 2 hidden layers, ReLU, no biases, no output
@@ -28,25 +29,41 @@ STAGE_BYTES = 4 * 32 * 33 * 4    # the four waves' store staging tiles (csrc/mlp
 # include/nerfacc_hip.h: NFA_MLP_WGRAD_MIN_SLICE, NFA_MLP_WGRAD_MAX_SLICES
 WGRAD_MIN_SLICE = 256
 WGRAD_MAX_SLICES = 256
+MAX_CAT_DIMS = 256               # n_input_dims + n_neurons of a network with a skip: the weight gradient's staging of one layer
 
 
 def _cdiv(a: int, b: int) -> int:
     return -(-a // b)
 
 
-def layer_dims(n_in: int, n_out: int, width: int, n_hidden: int) -> List[tuple]:
-    """``[(out_l, in_l)]`` of the ``n_hidden + 1`` matrices."""
-    ins = [n_in] + [width] * n_hidden
+def skip_mask_of(skip_layer: Optional[int], n_hidden: int) -> int:
+    """Bit ``l`` set: layer ``l`` takes ``[H_{l-1}, x]``.  The reference's rule (ref: examples/radiance_fields/mlp.py:50-57,
+    92-97): the input is appended after hidden layer ``i`` when ``i > 0 and i % skip_layer == 0``, so layer ``i + 1`` sees it."""
+    if skip_layer is None:
+        return 0
+    return sum(1 << (i + 1) for i in range(1, n_hidden) if i % skip_layer == 0)
+
+
+def layer_dims(n_in: int, n_out: int, width: int, n_hidden: int, skip_mask: int = 0) -> List[tuple]:
+    """``[(out_l, in_l)]`` of the ``n_hidden + 1`` matrices; a layer of ``skip_mask`` has ``width + n_in`` inputs."""
+    ins = [n_in] + [width + (n_in if (skip_mask >> l) & 1 else 0) for l in range(1, n_hidden + 1)]
     outs = [width] * n_hidden + [n_out]
     return list(zip(outs, ins))
 
 
-def image_elems(n_in: int, n_out: int, width: int, n_hidden: int) -> tuple:
-    """Elements of the packed forward and backward weight images (include/nerfacc_hip.h: nfa_mlp_pack_weights)."""
-    dims = layer_dims(n_in, n_out, width, n_hidden)
-    fwd = sum(_cdiv(o, 32) * _cdiv(i, 16) * 512 for o, i in dims)
+def image_elems(n_in: int, n_out: int, width: int, n_hidden: int, skip_mask: int = 0) -> tuple:
+    """Elements of the packed forward and backward weight images (include/nerfacc_hip.h: nfa_mlp_pack_weights,
+    nfa_mlp_desc): the x part of a cat layer starts on a k-step of its own."""
+    dims = layer_dims(n_in, n_out, width, n_hidden, skip_mask)
+    kq = [_cdiv(width, 16) + _cdiv(n_in, 16) if (skip_mask >> l) & 1 else _cdiv(i, 16) for l, (o, i) in enumerate(dims)]
+    fwd = sum(_cdiv(o, 32) * q * 512 for (o, i), q in zip(dims, kq))
     bwd = sum(_cdiv(i, 32) * _cdiv(o, 16) * 512 for o, i in dims)
     return fwd, bwd
+
+
+def lds_bias_bytes(width: int, n_hidden: int, bias: bool) -> int:
+    """Bytes of the float32 biases as the forward pass holds them beside its image (the output layer padded to 32 rows)."""
+    return (n_hidden * width + 32) * 4 if bias else 0
 
 
 def wgrad_slices(n_points: int) -> int:
@@ -58,12 +75,21 @@ def wgrad_slices(n_points: int) -> int:
 
 # ---------------------------------------------------------------- the arithmetic restated in torch (CPU tensors)
 
-def _forward_torch(x: Tensor, weights: Sequence[Tensor], dtype: torch.dtype, out_f32: bool):
-    """(y, hidden): float32 sums of exact products, rounded where the kernels round (x, W, every hidden activation, y)."""
-    h = x.to(dtype).float()
-    hidden = []
+def _cat_input(h: Tensor, x0: Tensor, l: int, skip_mask: int) -> Tensor:
+    """The input of layer ``l``: ``[h, x0]`` at a cat layer, ``x0`` the rounded network input (or tangent input)."""
+    return torch.cat([h, x0], dim=1) if (skip_mask >> l) & 1 else h
+
+
+def _forward_torch(x: Tensor, weights: Sequence[Tensor], dtype: torch.dtype, out_f32: bool, biases: Optional[Sequence[Tensor]] = None,
+                   skip_mask: int = 0):
+    """(y, hidden): float32 sums of exact products, rounded where the kernels round (x, W, every hidden activation, y).  A
+    bias is added in float32 and never rounded; a cat layer takes ``cat([h, x rounded])``."""
+    x0 = x.to(dtype).float()
+    h, hidden = x0, []
     for l, w in enumerate(weights):
-        z = h @ w.to(dtype).float().t()
+        z = _cat_input(h, x0, l, skip_mask) @ w.to(dtype).float().t()
+        if biases is not None:
+            z = z + biases[l].float()
         if l < len(weights) - 1:
             h = torch.relu(z).to(dtype).float()
             hidden.append(h)
@@ -71,41 +97,54 @@ def _forward_torch(x: Tensor, weights: Sequence[Tensor], dtype: torch.dtype, out
 
 
 def _backward_torch(x: Tensor, weights: Sequence[Tensor], hidden: Sequence[Tensor], g: Tensor, dtype: torch.dtype,
-                    need_x: bool, need_p: bool):
-    """(dL/dx in x's dtype, dL/dparams flat float32, [dZ_l]) with dZ_l rounded as the kernels round it."""
+                    need_x: bool, need_p: bool, bias: bool = False, skip_mask: int = 0):
+    """(dL/dx in x's dtype, dL/dparams flat float32: matrices, then biases, [dZ_l]) with dZ_l rounded as the kernels round it.
+    dL/dx is the float32 sum of layer 0's product and the skip columns' products of every cat layer, rounded once."""
+    x0 = x.to(dtype).float()
+    W = weights[0].shape[0]
     dz = g.to(dtype).float()
-    dzs, g_w = [dz], []
-    g_x = None
+    dzs, g_w, g_b = [dz], [], []
+    g_x, skips = None, []
     for l in range(len(weights) - 1, -1, -1):
-        h_prev = hidden[l - 1] if l > 0 else x.to(dtype).float()
+        h_prev = hidden[l - 1] if l > 0 else x0
         if need_p:
-            g_w.append(dz.t() @ h_prev)
+            g_w.append(dz.t() @ _cat_input(h_prev, x0, l, skip_mask))
+            g_b.append(dz.sum(0))
         if l == 0 and not need_x:
             break
         dh = dz @ weights[l].to(dtype).float()
         if l > 0:
+            if (skip_mask >> l) & 1:
+                skips.append(dh[:, W:])
+                dh = dh[:, :W]
             dz = (dh * (h_prev > 0)).to(dtype).float()
             dzs.append(dz)
         else:
+            for s in reversed(skips):   # ascending layers, as the kernel adds them
+                dh = dh + s
             g_x = dh.to(x.dtype)
-    g_p = torch.cat([w.reshape(-1) for w in reversed(g_w)]) if need_p else None
+    g_p = torch.cat([w.reshape(-1) for w in reversed(g_w)] + (list(reversed(g_b)) if bias else [])) if need_p else None
     return g_x, g_p, dzs[::-1]
 
 
 def _tangent_torch(v: Tensor, weights: Sequence[Tensor], hidden: Sequence[Tensor], dzs: Sequence[Tensor], dtype: torch.dtype,
-                   need_p: bool):
+                   need_p: bool, bias: bool = False, skip_mask: int = 0):
     """The second order: (u float32 unrounded, ds/dparams flat float32, [T_{-1}, T_0 .. T_{L-1}]) for the cotangent ``v`` of
     dL/dx.  The derivative of the network along ``v`` with the SAVED masks (``hidden`` > 0, never a ReLU of the tangent),
     every ``T_l`` rounded after its mask as the tangent kernel rounds it; ``ds/dW_l = dZ_l^T T_{l-1}`` with the first
-    backward's ``dZ_l``."""
-    t = v.to(dtype).float()
-    ts = [t]
+    backward's ``dZ_l``.  A bias has no tangent and ``ds/db`` is zero (the bias segment of the flat gradient); a cat layer
+    sees ``[T_{l-1}, v]``."""
+    t0 = v.to(dtype).float()
+    t, ts = t0, [t0]
     for l, w in enumerate(weights):
-        z = t @ w.to(dtype).float().t()
+        z = _cat_input(t, t0, l, skip_mask) @ w.to(dtype).float().t()
         if l < len(weights) - 1:
             t = (z * (hidden[l] > 0)).to(dtype).float()
             ts.append(t)
-    g_p = torch.cat([(dz.t() @ t).reshape(-1) for dz, t in zip(dzs, ts)]) if need_p else None
+    g_p = None
+    if need_p:
+        g_p = torch.cat([(dz.t() @ _cat_input(t, t0, l, skip_mask)).reshape(-1) for l, (dz, t) in enumerate(zip(dzs, ts))] +
+                        ([torch.zeros(sum(w.shape[0] for w in weights))] if bias else []))
     return z, g_p, ts
 
 
@@ -122,7 +161,7 @@ class _MLPFn(torch.autograd.Function):
             ctx.save_for_backward(x, params)
             return torch.empty(0, mlp.n_output_dims, dtype=mlp.out_dtype, device=x.device)
         if not x.is_cuda:
-            y, hidden = _forward_torch(x, mlp._views(params), mlp.dtype, out_f32)
+            y, hidden = _forward_torch(x, mlp._views(params), mlp.dtype, out_f32, mlp._bias_views(params), mlp.skip_mask)
             ctx.save_for_backward(x, params, *hidden)
             return y
         B.require_device(x, params)
@@ -131,8 +170,12 @@ class _MLPFn(torch.autograd.Function):
         y = torch.empty(N, mlp.n_output_dims, dtype=mlp.out_dtype, device=x.device)
         hidden = torch.empty(mlp.n_hidden_layers, N, mlp.n_neurons, dtype=mlp.dtype, device=x.device) if need_grad else None
         with torch.cuda.device(x.device):
-            B.call("nfa_mlp_fwd", elem, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(fwd_img), N, *mlp._shape, B.ptr(y),
-                   B.ELEM_CODES[y.dtype], B.ptr(hidden), int(need_grad), B.stream())
+            if mlp._plain:
+                B.call("nfa_mlp_fwd", elem, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(fwd_img), N, *mlp._shape, B.ptr(y),
+                       B.ELEM_CODES[y.dtype], B.ptr(hidden), int(need_grad), B.stream())
+            else:
+                B.call("nfa_mlp_net_fwd", elem, mlp._desc, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(fwd_img), mlp._bias_ptr(params), N,
+                       B.ptr(y), B.ELEM_CODES[y.dtype], B.ptr(hidden), int(need_grad), B.stream())
         if need_grad:   # the second order runs the chain again on the forward image
             ctx.save_for_backward(x, params, hidden, bwd_img, *([fwd_img] if mlp.second_order else []))
         return y
@@ -165,7 +208,8 @@ class _MLPBwdFn(torch.autograd.Function):
         g = g.contiguous()
         if not x.is_cuda:
             with torch.autocast("cpu", enabled=False):   # a backward called under autocast must not round the float32 sums
-                g_x, g_p, dzs = _backward_torch(x, mlp._views(params), saved, g, mlp.dtype, need_x, need_p)
+                g_x, g_p, dzs = _backward_torch(x, mlp._views(params), saved, g, mlp.dtype, need_x, need_p, mlp.bias_enabled,
+                                                mlp.skip_mask)
             if mlp.second_order:   # retained only under create_graph=True: a plain backward runs this in no-grad mode
                 ctx.save_for_backward(params, *saved, *dzs)
             return g_x, g_p
@@ -176,14 +220,17 @@ class _MLPBwdFn(torch.autograd.Function):
         g_x = torch.empty_like(x) if need_x else None
         g_p = None
         with torch.cuda.device(dev):
-            B.call("nfa_mlp_bwd_data", elem, B.ptr(g), B.ELEM_CODES[g.dtype], B.ptr(hidden), B.ptr(bwd_img), N, *mlp._shape,
-                   B.ptr(dz), None if dz_out is g else B.ptr(dz_out), B.ptr(g_x), B.ELEM_CODES[x.dtype], B.stream())
+            if mlp._plain:
+                B.call("nfa_mlp_bwd_data", elem, B.ptr(g), B.ELEM_CODES[g.dtype], B.ptr(hidden), B.ptr(bwd_img), N, *mlp._shape,
+                       B.ptr(dz), None if dz_out is g else B.ptr(dz_out), B.ptr(g_x), B.ELEM_CODES[x.dtype], B.stream())
+            else:
+                B.call("nfa_mlp_net_bwd_data", elem, mlp._desc, B.ptr(g), B.ELEM_CODES[g.dtype], B.ptr(hidden), B.ptr(bwd_img), N,
+                       B.ptr(dz), None if dz_out is g else B.ptr(dz_out), B.ptr(g_x), B.ELEM_CODES[x.dtype], B.stream())
             if need_p:
                 P = params.numel()
                 partials = torch.empty(wgrad_slices(N) * P, dtype=torch.float32, device=dev)
                 g_p = torch.empty(P, dtype=torch.float32, device=dev)
-                B.call("nfa_mlp_bwd_weights", elem, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(hidden), B.ptr(dz), B.ptr(dz_out), N,
-                       *mlp._shape, B.ptr(partials), partials.numel(), B.ptr(g_p), B.stream())
+                mlp._weight_gradient(elem, x, hidden, dz, dz_out, N, partials, g_p, zero_bias=False)
         if mlp.second_order:   # retained only under create_graph=True: a plain backward runs this in no-grad mode
             ctx.save_for_backward(hidden, dz, dz_out, *fwd_img)
         return g_x, g_p
@@ -203,7 +250,7 @@ class _MLPBwdFn(torch.autograd.Function):
         none = (None,) * (6 + ctx.n_saved)
         if gg_x is None or not (need_p or need_g):
             return none
-        N, P = gg_x.shape[0], mlp._offsets[-1]
+        N, P = gg_x.shape[0], mlp._bias_offsets[-1]   # all parameters: matrices, then biases
         v = gg_x.contiguous()
         u_dtype = ctx.g_dtype if ctx.g_dtype in (torch.float32, mlp.dtype) else torch.float32
         if N == 0:
@@ -214,7 +261,7 @@ class _MLPBwdFn(torch.autograd.Function):
             params, *saved = ctx.saved_tensors
             hidden, dzs = saved[:L], saved[L:]
             with torch.autocast("cpu", enabled=False):
-                u, g_p, _ = _tangent_torch(v, mlp._views(params), hidden, dzs, mlp.dtype, need_p)
+                u, g_p, _ = _tangent_torch(v, mlp._views(params), hidden, dzs, mlp.dtype, need_p, mlp.bias_enabled, mlp.skip_mask)
             return (None, g_p, u.to(ctx.g_dtype) if need_g else None) + none[3:]
         hidden, dz, dz_out, fwd_img = ctx.saved_tensors
         elem, dev = B.ELEM_CODES[mlp.dtype], v.device
@@ -222,13 +269,16 @@ class _MLPBwdFn(torch.autograd.Function):
         u = torch.empty(N, mlp.n_output_dims, dtype=u_dtype, device=dev)
         g_p = None
         with torch.cuda.device(dev):
-            B.call("nfa_mlp_tangent", elem, B.ptr(v), B.ELEM_CODES[v.dtype], B.ptr(hidden), B.ptr(fwd_img), N, *mlp._shape,
-                   B.ptr(tangent), B.ptr(u), B.ELEM_CODES[u_dtype], B.stream())
-            if need_p:   # ds/dW_l = dZ_l^T T_{l-1}: the weight gradient pass on (v, T) in the place of (x, H)
+            if mlp._plain:
+                B.call("nfa_mlp_tangent", elem, B.ptr(v), B.ELEM_CODES[v.dtype], B.ptr(hidden), B.ptr(fwd_img), N, *mlp._shape,
+                       B.ptr(tangent), B.ptr(u), B.ELEM_CODES[u_dtype], B.stream())
+            else:
+                B.call("nfa_mlp_net_tangent", elem, mlp._desc, B.ptr(v), B.ELEM_CODES[v.dtype], B.ptr(hidden), B.ptr(fwd_img), N,
+                       B.ptr(tangent), B.ptr(u), B.ELEM_CODES[u_dtype], B.stream())
+            if need_p:   # ds/dW_l = dZ_l^T [T_{l-1}(, v)]: the weight gradient pass on (v, T) in the place of (x, H); ds/db = 0
                 partials = torch.empty(wgrad_slices(N) * P, dtype=torch.float32, device=dev)
                 g_p = torch.empty(P, dtype=torch.float32, device=dev)
-                B.call("nfa_mlp_bwd_weights", elem, B.ptr(v), B.ELEM_CODES[v.dtype], B.ptr(tangent), B.ptr(dz), B.ptr(dz_out), N,
-                       *mlp._shape, B.ptr(partials), partials.numel(), B.ptr(g_p), B.stream())
+                mlp._weight_gradient(elem, v, tangent, dz, dz_out, N, partials, g_p, zero_bias=True)
         return (None, g_p, (u if u.dtype == ctx.g_dtype else u.to(ctx.g_dtype)) if need_g else None) + none[3:]
 
 
@@ -258,11 +308,27 @@ class FusedMLP(nn.Module):
     the same bits on every run.  It costs memory only under ``create_graph=True``, where the graph keeps the ``dZ_l`` alive.
     The derivative of ``dL/dparams`` and a third order raise.  Without it (the default) differentiating the gradients again
     raises ``NotImplementedError``.
+
+    ``bias=True`` and ``skip_layer=`` make it the reference's own ``MLP`` class (ref: examples/radiance_fields/mlp.py), in
+    the same launches.  ``bias``: every layer ``l`` has a float32 bias ``b_l [out_l]``, ``z_l = b_l + W_l in_l``; the bias is
+    never rounded to ``dtype`` (it is the float32 value the layer's sum starts from) and ``dL/db_l = sum_p dZ_l[p]`` is float32,
+    without atomics.  ``skip_layer``: the reference's rule, after hidden layer ``i`` with ``i > 0 and i % skip_layer == 0`` the
+    network input is appended, ``in_{i+1} = cat([H_i, x])`` in this column order, and the next matrix (which may be the output
+    matrix) is ``[out, n_neurons + n_input_dims]``; a ``skip_layer`` that selects no layer is the plain chain bit for bit.
+    ``params`` then holds all matrices in layer order, each ``[out, in_l]`` row-major, and behind them all biases in layer
+    order, initialised to zero (:meth:`bias` is a view of one); without either argument offsets, random draws and values are
+    unchanged, and Xavier uses each matrix's true fan-in.  With the second order ``T_l`` at such a layer sees ``[T_{l-1}, v]``,
+    and the gradient of ``<v, dL/dx>`` towards the biases is exactly zero (the bias segment of the flat gradient).
+    Limits besides those above: with a skip ``n_input_dims + n_neurons <= 256`` (what the weight gradient stages for one
+    layer), and the LDS budget counts the longer images and, for the forward pass, ``(n_hidden_layers n_neurons + 32) * 4``
+    bytes of biases.  :func:`reference_mlp` builds the module from the reference's argument names and
+    :meth:`load_reference_state_dict` takes its state dict.
     """
 
     def __init__(self, n_input_dims: int, n_output_dims: int, n_neurons: int = 64, n_hidden_layers: int = 2,
                  dtype: torch.dtype = torch.float16, out_dtype: Optional[torch.dtype] = None,
-                 generator: Optional[torch.Generator] = None, second_order: bool = False):
+                 generator: Optional[torch.Generator] = None, second_order: bool = False, bias: bool = False,
+                 skip_layer: Optional[int] = None):
         super().__init__()
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError(f"FusedMLP: dtype {dtype}: torch.float16 or torch.bfloat16")
@@ -276,21 +342,34 @@ class FusedMLP(nn.Module):
             raise ValueError(f"FusedMLP: n_input_dims {n_input_dims}: 1 to {MAX_INPUT_DIMS}")
         if not 1 <= n_output_dims <= MAX_OUTPUT_DIMS:
             raise ValueError(f"FusedMLP: n_output_dims {n_output_dims}: 1 to {MAX_OUTPUT_DIMS}")
-        fwd, bwd = image_elems(n_input_dims, n_output_dims, n_neurons, n_hidden_layers)
-        if max(fwd, bwd) * 2 + STAGE_BYTES > LDS_BUDGET:
-            raise ValueError(f"FusedMLP: the packed weights do not fit the LDS: forward image {fwd * 2} B, backward image {bwd * 2} B, "
+        if skip_layer is not None and not (isinstance(skip_layer, int) and skip_layer >= 1):
+            raise ValueError(f"FusedMLP: skip_layer {skip_layer!r}: None or a positive integer")
+        skip_mask = skip_mask_of(skip_layer, n_hidden_layers)
+        if skip_mask and n_input_dims + n_neurons > MAX_CAT_DIMS:
+            raise ValueError(f"FusedMLP: n_input_dims {n_input_dims} + n_neurons {n_neurons} = {n_input_dims + n_neurons}: a layer that "
+                             f"takes [H, x] (skip_layer {skip_layer}) holds at most {MAX_CAT_DIMS} inputs")
+        fwd, bwd = image_elems(n_input_dims, n_output_dims, n_neurons, n_hidden_layers, skip_mask)
+        bias_bytes = lds_bias_bytes(n_neurons, n_hidden_layers, bool(bias))
+        if max(fwd * 2 + bias_bytes, bwd * 2) + STAGE_BYTES > LDS_BUDGET:
+            raise ValueError(f"FusedMLP: the packed weights do not fit the LDS: forward image {fwd * 2} B"
+                             + (f" with {bias_bytes} B of biases" if bias else "") + f", backward image {bwd * 2} B, "
                              f"each with {STAGE_BYTES} B of store staging, against {LDS_BUDGET} B per compute unit "
                              f"(n_input_dims {n_input_dims}, n_output_dims {n_output_dims}, n_neurons {n_neurons}, "
-                             f"n_hidden_layers {n_hidden_layers})")
+                             f"n_hidden_layers {n_hidden_layers}" + (f", bias {bool(bias)}, skip_layer {skip_layer}" if bias or skip_mask else "")
+                             + ")")
         self.n_input_dims, self.n_output_dims = n_input_dims, n_output_dims
         self.n_neurons, self.n_hidden_layers = n_neurons, n_hidden_layers
         self.dtype, self.out_dtype = dtype, out_dtype or dtype
         self.second_order = bool(second_order)
+        self.bias_enabled, self.skip_layer, self.skip_mask = bool(bias), skip_layer, skip_mask
         self._shape = (n_input_dims, n_output_dims, n_neurons, n_hidden_layers)
-        self._dims = layer_dims(*self._shape)
-        self._offsets = [0]
+        self._dims = layer_dims(*self._shape, skip_mask)
+        self._offsets = [0]   # of the matrices; the last one is where the biases start
         for o, i in self._dims:
             self._offsets.append(self._offsets[-1] + o * i)
+        self._bias_offsets = [self._offsets[-1]]
+        for o, _ in self._dims:
+            self._bias_offsets.append(self._bias_offsets[-1] + (o if self.bias_enabled else 0))
         self._image_elems = (fwd, bwd)
         self._packed = None   # (key, forward image, backward image)
         if generator is None:
@@ -299,6 +378,8 @@ class FusedMLP(nn.Module):
         for o, i in self._dims:
             bound = math.sqrt(6.0 / (i + o))
             init.append((torch.rand(o * i, generator=generator, dtype=torch.float32) * 2.0 - 1.0) * bound)
+        if self.bias_enabled:
+            init.append(torch.zeros(self._bias_offsets[-1] - self._offsets[-1]))
         self.params = nn.Parameter(torch.cat(init))
 
     @property
@@ -308,22 +389,84 @@ class FusedMLP(nn.Module):
     def _views(self, params: Tensor) -> List[Tensor]:
         return [params[self._offsets[l]:self._offsets[l + 1]].view(*self._dims[l]) for l in range(self.n_layers)]
 
+    def _bias_views(self, params: Tensor) -> Optional[List[Tensor]]:
+        if not self.bias_enabled:
+            return None
+        return [params[self._bias_offsets[l]:self._bias_offsets[l + 1]] for l in range(self.n_layers)]
+
+    def _bias_ptr(self, params: Tensor) -> Optional[int]:
+        return params.data_ptr() + 4 * self._offsets[-1] if self.bias_enabled else None
+
+    @property
+    def _desc(self) -> "B.MLPDesc":
+        """struct nfa_mlp_desc of this network (built once; not part of the module's state)."""
+        d = self.__dict__.get("_desc_cache")
+        if d is None:
+            d = self.__dict__["_desc_cache"] = B.MLPDesc(*self._shape, int(self.bias_enabled), self.skip_mask)
+        return d
+
+    @property
+    def _plain(self) -> bool:
+        """No bias and no skip: the network of the ``nfa_mlp_*`` entries, which such a module keeps calling (the
+        ``nfa_mlp_net_*`` entries with ``bias = 0, skip_mask = 0`` are the same passes)."""
+        return not self.bias_enabled and self.skip_mask == 0
+
+    def _weight_gradient(self, elem, x, hidden, dz, dz_out, N, partials, g_p, zero_bias: bool) -> None:
+        """dW (and db) on ``(x, hidden)``, or the second order's on ``(v, tangent)``, whose bias segment is zero."""
+        if self._plain:
+            B.call("nfa_mlp_bwd_weights", elem, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(hidden), B.ptr(dz), B.ptr(dz_out), N,
+                   *self._shape, B.ptr(partials), partials.numel(), B.ptr(g_p), B.stream())
+        else:
+            B.call("nfa_mlp_net_bwd_weights", elem, self._desc, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(hidden), B.ptr(dz),
+                   B.ptr(dz_out), N, B.ptr(partials), partials.numel(), B.ptr(g_p), int(zero_bias), B.stream())
+
     def weight(self, l: int) -> Tensor:
         """The view ``[out_l, in_l]`` of matrix ``l`` in ``params``."""
         return self._views(self.params)[l]
 
+    def bias(self, l: int) -> Tensor:
+        """The view ``[out_l]`` of bias ``l`` in ``params`` (a module with ``bias=True``)."""
+        if not self.bias_enabled:
+            raise ValueError("FusedMLP: this module has no biases (bias=False)")
+        return self._bias_views(self.params)[l]
+
     def linear_weights(self) -> List[Tensor]:
-        """Copies of the matrices, for ``nn.Linear(bias=False).weight``."""
+        """Copies of the matrices, for ``nn.Linear.weight``."""
         return [w.detach().clone() for w in self._views(self.params)]
 
+    def linear_biases(self) -> List[Tensor]:
+        """Copies of the biases, for ``nn.Linear(bias=True).bias``."""
+        return [b.detach().clone() for b in (self._bias_views(self.params) or [])]
+
     @torch.no_grad()
-    def load_linear_weights(self, weights: Sequence[Tensor]) -> None:
+    def load_linear_weights(self, weights: Sequence[Tensor], biases: Optional[Sequence[Tensor]] = None) -> None:
         if len(weights) != self.n_layers:
             raise ValueError(f"FusedMLP: {len(weights)} matrices for {self.n_layers} layers")
+        if biases is not None and not self.bias_enabled:
+            raise ValueError("FusedMLP: biases given to a module without biases (bias=False)")
+        if biases is not None and len(biases) != self.n_layers:
+            raise ValueError(f"FusedMLP: {len(biases)} biases for {self.n_layers} layers")
         for l, (w, v) in enumerate(zip(weights, self._views(self.params))):
             if tuple(w.shape) != tuple(v.shape):
                 raise ValueError(f"FusedMLP: matrix {l} is {tuple(w.shape)}, expected {tuple(v.shape)}")
+        for l, (b, v) in enumerate(zip(biases or [], self._bias_views(self.params) or [])):
+            if tuple(b.shape) != tuple(v.shape):
+                raise ValueError(f"FusedMLP: bias {l} is {tuple(b.shape)}, expected {tuple(v.shape)}")
+        for w, v in zip(weights, self._views(self.params)):
             v.copy_(w)
+        for b, v in zip(biases or [], self._bias_views(self.params) or []):
+            v.copy_(b)
+
+    def load_reference_state_dict(self, sd: dict) -> None:
+        """Takes the state dict of the reference's ``MLP`` (ref: examples/radiance_fields/mlp.py): ``hidden_layers.{i}.weight``,
+        ``output_layer.weight`` and, for a module with biases, the ``.bias`` keys beside them.  Any other key, a missing key and
+        a wrong shape raise ``ValueError``."""
+        names = [f"hidden_layers.{i}" for i in range(self.n_hidden_layers)] + ["output_layer"]
+        want = {n + ".weight" for n in names} | ({n + ".bias" for n in names} if self.bias_enabled else set())
+        if set(sd) != want:
+            raise ValueError(f"FusedMLP: load_reference_state_dict: missing keys {sorted(want - set(sd))}, unexpected keys "
+                             f"{sorted(set(sd) - want)}")
+        self.load_linear_weights([sd[n + ".weight"] for n in names], [sd[n + ".bias"] for n in names] if self.bias_enabled else None)
 
     def _images(self, params: Tensor):
         """The packed images of the current masters: one small launch per change of ``params``."""
@@ -332,8 +475,12 @@ class FusedMLP(nn.Module):
             fwd = torch.empty(self._image_elems[0], dtype=self.dtype, device=params.device)
             bwd = torch.empty(self._image_elems[1], dtype=self.dtype, device=params.device)
             with torch.cuda.device(params.device):
-                B.call("nfa_mlp_pack_weights", B.ELEM_CODES[self.dtype], B.ptr(params), *self._shape, B.ptr(fwd), fwd.numel(),
-                       B.ptr(bwd), bwd.numel(), B.stream())
+                if self._plain:
+                    B.call("nfa_mlp_pack_weights", B.ELEM_CODES[self.dtype], B.ptr(params), *self._shape, B.ptr(fwd), fwd.numel(),
+                           B.ptr(bwd), bwd.numel(), B.stream())
+                else:
+                    B.call("nfa_mlp_net_pack_weights", B.ELEM_CODES[self.dtype], self._desc, B.ptr(params), B.ptr(fwd), fwd.numel(),
+                           B.ptr(bwd), bwd.numel(), B.stream())
             self._packed = (key, fwd, bwd)
         return self._packed[1], self._packed[2]
 
@@ -347,7 +494,8 @@ class FusedMLP(nn.Module):
 
     def extra_repr(self) -> str:
         return (f"{self.n_input_dims} -> {' -> '.join([str(self.n_neurons)] * self.n_hidden_layers)} -> {self.n_output_dims}, "
-                f"dtype={self.dtype}, out_dtype={self.out_dtype}" + (", second_order=True" if self.second_order else ""))
+                f"dtype={self.dtype}, out_dtype={self.out_dtype}" + (", second_order=True" if self.second_order else "")
+                + (", bias=True" if self.bias_enabled else "") + (f", skip_layer={self.skip_layer}" if self.skip_layer is not None else ""))
 
 
 _TCNN_KEYS = ("otype", "activation", "output_activation", "n_neurons", "n_hidden_layers")
@@ -373,3 +521,26 @@ def mlp_from_tcnn_config(n_input_dims: int, n_output_dims: int, config: dict, dt
         raise ValueError(f"mlp_from_tcnn_config: 'n_hidden_layers': {n_hidden!r} is not supported, 1 to {MAX_HIDDEN_LAYERS}")
     return FusedMLP(n_input_dims, n_output_dims, n_neurons, n_hidden, dtype=dtype, out_dtype=out_dtype, generator=generator,
                     second_order=second_order)
+
+
+def reference_mlp(input_dim: int, output_dim: int, net_depth: int = 4, net_width: int = 64, skip_layer: Optional[int] = 4,
+                  bias_enabled: bool = True, dtype: torch.dtype = torch.float16, out_dtype: Optional[torch.dtype] = None,
+                  generator: Optional[torch.Generator] = None, second_order: bool = False, output_enabled: bool = True,
+                  hidden_activation: str = "ReLU", output_activation: str = "None") -> FusedMLP:
+    """A :class:`FusedMLP` from the argument names of the reference's ``MLP`` (ref: examples/radiance_fields/mlp.py:14-29):
+    ``net_depth`` is ``n_hidden_layers``, ``net_width`` is ``n_neurons``.  What the kernels do not hold raises ``ValueError``
+    naming the argument: ``net_depth`` 0 or above 4, ``net_width`` other than 64 or 128, ``output_enabled=False``, a hidden
+    activation other than ReLU, an output activation (those live in :func:`nerfacc_amd.rendering_from_raw`).  The defaults of
+    depth and width are NOT the reference's (8 x 256, which stays torch): give both."""
+    if not (isinstance(net_depth, int) and 1 <= net_depth <= MAX_HIDDEN_LAYERS):
+        raise ValueError(f"reference_mlp: 'net_depth': {net_depth!r} is not supported, 1 to {MAX_HIDDEN_LAYERS}")
+    if net_width not in WIDTHS:
+        raise ValueError(f"reference_mlp: 'net_width': {net_width!r} is not supported, one of {WIDTHS}")
+    if not output_enabled:
+        raise ValueError("reference_mlp: 'output_enabled': False is not supported (the network ends in its output layer)")
+    if hidden_activation != "ReLU":
+        raise ValueError(f"reference_mlp: 'hidden_activation': {hidden_activation!r} is not supported, only 'ReLU'")
+    if output_activation not in ("None", None):
+        raise ValueError(f"reference_mlp: 'output_activation': {output_activation!r} is not supported, only 'None'")
+    return FusedMLP(input_dim, output_dim, net_width, net_depth, dtype=dtype, out_dtype=out_dtype, generator=generator,
+                    second_order=second_order, bias=bias_enabled, skip_layer=skip_layer)
