@@ -1142,6 +1142,38 @@ int nfa_mlp_net_bwd_weights(int32_t elem, const nfa_mlp_desc *net, const void *x
 int nfa_mlp_net_tangent(int32_t elem, const nfa_mlp_desc *net, const void *v, int32_t v_elem, const void *hidden, const void *fwd_image,
                         int64_t n_points, void *tangent, void *u, int32_t u_elem, nfa_stream_t stream);
 
+/* The same network with STREAMED weights (csrc/mlp_stream.hip), for what the entries above refuse: NeRF's 63 -> 8 x 256 trunk
+ * (ref: examples/radiance_fields/mlp.py, NerfMLP).  Descriptor, parameter layout, images (nfa_mlp_stream_pack_weights writes
+ * exactly what nfa_mlp_net_pack_weights would), buffers, arithmetic and rounding points are those of the nfa_mlp_net_* entries,
+ * and so are the argument lists and the null-pointer, alignment, negative-n_points and n_points = 0 checks.  The images stay in
+ * global memory and pass through the LDS one row tile of one layer at a time (a "piece": 32 rows x all k-steps of the layer),
+ * through a ring of two slots, while a workgroup's NFA_MLP_STREAM_POINTS points wait in registers; the fused passes launch
+ * min(ceil(n_points / NFA_MLP_STREAM_POINTS), NFA_MLP_STREAM_GROUPS) workgroups, each sweeping the points with that stride.
+ * Limits, checked by every entry in this order after the null descriptor and elem: width 128 or 256; n_hidden 1 .. 8; n_in
+ * 1 .. 320; n_out 1 .. 288; n_points >= 0; bias 0 or 1; skip_mask with bits 2 .. n_hidden only (no limit on n_in + width);
+ * the ring: 2 slots of the largest piece (at most (width / 16 + 20) KiB) + 16896 B of store staging + 1280 B of piece table +
+ * (n_hidden width + 32 ceil(n_out / 32)) 4 B of biases (bias != 0; the forward pass stages them once per workgroup) against
+ * 160 KiB of LDS, which holds for every shape inside the other limits (101248 B at most).
+ * There is no tangent entry: the second order is not implemented for the streamed network.
+ * nfa_mlp_stream_bwd_weights: partials holds s slices of n_params floats, s = clamp(ceil(n_points / NFA_MLP_STREAM_WGRAD_MIN_SLICE),
+ * 1, NFA_MLP_STREAM_WGRAD_MAX_SLICES) cut as in nfa_mlp_bwd_weights (slice length rounded up to 64 points, s the slices that
+ * are not empty): a function of n_points alone, at most 16 (the trunk has 0.6 M parameters: 38 MB of partials).  Grid (slice,
+ * layer, 128 x 128 macro tile of dW_l); the slices are summed in ascending order: no atomics, bitwise reproducible. */
+#define NFA_MLP_STREAM_POINTS 128
+#define NFA_MLP_STREAM_GROUPS 256
+#define NFA_MLP_STREAM_WGRAD_MIN_SLICE 256
+#define NFA_MLP_STREAM_WGRAD_MAX_SLICES 16
+int nfa_mlp_stream_pack_weights(int32_t elem, const nfa_mlp_desc *net, const float *params, void *fwd_image, int64_t fwd_elems,
+                                void *bwd_image, int64_t bwd_elems, nfa_stream_t stream);
+int nfa_mlp_stream_fwd(int32_t elem, const nfa_mlp_desc *net, const void *x, int32_t x_elem, const void *fwd_image, const float *bias,
+                       int64_t n_points, void *y, int32_t y_elem, void *hidden, int32_t save_hidden, nfa_stream_t stream);
+int nfa_mlp_stream_bwd_data(int32_t elem, const nfa_mlp_desc *net, const void *grad_y, int32_t g_elem, const void *hidden,
+                            const void *bwd_image, int64_t n_points, void *dz, void *dz_out, void *grad_x, int32_t x_elem,
+                            nfa_stream_t stream);
+int nfa_mlp_stream_bwd_weights(int32_t elem, const nfa_mlp_desc *net, const void *x, int32_t x_elem, const void *hidden, const void *dz,
+                               const void *dz_out, int64_t n_points, float *partials, int64_t partial_floats, float *grad_params,
+                               int32_t zero_bias, nfa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -180,6 +180,10 @@ _SIGS = {
     "nfa_mlp_net_bwd_data": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp],
     "nfa_mlp_net_bwd_weights": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp],
     "nfa_mlp_net_tangent": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _vp],
+    "nfa_mlp_stream_pack_weights": [_i32, C.POINTER(MLPDesc), _vp, _vp, _i64, _vp, _i64, _vp],
+    "nfa_mlp_stream_fwd": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp],
+    "nfa_mlp_stream_bwd_data": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp],
+    "nfa_mlp_stream_bwd_weights": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],

@@ -1,5 +1,7 @@
 """The field's network as fused half-precision MFMA passes (csrc/mlp.hip): tiny-cuda-nn's ``FullyFusedMLP``, and with
-``bias=`` / ``skip_layer=`` the reference's own ``MLP`` class (ref: examples/radiance_fields/mlp.py) up to 128 neurons.
+``bias=`` / ``skip_layer=`` the reference's own ``MLP`` class (ref: examples/radiance_fields/mlp.py) up to 128 neurons.  Wider and
+deeper networks -- 128 or 256 neurons, up to 8 hidden layers: the reference's ``NerfMLP`` -- are :class:`StreamedMLP` and
+:class:`NerfMLP` at the end of this module (csrc/mlp_stream.hip: the packed weights stream through the LDS).
 
 The reference's NGP fields put ``tcnn.Network(otype="FullyFusedMLP")`` between the encodings and the renderer (ref:
 examples/radiance_fields/ngp.py:131-135, 150-154, 255-259): 64 neurons, 1 or 2 hidden layers, ReLU, no biases, no output
@@ -174,7 +176,7 @@ class _MLPFn(torch.autograd.Function):
                 B.call("nfa_mlp_fwd", elem, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(fwd_img), N, *mlp._shape, B.ptr(y),
                        B.ELEM_CODES[y.dtype], B.ptr(hidden), int(need_grad), B.stream())
             else:
-                B.call("nfa_mlp_net_fwd", elem, mlp._desc, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(fwd_img), mlp._bias_ptr(params), N,
+                B.call(mlp._entry("fwd"), elem, mlp._desc, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(fwd_img), mlp._bias_ptr(params), N,
                        B.ptr(y), B.ELEM_CODES[y.dtype], B.ptr(hidden), int(need_grad), B.stream())
         if need_grad:   # the second order runs the chain again on the forward image
             ctx.save_for_backward(x, params, hidden, bwd_img, *([fwd_img] if mlp.second_order else []))
@@ -224,11 +226,11 @@ class _MLPBwdFn(torch.autograd.Function):
                 B.call("nfa_mlp_bwd_data", elem, B.ptr(g), B.ELEM_CODES[g.dtype], B.ptr(hidden), B.ptr(bwd_img), N, *mlp._shape,
                        B.ptr(dz), None if dz_out is g else B.ptr(dz_out), B.ptr(g_x), B.ELEM_CODES[x.dtype], B.stream())
             else:
-                B.call("nfa_mlp_net_bwd_data", elem, mlp._desc, B.ptr(g), B.ELEM_CODES[g.dtype], B.ptr(hidden), B.ptr(bwd_img), N,
+                B.call(mlp._entry("bwd_data"), elem, mlp._desc, B.ptr(g), B.ELEM_CODES[g.dtype], B.ptr(hidden), B.ptr(bwd_img), N,
                        B.ptr(dz), None if dz_out is g else B.ptr(dz_out), B.ptr(g_x), B.ELEM_CODES[x.dtype], B.stream())
             if need_p:
                 P = params.numel()
-                partials = torch.empty(wgrad_slices(N) * P, dtype=torch.float32, device=dev)
+                partials = torch.empty(mlp._slices(N) * P, dtype=torch.float32, device=dev)
                 g_p = torch.empty(P, dtype=torch.float32, device=dev)
                 mlp._weight_gradient(elem, x, hidden, dz, dz_out, N, partials, g_p, zero_bias=False)
         if mlp.second_order:   # retained only under create_graph=True: a plain backward runs this in no-grad mode
@@ -239,6 +241,9 @@ class _MLPBwdFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gg_x, gg_p):
         mlp = ctx.mlp
+        if isinstance(mlp, StreamedMLP):
+            raise NotImplementedError("StreamedMLP: the second order (differentiating dL/dx or dL/dparams again, create_graph=True) is "
+                                      "not implemented for the streamed network; FusedMLP(second_order=True) holds up to 128 neurons")
         if not mlp.second_order:
             raise NotImplementedError("FusedMLP: the second order (differentiating dL/dx or dL/dparams again, create_graph=True) is not "
                                       "enabled for this module: construct it with second_order=True (that of dL/dx, which an "
@@ -357,6 +362,21 @@ class FusedMLP(nn.Module):
                              f"(n_input_dims {n_input_dims}, n_output_dims {n_output_dims}, n_neurons {n_neurons}, "
                              f"n_hidden_layers {n_hidden_layers}" + (f", bias {bool(bias)}, skip_layer {skip_layer}" if bias or skip_mask else "")
                              + ")")
+        self._setup(n_input_dims, n_output_dims, n_neurons, n_hidden_layers, dtype, out_dtype, generator, second_order, bias,
+                    skip_layer, skip_mask, (fwd, bwd))
+
+    _NAME = "FusedMLP"
+
+    def _entry(self, name: str) -> str:
+        """The C entry of a pass of a network with a descriptor."""
+        return "nfa_mlp_net_" + name
+
+    _slices = staticmethod(wgrad_slices)
+
+    def _setup(self, n_input_dims, n_output_dims, n_neurons, n_hidden_layers, dtype, out_dtype, generator, second_order, bias,
+               skip_layer, skip_mask, image_elems_) -> None:
+        """The module's state and its initial parameters, once the constructor has accepted the configuration."""
+        fwd, bwd = image_elems_
         self.n_input_dims, self.n_output_dims = n_input_dims, n_output_dims
         self.n_neurons, self.n_hidden_layers = n_neurons, n_hidden_layers
         self.dtype, self.out_dtype = dtype, out_dtype or dtype
@@ -417,7 +437,7 @@ class FusedMLP(nn.Module):
             B.call("nfa_mlp_bwd_weights", elem, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(hidden), B.ptr(dz), B.ptr(dz_out), N,
                    *self._shape, B.ptr(partials), partials.numel(), B.ptr(g_p), B.stream())
         else:
-            B.call("nfa_mlp_net_bwd_weights", elem, self._desc, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(hidden), B.ptr(dz),
+            B.call(self._entry("bwd_weights"), elem, self._desc, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(hidden), B.ptr(dz),
                    B.ptr(dz_out), N, B.ptr(partials), partials.numel(), B.ptr(g_p), int(zero_bias), B.stream())
 
     def weight(self, l: int) -> Tensor:
@@ -427,7 +447,7 @@ class FusedMLP(nn.Module):
     def bias(self, l: int) -> Tensor:
         """The view ``[out_l]`` of bias ``l`` in ``params`` (a module with ``bias=True``)."""
         if not self.bias_enabled:
-            raise ValueError("FusedMLP: this module has no biases (bias=False)")
+            raise ValueError(f"{self._NAME}: this module has no biases (bias=False)")
         return self._bias_views(self.params)[l]
 
     def linear_weights(self) -> List[Tensor]:
@@ -441,17 +461,17 @@ class FusedMLP(nn.Module):
     @torch.no_grad()
     def load_linear_weights(self, weights: Sequence[Tensor], biases: Optional[Sequence[Tensor]] = None) -> None:
         if len(weights) != self.n_layers:
-            raise ValueError(f"FusedMLP: {len(weights)} matrices for {self.n_layers} layers")
+            raise ValueError(f"{self._NAME}: {len(weights)} matrices for {self.n_layers} layers")
         if biases is not None and not self.bias_enabled:
-            raise ValueError("FusedMLP: biases given to a module without biases (bias=False)")
+            raise ValueError(f"{self._NAME}: biases given to a module without biases (bias=False)")
         if biases is not None and len(biases) != self.n_layers:
-            raise ValueError(f"FusedMLP: {len(biases)} biases for {self.n_layers} layers")
+            raise ValueError(f"{self._NAME}: {len(biases)} biases for {self.n_layers} layers")
         for l, (w, v) in enumerate(zip(weights, self._views(self.params))):
             if tuple(w.shape) != tuple(v.shape):
-                raise ValueError(f"FusedMLP: matrix {l} is {tuple(w.shape)}, expected {tuple(v.shape)}")
+                raise ValueError(f"{self._NAME}: matrix {l} is {tuple(w.shape)}, expected {tuple(v.shape)}")
         for l, (b, v) in enumerate(zip(biases or [], self._bias_views(self.params) or [])):
             if tuple(b.shape) != tuple(v.shape):
-                raise ValueError(f"FusedMLP: bias {l} is {tuple(b.shape)}, expected {tuple(v.shape)}")
+                raise ValueError(f"{self._NAME}: bias {l} is {tuple(b.shape)}, expected {tuple(v.shape)}")
         for w, v in zip(weights, self._views(self.params)):
             v.copy_(w)
         for b, v in zip(biases or [], self._bias_views(self.params) or []):
@@ -464,7 +484,7 @@ class FusedMLP(nn.Module):
         names = [f"hidden_layers.{i}" for i in range(self.n_hidden_layers)] + ["output_layer"]
         want = {n + ".weight" for n in names} | ({n + ".bias" for n in names} if self.bias_enabled else set())
         if set(sd) != want:
-            raise ValueError(f"FusedMLP: load_reference_state_dict: missing keys {sorted(want - set(sd))}, unexpected keys "
+            raise ValueError(f"{self._NAME}: load_reference_state_dict: missing keys {sorted(want - set(sd))}, unexpected keys "
                              f"{sorted(set(sd) - want)}")
         self.load_linear_weights([sd[n + ".weight"] for n in names], [sd[n + ".bias"] for n in names] if self.bias_enabled else None)
 
@@ -479,16 +499,16 @@ class FusedMLP(nn.Module):
                     B.call("nfa_mlp_pack_weights", B.ELEM_CODES[self.dtype], B.ptr(params), *self._shape, B.ptr(fwd), fwd.numel(),
                            B.ptr(bwd), bwd.numel(), B.stream())
                 else:
-                    B.call("nfa_mlp_net_pack_weights", B.ELEM_CODES[self.dtype], self._desc, B.ptr(params), B.ptr(fwd), fwd.numel(),
+                    B.call(self._entry("pack_weights"), B.ELEM_CODES[self.dtype], self._desc, B.ptr(params), B.ptr(fwd), fwd.numel(),
                            B.ptr(bwd), bwd.numel(), B.stream())
             self._packed = (key, fwd, bwd)
         return self._packed[1], self._packed[2]
 
     def forward(self, x: Tensor) -> Tensor:
         if x.dim() != 2 or x.shape[1] != self.n_input_dims:
-            raise ValueError(f"FusedMLP: x must be [N, {self.n_input_dims}], got {tuple(x.shape)}")
+            raise ValueError(f"{self._NAME}: x must be [N, {self.n_input_dims}], got {tuple(x.shape)}")
         if x.dtype not in (torch.float32, self.dtype):
-            raise TypeError(f"FusedMLP: x is {x.dtype}: torch.float32 or the network's {self.dtype}")
+            raise TypeError(f"{self._NAME}: x is {x.dtype}: torch.float32 or the network's {self.dtype}")
         with torch.autocast(x.device.type, enabled=False):
             return _MLPFn.apply(x.contiguous(), self.params.float().contiguous(), self)
 
@@ -531,7 +551,8 @@ def reference_mlp(input_dim: int, output_dim: int, net_depth: int = 4, net_width
     ``net_depth`` is ``n_hidden_layers``, ``net_width`` is ``n_neurons``.  What the kernels do not hold raises ``ValueError``
     naming the argument: ``net_depth`` 0 or above 4, ``net_width`` other than 64 or 128, ``output_enabled=False``, a hidden
     activation other than ReLU, an output activation (those live in :func:`nerfacc_amd.rendering_from_raw`).  The defaults of
-    depth and width are NOT the reference's (8 x 256, which stays torch): give both."""
+    depth and width are NOT the reference's (8 x 256, which this class does not hold: that network is :class:`StreamedMLP` /
+    :class:`NerfMLP`): give both."""
     if not (isinstance(net_depth, int) and 1 <= net_depth <= MAX_HIDDEN_LAYERS):
         raise ValueError(f"reference_mlp: 'net_depth': {net_depth!r} is not supported, 1 to {MAX_HIDDEN_LAYERS}")
     if net_width not in WIDTHS:
@@ -544,3 +565,221 @@ def reference_mlp(input_dim: int, output_dim: int, net_depth: int = 4, net_width
         raise ValueError(f"reference_mlp: 'output_activation': {output_activation!r} is not supported, only 'None'")
     return FusedMLP(input_dim, output_dim, net_width, net_depth, dtype=dtype, out_dtype=out_dtype, generator=generator,
                     second_order=second_order, bias=bias_enabled, skip_layer=skip_layer)
+
+
+# ---------------------------------------------------------------- streamed weights (csrc/mlp_stream.hip)
+
+STREAM_WIDTHS = (128, 256)
+STREAM_MAX_HIDDEN_LAYERS = 8
+STREAM_MAX_INPUT_DIMS = 320
+STREAM_MAX_OUTPUT_DIMS = 288
+# include/nerfacc_hip.h: NFA_MLP_STREAM_POINTS, NFA_MLP_STREAM_GROUPS, NFA_MLP_STREAM_WGRAD_MIN_SLICE, NFA_MLP_STREAM_WGRAD_MAX_SLICES
+STREAM_POINTS = 128              # points a workgroup carries through one pass of the image
+STREAM_GROUPS = 256              # workgroups of a fused pass at most: the persistent grid
+STREAM_WGRAD_MIN_SLICE = 256
+STREAM_WGRAD_MAX_SLICES = 16
+STREAM_SLOTS = 2                 # csrc/mlp_stream.hip: ST_SLOTS
+STREAM_TABLE_BYTES = 160 * 8     # the piece table (ST_MAX_PIECES entries)
+
+
+def stream_wgrad_slices(n_points: int) -> int:
+    """Slices the streamed weight gradient cuts ``n_points`` into (include/nerfacc_hip.h: nfa_mlp_stream_bwd_weights):
+    ``clamp(ceil(n_points / 256), 1, 16)`` slices of a length rounded up to 64 points, those that are not empty."""
+    s = min(max(_cdiv(n_points, STREAM_WGRAD_MIN_SLICE), 1), STREAM_WGRAD_MAX_SLICES)
+    slice_len = _cdiv(_cdiv(n_points, s), 64) * 64
+    return _cdiv(n_points, slice_len)
+
+
+def stream_piece_bytes(n_in: int, n_out: int, width: int, n_hidden: int, skip_mask: int = 0) -> int:
+    """Bytes of the largest piece (one row tile of one layer: 32 rows x all its k-steps, 1 KiB each) of either image."""
+    dims = layer_dims(n_in, n_out, width, n_hidden, skip_mask)
+    fwd = [_cdiv(width, 16) + _cdiv(n_in, 16) if (skip_mask >> l) & 1 else _cdiv(i, 16) for l, (o, i) in enumerate(dims)]
+    bwd = [_cdiv(o, 16) for o, i in dims]
+    return max(fwd + bwd) * 1024
+
+
+def stream_bias_bytes(n_out: int, width: int, n_hidden: int, bias: int) -> int:
+    """Bytes of the float32 biases as the streamed forward pass holds them in LDS (the output layer padded to whole row tiles)."""
+    return (n_hidden * width + _cdiv(n_out, 32) * 32) * 4 if bias else 0
+
+
+def stream_lds_bytes(n_in: int, n_out: int, width: int, n_hidden: int, bias: int, skip_mask: int = 0) -> int:
+    """LDS of a streamed fused pass at most: the ring, the store staging, the piece table and the forward's biases."""
+    return (STREAM_SLOTS * stream_piece_bytes(n_in, n_out, width, n_hidden, skip_mask) + STAGE_BYTES + STREAM_TABLE_BYTES
+            + stream_bias_bytes(n_out, width, n_hidden, bias))
+
+
+def stream_limits_error(n_in: int, n_out: int, width: int, n_hidden: int, bias: int, skip_mask: int) -> Optional[str]:
+    """What csrc/mlp_stream.hip's check_stream_shape refuses, in its order; None for a network the streamed passes hold."""
+    if width not in STREAM_WIDTHS:
+        return f"width {width}: 128 or 256 neurons are supported"
+    if not 1 <= n_hidden <= STREAM_MAX_HIDDEN_LAYERS:
+        return f"n_hidden {n_hidden}: 1 to {STREAM_MAX_HIDDEN_LAYERS} hidden layers are supported"
+    if not 1 <= n_in <= STREAM_MAX_INPUT_DIMS:
+        return f"n_in {n_in}: 1 to {STREAM_MAX_INPUT_DIMS} input features are supported"
+    if not 1 <= n_out <= STREAM_MAX_OUTPUT_DIMS:
+        return f"n_out {n_out}: 1 to {STREAM_MAX_OUTPUT_DIMS} outputs are supported"
+    if bias not in (0, 1):
+        return f"bias {bias}: 0 or 1"
+    if skip_mask & ~((2 << n_hidden) - 4):
+        return (f"skip_mask 0x{skip_mask:x}: only bits 2 to n_hidden ({n_hidden}) may be set: layer 0 takes x itself and layer 1 "
+                "follows it")
+    piece = stream_piece_bytes(n_in, n_out, width, n_hidden, skip_mask)
+    lds = stream_lds_bytes(n_in, n_out, width, n_hidden, bias, skip_mask)
+    if lds > LDS_BUDGET:
+        return (f"the ring does not fit the LDS: {STREAM_SLOTS} slots of the largest piece ({piece} B) with {STAGE_BYTES} B of store "
+                f"staging, {STREAM_TABLE_BYTES} B of piece table and {stream_bias_bytes(n_out, width, n_hidden, bias)} B of biases are "
+                f"{lds} B, against {LDS_BUDGET} B per compute unit (n_in {n_in}, "
+                f"n_out {n_out}, width {width}, n_hidden {n_hidden}, bias {bias}, skip_mask 0x{skip_mask:x})")
+    return None
+
+
+class StreamedMLP(FusedMLP):
+    """:class:`FusedMLP` for the networks it refuses: 128 or 256 neurons, 1..8 hidden layers, ``n_input_dims`` 1..320,
+    ``n_output_dims`` 1..288, biases and the reference's skip rule (``skip_layer``; no limit on ``n_input_dims + n_neurons``).
+    NeRF's trunk is ``StreamedMLP(63, 257, 256, 8, skip_layer=4)``.
+
+    The contract is :class:`FusedMLP`'s, word for word: one flat float32 ``params`` (all matrices, then all biases), the same
+    accessors and loaders, Xavier per matrix with its true fan-in and zero biases, float32 or ``dtype`` ``x``, ``dtype`` or
+    float32 ``y``, ``dL/dx`` in ``x``'s dtype, ``dL/dparams`` float32 without atomics (the same bits on every run),
+    ``torch.autocast`` changes nothing, the packed images are rebuilt when ``params`` changes, ``N = 0`` works, CPU tensors
+    take the torch restatement.  Arithmetic and rounding points are the same too; a 128-wide network that both classes hold
+    gives the same bits for ``y`` and ``dL/dx``.
+
+    What differs is the kernels (csrc/mlp_stream.hip): the packed weights stay in global memory and pass through the LDS one
+    32-row tile of one layer at a time, through a ring of two slots, while a workgroup's 128 points wait in registers; the
+    weight gradient runs on a grid (point slice, layer, 128 x 128 tile of the matrix) with at most 16 slices
+    (:func:`stream_wgrad_slices`).  There is no second order: differentiating the gradients again raises
+    ``NotImplementedError`` (NeRF has no Eikonal term).
+    """
+
+    _NAME = "StreamedMLP"
+    _slices = staticmethod(stream_wgrad_slices)
+
+    def __init__(self, n_input_dims: int, n_output_dims: int, n_neurons: int = 256, n_hidden_layers: int = 8,
+                 dtype: torch.dtype = torch.float16, out_dtype: Optional[torch.dtype] = None,
+                 generator: Optional[torch.Generator] = None, bias: bool = True, skip_layer: Optional[int] = 4):
+        nn.Module.__init__(self)
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"StreamedMLP: dtype {dtype}: torch.float16 or torch.bfloat16")
+        if out_dtype not in (None, dtype, torch.float32):
+            raise ValueError(f"StreamedMLP: out_dtype {out_dtype}: None, dtype ({dtype}) or torch.float32")
+        if skip_layer is not None and not (isinstance(skip_layer, int) and skip_layer >= 1):
+            raise ValueError(f"StreamedMLP: skip_layer {skip_layer!r}: None or a positive integer")
+        for name, v in (("n_input_dims", n_input_dims), ("n_output_dims", n_output_dims), ("n_neurons", n_neurons),
+                        ("n_hidden_layers", n_hidden_layers)):
+            if not isinstance(v, int):
+                raise ValueError(f"StreamedMLP: {name} {v!r}: an integer")
+        skip_mask = skip_mask_of(skip_layer, n_hidden_layers) if 1 <= n_hidden_layers <= STREAM_MAX_HIDDEN_LAYERS else 0
+        err = stream_limits_error(n_input_dims, n_output_dims, n_neurons, n_hidden_layers, int(bool(bias)), skip_mask)
+        if err:
+            raise ValueError("StreamedMLP: " + err)
+        self._setup(n_input_dims, n_output_dims, n_neurons, n_hidden_layers, dtype, out_dtype, generator, False, bias, skip_layer,
+                    skip_mask, image_elems(n_input_dims, n_output_dims, n_neurons, n_hidden_layers, skip_mask))
+
+    def _entry(self, name: str) -> str:
+        return "nfa_mlp_stream_" + name
+
+    @property
+    def _plain(self) -> bool:
+        return False   # the streamed entries all take the descriptor
+
+
+class NerfMLP(nn.Module):
+    """The reference's ``NerfMLP`` (ref: examples/radiance_fields/mlp.py:114-165), the network of its vanilla NeRF and T-NeRF
+    fields, as two :class:`StreamedMLP`: ``forward(x, condition=None) -> (raw_rgb, raw_sigma)`` and ``query_density(x)``.
+
+    ``trunk``: the reference's ``base`` (``net_depth`` x ``net_width``, biases, the input appended after every hidden layer
+    ``i > 0`` with ``i % skip_layer == 0``) with ONE merged output matrix in the place of the linear layers that read its
+    output.  With a condition (``condition_dim > 0``) rows ``0 .. net_width-1`` are ``bottleneck_layer`` and row
+    ``net_width`` is ``sigma_layer``; without one rows 0..2 are the colour layer and row 3 is ``sigma_layer``.  These are
+    linear maps of the same vector, so merging them is exact; if the base ends in ``cat([H, x])``, the merged layer is a cat
+    output layer.  Each block of rows is initialised with its own Xavier fan, as the reference's separate layers are.
+    ``head`` (with a condition): ``StreamedMLP(net_width + condition_dim, 3, net_width_condition, net_depth_condition)``
+    without a skip, applied to ``cat([bottleneck, condition])``.
+
+    A ``condition`` of one row per ray is broadcast over ``x``'s middle dimensions as the reference does.  Outputs are
+    ``dtype``.  What stays torch, on purpose: the split of the trunk's output, the cat with the condition, and their
+    backward; and ``query_density`` runs the whole merged output layer (about an eighth more work than sigma alone needs).
+    :meth:`load_reference_state_dict` takes the reference module's state dict.
+    """
+
+    def __init__(self, input_dim: int, condition_dim: int, net_depth: int = 8, net_width: int = 256, skip_layer: Optional[int] = 4,
+                 net_depth_condition: int = 1, net_width_condition: int = 128, dtype: torch.dtype = torch.float16,
+                 generator: Optional[torch.Generator] = None):
+        super().__init__()
+        if not (isinstance(condition_dim, int) and condition_dim >= 0):
+            raise ValueError(f"NerfMLP: condition_dim {condition_dim!r}: a non-negative integer")
+        if generator is None:
+            generator = torch.Generator().manual_seed(1337)
+        self.input_dim, self.condition_dim, self.net_width = input_dim, condition_dim, net_width
+        n_out = net_width + 1 if condition_dim > 0 else 4
+        self.trunk = StreamedMLP(input_dim, n_out, net_width, net_depth, dtype=dtype, generator=generator, bias=True,
+                                 skip_layer=skip_layer)
+        with torch.no_grad():   # the merged output matrix: each block of rows with the fan of the layer it is
+            w = self.trunk.weight(net_depth)
+            fan_in, r0 = w.shape[1], 0
+            for rows in ((net_width, 1) if condition_dim > 0 else (3, 1)):
+                bound = math.sqrt(6.0 / (fan_in + rows))
+                w[r0:r0 + rows] = (torch.rand(rows, fan_in, generator=generator, dtype=torch.float32) * 2.0 - 1.0) * bound
+                r0 += rows
+        self.head = None
+        if condition_dim > 0:
+            self.head = StreamedMLP(net_width + condition_dim, 3, net_width_condition, net_depth_condition, dtype=dtype,
+                                    generator=generator, bias=True, skip_layer=None)
+
+    def _trunk(self, x: Tensor) -> Tensor:
+        if x.shape[-1] != self.input_dim:
+            raise ValueError(f"NerfMLP: x must be [..., {self.input_dim}], got {tuple(x.shape)}")
+        return self.trunk(x.reshape(-1, self.input_dim))
+
+    def query_density(self, x: Tensor) -> Tensor:
+        row = self.net_width if self.head is not None else 3
+        return self._trunk(x)[:, row:row + 1].reshape(*x.shape[:-1], 1)
+
+    def forward(self, x: Tensor, condition: Optional[Tensor] = None):
+        if (condition is None) != (self.head is None):
+            raise ValueError(f"NerfMLP: condition_dim is {self.condition_dim}: a condition " +
+                             ("is required" if condition is None else "cannot be taken"))
+        lead = x.shape[:-1]
+        y = self._trunk(x)
+        if self.head is None:
+            return y[:, :3].reshape(*lead, 3), y[:, 3:4].reshape(*lead, 1)
+        W = self.net_width
+        if condition.shape[:-1] != lead:   # one row per ray, broadcast over the samples (ref: mlp.py:157-161)
+            num_rays, n_dim = condition.shape
+            condition = condition.view([num_rays] + [1] * (x.dim() - condition.dim()) + [n_dim]).expand(list(lead) + [n_dim])
+        if condition.shape[-1] != self.condition_dim:
+            raise ValueError(f"NerfMLP: condition must be [..., {self.condition_dim}], got {tuple(condition.shape)}")
+        h = torch.cat([y[:, :W], condition.reshape(-1, self.condition_dim).to(y.device)], dim=-1)
+        if h.dtype not in (torch.float32, self.head.dtype):
+            h = h.float()
+        return self.head(h).reshape(*lead, 3), y[:, W:W + 1].reshape(*lead, 1)
+
+    def reference_keys(self) -> List[str]:
+        """The keys of the reference module's state dict for this configuration."""
+        names = [f"base.hidden_layers.{i}" for i in range(self.trunk.n_hidden_layers)] + ["sigma_layer.output_layer"]
+        if self.head is not None:
+            names += ["bottleneck_layer.output_layer"] + [f"rgb_layer.hidden_layers.{i}" for i in range(self.head.n_hidden_layers)]
+        names += ["rgb_layer.output_layer"]
+        return [n + s for n in names for s in (".weight", ".bias")]
+
+    def load_reference_state_dict(self, sd: dict) -> None:
+        """Takes the state dict of the reference's ``NerfMLP``: ``base.hidden_layers.{i}.*``, ``sigma_layer.output_layer.*``,
+        ``bottleneck_layer.output_layer.*``, ``rgb_layer.hidden_layers.{i}.*``, ``rgb_layer.output_layer.*`` (``.weight`` and
+        ``.bias`` each).  Any other key, a missing key and a wrong shape raise ``ValueError``."""
+        want = set(self.reference_keys())
+        if set(sd) != want:
+            raise ValueError(f"NerfMLP: load_reference_state_dict: missing keys {sorted(want - set(sd))}, unexpected keys "
+                             f"{sorted(set(sd) - want)}")
+        D = self.trunk.n_hidden_layers
+        first = "bottleneck_layer.output_layer" if self.head is not None else "rgb_layer.output_layer"
+        for suffix, dim in ((".weight", 2), (".bias", 1)):
+            for k in (first + suffix, "sigma_layer.output_layer" + suffix):
+                if sd[k].dim() != dim or (dim == 2 and sd[k].shape[1] != self.trunk._dims[D][1]):
+                    raise ValueError(f"NerfMLP: load_reference_state_dict: '{k}' is {tuple(sd[k].shape)}")
+        merged = lambda s: torch.cat([sd[first + s], sd["sigma_layer.output_layer" + s]], dim=0)
+        self.trunk.load_linear_weights([sd[f"base.hidden_layers.{i}.weight"] for i in range(D)] + [merged(".weight")],
+                                       [sd[f"base.hidden_layers.{i}.bias"] for i in range(D)] + [merged(".bias")])
+        if self.head is not None:
+            self.head.load_reference_state_dict({k[len("rgb_layer."):]: v for k, v in sd.items() if k.startswith("rgb_layer.")})
