@@ -1174,6 +1174,93 @@ int nfa_mlp_stream_bwd_weights(int32_t elem, const nfa_mlp_desc *net, const void
                                const void *dz_out, int64_t n_points, float *partials, int64_t partial_floats, float *grad_params,
                                int32_t zero_bias, nfa_stream_t stream);
 
+/* ------------------------------------------------------------------ fused optimiser (csrc/optim.hip)
+ * One Adam / AdamW step (torch's, non-amsgrad) over a LIST of float32 tensors in at most three launches, whatever the length
+ * of the list, with the loss scale, its overflow policy (torch's GradScaler) and a warm-up + multi-step LR schedule held and
+ * advanced on the device: no host read, so a whole training step captures into one graph.  The launches are cut at the
+ * all-to-all seams (no grid-wide barrier): nfa_optim_scan (only with a scaler), nfa_optim_decide (one wave), nfa_optim_update.
+ *
+ * The list is two device arrays the caller builds once per set of pointers and sizes: `table` (one nfa_optim_tensor per
+ * tensor) and `work` (one nfa_optim_chunk per NFA_OPTIM_CHUNK elements of a tensor, the last chunk of a tensor shorter: no
+ * chunk crosses a tensor, every element is in exactly one chunk).  A workgroup takes chunks in a grid-stride loop.  Where the
+ * four pointers of a tensor are 16-byte aligned a lane moves 16-byte pieces and the tail (n % 4 elements) goes element by
+ * element; otherwise the whole tensor does.  Both paths run the same per-element function: the same bits.  No atomics.
+ *
+ * Per element, float32, every operation rounded on its own, in this order (G: the group's scalars, below):
+ *     g = grad * inv_scale
+ *     skip_zero_grad and g == 0:  p, m, v stay as they are (no decay either)
+ *     L2 decay (weight_decay != 0, not decoupled):  g = g + weight_decay * p
+ *     decoupled decay:                              p = p * decay
+ *     m = m + one_minus_beta1 * (g - m)
+ *     v = beta2 * v + one_minus_beta2 * (g * g)
+ *     p = p - (step_size * m) / (sqrt(v) / bc2_sqrt + eps)
+ * zero_grad: grad = 0 afterwards, on a skipped step too.  On a skipped step nothing else is written. */
+#define NFA_OPTIM_CHUNK 4096       /* elements per work-list entry (a multiple of 4) */
+#define NFA_OPTIM_MAX_GROUPS 16
+#define NFA_OPTIM_MAX_MILESTONES 8
+#define NFA_OPTIM_DECOUPLED 1      /* nfa_optim_group.flags: weight decay is AdamW's */
+#define NFA_OPTIM_SKIP_ZERO_GRAD 2 /* an element whose unscaled gradient is exactly 0 is left alone (tiny-cuda-nn's rule) */
+typedef struct nfa_optim_tensor {   /* 48 bytes */
+    float *p, *grad, *exp_avg, *exp_avg_sq;
+    int64_t n;
+    int32_t group;                  /* index into the groups of nfa_optim_args */
+    int32_t reserved;
+} nfa_optim_tensor;
+typedef struct nfa_optim_chunk {    /* elements [chunk * NFA_OPTIM_CHUNK, min(n, (chunk + 1) * NFA_OPTIM_CHUNK)) of table[tensor] */
+    int32_t tensor, chunk;
+} nfa_optim_chunk;
+/* The scaler's state, device memory owned by the caller (32 bytes).  found: set to 1 by nfa_optim_scan, read and cleared by
+ * nfa_optim_decide.  Policy (torch.amp.GradScaler): found -> scale *= backoff_factor, tracker = 0, skipped += 1 and the step
+ * is skipped; else tracker += 1 and at growth_interval scale *= growth_factor (kept if finite), tracker = 0. */
+typedef struct nfa_optim_scaler {
+    float scale;
+    int32_t tracker, found, reserved;
+    int64_t skipped, reserved2;
+} nfa_optim_scaler;
+typedef struct nfa_optim_group {    /* a param group's settings as the host has them now (48 bytes) */
+    double lr, beta1, beta2, eps, weight_decay;
+    int32_t flags, reserved;
+} nfa_optim_group;
+/* HOST struct, passed by value into the decide launch (a captured graph keeps the values it was captured with).
+ * Schedule: factor(t) = (start_factor + (1 - start_factor) * min(t, warmup_iters) / warmup_iters) * gamma^(milestones <= t),
+ * t = nfa_optim_state.calls, the power by repeated multiplication, all in double; warmup_iters = 0 and n_milestones = 0: 1. */
+typedef struct nfa_optim_args {
+    int32_t n_groups, n_milestones;
+    nfa_optim_group groups[NFA_OPTIM_MAX_GROUPS];
+    double start_factor, gamma;
+    int64_t warmup_iters;
+    int64_t milestones[NFA_OPTIM_MAX_MILESTONES];
+    float growth_factor, backoff_factor;   /* of the scaler */
+    int32_t growth_interval, reserved;     /* <= 0: the scale stays fixed on clean steps */
+} nfa_optim_args;
+typedef struct nfa_optim_group_scalars {   /* 48 bytes; what nfa_optim_update reads, each a double expression rounded once */
+    float step_size;        /* lr * factor / (1 - beta1^step) */
+    float bc2_sqrt;         /* sqrt(1 - beta2^step) */
+    float decay;            /* 1 - lr * factor * weight_decay */
+    float one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay;
+    int32_t flags, reserved[3];
+} nfa_optim_group_scalars;
+/* Device memory owned by the caller; calls = step = 0 and every power 1.0 at the start.  step counts PERFORMED updates (bias
+ * correction), calls counts nfa_optim_decide launches (the schedule).  beta^step are running products in double. */
+typedef struct nfa_optim_state {
+    int64_t calls, step;
+    double beta1_pow[NFA_OPTIM_MAX_GROUPS], beta2_pow[NFA_OPTIM_MAX_GROUPS];
+    float inv_scale;   /* this step's: float(1 / scale) of the scale the gradients were made with; 1 without a scaler */
+    int32_t skip;      /* this step's: the scan found a non-finite gradient */
+    float factor;      /* this step's schedule factor (for inspection) */
+    int32_t reserved;
+    nfa_optim_group_scalars group[NFA_OPTIM_MAX_GROUPS];
+} nfa_optim_state;
+int nfa_optim_chunk_elems(void);   /* NFA_OPTIM_CHUNK */
+/* scaler->found = 1 if any gradient of the list is not finite (left alone otherwise).  dtype: NFA_ELEM_F32, anything else is
+ * NFA_EINVAL.  n_tensors = 0 or n_chunks = 0: nothing to do. */
+int nfa_optim_scan(int32_t dtype, const nfa_optim_tensor *table, int32_t n_tensors, const nfa_optim_chunk *work, int64_t n_chunks,
+                   nfa_optim_scaler *scaler, nfa_stream_t stream);
+/* This step's scalars into *state, the counters, the powers and the scaler advanced.  scaler NULL: no loss scaling. */
+int nfa_optim_decide(const nfa_optim_args *args_host, nfa_optim_state *state, nfa_optim_scaler *scaler, nfa_stream_t stream);
+int nfa_optim_update(int32_t dtype, const nfa_optim_tensor *table, int32_t n_tensors, const nfa_optim_chunk *work, int64_t n_chunks,
+                     const nfa_optim_state *state, int32_t zero_grad, nfa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

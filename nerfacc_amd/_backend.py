@@ -47,6 +47,22 @@ class MLPDesc(C.Structure):
     _fields_ = [("n_in", _i32), ("n_out", _i32), ("width", _i32), ("n_hidden", _i32), ("bias", _i32), ("skip_mask", _i32)]
 
 
+OPTIM_MAX_GROUPS, OPTIM_MAX_MILESTONES = 16, 8   # include/nerfacc_hip.h: NFA_OPTIM_MAX_GROUPS, NFA_OPTIM_MAX_MILESTONES
+
+
+class OptimGroup(C.Structure):
+    """struct nfa_optim_group (include/nerfacc_hip.h)."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("flags", _i32), ("reserved", _i32)]
+
+
+class OptimArgs(C.Structure):
+    """struct nfa_optim_args (include/nerfacc_hip.h)."""
+    _fields_ = [("n_groups", _i32), ("n_milestones", _i32), ("groups", OptimGroup * OPTIM_MAX_GROUPS),
+                ("start_factor", C.c_double), ("gamma", C.c_double), ("warmup_iters", _i64), ("milestones", _i64 * OPTIM_MAX_MILESTONES),
+                ("growth_factor", _f32), ("backoff_factor", _f32), ("growth_interval", _i32), ("reserved", _i32)]
+
+
 # name -> argtypes (all return int unless listed in _RESTYPES)
 _SIGS = {
     "nfa_exclusive_cumsum_i64": [_vp, _i64, _vp, _vp, _vp, _vp],
@@ -184,6 +200,10 @@ _SIGS = {
     "nfa_mlp_stream_fwd": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp],
     "nfa_mlp_stream_bwd_data": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp],
     "nfa_mlp_stream_bwd_weights": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp],
+    "nfa_optim_chunk_elems": [],
+    "nfa_optim_scan": [_i32, _vp, _i32, _vp, _i64, _vp, _vp],
+    "nfa_optim_decide": [C.POINTER(OptimArgs), _vp, _vp, _vp],
+    "nfa_optim_update": [_i32, _vp, _i32, _vp, _i64, _vp, _i32, _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],
