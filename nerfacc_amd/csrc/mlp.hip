@@ -32,6 +32,22 @@
 // on load / when packed, every hidden activation after its ReLU, every dZ_l and T_l after its mask, y, dx and u once as stored (float32
 // outputs are the accumulators themselves).  Products are exact in float32 and summed by the MFMA in float32.
 //
+// Number-format edges (IEEE arithmetic and torch.autograd's semantics; tests/test_mlp_edges_{cpu,gpu}.py):
+//   1. every rounding above is ONE round-to-nearest-even of the exact float32 value over the whole range: results among the fp16
+//      subnormals are kept (gradual underflow, ties to even), a value at or above MAX + ulp/2 becomes +-inf and one float32 step
+//      below it MAX (fp16: 65520 -> inf, 65519.996 -> 65504; bf16: (2 - 2^-8) 2^127 -> inf), never saturated (bf16: pinned by
+//      the tests' hand-built rows; their scaled bf16 cases pass 2^128 with one product, inf in the float32 accumulator already);
+//   2. fp16 subnormals reach the MFMA un-flushed on both sides: as packed weights (A) and as x, H_l, dZ_l fragments (B);
+//   3. relu(NaN) = NaN, relu(-inf) = 0, relu(+inf) = +inf; the backward's and the tangent's mask is a SELECT (dZ = dH where
+//      H > 0, else 0, whatever dH is; H = NaN counts as not positive), never a multiplication by 0 or 1;
+//   4. a non-finite value in row p of x, g or v changes row p of y, H_l, dZ_l, T_l, dx and u and nothing else in them, also for
+//      p = N - 1 of a partial tile, whose clamped loads put that row into lanes that do not store;
+//   5. an element of dL/dparams is NaN, +inf, -inf or finite exactly where IEEE sums of the rounded operands are (inf * 0 = NaN:
+//      a padded zero never hides an infinity of a real row), and the finite ones are the same bits;
+//   6. so an overflow that is born inside the backward (g * scale finite, dZ_l past MAX) reaches dL/dparams as inf or NaN and
+//      DeviceGradScaler skips the step.
+// Not covered: bf16 subnormals, overflow of a float32 accumulator, non-finite biases.
+//
 // EXEC is all ones around every MFMA: a partial tile clamps the point index of its loads and masks only its stores.
 #include "mlp_tiles.h"
 

@@ -119,7 +119,7 @@ def _backward_torch(x: Tensor, weights: Sequence[Tensor], hidden: Sequence[Tenso
             if (skip_mask >> l) & 1:
                 skips.append(dh[:, W:])
                 dh = dh[:, :W]
-            dz = (dh * (h_prev > 0)).to(dtype).float()
+            dz = torch.where(h_prev > 0, dh, torch.zeros_like(dh)).to(dtype).float()   # a select
             dzs.append(dz)
         else:
             for s in reversed(skips):   # ascending layers, as the kernel adds them
@@ -141,7 +141,7 @@ def _tangent_torch(v: Tensor, weights: Sequence[Tensor], hidden: Sequence[Tensor
     for l, w in enumerate(weights):
         z = _cat_input(t, t0, l, skip_mask) @ w.to(dtype).float().t()
         if l < len(weights) - 1:
-            t = (z * (hidden[l] > 0)).to(dtype).float()
+            t = torch.where(hidden[l] > 0, z, torch.zeros_like(z)).to(dtype).float()
             ts.append(t)
     g_p = None
     if need_p:

@@ -124,7 +124,7 @@ def backward(x, weights, hidden, g, skip_mask, dtype, exact=False, free=None):
             dh = dz @ wh + 0.0
             e_pre = e @ wh.abs() + (K + 2) * U32 * (dz.abs() @ wh.abs())
             mask = (h_prev > 0).double()
-            dz = rnd(dh * mask, dtype, exact)
+            dz = rnd(torch.where(h_prev > 0, dh, torch.zeros_like(dh)), dtype, exact)   # a select
             e = (e_pre + ulp(dtype, dh.abs() + e_pre)) * mask
             if free is not None:
                 unsure = free["z"][l - 1].abs() <= free["e_z"][l - 1]
@@ -159,7 +159,7 @@ def tangent(v, weights, hidden, skip_mask, dtype, out_f32=False, exact=False):
             assert float(s_abs.max()) < 2 ** 24
         if l < len(weights) - 1:
             mask = (hidden[l] > 0).double()
-            t = rnd(z * mask, dtype, exact)
+            t = rnd(torch.where(hidden[l] > 0, z, torch.zeros_like(z)), dtype, exact)
             e = (e_pre + ulp(dtype, z.abs() + e_pre)) * mask
             ts.append(t)
             e_ts.append(e)

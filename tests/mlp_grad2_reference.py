@@ -32,7 +32,7 @@ def tangent(v, weights, hidden, dtype, out_f32=False, exact=False):
             assert float(s_abs.max()) < 2 ** 24
         if l < len(weights) - 1:
             mask = (hidden[l] > 0).double()
-            t = R.rnd(z * mask, dtype, exact)
+            t = R.rnd(torch.where(hidden[l] > 0, z, torch.zeros_like(z)), dtype, exact)
             e = (e_pre + R.ulp(dtype, z.abs() + e_pre)) * mask
             ts.append(t)
             e_ts.append(e)

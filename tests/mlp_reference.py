@@ -83,7 +83,7 @@ def backward(x, weights, hidden, g, dtype, exact=False):
         e_pre = e @ wq.abs() + (K + 2) * U32 * (dz.abs() @ wq.abs())
         if l > 0:
             mask = (h_prev > 0).double()
-            dz = rnd(dh * mask, dtype, exact)
+            dz = rnd(torch.where(h_prev > 0, dh, torch.zeros_like(dh)), dtype, exact)   # a select
             e = (e_pre + ulp(dtype, dh.abs() + e_pre)) * mask
             dzs.append(dz)
             e_dzs.append(e)

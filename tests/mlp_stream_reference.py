@@ -157,7 +157,7 @@ def backward_with_error(x0, e_x, weights, g, e_g, skip_mask, dtype, free, x_dtyp
             dh = dz @ wh
             e_pre = e @ wh.abs() + (K + 2) * U32 * (dz.abs() @ wh.abs())
             mask = (h_prev > 0).double()
-            dz = rnd(dh * mask, dtype)
+            dz = rnd(torch.where(h_prev > 0, dh, torch.zeros_like(dh)), dtype)   # a select
             e = (e_pre + ulp(dtype, dh.abs() + e_pre)) * mask
             unsure = free["z"][l - 1].abs() <= free["e_z"][l - 1]
             e = torch.where(unsure, dh.abs() + e_pre + ulp(dtype, dh.abs() + e_pre), e)
