@@ -1142,6 +1142,51 @@ int nfa_mlp_net_bwd_weights(int32_t elem, const nfa_mlp_desc *net, const void *x
 int nfa_mlp_net_tangent(int32_t elem, const nfa_mlp_desc *net, const void *v, int32_t v_elem, const void *hidden, const void *fwd_image,
                         int64_t n_points, void *tangent, void *u, int32_t u_elem, nfa_stream_t stream);
 
+/* The same network with tiny-cuda-nn's activation set: ONE hidden activation f for all hidden layers and one output activation
+ * f_out, each an NFA_MLP_ACT_* code.  With y_l = f(z_l) as stored (rounded to elem), f' and rho = f'' / f' are formed from y:
+ *   NONE         z                                  f' = 1                        rho = 0
+ *   RELU         max(z, 0)                          select y > 0                  0
+ *   LEAKY_RELU   z > 0 ? z : 0.01f z                y > 0 ? 1 : 0.01f (select)    0
+ *   SIGMOID      1 / (1 + e^-z)                     y (1 - y)                     1 - 2 y
+ *   TANH         tanh z                             1 - y^2                       -2 y
+ *   SOFTPLUS     max(z, 0) + log1p(e^(-beta |z|)) / beta   1 - e^(-beta y)        beta e^(-beta y)
+ *   EXPONENTIAL  e^z                                y                             1
+ * Transcendentals are float32 with the accurate device functions; the result is rounded once where ReLU's is.  Forward:
+ * H_l = f(z_l), y = f_out(z_L).  Data gradient: dZ_L = rnd(grad_y * f_out'(y)), dZ_l = rnd(dH_l * f'(H_l)); y is the
+ * forward's output as stored (y_elem: elem or NFA_ELEM_F32), read only when f_out is not NONE, and then dz_out is required.
+ * Tangent, A_l = W_l [T_{l-1}(, v)]: T_l = rnd(A_l * f'(H_l)), u = f_out'(y) * A_L, and, when r and r_out are given (both or
+ * neither; then dz and dz_out of the first backward are read), R_l = rnd((rho(H_l) dZ_l) A_l) to r [n_hidden, n_points, width]
+ * and R_L = rnd((rho_out(y) dZ_L) A_L) to r_out [n_points, n_out], exact zeros where rho is identically zero.
+ * Curvature pass (the data gradient's chain with an injected cotangent): E_L = r_out, E_{l-1} = rnd((W_l^T E_l)[:width] *
+ * f'(H_{l-1}) + R_{l-1}) with R from `inject` (laid out as `hidden`, 8-byte aligned), written to e [n_hidden, n_points, width];
+ * grad_x = ds/dx = W_0^T E_0 + sum over the cat layers W_l[:, width:]^T E_l.  The second-order parameter gradient is
+ * nfa_mlp_net_bwd_weights twice, on (v, tangent, dz, dz_out) with zero_bias = 1 and on (x, hidden, e, r_out) with zero_bias = 0,
+ * and the sum of the two.  Images, descriptor, nfa_mlp_net_pack_weights and nfa_mlp_net_bwd_weights are shared unchanged.
+ * Checks: those of the nfa_mlp_net_* twins in their order, with the activation checked right after the shape: null `act`, a
+ * code outside NFA_MLP_ACT_NONE .. NFA_MLP_ACT_EXPONENTIAL, beta <= 0 (or NaN).  With hidden = NFA_MLP_ACT_RELU and output = NFA_MLP_ACT_NONE
+ * every pass gives the bits of its twin. */
+#define NFA_MLP_ACT_NONE 0
+#define NFA_MLP_ACT_RELU 1
+#define NFA_MLP_ACT_LEAKY_RELU 2
+#define NFA_MLP_ACT_SIGMOID 3
+#define NFA_MLP_ACT_TANH 4
+#define NFA_MLP_ACT_SOFTPLUS 5
+#define NFA_MLP_ACT_EXPONENTIAL 6
+typedef struct nfa_mlp_act { int32_t hidden, output; float beta; } nfa_mlp_act;
+int nfa_mlp_act_fwd(int32_t elem, const nfa_mlp_desc *net, const nfa_mlp_act *act, const void *x, int32_t x_elem,
+                    const void *fwd_image, const float *bias, int64_t n_points, void *y, int32_t y_elem, void *hidden,
+                    int32_t save_hidden, nfa_stream_t stream);
+int nfa_mlp_act_bwd_data(int32_t elem, const nfa_mlp_desc *net, const nfa_mlp_act *act, const void *grad_y, int32_t g_elem,
+                         const void *y, int32_t y_elem, const void *hidden, const void *bwd_image, int64_t n_points, void *dz,
+                         void *dz_out, void *grad_x, int32_t x_elem, nfa_stream_t stream);
+int nfa_mlp_act_tangent(int32_t elem, const nfa_mlp_desc *net, const nfa_mlp_act *act, const void *v, int32_t v_elem,
+                        const void *y, int32_t y_elem, const void *hidden, const void *dz, const void *dz_out,
+                        const void *fwd_image, int64_t n_points, void *tangent, void *r, void *r_out, void *u, int32_t u_elem,
+                        nfa_stream_t stream);
+int nfa_mlp_act_curvature(int32_t elem, const nfa_mlp_desc *net, const nfa_mlp_act *act, const void *r_out, const void *hidden,
+                          const void *inject, const void *bwd_image, int64_t n_points, void *e, void *grad_x, int32_t x_elem,
+                          nfa_stream_t stream);
+
 /* The same network with STREAMED weights (csrc/mlp_stream.hip), for what the entries above refuse: NeRF's 63 -> 8 x 256 trunk
  * (ref: examples/radiance_fields/mlp.py, NerfMLP).  Descriptor, parameter layout, images (nfa_mlp_stream_pack_weights writes
  * exactly what nfa_mlp_net_pack_weights would), buffers, arithmetic and rounding points are those of the nfa_mlp_net_* entries,

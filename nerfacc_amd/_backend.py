@@ -47,6 +47,15 @@ class MLPDesc(C.Structure):
     _fields_ = [("n_in", _i32), ("n_out", _i32), ("width", _i32), ("n_hidden", _i32), ("bias", _i32), ("skip_mask", _i32)]
 
 
+class MLPAct(C.Structure):
+    """struct nfa_mlp_act (include/nerfacc_hip.h)."""
+    _fields_ = [("hidden", _i32), ("output", _i32), ("beta", _f32)]
+
+
+# include/nerfacc_hip.h: NFA_MLP_ACT_*
+ACT_CODES = {"None": 0, "ReLU": 1, "LeakyReLU": 2, "Sigmoid": 3, "Tanh": 4, "Softplus": 5, "Exponential": 6}
+
+
 OPTIM_MAX_GROUPS, OPTIM_MAX_MILESTONES = 16, 8   # include/nerfacc_hip.h: NFA_OPTIM_MAX_GROUPS, NFA_OPTIM_MAX_MILESTONES
 
 
@@ -196,6 +205,11 @@ _SIGS = {
     "nfa_mlp_net_bwd_data": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp],
     "nfa_mlp_net_bwd_weights": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp],
     "nfa_mlp_net_tangent": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _vp],
+    "nfa_mlp_act_fwd": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPAct), _vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp],
+    "nfa_mlp_act_bwd_data": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPAct), _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp],
+    "nfa_mlp_act_tangent": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPAct), _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                            _i32, _vp],
+    "nfa_mlp_act_curvature": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPAct), _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp],
     "nfa_mlp_stream_pack_weights": [_i32, C.POINTER(MLPDesc), _vp, _vp, _i64, _vp, _i64, _vp],
     "nfa_mlp_stream_fwd": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp],
     "nfa_mlp_stream_bwd_data": [_i32, C.POINTER(MLPDesc), _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp],

@@ -14,6 +14,17 @@
 // The tangent pass is the second order: with v the cotangent of dx and s = <v, dx>, u = ds/dg and ds/dW_l = dZ_l^T T_{l-1}, which is
 // the weight gradient pass run on (v, T) in the place of (x, H).  The masks are the saved ones, never a ReLU of the tangent.
 //
+// Activations (nfa_mlp_act, the ACT instantiations: one per type, width and pass, the general form, the codes run-time values
+// switched once per layer): one hidden activation f and one output activation f_out of None, ReLU, LeakyReLU (slope 0.01f), Sigmoid,
+// Tanh, Softplus (beta) and Exponential.  With y = f(z) as STORED (rounded), f' and rho = f'' / f' are formed from y, never from z:
+//   forward     H_l = f(z_l), y = f_out(z_L)                                   float32, accurate expf / log1pf / tanhf, rounded once
+//   data grad   dZ_L = g * f_out'(y), dZ_l = dH_l * f'(H_l)                    a select for ReLU and LeakyReLU, a product otherwise
+//   tangent     A_l = W_l [T_{l-1}(, v)], T_l = A_l * f'(H_l), u = f_out'(y) * A_L; and R_l = (rho(H_l) dZ_l) A_l, R_L = (rho_out(y) dZ_L) A_L
+//   curvature   E_L = R_L, E_{l-1} = (W_l^T E_l)[:W] * f'(H_{l-1}) + R_{l-1}, ds/dx = W_0^T E_0 + sum_cat W_l[:, W:]^T E_l
+// The curvature pass is the data gradient's chain (the same kernel) with R injected before the rounding: the second derivative of
+// an activation puts a cotangent into every layer.  ds/dW_l = dZ_l^T [T_{l-1}(, v)] + E_l^T [H_{l-1}(, x)] and ds/db_l = sum_p E_l[p]
+// are the weight gradient pass twice.  Where rho is identically zero R is an exact zero, never a product with it.
+//
 // Everything works TRANSPOSED, with the weights as the A operand of v_mfma_f32_32x32x16_{f16,bf16}: a wave owns 32 points, a point
 // is a COLUMN of every tile and so stays on lane (point & 31) of both lane halves through all layers.  The 32x32 float32 result
 // of one layer has its rows (neurons) in the 16 accumulator registers of a lane; converted pairwise to half, registers
@@ -76,12 +87,16 @@ __device__ __forceinline__ Shape shape_of(Shape S)
 // the forward saved, the rounded T_l go to `save` (optional): the derivative of the chain along `in`, which is linear in it.
 // `bias` (forward only; the tangent of a bias is zero): b_0 .. b_L float32, staged once behind the image; every accumulator
 // starts from its rows.  A cat layer runs kq0 more k-steps whose B fragments are rows of `in`, loaded again as layer 0 loads them.
-template <class E, int W, bool TANGENT, bool EXT>
+// ACT (implies EXT): the hidden and the output activation are the run-time codes of `A`, switched once per layer outside the element
+// loops; the forward applies f, the tangent multiplies by f' formed from the saved activations and, given A.r, also writes
+// R_l = (rho(H_l) dZ_l) A_l and R_L, the cotangents the curvature pass injects.
+template <class E, int W, bool TANGENT, bool EXT, bool ACT = false>
 __device__ __forceinline__ void mlp_chain(const Shape &S, const void *__restrict__ in, int in_f32, int in_vec,
                                           const uint16_t *__restrict__ image, int64_t image_elems, const float *__restrict__ bias,
                                           int64_t N, void *__restrict__ out, int out_f32, const uint16_t *__restrict__ mask,
-                                          uint16_t *__restrict__ save)
+                                          uint16_t *__restrict__ save, const ActOps &A = ActOps{})
 {
+    static_assert(EXT || !ACT, "ACT is an instantiation of the general form");
     constexpr int MT = W / 32, KQ = W / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char mlp_lds[];
     nfa_v4u *wimg = reinterpret_cast<nfa_v4u *>(mlp_lds);
@@ -112,17 +127,39 @@ __device__ __forceinline__ void mlp_chain(const Shape &S, const void *__restrict
         for (int l = 1;; ++l) {
             // H_{l-1} = relu(acc) (T_{l-1} = acc * (H_{l-1} > 0)), rounded: the next product's B fragments, and what the
             // backward (the second weight gradient) reads
+            if constexpr (ACT) {
+                act_switch(A.hidden, [&](auto code) __attribute__((always_inline)) {
+                    constexpr int CODE = decltype(code)::value;
 #pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                if constexpr (TANGENT) {
-                    mask_tile_row<E, W>(acc[t], mask + (int64_t)(l - 1) * N * W, pc, t, h);
-                } else {
+                    for (int t = 0; t < MT; ++t) {
+                        if constexpr (TANGENT) {
+                            f32x16 rr;
+                            tangent_tile_row<E, W, CODE>(acc[t], rr, mask + (int64_t)(l - 1) * N * W,
+                                                         A.r ? A.dz + (int64_t)(l - 1) * N * W : nullptr, pc, t, h, A.beta);
+                            if (A.r && p < N)
+                                store_tile_row<W>(A.r + (int64_t)(l - 1) * N * W, p, t, h, acc_frag<E>(rr, 0), acc_frag<E>(rr, 1));
+                        } else {
 #pragma unroll
-                    for (int i = 0; i < 16; ++i) acc[t][i] = acc[t][i] < 0.f ? 0.f : acc[t][i];
+                            for (int i = 0; i < 16; ++i) acc[t][i] = act_value<CODE>(acc[t][i], A.beta);
+                        }
+                        hf[2 * t] = acc_frag<E>(acc[t], 0);
+                        hf[2 * t + 1] = acc_frag<E>(acc[t], 1);
+                        if (save && p < N) store_tile_row<W>(save + (int64_t)(l - 1) * N * W, p, t, h, hf[2 * t], hf[2 * t + 1]);
+                    }
+                });
+            } else {
+#pragma unroll
+                for (int t = 0; t < MT; ++t) {
+                    if constexpr (TANGENT) {
+                        mask_tile_row<E, W>(acc[t], mask + (int64_t)(l - 1) * N * W, pc, t, h);
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) acc[t][i] = acc[t][i] < 0.f ? 0.f : acc[t][i];
+                    }
+                    hf[2 * t] = acc_frag<E>(acc[t], 0);
+                    hf[2 * t + 1] = acc_frag<E>(acc[t], 1);
+                    if (save && p < N) store_tile_row<W>(save + (int64_t)(l - 1) * N * W, p, t, h, hf[2 * t], hf[2 * t + 1]);
                 }
-                hf[2 * t] = acc_frag<E>(acc[t], 0);
-                hf[2 * t + 1] = acc_frag<E>(acc[t], 1);
-                if (save && p < N) store_tile_row<W>(save + (int64_t)(l - 1) * N * W, p, t, h, hf[2 * t], hf[2 * t + 1]);
             }
             if (l == S.n_hidden) break;
             const bool cat = EXT && S.cat(l);
@@ -153,7 +190,20 @@ __device__ __forceinline__ void mlp_chain(const Shape &S, const void *__restrict
             }
         }
         const int64_t row0 = tile * 32;
-        stage_store<E>(o, st, out, out_f32 != 0, row0, (int)(N - row0 < 32 ? N - row0 : 32), S.n_out, 0, S.n_out, lane);
+        const int nrows = (int)(N - row0 < 32 ? N - row0 : 32);
+        if constexpr (ACT && TANGENT) {   // u = f_out'(y) A_L, R_L = (rho_out(y) dZ_L) A_L
+            f32x16 ro;
+            act_switch(A.output, [&](auto code) __attribute__((always_inline)) {
+                tangent_out_tile<E, decltype(code)::value>(o, ro, A, pc, S.n_out, h);
+            });
+            if (A.r_out) stage_store<E>(ro, st, A.r_out, false, row0, nrows, S.n_out, 0, S.n_out, lane);
+        } else if constexpr (ACT) {
+            act_switch(A.output, [&](auto code) __attribute__((always_inline)) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[i] = act_value<decltype(code)::value>(o[i], A.beta);
+            });
+        }
+        stage_store<E>(o, st, out, out_f32 != 0, row0, nrows, S.n_out, 0, S.n_out, lane);
     }
 }
 
@@ -178,18 +228,43 @@ __global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_tangent_kernel(Shape
     mlp_chain<E, W, true, EXT>(shape_of<EXT>(S), v, v_f32, v_vec, image, image_elems, nullptr, N, u, u_f32, hidden, tangent);
 }
 
+// The ACT instantiations of both: one per (type, width), whatever the activations
+template <class E, int W>
+__global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_act_fwd_kernel(Shape S, ActOps A, const void *__restrict__ x, int x_f32,
+                                                                          int x_vec, const uint16_t *__restrict__ image,
+                                                                          int64_t image_elems, const float *__restrict__ bias, int64_t N,
+                                                                          void *__restrict__ y, int y_f32, uint16_t *__restrict__ hidden)
+{
+    mlp_chain<E, W, false, true, true>(S, x, x_f32, x_vec, image, image_elems, bias, N, y, y_f32, nullptr, hidden, A);
+}
+
+template <class E, int W>
+__global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_act_tangent_kernel(Shape S, ActOps A, const void *__restrict__ v, int v_f32,
+                                                                              int v_vec, const uint16_t *__restrict__ hidden,
+                                                                              const uint16_t *__restrict__ image, int64_t image_elems,
+                                                                              int64_t N, uint16_t *__restrict__ tangent,
+                                                                              void *__restrict__ u, int u_f32)
+{
+    mlp_chain<E, W, true, true, true>(S, v, v_f32, v_vec, image, image_elems, nullptr, N, u, u_f32, hidden, tangent, A);
+}
+
 // ---------------------------------------------------------------- data gradient
 
-template <class E, int W, bool EXT>
+// The gradient chain dZ_L = g (* f_out'(y)), dZ_l = (W_{l+1}^T dZ_{l+1})[:W] * f'(H_l), dx over the workgroup's tiles.  ACT: the
+// activations of `A`; with A.inject it is the curvature pass, E_l = (W_{l+1}^T E_{l+1})[:W] * f'(H_l) + R_l, started from g = R_L.
+// One kernel template for both, so that the chain exists once; the instantiations without ACT never read `A`.
+template <class E, int W, bool EXT, bool ACT = false>
 __global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_bwd_data_kernel(Shape S_, const void *__restrict__ g, int g_f32, int g_vec,
                                                                            const uint16_t *__restrict__ hidden,
                                                                            const uint16_t *__restrict__ image, int64_t image_elems,
                                                                            int64_t N, uint16_t *__restrict__ dz,
                                                                            uint16_t *__restrict__ dz_out, void *__restrict__ dx,
-                                                                           int dx_f32)
+                                                                           int dx_f32, ActOps A)
 {
+    static_assert(EXT || !ACT, "ACT is an instantiation of the general form");
     constexpr int MT = W / 32, KQ = W / 16;
     const Shape S = shape_of<EXT>(S_);
+    const bool out_act = ACT && A.output != NFA_MLP_ACT_NONE;   // dZ_L = g * f_out'(y), which then lives in dz_out
     extern __shared__ __attribute__((aligned(16))) unsigned char mlp_lds[];
     nfa_v4u *wimg = reinterpret_cast<nfa_v4u *>(mlp_lds);
     stage_image(wimg, reinterpret_cast<const nfa_v4u *>(image), image_elems / 8);
@@ -207,7 +282,14 @@ __global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_bwd_data_kernel(Shap
         // dH_last = W_L^T dZ_L, dZ_L = g rounded
         int64_t off16 = S.bwd_off(L - 1) / 8;
         for (int q = 0; q < kqo; ++q) {
-            const nfa_v4u b = load_row8<E>(g, g_f32 != 0, pc, S.n_out, 16 * q + 8 * h, g_vec != 0);
+            nfa_v4u b;
+            if (out_act) {
+                act_switch(A.output, [&](auto code) __attribute__((always_inline)) {
+                    b = load_row8_deriv<E, decltype(code)::value>(g, g_f32 != 0, A.y, A.y_f32 != 0, pc, S.n_out, 16 * q + 8 * h, A.beta);
+                });
+            } else {
+                b = load_row8<E>(g, g_f32 != 0, pc, S.n_out, 16 * q + 8 * h, g_vec != 0);
+            }
             if (dz_out && p < N) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
@@ -222,12 +304,25 @@ __global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_bwd_data_kernel(Shap
         for (int l = S.n_hidden - 1;; --l) {
             // dZ_l = dH_l * (H_l > 0), rounded
             const uint16_t *hl = hidden + (int64_t)l * N * W;
+            if constexpr (ACT) {
+                const uint16_t *inj = A.inject ? A.inject + (int64_t)l * N * W : nullptr;
+                act_switch(A.hidden, [&](auto code) __attribute__((always_inline)) {
 #pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                mask_tile_row<E, W>(acc[t], hl, pc, t, h);
-                df[2 * t] = acc_frag<E>(acc[t], 0);
-                df[2 * t + 1] = acc_frag<E>(acc[t], 1);
-                if (p < N) store_tile_row<W>(dz + (int64_t)l * N * W, p, t, h, df[2 * t], df[2 * t + 1]);
+                    for (int t = 0; t < MT; ++t) {
+                        deriv_tile_row<E, W, decltype(code)::value>(acc[t], hl, inj, pc, t, h, A.beta);
+                        df[2 * t] = acc_frag<E>(acc[t], 0);
+                        df[2 * t + 1] = acc_frag<E>(acc[t], 1);
+                        if (p < N) store_tile_row<W>(dz + (int64_t)l * N * W, p, t, h, df[2 * t], df[2 * t + 1]);
+                    }
+                });
+            } else {
+#pragma unroll
+                for (int t = 0; t < MT; ++t) {
+                    mask_tile_row<E, W>(acc[t], hl, pc, t, h);
+                    df[2 * t] = acc_frag<E>(acc[t], 0);
+                    df[2 * t + 1] = acc_frag<E>(acc[t], 1);
+                    if (p < N) store_tile_row<W>(dz + (int64_t)l * N * W, p, t, h, df[2 * t], df[2 * t + 1]);
+                }
             }
             if (l == 0) break;
             off16 = S.bwd_off(l) / 8;
@@ -261,9 +356,10 @@ __global__ __launch_bounds__(MLP_WAVES * NFA_WAVE) void mlp_bwd_data_kernel(Shap
                     if (!S.cat(l)) continue;
                     // rows W + 32m .. of the layer's image: row tile MT + m
                     const int64_t base = S.bwd_off(l) / 8;
-                    if (l == L - 1) {   // dZ_L = g, natural k order as in the first product
+                    if (l == L - 1) {   // dZ_L = g (with an output activation: what this lane's wave wrote to dz_out), natural k order
                         for (int q = 0; q < kqo; ++q) {
-                            const nfa_v4u b = load_row8<E>(g, g_f32 != 0, pc, S.n_out, 16 * q + 8 * h, g_vec != 0);
+                            const nfa_v4u b = out_act ? load_row8<E>(dz_out, false, pc, S.n_out, 16 * q + 8 * h, false)
+                                                      : load_row8<E>(g, g_f32 != 0, pc, S.n_out, 16 * q + 8 * h, g_vec != 0);
                             o = mfma<E>(wimg[base + ((MT + m) * kqo + q) * 64 + lane], b, o);
                         }
                     } else {
@@ -431,6 +527,31 @@ bool dispatch_mlp(int32_t elem, const Shape &S, F &&f)
     return true;
 }
 
+// The ACT instantiations: f(element tag, width).  One per (type, width, pass), the general (EXT) form whatever the network.
+template <class F>
+bool dispatch_mlp_act(int32_t elem, const Shape &S, F &&f)
+{
+    auto widths = [&](auto tag) {
+        if (S.W == 64) f(tag, std::integral_constant<int, 64>{});
+        else f(tag, std::integral_constant<int, 128>{});
+    };
+    if (elem == NFA_ELEM_F16) widths(ElemTag<nfa_f16>{});
+    else if (elem == NFA_ELEM_BF16) widths(ElemTag<nfa_bf16>{});
+    else return false;
+    return true;
+}
+
+int check_act(const char *who, const nfa_mlp_act *act)
+{
+    NFA_REQUIRE(act, "%s: the activation descriptor is null", who);
+    NFA_REQUIRE(act->hidden >= NFA_MLP_ACT_NONE && act->hidden <= NFA_MLP_ACT_EXPONENTIAL, "%s: hidden activation %d: an NFA_MLP_ACT_* code, %d to %d",
+                who, act->hidden, NFA_MLP_ACT_NONE, NFA_MLP_ACT_EXPONENTIAL);
+    NFA_REQUIRE(act->output >= NFA_MLP_ACT_NONE && act->output <= NFA_MLP_ACT_EXPONENTIAL, "%s: output activation %d: an NFA_MLP_ACT_* code, %d to %d",
+                who, act->output, NFA_MLP_ACT_NONE, NFA_MLP_ACT_EXPONENTIAL);
+    NFA_REQUIRE(act->beta > 0.f, "%s: beta %g: Softplus' beta must be positive", who, (double)act->beta);
+    return NFA_OK;
+}
+
 // workgroups of a fused pass: as many as stay resident (LDS and the 8 that 32 waves allow), never more than there are tiles
 unsigned fused_grid(int64_t n_points, int64_t lds_bytes)
 {
@@ -470,10 +591,13 @@ int pack_weights(const char *who, int32_t elem, const nfa_mlp_desc *net, const f
 }
 
 int fwd(const char *who, int32_t elem, const nfa_mlp_desc *net, const void *x, int32_t x_elem, const void *fwd_image, const float *bias,
-        int64_t n_points, void *y, int32_t y_elem, void *hidden, int32_t save_hidden, nfa_stream_t stream)
+        int64_t n_points, void *y, int32_t y_elem, void *hidden, int32_t save_hidden, nfa_stream_t stream,
+        const nfa_mlp_act *act = nullptr, bool with_act = false)
 {
     Shape S;
     if (int rc = check_shape(who, elem, net, n_points, &S)) return rc;
+    if (with_act)
+        if (int rc = check_act(who, act)) return rc;
     NFA_REQUIRE(x_elem == NFA_ELEM_F32 || x_elem == elem, "%s: x_elem %d: float32 or the network's type (%d)", who, x_elem, elem);
     NFA_REQUIRE(y_elem == NFA_ELEM_F32 || y_elem == elem, "%s: y_elem %d: float32 or the network's type (%d)", who, y_elem, elem);
     if (n_points == 0) return NFA_OK;
@@ -483,6 +607,21 @@ int fwd(const char *who, int32_t elem, const nfa_mlp_desc *net, const void *x, i
                 "%s: misaligned pointer (image 16, hidden 8, x, y and bias their element)", who);
     const int64_t img = S.fwd_off(S.layers()), lds = img * 2 + (int64_t)S.lds_bias_floats() * 4 + STAGE_BYTES;
     int rc = NFA_OK;
+    if (with_act) {
+        ActOps A;
+        A.hidden = act->hidden, A.output = act->output, A.beta = act->beta;
+        dispatch_mlp_act(elem, S, [&](auto tag, auto w) {
+            using E = typename decltype(tag)::type;
+            auto kern = mlp_act_fwd_kernel<E, decltype(w)::value>;
+            if ((rc = allow_lds(who, kern, lds)) != NFA_OK) return;
+            kern<<<fused_grid(n_points, lds), MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(
+                S, A, x, x_elem == NFA_ELEM_F32, row8_vec(x, S.n_in), static_cast<const uint16_t *>(fwd_image), img,
+                S.bias ? bias : nullptr, n_points, y, y_elem == NFA_ELEM_F32, save_hidden ? static_cast<uint16_t *>(hidden) : nullptr);
+        });
+        if (rc != NFA_OK) return rc;
+        NFA_CHECK_LAUNCH(who);
+        return NFA_OK;
+    }
     dispatch_mlp(elem, S, [&](auto tag, auto w, auto ext) {
         using E = typename decltype(tag)::type;
         auto kern = mlp_fwd_kernel<E, decltype(w)::value, decltype(ext)::value>;
@@ -497,10 +636,16 @@ int fwd(const char *who, int32_t elem, const nfa_mlp_desc *net, const void *x, i
 }
 
 int bwd_data(const char *who, int32_t elem, const nfa_mlp_desc *net, const void *grad_y, int32_t g_elem, const void *hidden,
-             const void *bwd_image, int64_t n_points, void *dz, void *dz_out, void *grad_x, int32_t x_elem, nfa_stream_t stream)
+             const void *bwd_image, int64_t n_points, void *dz, void *dz_out, void *grad_x, int32_t x_elem, nfa_stream_t stream,
+             const nfa_mlp_act *act = nullptr, bool with_act = false, const void *y = nullptr, int32_t y_elem = NFA_ELEM_F32,
+             const void *inject = nullptr, bool curvature = false)
 {
     Shape S;
     if (int rc = check_shape(who, elem, net, n_points, &S)) return rc;
+    if (with_act) {
+        if (int rc = check_act(who, act)) return rc;
+        NFA_REQUIRE(y_elem == NFA_ELEM_F32 || y_elem == elem, "%s: y_elem %d: float32 or the network's type (%d)", who, y_elem, elem);
+    }
     NFA_REQUIRE(g_elem == NFA_ELEM_F32 || g_elem == elem, "%s: g_elem %d: float32 or the network's type (%d)", who, g_elem, elem);
     NFA_REQUIRE(x_elem == NFA_ELEM_F32 || x_elem == elem, "%s: x_elem %d: float32 or the network's type (%d)", who, x_elem, elem);
     if (n_points == 0) return NFA_OK;
@@ -510,6 +655,34 @@ int bwd_data(const char *who, int32_t elem, const nfa_mlp_desc *net, const void 
                 "%s: misaligned pointer (image 16, hidden and dz 8, the others their element)", who);
     const int64_t img = S.bwd_off(S.layers()), lds = img * 2 + STAGE_BYTES;
     int rc = NFA_OK;
+    if (with_act) {
+        ActOps A;
+        A.hidden = act->hidden, A.beta = act->beta;
+        if (curvature) {   // E_L = R_L as it is: no output derivative
+            NFA_REQUIRE(inject, "%s: null pointer (inject)", who);
+            NFA_REQUIRE(aligned_to(inject, 8), "%s: misaligned pointer (inject 8)", who);
+            A.output = NFA_MLP_ACT_NONE, A.inject = static_cast<const uint16_t *>(inject);
+        } else {
+            A.output = act->output;
+            if (A.output != NFA_MLP_ACT_NONE) {
+                NFA_REQUIRE(y && dz_out, "%s: null pointer (an output activation needs y and dz_out)", who);
+                NFA_REQUIRE(aligned_to(y, y_elem == NFA_ELEM_F32 ? 4 : 2), "%s: misaligned pointer (y its element)", who);
+                A.y = y, A.y_f32 = y_elem == NFA_ELEM_F32;
+            }
+        }
+        dispatch_mlp_act(elem, S, [&](auto tag, auto w) {
+            using E = typename decltype(tag)::type;
+            auto kern = mlp_bwd_data_kernel<E, decltype(w)::value, true, true>;
+            if ((rc = allow_lds(who, kern, lds)) != NFA_OK) return;
+            kern<<<fused_grid(n_points, lds), MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(
+                S, grad_y, g_elem == NFA_ELEM_F32, row8_vec(grad_y, S.n_out), static_cast<const uint16_t *>(hidden),
+                static_cast<const uint16_t *>(bwd_image), img, n_points, static_cast<uint16_t *>(dz), static_cast<uint16_t *>(dz_out),
+                grad_x, x_elem == NFA_ELEM_F32, A);
+        });
+        if (rc != NFA_OK) return rc;
+        NFA_CHECK_LAUNCH(who);
+        return NFA_OK;
+    }
     dispatch_mlp(elem, S, [&](auto tag, auto w, auto ext) {
         using E = typename decltype(tag)::type;
         auto kern = mlp_bwd_data_kernel<E, decltype(w)::value, decltype(ext)::value>;
@@ -517,7 +690,7 @@ int bwd_data(const char *who, int32_t elem, const nfa_mlp_desc *net, const void 
         kern<<<fused_grid(n_points, lds), MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(
             S, grad_y, g_elem == NFA_ELEM_F32, row8_vec(grad_y, S.n_out), static_cast<const uint16_t *>(hidden),
             static_cast<const uint16_t *>(bwd_image), img, n_points, static_cast<uint16_t *>(dz), static_cast<uint16_t *>(dz_out),
-            grad_x, x_elem == NFA_ELEM_F32);
+            grad_x, x_elem == NFA_ELEM_F32, ActOps{});
     });
     if (rc != NFA_OK) return rc;
     NFA_CHECK_LAUNCH(who);
@@ -553,10 +726,16 @@ int bwd_weights(const char *who, int32_t elem, const nfa_mlp_desc *net, const vo
 }
 
 int tangent_pass(const char *who, int32_t elem, const nfa_mlp_desc *net, const void *v, int32_t v_elem, const void *hidden,
-                 const void *fwd_image, int64_t n_points, void *tangent, void *u, int32_t u_elem, nfa_stream_t stream)
+                 const void *fwd_image, int64_t n_points, void *tangent, void *u, int32_t u_elem, nfa_stream_t stream,
+                 const nfa_mlp_act *act = nullptr, bool with_act = false, const void *y = nullptr, int32_t y_elem = NFA_ELEM_F32,
+                 const void *dz = nullptr, const void *dz_out = nullptr, void *r = nullptr, void *r_out = nullptr)
 {
     Shape S;
     if (int rc = check_shape(who, elem, net, n_points, &S)) return rc;
+    if (with_act) {
+        if (int rc = check_act(who, act)) return rc;
+        NFA_REQUIRE(y_elem == NFA_ELEM_F32 || y_elem == elem, "%s: y_elem %d: float32 or the network's type (%d)", who, y_elem, elem);
+    }
     NFA_REQUIRE(v_elem == NFA_ELEM_F32 || v_elem == elem, "%s: v_elem %d: float32 or the network's type (%d)", who, v_elem, elem);
     NFA_REQUIRE(u_elem == NFA_ELEM_F32 || u_elem == elem, "%s: u_elem %d: float32 or the network's type (%d)", who, u_elem, elem);
     if (n_points == 0) return NFA_OK;
@@ -566,6 +745,29 @@ int tangent_pass(const char *who, int32_t elem, const nfa_mlp_desc *net, const v
                 "%s: misaligned pointer (image 16, hidden and tangent 8, v and u their element)", who);
     const int64_t img = S.fwd_off(S.layers()), lds = img * 2 + STAGE_BYTES;   // no biases: a bias has no tangent
     int rc = NFA_OK;
+    if (with_act) {
+        ActOps A;
+        A.hidden = act->hidden, A.output = act->output, A.beta = act->beta;
+        NFA_REQUIRE((r != nullptr) == (r_out != nullptr), "%s: r and r_out: both or neither", who);
+        NFA_REQUIRE(!r || (dz && dz_out), "%s: null pointer (r and r_out need dz and dz_out)", who);
+        NFA_REQUIRE(A.output == NFA_MLP_ACT_NONE || y, "%s: null pointer (an output activation needs y)", who);
+        NFA_REQUIRE(aligned_to(y, y_elem == NFA_ELEM_F32 ? 4 : 2) && aligned_to(dz, 8) && aligned_to(dz_out, 2) && aligned_to(r, 8) &&
+                    aligned_to(r_out, 2), "%s: misaligned pointer (dz and r 8, y, dz_out and r_out their element)", who);
+        A.y = y, A.y_f32 = y_elem == NFA_ELEM_F32;
+        A.dz = static_cast<const uint16_t *>(dz), A.dz_out = static_cast<const uint16_t *>(dz_out);
+        A.r = static_cast<uint16_t *>(r), A.r_out = static_cast<uint16_t *>(r_out);
+        dispatch_mlp_act(elem, S, [&](auto tag, auto w) {
+            using E = typename decltype(tag)::type;
+            auto kern = mlp_act_tangent_kernel<E, decltype(w)::value>;
+            if ((rc = allow_lds(who, kern, lds)) != NFA_OK) return;
+            kern<<<fused_grid(n_points, lds), MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(
+                S, A, v, v_elem == NFA_ELEM_F32, row8_vec(v, S.n_in), static_cast<const uint16_t *>(hidden),
+                static_cast<const uint16_t *>(fwd_image), img, n_points, static_cast<uint16_t *>(tangent), u, u_elem == NFA_ELEM_F32);
+        });
+        if (rc != NFA_OK) return rc;
+        NFA_CHECK_LAUNCH(who);
+        return NFA_OK;
+    }
     dispatch_mlp(elem, S, [&](auto tag, auto w, auto ext) {
         using E = typename decltype(tag)::type;
         auto kern = mlp_tangent_kernel<E, decltype(w)::value, decltype(ext)::value>;
@@ -615,6 +817,40 @@ int nfa_mlp_net_tangent(int32_t elem, const nfa_mlp_desc *net, const void *v, in
                         int64_t n_points, void *tangent, void *u, int32_t u_elem, nfa_stream_t stream)
 {
     return tangent_pass("nfa_mlp_net_tangent", elem, net, v, v_elem, hidden, fwd_image, n_points, tangent, u, u_elem, stream);
+}
+
+// The entries with activations: the same passes in their ACT instantiations.
+
+int nfa_mlp_act_fwd(int32_t elem, const nfa_mlp_desc *net, const nfa_mlp_act *act, const void *x, int32_t x_elem,
+                    const void *fwd_image, const float *bias, int64_t n_points, void *y, int32_t y_elem, void *hidden,
+                    int32_t save_hidden, nfa_stream_t stream)
+{
+    return fwd("nfa_mlp_act_fwd", elem, net, x, x_elem, fwd_image, bias, n_points, y, y_elem, hidden, save_hidden, stream, act, true);
+}
+
+int nfa_mlp_act_bwd_data(int32_t elem, const nfa_mlp_desc *net, const nfa_mlp_act *act, const void *grad_y, int32_t g_elem,
+                         const void *y, int32_t y_elem, const void *hidden, const void *bwd_image, int64_t n_points, void *dz,
+                         void *dz_out, void *grad_x, int32_t x_elem, nfa_stream_t stream)
+{
+    return bwd_data("nfa_mlp_act_bwd_data", elem, net, grad_y, g_elem, hidden, bwd_image, n_points, dz, dz_out, grad_x, x_elem, stream,
+                    act, true, y, y_elem);
+}
+
+int nfa_mlp_act_tangent(int32_t elem, const nfa_mlp_desc *net, const nfa_mlp_act *act, const void *v, int32_t v_elem,
+                        const void *y, int32_t y_elem, const void *hidden, const void *dz, const void *dz_out,
+                        const void *fwd_image, int64_t n_points, void *tangent, void *r, void *r_out, void *u, int32_t u_elem,
+                        nfa_stream_t stream)
+{
+    return tangent_pass("nfa_mlp_act_tangent", elem, net, v, v_elem, hidden, fwd_image, n_points, tangent, u, u_elem, stream, act, true,
+                        y, y_elem, dz, dz_out, r, r_out);
+}
+
+int nfa_mlp_act_curvature(int32_t elem, const nfa_mlp_desc *net, const nfa_mlp_act *act, const void *r_out, const void *hidden,
+                          const void *inject, const void *bwd_image, int64_t n_points, void *e, void *grad_x, int32_t x_elem,
+                          nfa_stream_t stream)
+{
+    return bwd_data("nfa_mlp_act_curvature", elem, net, r_out, elem, hidden, bwd_image, n_points, e, nullptr, grad_x, x_elem, stream,
+                    act, true, nullptr, NFA_ELEM_F32, inject, true);
 }
 
 // The tiny-cuda-nn entries: the same passes for a descriptor without biases and without skips.

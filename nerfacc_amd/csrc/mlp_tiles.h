@@ -190,6 +190,165 @@ __device__ __forceinline__ nfa_v4u load_tile_frag(const uint16_t *m, int64_t p, 
     return nfa_v4u{a[0], a[1], b[0], b[1]};
 }
 
+// ---------------------------------------------------------------- activations (nfa_mlp_act; the ACT instantiations of mlp.hip)
+
+// What an ACT instantiation takes beside the operands of the plain pass.  The codes and beta are wave-uniform.
+struct ActOps {
+    int32_t hidden = 0, output = 0;
+    float beta = 1.f;
+    const void *y = nullptr;            // the output as the forward stored it (the derivatives of the output activation)
+    int32_t y_f32 = 0;
+    const uint16_t *dz = nullptr;       // tangent: dZ_0 .. dZ_{L-1} and dZ_L of the first backward
+    const uint16_t *dz_out = nullptr;
+    uint16_t *r = nullptr;              // tangent: R_0 .. R_{L-1} (laid out as `hidden`) and R_L [N, n_out]; both or neither
+    uint16_t *r_out = nullptr;
+    const uint16_t *inject = nullptr;   // curvature: R_l, added to dH_l f'(H_l) before the rounding
+};
+
+// f(integral_constant<code>) for a wave-uniform activation code: one switch, the element loops inside the cases
+template <class F>
+__device__ __forceinline__ void act_switch(int code, F &&f)
+{
+    switch (code) {
+    case NFA_MLP_ACT_RELU: f(std::integral_constant<int, NFA_MLP_ACT_RELU>{}); break;
+    case NFA_MLP_ACT_LEAKY_RELU: f(std::integral_constant<int, NFA_MLP_ACT_LEAKY_RELU>{}); break;
+    case NFA_MLP_ACT_SIGMOID: f(std::integral_constant<int, NFA_MLP_ACT_SIGMOID>{}); break;
+    case NFA_MLP_ACT_TANH: f(std::integral_constant<int, NFA_MLP_ACT_TANH>{}); break;
+    case NFA_MLP_ACT_SOFTPLUS: f(std::integral_constant<int, NFA_MLP_ACT_SOFTPLUS>{}); break;
+    case NFA_MLP_ACT_EXPONENTIAL: f(std::integral_constant<int, NFA_MLP_ACT_EXPONENTIAL>{}); break;
+    default: f(std::integral_constant<int, NFA_MLP_ACT_NONE>{}); break;
+    }
+}
+
+constexpr bool act_has_rho(int code)
+{
+    return code == NFA_MLP_ACT_SIGMOID || code == NFA_MLP_ACT_TANH || code == NFA_MLP_ACT_SOFTPLUS || code == NFA_MLP_ACT_EXPONENTIAL;
+}
+
+// y = f(z), float32, the accurate device functions; the caller rounds once
+template <int CODE>
+__device__ __forceinline__ float act_value(float z, float beta)
+{
+    if constexpr (CODE == NFA_MLP_ACT_RELU) return z < 0.f ? 0.f : z;
+    else if constexpr (CODE == NFA_MLP_ACT_LEAKY_RELU) return z > 0.f ? z : 0.01f * z;
+    else if constexpr (CODE == NFA_MLP_ACT_SIGMOID) return 1.f / (1.f + expf(-z));
+    else if constexpr (CODE == NFA_MLP_ACT_TANH) return tanhf(z);
+    else if constexpr (CODE == NFA_MLP_ACT_SOFTPLUS) return (z > 0.f ? z : 0.f) + log1pf(expf(-beta * fabsf(z))) / beta;   // NaN: the log term
+    else if constexpr (CODE == NFA_MLP_ACT_EXPONENTIAL) return expf(z);
+    else return z;
+}
+
+// d * f'(y) from the stored y.  ReLU and LeakyReLU select (y = NaN counts as not positive), the others multiply.
+template <int CODE>
+__device__ __forceinline__ float act_times_deriv(float d, float y, float beta)
+{
+    if constexpr (CODE == NFA_MLP_ACT_RELU) return y > 0.f ? d : 0.f;
+    else if constexpr (CODE == NFA_MLP_ACT_LEAKY_RELU) return y > 0.f ? d : 0.01f * d;
+    else if constexpr (CODE == NFA_MLP_ACT_SIGMOID) return d * (y * (1.f - y));
+    else if constexpr (CODE == NFA_MLP_ACT_TANH) return d * (1.f - y * y);
+    else if constexpr (CODE == NFA_MLP_ACT_SOFTPLUS) return d * (1.f - expf(-beta * y));
+    else if constexpr (CODE == NFA_MLP_ACT_EXPONENTIAL) return d * y;
+    else return d;
+}
+
+// rho = f'' / f' from the stored y (only for the codes of act_has_rho)
+template <int CODE>
+__device__ __forceinline__ float act_rho(float y, float beta)
+{
+    if constexpr (CODE == NFA_MLP_ACT_SIGMOID) return 1.f - 2.f * y;
+    else if constexpr (CODE == NFA_MLP_ACT_TANH) return -2.f * y;
+    else if constexpr (CODE == NFA_MLP_ACT_SOFTPLUS) return beta * expf(-beta * y);
+    else if constexpr (CODE == NFA_MLP_ACT_EXPONENTIAL) return 1.f;
+    else return 0.f;
+}
+
+// R = (rho(y) dZ) A, an exact zero where rho is identically zero (never a product with it)
+template <int CODE>
+__device__ __forceinline__ float act_curvature(float a, float y, float dz, float beta)
+{
+    if constexpr (act_has_rho(CODE)) return (act_rho<CODE>(y, beta) * dz) * a;
+    else return 0.f;
+}
+
+// acc = acc * f'(H) (+ inject) for tile t of row p: mask_tile_row for any activation, the pieces store_tile_row wrote
+template <class E, int W, int CODE>
+__device__ __forceinline__ void deriv_tile_row(f32x16 &acc, const uint16_t *m, const uint16_t *inject, int64_t p, int t, int h, float beta)
+{
+    const nfa_v2u *hp = reinterpret_cast<const nfa_v2u *>(m + p * W + 32 * t + 4 * h);
+    const nfa_v2u *ip = reinterpret_cast<const nfa_v2u *>(inject + p * W + 32 * t + 4 * h);
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+        const nfa_v2u hv = hp[2 * gq];
+        nfa_v2u iv = {0u, 0u};
+        if (inject) iv = ip[2 * gq];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float d = act_times_deriv<CODE>(acc[4 * gq + i], unpack_half<E>(hv[i >> 1], i & 1), beta);
+            acc[4 * gq + i] = inject ? d + unpack_half<E>(iv[i >> 1], i & 1) : d;
+        }
+    }
+}
+
+// The tangent's step at a hidden layer: rr = (rho(H) dZ) A (zero without `dz`), then acc = A * f'(H)
+template <class E, int W, int CODE>
+__device__ __forceinline__ void tangent_tile_row(f32x16 &acc, f32x16 &rr, const uint16_t *m, const uint16_t *dz, int64_t p, int t, int h,
+                                                 float beta)
+{
+    const nfa_v2u *hp = reinterpret_cast<const nfa_v2u *>(m + p * W + 32 * t + 4 * h);
+    const nfa_v2u *dp = reinterpret_cast<const nfa_v2u *>(dz + p * W + 32 * t + 4 * h);
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+        const nfa_v2u hv = hp[2 * gq];
+        nfa_v2u dv = {0u, 0u};
+        if (act_has_rho(CODE) && dz) dv = dp[2 * gq];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float y = unpack_half<E>(hv[i >> 1], i & 1), a = acc[4 * gq + i];
+            rr[4 * gq + i] = dz ? act_curvature<CODE>(a, y, unpack_half<E>(dv[i >> 1], i & 1), beta) : 0.f;
+            acc[4 * gq + i] = act_times_deriv<CODE>(a, y, beta);
+        }
+    }
+}
+
+// element `i` of a float32 or E matrix as float32
+template <class E>
+__device__ __forceinline__ float load_elem(const void *base, bool is_f32, int64_t i)
+{
+    return is_f32 ? static_cast<const float *>(base)[i] : half_value<E>(static_cast<const uint16_t *>(base)[i]);
+}
+
+// load_row8 of g * f_out'(y): dZ_L of a network with an output activation, rounded once
+template <class E, int CODE>
+__device__ __forceinline__ nfa_v4u load_row8_deriv(const void *g, bool g_f32, const void *y, bool y_f32, int64_t row, int ld, int k0, float beta)
+{
+    uint32_t b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        b[j] = 0u;
+        if (k0 + j < ld) b[j] = half_bits<E>(act_times_deriv<CODE>(load_elem<E>(g, g_f32, row * ld + k0 + j), load_elem<E>(y, y_f32, row * ld + k0 + j), beta));
+    }
+    nfa_v4u f;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) f[d] = b[2 * d] | (b[2 * d + 1] << 16);
+    return f;
+}
+
+// The tangent's step at the output layer, on the accumulator tile o = A_L (rows = outputs): ro = (rho(y) dZ_L) A_L, o = f_out'(y) A_L
+template <class E, int CODE>
+__device__ __forceinline__ void tangent_out_tile(f32x16 &o, f32x16 &ro, const ActOps &A, int64_t p, int n_out, int h)
+{
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int row = acc_row(reg, h);
+        float y = 0.f, d = 0.f;
+        if (CODE != NFA_MLP_ACT_NONE && row < n_out) y = load_elem<E>(A.y, A.y_f32 != 0, p * n_out + row);
+        if (act_has_rho(CODE) && A.r_out && row < n_out) d = load_elem<E>(A.dz_out, false, p * n_out + row);
+        const float a = o[reg];
+        ro[reg] = A.r_out ? act_curvature<CODE>(a, y, d, A.beta) : 0.f;
+        o[reg] = act_times_deriv<CODE>(a, y, A.beta);
+    }
+}
+
 // An accumulator tile's start: rows 32m .. 32m+31 of a layer's float32 bias (lb: that tile's 32 floats in LDS), or zero.
 __device__ __forceinline__ void init_acc(f32x16 &a, bool has_bias, const float *lb, int h)
 {

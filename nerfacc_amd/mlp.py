@@ -82,29 +82,116 @@ def _cat_input(h: Tensor, x0: Tensor, l: int, skip_mask: int) -> Tensor:
     return torch.cat([h, x0], dim=1) if (skip_mask >> l) & 1 else h
 
 
+ACTIVATIONS = ("None", "ReLU", "LeakyReLU", "Sigmoid", "Tanh", "Softplus", "Exponential")   # tiny-cuda-nn's names; B.ACT_CODES
+UNSUPPORTED_ACTIVATIONS = ("Sine", "Squareplus")   # tcnn's other two: Sine's derivative needs the pre-activation, which no pass stores
+CURVED_ACTIVATIONS = ("Sigmoid", "Tanh", "Softplus", "Exponential")   # rho = f'' / f' is not identically zero
+LEAKY_SLOPE = 0.009999999776482582   # 0.01f
+DEFAULT_ACT = ("ReLU", "None", 10.0)
+
+
+def check_activation(who: str, what: str, name) -> str:
+    if name is None:
+        name = "None"
+    if name in UNSUPPORTED_ACTIVATIONS:
+        raise ValueError(f"{who}: {what} {name!r} is not supported ({' and '.join(UNSUPPORTED_ACTIVATIONS)} stay refused: Sine's derivative "
+                         f"needs the pre-activation, which no pass stores); one of {', '.join(ACTIVATIONS)}")
+    if name not in ACTIVATIONS:
+        raise ValueError(f"{who}: {what} {name!r}: one of {', '.join(ACTIVATIONS)}")
+    return name
+
+
+def _act(name: str, z: Tensor, beta: float) -> Tensor:
+    """``f(z)`` in ``z``'s own precision (float32 where the kernels are restated), unrounded."""
+    if name == "ReLU":
+        return torch.relu(z)
+    if name == "LeakyReLU":
+        return torch.where(z > 0, z, z * LEAKY_SLOPE)
+    if name == "Sigmoid":
+        return 1.0 / (1.0 + torch.exp(-z))
+    if name == "Tanh":
+        return torch.tanh(z)
+    if name == "Softplus":
+        return torch.where(z > 0, z, torch.zeros_like(z)) + torch.log1p(torch.exp(-beta * z.abs())) / beta
+    if name == "Exponential":
+        return torch.exp(z)
+    return z
+
+
+def _times_deriv(name: str, d: Tensor, y: Tensor, beta: float) -> Tensor:
+    """``d * f'(y)`` with ``f'`` formed from the stored ``y``; ReLU and LeakyReLU select."""
+    if name == "ReLU":
+        return torch.where(y > 0, d, torch.zeros_like(d))
+    if name == "LeakyReLU":
+        return torch.where(y > 0, d, d * LEAKY_SLOPE)
+    if name == "Sigmoid":
+        return d * (y * (1.0 - y))
+    if name == "Tanh":
+        return d * (1.0 - y * y)
+    if name == "Softplus":
+        return d * (1.0 - torch.exp(-beta * y))
+    if name == "Exponential":
+        return d * y
+    return d
+
+
+def _curvature_term(name: str, a: Tensor, y: Tensor, dz: Tensor, beta: float) -> Tensor:
+    """``R = (rho(y) dZ) A``, an exact zero where ``rho`` is identically zero."""
+    if name == "Sigmoid":
+        rho = 1.0 - 2.0 * y
+    elif name == "Tanh":
+        rho = -2.0 * y
+    elif name == "Softplus":
+        rho = beta * torch.exp(-beta * y)
+    elif name == "Exponential":
+        rho = torch.ones_like(y)
+    else:
+        return torch.zeros_like(a)
+    return (rho * dz) * a
+
+
+def _rnd(t: Tensor, dtype: torch.dtype) -> Tensor:
+    """``t`` rounded once to ``dtype`` and widened to float32 again.  ``dtype=torch.float64`` is the unrounded form of the
+    restatements: nothing rounds and every sum is float64 (what the tests compare with ``torch.autograd``)."""
+    return t.double() if dtype == torch.float64 else t.to(dtype).float()
+
+
+def _wide(t: Tensor, dtype: torch.dtype) -> Tensor:
+    return t.double() if dtype == torch.float64 else t.float()
+
+
 def _forward_torch(x: Tensor, weights: Sequence[Tensor], dtype: torch.dtype, out_f32: bool, biases: Optional[Sequence[Tensor]] = None,
-                   skip_mask: int = 0):
+                   skip_mask: int = 0, act: tuple = DEFAULT_ACT):
     """(y, hidden): float32 sums of exact products, rounded where the kernels round (x, W, every hidden activation, y).  A
-    bias is added in float32 and never rounded; a cat layer takes ``cat([h, x rounded])``."""
-    x0 = x.to(dtype).float()
+    bias is added in float32 and never rounded; a cat layer takes ``cat([h, x rounded])``.  ``act``: (hidden activation,
+    output activation, beta); the activation is evaluated in float32 and rounded once."""
+    hid, out, beta = act
+    x0 = _rnd(x, dtype)
     h, hidden = x0, []
     for l, w in enumerate(weights):
-        z = _cat_input(h, x0, l, skip_mask) @ w.to(dtype).float().t()
+        z = _cat_input(h, x0, l, skip_mask) @ _rnd(w, dtype).t()
         if biases is not None:
-            z = z + biases[l].float()
+            z = z + _wide(biases[l], dtype)
         if l < len(weights) - 1:
-            h = torch.relu(z).to(dtype).float()
+            h = _rnd(_act(hid, z, beta), dtype)
             hidden.append(h)
+    z = _act(out, z, beta)
     return (z if out_f32 else z.to(dtype)), hidden
 
 
 def _backward_torch(x: Tensor, weights: Sequence[Tensor], hidden: Sequence[Tensor], g: Tensor, dtype: torch.dtype,
-                    need_x: bool, need_p: bool, bias: bool = False, skip_mask: int = 0):
-    """(dL/dx in x's dtype, dL/dparams flat float32: matrices, then biases, [dZ_l]) with dZ_l rounded as the kernels round it.
-    dL/dx is the float32 sum of layer 0's product and the skip columns' products of every cat layer, rounded once."""
-    x0 = x.to(dtype).float()
+                    need_x: bool, need_p: bool, bias: bool = False, skip_mask: int = 0, act: tuple = DEFAULT_ACT,
+                    y: Optional[Tensor] = None, inject: Optional[Sequence[Tensor]] = None):
+    """(dL/dx in x's dtype, dL/dparams flat float32: matrices, then biases, [dZ_l]) with dZ_l rounded as the kernels round it:
+    ``dZ_L = rnd(g * f_out'(y))``, ``dZ_l = rnd(dH_l * f'(H_l))``.  dL/dx is the float32 sum of layer 0's product and the skip
+    columns' products of every cat layer, rounded once.  With ``inject`` (the tangent's ``[R_0 .. R_{L-1}]``; ``g`` is then
+    ``R_L`` and takes no output derivative) this is the curvature pass: ``E_l = rnd(dH_l * f'(H_l) + R_l)``."""
+    hid, out, beta = act
+    x0 = _rnd(x, dtype)
     W = weights[0].shape[0]
-    dz = g.to(dtype).float()
+    if out == "None" or inject is not None:
+        dz = _rnd(g, dtype)
+    else:
+        dz = _rnd(_times_deriv(out, _wide(g, dtype), _wide(y, dtype), beta), dtype)
     dzs, g_w, g_b = [dz], [], []
     g_x, skips = None, []
     for l in range(len(weights) - 1, -1, -1):
@@ -114,12 +201,15 @@ def _backward_torch(x: Tensor, weights: Sequence[Tensor], hidden: Sequence[Tenso
             g_b.append(dz.sum(0))
         if l == 0 and not need_x:
             break
-        dh = dz @ weights[l].to(dtype).float()
+        dh = dz @ _rnd(weights[l], dtype)
         if l > 0:
             if (skip_mask >> l) & 1:
                 skips.append(dh[:, W:])
                 dh = dh[:, :W]
-            dz = torch.where(h_prev > 0, dh, torch.zeros_like(dh)).to(dtype).float()   # a select
+            dz = _times_deriv(hid, dh, h_prev, beta)   # ReLU: a select
+            if inject is not None:
+                dz = dz + inject[l - 1]
+            dz = _rnd(dz, dtype)
             dzs.append(dz)
         else:
             for s in reversed(skips):   # ascending layers, as the kernel adds them
@@ -130,24 +220,45 @@ def _backward_torch(x: Tensor, weights: Sequence[Tensor], hidden: Sequence[Tenso
 
 
 def _tangent_torch(v: Tensor, weights: Sequence[Tensor], hidden: Sequence[Tensor], dzs: Sequence[Tensor], dtype: torch.dtype,
-                   need_p: bool, bias: bool = False, skip_mask: int = 0):
-    """The second order: (u float32 unrounded, ds/dparams flat float32, [T_{-1}, T_0 .. T_{L-1}]) for the cotangent ``v`` of
-    dL/dx.  The derivative of the network along ``v`` with the SAVED masks (``hidden`` > 0, never a ReLU of the tangent),
-    every ``T_l`` rounded after its mask as the tangent kernel rounds it; ``ds/dW_l = dZ_l^T T_{l-1}`` with the first
-    backward's ``dZ_l``.  A bias has no tangent and ``ds/db`` is zero (the bias segment of the flat gradient); a cat layer
-    sees ``[T_{l-1}, v]``."""
-    t0 = v.to(dtype).float()
-    t, ts = t0, [t0]
+                   need_p: bool, bias: bool = False, skip_mask: int = 0, act: tuple = DEFAULT_ACT, y: Optional[Tensor] = None):
+    """:func:`_tangent_terms` without the curvature cotangents: (u, ds/dparams, [T_l])."""
+    return _tangent_terms(v, weights, hidden, dzs, dtype, need_p, bias, skip_mask, act, y)[:3]
+
+
+def _tangent_terms(v: Tensor, weights: Sequence[Tensor], hidden: Sequence[Tensor], dzs: Sequence[Tensor], dtype: torch.dtype,
+                   need_p: bool, bias: bool = False, skip_mask: int = 0, act: tuple = DEFAULT_ACT, y: Optional[Tensor] = None):
+    """The second order: (u float32 unrounded, ds/dparams flat float32, [T_{-1}, T_0 .. T_{L-1}], [R_0 .. R_L]) for the cotangent
+    ``v`` of dL/dx.  The derivative of the network along ``v`` with the SAVED activations (``f'`` from ``hidden``, never an
+    activation of the tangent): ``T_l = rnd(A_l * f'(H_l))``, ``u = f_out'(y) * A_L``; ``ds/dW_l = dZ_l^T T_{l-1}`` with the
+    first backward's ``dZ_l`` is the part of the parameter gradient returned here, whose bias segment is zero; a cat layer sees
+    ``[T_{l-1}, v]``.  ``R_l = rnd((rho(H_l) dZ_l) A_l)`` are the cotangents the curvature pass injects (zeros where ``rho`` is)."""
+    hid, out, beta = act
+    t0 = _rnd(v, dtype)
+    t, ts, rs = t0, [t0], []
     for l, w in enumerate(weights):
-        z = _cat_input(t, t0, l, skip_mask) @ w.to(dtype).float().t()
+        z = _cat_input(t, t0, l, skip_mask) @ _rnd(w, dtype).t()
         if l < len(weights) - 1:
-            t = torch.where(hidden[l] > 0, z, torch.zeros_like(z)).to(dtype).float()
+            rs.append(_rnd(_curvature_term(hid, z, hidden[l], dzs[l], beta), dtype))
+            t = _rnd(_times_deriv(hid, z, hidden[l], beta), dtype)
             ts.append(t)
+    if out != "None":
+        rs.append(_rnd(_curvature_term(out, z, _wide(y, dtype), dzs[-1], beta), dtype))
+        z = _times_deriv(out, z, _wide(y, dtype), beta)
+    else:
+        rs.append(torch.zeros_like(z))
     g_p = None
     if need_p:
         g_p = torch.cat([(dz.t() @ _cat_input(t, t0, l, skip_mask)).reshape(-1) for l, (dz, t) in enumerate(zip(dzs, ts))] +
                         ([torch.zeros(sum(w.shape[0] for w in weights))] if bias else []))
-    return z, g_p, ts
+    return z, g_p, ts, rs
+
+
+def _curvature_torch(x: Tensor, weights: Sequence[Tensor], hidden: Sequence[Tensor], rs: Sequence[Tensor], dtype: torch.dtype,
+                     need_x: bool, need_p: bool, bias: bool = False, skip_mask: int = 0, act: tuple = DEFAULT_ACT):
+    """The curvature pass: (ds/dx in x's dtype, the second part of ds/dparams: ``E_l^T [H_{l-1}(, x)]`` and ``sum_p E_l[p]``,
+    [E_0 .. E_L]) with ``E_L = R_L``, ``E_{l-1} = rnd((W_l^T E_l)[:W] * f'(H_{l-1}) + R_{l-1})``: the data gradient's chain
+    and the weight gradient on ``(x, H, E)``."""
+    return _backward_torch(x, weights, hidden, rs[-1], dtype, need_x, need_p, bias, skip_mask, act, None, inject=rs[:-1])
 
 
 # ---------------------------------------------------------------- autograd
@@ -163,8 +274,8 @@ class _MLPFn(torch.autograd.Function):
             ctx.save_for_backward(x, params)
             return torch.empty(0, mlp.n_output_dims, dtype=mlp.out_dtype, device=x.device)
         if not x.is_cuda:
-            y, hidden = _forward_torch(x, mlp._views(params), mlp.dtype, out_f32, mlp._bias_views(params), mlp.skip_mask)
-            ctx.save_for_backward(x, params, *hidden)
+            y, hidden = _forward_torch(x, mlp._views(params), mlp.dtype, out_f32, mlp._bias_views(params), mlp.skip_mask, mlp._act_names)
+            ctx.save_for_backward(x, params, *hidden, *([y] if mlp._out_act else []))
             return y
         B.require_device(x, params)
         elem = B.ELEM_CODES[mlp.dtype]
@@ -175,11 +286,14 @@ class _MLPFn(torch.autograd.Function):
             if mlp._plain:
                 B.call("nfa_mlp_fwd", elem, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(fwd_img), N, *mlp._shape, B.ptr(y),
                        B.ELEM_CODES[y.dtype], B.ptr(hidden), int(need_grad), B.stream())
+            elif mlp._act is not None:
+                B.call("nfa_mlp_act_fwd", elem, mlp._desc, mlp._act, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(fwd_img),
+                       mlp._bias_ptr(params), N, B.ptr(y), B.ELEM_CODES[y.dtype], B.ptr(hidden), int(need_grad), B.stream())
             else:
                 B.call(mlp._entry("fwd"), elem, mlp._desc, B.ptr(x), B.ELEM_CODES[x.dtype], B.ptr(fwd_img), mlp._bias_ptr(params), N,
                        B.ptr(y), B.ELEM_CODES[y.dtype], B.ptr(hidden), int(need_grad), B.stream())
         if need_grad:   # the second order runs the chain again on the forward image
-            ctx.save_for_backward(x, params, hidden, bwd_img, *([fwd_img] if mlp.second_order else []))
+            ctx.save_for_backward(x, params, hidden, bwd_img, *([fwd_img] if mlp.second_order else []), *([y] if mlp._out_act else []))
         return y
 
     @staticmethod
@@ -188,7 +302,9 @@ class _MLPFn(torch.autograd.Function):
         if g_y is None or not (need_x or need_p):
             return None, None, None
         x, params, *saved = ctx.saved_tensors
-        g_x, g_p = _MLPBwdFn.apply(x, params, g_y, ctx.mlp, need_x, need_p, *saved)
+        # y (saved for an output activation) is this function's own output: detached, or the second backward would come back
+        # through here with a zero cotangent.  What dL/dx owes to y is in the second order's own formulas (R_L).
+        g_x, g_p = _MLPBwdFn.apply(x, params, g_y, ctx.mlp, need_x, need_p, *[t.detach() for t in saved])
         return g_x, g_p, None
 
 
@@ -196,11 +312,14 @@ class _MLPBwdFn(torch.autograd.Function):
     """The backward as a function ``(x, params, g_y) -> (g_x, g_params)`` of its own, so that differentiating it again
     (``create_graph=True``) fails with a message that names the module instead of a missing ``grad_fn``, or, for a module
     with ``second_order=True``, runs the tangent pass: with ``v`` the cotangent of ``g_x`` and ``s = <v, g_x>``,
-    ``T_{-1} = v``, ``T_l = M_l * (W_l T_{l-1})``, ``ds/dg_y = W_L T_{L-1}``, ``ds/dW_l = dZ_l^T T_{l-1}``, ``ds/dx = 0``."""
+    ``T_{-1} = v``, ``T_l = M_l * (W_l T_{l-1})``, ``ds/dg_y = W_L T_{L-1}``, ``ds/dW_l = dZ_l^T T_{l-1}``, ``ds/dx = 0``.  With an
+    activation that has curvature the tangent pass also writes ``R_l``, the curvature pass turns them into ``E_l`` and ``ds/dx``,
+    and ``ds/dparams`` gains the weight gradient on ``(x, H, E)``: the two float32 results are added with one torch add."""
 
     @staticmethod
     def forward(ctx, x: Tensor, params: Tensor, g: Tensor, mlp: "FusedMLP", need_x: bool, need_p: bool, *saved):
         ctx.set_materialize_grads(False)
+        saved = list(saved)
         ctx.mlp, ctx.g_dtype, ctx.g_shape, ctx.n_saved = mlp, g.dtype, g.shape, len(saved)
         N = x.shape[0]
         if N == 0:
@@ -209,22 +328,28 @@ class _MLPBwdFn(torch.autograd.Function):
             g = g.float()
         g = g.contiguous()
         if not x.is_cuda:
+            hidden_cpu, y = (saved[:-1], saved[-1]) if mlp._out_act else (saved, None)
             with torch.autocast("cpu", enabled=False):   # a backward called under autocast must not round the float32 sums
-                g_x, g_p, dzs = _backward_torch(x, mlp._views(params), saved, g, mlp.dtype, need_x, need_p, mlp.bias_enabled,
-                                                mlp.skip_mask)
+                g_x, g_p, dzs = _backward_torch(x, mlp._views(params), hidden_cpu, g, mlp.dtype, need_x, need_p, mlp.bias_enabled,
+                                                mlp.skip_mask, mlp._act_names, y)
             if mlp.second_order:   # retained only under create_graph=True: a plain backward runs this in no-grad mode
-                ctx.save_for_backward(params, *saved, *dzs)
+                ctx.save_for_backward(params, *hidden_cpu, *dzs, *([x] if mlp._act is not None else []), *([y] if mlp._out_act else []))
             return g_x, g_p
+        y = saved.pop() if mlp._out_act else None
         hidden, bwd_img, *fwd_img = saved
         elem, dev = B.ELEM_CODES[mlp.dtype], x.device
         dz = torch.empty(mlp.n_hidden_layers, N, mlp.n_neurons, dtype=mlp.dtype, device=dev)
-        dz_out = g if g.dtype == mlp.dtype else torch.empty(N, mlp.n_output_dims, dtype=mlp.dtype, device=dev)
+        dz_out = g if g.dtype == mlp.dtype and not mlp._out_act else torch.empty(N, mlp.n_output_dims, dtype=mlp.dtype, device=dev)
         g_x = torch.empty_like(x) if need_x else None
         g_p = None
         with torch.cuda.device(dev):
             if mlp._plain:
                 B.call("nfa_mlp_bwd_data", elem, B.ptr(g), B.ELEM_CODES[g.dtype], B.ptr(hidden), B.ptr(bwd_img), N, *mlp._shape,
                        B.ptr(dz), None if dz_out is g else B.ptr(dz_out), B.ptr(g_x), B.ELEM_CODES[x.dtype], B.stream())
+            elif mlp._act is not None:
+                B.call("nfa_mlp_act_bwd_data", elem, mlp._desc, mlp._act, B.ptr(g), B.ELEM_CODES[g.dtype], B.ptr(y),
+                       B.ELEM_CODES[mlp.out_dtype], B.ptr(hidden), B.ptr(bwd_img), N, B.ptr(dz), None if dz_out is g else B.ptr(dz_out),
+                       B.ptr(g_x), B.ELEM_CODES[x.dtype], B.stream())
             else:
                 B.call(mlp._entry("bwd_data"), elem, mlp._desc, B.ptr(g), B.ELEM_CODES[g.dtype], B.ptr(hidden), B.ptr(bwd_img), N,
                        B.ptr(dz), None if dz_out is g else B.ptr(dz_out), B.ptr(g_x), B.ELEM_CODES[x.dtype], B.stream())
@@ -234,7 +359,7 @@ class _MLPBwdFn(torch.autograd.Function):
                 g_p = torch.empty(P, dtype=torch.float32, device=dev)
                 mlp._weight_gradient(elem, x, hidden, dz, dz_out, N, partials, g_p, zero_bias=False)
         if mlp.second_order:   # retained only under create_graph=True: a plain backward runs this in no-grad mode
-            ctx.save_for_backward(hidden, dz, dz_out, *fwd_img)
+            ctx.save_for_backward(hidden, dz, dz_out, *fwd_img, *([x, bwd_img] if mlp._act is not None else []), *([y] if mlp._out_act else []))
         return g_x, g_p
 
     @staticmethod
@@ -252,22 +377,35 @@ class _MLPBwdFn(torch.autograd.Function):
             raise NotImplementedError("FusedMLP: the second order of dL/dparams (a cotangent for dL/dparams) is not implemented, "
                                       "only that of dL/dx")
         need_p, need_g = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        need_x = ctx.needs_input_grad[0] and mlp._curved   # ds/dx is zero (None) when no activation has curvature
         none = (None,) * (6 + ctx.n_saved)
-        if gg_x is None or not (need_p or need_g):
+        if gg_x is None or not (need_p or need_g or need_x):
             return none
         N, P = gg_x.shape[0], mlp._bias_offsets[-1]   # all parameters: matrices, then biases
         v = gg_x.contiguous()
         u_dtype = ctx.g_dtype if ctx.g_dtype in (torch.float32, mlp.dtype) else torch.float32
         if N == 0:
             u = torch.empty(ctx.g_shape, dtype=ctx.g_dtype, device=v.device) if need_g else None
-            return (None, torch.zeros(P, dtype=torch.float32, device=v.device) if need_p else None, u) + none[3:]
+            return (torch.zeros_like(v) if need_x else None, torch.zeros(P, dtype=torch.float32, device=v.device) if need_p else None,
+                    u) + none[3:]
         L = mlp.n_hidden_layers
         if not v.is_cuda:
             params, *saved = ctx.saved_tensors
+            y = saved.pop() if mlp._out_act else None
+            x = saved.pop() if mlp._act is not None else None
             hidden, dzs = saved[:L], saved[L:]
+            s_x = None
             with torch.autocast("cpu", enabled=False):
-                u, g_p, _ = _tangent_torch(v, mlp._views(params), hidden, dzs, mlp.dtype, need_p, mlp.bias_enabled, mlp.skip_mask)
-            return (None, g_p, u.to(ctx.g_dtype) if need_g else None) + none[3:]
+                ws = mlp._views(params)
+                u, g_p, _, rs = _tangent_terms(v, ws, hidden, dzs, mlp.dtype, need_p, mlp.bias_enabled, mlp.skip_mask, mlp._act_names, y)
+                if mlp._curved and (need_p or need_x):
+                    s_x, g_p2, _ = _curvature_torch(x, ws, hidden, rs, mlp.dtype, need_x, need_p, mlp.bias_enabled, mlp.skip_mask,
+                                                    mlp._act_names)
+                    if need_p:
+                        g_p = g_p + g_p2
+            return (s_x, g_p, u.to(ctx.g_dtype) if need_g else None) + none[3:]
+        if mlp._act is not None:
+            return _MLPBwdFn._backward_act(ctx, v, u_dtype, need_x, need_p, need_g) + none[3:]
         hidden, dz, dz_out, fwd_img = ctx.saved_tensors
         elem, dev = B.ELEM_CODES[mlp.dtype], v.device
         tangent = torch.empty(L, N, mlp.n_neurons, dtype=mlp.dtype, device=dev) if need_p else None
@@ -286,10 +424,46 @@ class _MLPBwdFn(torch.autograd.Function):
                 mlp._weight_gradient(elem, v, tangent, dz, dz_out, N, partials, g_p, zero_bias=True)
         return (None, g_p, (u if u.dtype == ctx.g_dtype else u.to(ctx.g_dtype)) if need_g else None) + none[3:]
 
+    @staticmethod
+    def _backward_act(ctx, v: Tensor, u_dtype: torch.dtype, need_x: bool, need_p: bool, need_g: bool):
+        """The second order of a module with activations on the device: the tangent pass (which also writes ``R_l``), the
+        curvature pass and the weight gradient pass twice.  Returns (ds/dx, ds/dparams, ds/dg)."""
+        mlp = ctx.mlp
+        saved = list(ctx.saved_tensors)
+        y = saved.pop() if mlp._out_act else None
+        hidden, dz, dz_out, fwd_img, x, bwd_img = saved
+        N, P, L = v.shape[0], mlp._bias_offsets[-1], mlp.n_hidden_layers
+        elem, dev = B.ELEM_CODES[mlp.dtype], v.device
+        curved = mlp._curved and (need_p or need_x)
+        half = lambda *shape: torch.empty(*shape, dtype=mlp.dtype, device=dev)
+        tangent = half(L, N, mlp.n_neurons) if need_p else None
+        r, r_out = (half(L, N, mlp.n_neurons), half(N, mlp.n_output_dims)) if curved else (None, None)
+        u = torch.empty(N, mlp.n_output_dims, dtype=u_dtype, device=dev)
+        s_x = g_p = None
+        with torch.cuda.device(dev):
+            B.call("nfa_mlp_act_tangent", elem, mlp._desc, mlp._act, B.ptr(v), B.ELEM_CODES[v.dtype], B.ptr(y), B.ELEM_CODES[mlp.out_dtype],
+                   B.ptr(hidden), B.ptr(dz), B.ptr(dz_out), B.ptr(fwd_img), N, B.ptr(tangent), B.ptr(r), B.ptr(r_out), B.ptr(u),
+                   B.ELEM_CODES[u_dtype], B.stream())
+            if curved:
+                e = half(L, N, mlp.n_neurons)
+                s_x = torch.empty_like(x) if need_x else None
+                B.call("nfa_mlp_act_curvature", elem, mlp._desc, mlp._act, B.ptr(r_out), B.ptr(hidden), B.ptr(r), B.ptr(bwd_img), N,
+                       B.ptr(e), B.ptr(s_x), B.ELEM_CODES[x.dtype], B.stream())
+            if need_p:
+                partials = torch.empty(wgrad_slices(N) * P, dtype=torch.float32, device=dev)
+                g_p = torch.empty(P, dtype=torch.float32, device=dev)
+                mlp._weight_gradient(elem, v, tangent, dz, dz_out, N, partials, g_p, zero_bias=True)
+                if curved:   # + E_l^T [H_{l-1}(, x)] and sum_p E_l: the same pass on (x, H, E); one torch add of two P-vectors
+                    g_p2 = torch.empty(P, dtype=torch.float32, device=dev)
+                    mlp._weight_gradient(elem, x, hidden, e, r_out, N, partials, g_p2, zero_bias=False)
+                    g_p = g_p + g_p2
+        return s_x, g_p, (u if u.dtype == ctx.g_dtype else u.to(ctx.g_dtype)) if need_g else None
+
 
 class FusedMLP(nn.Module):
-    """tiny-cuda-nn's ``FullyFusedMLP``: ``n_hidden_layers + 1`` weight matrices, no biases, ReLU on the hidden layers and
-    no output activation, as one native launch forward and three backward (and, on request, three for the second order).
+    """tiny-cuda-nn's ``FullyFusedMLP``: ``n_hidden_layers + 1`` weight matrices, by default no biases, ReLU on the hidden
+    layers and no output activation, as one native launch forward and three backward (and, on request, three for the second
+    order, six with an activation that has curvature).
 
     ``n_neurons`` 64 or 128, ``n_hidden_layers`` 1..4, ``n_input_dims`` 1..256, ``n_output_dims`` 1..32; a configuration
     whose packed weights do not fit the 160 KiB of LDS of a compute unit is refused here, with the sizes in the message.
@@ -306,11 +480,13 @@ class FusedMLP(nn.Module):
     restatement with the same rounding points.
 
     ``second_order=True`` makes ``dL/dx`` differentiable once more (``create_graph=True``: an Eikonal term on an SDF field's
-    normals): one more fused launch, the tangent pass, and the weight gradient passes again.  For a ReLU network this is
-    exact: ``dL/dx`` is linear in ``dL/dy`` and in each matrix and its masks are piecewise constant, so the gradient of
-    ``<v, dL/dx>`` towards ``x`` is zero (``None``), towards ``dL/dy`` it is the network's derivative along ``v`` and towards
-    the masters a weight gradient with the tangent activations in the place of the activations; float32, without atomics,
-    the same bits on every run.  It costs memory only under ``create_graph=True``, where the graph keeps the ``dZ_l`` alive.
+    normals): one more fused launch, the tangent pass, and the weight gradient passes again.  For a network whose activations
+    are piecewise linear (``None``, ``ReLU``, ``LeakyReLU``) this is exact: ``dL/dx`` is linear in ``dL/dy`` and in each matrix
+    and its derivative factors are piecewise constant, so the gradient of ``<v, dL/dx>`` towards ``x`` is zero (``None``),
+    towards ``dL/dy`` it is the network's derivative along ``v`` and towards the masters a weight gradient with the tangent
+    activations in the place of the activations; float32, without atomics, the same bits on every run.  With an activation that
+    has curvature (below) it is exact too, by one more fused launch, the curvature pass: the gradient towards ``x`` is then a
+    tensor of ``x``'s dtype, which an encoding's own second order receives through autograd.  It costs memory only under ``create_graph=True``, where the graph keeps the ``dZ_l`` alive.
     The derivative of ``dL/dparams`` and a third order raise.  Without it (the default) differentiating the gradients again
     raises ``NotImplementedError``.
 
@@ -328,13 +504,32 @@ class FusedMLP(nn.Module):
     layer), and the LDS budget counts the longer images and, for the forward pass, ``(n_hidden_layers n_neurons + 32) * 4``
     bytes of biases.  :func:`reference_mlp` builds the module from the reference's argument names and
     :meth:`load_reference_state_dict` takes its state dict.
+
+    ``activation`` (all hidden layers) and ``output_activation``: tiny-cuda-nn's ``None``, ``ReLU``, ``LeakyReLU`` (slope
+    0.01), ``Sigmoid``, ``Tanh``, ``Softplus`` (``max(z, 0) + log1p(exp(-beta |z|)) / beta`` with ``beta = activation_beta``:
+    10 is tiny-cuda-nn's constant, NeuS' SDF network uses 100) and ``Exponential``, in the same launches (the ``nfa_mlp_act_*``
+    entries; the default pair calls the entries it always called).  ``Sine`` and ``Squareplus`` raise ``ValueError``.  The
+    activation is evaluated in float32 and rounded once to ``dtype``; every derivative is formed from the stored, rounded
+    activation (Sigmoid ``y (1 - y)``, Tanh ``1 - y^2``, Softplus ``1 - exp(-beta y)``, Exponential ``y``), as tiny-cuda-nn's
+    fused network forms it, so the forward hands ``y`` to the backward when there is an output activation.  With
+    ``second_order=True`` and Sigmoid, Tanh, Softplus or Exponential anywhere, the tangent pass also writes the cotangents
+    ``R_l = (f''/f')(H_l) dZ_l A_l`` that the activation's second derivative puts into every layer, the curvature pass (the data
+    gradient's chain with ``R_l`` injected) turns them into ``E_l`` and the gradient of ``<v, dL/dx>`` towards ``x``, and the
+    gradient towards the masters is the weight gradient pass run twice, on ``(v, T, dZ)`` and on ``(x, H, E)``: the two float32
+    results are added with one torch add of two ``P``-vectors, the only torch pass; the bias segment is then ``sum_p E_l[p]``,
+    no longer zero.
     """
 
     def __init__(self, n_input_dims: int, n_output_dims: int, n_neurons: int = 64, n_hidden_layers: int = 2,
                  dtype: torch.dtype = torch.float16, out_dtype: Optional[torch.dtype] = None,
                  generator: Optional[torch.Generator] = None, second_order: bool = False, bias: bool = False,
-                 skip_layer: Optional[int] = None):
+                 skip_layer: Optional[int] = None, activation: str = "ReLU", output_activation: str = "None",
+                 activation_beta: float = 10.0):
         super().__init__()
+        activation = check_activation("FusedMLP", "activation", activation)
+        output_activation = check_activation("FusedMLP", "output_activation", output_activation)
+        if not (isinstance(activation_beta, (int, float)) and activation_beta > 0 and math.isfinite(activation_beta)):
+            raise ValueError(f"FusedMLP: activation_beta {activation_beta!r}: a positive number (Softplus' beta)")
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError(f"FusedMLP: dtype {dtype}: torch.float16 or torch.bfloat16")
         if out_dtype not in (None, dtype, torch.float32):
@@ -363,7 +558,7 @@ class FusedMLP(nn.Module):
                              f"n_hidden_layers {n_hidden_layers}" + (f", bias {bool(bias)}, skip_layer {skip_layer}" if bias or skip_mask else "")
                              + ")")
         self._setup(n_input_dims, n_output_dims, n_neurons, n_hidden_layers, dtype, out_dtype, generator, second_order, bias,
-                    skip_layer, skip_mask, (fwd, bwd))
+                    skip_layer, skip_mask, (fwd, bwd), (activation, output_activation, float(activation_beta)))
 
     _NAME = "FusedMLP"
 
@@ -374,9 +569,13 @@ class FusedMLP(nn.Module):
     _slices = staticmethod(wgrad_slices)
 
     def _setup(self, n_input_dims, n_output_dims, n_neurons, n_hidden_layers, dtype, out_dtype, generator, second_order, bias,
-               skip_layer, skip_mask, image_elems_) -> None:
+               skip_layer, skip_mask, image_elems_, act: tuple = DEFAULT_ACT) -> None:
         """The module's state and its initial parameters, once the constructor has accepted the configuration."""
         fwd, bwd = image_elems_
+        self.activation, self.output_activation, self.activation_beta = act
+        self._act_names = act
+        self._out_act = act[1] != "None"                                   # the backward needs y
+        self._curved = act[0] in CURVED_ACTIVATIONS or act[1] in CURVED_ACTIVATIONS   # the second order has a curvature pass
         self.n_input_dims, self.n_output_dims = n_input_dims, n_output_dims
         self.n_neurons, self.n_hidden_layers = n_neurons, n_hidden_layers
         self.dtype, self.out_dtype = dtype, out_dtype or dtype
@@ -429,7 +628,18 @@ class FusedMLP(nn.Module):
     def _plain(self) -> bool:
         """No bias and no skip: the network of the ``nfa_mlp_*`` entries, which such a module keeps calling (the
         ``nfa_mlp_net_*`` entries with ``bias = 0, skip_mask = 0`` are the same passes)."""
-        return not self.bias_enabled and self.skip_mask == 0
+        return not self.bias_enabled and self.skip_mask == 0 and self._act is None
+
+    @property
+    def _act(self) -> Optional["B.MLPAct"]:
+        """struct nfa_mlp_act of this network, or None for the default pair (ReLU, None), whose module calls the entries
+        without activations."""
+        if self._act_names[:2] == DEFAULT_ACT[:2]:
+            return None
+        a = self.__dict__.get("_act_cache")
+        if a is None:
+            a = self.__dict__["_act_cache"] = B.MLPAct(B.ACT_CODES[self.activation], B.ACT_CODES[self.output_activation], self.activation_beta)
+        return a
 
     def _weight_gradient(self, elem, x, hidden, dz, dz_out, N, partials, g_p, zero_bias: bool) -> None:
         """dW (and db) on ``(x, hidden)``, or the second order's on ``(v, tangent)``, whose bias segment is zero."""
@@ -515,7 +725,9 @@ class FusedMLP(nn.Module):
     def extra_repr(self) -> str:
         return (f"{self.n_input_dims} -> {' -> '.join([str(self.n_neurons)] * self.n_hidden_layers)} -> {self.n_output_dims}, "
                 f"dtype={self.dtype}, out_dtype={self.out_dtype}" + (", second_order=True" if self.second_order else "")
-                + (", bias=True" if self.bias_enabled else "") + (f", skip_layer={self.skip_layer}" if self.skip_layer is not None else ""))
+                + (", bias=True" if self.bias_enabled else "") + (f", skip_layer={self.skip_layer}" if self.skip_layer is not None else "")
+                + (f", activation={self.activation}, output_activation={self.output_activation}"
+                   + (f", activation_beta={self.activation_beta:g}" if "Softplus" in self._act_names[:2] else "") if self._act is not None else ""))
 
 
 _TCNN_KEYS = ("otype", "activation", "output_activation", "n_neurons", "n_hidden_layers")
@@ -523,24 +735,31 @@ _TCNN_KEYS = ("otype", "activation", "output_activation", "n_neurons", "n_hidden
 
 def mlp_from_tcnn_config(n_input_dims: int, n_output_dims: int, config: dict, dtype: torch.dtype = torch.float16,
                          out_dtype: Optional[torch.dtype] = None, generator: Optional[torch.Generator] = None,
-                         second_order: bool = False) -> FusedMLP:
+                         second_order: bool = False, activations: bool = False, activation_beta: float = 10.0) -> FusedMLP:
     """A :class:`FusedMLP` from a tiny-cuda-nn network config: ``{"otype": "FullyFusedMLP", "activation": "ReLU",
     "output_activation": "None", "n_neurons": 64 | 128, "n_hidden_layers": 1..4}``.  Anything else raises ``ValueError``
-    with the offending key in the message (defaults are tcnn's: 128 neurons, 5 hidden layers, so give both)."""
+    with the offending key in the message (defaults are tcnn's: 128 neurons, 5 hidden layers, so give both).  With
+    ``activations=True`` the keys ``activation`` and ``output_activation`` take tiny-cuda-nn's names ``None``, ``ReLU``,
+    ``LeakyReLU``, ``Sigmoid``, ``Tanh``, ``Softplus`` (``activation_beta``: tcnn's constant 10), ``Exponential``; ``Sine`` and
+    ``Squareplus`` raise."""
     for k in config:
         if k not in _TCNN_KEYS:
             raise ValueError(f"mlp_from_tcnn_config: key '{k}' is not supported (supported: {', '.join(_TCNN_KEYS)})")
     for k, want, default in (("otype", "FullyFusedMLP", "FullyFusedMLP"), ("activation", "ReLU", "ReLU"),
                              ("output_activation", "None", "None")):
-        if config.get(k, default) != want:
+        if activations and k != "otype":
+            check_activation("mlp_from_tcnn_config", f"'{k}':", config.get(k, default))
+        elif config.get(k, default) != want:
             raise ValueError(f"mlp_from_tcnn_config: '{k}': {config.get(k)!r} is not supported, only {want!r}")
     n_neurons, n_hidden = config.get("n_neurons", 128), config.get("n_hidden_layers", 5)
     if n_neurons not in WIDTHS:
         raise ValueError(f"mlp_from_tcnn_config: 'n_neurons': {n_neurons!r} is not supported, one of {WIDTHS}")
     if not (isinstance(n_hidden, int) and 1 <= n_hidden <= MAX_HIDDEN_LAYERS):
         raise ValueError(f"mlp_from_tcnn_config: 'n_hidden_layers': {n_hidden!r} is not supported, 1 to {MAX_HIDDEN_LAYERS}")
+    act = dict(activation=config.get("activation", "ReLU"), output_activation=config.get("output_activation", "None"),
+               activation_beta=activation_beta) if activations else {}
     return FusedMLP(n_input_dims, n_output_dims, n_neurons, n_hidden, dtype=dtype, out_dtype=out_dtype, generator=generator,
-                    second_order=second_order)
+                    second_order=second_order, **act)
 
 
 def reference_mlp(input_dim: int, output_dim: int, net_depth: int = 4, net_width: int = 64, skip_layer: Optional[int] = 4,
@@ -634,6 +853,13 @@ def stream_limits_error(n_in: int, n_out: int, width: int, n_hidden: int, bias: 
     return None
 
 
+def refuse_activations(who: str, activation, output_activation, activation_beta) -> None:
+    """The streamed kernels hold ReLU hidden layers and no output activation only."""
+    if (activation, output_activation if output_activation is not None else "None", activation_beta) != DEFAULT_ACT:
+        raise ValueError(f"{who}: activation {activation!r}, output_activation {output_activation!r}, activation_beta {activation_beta!r}: "
+                         "the streamed network holds only 'ReLU', 'None' and 10.0 (other activations: FusedMLP, up to 128 neurons)")
+
+
 class StreamedMLP(FusedMLP):
     """:class:`FusedMLP` for the networks it refuses: 128 or 256 neurons, 1..8 hidden layers, ``n_input_dims`` 1..320,
     ``n_output_dims`` 1..288, biases and the reference's skip rule (``skip_layer``; no limit on ``n_input_dims + n_neurons``).
@@ -658,8 +884,10 @@ class StreamedMLP(FusedMLP):
 
     def __init__(self, n_input_dims: int, n_output_dims: int, n_neurons: int = 256, n_hidden_layers: int = 8,
                  dtype: torch.dtype = torch.float16, out_dtype: Optional[torch.dtype] = None,
-                 generator: Optional[torch.Generator] = None, bias: bool = True, skip_layer: Optional[int] = 4):
+                 generator: Optional[torch.Generator] = None, bias: bool = True, skip_layer: Optional[int] = 4,
+                 activation: str = "ReLU", output_activation: str = "None", activation_beta: float = 10.0):
         nn.Module.__init__(self)
+        refuse_activations("StreamedMLP", activation, output_activation, activation_beta)
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError(f"StreamedMLP: dtype {dtype}: torch.float16 or torch.bfloat16")
         if out_dtype not in (None, dtype, torch.float32):
@@ -706,8 +934,10 @@ class NerfMLP(nn.Module):
 
     def __init__(self, input_dim: int, condition_dim: int, net_depth: int = 8, net_width: int = 256, skip_layer: Optional[int] = 4,
                  net_depth_condition: int = 1, net_width_condition: int = 128, dtype: torch.dtype = torch.float16,
-                 generator: Optional[torch.Generator] = None):
+                 generator: Optional[torch.Generator] = None, activation: str = "ReLU", output_activation: str = "None",
+                 activation_beta: float = 10.0):
         super().__init__()
+        refuse_activations("NerfMLP", activation, output_activation, activation_beta)
         if not (isinstance(condition_dim, int) and condition_dim >= 0):
             raise ValueError(f"NerfMLP: condition_dim {condition_dim!r}: a non-negative integer")
         if generator is None:
