@@ -909,6 +909,35 @@ int nfa_vmgrid_bwd(int32_t reduce, int32_t elem, const float *x, const float *pa
 int nfa_vmgrid_resample(const float *src_params, const int32_t *src_res_host, float *dst_params, const int32_t *dst_res_host,
                         int32_t n_components, nfa_stream_t stream);
 
+/* A dense 3-D feature grid sampled trilinearly (DVGO's density and feature grids, TiNeuVox's feature volume with
+ * `mult_dist_interp`), x [n_points, 3] in [0, 1].  res_host: 3 host ints (R_x, R_y, R_z) read during the call, every one >= 2.
+ * n_features C: 1, 2 or a multiple of 4 up to 64.  params: one float32 table of fewer than 2^31 floats, a row-major
+ * [R_z, R_y, R_x, C] block (x fastest among the nodes, a node's C values contiguous); it may exceed 4 GiB.  strides_host:
+ * n_strides (1..4) host ints in 1..8 read during the call; stride s has the nodes at the table indices 0, s, 2 s, .. per axis,
+ * n_d = ceil(R_d / s) >= 2 of them (the view [::s, ::s, ::s]), sampled with the border rule of grid_sample(
+ * padding_mode="border", align_corners=True) (node coordinate x_d (n_d - 1) clamped to [0, n_d - 1], NaN to 0: every input
+ * reads and writes inside the table).  y [n_points, n_strides C], stride k at the columns k C .. k C + C - 1, elements of
+ * type `elem` (NFA_ELEM_*; float32 arithmetic in the order of csrc/voxgrid.hip's header, rounded once).
+ * nfa_voxgrid_bwd: grad_y in y's shape and `elem`; grad_params (the table's size, float32, zeroed by the caller; float
+ * atomics, so its last bits depend on the arrival order) and grad_x [n_points, 3] (no atomics: bitwise reproducible; 0 on an
+ * axis whose coordinate is outside [0, 1] or not finite) are each optional, at least one.  The samples are recomputed from
+ * x and params.  No pointer needs more than its element's alignment.
+ * n_points == 0 returns NFA_OK before anything else is looked at.  Otherwise the arguments are checked in this order, each
+ * with its own message, before any launch: n_points, elem, n_features, res_host (null; a resolution below 2; the size
+ * limit), n_strides, strides_host (null; a stride outside 1..8; fewer than 2 nodes), null pointers.
+ * nfa_voxgrid_resample (DVGO's `scale_volume_grid`): dst_params, a table of the same layout at the resolution dst_res_host,
+ * receives at every node the trilinear sample of src_params at, per axis, (float)i' * ((float)(R - 1) / (float)(R' - 1)):
+ * F.interpolate(mode="trilinear", align_corners=True).  Up, down or unchanged, each axis on its own; equal resolutions copy
+ * (finite values).  The tables must not overlap.  Checked in this order: n_features, the resolution tables (the source, then
+ * the destination: null; a resolution below 2; the size limit), null pointers. */
+int nfa_voxgrid_fwd(int32_t elem, const float *x, const float *params, int64_t n_points, int32_t n_features, const int32_t *res_host,
+                    int32_t n_strides, const int32_t *strides_host, void *y, nfa_stream_t stream);
+int nfa_voxgrid_bwd(int32_t elem, const float *x, const float *params, const void *grad_y, int64_t n_points, int32_t n_features,
+                    const int32_t *res_host, int32_t n_strides, const int32_t *strides_host, float *grad_params, float *grad_x,
+                    nfa_stream_t stream);
+int nfa_voxgrid_resample(const float *src_params, const int32_t *src_res_host, float *dst_params, const int32_t *dst_res_host,
+                         int32_t n_features, nfa_stream_t stream);
+
 /* The regularisers TensoRF puts on the VM tables themselves, over the VM grid above (same n_components, res_host and params
  * layout).  Mode m with its plane seen as p[j, i, k], j < H = R_b rows, i < W = R_a, k < C, and its line as l[r, k], r < R = R_c:
  *   tv_h     = sum (p[j+1,i,k] - p[j,i,k])^2 / (C (H-1) W)         tv_line = sum (l[r+1,k] - l[r,k])^2 / (C (R-1))

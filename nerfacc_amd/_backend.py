@@ -182,6 +182,9 @@ _SIGS = {
     "nfa_vmgrid_fwd": [_i32, _i32, _vp, _vp, _i64, _i32, C.POINTER(_i32), _vp, _vp],
     "nfa_vmgrid_bwd": [_i32, _i32, _vp, _vp, _vp, _i64, _i32, C.POINTER(_i32), _vp, _vp, _vp],
     "nfa_vmgrid_resample": [_vp, C.POINTER(_i32), _vp, C.POINTER(_i32), _i32, _vp],
+    "nfa_voxgrid_fwd": [_i32, _vp, _vp, _i64, _i32, C.POINTER(_i32), _i32, C.POINTER(_i32), _vp, _vp],
+    "nfa_voxgrid_bwd": [_i32, _vp, _vp, _vp, _i64, _i32, C.POINTER(_i32), _i32, C.POINTER(_i32), _vp, _vp, _vp],
+    "nfa_voxgrid_resample": [_vp, C.POINTER(_i32), _vp, C.POINTER(_i32), _i32, _vp],
     "nfa_vmreg_partials": [_i32, C.POINTER(_i32)],
     "nfa_vmreg_fwd": [_vp, _i32, C.POINTER(_i32), _vp, _i64, _vp, _vp, _vp],
     "nfa_vmreg_bwd": [_vp, _i32, C.POINTER(_i32), _vp, _vp, _vp, _vp],

@@ -10,6 +10,8 @@ Parameter layout compatibility with tcnn checkpoints is not a goal.
 dynamic scene) as one native pass each way (csrc/planes.hip); it shares ``out_dtype`` and the device rules below.
 ``VMGridEncoding`` is TensoRF's vector-matrix decomposition (three plane x line modes, concatenated for the appearance or
 summed for the density) with its grid resampling (csrc/vmgrid.hip), under the same rules.
+``VoxelGridEncoding`` is the dense voxel grid of DVGO and TiNeuVox (trilinear samples of one ``[R_z, R_y, R_x, C]`` table at
+up to four node strides, TiNeuVox's multi-distance interpolation) with its resampling (csrc/voxgrid.hip), under the same rules.
 ``SinusoidalEncoding`` is NeRF's positional encoding, the front end of the reference's MLP fields
 (``examples/radiance_fields/mlp.py``: ``SinusoidalEncoder``), with one native pass each for the forward, the backward and the
 second order (csrc/sinenc.hip); it has no parameters and is not reachable through ``encoding_from_tcnn_config``.
@@ -39,7 +41,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _backend as B
 
-__all__ = ["HashGridEncoding", "SphericalHarmonicsEncoding", "PlaneGridEncoding", "VMGridEncoding", "SinusoidalEncoding",
+__all__ = ["HashGridEncoding", "SphericalHarmonicsEncoding", "PlaneGridEncoding", "VMGridEncoding", "VoxelGridEncoding", "SinusoidalEncoding",
            "barf_window", "encoding_from_tcnn_config"]
 
 _M32 = 0xFFFFFFFF
@@ -893,6 +895,182 @@ class VMGridEncoding(nn.Module):
 
     def extra_repr(self) -> str:
         return (f"resolution={self.resolution}, n_components={self.n_components}, reduce={self.reduce!r}"
+                + (f", init_scale={self.init_scale}" if self.init_scale != 0.1 else "")
+                + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else ""))
+
+
+VOXEL_MAX_STRIDES = 4
+
+
+class VoxelTable:
+    """The shape of a dense voxel grid, computed once on the host: ``res`` ``(R_x, R_y, R_z)``, ``n_features`` C, ``strides``
+    and, per stride ``s``, ``nodes[k][d] = ceil(R_d / s)``; the table is one row-major ``[R_z, R_y, R_x, C]`` block."""
+
+    def __init__(self, resolution, n_features: int, strides=(1,)):
+        self.res = [int(r) for r in resolution]
+        self.n_features = int(n_features)
+        self.strides = [int(s) for s in strides]
+        self.nodes = [[-(-r // s) for r in self.res] for s in self.strides]
+        self.n_params = self.res[0] * self.res[1] * self.res[2] * self.n_features
+        # host arrays handed to nfa_voxgrid_{fwd,bwd,resample} (read synchronously by each call)
+        self.c_res = (ctypes.c_int32 * 3)(*[min(r, (1 << 31) - 1) for r in self.res])
+        self.c_strides = (ctypes.c_int32 * len(self.strides))(*self.strides)
+
+
+def _volume_value(table: Tensor, Rx: int, Ry: int, s: int, cx, cy, cz) -> Tensor:
+    """axis.h's volume_value, the 8-tap sum of csrc/voxgrid.hip, on a ``[R_z * R_y * R_x, C]`` table whose sampled nodes are
+    ``s`` apart: ``c* = (i, f)`` per axis, corners ``k = k_x + 2 k_y + 4 k_z`` in order, from 0, weights ``(w_x w_y) w_z``."""
+    (ix, fx), (iy, fy), (iz, fz) = cx, cy, cz
+    row = ((iz * s) * Ry + iy * s) * Rx + ix * s
+    v = torch.zeros(ix.shape[0], table.shape[1], dtype=table.dtype, device=table.device)
+    for k in range(8):
+        kx, ky, kz = k & 1, (k >> 1) & 1, k >> 2
+        w = ((fx if kx else 1.0 - fx) * (fy if ky else 1.0 - fy)) * (fz if kz else 1.0 - fz)
+        v = v + w[:, None] * table[row + ((kz * s * Ry + ky * s) * Rx + kx * s)]
+    return v
+
+
+def _voxgrid_torch(x: Tensor, params: Tensor, t: VoxelTable) -> Tensor:
+    """The voxel grid in torch, op for op as csrc/voxgrid.hip computes it (x [N, 3] and params in one float dtype), with int64
+    gathers."""
+    table = params.view(-1, t.n_features)
+    outs = []
+    for s, n in zip(t.strides, t.nodes):
+        cell = [_locate_nodes(x[:, d] * float(n[d] - 1), n[d]) for d in range(3)]
+        outs.append(_volume_value(table, t.res[0], t.res[1], s, *cell))
+    return torch.cat(outs, -1)
+
+
+def _voxel_resample_torch(params: Tensor, src: VoxelTable, dst: VoxelTable) -> Tensor:
+    """``nfa_voxgrid_resample`` in torch, op for op (DVGO's ``scale_volume_grid``): the table of ``dst`` whose every node is
+    the sample of ``src``'s table at ``i' * ((R - 1) / (R' - 1))`` per axis, the quotient and the product in params' dtype."""
+    dt, dev = params.dtype, params.device
+
+    def nodes(d):
+        scale = torch.tensor(src.res[d] - 1, dtype=dt) / torch.tensor(dst.res[d] - 1, dtype=dt)
+        return _locate_nodes(torch.arange(dst.res[d], dtype=dt, device=dev) * scale.to(dev), src.res[d])
+
+    Wx, Wy, Wz = dst.res
+    cx = tuple(v.repeat(Wy * Wz) for v in nodes(0))                          # node (i'_z, i'_y, i'_x), row-major: x runs fastest
+    cy = tuple(v.repeat_interleave(Wx).repeat(Wz) for v in nodes(1))
+    cz = tuple(v.repeat_interleave(Wx * Wy) for v in nodes(2))
+    return _volume_value(params.view(-1, src.n_features), src.res[0], src.res[1], 1, cx, cy, cz).reshape(-1)
+
+
+class VoxelGridEncoding(nn.Module):
+    """A dense 3-D feature grid sampled trilinearly, as one native pass each way (csrc/voxgrid.hip): DVGO's density grid
+    (``n_features=1``) and ``k0`` feature grid (12), TiNeuVox's feature volume with its multi-distance interpolation
+    (``strides=(1, 2, 4)`` is ``mult_dist_interp``), ReLU-Fields-style grids.  ``forward(x[..., 3])`` for ``x`` in [0, 1]^3
+    (DVGO's and TiNeuVox's ``u`` in [-1, 1] is ``x = (u + 1) / 2``) gives ``[..., C * len(strides)]``, the k-th stride at the
+    columns ``k C .. k C + C - 1``.
+
+    ``resolution`` ``(R_x, R_y, R_z)``, every one at least 2; ``n_features`` C: 1, 2 or a multiple of 4 up to 64.  ``strides``:
+    at most 4, each in 1..8.  Stride ``s`` has its nodes at the table indices ``0, s, 2s, ..`` per axis, ``ceil(R / s)`` of them
+    (at least 2 on every axis), the last one at ``s (ceil(R / s) - 1)``: it is sampled as ``F.grid_sample(mode="bilinear",
+    padding_mode="border", align_corners=True)`` samples the view ``grid[:, :, ::s, ::s, ::s]``.  (TiNeuVox pads its grid so
+    that ``R - 1`` is a multiple of 4 and all levels span the same box; here any ``R`` is legal.)
+
+    ``params`` is one flat float32 table (fewer than 2^31 values), a row-major ``[R_z, R_y, R_x, C]`` block: x runs fastest
+    among the nodes and a node's channels are contiguous.  ``grid()`` is that 4-D view, and ``grid().permute(3, 2, 1, 0)[None]``
+    the ``[1, C, N_x, N_y, N_z]`` tensor DVGO and TiNeuVox keep and hand to ``grid_sample`` with flipped coordinates;
+    ``load_grid`` copies such a tensor in.  Initialised as ``init_scale * randn``.
+
+    Every input is legal: a coordinate outside [0, 1] samples the border (``grid_sample``'s zero padding differs outside the
+    box only), NaN samples node 0, and ``dL/dx`` is zero on such an axis.  Differentiable once w.r.t. ``params`` (float atomics:
+    the last bits change from run to run) and ``x`` (bitwise reproducible); the torch path (CPU tensors, other dtypes) is
+    differentiated by autograd.  ``out_dtype`` as for :class:`HashGridEncoding`.  ``resampled(resolution)`` is DVGO's
+    ``scale_volume_grid``."""
+
+    def __init__(self, resolution, n_features: int = 12, strides=(1,), init_scale: float = 0.1, out_dtype=None):
+        super().__init__()
+        self._configure(resolution, n_features, strides, init_scale, out_dtype)
+        self.params = nn.Parameter(torch.randn(self.table.n_params, dtype=torch.float32) * self.init_scale)
+
+    def _configure(self, resolution, n_features, strides, init_scale, out_dtype):
+        """The checks and everything of the module but ``params`` (``resampled`` fills those itself)."""
+        self.out_dtype = _check_out_dtype(out_dtype)
+        if not (isinstance(n_features, int) and (n_features in (1, 2) or (4 <= n_features <= 64 and n_features % 4 == 0))):
+            raise ValueError(f"VoxelGridEncoding: n_features must be 1, 2 or a multiple of 4 up to 64 (got {n_features})")
+        resolution, strides = tuple(int(r) for r in resolution), tuple(int(s) for s in strides)
+        if len(resolution) != 3:
+            raise ValueError(f"VoxelGridEncoding: resolution must have 3 entries (got {len(resolution)})")
+        if min(resolution) < 2:
+            raise ValueError(f"VoxelGridEncoding: every resolution must be at least 2 (got {resolution})")
+        if not 1 <= len(strides) <= VOXEL_MAX_STRIDES:
+            raise ValueError(f"VoxelGridEncoding: strides must have 1..{VOXEL_MAX_STRIDES} entries (got {len(strides)})")
+        for s in strides:
+            if not 1 <= s <= 8:
+                raise ValueError(f"VoxelGridEncoding: every stride must be in 1..8 (got {strides})")
+            if min(-(-r // s) for r in resolution) < 2:
+                raise ValueError(f"VoxelGridEncoding: stride {s} leaves fewer than 2 nodes along an axis of resolution {resolution}")
+        self.n_input_dims, self.n_features, self.strides, self.resolution = 3, n_features, strides, resolution
+        self.table = VoxelTable(resolution, n_features, strides)
+        if self.table.n_params >= 1 << 31:
+            raise ValueError(f"VoxelGridEncoding: {self.table.n_params} parameters (at most 2^31 - 1)")
+        self.n_output_dims = n_features * len(strides)
+        self.init_scale = float(init_scale)
+
+    _entries = ("nfa_voxgrid_fwd", "nfa_voxgrid_bwd")
+
+    def grid(self) -> Tensor:
+        """The table as a ``[R_z, R_y, R_x, C]`` view of ``params``."""
+        Rx, Ry, Rz = self.resolution
+        return self.params.view(Rz, Ry, Rx, self.n_features)
+
+    @torch.no_grad()
+    def load_grid(self, t: Tensor) -> None:
+        """Copy a DVGO / TiNeuVox grid, ``[1, C, N_x, N_y, N_z]`` or ``[C, N_x, N_y, N_z]``, into ``params``."""
+        if t.dim() == 5 and t.shape[0] == 1:
+            t = t[0]
+        want = (self.n_features, *self.resolution)
+        if tuple(t.shape) != want:
+            raise ValueError(f"VoxelGridEncoding.load_grid: the grid must have shape {(1, *want)} or {want} (got {tuple(t.shape)})")
+        self.grid().copy_(t.permute(3, 2, 1, 0))
+
+    def _lead(self, dtype: torch.dtype):
+        return (B.ELEM_CODES[dtype],)
+
+    def _table_args(self, n_points: int):
+        return n_points, self.n_features, self.table.c_res, len(self.strides), self.table.c_strides
+
+    def forward(self, x: Tensor) -> Tensor:
+        assert x.shape[-1] == 3, "VoxelGridEncoding: x must have shape (..., 3)"
+        out = _resolve_out_dtype(self.out_dtype, x)
+        x, ctx = _autocast_off(x)
+        with ctx:
+            lead = x.shape[:-1]
+            x2 = x.reshape(-1, 3)
+            p = self.params
+            if x2.is_cuda and x2.dtype == torch.float32 and p.dtype == torch.float32 and p.device == x2.device:
+                y = _GridFn.apply(x2.contiguous(), p, self, out)   # (element-wise access: no alignment beyond 4 bytes)
+            else:
+                dt = torch.promote_types(x2.dtype, p.dtype)
+                y = _voxgrid_torch(x2.to(dt), p.to(dt), self.table)
+                if self.out_dtype is not None:
+                    y = y.to(out)
+            return y.view(*lead, self.n_output_dims)
+
+    @torch.no_grad()
+    def resampled(self, resolution) -> "VoxelGridEncoding":
+        """A new module on the same device whose table is this one resampled to ``resolution`` (each axis up, down or
+        unchanged) in one launch: ``F.interpolate(mode="trilinear", align_corners=True)``, DVGO's ``scale_volume_grid``.  The
+        same resolution copies the table bit for bit (finite values).  ``strides`` carry over and must fit the new resolution.
+        Optimiser state does not follow: build a new optimiser, as DVGO does."""
+        new = VoxelGridEncoding.__new__(VoxelGridEncoding)   # (no random table is drawn for a module that gets this one's samples)
+        nn.Module.__init__(new)
+        new._configure(resolution, self.n_features, self.strides, self.init_scale, self.out_dtype)
+        p = self.params.detach()
+        if p.is_cuda and p.dtype == torch.float32:
+            q = torch.empty(new.table.n_params, dtype=torch.float32, device=p.device)
+            with torch.cuda.device(p.device):
+                B.call("nfa_voxgrid_resample", B.ptr(p), self.table.c_res, B.ptr(q), new.table.c_res, self.n_features, B.stream())
+        else:
+            q = _voxel_resample_torch(p, self.table, new.table)
+        new.params = nn.Parameter(q, requires_grad=self.params.requires_grad)
+        return new
+
+    def extra_repr(self) -> str:
+        return (f"resolution={self.resolution}, n_features={self.n_features}, strides={self.strides}"
                 + (f", init_scale={self.init_scale}" if self.init_scale != 0.1 else "")
                 + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else ""))
 
