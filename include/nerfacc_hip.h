@@ -1335,6 +1335,51 @@ int nfa_optim_decide(const nfa_optim_args *args_host, nfa_optim_state *state, nf
 int nfa_optim_update(int32_t dtype, const nfa_optim_tensor *table, int32_t n_tensors, const nfa_optim_chunk *work, int64_t n_chunks,
                      const nfa_optim_state *state, int32_t zero_grad, nfa_stream_t stream);
 
+/* ------------------------------------------------------------------ photometric loss (csrc/photo.hip)
+ * The target side of a training step: the pixel gather, the background blend, the loss, its gradient and the MSE.  The
+ * per-element terms (P = param; s(d) = 1, -1 or d itself for d > 0, d < 0, otherwise), float32, each operation rounded:
+ *     NFA_PHOTO_L1           |d|                                               dterm/dd = s(d)
+ *     NFA_PHOTO_L2           d * d                                             2 * d
+ *     NFA_PHOTO_SMOOTH_L1    |d| < P ? ((0.5 * d) * d) / P : |d| - 0.5 * P     |d| < P ? d / P : s(d)        (P > 0)
+ *     NFA_PHOTO_HUBER        |d| <= P ? (0.5 * d) * d : P * (|d| - 0.5 * P)    |d| <= P ? d : P * s(d)
+ *     NFA_PHOTO_RELATIVE_L2  (d * d) / (rgb * rgb + 0.01)                      (2 * d) / (rgb * rgb + 0.01)  (instant-ngp's)
+ *     NFA_PHOTO_CHARBONNIER  sqrt(d * d + P * P)                               d / sqrt(d * d + P * P) */
+#define NFA_PHOTO_L1 0
+#define NFA_PHOTO_L2 1
+#define NFA_PHOTO_SMOOTH_L1 2
+#define NFA_PHOTO_HUBER 3
+#define NFA_PHOTO_RELATIVE_L2 4
+#define NFA_PHOTO_CHARBONNIER 5
+/* Targets, loss and MSE of n_rays rays in two launches (one when rgb is NULL).  Replaces, ref: examples/datasets/
+ * nerf_synthetic.py:195 (`rgba = images[image_id, y, x] / 255.0`) and :153 (`pixels = rgba[:, :3] * alpha + color_bkgd *
+ * (1 - alpha)`), dnerf_synthetic.py:155,197 (the same), nerf_360_v2.py:327 (the RGB-only gather), and the trainers'
+ * `F.smooth_l1_loss(rgb, pixels)` and `F.mse_loss(rgb, pixels)` (examples/train_ngp_nerf_occ.py:198,208,245,
+ * train_ngp_nerf_prop.py:243,253,295, train_mlp_nerf.py:170,179,226, train_mlp_tnerf.py:163,172,211).
+ * Source, exactly one of: images, a uint8 stack [n_images, height, width, n_channels] read at (image_ids, y, x) [n_rays]
+ * (index_dtype 1: int32, 2: int64, one type for the three; image_ids NULL: image 0; x and y NULL: ray i reads pixel i of
+ * the stack in memory order), every index clamped into the stack, the byte offset formed in 64 bits, a channel float(byte) /
+ * 255.0f; or pixels_in, float32 [n_rays, n_channels].  n_channels 3 or 4.  With 4 channels and bkgd ([3]: bkgd_stride 0, or
+ * [n_rays, 3]: 3) target = (p * a) + (b * (1.0f - a)); bkgd NULL: the three colour channels as they are.
+ * rgb [n_rays, 3] of type elem (NFA_ELEM_*), computed in float32; d = rgb - target.  weights [n_rays] or NULL.
+ * Writes pixels [n_rays, 3] (the target), loss[0] = sum w * term / (3 n_rays), mse[0] = sum d * d / (3 n_rays) and, if not
+ * NULL, per_ray [n_rays] = (w * ((t_0 + t_1) + t_2)) / 3.0f.  The sums are float64 without atomics: a workgroup adds the
+ * nfa_photometric_chunk() rays of a chunk in a fixed order into partials [n_partials >= ceil(n_rays / chunk), 2] (scratch,
+ * 8-byte aligned, need not be initialised), a second launch of one wave adds those (lane t: t, t + 64, .. in order; then
+ * the lanes in order), divides by 3 n_rays and rounds to float32 once.  rgb NULL: only pixels is written (kind, weights,
+ * partials, loss, mse, per_ray are not looked at).  n_rays == 0 returns at once and writes nothing.  No host read. */
+int nfa_photometric_fwd(const void *rgb, int32_t elem, int64_t n_rays, const uint8_t *images, int64_t n_images, int64_t height,
+                        int64_t width, const void *image_ids, const void *x, const void *y, int32_t index_dtype,
+                        const float *pixels_in, int32_t n_channels, const float *bkgd, int64_t bkgd_stride, const float *weights,
+                        int32_t kind, float param, float *pixels, double *partials, int64_t n_partials, float *loss, float *mse,
+                        float *per_ray, nfa_stream_t stream);
+/* Its backward, ref: what `(loss * scale).backward()` delivers at rgb (examples/train_ngp_nerf_occ.py:202, train_ngp_nerf_prop.py:247), one launch:
+ * g_rgb [n_rays, 3] of type elem = ((g * w) * inv) * dterm/dd, rounded once, with g = g_loss[0] read on the device (the
+ * gradient that arrived at the loss: the loss scale), inv = 1.0f / (float)(3 n_rays) and d = rgb - pixels, pixels being the
+ * forward's output.  per_ray and mse carry no gradient. */
+int nfa_photometric_bwd(const void *rgb, int32_t elem, const float *pixels, const float *weights, const float *g_loss,
+                        int64_t n_rays, int32_t kind, float param, void *g_rgb, nfa_stream_t stream);
+int nfa_photometric_chunk(void);   /* rays per partial pair of the forward's reduction (a constant of the build) */
+
 #ifdef __cplusplus
 }
 #endif

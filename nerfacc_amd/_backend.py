@@ -221,6 +221,10 @@ _SIGS = {
     "nfa_optim_scan": [_i32, _vp, _i32, _vp, _i64, _vp, _vp],
     "nfa_optim_decide": [C.POINTER(OptimArgs), _vp, _vp, _vp],
     "nfa_optim_update": [_i32, _vp, _i32, _vp, _i64, _vp, _i32, _vp],
+    "nfa_photometric_fwd": [_vp, _i32, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _i32, _f32, _vp, _vp,
+                            _i64, _vp, _vp, _vp, _vp],
+    "nfa_photometric_bwd": [_vp, _i32, _vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp],
+    "nfa_photometric_chunk": [],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],
