@@ -2663,13 +2663,17 @@ int nfa_render_from_alpha_bwd(const float *alphas, const float *trans, const flo
 }
 
 // VisibilityOp's band [s_lo, s_hi] around S = -ln(eps), where exp(-S) crosses eps; expf is good to a couple of ulps, the band
-// is +-2e-5 relative (~20 ulps)
+// is +-2e-5 relative (~20 ulps).  That reasoning needs a normal eps: below 2^-126 expf's result moves in steps of 2^-149, up
+// to a seventh of eps itself, so it rounds up to eps for sums as far as 0.07 beyond -ln(eps) -- no band of a few ulps covers
+// that, and the band is everything: expf is evaluated at every sample.
 static void visibility_band(float early_stop_eps, float &s_lo, float &s_hi)
 {
-    if (early_stop_eps > 0.0f) {
+    if (early_stop_eps >= 0x1p-126f) {
         const double L = -log((double)early_stop_eps);
         const double w = 2e-5 * (L > 1.0 ? L : 1.0);
         s_lo = (float)(L - w); s_hi = (float)(L + w);
+    } else if (early_stop_eps > 0.0f) {
+        s_lo = -INFINITY; s_hi = INFINITY;
     } else {   // every transmittance >= eps (exp(-S) is never negative; a NaN sum stays invisible as before)
         s_lo = INFINITY; s_hi = INFINITY;
     }

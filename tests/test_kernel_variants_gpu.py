@@ -157,10 +157,25 @@ def test_scans_scalar_form(dev, monkeypatch, kind):
 
 
 # ----------------------------------------------------------------------------- transmittance / weights
+# The *_saturated tests run the same bodies with densities up to SIG_SAT: sigma * delta reaches 420, so alpha == 1 and T == 0
+# exactly over most of a ray (tests/test_render_edges_gpu.py places such samples one by one).
+SIG_SAT = 2e4
+
+
 @pytest.mark.parametrize("prefix", [False, True])
 @pytest.mark.parametrize("grad_t", [False, True])
 def test_render_weight_from_density_scalar_form(dev, monkeypatch, prefix, grad_t):
-    rays, ri, ts, te, sig, g = case(dev, 2)
+    _render_weight_from_density_scalar_form(dev, monkeypatch, prefix, grad_t, 2.0)
+
+
+@pytest.mark.parametrize("prefix", [False, True])
+@pytest.mark.parametrize("grad_t", [False, True])
+def test_render_weight_from_density_scalar_form_saturated(dev, monkeypatch, prefix, grad_t):
+    _render_weight_from_density_scalar_form(dev, monkeypatch, prefix, grad_t, SIG_SAT)
+
+
+def _render_weight_from_density_scalar_form(dev, monkeypatch, prefix, grad_t, sig_max):
+    rays, ri, ts, te, sig, g = case(dev, 2, sig_max=sig_max)
     pf = (0.2 + 0.8 * torch.rand(rays.n, generator=g)).to(dev) if prefix else None
     R = rays.R
     log = CallLog(monkeypatch)
@@ -218,7 +233,16 @@ def _incoming(opac, depth, g_o, g_d):
 
 @pytest.mark.parametrize("mode", ["sigma_extras", "sigma_colors", "alpha_extras", "alpha_colors"])
 def test_rendering_scalar_form(dev, monkeypatch, mode):
-    rays, ri, ts, te, sig, g = case(dev, 4)
+    _rendering_scalar_form(dev, monkeypatch, mode, 2.0)
+
+
+@pytest.mark.parametrize("mode", ["sigma_extras", "sigma_colors"])   # (the alpha modes' reference is autograd over a cumprod: not
+def test_rendering_scalar_form_saturated(dev, monkeypatch, mode):     #  the contract at alpha == 1, see test_render_edges_gpu.py)
+    _rendering_scalar_form(dev, monkeypatch, mode, SIG_SAT)
+
+
+def _rendering_scalar_form(dev, monkeypatch, mode, sig_max):
+    rays, ri, ts, te, sig, g = case(dev, 4, sig_max=sig_max)
     R, dens, extras = rays.R, mode.startswith("sigma"), mode.endswith("extras")
     rgb = torch.rand(rays.n, 3, generator=g).to(dev)
     al = (torch.rand(rays.n, generator=g) * 0.05).to(dev)
@@ -290,7 +314,16 @@ def test_rendering_scalar_form(dev, monkeypatch, mode):
 @pytest.mark.parametrize("density", [True, False])
 @pytest.mark.parametrize("counts", [False, True])
 def test_visibility_scalar_form(dev, monkeypatch, density, counts):
-    rays, ri, ts, te, sig, g = case(dev, 5, sig_max=20.0)
+    _visibility_scalar_form(dev, monkeypatch, density, counts, 20.0)
+
+
+@pytest.mark.parametrize("counts", [False, True])
+def test_visibility_scalar_form_saturated(dev, monkeypatch, counts):
+    _visibility_scalar_form(dev, monkeypatch, True, counts, SIG_SAT)
+
+
+def _visibility_scalar_form(dev, monkeypatch, density, counts, sig_max):
+    rays, ri, ts, te, sig, g = case(dev, 5, sig_max=sig_max)
     al = (torch.rand(rays.n, generator=g) * 0.2).to(dev)
     pf = (0.5 + 0.5 * torch.rand(rays.n, generator=g)).to(dev)
     seg = seginfo_from_ray_indices(ri, rays.R)
@@ -366,8 +399,17 @@ def test_compact_samples_scalar_form(dev, monkeypatch):
 
 @pytest.mark.parametrize("alpha_thre", [0.0, 0.01])
 def test_render_step_accumulate_scalar_form(dev, monkeypatch, alpha_thre):
+    _render_step_accumulate_scalar_form(dev, monkeypatch, alpha_thre, 4.0)
+
+
+@pytest.mark.parametrize("alpha_thre", [0.0, 0.01])
+def test_render_step_accumulate_scalar_form_saturated(dev, monkeypatch, alpha_thre):
+    _render_step_accumulate_scalar_form(dev, monkeypatch, alpha_thre, SIG_SAT)
+
+
+def _render_step_accumulate_scalar_form(dev, monkeypatch, alpha_thre, sig_max):
     from nerfacc_amd import marching
-    rays, ri, ts, te, sig, g = case(dev, 7, sig_max=4.0)
+    rays, ri, ts, te, sig, g = case(dev, 7, sig_max=sig_max)
     R = rays.R
     rgbs = torch.rand(rays.n, 3, generator=g).to(dev)
     c0 = torch.rand(R, 3, generator=g).to(dev)
