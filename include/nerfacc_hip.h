@@ -965,6 +965,42 @@ int nfa_vmreg_fwd(const float *params, int32_t n_components, const int32_t *res_
 int nfa_vmreg_bwd(const float *params, int32_t n_components, const int32_t *res_host, const float *grad_terms, const float *signs,
                   float *grad_params, nfa_stream_t stream);
 
+/* The regularisers of the dense voxel grid above (same n_features, res_host and params layout; the base table, whatever the
+ * strides): total variation along x, y and z under a penalty rho chosen by `kind`, and the L1 pull towards 0.  With the table
+ * seen as g[z, y, x, c]:
+ *   NFA_VOXREG_L2: rho(d) = d^2;  NFA_VOXREG_L1: |d|;  NFA_VOXREG_HUBER: d^2 / 2 for |d| <= 1, else |d| - 1/2 (smooth L1, beta 1)
+ *   tv_x = sum rho(g[z,y,x+1,c] - g[z,y,x,c]) / n_x,  n_x = C R_z R_y (R_x - 1)        likewise tv_y, tv_z
+ *   l1   = sum |g| / (C R_z R_y R_x)
+ * `reduction`: NFA_VOXREG_MEAN divides by the counts as written, NFA_VOXREG_SUM by 1.  These formulas are the contract.
+ * nfa_voxreg_fwd: terms [4] = (tv_x, tv_y, tv_z, l1), two launches (per-workgroup sums into partials, then one workgroup), no
+ * atomics: the same bits on every run; the order of the sums and the longest chain of additions (184) are in
+ * csrc/voxreg.hip's header.  partials: device scratch of n_partials >= nfa_voxreg_partials(n_features, res_host) rows of 4
+ * floats, contents irrelevant before and after.  nfa_voxreg_partials is host-only arithmetic on the shape (-1 with a message
+ * for a shape the passes refuse).
+ * nfa_voxreg_bwd: grad_terms [4], a DEVICE pointer; grad_params (the table's size) receives sum_t grad_terms[t] d terms[t] / d
+ * params in one launch with plain stores: every element is written (the caller need not zero it) and the result is bitwise
+ * reproducible.  The derivative of |v| is 0 at 0, that of the Huber penalty clamp(d, -1, 1).
+ * nfa_voxreg_add_grad (the form of DVGO's `total_variation_add_grad`): weights [4], a HOST pointer read during the call, take
+ * grad_terms' place; grad (the table's size) becomes grad + that gradient, in place, in one launch, where dense != 0 or the
+ * element of grad is not 0 (a NaN is not 0); elsewhere it keeps its bits.  The value added has the bits nfa_voxreg_bwd
+ * writes for grad_terms = weights.
+ * NaN and Inf parameters reach the terms and the elements whose stencil touches them; no index depends on data and nothing
+ * is read back from the device.  params, partials, grad_params and grad must be 16-byte aligned; the table may exceed 4 GiB.
+ * The arguments are checked in this order, each with its own message, before any launch: n_features, res_host (null; a
+ * resolution below 2; the size limit), kind, reduction, null pointers, alignment, n_partials. */
+#define NFA_VOXREG_L2 0
+#define NFA_VOXREG_L1 1
+#define NFA_VOXREG_HUBER 2
+#define NFA_VOXREG_MEAN 0
+#define NFA_VOXREG_SUM 1
+int64_t nfa_voxreg_partials(int32_t n_features, const int32_t *res_host);
+int nfa_voxreg_fwd(const float *params, int32_t n_features, const int32_t *res_host, int32_t kind, int32_t reduction, float *partials,
+                   int64_t n_partials, float *terms, nfa_stream_t stream);
+int nfa_voxreg_bwd(const float *params, int32_t n_features, const int32_t *res_host, int32_t kind, int32_t reduction,
+                   const float *grad_terms, float *grad_params, nfa_stream_t stream);
+int nfa_voxreg_add_grad(const float *params, int32_t n_features, const int32_t *res_host, int32_t kind, int32_t reduction,
+                        const float *weights, int32_t dense, float *grad, nfa_stream_t stream);
+
 /* NeRF's sinusoidal (positional) encoding (ref: examples/radiance_fields/mlp.py, SinusoidalEncoder) of x [n_points, n_dims],
  * n_dims D in 1..4, with the n_freqs L in 0..16 frequencies s_k = 2^(min_deg + k) (-16 <= min_deg, min_deg + L <= 32).  A row
  * has K = (identity ? D : 0) + 2 L D columns in the reference's order: x (identity != 0; bitwise copies), then

@@ -188,6 +188,10 @@ _SIGS = {
     "nfa_vmreg_partials": [_i32, C.POINTER(_i32)],
     "nfa_vmreg_fwd": [_vp, _i32, C.POINTER(_i32), _vp, _i64, _vp, _vp, _vp],
     "nfa_vmreg_bwd": [_vp, _i32, C.POINTER(_i32), _vp, _vp, _vp, _vp],
+    "nfa_voxreg_partials": [_i32, C.POINTER(_i32)],
+    "nfa_voxreg_fwd": [_vp, _i32, C.POINTER(_i32), _i32, _i32, _vp, _i64, _vp, _vp],
+    "nfa_voxreg_bwd": [_vp, _i32, C.POINTER(_i32), _i32, _i32, _vp, _vp, _vp],
+    "nfa_voxreg_add_grad": [_vp, _i32, C.POINTER(_i32), _i32, _i32, C.POINTER(_f32), _i32, _vp, _vp],
     "nfa_sinenc_fwd": [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp],
     "nfa_sinenc_bwd": [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "nfa_sinenc_bwd_bwd": [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
@@ -231,7 +235,7 @@ _SIGS = {
     "nfa_set_tuning": [C.c_char_p, C.c_char_p],
     "nfa_device_arch": [C.c_char_p, _int],
 }
-_RESTYPES = {"nfa_grid_rebinarize_scratch_bytes": _i64, "nfa_hashgrid_sorted_scratch_bytes": _i64, "nfa_hashgrid_sorted_scratch_bytes_d": _i64, "nfa_planereg_partials": _i64, "nfa_vmreg_partials": _i64, "nfa_bricks_words": _i64, "nfa_walk_bits_words": _i64, "nfa_pdf_loss_partials": _i64, "nfa_cumsum_scratch_bytes": _i64, "nfa_seg_table_rows": _i64, "nfa_seg_plan": None, "nfa_last_error": C.c_char_p}
+_RESTYPES = {"nfa_grid_rebinarize_scratch_bytes": _i64, "nfa_hashgrid_sorted_scratch_bytes": _i64, "nfa_hashgrid_sorted_scratch_bytes_d": _i64, "nfa_planereg_partials": _i64, "nfa_vmreg_partials": _i64, "nfa_voxreg_partials": _i64, "nfa_bricks_words": _i64, "nfa_walk_bits_words": _i64, "nfa_pdf_loss_partials": _i64, "nfa_cumsum_scratch_bytes": _i64, "nfa_seg_table_rows": _i64, "nfa_seg_plan": None, "nfa_last_error": C.c_char_p}
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -278,6 +282,9 @@ INTERP_CODES = {"Linear": 0, "Smoothstep": 1}
 PLANE_REDUCE_CODES = {"product": 0, "sum": 1}
 # include/nerfacc_hip.h: NFA_VM_*, what the VM grid does with the three modes' terms
 VM_REDUCE_CODES = {"concat": 0, "sum": 1}
+# include/nerfacc_hip.h: NFA_VOXREG_*, the penalty and the reduction of the voxel grid's regularisers
+VOXREG_KIND_CODES = {"l2": 0, "l1": 1, "huber": 2}
+VOXREG_REDUCTION_CODES = {"mean": 0, "sum": 1}
 
 
 def set_tuning(name: str, value: Optional[str]) -> None:

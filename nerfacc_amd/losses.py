@@ -1,5 +1,5 @@
 """Regularisers over packed samples (native kernels: csrc/segscan.hip, ``DistortionFwdOp`` / ``DistortionBwdOp``), over
-the tables of a plane grid (csrc/planereg.hip) and over the tables of a VM grid (csrc/vmreg.hip).
+the tables of a plane grid (csrc/planereg.hip), of a VM grid (csrc/vmreg.hip) and of a dense voxel grid (csrc/voxreg.hip).
 
 ``distortion`` is the Mip-NeRF 360 distortion loss (Barron et al. 2022, eq. 15), the other half of the proposal-sampling
 recipe ``PropNetEstimator`` implements.  Earlier nerfacc releases shipped a packed version; 0.5 dropped it.
@@ -12,10 +12,16 @@ time and the L1 pull of the space-time planes towards 1, as one native pass each
 of a :class:`~nerfacc_amd.encodings.VMGridEncoding`: total variation, the L1 pull towards 0 and the orthogonality penalty on
 the line components, as two launches forward and one backward.
 
+``voxel_terms`` / ``voxel_regularization`` / ``voxel_tv_add_grad_`` are the regularisers DVGO (Sun et al. 2022) and TiNeuVox
+put on a :class:`~nerfacc_amd.encodings.VoxelGridEncoding`'s table (csrc/voxreg.hip): total variation along the three axes
+under an l2, l1 or Huber penalty and the L1 pull towards 0, as two launches forward and one backward, and as one in-place
+launch that adds the gradient straight into ``params.grad``.
+
 Not part of ``nerfacc_amd.__all__`` (that list mirrors the reference's exactly); import the module.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Optional
 
@@ -27,7 +33,8 @@ from . import _backend as B
 from ._segments import SegInfo, batched_native, resolve
 from .encodings import _aligned16
 
-__all__ = ["distortion", "plane_terms", "plane_regularization", "vm_terms", "vm_regularization"]
+__all__ = ["distortion", "plane_terms", "plane_regularization", "vm_terms", "vm_regularization", "voxel_terms", "voxel_regularization",
+           "voxel_tv_add_grad_"]
 
 
 class _Distortion(torch.autograd.Function):
@@ -495,3 +502,209 @@ def vm_regularization(enc, tv: float = 0.0, l1: float = 0.0, tv_line: float = 0.
     It is ``vm_terms(enc)`` dotted with a constant weight tensor that is built once per (weights, device) and kept, so a call
     makes no host-to-device copy after the first."""
     return (vm_terms(enc) * _vm_weights(enc, float(tv), float(l1), float(tv_line), float(ortho))).sum()
+
+
+# ----------------------------------------------------------------------------- voxel-grid regularisers (csrc/voxreg.hip)
+def _voxel_check(fn: str, enc, kind: str, reduction: str) -> None:
+    from .encodings import VoxelGridEncoding
+    if not isinstance(enc, VoxelGridEncoding):
+        raise ValueError(f"{fn}: enc must be a VoxelGridEncoding (got {type(enc).__name__})")
+    if kind not in B.VOXREG_KIND_CODES:
+        raise ValueError(f"{fn}: kind must be 'l2', 'l1' or 'huber' (got {kind!r})")
+    if reduction not in B.VOXREG_REDUCTION_CODES:
+        raise ValueError(f"{fn}: reduction must be 'mean' or 'sum' (got {reduction!r})")
+
+
+def _voxel_counts(res, C: int):
+    """The number of summands of (tv_x, tv_y, tv_z, l1) on a ``[R_z, R_y, R_x, C]`` table; every one positive."""
+    Rx, Ry, Rz = res
+    return (C * Rz * Ry * (Rx - 1), C * Rz * (Ry - 1) * Rx, C * (Rz - 1) * Ry * Rx, C * Rz * Ry * Rx)
+
+
+def _voxel_rho(d: Tensor, kind: str) -> Tensor:
+    if kind == "l2":
+        return d * d
+    a = d.abs()
+    return a if kind == "l1" else torch.where(a <= 1.0, 0.5 * (d * d), a - 0.5)
+
+
+def _voxel_p(d: Tensor, kind: str) -> Tensor:
+    """``P`` of csrc/voxreg.hip's backward: the identity for l2 (its factor 2 is in ``k_t``), ``rho'`` otherwise."""
+    if kind == "l2":
+        return d
+    if kind == "l1":
+        return _sign0(d)
+    one = torch.ones_like(d)
+    return torch.where(d < -1.0, -one, torch.where(d > 1.0, one, d))
+
+
+def _voxel_diffs(g: Tensor):
+    """The differences of ``g[z, y, x, c]`` towards the next node along x, y and z."""
+    return g[:, :, 1:] - g[:, :, :-1], g[:, 1:] - g[:, :-1], g[1:] - g[:-1]
+
+
+def _voxel_terms_torch(params: Tensor, res, C: int, kind: str, reduction: str) -> Tensor:
+    """The four terms by slicing, in ``params``' dtype; differentiated by autograd."""
+    g = params.view(res[2], res[1], res[0], C)
+    n = _voxel_counts(res, C) if reduction == "mean" else (1, 1, 1, 1)
+    sums = [_voxel_rho(d, kind).sum() for d in _voxel_diffs(g)] + [g.abs().sum()]
+    return torch.stack([s / c for s, c in zip(sums, n)])
+
+
+def _voxel_terms_grad_torch(params: Tensor, grad_terms: Tensor, res, C: int, kind: str, reduction: str) -> Tensor:
+    """``d (grad_terms . terms) / d params`` in float32, operation for operation as ``nfa_voxreg_bwd`` forms it (the stencils
+    and their order: csrc/voxreg.hip's header), so the two agree bit for bit: with ``c_t = grad_terms[t] * (float)(1 / n_t)``
+    (``* 1`` with ``"sum"``), ``k_t = 2 c_t`` for l2 and ``c_t`` otherwise,
+
+        gx = (x >= 1 ? P(g - g[x-1]) : 0) - (x + 1 < R_x ? P(g[x+1] - g) : 0)          likewise gy, gz
+        v  = k_x gx;   v = v + k_y gy;   v = v + k_z gz;   v = v + c_l sign0(g)"""
+    p32, g32 = params.detach().to(torch.float32), grad_terms.detach().to(torch.float32).reshape(4)
+    g = p32.view(res[2], res[1], res[0], C)
+    scale = [1.0 / n if reduction == "mean" else 1.0 for n in _voxel_counts(res, C)]
+    c = g32 * torch.tensor(scale, dtype=torch.float32, device=g.device)
+    k = 2.0 * c if kind == "l2" else c
+    v = None
+    for t, (dim, d) in enumerate(zip((2, 1, 0), _voxel_diffs(g))):
+        pd = _voxel_p(d, kind)
+        zero = torch.zeros_like(pd.narrow(dim, 0, 1))
+        part = k[t] * (torch.cat([zero, pd], dim) - torch.cat([pd, zero], dim))
+        v = part if v is None else v + part
+    return (v + c[3] * _sign0(g)).reshape(-1)
+
+
+def _voxreg_args(enc, kind: str, reduction: str):
+    return enc.n_features, enc.table.c_res, B.VOXREG_KIND_CODES[kind], B.VOXREG_REDUCTION_CODES[reduction]
+
+
+class _VoxelTermsFn(torch.autograd.Function):
+    """``terms`` in two launches (``nfa_voxreg_fwd``); the table gradient through :class:`_VoxelTermsBwdFn`."""
+
+    @staticmethod
+    def forward(ctx, params, enc, kind, reduction):
+        dev = B.require_device(params)
+        p = _aligned16(params)
+        n_partials = B.load().nfa_voxreg_partials(enc.n_features, enc.table.c_res)   # (host arithmetic on the shape)
+        partials = torch.empty(n_partials, 4, dtype=torch.float32, device=dev)
+        terms = torch.empty(4, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            B.call("nfa_voxreg_fwd", B.ptr(p), *_voxreg_args(enc, kind, reduction), B.ptr(partials), n_partials, B.ptr(terms), B.stream())
+        ctx.enc, ctx.kind, ctx.reduction = enc, kind, reduction
+        ctx.save_for_backward(p)
+        return terms
+
+    @staticmethod
+    def backward(ctx, g_terms):
+        if g_terms is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        (p,) = ctx.saved_tensors
+        return _VoxelTermsBwdFn.apply(p, g_terms.to(torch.float32).contiguous(), ctx.enc, ctx.kind, ctx.reduction), None, None, None
+
+
+class _VoxelTermsBwdFn(torch.autograd.Function):
+    """The backward as a function ``(params, g_terms) -> g_params`` of its own, so that differentiating it again fails with
+    a message that names ``voxel_terms`` instead of a missing ``grad_fn`` (as ``_VMTermsBwdFn`` does)."""
+
+    @staticmethod
+    def forward(ctx, p, g, enc, kind, reduction):
+        g_p = torch.empty_like(p)   # (every element is written)
+        with torch.cuda.device(p.device):
+            B.call("nfa_voxreg_bwd", B.ptr(p), *_voxreg_args(enc, kind, reduction), B.ptr(g), B.ptr(g_p), B.stream())
+        return g_p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gg_p):
+        raise NotImplementedError("voxel_terms: the second order (differentiating dL/dparams again) is not implemented on the "
+                                  "native path; the torch path on CPU tensors is differentiated by autograd")
+
+
+def voxel_terms(enc, kind: str = "l2", reduction: str = "mean") -> Tensor:
+    """The four regularisation terms of a :class:`~nerfacc_amd.encodings.VoxelGridEncoding`'s table: ``[4]`` float32 on
+    ``enc.params``' device, ``(tv_x, tv_y, tv_z, l1)``.  With the table seen as ``g[z, y, x, c]`` (``enc.grid()``; the base
+    table, whatever ``strides``) of resolution ``(R_x, R_y, R_z)`` with ``C`` features:
+
+        tv_x = sum rho(g[z,y,x+1,c] - g[z,y,x,c]) / (C R_z R_y (R_x-1))
+        tv_y = sum rho(g[z,y+1,x,c] - g[z,y,x,c]) / (C R_z (R_y-1) R_x)
+        tv_z = sum rho(g[z+1,y,x,c] - g[z,y,x,c]) / (C (R_z-1) R_y R_x)
+        l1   = sum |g| / (C R_z R_y R_x)
+
+    ``kind`` picks the penalty: ``"l2"``: ``rho(d) = d^2``; ``"l1"``: ``|d|`` (derivative ``sign(d)``, 0 at 0); ``"huber"``:
+    ``d^2 / 2`` for ``|d| <= 1``, else ``|d| - 1/2`` (``F.smooth_l1_loss`` with ``beta=1``; derivative ``clamp(d, -1, 1)``).
+    ``reduction="sum"`` leaves the divisions out.  The derivative of ``|g|`` is ``sign(g)``, 0 at 0.
+
+    These are the terms DVGO and TiNeuVox build their total variation from (on the ``[1, C, N_x, N_y, N_z]`` view
+    ``grid().permute(3, 2, 1, 0)[None]``, the differences along dims 2, 3, 4 are those along x, y, z here); nothing beyond
+    these formulas is claimed.
+
+    Differentiable once towards ``enc.params``.  CUDA float32 parameters run on libnerfacc_hip.so (csrc/voxreg.hip: two
+    launches forward, one backward, no atomics, nothing read back from the device: the same bits on every run); anything
+    else (CPU tensors, other dtypes) runs the same formulas in torch and is differentiated by autograd."""
+    _voxel_check("voxel_terms", enc, kind, reduction)
+    params = enc.params
+    if params.is_cuda and params.dtype == torch.float32:
+        return _VoxelTermsFn.apply(params, enc, kind, reduction)
+    dt = torch.promote_types(params.dtype, torch.float32)
+    return _voxel_terms_torch(params.to(dt), enc.resolution, enc.n_features, kind, reduction).to(torch.float32)
+
+
+_VOXEL_WEIGHTS: dict = {}   # (the four weights, device) -> [4]
+
+
+def _voxel_weights(enc, wx: float, wy: float, wz: float, l1: float) -> Tensor:
+    key = (wx, wy, wz, l1, enc.params.device)
+    w = _VOXEL_WEIGHTS.get(key)
+    if w is None:
+        w = _VOXEL_WEIGHTS[key] = torch.tensor([wx, wy, wz, l1], dtype=torch.float32, device=enc.params.device)
+    return w
+
+
+def voxel_regularization(enc, tv: float = 0.0, l1: float = 0.0, kind: str = "l2", tv_xyz=None, reduction: str = "mean") -> Tensor:
+    """The weighted sum of :func:`voxel_terms`, a scalar:
+
+        tv (tv_x + tv_y + tv_z) + l1 l1          or, with tv_xyz = (wx, wy, wz):    wx tv_x + wy tv_y + wz tv_z + l1 l1
+
+    It is ``voxel_terms(enc, kind, reduction)`` dotted with a constant weight tensor that is built once per (weights, device)
+    and kept, so a call makes no host-to-device copy after the first."""
+    wx, wy, wz = (float(tv),) * 3 if tv_xyz is None else (float(w) for w in tv_xyz)
+    return (voxel_terms(enc, kind, reduction) * _voxel_weights(enc, wx, wy, wz, float(l1))).sum()
+
+
+@torch.no_grad()
+def voxel_tv_add_grad_(enc, wx: float, wy: float, wz: float, l1: float = 0.0, kind: str = "huber", dense: bool = True,
+                       reduction: str = "sum") -> None:
+    """Adds the gradient of ``wx tv_x + wy tv_y + wz tv_z + l1 l1`` (:func:`voxel_terms`' terms) into ``enc.params.grad`` in
+    place, without building the loss: one launch, no allocation.  Per element, with ``c_t`` the weight times ``1 / n_t``
+    (times 1 with ``reduction="sum"``), ``k_t = 2 c_t`` and ``P(d) = d`` for ``"l2"``, ``k_t = c_t`` and ``P = rho'`` otherwise:
+
+        gx = (x >= 1 ? P(g - g[x-1]) : 0) - (x + 1 < R_x ? P(g[x+1] - g) : 0)          likewise gy, gz
+        grad += ((k_x gx + k_y gy) + k_z gz) + c_l sign(g)
+
+    ``dense=True`` adds everywhere (``grad is None``: zeros are allocated first).  ``dense=False`` adds only where the gradient
+    is not exactly 0 (a NaN is not 0) and writes nothing elsewhere (``grad is None``: nothing happens): exactly-zero gradients
+    stay exactly zero, so ``FusedAdam(skip_zero_grad=True)`` still skips the voxels no ray touched.
+
+    ``reduction="sum", kind="huber"`` with ``wx = wy = wz = w / 6`` is the form of DVGO's in-place total variation
+    (``total_variation_add_grad``: the clamped differences towards the six neighbours, early in training everywhere,
+    afterwards only where the data term left a gradient).  The ``1/6`` and the clamp are from memory of DVGO's extension,
+    which was not at hand: the formulas above are what is computed, nothing beyond them is claimed.
+
+    CUDA float32 parameters with a contiguous, 16-byte-aligned float32 gradient run on libnerfacc_hip.so
+    (``nfa_voxreg_add_grad``); anything else runs :func:`_voxel_terms_grad_torch` and a masked add in torch, with the same bits."""
+    _voxel_check("voxel_tv_add_grad_", enc, kind, reduction)
+    p = enc.params
+    if p.grad is None:
+        if not dense:
+            return
+        p.grad = torch.zeros_like(p)
+    grad = p.grad
+    w = [float(wx), float(wy), float(wz), float(l1)]
+    if (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.data_ptr() % 16 == 0 and grad.dtype == torch.float32
+            and grad.device == p.device and not grad.is_sparse and grad.is_contiguous() and grad.data_ptr() % 16 == 0):
+        with torch.cuda.device(p.device):
+            B.call("nfa_voxreg_add_grad", B.ptr(p), *_voxreg_args(enc, kind, reduction), (ctypes.c_float * 4)(*w), int(bool(dense)),
+                   B.ptr(grad), B.stream())
+        return
+    G = _voxel_terms_grad_torch(p, torch.tensor(w, dtype=torch.float32, device=p.device), enc.resolution, enc.n_features, kind, reduction)
+    g32 = grad.to(torch.float32)
+    total = g32 + G
+    grad.copy_(total if dense else torch.where(g32 != 0, total, g32))
