@@ -1416,6 +1416,53 @@ int nfa_photometric_bwd(const void *rgb, int32_t elem, const float *pixels, cons
                         int64_t n_rays, int32_t kind, float param, void *g_rgb, nfa_stream_t stream);
 int nfa_photometric_chunk(void);   /* rays per partial pair of the forward's reduction (a constant of the build) */
 
+/* ------------------------------------------------------------------ fused Instant-NGP field query (csrc/ngp_field.hip) */
+
+/* The no-grad query of the reference's NGPRadianceField / NGPDensityField (examples/radiance_fields/ngp.py) as one launch:
+ * positions to box coordinates (or the unit-sphere contraction) and the selector, the 3-D hash grid with 2 features per
+ * level, the base network (2 n_levels -> 64 -> 1 + geo_feat_dim, ReLU), and for nfa_ngp_field the spherical harmonics of
+ * degree 4 and the head network (16 + geo_feat_dim -> 64 -> 64 -> 3).  Nothing is saved for a backward.
+ * nfa_ngp_grid: the level table exactly as the nfa_hashgrid_* entries take it (host arrays, read during the call; same
+ * checks), with the float32 table `params`, n_features = 2, n_levels 1..16 and interp NFA_INTERP_*.
+ * nfa_ngp_input, one of two forms: positions [n_points, 3] world positions (dirs [n_points, 3] raw view directions, read by
+ * nfa_ngp_field only), or positions NULL and ray samples: the midpoint rays_o[r] + (rays_d[r] * (t_start + t_end)) / 2 and
+ * the direction rays_d[r], r = ray_indices[i] (int64, any order; an index outside [0, n_rays) gives a NaN point), the
+ * arithmetic of nfa_sample_positions_fwd bit for bit.
+ * The box: aabb_host (6 floats read during the call) or aabb (6 floats on the device), exactly one; contraction 0: x = (p -
+ * min) / (max - min); 1: the unit-sphere contraction of nfa_sample_positions_fwd.  selector = all(0 < x < 1).
+ * base_image: the forward image of nfa_mlp_pack_weights for (2 n_levels, 1 + geo_feat_dim, 64, 1); head_image: the image
+ * nfa_ngp_pack_head writes.  elem (NFA_ELEM_F16 / NFA_ELEM_BF16) is the type of both images and of every rounding.
+ * Outputs, each optional (NULL), at least one: sigma [n_points] the raw density, rounded to elem as nfa_mlp_fwd stores it,
+ * as elem or widened to float32 (sigma_elem); density [n_points] = selector ? act(sigma + density_bias) : 0 in float32 with
+ * nfa_rendering_from_raw's NFA_ACT_* codes; selector [n_points] bytes (1 = inside); feat [n_points, geo_feat_dim] of type elem (nfa_ngp_density; geo_feat_dim >= 1);
+ * rgb [n_points, 3] the raw colour rounded to elem, as elem or widened (rgb_elem); rgb_act [n_points, 3] float32 =
+ * 1 / (1 + expf(-rgb)).  geo_feat_dim 0..15 (nfa_ngp_field: 1..15).  n_points == 0 returns after the checks. */
+typedef struct nfa_ngp_grid {
+    const float *params;
+    int64_t n_params;
+    int32_t n_levels, n_features, log2_hashmap_size, interp;
+    const float *scales_host;
+    const int32_t *resolutions_host, *sizes_host;
+} nfa_ngp_grid;
+typedef struct nfa_ngp_input {
+    const float *positions, *dirs;
+    const float *rays_o, *rays_d, *t_starts, *t_ends;
+    const int64_t *ray_indices;
+    int64_t n_rays;
+} nfa_ngp_input;
+int nfa_ngp_density(int32_t elem, const nfa_ngp_grid *grid, const void *base_image, int32_t geo_feat_dim, const nfa_ngp_input *in,
+                    int64_t n_points, const float *aabb_host, const float *aabb, int32_t contraction, int32_t density_act,
+                    float density_bias, void *sigma, int32_t sigma_elem, float *density, uint8_t *selector, void *feat, nfa_stream_t stream);
+int nfa_ngp_field(int32_t elem, const nfa_ngp_grid *grid, const void *base_image, const void *head_image, int32_t geo_feat_dim,
+                  const nfa_ngp_input *in, int64_t n_points, const float *aabb_host, const float *aabb, int32_t contraction,
+                  int32_t density_act, float density_bias, void *sigma, int32_t sigma_elem, void *rgb, int32_t rgb_elem, float *density,
+                  uint8_t *selector, float *rgb_act, nfa_stream_t stream);
+/* The head network's forward image for nfa_ngp_field from its float32 masters (W_0 [64, 16 + geo_feat_dim], W_1 [64, 64],
+ * W_2 [3, 64], flat): nfa_mlp_pack_weights' forward image (image_elems = its fwd_elems for (16 + geo_feat_dim, 3, 64, 2)),
+ * except that k-step 1 of layer 0 indexes the rows of the base network's output tile in the permuted k order: position 0
+ * (the density row) and positions beyond geo_feat_dim are zero columns. */
+int nfa_ngp_pack_head(int32_t elem, const float *params, int32_t geo_feat_dim, void *head_image, int64_t image_elems, nfa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,18 @@ class MLPAct(C.Structure):
     _fields_ = [("hidden", _i32), ("output", _i32), ("beta", _f32)]
 
 
+class NGPGrid(C.Structure):
+    """struct nfa_ngp_grid (include/nerfacc_hip.h)."""
+    _fields_ = [("params", _vp), ("n_params", _i64), ("n_levels", _i32), ("n_features", _i32), ("log2_hashmap_size", _i32), ("interp", _i32),
+                ("scales_host", _vp), ("resolutions_host", _vp), ("sizes_host", _vp)]
+
+
+class NGPInput(C.Structure):
+    """struct nfa_ngp_input (include/nerfacc_hip.h)."""
+    _fields_ = [("positions", _vp), ("dirs", _vp), ("rays_o", _vp), ("rays_d", _vp), ("t_starts", _vp), ("t_ends", _vp),
+                ("ray_indices", _vp), ("n_rays", _i64)]
+
+
 # include/nerfacc_hip.h: NFA_MLP_ACT_*
 ACT_CODES = {"None": 0, "ReLU": 1, "LeakyReLU": 2, "Sigmoid": 3, "Tanh": 4, "Softplus": 5, "Exponential": 6}
 
@@ -229,6 +241,10 @@ _SIGS = {
                             _i64, _vp, _vp, _vp, _vp],
     "nfa_photometric_bwd": [_vp, _i32, _vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp],
     "nfa_photometric_chunk": [],
+    "nfa_ngp_density": [_i32, C.POINTER(NGPGrid), _vp, _i32, C.POINTER(NGPInput), _i64, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _vp, _vp, _vp, _vp],
+    "nfa_ngp_field": [_i32, C.POINTER(NGPGrid), _vp, _vp, _i32, C.POINTER(NGPInput), _i64, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _vp, _i32,
+                      _vp, _vp, _vp, _vp],
+    "nfa_ngp_pack_head": [_i32, _vp, _i32, _vp, _i64, _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],

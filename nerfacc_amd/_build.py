@@ -17,13 +17,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libnerfacc_hip.so")
-SOURCES = ["grid.hip", "walk.hip", "gridupd.hip", "traverse2.hip", "segscan.hip", "pdf.hip", "camera.hip", "pack.hip", "encoding.hip", "samples.hip", "rays.hip", "planes.hip", "planereg.hip", "vmgrid.hip", "vmreg.hip", "voxgrid.hip", "voxreg.hip", "sinenc.hip", "mlp.hip", "mlp_stream.hip", "optim.hip", "photo.hip"]
+SOURCES = ["grid.hip", "walk.hip", "gridupd.hip", "traverse2.hip", "segscan.hip", "pdf.hip", "camera.hip", "pack.hip", "encoding.hip", "samples.hip", "rays.hip", "planes.hip", "planereg.hip", "vmgrid.hip", "vmreg.hip", "voxgrid.hip", "voxreg.hip", "sinenc.hip", "mlp.hip", "mlp_stream.hip", "optim.hip", "photo.hip", "ngp_field.hip"]
 ARCH = os.environ.get("NERFACC_AMD_ARCH", "gfx950")
 # -ffp-contract=off: the traversal must not fuse a*b+c (floating-point contract)
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"--offload-arch={ARCH}",
          "-Wall", "-Wno-unused-function"] + os.environ.get("NERFACC_AMD_EXTRA_FLAGS", "").split()  # tuning experiments
-
-
 def hipcc() -> str | None:
     for cand in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
         if cand and os.path.exists(cand):

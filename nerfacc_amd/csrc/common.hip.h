@@ -299,6 +299,19 @@ static bool dispatch_elem(int32_t elem, F &&f)
     return true;
 }
 
+// The density activations of raw field outputs (NFA_ACT_*), on z = raw + bias: the one copy that the rendering passes from raw
+// outputs (segscan.hip: RawAct) and the fused field query (ngp_field.hip) both call.
+__device__ __forceinline__ float raw_density_act(int32_t code, float z)
+{
+    switch (code) {
+    case NFA_ACT_TRUNC_EXP:
+    case NFA_ACT_EXP: return expf(z);
+    case NFA_ACT_RELU: return z < 0.0f ? 0.0f : z;
+    case NFA_ACT_SOFTPLUS: return z > 20.0f ? z : log1pf(expf(z));   // torch's defaults: beta 1, threshold 20
+    default: return z;
+    }
+}
+
 template <bool NT = false>
 __device__ __forceinline__ void store_f4(float *p, float a, float b, float c, float d)
 {

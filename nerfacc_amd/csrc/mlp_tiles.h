@@ -367,9 +367,10 @@ __device__ __forceinline__ void init_acc(f32x16 &a, bool has_bias, const float *
 
 // A wave's 32 x 32 accumulator tile (row = column of the output matrix, column = point) to memory through its LDS staging
 // tile, so that stores run along the output rows: columns col0 .. col0+ncols-1 of rows row0 .. row0+nrows-1 of out [*, ld].
+// They are rows tile_row0 .. of the tile (0 for every pass but the fused field query, whose geometry feature starts at row 1).
 template <class E>
 __device__ __forceinline__ void stage_store(const f32x16 &acc, float *st, void *out, bool out_f32, int64_t row0, int nrows, int ld,
-                                            int col0, int ncols, int lane)
+                                            int col0, int ncols, int lane, int tile_row0 = 0)
 {
     const int r = lane & 31, h = lane >> 5;
 #pragma unroll
@@ -380,7 +381,7 @@ __device__ __forceinline__ void stage_store(const f32x16 &acc, float *st, void *
     const int total = nrows * ncols;
     for (int i = lane; i < total; i += NFA_WAVE) {
         const int pr = i / ncols, c = i - pr * ncols;
-        const float v = st[pr * STAGE_LD + c];
+        const float v = st[pr * STAGE_LD + tile_row0 + c];
         const int64_t gi = (row0 + pr) * ld + col0 + c;
         if (out_f32) static_cast<float *>(out)[gi] = v;
         else static_cast<uint16_t *>(out)[gi] = (uint16_t)half_bits<E>(v);

@@ -31,6 +31,21 @@ __device__ __forceinline__ void box_resolve(const SampleBox &b, float lo[3], flo
     }
 }
 
+// o[r], d[r]; an index outside [0, n_rays) reads row 0 and yields NaN rows (never an address outside the arrays)
+__device__ __forceinline__ void ray_rows(const float *__restrict__ o, const float *__restrict__ d, int64_t r, int64_t n_rays,
+                                         float ro[3], float rd[3])
+{
+    const bool ok = (uint64_t)r < (uint64_t)n_rays;
+    const int64_t b = ok ? 3 * r : 0;
+    const float bad = __builtin_nanf("");
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float vo = o[b + k], vd = d[b + k];
+        ro[k] = ok ? vo : bad;
+        rd[k] = ok ? vd : bad;
+    }
+}
+
 __device__ __forceinline__ void sample_point(const float o[3], const float d[3], float ts, float te, float p[3])
 {
     const float s = ts + te;

@@ -1785,16 +1785,7 @@ struct RawAct {
     int32_t mask_vec;      // mask is 4-byte aligned
     int32_t dens, col;     // NFA_ACT_* / NFA_RGB_ACT_*
     float bias;
-    __device__ __forceinline__ float density(float z) const
-    {
-        switch (dens) {
-        case NFA_ACT_TRUNC_EXP:
-        case NFA_ACT_EXP: return expf(z);
-        case NFA_ACT_RELU: return z < 0.0f ? 0.0f : z;
-        case NFA_ACT_SOFTPLUS: return z > 20.0f ? z : log1pf(expf(z));   // torch's defaults: beta 1, threshold 20
-        default: return z;
-        }
-    }
+    __device__ __forceinline__ float density(float z) const { return raw_density_act(dens, z); }
     // d density / d z, given the density itself
     __device__ __forceinline__ float density_grad(float z, float s) const
     {
