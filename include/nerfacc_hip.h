@@ -1463,6 +1463,53 @@ int nfa_ngp_field(int32_t elem, const nfa_ngp_grid *grid, const void *base_image
  * (the density row) and positions beyond geo_feat_dim are zero columns. */
 int nfa_ngp_pack_head(int32_t elem, const float *params, int32_t geo_feat_dim, void *head_image, int64_t image_elems, nfa_stream_t stream);
 
+/* The same field with grad: one launch forward, one launch backward (csrc/ngp_field.hip, "Training").
+ * nfa_ngp_train_fwd is nfa_ngp_field (full != 0) or nfa_ngp_density (full == 0; head_image is not read, feat is not written)
+ * bit for bit, with the same arguments and checks, and additionally stores what the backward and nfa_mlp_bwd_weights read, all of
+ * type elem: enc [n_points, 2 n_levels] the encoded row (the base network's x; 16-byte aligned), base_hidden [1, n_points, 64]
+ * and head_hidden [2, n_points, 64] the activations as nfa_mlp_fwd saves them (16-byte aligned), base_out [n_points, 1 +
+ * geo_feat_dim] the base network's output, head_x [n_points, 16 + geo_feat_dim] the head's input (harmonics, then the geometry
+ * feature).  head_x and head_hidden are used only when full.
+ * nfa_ngp_train_bwd reads them, the same grid, input and box, and the gradients of the outputs; it writes each network's dz
+ * [n_hidden, n_points, 64] (16-byte aligned) and dz_out [n_points, n_out] of type elem, which nfa_mlp_bwd_weights takes next to
+ * (enc, base_hidden) and (head_x, head_hidden), and adds the table gradient into grad_table [n_params] float32 with float atomics
+ * (zeroed by the caller; NULL: no scatter).  Gradients towards positions and directions are not formed.
+ * mode NFA_NGP_GRAD_RAW: g_rgb [n_points, 3] and g_sigma [n_points] are the gradients of the raw outputs, float32 or elem
+ * (g_*_elem), each rounded once to elem.  NFA_NGP_GRAD_ACTIVATED: they are the gradients of rgb_act and density (float32):
+ * g_rgb * s (1 - s) with s = 1 / (1 + expf(-raw_rgb)), raw_rgb [n_points, 3] of type elem being the forward's `rgb`, and
+ * selector ? g_sigma * act'(sigma + density_bias) : 0 with sigma = base_out[:, 0] (trunc_exp: expf(min(z, 15))), float32
+ * products rounded once.  A NULL g_rgb or g_sigma is a zero gradient.  The images are those of nfa_ngp_pack_bwd. */
+#define NFA_NGP_GRAD_RAW 0
+#define NFA_NGP_GRAD_ACTIVATED 1
+typedef struct nfa_ngp_saved {
+    void *enc, *base_hidden, *base_out, *head_x, *head_hidden;
+} nfa_ngp_saved;
+typedef struct nfa_ngp_grads {
+    const void *g_rgb;
+    int32_t g_rgb_elem;
+    const void *g_sigma;
+    int32_t g_sigma_elem;
+    const void *raw_rgb;
+    void *head_dz, *head_dz_out, *base_dz, *base_dz_out;
+    float *grad_table;
+} nfa_ngp_grads;
+int nfa_ngp_train_fwd(int32_t elem, int32_t full, const nfa_ngp_grid *grid, const void *base_image, const void *head_image,
+                      int32_t geo_feat_dim, const nfa_ngp_input *in, int64_t n_points, const float *aabb_host, const float *aabb,
+                      int32_t contraction, int32_t density_act, float density_bias, const nfa_ngp_saved *save, void *sigma,
+                      int32_t sigma_elem, void *rgb, int32_t rgb_elem, float *density, uint8_t *selector, float *rgb_act, nfa_stream_t stream);
+int nfa_ngp_train_bwd(int32_t elem, int32_t full, int32_t mode, const nfa_ngp_grid *grid, const void *base_bwd_image,
+                      const void *head_bwd_image, int32_t geo_feat_dim, const nfa_ngp_input *in, int64_t n_points, const float *aabb_host,
+                      const float *aabb, int32_t contraction, int32_t density_act, float density_bias, const nfa_ngp_saved *saved,
+                      const nfa_ngp_grads *grads, nfa_stream_t stream);
+/* The backward images of nfa_ngp_train_bwd from a network's float32 masters, image_elems = nfa_mlp_pack_weights' bwd_elems of the
+ * shape.  net NFA_NGP_NET_BASE: (2 n_levels, 1 + geo_feat_dim, 64, 1), its backward image with the last layer in the permuted k
+ * order as well.  NFA_NGP_NET_HEAD: (16 + geo_feat_dim, 3, 64, 2; n_levels is not read), its backward image with layer 0's rows
+ * being rows of the base network's output tile: row 0 zero, rows 1 .. geo_feat_dim the geometry feature's columns of W_0. */
+#define NFA_NGP_NET_BASE 0
+#define NFA_NGP_NET_HEAD 1
+int nfa_ngp_pack_bwd(int32_t elem, int32_t net, const float *params, int32_t n_levels, int32_t geo_feat_dim, void *image,
+                     int64_t image_elems, nfa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

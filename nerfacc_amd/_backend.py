@@ -58,6 +58,17 @@ class NGPGrid(C.Structure):
                 ("scales_host", _vp), ("resolutions_host", _vp), ("sizes_host", _vp)]
 
 
+class NGPSaved(C.Structure):
+    """struct nfa_ngp_saved (include/nerfacc_hip.h)."""
+    _fields_ = [("enc", _vp), ("base_hidden", _vp), ("base_out", _vp), ("head_x", _vp), ("head_hidden", _vp)]
+
+
+class NGPGrads(C.Structure):
+    """struct nfa_ngp_grads (include/nerfacc_hip.h)."""
+    _fields_ = [("g_rgb", _vp), ("g_rgb_elem", _i32), ("g_sigma", _vp), ("g_sigma_elem", _i32), ("raw_rgb", _vp), ("head_dz", _vp),
+                ("head_dz_out", _vp), ("base_dz", _vp), ("base_dz_out", _vp), ("grad_table", _vp)]
+
+
 class NGPInput(C.Structure):
     """struct nfa_ngp_input (include/nerfacc_hip.h)."""
     _fields_ = [("positions", _vp), ("dirs", _vp), ("rays_o", _vp), ("rays_d", _vp), ("t_starts", _vp), ("t_ends", _vp),
@@ -245,6 +256,11 @@ _SIGS = {
     "nfa_ngp_field": [_i32, C.POINTER(NGPGrid), _vp, _vp, _i32, C.POINTER(NGPInput), _i64, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _vp, _i32,
                       _vp, _vp, _vp, _vp],
     "nfa_ngp_pack_head": [_i32, _vp, _i32, _vp, _i64, _vp],
+    "nfa_ngp_pack_bwd": [_i32, _i32, _vp, _i32, _i32, _vp, _i64, _vp],
+    "nfa_ngp_train_fwd": [_i32, _i32, C.POINTER(NGPGrid), _vp, _vp, _i32, C.POINTER(NGPInput), _i64, _vp, _vp, _i32, _i32, _f32,
+                          C.POINTER(NGPSaved), _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp],
+    "nfa_ngp_train_bwd": [_i32, _i32, _i32, C.POINTER(NGPGrid), _vp, _vp, _i32, C.POINTER(NGPInput), _i64, _vp, _vp, _i32, _i32, _f32,
+                          C.POINTER(NGPSaved), C.POINTER(NGPGrads), _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],

@@ -312,6 +312,19 @@ __device__ __forceinline__ float raw_density_act(int32_t code, float z)
     }
 }
 
+// d act / d z given z and s = act(z): the derivative forms of the rendering backward from raw outputs, which the fused field's
+// training backward (ngp_field.hip) multiplies in too.  trunc_exp: exp(min(z, 15)), ref: examples/radiance_fields/ngp.py:23-36.
+__device__ __forceinline__ float raw_density_grad(int32_t code, float z, float s)
+{
+    switch (code) {
+    case NFA_ACT_TRUNC_EXP: return expf(fminf(z, 15.0f));
+    case NFA_ACT_EXP: return s;
+    case NFA_ACT_RELU: return z > 0.0f ? 1.0f : 0.0f;
+    case NFA_ACT_SOFTPLUS: return z > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-z));
+    default: return 1.0f;
+    }
+}
+
 template <bool NT = false>
 __device__ __forceinline__ void store_f4(float *p, float a, float b, float c, float d)
 {

@@ -158,6 +158,18 @@ template <int D> struct Corner {
     }
 };
 
+// One corner's share of the table gradient: w_c * dL/dy added to entry e of a zeroed float32 table gradient with no-return
+// float atomics, for the fused field's training backward (ngp_field.hip).  It is hashgrid_bwd_kernel's statement word for word;
+// that kernel keeps its own copy, because calling this one swaps the operands of its commutative multiplies in the generated
+// code, and encoding.hip's device code is to stay what it is.
+template <int F>
+__device__ __forceinline__ void scatter_corner(float *g_params, uint32_t e, const float wc, const FVec<F> g)
+{
+    float *dst = g_params + (size_t)e * F;
+#pragma unroll
+    for (int j = 0; j < F; ++j) unsafeAtomicAdd(dst + j, wc * g.v[j]);
+}
+
 // ---------------------------------------------------------------- spherical harmonics
 // tiny-cuda-nn's convention: directions d in [0, 1]^3, u = 2 d - 1 (not renormalised); degree^2 outputs per point.
 #define SH_C0 0.28209479177387814f

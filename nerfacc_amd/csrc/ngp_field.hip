@@ -29,6 +29,27 @@
 // are its bits; the head sums its second k-step in another order, so the raw colour may differ in the last bit of a float32 sum.
 //
 // EXEC is all ones around every MFMA: a partial tile clamps the point index of its loads and masks only its stores.
+//
+// Training (ngp_train_fwd_kernel, ngp_train_bwd_kernel): the same layout each way, one launch each.
+//   forward    ngp_forward<TRAIN = true>: the query's arithmetic (one function, so the outputs are the query's bits) plus five
+//              stores in the formats nfa_mlp_bwd_data / nfa_mlp_bwd_weights read: the encoded row [N, 2 n_levels] straight out
+//              of grid_frag's operand registers (a lane's four levels of a k-step are 16 contiguous bytes of its row), the base
+//              hidden [1, N, 64] and the head hidden [2, N, 64] (store_tile_row), the base output tile's rows 0 .. G [N, 1 + G]
+//              and the head's input [N, 16 + G] = harmonics, geometry feature (stage_store).  Nothing else is saved.
+//   backward   dZ_L of the head = the colour gradient (activated mode: g * s (1 - s), s from the stored raw colour) rounded once,
+//              natural k order, lane half 0; mlp_bwd_data_kernel's chain on the head's backward image with the saved masks;
+//              layer 0's product is ONE 32 x 32 tile whose rows are the base output tile's rows (ngp_bwd_pack_kernel: row 0
+//              zero, rows 1 .. G the geometry feature's columns of W_0; the harmonics' rows are not computed).  The density
+//              gradient (activated mode: g * act'(raw + bias), 0 outside the box) goes into row 0, register 0 of lane half 0;
+//              the tile rounded once is the base network's dZ_L and acc_frag of it the B operand of the base backward, whose
+//              last layer is therefore packed in the permuted k order: no LDS exchange, the forward's trick mirrored.  The last
+//              product leaves dEnc in accumulators: register 4 g + 2 j + f of lane half h is feature f of level 4 g + 2 h + j,
+//              so each lane half owns 8 of 16 levels.  Each value is rounded once (the composed chain's hash grid reads a half
+//              grad_y) and scattered with hashgrid_bwd_kernel's arithmetic: locate, the corner weights and corner_index from
+//              the position again, scatter_corner's float atomics (encoding_dev.h).  The weight gradients stay nfa_mlp_bwd_weights on what both
+//              launches wrote (hidden, dz, dz_out), so no gradient between the networks ever exists in memory.
+// The k-steps' gathers and the saved stores do not overlap: the encoded row is stored from the operand registers after the
+// gathers have landed and before the first MFMA, and the staging tile is the query's own.
 #include "encoding_dev.h"
 #include "mlp_tiles.h"
 #include "samples.h"
@@ -63,6 +84,18 @@ struct NgpArgs {
     float *density, *rgb_act;
     uint16_t *feat;
     uint8_t *sel;
+    // training: what the forward saves and the backward reads, all of the networks' type (NULL in the query)
+    uint16_t *s_enc, *s_bhid, *s_bout, *s_hx, *s_hhid;
+};
+
+// The training backward's own operands.  The images of NgpArgs are the backward images there.
+struct NgpGrads {
+    const void *g_rgb, *g_sigma;   // [N, 3], [N]; NULL: zero
+    int32_t g_rgb_f32, g_sigma_f32;
+    int32_t activated;             // the gradients are those of the activated outputs
+    const uint16_t *raw_rgb;       // [N, 3] the raw colour as the forward stored it (activated mode)
+    uint16_t *hdz, *hdzo, *bdz, *bdzo;
+    float *grad_table;             // zeroed by the caller; NULL: no scatter
 };
 
 // The B fragment of k-step q of the base network's first layer: levels 8 q + 4 h .. + 3 of the point at x (in [0, 1]^3), F = 2.
@@ -117,9 +150,39 @@ __device__ __forceinline__ void zero_acc(f32x16 &a)
     for (int i = 0; i < 16; ++i) a[i] = 0.f;
 }
 
-// RAYS: the ray-sample input form.  FULL: density and colour; otherwise the kernel stops after the base network.  I: NFA_INTERP_*.
-template <class E, bool RAYS, bool FULL, int I>
-__global__ NFA_NO_PACKED_F32 __launch_bounds__(MLP_WAVES * NFA_WAVE) void ngp_field_kernel(const NgpArgs a)
+// row p of a saved [*, 64] activation matrix from the fragments relu_frags made (what FusedMLP's forward saves)
+__device__ __forceinline__ void save_hidden(uint16_t *m, int64_t p, bool live, int h, const nfa_v4u (&hf)[4])
+{
+    if (live) {
+        store_tile_row<64>(m, p, 0, h, hf[0], hf[1]);
+        store_tile_row<64>(m, p, 1, h, hf[2], hf[3]);
+    }
+}
+
+// The point pc: box coordinates into x (and the raw direction into dir); returns the selector.
+template <bool RAYS, bool DIRS>
+__device__ __forceinline__ bool ngp_point(const NgpArgs &a, int64_t pc, const float *lo, const float *ext, float *x, float *dir)
+{
+    if constexpr (RAYS) {
+        float ro[3];
+        ray_rows(a.o, a.d, a.ri[pc], a.n_rays, ro, dir);
+        sample_point(ro, dir, a.ts[pc], a.te[pc], x);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            x[k] = a.x[3 * pc + k];
+            if constexpr (DIRS) dir[k] = a.dirs[3 * pc + k];
+        }
+    }
+    if (a.contract) sample_normalise<SP_SPHERE>(x, lo, ext);
+    else sample_normalise<SP_AABB>(x, lo, ext);
+    return sample_inside(x);
+}
+
+// RAYS: the ray-sample input form.  FULL: density and colour; otherwise the pass stops after the base network.  I: NFA_INTERP_*.
+// TRAIN: also store what the backward needs (header).
+template <class E, bool RAYS, bool FULL, int I, bool TRAIN>
+__device__ __forceinline__ void ngp_forward(const NgpArgs &a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char ngp_lds[];
     nfa_v4u *bimg = reinterpret_cast<nfa_v4u *>(ngp_lds);
@@ -138,26 +201,30 @@ __global__ NFA_NO_PACKED_F32 __launch_bounds__(MLP_WAVES * NFA_WAVE) void ngp_fi
         const int64_t p = tile * 32 + r, pc = p < N ? p : N - 1;
         // ---- the point: world position (and direction), then box coordinates and the selector
         float x[3], dir[3] = {0.f, 0.f, 0.f};
-        if constexpr (RAYS) {
-            float ro[3];
-            ray_rows(a.o, a.d, a.ri[pc], a.n_rays, ro, dir);
-            sample_point(ro, dir, a.ts[pc], a.te[pc], x);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                x[k] = a.x[3 * pc + k];
-                if constexpr (FULL) dir[k] = a.dirs[3 * pc + k];
-            }
-        }
-        if (a.contract) sample_normalise<SP_SPHERE>(x, lo, ext);
-        else sample_normalise<SP_AABB>(x, lo, ext);
-        const bool inside = sample_inside(x);
+        const bool inside = ngp_point<RAYS, FULL>(a, pc, lo, ext, x, dir);
         // ---- hash grid into the operand registers of both k-steps, then the base network
         nfa_v4u b[2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             b[q] = nfa_v4u{0u, 0u, 0u, 0u};
             if (q < kq0) b[q] = grid_frag<E, I>(a.T, a.table, x, q, h);
+        }
+        if constexpr (TRAIN) {   // the encoded row: a dword per level, the lane's four levels of a k-step side by side
+            const int nl = a.T.n_levels;
+            uint32_t *row = reinterpret_cast<uint32_t *>(a.s_enc) + p * nl;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int l0 = 8 * q + 4 * h;
+                if (q < kq0 && p < N) {
+                    if ((nl & 3) == 0) {   // rows of 16 n_levels / 4 bytes: one 16-byte store
+                        if (l0 < nl) *reinterpret_cast<nfa_v4u *>(row + l0) = b[q];
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (l0 + i < nl) row[l0 + i] = b[q][i];
+                    }
+                }
+            }
         }
         f32x16 acc[2];
         nfa_v4u hf[4];
@@ -171,6 +238,7 @@ __global__ NFA_NO_PACKED_F32 __launch_bounds__(MLP_WAVES * NFA_WAVE) void ngp_fi
             }
         }
         relu_frags<E>(acc, hf);
+        if constexpr (TRAIN) save_hidden(a.s_bhid, p, p < N, h, hf);
         f32x16 o;
         zero_acc(o);
 #pragma unroll
@@ -191,6 +259,7 @@ __global__ NFA_NO_PACKED_F32 __launch_bounds__(MLP_WAVES * NFA_WAVE) void ngp_fi
             }
         }
         if (a.feat) stage_store<E>(o, st, a.feat, false, row0, nrows, a.G, 0, a.G, lane, 1);   // rows 1 .. G of the tile
+        if constexpr (TRAIN) stage_store<E>(o, st, a.s_bout, false, row0, nrows, 1 + a.G, 0, 1 + a.G, lane);
         if constexpr (FULL) {
             // ---- head layer 0: k-step 0 the harmonics of (d + 1) / 2 as tcnn maps it, k-step 1 the base tile's rows 0 .. 15
             float sh[16];
@@ -207,6 +276,17 @@ __global__ NFA_NO_PACKED_F32 __launch_bounds__(MLP_WAVES * NFA_WAVE) void ngp_fi
                 bs[d] = pack_halves<E>(s0, s1);
             }
             const nfa_v4u bg = acc_frag<E>(o, 0);
+            if constexpr (TRAIN) {   // the head's input row: the harmonics (a tile of their own: row i = harmonic i), then rows 1 .. G
+                f32x16 ht;
+                zero_acc(ht);
+#pragma unroll
+                for (int reg = 0; reg < 8; ++reg) {
+                    const int i0 = (reg & 3) + 8 * (reg >> 2);   // acc_row(reg, 0); lane half 1 holds row i0 + 4
+                    ht[reg] = sel_mask(h ? ~0u : 0u, sh[i0 + 4], sh[i0]);
+                }
+                stage_store<E>(ht, st, a.s_hx, false, row0, nrows, 16 + a.G, 0, 16, lane);
+                stage_store<E>(o, st, a.s_hx, false, row0, nrows, 16 + a.G, 16, a.G, lane, 1);
+            }
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
                 zero_acc(acc[m]);
@@ -214,6 +294,7 @@ __global__ NFA_NO_PACKED_F32 __launch_bounds__(MLP_WAVES * NFA_WAVE) void ngp_fi
                 acc[m] = mfma<E>(himg[(m * 2 + 1) * 64 + lane], bg, acc[m]);
             }
             relu_frags<E>(acc, hf);
+            if constexpr (TRAIN) save_hidden(a.s_hhid, p, p < N, h, hf);
             int off16 = 2 * 2 * 64;
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
@@ -222,6 +303,7 @@ __global__ NFA_NO_PACKED_F32 __launch_bounds__(MLP_WAVES * NFA_WAVE) void ngp_fi
                 for (int q = 0; q < 4; ++q) acc[m] = mfma<E>(himg[off16 + (m * 4 + q) * 64 + lane], hf[q], acc[m]);
             }
             relu_frags<E>(acc, hf);
+            if constexpr (TRAIN) save_hidden(a.s_hhid + N * 64, p, p < N, h, hf);
             off16 += 2 * 4 * 64;
             zero_acc(o);
 #pragma unroll
@@ -236,6 +318,185 @@ __global__ NFA_NO_PACKED_F32 __launch_bounds__(MLP_WAVES * NFA_WAVE) void ngp_fi
                 stage_store<E>(o, st, a.rgb_act, true, row0, nrows, 3, 0, 3, lane);
             }
         }
+    }
+}
+
+template <class E, bool RAYS, bool FULL, int I>
+__global__ NFA_NO_PACKED_F32 __launch_bounds__(MLP_WAVES * NFA_WAVE) void ngp_field_kernel(const NgpArgs a)
+{
+    ngp_forward<E, RAYS, FULL, I, false>(a);
+}
+
+template <class E, bool RAYS, bool FULL, int I>
+__global__ NFA_NO_PACKED_F32 __launch_bounds__(MLP_WAVES * NFA_WAVE) void ngp_train_fwd_kernel(const NgpArgs a)
+{
+    ngp_forward<E, RAYS, FULL, I, true>(a);
+}
+
+// dZ = dH * (H > 0) with the saved activations, rounded: the next product's B fragments and a row of the network's dz
+template <class E>
+__device__ __forceinline__ void mask_frags(f32x16 (&acc)[2], nfa_v4u (&df)[4], const uint16_t *hid, uint16_t *dz, int64_t pc, int64_t p,
+                                           bool live, int h)
+{
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        mask_tile_row<E, 64>(acc[t], hid, pc, t, h);
+        df[2 * t] = acc_frag<E>(acc[t], 0);
+        df[2 * t + 1] = acc_frag<E>(acc[t], 1);
+        if (live) store_tile_row<64>(dz, p, t, h, df[2 * t], df[2 * t + 1]);
+    }
+}
+
+// The training backward (header).  a.base_img / a.head_img: the images of ngp_bwd_pack_kernel, blocks in Shape::bwd_off's order:
+// head W_0^T (4 blocks, one row tile), W_1^T (8), W_2^T (2); base W_0^T (4), W_1^T (2).
+template <class E, bool RAYS, bool FULL, int I>
+__global__ NFA_NO_PACKED_F32 __launch_bounds__(MLP_WAVES * NFA_WAVE) void ngp_train_bwd_kernel(const NgpArgs a, const NgpGrads g)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ngp_lds[];
+    nfa_v4u *bimg = reinterpret_cast<nfa_v4u *>(ngp_lds);
+    const int64_t b16 = a.base_elems / 8, h16 = FULL ? a.head_elems / 8 : 0;
+    nfa_v4u *himg = bimg + b16;
+    for (int64_t i = threadIdx.x; i < b16; i += blockDim.x) bimg[i] = reinterpret_cast<const nfa_v4u *>(a.base_img)[i];
+    for (int64_t i = threadIdx.x; i < h16; i += blockDim.x) himg[i] = reinterpret_cast<const nfa_v4u *>(a.head_img)[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    float *st = reinterpret_cast<float *>(himg + h16) + wave * 32 * STAGE_LD;
+    float lo[3], ext[3];
+    box_resolve(a.box, lo, ext);
+    const int64_t N = a.N, n_tiles = (N + 31) / 32;
+    const int G = a.G, nl = a.T.n_levels;
+    for (int64_t tile = (int64_t)blockIdx.x * MLP_WAVES + wave; tile < n_tiles; tile += (int64_t)gridDim.x * MLP_WAVES) {
+        const int64_t p = tile * 32 + r, pc = p < N ? p : N - 1;
+        const bool live = p < N;
+        float x[3], dir[3];
+        const bool inside = ngp_point<RAYS, false>(a, pc, lo, ext, x, dir);
+        // ---- the density gradient at the raw value: a float32 product, rounded with the tile below
+        float gs = 0.f;
+        if (g.g_sigma) gs = load_elem<E>(g.g_sigma, g.g_sigma_f32 != 0, pc);
+        if (g.activated) {
+            const float z = half_value<E>(a.s_bout[pc * (1 + G)]) + a.bias;
+            const float d = gs * raw_density_grad(a.act, z, raw_density_act(a.act, z));
+            gs = inside ? d : 0.0f;   // a select, as the forward's
+        }
+        f32x16 o, acc[2];
+        nfa_v4u df[4];
+        zero_acc(o);
+        if constexpr (FULL) {
+            // ---- the head: dZ_L [3] in natural k order is elements 0 .. 2 of lane half 0
+            uint32_t w0 = 0u, w1 = 0u;
+            if (g.g_rgb) {
+                float c[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    c[k] = load_elem<E>(g.g_rgb, g.g_rgb_f32 != 0, 3 * pc + k);
+                    if (g.activated) {
+                        const float s = 1.0f / (1.0f + expf(-half_value<E>(g.raw_rgb[3 * pc + k])));
+                        c[k] = c[k] * (s * (1.0f - s));
+                    }
+                }
+                w0 = pack_halves<E>(c[0], c[1]);
+                w1 = half_bits<E>(c[2]);
+            }
+            if (h == 0 && live) {
+                g.hdzo[3 * p] = (uint16_t)w0;
+                g.hdzo[3 * p + 1] = (uint16_t)(w0 >> 16);
+                g.hdzo[3 * p + 2] = (uint16_t)w1;
+            }
+            const nfa_v4u b = {h ? 0u : w0, h ? 0u : w1, 0u, 0u};
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                zero_acc(acc[m]);
+                acc[m] = mfma<E>(himg[(12 + m) * 64 + lane], b, acc[m]);
+            }
+            mask_frags<E>(acc, df, a.s_hhid + N * 64, g.hdz + N * 64, pc, p, live, h);
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                zero_acc(acc[m]);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[m] = mfma<E>(himg[(4 + m * 4 + q) * 64 + lane], df[q], acc[m]);
+            }
+            mask_frags<E>(acc, df, a.s_hhid, g.hdz, pc, p, live, h);
+            // rows of the base output tile: row 0 an exact zero, rows 1 .. G the geometry feature's gradient
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o = mfma<E>(himg[q * 64 + lane], df[q], o);
+        }
+        // ---- the base network: dZ_L = the tile with the density gradient in row 0, rounded once
+        o[0] = h ? o[0] : gs;
+        const int64_t row0 = tile * 32;
+        const int nrows = (int)(N - row0 < 32 ? N - row0 : 32);
+        stage_store<E>(o, st, g.bdzo, false, row0, nrows, 1 + G, 0, 1 + G, lane);
+        const nfa_v4u bg = acc_frag<E>(o, 0);
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            zero_acc(acc[m]);
+            acc[m] = mfma<E>(bimg[(4 + m) * 64 + lane], bg, acc[m]);
+        }
+        mask_frags<E>(acc, df, a.s_bhid, g.bdz, pc, p, live, h);
+        if (!g.grad_table) continue;   // (wave-uniform)
+        f32x16 de;
+        zero_acc(de);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) de = mfma<E>(bimg[q * 64 + lane], df[q], de);
+        // ---- scatter: register 4 gq + 2 j + f is feature f of level 4 gq + 2 h + j
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int la = 4 * gq + j;   // lane half 0's level; lane half 1 takes la + 2
+                if (la < nl) {               // wave-uniform
+                    const bool upper = la + 2 < nl;
+                    const LevelRef A(a.T, la), U(a.T, upper ? la + 2 : la);
+                    LevelRef L = A;
+                    if (h) L = U;
+                    FVec<2> gv;
+                    gv.v[0] = half_value<E>(half_bits<E>(de[4 * gq + 2 * j]));
+                    gv.v[1] = half_value<E>(half_bits<E>(de[4 * gq + 2 * j + 1]));
+                    if (live && (h == 0 || upper)) {
+                        Cell<3> c = locate<3>(x, L.scale);
+                        if constexpr (I == NFA_INTERP_SMOOTHSTEP) {
+                            float d1[3], d2[3];
+                            smoothstep(c, d1, d2);
+                        }
+#pragma unroll
+                        for (int corner = 0; corner < 8; ++corner)
+                            scatter_corner<2>(g.grad_table, L.offset + corner_index(c, corner, L), Corner<3>(c, corner).first_order(), gv);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// The backward images of the training backward: mlp_pack_kernel's backward image (A = W_l^T, rows = the layer's inputs, k = its
+// outputs), except that
+//   head (G >= 1)  layer 0's rows are ROWS OF THE BASE OUTPUT TILE: row i holds column 16 + i - 1 of W_0 for i = 1 .. G and zero
+//                  elsewhere (row 0 is the density row; the harmonics' columns are not packed);
+//   base (G < 0)   the last layer is in the permuted k order too: its B operand is acc_frag of a tile, not a row from memory.
+template <class E>
+__global__ __launch_bounds__(256) void ngp_bwd_pack_kernel(Shape S, int G, const float *__restrict__ params, uint16_t *__restrict__ img,
+                                                           int64_t elems)
+{
+    const int L = S.layers();
+    const bool head = G >= 0;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < elems; e += (int64_t)gridDim.x * 256) {
+        int l = 0;
+        int64_t off = 0;
+        for (;; ++l) {
+            const int64_t sz = (int64_t)S.bwd_mt(l) * S.bwd_kq(l) * 512;
+            if (e < off + sz || l == L - 1) break;
+            off += sz;
+        }
+        const int64_t local = e - off;
+        const int j = (int)(local & 7), lane = (int)((local >> 3) & 63), hh = lane >> 5;
+        const int64_t blk = local >> 9;
+        const int KQ = S.bwd_kq(l), q = (int)(blk % KQ), m = (int)(blk / KQ);
+        const int k = 16 * q + kpos(!head || l != L - 1, hh, j);
+        int row = 32 * m + (lane & 31);
+        if (head && l == 0) row = row >= 1 && row <= G ? 16 + row - 1 : -1;
+        const int in = S.in_dim(l), out = S.out_dim(l);
+        float v = 0.f;
+        if (row >= 0 && row < in && k < out) v = params[S.master_off(l) + (int64_t)k * in + row];
+        img[e] = (uint16_t)half_bits<E>(v);
     }
 }
 
@@ -293,9 +554,13 @@ struct NgpOutputs {
     uint8_t *selector;
 };
 
+// The three passes behind the entries.  save: the training forward's stores and the backward's reads; grads (with mode): the
+// backward, whose images are the backward images and which has no outputs of the query's kind.
 int ngp_query(const char *who, bool full, int32_t elem, const nfa_ngp_grid *grid, const void *base_image, const void *head_image,
               int32_t G, const nfa_ngp_input *in, int64_t N, const float *aabb_host, const float *aabb, int32_t contraction,
-              int32_t density_act, float density_bias, const NgpOutputs &out, nfa_stream_t stream)
+              int32_t density_act, float density_bias, const NgpOutputs &out, nfa_stream_t stream, bool train = false,
+              const nfa_ngp_saved *save = nullptr, bool backward = false, int32_t mode = NFA_NGP_GRAD_RAW,
+              const nfa_ngp_grads *grads = nullptr)
 {
     NFA_REQUIRE(elem == NFA_ELEM_F16 || elem == NFA_ELEM_BF16, "%s: elem %d: the networks' type is NFA_ELEM_F16 or NFA_ELEM_BF16", who, elem);
     NFA_REQUIRE(grid && in, "%s: the grid or the input descriptor is null", who);
@@ -318,19 +583,59 @@ int ngp_query(const char *who, bool full, int32_t elem, const nfa_ngp_grid *grid
     const bool rays = in->positions == nullptr;
     NFA_REQUIRE(!rays || (in->n_rays >= 1 && in->n_rays < ((int64_t)1 << 31) - 64), "%s: n_rays %lld out of range", who,
                 (long long)in->n_rays);
+    NFA_REQUIRE(mode == NFA_NGP_GRAD_RAW || mode == NFA_NGP_GRAD_ACTIVATED,
+                "%s: mode must be NFA_NGP_GRAD_RAW (0) or NFA_NGP_GRAD_ACTIVATED (1) (got %d)", who, mode);
+    NFA_REQUIRE(!train || save, "%s: the descriptor of the saved buffers is null", who);
+    NFA_REQUIRE(!backward || grads, "%s: the descriptor of the gradients is null", who);
+    if (backward) {
+        NFA_REQUIRE(grads->g_sigma_elem == NFA_ELEM_F32 || grads->g_sigma_elem == elem, "%s: g_sigma_elem %d: float32 or the networks' type (%d)",
+                    who, grads->g_sigma_elem, elem);
+        NFA_REQUIRE(!full || grads->g_rgb_elem == NFA_ELEM_F32 || grads->g_rgb_elem == elem, "%s: g_rgb_elem %d: float32 or the networks' type (%d)",
+                    who, grads->g_rgb_elem, elem);
+    }
     if (N == 0) return NFA_OK;
     NFA_REQUIRE(grid->params && base_image && (!full || head_image), "%s: null pointer (table or image)", who);
     NFA_REQUIRE(rays ? (in->rays_o && in->rays_d && in->t_starts && in->t_ends && in->ray_indices) : (!full || in->dirs),
                 "%s: null input pointer (positions with dirs, or rays_o, rays_d, t_starts, t_ends and ray_indices)", who);
-    NFA_REQUIRE(out.sigma || out.density || out.feat || out.selector || (full && (out.rgb || out.rgb_act)), "%s: no output requested", who);
+    NFA_REQUIRE(backward || out.sigma || out.density || out.feat || out.selector || (full && (out.rgb || out.rgb_act)),
+                "%s: no output requested", who);
     NFA_REQUIRE(!out.feat || G >= 1, "%s: feat needs geo_feat_dim >= 1", who);
     NFA_REQUIRE(aligned_to(base_image, 16) && aligned_to(head_image, 16) && aligned_to(grid->params, 8) &&
                 aligned_to(out.sigma, out.sigma_elem == NFA_ELEM_F32 ? 4 : 2) && aligned_to(out.rgb, out.rgb_elem == NFA_ELEM_F32 ? 4 : 2) &&
                 aligned_to(out.feat, 2), "%s: misaligned pointer (images 16, table 8, the outputs their element)", who);
     const Shape SB = base_shape(grid->n_levels, G), SH = head_shape(G);
+    NgpGrads g = {};
+    if (train) {
+        NFA_REQUIRE(save->enc && save->base_hidden && save->base_out && (!full || (save->head_x && save->head_hidden)),
+                    "%s: null pointer (a saved buffer: enc, base_hidden, base_out%s)", who, full ? ", head_x, head_hidden" : "");
+        NFA_REQUIRE(aligned_to(save->enc, 16) && aligned_to(save->base_hidden, 16) && aligned_to(save->head_hidden, 16) &&
+                    aligned_to(save->base_out, 2) && aligned_to(save->head_x, 2),
+                    "%s: misaligned pointer (enc and the hidden activations 16, base_out and head_x their element)", who);
+        a.s_enc = static_cast<uint16_t *>(save->enc), a.s_bhid = static_cast<uint16_t *>(save->base_hidden);
+        a.s_bout = static_cast<uint16_t *>(save->base_out), a.s_hx = static_cast<uint16_t *>(save->head_x);
+        a.s_hhid = static_cast<uint16_t *>(save->head_hidden);
+    }
+    if (backward) {
+        const bool act = mode == NFA_NGP_GRAD_ACTIVATED;
+        NFA_REQUIRE(grads->base_dz && grads->base_dz_out && (!full || (grads->head_dz && grads->head_dz_out)),
+                    "%s: null pointer (base_dz, base_dz_out%s)", who, full ? ", head_dz, head_dz_out" : "");
+        NFA_REQUIRE(!(act && full && grads->g_rgb) || grads->raw_rgb, "%s: null pointer (raw_rgb: the activated mode forms the sigmoid from it)", who);
+        NFA_REQUIRE(aligned_to(grads->base_dz, 16) && aligned_to(grads->head_dz, 16) && aligned_to(grads->base_dz_out, 2) &&
+                    aligned_to(grads->head_dz_out, 2) && aligned_to(grads->raw_rgb, 2) && aligned_to(grads->grad_table, 8) &&
+                    aligned_to(grads->g_sigma, grads->g_sigma_elem == NFA_ELEM_F32 ? 4 : 2) &&
+                    aligned_to(grads->g_rgb, grads->g_rgb_elem == NFA_ELEM_F32 ? 4 : 2),
+                    "%s: misaligned pointer (base_dz and head_dz 16, grad_table 8, the others their element)", who);
+        g.g_rgb = full ? grads->g_rgb : nullptr, g.g_sigma = grads->g_sigma;
+        g.g_rgb_f32 = grads->g_rgb_elem == NFA_ELEM_F32, g.g_sigma_f32 = grads->g_sigma_elem == NFA_ELEM_F32;
+        g.activated = act, g.raw_rgb = static_cast<const uint16_t *>(grads->raw_rgb);
+        g.hdz = static_cast<uint16_t *>(grads->head_dz), g.hdzo = static_cast<uint16_t *>(grads->head_dz_out);
+        g.bdz = static_cast<uint16_t *>(grads->base_dz), g.bdzo = static_cast<uint16_t *>(grads->base_dz_out);
+        g.grad_table = grads->grad_table;
+    }
     a.table = grid->params;
     a.base_img = static_cast<const uint16_t *>(base_image), a.head_img = static_cast<const uint16_t *>(head_image);
-    a.base_elems = SB.fwd_off(SB.layers()), a.head_elems = full ? SH.fwd_off(SH.layers()) : 0;
+    a.base_elems = backward ? SB.bwd_off(SB.layers()) : SB.fwd_off(SB.layers());
+    a.head_elems = !full ? 0 : backward ? SH.bwd_off(SH.layers()) : SH.fwd_off(SH.layers());
     a.kq0 = SB.fwd_kq(0), a.G = G;
     a.x = in->positions, a.dirs = in->dirs;
     a.o = in->rays_o, a.d = in->rays_d, a.ts = in->t_starts, a.te = in->t_ends, a.ri = in->ray_indices;
@@ -346,7 +651,15 @@ int ngp_query(const char *who, bool full, int32_t elem, const nfa_ngp_grid *grid
     int rc = NFA_OK;
     auto launch = [&](auto tag, auto rays_c, auto full_c, auto interp_c) {
         using E = typename decltype(tag)::type;
-        auto kern = ngp_field_kernel<E, decltype(rays_c)::value, decltype(full_c)::value, decltype(interp_c)::value>;
+        constexpr bool R = decltype(rays_c)::value, F = decltype(full_c)::value;
+        constexpr int I = decltype(interp_c)::value;
+        if (backward) {
+            auto kern = ngp_train_bwd_kernel<E, R, F, I>;
+            if ((rc = allow_lds(who, kern, lds)) != NFA_OK) return;
+            kern<<<grid_dim, MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(a, g);
+            return;
+        }
+        auto kern = train ? ngp_train_fwd_kernel<E, R, F, I> : ngp_field_kernel<E, R, F, I>;
         if ((rc = allow_lds(who, kern, lds)) != NFA_OK) return;
         kern<<<grid_dim, MLP_WAVES * NFA_WAVE, (size_t)lds, as_stream(stream)>>>(a);
     };
@@ -387,6 +700,50 @@ int nfa_ngp_pack_head(int32_t elem, const float *params, int32_t geo_feat_dim, v
         ngp_head_pack_kernel<nfa_bf16><<<grid_1d(want, 256), 256, 0, as_stream(stream)>>>(S, geo_feat_dim, params, static_cast<uint16_t *>(head_image), want);
     NFA_CHECK_LAUNCH("ngp_pack_head");
     return NFA_OK;
+}
+
+int nfa_ngp_pack_bwd(int32_t elem, int32_t net, const float *params, int32_t n_levels, int32_t geo_feat_dim, void *image,
+                     int64_t image_elems, nfa_stream_t stream)
+{
+    NFA_REQUIRE(elem == NFA_ELEM_F16 || elem == NFA_ELEM_BF16, "ngp_pack_bwd: elem %d: the network's type is NFA_ELEM_F16 or NFA_ELEM_BF16", elem);
+    NFA_REQUIRE(net == NFA_NGP_NET_BASE || net == NFA_NGP_NET_HEAD, "ngp_pack_bwd: net must be NFA_NGP_NET_BASE (0) or NFA_NGP_NET_HEAD (1) (got %d)", net);
+    const bool head = net == NFA_NGP_NET_HEAD;
+    NFA_REQUIRE(head || (n_levels >= 1 && n_levels <= 16), "ngp_pack_bwd: n_levels must be in 1..16 (got %d)", n_levels);
+    NFA_REQUIRE(geo_feat_dim >= (head ? 1 : 0) && geo_feat_dim <= 15, "ngp_pack_bwd: geo_feat_dim must be in %d..15 (got %d)", head ? 1 : 0,
+                geo_feat_dim);
+    const Shape S = head ? head_shape(geo_feat_dim) : base_shape(n_levels, geo_feat_dim);
+    const int64_t want = S.bwd_off(S.layers());
+    NFA_REQUIRE(image_elems == want, "ngp_pack_bwd: the image holds %lld elements for this shape, got %lld", (long long)want,
+                (long long)image_elems);
+    NFA_REQUIRE(params && image, "ngp_pack_bwd: null pointer");
+    NFA_REQUIRE(aligned_to(image, 16), "ngp_pack_bwd: the image must be 16-byte aligned");
+    const int G = head ? geo_feat_dim : -1;
+    if (elem == NFA_ELEM_F16)
+        ngp_bwd_pack_kernel<nfa_f16><<<grid_1d(want, 256), 256, 0, as_stream(stream)>>>(S, G, params, static_cast<uint16_t *>(image), want);
+    else
+        ngp_bwd_pack_kernel<nfa_bf16><<<grid_1d(want, 256), 256, 0, as_stream(stream)>>>(S, G, params, static_cast<uint16_t *>(image), want);
+    NFA_CHECK_LAUNCH("ngp_pack_bwd");
+    return NFA_OK;
+}
+
+int nfa_ngp_train_fwd(int32_t elem, int32_t full, const nfa_ngp_grid *grid, const void *base_image, const void *head_image,
+                      int32_t geo_feat_dim, const nfa_ngp_input *in, int64_t n_points, const float *aabb_host, const float *aabb,
+                      int32_t contraction, int32_t density_act, float density_bias, const nfa_ngp_saved *save, void *sigma,
+                      int32_t sigma_elem, void *rgb, int32_t rgb_elem, float *density, uint8_t *selector, float *rgb_act, nfa_stream_t stream)
+{
+    const NgpOutputs out = {sigma, sigma_elem, rgb, rgb_elem, density, rgb_act, nullptr, selector};
+    return ngp_query("ngp_train_fwd", full != 0, elem, grid, base_image, head_image, geo_feat_dim, in, n_points, aabb_host, aabb, contraction,
+                     density_act, density_bias, out, stream, true, save);
+}
+
+int nfa_ngp_train_bwd(int32_t elem, int32_t full, int32_t mode, const nfa_ngp_grid *grid, const void *base_bwd_image,
+                      const void *head_bwd_image, int32_t geo_feat_dim, const nfa_ngp_input *in, int64_t n_points, const float *aabb_host,
+                      const float *aabb, int32_t contraction, int32_t density_act, float density_bias, const nfa_ngp_saved *saved,
+                      const nfa_ngp_grads *grads, nfa_stream_t stream)
+{
+    const NgpOutputs out = {nullptr, NFA_ELEM_F32, nullptr, NFA_ELEM_F32, nullptr, nullptr, nullptr, nullptr};
+    return ngp_query("ngp_train_bwd", full != 0, elem, grid, base_bwd_image, head_bwd_image, geo_feat_dim, in, n_points, aabb_host, aabb,
+                     contraction, density_act, density_bias, out, stream, true, saved, true, mode, grads);
 }
 
 int nfa_ngp_density(int32_t elem, const nfa_ngp_grid *grid, const void *base_image, int32_t geo_feat_dim, const nfa_ngp_input *in,

@@ -1787,16 +1787,7 @@ struct RawAct {
     float bias;
     __device__ __forceinline__ float density(float z) const { return raw_density_act(dens, z); }
     // d density / d z, given the density itself
-    __device__ __forceinline__ float density_grad(float z, float s) const
-    {
-        switch (dens) {
-        case NFA_ACT_TRUNC_EXP: return expf(fminf(z, 15.0f));
-        case NFA_ACT_EXP: return s;
-        case NFA_ACT_RELU: return z > 0.0f ? 1.0f : 0.0f;
-        case NFA_ACT_SOFTPLUS: return z > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-z));
-        default: return 1.0f;
-        }
-    }
+    __device__ __forceinline__ float density_grad(float z, float s) const { return raw_density_grad(dens, z, s); }
     __device__ __forceinline__ void colours(float c[3 * SE]) const
     {
         if (col == NFA_RGB_ACT_SIGMOID) {

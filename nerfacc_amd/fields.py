@@ -19,6 +19,12 @@ Differences from the reference, all in what cannot be expressed natively: ``dens
 ``query_density(return_feat=True)`` returns stays in the networks' ``dtype``.  Outside the box the density is an exact zero
 (a select, as :func:`nerfacc_amd.rawrender.activate_density`).
 
+``fused_training=True`` (off by default) gives a query WITH grad the same treatment when only parameters require grad: one
+launch forward that saves what the backward needs (``nfa_ngp_train_fwd``), one launch backward for both networks' data gradients
+and the table scatter (``nfa_ngp_train_bwd``), then the networks' usual weight-gradient passes.  Its outputs are the no-grad
+launch's bits; its gradients have the composed chain's rounding points.  Positions, directions or rays that require grad, a
+``deterministic=True`` encoding, ``return_feat=True`` and every configuration outside ``fused_supported`` take the composed chain.
+
 Not part of ``nerfacc_amd.__all__``: ``from nerfacc_amd.fields import NGPRadianceField, NGPDensityField``.
 """
 from __future__ import annotations
@@ -39,11 +45,107 @@ from .samples import _contract_torch, sample_positions
 FUSED_MAX_LEVELS = 16
 
 
+class _NGPTrainFn(torch.autograd.Function):
+    """A query with grad as one launch: the no-grad launch's outputs, and the buffers the backward reads."""
+
+    @staticmethod
+    def forward(ctx, table: Tensor, base_p: Tensor, head_p: Optional[Tensor], field: "_NGPField", full: bool, activated: bool, n: int,
+                shape: tuple, inputs: dict):
+        ctx.set_materialize_grads(False)
+        dev, dt, G = table.device, field.dtype, field.geo_feat_dim
+        new = lambda *s: torch.empty(*s, dtype=dt, device=dev)
+        saved = [new(n, 2 * field.n_levels), new(1, n, 64), new(n, 1 + G)] + ([new(n, 16 + G), new(2, n, 64)] if full else [])
+        if not full:
+            want = ["density"]
+        else:   # the activated mode keeps the raw colour: the backward forms the sigmoid from it
+            want = ["rgb_act", "density", "rgb"] if activated else ["rgb", "sigma", "selector"]
+        out = field._launch(full, n, shape, want, rgb_dtype=dt if activated else torch.float32, save=B.NGPSaved(*[B.ptr(t) for t in saved]),
+                            **inputs)
+        keep = field._operands(full, **inputs)[3]
+        ctx.field, ctx.full, ctx.activated, ctx.n, ctx.keys, ctx.n_keep = field, full, activated, n, list(inputs), len(keep)
+        ctx.save_for_backward(table, base_p, head_p, *keep, *saved, *([out["rgb"]] if full and activated else []))
+        if not full:
+            return out["density"]
+        if activated:
+            return out["rgb_act"], out["density"]
+        ctx.mark_non_differentiable(out["selector"])
+        return out["rgb"], out["sigma"].view(shape), out["selector"]
+
+    @staticmethod
+    def backward(ctx, *grads):
+        need = ctx.needs_input_grad[:3]
+        g_rgb, g_sigma = (grads[0], grads[1]) if ctx.full else (None, grads[0])
+        if not any(need) or (g_rgb is None and g_sigma is None):
+            return (None,) * 9
+        table, base_p, head_p, *rest = ctx.saved_tensors
+        g = _NGPTrainBwdFn.apply(table, base_p, head_p, g_rgb, g_sigma, ctx.field, ctx.full, ctx.activated, ctx.n, ctx.keys, ctx.n_keep, need,
+                                 *[t.detach() for t in rest])
+        return (*g, None, None, None, None, None, None)
+
+
+class _NGPTrainBwdFn(torch.autograd.Function):
+    """The backward as a function of its own, so that differentiating it again (``create_graph=True``) fails with a message that
+    names the module (as ``mlp._MLPBwdFn`` does)."""
+
+    @staticmethod
+    def forward(ctx, table, base_p, head_p, g_rgb, g_sigma, field, full, activated, n, keys, n_keep, need, *rest):
+        ctx.set_materialize_grads(False)
+        ctx.name = type(field).__name__
+        need_t, need_b, need_h = need[0], need[1], bool(full and need[2])
+        if n == 0:
+            return tuple(torch.zeros_like(p) if w else None for p, w in ((table, need_t), (base_p, need_b), (head_p, need_h)))
+        keep, saved = list(rest[:n_keep]), list(rest[n_keep:])
+        raw_rgb = saved.pop() if full and activated else None
+        dev, dt, G = table.device, field.dtype, field.geo_feat_dim
+        elem = B.ELEM_CODES[dt]
+
+        def grad(t):   # float32 or the networks' type, contiguous; the kernel rounds once
+            if t is None:
+                return None, B.ELEM_CODES[torch.float32]
+            t = (t if t.dtype in (torch.float32, dt) else t.float()).contiguous()
+            return t, B.ELEM_CODES[t.dtype]
+
+        (g_rgb, rgb_elem), (g_sigma, sigma_elem) = grad(g_rgb), grad(g_sigma)
+        new = lambda *s: torch.empty(*s, dtype=dt, device=dev)
+        bdz, bdzo = new(1, n, 64), new(n, 1 + G)
+        hdz, hdzo = (new(2, n, 64), new(n, 3)) if full else (None, None)
+        g_t = torch.zeros_like(table) if need_t else None
+        rays = len(keys) == 1 and keys[0] == "rays"
+        grid, inp, box, keep = field._operands(full, rays=tuple(keep)) if rays else field._operands(full, **dict(zip(keys, keep)))
+        gr = B.NGPGrads(B.ptr(g_rgb), rgb_elem, B.ptr(g_sigma), sigma_elem, B.ptr(raw_rgb), B.ptr(hdz), B.ptr(hdzo), B.ptr(bdz), B.ptr(bdzo),
+                        B.ptr(g_t))
+        sv = B.NGPSaved(*[B.ptr(t) for t in saved])
+        g_b = g_h = None
+        with torch.cuda.device(dev):
+            B.call("nfa_ngp_train_bwd", elem, int(full), int(activated), ctypes.byref(grid), B.ptr(field._bwd_image(False)),
+                   B.ptr(field._bwd_image(True)) if full else None, G, ctypes.byref(inp), n, *box, int(field.unbounded),
+                   DENSITY_ACTIVATIONS[field.density_activation], field.density_bias, ctypes.byref(sv), ctypes.byref(gr), B.stream())
+            for mlp, want, x, hidden, dz, dzo in ((field.mlp_base, need_b, saved[0], saved[1], bdz, bdzo),
+                                                  (getattr(field, "mlp_head", None), need_h, *(saved[3:5] if full else (None, None)), hdz, hdzo)):
+                if not want:
+                    continue
+                P = mlp.params.numel()
+                partials = torch.empty(mlp._slices(n) * P, dtype=torch.float32, device=dev)
+                g_p = torch.empty(P, dtype=torch.float32, device=dev)
+                mlp._weight_gradient(elem, x, hidden, dz, dzo, n, partials, g_p, zero_bias=False)
+                if mlp is field.mlp_base:
+                    g_b = g_p
+                else:
+                    g_h = g_p
+        return g_t, g_b, g_h
+
+    @staticmethod
+    def backward(ctx, *gg):
+        raise NotImplementedError(f"{ctx.name}(fused_training=True): the second order (differentiating the parameters' gradients again, "
+                                  "create_graph=True) is not implemented by the fused training pass; construct the module with "
+                                  "fused_training=False")
+
+
 class _NGPField(nn.Module):
     """What the two fields share: the box, the grid, the base network and the fused launch."""
 
     def __init__(self, aabb, num_dim, density_activation, density_bias, unbounded, base_resolution, max_resolution, geo_feat_dim,
-                 n_levels, log2_hashmap_size, dtype, interpolation, fused):
+                 n_levels, log2_hashmap_size, dtype, interpolation, fused, fused_training=False):
         super().__init__()
         if not isinstance(aabb, Tensor):
             aabb = torch.tensor(aabb, dtype=torch.float32)
@@ -54,12 +156,13 @@ class _NGPField(nn.Module):
         self.density_activation, self.density_bias = density_activation, float(density_bias)
         self.base_resolution, self.max_resolution = base_resolution, max_resolution
         self.geo_feat_dim, self.n_levels, self.log2_hashmap_size = int(geo_feat_dim), int(n_levels), int(log2_hashmap_size)
-        self.dtype, self.fused = dtype, bool(fused)
+        self.dtype, self.fused, self.fused_training = dtype, bool(fused), bool(fused_training)
         per_level_scale = math.exp((math.log(max_resolution) - math.log(base_resolution)) / (n_levels - 1)) if n_levels > 1 else 1.0
         self.encoding = HashGridEncoding(self.num_dim, n_levels, 2, log2_hashmap_size, base_resolution, per_level_scale, out_dtype=dtype,
                                          interpolation=interpolation)
         self.mlp_base = FusedMLP(2 * self.n_levels, 1 + self.geo_feat_dim, 64, 1, dtype=dtype)
         self._head_packed = None   # (key, image)
+        self._bwd_packed = {}      # head?: (key, image)
 
     # ---------------------------------------------------------------- the composed chain
 
@@ -89,13 +192,48 @@ class _NGPField(nn.Module):
         ok = self.num_dim == 3 and self.n_levels <= FUSED_MAX_LEVELS and not callable(self.density_activation) and self.geo_feat_dim <= 15
         return ok and (not full or (getattr(self, "use_viewdirs", False) and self.geo_feat_dim >= 1))
 
+    def _on_device(self, ts: List[Tensor]) -> bool:
+        return all(t.is_cuda and t.device == self.encoding.params.device for t in ts) and all(t.dtype == torch.float32 for t in ts[:4])
+
     def _use_fused(self, full: bool, *tensors: Optional[Tensor]) -> bool:
         if not (self.fused and self.fused_supported(full)):
             return False
         ts = [t for t in tensors if t is not None]
-        if not all(t.is_cuda and t.device == self.encoding.params.device for t in ts) or not all(t.dtype == torch.float32 for t in ts[:4]):
+        if not self._on_device(ts):
             return False
         return not (torch.is_grad_enabled() and any(t.requires_grad for t in [*self.parameters(), *ts]))
+
+    def _train_params(self, full: bool) -> List[Tensor]:
+        return [self.encoding.params, self.mlp_base.params] + ([self.mlp_head.params] if full else [])
+
+    def _use_train(self, full: bool, *tensors: Optional[Tensor]) -> bool:
+        """The fused training pass serves this query: grad is on and wanted by parameters only."""
+        if not (self.fused_training and torch.is_grad_enabled() and self.fused_supported(full)) or self.encoding.deterministic:
+            return False
+        ts = [t for t in tensors if t is not None]
+        if not self._on_device(ts) or any(t.requires_grad for t in ts):
+            return False
+        return any(p.requires_grad for p in self._train_params(full))
+
+    def _train(self, full: bool, activated: bool, n: int, shape, **inputs):
+        """The outputs of one training launch: raw ``(rgb, sigma, selector)``, activated ``(rgb_act, density)``, without ``full``
+        the density alone."""
+        params = self._train_params(full)
+        return _NGPTrainFn.apply(params[0], params[1], params[2] if full else None, self, full, activated, n, tuple(shape), inputs)
+
+    def _bwd_image(self, head: bool) -> Tensor:
+        """A network's backward image for the fused training backward, cached and rebuilt like ``_head_image``."""
+        mlp = self.mlp_head if head else self.mlp_base
+        p = mlp.params
+        key = (p.data_ptr(), p._version, p.device)
+        if head not in self._bwd_packed or self._bwd_packed[head][0] != key:
+            shape = (16 + self.geo_feat_dim, 3, 64, 2) if head else (2 * self.n_levels, 1 + self.geo_feat_dim, 64, 1)
+            img = torch.empty(image_elems(*shape)[1], dtype=self.dtype, device=p.device)
+            with torch.cuda.device(p.device):
+                B.call("nfa_ngp_pack_bwd", B.ELEM_CODES[self.dtype], int(head), B.ptr(p), self.n_levels, self.geo_feat_dim, B.ptr(img),
+                       img.numel(), B.stream())
+            self._bwd_packed[head] = (key, img)
+        return self._bwd_packed[head][1]
 
     def _head_image(self) -> Tensor:
         """The head's forward image in the fused launch's k order, rebuilt when the masters change (as FusedMLP's images)."""
@@ -108,11 +246,9 @@ class _NGPField(nn.Module):
             self._head_packed = (key, img)
         return self._head_packed[1]
 
-    def _launch(self, full: bool, n: int, shape, want: List[str], positions=None, dirs=None, rays=None, rgb_dtype=torch.float32,
-                outputs: Optional[dict] = None):
-        """One fused launch; returns the outputs named in ``want`` (sigma, density, selector, feat, rgb, rgb_act), shaped ``shape``
-        (``outputs``: the caller's own contiguous tensors for them)."""
-        dev, enc, t = self.encoding.params.device, self.encoding, self.encoding.table
+    def _operands(self, full: bool, positions=None, dirs=None, rays=None):
+        """(grid descriptor, input descriptor, the box's two arguments, the tensors they point into) of a native call."""
+        enc, t = self.encoding, self.encoding.table
         vp = lambda a: ctypes.cast(a, ctypes.c_void_p)
         grid = B.NGPGrid(B.ptr(enc.params), enc.params.numel(), enc.n_levels, 2, t.log2_hashmap_size, enc.interp, vp(t.c_scales), vp(t.c_res),
                          vp(t.c_sizes))
@@ -123,6 +259,15 @@ class _NGPField(nn.Module):
             inp = B.NGPInput(None, None, *[B.ptr(x) for x in keep], keep[0].shape[0])
         else:
             inp = B.NGPInput(B.ptr(keep[0]), B.ptr(keep[1]) if full else None, None, None, None, None, None, 0)
+        box = (None, B.ptr(self.aabb)) if self.aabb.is_cuda else ((ctypes.c_float * 6)(*self.aabb.tolist()), None)
+        return grid, inp, box, keep
+
+    def _launch(self, full: bool, n: int, shape, want: List[str], positions=None, dirs=None, rays=None, rgb_dtype=torch.float32,
+                outputs: Optional[dict] = None, save: Optional["B.NGPSaved"] = None):
+        """One fused launch; returns the outputs named in ``want`` (sigma, density, selector, feat, rgb, rgb_act), shaped ``shape``
+        (``outputs``: the caller's own contiguous tensors for them).  ``save``: the training forward, which fills its buffers."""
+        dev = self.encoding.params.device
+        grid, inp, box, keep = self._operands(full, positions, dirs, rays)
         specs = {"sigma": ((1,), torch.float32), "density": ((1,), torch.float32), "selector": ((), torch.bool),
                  "feat": ((self.geo_feat_dim,), self.dtype), "rgb": ((3,), rgb_dtype), "rgb_act": ((3,), torch.float32)}
         out = dict.fromkeys(specs)
@@ -132,12 +277,15 @@ class _NGPField(nn.Module):
         if n == 0:
             return out
         act = DENSITY_ACTIVATIONS[self.density_activation]
-        box = (None, B.ptr(self.aabb)) if self.aabb.is_cuda else ((ctypes.c_float * 6)(*self.aabb.tolist()), None)
         lead = (B.ELEM_CODES[self.dtype], ctypes.byref(grid), B.ptr(self.mlp_base._images(self.mlp_base.params)[0]))
         tail = (self.geo_feat_dim, ctypes.byref(inp), n, *box, int(self.unbounded), act, self.density_bias, B.ptr(out["sigma"]),
                 B.ELEM_CODES[torch.float32])
         with torch.cuda.device(dev):
-            if full:
+            if save is not None:
+                B.call("nfa_ngp_train_fwd", lead[0], int(full), lead[1], lead[2], B.ptr(self._head_image()) if full else None,
+                       *tail[:-2], ctypes.byref(save), *tail[-2:], B.ptr(out["rgb"]), B.ELEM_CODES[rgb_dtype], B.ptr(out["density"]),
+                       B.ptr(out["selector"]), B.ptr(out["rgb_act"]), B.stream())
+            elif full:
                 B.call("nfa_ngp_field", *lead, B.ptr(self._head_image()), *tail, B.ptr(out["rgb"]), B.ELEM_CODES[rgb_dtype],
                        B.ptr(out["density"]), B.ptr(out["selector"]), B.ptr(out["rgb_act"]), B.stream())
             else:
@@ -146,6 +294,9 @@ class _NGPField(nn.Module):
 
     def density_on_rays(self, rays_o: Tensor, rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor) -> Tensor:
         """Densities ``[n]`` at the midpoints of packed ray samples: a trainer's ``sigma_fn``."""
+        if self._use_train(False, rays_o, rays_d, t_starts, t_ends, ray_indices):
+            n = t_starts.numel()
+            return self._train(False, True, n, (n,), rays=(rays_o, rays_d, t_starts, t_ends, ray_indices)).view(n)
         if self._use_fused(False, rays_o, rays_d, t_starts, t_ends, ray_indices):
             n = t_starts.numel()
             return self._launch(False, n, (n,), ["density"], rays=(rays_o, rays_d, t_starts, t_ends, ray_indices))["density"].view(n)
@@ -156,14 +307,16 @@ class _NGPField(nn.Module):
 
 class NGPRadianceField(_NGPField):
     """Instant-NGP radiance field (the reference's constructor arguments; ``dtype`` fp16 or bf16 is the networks' type,
-    ``interpolation`` the hash grid's, ``fused=False`` switches the fused dispatch off)."""
+    ``interpolation`` the hash grid's, ``fused=False`` switches the fused dispatch off, ``fused_training=True`` the fused
+    training pass on)."""
 
     def __init__(self, aabb: Union[Tensor, List[float]], num_dim: int = 3, use_viewdirs: bool = True,
                  density_activation: Union[str, Callable] = "trunc_exp", unbounded: bool = False, base_resolution: int = 16,
                  max_resolution: int = 4096, geo_feat_dim: int = 15, n_levels: int = 16, log2_hashmap_size: int = 19, *,
-                 density_bias: float = -1.0, dtype: torch.dtype = torch.float16, interpolation: str = "Linear", fused: bool = True):
+                 density_bias: float = -1.0, dtype: torch.dtype = torch.float16, interpolation: str = "Linear", fused: bool = True,
+                 fused_training: bool = False):
         super().__init__(aabb, num_dim, density_activation, density_bias, unbounded, base_resolution, max_resolution, geo_feat_dim,
-                         n_levels, log2_hashmap_size, dtype, interpolation, fused)
+                         n_levels, log2_hashmap_size, dtype, interpolation, fused, fused_training)
         self.use_viewdirs = bool(use_viewdirs)
         if self.use_viewdirs:
             self.direction_encoding = SphericalHarmonicsEncoding(3, 4, out_dtype=dtype)
@@ -171,6 +324,8 @@ class NGPRadianceField(_NGPField):
             self.mlp_head = FusedMLP((16 if self.use_viewdirs else 0) + self.geo_feat_dim, 3, 64, 2, dtype=dtype)
 
     def query_density(self, x: Tensor, return_feat: bool = False):
+        if not return_feat and self._use_train(False, x):
+            return self._train(False, True, x.numel() // 3, x.shape[:-1], positions=x.reshape(-1, 3))
         if self._use_fused(False, x):
             want = ["density"] + (["feat"] if return_feat and self.geo_feat_dim else [])
             out = self._launch(False, x.numel() // 3, x.shape[:-1], want, positions=x.reshape(-1, 3))
@@ -194,6 +349,9 @@ class NGPRadianceField(_NGPField):
         if not (self.use_viewdirs and directions is not None):
             raise ValueError("NGPRadianceField.forward needs view directions (use_viewdirs=True); query_density takes positions alone")
         assert positions.shape == directions.shape, f"{positions.shape} v.s. {directions.shape}"
+        if self._use_train(True, positions, directions):
+            return self._train(True, True, positions.numel() // 3, positions.shape[:-1], positions=positions.reshape(-1, 3),
+                               dirs=directions.reshape(-1, 3))
         if self._use_fused(True, positions, directions):
             out = self._launch(True, positions.numel() // 3, positions.shape[:-1], ["rgb_act", "density"],
                                positions=positions.reshape(-1, 3), dirs=directions.reshape(-1, 3))
@@ -203,6 +361,9 @@ class NGPRadianceField(_NGPField):
 
     def query_raw(self, positions: Tensor, directions: Tensor):
         """``(raw_rgbs [..., 3], raw_sigmas [...], selector [...])`` at world positions, before any activation."""
+        if self._use_train(True, positions, directions):
+            return self._train(True, False, positions.numel() // 3, positions.shape[:-1], positions=positions.reshape(-1, 3),
+                               dirs=directions.reshape(-1, 3))
         if self._use_fused(True, positions, directions):
             out = self._launch(True, positions.numel() // 3, positions.shape[:-1], ["rgb", "sigma", "selector"],
                                positions=positions.reshape(-1, 3), dirs=directions.reshape(-1, 3))
@@ -214,6 +375,9 @@ class NGPRadianceField(_NGPField):
         """The field at the midpoints of packed ray samples.  ``raw=True``: ``(raw_rgbs [n, 3], raw_sigmas [n], selector [n])``,
         what :func:`nerfacc_amd.rendering_from_raw` takes; otherwise ``(rgbs [n, 3], sigmas [n])`` activated."""
         n = t_starts.numel()
+        if self._use_train(True, rays_o, rays_d, t_starts, t_ends, ray_indices):
+            out = self._train(True, not raw, n, (n,), rays=(rays_o, rays_d, t_starts, t_ends, ray_indices))
+            return out if raw else (out[0], out[1].view(n))
         if self._use_fused(True, rays_o, rays_d, t_starts, t_ends, ray_indices):
             want = ["rgb", "sigma", "selector"] if raw else ["rgb_act", "density"]
             out = self._launch(True, n, (n,), want, rays=(rays_o, rays_d, t_starts, t_ends, ray_indices))
@@ -231,11 +395,13 @@ class NGPDensityField(_NGPField):
     def __init__(self, aabb: Union[Tensor, List[float]], num_dim: int = 3, density_activation: Union[str, Callable] = "trunc_exp",
                  unbounded: bool = False, base_resolution: int = 16, max_resolution: int = 128, n_levels: int = 5,
                  log2_hashmap_size: int = 17, *, density_bias: float = -1.0, dtype: torch.dtype = torch.float16,
-                 interpolation: str = "Linear", fused: bool = True):
+                 interpolation: str = "Linear", fused: bool = True, fused_training: bool = False):
         super().__init__(aabb, num_dim, density_activation, density_bias, unbounded, base_resolution, max_resolution, 0, n_levels,
-                         log2_hashmap_size, dtype, interpolation, fused)
+                         log2_hashmap_size, dtype, interpolation, fused, fused_training)
 
     def forward(self, positions: Tensor) -> Tensor:
+        if self._use_train(False, positions):
+            return self._train(False, True, positions.numel() // 3, positions.shape[:-1], positions=positions.reshape(-1, 3))
         if self._use_fused(False, positions):
             return self._launch(False, positions.numel() // 3, positions.shape[:-1], ["density"], positions=positions.reshape(-1, 3))["density"]
         raw, _, selector = self._base(positions)
