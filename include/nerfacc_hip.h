@@ -821,6 +821,25 @@ int nfa_hashgrid_bwd_sorted_d(int32_t n_dims, int32_t interp, int32_t elem, cons
                               const int32_t *sizes_host, int64_t n_params, float *grad_params, float *grad_x,
                               void *scratch, int64_t scratch_bytes, nfa_stream_t stream);
 int64_t nfa_hashgrid_sorted_scratch_bytes_d(int32_t n_dims, int64_t n_points, int32_t n_levels, int32_t log2_hashmap_size);
+/* The table gradient with equal cells merged before the atomics (csrc/hashgrid_merged.hip): a third way of forming
+ * dL/dparams, next to nfa_hashgrid_bwd_d (one float atomic per point, corner and feature) and nfa_hashgrid_bwd_sorted_d.  One
+ * lane per point and one level per workgroup row; consecutive points that fall in the same cell of the level (neighbouring
+ * samples of a ray on a coarse level) are summed inside the wave first, and a level whose slice size_l * n_features is at most
+ * NFA_HG_MERGED_LDS_FLOATS floats is summed in a copy in LDS per workgroup before its non-zero entries are added to
+ * grad_params.  Every term is the float32 value the atomic pass adds (w_c * dL/dy[j], both interpolations); only the order of
+ * the additions differs.  The result still ends in float atomics: it is NOT bitwise reproducible (nfa_hashgrid_bwd_sorted_d
+ * is), and lies within the rounding of a float32 sum of the other two.
+ *   n_dims 2, 3 or 4; interp NFA_INTERP_*; elem the type of grad_y [n_points, n_levels * n_features] (NFA_ELEM_*; a half
+ *   grad_y must be 16-byte aligned); x [n_points, n_dims] float32 (16-byte aligned at n_dims 2 and 4); the grid description as
+ *   in every nfa_hashgrid_* entry.  grad_params [n_params] float32 is ADDED INTO: the caller zeroes it.  params is not read
+ *   and grad_x is not formed: call nfa_hashgrid_bwd_d with a null grad_params for it.  n_points == 0 returns NFA_OK without a
+ *   launch.  At most two launches whose shapes depend on (n_points, the level table) alone; no scratch, nothing read back, so
+ *   the call can be captured into a graph. */
+#define NFA_HG_MERGED_LDS_FLOATS 16384   /* 64 KiB: two workgroups in a CU's 160 KiB of LDS */
+int nfa_hashgrid_bwd_merged(int32_t n_dims, int32_t interp, int32_t elem, const float *x, const void *grad_y, int64_t n_points,
+                            int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,
+                            const int32_t *resolutions_host, const int32_t *sizes_host, int64_t n_params, float *grad_params,
+                            nfa_stream_t stream);
 int nfa_sh_fwd_t(int32_t elem, const float *dirs, int64_t n_points, int32_t degree, void *out, nfa_stream_t stream);
 int nfa_sh_bwd_t(int32_t elem, const float *dirs, const void *grad_out, int64_t n_points, int32_t degree,
                  float *grad_dirs, nfa_stream_t stream);

@@ -17,11 +17,15 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libnerfacc_hip.so")
-SOURCES = ["grid.hip", "walk.hip", "gridupd.hip", "traverse2.hip", "segscan.hip", "pdf.hip", "camera.hip", "pack.hip", "encoding.hip", "samples.hip", "rays.hip", "planes.hip", "planereg.hip", "vmgrid.hip", "vmreg.hip", "voxgrid.hip", "voxreg.hip", "sinenc.hip", "mlp.hip", "mlp_stream.hip", "optim.hip", "photo.hip", "ngp_field.hip"]
+SOURCES = ["grid.hip", "walk.hip", "gridupd.hip", "traverse2.hip", "segscan.hip", "pdf.hip", "camera.hip", "pack.hip", "encoding.hip", "hashgrid_merged.hip", "samples.hip", "rays.hip", "planes.hip", "planereg.hip", "vmgrid.hip", "vmreg.hip", "voxgrid.hip", "voxreg.hip", "sinenc.hip", "mlp.hip", "mlp_stream.hip", "optim.hip", "photo.hip", "ngp_field.hip"]
 ARCH = os.environ.get("NERFACC_AMD_ARCH", "gfx950")
 # -ffp-contract=off: the traversal must not fuse a*b+c (floating-point contract)
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"--offload-arch={ARCH}",
          "-Wall", "-Wno-unused-function"] + os.environ.get("NERFACC_AMD_EXTRA_FLAGS", "").split()  # tuning experiments
+# per-source flags: the merged table gradient is built without packed float32 instructions (its sums stay single v_add_f32)
+SOURCE_FLAGS = {"hashgrid_merged.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def hipcc() -> str | None:
     for cand in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
         if cand and os.path.exists(cand):
@@ -43,7 +47,7 @@ HASH_PATH = LIB_PATH + ".hash"
 
 def _source_hash() -> str:
     h = hashlib.sha256()
-    h.update(" ".join(FLAGS).encode())
+    h.update(" ".join(FLAGS + [f for s in sorted(SOURCE_FLAGS) for f in [s] + SOURCE_FLAGS[s]]).encode())
     for d in sorted(_deps()):
         if os.path.exists(d):
             h.update(os.path.basename(d).encode())
@@ -78,7 +82,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
             def compile_one(src: str) -> str:
                 obj = os.path.join(obj_dir, f"{src}.{tag}.o")
-                cmd = [cc, *FLAGS, "-c", os.path.join(CSRC, src), "-o", obj]
+                cmd = [cc, *FLAGS, *SOURCE_FLAGS.get(src, []), "-c", os.path.join(CSRC, src), "-o", obj]
                 if verbose:
                     print(" ".join(cmd))
                 subprocess.run(cmd, check=True)

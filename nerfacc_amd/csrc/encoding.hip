@@ -80,8 +80,8 @@
 
 namespace nfa {
 
-// K consecutive halves (E = fp16 or bf16) at p from / as floats, K = 1, 2, 4 or a multiple of 8: pieces of 2, 4, 8 or 16
-// bytes; p is aligned to the piece.
+// K consecutive halves (E = fp16 or bf16) at p from floats, K = 1, 2, 4 or a multiple of 8: pieces of 2, 4, 8 or 16 bytes; p is
+// aligned to the piece (load_elems, its counterpart, is in encoding_dev.h).
 template <int K, class E>
 __device__ __forceinline__ void store_elems(E *p, const float *v)
 {
@@ -102,38 +102,9 @@ __device__ __forceinline__ void store_elems(E *p, const float *v)
         }
     }
 }
-template <int K, class E>
-__device__ __forceinline__ void load_elems(const E *p, float *v)
-{
-    if constexpr (K == 1) {
-        v[0] = half_value<E>(*reinterpret_cast<const uint16_t *>(p));
-    } else if constexpr (K == 2) {
-        const uint32_t w = *reinterpret_cast<const uint32_t *>(p);
-        v[0] = unpack_half<E>(w, 0); v[1] = unpack_half<E>(w, 1);
-    } else if constexpr (K == 4) {
-        const nfa_v2u w = *reinterpret_cast<const nfa_v2u *>(p);
-        v[0] = unpack_half<E>(w.x, 0); v[1] = unpack_half<E>(w.x, 1); v[2] = unpack_half<E>(w.y, 0); v[3] = unpack_half<E>(w.y, 1);
-    } else {
-        static_assert(K % 8 == 0, "K must be 1, 2, 4 or a multiple of 8");
-#pragma unroll
-        for (int k = 0; k < K; k += 8) {
-            const nfa_v4u w = *reinterpret_cast<const nfa_v4u *>(p + k);
-            v[k] = unpack_half<E>(w.x, 0); v[k + 1] = unpack_half<E>(w.x, 1); v[k + 2] = unpack_half<E>(w.y, 0);
-            v[k + 3] = unpack_half<E>(w.y, 1); v[k + 4] = unpack_half<E>(w.z, 0); v[k + 5] = unpack_half<E>(w.z, 1);
-            v[k + 6] = unpack_half<E>(w.w, 0); v[k + 7] = unpack_half<E>(w.w, 1);
-        }
-    }
-}
 
-// A point's F values of a level (piece = n * n_levels + l) from / as floats: float as one FVec<F>, halves as 2 F bytes
-template <int F, class E>
-__device__ __forceinline__ FVec<F> load_piece(const E *__restrict__ p, int64_t piece)
-{
-    FVec<F> v;
-    if constexpr (std::is_same<E, float>::value) v = reinterpret_cast<const FVec<F> *>(p)[piece];
-    else load_elems<F>(p + piece * F, v.v);
-    return v;
-}
+// A point's F values of a level (piece = n * n_levels + l) from floats: float as one FVec<F>, halves as 2 F bytes (load_piece:
+// encoding_dev.h)
 template <int F, class E>
 __device__ __forceinline__ void store_piece(E *__restrict__ p, int64_t piece, const float *v)
 {
@@ -512,31 +483,8 @@ static unsigned hashgrid_grid(int64_t n_points, const HashGridLevels &T)
 
 // ---------------------------------------------------------------- the entries, one implementation per element type
 // Each pass is a check of its arguments (which builds the level table) and a launch with the checked table; the `_sorted`
-// passes check once under their own name and call the launch half of the plain pass.
-static int check_interp(const char *name, int32_t interp)
-{
-    NFA_REQUIRE(interp == NFA_INTERP_LINEAR || interp == NFA_INTERP_SMOOTHSTEP,
-                "%s: interp must be NFA_INTERP_LINEAR (0) or NFA_INTERP_SMOOTHSTEP (1) (got %d)", name, interp);
-    return NFA_OK;
-}
-
-// Host-side dispatch of a run-time value to a compile-time one, f(std::integral_constant<int, V>), for the V... it was
-// checked to be one of; of a grid's (n_dims, n_features, interp) to f(.. <int, D>, .. <int, F>, .. <int, I>) for the Dims... a
-// pass is instantiated for (all three, or 3 alone: the second order); and of the spherical-harmonics degree.
-template <int... V, class Fn>
-static void dispatch_int(int32_t v, Fn &&f)
-{
-    (void)((v == V && (f(std::integral_constant<int, V>{}), true)) || ...);
-}
-template <int... Dims, class Fn>
-static void dispatch_grid(const GridArgs &G, int32_t interp, Fn &&f)
-{
-    dispatch_int<Dims...>(G.n_dims, [&](auto d) {
-        dispatch_int<NFA_INTERP_LINEAR, NFA_INTERP_SMOOTHSTEP>(interp, [&](auto i) {
-            dispatch_int<1, 2, 4, 8>(G.n_features, [&](auto n) { f(d, n, i); });
-        });
-    });
-}
+// passes check once under their own name and call the launch half of the plain pass.  check_interp, dispatch_int, dispatch_grid
+// and ELEM_DISPATCH are in encoding_dev.h.
 template <class Fn>
 static void dispatch_degree(int32_t degree, Fn &&f)
 {
@@ -1101,12 +1049,6 @@ static int hashgrid_bwd_bwd_sorted(int32_t interp, const float *x, const float *
 }  // namespace nfa
 
 using namespace nfa;
-
-#define ELEM_DISPATCH(name, elem, call)                                                        \
-    int rc = NFA_OK;                                                                           \
-    if (!dispatch_elem(elem, [&](auto tag) { using E = typename decltype(tag)::type; rc = call; })) \
-        NFA_REQUIRE(false, name ": elem must be NFA_ELEM_F32, NFA_ELEM_F16 or NFA_ELEM_BF16 (got %d)", (int)(elem)); \
-    return rc
 
 int nfa_hashgrid_fwd_d(int32_t n_dims, int32_t interp, int32_t elem, const float *x, const float *params, int64_t n_points,
                        int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, const float *scales_host,

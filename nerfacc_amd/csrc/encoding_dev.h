@@ -170,6 +170,41 @@ __device__ __forceinline__ void scatter_corner(float *g_params, uint32_t e, cons
     for (int j = 0; j < F; ++j) unsafeAtomicAdd(dst + j, wc * g.v[j]);
 }
 
+// K consecutive halves (E = fp16 or bf16) at p as floats, K = 1, 2, 4 or a multiple of 8: pieces of 2, 4, 8 or 16 bytes; p is
+// aligned to the piece.
+template <int K, class E>
+__device__ __forceinline__ void load_elems(const E *p, float *v)
+{
+    if constexpr (K == 1) {
+        v[0] = half_value<E>(*reinterpret_cast<const uint16_t *>(p));
+    } else if constexpr (K == 2) {
+        const uint32_t w = *reinterpret_cast<const uint32_t *>(p);
+        v[0] = unpack_half<E>(w, 0); v[1] = unpack_half<E>(w, 1);
+    } else if constexpr (K == 4) {
+        const nfa_v2u w = *reinterpret_cast<const nfa_v2u *>(p);
+        v[0] = unpack_half<E>(w.x, 0); v[1] = unpack_half<E>(w.x, 1); v[2] = unpack_half<E>(w.y, 0); v[3] = unpack_half<E>(w.y, 1);
+    } else {
+        static_assert(K % 8 == 0, "K must be 1, 2, 4 or a multiple of 8");
+#pragma unroll
+        for (int k = 0; k < K; k += 8) {
+            const nfa_v4u w = *reinterpret_cast<const nfa_v4u *>(p + k);
+            v[k] = unpack_half<E>(w.x, 0); v[k + 1] = unpack_half<E>(w.x, 1); v[k + 2] = unpack_half<E>(w.y, 0);
+            v[k + 3] = unpack_half<E>(w.y, 1); v[k + 4] = unpack_half<E>(w.z, 0); v[k + 5] = unpack_half<E>(w.z, 1);
+            v[k + 6] = unpack_half<E>(w.w, 0); v[k + 7] = unpack_half<E>(w.w, 1);
+        }
+    }
+}
+
+// A point's F values of a level (piece = n * n_levels + l) as floats: float as one FVec<F>, halves as 2 F bytes
+template <int F, class E>
+__device__ __forceinline__ FVec<F> load_piece(const E *__restrict__ p, int64_t piece)
+{
+    FVec<F> v;
+    if constexpr (std::is_same<E, float>::value) v = reinterpret_cast<const FVec<F> *>(p)[piece];
+    else load_elems<F>(p + piece * F, v.v);
+    return v;
+}
+
 // ---------------------------------------------------------------- spherical harmonics
 // tiny-cuda-nn's convention: directions d in [0, 1]^3, u = 2 d - 1 (not renormalised); degree^2 outputs per point.
 #define SH_C0 0.28209479177387814f
@@ -259,5 +294,37 @@ static int hashgrid_table(const char *name, const GridArgs &G, HashGridLevels &T
     T.pts_per_wave = 64 / G.n_levels;
     return NFA_OK;
 }
+
+static int check_interp(const char *name, int32_t interp)
+{
+    NFA_REQUIRE(interp == NFA_INTERP_LINEAR || interp == NFA_INTERP_SMOOTHSTEP,
+                "%s: interp must be NFA_INTERP_LINEAR (0) or NFA_INTERP_SMOOTHSTEP (1) (got %d)", name, interp);
+    return NFA_OK;
+}
+
+// Host-side dispatch of a run-time value to a compile-time one, f(std::integral_constant<int, V>), for the V... it was
+// checked to be one of; of a grid's (n_dims, n_features, interp) to f(.. <int, D>, .. <int, F>, .. <int, I>) for the Dims... a
+// pass is instantiated for (all three, or 3 alone: the second order); and of the spherical-harmonics degree.
+template <int... V, class Fn>
+static void dispatch_int(int32_t v, Fn &&f)
+{
+    (void)((v == V && (f(std::integral_constant<int, V>{}), true)) || ...);
+}
+template <int... Dims, class Fn>
+static void dispatch_grid(const GridArgs &G, int32_t interp, Fn &&f)
+{
+    dispatch_int<Dims...>(G.n_dims, [&](auto d) {
+        dispatch_int<NFA_INTERP_LINEAR, NFA_INTERP_SMOOTHSTEP>(interp, [&](auto i) {
+            dispatch_int<1, 2, 4, 8>(G.n_features, [&](auto n) { f(d, n, i); });
+        });
+    });
+}
+
+// The body of an extern "C" entry that takes an element code: `call` with E the element type, or NFA_EINVAL under `name`
+#define ELEM_DISPATCH(name, elem, call)                                                        \
+    int rc = NFA_OK;                                                                           \
+    if (!nfa::dispatch_elem(elem, [&](auto tag) { using E = typename decltype(tag)::type; rc = call; })) \
+        NFA_REQUIRE(false, name ": elem must be NFA_ELEM_F32, NFA_ELEM_F16 or NFA_ELEM_BF16 (got %d)", (int)(elem)); \
+    return rc
 
 }  // namespace nfa

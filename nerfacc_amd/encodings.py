@@ -47,6 +47,7 @@ __all__ = ["HashGridEncoding", "SphericalHarmonicsEncoding", "PlaneGridEncoding"
 _M32 = 0xFFFFFFFF
 _PRIMES = (1, 2654435761, 805459861, 3674653429)   # tcnn's hash primes of dimensions 0..3
 GRID_DIMS = (2, 3, 4)   # input dimensions of the native hash grid
+TABLE_GRADIENTS = ("atomic", "merged")   # how the native first-order dL/dparams is formed when it is not sorted
 
 _libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
 _libm.exp2f.restype = ctypes.c_float
@@ -240,12 +241,18 @@ class _HashGridBwdFn(torch.autograd.Function):
         g_x = torch.empty_like(x) if need_x else None
         if x.shape[0]:
             with torch.cuda.device(x.device):
-                args = (B.ptr(x), B.ptr(params), B.ptr(g), *_table_args(enc, x.shape[0], params), B.ptr(g_p), B.ptr(g_x))
+                table = _table_args(enc, x.shape[0], params)
+                plain_p = g_p   # the table gradient the plain (or sorted) pass forms
+                if enc.table_gradient == "merged" and need_p:
+                    B.call("nfa_hashgrid_bwd_merged", enc.n_input_dims, enc.interp, B.ELEM_CODES[dtype], B.ptr(x), B.ptr(g), *table,
+                           B.ptr(g_p), B.stream())
+                    plain_p = None   # dL/dx, if wanted, from the plain pass without a table gradient
+                args = (B.ptr(x), B.ptr(params), B.ptr(g), *table, B.ptr(plain_p), B.ptr(g_x))
                 if enc.deterministic and need_p:
                     scratch = _sorted_scratch(enc, x.shape[0], x.device)
                     entry, lead = _entry("nfa_hashgrid_bwd_sorted", dtype, enc.interp, enc.n_input_dims)
                     B.call(entry, *lead, *args, B.ptr(scratch), scratch.numel(), B.stream())
-                else:
+                elif plain_p is not None or need_x:
                     entry, lead = _entry("nfa_hashgrid_bwd", dtype, enc.interp, enc.n_input_dims)
                     B.call(entry, *lead, *args, B.stream())
         ctx.enc, ctx.dtype = enc, dtype
@@ -366,14 +373,30 @@ class HashGridEncoding(nn.Module):
     derivative gains the curvature along each axis.  All three native passes, both table-gradient modes and every
     ``out_dtype`` take it; parameters, ``state_dict``, the level table and the initialisation do not depend on it.
     tcnn's ``"Nearest"`` is not provided.
+
+    ``table_gradient``: ``"atomic"`` (the default) or ``"merged"`` (case-insensitive).  ``"merged"`` forms the native
+    first-order ``dL/dparams`` with ``nfa_hashgrid_bwd_merged`` (csrc/hashgrid_merged.hip): one lane per point and level,
+    consecutive points that share a cell of the level are summed inside the wave, and a level small enough is summed in LDS
+    before anything is added to memory.  It pays on points ordered along rays, whose neighbours collide on the coarse
+    levels; DESIGN.md, "Hash grid: merged table gradient", has the measurements.  The terms are the atomic path's, the order
+    of their float32 sum is not, and the result still ends in float atomics: it is not reproducible run to run, and
+    ``deterministic=True`` together with it raises ``ValueError``.  ``dL/dx``, when wanted, comes from one more call of the
+    plain backward without a table gradient, bit-equal to the default's.  The second order's table gradient (``G2_T``) keeps
+    the atomic path.  Every input dimension, ``out_dtype`` and interpolation takes it; the torch path ignores it.
     """
 
     def __init__(self, n_input_dims: int = 3, n_levels: int = 16, n_features_per_level: int = 2,
                  log2_hashmap_size: int = 19, base_resolution: float = 16, per_level_scale: float = 2.0, out_dtype=None,
-                 deterministic: bool = False, interpolation: str = "Linear"):
+                 deterministic: bool = False, interpolation: str = "Linear", table_gradient: str = "atomic"):
         super().__init__()
         self.out_dtype = _check_out_dtype(out_dtype)
         self.deterministic = bool(deterministic)
+        if not isinstance(table_gradient, str) or table_gradient.lower() not in TABLE_GRADIENTS:
+            raise ValueError(f"HashGridEncoding: table_gradient must be 'atomic' or 'merged' (got {table_gradient!r})")
+        self.table_gradient = table_gradient.lower()
+        if self.deterministic and self.table_gradient == "merged":
+            raise ValueError("HashGridEncoding: table_gradient='merged' ends in float atomics and is not reproducible; "
+                             "deterministic=True takes table_gradient='atomic' (the sorted path is the reproducible one)")
         names = {k.lower(): k for k in B.INTERP_CODES}
         if not isinstance(interpolation, str) or interpolation.lower() not in names:
             raise ValueError(f"HashGridEncoding: interpolation must be 'Linear' or 'Smoothstep' (got {interpolation!r})")
@@ -430,7 +453,8 @@ class HashGridEncoding(nn.Module):
                 f"log2_hashmap_size={self.log2_hashmap_size}, base_resolution={self.base_resolution}, "
                 f"per_level_scale={self.per_level_scale}") + ((f", out_dtype={self.out_dtype}" if self.out_dtype is not None else "")
                 + (", deterministic=True" if self.deterministic else "")
-                + (f", interpolation={self.interpolation}" if self.interp else ""))
+                + (f", interpolation={self.interpolation}" if self.interp else "")
+                + (f", table_gradient={self.table_gradient}" if self.table_gradient != "atomic" else ""))
 
 
 # Instant-NGP's real spherical-harmonics basis (tcnn's constants)
@@ -1259,10 +1283,12 @@ class SinusoidalEncoding(nn.Module):
                 + (f", out_dtype={self.out_dtype}" if self.out_dtype is not None else ""))
 
 
-def encoding_from_tcnn_config(n_input_dims: int, config: dict, out_dtype=None, deterministic: bool = False) -> nn.Module:
+def encoding_from_tcnn_config(n_input_dims: int, config: dict, out_dtype=None, deterministic: bool = False,
+                              table_gradient: str = "atomic") -> nn.Module:
     """The encoding a tiny-cuda-nn encoding config describes: ``HashGrid`` (linear interpolation), ``SphericalHarmonics``,
     or ``Composite`` with ONE nested encoding over all input dimensions (as ``ngp.py`` builds its direction encoding).
-    Anything else raises ``ValueError``.  ``out_dtype`` is handed to the encoding built, ``deterministic`` to a hash grid.
+    Anything else raises ``ValueError``.  ``out_dtype`` is handed to the encoding built, ``deterministic`` and
+    ``table_gradient`` to a hash grid.
     ``"interpolation": "Smoothstep"`` is still refused here; build it with ``HashGridEncoding(..., interpolation="Smoothstep")``.
     A ``HashGrid`` of other than 3 input dimensions is refused here too (``only 3 input dimensions``); build a 2-D or 4-D grid
     with ``HashGridEncoding(n_input_dims=2 or 4, ...)``."""
@@ -1281,7 +1307,7 @@ def encoding_from_tcnn_config(n_input_dims: int, config: dict, out_dtype=None, d
                                 log2_hashmap_size=int(config.get("log2_hashmap_size", 19)),
                                 base_resolution=config.get("base_resolution", 16),
                                 per_level_scale=float(config.get("per_level_scale", 2.0)), out_dtype=out_dtype,
-                                deterministic=deterministic)
+                                deterministic=deterministic, table_gradient=table_gradient)
     if otype == "SphericalHarmonics":
         return SphericalHarmonicsEncoding(n_input_dims, degree=int(config.get("degree", 4)), out_dtype=out_dtype)
     if otype == "Composite":
@@ -1292,5 +1318,5 @@ def encoding_from_tcnn_config(n_input_dims: int, config: dict, out_dtype=None, d
         dims = inner.pop("n_dims_to_encode", n_input_dims)
         if dims != n_input_dims:
             raise ValueError(f"Composite: the nested encoding must cover all {n_input_dims} dimensions (got {dims})")
-        return encoding_from_tcnn_config(n_input_dims, inner, out_dtype, deterministic)
+        return encoding_from_tcnn_config(n_input_dims, inner, out_dtype, deterministic, table_gradient)
     raise ValueError(f"unsupported tcnn encoding {otype!r} (supported: HashGrid, SphericalHarmonics, Composite)")

@@ -23,7 +23,8 @@ Differences from the reference, all in what cannot be expressed natively: ``dens
 launch forward that saves what the backward needs (``nfa_ngp_train_fwd``), one launch backward for both networks' data gradients
 and the table scatter (``nfa_ngp_train_bwd``), then the networks' usual weight-gradient passes.  Its outputs are the no-grad
 launch's bits; its gradients have the composed chain's rounding points.  Positions, directions or rays that require grad, a
-``deterministic=True`` encoding, ``return_feat=True`` and every configuration outside ``fused_supported`` take the composed chain.
+``deterministic=True`` or ``table_gradient="merged"`` encoding, ``return_feat=True`` and every configuration outside
+``fused_supported`` take the composed chain.  ``table_gradient`` is handed to the hash grid (:class:`HashGridEncoding`).
 
 Not part of ``nerfacc_amd.__all__``: ``from nerfacc_amd.fields import NGPRadianceField, NGPDensityField``.
 """
@@ -145,7 +146,7 @@ class _NGPField(nn.Module):
     """What the two fields share: the box, the grid, the base network and the fused launch."""
 
     def __init__(self, aabb, num_dim, density_activation, density_bias, unbounded, base_resolution, max_resolution, geo_feat_dim,
-                 n_levels, log2_hashmap_size, dtype, interpolation, fused, fused_training=False):
+                 n_levels, log2_hashmap_size, dtype, interpolation, fused, fused_training=False, table_gradient="atomic"):
         super().__init__()
         if not isinstance(aabb, Tensor):
             aabb = torch.tensor(aabb, dtype=torch.float32)
@@ -159,7 +160,7 @@ class _NGPField(nn.Module):
         self.dtype, self.fused, self.fused_training = dtype, bool(fused), bool(fused_training)
         per_level_scale = math.exp((math.log(max_resolution) - math.log(base_resolution)) / (n_levels - 1)) if n_levels > 1 else 1.0
         self.encoding = HashGridEncoding(self.num_dim, n_levels, 2, log2_hashmap_size, base_resolution, per_level_scale, out_dtype=dtype,
-                                         interpolation=interpolation)
+                                         interpolation=interpolation, table_gradient=table_gradient)
         self.mlp_base = FusedMLP(2 * self.n_levels, 1 + self.geo_feat_dim, 64, 1, dtype=dtype)
         self._head_packed = None   # (key, image)
         self._bwd_packed = {}      # head?: (key, image)
@@ -208,7 +209,8 @@ class _NGPField(nn.Module):
 
     def _use_train(self, full: bool, *tensors: Optional[Tensor]) -> bool:
         """The fused training pass serves this query: grad is on and wanted by parameters only."""
-        if not (self.fused_training and torch.is_grad_enabled() and self.fused_supported(full)) or self.encoding.deterministic:
+        if not (self.fused_training and torch.is_grad_enabled() and self.fused_supported(full)) or self.encoding.deterministic \
+                or self.encoding.table_gradient != "atomic":   # (the fused backward scatters per point: the atomic path)
             return False
         ts = [t for t in tensors if t is not None]
         if not self._on_device(ts) or any(t.requires_grad for t in ts):
@@ -314,9 +316,9 @@ class NGPRadianceField(_NGPField):
                  density_activation: Union[str, Callable] = "trunc_exp", unbounded: bool = False, base_resolution: int = 16,
                  max_resolution: int = 4096, geo_feat_dim: int = 15, n_levels: int = 16, log2_hashmap_size: int = 19, *,
                  density_bias: float = -1.0, dtype: torch.dtype = torch.float16, interpolation: str = "Linear", fused: bool = True,
-                 fused_training: bool = False):
+                 fused_training: bool = False, table_gradient: str = "atomic"):
         super().__init__(aabb, num_dim, density_activation, density_bias, unbounded, base_resolution, max_resolution, geo_feat_dim,
-                         n_levels, log2_hashmap_size, dtype, interpolation, fused, fused_training)
+                         n_levels, log2_hashmap_size, dtype, interpolation, fused, fused_training, table_gradient)
         self.use_viewdirs = bool(use_viewdirs)
         if self.use_viewdirs:
             self.direction_encoding = SphericalHarmonicsEncoding(3, 4, out_dtype=dtype)
@@ -395,9 +397,9 @@ class NGPDensityField(_NGPField):
     def __init__(self, aabb: Union[Tensor, List[float]], num_dim: int = 3, density_activation: Union[str, Callable] = "trunc_exp",
                  unbounded: bool = False, base_resolution: int = 16, max_resolution: int = 128, n_levels: int = 5,
                  log2_hashmap_size: int = 17, *, density_bias: float = -1.0, dtype: torch.dtype = torch.float16,
-                 interpolation: str = "Linear", fused: bool = True, fused_training: bool = False):
+                 interpolation: str = "Linear", fused: bool = True, fused_training: bool = False, table_gradient: str = "atomic"):
         super().__init__(aabb, num_dim, density_activation, density_bias, unbounded, base_resolution, max_resolution, 0, n_levels,
-                         log2_hashmap_size, dtype, interpolation, fused, fused_training)
+                         log2_hashmap_size, dtype, interpolation, fused, fused_training, table_gradient)
 
     def forward(self, positions: Tensor) -> Tensor:
         if self._use_train(False, positions):

@@ -30,7 +30,14 @@ times the three native passes of a HashGridEncoding(interpolation=...) next to t
 points: the forward, the backward (table gradient and dL/dx; atomic and deterministic=True) and the second-order pass alone (the
 backward of a dL/dx built with create_graph; atomic and sorted).  All take turns window by window in one process; `*_us` is
 the median over the windows, `*_spread` the (min, max), `*_ratio` the named grid's median over Linear's.  With
-`--interpolation Linear` the second grid is Linear again: the ratios are then the spread of a pass against itself."""
+`--interpolation Linear` the second grid is Linear again: the ratios are then the spread of a pass against itself.
+    python scripts/bench_encodings.py --merged [--dtype bfloat16] [--sizes 18,20] [--reps 10] [--windows 7] [--plans 8,1024,0 ..]
+times the merged table gradient (HashGridEncoding(table_gradient="merged"): nfa_hashgrid_bwd_merged) next to the atomic and the
+sorted one of the same build, on the same inputs: the backward towards the table (zeroing included) on uniform and occgrid
+points, the three taking turns window by window; `*_us` is the median over the windows, `*_spread` the (min, max).  Each
+`--plans ratio,span,cap` adds the merged path under that span rule (the NFA_HG_MERGED_PLAN knob of csrc/hashgrid_merged.hip:
+flush ratio, points per workgroup without LDS, LDS cap in floats; cap 0 is the run merge alone) as `merged[ratio,span,cap]`.
+`merged_vs_sorted_max_abs` and `atomic_vs_sorted_max_abs` are the largest differences from the sorted gradient."""
 import argparse
 import json
 import math
@@ -149,6 +156,46 @@ def deterministic_rows(args, dev, dtype):
                 row.update(alternating_stats({"atomic_bwd_params": lambda: bwd("atomic"), "sorted_bwd_params": lambda: bwd("sorted")},
                                              args.reps, args.windows))
                 row["sorted_over_atomic"] = row["sorted_bwd_params_us"] / row["atomic_bwd_params_us"]
+                print(json.dumps(row), flush=True)
+                del ys
+
+
+def merged_rows(args, dev, dtype):
+    sizes = [1 << int(s) for s in args.sizes.split(",")]
+    torch.manual_seed(0)
+    uni = torch.rand(max(sizes), 3, device=dev)
+    real, _ = occgrid_midpoints(dev, max(sizes))
+    out_dtype = None if dtype == torch.float32 else dtype
+    for cname, cfg in CONFIGS.items():
+        enc, det = sorted_pair(cfg, dev, out_dtype)
+        mer = HashGridEncoding(3, out_dtype=out_dtype, table_gradient="merged", **cfg)
+        mer.params = enc.params
+        L, F = enc.n_levels, enc.n_features_per_level
+        for N in sizes:
+            for pname, pts in (("uniform", uni[:N]), ("occgrid", real[:N])):
+                x = pts.clone()
+                g = torch.randn(N, L * F, device=dev).to(dtype)
+                ys = {"atomic": enc(x), "sorted": det(x), "merged": mer(x)}
+
+                def bwd(k, plan=None):
+                    B.set_tuning("NFA_HG_MERGED_PLAN", plan)
+                    enc.params.grad = None
+                    torch.autograd.backward(ys[k], g, retain_graph=True)
+
+                grads = {}
+                for k in ys:
+                    bwd(k)
+                    grads[k] = enc.params.grad.clone()
+                row = dict(config=cname, points=pname, dtype=str(dtype), N=N, L=L, F=F, grad_max_abs=float(grads["sorted"].abs().max()),
+                           merged_vs_sorted_max_abs=float((grads["merged"] - grads["sorted"]).abs().max()),
+                           atomic_vs_sorted_max_abs=float((grads["atomic"] - grads["sorted"]).abs().max()))
+                fns = {k + "_bwd_params": (lambda k=k: bwd(k)) for k in ys}
+                for plan in args.plans:
+                    fns[f"merged[{plan}]_bwd_params"] = lambda plan=plan: bwd("merged", plan)
+                row.update(alternating_stats(fns, args.reps, args.windows))
+                B.set_tuning("NFA_HG_MERGED_PLAN", None)
+                row["merged_over_atomic"] = row["merged_bwd_params_us"] / row["atomic_bwd_params_us"]
+                row["merged_over_sorted"] = row["merged_bwd_params_us"] / row["sorted_bwd_params_us"]
                 print(json.dumps(row), flush=True)
                 del ys
 
@@ -298,12 +345,16 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--eikonal", action="store_true")
     ap.add_argument("--deterministic", action="store_true")
+    ap.add_argument("--merged", action="store_true")
+    ap.add_argument("--plans", nargs="*", default=[], help="with --merged: span rules ratio,span,cap to time next to the built-in one")
     ap.add_argument("--interpolation", default=None, help="time this interpolation's passes against Linear's")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     B.load()
     if args.interpolation is not None:
         return interpolation_rows(args, dev)
+    if args.merged:
+        return merged_rows(args, dev, getattr(torch, args.dtype))
     if args.deterministic:
         return deterministic_rows(args, dev, getattr(torch, args.dtype))
     if args.eikonal:
