@@ -1529,6 +1529,40 @@ int nfa_ngp_train_bwd(int32_t elem, int32_t full, int32_t mode, const nfa_ngp_gr
 int nfa_ngp_pack_bwd(int32_t elem, int32_t net, const float *params, int32_t n_levels, int32_t geo_feat_dim, void *image,
                      int64_t image_elems, nfa_stream_t stream);
 
+/* ------------------------------------------------------------------ fused NeRF field query (csrc/nerf_field.hip) */
+
+/* The no-grad query of the reference's VanillaNeRFRadianceField (examples/radiance_fields/mlp.py) as one launch: the sinusoidal
+ * encoding of the position (degrees 0 .. 10 with identity: 63 columns), the trunk (63 -> n_hidden x width -> width + 1 with
+ * biases and the reference's skip rule; rows 0 .. width-1 of the merged output matrix are the bottleneck, row width is sigma),
+ * the encoding of the view direction (degrees 0 .. 4 with identity: 27 columns), the colour head (width + 27 -> n_hidden x 128
+ * -> 3 with biases) on [bottleneck, encoded direction], and the output activations.  Nothing is saved for a backward and
+ * nothing between the inputs and the outputs exists in memory.  nfa_nerf_density stops behind sigma's row tile.
+ * trunk, head: nfa_mlp_desc of the two networks.  Limits, checked in this order after elem: trunk width 128 or 256; trunk
+ * n_hidden 1 .. 8; trunk n_in 63; trunk n_out width + 1; trunk bias 1; trunk skip_mask with bits 2 .. n_hidden only; head width
+ * 128; head n_hidden 1 .. 4; head n_in trunk width + 27; head n_out 3; head bias 1; head skip_mask 0; n_points >= 0.
+ * trunk_image: the forward image of nfa_mlp_stream_pack_weights for the trunk; head_image: the image nfa_nerf_pack_head
+ * writes; trunk_bias, head_bias: the float32 biases of all layers in layer order (behind the matrices in the flat parameters).
+ * elem (NFA_ELEM_F16 / NFA_ELEM_BF16) is the type of both images and of every rounding: the encoded rows, every hidden
+ * activation and the bottleneck are rounded once, as the composed modules round them.
+ * in: nfa_ngp_input, positions [n_points, 3] with dirs [n_points, 3] (read by nfa_nerf_field only), or positions NULL and ray
+ * samples, the midpoint and the direction rays_d[r] exactly as nfa_ngp_field forms them.  No box: the field takes world positions.
+ * Outputs, each optional (NULL), at least one: sigma [n_points] and rgb [n_points, 3], float32 or elem (sigma_elem, rgb_elem).
+ * activated 0: the raw values, the float32 accumulators themselves or rounded once to elem.  activated 1: relu(sigma) and
+ * 1 / (1 + expf(-rgb)) in float32 of the raw values rounded to elem (what the modules apply to the networks' elem outputs),
+ * stored as float32 or rounded to elem.  n_points == 0 returns after the checks.
+ * Launch: min(ceil(n_points / NFA_MLP_STREAM_POINTS), NFA_MLP_STREAM_GROUPS) workgroups of 256 lanes, as the streamed passes. */
+int nfa_nerf_field(int32_t elem, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *trunk_image, const void *head_image,
+                   const float *trunk_bias, const float *head_bias, const nfa_ngp_input *in, int64_t n_points, int32_t activated,
+                   void *sigma, int32_t sigma_elem, void *rgb, int32_t rgb_elem, nfa_stream_t stream);
+int nfa_nerf_density(int32_t elem, const nfa_mlp_desc *trunk, const void *trunk_image, const float *trunk_bias, const nfa_ngp_input *in,
+                     int64_t n_points, int32_t activated, void *sigma, int32_t sigma_elem, nfa_stream_t stream);
+/* The head's forward image for nfa_nerf_field from its float32 masters (the flat parameters of (trunk_width + 27, 3, 128,
+ * n_hidden) with biases): nfa_mlp_stream_pack_weights' forward image (image_elems = its fwd_elems), except that layer 0 is
+ * packed as a cat layer whose H part is the trunk_width bottleneck columns (the permuted k order) and whose x part is the 27
+ * direction columns, on k-steps of their own in natural order. */
+int nfa_nerf_pack_head(int32_t elem, const nfa_mlp_desc *head, int32_t trunk_width, const float *params, void *head_image,
+                       int64_t image_elems, nfa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -262,6 +262,10 @@ _SIGS = {
                           C.POINTER(NGPSaved), _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp],
     "nfa_ngp_train_bwd": [_i32, _i32, _i32, C.POINTER(NGPGrid), _vp, _vp, _i32, C.POINTER(NGPInput), _i64, _vp, _vp, _i32, _i32, _f32,
                           C.POINTER(NGPSaved), C.POINTER(NGPGrads), _vp],
+    "nfa_nerf_field": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPDesc), _vp, _vp, _vp, _vp, C.POINTER(NGPInput), _i64, _i32, _vp, _i32, _vp, _i32,
+                       _vp],
+    "nfa_nerf_density": [_i32, C.POINTER(MLPDesc), _vp, _vp, C.POINTER(NGPInput), _i64, _i32, _vp, _i32, _vp],
+    "nfa_nerf_pack_head": [_i32, C.POINTER(MLPDesc), _i32, _vp, _vp, _i64, _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],

@@ -26,7 +26,12 @@ launch's bits; its gradients have the composed chain's rounding points.  Positio
 ``deterministic=True`` or ``table_gradient="merged"`` encoding, ``return_feat=True`` and every configuration outside
 ``fused_supported`` take the composed chain.  ``table_gradient`` is handed to the hash grid (:class:`HashGridEncoding`).
 
-Not part of ``nerfacc_amd.__all__``: ``from nerfacc_amd.fields import NGPRadianceField, NGPDensityField``.
+The reference's vanilla NeRF field (ref: examples/radiance_fields/mlp.py: ``VanillaNeRFRadianceField``) is
+:class:`VanillaNeRFRadianceField` at the end of this module: two :class:`~nerfacc_amd.encodings.SinusoidalEncoding` and a
+:class:`~nerfacc_amd.mlp.NerfMLP`, with the no-grad query as one launch of csrc/nerf_field.hip.
+
+Not part of ``nerfacc_amd.__all__``: ``from nerfacc_amd.fields import NGPRadianceField, NGPDensityField,
+VanillaNeRFRadianceField``.
 """
 from __future__ import annotations
 
@@ -38,8 +43,8 @@ import torch
 from torch import Tensor, nn
 
 from . import _backend as B
-from .encodings import HashGridEncoding, SphericalHarmonicsEncoding
-from .mlp import FusedMLP, image_elems
+from .encodings import HashGridEncoding, SinusoidalEncoding, SphericalHarmonicsEncoding
+from .mlp import FusedMLP, NerfMLP, image_elems
 from .rawrender import DENSITY_ACTIVATIONS, activate_density
 from .samples import _contract_torch, sample_positions
 
@@ -408,3 +413,204 @@ class NGPDensityField(_NGPField):
             return self._launch(False, positions.numel() // 3, positions.shape[:-1], ["density"], positions=positions.reshape(-1, 3))["density"]
         raw, _, selector = self._base(positions)
         return self._activate(raw, selector)
+
+
+# ---------------------------------------------------------------- the vanilla NeRF field (csrc/nerf_field.hip)
+
+NERF_POS_DIMS, NERF_DIR_DIMS = 63, 27   # SinusoidalEncoding(3, 0, 10, True) and (3, 0, 4, True)
+NERF_HEAD_WIDTH, NERF_MAX_HIDDEN, NERF_HEAD_MAX_HIDDEN = 128, 8, 4
+
+
+def nerf_field_limits_error(trunk: Optional[tuple], head: Optional[tuple], trunk_width: int = 0) -> Optional[str]:
+    """What csrc/nerf_field.hip's check_field_shape refuses, in its order and its words; None for networks the fused query
+    holds.  ``trunk`` / ``head``: ``(n_in, n_out, width, n_hidden, bias, skip_mask)`` of struct nfa_mlp_desc, or None."""
+    if trunk is not None:
+        n_in, n_out, w, d, bias, mask = trunk
+        if w not in (128, 256):
+            return f"trunk width {w}: 128 or 256 neurons are supported"
+        if not 1 <= d <= NERF_MAX_HIDDEN:
+            return f"trunk n_hidden {d}: 1 to {NERF_MAX_HIDDEN} hidden layers are supported"
+        if n_in != NERF_POS_DIMS:
+            return f"trunk n_in {n_in}: the encoded position has {NERF_POS_DIMS} features"
+        if n_out != w + 1:
+            return f"trunk n_out {n_out}: width + 1 = {w + 1} outputs (the bottleneck, then sigma)"
+        if bias != 1:
+            return f"trunk bias {bias}: the field's networks have biases (1)"
+        if mask & ~((2 << d) - 4):
+            return (f"trunk skip_mask 0x{mask:x}: only bits 2 to n_hidden ({d}) may be set: layer 0 takes x itself and layer 1 "
+                    "follows it")
+        trunk_width = w
+    if head is not None:
+        n_in, n_out, w, d, bias, mask = head
+        if trunk_width not in (128, 256):
+            return f"trunk width {trunk_width}: 128 or 256 neurons are supported"
+        if w != NERF_HEAD_WIDTH:
+            return f"head width {w}: {NERF_HEAD_WIDTH} neurons are supported"
+        if not 1 <= d <= NERF_HEAD_MAX_HIDDEN:
+            return f"head n_hidden {d}: 1 to {NERF_HEAD_MAX_HIDDEN} hidden layers are supported"
+        if n_in != trunk_width + NERF_DIR_DIMS:
+            return (f"head n_in {n_in}: trunk width + {NERF_DIR_DIMS} = {trunk_width + NERF_DIR_DIMS} inputs (the bottleneck, then the "
+                    "encoded direction)")
+        if n_out != 3:
+            return f"head n_out {n_out}: 3 outputs (the colour)"
+        if bias != 1:
+            return f"head bias {bias}: the field's networks have biases (1)"
+        if mask:
+            return f"head skip_mask 0x{mask:x}: the head has no skip"
+    return None
+
+
+class VanillaNeRFRadianceField(nn.Module):
+    """The reference's vanilla NeRF field (its constructor arguments; ``dtype`` fp16 or bf16 is the networks' type,
+    ``generator`` seeds their initial weights, ``fused=False`` switches the fused dispatch off): ``posi_encoder`` and
+    ``view_encoder`` (:class:`SinusoidalEncoding` of degrees (0, 10) and (0, 4) with identity, ``out_dtype=dtype``) in front of
+    ``mlp`` (:class:`NerfMLP` (63, 27)).  It takes world positions: there is no box and no selector.
+
+    With grad enabled and something that requires it, on CPU tensors, with ``fused=False`` and for a shape outside
+    :meth:`fused_supported` a query runs those native passes in their order (the *composed chain*: encoder, trunk, split,
+    encoder, cat, head, activation).  Under ``torch.no_grad()``, or when nothing requires grad, a supported field on its device
+    takes ONE launch instead (csrc/nerf_field.hip): nothing between the positions and the outputs exists in memory, and
+    ``query_density`` computes one output tile of the trunk instead of nine.  Rounding points are the composed chain's, sigma
+    has its bits; the raw colour may differ in the last bit of a float32 sum (the head's first layer sums in another order).
+    Outputs are ``dtype`` on both paths, as :class:`NerfMLP`'s are.
+
+    ``fused`` is a bool, or a dict ``{"density": bool, "full": bool}`` per query kind (default: both on; DESIGN.md, "Fused NeRF
+    field", has the measurements behind the defaults)."""
+
+    def __init__(self, net_depth: int = 8, net_width: int = 256, skip_layer: Optional[int] = 4, net_depth_condition: int = 1,
+                 net_width_condition: int = 128, dtype: torch.dtype = torch.float16, generator: Optional[torch.Generator] = None,
+                 fused: Union[bool, dict] = True):
+        super().__init__()
+        self.posi_encoder = SinusoidalEncoding(3, 0, 10, True, out_dtype=dtype)
+        self.view_encoder = SinusoidalEncoding(3, 0, 4, True, out_dtype=dtype)
+        self.mlp = NerfMLP(self.posi_encoder.latent_dim, self.view_encoder.latent_dim, net_depth, net_width, skip_layer,
+                           net_depth_condition, net_width_condition, dtype=dtype, generator=generator)
+        self.dtype = dtype
+        self.fused = dict(density=bool(fused), full=bool(fused)) if not isinstance(fused, dict) else \
+            dict(density=bool(fused.get("density", True)), full=bool(fused.get("full", True)))
+        self._head_packed = None   # (key, image)
+
+    # ---------------------------------------------------------------- the fused launch
+
+    def _descs(self):
+        t, h = self.mlp.trunk, self.mlp.head
+        return ((*t._shape, int(t.bias_enabled), t.skip_mask), (*h._shape, int(h.bias_enabled), h.skip_mask))
+
+    def fused_supported(self, full: bool = True) -> bool:
+        """The shapes csrc/nerf_field.hip serves: ``net_width`` 128 or 256, ``net_depth`` 1..8, any ``skip_layer``,
+        ``net_width_condition`` 128, ``net_depth_condition`` 1..4 (the encoders are fixed at the reference's degrees)."""
+        trunk, head = self._descs()
+        return nerf_field_limits_error(trunk, head if full else None) is None
+
+    def _use_fused(self, full: bool, *tensors: Optional[Tensor]) -> bool:
+        if not (self.fused["full" if full else "density"] and self.fused_supported(full)):
+            return False
+        ts = [t for t in tensors if t is not None]
+        dev = self.mlp.trunk.params.device
+        if not (all(t.is_cuda and t.device == dev for t in ts) and all(t.dtype == torch.float32 for t in ts[:4])):
+            return False
+        return not (torch.is_grad_enabled() and any(t.requires_grad for t in [*self.parameters(), *ts]))
+
+    def _head_image(self) -> Tensor:
+        """The head's forward image in the fused launch's k order, rebuilt when the masters change (as StreamedMLP's images)."""
+        h = self.mlp.head
+        p = h.params
+        key = (p.data_ptr(), p._version, p.device)
+        if self._head_packed is None or self._head_packed[0] != key:
+            img = torch.empty(h._image_elems[0], dtype=self.dtype, device=p.device)
+            with torch.cuda.device(p.device):
+                B.call("nfa_nerf_pack_head", B.ELEM_CODES[self.dtype], h._desc, self.mlp.net_width, B.ptr(p), B.ptr(img), img.numel(),
+                       B.stream())
+            self._head_packed = (key, img)
+        return self._head_packed[1]
+
+    def _launch(self, full: bool, n: int, activated: bool, positions=None, dirs=None, rays=None, rgb_dtype=None, sigma_dtype=None):
+        """One fused launch: ``(rgb [n, 3] or None, sigma [n])``, raw or activated, in ``dtype`` unless told otherwise."""
+        t, h = self.mlp.trunk, self.mlp.head
+        dev = t.params.device
+        sigma = torch.empty(n, dtype=sigma_dtype or self.dtype, device=dev)
+        rgb = torch.empty(n, 3, dtype=rgb_dtype or self.dtype, device=dev) if full else None
+        if n == 0:
+            return rgb, sigma
+        keep = [x.contiguous() for x in (rays[:5] if rays is not None else (positions, dirs)) if x is not None]
+        if rays is not None:
+            keep[4] = keep[4] if keep[4].dtype == torch.int64 else keep[4].to(torch.int64)
+            inp = B.NGPInput(None, None, *[B.ptr(x) for x in keep], keep[0].shape[0])
+        else:
+            inp = B.NGPInput(B.ptr(keep[0]), B.ptr(keep[1]) if full else None, None, None, None, None, None, 0)
+        elem = B.ELEM_CODES[self.dtype]
+        with torch.cuda.device(dev):
+            tp = t.params
+            timg = t._images(tp)[0]
+            if full:
+                hp = h.params
+                B.call("nfa_nerf_field", elem, t._desc, h._desc, B.ptr(timg), B.ptr(self._head_image()), t._bias_ptr(tp), h._bias_ptr(hp),
+                       ctypes.byref(inp), n, int(activated), B.ptr(sigma), B.ELEM_CODES[sigma.dtype], B.ptr(rgb), B.ELEM_CODES[rgb.dtype],
+                       B.stream())
+            else:
+                B.call("nfa_nerf_density", elem, t._desc, B.ptr(timg), t._bias_ptr(tp), ctypes.byref(inp), n, int(activated), B.ptr(sigma),
+                       B.ELEM_CODES[sigma.dtype], B.stream())
+        return rgb, sigma
+
+    # ---------------------------------------------------------------- the reference's methods
+
+    def query_density(self, x: Tensor) -> Tensor:
+        if self._use_fused(False, x):
+            return self._launch(False, x.numel() // 3, True, positions=x.reshape(-1, 3))[1].view(*x.shape[:-1], 1)
+        return torch.relu(self.mlp.query_density(self.posi_encoder(x)))
+
+    def query_opacity(self, x: Tensor, step_size) -> Tensor:
+        return self.query_density(x) * step_size   # (small densities: 1 - exp(-density * step_size) is the same)
+
+    def forward(self, x: Tensor, condition: Optional[Tensor] = None):
+        if condition is not None and condition.shape == x.shape and self._use_fused(True, x, condition):
+            rgb, sigma = self._launch(True, x.numel() // 3, True, positions=x.reshape(-1, 3), dirs=condition.reshape(-1, 3))
+            return rgb.view(*x.shape[:-1], 3), sigma.view(*x.shape[:-1], 1)
+        rgb, sigma = self.mlp(self.posi_encoder(x), None if condition is None else self.view_encoder(condition))
+        return torch.sigmoid(rgb), torch.relu(sigma)
+
+    # ---------------------------------------------------------------- the methods in the NGP fields' shape
+
+    def query_raw(self, positions: Tensor, directions: Tensor):
+        """``(raw_rgbs [..., 3], raw_sigmas [...])`` at world positions, before any activation."""
+        if positions.shape == directions.shape and self._use_fused(True, positions, directions):
+            rgb, sigma = self._launch(True, positions.numel() // 3, False, positions=positions.reshape(-1, 3),
+                                      dirs=directions.reshape(-1, 3))
+            return rgb.view(*positions.shape[:-1], 3), sigma.view(positions.shape[:-1])
+        rgb, sigma = self.mlp(self.posi_encoder(positions), self.view_encoder(directions))
+        return rgb, sigma.squeeze(-1)
+
+    def density_on_rays(self, rays_o: Tensor, rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor) -> Tensor:
+        """Densities ``[n]`` at the midpoints of packed ray samples: a trainer's ``sigma_fn``."""
+        if self._use_fused(False, rays_o, rays_d, t_starts, t_ends, ray_indices):
+            return self._launch(False, t_starts.numel(), True, rays=(rays_o, rays_d, t_starts, t_ends, ray_indices))[1]
+        s = sample_positions(rays_o, rays_d, t_starts, t_ends, ray_indices)
+        return self.query_density(s.positions).squeeze(-1)
+
+    def query_on_rays(self, rays_o: Tensor, rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, raw: bool = True):
+        """The field at the midpoints of packed ray samples.  ``raw=True``: ``(raw_rgbs [n, 3], raw_sigmas [n])``, what
+        :func:`nerfacc_amd.rendering_from_raw` takes; otherwise ``(rgbs [n, 3], sigmas [n])`` activated."""
+        if self._use_fused(True, rays_o, rays_d, t_starts, t_ends, ray_indices):
+            return self._launch(True, t_starts.numel(), not raw, rays=(rays_o, rays_d, t_starts, t_ends, ray_indices))
+        s = sample_positions(rays_o, rays_d, t_starts, t_ends, ray_indices, dirs="raw")
+        if raw:
+            return self.query_raw(s.positions, s.dirs)
+        rgb, sigma = self.forward(s.positions, s.dirs)
+        return rgb, sigma.squeeze(-1)
+
+    def load_reference_state_dict(self, sd: dict) -> None:
+        """Takes the reference module's state dict: ``mlp.base.*``, ``mlp.sigma_layer.*``, ``mlp.bottleneck_layer.*``,
+        ``mlp.rgb_layer.*`` (through :meth:`NerfMLP.load_reference_state_dict`) and the encoders' ``scales`` buffers, which
+        must be the reference's ``2^k``.  Any other key, a missing key and a wrong shape raise ``ValueError``."""
+        sd = dict(sd)
+        for name, enc in (("posi_encoder", self.posi_encoder), ("view_encoder", self.view_encoder)):
+            scales = sd.pop(name + ".scales", None)
+            if scales is not None:
+                want = torch.tensor([2.0 ** k for k in range(enc.min_deg, enc.max_deg)], dtype=torch.float64)
+                if scales.numel() != want.numel() or not torch.equal(scales.detach().cpu().double().reshape(-1), want):
+                    raise ValueError(f"VanillaNeRFRadianceField: load_reference_state_dict: '{name}.scales' is not 2^k for k in "
+                                     f"{enc.min_deg} .. {enc.max_deg - 1}")
+        other = sorted(k for k in sd if not k.startswith("mlp."))
+        if other:
+            raise ValueError(f"VanillaNeRFRadianceField: load_reference_state_dict: unexpected keys {other}")
+        self.mlp.load_reference_state_dict({k[len("mlp."):]: v for k, v in sd.items()})
