@@ -1563,6 +1563,37 @@ int nfa_nerf_density(int32_t elem, const nfa_mlp_desc *trunk, const void *trunk_
 int nfa_nerf_pack_head(int32_t elem, const nfa_mlp_desc *head, int32_t trunk_width, const float *params, void *head_image,
                        int64_t image_elems, nfa_stream_t stream);
 
+/* ------------------------------------------------------------------ fused T-NeRF field query (csrc/nerf_field.hip, WARP) */
+
+/* The no-grad query of the reference's TNeRFRadianceField (examples/radiance_fields/mlp.py:248-283) as one launch.
+ * nfa_tnerf_field replaces forward (:279-283): posi_encoder (3, 0, 4) and time_encoder (1, 0, 4) with identity, their cat (36
+ * columns), the warp MLP (36 -> n_hidden x 64 -> 3 with biases and the reference's skip rule), x' = x + warp(...), then
+ * everything nfa_nerf_field does at x'.  nfa_tnerf_density replaces query_density (:273-277; query_opacity :264-271 calls it
+ * after its torch.randint gather) and ends behind sigma's row tile as nfa_nerf_density does.  nfa_tnerf_warp is the warp stage
+ * alone, lines :274-276 / :280-282, and writes x'.
+ * warp: nfa_mlp_desc of the warp network.  Limits, checked in this order after elem and before those of nfa_nerf_field: warp
+ * width 64; warp n_hidden 1 .. 4; warp n_in 36; warp n_out 3; warp bias 1; warp skip_mask with bits 2 .. n_hidden only.
+ * warp_image: the forward image of nfa_mlp_net_pack_weights for the warp network, unchanged (a workgroup keeps it in LDS for
+ * all its passes); warp_bias: its float32 biases in layer order.  trunk, head, their images and biases, elem, in, activated,
+ * sigma, rgb and the launch are nfa_nerf_field's.
+ * times: float32, one per point [n_points] in the position form, one per ray [n_rays] in the ray-sample form, read through
+ * ray_indices next to rays_o / rays_d (an index outside [0, n_rays) yields NaN, as for those).
+ * Rounding: the 36 encoded columns once to elem, every warp activation after its ReLU, the deformation not at all: x' is the
+ * float32 sum of x and the output layer's float32 accumulator, the bits of x + FusedMLP(out float32)(cat(...)).  Behind x' the
+ * rounding points are nfa_nerf_field's.
+ * warped [n_points, 3] float32: x', optional (NULL) for nfa_tnerf_field and nfa_tnerf_density, where sigma or rgb must be asked
+ * for; the one output of nfa_tnerf_warp.  n_points == 0 returns after the checks.
+ * nfa_tnerf_warp launches min(ceil(n_points / 128), 2 NFA_MLP_STREAM_GROUPS) workgroups of 256 lanes, a wave per 32 points. */
+int nfa_tnerf_field(int32_t elem, const nfa_mlp_desc *warp, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *warp_image,
+                    const void *trunk_image, const void *head_image, const float *warp_bias, const float *trunk_bias, const float *head_bias,
+                    const nfa_ngp_input *in, const float *times, int64_t n_points, int32_t activated, void *sigma, int32_t sigma_elem,
+                    void *rgb, int32_t rgb_elem, float *warped, nfa_stream_t stream);
+int nfa_tnerf_density(int32_t elem, const nfa_mlp_desc *warp, const nfa_mlp_desc *trunk, const void *warp_image, const void *trunk_image,
+                      const float *warp_bias, const float *trunk_bias, const nfa_ngp_input *in, const float *times, int64_t n_points,
+                      int32_t activated, void *sigma, int32_t sigma_elem, float *warped, nfa_stream_t stream);
+int nfa_tnerf_warp(int32_t elem, const nfa_mlp_desc *warp, const void *warp_image, const float *warp_bias, const nfa_ngp_input *in,
+                   const float *times, int64_t n_points, float *warped, nfa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

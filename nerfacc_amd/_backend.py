@@ -266,6 +266,11 @@ _SIGS = {
                        _vp],
     "nfa_nerf_density": [_i32, C.POINTER(MLPDesc), _vp, _vp, C.POINTER(NGPInput), _i64, _i32, _vp, _i32, _vp],
     "nfa_nerf_pack_head": [_i32, C.POINTER(MLPDesc), _i32, _vp, _vp, _i64, _vp],
+    "nfa_tnerf_field": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPDesc), C.POINTER(MLPDesc), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(NGPInput), _vp,
+                        _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp],
+    "nfa_tnerf_density": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPDesc), _vp, _vp, _vp, _vp, C.POINTER(NGPInput), _vp, _i64, _i32, _vp, _i32, _vp,
+                          _vp],
+    "nfa_tnerf_warp": [_i32, C.POINTER(MLPDesc), _vp, _vp, C.POINTER(NGPInput), _vp, _i64, _vp, _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],

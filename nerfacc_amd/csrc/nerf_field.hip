@@ -40,6 +40,23 @@
 // NerfMLP's half outputs: relu, and 1 / (1 + expf(-c)).  The trunk sees the composed chain's operands in its order, so sigma
 // has its bits; the head's layer 0 sums its k-steps in another order than load_row8's natural one (bottleneck permuted,
 // direction behind it), so the raw colour may differ in the last bit of a float32 sum.
+//
+// The WARP instantiations are the reference's T-NeRF field (ref: examples/radiance_fields/mlp.py, TNeRFRadianceField): in front
+// of the pass above a wave moves its points by the warp network, x' = x + warp([enc(x), enc(t)]), and x' takes x's place.
+//   warp weights  FusedMLP's packed forward image of (36 -> n_hidden x 64 -> 3), unchanged, RESIDENT in LDS behind the ring, the
+//                 table and the biases, with its float32 biases next to it: copied once per workgroup, read by every pass.  The
+//                 warp stage has no ring traffic and no barrier; a wave runs it at its own pace while the trunk's first piece,
+//                 prefetched by the previous pass's last hand_over, waits in its slot.
+//   warp input    the 36-wide row (x, 12 sines, 12 cosines, t, 4 sines, 4 cosines; zeros up to 48) never exists in memory: three
+//                 B fragments in natural k order, the bits SinusoidalEncoding (3, 0, 4) and (1, 0, 4) store and torch.cat
+//                 joins.  The 12 + 4 sincosf of a point are split between its two lanes (lane half h takes frequencies 2 h and
+//                 2 h + 1 of both encoders) and exchanged: 8 evaluations and 8 exchanges per lane.
+//   chain         mlp.hip's: two row tiles per hidden layer, biases the values the accumulators start from, acc_frag between
+//                 layers, a cat layer's three k-steps on the held input fragments BEHIND its four H k-steps, one output tile.
+//                 Every accumulator sees FusedMLP's operands in FusedMLP's order, so the deformation has its bits.
+//   hand-off      the deformation is registers 0 .. 2 of lane half 0 of the output tile, float32, never rounded; lane half 1
+//                 reads it from the lane 32 away; x' = x + deformation in float32 on both halves.  Lane half 0 stores x' if
+//                 `warped` is asked for (12 contiguous bytes per lane).  nfa_tnerf_warp is this stage alone (tnerf_warp_kernel).
 #include "mlp_tiles.h"
 #include "samples.h"
 
@@ -54,6 +71,9 @@ constexpr int NF_MAX_PIECES = 160;         // 8 * 8 + 9 of the trunk and 4 * 4 +
 constexpr int NF_MAX_HIDDEN = 8, NF_HEAD_MAX_HIDDEN = 4, NF_HEAD_W = 128;
 constexpr int NF_POS_L = 10, NF_DIR_L = 4;                               // the reference's degrees (0, 10) and (0, 4)
 constexpr int NF_POS_DIMS = 3 + 6 * NF_POS_L, NF_DIR_DIMS = 3 + 6 * NF_DIR_L;   // 63 and 27, with identity
+constexpr int NF_WARP_L = 4, NF_WARP_W = 64, NF_WARP_MAX_HIDDEN = 4;   // the reference's warp: degrees (0, 4) of x and of t
+constexpr int NF_WARP_DIMS = 3 + 6 * NF_WARP_L + 1 + 2 * NF_WARP_L;    // 36 = 27 + 9, with both identities
+constexpr int NF_WARP_KQ0 = (NF_WARP_DIMS + 15) / 16;
 static_assert(NF_POINTS == NFA_MLP_STREAM_POINTS, "the streamed passes' split");
 
 struct Piece { int32_t off16, n16; };   // of its image, in 16-byte fragments
@@ -148,6 +168,17 @@ struct NerfArgs {
     int32_t sigma_f32, rgb_f32, activated;
 };
 
+// what a WARP instantiation takes beside them
+struct WarpArgs {
+    Shape S;
+    const uint16_t *img;
+    const float *bias;
+    const float *times;   // [N] in the position form, [n_rays] in the ray-sample form
+    float *warped;        // [N, 3], optional
+    int32_t img16;        // the image in 16-byte fragments
+};
+struct TNerfArgs : NerfArgs { WarpArgs w; };
+
 // ---------------------------------------------------------------- the encoders in registers
 
 // The packed (sin, cos) pairs of all 3 L items (k, d), item 3 k + d, of the lane's point on every lane: lane half h evaluates
@@ -200,6 +231,142 @@ __device__ __forceinline__ void enc_frags(const float (&x)[3], int lane, int h, 
     }
 }
 
+// ---------------------------------------------------------------- the warp stage (WARP instantiations, tnerf_warp_kernel)
+
+// The three B fragments of the warp network's input row [enc(x), enc(t)] in natural k order (header: warp input)
+template <class E>
+__device__ __forceinline__ void warp_frags(const float (&x)[3], float t, int lane, int h, nfa_v4u (&f)[NF_WARP_KQ0])
+{
+    constexpr int L = NF_WARP_L, XD = 3 + 6 * L;
+    uint32_t it[3 * L], xb[3], tt[L];
+    sin_items<E, L>(x, lane, h, it);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) xb[k] = half_bits<E>(x[k]);
+    const int other = (lane ^ 32) << 2;
+#pragma unroll
+    for (int j = 0; j < L / 2; ++j) {
+        const float sc = h ? (float)(1 << (j + L / 2)) : (float)(1 << j);
+        float s, c;
+        sincosf(t * sc, &s, &c);
+        const uint32_t own = pack_halves<E>(s, c);
+        const uint32_t got = (uint32_t)__builtin_amdgcn_ds_bpermute(other, (int)own);
+        tt[j] = h ? got : own;
+        tt[L / 2 + j] = h ? own : got;
+    }
+    const uint32_t tb = half_bits<E>(t);
+    auto col = [&](int c) __attribute__((always_inline)) -> uint32_t {
+        if (c < XD) return enc_col<L>(xb, it, c);
+        if (c == XD) return tb;
+        if (c < XD + 1 + L) return tt[c - XD - 1] & 0xFFFFu;
+        if (c < XD + 1 + 2 * L) return tt[c - XD - 1 - L] >> 16;
+        return 0u;
+    };
+#pragma unroll
+    for (int q = 0; q < NF_WARP_KQ0; ++q) {
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const uint32_t lo = col(16 * q + 2 * d) | (col(16 * q + 2 * d + 1) << 16);
+            const uint32_t hi = col(16 * q + 8 + 2 * d) | (col(16 * q + 8 + 2 * d + 1) << 16);
+            f[q][d] = h ? hi : lo;
+        }
+    }
+}
+
+// floats of the warp's biases in LDS: Shape::lds_bias_floats, layer l at 64 l, the output layer padded to a row tile
+__device__ __forceinline__ void stage_warp(const WarpArgs &w, nfa_v4u *wimg, float *wb)
+{
+    const nfa_v4u *src = reinterpret_cast<const nfa_v4u *>(w.img);
+    for (int i = threadIdx.x; i < w.img16; i += NF_THREADS) wimg[i] = src[i];
+    const int n = w.S.lds_bias_floats();
+    for (int i = threadIdx.x; i < n; i += NF_THREADS) wb[i] = i - w.S.n_hidden * NF_WARP_W < 3 ? w.bias[i] : 0.f;
+}
+
+// x <- x + warp([enc(x), enc(t)]) for the wave's 32 points, on both lane halves (header: chain, hand-off).  No barrier.
+template <class E>
+__device__ __forceinline__ void warp_stage(const Shape &S, const nfa_v4u *wimg, const float *wb, float (&x)[3], float t, int lane_)
+{
+    constexpr int W = NF_WARP_W, MT = W / 32, KQ = W / 16, KQ0 = NF_WARP_KQ0;
+    // The stage's per-lane addresses and selects are formed from a lane index the compiler cannot see through: hoisted out of
+    // the pass loop they would stay live across the trunk and the head, and W = 128 would lose its second wave per SIMD.
+    int lane = lane_;
+    asm volatile("" : "+v"(lane));
+    const int h = lane >> 5;
+    nfa_v4u xf[KQ0];
+    warp_frags<E>(x, t, lane, h, xf);
+    f32x16 acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        init_acc(acc[m], true, wb + 32 * m, h);
+#pragma unroll
+        for (int q = 0; q < KQ0; ++q) acc[m] = mfma<E>(wimg[(m * KQ0 + q) * 64 + lane], xf[q], acc[m]);
+    }
+    int off16 = MT * KQ0 * 64;
+    nfa_v4u hf[KQ];
+    for (int l = 1;; ++l) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[m][i] = acc[m][i] < 0.f ? 0.f : acc[m][i];
+            hf[2 * m] = acc_frag<E>(acc[m], 0);
+            hf[2 * m + 1] = acc_frag<E>(acc[m], 1);
+        }
+        if (l == S.n_hidden) break;
+        const bool cat = S.cat(l);
+        const int kql = KQ + (cat ? KQ0 : 0);
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const nfa_v4u *A = wimg + off16 + m * kql * 64 + lane;
+            init_acc(acc[m], true, wb + l * W + 32 * m, h);
+#pragma unroll
+            for (int q = 0; q < KQ; ++q) acc[m] = mfma<E>(A[q * 64], hf[q], acc[m]);
+            if (cat) {
+#pragma unroll
+                for (int q = 0; q < KQ0; ++q) acc[m] = mfma<E>(A[(KQ + q) * 64], xf[q], acc[m]);
+            }
+        }
+        off16 += MT * kql * 64;
+    }
+    f32x16 o;
+    init_acc(o, true, wb + S.n_hidden * W, h);
+    const nfa_v4u *A = wimg + off16 + lane;
+#pragma unroll
+    for (int q = 0; q < KQ; ++q) o = mfma<E>(A[q * 64], hf[q], o);
+    if (S.cat(S.n_hidden)) {
+#pragma unroll
+        for (int q = 0; q < KQ0; ++q) o = mfma<E>(A[(KQ + q) * 64], xf[q], o);
+    }
+    const int other = (lane ^ 32) << 2;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {   // rows 0 .. 2 of the tile: registers 0 .. 2 of lane half 0
+        const float got = __int_as_float(__builtin_amdgcn_ds_bpermute(other, __float_as_int(o[k])));
+        x[k] = x[k] + (h ? got : o[k]);
+    }
+}
+
+// the point of a lane and its time (and, FULL, its direction) in either input form
+template <bool RAYS, bool DIRS, class A>
+__device__ __forceinline__ void load_point(const A &a, const float *times, int64_t pc, float (&x)[3], float (&dir)[3], float &t)
+{
+    if constexpr (RAYS) {
+        float ro[3];
+        const int64_t ray = a.ri[pc];
+        ray_rows(a.o, a.d, ray, a.n_rays, ro, dir);
+        sample_point(ro, dir, a.ts[pc], a.te[pc], x);
+        if (times) {
+            const bool ok = (uint64_t)ray < (uint64_t)a.n_rays;
+            const float v = times[ok ? ray : 0];
+            t = ok ? v : __builtin_nanf("");
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            x[k] = a.x[3 * pc + k];
+            if constexpr (DIRS) dir[k] = a.dirs[3 * pc + k];
+        }
+        if (times) t = times[pc];
+    }
+}
+
 // an output value: raw (the accumulator, rounded once if the output is the half type) or activated (header)
 template <class E>
 __device__ __forceinline__ void put_out(void *out, bool out_f32, int64_t i, float v, bool activated, bool colour)
@@ -215,8 +382,10 @@ __device__ __forceinline__ void put_out(void *out, bool out_f32, int64_t i, floa
 // ---------------------------------------------------------------- the query
 
 // W: the trunk's width.  RAYS: the ray-sample input form.  FULL: sigma and colour; otherwise the pass ends with sigma's tile.
-template <class E, int W, bool RAYS, bool FULL>
-__global__ __launch_bounds__(NF_THREADS) void nerf_field_kernel(const NerfArgs a)
+// WARP: the T-NeRF field, the warp stage in front of every pass; the instantiations without it never see WarpArgs.
+// A W = 128 WARP instantiation asks for the two waves per SIMD its plain twin has by itself (1: no request).
+template <class E, int W, bool RAYS, bool FULL, bool WARP = false>
+__global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP && W == 128 ? 2 : 1))) void nerf_field_kernel(const std::conditional_t<WARP, TNerfArgs, NerfArgs> a)
 {
     constexpr int MT = W / 32, KQ = W / 16, KQX = (NF_POS_DIMS + 15) / 16, KQD = (NF_DIR_DIMS + 15) / 16;
     constexpr int HW = NF_HEAD_W, HMT = HW / 32, HKQ = HW / 16;
@@ -233,6 +402,12 @@ __global__ __launch_bounds__(NF_THREADS) void nerf_field_kernel(const NerfArgs a
     float *hb = tb + n_tb;
     for (int i = threadIdx.x; i < n_tb; i += NF_THREADS) tb[i] = i - D * W < W + 1 ? a.tbias[i] : 0.f;
     for (int i = threadIdx.x; i < n_hb; i += NF_THREADS) hb[i] = i - Dc * HW < 3 ? a.hbias[i] : 0.f;
+    nfa_v4u *wimg = reinterpret_cast<nfa_v4u *>(hb + n_hb);   // WARP: the resident image, 16-byte aligned (every part before it is)
+    float *wb = nullptr;
+    if constexpr (WARP) {
+        wb = reinterpret_cast<float *>(wimg + a.w.img16);
+        stage_warp(a.w, wimg, wb);   // ring.start()'s barriers publish it
+    }
     FieldRing<MAXV> ring;
     if (threadIdx.x == 0) nerf_pieces(T, H, FULL, tab, nullptr, nullptr);
     ring.timg = reinterpret_cast<const nfa_v4u *>(a.timg);
@@ -247,17 +422,16 @@ __global__ __launch_bounds__(NF_THREADS) void nerf_field_kernel(const NerfArgs a
     for (int64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
         const int64_t p = (pass * NF_WAVES + wave) * 32 + r, pc = p < N ? p : N - 1;
         // ---- the point and both encoded rows, before layer 0's first fetch
-        float x[3], dir[3] = {0.f, 0.f, 0.f};
-        if constexpr (RAYS) {
-            float ro[3];
-            ray_rows(a.o, a.d, a.ri[pc], a.n_rays, ro, dir);
-            sample_point(ro, dir, a.ts[pc], a.te[pc], x);
-        } else {
+        float x[3], dir[3] = {0.f, 0.f, 0.f}, t = 0.f;
+        if constexpr (WARP) {
+            load_point<RAYS, FULL>(a, a.w.times, pc, x, dir, t);
+            warp_stage<E>(a.w.S, wimg, wb, x, t, lane);
+            if (a.w.warped && h == 0 && p < N) {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                x[k] = a.x[3 * pc + k];
-                if constexpr (FULL) dir[k] = a.dirs[3 * pc + k];
+                for (int k = 0; k < 3; ++k) a.w.warped[3 * p + k] = x[k];
             }
+        } else {
+            load_point<RAYS, FULL>(a, nullptr, pc, x, dir, t);
         }
         nfa_v4u xf[KQX], df[KQD];
         enc_frags<E, NF_POS_L, KQX>(x, lane, h, xf);
@@ -372,6 +546,29 @@ __global__ __launch_bounds__(NF_THREADS) void nerf_field_kernel(const NerfArgs a
     }
 }
 
+// The warp stage alone (nfa_tnerf_warp): a wave per 32-point tile, the image resident as above, x' to memory.
+template <class E, bool RAYS>
+__global__ __launch_bounds__(NF_THREADS) void tnerf_warp_kernel(const TNerfArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char nf_lds[];
+    nfa_v4u *wimg = reinterpret_cast<nfa_v4u *>(nf_lds);
+    float *wb = reinterpret_cast<float *>(wimg + a.w.img16);
+    stage_warp(a.w, wimg, wb);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int64_t N = a.N, n_tiles = ceil_div64(N, 32);
+    for (int64_t tile = (int64_t)blockIdx.x * NF_WAVES + wave; tile < n_tiles; tile += (int64_t)gridDim.x * NF_WAVES) {
+        const int64_t p = tile * 32 + r, pc = p < N ? p : N - 1;
+        float x[3], dir[3], t = 0.f;
+        load_point<RAYS, false>(a, a.w.times, pc, x, dir, t);
+        warp_stage<E>(a.w.S, wimg, wb, x, t, lane);
+        if (h == 0 && p < N) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a.w.warped[3 * p + k] = x[k];
+        }
+    }
+}
+
 // The head's forward image: mlp_pack_kernel's image of (tw + 27 -> Dc x 128 -> 3), except that layer 0 is a cat layer whose H
 // part is the trunk's tw bottleneck columns in the permuted k order and whose x part, the 27 direction columns, starts on a
 // k-step of its own in natural order.  tw is a multiple of 16, so the sizes are those of the plain shape.
@@ -438,9 +635,48 @@ int check_field_shape(const char *who, int32_t elem, const nfa_mlp_desc *trunk, 
     return NFA_OK;
 }
 
+// The one statement of the warp networks the T-NeRF entries hold (nerfacc_amd/fields.py: tnerf_field_limits_error says the same
+// words), checked after elem and before the trunk and the head.
+int check_warp_shape(const char *who, int32_t elem, const nfa_mlp_desc *warp, Shape *S)
+{
+    NFA_REQUIRE(elem == NFA_ELEM_F16 || elem == NFA_ELEM_BF16, "%s: elem %d: the networks' type is NFA_ELEM_F16 or NFA_ELEM_BF16", who, elem);
+    NFA_REQUIRE(warp, "%s: the network descriptor is null", who);
+    const int d = warp->n_hidden;
+    NFA_REQUIRE(warp->width == NF_WARP_W, "%s: warp width %d: %d neurons are supported", who, warp->width, NF_WARP_W);
+    NFA_REQUIRE(d >= 1 && d <= NF_WARP_MAX_HIDDEN, "%s: warp n_hidden %d: 1 to %d hidden layers are supported", who, d, NF_WARP_MAX_HIDDEN);
+    NFA_REQUIRE(warp->n_in == NF_WARP_DIMS, "%s: warp n_in %d: the encoded position and time have %d features", who, warp->n_in, NF_WARP_DIMS);
+    NFA_REQUIRE(warp->n_out == 3, "%s: warp n_out %d: 3 outputs (the deformation)", who, warp->n_out);
+    NFA_REQUIRE(warp->bias == 1, "%s: warp bias %d: the field's networks have biases (1)", who, warp->bias);
+    NFA_REQUIRE((warp->skip_mask & ~((2 << d) - 4)) == 0, "%s: warp skip_mask 0x%x: only bits 2 to n_hidden (%d) may be set: layer 0 "
+                "takes x itself and layer 1 follows it", who, (unsigned)warp->skip_mask, d);
+    *S = Shape{NF_WARP_DIMS, 3, NF_WARP_W, d, 1, warp->skip_mask};
+    return NFA_OK;
+}
+
+// bytes of the resident warp image and its biases in LDS
+int64_t warp_lds_bytes(const Shape &S) { return S.fwd_off(S.layers()) * 2 + (int64_t)S.lds_bias_floats() * 4; }
+
+int check_warp_pointers(const char *who, const WarpArgs &w)
+{
+    NFA_REQUIRE(w.img && w.bias && w.times, "%s: null pointer (warp image, warp bias or times)", who);
+    NFA_REQUIRE(aligned_to(w.img, 16) && aligned_to(w.bias, 4) && aligned_to(w.times, 4) && aligned_to(w.warped, 4),
+                "%s: misaligned pointer (warp image 16, warp bias, times and warped 4)", who);
+    return NFA_OK;
+}
+
+WarpArgs warp_args(const Shape &S, const void *image, const float *bias, const float *times, float *warped)
+{
+    WarpArgs w = {};
+    w.S = S;
+    w.img = static_cast<const uint16_t *>(image), w.bias = bias, w.times = times, w.warped = warped;
+    w.img16 = (int32_t)(S.fwd_off(S.layers()) / 8);
+    return w;
+}
+
 int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *trunk_image,
                const void *head_image, const float *trunk_bias, const float *head_bias, const nfa_ngp_input *in, int64_t N,
-               int32_t activated, void *sigma, int32_t sigma_elem, void *rgb, int32_t rgb_elem, nfa_stream_t stream)
+               int32_t activated, void *sigma, int32_t sigma_elem, void *rgb, int32_t rgb_elem, nfa_stream_t stream,
+               const WarpArgs *warp = nullptr)   // the T-NeRF entries: S checked, the pointers as the caller gave them
 {
     Shape T, H = {};
     if (int rc = check_field_shape(who, elem, trunk, head, 0, N, &T, full ? &H : nullptr)) return rc;
@@ -460,6 +696,8 @@ int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *tru
                 aligned_to(in->t_starts, 4) && aligned_to(in->t_ends, 4) && aligned_to(in->ray_indices, 8) &&
                 aligned_to(sigma, sigma_elem == NFA_ELEM_F32 ? 4 : 2) && aligned_to(rgb, rgb_elem == NFA_ELEM_F32 ? 4 : 2),
                 "%s: misaligned pointer (images 16, ray_indices 8, the others their element)", who);
+    if (warp)
+        if (int rc = check_warp_pointers(who, *warp)) return rc;
     NerfArgs a = {};
     a.T = T, a.H = H;
     a.timg = static_cast<const uint16_t *>(trunk_image), a.himg = static_cast<const uint16_t *>(head_image);
@@ -473,18 +711,28 @@ int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *tru
     a.sigma = sigma, a.sigma_f32 = sigma_elem == NFA_ELEM_F32;
     a.rgb = full ? rgb : nullptr, a.rgb_f32 = rgb_elem == NFA_ELEM_F32;
     a.activated = activated;
-    const int64_t lds = nerf_lds_bytes(slot16, trunk_bias_floats(T) + (full ? head_bias_floats(H) : 0));
+    const int64_t lds = nerf_lds_bytes(slot16, trunk_bias_floats(T) + (full ? head_bias_floats(H) : 0)) + (warp ? warp_lds_bytes(warp->S) : 0);
     const int64_t want = ceil_div64(N, NF_POINTS);
     const unsigned grid = (unsigned)(want < NFA_MLP_STREAM_GROUPS ? want : NFA_MLP_STREAM_GROUPS);
     int rc = NFA_OK;
-    auto launch = [&](auto tag, auto w, auto rays_c, auto full_c) {
+    auto launch = [&](auto tag, auto w, auto rays_c, auto full_c, auto warp_c) {
         using E = typename decltype(tag)::type;
-        auto kern = nerf_field_kernel<E, decltype(w)::value, decltype(rays_c)::value, decltype(full_c)::value>;
+        constexpr bool WARP = decltype(warp_c)::value;
+        auto kern = nerf_field_kernel<E, decltype(w)::value, decltype(rays_c)::value, decltype(full_c)::value, WARP>;
         if ((rc = allow_lds(who, kern, lds)) != NFA_OK) return;
-        kern<<<grid, NF_THREADS, (size_t)lds, as_stream(stream)>>>(a);
+        if constexpr (WARP) {
+            TNerfArgs ta = {};
+            static_cast<NerfArgs &>(ta) = a;
+            ta.w = *warp;
+            kern<<<grid, NF_THREADS, (size_t)lds, as_stream(stream)>>>(ta);
+        } else {
+            kern<<<grid, NF_THREADS, (size_t)lds, as_stream(stream)>>>(a);
+        }
     };
     auto by_form = [&](auto tag, auto w) {
-        dispatch_bool(rays, [&](auto rays_c) { dispatch_bool(full, [&](auto full_c) { launch(tag, w, rays_c, full_c); }); });
+        dispatch_bool(rays, [&](auto rays_c) {
+            dispatch_bool(full, [&](auto full_c) { dispatch_bool(warp != nullptr, [&](auto warp_c) { launch(tag, w, rays_c, full_c, warp_c); }); });
+        });
     };
     auto by_width = [&](auto tag) {
         if (T.W == 128) by_form(tag, std::integral_constant<int, 128>{});
@@ -535,6 +783,65 @@ int nfa_nerf_field(int32_t elem, const nfa_mlp_desc *trunk, const nfa_mlp_desc *
 {
     return nerf_query("nfa_nerf_field", true, elem, trunk, head, trunk_image, head_image, trunk_bias, head_bias, in, n_points, activated, sigma,
                       sigma_elem, rgb, rgb_elem, stream);
+}
+
+int nfa_tnerf_field(int32_t elem, const nfa_mlp_desc *warp, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *warp_image,
+                    const void *trunk_image, const void *head_image, const float *warp_bias, const float *trunk_bias, const float *head_bias,
+                    const nfa_ngp_input *in, const float *times, int64_t n_points, int32_t activated, void *sigma, int32_t sigma_elem,
+                    void *rgb, int32_t rgb_elem, float *warped, nfa_stream_t stream)
+{
+    const char *who = "nfa_tnerf_field";
+    Shape S;
+    if (int rc = check_warp_shape(who, elem, warp, &S)) return rc;
+    const WarpArgs w = warp_args(S, warp_image, warp_bias, times, warped);
+    return nerf_query(who, true, elem, trunk, head, trunk_image, head_image, trunk_bias, head_bias, in, n_points, activated, sigma, sigma_elem,
+                      rgb, rgb_elem, stream, &w);
+}
+
+int nfa_tnerf_density(int32_t elem, const nfa_mlp_desc *warp, const nfa_mlp_desc *trunk, const void *warp_image, const void *trunk_image,
+                      const float *warp_bias, const float *trunk_bias, const nfa_ngp_input *in, const float *times, int64_t n_points,
+                      int32_t activated, void *sigma, int32_t sigma_elem, float *warped, nfa_stream_t stream)
+{
+    const char *who = "nfa_tnerf_density";
+    Shape S;
+    if (int rc = check_warp_shape(who, elem, warp, &S)) return rc;
+    const WarpArgs w = warp_args(S, warp_image, warp_bias, times, warped);
+    return nerf_query(who, false, elem, trunk, nullptr, trunk_image, nullptr, trunk_bias, nullptr, in, n_points, activated, sigma, sigma_elem,
+                      nullptr, NFA_ELEM_F32, stream, &w);
+}
+
+int nfa_tnerf_warp(int32_t elem, const nfa_mlp_desc *warp, const void *warp_image, const float *warp_bias, const nfa_ngp_input *in,
+                   const float *times, int64_t n_points, float *warped, nfa_stream_t stream)
+{
+    const char *who = "nfa_tnerf_warp";
+    Shape S;
+    if (int rc = check_warp_shape(who, elem, warp, &S)) return rc;
+    NFA_REQUIRE(n_points >= 0, "%s: n_points %lld is negative", who, (long long)n_points);
+    NFA_REQUIRE(in, "%s: the input descriptor is null", who);
+    if (n_points == 0) return NFA_OK;
+    const bool rays = in->positions == nullptr;
+    NFA_REQUIRE(!rays || (in->n_rays >= 1 && in->n_rays < ((int64_t)1 << 31) - 64), "%s: n_rays %lld out of range", who, (long long)in->n_rays);
+    NFA_REQUIRE(!rays || (in->rays_o && in->rays_d && in->t_starts && in->t_ends && in->ray_indices),
+                "%s: null input pointer (positions, or rays_o, rays_d, t_starts, t_ends and ray_indices)", who);
+    NFA_REQUIRE(warped, "%s: no output requested", who);
+    NFA_REQUIRE(aligned_to(in->positions, 4) && aligned_to(in->rays_o, 4) && aligned_to(in->rays_d, 4) && aligned_to(in->t_starts, 4) &&
+                aligned_to(in->t_ends, 4) && aligned_to(in->ray_indices, 8), "%s: misaligned pointer (ray_indices 8, the others their element)", who);
+    TNerfArgs a = {};
+    a.w = warp_args(S, warp_image, warp_bias, times, warped);
+    if (int rc = check_warp_pointers(who, a.w)) return rc;
+    a.x = in->positions;
+    a.o = in->rays_o, a.d = in->rays_d, a.ts = in->t_starts, a.te = in->t_ends, a.ri = in->ray_indices;
+    a.n_rays = in->n_rays, a.N = n_points;
+    const int64_t lds = warp_lds_bytes(S), want = ceil_div64(n_points, NF_POINTS);
+    const unsigned grid = (unsigned)(want < 2 * NFA_MLP_STREAM_GROUPS ? want : 2 * NFA_MLP_STREAM_GROUPS);   // 42 KiB: two workgroups a CU and more
+    dispatch_bool(elem == NFA_ELEM_F16, [&](auto f16) {
+        using E = std::conditional_t<decltype(f16)::value, nfa_f16, nfa_bf16>;
+        dispatch_bool(rays, [&](auto rays_c) {
+            tnerf_warp_kernel<E, decltype(rays_c)::value><<<grid, NF_THREADS, (size_t)lds, as_stream(stream)>>>(a);
+        });
+    });
+    NFA_CHECK_LAUNCH(who);
+    return NFA_OK;
 }
 
 }  // extern "C"

@@ -28,10 +28,12 @@ launch's bits; its gradients have the composed chain's rounding points.  Positio
 
 The reference's vanilla NeRF field (ref: examples/radiance_fields/mlp.py: ``VanillaNeRFRadianceField``) is
 :class:`VanillaNeRFRadianceField` at the end of this module: two :class:`~nerfacc_amd.encodings.SinusoidalEncoding` and a
-:class:`~nerfacc_amd.mlp.NerfMLP`, with the no-grad query as one launch of csrc/nerf_field.hip.
+:class:`~nerfacc_amd.mlp.NerfMLP`, with the no-grad query as one launch of csrc/nerf_field.hip.  Its dynamic-scene field
+(``TNeRFRadianceField``) is :class:`TNeRFRadianceField` behind it: a warp network in front of the vanilla field, the no-grad query
+one launch of the same kernel with a warp stage.
 
 Not part of ``nerfacc_amd.__all__``: ``from nerfacc_amd.fields import NGPRadianceField, NGPDensityField,
-VanillaNeRFRadianceField``.
+VanillaNeRFRadianceField, TNeRFRadianceField``.
 """
 from __future__ import annotations
 
@@ -44,7 +46,7 @@ from torch import Tensor, nn
 
 from . import _backend as B
 from .encodings import HashGridEncoding, SinusoidalEncoding, SphericalHarmonicsEncoding
-from .mlp import FusedMLP, NerfMLP, image_elems
+from .mlp import FusedMLP, NerfMLP, image_elems, reference_mlp
 from .rawrender import DENSITY_ACTIVATIONS, activate_density
 from .samples import _contract_torch, sample_positions
 
@@ -614,3 +616,207 @@ class VanillaNeRFRadianceField(nn.Module):
         if other:
             raise ValueError(f"VanillaNeRFRadianceField: load_reference_state_dict: unexpected keys {other}")
         self.mlp.load_reference_state_dict({k[len("mlp."):]: v for k, v in sd.items()})
+
+
+# ---------------------------------------------------------------- the T-NeRF field (csrc/nerf_field.hip, the WARP instantiations)
+
+TNERF_WARP_DIMS, TNERF_WARP_WIDTH, TNERF_WARP_MAX_HIDDEN = 36, 64, 4   # SinusoidalEncoding(3, 0, 4, True) and (1, 0, 4, True)
+
+
+def tnerf_field_limits_error(warp: tuple, trunk: Optional[tuple], head: Optional[tuple]) -> Optional[str]:
+    """What csrc/nerf_field.hip's check_warp_shape and then check_field_shape refuse, in their order and their words; None
+    for networks the fused T-NeRF query holds.  Each: ``(n_in, n_out, width, n_hidden, bias, skip_mask)``, or None."""
+    n_in, n_out, w, d, bias, mask = warp
+    if w != TNERF_WARP_WIDTH:
+        return f"warp width {w}: {TNERF_WARP_WIDTH} neurons are supported"
+    if not 1 <= d <= TNERF_WARP_MAX_HIDDEN:
+        return f"warp n_hidden {d}: 1 to {TNERF_WARP_MAX_HIDDEN} hidden layers are supported"
+    if n_in != TNERF_WARP_DIMS:
+        return f"warp n_in {n_in}: the encoded position and time have {TNERF_WARP_DIMS} features"
+    if n_out != 3:
+        return f"warp n_out {n_out}: 3 outputs (the deformation)"
+    if bias != 1:
+        return f"warp bias {bias}: the field's networks have biases (1)"
+    if mask & ~((2 << d) - 4):
+        return f"warp skip_mask 0x{mask:x}: only bits 2 to n_hidden ({d}) may be set: layer 0 takes x itself and layer 1 follows it"
+    return nerf_field_limits_error(trunk, head)
+
+
+class TNeRFRadianceField(nn.Module):
+    """The reference's dynamic-scene field (ref: examples/radiance_fields/mlp.py: ``TNeRFRadianceField``, the field of
+    ``train_mlp_tnerf.py``): ``posi_encoder`` and ``time_encoder`` (:class:`SinusoidalEncoding` (3, 0, 4) and (1, 0, 4) with
+    identity, ``out_dtype=dtype``) feed ``warp`` (:func:`reference_mlp` (36, 3, 4, 64, skip_layer 2), float32 output, its output
+    layer initialised ``uniform_(0, 1e-4)`` with a zero bias as in the reference), and ``nerf``
+    (:class:`VanillaNeRFRadianceField`) is queried at ``x + warp(cat(posi_encoder(x), time_encoder(t)))``.  The deformation is
+    never rounded to the half type: the sum is float32.
+
+    With grad enabled and something that requires it, on CPU tensors, with ``fused=False`` and for a shape outside
+    :meth:`fused_supported` a query runs the native passes in their order (the *composed chain*: two encoders, ``cat``,
+    :class:`FusedMLP`, add, then ``nerf``'s own methods), which trains: the warp network's gradients come through the trunk's
+    ``dL/dx`` and the position encoder's backward.  Under ``torch.no_grad()``, or when nothing requires grad, a supported field
+    takes ONE launch (csrc/nerf_field.hip, the WARP instantiations): the warp network's image stays in LDS, and nothing between
+    ``(x, t, dir)``, or a ray sample and its ray's timestamp, and the outputs exists in memory.  The warped positions and sigma
+    are the composed chain's bits; the raw colour carries the vanilla field's one last-bit difference.
+
+    ``fused`` is a bool or ``{"density": bool, "full": bool}`` (:meth:`warped_positions` follows ``"density"``); it is handed
+    to ``nerf`` as well.  DESIGN.md, "Fused T-NeRF field", has the measurements behind the defaults."""
+
+    def __init__(self, dtype: torch.dtype = torch.float16, generator: Optional[torch.Generator] = None, fused: Union[bool, dict] = True):
+        super().__init__()
+        self.posi_encoder = SinusoidalEncoding(3, 0, 4, True, out_dtype=dtype)
+        self.time_encoder = SinusoidalEncoding(1, 0, 4, True, out_dtype=dtype)
+        self.warp = reference_mlp(self.posi_encoder.latent_dim + self.time_encoder.latent_dim, 3, 4, 64, 2, dtype=dtype,
+                                  out_dtype=torch.float32, generator=generator)
+        with torch.no_grad():   # output_init=functools.partial(torch.nn.init.uniform_, b=1e-4); the bias is zero already
+            out = self.warp.weight(self.warp.n_hidden_layers)
+            out.copy_(torch.rand(out.shape, generator=generator or torch.Generator().manual_seed(1337)) * 1e-4)
+        self.nerf = VanillaNeRFRadianceField(dtype=dtype, generator=generator, fused=fused)
+        self.dtype = dtype
+        self.fused = dict(self.nerf.fused)
+
+    # ---------------------------------------------------------------- the fused launch
+
+    def fused_supported(self, full: bool = True) -> bool:
+        """The shapes csrc/nerf_field.hip serves with a warp stage: the warp network (36, 3, 64, 1..4 hidden layers, biases,
+        any skip) in front of what :meth:`VanillaNeRFRadianceField.fused_supported` lists."""
+        w = self.warp
+        trunk, head = self.nerf._descs()
+        return tnerf_field_limits_error((*w._shape, int(w.bias_enabled), w.skip_mask), trunk, head if full else None) is None
+
+    def _use_fused(self, full: bool, *tensors: Optional[Tensor]) -> bool:
+        if not (self.fused["full" if full else "density"] and self.fused_supported(full)):
+            return False
+        ts = [t for t in tensors if t is not None]
+        dev = self.warp.params.device
+        if not (all(t.is_cuda and t.device == dev for t in ts) and all(t.dtype == torch.float32 for t in ts if t.is_floating_point())):
+            return False
+        return not (torch.is_grad_enabled() and any(t.requires_grad for t in [*self.parameters(), *ts]))
+
+    def _launch(self, kind: str, n: int, activated: bool = False, positions=None, times=None, dirs=None, rays=None, warped: bool = False,
+                rgb_dtype=None, sigma_dtype=None):
+        """One fused launch.  ``kind``: ``"full"``: ``(rgb [n, 3], sigma [n], warped [n, 3] or None)``; ``"density"``:
+        ``(None, sigma, warped or None)``; ``"warp"``: ``(None, None, warped)``.  ``times``: [n] with ``positions``, [n_rays]
+        with ``rays``."""
+        full = kind == "full"
+        w, t, h = self.warp, self.nerf.mlp.trunk, self.nerf.mlp.head
+        dev = w.params.device
+        sigma = torch.empty(n, dtype=sigma_dtype or self.dtype, device=dev) if kind != "warp" else None
+        rgb = torch.empty(n, 3, dtype=rgb_dtype or self.dtype, device=dev) if full else None
+        xw = torch.empty(n, 3, dtype=torch.float32, device=dev) if warped or kind == "warp" else None
+        if n == 0:
+            return rgb, sigma, xw
+        keep = [x.contiguous() for x in (rays[:5] if rays is not None else (positions, dirs)) if x is not None]
+        times = times.contiguous()
+        if rays is not None:
+            keep[4] = keep[4] if keep[4].dtype == torch.int64 else keep[4].to(torch.int64)
+            inp = B.NGPInput(None, None, *[B.ptr(x) for x in keep], keep[0].shape[0])
+        else:
+            inp = B.NGPInput(B.ptr(keep[0]), B.ptr(keep[1]) if full else None, None, None, None, None, None, 0)
+        elem = B.ELEM_CODES[self.dtype]
+        with torch.cuda.device(dev):
+            wp, tp = w.params, t.params
+            wimg = w._images(wp)[0]
+            if kind == "warp":
+                B.call("nfa_tnerf_warp", elem, w._desc, B.ptr(wimg), w._bias_ptr(wp), ctypes.byref(inp), B.ptr(times), n, B.ptr(xw),
+                       B.stream())
+                return rgb, sigma, xw
+            timg = t._images(tp)[0]
+            if full:
+                hp = h.params
+                B.call("nfa_tnerf_field", elem, w._desc, t._desc, h._desc, B.ptr(wimg), B.ptr(timg), B.ptr(self.nerf._head_image()),
+                       w._bias_ptr(wp), t._bias_ptr(tp), h._bias_ptr(hp), ctypes.byref(inp), B.ptr(times), n, int(activated), B.ptr(sigma),
+                       B.ELEM_CODES[sigma.dtype], B.ptr(rgb), B.ELEM_CODES[rgb.dtype], B.ptr(xw) if xw is not None else None, B.stream())
+            else:
+                B.call("nfa_tnerf_density", elem, w._desc, t._desc, B.ptr(wimg), B.ptr(timg), w._bias_ptr(wp), t._bias_ptr(tp),
+                       ctypes.byref(inp), B.ptr(times), n, int(activated), B.ptr(sigma), B.ELEM_CODES[sigma.dtype],
+                       B.ptr(xw) if xw is not None else None, B.stream())
+        return rgb, sigma, xw
+
+    @staticmethod
+    def _point_times(x: Tensor, t: Tensor) -> bool:
+        """One timestamp per point: ``t`` is ``x``'s shape with a last dimension of 1."""
+        return t.shape == (*x.shape[:-1], 1)
+
+    # ---------------------------------------------------------------- the reference's methods
+
+    def warped_positions(self, x: Tensor, t: Tensor) -> Tensor:
+        """``x + warp(cat(posi_encoder(x), time_encoder(t)))``, float32, in ``x``'s shape."""
+        if self._point_times(x, t) and self._use_fused(False, x, t):
+            return self._launch("warp", x.numel() // 3, positions=x.reshape(-1, 3), times=t.reshape(-1))[2].view(x.shape)
+        enc = torch.cat([self.posi_encoder(x), self.time_encoder(t)], dim=-1)
+        return x + self.warp(enc.reshape(-1, enc.shape[-1])).view(x.shape)
+
+    def query_density(self, x: Tensor, t: Tensor) -> Tensor:
+        if self._point_times(x, t) and self._use_fused(False, x, t):
+            sigma = self._launch("density", x.numel() // 3, True, positions=x.reshape(-1, 3), times=t.reshape(-1))[1]
+            return sigma.view(*x.shape[:-1], 1)
+        return self.nerf.query_density(self.warped_positions(x, t))
+
+    def query_opacity(self, x: Tensor, timestamps: Tensor, step_size) -> Tensor:
+        idxs = torch.randint(0, len(timestamps), (x.shape[0],), device=x.device)
+        return self.query_density(x, timestamps[idxs]) * step_size   # (small densities: 1 - exp(-density * step_size) is the same)
+
+    def forward(self, x: Tensor, t: Tensor, condition: Optional[Tensor] = None):
+        if condition is not None and condition.shape == x.shape and self._point_times(x, t) and self._use_fused(True, x, t, condition):
+            rgb, sigma, _ = self._launch("full", x.numel() // 3, True, positions=x.reshape(-1, 3), times=t.reshape(-1),
+                                         dirs=condition.reshape(-1, 3))
+            return rgb.view(*x.shape[:-1], 3), sigma.view(*x.shape[:-1], 1)
+        return self.nerf(self.warped_positions(x, t), condition=condition)
+
+    # ---------------------------------------------------------------- the methods in the other fields' shape
+
+    def query_raw(self, positions: Tensor, t: Tensor, directions: Tensor):
+        """``(raw_rgbs [..., 3], raw_sigmas [...])`` at world positions and times ``[..., 1]``, before any activation."""
+        if positions.shape == directions.shape and self._point_times(positions, t) and self._use_fused(True, positions, t, directions):
+            rgb, sigma, _ = self._launch("full", positions.numel() // 3, False, positions=positions.reshape(-1, 3), times=t.reshape(-1),
+                                         dirs=directions.reshape(-1, 3))
+            return rgb.view(*positions.shape[:-1], 3), sigma.view(positions.shape[:-1])
+        return self.nerf.query_raw(self.warped_positions(positions, t), directions)
+
+    def _ray_times(self, rays_o: Tensor, timestamps: Tensor) -> bool:
+        return timestamps.numel() == rays_o.shape[0]
+
+    def density_on_rays(self, rays_o: Tensor, rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor,
+                        timestamps: Tensor) -> Tensor:
+        """Densities ``[n]`` at the midpoints of packed ray samples, each at its ray's time (``timestamps`` ``[n_rays, 1]``): a
+        trainer's ``sigma_fn``."""
+        if self._ray_times(rays_o, timestamps) and self._use_fused(False, rays_o, rays_d, t_starts, t_ends, timestamps, ray_indices):
+            return self._launch("density", t_starts.numel(), True, rays=(rays_o, rays_d, t_starts, t_ends, ray_indices),
+                                times=timestamps.reshape(-1))[1]
+        s = sample_positions(rays_o, rays_d, t_starts, t_ends, ray_indices)
+        return self.query_density(s.positions, timestamps.reshape(-1, 1)[ray_indices]).squeeze(-1)
+
+    def query_on_rays(self, rays_o: Tensor, rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, timestamps: Tensor,
+                      raw: bool = True):
+        """The field at the midpoints of packed ray samples, each at its ray's time.  ``raw=True``: ``(raw_rgbs [n, 3],
+        raw_sigmas [n])``, what :func:`nerfacc_amd.rendering_from_raw` takes; otherwise ``(rgbs [n, 3], sigmas [n])`` activated."""
+        if self._ray_times(rays_o, timestamps) and self._use_fused(True, rays_o, rays_d, t_starts, t_ends, timestamps, ray_indices):
+            return self._launch("full", t_starts.numel(), not raw, rays=(rays_o, rays_d, t_starts, t_ends, ray_indices),
+                                times=timestamps.reshape(-1))[:2]
+        s = sample_positions(rays_o, rays_d, t_starts, t_ends, ray_indices, dirs="raw")
+        t = timestamps.reshape(-1, 1)[ray_indices]
+        if raw:
+            return self.query_raw(s.positions, t, s.dirs)
+        rgb, sigma = self.forward(s.positions, t, s.dirs)
+        return rgb, sigma.squeeze(-1)
+
+    def load_reference_state_dict(self, sd: dict) -> None:
+        """Takes the reference module's state dict: ``warp.hidden_layers.N.*`` and ``warp.output_layer.*`` (through
+        :meth:`FusedMLP.load_reference_state_dict`), ``nerf.*`` (through :meth:`VanillaNeRFRadianceField.load_reference_state_dict`)
+        and the encoders' ``scales`` buffers, which must be the reference's ``2^k``.  Any other key, a missing key and a wrong
+        shape raise ``ValueError``."""
+        sd = dict(sd)
+        for name, enc in (("posi_encoder", self.posi_encoder), ("time_encoder", self.time_encoder)):
+            scales = sd.pop(name + ".scales", None)
+            if scales is not None:
+                want = torch.tensor([2.0 ** k for k in range(enc.min_deg, enc.max_deg)], dtype=torch.float64)
+                if scales.numel() != want.numel() or not torch.equal(scales.detach().cpu().double().reshape(-1), want):
+                    raise ValueError(f"TNeRFRadianceField: load_reference_state_dict: '{name}.scales' is not 2^k for k in "
+                                     f"{enc.min_deg} .. {enc.max_deg - 1}")
+        other = sorted(k for k in sd if not k.startswith(("warp.", "nerf.")))
+        if other:
+            raise ValueError(f"TNeRFRadianceField: load_reference_state_dict: unexpected keys {other}")
+        warp_sd = {k[len("warp."):]: v for k, v in sd.items() if k.startswith("warp.")}
+        nerf_sd = {k[len("nerf."):]: v for k, v in sd.items() if k.startswith("nerf.")}
+        self.warp.load_reference_state_dict(warp_sd)
+        self.nerf.load_reference_state_dict(nerf_sd)
