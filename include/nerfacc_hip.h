@@ -1563,6 +1563,46 @@ int nfa_nerf_density(int32_t elem, const nfa_mlp_desc *trunk, const void *trunk_
 int nfa_nerf_pack_head(int32_t elem, const nfa_mlp_desc *head, int32_t trunk_width, const float *params, void *head_image,
                        int64_t image_elems, nfa_stream_t stream);
 
+/* The same field with grad, when only parameters want it: one launch forward, one launch backward (csrc/nerf_field.hip,
+ * "Training forward"; csrc/nerf_train.hip).
+ * nfa_nerf_train_fwd is nfa_nerf_field bit for bit, with the same arguments and checks (`save` is checked behind `in`), and
+ * additionally stores, all of type elem and 16-byte aligned, in the layouts nfa_mlp_stream_bwd_weights takes: enc_x
+ * [n_points, 63] the encoded position rows (the trunk's x), trunk_hidden [n_hidden, n_points, width] and head_hidden [head
+ * n_hidden, n_points, 128] the activations as nfa_mlp_stream_fwd saves them, head_in [n_points, width + 27] the head's input
+ * (the bottleneck rounded once, then the encoded direction).
+ * nfa_nerf_train_bwd forms the data gradients of both networks from the gradients of the outputs: it reads trunk_hidden and
+ * head_hidden, the BACKWARD images of nfa_mlp_stream_pack_weights for the two networks, g_rgb [n_points, 3] and g_sigma
+ * [n_points] (float32 or elem, g_*_elem; NULL is a zero gradient), and writes head_dz [head n_hidden, n_points, 128],
+ * head_dz_out [n_points, 3], trunk_dz [n_hidden, n_points, width] and trunk_dz_out [n_points, width + 1] of type elem (16-byte
+ * aligned, head_dz_out 2), which nfa_mlp_stream_bwd_weights takes next to (enc_x, trunk_hidden) and (head_in, head_hidden).
+ * activated 0: g_* are the gradients of the raw outputs, rounded once to elem.  activated 1: of the activated outputs y_rgb
+ * [n_points, 3] and y_sigma [n_points] as the forward stored them (float32 or elem, y_*_elem; each required with its g_*):
+ * (g_rgb (1 - y)) y and y > 0 ? g_sigma : 0 in float32, rounded once.  The head's layer-0 data gradient is formed for the
+ * bottleneck's columns only, rounded once, and is the operand of the trunk's output layer (with g_sigma's column) without
+ * passing through memory; gradients towards positions and directions are not formed.  Rounding points are those of
+ * nfa_mlp_stream_bwd_data run on the head and then on the trunk.  Checks, in this order: those of nfa_nerf_field's shapes; the
+ * descriptors; activated; the element codes; n_points == 0 returns; the pointers; their alignment. */
+typedef struct nfa_nerf_saved {
+    void *enc_x, *trunk_hidden, *head_in, *head_hidden;
+} nfa_nerf_saved;
+typedef struct nfa_nerf_grads {
+    const void *g_rgb;
+    int32_t g_rgb_elem;
+    const void *g_sigma;
+    int32_t g_sigma_elem;
+    const void *y_rgb;
+    int32_t y_rgb_elem;
+    const void *y_sigma;
+    int32_t y_sigma_elem;
+    void *head_dz, *head_dz_out, *trunk_dz, *trunk_dz_out;
+} nfa_nerf_grads;
+int nfa_nerf_train_fwd(int32_t elem, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *trunk_image, const void *head_image,
+                       const float *trunk_bias, const float *head_bias, const nfa_ngp_input *in, int64_t n_points, int32_t activated,
+                       const nfa_nerf_saved *save, void *sigma, int32_t sigma_elem, void *rgb, int32_t rgb_elem, nfa_stream_t stream);
+int nfa_nerf_train_bwd(int32_t elem, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *trunk_bwd_image,
+                       const void *head_bwd_image, int64_t n_points, int32_t activated, const nfa_nerf_saved *saved,
+                       const nfa_nerf_grads *grads, nfa_stream_t stream);
+
 /* ------------------------------------------------------------------ fused T-NeRF field query (csrc/nerf_field.hip, WARP) */
 
 /* The no-grad query of the reference's TNeRFRadianceField (examples/radiance_fields/mlp.py:248-283) as one launch.

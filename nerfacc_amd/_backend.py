@@ -69,6 +69,17 @@ class NGPGrads(C.Structure):
                 ("head_dz_out", _vp), ("base_dz", _vp), ("base_dz_out", _vp), ("grad_table", _vp)]
 
 
+class NerfSaved(C.Structure):
+    """struct nfa_nerf_saved (include/nerfacc_hip.h)."""
+    _fields_ = [("enc_x", _vp), ("trunk_hidden", _vp), ("head_in", _vp), ("head_hidden", _vp)]
+
+
+class NerfGrads(C.Structure):
+    """struct nfa_nerf_grads (include/nerfacc_hip.h)."""
+    _fields_ = [("g_rgb", _vp), ("g_rgb_elem", _i32), ("g_sigma", _vp), ("g_sigma_elem", _i32), ("y_rgb", _vp), ("y_rgb_elem", _i32),
+                ("y_sigma", _vp), ("y_sigma_elem", _i32), ("head_dz", _vp), ("head_dz_out", _vp), ("trunk_dz", _vp), ("trunk_dz_out", _vp)]
+
+
 class NGPInput(C.Structure):
     """struct nfa_ngp_input (include/nerfacc_hip.h)."""
     _fields_ = [("positions", _vp), ("dirs", _vp), ("rays_o", _vp), ("rays_d", _vp), ("t_starts", _vp), ("t_ends", _vp),
@@ -266,6 +277,9 @@ _SIGS = {
                        _vp],
     "nfa_nerf_density": [_i32, C.POINTER(MLPDesc), _vp, _vp, C.POINTER(NGPInput), _i64, _i32, _vp, _i32, _vp],
     "nfa_nerf_pack_head": [_i32, C.POINTER(MLPDesc), _i32, _vp, _vp, _i64, _vp],
+    "nfa_nerf_train_fwd": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPDesc), _vp, _vp, _vp, _vp, C.POINTER(NGPInput), _i64, _i32, C.POINTER(NerfSaved),
+                           _vp, _i32, _vp, _i32, _vp],
+    "nfa_nerf_train_bwd": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPDesc), _vp, _vp, _i64, _i32, C.POINTER(NerfSaved), C.POINTER(NerfGrads), _vp],
     "nfa_tnerf_field": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPDesc), C.POINTER(MLPDesc), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(NGPInput), _vp,
                         _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp],
     "nfa_tnerf_density": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPDesc), _vp, _vp, _vp, _vp, C.POINTER(NGPInput), _vp, _i64, _i32, _vp, _i32, _vp,

@@ -17,16 +17,17 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libnerfacc_hip.so")
-SOURCES = ["grid.hip", "walk.hip", "gridupd.hip", "traverse2.hip", "segscan.hip", "pdf.hip", "camera.hip", "pack.hip", "encoding.hip", "hashgrid_merged.hip", "samples.hip", "rays.hip", "planes.hip", "planereg.hip", "vmgrid.hip", "vmreg.hip", "voxgrid.hip", "voxreg.hip", "sinenc.hip", "mlp.hip", "mlp_stream.hip", "optim.hip", "photo.hip", "ngp_field.hip", "nerf_field.hip"]
+SOURCES = ["grid.hip", "walk.hip", "gridupd.hip", "traverse2.hip", "segscan.hip", "pdf.hip", "camera.hip", "pack.hip", "encoding.hip", "hashgrid_merged.hip", "samples.hip", "rays.hip", "planes.hip", "planereg.hip", "vmgrid.hip", "vmreg.hip", "voxgrid.hip", "voxreg.hip", "sinenc.hip", "mlp.hip", "mlp_stream.hip", "optim.hip", "photo.hip", "ngp_field.hip", "nerf_field.hip", "nerf_train.hip"]
 ARCH = os.environ.get("NERFACC_AMD_ARCH", "gfx950")
 # -ffp-contract=off: the traversal must not fuse a*b+c (floating-point contract)
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"--offload-arch={ARCH}",
          "-Wall", "-Wno-unused-function"] + os.environ.get("NERFACC_AMD_EXTRA_FLAGS", "").split()  # tuning experiments
 # per-source flags: the merged table gradient is built without packed float32 instructions (its sums stay single v_add_f32),
 # and so is the fused NeRF field: the precaution csrc/ngp_field.hip takes for its kernels with a function attribute (see the
-# comment there), here for the whole file, whose kernels form the same kind of float32 epilogues and encodings
+# comment there), here for the whole file, whose kernels form the same kind of float32 epilogues and encodings; its training
+# backward (nerf_train.hip) is built the same way
 NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-SOURCE_FLAGS = {"hashgrid_merged.hip": NO_PACKED_F32, "nerf_field.hip": NO_PACKED_F32}
+SOURCE_FLAGS = {"hashgrid_merged.hip": NO_PACKED_F32, "nerf_field.hip": NO_PACKED_F32, "nerf_train.hip": NO_PACKED_F32}
 
 
 def hipcc() -> str | None:

@@ -1,8 +1,8 @@
 // nerf_field.hip -- the no-grad query of the reference's vanilla NeRF field as ONE launch: both sinusoidal encoders, the trunk,
 // the colour head and the output activations (ref: examples/radiance_fields/mlp.py, VanillaNeRFRadianceField over NerfMLP).
-// Inference only: nothing is saved for a backward.  The composed chain (SinusoidalEncoding twice, StreamedMLP, split, cat,
-// StreamedMLP, activations) moves about 1.9 KB per point through memory at the reference's shape; this pass reads 24 B (a
-// position and a direction, or 16 B of a ray sample) and writes 4 to 16 B.
+// Nothing is saved for a backward, except by the training forward below.  The composed chain (SinusoidalEncoding twice,
+// StreamedMLP, split, cat, StreamedMLP, activations) moves about 1.9 KB per point through memory at the reference's shape; this
+// pass reads 24 B (a position and a direction, or 16 B of a ray sample) and writes 4 to 16 B.
 //
 // Work split, image format, arithmetic and rounding points are mlp_stream.hip's: a persistent grid, 4 waves x one 32-point
 // tile, 128 points per pass of the images (NFA_MLP_STREAM_POINTS), the weights as the A operand of v_mfma_f32_32x32x16, one
@@ -41,6 +41,19 @@
 // has its bits; the head's layer 0 sums its k-steps in another order than load_row8's natural one (bottleneck permuted,
 // direction behind it), so the raw colour may differ in the last bit of a float32 sum.
 //
+// Training forward (the SAVE instantiations, nfa_nerf_train_fwd): the same pass, the same accumulators and outputs, which also
+// stores what nerf_train.hip's backward and nfa_mlp_stream_bwd_weights read.  The rows exist only as operand fragments:
+//   hidden        [D, N, W] and [Dh, N, 128]: a lane's fragments of a row tile are 8-byte pieces of its point's row, and the two
+//                 lane halves' pieces alternate, so store_tile_row writes whole 64-byte runs (mlp_stream.hip's store).
+//   63 and W + 27 the encoded position rows and the head's input rows (bottleneck rounded once, then the encoded direction) are
+//                 no 16-byte rows, but a wave's 32 of them are one contiguous 16-byte aligned span: the lanes drop their
+//                 fragments' halves into the wave's LDS tile (row-major, 2-byte LDS writes), and the wave copies the tile out
+//                 as 16-byte pieces, 1 KiB per store instruction (nerf_field.h).  No row leaves as per-lane element stores.
+//   budget, W = 256   LDS: 2 x 20 KiB ring, 1.25 KiB table, 9.75 KiB biases, 4 x 17.7 KiB staging = 121.75 KiB of 160 (one
+//                 workgroup per CU, as the registers allow anyway).  Registers: 256 + 190 (the plain full query: 256 + 155), no
+//                 scratch ("Fused NeRF field: training").  Per point it writes 126 + 566 B of rows and 512 D + 256 Dh B
+//                 of activations.
+//
 // The WARP instantiations are the reference's T-NeRF field (ref: examples/radiance_fields/mlp.py, TNeRFRadianceField): in front
 // of the pass above a wave moves its points by the warp network, x' = x + warp([enc(x), enc(t)]), and x' takes x's place.
 //   warp weights  FusedMLP's packed forward image of (36 -> n_hidden x 64 -> 3), unchanged, RESIDENT in LDS behind the ring, the
@@ -57,26 +70,15 @@
 //   hand-off      the deformation is registers 0 .. 2 of lane half 0 of the output tile, float32, never rounded; lane half 1
 //                 reads it from the lane 32 away; x' = x + deformation in float32 on both halves.  Lane half 0 stores x' if
 //                 `warped` is asked for (12 contiguous bytes per lane).  nfa_tnerf_warp is this stage alone (tnerf_warp_kernel).
-#include "mlp_tiles.h"
+#include "nerf_field.h"
 #include "samples.h"
 
 namespace nfa {
 namespace {
 
-constexpr int NF_WAVES = 4;
-constexpr int NF_THREADS = NF_WAVES * NFA_WAVE;
-constexpr int NF_POINTS = NF_WAVES * 32;   // points of a workgroup per pass of the images
-constexpr int NF_SLOTS = 2;
-constexpr int NF_MAX_PIECES = 160;         // 8 * 8 + 9 of the trunk and 4 * 4 + 1 of the head at most
-constexpr int NF_MAX_HIDDEN = 8, NF_HEAD_MAX_HIDDEN = 4, NF_HEAD_W = 128;
-constexpr int NF_POS_L = 10, NF_DIR_L = 4;                               // the reference's degrees (0, 10) and (0, 4)
-constexpr int NF_POS_DIMS = 3 + 6 * NF_POS_L, NF_DIR_DIMS = 3 + 6 * NF_DIR_L;   // 63 and 27, with identity
 constexpr int NF_WARP_L = 4, NF_WARP_W = 64, NF_WARP_MAX_HIDDEN = 4;   // the reference's warp: degrees (0, 4) of x and of t
 constexpr int NF_WARP_DIMS = 3 + 6 * NF_WARP_L + 1 + 2 * NF_WARP_L;    // 36 = 27 + 9, with both identities
 constexpr int NF_WARP_KQ0 = (NF_WARP_DIMS + 15) / 16;
-static_assert(NF_POINTS == NFA_MLP_STREAM_POINTS, "the streamed passes' split");
-
-struct Piece { int32_t off16, n16; };   // of its image, in 16-byte fragments
 
 // The order in which a pass consumes the pieces: the trunk's (n_trunk of them), then the head's.  Returns their number.
 __host__ __device__ inline int nerf_pieces(const Shape &T, const Shape &H, bool full, Piece *tab, int *max_n16, int *n_trunk)
@@ -107,54 +109,6 @@ __host__ __device__ inline int64_t nerf_lds_bytes(int slot16, int bias_floats)
     return (int64_t)NF_SLOTS * slot16 * 16 + (int64_t)NF_MAX_PIECES * sizeof(Piece) + (int64_t)bias_floats * 4;
 }
 
-// mlp_stream.hip's ring over two images: pieces below n_trunk come from the trunk's, the others from the head's
-template <int MAXV>
-struct FieldRing {
-    const nfa_v4u *timg, *himg;
-    nfa_v4u *slots;
-    const Piece *tab;
-    int slot16, n_trunk, n_pieces, next, cur;
-    nfa_v4u regs[MAXV];
-
-    __device__ __forceinline__ const nfa_v4u *source(int i) const { return (i < n_trunk ? timg : himg) + tab[i].off16; }
-    // thread 0 has written the table; stages piece 0
-    __device__ __forceinline__ void start()
-    {
-        __syncthreads();
-        const nfa_v4u *src = source(0);
-        const int n16 = tab[0].n16;
-        for (int i = threadIdx.x; i < n16; i += NF_THREADS) slots[i] = src[i];
-        __syncthreads();
-        cur = 0;
-        next = 1;   // every network has at least two pieces
-    }
-    __device__ __forceinline__ const nfa_v4u *piece() const { return slots + cur * slot16; }
-    // issues the loads of the next piece; the current one is read between fetch() and hand_over()
-    __device__ __forceinline__ void fetch()
-    {
-        const nfa_v4u *src = source(next);
-        const int n16 = tab[next].n16;
-#pragma unroll
-        for (int v = 0; v < MAXV; ++v) {
-            const int i = threadIdx.x + v * NF_THREADS;
-            if (i < n16) regs[v] = src[i];
-        }
-    }
-    __device__ __forceinline__ void hand_over()
-    {
-        const int n16 = tab[next].n16;
-        nfa_v4u *d = slots + (cur ^ 1) * slot16;
-#pragma unroll
-        for (int v = 0; v < MAXV; ++v) {
-            const int i = threadIdx.x + v * NF_THREADS;
-            if (i < n16) d[i] = regs[v];
-        }
-        __syncthreads();
-        cur ^= 1;
-        next = next + 1 == n_pieces ? 0 : next + 1;
-    }
-};
-
 struct NerfArgs {
     Shape T, H;
     const uint16_t *timg, *himg;
@@ -166,6 +120,7 @@ struct NerfArgs {
     int64_t n_rays, N;
     void *sigma, *rgb;
     int32_t sigma_f32, rgb_f32, activated;
+    uint16_t *sv_x, *sv_th, *sv_hx, *sv_hh;   // SAVE: the training forward's four buffers (header: training forward)
 };
 
 // what a WARP instantiation takes beside them
@@ -384,13 +339,16 @@ __device__ __forceinline__ void put_out(void *out, bool out_f32, int64_t i, floa
 // W: the trunk's width.  RAYS: the ray-sample input form.  FULL: sigma and colour; otherwise the pass ends with sigma's tile.
 // WARP: the T-NeRF field, the warp stage in front of every pass; the instantiations without it never see WarpArgs.
 // A W = 128 WARP instantiation asks for the two waves per SIMD its plain twin has by itself (1: no request).
-template <class E, int W, bool RAYS, bool FULL, bool WARP = false>
+// SAVE: nfa_nerf_train_fwd, the full query that also stores what the backward reads; the arithmetic is untouched.
+template <class E, int W, bool RAYS, bool FULL, bool WARP = false, bool SAVE = false>
 __global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP && W == 128 ? 2 : 1))) void nerf_field_kernel(const std::conditional_t<WARP, TNerfArgs, NerfArgs> a)
 {
     constexpr int MT = W / 32, KQ = W / 16, KQX = (NF_POS_DIMS + 15) / 16, KQD = (NF_DIR_DIMS + 15) / 16;
     constexpr int HW = NF_HEAD_W, HMT = HW / 32, HKQ = HW / 16;
     constexpr int MAXV = ((KQ + KQX) * 64 + NF_THREADS - 1) / NF_THREADS;   // the trunk's cat layer, the largest piece
     static_assert(KQ + KQD <= KQ + KQX && HKQ <= KQ, "no piece of the head is larger");
+    static_assert(!SAVE || (FULL && !WARP), "the training forward is the full vanilla query");
+    constexpr int HX = W + NF_DIR_DIMS;   // the head's input row
     extern __shared__ __attribute__((aligned(16))) unsigned char nf_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const Shape &T = a.T, &H = a.H;
@@ -403,6 +361,7 @@ __global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP
     for (int i = threadIdx.x; i < n_tb; i += NF_THREADS) tb[i] = i - D * W < W + 1 ? a.tbias[i] : 0.f;
     for (int i = threadIdx.x; i < n_hb; i += NF_THREADS) hb[i] = i - Dc * HW < 3 ? a.hbias[i] : 0.f;
     nfa_v4u *wimg = reinterpret_cast<nfa_v4u *>(hb + n_hb);   // WARP: the resident image, 16-byte aligned (every part before it is)
+    uint16_t *st = reinterpret_cast<uint16_t *>(hb + n_hb) + wave * (row_stage_bytes(HX) / 2);   // SAVE: the wave's staging tile, there instead
     float *wb = nullptr;
     if constexpr (WARP) {
         wb = reinterpret_cast<float *>(wimg + a.w.img16);
@@ -410,12 +369,12 @@ __global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP
     }
     FieldRing<MAXV> ring;
     if (threadIdx.x == 0) nerf_pieces(T, H, FULL, tab, nullptr, nullptr);
-    ring.timg = reinterpret_cast<const nfa_v4u *>(a.timg);
-    ring.himg = reinterpret_cast<const nfa_v4u *>(a.himg);
+    ring.img0 = reinterpret_cast<const nfa_v4u *>(a.timg);
+    ring.img1 = reinterpret_cast<const nfa_v4u *>(a.himg);
     ring.slots = reinterpret_cast<nfa_v4u *>(nf_lds);
     ring.tab = tab;
     ring.slot16 = a.slot16;
-    ring.n_trunk = D * MT + (FULL ? MT + 1 : 1);
+    ring.n0 = D * MT + (FULL ? MT + 1 : 1);
     ring.n_pieces = a.n_pieces;
     ring.start();
     const int64_t N = a.N, n_pass = ceil_div64(N, NF_POINTS);
@@ -436,6 +395,12 @@ __global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP
         nfa_v4u xf[KQX], df[KQD];
         enc_frags<E, NF_POS_L, KQX>(x, lane, h, xf);
         if constexpr (FULL) enc_frags<E, NF_DIR_L, KQD>(dir, lane, h, df);
+        const int64_t row0 = p - r;
+        if constexpr (SAVE) {   // the encoded position rows [N, 63]
+#pragma unroll
+            for (int q = 0; q < KQX; ++q) stage_put8(st, NF_POS_DIMS, r, 16 * q + 8 * h, xf[q]);
+            stage_flush(st, a.sv_x, row0, tile_rows(row0, N), NF_POS_DIMS, lane);
+        }
         // ---- the trunk
         f32x16 acc[MT];
 #pragma unroll
@@ -455,6 +420,8 @@ __global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP
                 for (int i = 0; i < 16; ++i) acc[m][i] = acc[m][i] < 0.f ? 0.f : acc[m][i];
                 hf[2 * m] = acc_frag<E>(acc[m], 0);
                 hf[2 * m + 1] = acc_frag<E>(acc[m], 1);
+                if constexpr (SAVE)
+                    if (p < N) store_tile_row<W>(a.sv_th + (int64_t)(l - 1) * N * W, p, m, h, hf[2 * m], hf[2 * m + 1]);
             }
             if (l == D) break;
             const bool cat = T.cat(l);
@@ -492,8 +459,17 @@ __global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP
                 if (m < MT) {   // no activation: the bottleneck is a linear layer
                     bf[2 * m] = acc_frag<E>(o, 0);
                     bf[2 * m + 1] = acc_frag<E>(o, 1);
+                    if constexpr (SAVE) {
+                        stage_put_acc_frag(st, HX, r, h, m, 0, bf[2 * m]);
+                        stage_put_acc_frag(st, HX, r, h, m, 1, bf[2 * m + 1]);
+                    }
                 }
             }
+        }
+        if constexpr (SAVE) {   // the head's input rows [N, W + 27]: the bottleneck staged above, then the encoded direction
+#pragma unroll
+            for (int q = 0; q < KQD; ++q) stage_put8(st, HX, r, W + 16 * q + 8 * h, df[q]);
+            stage_flush(st, a.sv_hx, row0, tile_rows(row0, N), HX, lane);
         }
         const bool live = h == 0 && p < N;
         if (live && a.sigma) put_out<E>(a.sigma, a.sigma_f32 != 0, p, o[0], a.activated != 0, false);
@@ -518,6 +494,8 @@ __global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP
                     for (int i = 0; i < 16; ++i) acc[m][i] = acc[m][i] < 0.f ? 0.f : acc[m][i];
                     hc[2 * m] = acc_frag<E>(acc[m], 0);
                     hc[2 * m + 1] = acc_frag<E>(acc[m], 1);
+                    if constexpr (SAVE)
+                        if (p < N) store_tile_row<HW>(a.sv_hh + (int64_t)(l - 1) * N * HW, p, m, h, hc[2 * m], hc[2 * m + 1]);
                 }
                 if (l == Dc) break;
 #pragma unroll
@@ -600,41 +578,6 @@ __global__ __launch_bounds__(256) void nerf_head_pack_kernel(Shape S, int tw, co
 
 // ---------------------------------------------------------------- host side
 
-// The one statement of the shapes the fused query holds (nerfacc_amd/fields.py: nerf_field_limits_error says the same words).
-int check_field_shape(const char *who, int32_t elem, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, int32_t trunk_width,
-                      int64_t n_points, Shape *T, Shape *H)
-{
-    NFA_REQUIRE(elem == NFA_ELEM_F16 || elem == NFA_ELEM_BF16, "%s: elem %d: the networks' type is NFA_ELEM_F16 or NFA_ELEM_BF16", who, elem);
-    if (T) {
-        NFA_REQUIRE(trunk, "%s: the network descriptor is null", who);
-        const int w = trunk->width, d = trunk->n_hidden;
-        NFA_REQUIRE(w == 128 || w == 256, "%s: trunk width %d: 128 or 256 neurons are supported", who, w);
-        NFA_REQUIRE(d >= 1 && d <= NF_MAX_HIDDEN, "%s: trunk n_hidden %d: 1 to %d hidden layers are supported", who, d, NF_MAX_HIDDEN);
-        NFA_REQUIRE(trunk->n_in == NF_POS_DIMS, "%s: trunk n_in %d: the encoded position has %d features", who, trunk->n_in, NF_POS_DIMS);
-        NFA_REQUIRE(trunk->n_out == w + 1, "%s: trunk n_out %d: width + 1 = %d outputs (the bottleneck, then sigma)", who, trunk->n_out, w + 1);
-        NFA_REQUIRE(trunk->bias == 1, "%s: trunk bias %d: the field's networks have biases (1)", who, trunk->bias);
-        NFA_REQUIRE((trunk->skip_mask & ~((2 << d) - 4)) == 0, "%s: trunk skip_mask 0x%x: only bits 2 to n_hidden (%d) may be set: layer 0 "
-                    "takes x itself and layer 1 follows it", who, (unsigned)trunk->skip_mask, d);
-        *T = Shape{trunk->n_in, trunk->n_out, w, d, 1, trunk->skip_mask};
-        trunk_width = w;
-    }
-    if (H) {
-        NFA_REQUIRE(head, "%s: the network descriptor is null", who);
-        NFA_REQUIRE(trunk_width == 128 || trunk_width == 256, "%s: trunk width %d: 128 or 256 neurons are supported", who, trunk_width);
-        const int d = head->n_hidden;
-        NFA_REQUIRE(head->width == NF_HEAD_W, "%s: head width %d: %d neurons are supported", who, head->width, NF_HEAD_W);
-        NFA_REQUIRE(d >= 1 && d <= NF_HEAD_MAX_HIDDEN, "%s: head n_hidden %d: 1 to %d hidden layers are supported", who, d, NF_HEAD_MAX_HIDDEN);
-        NFA_REQUIRE(head->n_in == trunk_width + NF_DIR_DIMS, "%s: head n_in %d: trunk width + %d = %d inputs (the bottleneck, then the encoded "
-                    "direction)", who, head->n_in, NF_DIR_DIMS, trunk_width + NF_DIR_DIMS);
-        NFA_REQUIRE(head->n_out == 3, "%s: head n_out %d: 3 outputs (the colour)", who, head->n_out);
-        NFA_REQUIRE(head->bias == 1, "%s: head bias %d: the field's networks have biases (1)", who, head->bias);
-        NFA_REQUIRE(head->skip_mask == 0, "%s: head skip_mask 0x%x: the head has no skip", who, (unsigned)head->skip_mask);
-        *H = Shape{head->n_in, 3, NF_HEAD_W, d, 1, 0};
-    }
-    NFA_REQUIRE(n_points >= 0, "%s: n_points %lld is negative", who, (long long)n_points);
-    return NFA_OK;
-}
-
 // The one statement of the warp networks the T-NeRF entries hold (nerfacc_amd/fields.py: tnerf_field_limits_error says the same
 // words), checked after elem and before the trunk and the head.
 int check_warp_shape(const char *who, int32_t elem, const nfa_mlp_desc *warp, Shape *S)
@@ -676,11 +619,13 @@ WarpArgs warp_args(const Shape &S, const void *image, const float *bias, const f
 int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *trunk_image,
                const void *head_image, const float *trunk_bias, const float *head_bias, const nfa_ngp_input *in, int64_t N,
                int32_t activated, void *sigma, int32_t sigma_elem, void *rgb, int32_t rgb_elem, nfa_stream_t stream,
-               const WarpArgs *warp = nullptr)   // the T-NeRF entries: S checked, the pointers as the caller gave them
+               const WarpArgs *warp = nullptr,   // the T-NeRF entries: S checked, the pointers as the caller gave them
+               bool train = false, const nfa_nerf_saved *save = nullptr)   // nfa_nerf_train_fwd
 {
     Shape T, H = {};
     if (int rc = check_field_shape(who, elem, trunk, head, 0, N, &T, full ? &H : nullptr)) return rc;
     NFA_REQUIRE(in, "%s: the input descriptor is null", who);
+    NFA_REQUIRE(!train || save, "%s: the saved-buffers descriptor is null", who);
     NFA_REQUIRE(activated == 0 || activated == 1, "%s: activated must be 0 (raw outputs) or 1 (relu, sigmoid) (got %d)", who, activated);
     NFA_REQUIRE(sigma_elem == NFA_ELEM_F32 || sigma_elem == elem, "%s: sigma_elem %d: float32 or the networks' type (%d)", who, sigma_elem, elem);
     NFA_REQUIRE(!full || rgb_elem == NFA_ELEM_F32 || rgb_elem == elem, "%s: rgb_elem %d: float32 or the networks' type (%d)", who, rgb_elem, elem);
@@ -699,6 +644,14 @@ int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *tru
     if (warp)
         if (int rc = check_warp_pointers(who, *warp)) return rc;
     NerfArgs a = {};
+    if (train) {
+        NFA_REQUIRE(save->enc_x && save->trunk_hidden && save->head_in && save->head_hidden,
+                    "%s: null pointer (enc_x, trunk_hidden, head_in or head_hidden)", who);
+        NFA_REQUIRE(aligned_to(save->enc_x, 16) && aligned_to(save->trunk_hidden, 16) && aligned_to(save->head_in, 16) &&
+                    aligned_to(save->head_hidden, 16), "%s: misaligned pointer (the saved buffers 16)", who);
+        a.sv_x = static_cast<uint16_t *>(save->enc_x), a.sv_th = static_cast<uint16_t *>(save->trunk_hidden);
+        a.sv_hx = static_cast<uint16_t *>(save->head_in), a.sv_hh = static_cast<uint16_t *>(save->head_hidden);
+    }
     a.T = T, a.H = H;
     a.timg = static_cast<const uint16_t *>(trunk_image), a.himg = static_cast<const uint16_t *>(head_image);
     a.tbias = trunk_bias, a.hbias = head_bias;
@@ -711,13 +664,22 @@ int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *tru
     a.sigma = sigma, a.sigma_f32 = sigma_elem == NFA_ELEM_F32;
     a.rgb = full ? rgb : nullptr, a.rgb_f32 = rgb_elem == NFA_ELEM_F32;
     a.activated = activated;
-    const int64_t lds = nerf_lds_bytes(slot16, trunk_bias_floats(T) + (full ? head_bias_floats(H) : 0)) + (warp ? warp_lds_bytes(warp->S) : 0);
+    const int64_t lds = nerf_lds_bytes(slot16, trunk_bias_floats(T) + (full ? head_bias_floats(H) : 0)) + (warp ? warp_lds_bytes(warp->S) : 0) +
+                        (train ? (int64_t)NF_WAVES * row_stage_bytes(T.W + NF_DIR_DIMS) : 0);
     const int64_t want = ceil_div64(N, NF_POINTS);
     const unsigned grid = (unsigned)(want < NFA_MLP_STREAM_GROUPS ? want : NFA_MLP_STREAM_GROUPS);
     int rc = NFA_OK;
     auto launch = [&](auto tag, auto w, auto rays_c, auto full_c, auto warp_c) {
         using E = typename decltype(tag)::type;
         constexpr bool WARP = decltype(warp_c)::value;
+        if constexpr (decltype(full_c)::value && !WARP) {
+            if (train) {
+                auto kern = nerf_field_kernel<E, decltype(w)::value, decltype(rays_c)::value, true, false, true>;
+                if ((rc = allow_lds(who, kern, lds)) != NFA_OK) return;
+                kern<<<grid, NF_THREADS, (size_t)lds, as_stream(stream)>>>(a);
+                return;
+            }
+        }
         auto kern = nerf_field_kernel<E, decltype(w)::value, decltype(rays_c)::value, decltype(full_c)::value, WARP>;
         if ((rc = allow_lds(who, kern, lds)) != NFA_OK) return;
         if constexpr (WARP) {
@@ -783,6 +745,14 @@ int nfa_nerf_field(int32_t elem, const nfa_mlp_desc *trunk, const nfa_mlp_desc *
 {
     return nerf_query("nfa_nerf_field", true, elem, trunk, head, trunk_image, head_image, trunk_bias, head_bias, in, n_points, activated, sigma,
                       sigma_elem, rgb, rgb_elem, stream);
+}
+
+int nfa_nerf_train_fwd(int32_t elem, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *trunk_image, const void *head_image,
+                       const float *trunk_bias, const float *head_bias, const nfa_ngp_input *in, int64_t n_points, int32_t activated,
+                       const nfa_nerf_saved *save, void *sigma, int32_t sigma_elem, void *rgb, int32_t rgb_elem, nfa_stream_t stream)
+{
+    return nerf_query("nfa_nerf_train_fwd", true, elem, trunk, head, trunk_image, head_image, trunk_bias, head_bias, in, n_points, activated,
+                      sigma, sigma_elem, rgb, rgb_elem, stream, nullptr, true, save);
 }
 
 int nfa_tnerf_field(int32_t elem, const nfa_mlp_desc *warp, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *warp_image,

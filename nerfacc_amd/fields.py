@@ -462,6 +462,83 @@ def nerf_field_limits_error(trunk: Optional[tuple], head: Optional[tuple], trunk
     return None
 
 
+class _NerfTrainFn(torch.autograd.Function):
+    """A full query with grad as one launch (``nfa_nerf_train_fwd``): the no-grad launch's outputs, and the buffers the backward
+    and the weight-gradient passes read."""
+
+    @staticmethod
+    def forward(ctx, trunk_p: Tensor, head_p: Tensor, field: "VanillaNeRFRadianceField", activated: bool, n: int, inputs: dict,
+                rgb_dtype, sigma_dtype):
+        ctx.set_materialize_grads(False)
+        t, h = field.mlp.trunk, field.mlp.head
+        dev, dt, W = trunk_p.device, field.dtype, t.n_neurons
+        new = lambda *s: torch.empty(*s, dtype=dt, device=dev)
+        saved = [new(n, NERF_POS_DIMS), new(t.n_hidden_layers, n, W), new(n, W + NERF_DIR_DIMS), new(h.n_hidden_layers, n, NERF_HEAD_WIDTH)]
+        rgb, sigma = field._launch(True, n, activated, rgb_dtype=rgb_dtype, sigma_dtype=sigma_dtype, save=saved, **inputs)
+        ctx.field, ctx.activated, ctx.n = field, activated, n
+        ctx.save_for_backward(trunk_p, head_p, *saved, *([rgb, sigma] if activated else []))
+        return rgb, sigma
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_sigma):
+        need = ctx.needs_input_grad[:2]
+        if not any(need) or (g_rgb is None and g_sigma is None):
+            return (None,) * 8
+        trunk_p, head_p, *rest = ctx.saved_tensors
+        g = _NerfTrainBwdFn.apply(trunk_p, head_p, g_rgb, g_sigma, ctx.field, ctx.activated, ctx.n, need, *[t.detach() for t in rest])
+        return (*g, None, None, None, None, None, None)
+
+
+class _NerfTrainBwdFn(torch.autograd.Function):
+    """The backward as a function of its own (as ``_NGPTrainBwdFn``): one launch for both networks' data gradients
+    (``nfa_nerf_train_bwd``), then the two streamed weight-gradient passes.  Differentiating it again raises."""
+
+    @staticmethod
+    def forward(ctx, trunk_p, head_p, g_rgb, g_sigma, field, activated, n, need, *saved):
+        ctx.set_materialize_grads(False)
+        ctx.name = type(field).__name__
+        if n == 0:
+            return tuple(torch.zeros_like(p) if w else None for p, w in ((trunk_p, need[0]), (head_p, need[1])))
+        t, h = field.mlp.trunk, field.mlp.head
+        dev, dt, W = trunk_p.device, field.dtype, t.n_neurons
+        elem, f32 = B.ELEM_CODES[dt], B.ELEM_CODES[torch.float32]
+        enc_x, t_hidden, h_in, h_hidden, *ys = saved
+        y_rgb, y_sigma = ys if activated else (None, None)
+
+        def grad(g):   # float32 or the networks' type, contiguous; the kernel rounds once
+            if g is None:
+                return None, f32
+            g = (g if g.dtype in (torch.float32, dt) else g.float()).contiguous()
+            return g, B.ELEM_CODES[g.dtype]
+
+        (g_rgb, rgb_elem), (g_sigma, sigma_elem) = grad(g_rgb), grad(g_sigma)
+        new = lambda *s: torch.empty(*s, dtype=dt, device=dev)
+        hdz, hdzo, tdz, tdzo = new(h.n_hidden_layers, n, NERF_HEAD_WIDTH), new(n, 3), new(t.n_hidden_layers, n, W), new(n, W + 1)
+        gr = B.NerfGrads(B.ptr(g_rgb), rgb_elem, B.ptr(g_sigma), sigma_elem, B.ptr(y_rgb), B.ELEM_CODES[y_rgb.dtype] if activated else f32,
+                         B.ptr(y_sigma), B.ELEM_CODES[y_sigma.dtype] if activated else f32, B.ptr(hdz), B.ptr(hdzo), B.ptr(tdz), B.ptr(tdzo))
+        sv = B.NerfSaved(B.ptr(enc_x), B.ptr(t_hidden), B.ptr(h_in), B.ptr(h_hidden))
+        out = []
+        with torch.cuda.device(dev):
+            B.call("nfa_nerf_train_bwd", elem, t._desc, h._desc, B.ptr(t._images(trunk_p)[1]), B.ptr(h._images(head_p)[1]), n, int(activated),
+                   ctypes.byref(sv), ctypes.byref(gr), B.stream())
+            for mlp, params, want, x, hidden, dz, dzo in ((t, trunk_p, need[0], enc_x, t_hidden, tdz, tdzo),
+                                                          (h, head_p, need[1], h_in, h_hidden, hdz, hdzo)):
+                g_p = None
+                if want:
+                    P = params.numel()
+                    partials = torch.empty(mlp._slices(n) * P, dtype=torch.float32, device=dev)
+                    g_p = torch.empty(P, dtype=torch.float32, device=dev)
+                    mlp._weight_gradient(elem, x, hidden, dz, dzo, n, partials, g_p, zero_bias=False)
+                out.append(g_p)
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *gg):
+        raise NotImplementedError(f"{ctx.name}(fused_training=True): the second order (differentiating the parameters' gradients again, "
+                                  "create_graph=True) is not implemented by the fused training pass; construct the module with "
+                                  "fused_training=False")
+
+
 class VanillaNeRFRadianceField(nn.Module):
     """The reference's vanilla NeRF field (its constructor arguments; ``dtype`` fp16 or bf16 is the networks' type,
     ``generator`` seeds their initial weights, ``fused=False`` switches the fused dispatch off): ``posi_encoder`` and
@@ -477,12 +554,22 @@ class VanillaNeRFRadianceField(nn.Module):
     Outputs are ``dtype`` on both paths, as :class:`NerfMLP`'s are.
 
     ``fused`` is a bool, or a dict ``{"density": bool, "full": bool}`` per query kind (default: both on; DESIGN.md, "Fused NeRF
-    field", has the measurements behind the defaults)."""
+    field", has the measurements behind the defaults).
+
+    ``fused_training=True`` (off by default) gives a full query WITH grad the same treatment when only parameters require grad:
+    ``forward(x, condition)``, ``query_raw`` and ``query_on_rays`` take one launch forward that also saves what the backward
+    needs (``nfa_nerf_train_fwd``), one launch backward for both networks' data gradients (``nfa_nerf_train_bwd``,
+    csrc/nerf_train.hip), then the networks' usual weight-gradient passes.  Outputs are the no-grad launch's bits, gradients
+    have the composed chain's rounding points and are the same bits on every run; differentiating them again raises
+    ``NotImplementedError``.  Positions, directions or rays that require grad, ``condition=None`` or a broadcast condition, CPU
+    tensors, density-only queries, ``fused={"full": False}`` and shapes outside :meth:`fused_supported` keep the composed chain
+    (DESIGN.md, "Fused NeRF field: training")."""
 
     def __init__(self, net_depth: int = 8, net_width: int = 256, skip_layer: Optional[int] = 4, net_depth_condition: int = 1,
                  net_width_condition: int = 128, dtype: torch.dtype = torch.float16, generator: Optional[torch.Generator] = None,
-                 fused: Union[bool, dict] = True):
+                 fused: Union[bool, dict] = True, fused_training: bool = False):
         super().__init__()
+        self.fused_training = bool(fused_training)
         self.posi_encoder = SinusoidalEncoding(3, 0, 10, True, out_dtype=dtype)
         self.view_encoder = SinusoidalEncoding(3, 0, 4, True, out_dtype=dtype)
         self.mlp = NerfMLP(self.posi_encoder.latent_dim, self.view_encoder.latent_dim, net_depth, net_width, skip_layer,
@@ -513,6 +600,23 @@ class VanillaNeRFRadianceField(nn.Module):
             return False
         return not (torch.is_grad_enabled() and any(t.requires_grad for t in [*self.parameters(), *ts]))
 
+    def _use_train(self, *tensors: Tensor) -> bool:
+        """The fused training pass serves this full query: grad is on and wanted by parameters only (``fused={"full": False}``
+        switches it off with the fused full query, whose kernel it is)."""
+        if not (self.fused_training and self.fused["full"] and torch.is_grad_enabled() and self.fused_supported(True)):
+            return False
+        dev = self.mlp.trunk.params.device
+        if not (all(t.is_cuda and t.device == dev for t in tensors) and all(t.dtype == torch.float32 for t in tensors[:4])):
+            return False
+        if any(t.requires_grad for t in tensors):
+            return False
+        return self.mlp.trunk.params.requires_grad or self.mlp.head.params.requires_grad
+
+    def _train(self, activated: bool, n: int, rgb_dtype=None, sigma_dtype=None, **inputs):
+        """``(rgb [n, 3], sigma [n])`` of one training launch, raw or activated, differentiable towards the parameters."""
+        with torch.autocast("cuda", enabled=False):
+            return _NerfTrainFn.apply(self.mlp.trunk.params, self.mlp.head.params, self, activated, n, inputs, rgb_dtype, sigma_dtype)
+
     def _head_image(self) -> Tensor:
         """The head's forward image in the fused launch's k order, rebuilt when the masters change (as StreamedMLP's images)."""
         h = self.mlp.head
@@ -526,8 +630,10 @@ class VanillaNeRFRadianceField(nn.Module):
             self._head_packed = (key, img)
         return self._head_packed[1]
 
-    def _launch(self, full: bool, n: int, activated: bool, positions=None, dirs=None, rays=None, rgb_dtype=None, sigma_dtype=None):
-        """One fused launch: ``(rgb [n, 3] or None, sigma [n])``, raw or activated, in ``dtype`` unless told otherwise."""
+    def _launch(self, full: bool, n: int, activated: bool, positions=None, dirs=None, rays=None, rgb_dtype=None, sigma_dtype=None,
+                save: Optional[List[Tensor]] = None):
+        """One fused launch: ``(rgb [n, 3] or None, sigma [n])``, raw or activated, in ``dtype`` unless told otherwise.  ``save``:
+        the training forward, which fills these four buffers (struct nfa_nerf_saved)."""
         t, h = self.mlp.trunk, self.mlp.head
         dev = t.params.device
         sigma = torch.empty(n, dtype=sigma_dtype or self.dtype, device=dev)
@@ -544,7 +650,12 @@ class VanillaNeRFRadianceField(nn.Module):
         with torch.cuda.device(dev):
             tp = t.params
             timg = t._images(tp)[0]
-            if full:
+            if save is not None:
+                hp, sv = h.params, B.NerfSaved(*[B.ptr(b) for b in save])
+                B.call("nfa_nerf_train_fwd", elem, t._desc, h._desc, B.ptr(timg), B.ptr(self._head_image()), t._bias_ptr(tp), h._bias_ptr(hp),
+                       ctypes.byref(inp), n, int(activated), ctypes.byref(sv), B.ptr(sigma), B.ELEM_CODES[sigma.dtype], B.ptr(rgb),
+                       B.ELEM_CODES[rgb.dtype], B.stream())
+            elif full:
                 hp = h.params
                 B.call("nfa_nerf_field", elem, t._desc, h._desc, B.ptr(timg), B.ptr(self._head_image()), t._bias_ptr(tp), h._bias_ptr(hp),
                        ctypes.byref(inp), n, int(activated), B.ptr(sigma), B.ELEM_CODES[sigma.dtype], B.ptr(rgb), B.ELEM_CODES[rgb.dtype],
@@ -565,6 +676,9 @@ class VanillaNeRFRadianceField(nn.Module):
         return self.query_density(x) * step_size   # (small densities: 1 - exp(-density * step_size) is the same)
 
     def forward(self, x: Tensor, condition: Optional[Tensor] = None):
+        if condition is not None and condition.shape == x.shape and self._use_train(x, condition):
+            rgb, sigma = self._train(True, x.numel() // 3, positions=x.reshape(-1, 3), dirs=condition.reshape(-1, 3))
+            return rgb.view(*x.shape[:-1], 3), sigma.view(*x.shape[:-1], 1)
         if condition is not None and condition.shape == x.shape and self._use_fused(True, x, condition):
             rgb, sigma = self._launch(True, x.numel() // 3, True, positions=x.reshape(-1, 3), dirs=condition.reshape(-1, 3))
             return rgb.view(*x.shape[:-1], 3), sigma.view(*x.shape[:-1], 1)
@@ -575,6 +689,9 @@ class VanillaNeRFRadianceField(nn.Module):
 
     def query_raw(self, positions: Tensor, directions: Tensor):
         """``(raw_rgbs [..., 3], raw_sigmas [...])`` at world positions, before any activation."""
+        if positions.shape == directions.shape and self._use_train(positions, directions):
+            rgb, sigma = self._train(False, positions.numel() // 3, positions=positions.reshape(-1, 3), dirs=directions.reshape(-1, 3))
+            return rgb.view(*positions.shape[:-1], 3), sigma.view(positions.shape[:-1])
         if positions.shape == directions.shape and self._use_fused(True, positions, directions):
             rgb, sigma = self._launch(True, positions.numel() // 3, False, positions=positions.reshape(-1, 3),
                                       dirs=directions.reshape(-1, 3))
@@ -592,6 +709,8 @@ class VanillaNeRFRadianceField(nn.Module):
     def query_on_rays(self, rays_o: Tensor, rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, raw: bool = True):
         """The field at the midpoints of packed ray samples.  ``raw=True``: ``(raw_rgbs [n, 3], raw_sigmas [n])``, what
         :func:`nerfacc_amd.rendering_from_raw` takes; otherwise ``(rgbs [n, 3], sigmas [n])`` activated."""
+        if self._use_train(rays_o, rays_d, t_starts, t_ends, ray_indices):
+            return self._train(not raw, t_starts.numel(), rays=(rays_o, rays_d, t_starts, t_ends, ray_indices))
         if self._use_fused(True, rays_o, rays_d, t_starts, t_ends, ray_indices):
             return self._launch(True, t_starts.numel(), not raw, rays=(rays_o, rays_d, t_starts, t_ends, ray_indices))
         s = sample_positions(rays_o, rays_d, t_starts, t_ends, ray_indices, dirs="raw")
