@@ -1634,6 +1634,38 @@ int nfa_tnerf_density(int32_t elem, const nfa_mlp_desc *warp, const nfa_mlp_desc
 int nfa_tnerf_warp(int32_t elem, const nfa_mlp_desc *warp, const void *warp_image, const float *warp_bias, const nfa_ngp_input *in,
                    const float *times, int64_t n_points, float *warped, nfa_stream_t stream);
 
+/* The same field with grad, when only parameters want it: one launch forward, one launch backward (csrc/nerf_field.hip,
+ * "T-NeRF training forward"; csrc/nerf_train.hip, the WARP instantiations).
+ * nfa_tnerf_train_fwd is nfa_tnerf_field bit for bit (rgb, sigma and warped, which is required here), stores the four buffers
+ * of nfa_nerf_train_fwd at x', and additionally, of type elem and 16-byte aligned, in the layouts nfa_mlp_net_bwd_weights takes:
+ * warp_in [n_points, 36] the warp network's input rows and warp_hidden [warp n_hidden, n_points, 64] its activations as
+ * nfa_mlp_net_fwd saves them.  warped [n_points, 3] float32 is x'; the backward recomputes the sines and cosines from it.
+ * nfa_tnerf_train_bwd is nfa_nerf_train_bwd with four more stages in the same launch: the trunk's dL/d(encoded x') through
+ * layer 0 and the x columns of every cat layer, summed and rounded once to elem as nfa_mlp_stream_bwd_data's grad_x is (the
+ * [n_points, 63] row is never written); nfa_sinenc_bwd's formulas on it in float32 (dL/dx'); that value rounded once to elem as
+ * warp_dz_out [n_points, 3] (2-byte aligned); and nfa_mlp_net_bwd_data's chain on the warp network's BACKWARD image of
+ * nfa_mlp_net_pack_weights, resident in LDS, which writes warp_dz [warp n_hidden, n_points, 64] (16-byte aligned).  No gradient
+ * towards positions, times or directions is formed.  The trunk's and the head's gradients are nfa_nerf_train_bwd's bits.
+ * Checks, in this order: the warp's limits, then those of nfa_nerf_train_fwd / nfa_nerf_train_bwd with the warp's descriptors,
+ * pointers and alignment checked next to the others; nfa_tnerf_train_bwd also refuses a warp whose backward image does not fit
+ * the LDS behind the ring.  n_points == 0 returns after the checks. */
+typedef struct nfa_tnerf_saved {
+    void *warp_in, *warp_hidden;
+    float *warped;
+} nfa_tnerf_saved;
+typedef struct nfa_tnerf_grads {
+    void *warp_dz, *warp_dz_out;
+} nfa_tnerf_grads;
+int nfa_tnerf_train_fwd(int32_t elem, const nfa_mlp_desc *warp, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *warp_image,
+                        const void *trunk_image, const void *head_image, const float *warp_bias, const float *trunk_bias,
+                        const float *head_bias, const nfa_ngp_input *in, const float *times, int64_t n_points, int32_t activated,
+                        const nfa_nerf_saved *save, const nfa_tnerf_saved *warp_save, void *sigma, int32_t sigma_elem, void *rgb,
+                        int32_t rgb_elem, nfa_stream_t stream);
+int nfa_tnerf_train_bwd(int32_t elem, const nfa_mlp_desc *warp, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head,
+                        const void *warp_bwd_image, const void *trunk_bwd_image, const void *head_bwd_image, int64_t n_points,
+                        int32_t activated, const nfa_nerf_saved *saved, const nfa_tnerf_saved *warp_saved, const nfa_nerf_grads *grads,
+                        const nfa_tnerf_grads *warp_grads, nfa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,16 @@ class NerfGrads(C.Structure):
                 ("y_sigma", _vp), ("y_sigma_elem", _i32), ("head_dz", _vp), ("head_dz_out", _vp), ("trunk_dz", _vp), ("trunk_dz_out", _vp)]
 
 
+class TNerfSaved(C.Structure):
+    """struct nfa_tnerf_saved (include/nerfacc_hip.h)."""
+    _fields_ = [("warp_in", _vp), ("warp_hidden", _vp), ("warped", _vp)]
+
+
+class TNerfGrads(C.Structure):
+    """struct nfa_tnerf_grads (include/nerfacc_hip.h)."""
+    _fields_ = [("warp_dz", _vp), ("warp_dz_out", _vp)]
+
+
 class NGPInput(C.Structure):
     """struct nfa_ngp_input (include/nerfacc_hip.h)."""
     _fields_ = [("positions", _vp), ("dirs", _vp), ("rays_o", _vp), ("rays_d", _vp), ("t_starts", _vp), ("t_ends", _vp),
@@ -285,6 +295,10 @@ _SIGS = {
     "nfa_tnerf_density": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPDesc), _vp, _vp, _vp, _vp, C.POINTER(NGPInput), _vp, _i64, _i32, _vp, _i32, _vp,
                           _vp],
     "nfa_tnerf_warp": [_i32, C.POINTER(MLPDesc), _vp, _vp, C.POINTER(NGPInput), _vp, _i64, _vp, _vp],
+    "nfa_tnerf_train_fwd": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPDesc), C.POINTER(MLPDesc), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(NGPInput),
+                            _vp, _i64, _i32, C.POINTER(NerfSaved), C.POINTER(TNerfSaved), _vp, _i32, _vp, _i32, _vp],
+    "nfa_tnerf_train_bwd": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPDesc), C.POINTER(MLPDesc), _vp, _vp, _vp, _i64, _i32, C.POINTER(NerfSaved),
+                            C.POINTER(TNerfSaved), C.POINTER(NerfGrads), C.POINTER(TNerfGrads), _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],

@@ -1,5 +1,6 @@
 // nerf_field.h -- what the fused NeRF field's query (nerf_field.hip) and its training backward (nerf_train.hip) share: the limits,
-// the ring over two packed images, the one statement of the shapes, and the staged store of rows that are no 16-byte rows.
+// the ring over two packed images, the one statement of the shapes (the T-NeRF warp network's included), and the staged store of
+// rows that are no 16-byte rows.
 #pragma once
 #include "mlp_tiles.h"
 
@@ -15,6 +16,9 @@ constexpr int NF_MAX_HIDDEN = 8, NF_HEAD_MAX_HIDDEN = 4, NF_HEAD_W = 128;
 constexpr int NF_POS_L = 10, NF_DIR_L = 4;                               // the reference's degrees (0, 10) and (0, 4)
 constexpr int NF_POS_DIMS = 3 + 6 * NF_POS_L, NF_DIR_DIMS = 3 + 6 * NF_DIR_L;   // 63 and 27, with identity
 static_assert(NF_POINTS == NFA_MLP_STREAM_POINTS, "the streamed passes' split");
+constexpr int NF_WARP_L = 4, NF_WARP_W = 64, NF_WARP_MAX_HIDDEN = 4;   // the reference's warp: degrees (0, 4) of x and of t
+constexpr int NF_WARP_DIMS = 3 + 6 * NF_WARP_L + 1 + 2 * NF_WARP_L;    // 36 = 27 + 9, with both identities
+constexpr int NF_WARP_KQ0 = (NF_WARP_DIMS + 15) / 16;
 
 struct Piece { int32_t off16, n16; };   // of its image, in 16-byte fragments
 
@@ -75,7 +79,7 @@ struct FieldRing {
 // fewer than eight halves; those leave one by one.
 
 // bytes of a wave's staging tile for rows of ld halves
-__host__ __device__ inline int row_stage_bytes(int ld) { return (32 * ld * 2 + 15) / 16 * 16; }
+__host__ __device__ constexpr int row_stage_bytes(int ld) { return (32 * ld * 2 + 15) / 16 * 16; }
 
 // halves c0 .. c0 + 2 n - 1 of row r, columns >= ld dropped
 template <int N2>
@@ -157,6 +161,24 @@ int check_field_shape(const char *who, int32_t elem, const nfa_mlp_desc *trunk, 
         *H = Shape{head->n_in, 3, NF_HEAD_W, d, 1, 0};
     }
     NFA_REQUIRE(n_points >= 0, "%s: n_points %lld is negative", who, (long long)n_points);
+    return NFA_OK;
+}
+
+// The one statement of the warp networks the T-NeRF entries hold (nerfacc_amd/fields.py: tnerf_field_limits_error says the same
+// words), checked after elem and before the trunk and the head.
+int check_warp_shape(const char *who, int32_t elem, const nfa_mlp_desc *warp, Shape *S)
+{
+    NFA_REQUIRE(elem == NFA_ELEM_F16 || elem == NFA_ELEM_BF16, "%s: elem %d: the networks' type is NFA_ELEM_F16 or NFA_ELEM_BF16", who, elem);
+    NFA_REQUIRE(warp, "%s: the network descriptor is null", who);
+    const int d = warp->n_hidden;
+    NFA_REQUIRE(warp->width == NF_WARP_W, "%s: warp width %d: %d neurons are supported", who, warp->width, NF_WARP_W);
+    NFA_REQUIRE(d >= 1 && d <= NF_WARP_MAX_HIDDEN, "%s: warp n_hidden %d: 1 to %d hidden layers are supported", who, d, NF_WARP_MAX_HIDDEN);
+    NFA_REQUIRE(warp->n_in == NF_WARP_DIMS, "%s: warp n_in %d: the encoded position and time have %d features", who, warp->n_in, NF_WARP_DIMS);
+    NFA_REQUIRE(warp->n_out == 3, "%s: warp n_out %d: 3 outputs (the deformation)", who, warp->n_out);
+    NFA_REQUIRE(warp->bias == 1, "%s: warp bias %d: the field's networks have biases (1)", who, warp->bias);
+    NFA_REQUIRE((warp->skip_mask & ~((2 << d) - 4)) == 0, "%s: warp skip_mask 0x%x: only bits 2 to n_hidden (%d) may be set: layer 0 "
+                "takes x itself and layer 1 follows it", who, (unsigned)warp->skip_mask, d);
+    *S = Shape{NF_WARP_DIMS, 3, NF_WARP_W, d, 1, warp->skip_mask};
     return NFA_OK;
 }
 

@@ -70,15 +70,19 @@
 //   hand-off      the deformation is registers 0 .. 2 of lane half 0 of the output tile, float32, never rounded; lane half 1
 //                 reads it from the lane 32 away; x' = x + deformation in float32 on both halves.  Lane half 0 stores x' if
 //                 `warped` is asked for (12 contiguous bytes per lane).  nfa_tnerf_warp is this stage alone (tnerf_warp_kernel).
+//
+// T-NeRF training forward (WARP with SAVE, nfa_tnerf_train_fwd): both of the above in one instantiation, the same accumulators, so
+// rgb, sigma and warped are nfa_tnerf_field's bits and the four buffers are what nfa_nerf_train_fwd stores at x'.  The warp stage
+// also stores its input rows [N, 36] (through the wave's staging tile) and its activations [D_w, N, 64] (store_tile_row); x' is
+// `warped`.  The plain training forward's LDS and the resident warp image do not fit together (121.75 + 41.1 KiB), so here the
+// head's input rows leave as TWO spans of 16 rows (16 (W + 27) halves are a multiple of 16 bytes): lanes r < 16 stage and the wave
+// flushes, then lanes r >= 16.  The staging halves (4 x 8.8 KiB at W = 256; 127.5 KiB in all), no arithmetic changes, and the
+// bottleneck fragments are held until the head's layer 0 anyway ("Fused T-NeRF field: training").
 #include "nerf_field.h"
 #include "samples.h"
 
 namespace nfa {
 namespace {
-
-constexpr int NF_WARP_L = 4, NF_WARP_W = 64, NF_WARP_MAX_HIDDEN = 4;   // the reference's warp: degrees (0, 4) of x and of t
-constexpr int NF_WARP_DIMS = 3 + 6 * NF_WARP_L + 1 + 2 * NF_WARP_L;    // 36 = 27 + 9, with both identities
-constexpr int NF_WARP_KQ0 = (NF_WARP_DIMS + 15) / 16;
 
 // The order in which a pass consumes the pieces: the trunk's (n_trunk of them), then the head's.  Returns their number.
 __host__ __device__ inline int nerf_pieces(const Shape &T, const Shape &H, bool full, Piece *tab, int *max_n16, int *n_trunk)
@@ -133,6 +137,10 @@ struct WarpArgs {
     int32_t img16;        // the image in 16-byte fragments
 };
 struct TNerfArgs : NerfArgs { WarpArgs w; };
+// WARP with SAVE (nfa_tnerf_train_fwd): the warp's input rows [N, 36] and hidden activations [D_w, N, 64]; x' is w.warped
+struct TNerfTrainArgs : TNerfArgs { uint16_t *sv_win, *sv_wh; };
+// what the warp stage of that instantiation stores, and the wave's staging tile
+struct WarpSave { uint16_t *in, *hidden, *st; int64_t N, p; };
 
 // ---------------------------------------------------------------- the encoders in registers
 
@@ -237,8 +245,10 @@ __device__ __forceinline__ void stage_warp(const WarpArgs &w, nfa_v4u *wimg, flo
 }
 
 // x <- x + warp([enc(x), enc(t)]) for the wave's 32 points, on both lane halves (header: chain, hand-off).  No barrier.
-template <class E>
-__device__ __forceinline__ void warp_stage(const Shape &S, const nfa_v4u *wimg, const float *wb, float (&x)[3], float t, int lane_)
+// SAVE: the input rows leave through the wave's staging tile, the activations as store_tile_row's 64-byte runs.
+template <class E, bool SAVE = false>
+__device__ __forceinline__ void warp_stage(const Shape &S, const nfa_v4u *wimg, const float *wb, float (&x)[3], float t, int lane_,
+                                           const WarpSave *sv = nullptr)
 {
     constexpr int W = NF_WARP_W, MT = W / 32, KQ = W / 16, KQ0 = NF_WARP_KQ0;
     // The stage's per-lane addresses and selects are formed from a lane index the compiler cannot see through: hoisted out of
@@ -248,6 +258,12 @@ __device__ __forceinline__ void warp_stage(const Shape &S, const nfa_v4u *wimg, 
     const int h = lane >> 5;
     nfa_v4u xf[KQ0];
     warp_frags<E>(x, t, lane, h, xf);
+    if constexpr (SAVE) {
+        const int r = lane & 31;
+#pragma unroll
+        for (int q = 0; q < KQ0; ++q) stage_put8(sv->st, NF_WARP_DIMS, r, 16 * q + 8 * h, xf[q]);
+        stage_flush(sv->st, sv->in, sv->p - r, tile_rows(sv->p - r, sv->N), NF_WARP_DIMS, lane);
+    }
     f32x16 acc[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
@@ -264,6 +280,8 @@ __device__ __forceinline__ void warp_stage(const Shape &S, const nfa_v4u *wimg, 
             for (int i = 0; i < 16; ++i) acc[m][i] = acc[m][i] < 0.f ? 0.f : acc[m][i];
             hf[2 * m] = acc_frag<E>(acc[m], 0);
             hf[2 * m + 1] = acc_frag<E>(acc[m], 1);
+            if constexpr (SAVE)
+                if (sv->p < sv->N) store_tile_row<W>(sv->hidden + (int64_t)(l - 1) * sv->N * W, sv->p, m, h, hf[2 * m], hf[2 * m + 1]);
         }
         if (l == S.n_hidden) break;
         const bool cat = S.cat(l);
@@ -340,15 +358,19 @@ __device__ __forceinline__ void put_out(void *out, bool out_f32, int64_t i, floa
 // WARP: the T-NeRF field, the warp stage in front of every pass; the instantiations without it never see WarpArgs.
 // A W = 128 WARP instantiation asks for the two waves per SIMD its plain twin has by itself (1: no request).
 // SAVE: nfa_nerf_train_fwd, the full query that also stores what the backward reads; the arithmetic is untouched.
+// WARP with SAVE: nfa_tnerf_train_fwd (header: T-NeRF training forward); one workgroup per CU by its LDS, so no request either.
 template <class E, int W, bool RAYS, bool FULL, bool WARP = false, bool SAVE = false>
-__global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP && W == 128 ? 2 : 1))) void nerf_field_kernel(const std::conditional_t<WARP, TNerfArgs, NerfArgs> a)
+__global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP && !SAVE && W == 128 ? 2 : 1))) void nerf_field_kernel(
+    const std::conditional_t<WARP, std::conditional_t<SAVE, TNerfTrainArgs, TNerfArgs>, NerfArgs> a)
 {
     constexpr int MT = W / 32, KQ = W / 16, KQX = (NF_POS_DIMS + 15) / 16, KQD = (NF_DIR_DIMS + 15) / 16;
     constexpr int HW = NF_HEAD_W, HMT = HW / 32, HKQ = HW / 16;
     constexpr int MAXV = ((KQ + KQX) * 64 + NF_THREADS - 1) / NF_THREADS;   // the trunk's cat layer, the largest piece
     static_assert(KQ + KQD <= KQ + KQX && HKQ <= KQ, "no piece of the head is larger");
-    static_assert(!SAVE || (FULL && !WARP), "the training forward is the full vanilla query");
+    static_assert(!SAVE || FULL, "the training forward is a full query");
     constexpr int HX = W + NF_DIR_DIMS;   // the head's input row
+    constexpr int ST_BYTES = WARP ? 16 * HX * 2 : row_stage_bytes(HX);   // WARP: the head's input rows leave as two spans of 16
+    static_assert(ST_BYTES % 16 == 0 && ST_BYTES >= row_stage_bytes(NF_POS_DIMS) && ST_BYTES >= row_stage_bytes(NF_WARP_DIMS), "every staged tile fits");
     extern __shared__ __attribute__((aligned(16))) unsigned char nf_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const Shape &T = a.T, &H = a.H;
@@ -361,11 +383,12 @@ __global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP
     for (int i = threadIdx.x; i < n_tb; i += NF_THREADS) tb[i] = i - D * W < W + 1 ? a.tbias[i] : 0.f;
     for (int i = threadIdx.x; i < n_hb; i += NF_THREADS) hb[i] = i - Dc * HW < 3 ? a.hbias[i] : 0.f;
     nfa_v4u *wimg = reinterpret_cast<nfa_v4u *>(hb + n_hb);   // WARP: the resident image, 16-byte aligned (every part before it is)
-    uint16_t *st = reinterpret_cast<uint16_t *>(hb + n_hb) + wave * (row_stage_bytes(HX) / 2);   // SAVE: the wave's staging tile, there instead
+    uint16_t *st = reinterpret_cast<uint16_t *>(hb + n_hb) + wave * (ST_BYTES / 2);   // SAVE: the wave's staging tile, there instead
     float *wb = nullptr;
     if constexpr (WARP) {
         wb = reinterpret_cast<float *>(wimg + a.w.img16);
         stage_warp(a.w, wimg, wb);   // ring.start()'s barriers publish it
+        if constexpr (SAVE) st = reinterpret_cast<uint16_t *>(wb + a.w.S.lds_bias_floats()) + wave * (ST_BYTES / 2);   // behind both
     }
     FieldRing<MAXV> ring;
     if (threadIdx.x == 0) nerf_pieces(T, H, FULL, tab, nullptr, nullptr);
@@ -384,7 +407,12 @@ __global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP
         float x[3], dir[3] = {0.f, 0.f, 0.f}, t = 0.f;
         if constexpr (WARP) {
             load_point<RAYS, FULL>(a, a.w.times, pc, x, dir, t);
-            warp_stage<E>(a.w.S, wimg, wb, x, t, lane);
+            if constexpr (SAVE) {
+                const WarpSave sv = {a.sv_win, a.sv_wh, st, N, p};
+                warp_stage<E, true>(a.w.S, wimg, wb, x, t, lane, &sv);
+            } else {
+                warp_stage<E>(a.w.S, wimg, wb, x, t, lane);
+            }
             if (a.w.warped && h == 0 && p < N) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) a.w.warped[3 * p + k] = x[k];
@@ -459,17 +487,33 @@ __global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP
                 if (m < MT) {   // no activation: the bottleneck is a linear layer
                     bf[2 * m] = acc_frag<E>(o, 0);
                     bf[2 * m + 1] = acc_frag<E>(o, 1);
-                    if constexpr (SAVE) {
+                    if constexpr (SAVE && !WARP) {
                         stage_put_acc_frag(st, HX, r, h, m, 0, bf[2 * m]);
                         stage_put_acc_frag(st, HX, r, h, m, 1, bf[2 * m + 1]);
                     }
                 }
             }
         }
-        if constexpr (SAVE) {   // the head's input rows [N, W + 27]: the bottleneck staged above, then the encoded direction
+        if constexpr (SAVE && !WARP) {   // the head's input rows [N, W + 27]: the bottleneck staged above, then the encoded direction
 #pragma unroll
             for (int q = 0; q < KQD; ++q) stage_put8(st, HX, r, W + 16 * q + 8 * h, df[q]);
             stage_flush(st, a.sv_hx, row0, tile_rows(row0, N), HX, lane);
+        }
+        if constexpr (SAVE && WARP) {   // the same rows as two spans of 16: half the staging (header: T-NeRF training forward)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                if ((r >> 4) == s) {
+#pragma unroll
+                    for (int m = 0; m < MT; ++m) {
+                        stage_put_acc_frag(st, HX, r & 15, h, m, 0, bf[2 * m]);
+                        stage_put_acc_frag(st, HX, r & 15, h, m, 1, bf[2 * m + 1]);
+                    }
+#pragma unroll
+                    for (int q = 0; q < KQD; ++q) stage_put8(st, HX, r & 15, W + 16 * q + 8 * h, df[q]);
+                }
+                const int left = tile_rows(row0, N) - 16 * s;
+                stage_flush(st, a.sv_hx, row0 + 16 * s, left < 0 ? 0 : (left < 16 ? left : 16), HX, lane);
+            }
         }
         const bool live = h == 0 && p < N;
         if (live && a.sigma) put_out<E>(a.sigma, a.sigma_f32 != 0, p, o[0], a.activated != 0, false);
@@ -578,24 +622,6 @@ __global__ __launch_bounds__(256) void nerf_head_pack_kernel(Shape S, int tw, co
 
 // ---------------------------------------------------------------- host side
 
-// The one statement of the warp networks the T-NeRF entries hold (nerfacc_amd/fields.py: tnerf_field_limits_error says the same
-// words), checked after elem and before the trunk and the head.
-int check_warp_shape(const char *who, int32_t elem, const nfa_mlp_desc *warp, Shape *S)
-{
-    NFA_REQUIRE(elem == NFA_ELEM_F16 || elem == NFA_ELEM_BF16, "%s: elem %d: the networks' type is NFA_ELEM_F16 or NFA_ELEM_BF16", who, elem);
-    NFA_REQUIRE(warp, "%s: the network descriptor is null", who);
-    const int d = warp->n_hidden;
-    NFA_REQUIRE(warp->width == NF_WARP_W, "%s: warp width %d: %d neurons are supported", who, warp->width, NF_WARP_W);
-    NFA_REQUIRE(d >= 1 && d <= NF_WARP_MAX_HIDDEN, "%s: warp n_hidden %d: 1 to %d hidden layers are supported", who, d, NF_WARP_MAX_HIDDEN);
-    NFA_REQUIRE(warp->n_in == NF_WARP_DIMS, "%s: warp n_in %d: the encoded position and time have %d features", who, warp->n_in, NF_WARP_DIMS);
-    NFA_REQUIRE(warp->n_out == 3, "%s: warp n_out %d: 3 outputs (the deformation)", who, warp->n_out);
-    NFA_REQUIRE(warp->bias == 1, "%s: warp bias %d: the field's networks have biases (1)", who, warp->bias);
-    NFA_REQUIRE((warp->skip_mask & ~((2 << d) - 4)) == 0, "%s: warp skip_mask 0x%x: only bits 2 to n_hidden (%d) may be set: layer 0 "
-                "takes x itself and layer 1 follows it", who, (unsigned)warp->skip_mask, d);
-    *S = Shape{NF_WARP_DIMS, 3, NF_WARP_W, d, 1, warp->skip_mask};
-    return NFA_OK;
-}
-
 // bytes of the resident warp image and its biases in LDS
 int64_t warp_lds_bytes(const Shape &S) { return S.fwd_off(S.layers()) * 2 + (int64_t)S.lds_bias_floats() * 4; }
 
@@ -620,12 +646,13 @@ int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *tru
                const void *head_image, const float *trunk_bias, const float *head_bias, const nfa_ngp_input *in, int64_t N,
                int32_t activated, void *sigma, int32_t sigma_elem, void *rgb, int32_t rgb_elem, nfa_stream_t stream,
                const WarpArgs *warp = nullptr,   // the T-NeRF entries: S checked, the pointers as the caller gave them
-               bool train = false, const nfa_nerf_saved *save = nullptr)   // nfa_nerf_train_fwd
+               bool train = false, const nfa_nerf_saved *save = nullptr,   // nfa_nerf_train_fwd
+               const nfa_tnerf_saved *wsave = nullptr)                      // nfa_tnerf_train_fwd, next to warp and save
 {
     Shape T, H = {};
     if (int rc = check_field_shape(who, elem, trunk, head, 0, N, &T, full ? &H : nullptr)) return rc;
     NFA_REQUIRE(in, "%s: the input descriptor is null", who);
-    NFA_REQUIRE(!train || save, "%s: the saved-buffers descriptor is null", who);
+    NFA_REQUIRE(!train || (save && (!warp || wsave)), "%s: the saved-buffers descriptor is null", who);
     NFA_REQUIRE(activated == 0 || activated == 1, "%s: activated must be 0 (raw outputs) or 1 (relu, sigmoid) (got %d)", who, activated);
     NFA_REQUIRE(sigma_elem == NFA_ELEM_F32 || sigma_elem == elem, "%s: sigma_elem %d: float32 or the networks' type (%d)", who, sigma_elem, elem);
     NFA_REQUIRE(!full || rgb_elem == NFA_ELEM_F32 || rgb_elem == elem, "%s: rgb_elem %d: float32 or the networks' type (%d)", who, rgb_elem, elem);
@@ -647,8 +674,10 @@ int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *tru
     if (train) {
         NFA_REQUIRE(save->enc_x && save->trunk_hidden && save->head_in && save->head_hidden,
                     "%s: null pointer (enc_x, trunk_hidden, head_in or head_hidden)", who);
+        NFA_REQUIRE(!warp || (wsave->warp_in && wsave->warp_hidden && wsave->warped), "%s: null pointer (warp_in, warp_hidden or warped)", who);
         NFA_REQUIRE(aligned_to(save->enc_x, 16) && aligned_to(save->trunk_hidden, 16) && aligned_to(save->head_in, 16) &&
-                    aligned_to(save->head_hidden, 16), "%s: misaligned pointer (the saved buffers 16)", who);
+                    aligned_to(save->head_hidden, 16) && (!warp || (aligned_to(wsave->warp_in, 16) && aligned_to(wsave->warp_hidden, 16))),
+                    "%s: misaligned pointer (the saved buffers 16)", who);
         a.sv_x = static_cast<uint16_t *>(save->enc_x), a.sv_th = static_cast<uint16_t *>(save->trunk_hidden);
         a.sv_hx = static_cast<uint16_t *>(save->head_in), a.sv_hh = static_cast<uint16_t *>(save->head_hidden);
     }
@@ -665,18 +694,26 @@ int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *tru
     a.rgb = full ? rgb : nullptr, a.rgb_f32 = rgb_elem == NFA_ELEM_F32;
     a.activated = activated;
     const int64_t lds = nerf_lds_bytes(slot16, trunk_bias_floats(T) + (full ? head_bias_floats(H) : 0)) + (warp ? warp_lds_bytes(warp->S) : 0) +
-                        (train ? (int64_t)NF_WAVES * row_stage_bytes(T.W + NF_DIR_DIMS) : 0);
+                        (train ? (int64_t)NF_WAVES * (warp ? 16 * (T.W + NF_DIR_DIMS) * 2 : row_stage_bytes(T.W + NF_DIR_DIMS)) : 0);
     const int64_t want = ceil_div64(N, NF_POINTS);
     const unsigned grid = (unsigned)(want < NFA_MLP_STREAM_GROUPS ? want : NFA_MLP_STREAM_GROUPS);
     int rc = NFA_OK;
     auto launch = [&](auto tag, auto w, auto rays_c, auto full_c, auto warp_c) {
         using E = typename decltype(tag)::type;
         constexpr bool WARP = decltype(warp_c)::value;
-        if constexpr (decltype(full_c)::value && !WARP) {
+        if constexpr (decltype(full_c)::value) {
             if (train) {
-                auto kern = nerf_field_kernel<E, decltype(w)::value, decltype(rays_c)::value, true, false, true>;
+                auto kern = nerf_field_kernel<E, decltype(w)::value, decltype(rays_c)::value, true, WARP, true>;
                 if ((rc = allow_lds(who, kern, lds)) != NFA_OK) return;
-                kern<<<grid, NF_THREADS, (size_t)lds, as_stream(stream)>>>(a);
+                if constexpr (WARP) {
+                    TNerfTrainArgs ta = {};
+                    static_cast<NerfArgs &>(ta) = a;
+                    ta.w = *warp;
+                    ta.sv_win = static_cast<uint16_t *>(wsave->warp_in), ta.sv_wh = static_cast<uint16_t *>(wsave->warp_hidden);
+                    kern<<<grid, NF_THREADS, (size_t)lds, as_stream(stream)>>>(ta);
+                } else {
+                    kern<<<grid, NF_THREADS, (size_t)lds, as_stream(stream)>>>(a);
+                }
                 return;
             }
         }
@@ -766,6 +803,20 @@ int nfa_tnerf_field(int32_t elem, const nfa_mlp_desc *warp, const nfa_mlp_desc *
     const WarpArgs w = warp_args(S, warp_image, warp_bias, times, warped);
     return nerf_query(who, true, elem, trunk, head, trunk_image, head_image, trunk_bias, head_bias, in, n_points, activated, sigma, sigma_elem,
                       rgb, rgb_elem, stream, &w);
+}
+
+int nfa_tnerf_train_fwd(int32_t elem, const nfa_mlp_desc *warp, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *warp_image,
+                        const void *trunk_image, const void *head_image, const float *warp_bias, const float *trunk_bias,
+                        const float *head_bias, const nfa_ngp_input *in, const float *times, int64_t n_points, int32_t activated,
+                        const nfa_nerf_saved *save, const nfa_tnerf_saved *warp_save, void *sigma, int32_t sigma_elem, void *rgb,
+                        int32_t rgb_elem, nfa_stream_t stream)
+{
+    const char *who = "nfa_tnerf_train_fwd";
+    Shape S;
+    if (int rc = check_warp_shape(who, elem, warp, &S)) return rc;
+    const WarpArgs w = warp_args(S, warp_image, warp_bias, times, warp_save ? warp_save->warped : nullptr);
+    return nerf_query(who, true, elem, trunk, head, trunk_image, head_image, trunk_bias, head_bias, in, n_points, activated, sigma, sigma_elem,
+                      rgb, rgb_elem, stream, &w, true, save, warp_save);
 }
 
 int nfa_tnerf_density(int32_t elem, const nfa_mlp_desc *warp, const nfa_mlp_desc *trunk, const void *warp_image, const void *trunk_image,

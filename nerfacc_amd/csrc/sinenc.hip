@@ -36,6 +36,7 @@
 // Half element types are widened as a piece is loaded and rounded once as it is stored.
 #include "common.hip.h"
 #include "axis.h"   // store_elem / load_elem
+#include "sinenc_dev.h"   // the backward's arithmetic, shared with nerf_train.hip
 
 namespace nfa {
 
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(NFA_SINENC_BLOCK) void sinenc_bwd_kernel(const floa
             if constexpr (MOD) a = sin_amp(var, fw, n0 * S.D + e, it.k, sc);
             float *row = tile + it.p * S.K + S.id + it.j;
             const float gs = row[0], gc = row[S.DL];
-            row[0] = (sc * a) * (gs * c - gc * s);
+            row[0] = sin_bwd_tx(sc, a, gs, gc, s, c);
             if (grad_var != nullptr) row[S.DL] = (sc * sc) * (gs * (a * s) + gc * (a * c));
         }
         __syncthreads();
@@ -189,9 +190,7 @@ __global__ __launch_bounds__(NFA_SINENC_BLOCK) void sinenc_bwd_kernel(const floa
             const int p = (int)(((float)i + 0.5f) * S.rD), d = i - p * S.D;
             const float *row = tile + p * S.K;
             if (grad_x != nullptr) {
-                float acc = S.id ? row[d] : 0.0f;
-                for (int k = 0; k < S.L; ++k) acc = acc + row[S.id + k * S.D + d];
-                grad_x[n0 * S.D + i] = acc;
+                grad_x[n0 * S.D + i] = sin_bwd_sum(S.id ? row[d] : 0.0f, row + S.id + d, S.L, S.D);
             }
             if (grad_var != nullptr) {
                 float acc = 0.0f;

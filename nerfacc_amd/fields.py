@@ -761,6 +761,87 @@ def tnerf_field_limits_error(warp: tuple, trunk: Optional[tuple], head: Optional
     return nerf_field_limits_error(trunk, head)
 
 
+class _TNerfTrainFn(torch.autograd.Function):
+    """A full T-NeRF query with grad as one launch (``nfa_tnerf_train_fwd``): the no-grad launch's outputs, and the buffers the
+    backward and the three weight-gradient passes read (shaped like ``_NerfTrainFn``)."""
+
+    @staticmethod
+    def forward(ctx, warp_p: Tensor, trunk_p: Tensor, head_p: Tensor, field: "TNeRFRadianceField", activated: bool, n: int, inputs: dict,
+                rgb_dtype, sigma_dtype):
+        ctx.set_materialize_grads(False)
+        w, t, h = field.warp, field.nerf.mlp.trunk, field.nerf.mlp.head
+        dev, dt, W = trunk_p.device, field.dtype, t.n_neurons
+        new = lambda *s: torch.empty(*s, dtype=dt, device=dev)
+        saved = [new(n, NERF_POS_DIMS), new(t.n_hidden_layers, n, W), new(n, W + NERF_DIR_DIMS), new(h.n_hidden_layers, n, NERF_HEAD_WIDTH),
+                 new(n, TNERF_WARP_DIMS), new(w.n_hidden_layers, n, TNERF_WARP_WIDTH)]
+        rgb, sigma, xw = field._launch("full", n, activated, rgb_dtype=rgb_dtype, sigma_dtype=sigma_dtype, warped=True, save=saved, **inputs)
+        ctx.field, ctx.activated, ctx.n = field, activated, n
+        ctx.save_for_backward(warp_p, trunk_p, head_p, *saved, xw, *([rgb, sigma] if activated else []))
+        return rgb, sigma
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_sigma):
+        need = ctx.needs_input_grad[:3]
+        if not any(need) or (g_rgb is None and g_sigma is None):
+            return (None,) * 9
+        warp_p, trunk_p, head_p, *rest = ctx.saved_tensors
+        g = _TNerfTrainBwdFn.apply(warp_p, trunk_p, head_p, g_rgb, g_sigma, ctx.field, ctx.activated, ctx.n, need, *[t.detach() for t in rest])
+        return (*g, None, None, None, None, None, None)
+
+
+class _TNerfTrainBwdFn(torch.autograd.Function):
+    """The backward as a function of its own (as ``_NerfTrainBwdFn``): one launch for all three networks' data gradients
+    (``nfa_tnerf_train_bwd``), then the warp's and the two streamed weight-gradient passes.  Differentiating it again raises."""
+
+    @staticmethod
+    def forward(ctx, warp_p, trunk_p, head_p, g_rgb, g_sigma, field, activated, n, need, *saved):
+        ctx.set_materialize_grads(False)
+        ctx.name = type(field).__name__
+        if n == 0:
+            return tuple(torch.zeros_like(p) if want else None for p, want in zip((warp_p, trunk_p, head_p), need))
+        w, t, h = field.warp, field.nerf.mlp.trunk, field.nerf.mlp.head
+        dev, dt, W = trunk_p.device, field.dtype, t.n_neurons
+        elem, f32 = B.ELEM_CODES[dt], B.ELEM_CODES[torch.float32]
+        enc_x, t_hidden, h_in, h_hidden, w_in, w_hidden, xw, *ys = saved
+        y_rgb, y_sigma = ys if activated else (None, None)
+
+        def grad(g):   # float32 or the networks' type, contiguous; the kernel rounds once
+            if g is None:
+                return None, f32
+            g = (g if g.dtype in (torch.float32, dt) else g.float()).contiguous()
+            return g, B.ELEM_CODES[g.dtype]
+
+        (g_rgb, rgb_elem), (g_sigma, sigma_elem) = grad(g_rgb), grad(g_sigma)
+        new = lambda *s: torch.empty(*s, dtype=dt, device=dev)
+        hdz, hdzo, tdz, tdzo = new(h.n_hidden_layers, n, NERF_HEAD_WIDTH), new(n, 3), new(t.n_hidden_layers, n, W), new(n, W + 1)
+        wdz, wdzo = new(w.n_hidden_layers, n, TNERF_WARP_WIDTH), new(n, 3)
+        gr = B.NerfGrads(B.ptr(g_rgb), rgb_elem, B.ptr(g_sigma), sigma_elem, B.ptr(y_rgb), B.ELEM_CODES[y_rgb.dtype] if activated else f32,
+                         B.ptr(y_sigma), B.ELEM_CODES[y_sigma.dtype] if activated else f32, B.ptr(hdz), B.ptr(hdzo), B.ptr(tdz), B.ptr(tdzo))
+        sv = B.NerfSaved(B.ptr(enc_x), B.ptr(t_hidden), B.ptr(h_in), B.ptr(h_hidden))
+        wsv, wgr = B.TNerfSaved(B.ptr(w_in), B.ptr(w_hidden), B.ptr(xw)), B.TNerfGrads(B.ptr(wdz), B.ptr(wdzo))
+        out = []
+        with torch.cuda.device(dev):
+            B.call("nfa_tnerf_train_bwd", elem, w._desc, t._desc, h._desc, B.ptr(w._images(warp_p)[1]), B.ptr(t._images(trunk_p)[1]),
+                   B.ptr(h._images(head_p)[1]), n, int(activated), ctypes.byref(sv), ctypes.byref(wsv), ctypes.byref(gr), ctypes.byref(wgr),
+                   B.stream())
+            for mlp, params, want, x, hidden, dz, dzo in ((w, warp_p, need[0], w_in, w_hidden, wdz, wdzo), (t, trunk_p, need[1], enc_x, t_hidden, tdz, tdzo),
+                                                          (h, head_p, need[2], h_in, h_hidden, hdz, hdzo)):
+                g_p = None
+                if want:
+                    P = params.numel()
+                    partials = torch.empty(mlp._slices(n) * P, dtype=torch.float32, device=dev)
+                    g_p = torch.empty(P, dtype=torch.float32, device=dev)
+                    mlp._weight_gradient(elem, x, hidden, dz, dzo, n, partials, g_p, zero_bias=False)
+                out.append(g_p)
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *gg):
+        raise NotImplementedError(f"{ctx.name}(fused_training=True): the second order (differentiating the parameters' gradients again, "
+                                  "create_graph=True) is not implemented by the fused training pass; construct the module with "
+                                  "fused_training=False")
+
+
 class TNeRFRadianceField(nn.Module):
     """The reference's dynamic-scene field (ref: examples/radiance_fields/mlp.py: ``TNeRFRadianceField``, the field of
     ``train_mlp_tnerf.py``): ``posi_encoder`` and ``time_encoder`` (:class:`SinusoidalEncoding` (3, 0, 4) and (1, 0, 4) with
@@ -778,10 +859,23 @@ class TNeRFRadianceField(nn.Module):
     are the composed chain's bits; the raw colour carries the vanilla field's one last-bit difference.
 
     ``fused`` is a bool or ``{"density": bool, "full": bool}`` (:meth:`warped_positions` follows ``"density"``); it is handed
-    to ``nerf`` as well.  DESIGN.md, "Fused T-NeRF field", has the measurements behind the defaults."""
+    to ``nerf`` as well.  DESIGN.md, "Fused T-NeRF field", has the measurements behind the defaults.
 
-    def __init__(self, dtype: torch.dtype = torch.float16, generator: Optional[torch.Generator] = None, fused: Union[bool, dict] = True):
+    ``fused_training=True`` (off by default) gives a full query WITH grad the same treatment when only parameters require grad
+    and ``warp.params`` is among them: ``forward(x, t, condition)``, ``query_raw`` and ``query_on_rays`` take one launch forward
+    (``nfa_tnerf_train_fwd``: the no-grad launch's bits, and what the backward reads), one launch backward for all three
+    networks' data gradients (``nfa_tnerf_train_bwd``, csrc/nerf_train.hip: the trunk's ``dL/dx``, the position encoder's
+    backward and the warp network's chain follow the vanilla pass in registers and LDS), then the three networks' usual
+    weight-gradient passes.  Gradients have the composed chain's rounding points and are the same bits on every run;
+    differentiating them again raises ``NotImplementedError``.  Inputs that require grad, ``condition=None`` or a broadcast
+    condition, a ``t`` or ``timestamps`` of another shape, CPU tensors, density-only queries and :meth:`warped_positions`,
+    ``fused={"full": False}``, shapes outside :meth:`fused_supported` and a frozen warp keep the composed chain (DESIGN.md,
+    "Fused T-NeRF field: training")."""
+
+    def __init__(self, dtype: torch.dtype = torch.float16, generator: Optional[torch.Generator] = None, fused: Union[bool, dict] = True,
+                 fused_training: bool = False):
         super().__init__()
+        self.fused_training = bool(fused_training)
         self.posi_encoder = SinusoidalEncoding(3, 0, 4, True, out_dtype=dtype)
         self.time_encoder = SinusoidalEncoding(1, 0, 4, True, out_dtype=dtype)
         self.warp = reference_mlp(self.posi_encoder.latent_dim + self.time_encoder.latent_dim, 3, 4, 64, 2, dtype=dtype,
@@ -811,11 +905,27 @@ class TNeRFRadianceField(nn.Module):
             return False
         return not (torch.is_grad_enabled() and any(t.requires_grad for t in [*self.parameters(), *ts]))
 
+    def _use_train(self, *tensors: Tensor) -> bool:
+        """The fused training pass serves this full query: grad is on, wanted by parameters only, the warp's among them."""
+        if not (self.fused_training and self.fused["full"] and torch.is_grad_enabled() and self.fused_supported(True)):
+            return False
+        dev = self.warp.params.device
+        if not (all(t.is_cuda and t.device == dev for t in tensors) and all(t.dtype == torch.float32 for t in tensors if t.is_floating_point())):
+            return False
+        return self.warp.params.requires_grad and not any(t.requires_grad for t in tensors)
+
+    def _train(self, activated: bool, n: int, rgb_dtype=None, sigma_dtype=None, **inputs):
+        """``(rgb [n, 3], sigma [n])`` of one training launch, raw or activated, differentiable towards the parameters."""
+        m = self.nerf.mlp
+        with torch.autocast("cuda", enabled=False):
+            return _TNerfTrainFn.apply(self.warp.params, m.trunk.params, m.head.params, self, activated, n, inputs, rgb_dtype, sigma_dtype)
+
     def _launch(self, kind: str, n: int, activated: bool = False, positions=None, times=None, dirs=None, rays=None, warped: bool = False,
-                rgb_dtype=None, sigma_dtype=None):
+                rgb_dtype=None, sigma_dtype=None, save: Optional[List[Tensor]] = None):
         """One fused launch.  ``kind``: ``"full"``: ``(rgb [n, 3], sigma [n], warped [n, 3] or None)``; ``"density"``:
         ``(None, sigma, warped or None)``; ``"warp"``: ``(None, None, warped)``.  ``times``: [n] with ``positions``, [n_rays]
-        with ``rays``."""
+        with ``rays``.  ``save``: the training forward, which fills these six buffers (struct nfa_nerf_saved, then ``warp_in`` and
+        ``warp_hidden`` of struct nfa_tnerf_saved, whose third member is ``warped``)."""
         full = kind == "full"
         w, t, h = self.warp, self.nerf.mlp.trunk, self.nerf.mlp.head
         dev = w.params.device
@@ -840,7 +950,14 @@ class TNeRFRadianceField(nn.Module):
                        B.stream())
                 return rgb, sigma, xw
             timg = t._images(tp)[0]
-            if full:
+            if save is not None:
+                hp = h.params
+                sv, wsv = B.NerfSaved(*[B.ptr(b) for b in save[:4]]), B.TNerfSaved(B.ptr(save[4]), B.ptr(save[5]), B.ptr(xw))
+                B.call("nfa_tnerf_train_fwd", elem, w._desc, t._desc, h._desc, B.ptr(wimg), B.ptr(timg), B.ptr(self.nerf._head_image()),
+                       w._bias_ptr(wp), t._bias_ptr(tp), h._bias_ptr(hp), ctypes.byref(inp), B.ptr(times), n, int(activated),
+                       ctypes.byref(sv), ctypes.byref(wsv), B.ptr(sigma), B.ELEM_CODES[sigma.dtype], B.ptr(rgb), B.ELEM_CODES[rgb.dtype],
+                       B.stream())
+            elif full:
                 hp = h.params
                 B.call("nfa_tnerf_field", elem, w._desc, t._desc, h._desc, B.ptr(wimg), B.ptr(timg), B.ptr(self.nerf._head_image()),
                        w._bias_ptr(wp), t._bias_ptr(tp), h._bias_ptr(hp), ctypes.byref(inp), B.ptr(times), n, int(activated), B.ptr(sigma),
@@ -876,6 +993,9 @@ class TNeRFRadianceField(nn.Module):
         return self.query_density(x, timestamps[idxs]) * step_size   # (small densities: 1 - exp(-density * step_size) is the same)
 
     def forward(self, x: Tensor, t: Tensor, condition: Optional[Tensor] = None):
+        if condition is not None and condition.shape == x.shape and self._point_times(x, t) and self._use_train(x, t, condition):
+            rgb, sigma = self._train(True, x.numel() // 3, positions=x.reshape(-1, 3), times=t.reshape(-1), dirs=condition.reshape(-1, 3))
+            return rgb.view(*x.shape[:-1], 3), sigma.view(*x.shape[:-1], 1)
         if condition is not None and condition.shape == x.shape and self._point_times(x, t) and self._use_fused(True, x, t, condition):
             rgb, sigma, _ = self._launch("full", x.numel() // 3, True, positions=x.reshape(-1, 3), times=t.reshape(-1),
                                          dirs=condition.reshape(-1, 3))
@@ -886,6 +1006,10 @@ class TNeRFRadianceField(nn.Module):
 
     def query_raw(self, positions: Tensor, t: Tensor, directions: Tensor):
         """``(raw_rgbs [..., 3], raw_sigmas [...])`` at world positions and times ``[..., 1]``, before any activation."""
+        if positions.shape == directions.shape and self._point_times(positions, t) and self._use_train(positions, t, directions):
+            rgb, sigma = self._train(False, positions.numel() // 3, positions=positions.reshape(-1, 3), times=t.reshape(-1),
+                                     dirs=directions.reshape(-1, 3))
+            return rgb.view(*positions.shape[:-1], 3), sigma.view(positions.shape[:-1])
         if positions.shape == directions.shape and self._point_times(positions, t) and self._use_fused(True, positions, t, directions):
             rgb, sigma, _ = self._launch("full", positions.numel() // 3, False, positions=positions.reshape(-1, 3), times=t.reshape(-1),
                                          dirs=directions.reshape(-1, 3))
@@ -909,6 +1033,8 @@ class TNeRFRadianceField(nn.Module):
                       raw: bool = True):
         """The field at the midpoints of packed ray samples, each at its ray's time.  ``raw=True``: ``(raw_rgbs [n, 3],
         raw_sigmas [n])``, what :func:`nerfacc_amd.rendering_from_raw` takes; otherwise ``(rgbs [n, 3], sigmas [n])`` activated."""
+        if self._ray_times(rays_o, timestamps) and self._use_train(rays_o, rays_d, t_starts, t_ends, timestamps, ray_indices):
+            return self._train(not raw, t_starts.numel(), rays=(rays_o, rays_d, t_starts, t_ends, ray_indices), times=timestamps.reshape(-1))
         if self._ray_times(rays_o, timestamps) and self._use_fused(True, rays_o, rays_d, t_starts, t_ends, timestamps, ray_indices):
             return self._launch("full", t_starts.numel(), not raw, rays=(rays_o, rays_d, t_starts, t_ends, ray_indices),
                                 times=timestamps.reshape(-1))[:2]
