@@ -1666,6 +1666,43 @@ int nfa_tnerf_train_bwd(int32_t elem, const nfa_mlp_desc *warp, const nfa_mlp_de
                         int32_t activated, const nfa_nerf_saved *saved, const nfa_tnerf_saved *warp_saved, const nfa_nerf_grads *grads,
                         const nfa_tnerf_grads *warp_grads, nfa_stream_t stream);
 
+/* ------------------------------------------------------------------ fused NDR T-NeRF field query (csrc/ndr_warp.h, nerf_field.hip) */
+
+/* The no-grad query of the reference's NDRTNeRFRadianceField (examples/radiance_fields/mlp.py:286-395) as one launch: the
+ * invertible warp (three coupling blocks, each time_layers_1 -> warp_layers_1 -> w += dw -> time_layers_2 -> warp_layers_2 ->
+ * inverse 2-D rotation of (u, v) - translation; the axes rolled [1, 2, 0] and [2, 0, 1] between the blocks), then everything
+ * nfa_nerf_field (nfa_ndr_field) or nfa_nerf_density (nfa_ndr_density) does at the warped position.  nfa_ndr_warp is the warp alone.
+ * The warp's shapes are fixed at the reference's: time encoder (1, 0, 4), position encoders (2, 0, 4) and (1, 0, 4), time layers
+ * 9 -> 64, warp_layers_1 82 -> 2 x 128 -> 1, warp_layers_2 73 -> 128 -> 3, all with biases.
+ * warp_image, of type elem and 16-byte aligned: warp_image_elems = 3 * 49152 elements, for block i = 0, 1, 2 in this order the
+ *   image of time_layers_1[i] (1024 elements), the forward image of nfa_mlp_net_pack_weights for warp_layers_1[i] (32768), the image
+ *   of time_layers_2[i] (1024) and the forward image for warp_layers_2[i] (14336).  A time layer's image is that of a layer 0 with
+ *   two row tiles and one k-step: element ((m * 64 + 32 h + r) * 8 + j) is W[32 m + r][8 h + j], zero for columns >= 9.
+ * warp_bias: warp_bias_floats = 3 * 576 floats, per block the biases of time_layers_1[i] (64), warp_layers_1[i] (128, 128, then the
+ *   output layer's one bias and 31 zeros), time_layers_2[i] (64), warp_layers_2[i] (128, then three biases and 29 zeros).
+ * Both sizes are checked first after elem; the remaining checks are those of nfa_nerf_field / nfa_nerf_density, the warp's pointers
+ * next to the other pointers: n_points == 0 returns before any pointer is looked at, as everywhere.
+ * times, warped, in, activated, sigma, rgb and the launch: as for nfa_tnerf_field.  The weights go through the LDS ring of the
+ * trunk, 54 pieces in front of the trunk's.
+ * Rounding: the encoded columns once to elem; a time layer is half operands, a float32 accumulator that starts from the bias, one
+ * rounding to elem; the nets are nfa_mlp_net_fwd's arithmetic on the natural-order cat rows with a float32 output that is never
+ * rounded; w + dw, (u, v) - translation, sincosf(theta) and the rotation (c du + s dv, c dv - s du) are float32, every operation
+ * rounded on its own.  warped is bit for bit what those passes give one after the other.
+ * nfa_ndr_time_features is the composed chain's pass for the six time layers: time_image [6][1024] the six images above in the
+ * order time_layers_1[0], time_layers_2[0], time_layers_1[1], ..., time_bias [6][64] (both 16-byte aligned), times [n_points];
+ * out [n_points, 6, 64] of type elem, the bits the fused stage forms in registers. */
+int nfa_ndr_field(int32_t elem, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *warp_image, int64_t warp_image_elems,
+                  const void *trunk_image, const void *head_image, const float *warp_bias, int64_t warp_bias_floats, const float *trunk_bias,
+                  const float *head_bias, const nfa_ngp_input *in, const float *times, int64_t n_points, int32_t activated, void *sigma,
+                  int32_t sigma_elem, void *rgb, int32_t rgb_elem, float *warped, nfa_stream_t stream);
+int nfa_ndr_density(int32_t elem, const nfa_mlp_desc *trunk, const void *warp_image, int64_t warp_image_elems, const void *trunk_image,
+                    const float *warp_bias, int64_t warp_bias_floats, const float *trunk_bias, const nfa_ngp_input *in, const float *times,
+                    int64_t n_points, int32_t activated, void *sigma, int32_t sigma_elem, float *warped, nfa_stream_t stream);
+int nfa_ndr_warp(int32_t elem, const void *warp_image, int64_t warp_image_elems, const float *warp_bias, int64_t warp_bias_floats,
+                 const nfa_ngp_input *in, const float *times, int64_t n_points, float *warped, nfa_stream_t stream);
+int nfa_ndr_time_features(int32_t elem, const void *time_image, const float *time_bias, const float *times, int64_t n_points, void *out,
+                          nfa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

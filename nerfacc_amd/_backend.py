@@ -299,6 +299,11 @@ _SIGS = {
                             _vp, _i64, _i32, C.POINTER(NerfSaved), C.POINTER(TNerfSaved), _vp, _i32, _vp, _i32, _vp],
     "nfa_tnerf_train_bwd": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPDesc), C.POINTER(MLPDesc), _vp, _vp, _vp, _i64, _i32, C.POINTER(NerfSaved),
                             C.POINTER(TNerfSaved), C.POINTER(NerfGrads), C.POINTER(TNerfGrads), _vp],
+    "nfa_ndr_field": [_i32, C.POINTER(MLPDesc), C.POINTER(MLPDesc), _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, C.POINTER(NGPInput), _vp, _i64, _i32,
+                      _vp, _i32, _vp, _i32, _vp, _vp],
+    "nfa_ndr_density": [_i32, C.POINTER(MLPDesc), _vp, _i64, _vp, _vp, _i64, _vp, C.POINTER(NGPInput), _vp, _i64, _i32, _vp, _i32, _vp, _vp],
+    "nfa_ndr_warp": [_i32, _vp, _i64, _vp, _i64, C.POINTER(NGPInput), _vp, _i64, _vp, _vp],
+    "nfa_ndr_time_features": [_i32, _vp, _vp, _vp, _i64, _vp, _vp],
     "nfa_cumsum_scratch_bytes": [_i64],
     "nfa_last_error": [],
     "nfa_version": [],

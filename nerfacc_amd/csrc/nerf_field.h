@@ -22,16 +22,33 @@ constexpr int NF_WARP_KQ0 = (NF_WARP_DIMS + 15) / 16;
 
 struct Piece { int32_t off16, n16; };   // of its image, in 16-byte fragments
 
-// mlp_stream.hip's ring over two images: pieces below n0 come from img0, the others from img1
-template <int MAXV>
-struct FieldRing {
+// mlp_stream.hip's ring over two images: pieces below n0 come from img0, the others from img1.  PRE (the NDR field): a third image
+// in front of them, the pieces below n_pre; the ring without it has no such members.
+template <bool PRE>
+struct RingPre {};
+template <>
+struct RingPre<true> {
+    const nfa_v4u *pre;
+    int n_pre;
+};
+
+template <int MAXV, bool PRE = false>
+struct FieldRing : RingPre<PRE> {
     const nfa_v4u *img0, *img1;
     nfa_v4u *slots;
     const Piece *tab;
     int slot16, n0, n_pieces, next, cur;
     nfa_v4u regs[MAXV];
 
-    __device__ __forceinline__ const nfa_v4u *source(int i) const { return (i < n0 ? img0 : img1) + tab[i].off16; }
+    __device__ __forceinline__ const nfa_v4u *source(int i) const
+    {
+        if constexpr (PRE) {   // a select of three values, not of three members' addresses: the ring stays in registers
+            const uintptr_t a = reinterpret_cast<uintptr_t>(img0), b = reinterpret_cast<uintptr_t>(img1), c = reinterpret_cast<uintptr_t>(this->pre);
+            const uintptr_t s = i < n0 ? a : b;
+            return reinterpret_cast<const nfa_v4u *>(i < this->n_pre ? c : s) + tab[i].off16;
+        }
+        return (i < n0 ? img0 : img1) + tab[i].off16;
+    }
     // thread 0 has written the table; stages piece 0
     __device__ __forceinline__ void start()
     {

@@ -78,7 +78,14 @@
 // head's input rows leave as TWO spans of 16 rows (16 (W + 27) halves are a multiple of 16 bytes): lanes r < 16 stage and the wave
 // flushes, then lanes r >= 16.  The staging halves (4 x 8.8 KiB at W = 256; 127.5 KiB in all), no arithmetic changes, and the
 // bottleneck fragments are held until the head's layer 0 anyway ("Fused T-NeRF field: training").
-#include "nerf_field.h"
+//
+// The NDR instantiations (WARP == 2) are the reference's NDRTNeRFRadianceField: the invertible warp of ndr_warp.h in front of the
+// same pass.  Its 54 pieces stand in front of the trunk's in the piece table and come from an image of their own (FieldRing's PRE),
+// so the head's last piece prefetches the warp's first; its biases and the four waves' cat tiles lie behind the head's biases.
+// Budget of the full query at W = 256: 81.75 KiB of LDS (ndr_warp.h), 256 + 174 registers, no scratch (density: 217 + 128; W = 128:
+// 204 + 64 and 149 + 64); nfa_ndr_warp, the stage alone (ndr_warp_kernel: the same ring over the warp's pieces only), 47.2 KiB,
+// 126 + 64 registers, no scratch (-Rpass-analysis=kernel-resource-usage).
+#include "ndr_warp.h"
 #include "samples.h"
 
 namespace nfa {
@@ -139,6 +146,7 @@ struct WarpArgs {
 struct TNerfArgs : NerfArgs { WarpArgs w; };
 // WARP with SAVE (nfa_tnerf_train_fwd): the warp's input rows [N, 36] and hidden activations [D_w, N, 64]; x' is w.warped
 struct TNerfTrainArgs : TNerfArgs { uint16_t *sv_win, *sv_wh; };
+struct NdrArgs : NerfArgs { NdrWarp n; };
 // what the warp stage of that instantiation stores, and the wave's staging tile
 struct WarpSave { uint16_t *in, *hidden, *st; int64_t N, p; };
 
@@ -359,10 +367,12 @@ __device__ __forceinline__ void put_out(void *out, bool out_f32, int64_t i, floa
 // A W = 128 WARP instantiation asks for the two waves per SIMD its plain twin has by itself (1: no request).
 // SAVE: nfa_nerf_train_fwd, the full query that also stores what the backward reads; the arithmetic is untouched.
 // WARP with SAVE: nfa_tnerf_train_fwd (header: T-NeRF training forward); one workgroup per CU by its LDS, so no request either.
-template <class E, int W, bool RAYS, bool FULL, bool WARP = false, bool SAVE = false>
-__global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP && !SAVE && W == 128 ? 2 : 1))) void nerf_field_kernel(
-    const std::conditional_t<WARP, std::conditional_t<SAVE, TNerfTrainArgs, TNerfArgs>, NerfArgs> a)
+// WARP == 2: the NDR field, ndr_warp.h's stage in front of every pass (never with SAVE).
+template <class E, int W, bool RAYS, bool FULL, int WARP = 0, bool SAVE = false>
+__global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP == 1 && !SAVE && W == 128 ? 2 : 1))) void nerf_field_kernel(
+    const std::conditional_t<WARP == 2, NdrArgs, std::conditional_t<WARP == 1, std::conditional_t<SAVE, TNerfTrainArgs, TNerfArgs>, NerfArgs>> a)
 {
+    static_assert(WARP != 2 || !SAVE, "the NDR field has no training forward");
     constexpr int MT = W / 32, KQ = W / 16, KQX = (NF_POS_DIMS + 15) / 16, KQD = (NF_DIR_DIMS + 15) / 16;
     constexpr int HW = NF_HEAD_W, HMT = HW / 32, HKQ = HW / 16;
     constexpr int MAXV = ((KQ + KQX) * 64 + NF_THREADS - 1) / NF_THREADS;   // the trunk's cat layer, the largest piece
@@ -385,19 +395,29 @@ __global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP
     nfa_v4u *wimg = reinterpret_cast<nfa_v4u *>(hb + n_hb);   // WARP: the resident image, 16-byte aligned (every part before it is)
     uint16_t *st = reinterpret_cast<uint16_t *>(hb + n_hb) + wave * (ST_BYTES / 2);   // SAVE: the wave's staging tile, there instead
     float *wb = nullptr;
-    if constexpr (WARP) {
+    if constexpr (WARP == 1) {
         wb = reinterpret_cast<float *>(wimg + a.w.img16);
         stage_warp(a.w, wimg, wb);   // ring.start()'s barriers publish it
         if constexpr (SAVE) st = reinterpret_cast<uint16_t *>(wb + a.w.S.lds_bias_floats()) + wave * (ST_BYTES / 2);   // behind both
     }
-    FieldRing<MAXV> ring;
-    if (threadIdx.x == 0) nerf_pieces(T, H, FULL, tab, nullptr, nullptr);
+    constexpr int N_PRE = WARP == 2 ? ND_PIECES : 0;
+    if constexpr (WARP == 2) {   // the warp's biases (padded by the packer), then the waves' cat tiles
+        wb = hb + n_hb;
+        for (int i = threadIdx.x; i < ND_BIAS_FLOATS; i += NF_THREADS) wb[i] = a.n.bias[i];
+        st = reinterpret_cast<uint16_t *>(wb + ND_BIAS_FLOATS) + wave * (ND_STAGE_BYTES / 2);
+    }
+    FieldRing<MAXV, WARP == 2> ring;
+    if (threadIdx.x == 0) {
+        if constexpr (WARP == 2) ndr_pieces(tab);
+        nerf_pieces(T, H, FULL, tab + N_PRE, nullptr, nullptr);
+    }
+    if constexpr (WARP == 2) ring.pre = reinterpret_cast<const nfa_v4u *>(a.n.img), ring.n_pre = N_PRE;
     ring.img0 = reinterpret_cast<const nfa_v4u *>(a.timg);
     ring.img1 = reinterpret_cast<const nfa_v4u *>(a.himg);
     ring.slots = reinterpret_cast<nfa_v4u *>(nf_lds);
     ring.tab = tab;
     ring.slot16 = a.slot16;
-    ring.n0 = D * MT + (FULL ? MT + 1 : 1);
+    ring.n0 = N_PRE + D * MT + (FULL ? MT + 1 : 1);
     ring.n_pieces = a.n_pieces;
     ring.start();
     const int64_t N = a.N, n_pass = ceil_div64(N, NF_POINTS);
@@ -405,7 +425,14 @@ __global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(WARP
         const int64_t p = (pass * NF_WAVES + wave) * 32 + r, pc = p < N ? p : N - 1;
         // ---- the point and both encoded rows, before layer 0's first fetch
         float x[3], dir[3] = {0.f, 0.f, 0.f}, t = 0.f;
-        if constexpr (WARP) {
+        if constexpr (WARP == 2) {
+            load_point<RAYS, FULL>(a, a.n.times, pc, x, dir, t);
+            ndr_stage<E>(ring, wb, st, x, t, lane);
+            if (a.n.warped && h == 0 && p < N) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) a.n.warped[3 * p + k] = x[k];
+            }
+        } else if constexpr (WARP == 1) {
             load_point<RAYS, FULL>(a, a.w.times, pc, x, dir, t);
             if constexpr (SAVE) {
                 const WarpSave sv = {a.sv_win, a.sv_wh, st, N, p};
@@ -591,6 +618,65 @@ __global__ __launch_bounds__(NF_THREADS) void tnerf_warp_kernel(const TNerfArgs 
     }
 }
 
+// The NDR warp alone (nfa_ndr_warp): the query's pass loop with the warp's pieces as the whole table.
+__host__ __device__ inline int64_t ndr_warp_lds_bytes()
+{
+    return (int64_t)NF_SLOTS * ND_MAX_PIECE16 * 16 + (int64_t)ND_PIECES * sizeof(Piece) + ND_BIAS_FLOATS * 4 + NF_WAVES * ND_STAGE_BYTES;
+}
+
+template <class E, bool RAYS>
+__global__ __launch_bounds__(NF_THREADS) void ndr_warp_kernel(const NdrArgs a)
+{
+    constexpr int MAXV = (ND_MAX_PIECE16 + NF_THREADS - 1) / NF_THREADS;
+    extern __shared__ __attribute__((aligned(16))) unsigned char nf_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    Piece *tab = reinterpret_cast<Piece *>(nf_lds + (int64_t)NF_SLOTS * ND_MAX_PIECE16 * 16);
+    float *wb = reinterpret_cast<float *>(tab + ND_PIECES);
+    uint16_t *st = reinterpret_cast<uint16_t *>(wb + ND_BIAS_FLOATS) + wave * (ND_STAGE_BYTES / 2);
+    for (int i = threadIdx.x; i < ND_BIAS_FLOATS; i += NF_THREADS) wb[i] = a.n.bias[i];
+    if (threadIdx.x == 0) ndr_pieces(tab);
+    FieldRing<MAXV> ring;
+    ring.img0 = ring.img1 = reinterpret_cast<const nfa_v4u *>(a.n.img);
+    ring.slots = reinterpret_cast<nfa_v4u *>(nf_lds);
+    ring.tab = tab;
+    ring.slot16 = ND_MAX_PIECE16;
+    ring.n0 = ring.n_pieces = ND_PIECES;
+    ring.start();
+    const int64_t N = a.N, n_pass = ceil_div64(N, NF_POINTS);
+    for (int64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
+        const int64_t p = (pass * NF_WAVES + wave) * 32 + r, pc = p < N ? p : N - 1;
+        float x[3], dir[3], t = 0.f;
+        load_point<RAYS, false>(a, a.n.times, pc, x, dir, t);
+        ndr_stage<E>(ring, wb, st, x, t, lane);
+        if (h == 0 && p < N) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a.n.warped[3 * p + k] = x[k];
+        }
+    }
+}
+
+// The six time layers of the NDR warp on t [n]: out [n, 6, 64], feature row 2 i + s is time_layers_{s+1}[i].  A wave per 32
+// points, the twelve row tiles straight from the image (12 KiB, cached): time_tile is what the fused stage calls.
+template <class E>
+__global__ __launch_bounds__(NF_THREADS) void ndr_time_features_kernel(const nfa_v4u *__restrict__ img, const float *__restrict__ bias,
+                                                                       const float *__restrict__ times, int64_t N, uint16_t *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int64_t n_tiles = ceil_div64(N, 32);
+    for (int64_t tile = (int64_t)blockIdx.x * NF_WAVES + wave; tile < n_tiles; tile += (int64_t)gridDim.x * NF_WAVES) {
+        const int64_t p = tile * 32 + r, pc = p < N ? p : N - 1;
+        const nfa_v4u te = time_frag<E>(times[pc], lane, h);
+#pragma unroll 1
+        for (int j = 0; j < 2 * ND_BLOCKS; ++j) {
+#pragma unroll
+            for (int m = 0; m < ND_TMT; ++m) {
+                const f32x16 acc = time_tile<E>(img + (j * ND_TMT + m) * 64, bias + j * ND_TW + 32 * m, te, lane, h);
+                if (p < N) store_tile_row<ND_TW>(out, p * (2 * ND_BLOCKS) + j, m, h, acc_frag<E>(acc, 0), acc_frag<E>(acc, 1));
+            }
+        }
+    }
+}
+
 // The head's forward image: mlp_pack_kernel's image of (tw + 27 -> Dc x 128 -> 3), except that layer 0 is a cat layer whose H
 // part is the trunk's tw bottleneck columns in the permuted k order and whose x part, the 27 direction columns, starts on a
 // k-step of its own in natural order.  tw is a multiple of 16, so the sizes are those of the plain shape.
@@ -642,12 +728,15 @@ WarpArgs warp_args(const Shape &S, const void *image, const float *bias, const f
     return w;
 }
 
+int check_ndr_pointers(const char *who, const NdrWarp &n);
+
 int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *trunk_image,
                const void *head_image, const float *trunk_bias, const float *head_bias, const nfa_ngp_input *in, int64_t N,
                int32_t activated, void *sigma, int32_t sigma_elem, void *rgb, int32_t rgb_elem, nfa_stream_t stream,
                const WarpArgs *warp = nullptr,   // the T-NeRF entries: S checked, the pointers as the caller gave them
                bool train = false, const nfa_nerf_saved *save = nullptr,   // nfa_nerf_train_fwd
-               const nfa_tnerf_saved *wsave = nullptr)                      // nfa_tnerf_train_fwd, next to warp and save
+               const nfa_tnerf_saved *wsave = nullptr,                     // nfa_tnerf_train_fwd, next to warp and save
+               const NdrWarp *ndr = nullptr)                                // the NDR entries: checked by check_ndr_warp
 {
     Shape T, H = {};
     if (int rc = check_field_shape(who, elem, trunk, head, 0, N, &T, full ? &H : nullptr)) return rc;
@@ -670,6 +759,8 @@ int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *tru
                 "%s: misaligned pointer (images 16, ray_indices 8, the others their element)", who);
     if (warp)
         if (int rc = check_warp_pointers(who, *warp)) return rc;
+    if (ndr)
+        if (int rc = check_ndr_pointers(who, *ndr)) return rc;
     NerfArgs a = {};
     if (train) {
         NFA_REQUIRE(save->enc_x && save->trunk_hidden && save->head_in && save->head_hidden,
@@ -685,8 +776,9 @@ int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *tru
     a.timg = static_cast<const uint16_t *>(trunk_image), a.himg = static_cast<const uint16_t *>(head_image);
     a.tbias = trunk_bias, a.hbias = head_bias;
     int slot16 = 0;
-    a.n_pieces = nerf_pieces(T, H, full, nullptr, &slot16, nullptr);
-    a.slot16 = slot16;
+    a.n_pieces = nerf_pieces(T, H, full, nullptr, &slot16, nullptr) + (ndr ? ND_PIECES : 0);
+    a.slot16 = ndr && slot16 < ND_MAX_PIECE16 ? ND_MAX_PIECE16 : slot16;
+    slot16 = a.slot16;
     a.x = in->positions, a.dirs = in->dirs;
     a.o = in->rays_o, a.d = in->rays_d, a.ts = in->t_starts, a.te = in->t_ends, a.ri = in->ray_indices;
     a.n_rays = in->n_rays, a.N = N;
@@ -694,7 +786,8 @@ int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *tru
     a.rgb = full ? rgb : nullptr, a.rgb_f32 = rgb_elem == NFA_ELEM_F32;
     a.activated = activated;
     const int64_t lds = nerf_lds_bytes(slot16, trunk_bias_floats(T) + (full ? head_bias_floats(H) : 0)) + (warp ? warp_lds_bytes(warp->S) : 0) +
-                        (train ? (int64_t)NF_WAVES * (warp ? 16 * (T.W + NF_DIR_DIMS) * 2 : row_stage_bytes(T.W + NF_DIR_DIMS)) : 0);
+                        (train ? (int64_t)NF_WAVES * (warp ? 16 * (T.W + NF_DIR_DIMS) * 2 : row_stage_bytes(T.W + NF_DIR_DIMS)) : 0) +
+                        (ndr ? (int64_t)ND_BIAS_FLOATS * 4 + NF_WAVES * ND_STAGE_BYTES : 0);
     const int64_t want = ceil_div64(N, NF_POINTS);
     const unsigned grid = (unsigned)(want < NFA_MLP_STREAM_GROUPS ? want : NFA_MLP_STREAM_GROUPS);
     int rc = NFA_OK;
@@ -728,9 +821,20 @@ int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *tru
             kern<<<grid, NF_THREADS, (size_t)lds, as_stream(stream)>>>(a);
         }
     };
+    auto launch_ndr = [&](auto tag, auto w, auto rays_c, auto full_c) {
+        auto kern = nerf_field_kernel<typename decltype(tag)::type, decltype(w)::value, decltype(rays_c)::value, decltype(full_c)::value, 2>;
+        if ((rc = allow_lds(who, kern, lds)) != NFA_OK) return;
+        NdrArgs na = {};
+        static_cast<NerfArgs &>(na) = a;
+        na.n = *ndr;
+        kern<<<grid, NF_THREADS, (size_t)lds, as_stream(stream)>>>(na);
+    };
     auto by_form = [&](auto tag, auto w) {
         dispatch_bool(rays, [&](auto rays_c) {
-            dispatch_bool(full, [&](auto full_c) { dispatch_bool(warp != nullptr, [&](auto warp_c) { launch(tag, w, rays_c, full_c, warp_c); }); });
+            dispatch_bool(full, [&](auto full_c) {
+                if (ndr) launch_ndr(tag, w, rays_c, full_c);
+                else dispatch_bool(warp != nullptr, [&](auto warp_c) { launch(tag, w, rays_c, full_c, warp_c); });
+            });
         });
     };
     auto by_width = [&](auto tag) {
@@ -741,6 +845,26 @@ int nerf_query(const char *who, bool full, int32_t elem, const nfa_mlp_desc *tru
     else by_width(ElemTag<nfa_bf16>{});
     if (rc != NFA_OK) return rc;
     NFA_CHECK_LAUNCH(who);
+    return NFA_OK;
+}
+
+// The one statement of what the NDR entries take as the warp: checked after elem and before the trunk and the head.
+int check_ndr_warp(const char *who, int32_t elem, const void *image, int64_t image_elems, const float *bias, int64_t bias_floats,
+                   const float *times, float *warped, NdrWarp *n)
+{
+    NFA_REQUIRE(elem == NFA_ELEM_F16 || elem == NFA_ELEM_BF16, "%s: elem %d: the networks' type is NFA_ELEM_F16 or NFA_ELEM_BF16", who, elem);
+    NFA_REQUIRE(image_elems == ND_IMAGE_ELEMS, "%s: the warp image holds %lld elements, got %lld", who, (long long)ND_IMAGE_ELEMS, (long long)image_elems);
+    NFA_REQUIRE(bias_floats == ND_BIAS_FLOATS, "%s: the warp's bias block holds %d floats, got %lld", who, ND_BIAS_FLOATS, (long long)bias_floats);
+    *n = NdrWarp{static_cast<const uint16_t *>(image), bias, times, warped};
+    return NFA_OK;
+}
+
+// its pointers, checked with the other pointers: behind the return for n_points == 0, as in every other entry
+int check_ndr_pointers(const char *who, const NdrWarp &n)
+{
+    NFA_REQUIRE(n.img && n.bias && n.times, "%s: null pointer (warp image, warp bias or times)", who);
+    NFA_REQUIRE(aligned_to(n.img, 16) && aligned_to(n.bias, 4) && aligned_to(n.times, 4) && aligned_to(n.warped, 4),
+                "%s: misaligned pointer (warp image 16, warp bias, times and warped 4)", who);
     return NFA_OK;
 }
 
@@ -861,6 +985,83 @@ int nfa_tnerf_warp(int32_t elem, const nfa_mlp_desc *warp, const void *warp_imag
             tnerf_warp_kernel<E, decltype(rays_c)::value><<<grid, NF_THREADS, (size_t)lds, as_stream(stream)>>>(a);
         });
     });
+    NFA_CHECK_LAUNCH(who);
+    return NFA_OK;
+}
+
+int nfa_ndr_field(int32_t elem, const nfa_mlp_desc *trunk, const nfa_mlp_desc *head, const void *warp_image, int64_t warp_image_elems,
+                  const void *trunk_image, const void *head_image, const float *warp_bias, int64_t warp_bias_floats, const float *trunk_bias,
+                  const float *head_bias, const nfa_ngp_input *in, const float *times, int64_t n_points, int32_t activated, void *sigma,
+                  int32_t sigma_elem, void *rgb, int32_t rgb_elem, float *warped, nfa_stream_t stream)
+{
+    const char *who = "nfa_ndr_field";
+    NdrWarp n;
+    if (int rc = check_ndr_warp(who, elem, warp_image, warp_image_elems, warp_bias, warp_bias_floats, times, warped, &n)) return rc;
+    return nerf_query(who, true, elem, trunk, head, trunk_image, head_image, trunk_bias, head_bias, in, n_points, activated, sigma, sigma_elem,
+                      rgb, rgb_elem, stream, nullptr, false, nullptr, nullptr, &n);
+}
+
+int nfa_ndr_density(int32_t elem, const nfa_mlp_desc *trunk, const void *warp_image, int64_t warp_image_elems, const void *trunk_image,
+                    const float *warp_bias, int64_t warp_bias_floats, const float *trunk_bias, const nfa_ngp_input *in, const float *times,
+                    int64_t n_points, int32_t activated, void *sigma, int32_t sigma_elem, float *warped, nfa_stream_t stream)
+{
+    const char *who = "nfa_ndr_density";
+    NdrWarp n;
+    if (int rc = check_ndr_warp(who, elem, warp_image, warp_image_elems, warp_bias, warp_bias_floats, times, warped, &n)) return rc;
+    return nerf_query(who, false, elem, trunk, nullptr, trunk_image, nullptr, trunk_bias, nullptr, in, n_points, activated, sigma, sigma_elem,
+                      nullptr, NFA_ELEM_F32, stream, nullptr, false, nullptr, nullptr, &n);
+}
+
+int nfa_ndr_warp(int32_t elem, const void *warp_image, int64_t warp_image_elems, const float *warp_bias, int64_t warp_bias_floats,
+                 const nfa_ngp_input *in, const float *times, int64_t n_points, float *warped, nfa_stream_t stream)
+{
+    const char *who = "nfa_ndr_warp";
+    NdrArgs a = {};
+    if (int rc = check_ndr_warp(who, elem, warp_image, warp_image_elems, warp_bias, warp_bias_floats, times, warped, &a.n)) return rc;
+    NFA_REQUIRE(n_points >= 0, "%s: n_points %lld is negative", who, (long long)n_points);
+    NFA_REQUIRE(in, "%s: the input descriptor is null", who);
+    if (n_points == 0) return NFA_OK;
+    const bool rays = in->positions == nullptr;
+    NFA_REQUIRE(!rays || (in->n_rays >= 1 && in->n_rays < ((int64_t)1 << 31) - 64), "%s: n_rays %lld out of range", who, (long long)in->n_rays);
+    NFA_REQUIRE(!rays || (in->rays_o && in->rays_d && in->t_starts && in->t_ends && in->ray_indices),
+                "%s: null input pointer (positions, or rays_o, rays_d, t_starts, t_ends and ray_indices)", who);
+    NFA_REQUIRE(warped, "%s: no output requested", who);
+    NFA_REQUIRE(aligned_to(in->positions, 4) && aligned_to(in->rays_o, 4) && aligned_to(in->rays_d, 4) && aligned_to(in->t_starts, 4) &&
+                aligned_to(in->t_ends, 4) && aligned_to(in->ray_indices, 8), "%s: misaligned pointer (ray_indices 8, the others their element)", who);
+    if (int rc = check_ndr_pointers(who, a.n)) return rc;
+    a.x = in->positions;
+    a.o = in->rays_o, a.d = in->rays_d, a.ts = in->t_starts, a.te = in->t_ends, a.ri = in->ray_indices;
+    a.n_rays = in->n_rays, a.N = n_points;
+    const int64_t lds = ndr_warp_lds_bytes(), want = ceil_div64(n_points, NF_POINTS);
+    const unsigned grid = (unsigned)(want < 2 * NFA_MLP_STREAM_GROUPS ? want : 2 * NFA_MLP_STREAM_GROUPS);   // 48 KiB: two workgroups a CU and more
+    dispatch_bool(elem == NFA_ELEM_F16, [&](auto f16) {
+        using E = std::conditional_t<decltype(f16)::value, nfa_f16, nfa_bf16>;
+        dispatch_bool(rays, [&](auto rays_c) {
+            ndr_warp_kernel<E, decltype(rays_c)::value><<<grid, NF_THREADS, (size_t)lds, as_stream(stream)>>>(a);
+        });
+    });
+    NFA_CHECK_LAUNCH(who);
+    return NFA_OK;
+}
+
+int nfa_ndr_time_features(int32_t elem, const void *time_image, const float *time_bias, const float *times, int64_t n_points, void *out,
+                          nfa_stream_t stream)
+{
+    const char *who = "nfa_ndr_time_features";
+    NFA_REQUIRE(elem == NFA_ELEM_F16 || elem == NFA_ELEM_BF16, "%s: elem %d: the networks' type is NFA_ELEM_F16 or NFA_ELEM_BF16", who, elem);
+    NFA_REQUIRE(n_points >= 0, "%s: n_points %lld is negative", who, (long long)n_points);
+    if (n_points == 0) return NFA_OK;
+    NFA_REQUIRE(time_image && time_bias && times && out, "%s: null pointer", who);
+    NFA_REQUIRE(aligned_to(time_image, 16) && aligned_to(time_bias, 16) && aligned_to(times, 4) && aligned_to(out, 16),
+                "%s: misaligned pointer (image, bias and out 16, times 4)", who);
+    const int64_t want = ceil_div64(n_points, NF_POINTS);
+    const unsigned grid = (unsigned)(want < 8 * NFA_MLP_STREAM_GROUPS ? want : 8 * NFA_MLP_STREAM_GROUPS);
+    if (elem == NFA_ELEM_F16)
+        ndr_time_features_kernel<nfa_f16><<<grid, NF_THREADS, 0, as_stream(stream)>>>(static_cast<const nfa_v4u *>(time_image), time_bias, times, n_points,
+                                                                                      static_cast<uint16_t *>(out));
+    else
+        ndr_time_features_kernel<nfa_bf16><<<grid, NF_THREADS, 0, as_stream(stream)>>>(static_cast<const nfa_v4u *>(time_image), time_bias, times, n_points,
+                                                                                       static_cast<uint16_t *>(out));
     NFA_CHECK_LAUNCH(who);
     return NFA_OK;
 }

@@ -30,10 +30,11 @@ The reference's vanilla NeRF field (ref: examples/radiance_fields/mlp.py: ``Vani
 :class:`VanillaNeRFRadianceField` at the end of this module: two :class:`~nerfacc_amd.encodings.SinusoidalEncoding` and a
 :class:`~nerfacc_amd.mlp.NerfMLP`, with the no-grad query as one launch of csrc/nerf_field.hip.  Its dynamic-scene field
 (``TNeRFRadianceField``) is :class:`TNeRFRadianceField` behind it: a warp network in front of the vanilla field, the no-grad query
-one launch of the same kernel with a warp stage.
+one launch of the same kernel with a warp stage.  ``NDRTNeRFRadianceField``, the dynamic-scene field with NDR's invertible warp,
+is :class:`NDRTNeRFRadianceField` at the end: three coupling blocks whose weights stream through the trunk's LDS ring.
 
 Not part of ``nerfacc_amd.__all__``: ``from nerfacc_amd.fields import NGPRadianceField, NGPDensityField,
-VanillaNeRFRadianceField, TNeRFRadianceField``.
+VanillaNeRFRadianceField, TNeRFRadianceField, NDRTNeRFRadianceField``.
 """
 from __future__ import annotations
 
@@ -1065,3 +1066,342 @@ class TNeRFRadianceField(nn.Module):
         nerf_sd = {k[len("nerf."):]: v for k, v in sd.items() if k.startswith("nerf.")}
         self.warp.load_reference_state_dict(warp_sd)
         self.nerf.load_reference_state_dict(nerf_sd)
+
+
+# ---------------------------------------------------------------- the NDR T-NeRF field (csrc/ndr_warp.h, nerf_field.hip WARP == 2)
+
+NDR_BLOCKS, NDR_TIME_DIMS, NDR_TIME_WIDTH = 3, 9, 64
+NDR_NET1, NDR_NET2 = (82, 1, 128, 2, 1, 0), (73, 3, 128, 1, 1, 0)   # struct nfa_mlp_desc of warp_layers_1[i] and warp_layers_2[i]
+NDR_IMAGE_ELEMS, NDR_BIAS_FLOATS = 3 * 49152, 3 * 576             # include/nerfacc_hip.h: nfa_ndr_field's warp_image and warp_bias
+
+
+def ndr_field_limits_error(nets1: List[tuple], nets2: List[tuple], times: List[tuple], trunk: Optional[tuple],
+                           head: Optional[tuple]) -> Optional[str]:
+    """None for a field the fused NDR query holds: exactly the reference's warp (three blocks; ``nets1`` / ``nets2`` the
+    descriptors of ``warp_layers_1`` / ``warp_layers_2``, ``times`` the shapes of the twelve time-layer tensors) in front of
+    what :func:`nerf_field_limits_error` accepts."""
+    if len(nets1) != NDR_BLOCKS or len(nets2) != NDR_BLOCKS:
+        return f"{len(nets1)} and {len(nets2)} warp networks: {NDR_BLOCKS} coupling blocks are supported"
+    for name, descs, want in (("warp_layers_1", nets1, NDR_NET1), ("warp_layers_2", nets2, NDR_NET2)):
+        for i, d in enumerate(descs):
+            if tuple(d) != want:
+                return f"{name}[{i}] {tuple(d)}: (n_in, n_out, width, n_hidden, bias, skip_mask) = {want} is supported"
+    want_t = [(NDR_TIME_WIDTH, NDR_TIME_DIMS), (NDR_TIME_WIDTH,)] * (2 * NDR_BLOCKS)
+    if [tuple(s) for s in times] != want_t:
+        return f"time layers {[tuple(s) for s in times]}: {2 * NDR_BLOCKS} layers of {NDR_TIME_DIMS} -> {NDR_TIME_WIDTH} with biases are supported"
+    return nerf_field_limits_error(trunk, head)
+
+
+class _NdrTimeFn(torch.autograd.Function):
+    """The six time layers on ``t [n]`` as one native pass (``nfa_ndr_time_features``): ``[n, 6, 64]`` of the networks' type, the
+    bits the fused launch forms in registers.  Backward towards the six matrices and biases: torch matmuls of the gradient
+    ``[n, 64]`` against the encoded time ``[n, 9]``.  No gradient towards ``t``."""
+
+    @staticmethod
+    def forward(ctx, t: Tensor, t_enc: Tensor, field: "NDRTNeRFRadianceField", *wb: Tensor):
+        if t.requires_grad:
+            raise NotImplementedError("NDRTNeRFRadianceField: no gradient towards the times is implemented")
+        n, dev = t.numel(), t.device
+        out = torch.empty(n, 2 * NDR_BLOCKS, NDR_TIME_WIDTH, dtype=field.dtype, device=dev)
+        if n:
+            img, bias = field._time_image()
+            with torch.cuda.device(dev):
+                B.call("nfa_ndr_time_features", B.ELEM_CODES[field.dtype], B.ptr(img), B.ptr(bias), B.ptr(t), n, B.ptr(out), B.stream())
+        ctx.save_for_backward(t_enc)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (t_enc,) = ctx.saved_tensors
+        G = g.float().reshape(g.shape[0], -1)                                  # [n, 6 * 64]
+        dW = (G.t() @ t_enc.float()).view(2 * NDR_BLOCKS, NDR_TIME_WIDTH, NDR_TIME_DIMS)
+        db = G.sum(0).view(2 * NDR_BLOCKS, NDR_TIME_WIDTH)
+        grads = [v for j in range(2 * NDR_BLOCKS) for v in (dW[j], db[j])]
+        return (None, None, None, *[v if need else None for v, need in zip(grads, ctx.needs_input_grad[3:])])
+
+
+class NDRTNeRFRadianceField(nn.Module):
+    """The reference's dynamic-scene field with the invertible warp of Neural Deformable Radiance fields (ref:
+    examples/radiance_fields/mlp.py: ``NDRTNeRFRadianceField``; arXiv 2206.15258).  ``time_encoder``, ``posi_encoder_1`` and
+    ``posi_encoder_2`` are :class:`SinusoidalEncoding` (1, 0, 4), (2, 0, 4) and (1, 0, 4) with identity, ``out_dtype=dtype``;
+    ``warp_layers_1[i]`` is :func:`reference_mlp` (82, 1, 2, 128) and ``warp_layers_2[i]`` (73, 3, 1, 128), float32 outputs, output
+    layers initialised ``uniform_(0, 1e-4)`` with zero bias; ``time_layers_1[i]`` and ``time_layers_2[i]`` hold the reference's
+    ``DenseLayer(9, 64)`` as float32 ``weight [64, 9]`` and ``bias [64]``; ``nerf`` is :class:`VanillaNeRFRadianceField`.  Three
+    coupling blocks move ``x = (u, v, w)``::
+
+        dw = warp_layers_1[i](cat[posi_encoder_1(u, v), time_layers_1[i](time_encoder(t))]);   w = w + dw
+        theta, tu, tv = warp_layers_2[i](cat[posi_encoder_2(w), time_layers_2[i](time_encoder(t))])
+        u, v = cos(theta) (u - tu) + sin(theta) (v - tv),  cos(theta) (v - tv) - sin(theta) (u - tu)
+
+    with the axes rolled ``[1, 2, 0]`` behind block 0 and ``[2, 0, 1]`` behind block 1, and ``nerf`` is queried at the result.
+    ``dw``, ``theta``, the translation, the sums and the rotation are float32 and never rounded to the half type; a time layer
+    rounds once to ``dtype``; ``sin`` and ``cos`` of ``theta`` are a float32 :class:`SinusoidalEncoding` (1, 0, 1).
+
+    With grad enabled and something that requires it, on CPU tensors, with ``fused=False`` and for a shape outside
+    :meth:`fused_supported` a query runs the native passes in their order (the *composed chain*), which trains every parameter;
+    the six time layers are one native pass there (``nfa_ndr_time_features``).  Under ``torch.no_grad()``, or when nothing
+    requires grad, a supported field takes ONE launch (``nfa_ndr_field``, ``nfa_ndr_density``, ``nfa_ndr_warp``): the warp's
+    288 KiB of weights stream through the trunk's LDS ring in front of the trunk's own, and nothing between ``(x, t, dir)``, or a
+    ray sample and its ray's timestamp, and the outputs exists in memory.  The warped positions and sigma are the composed
+    chain's bits; the raw colour carries the vanilla field's one last-bit difference.
+
+    ``fused`` is a bool or ``{"density": bool, "full": bool}`` (:meth:`warp` follows ``"density"``), handed to ``nerf`` as well;
+    DESIGN.md, "Fused NDR field", has the measurements.  There is no fused training pass, no gradient towards ``x``, ``t`` or
+    the rays through the fused launch, and no inverse warp."""
+
+    def __init__(self, dtype: torch.dtype = torch.float16, generator: Optional[torch.Generator] = None, fused: Union[bool, dict] = True):
+        super().__init__()
+        self.time_encoder = SinusoidalEncoding(1, 0, 4, True, out_dtype=dtype)
+        self.posi_encoder_1 = SinusoidalEncoding(2, 0, 4, True, out_dtype=dtype)
+        self.posi_encoder_2 = SinusoidalEncoding(1, 0, 4, True, out_dtype=dtype)
+        self._rot_encoder = SinusoidalEncoding(1, 0, 1, False)   # (sin theta, cos theta) in float32
+        gen = generator or torch.Generator().manual_seed(1337)
+        self.warp_layers_1, self.warp_layers_2 = nn.ModuleList(), nn.ModuleList()
+        self.time_layers_1, self.time_layers_2 = nn.ModuleList(), nn.ModuleList()
+        for _ in range(NDR_BLOCKS):
+            for nets, (n_in, n_out, width, depth, _, _) in ((self.warp_layers_1, NDR_NET1), (self.warp_layers_2, NDR_NET2)):
+                net = reference_mlp(n_in, n_out, depth, width, None, dtype=dtype, out_dtype=torch.float32, generator=generator)
+                with torch.no_grad():   # output_init=functools.partial(torch.nn.init.uniform_, b=1e-4); the bias is zero already
+                    out = net.weight(depth)
+                    out.copy_(torch.rand(out.shape, generator=gen) * 1e-4)
+                nets.append(net)
+            for layers in (self.time_layers_1, self.time_layers_2):
+                lin = nn.Linear(NDR_TIME_DIMS, NDR_TIME_WIDTH)   # a holder of weight and bias in nn.Linear layout; never called
+                with torch.no_grad():                            # DenseLayer: xavier_uniform_, zero bias
+                    bound = math.sqrt(6.0 / (NDR_TIME_DIMS + NDR_TIME_WIDTH))
+                    lin.weight.copy_((torch.rand(lin.weight.shape, generator=gen) * 2 - 1) * bound)
+                    lin.bias.zero_()
+                layers.append(lin)
+        self.nerf = VanillaNeRFRadianceField(dtype=dtype, generator=generator, fused=fused)
+        self.dtype = dtype
+        self.fused = dict(self.nerf.fused)
+        self._time_packed = None   # (key, image, bias)
+        self._warp_packed = None   # (key, image, bias)
+
+    # ---------------------------------------------------------------- the packed warp
+
+    def _time_tensors(self) -> List[Tensor]:
+        return [v for i in range(len(self.time_layers_1)) for lin in (self.time_layers_1[i], self.time_layers_2[i]) for v in (lin.weight, lin.bias)]
+
+    @staticmethod
+    def _key(ts: List[Tensor]):
+        return tuple((t.data_ptr(), t._version, t.device) for t in ts)
+
+    def _time_image(self):
+        """``(image [6, 1024] of dtype, bias [6, 64] float32)`` of the six time layers in ``nfa_ndr_time_features``' layout, rebuilt
+        when a master changes."""
+        ts = self._time_tensors()
+        key = self._key(ts)
+        if self._time_packed is None or self._time_packed[0] != key:
+            with torch.no_grad():
+                w = torch.stack([v.detach() for v in ts[0::2]])                               # [6, 64, 9]
+                w = torch.nn.functional.pad(w, (0, 16 - NDR_TIME_DIMS)).to(self.dtype)       # [6, 64, 16]: (m, r) rows, (h, j) columns
+                img = w.view(-1, 2, 32, 2, 8).permute(0, 1, 3, 2, 4).reshape(-1, 1024).contiguous()
+                bias = torch.stack([v.detach().float() for v in ts[1::2]]).contiguous()
+            self._time_packed = (key, img, bias)
+        return self._time_packed[1], self._time_packed[2]
+
+    def _warp_image(self):
+        """``(image, bias)`` of the whole warp as ``nfa_ndr_field`` takes them: the nets' :class:`FusedMLP` forward images and
+        the time layers' in one buffer, one float32 bias block (the way ``_head_image()`` is kept)."""
+        nets = [n for i in range(NDR_BLOCKS) for n in (self.warp_layers_1[i], self.warp_layers_2[i])]
+        key = self._key([n.params for n in nets] + self._time_tensors())
+        if self._warp_packed is None or self._warp_packed[0] != key:
+            with torch.no_grad():
+                timg, tbias = self._time_image()
+                parts, biases = [], []
+                for j, net in enumerate(nets):
+                    p = net.params
+                    parts += [timg[j], net._images(p)[0]]
+                    biases.append(tbias[j])
+                    for b in net._bias_views(p.detach()):
+                        biases.append(torch.nn.functional.pad(b.float(), (0, -b.numel() % 32)))
+                img, bias = torch.cat(parts).contiguous(), torch.cat(biases).contiguous()
+            assert img.numel() == NDR_IMAGE_ELEMS and bias.numel() == NDR_BIAS_FLOATS
+            self._warp_packed = (key, img, bias)
+        return self._warp_packed[1], self._warp_packed[2]
+
+    # ---------------------------------------------------------------- the fused launch
+
+    def fused_supported(self, full: bool = True) -> bool:
+        """Exactly the reference's warp (three blocks of (82, 1, 2 x 128) and (73, 3, 1 x 128) networks with biases and without a
+        skip, twelve ``[64, 9]`` / ``[64]`` time-layer tensors) in front of what :meth:`VanillaNeRFRadianceField.fused_supported`
+        lists."""
+        desc = lambda nets: [(*n._shape, int(n.bias_enabled), n.skip_mask) for n in nets]
+        trunk, head = self.nerf._descs()
+        return ndr_field_limits_error(desc(self.warp_layers_1), desc(self.warp_layers_2), [t.shape for t in self._time_tensors()],
+                                      trunk, head if full else None) is None
+
+    def _use_fused(self, full: bool, *tensors: Optional[Tensor]) -> bool:
+        if not (self.fused["full" if full else "density"] and self.fused_supported(full)):
+            return False
+        ts = [t for t in tensors if t is not None]
+        dev = self.warp_layers_1[0].params.device
+        if not (all(t.is_cuda and t.device == dev for t in ts) and all(t.dtype == torch.float32 for t in ts if t.is_floating_point())):
+            return False
+        return not (torch.is_grad_enabled() and any(t.requires_grad for t in [*self.parameters(), *ts]))
+
+    def _launch(self, kind: str, n: int, activated: bool = False, positions=None, times=None, dirs=None, rays=None, warped: bool = False,
+                rgb_dtype=None, sigma_dtype=None):
+        """One fused launch.  ``kind``: ``"full"``: ``(rgb [n, 3], sigma [n], warped [n, 3] or None)``; ``"density"``:
+        ``(None, sigma, warped or None)``; ``"warp"``: ``(None, None, warped)``.  ``times``: [n] with ``positions``, [n_rays]
+        with ``rays``."""
+        full = kind == "full"
+        t, h = self.nerf.mlp.trunk, self.nerf.mlp.head
+        dev = t.params.device
+        sigma = torch.empty(n, dtype=sigma_dtype or self.dtype, device=dev) if kind != "warp" else None
+        rgb = torch.empty(n, 3, dtype=rgb_dtype or self.dtype, device=dev) if full else None
+        xw = torch.empty(n, 3, dtype=torch.float32, device=dev) if warped or kind == "warp" else None
+        if n == 0:
+            return rgb, sigma, xw
+        keep = [x.contiguous() for x in (rays[:5] if rays is not None else (positions, dirs)) if x is not None]
+        times = times.contiguous()
+        if rays is not None:
+            keep[4] = keep[4] if keep[4].dtype == torch.int64 else keep[4].to(torch.int64)
+            inp = B.NGPInput(None, None, *[B.ptr(x) for x in keep], keep[0].shape[0])
+        else:
+            inp = B.NGPInput(B.ptr(keep[0]), B.ptr(keep[1]) if full else None, None, None, None, None, None, 0)
+        elem = B.ELEM_CODES[self.dtype]
+        with torch.cuda.device(dev):
+            wimg, wbias = self._warp_image()
+            if kind == "warp":
+                B.call("nfa_ndr_warp", elem, B.ptr(wimg), wimg.numel(), B.ptr(wbias), wbias.numel(), ctypes.byref(inp), B.ptr(times), n,
+                       B.ptr(xw), B.stream())
+                return rgb, sigma, xw
+            tp = t.params
+            timg = t._images(tp)[0]
+            if full:
+                B.call("nfa_ndr_field", elem, t._desc, h._desc, B.ptr(wimg), wimg.numel(), B.ptr(timg), B.ptr(self.nerf._head_image()),
+                       B.ptr(wbias), wbias.numel(), t._bias_ptr(tp), h._bias_ptr(h.params), ctypes.byref(inp), B.ptr(times), n, int(activated),
+                       B.ptr(sigma), B.ELEM_CODES[sigma.dtype], B.ptr(rgb), B.ELEM_CODES[rgb.dtype], B.ptr(xw) if xw is not None else None,
+                       B.stream())
+            else:
+                B.call("nfa_ndr_density", elem, t._desc, B.ptr(wimg), wimg.numel(), B.ptr(timg), B.ptr(wbias), wbias.numel(), t._bias_ptr(tp),
+                       ctypes.byref(inp), B.ptr(times), n, int(activated), B.ptr(sigma), B.ELEM_CODES[sigma.dtype],
+                       B.ptr(xw) if xw is not None else None, B.stream())
+        return rgb, sigma, xw
+
+    _point_times = staticmethod(TNeRFRadianceField._point_times)
+
+    # ---------------------------------------------------------------- the composed chain
+
+    def _time_features(self, t: Tensor, t_enc: Tensor) -> Tensor:
+        """``[n, 6, 64]`` of ``dtype``: row ``2 i + s`` is ``time_layers_{s+1}[i](t_enc)``, FusedMLP's layer arithmetic without an
+        activation (half operands, a float32 sum that starts from the bias, one rounding)."""
+        if t.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("NDRTNeRFRadianceField: no gradient towards the times is implemented")
+        ts = self._time_tensors()
+        if t.is_cuda and t.dtype == torch.float32:
+            with torch.autocast("cuda", enabled=False):
+                return _NdrTimeFn.apply(t.contiguous(), t_enc, self, *ts)
+        x = t_enc.to(self.dtype).float()
+        return torch.stack([(x @ w.to(self.dtype).float().t() + b.float()).to(self.dtype) for w, b in zip(ts[0::2], ts[1::2])], 1)
+
+    def _block(self, x: Tensor, feat: Tensor, i: int) -> Tensor:
+        uv, w = x[:, :2], x[:, 2:]
+        w = w + self.warp_layers_1[i](torch.cat([self.posi_encoder_1(uv), feat[:, 2 * i]], -1))
+        rt = self.warp_layers_2[i](torch.cat([self.posi_encoder_2(w), feat[:, 2 * i + 1]], -1))
+        sc = self._rot_encoder(rt[:, :1])
+        s, c = sc[:, :1], sc[:, 1:]
+        d = uv - rt[:, 1:]
+        du, dv = d[:, :1], d[:, 1:]
+        return torch.cat([c * du + s * dv, c * dv - s * du, w], -1)
+
+    # ---------------------------------------------------------------- the reference's methods
+
+    def warp(self, x: Tensor, t: Tensor) -> Tensor:
+        """The warped positions, float32, in ``x``'s shape (``t``: ``x``'s shape with a last dimension of 1)."""
+        if self._point_times(x, t) and self._use_fused(False, x, t):
+            return self._launch("warp", x.numel() // 3, positions=x.reshape(-1, 3), times=t.reshape(-1))[2].view(x.shape)
+        if not self._point_times(x, t):
+            raise ValueError(f"NDRTNeRFRadianceField: t must be {(*x.shape[:-1], 1)} for x {tuple(x.shape)} (got {tuple(t.shape)})")
+        p, t1 = x.reshape(-1, 3), t.reshape(-1)
+        feat = self._time_features(t1, self.time_encoder(t1.view(-1, 1)))
+        p = self._block(p, feat, 0)[:, [1, 2, 0]]
+        p = self._block(p, feat, 1)[:, [2, 0, 1]]
+        return self._block(p, feat, 2).view(x.shape)
+
+    def query_density(self, x: Tensor, t: Tensor) -> Tensor:
+        if self._point_times(x, t) and self._use_fused(False, x, t):
+            sigma = self._launch("density", x.numel() // 3, True, positions=x.reshape(-1, 3), times=t.reshape(-1))[1]
+            return sigma.view(*x.shape[:-1], 1)
+        return self.nerf.query_density(self.warp(x, t))
+
+    def query_opacity(self, x: Tensor, timestamps: Tensor, step_size) -> Tensor:
+        idxs = torch.randint(0, len(timestamps), (x.shape[0],), device=x.device)
+        return self.query_density(x, timestamps[idxs]) * step_size   # (small densities: 1 - exp(-density * step_size) is the same)
+
+    def forward(self, x: Tensor, t: Tensor, condition: Optional[Tensor] = None):
+        if condition is not None and condition.shape == x.shape and self._point_times(x, t) and self._use_fused(True, x, t, condition):
+            rgb, sigma, _ = self._launch("full", x.numel() // 3, True, positions=x.reshape(-1, 3), times=t.reshape(-1),
+                                         dirs=condition.reshape(-1, 3))
+            return rgb.view(*x.shape[:-1], 3), sigma.view(*x.shape[:-1], 1)
+        return self.nerf(self.warp(x, t), condition=condition)
+
+    # ---------------------------------------------------------------- the methods in the other fields' shape
+
+    def query_raw(self, positions: Tensor, t: Tensor, directions: Tensor):
+        """``(raw_rgbs [..., 3], raw_sigmas [...])`` at world positions and times ``[..., 1]``, before any activation."""
+        if positions.shape == directions.shape and self._point_times(positions, t) and self._use_fused(True, positions, t, directions):
+            rgb, sigma, _ = self._launch("full", positions.numel() // 3, False, positions=positions.reshape(-1, 3), times=t.reshape(-1),
+                                         dirs=directions.reshape(-1, 3))
+            return rgb.view(*positions.shape[:-1], 3), sigma.view(positions.shape[:-1])
+        return self.nerf.query_raw(self.warp(positions, t), directions)
+
+    def density_on_rays(self, rays_o: Tensor, rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor,
+                        timestamps: Tensor) -> Tensor:
+        """Densities ``[n]`` at the midpoints of packed ray samples, each at its ray's time (``timestamps`` ``[n_rays, 1]``): a
+        trainer's ``sigma_fn``."""
+        if timestamps.numel() == rays_o.shape[0] and self._use_fused(False, rays_o, rays_d, t_starts, t_ends, timestamps, ray_indices):
+            return self._launch("density", t_starts.numel(), True, rays=(rays_o, rays_d, t_starts, t_ends, ray_indices),
+                                times=timestamps.reshape(-1))[1]
+        s = sample_positions(rays_o, rays_d, t_starts, t_ends, ray_indices)
+        return self.query_density(s.positions, timestamps.reshape(-1, 1)[ray_indices]).squeeze(-1)
+
+    def query_on_rays(self, rays_o: Tensor, rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, timestamps: Tensor,
+                      raw: bool = True):
+        """The field at the midpoints of packed ray samples, each at its ray's time.  ``raw=True``: ``(raw_rgbs [n, 3],
+        raw_sigmas [n])``, what :func:`nerfacc_amd.rendering_from_raw` takes; otherwise ``(rgbs [n, 3], sigmas [n])`` activated."""
+        if timestamps.numel() == rays_o.shape[0] and self._use_fused(True, rays_o, rays_d, t_starts, t_ends, timestamps, ray_indices):
+            return self._launch("full", t_starts.numel(), not raw, rays=(rays_o, rays_d, t_starts, t_ends, ray_indices),
+                                times=timestamps.reshape(-1))[:2]
+        s = sample_positions(rays_o, rays_d, t_starts, t_ends, ray_indices, dirs="raw")
+        t = timestamps.reshape(-1, 1)[ray_indices]
+        if raw:
+            return self.query_raw(s.positions, t, s.dirs)
+        rgb, sigma = self.forward(s.positions, t, s.dirs)
+        return rgb, sigma.squeeze(-1)
+
+    def load_reference_state_dict(self, sd: dict) -> None:
+        """Takes the reference module's state dict: ``warp_layers_{1,2}.N.hidden_layers.M.*`` and ``.output_layer.*`` (through
+        :meth:`FusedMLP.load_reference_state_dict`), ``time_layers_{1,2}.N.output_layer.*``, ``nerf.*`` (through
+        :meth:`VanillaNeRFRadianceField.load_reference_state_dict`) and the three encoders' ``scales`` buffers, which must be the
+        reference's ``2^k``.  Any other key, a missing key and a wrong shape raise ``ValueError``."""
+        who = "NDRTNeRFRadianceField: load_reference_state_dict"
+        sd = dict(sd)
+        for name in ("time_encoder", "posi_encoder_1", "posi_encoder_2"):
+            enc, scales = getattr(self, name), sd.pop(name + ".scales", None)
+            if scales is not None:
+                want = torch.tensor([2.0 ** k for k in range(enc.min_deg, enc.max_deg)], dtype=torch.float64)
+                if scales.numel() != want.numel() or not torch.equal(scales.detach().cpu().double().reshape(-1), want):
+                    raise ValueError(f"{who}: '{name}.scales' is not 2^k for k in {enc.min_deg} .. {enc.max_deg - 1}")
+        groups = {f"{g}.{i}.": m for g in ("warp_layers_1", "warp_layers_2", "time_layers_1", "time_layers_2")
+                  for i, m in enumerate(getattr(self, g))}
+        groups["nerf."] = self.nerf
+        other = sorted(k for k in sd if not k.startswith(tuple(groups)))
+        if other:
+            raise ValueError(f"{who}: unexpected keys {other}")
+        for prefix, m in groups.items():
+            part = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+            if not prefix.startswith("time_layers"):
+                m.load_reference_state_dict(part)
+                continue
+            want = {"output_layer.weight": m.weight, "output_layer.bias": m.bias}
+            if set(part) != set(want):
+                raise ValueError(f"{who}: '{prefix}': missing keys {sorted(set(want) - set(part))}, unexpected keys {sorted(set(part) - set(want))}")
+            for k, dst in want.items():
+                if tuple(part[k].shape) != tuple(dst.shape):
+                    raise ValueError(f"{who}: '{prefix}{k}' is {tuple(part[k].shape)}, expected {tuple(dst.shape)}")
+            with torch.no_grad():
+                for k, dst in want.items():
+                    dst.copy_(part[k])
